@@ -18,6 +18,13 @@ rendezvous on 127.0.0.1) when it was not already started by a launcher; the batc
 ranks, rank 0 builds the device-form key and broadcasts it once over RCCL; there is no
 collective in the timed region ("scaling": "weak").
 
+A plain run sets up, warms up, times `--steps` steps and prints the line (headline, `ms_per_step`
+and the roofline of the timed steps).  `--full` adds the legs that take runs of their own: one
+untimed step per kernel alone, the host-pointer leg (`host_io`), the rocprofv3 --pmc child passes
+(`roofline.traffic`) and the CPU baseline (`cpu_baseline`).  `--dump-outputs DIR` writes the
+output of the last timed step; the inputs and the key come from fixed seeds, so two builds run
+with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 
@@ -43,6 +50,8 @@ PEAK_HBM_GBS = 8000.0     # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MI
 NOMINAL_SCLK_HZ = 2.4e9   # "Max clock 2400 MHz", same guide (the clock under this workload is 2.1-2.3 GHz)
 W_BYTES = {"params1024": 16, "params512": 16, "params2048": 16, "params64": 8, "synth64": 8,
            "rns2": 16}
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: cap on the bytes written
+DUMP_SAMPLE_SEED = 2024    # --dump-outputs: rows kept when the whole output is over the cap
 
 
 def rns2_moduli(S, n=1024):
@@ -318,6 +327,23 @@ def cpu_baseline(p, sk, key_seed, cap, seconds_target=8.0, seconds_full=30.0):
     return res
 
 
+def dump_outputs(directory, out, r):
+    """--dump-outputs: the device-resident result [batch][3][n+1] of the last timed step as
+    DIR/bootstrap_out.npy.  The words are residues mod r, exact in float32 up to r = 2^24.  A
+    result over DUMP_MAX_BYTES is reduced to a fixed, seeded sample of rows (same arguments, same
+    rows), kept in increasing order."""
+    import torch
+    dtype = np.float32 if r <= 1 << 24 else np.float64
+    row_bytes = out[0].numel() * np.dtype(dtype).itemsize
+    rows = out.shape[0]
+    if rows * row_bytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, DUMP_MAX_BYTES // row_bytes,
+                                                                       replace=False))
+        out = out.index_select(0, torch.from_numpy(keep).to(out.device))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "bootstrap_out.npy"), out.cpu().numpy().astype(dtype))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -405,7 +431,21 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal without a GPU: the ranks rendezvous over gloo, take the "
                          "MAX of a dummy timing and rank 0 prints a stub line (tests/)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline does not need: the untimed step of each kernel "
+                         "alone, the host-pointer leg, the rocprofv3 --pmc child passes and the CPU "
+                         "baseline (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write rank 0's output of the last step as "
+                         "DIR/bootstrap_out.npy ([rows][3][n+1], AND / OR / XOR, a then b; float32 when "
+                         "r <= 2^24, else float64): every row when that fits in %d MB, else a fixed, "
+                         "seeded sample of rows in increasing order" % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run sets up, warms up, times the steps and prints the line: nothing else
+        args.no_isolated = args.no_host_io = args.no_live_counters = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         self_launch(args)          # does not return
@@ -496,6 +536,9 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    # (before the --full legs: they run more steps into `out`)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, p.r)
 
     tm = eng.timing_read(reset=True)
     lanes = 2 if (args.lanes or 2) == 2 and B > (tm["chunk"] or B) else 1

@@ -26,7 +26,7 @@ def _run(*extra):
 
 
 def test_bench_line_contract():
-    d = _run("--chunk", "64")                       # four chunks: two lanes, as at the default workload
+    d = _run("--full", "--chunk", "64")             # four chunks: two lanes, as at the default workload
     assert d["metric"] == "bootstraps/sec" and d["unit"] == "bootstraps/sec"
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -95,7 +95,7 @@ def test_host_buffers_run_at_the_device_resident_rate():
     tools/io_variants.py (profiles/r04_exp_io_variants.txt): three steps here cannot resolve 0.3 %."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-isolated", "--no-live-counters"], env=env, capture_output=True,
+                        "--full", "--no-cpu-baseline", "--no-isolated", "--no-live-counters"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -111,7 +111,7 @@ def test_host_buffers_run_at_the_device_resident_rate():
 
 
 def test_bench_flags():
-    d = _run("--no-cpu-baseline", "--no-host-io", "--flatten", "random", "--lanes", "1", "--chunk", "64")
+    d = _run("--full", "--no-cpu-baseline", "--no-host-io", "--flatten", "random", "--lanes", "1", "--chunk", "64")
     assert d["roofline"]["traffic"] is None and "counters" in d["roofline"]["traffic_note"]
     assert "cpu_baseline" not in d and "host_io" not in d
     assert "random flatten" in d["config"]["workload"] and d["value"] > 0
@@ -121,3 +121,22 @@ def test_bench_flags():
     assert k["k_extprod"]["launch_ms_alone"] == k["k_extprod"]["launch_ms"]
     # the CRT kernel is reported under the name the engine launches in this mode
     assert "k_crt_lean" not in k and k["k_crt_lean_rnd"]["name"] == "k_crt_lean_rnd<4, 3, false>"
+
+
+def test_plain_run_is_lean_and_dumps_the_same_outputs(tmp_path):
+    """Without --full the line holds the headline and the roofline of the timed steps only, and
+    --dump-outputs writes the last timed step's result: the words mod r, the same in two runs with
+    the same arguments (inputs and key from fixed seeds)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = _run("--dump-outputs", str(tmp_path / str(i)))
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert d["metric"] == "bootstraps/sec" and d["dtype"] == "i32" and d["higher_is_better"] is True
+        assert "cpu_baseline" not in d and "host_io" not in d and d["roofline"]["traffic"] is None
+        dumps.append(np.load(str(tmp_path / str(i) / "bootstrap_out.npy")))
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape == (256, 3, 65)
+    assert a.min() >= 0 and a.max() < 16 * 64 and np.array_equal(a, np.round(a)) and a.any()
+    assert np.array_equal(a, dumps[1])

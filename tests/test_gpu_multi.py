@@ -238,7 +238,7 @@ def test_bench_ranks_rehearsal_on_one_gpu(ranks):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["SGFHE_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--config",
-                        "params64", "--batch", "512", "--steps", "2", "--warmup", "1"],
+                        "params64", "--batch", "512", "--steps", "2", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -283,7 +283,7 @@ def test_bench_under_torchrun_with_rccl_one_rank():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                         os.path.join(root, "bench.py"), "--gpus", "1", "--config", "params512", "--batch",
-                        "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+                        "64", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@
 TAG=${1:-rXX}
 O=gpurun_out
 mkdir -p $O
-run() { name=$1; shift; python bench.py "$@" > $O/bench_${TAG}_$name.json 2> $O/bench_${TAG}_$name.err; echo "$name done"; }
+run() { name=$1; shift; python bench.py --full "$@" > $O/bench_${TAG}_$name.json 2> $O/bench_${TAG}_$name.err; echo "$name done"; }
 run params1024 --steps 20 --warmup 2
 run params1024_b8192 --batch 8192 --steps 3 --warmup 1 --no-cpu-baseline          # config 5's per-GPU shard
 run params1024_one_lane --lanes 1 --steps 3 --warmup 1 --no-cpu-baseline --no-host-io

@@ -265,7 +265,8 @@ int32_t sgfhe_bootstrap_batch_device(sgfhe_ctx *ctx, const uint64_t *a1, const u
                                      uint64_t *out, uint32_t flags, void *stream);
 int32_t sgfhe_sync(sgfhe_ctx *ctx);
 /* Frees the staging buffers sgfhe_bootstrap_batch keeps on the ctx (device and page-locked host
- * memory, sized by the largest batch seen); the next call allocates them again. */
+ * memory, sized by the largest batch seen), and the wire table and call staging of sgfhe_circuit_run;
+ * the next call allocates them again. */
 int32_t sgfhe_release_host_staging(sgfhe_ctx *ctx);
 
 /*
@@ -390,6 +391,54 @@ int32_t sgfhe_host_pack_public(const sgfhe_params *p, const uint64_t *a, const u
 /* normalize_ciphertext(::PublicEncryptedCiphertext) (src/fhe.jl:444-449). */
 int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits, const uint8_t *b_bits,
                                     uint64_t *a, uint64_t *b);
+
+/*
+ * Gate circuits, evaluated on the device level by level over many independent instances.
+ *
+ * Model.  A circuit has `n_inputs` input wires and `n_gates` nodes; every node is one
+ * bootstrap(bkey, rng, x, y) (src/fhe.jl:608-621), which yields AND, OR and XOR together.  Wire ids:
+ * inputs 0 .. n_inputs - 1; node g produces n_inputs + 3 g + 0 (AND), + 1 (OR), + 2 (XOR).  A wire
+ * REFERENCE is a uint32: the wire id, plus SGFHE_CIRCUIT_NOT (bit 31) for its negation; the id
+ * SGFHE_CIRCUIT_FALSE is the constant FALSE (the trivial LWE (0, 0)), so FALSE | NOT is TRUE.
+ * NOT w = enc_trivial(true) - w with the reference's LWE subtraction (src/fhe.jl:221-223, enc_trivial
+ * :669-670): a -> -a mod r, b -> (Dr - b) mod r, Dr = r / 4 -- so NAND, NOR, XNOR, ANDNOT ... cost their
+ * one bootstrap and nothing more.  A node's two inputs (gates[g][0], gates[g][1]) name an input wire, the
+ * constant or a wire of an EARLIER node: array order is a topological order.  `outputs` lists wire
+ * references; they may name inputs, the constant and negated wires.
+ *
+ * Plan (sgfhe_circuit_create, host only; one plan serves every ctx and clone).  Validation: ids in range,
+ * the rule above, n_outputs >= 1, n_inputs, n_gates, n_outputs and n_inputs + 3 n_gates below 2^31 - 1;
+ * anything else is SGFHE_ERR_INVALID_ARG, an allocation failure SGFHE_ERR_OOM (*out is then NULL).  Nodes
+ * no output depends on are dropped; the others get level = 1 + the largest level of their input nodes
+ * (inputs and the constant are level 0).  Every wire something reads gets a slot of a device wire table
+ * ([slot][instance][n + 1] words); a slot is reused only after the last level that reads its wire, output
+ * wires stay to the end.
+ * info[0] levels, [1] nodes evaluated per instance, [2] widest level (nodes), [3] wire slots.
+ *
+ * Run (sgfhe_circuit_run): in [n_inputs][instances][n + 1], out [n_outputs][instances][n + 1], uint64 in
+ * [0, r), a then b (the layout of one gate of sgfhe_bootstrap_batch's output).  Host pointers; synchronous.
+ * `in` may be NULL when n_inputs is 0.  instances = 0 does nothing.  The ctx is locked for the whole run and
+ * the coalescer is not used.  Row and call numbering -- the contract of the randomised flatten: within a
+ * level the nodes are taken in ascending index, row = rank_in_level * instances + instance; a level's rows
+ * go to the device in calls of at most SGFHE_CIRCUIT_CALL_ROWS rows, in order, levels in order; every call
+ * takes the next call number of the ctx's draw stream (as an sgfhe_bootstrap_batch call does) and a row
+ * draws as the bootstrap at its index within its call.  Each call is a gather kernel (the call's inputs from
+ * the wire table, NOT and the constant applied), the k-loop of sgfhe_bootstrap_batch_device, and a scatter
+ * kernel (the outputs something reads into their slots); no host synchronisation between levels.  The wire
+ * table and the per-call staging are kept on the ctx, grown on demand, and freed by
+ * sgfhe_release_host_staging and sgfhe_ctx_destroy.  SGFHE_ERR_NO_KEY before a key is uploaded (nothing is
+ * written to `out`).
+ */
+typedef struct sgfhe_circuit sgfhe_circuit;
+#define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
+#define SGFHE_CIRCUIT_NOT 0x80000000u
+#define SGFHE_CIRCUIT_CALL_ROWS 8192u
+int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates /* [n_gates][2] */, size_t n_gates,
+                             const uint32_t *outputs, size_t n_outputs, sgfhe_circuit **out);
+int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
+int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
+int32_t sgfhe_circuit_run(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
+                          uint64_t *out);
 
 /*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled

@@ -139,6 +139,10 @@ def lib():
         "sgfhe_timing_read": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
         "sgfhe_kernel_names": (i32, [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz]),
         "sgfhe_release_host_staging": (i32, [vp]),
+        "sgfhe_circuit_create": (i32, [u32, vp, sz, vp, sz, ctypes.POINTER(vp)]),
+        "sgfhe_circuit_info": (i32, [vp, _u64p]),
+        "sgfhe_circuit_destroy": (i32, [vp]),
+        "sgfhe_circuit_run": (i32, [vp, vp, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -161,4 +165,5 @@ EXPORTED_SYMBOLS = (
     "sgfhe_host_pack_private", "sgfhe_host_normalize_private", "sgfhe_host_split_ciphertext",
     "sgfhe_host_decrypt_lwe", "sgfhe_host_decrypt_rlwe", "sgfhe_host_public_key",
     "sgfhe_host_encrypt_public", "sgfhe_host_pack_public", "sgfhe_host_normalize_public", "sgfhe_timing_enable", "sgfhe_timing_read",
-    "sgfhe_kernel_names", "sgfhe_release_host_staging")
+    "sgfhe_kernel_names", "sgfhe_release_host_staging", "sgfhe_circuit_create", "sgfhe_circuit_info",
+    "sgfhe_circuit_destroy", "sgfhe_circuit_run")

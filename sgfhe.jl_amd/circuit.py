@@ -1,0 +1,245 @@
+"""Gate circuits evaluated on the device level by level over many independent instances
+(sgfhe_circuit_* of include/sgfhe_hip.h).
+
+A circuit is a list of nodes; every node is one bootstrap(bkey, rng, x, y) (src/fhe.jl:608-621) and
+yields AND, OR and XOR together.  NOT is linear (enc_trivial(true) - w, src/fhe.jl:221-223,669-670), so
+NAND, NOR, XNOR, ANDNOT ... cost their one bootstrap.  Running one circuit over many instances makes
+every level a wide batch: the throughput form of the engine.
+
+    c = Circuit(2)
+    x, y = c.inputs
+    and_, or_, xor_ = c.gate(x, y)
+    c.output(~and_, xor_)                         # NAND, XOR
+    outs = evaluate_circuit(bkey, None, c, [[e_x0, e_x1], [e_y0, e_y1]])   # 2 instances
+"""
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .scheme import LWE, EncryptedBit, _set_flatten_mode
+
+FALSE_ID = 0x7FFFFFFF      # SGFHE_CIRCUIT_FALSE
+NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
+CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
+
+
+class Wire:
+    """A wire reference: the wire id, plus bit 31 for its negation (`~w`)."""
+
+    __slots__ = ("ref",)
+
+    def __init__(self, ref):
+        self.ref = int(ref) & 0xFFFFFFFF
+
+    def __invert__(self):
+        return Wire(self.ref ^ NOT_BIT)
+
+    @property
+    def id(self):
+        return self.ref & ~NOT_BIT & 0xFFFFFFFF
+
+    @property
+    def negated(self):
+        return bool(self.ref & NOT_BIT)
+
+    def __eq__(self, other):
+        return isinstance(other, Wire) and other.ref == self.ref
+
+    def __hash__(self):
+        return hash(self.ref)
+
+    def __repr__(self):
+        return "%sWire(%s)" % ("~" if self.negated else "", "FALSE" if self.id == FALSE_ID else self.id)
+
+
+class Circuit:
+    """Builder of a gate circuit: `n_inputs` input wires, nodes added with gate(), outputs set with
+    output().  The C plan (sgfhe_circuit_create) is made on first use and freed with the object."""
+
+    FALSE = Wire(FALSE_ID)
+    TRUE = Wire(FALSE_ID | NOT_BIT)
+
+    def __init__(self, n_inputs):
+        if not 0 <= int(n_inputs) < FALSE_ID:
+            raise ValueError("n_inputs out of range")
+        self.n_inputs = int(n_inputs)
+        self.inputs = [Wire(i) for i in range(self.n_inputs)]
+        self.gates = []            # [(x ref, y ref)]
+        self.outputs = []          # [ref]
+        self._plan = None
+        self._L = None
+
+    def _ref(self, w):
+        if not isinstance(w, Wire):
+            raise TypeError("expected a Wire, got %r" % (w,))
+        return w.ref
+
+    def gate(self, x, y):
+        """One node: bootstrap(x, y).  Returns its (AND, OR, XOR) wires."""
+        self.gates.append((self._ref(x), self._ref(y)))
+        self._invalidate()
+        base = self.n_inputs + 3 * (len(self.gates) - 1)
+        return Wire(base), Wire(base + 1), Wire(base + 2)
+
+    def output(self, *wires):
+        """Set the circuit's outputs (wire references: inputs, constants and negated wires allowed)."""
+        self.outputs = [self._ref(w) for w in wires]
+        self._invalidate()
+
+    @property
+    def n_gates(self):
+        return len(self.gates)
+
+    @property
+    def n_outputs(self):
+        return len(self.outputs)
+
+    # ---- the C plan -----------------------------------------------------------------------------
+    def _invalidate(self):
+        if self._plan is not None:
+            self._L.sgfhe_circuit_destroy(self._plan)
+            self._plan = None
+
+    def handle(self):
+        """The sgfhe_circuit* of this circuit (created on first use)."""
+        if self._plan is None:
+            from .engine import SgfheError
+            L = _lib.lib()
+            g = np.ascontiguousarray(np.array(self.gates, dtype=np.uint32).reshape(-1, 2))
+            o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
+            h = ctypes.c_void_p()
+            rc = L.sgfhe_circuit_create(self.n_inputs, g.ctypes.data_as(ctypes.c_void_p), len(self.gates),
+                                        o.ctypes.data_as(ctypes.c_void_p), len(self.outputs), ctypes.byref(h))
+            if rc != 0:
+                raise SgfheError(rc, "sgfhe_circuit_create: %s" % (
+                    "malformed circuit (ids, topological order, at least one output)" if rc == -1 else "out of memory"))
+            self._L, self._plan = L, h
+        return self._plan
+
+    def info(self):
+        """dict(levels, nodes (evaluated per instance), widest (nodes in the widest level), slots)."""
+        info = (ctypes.c_uint64 * 4)()
+        h = self.handle()
+        rc = self._L.sgfhe_circuit_info(h, info)
+        assert rc == 0
+        return dict(levels=int(info[0]), nodes=int(info[1]), widest=int(info[2]), slots=int(info[3]))
+
+    def __del__(self):
+        try:
+            self._invalidate()
+        except Exception:
+            pass
+
+    # ---- host statements of the model -------------------------------------------------------------
+    def schedule(self):
+        """The levels the planner runs: a list (level 1, 2, ...) of lists of node indices in ascending
+        order, after pruning the nodes no output depends on (the C planner's rule, in Python)."""
+        def node(ref):   # producing node of a wire, -1 for inputs and the constant
+            i = ref & ~NOT_BIT & 0xFFFFFFFF
+            return -1 if i == FALSE_ID or i < self.n_inputs else (i - self.n_inputs) // 3
+
+        live = [False] * len(self.gates)
+        for ref in self.outputs:
+            if node(ref) >= 0:
+                live[node(ref)] = True
+        for g in range(len(self.gates) - 1, -1, -1):
+            if live[g]:
+                for ref in self.gates[g]:
+                    if node(ref) >= 0:
+                        live[node(ref)] = True
+        level = [0] * len(self.gates)
+        for g, (x, y) in enumerate(self.gates):
+            if live[g]:
+                level[g] = 1 + max(level[node(x)] if node(x) >= 0 else 0, level[node(y)] if node(y) >= 0 else 0)
+        levels = [[] for _ in range(max(level, default=0))]
+        for g in range(len(self.gates)):
+            if level[g]:
+                levels[level[g] - 1].append(g)
+        return levels
+
+    def evaluate_plain(self, bits):
+        """The circuit in clear: bits [n_inputs][instances] (bool) -> [n_outputs][instances] (bool)."""
+        bits = np.asarray(bits, dtype=bool).reshape(self.n_inputs, -1)
+        inst = bits.shape[1]
+        wires = {}
+
+        def val(ref):
+            i = ref & ~NOT_BIT & 0xFFFFFFFF
+            v = np.zeros(inst, dtype=bool) if i == FALSE_ID else (bits[i] if i < self.n_inputs else wires[i])
+            return ~v if ref & NOT_BIT else v
+
+        for levelnodes in self.schedule():
+            for g in levelnodes:
+                x, y = val(self.gates[g][0]), val(self.gates[g][1])
+                base = self.n_inputs + 3 * g
+                wires[base], wires[base + 1], wires[base + 2] = x & y, x | y, x ^ y
+        if not self.outputs:
+            raise ValueError("circuit has no outputs")
+        return np.stack([val(ref) for ref in self.outputs])
+
+
+def lwe_not(words, r):
+    """NOT of LWEs [..., n + 1] over Z_r: enc_trivial(true) - w (a -> -a, b -> Dr - b, mod r)."""
+    words = np.asarray(words, dtype=np.uint64)
+    t = np.zeros(words.shape[-1], dtype=np.uint64)
+    t[-1] = r // 4
+    return (t + np.uint64(r) - words) & np.uint64(r - 1)
+
+
+def replay_levels(circuit, inputs, r, boot):
+    """The circuit composed on the host from whole-level bootstrap calls, in the row and call order of
+    sgfhe_circuit_run: inputs [n_inputs][instances][n + 1] -> outputs [n_outputs][instances][n + 1].
+    `boot(call, a1, b1, a2, b2)` runs one call (rows of at most CALL_ROWS) and returns [rows][3][n + 1];
+    `call` counts the calls from 0.  A checking and measuring aid: the engine's circuit path does this on
+    the device (Engine.circuit_run)."""
+    inputs = np.asarray(inputs, dtype=np.uint64)
+    inst, row = inputs.shape[1], inputs.shape[2]
+    n = row - 1
+    wires = {}
+
+    def val(ref):
+        i = ref & ~NOT_BIT & 0xFFFFFFFF
+        v = np.zeros((inst, row), dtype=np.uint64) if i == FALSE_ID else \
+            (inputs[i] if i < circuit.n_inputs else wires[i])
+        return lwe_not(v, r) if ref & NOT_BIT else v
+
+    call = 0
+    for nodes in circuit.schedule():
+        x = np.concatenate([val(circuit.gates[g][0]) for g in nodes])    # row = rank * instances + instance
+        y = np.concatenate([val(circuit.gates[g][1]) for g in nodes])
+        res = np.zeros((len(x), 3, row), dtype=np.uint64)
+        for r0 in range(0, len(x), CALL_ROWS):
+            sl = slice(r0, r0 + CALL_ROWS)
+            res[sl] = boot(call, x[sl, :n], x[sl, n], y[sl, :n], y[sl, n])
+            call += 1
+        for k, g in enumerate(nodes):
+            for w in range(3):
+                wires[circuit.n_inputs + 3 * g + w] = res[k * inst:(k + 1) * inst, w]
+    return np.stack([val(ref) for ref in circuit.outputs]) if circuit.outputs else np.zeros((0, inst, row), np.uint64)
+
+
+def evaluate_circuit(bkey, rng, circuit, inputs):
+    """The circuit over many instances on the HIP engine.  rng = None: deterministic flatten; a numpy
+    Generator: randomised flatten (its ChaCha8 key drawn from `rng`, call counter from 0).
+    inputs: [n_inputs][instances] of EncryptedBit, or the array form [n_inputs][instances][n + 1] uint64.
+    Returns [n_outputs][instances] of EncryptedBit (the array form when given the array form)."""
+    n = bkey.params.n
+    as_bits = not isinstance(inputs, np.ndarray)
+    if as_bits:
+        arr = np.zeros((circuit.n_inputs, len(inputs[0]) if circuit.n_inputs else 0, n + 1), dtype=np.uint64)
+        for i, row in enumerate(inputs):
+            if len(row) != arr.shape[1]:
+                raise ValueError("ragged inputs: every input needs one EncryptedBit per instance")
+            for t, e in enumerate(row):
+                arr[i, t, :n] = e.lwe.a
+                arr[i, t, n] = e.lwe.b
+        inputs = arr
+    with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
+        _set_flatten_mode(bkey, rng)
+        out = bkey.engine.circuit_run(circuit, inputs)
+    if not as_bits:
+        return out
+    return [[EncryptedBit(LWE(out[o, t, :n], out[o, t, n])) for t in range(out.shape[1])]
+            for o in range(out.shape[0])]

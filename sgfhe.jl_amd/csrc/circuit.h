@@ -1,0 +1,180 @@
+// Host-side planner of sgfhe_circuit_* (include/sgfhe_hip.h): validates a gate
+// graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
+// slot of the device wire table by liveness, and fixes the row and call numbering of a run.  Plain C++,
+// no HIP: tests/native/circuit_plan_sanitized.cpp drives it under ASan / UBSan on the CPU.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <functional>
+#include <new>
+#include <queue>
+#include <vector>
+
+#include "../../include/sgfhe_hip.h"
+
+namespace sgfhe {
+
+// A wire id below 2^31 - 1 (0x7FFFFFFF is the constant FALSE), bit 31 = NOT.  Slot references in the
+// device tables use the same encoding with slot numbers in place of wire ids.
+constexpr uint32_t CIRC_FALSE = SGFHE_CIRCUIT_FALSE;
+constexpr uint32_t CIRC_NOT = SGFHE_CIRCUIT_NOT;
+constexpr uint32_t CIRC_NONE = 0xFFFFFFFFu;     // out_slot of a gate output nothing reads
+
+struct CircuitPlan {
+    uint32_t n_inputs = 0, n_gates = 0, n_outputs = 0;
+    uint32_t levels = 0, widest = 0, slots = 0;
+    std::vector<uint32_t> level;        // [n_gates]: level of every node, 0 = pruned
+    std::vector<uint32_t> order;        // live nodes, level by level, ascending index within a level
+    std::vector<uint32_t> level_start;  // [levels + 2]: level L's nodes are order[level_start[L] .. level_start[L + 1])
+                                        // (level 0 holds none: level_start[0] == level_start[1] == 0)
+    std::vector<uint32_t> input_slot;   // [n_inputs]: slot of every input wire, CIRC_NONE if nothing reads it
+    // Device tables, one entry per live node in `order`, uploaded once per run:
+    std::vector<uint32_t> in_ref;       // [live][2]: the node's inputs as slot references (CIRC_NOT, CIRC_FALSE)
+    std::vector<uint32_t> out_slot;     // [live][3]: slot of its AND / OR / XOR wire, CIRC_NONE if unread
+    std::vector<uint32_t> out_ref;      // [n_outputs]: the circuit's outputs as slot references
+
+    size_t live() const { return order.size(); }
+    // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
+    uint64_t level_rows(uint32_t L, uint64_t instances) const {
+        return (uint64_t)(level_start[L + 1] - level_start[L]) * instances;
+    }
+};
+
+namespace circuit_detail {
+inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
+}  // namespace circuit_detail
+
+// Builds `P` from the arrays of sgfhe_circuit_create.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
+// malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it.
+inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
+                            size_t n_outputs, CircuitPlan &P) noexcept {
+    using circuit_detail::wire_id;
+    // ---- validate: every size below 2^31, wire ids below the constant, inputs name earlier wires only
+    if (n_outputs < 1 || !outputs || (n_gates && !gates)) return SGFHE_ERR_INVALID_ARG;
+    if (n_inputs >= 0x80000000u || n_gates >= 0x80000000u || n_outputs >= 0x80000000u) return SGFHE_ERR_INVALID_ARG;
+    const uint64_t n_wires = (uint64_t)n_inputs + 3 * (uint64_t)n_gates;
+    if (n_wires >= CIRC_FALSE) return SGFHE_ERR_INVALID_ARG;
+    for (size_t g = 0; g < n_gates; g++)
+        for (int j = 0; j < 2; j++) {
+            const uint32_t id = wire_id(gates[2 * g + j]);
+            if (id == CIRC_FALSE || id < n_inputs) continue;
+            if (id >= n_wires || (id - n_inputs) / 3 >= g) return SGFHE_ERR_INVALID_ARG;   // own or later node
+        }
+    for (size_t o = 0; o < n_outputs; o++) {
+        const uint32_t id = wire_id(outputs[o]);
+        if (id != CIRC_FALSE && id >= n_wires) return SGFHE_ERR_INVALID_ARG;
+    }
+    try {
+        P = CircuitPlan();
+        P.n_inputs = n_inputs;
+        P.n_gates = (uint32_t)n_gates;
+        P.n_outputs = (uint32_t)n_outputs;
+        const uint32_t NG = (uint32_t)n_gates;
+        auto node_of = [&](uint32_t id) -> int64_t {   // producing node of a wire, -1 for inputs and the constant
+            return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
+        };
+        // ---- prune: a node is live when an output reaches it (walk back from the outputs, last node first)
+        std::vector<uint8_t> live(NG, 0);
+        for (size_t o = 0; o < n_outputs; o++) {
+            const int64_t g = node_of(wire_id(outputs[o]));
+            if (g >= 0) live[g] = 1;
+        }
+        for (uint32_t g = NG; g-- > 0;) {
+            if (!live[g]) continue;
+            for (int j = 0; j < 2; j++) {
+                const int64_t h = node_of(wire_id(gates[2 * g + j]));
+                if (h >= 0) live[h] = 1;
+            }
+        }
+        // ---- level ASAP: 1 + the largest level of its input nodes (inputs and the constant: 0)
+        P.level.assign(NG, 0);
+        for (uint32_t g = 0; g < NG; g++) {
+            if (!live[g]) continue;
+            uint32_t L = 0;
+            for (int j = 0; j < 2; j++) {
+                const int64_t h = node_of(wire_id(gates[2 * g + j]));
+                if (h >= 0) L = std::max(L, P.level[h]);
+            }
+            P.level[g] = L + 1;
+            P.levels = std::max(P.levels, L + 1);
+        }
+        // ---- order: level by level, ascending node index within a level (counting sort)
+        P.level_start.assign((size_t)P.levels + 2, 0);
+        for (uint32_t g = 0; g < NG; g++)
+            if (P.level[g]) P.level_start[P.level[g] + 1]++;
+        for (uint32_t L = 1; L <= P.levels; L++) {
+            P.widest = std::max(P.widest, P.level_start[L + 1]);
+            P.level_start[L + 1] += P.level_start[L];
+        }
+        P.order.resize(P.level_start[P.levels + 1]);
+        {
+            std::vector<uint32_t> fill(P.level_start.begin(), P.level_start.end() - 1);
+            for (uint32_t g = 0; g < NG; g++)
+                if (P.level[g]) P.order[fill[P.level[g]]++] = g;
+        }
+        // ---- liveness: the last level that reads each wire (outputs: beyond the last level)
+        const uint32_t END = P.levels + 1;
+        constexpr uint32_t UNREAD = 0;   // no wire is read at level 0
+        std::vector<uint32_t> last_read((size_t)n_wires, UNREAD);
+        for (uint32_t g : P.order)
+            for (int j = 0; j < 2; j++) {
+                const uint32_t id = wire_id(gates[2 * g + j]);
+                if (id != CIRC_FALSE) last_read[id] = std::max(last_read[id], P.level[g]);
+            }
+        for (size_t o = 0; o < n_outputs; o++) {
+            const uint32_t id = wire_id(outputs[o]);
+            if (id != CIRC_FALSE) last_read[id] = END;
+        }
+        // ---- slots: a wire written at level L takes the lowest free slot; a slot is free again after the
+        // last level that reads its wire (so no call of level L overwrites what a later call of L gathers)
+        std::vector<uint32_t> slot_of((size_t)n_wires, CIRC_NONE);
+        std::vector<std::vector<uint32_t>> release((size_t)END + 1);   // slots freed after level L
+        std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> free_slots;
+        auto take = [&](uint32_t id) {
+            uint32_t s;
+            if (free_slots.empty()) s = P.slots++;
+            else { s = free_slots.top(); free_slots.pop(); }
+            slot_of[id] = s;
+            release[last_read[id]].push_back(s);
+        };
+        P.input_slot.assign(n_inputs, CIRC_NONE);
+        for (uint32_t i = 0; i < n_inputs; i++)
+            if (last_read[i] != UNREAD) { take(i); P.input_slot[i] = slot_of[i]; }
+        for (uint32_t L = 1; L <= P.levels; L++) {
+            for (uint32_t s : release[L - 1]) free_slots.push(s);
+            for (uint32_t k = P.level_start[L]; k < P.level_start[L + 1]; k++)
+                for (uint32_t w = 0; w < 3; w++) {
+                    const uint32_t id = n_inputs + 3 * P.order[k] + w;
+                    if (last_read[id] != UNREAD) take(id);
+                }
+        }
+        // ---- device tables
+        auto slot_ref = [&](uint32_t ref) -> uint32_t {
+            const uint32_t id = wire_id(ref);
+            return (id == CIRC_FALSE ? CIRC_FALSE : slot_of[id]) | (ref & CIRC_NOT);
+        };
+        P.in_ref.resize(2 * P.live());
+        P.out_slot.resize(3 * P.live());
+        for (size_t k = 0; k < P.live(); k++) {
+            const uint32_t g = P.order[k];
+            for (int j = 0; j < 2; j++) P.in_ref[2 * k + j] = slot_ref(gates[2 * g + j]);
+            for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
+        }
+        P.out_ref.resize(n_outputs);
+        for (size_t o = 0; o < n_outputs; o++) P.out_ref[o] = slot_ref(outputs[o]);
+    } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
+        P = CircuitPlan();
+        return SGFHE_ERR_OOM;
+    }
+    return SGFHE_OK;
+}
+
+}  // namespace sgfhe
+
+// The opaque handle of the C ABI: a plan is host data, independent of any ctx.
+struct sgfhe_circuit {
+    sgfhe::CircuitPlan plan;
+};

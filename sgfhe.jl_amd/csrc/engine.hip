@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "host_plumbing.h"
 #include "coalescer.h"
+#include "circuit.h"
 
 using namespace sgfhe;
 
@@ -221,6 +222,12 @@ struct sgfhe_ctx {
     size_t pin_in_words = 0, pin_out_words = 0;
     std::vector<uint64_t> co_buf;   // gathered inputs and results of a combined call this ctx leads (Coalescer)
     bool use_pin = true;   // SGFHE_HOST_PIN=0 in the environment: direct copies (A/B measurements)
+    // device buffers of sgfhe_circuit_run, grown on demand and kept like the I/O staging: the wire table
+    // [slot][instance][n + 1], one call's staging [a1 | a2 | b1 | b2 | result rows], the plan's node tables,
+    // and the collected outputs
+    uint64_t *circ_wires = nullptr, *circ_stage = nullptr, *circ_out = nullptr;
+    uint32_t *circ_tab = nullptr;
+    size_t circ_wires_words = 0, circ_stage_words = 0, circ_out_words = 0, circ_tab_words = 0;
     // timing
     bool timing = false;
     struct EvTriple { hipEvent_t e0, e1, e2; };  // ext = e0 -> e1, crt = e1 -> e2
@@ -1808,6 +1815,17 @@ int32_t sgfhe_ctx_clone(sgfhe_ctx *src, sgfhe_ctx **out) {
     return SGFHE_OK;
 }
 
+// the buffers of sgfhe_circuit_run (the caller has waited for the ctx's work)
+static void free_circuit_buffers(sgfhe_ctx *c) {
+    if (c->circ_wires) (void)hipFree(c->circ_wires);
+    if (c->circ_stage) (void)hipFree(c->circ_stage);
+    if (c->circ_out) (void)hipFree(c->circ_out);
+    if (c->circ_tab) (void)hipFree(c->circ_tab);
+    c->circ_wires = c->circ_stage = c->circ_out = nullptr;
+    c->circ_tab = nullptr;
+    c->circ_wires_words = c->circ_stage_words = c->circ_out_words = c->circ_tab_words = 0;
+}
+
 int32_t sgfhe_ctx_destroy(sgfhe_ctx *c) {
     if (!c) return SGFHE_OK;
     (void)hipSetDevice(c->device);
@@ -1831,6 +1849,7 @@ int32_t sgfhe_ctx_destroy(sgfhe_ctx *c) {
     if (c->io_out) (void)hipFree(c->io_out);
     if (c->pin_in) (void)hipHostFree(c->pin_in);
     if (c->pin_out) (void)hipHostFree(c->pin_out);
+    free_circuit_buffers(c);
     if (c->d_bad) (void)hipFree(c->d_bad);
     if (c->d_rows) (void)hipFree(c->d_rows);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2876,6 +2895,7 @@ int32_t sgfhe_release_host_staging(sgfhe_ctx *c) {
     if (c->pin_out) (void)hipHostFree(c->pin_out);
     c->io_in = c->io_out = c->pin_in = c->pin_out = nullptr;
     c->io_in_words = c->io_out_words = c->pin_in_words = c->pin_out_words = 0;
+    free_circuit_buffers(c);
     return SGFHE_OK;
 }
 
@@ -2907,6 +2927,143 @@ int32_t sgfhe_timing_read(sgfhe_ctx *c, double *stats, int reset) {
         c->n_ext = c->n_crt = c->n_call = c->boots_call = 0;
     }
     return SGFHE_OK;
+}
+
+// ---- gate circuits (csrc/circuit.h plans) ---------------------------------------
+
+int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
+                             size_t n_outputs, sgfhe_circuit **out) {
+    if (!out) return SGFHE_ERR_INVALID_ARG;
+    *out = nullptr;
+    sgfhe_circuit *c = new (std::nothrow) sgfhe_circuit();
+    if (!c) return SGFHE_ERR_OOM;
+    const int32_t rc = circuit_plan(n_inputs, gates, n_gates, outputs, n_outputs, c->plan);
+    if (rc) {
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return SGFHE_OK;
+}
+
+int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]) {
+    if (!c || !info) return SGFHE_ERR_INVALID_ARG;
+    info[0] = c->plan.levels;
+    info[1] = c->plan.live();
+    info[2] = c->plan.widest;
+    info[3] = c->plan.slots;
+    return SGFHE_OK;
+}
+
+int32_t sgfhe_circuit_destroy(sgfhe_circuit *c) {
+    delete c;
+    return SGFHE_OK;
+}
+
+// a device buffer of the ctx grown to at least `words` elements (its contents are not kept)
+extern "C++" template <typename T>
+static int32_t circ_grow(sgfhe_ctx *c, T *&buf, size_t &cap, size_t words) {
+    if (words <= cap) return SGFHE_OK;
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    if (hipMalloc(&buf, words * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run: hipMalloc of " + std::to_string(words * sizeof(T)) +
+                                          " bytes failed");
+    }
+    cap = words;
+    return SGFHE_OK;
+}
+
+static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in,
+                                  uint64_t *out) {
+    const size_t n = c->n, row = n + 1;
+    const uint32_t inst = (uint32_t)instances;
+    const uint64_t r = c->par.r;
+    hipStream_t st = c->stream;
+    uint64_t max_rows = 0;   // the largest call
+    for (uint32_t L = 1; L <= P.levels; L++) {
+        const uint64_t rows = P.level_rows(L, instances);
+        max_rows = std::max(max_rows, rows < SGFHE_CIRCUIT_CALL_ROWS ? rows : (uint64_t)SGFHE_CIRCUIT_CALL_ROWS);
+    }
+    // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller)
+    const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size();
+    int32_t rc;
+    if ((rc = circ_grow(c, c->circ_wires, c->circ_wires_words, (size_t)P.slots * instances * row))) return rc;
+    if ((rc = circ_grow(c, c->circ_stage, c->circ_stage_words, (size_t)max_rows * 5 * row))) return rc;
+    if ((rc = circ_grow(c, c->circ_out, c->circ_out_words, (size_t)P.n_outputs * instances * row))) return rc;
+    if ((rc = circ_grow(c, c->circ_tab, c->circ_tab_words, tab_words))) return rc;
+    if (max_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
+                      // then a no-op and never waits on the host between levels)
+        const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
+        if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(max_rows, chunk0))))) return rc;
+    }
+    uint32_t *d_in_ref = c->circ_tab, *d_out_slot = d_in_ref + P.in_ref.size(), *d_out_ref = d_out_slot + P.out_slot.size();
+    HIPCHK(c, hipMemcpyAsync(d_in_ref, P.in_ref.data(), P.in_ref.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_out_slot, P.out_slot.data(), P.out_slot.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_out_ref, P.out_ref.data(), P.out_ref.size() * 4, hipMemcpyHostToDevice, st));
+    // inputs straight into their slots; runs of consecutive inputs in consecutive slots as one copy
+    const size_t in_words = instances * row;
+    for (uint32_t i = 0; i < P.n_inputs;) {
+        if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
+        uint32_t k = i + 1;
+        while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
+        HIPCHK(c, hipMemcpyAsync(c->circ_wires + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
+                                 (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
+        i = k;
+    }
+    uint64_t *a1 = c->circ_stage, *a2 = a1 + max_rows * n, *b1 = a2 + max_rows * n, *b2 = b1 + max_rows,
+             *res = b2 + max_rows;
+    for (uint32_t L = 1; L <= P.levels; L++) {
+        const uint64_t rows_total = P.level_rows(L, instances);
+        const uint32_t k0 = P.level_start[L];
+        for (uint64_t row0 = 0; row0 < rows_total; row0 += SGFHE_CIRCUIT_CALL_ROWS) {
+            const uint32_t rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, rows_total - row0);
+            const uint32_t tg = rows * (uint32_t)row;
+            hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires,
+                               d_in_ref + 2 * (size_t)k0, a1, b1, a2, b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
+            HIPCHK(c, hipGetLastError());
+            // the k-loop of sgfhe_bootstrap_batch_device: the next call number of the ctx's draw stream
+            if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, 0u, c->n, nullptr, st))) return rc;
+            hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, res,
+                               d_out_slot + 3 * (size_t)k0, c->circ_wires, (uint32_t)row0, rows, inst, (uint32_t)n);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    const size_t total = (size_t)P.n_outputs * instances * row;
+    const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
+    hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires, d_out_ref, c->circ_out,
+                       total, inst, (uint32_t)n, r);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->circ_out, total * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->pending = false;
+    return SGFHE_OK;
+}
+
+int32_t sgfhe_circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                          uint64_t *out) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    if (!circ || !out || (!in && circ->plan.n_inputs))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: NULL circuit, input or output pointer");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    const CircuitPlan &P = circ->plan;
+    if (instances == 0) return SGFHE_OK;
+    // rows of a level, and words of every table, must be addressable by the kernels' indices
+    if (instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
+    (void)hipSetDevice(c->device);
+    int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
+    if (rc) return rc;
+    rc = circuit_run_queued(c, P, instances, in, out);
+    if (rc) {   // whatever was queued finishes before the buffers can be touched again
+        (void)hipStreamSynchronize(c->stream);
+        c->pending = false;
+    }
+    return rc;
 }
 
 }  // extern "C"

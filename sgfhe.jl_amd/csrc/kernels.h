@@ -1783,6 +1783,67 @@ k_final(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out,
     }
 }
 
+// ---- gate circuits (sgfhe_circuit_run, csrc/circuit.h) ---------------------------------------------
+// Memory-bound copies of rows of n + 1 uint64 words (a[0..n) then b) between the wire table
+// ([slot][instances][n + 1]) and the staging of one bootstrap call, one thread per word: consecutive
+// threads touch consecutive words of a row, so loads and stores are coalesced 8-byte accesses (rows
+// are not 16-byte aligned).  Row R of a level is node rank R / instances, instance R % instances.
+// A slot reference is a slot number, or CIRC_FALSE (the trivial LWE (0, 0)), plus CIRC_NOT:
+// NOT w = enc_trivial(true) - w (fhe.jl:221-223,669-670), a -> -a mod r, b -> (Dr - b) mod r.
+constexpr uint32_t CIRC_REF_FALSE = 0x7FFFFFFFu, CIRC_REF_NOT = 0x80000000u, CIRC_SLOT_NONE = 0xFFFFFFFFu;
+
+__device__ __forceinline__ uint64_t circ_word(const uint64_t *__restrict__ wires, uint32_t ref, size_t inst_row,
+                                              uint32_t e, uint32_t n, uint64_t r) {
+    // inst_row = slot * instances + instance (not read for the constant)
+    const uint64_t v = (ref & ~CIRC_REF_NOT) == CIRC_REF_FALSE ? 0ull : wires[inst_row * (n + 1) + e];
+    if (!(ref & CIRC_REF_NOT)) return v;
+    return ((e < n ? 0ull : r / 4) + r - v) & (r - 1);
+}
+
+// a1 / a2 [rows][n], b1 / b2 [rows] of one call: blockIdx.y selects the input (0: x, 1: y)
+__global__ void __launch_bounds__(256)
+k_circ_gather(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref, uint64_t *__restrict__ a1,
+              uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
+              uint32_t rows, uint32_t instances, uint32_t n, uint64_t r) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * (n + 1)) return;
+    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
+    const uint32_t rank = R / instances, inst = R % instances, j = blockIdx.y;
+    const uint32_t ref = in_ref[2 * rank + j];
+    const uint64_t v = circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    uint64_t *a = j ? a2 : a1, *b = j ? b2 : b1;
+    if (e < n) a[(size_t)lr * n + e] = v;
+    else b[lr] = v;
+}
+
+// bootstrap output [rows][3][n + 1] -> the slots of the gate outputs something reads
+__global__ void __launch_bounds__(256)
+k_circ_scatter(const uint64_t *__restrict__ res, const uint32_t *__restrict__ out_slot, uint64_t *__restrict__ wires,
+               uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t w3 = 3 * (n + 1);
+    if (t >= rows * w3) return;
+    const uint32_t lr = t / w3, rem = t % w3, g = rem / (n + 1), e = rem % (n + 1), R = row0 + lr;
+    const uint32_t rank = R / instances, inst = R % instances;
+    const uint32_t slot = out_slot[3 * rank + g];
+    if (slot == CIRC_SLOT_NONE) return;
+    wires[((size_t)slot * instances + inst) * (n + 1) + e] = res[t];
+}
+
+// the circuit's outputs [n_outputs][instances][n + 1], NOT and the constant applied (grid-stride: the
+// array may hold more than 2^32 words)
+__global__ void __launch_bounds__(256)
+k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref, uint64_t *__restrict__ out,
+               size_t total, uint32_t instances, uint32_t n, uint64_t r) {
+    const size_t per_out = (size_t)instances * (n + 1);
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t o = t / per_out, w = t % per_out;
+        const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
+        const uint32_t ref = out_ref[o];
+        out[t] = circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    }
+}
+
 // digits -> canonical accumulators (debug hook)
 __global__ void __launch_bounds__(256)
 k_dump_acc(const uint64_t *__restrict__ dig, ulonglong2 *__restrict__ out,

@@ -225,6 +225,17 @@ class Engine:
     def sync(self):
         self._call("sgfhe_sync")
 
+    def circuit_run(self, circuit, inputs):
+        """A gate circuit (circuit.Circuit) over many instances on the device (sgfhe_circuit_run):
+        inputs [n_inputs][instances][n+1] uint64 (a then b) -> outputs [n_outputs][instances][n+1]."""
+        n = self.params.n
+        a, ptr = _c(inputs)
+        if a.ndim != 3 or a.shape[0] != circuit.n_inputs or a.shape[2] != n + 1:
+            raise ValueError("circuit_run: inputs must be [n_inputs=%d][instances][n+1=%d]" % (circuit.n_inputs, n + 1))
+        out = np.zeros((circuit.n_outputs, a.shape[1], n + 1), dtype=np.uint64)
+        self._call("sgfhe_circuit_run", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p))
+        return out
+
     def pack_encrypted_bits(self, a, b):
         """pack_encrypted_bits (fhe.jl:660-696) for `count` groups of n LWEs: a [count][n][n],
         b [count][n] -> (w, v), each [count][m] uint64 over Z_r."""

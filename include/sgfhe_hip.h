@@ -455,7 +455,7 @@ int32_t sgfhe_timing_enable(sgfhe_ctx *ctx, int enable);
 int32_t sgfhe_timing_read(sgfhe_ctx *ctx, double *stats, int reset);
 /* Names of the two k-loop kernels this ctx launches in its present flatten mode, as they appear in
  * a rocprofv3 kernel trace ("k_extprod<13, 4, false>", "k_crt_lean<5, 3>"; parameter sets outside
- * k_crt_lean's bounds and SGFHE_CRT_LEAN=0 give k_crt_acc2 / k_crt_acc), NUL-terminated into the
+ * k_crt_lean's bounds give k_crt_acc2 / k_crt_acc), NUL-terminated into the
  * caller's buffers (64 bytes suffice). */
 int32_t sgfhe_kernel_names(const sgfhe_ctx *ctx, char *extprod, size_t extprod_cap, char *crt,
                            size_t crt_cap);

@@ -163,7 +163,6 @@ struct sgfhe_ctx {
     // the quarter form's two transform kernels as one launch (k_ext_quarter) from this many gates per chain, up to
     // what fills the device once (fused_cap below); SGFHE_SMALL_FUSED=0: never, =n: from n gates
     uint32_t fused_min = 7;
-    bool iter_all = false;     // -DSGFHE_WITH_ITER_ALL builds, SGFHE_ITER_ALL=1: one launch per iteration (prototype)
     uint32_t split_max = 7;   // calls of at most this many gates take the quarter form (SGFHE_SMALL_SPLIT, 0 = never):
                               // 1 / 2 / 4 / 6 / 8 gates 15.1 / 15.9 / 17.8 / 19.7 / 23.5 ms against 17.9 / 18.6 / 20.3 /
                               // 22.0 / 23.3 with one workgroup per transform (profiles/r04_exp_quarter.txt)
@@ -198,7 +197,6 @@ struct sgfhe_ctx {
         uint32_t *ua = nullptr;
         int32_t *zpart = nullptr;  // small-batch form only: [cap_small][npr][4][2][m]
     } lane[2];
-    bool use_lean = true;     // SGFHE_CRT_LEAN=0 in the environment: keep k_crt_acc2 (A/B measurements)
     bool small_padded = false;  // SGFHE_SMALL_PADDED=1: small-batch grids padded to 8 bootstraps as up to round 3 (A/B)
     bool small_lanes = true;    // SGFHE_SMALL_LANES=0: a call of a few gates as one chunk on one stream (A/B)
     uint32_t small_lanes_max = 24;   // ... up to this many gates (SGFHE_SMALL_LANES=<n>)
@@ -245,7 +243,7 @@ struct sgfhe_ctx {
     // per device; a ctx is bound to one device and used by one host thread)
     uint32_t attr_done = 0;
 };
-enum : uint32_t { ATTR_EXTPROD = 1u, ATTR_SMALL = 2u, ATTR_SHORTPROD = 4u, ATTR_FUSED = 8u, ATTR_ITER = 16u };
+enum : uint32_t { ATTR_EXTPROD = 1u, ATTR_SMALL = 2u, ATTR_SHORTPROD = 4u, ATTR_FUSED = 8u };
 // Page-locked mirrors of the host-pointer entry point's staging buffers: per buffer at most this much
 // (a batch of 16384 at Params(1024) needs 268 + 403 MB).  Round 3 staged whole buffers and stopped at
 // 48 MB, where one CPU memcpy cost what pinning the caller's pages did; the copies are now pipelined
@@ -348,7 +346,7 @@ int mode_basis(const sgfhe_ctx *c) { return c->rnd ? c->nb - 1 : 0; }
 // The quarter form of the latency kernels exists for m >= 4096 where the lean CRT kernel of the flatten mode does
 // (both modes; not the three-plane digit records of B >= 2^46, MODE_WIDE).
 bool quarter_ok(const sgfhe_ctx *c, uint32_t mode) {
-    return c->logm >= 12 && c->split_max && c->use_lean &&
+    return c->logm >= 12 && c->split_max &&
            (mode == 0u ? c->h_lean.nl != 0 : (mode == MODE_RANDOM && c->lean_rnd_ok));
 }
 // Largest chain the fused quarter kernel takes: one workgroup per (gate, prime, quarter), one round of the
@@ -362,10 +360,7 @@ bool fused_takes(const sgfhe_ctx *c, uint32_t cnt, uint32_t mode) { return cnt >
 
 size_t lds_bytes(int logm, int npoly) { return (size_t)npoly * ((size_t)4 << logm); }
 // points per thread of k_extprod: 16, or 8 where 16 would leave half a wavefront idle (m <= 512)
-#ifndef SGFHE_EXT_LE3_MAX
-#define SGFHE_EXT_LE3_MAX 9
-#endif
-template <int LOGM> constexpr int ext_loge() { return LOGM <= SGFHE_EXT_LE3_MAX ? 3 : LOGE; }
+template <int LOGM> constexpr int ext_loge() { return LOGM <= EXT_LE3_MAX ? 3 : LOGE; }
 template <int LOGM> constexpr int threads_of() { return NttGeom<LOGM, LOGE>::T; }
 
 // ---- per-LOGM dispatch ------------------------------------------------------------------------
@@ -403,23 +398,6 @@ int32_t launch_extprod(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *ke
     }
     return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
 }
-
-#ifdef SGFHE_WITH_ITER_ALL   // prototype, not in the default build (kernels.h)
-// One launch per iteration (kernels.h k_iter_all): deterministic flatten, m = 8192, five primes, lean CRT constants.
-int32_t launch_iter_all(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cnt, uint32_t k,
-                        hipStream_t st) {
-    constexpr int LM = 13;
-    const size_t lds = lds_bytes(LM, 2 + SGFHE_IA_LP);   // exchange buffer of the inverse pair + the private accumulator planes
-    if (!(c->attr_done & ATTR_ITER)) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_iter_all<LM, 5, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->attr_done |= ATTR_ITER;
-    }
-    hipLaunchKernelGGL((k_iter_all<LM, 5, 3>), dim3(cnt), dim3(NttGeom<LM, 3>::T), lds, st, L.dig, keyk, L.ua,
-                       c->d_primes, c->d_lean, k, c->n);
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
-}
-#endif
 
 template <int LOGM>
 int32_t launch_small_t(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cpad,
@@ -639,9 +617,9 @@ int32_t launch_crt_raw(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32
     // the k-loop's own case (deterministic flatten, accumulator present): the integer-only kernel,
     // four coefficients per thread; every other mode, and parameter sets outside its bounds
     // (B < 2^12, Q < 2^30), the general one
-    const bool lean = mode == 0u && c->h_lean.nl != 0 && c->use_lean;
+    const bool lean = mode == 0u && c->h_lean.nl != 0;
     // the same for the randomised flatten (the k-loop's modes MODE_RANDOM and MODE_RANDOM | MODE_WIDE)
-    const bool lean_rnd = (mode & ~MODE_WIDE) == MODE_RANDOM && c->lean_rnd_ok && c->use_lean;
+    const bool lean_rnd = (mode & ~MODE_WIDE) == MODE_RANDOM && c->lean_rnd_ok;
     switch (c->npr) {
 #define X(NP)                                                                                     \
     case NP:                                                                                      \
@@ -834,13 +812,6 @@ int32_t run_iterations(sgfhe_ctx *c, ChunkJob *jobs, int njobs, uint64_t n_iters
             // a few gates, deterministic flatten, m >= 4096: each transform cut across four workgroups
             // (both flatten modes; not the three-plane digit records of B >= 2^46, MODE_WIDE)
             const bool quarter = small && quarter_ok(c, mode) && (cnt <= c->split_max || fused_takes(c, cnt, mode));
-#ifdef SGFHE_WITH_ITER_ALL
-            if (!small && c->iter_all && mode == 0u && c->logm == 13 && c->npr == 5 && c->use_lean && c->h_lean.nl == 3) {
-                const int32_t rci = launch_iter_all(c, *J.L, c->d_key + k * slice, J.cpad, (uint32_t)k, J.st);
-                if (rci) return rci;
-                continue;
-            }
-#endif
             int32_t rc = quarter ? launch_quarter(c, *J.L, c->d_key + k * slice, cnt, (uint32_t)k, mode, J.st)
                          : small ? launch_small(c, *J.L, c->d_key + k * slice, cnt, (uint32_t)k, mode, J.st)
                                  : launch_extprod(c, *J.L, c->d_key + k * slice, J.cpad, (uint32_t)k, mode, J.st);
@@ -989,13 +960,19 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
     // before the first kernel, one download behind the last -- without the copy streams' events.
     const size_t stride = (size_t)chunk * (two_lanes ? 2 : 1);
     const bool hp_single = hp && batch <= stride;
+    // rows [c0, c0 + cb) of the caller's a1, a2, b1, b2 into the page-locked mirror, laid out
+    // [a1 | a2 | b1 | b2] from word c0 (2 n + 2); returns where they start
+    auto stage_in = [&](size_t c0, size_t cb) -> uint64_t * {
+        uint64_t *pi = hp->p_in + c0 * (2 * (size_t)n + 2);
+        host_copy(pi, hp->a1 + c0 * n, cb * n * 8);
+        host_copy(pi + cb * n, hp->a2 + c0 * n, cb * n * 8);
+        memcpy(pi + 2 * cb * n, hp->b1 + c0, cb * 8);
+        memcpy(pi + 2 * cb * n + cb, hp->b2 + c0, cb * 8);
+        return pi;
+    };
     if (hp_single) {
-        const size_t nn = n;
-        host_copy(hp->p_in, hp->a1, batch * nn * 8);
-        host_copy(hp->p_in + batch * nn, hp->a2, batch * nn * 8);
-        memcpy(hp->p_in + 2 * batch * nn, hp->b1, batch * 8);
-        memcpy(hp->p_in + 2 * batch * nn + batch, hp->b2, batch * 8);
-        HIPCHK(c, hipMemcpyAsync(hp->d_in, hp->p_in, batch * (2 * nn + 2) * 8, hipMemcpyHostToDevice, st));
+        stage_in(0, batch);
+        HIPCHK(c, hipMemcpyAsync(hp->d_in, hp->p_in, batch * (2 * (size_t)n + 2) * 8, hipMemcpyHostToDevice, st));
     }
     if (two_lanes) {  // fork: the second lane starts after everything already queued on st
         HIPCHK(c, hipEventRecord(c->ev_fork, st));
@@ -1028,27 +1005,12 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
     };
     // SGFHE_DEBUG_IO=1: wall-clock phases of a pipelined host-pointer call
     const bool dbg_io = hp && getenv("SGFHE_DEBUG_IO") != nullptr;
-    // SGFHE_IO_EXP: experiments of round 4 (tools/io_variants.py, profiles/r04_exp_io_variants.txt):
-    // 1 = results collected only at the end, 2 = all results after the last kernel, 4 = all inputs
-    // before the first kernel.  The default (0) measured best: 1.003 x the device-resident call.
-    const int io_exp = hp && getenv("SGFHE_IO_EXP") ? atoi(getenv("SGFHE_IO_EXP")) : 0;
+    // (Round 4 also measured collecting the results only at the end, all results after the last kernel,
+    // and all inputs before the first kernel; this pipeline measured best, 1.003 x the device-resident
+    // call: profiles/r04_exp_io_variants.txt.)
     auto wall = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double tw0 = dbg_io ? wall() : 0.0;
     double tw_first = 0.0, tw_wait = 0.0;
-    hipEvent_t e_allin = nullptr;
-    if ((io_exp & 4) && !hp_single) {   // experiment: every chunk's inputs up front, one event
-        for (size_t c0 = 0; c0 < batch; c0 += chunk) {
-            const size_t cb = batch - c0 < chunk ? batch - c0 : chunk, w0 = c0 * (2 * (size_t)n + 2);
-            uint64_t *pi = hp->p_in + w0;
-            host_copy(pi, hp->a1 + c0 * n, cb * n * 8);
-            host_copy(pi + cb * n, hp->a2 + c0 * n, cb * n * 8);
-            memcpy(pi + 2 * cb * n, hp->b1 + c0, cb * 8);
-            memcpy(pi + 2 * cb * n + cb, hp->b2 + c0, cb * 8);
-        }
-        HIPCHK(c, hipMemcpyAsync(hp->d_in, hp->p_in, batch * (2 * (size_t)n + 2) * 8, hipMemcpyHostToDevice, c->stream_io));
-        HIPCHK(c, next_event(&e_allin));
-        HIPCHK(c, hipEventRecord(e_allin, c->stream_io));
-    }
     for (size_t g0 = 0; g0 < batch; g0 += stride) {
         ChunkJob jobs[2];
         int njobs = 0;
@@ -1068,18 +1030,9 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
             if (hp_single) {   // whole-call layout [a1 | a2 | b1 | b2], uploaded above
                 ja1 = hp->d_in + c0 * n; ja2 = hp->d_in + (batch + c0) * n;
                 jb1 = hp->d_in + 2 * batch * n + c0; jb2 = jb1 + batch;
-            } else if (hp && e_allin) {
-                const size_t w0 = c0 * (2 * (size_t)n + 2), cb = J.cb;
-                uint64_t *di = hp->d_in + w0;
-                if (g0 == 0) HIPCHK(c, hipStreamWaitEvent(J.st, e_allin, 0));
-                ja1 = di; ja2 = di + cb * n; jb1 = di + 2 * cb * n; jb2 = jb1 + cb;
             } else if (hp) {   // this chunk's inputs: caller's arrays -> page-locked mirror -> device, on stream_io
-                const size_t w0 = c0 * (2 * (size_t)n + 2), cb = J.cb;
-                uint64_t *pi = hp->p_in + w0, *di = hp->d_in + w0;
-                host_copy(pi, hp->a1 + c0 * n, cb * n * 8);
-                host_copy(pi + cb * n, hp->a2 + c0 * n, cb * n * 8);
-                memcpy(pi + 2 * cb * n, hp->b1 + c0, cb * 8);
-                memcpy(pi + 2 * cb * n + cb, hp->b2 + c0, cb * 8);
+                const size_t cb = J.cb;
+                uint64_t *pi = stage_in(c0, cb), *di = hp->d_in + c0 * (2 * (size_t)n + 2);
                 HIPCHK(c, hipMemcpyAsync(di, pi, cb * (2 * (size_t)n + 2) * 8, hipMemcpyHostToDevice, c->stream_io));
                 hipEvent_t ein;
                 HIPCHK(c, next_event(&ein));
@@ -1126,8 +1079,6 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
             }
             if (hp_single) {
                 // one download behind the join, below
-            } else if (hp && (io_exp & 2)) {
-                outq.push_back({nullptr, J.c0, J.cb});
             } else if (hp) {   // this chunk's results: device -> page-locked mirror on stream_io2, behind its last kernel
                 hipEvent_t ek, eo;
                 HIPCHK(c, next_event(&ek));
@@ -1142,7 +1093,7 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
             }
         }
         // with this group queued, collect the results of the group before it
-        if (hp && !(io_exp & 3)) {
+        if (hp) {
             const double t = dbg_io ? wall() : 0.0;
             HIPCHK(c, drain_out(out_before));
             if (dbg_io) tw_wait += wall() - t;
@@ -1167,13 +1118,6 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
         c->pending = false;
         host_copy(hp->out, hp->p_out, batch * hp->out_row_words * 8);
         return SGFHE_OK;
-    }
-    if (hp && (io_exp & 2)) {   // experiment: all results after the last kernel
-        HIPCHK(c, hipMemcpyAsync(hp->p_out, hp->d_out, batch * hp->out_row_words * 8, hipMemcpyDeviceToHost, st));
-        hipEvent_t eo;
-        HIPCHK(c, next_event(&eo));
-        HIPCHK(c, hipEventRecord(eo, st));
-        for (auto &o : outq) o.done = eo;
     }
     if (hp) {
         const double t1 = dbg_io ? wall() : 0.0;
@@ -1490,9 +1434,7 @@ int32_t build_constants(sgfhe_ctx *c) {
     c->rnd_ok = rnd_width_ok && npr_rnd != 0 && (c->nb == 2 || npr_rnd == npr_det);
     c->npr_max = c->nb == 2 ? npr_rnd : npr_det;
     {
-        const char *env = getenv("SGFHE_CRT_LEAN");
-        c->use_lean = !(env && env[0] == '0');
-        env = getenv("SGFHE_HOST_PIN");
+        const char *env = getenv("SGFHE_HOST_PIN");
         c->use_pin = !(env && env[0] == '0');
         env = getenv("SGFHE_SMALL_PADDED");
         c->small_padded = env && env[0] == '1';
@@ -1513,8 +1455,6 @@ int32_t build_constants(sgfhe_ctx *c) {
     {
         const char *env = getenv("SGFHE_SMALL_SPLIT");
         if (env) c->split_max = (uint32_t)atoi(env);
-        env = getenv("SGFHE_ITER_ALL");
-        c->iter_all = env && env[0] == '1';
         env = getenv("SGFHE_SMALL_FUSED");
         if (env) c->fused_min = (uint32_t)atoi(env);
     }
@@ -1789,8 +1729,6 @@ int32_t sgfhe_ctx_clone(sgfhe_ctx *src, sgfhe_ctx **out) {
     c->crt1_max = src->crt1_max;
     c->split_max = src->split_max;
     c->fused_min = src->fused_min;
-    c->iter_all = src->iter_all;
-    c->use_lean = src->use_lean;
     c->use_pin = src->use_pin;
     // its own: flatten mode (deterministic, call counter 0), lanes' work buffers, streams, events, staging,
     // timing, the error string and the lock
@@ -2869,12 +2807,12 @@ int32_t sgfhe_kernel_names(const sgfhe_ctx *c, char *extprod, size_t extprod_cap
     if (!c || !extprod || !crt || !extprod_cap || !crt_cap) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
     const bool wide = c->rnd && (c->B >> 46);
-    const int le = c->logm <= SGFHE_EXT_LE3_MAX ? 3 : LOGE;
+    const int le = c->logm <= EXT_LE3_MAX ? 3 : LOGE;
     snprintf(extprod, extprod_cap, "k_extprod<%d, %d, %s>", c->logm, le, wide ? "true" : "false");
     // the selection of launch_crt_raw for the k-loop's mode
-    if (!c->rnd && c->h_lean.nl && c->use_lean)
+    if (!c->rnd && c->h_lean.nl)
         snprintf(crt, crt_cap, "k_crt_lean<%u, %u>", c->npr, c->h_lean.nl);
-    else if (c->rnd && c->lean_rnd_ok && c->use_lean)
+    else if (c->rnd && c->lean_rnd_ok)
         snprintf(crt, crt_cap, "k_crt_lean_rnd<%u, %u, %s>", c->npr, c->h_lean.nl, wide ? "true" : "false");
     else if (!c->rnd)
         snprintf(crt, crt_cap, "k_crt_acc2<%u>", c->npr);

@@ -14,8 +14,6 @@
 //              the accumulator, flatten again (divide by B).
 #pragma once
 
-#include <type_traits>
-
 #include "ntt.h"
 
 namespace sgfhe {
@@ -24,10 +22,7 @@ typedef unsigned __int128 u128;
 
 constexpr int NPR_MAX = 7;  // at most this many RNS primes (p_i < 2^29); a ctx uses the fewest whose
                             // product covers 5 m B Q (4 at Params(64), 5 at Params(512/1024))
-#ifndef SGFHE_LOGE
-#define SGFHE_LOGE 4
-#endif
-constexpr int LOGE = SGFHE_LOGE;  // points per thread (2^LOGE) in every NTT of the engine
+constexpr int LOGE = 4;  // points per thread (2^LOGE) in every NTT of the engine
 
 struct PrimeK {
     int32_t p;        // prime, < 2^29
@@ -163,11 +158,9 @@ __device__ __forceinline__ int4 buf_ld_i4(BufRsrc r, uint32_t voff, uint32_t sof
 // reads, and a non-temporal store writes more slowly: tools/ubench_mall.hip, 4.0 against
 // 5.9 TB/s); on another box plain 1922, sc0 1924, sc1 1936, sc0 sc1 1935, sc0 nt 1903.  sc1
 // (write-through) it is.
-#ifndef SGFHE_YRES_AUX
-#define SGFHE_YRES_AUX 16
-#endif
+constexpr int YRES_AUX = 16;
 __device__ __forceinline__ void buf_st_u32(BufRsrc r, uint32_t voff, uint32_t soff, uint32_t v) {
-    __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)voff, (int)soff, SGFHE_YRES_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(v, r, (int)voff, (int)soff, YRES_AUX);
 }
 
 __device__ __forceinline__ const uint32_t *digit_lo_plane(const uint64_t *dig, size_t bc, uint32_t M) {
@@ -206,8 +199,8 @@ __device__ __forceinline__ void store_digits(uint64_t *__restrict__ dig, size_t 
 }
 
 // ---- randomised flatten (utils.jl:198-241) ----------------------------------------------------------
-// The draws come from a ChaCha counter stream (the RFC 8439 block function with SGFHE_RND_ROUNDS
-// rounds, 8 by default: "ChaCha8") keyed with the caller's 32 bytes, so the digit perturbations are
+// The draws come from a ChaCha counter stream (the RFC 8439 block function with RND_ROUNDS = 8
+// rounds: "ChaCha8") keyed with the caller's 32 bytes, so the digit perturbations are
 // cryptographically strong when the key is.  (Rounds 1-3 used Philox4x32-10 keyed by 64 bits: a
 // statistical generator.)  Functional parity only: the reference draws from the caller's Julia
 // rng, whose stream cannot be reproduced here.
@@ -222,9 +215,8 @@ __device__ __forceinline__ void store_digits(uint64_t *__restrict__ dig, size_t 
 // so a thread of k_crt_lean_rnd (four adjacent coefficients) computes exactly one block.
 // oracle/bigint_oracle.py restates the same stream, so the randomised mode is bit-comparable with
 // the oracle.
-#ifndef SGFHE_RND_ROUNDS
-#define SGFHE_RND_ROUNDS 8
-#endif
+// The round count fixes the stream, and with it every randomised result (and the oracle's restatement).
+constexpr int RND_ROUNDS = 8;
 struct ChaChaKey {
     uint32_t k[8];
 };
@@ -279,7 +271,7 @@ __device__ __forceinline__ void rnd_stream(const RndArgs &ra, uint32_t row, ChaC
 // the 128 bits of one coefficient (ctr.x = its index): a quarter of its quad's block
 __device__ __forceinline__ uint4 rnd128(const ChaChaKey &key, uint4 ctr) {
     uint32_t w[16];
-    chacha_block<SGFHE_RND_ROUNDS>(key, ctr.x >> 2, ctr.y, ctr.z, ctr.w, w);
+    chacha_block<RND_ROUNDS>(key, ctr.x >> 2, ctr.y, ctr.z, ctr.w, w);
     const uint32_t q = ctr.x & 3u;
     return make_uint4(q == 0 ? w[0] : q == 1 ? w[4] : q == 2 ? w[8] : w[12],
                       q == 0 ? w[1] : q == 1 ? w[5] : q == 2 ? w[9] : w[13],
@@ -327,36 +319,31 @@ __device__ __forceinline__ int32_t digit_reduce(uint64_t e, const Mod &md, int32
 // The four digit polynomials u = [a_lo, a_hi, b_lo, b_hi] (fhe.jl:524-526) go through the forward
 // NTT one at a time (phase = key row); the two product polynomials through the inverse NTT one at
 // a time.  The running NTT-domain sum z_0 lives in registers, z_1 in LDS.
-#ifndef SGFHE_EXT_WAVES
-#define SGFHE_EXT_WAVES 4
-#endif
+constexpr int EXT_WAVES = 4;  // waves per SIMD of __launch_bounds__ where a workgroup has 4 or more waves
 // Digit loads of a phase in groups (round 5, profiles/r05_exp_wide.txt).  The WIDE instantiations have three loads
 // per digit -- 48 values in flight beside the 32 accumulator registers -- and hipcc spilled five accumulator pairs
 // around the phase loop (44-52 bytes of scratch per lane, rounds 3-4): Params(2048) with the randomised flatten ran
 // at 297 bootstraps/s with the spills and runs at 345 without them (+16 %, same call).  The digits of a phase are
 // requested in SPLIT groups, each reduced before the next is requested (a scheduling barrier between the groups
-// bounds the values in flight): 2 groups remove the scratch at m = 8192 / 16384, 4 at m = 4096 too; the 32-bit
-// accumulator instead (-DSGFHE_WIDE_ACC32: 106-125 VGPRs, no scratch either) measured 339.
-#ifndef SGFHE_WIDE_SPLIT
-#define SGFHE_WIDE_SPLIT(LOGM) ((LOGM) >= 13 ? 2 : 4)
-#endif
-#ifndef SGFHE_DET_SPLIT     // the same for the two-plane kernels (A/B builds: -DSGFHE_DET_SPLIT=2)
-#define SGFHE_DET_SPLIT 0
-#endif
-// LE: points per thread (2^LE); 16 wherever that leaves a full wavefront, 8 for m <= 512
+// bounds the values in flight): 2 groups remove the scratch at m = 8192 / 16384, 4 at m = 4096 too; a 32-bit
+// column-0 accumulator instead (106-125 VGPRs, no scratch either) measured 339.
+constexpr int wide_split(int logm) { return logm >= 13 ? 2 : 4; }
+// The two-plane (deterministic) kernels are not split: 2 groups would give k_extprod<13, 4, false> 12 bytes of
+// scratch, and leave the radix-4 steps at m = 4096 / 16384 spilling 8-32 bytes (RESULTS.md, round 5).
+constexpr int DET_SPLIT = 0;
+// LE: points per thread (2^LE); 16 wherever that leaves a full wavefront, 8 for m <= 512 (8 measured
+// slower at m = 4096 and 8192 too: profiles/r02_exp_p512_points.txt, r04_exp_mid_le3.txt)
+constexpr int EXT_LE3_MAX = 9;   // largest log2(m) with 8 points per thread
 // WIDE: the digit planes carry a third plane (bits 48..55; MODE_WIDE): a separate instantiation, so
 // that the deterministic kernel is textually what it was.
 template <int LOGM, int LE, bool WIDE = false>
-__global__ void __launch_bounds__((NttGeom<LOGM, LE>::T), (NttGeom<LOGM, LE>::T >= 256 ? SGFHE_EXT_WAVES : 1))
+__global__ void __launch_bounds__((NttGeom<LOGM, LE>::T), (NttGeom<LOGM, LE>::T >= 256 ? EXT_WAVES : 1))
 k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
           uint32_t *__restrict__ yres, const uint32_t *__restrict__ ua, PrimeSet PS, uint32_t k,
           uint32_t n, uint32_t mode) {
     using G = NttGeom<LOGM, LE>;
     constexpr int M = G::M, T = G::T, E = G::E;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-#ifdef SGFHE_EXT_PRIO  // experiment: issue priority over a co-running k_crt_lean (second lane)
-    __builtin_amdgcn_s_setprio(SGFHE_EXT_PRIO);
-#endif
     int32_t *const z1 = reinterpret_cast<int32_t *>(lds) + M + threadIdx.x;  // z1[e * T]: private to the thread, conflict-free
 
     const int tid = threadIdx.x;
@@ -379,26 +366,14 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
 #endif
 
     const int32_t sRd = (mode & MODE_RANDOM) ? P.sRr : P.sR;  // digit offset of the flatten mode
-    constexpr int SPLIT = E == 16 ? (WIDE ? SGFHE_WIDE_SPLIT(LOGM) : SGFHE_DET_SPLIT) : 0;
-#ifdef SGFHE_ACC0_32
-    constexpr bool ACC32 = true;
-#elif defined(SGFHE_WIDE_ACC32)   // A/B build of round 5: the 32-bit accumulator in the WIDE instantiations only
-    constexpr bool ACC32 = WIDE && E == 16;
-#else
-    constexpr bool ACC32 = false;
-#endif
-    // ACC32: column 0 summed like column 1, Montgomery-reduced per phase (< 2.9 * 2^29); else the 64-bit
-    // NTT-domain sum of column 0 over the four phases (|.| < 1.98 * 2^60)
-    typename std::conditional<ACC32, int32_t, int64_t>::type acc0[E];
+    constexpr int SPLIT = E == 16 ? (WIDE ? wide_split(LOGM) : DET_SPLIT) : 0;
+    // the 64-bit NTT-domain sum of column 0 over the four phases (|.| < 1.98 * 2^60)
+    int64_t acc0[E];
 #pragma unroll
     for (int e = 0; e < E; e++) { acc0[e] = 0; z1[e * T] = 0; }
     // A real loop (not unrolled): one copy of the forward NTT in the instruction stream, and the
     // loads of a later phase cannot be hoisted over the registers of an earlier one.
-#ifdef SGFHE_PH_UNROLL
-#pragma unroll SGFHE_PH_UNROLL
-#else
 #pragma unroll 1
-#endif
     for (int ph = 0; ph < 4; ph++) {
         // The thread index is made opaque per iteration: otherwise the ~60 loop-invariant LDS /
         // twiddle addresses derived from it are hoisted out of the loop and spilled.
@@ -434,41 +409,29 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
 
         // 2. forward NTT of u[ph].  The key slice rows of this phase (from L2: every bootstrap of
         //    the launch reads the same slice) are requested after the transform.  Requesting them
-        //    before its last pass (-DSGFHE_KEY_EARLY) keeps 32 more registers live through that
-        //    pass: at the 128-register budget hipcc then spills or shuffles the accumulators, and
-        //    the kernel is slower (profiles/r02_exp_buffer_addressing.txt).
-#ifdef SGFHE_KEY_EARLY
-        constexpr bool KEY_EARLY = LOGM >= 13;
-#else
-        constexpr bool KEY_EARLY = false;
-#endif
+        //    before its last pass keeps 32 more registers live through that pass: at the
+        //    128-register budget hipcc then spills or shuffles the accumulators, and the kernel is
+        //    slower (profiles/r02_exp_buffer_addressing.txt).
         const uint32_t skey = (pi * 8u + (uint32_t)ph * 2u) * 4u * (uint32_t)M;  // byte offset of key row ph, column 0
         const uint32_t vkey = 4u * (uint32_t)E * (uint32_t)tid;
         int4 ka4[E / 4], kb4[E / 4];
-        auto load_key = [&]() {
+        ntt_forward<LOGM, 1, LE>(x, lds, P.twf, tid, md);
 #pragma unroll
-            for (int h = 0; h < E / 4; h++) {
+        for (int h = 0; h < E / 4; h++) {
 #ifdef SGFHE_ABL_NO_KEY
-                ka4[h] = make_int4(tid, h, ph, 7), kb4[h] = make_int4(h, tid, 5, ph);  // timing-only
+            ka4[h] = make_int4(tid, h, ph, 7), kb4[h] = make_int4(h, tid, 5, ph);  // timing-only
 #else
-                ka4[h] = buf_ld_i4(rkey, vkey + 16u * (uint32_t)h, skey);
-                kb4[h] = buf_ld_i4(rkey, vkey + 16u * (uint32_t)h, skey + 4u * (uint32_t)M);
+            ka4[h] = buf_ld_i4(rkey, vkey + 16u * (uint32_t)h, skey);
+            kb4[h] = buf_ld_i4(rkey, vkey + 16u * (uint32_t)h, skey + 4u * (uint32_t)M);
 #endif
-            }
-        };
-        if constexpr (KEY_EARLY) {
-            ntt_forward<LOGM, 1, LE>(x, lds, P.twf, tid, md, load_key);
-        } else {
-            ntt_forward<LOGM, 1, LE>(x, lds, P.twf, tid, md);
-            load_key();
         }
 
         // 3. pointwise: z_c += U * K[ph][c]   (fhe.jl:527-528 in the NTT domain), |U| < 3.95 * 2^29,
         //    |K| <= p / 2
         //    column 0: 64-bit multiply-accumulate (one v_mad_i64_i32 per product), reduced once after
-        //              the loop.  (SGFHE_ACC0_32: Montgomery-reduced per phase into 16 registers
-        //              instead of 32 -- 104 VGPRs and no spills, but 2 more multiplies per product:
-        //              measured 230.8 against 225.1 us per launch, profiles/r02_acc32_* vs r02_v1_*.)
+        //              the loop.  (Montgomery-reduced per phase into 16 registers instead of 32:
+        //              104 VGPRs and no spills, but 2 more multiplies per product; measured 230.8
+        //              against 225.1 us per launch, profiles/r02_acc32_* vs r02_v1_*.)
         //    column 1: Montgomery-reduced (|.| < 0.75 * 2^29) and added to the LDS accumulator
         const Mod &mdp = md;
 #pragma unroll
@@ -480,8 +443,7 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
             for (int t = 0; t < 4; t++) {
                 const int e = 4 * h + t;
                 const int32_t u = x[0][e];
-                if constexpr (ACC32) acc0[e] += smont(u, ka[t], mdp);
-                else acc0[e] += (int64_t)u * ka[t];
+                acc0[e] += (int64_t)u * ka[t];
                 int32_t *zp = reinterpret_cast<int32_t *>(lds) + M + e * T + tid;
                 *zp += smont(u, kb[t], mdp);
             }
@@ -493,28 +455,17 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
     int32_t z[2][E];
     // With 16 points per thread the first inverse pass takes column 0 as the Montgomery step
     // leaves it (|.| < 1.49 * 2^29) and reduces six more of its sums instead (ntt.h inv_red_mask).
-#if defined(SGFHE_ACC0_32)
-    constexpr bool WIDE0 = false;
-#elif SGFHE_INV_RADIX4
     // (the radix-4 inverse reduces column 0 on entry like column 1)
-    constexpr bool WIDE0 = !SGFHE_INV_R4(LOGM) && LE == 4 && NttGeom<LOGM, LE>::SLAST_INV >= 0 &&
+    constexpr bool WIDE0 = !inv_r4(LOGM) && LE == 4 && NttGeom<LOGM, LE>::SLAST_INV >= 0 &&
                            !(NttGeom<LOGM, LE>::RHO == 0 && NttGeom<LOGM, LE>::STOP == 0);
-#else
-    constexpr bool WIDE0 = LE == 4 && NttGeom<LOGM, LE>::SLAST_INV >= 0 &&
-                           !(NttGeom<LOGM, LE>::RHO == 0 && NttGeom<LOGM, LE>::STOP == 0);
-#endif
 #pragma unroll
     for (int e = 0; e < E; e++) {
-        if constexpr (ACC32) {
-            z[0][e] = sred((int32_t)acc0[e], md);
-        } else {
-            const int32_t r0 = sredc(acc0[e], md);   // |REDC| < 1.49 * 2^29
-            z[0][e] = WIDE0 ? r0 : sred(r0, md);
-        }
+        const int32_t r0 = sredc(acc0[e], md);   // |REDC| < 1.49 * 2^29
+        z[0][e] = WIDE0 ? r0 : sred(r0, md);
         z[1][e] = sred(z1[e * T], md);           // four phases: < 2.99 * 2^29
     }
     SGFHE_SYNC();  // every thread has taken its z_1 out of the buffer the exchanges now reuse
-    ntt_inverse<LOGM, 2, LE, (WIDE0 && !ACC32)>(z, lds, P.twi, tid, md);  // |z| < 1.4 * 2^29
+    ntt_inverse<LOGM, 2, LE, WIDE0>(z, lds, P.twi, tid, md);  // |z| < 1.4 * 2^29
 
     // Output addressing as for the digit loads: scalar offsets per column and coefficient, one
     // 32-bit lane offset.
@@ -534,30 +485,27 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
     }
     const uint32_t j = ua[(size_t)b * n + k];
     const uint32_t yoff = 3u * (uint32_t)P.p + P.hoff;
-#ifdef SGFHE_EPI_PLAIN   // (A/B build, round 4: not adopted -- see below)
-    // Both product polynomials go to LDS in the plain layout (word i of polynomial c at c m + i): lane
-    // t writes word t + T e and reads word (t - j + T e) mod m, consecutive lanes consecutive words
-    // either way, so neither access has a bank conflict whatever j is.  (Round 3 kept the transform's
-    // swizzled layout here; its j-shifted reads then collide where the run of 64 source indices
-    // crosses a swizzle boundary: 2.6 % of the kernel's LDS cycles, profiles/r03_v10_counters.json.)
-    // The buffer is the one the transform's last loads came from: every wave has to be done with them.
+    // The transform's swizzled layout is kept for this exchange.  Its j-shifted reads collide where
+    // the run of 64 source indices crosses a swizzle boundary (2.6 % of the kernel's LDS cycles,
+    // profiles/r03_v10_counters.json).  A plain layout (word i of polynomial c at c m + i) has no
+    // conflict for any j but needs one more workgroup barrier, and measured the same at m = 8192
+    // (2108 against 2110 bootstraps/s, same call) and 2.3-2.4 % slower at m = 4096 and 16384
+    // (profiles/r04_exp_epilogue.txt): LDS bandwidth is not what this kernel waits for.
+    lds_store<LOGM, 2, LE, G::STOP>(z, lds, tid);
     SGFHE_SYNC();
+    // Source index of output coefficient i = tid + T e is s_e = (i - j) mod 2m = s_0 + T e:
+    // the swizzled low part is computed once per thread.
     {
-        int32_t *const ldsi = reinterpret_cast<int32_t *>(lds);
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int e = 0; e < E; e++) ldsi[c * M + T * e + tid] = z[c][e];
-    }
-    SGFHE_SYNC();
-    {
+        constexpr uint32_t LOWMASK = (1u << G::STOP) - 1u;
         const uint32_t s0 = ((uint32_t)tid - j) & (2 * M - 1);
-        const uint32_t low = s0 & ((1u << G::STOP) - 1u);
+        const uint32_t lowswz = swz<LE>(s0 & LOWMASK);
         const uint32_t h0 = s0 >> G::STOP;
 #pragma unroll
         for (int e = 0; e < E; e++) {
             const uint32_t he = h0 + e;
-            const uint32_t addr = ((he & (E - 1)) << G::STOP) | low;
+            const uint32_t hipart = (he & (E - 1)) << G::STOP;
+            // swz is XOR-linear; for m = 8192 the e bits lie above every bit it reads
+            const uint32_t addr = hipart ^ lowswz ^ (G::STOP >= 9 ? 0u : swz_bits<LE>(hipart));
             // x^m = -1: the source is negated when bit LE of he is set.  -v = (v ^ -1) + 1, so
             // with smask = 0 / -1 the output is (v ^ smask) + (yoff - smask - z): one subtract and
             // one xor-add per residue, the per-e constants shared by both columns.
@@ -575,40 +523,6 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
             }
         }
     }
-#else
-    // The transform's swizzled layout is kept for this exchange.  Its j-shifted reads collide where
-    // the run of 64 source indices crosses a swizzle boundary (2.6 % of the kernel's LDS cycles,
-    // profiles/r03_v10_counters.json); the plain layout above has no conflict for any j but needs
-    // one more workgroup barrier, and measured the same at m = 8192 (2108 against 2110 bootstraps/s,
-    // same call) and 2.3-2.4 % slower at m = 4096 and 16384 (profiles/r04_exp_epilogue.txt): LDS
-    // bandwidth is not what this kernel waits for.
-    lds_store<LOGM, 2, LE, G::STOP>(z, lds, tid);
-    SGFHE_SYNC();
-    // Source index of output coefficient i = tid + T e is s_e = (i - j) mod 2m = s_0 + T e:
-    // the swizzled low part is computed once per thread.
-    {
-        constexpr uint32_t LOWMASK = (1u << G::STOP) - 1u;
-        const uint32_t s0 = ((uint32_t)tid - j) & (2 * M - 1);
-        const uint32_t lowswz = swz<LE>(s0 & LOWMASK);
-        const uint32_t h0 = s0 >> G::STOP;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const uint32_t he = h0 + e;
-            const uint32_t hipart = (he & (E - 1)) << G::STOP;
-            // swz is XOR-linear; for m = 8192 the e bits lie above every bit it reads
-            const uint32_t addr = hipart ^ lowswz ^ (G::STOP >= 9 ? 0u : swz_bits<LE>(hipart));
-            const uint32_t smask = 0u - ((he >> LE) & 1u);
-            const uint32_t yoe = yoff - smask;
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const uint32_t v = lds[c * M + addr];
-                const uint32_t y = (v ^ smask) + (yoe - (uint32_t)z[c][e]);
-                buf_st_u32(ryres, vout + ((uint32_t)(4 * T * e) & 4095u),
-                              (c ? sy1 : sy0) + ((uint32_t)(4 * T * e) & ~4095u), y);
-            }
-        }
-    }
-#endif
 }
 
 // ---- k_crt_acc --------------------------------------------------------------------------------
@@ -957,8 +871,6 @@ k_crt_lean(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     for (int q = 0; q < NP; q++) {
 #ifdef SGFHE_ABL_NO_YLOAD       // timing-only build: no residue loads (wrong results)
         yv[q] = make_uint4(t + q, yo, i + 7u * q, bc);
-#elif defined(SGFHE_CRT_PLAIN_LOADS)  // (A/B builds)
-        yv[q] = ld_off<uint4>(yres, yo + ((uint32_t)(4 * q) << logm));
 #else
         const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(
             reinterpret_cast<const char *>(yres) + yo + ((uint32_t)(4 * q) << logm)));
@@ -1053,7 +965,7 @@ k_crt_lean_rnd(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     uint32_t cz, cw;
     rnd_stream<ROWS>(ra, bc >> 1, key, cz, cw);
     uint32_t rw[16];   // the draws of the thread's four coefficients: one block of the stream
-    chacha_block<SGFHE_RND_ROUNDS>(key, cx >> 2, iter, cz, cw, rw);
+    chacha_block<RND_ROUNDS>(key, cx >> 2, iter, cz, cw, rw);
     uint64_t nlo[4], nhi[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -1138,7 +1050,7 @@ k_crt_lean_rnd1(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     uint32_t cz, cw;
     rnd_stream<ROWS>(ra, bc >> 1, key, cz, cw);
     uint32_t rw[16];
-    chacha_block<SGFHE_RND_ROUNDS>(key, cx >> 2, iter, cz, cw, rw);
+    chacha_block<RND_ROUNDS>(key, cx >> 2, iter, cz, cw, rw);
     const uint32_t sel = cx & 3u;   // this coefficient's four words of the block
     const uint32_t w0 = sel == 0 ? rw[0] : sel == 1 ? rw[4] : sel == 2 ? rw[8] : rw[12];
     const uint32_t w1 = sel == 0 ? rw[1] : sel == 1 ? rw[5] : sel == 2 ? rw[9] : rw[13];
@@ -1150,158 +1062,6 @@ k_crt_lean_rnd1(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     crt_lean_one<NP, NL, true>(y, d.x + (xm2 - r0), d.y + (xm2 - r1), K, lo, hi);
     store_digits(dig, bc, i, M, lo + r0, hi + r1);
 }
-
-// ---- one launch per iteration: the residues never leave the compute unit (round 4, PROTOTYPE) -------------------
-// Compiled only with -DSGFHE_WITH_ITER_ALL (tools/exp_r4_iter_all.sh); selected at run time by SGFHE_ITER_ALL=1.
-// Bit-exact (tests/test_gpu_parity.py::test_params1024_vs_oracle under that switch), and 17 % SLOWER than the two
-// kernels it replaces (1737 against 2083 bootstraps/s, same call, profiles/r04_exp_iter_all.txt): one workgroup of
-// 1024 threads per compute unit means every one of its ~135 workgroup barriers per iteration stalls the whole
-// compute unit, where two co-resident k_extprod workgroups fill each other's stalls; 8 points per thread cost a
-// fifth LDS pass per transform; and the register file (128 per thread) holds the transform's working set beside
-// 56 accumulators only, so column 1 of three primes lives in LDS.  Kept as the starting point for a design that
-// removes the hand-off without giving up two independent instruction streams per compute unit.
-#ifdef SGFHE_WITH_ITER_ALL
-// k_extprod hands 20 bytes per coefficient to the CRT kernel through memory, and that hand-off costs 11 % of the
-// path's throughput -- as clock: the socket is at its power limit (profiles/r04_exp_clock_handoff.txt).  Here one
-// workgroup of m / 8 threads owns a bootstrap with ALL its primes: every thread keeps the NTT-domain sums of both
-// product columns for every prime in registers (NP x 2 x 8), runs the forward transforms prime by prime inside the
-// phase loop, then per prime the inverse pair and the rotation in place, and ends with the CRT / accumulate /
-// flatten of its own 16 coefficients (crt_lean_one) -- no yres, no second kernel.  8 points per thread (the
-// register file holds 128 registers for each of 1024 threads); deterministic flatten, NP <= 5.
-// The prime index is a template parameter (recursion over PI) so that the accumulator arrays are only ever
-// indexed by constants: a `#pragma unroll` inside the rolled phase loop is not honoured, and a dynamically
-// indexed array lives in scratch memory.  Column 1 of the first LP primes accumulates in LDS (private words, as
-// k_extprod's z1), the rest in registers.
-template <int LOGM, int NP, int LP>
-struct IterAll {
-    static constexpr int LE = 3;
-    using G = NttGeom<LOGM, LE>;
-    static constexpr int M = G::M, T = G::T, E = G::E;
-    // private LDS word e of prime pi's column 1 (pi < LP): behind the 2 m words of the exchange buffer
-    static __device__ __forceinline__ int32_t *priv(uint32_t *lds, int pi, int tid) {
-        return reinterpret_cast<int32_t *>(lds) + (2 + pi) * M + tid;
-    }
-    template <int PI>
-    static __device__ __forceinline__ void forward(int32_t (&a0)[NP][E], int32_t (&a1)[NP - LP][E],
-                                                   const uint64_t *__restrict__ dig, uint32_t b,
-                                                   const int32_t *__restrict__ keyk, PrimeSet PS, uint32_t *lds, int ph) {
-        if constexpr (PI < NP) {
-            const PrimeK P = PS[PI];
-            const Mod md = mod_of(P);
-            // addresses behind an opaque zero: the loads of this prime are not hoisted over the work of the one before
-            const int tid = (int)threadIdx.x + (int)opaque_zero();
-            const uint32_t *dl = digit_lo_plane(dig, (size_t)b * 2 + (ph >> 1), M) + (ph & 1) * M;
-            const uint16_t *dh = digit_hi_plane(dig, (size_t)b * 2 + (ph >> 1), M) + (ph & 1) * M;
-            int32_t x[1][E];
-#pragma unroll
-            for (int e = 0; e < E; e++)
-                x[0][e] = digit_reduce(dl[tid + T * e] | ((uint64_t)dh[tid + T * e] << 32), md, P.sR);
-            SGFHE_SYNC();   // the exchange buffer is reused
-            ntt_forward<LOGM, 1, LE>(x, lds, P.twf, tid, md);
-            const int32_t *kp = keyk + ((size_t)PI * 8 + ph * 2) * M + E * (tid + (int)opaque_zero());
-#pragma unroll
-            for (int h = 0; h < E / 4; h++) {
-                const int4 a = reinterpret_cast<const int4 *>(kp)[h];
-                const int4 bq = reinterpret_cast<const int4 *>(kp + M)[h];
-                const int32_t ka[4] = {a.x, a.y, a.z, a.w}, kb[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const int e = 4 * h + t;
-                    a0[PI][e] += smont(x[0][e], ka[t], md);   // four phases: < 2.99 * 2^29
-                    if constexpr (PI < LP) priv(lds, PI, tid)[e * T] += smont(x[0][e], kb[t], md);
-                    else a1[PI - LP][e] += smont(x[0][e], kb[t], md);
-                }
-            }
-            forward<PI + 1>(a0, a1, dig, b, keyk, PS, lds, ph);
-        }
-    }
-    // inverse pair, rotation and residue form of prime PI, back into the accumulators' places
-    template <int PI>
-    static __device__ __forceinline__ void inverse(int32_t (&a0)[NP][E], int32_t (&a1)[NP - LP][E], PrimeSet PS,
-                                                   uint32_t *lds, uint32_t j) {
-        if constexpr (PI < NP) {
-            const PrimeK P = PS[PI];
-            const Mod md = mod_of(P);
-            const int tid = (int)threadIdx.x + (int)opaque_zero();
-            int32_t z[2][E];
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                z[0][e] = sred(a0[PI][e], md);
-                if constexpr (PI < LP) z[1][e] = sred(priv(lds, PI, tid)[e * T], md);
-                else z[1][e] = sred(a1[PI - LP][e], md);
-            }
-            SGFHE_SYNC();
-            ntt_inverse<LOGM, 2, LE>(z, lds, P.twi, tid, md);   // |.| < 1.4 * 2^29
-            lds_store<LOGM, 2, LE, G::STOP>(z, lds, tid);
-            SGFHE_SYNC();
-            constexpr uint32_t LOWMASK = (1u << G::STOP) - 1u;
-            const uint32_t s0 = ((uint32_t)tid - j) & (2 * M - 1);
-            const uint32_t lowswz = swz<LE>(s0 & LOWMASK);
-            const uint32_t h0 = s0 >> G::STOP;
-            const uint32_t yoff = 3u * (uint32_t)P.p + P.hoff;
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                const uint32_t he = h0 + e;
-                const uint32_t hipart = (he & (E - 1)) << G::STOP;
-                const uint32_t addr = hipart ^ lowswz ^ (G::STOP >= 9 ? 0u : swz_bits<LE>(hipart));
-                const uint32_t smask = 0u - ((he >> LE) & 1u);
-                const uint32_t yoe = yoff - smask;
-                // the residues k_extprod stores
-                a0[PI][e] = (int32_t)((lds[addr] ^ smask) + (yoe - (uint32_t)z[0][e]));
-                const int32_t y1 = (int32_t)((lds[M + addr] ^ smask) + (yoe - (uint32_t)z[1][e]));
-                if constexpr (PI < LP) priv(lds, PI, tid)[e * T] = y1;
-                else a1[PI - LP][e] = y1;
-            }
-            inverse<PI + 1>(a0, a1, PS, lds, j);
-        }
-    }
-};
-
-template <int LOGM, int NP, int NL>
-__global__ void __launch_bounds__((NttGeom<LOGM, 3>::T))
-k_iter_all(uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk, const uint32_t *__restrict__ ua,
-           PrimeSet PS, const CrtLean *__restrict__ K, uint32_t k, uint32_t n) {
-#ifndef SGFHE_IA_LP
-#define SGFHE_IA_LP 3
-#endif
-    constexpr int LP = SGFHE_IA_LP;
-    using IA = IterAll<LOGM, NP, LP>;
-    constexpr int M = IA::M, T = IA::T, E = IA::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // (2 + LP) m words
-    const uint32_t b = blockIdx.x;
-    int32_t a0[NP][E], a1[NP - LP][E];
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-#pragma unroll
-        for (int q = 0; q < NP; q++) a0[q][e] = 0;
-#pragma unroll
-        for (int q = 0; q < NP - LP; q++) a1[q][e] = 0;
-#pragma unroll
-        for (int q = 0; q < LP; q++) IA::priv(lds, q, (int)threadIdx.x)[e * T] = 0;
-    }
-#pragma unroll 1
-    for (int ph = 0; ph < 4; ph++) IA::template forward<0>(a0, a1, dig, b, keyk, PS, lds, ph);
-    IA::template inverse<0>(a0, a1, PS, lds, ua[(size_t)b * n + k]);
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-#ifdef SGFHE_IA_NOCRT
-            if (c + e >= 0) continue;
-#endif
-            const int tid = (int)threadIdx.x + (int)opaque_zero();   // one coefficient's loads at a time
-            uint32_t y[NP];
-#pragma unroll
-            for (int q = 0; q < NP; q++)
-                y[q] = (uint32_t)(c == 0 ? a0[q][e] : q < LP ? IA::priv(lds, q, tid)[e * T] : a1[q < LP ? 0 : q - LP][e]);
-            const uint32_t i = (uint32_t)tid + (uint32_t)(T * e);
-            const ulonglong2 d = load_digits(dig, (size_t)b * 2 + c, i, M);
-            uint64_t lo, hi;
-            crt_lean_one<NP, NL>(y, d.x, d.y, K, lo, hi);
-            store_digits(dig, (size_t)b * 2 + c, i, M, lo, hi);
-        }
-}
-#endif  // SGFHE_WITH_ITER_ALL
 
 // ---- small-batch ("latency") form of the external product --------------------------------------
 // A call with a handful of gates leaves most of the 256 CUs idle while one workgroup per

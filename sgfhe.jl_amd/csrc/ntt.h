@@ -36,24 +36,14 @@
 #define SGFHE_SYNC() __syncthreads()
 #endif
 
-#ifndef SGFHE_FWD_RADIX4
-#define SGFHE_FWD_RADIX4 1
-#endif
-#ifndef SGFHE_INV_RADIX4
-#define SGFHE_INV_RADIX4 1
-#endif
+namespace sgfhe {
+
 // Forward passes with per-lane twiddles take the radix-4 form (two more vector registers) only where
 // k_extprod keeps its registers without spilling: hipcc spills 16-20 bytes at m = 4096 and 16384.
-#ifndef SGFHE_FWD_VEC4
-#define SGFHE_FWD_VEC4(LOGM) ((LOGM) != 12 && (LOGM) != 14)
-#endif
+constexpr bool fwd_vec4(int logm) { return logm != 12 && logm != 14; }
 // The inverse keeps its radix-2 form (with the searched reduction pattern and the un-reduced entry
 // of column 0) at m = 4096, where the radix-4 steps cost k_extprod 20-24 bytes of scratch.
-#ifndef SGFHE_INV_R4
-#define SGFHE_INV_R4(LOGM) ((LOGM) != 12)
-#endif
-
-namespace sgfhe {
+constexpr bool inv_r4(int logm) { return logm != 12; }
 
 template <int LOGE>
 __host__ __device__ constexpr uint32_t swz_bits(uint32_t idx) {
@@ -381,17 +371,10 @@ __device__ __forceinline__ void exchange_sync() {
 }
 
 // forward LDS passes S = SCUR, SCUR - LOGE, ..., 0; data arrives in registers in layout SPREV
-struct NoHook {
-    __device__ __forceinline__ void operator()() const {}
-};
-// `before_last` runs just before the exchange into the last pass: the caller's place to issue
-// loads it needs right after the transform, so that their latency overlaps that pass.
 template <int LOGM, int NP, int LOGE, int SPREV, int SCUR>
 struct FwdPasses {
-    template <class F>
     static __device__ __forceinline__ void run(int32_t (&x)[NP][1 << LOGE], uint32_t *lds,
-                                               const int32_t *tw, int tid, const Mod &md,
-                                               const F &before_last) {
+                                               const int32_t *tw, int tid, const Mod &md) {
         int32_t t[(1 << LOGE) - 1], tp[(1 << LOGE) - 1];
         load_twiddles<LOGM, LOGE, SCUR, LOGE - 1, 0>(t, tw, (uint32_t)tid >> SCUR);
         // Product twiddles of the radix-4 steps (table tw + 2 m).  A pass whose twiddles are
@@ -399,12 +382,11 @@ struct FwdPasses {
         // (LOGE = 4: ten products); a pass with per-lane twiddles only its first pair (two more
         // vector registers).
         constexpr bool UNIFORM = (1 << SCUR) >= 64;
-        constexpr bool TWO_STEPS = SGFHE_FWD_RADIX4 && LOGE == 4 && UNIFORM;
-        if constexpr (SGFHE_FWD_RADIX4 && (UNIFORM || SGFHE_FWD_VEC4(LOGM))) {
+        constexpr bool TWO_STEPS = LOGE == 4 && UNIFORM;
+        if constexpr (UNIFORM || fwd_vec4(LOGM)) {
             load_twiddles<LOGM, LOGE, SCUR, LOGE - 2, LOGE - 2>(tp, tw + (2 << LOGM), (uint32_t)tid >> SCUR);
             if constexpr (TWO_STEPS) load_twiddles<LOGM, LOGE, SCUR, 0, 0>(tp, tw + (2 << LOGM), (uint32_t)tid >> SCUR);
         }
-        if constexpr (SCUR < LOGE) before_last();
         lds_store<LOGM, NP, LOGE, SPREV>(x, lds, tid);
         exchange_sync<LOGE, SCUR>();
         lds_load<LOGM, NP, LOGE, SCUR>(x, lds, tid);
@@ -420,7 +402,7 @@ struct FwdPasses {
             fwd_step4<NP, LOGE, 3>(x, t, tp, mdl);
             fwd_reduce_x0<NP, LOGE, 1>(x, mdl);
             fwd_step4<NP, LOGE, 1>(x, t, tp, mdl);
-        } else if constexpr (SGFHE_FWD_RADIX4 && (UNIFORM || SGFHE_FWD_VEC4(LOGM))) {
+        } else if constexpr (UNIFORM || fwd_vec4(LOGM)) {
             fwd_reduce_x<NP, LOGE>(x, mdl);
             fwd_step4<NP, LOGE, LOGE - 1>(x, t, tp, mdl);
             fwd_stages<NP, LOGE, LOGE - 3, 0>(x, t, mdl);
@@ -429,7 +411,7 @@ struct FwdPasses {
             fwd_stages<NP, LOGE, LOGE - 1, 0>(x, t, mdl);
         }
         if constexpr (SCUR >= LOGE)
-            FwdPasses<LOGM, NP, LOGE, SCUR, SCUR - LOGE>::run(x, lds, tw, tid, md, before_last);
+            FwdPasses<LOGM, NP, LOGE, SCUR, SCUR - LOGE>::run(x, lds, tw, tid, md);
     }
 };
 // inverse passes S = SCUR, SCUR + LOGE, ..., SLAST; data arrives in registers in layout SCUR and
@@ -438,11 +420,9 @@ struct FwdPasses {
 // WIDE0: polynomial 0 enters the first pass with |x| <= 1.5 * 2^29 instead of 0.75 (LOGE = 4 only)
 // product twiddles of inverse pass S (table tw + 2 m): for the step on local bits 0 / 1, and on 2 / 3
 // as well where the pass runs both steps (LOGE = 4, wave-uniform twiddles)
-template <int LOGM, int S>
-constexpr bool inv_pass_radix4() { return SGFHE_INV_RADIX4 && SGFHE_INV_R4(LOGM); }
 template <int LOGM, int LOGE, int S>
 __device__ __forceinline__ void load_inv_products(int32_t (&tp)[(1 << LOGE) - 1], const int32_t *tw, int tid) {
-    if constexpr (inv_pass_radix4<LOGM, S>()) {
+    if constexpr (inv_r4(LOGM)) {
         load_twiddles<LOGM, LOGE, S, 0, 0>(tp, tw + (2 << LOGM), (uint32_t)tid >> S);
         if constexpr (LOGE == 4 && (1 << S) >= 64)
             load_twiddles<LOGM, LOGE, S, 2, 2>(tp, tw + (2 << LOGM), (uint32_t)tid >> S);
@@ -455,18 +435,16 @@ struct InvPasses {
                                                const int32_t (&t)[(1 << LOGE) - 1],
                                                const int32_t (&tp)[(1 << LOGE) - 1]) {
         constexpr int MODE = (FINAL && SCUR == SLAST) ? 2 : 1;
-#if SGFHE_INV_RADIX4
-        if constexpr (!inv_pass_radix4<LOGM, SCUR>()) {
+        if constexpr (!inv_r4(LOGM)) {
             // radix-2 stages with the searched reduction pattern (inputs and outputs below 0.75 * 2^29)
             static_assert(!WIDE0 || (LOGE == 4 && !(FINAL && SLAST == 0)), "wide first pass: radix 16, not the final pass");
             inv_stages<NP, LOGE, 0, LOGE - 1, 0, MODE, (WIDE0 && SCUR == 0) ? 3 : MODE>(x, t, md);
-        } else
-        // Radix-4 steps with deferred reductions (inv_step4).  Every pass opens with one on local
-        // bits 0 and 1; a pass whose twiddles are wave-uniform (scalar registers) runs bits 2 and 3
-        // the same way, the others as radix-2 stages.  Reductions: the four-fold sums y0 after each
-        // step; in the radix-2 tail the sums of the last stage (in the final pass only those that
-        // can exceed 1.4 * 2^29).  tests/rns_model.py NttModel.inv_pass / RangeModel.inverse.
-        {
+        } else {
+            // Radix-4 steps with deferred reductions (inv_step4).  Every pass opens with one on local
+            // bits 0 and 1; a pass whose twiddles are wave-uniform (scalar registers) runs bits 2 and 3
+            // the same way, the others as radix-2 stages.  Reductions: the four-fold sums y0 after each
+            // step; in the radix-2 tail the sums of the last stage (in the final pass only those that
+            // can exceed 1.4 * 2^29).  tests/rns_model.py NttModel.inv_pass / RangeModel.inverse.
             static_assert(!WIDE0, "the radix-4 inverse takes every polynomial below 0.75 * 2^29");
             constexpr bool UNIFORM = (1 << SCUR) >= 64;
             inv_step4<NP, LOGE, 0>(x, t, tp, md);
@@ -483,10 +461,6 @@ struct InvPasses {
                 inv_stage<NP, LOGE, 2, MODE == 2 ? 0u : 0x0Fu, MODE == 2 ? 0u : 0x0Fu>(x, t, md);
             }
         }
-#else
-        static_assert(!WIDE0 || (LOGE == 4 && !(FINAL && SLAST == 0)), "wide first pass: radix 16, not the final pass");
-        inv_stages<NP, LOGE, 0, LOGE - 1, 0, MODE, (WIDE0 && SCUR == 0) ? 3 : MODE>(x, t, md);
-#endif
         if constexpr (SCUR < SLAST) {
             int32_t tn[(1 << LOGE) - 1], tpn[(1 << LOGE) - 1];
             load_twiddles<LOGM, LOGE, SCUR + LOGE, LOGE - 1, 0>(tn, tw,
@@ -502,19 +476,16 @@ struct InvPasses {
 
 // Forward transform.  In: x[q][e] = coefficient tid + T e of polynomial q, |x| <= 1.01 * 2^29.
 // Out: x[q][e] = slot E tid + e, |x| < 3.95 * 2^29.  `lds` must hold NP * m words.
-template <int LOGM, int NP, int LOGE, class F = NoHook>
+template <int LOGM, int NP, int LOGE>
 __device__ __forceinline__ void ntt_forward(int32_t (&x)[NP][1 << LOGE], uint32_t *lds,
-                                            const int32_t *tw, int tid, const Mod &md,
-                                            const F &before_last = F()) {
+                                            const int32_t *tw, int tid, const Mod &md) {
     using G = NttGeom<LOGM, LOGE>;
     constexpr int BLO = G::RHO == 0 ? 0 : LOGE - G::RHO;
     int32_t t[(1 << LOGE) - 1];
     load_twiddles<LOGM, LOGE, G::STOP, LOGE - 1, BLO>(t, tw, 0u);
     fwd_stages<NP, LOGE, LOGE - 1, BLO>(x, t, md);
     if constexpr (G::SFIRST >= 0)
-        FwdPasses<LOGM, NP, LOGE, G::STOP, G::SFIRST>::run(x, lds, tw, tid, md, before_last);
-    else
-        before_last();
+        FwdPasses<LOGM, NP, LOGE, G::STOP, G::SFIRST>::run(x, lds, tw, tid, md);
 }
 
 // Inverse transform (unscaled).  In: slots E tid + e, |x| <= 0.75 * 2^29 (WIDE0: polynomial 0 up

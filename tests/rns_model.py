@@ -255,13 +255,13 @@ def inv_red_mask(loge, B, bfirst, bhi, lastred):
 
 
 def fwd_vec4(logm):
-    """ntt.h SGFHE_FWD_VEC4: forward passes with per-lane twiddles take the radix-4 form except where
+    """ntt.h fwd_vec4: forward passes with per-lane twiddles take the radix-4 form except where
     k_extprod would spill registers (m = 4096, 16384)."""
     return logm not in (12, 14)
 
 
 def inv_r4(logm):
-    """ntt.h SGFHE_INV_R4: the inverse keeps its radix-2 form at m = 4096."""
+    """ntt.h inv_r4: the inverse keeps its radix-2 form at m = 4096."""
     return logm != 12
 
 

@@ -92,7 +92,7 @@ def test_host_buffers_run_at_the_device_resident_rate():
     (round 3's whole-buffer copies ran at 0.989 of the device-resident rate, unpipelined pageable copies at
     0.95): one attempt, no retry.  The rate itself -- 0.996-0.998 over 20
     alternating steps -- is bench.py's `host_io.vs_device_resident` in every committed bench line and
-    tools/io_variants.py (profiles/r04_exp_io_variants.txt): three steps here cannot resolve 0.3 %."""
+    profiles/r04_exp_io_variants.txt: three steps here cannot resolve 0.3 %."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
                         "--full", "--no-cpu-baseline", "--no-isolated", "--no-live-counters"], env=env, capture_output=True,

@@ -582,6 +582,10 @@ void launch_crt_lean_t(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32
         return;
     }
     const dim3 grid((total / 4 + 255) / 256), block(256);
+    if (NP == 5 && c->h_lean.p87) {
+        hipLaunchKernelGGL((k_crt_lean<5, 3, true>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm);
+        return;
+    }
     switch (c->h_lean.nl) {
     case 2: hipLaunchKernelGGL((k_crt_lean<NP, 2>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm); break;
     case 3: hipLaunchKernelGGL((k_crt_lean<NP, 3>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm); break;
@@ -1266,6 +1270,17 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
             // estimate's width (tests/rns_model.py CrtLean.digits asserts both).  Reference
             // parameter sets have three limbs and B ~ sqrt(Q); others fall back to k_crt_acc.
             c->lean_rnd_ok = (NL >= 3 || ((7 * B) >> 32) == 0 || K.B1 == 0) && B * B <= (Q << 27);
+            // crt_lean87_one: five primes, Q of 87 bits, B of 44 bits (Params(1024)); its register
+            // widths and quotient estimates hold for every such Q and B
+            // (tests/test_crt_lean87_model.py)
+            if (NPR == 5 && nq == 87 && nb == 44) {
+                const u128 mq = ((u128)1 << 122) / Q, mb = ((u128)1 << 96) / B;
+                K.mqw0 = (uint32_t)mq;
+                K.mqw1 = (uint32_t)(mq >> 32);
+                K.mbw0 = (uint32_t)mb;
+                K.mbw1 = (uint32_t)(mb >> 32);
+                K.p87 = 1;
+            }
         }
     }
 
@@ -2810,6 +2825,8 @@ int32_t sgfhe_kernel_names(const sgfhe_ctx *c, char *extprod, size_t extprod_cap
     const int le = c->logm <= EXT_LE3_MAX ? 3 : LOGE;
     snprintf(extprod, extprod_cap, "k_extprod<%d, %d, %s>", c->logm, le, wide ? "true" : "false");
     // the selection of launch_crt_raw for the k-loop's mode
+    // (k_crt_lean<5, 3, true>, the crt_lean87_one instantiation, reports as k_crt_lean<5, 3>: same
+    // function, same memory side)
     if (!c->rnd && c->h_lean.nl)
         snprintf(crt, crt_cap, "k_crt_lean<%u, %u>", c->npr, c->h_lean.nl);
     else if (c->rnd && c->lean_rnd_ok)

@@ -762,6 +762,9 @@ struct CrtLean {
     uint32_t nl;              // limbs in use (2, 3 or 4); 0 = parameter set outside this kernel's bounds
     uint32_t cR[4];           // randomised flatten: (-2 xmax (1 + B)) mod Q in 29-bit limbs
     uint32_t xm2lo, xm2hi;    //   2 xmax
+    uint32_t p87;             // 1: crt_lean87_one applies (five primes, Q of 87 bits, B of 44 bits)
+    uint32_t mqw0, mqw1;      //   floor(2^122 / Q)
+    uint32_t mbw0, mbw1;      //   floor(2^96 / B)
 };
 
 // (x m) >> 64 for x < 2^63.5 and m = m1 2^32 + m0 with m1 <= 2^20
@@ -850,7 +853,116 @@ __device__ __forceinline__ void crt_lean_one(const uint32_t (&y)[NP], uint64_t l
     hi_n = hq;
 }
 
-template <int NP, int NL>
+// crt_lean_one at five primes, Q of 87 bits and B of 44 bits (Params(1024)).  There the three 29-bit
+// limbs cover Q exactly (a = 0, t2 + sB = 31), so every shift of the recombination is a constant and
+// both quotients are read from 32-bit words: no 64-bit shift, no 64-bit compare.
+//   limb sums as crt_lean_one, hi_old B as h0 B0 + h0 B1 2^29 + h1 (8 B0) 2^29 + h1 (8 B1) 2^58
+//   U = L0 + lo(L1) 2^29,  X = L2 + 8 hi(L1):  S = U + 2^58 X exactly, U and X below 2^64
+//   q = (X mq) >> 64 with mq = floor(2^122 / Q) <= 2^36:  floor(S / Q) or one less
+//   x = S - q Q modulo 2^96 in 32-bit words, in [0, 2 Q): minus Q unless that borrows
+//   hq = ((x >> 32) mb) >> 64 with mb = floor(2^96 / B) <= 2^53:  floor(x / B) or one less
+//   lo = x - hq B modulo 2^64, in [0, 2 B): minus B, and hq + 1, unless that borrows.
+// The two corrections are subtract-with-borrow chains whose borrow-out selects.  Same digits as
+// crt_lean_one; tests/test_crt_lean87_model.py restates it with every register width checked and
+// both estimates checked against the exact quotients.
+__device__ __forceinline__ uint32_t sub_borrow(uint32_t a, uint32_t b, uint32_t bin, uint32_t &bout) {
+    uint32_t r;
+    bout = __builtin_sub_overflow(a, b, &r);
+    bout |= __builtin_sub_overflow(r, bin, &r);
+    return r;
+}
+
+// (x m) >> 64 for x < 2^64 and m = m1 2^32 + m0 with m1 < 2^24, less than one below the exact value:
+// mulhi64_lean with its three multiply-adds in this order (left to itself the compiler reassociates
+// them into four instructions and a move).  m0 and m1 are wave-uniform (SGPRs).
+__device__ __forceinline__ uint64_t mad_u64_u32_vs(uint32_t a, uint32_t b, uint64_t c) {
+    uint64_t r, cy;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(cy) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ uint64_t mulhi64_87(uint64_t x, uint32_t m0, uint32_t m1) {
+    const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32);
+    const uint64_t t1 = mad_u64_u32_vs(x0, m1, __umulhi(x0, m0));
+    const uint64_t t2 = mad_u64_u32_vs(x1, m0, t1);
+    return mad_u64_u32_vs(x1, m1, t2 >> 32);
+}
+
+// Q and B in 32-bit words as vector registers (one copy per thread, not one per use): the borrow
+// chains take them as their second operand, which has to be a VGPR.
+struct Lean87W {
+    uint32_t Q0, Q1, Q2, B0, B1;
+};
+
+template <int NP>
+__device__ __forceinline__ void crt_lean87_one(const uint32_t (&y)[NP], uint64_t lo_o, uint32_t h0,
+                                               uint32_t h1, const CrtLean *__restrict__ K, const Lean87W &W,
+                                               uint64_t &lo_n, uint64_t &hi_n) {
+    uint64_t acc = 0;
+#pragma unroll
+    for (int q = 0; q < NP; q++) acc += (uint64_t)y[q] * K->w[q];
+    const uint32_t alpha = (uint32_t)(acc >> 32) >> 26;
+    const uint32_t ylast = y[NP - 1] - K->hoff;
+    uint64_t L0 = lo_o + (uint64_t)h0 * K->B0;
+    uint64_t L1 = (uint64_t)h0 * K->B1 + (uint64_t)h1 * (K->B0 << 3);
+    uint64_t L2 = (uint64_t)h1 * (K->B1 << 3);
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+        const uint32_t yq = q == NP - 1 ? ylast : y[q];
+        L0 += (uint64_t)yq * K->c[q][0];
+        L1 += (uint64_t)yq * K->c[q][1];
+        L2 += (uint64_t)yq * K->c[q][2];
+    }
+    L0 += (uint64_t)alpha * K->cMn[0];
+    L1 += (uint64_t)alpha * K->cMn[1];
+    L2 += (uint64_t)alpha * K->cMn[2];
+    // (the multipliers 2^29 and 8 are hidden from the optimiser, which would otherwise turn these two
+    // multiply-adds into 64-bit shifts, masks and adds)
+    uint32_t m29 = 1u << 29, m3 = 8;
+    asm volatile("" : "+s"(m29), "+s"(m3));
+    const uint64_t U = (uint64_t)(uint32_t)L1 * m29 + L0;
+    const uint64_t X = (uint64_t)(uint32_t)(L1 >> 32) * m3 + L2;
+    // quotient by Q and q Q modulo 2^96
+    const uint64_t q = mulhi64_87(X, K->mqw0, K->mqw1);
+    const uint32_t qa = (uint32_t)q, qb = (uint32_t)(q >> 32);
+    const uint64_t p0 = (uint64_t)qa * K->Qw[0];
+    const uint64_t p1 = (uint64_t)qa * K->Qw[1] + (p0 >> 32);
+    const uint32_t p2 = (uint32_t)(p1 >> 32) + qa * K->Qw[2] + qb * K->Qw[1];
+    const uint64_t p12 = ((((uint64_t)p2 << 32) | (uint32_t)p1)) + (uint64_t)qb * K->Qw[0];
+    // x = S - q Q:  S = U + 2^58 X in words (U.lo, U.hi + (X << 26) mod 2^64)
+    const uint64_t s12 = (U >> 32) + (X << 26);
+    uint32_t br;
+    uint32_t x0 = sub_borrow((uint32_t)U, (uint32_t)p0, 0, br);
+    uint32_t x1 = sub_borrow((uint32_t)s12, (uint32_t)p12, br, br);
+    uint32_t x2 = (uint32_t)(s12 >> 32) - (uint32_t)(p12 >> 32) - br;
+    {   // in [0, 2 Q): subtract Q when that does not borrow
+        uint32_t b;
+        const uint32_t d0 = sub_borrow(x0, W.Q0, 0, b);
+        const uint32_t d1 = sub_borrow(x1, W.Q1, b, b);
+        const uint32_t d2 = sub_borrow(x2, W.Q2, b, b);
+        x0 = b ? x0 : d0;
+        x1 = b ? x1 : d1;
+        x2 = b ? x2 : d2;
+    }
+    // digits
+    uint64_t hq = mulhi64_87(((uint64_t)x2 << 32) | x1, K->mbw0, K->mbw1);
+    const uint32_t g0 = (uint32_t)hq, g1 = (uint32_t)(hq >> 32);
+    const uint64_t pb = (uint64_t)g0 * K->Bw0;
+    const uint32_t pbh = (uint32_t)(pb >> 32) + g0 * K->Bw1 + g1 * K->Bw0;
+    uint32_t b;
+    uint32_t lo0 = sub_borrow(x0, (uint32_t)pb, 0, b);
+    uint32_t lo1 = x1 - pbh - b;
+    {   // in [0, 2 B): subtract B when that does not borrow
+        const uint32_t d0 = sub_borrow(lo0, W.B0, 0, b);
+        const uint32_t d1 = sub_borrow(lo1, W.B1, b, b);
+        lo0 = b ? lo0 : d0;
+        lo1 = b ? lo1 : d1;
+        hq += 1u - b;
+    }
+    lo_n = ((uint64_t)lo1 << 32) | lo0;
+    hi_n = hq;
+}
+
+template <int NP, int NL, bool P87 = false>
 __global__ void __launch_bounds__(256)
 k_crt_lean(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
            const CrtLean *__restrict__ K, uint32_t quads, uint32_t logm) {
@@ -884,14 +996,22 @@ k_crt_lean(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     const uint32_t l0w[4] = {l0.x, l0.y, l0.z, l0.w}, l1w[4] = {l1.x, l1.y, l1.z, l1.w};
     const uint32_t h0w[4] = {h0.x & 0xFFFFu, h0.x >> 16, h0.y & 0xFFFFu, h0.y >> 16};
     const uint32_t h1w[4] = {h1.x & 0xFFFFu, h1.x >> 16, h1.y & 0xFFFFu, h1.y >> 16};
+    Lean87W W{};
+    if constexpr (P87) {
+        W = Lean87W{K->Qw[0], K->Qw[1], K->Qw[2], K->Bw0, K->Bw1};
+        asm volatile("" : "+v"(W.Q0), "+v"(W.Q1), "+v"(W.Q2), "+v"(W.B0), "+v"(W.B1));
+    }
     uint64_t nlo[4], nhi[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         uint32_t y[NP];
 #pragma unroll
         for (int q = 0; q < NP; q++) y[q] = j == 0 ? yv[q].x : j == 1 ? yv[q].y : j == 2 ? yv[q].z : yv[q].w;
-        crt_lean_one<NP, NL>(y, l0w[j] | ((uint64_t)h0w[j] << 32), l1w[j] | ((uint64_t)h1w[j] << 32), K,
-                             nlo[j], nhi[j]);
+        if constexpr (P87)
+            crt_lean87_one<NP>(y, l0w[j] | ((uint64_t)h0w[j] << 32), l1w[j], h1w[j], K, W, nlo[j], nhi[j]);
+        else
+            crt_lean_one<NP, NL>(y, l0w[j] | ((uint64_t)h0w[j] << 32), l1w[j] | ((uint64_t)h1w[j] << 32), K,
+                                 nlo[j], nhi[j]);
     }
     st_off<uint4>(dig, ol, make_uint4((uint32_t)nlo[0], (uint32_t)nlo[1], (uint32_t)nlo[2], (uint32_t)nlo[3]));
     st_off<uint4>(dig, ol + 4u * M,

@@ -265,8 +265,9 @@ int32_t sgfhe_bootstrap_batch_device(sgfhe_ctx *ctx, const uint64_t *a1, const u
                                      uint64_t *out, uint32_t flags, void *stream);
 int32_t sgfhe_sync(sgfhe_ctx *ctx);
 /* Frees the staging buffers sgfhe_bootstrap_batch keeps on the ctx (device and page-locked host
- * memory, sized by the largest batch seen), and the wire table and call staging of sgfhe_circuit_run;
- * the next call allocates them again. */
+ * memory, sized by the largest batch seen), the wire table and call staging of sgfhe_circuit_run[_ct],
+ * and the work buffers of the packing path (sgfhe_pack_encrypted_bits, the pack stage of
+ * sgfhe_circuit_run_ct); the next call allocates them again. */
 int32_t sgfhe_release_host_staging(sgfhe_ctx *ctx);
 
 /*
@@ -439,6 +440,39 @@ int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
 int32_t sgfhe_circuit_run(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
                           uint64_t *out);
+/*
+ * The same run with RLWE ciphertexts at both ends -- the reference's user flow (docs/src/manual.md:119-121,190-192,
+ * test/api.test.jl:86-108): split_ciphertext (src/fhe.jl:287-290) of every input and pack_encrypted_bits
+ * (src/fhe.jl:660-696) of every output done on the device inside the one queued run.  A ciphertext of n bits is one
+ * wire over n instances:
+ *   in_a, in_b   : [n_inputs][blocks][N] uint64 in [0, r), rlwe.a / rlwe.b of one ciphertext per (input, block);
+ *                  N = n (PackedCiphertext, what encrypt yields) or N = m (Ciphertext, what packing yields), one N
+ *                  per call.  May be NULL when n_inputs is 0.
+ *   instances    = blocks * n; instance block * n + i is bit i (0-based) of that block's ciphertext, the LWE
+ *                  split_ciphertext(ct)[i + 1] (the bytes of sgfhe_host_split_ciphertext)
+ *   out_w, out_v : [n_outputs][blocks][m] uint64 in [0, r): for every (output, block) the Ciphertext
+ *                  pack_encrypted_bits makes of that output wire's n LWEs of the block.  Both or neither.
+ *   out_lwe      : optional, [n_outputs][blocks * n][n + 1]: exactly what sgfhe_circuit_run returns.
+ * At least one of the two output forms must be requested.  Host pointers; synchronous; the ctx is locked for the
+ * whole run and the coalescer is not used.  blocks = 0 does nothing.  Before anything is queued or written:
+ * SGFHE_ERR_INVALID_ARG for NULL or inconsistent pointers, N neither n nor m, or blocks * n beyond the limits of
+ * sgfhe_circuit_run; SGFHE_ERR_NO_KEY; SGFHE_ERR_UNSUPPORTED for packed output where sgfhe_pack_encrypted_bits is
+ * unsupported (the exactness bound of the RNS primes).
+ * The run: the ciphertexts go up as they are (16 KB each at Params(1024), against 8.4 MB of LWEs); one split
+ * kernel writes extract() of every bit of every input something reads into its slot of the wire table; the levels
+ * run as in sgfhe_circuit_run; the pack stage takes the ciphertexts q = output * blocks + block in ascending
+ * order, max(1, SGFHE_CIRCUIT_CALL_ROWS / n) at a time (8 at Params(1024)), each such call being one
+ * sgfhe_pack_encrypted_bits(count = its ciphertexts) whose bootstrap inputs are gathered from the wire table
+ * (NOT, constant and pass-through outputs included); (w, v) of all ciphertexts come down in one copy each.  No host
+ * synchronisation before the final download.
+ * Randomised flatten: the level calls take the next call numbers of the ctx's draw stream as in
+ * sgfhe_circuit_run; the pack calls follow, one call number each, in ascending q; within a pack call ciphertext
+ * `ct` and bit `j` draw as in sgfhe_pack_encrypted_bits (bootstrap ct * n + j of the call; the flatten of as_i with
+ * y = 2^31 | i, z = ct).  out_lwe consumes nothing.  So the whole run equals, on one stream: sgfhe_circuit_run, then
+ * sgfhe_pack_encrypted_bits in groups of that many ciphertexts.  A run without out_w consumes the level calls only.
+ */
+int32_t sgfhe_circuit_run_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, const uint64_t *in_a,
+                             const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe);
 
 /*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled

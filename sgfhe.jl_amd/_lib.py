@@ -143,6 +143,7 @@ def lib():
         "sgfhe_circuit_info": (i32, [vp, _u64p]),
         "sgfhe_circuit_destroy": (i32, [vp]),
         "sgfhe_circuit_run": (i32, [vp, vp, sz, vp, vp]),
+        "sgfhe_circuit_run_ct": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -166,4 +167,4 @@ EXPORTED_SYMBOLS = (
     "sgfhe_host_decrypt_lwe", "sgfhe_host_decrypt_rlwe", "sgfhe_host_public_key",
     "sgfhe_host_encrypt_public", "sgfhe_host_pack_public", "sgfhe_host_normalize_public", "sgfhe_timing_enable", "sgfhe_timing_read",
     "sgfhe_kernel_names", "sgfhe_release_host_staging", "sgfhe_circuit_create", "sgfhe_circuit_info",
-    "sgfhe_circuit_destroy", "sgfhe_circuit_run")
+    "sgfhe_circuit_destroy", "sgfhe_circuit_run", "sgfhe_circuit_run_ct")

@@ -18,7 +18,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .scheme import LWE, EncryptedBit, _set_flatten_mode
+from .scheme import LWE, RLWE, Ciphertext, EncryptedBit, PackedCiphertext, _set_flatten_mode, split_ciphertext_array
 
 FALSE_ID = 0x7FFFFFFF      # SGFHE_CIRCUIT_FALSE
 NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
@@ -218,6 +218,70 @@ def replay_levels(circuit, inputs, r, boot):
             for w in range(3):
                 wires[circuit.n_inputs + 3 * g + w] = res[k * inst:(k + 1) * inst, w]
     return np.stack([val(ref) for ref in circuit.outputs]) if circuit.outputs else np.zeros((0, inst, row), np.uint64)
+
+
+def pack_calls(n):
+    """Ciphertexts per pack call of sgfhe_circuit_run_ct: max(1, CALL_ROWS / n)."""
+    return max(1, CALL_ROWS // n)
+
+
+def replay_ct(circuit, a, b, params, boot, pack):
+    """sgfhe_circuit_run_ct composed on the host: a, b [n_inputs][blocks][N] (N = n or m) -> ((w, v), lwe) with
+    w, v [n_outputs][blocks][m] and lwe [n_outputs][blocks * n][n + 1].  The inputs are split with
+    scheme.split_ciphertext_array (instance block * n + i = bit i of the block's ciphertext), the levels run
+    through replay_levels and `boot`, and the ciphertexts q = output * blocks + block are packed in ascending
+    order, pack_calls(n) at a time, by `pack(call, a, b)` (a [count][n][n], b [count][n] -> (w, v), each
+    [count][m]); `call` goes on counting after the levels' calls.  A checking and measuring aid."""
+    n, m = params.n, params.m
+    a = np.asarray(a, dtype=np.uint64)
+    b = np.asarray(b, dtype=np.uint64)
+    blocks = a.shape[1]
+    inputs = split_ciphertext_array(a, b, n, params.r).reshape(circuit.n_inputs, blocks * n, n + 1)
+    calls = [0]
+
+    def counted(call, *args):
+        calls[0] = call + 1
+        return boot(call, *args)
+
+    lwe = replay_levels(circuit, inputs, params.r, counted)
+    groups = lwe.reshape(circuit.n_outputs * blocks, n, n + 1)
+    w = np.zeros((len(groups), m), dtype=np.uint64)
+    v = np.zeros((len(groups), m), dtype=np.uint64)
+    cpc, call = pack_calls(n), calls[0]
+    for q0 in range(0, len(groups), cpc):
+        g = groups[q0:q0 + cpc]
+        w[q0:q0 + cpc], v[q0:q0 + cpc] = pack(call, np.ascontiguousarray(g[:, :, :n]), np.ascontiguousarray(g[:, :, n]))
+        call += 1
+    shape = (circuit.n_outputs, blocks, m)
+    return (w.reshape(shape), v.reshape(shape)), lwe
+
+
+def evaluate_circuit_ct(bkey, rng, circuit, cts):
+    """The circuit on RLWE ciphertexts, the reference's user flow (encrypt -> split_ciphertext -> gates ->
+    pack_encrypted_bits -> decrypt) with the split and the pack on the device (Engine.circuit_run_ct).
+    cts: [n_inputs][blocks] of PackedCiphertext or Ciphertext (all of one kind); bit i of a ciphertext is
+    instance i of its block.  rng as in evaluate_circuit.  Returns [n_outputs][blocks] of Ciphertext."""
+    p = bkey.params
+    if len(cts) != circuit.n_inputs:
+        raise ValueError("evaluate_circuit_ct: one row of ciphertexts per input wire")
+    blocks = len(cts[0]) if cts else 0
+    flat = [ct for row in cts for ct in row]
+    if any(len(row) != blocks for row in cts):
+        raise ValueError("ragged inputs: every input needs one ciphertext per block")
+    if not flat:
+        raise ValueError("evaluate_circuit_ct: at least one input ciphertext is needed (it fixes the blocks)")
+    kind = type(flat[0])
+    if kind not in (PackedCiphertext, Ciphertext) or any(type(ct) is not kind for ct in flat):
+        raise TypeError("evaluate_circuit_ct: PackedCiphertext or Ciphertext, all of one kind")
+    N = p.n if kind is PackedCiphertext else p.m
+    a = np.stack([np.asarray(ct.rlwe.a, dtype=np.uint64) for ct in flat]).reshape(circuit.n_inputs, blocks, -1)
+    b = np.stack([np.asarray(ct.rlwe.b, dtype=np.uint64) for ct in flat]).reshape(circuit.n_inputs, blocks, -1)
+    if a.shape[2] != N or b.shape[2] != N:
+        raise ValueError("evaluate_circuit_ct: ciphertext polynomials of length %d expected" % N)
+    with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
+        _set_flatten_mode(bkey, rng)
+        w, v = bkey.engine.circuit_run_ct(circuit, a, b)
+    return [[Ciphertext(p, RLWE(w[o, t], v[o, t])) for t in range(blocks)] for o in range(circuit.n_outputs)]
 
 
 def evaluate_circuit(bkey, rng, circuit, inputs):

@@ -226,6 +226,16 @@ struct sgfhe_ctx {
     uint64_t *circ_wires = nullptr, *circ_stage = nullptr, *circ_out = nullptr;
     uint32_t *circ_tab = nullptr;
     size_t circ_wires_words = 0, circ_stage_words = 0, circ_out_words = 0, circ_tab_words = 0;
+    // sgfhe_circuit_run_ct: the uploaded input ciphertexts [a | b], each [n_inputs][blocks][N]
+    uint64_t *circ_ct = nullptr;
+    size_t circ_ct_words = 0;
+    // work buffers of the packing path (pack_device), shared by sgfhe_pack_encrypted_bits and the pack stage
+    // of sgfhe_circuit_run_ct, grown and freed like the circuit buffers: one call's bootstrap inputs
+    // [a1 | a2 | b1 | b2], its un-reduced results, the flattened as_i, the group sums, and (w | v)
+    uint64_t *pack_lwe = nullptr, *pack_pdig = nullptr, *pack_wv = nullptr;
+    ulonglong2 *pack_raw = nullptr;
+    uint32_t *pack_yg = nullptr;
+    size_t pack_lwe_words = 0, pack_pdig_words = 0, pack_wv_words = 0, pack_raw_words = 0, pack_yg_words = 0;
     // timing
     bool timing = false;
     struct EvTriple { hipEvent_t e0, e1, e2; };  // ext = e0 -> e1, crt = e1 -> e2
@@ -1777,6 +1787,35 @@ static void free_circuit_buffers(sgfhe_ctx *c) {
     c->circ_wires = c->circ_stage = c->circ_out = nullptr;
     c->circ_tab = nullptr;
     c->circ_wires_words = c->circ_stage_words = c->circ_out_words = c->circ_tab_words = 0;
+    if (c->circ_ct) (void)hipFree(c->circ_ct);
+    c->circ_ct = nullptr;
+    c->circ_ct_words = 0;
+    if (c->pack_lwe) (void)hipFree(c->pack_lwe);
+    if (c->pack_raw) (void)hipFree(c->pack_raw);
+    if (c->pack_pdig) (void)hipFree(c->pack_pdig);
+    if (c->pack_yg) (void)hipFree(c->pack_yg);
+    if (c->pack_wv) (void)hipFree(c->pack_wv);
+    c->pack_lwe = c->pack_pdig = c->pack_wv = nullptr;
+    c->pack_raw = nullptr;
+    c->pack_yg = nullptr;
+    c->pack_lwe_words = c->pack_pdig_words = c->pack_wv_words = c->pack_raw_words = c->pack_yg_words = 0;
+}
+
+// a device buffer of the ctx grown to at least `words` elements (its contents are not kept)
+extern "C++" template <typename T>
+static int32_t circ_grow(sgfhe_ctx *c, T *&buf, size_t &cap, size_t words) {
+    if (words <= cap) return SGFHE_OK;
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    if (hipMalloc(&buf, words * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run: hipMalloc of " + std::to_string(words * sizeof(T)) +
+                                          " bytes failed");
+    }
+    cap = words;
+    return SGFHE_OK;
 }
 
 int32_t sgfhe_ctx_destroy(sgfhe_ctx *c) {
@@ -2529,6 +2568,56 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, con
     return rc;
 }
 
+// The pack work buffers of the ctx for calls of at most `count` ciphertexts and `total` ciphertexts of
+// (w | v), in the ctx's present flatten mode; before anything is queued (nothing of the ctx in flight).
+static int32_t pack_grow(sgfhe_ctx *c, size_t count, size_t total) {
+    const size_t n = c->n, M = c->M, nb = count * n;
+    const uint32_t G = c->rnd ? c->pack_G_rnd : c->pack_G;
+    const size_t groups = n / G, len = c->rnd ? M : n;
+    int32_t rc;
+    if ((rc = circ_grow(c, c->pack_lwe, c->pack_lwe_words, 2 * nb * n + 2 * nb))) return rc;
+    if ((rc = circ_grow(c, c->pack_raw, c->pack_raw_words, nb * 3 * (n + 1)))) return rc;
+    if ((rc = circ_grow(c, c->pack_pdig, c->pack_pdig_words, count * n * 2 * len))) return rc;
+    if ((rc = circ_grow(c, c->pack_yg, c->pack_yg_words, count * groups * 2 * c->npr * M))) return rc;
+    return circ_grow(c, c->pack_wv, c->pack_wv_words, 2 * total * M);
+}
+
+// pack_encrypted_bits (fhe.jl:660-696) of `count` groups of n LWEs resident on the device, queued on `st`:
+// the count * n bootstraps of (a1, b1) = trivial encryption of 1 with (a2, b2) = the bits (one call of the
+// ctx's draw stream), the flatten of every as_i, the half-width external products and the finish into
+// d_w / d_v [count][m].  The caller has grown the work buffers (pack_grow) and checked pack_G.
+static int32_t pack_device(sgfhe_ctx *c, const uint64_t *d_a1, const uint64_t *d_b1, const uint64_t *d_a2,
+                           const uint64_t *d_b2, size_t count, uint64_t *d_w, uint64_t *d_v, hipStream_t st) {
+    const size_t n = c->n, M = c->M, nb = count * n;
+    // rng != nothing: the n bootstraps and the flatten of every as_i (all m coefficients of the
+    // resized polynomial, utils.jl:253-264) draw from the ctx's ChaCha stream (fhe.jl:673,683-684)
+    const uint32_t mode = c->rnd ? MODE_RANDOM : 0u;
+    const uint32_t G = c->rnd ? c->pack_G_rnd : c->pack_G;
+    const uint32_t groups = (uint32_t)(n / G);
+    const size_t len = c->rnd ? M : n;  // stored coefficients per digit polynomial
+    int32_t rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, nb, (uint64_t *)c->pack_raw, SGFHE_FLAG_RAW_MODQ,
+                                  c->n, nullptr, st);
+    if (rc) return rc;
+    const RndArgs ra = {c->rnd_key, c->last_call, 0u, nullptr};
+    const size_t tf = count * n * len;
+    hipLaunchKernelGGL(k_pack_flatten, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, st, c->pack_raw,
+                       c->pack_pdig, c->d_crt, (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, mode, ra);
+    if ((rc = launch_shortprod(c, c->pack_pdig, c->pack_yg, (uint32_t)count, G, groups, mode, st))) return rc;
+    const size_t tw = count * M;
+    switch (c->npr) {
+#define X(NP)                                                                                     \
+    case NP:                                                                                      \
+        hipLaunchKernelGGL(k_pack_finish<NP>, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0,   \
+                           st, c->pack_yg, c->pack_raw, d_w, d_v, c->d_crt,                       \
+                           (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, groups);              \
+        break;
+        SGFHE_FOR_NPR(X)
+#undef X
+    }
+    HIPCHK(c, hipGetLastError());
+    return SGFHE_OK;
+}
+
 int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, size_t count,
                                   uint64_t *out_w, uint64_t *out_v) {
     if (!c || !a || !b || !out_w || !out_v) return SGFHE_ERR_INVALID_ARG;
@@ -2539,63 +2628,27 @@ int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_
     SGFHE_QUIESCE(c);
     const size_t n = c->n, M = c->M;
     const size_t nb = count * n;  // bootstraps
-    // rng != nothing: the n bootstraps and the flatten of every as_i (all m coefficients of the
-    // resized polynomial, utils.jl:253-264) draw from the ctx's ChaCha stream (fhe.jl:673,683-684)
-    const uint32_t mode = c->rnd ? MODE_RANDOM : 0u;
-    const uint32_t G = c->rnd ? c->pack_G_rnd : c->pack_G;
-    if (!G) return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
-    const uint32_t groups = (uint32_t)(n / G);
-    const size_t len = c->rnd ? M : n;  // stored coefficients per digit polynomial
-    uint64_t *d_lwe = nullptr, *d_pdig = nullptr, *d_wv = nullptr;
-    ulonglong2 *d_raw = nullptr;
-    uint32_t *d_yg = nullptr;
+    if (!(c->rnd ? c->pack_G_rnd : c->pack_G))
+        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
+    if (pack_grow(c, count, count)) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(hipErrorOutOfMemory));
     hipError_t e = hipSuccess;
     int32_t rc = SGFHE_OK;
     do {
         // [a1 = 0 | a2 | b1 = Dr | b2]: trivial encryption of 1 paired with every bit (fhe.jl:669-673)
-        if ((e = hipMalloc(&d_lwe, (2 * nb * n + 2 * nb) * 8))) break;
-        uint64_t *d_a1 = d_lwe, *d_a2 = d_lwe + nb * n, *d_b1 = d_a2 + nb * n, *d_b2 = d_b1 + nb;
-        if ((e = hipMalloc(&d_raw, nb * 3 * (n + 1) * 16))) break;
-        if ((e = hipMalloc(&d_pdig, count * n * 2 * len * 8))) break;
-        if ((e = hipMalloc(&d_yg, count * groups * 2 * c->npr * M * 4))) break;
-        if ((e = hipMalloc(&d_wv, 2 * count * M * 8))) break;
+        uint64_t *d_a1 = c->pack_lwe, *d_a2 = d_a1 + nb * n, *d_b1 = d_a2 + nb * n, *d_b2 = d_b1 + nb;
+        uint64_t *d_w = c->pack_wv, *d_v = d_w + count * M;
         if ((e = hipMemsetAsync(d_a1, 0, nb * n * 8, c->stream))) break;
         std::vector<uint64_t> ones(nb, c->par.r / 4);
         if ((e = hipMemcpyAsync(d_b1, ones.data(), nb * 8, hipMemcpyHostToDevice, c->stream))) break;
         if ((e = hipMemcpyAsync(d_a2, a, nb * n * 8, hipMemcpyHostToDevice, c->stream))) break;
         if ((e = hipMemcpyAsync(d_b2, b, nb * 8, hipMemcpyHostToDevice, c->stream))) break;
-        rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, nb, (uint64_t *)d_raw, SGFHE_FLAG_RAW_MODQ,
-                              c->n, nullptr, c->stream);
-        if (rc) break;
-        const RndArgs ra = {c->rnd_key, c->last_call, 0u, nullptr};
-        const size_t tf = count * n * len;
-        hipLaunchKernelGGL(k_pack_flatten, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, c->stream,
-                           d_raw, d_pdig, c->d_crt, (uint32_t)count, (uint32_t)n, (uint32_t)c->logm,
-                           mode, ra);
-        rc = launch_shortprod(c, d_pdig, d_yg, (uint32_t)count, G, groups, mode, c->stream);
-        if (rc) break;
-        const size_t tw = count * M;
-        switch (c->npr) {
-#define X(NP)                                                                                     \
-    case NP:                                                                                      \
-        hipLaunchKernelGGL(k_pack_finish<NP>, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0,   \
-                           c->stream, d_yg, d_raw, d_wv, d_wv + count * M, c->d_crt,              \
-                           (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, groups);              \
-        break;
-            SGFHE_FOR_NPR(X)
-#undef X
-        }
-        if ((e = hipGetLastError())) break;
-        if ((e = hipMemcpyAsync(out_w, d_wv, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
-        if ((e = hipMemcpyAsync(out_v, d_wv + count * M, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
+        if ((rc = pack_device(c, d_a1, d_b1, d_a2, d_b2, count, d_w, d_v, c->stream))) break;
+        if ((e = hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
+        if ((e = hipMemcpyAsync(out_v, d_v, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
         e = hipStreamSynchronize(c->stream);
     } while (0);
     if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    if (d_lwe) (void)hipFree(d_lwe);
-    if (d_raw) (void)hipFree(d_raw);
-    if (d_pdig) (void)hipFree(d_pdig);
-    if (d_yg) (void)hipFree(d_yg);
-    if (d_wv) (void)hipFree(d_wv);
+    if (rc) (void)hipStreamSynchronize(c->stream);   // whatever was queued finishes before the buffers are touched again
     return rc;
 }
 
@@ -2915,26 +2968,21 @@ int32_t sgfhe_circuit_destroy(sgfhe_circuit *c) {
     return SGFHE_OK;
 }
 
-// a device buffer of the ctx grown to at least `words` elements (its contents are not kept)
-extern "C++" template <typename T>
-static int32_t circ_grow(sgfhe_ctx *c, T *&buf, size_t &cap, size_t words) {
-    if (words <= cap) return SGFHE_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    if (hipMalloc(&buf, words * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run: hipMalloc of " + std::to_string(words * sizeof(T)) +
-                                          " bytes failed");
-    }
-    cap = words;
-    return SGFHE_OK;
-}
+// ciphertext form of a run (sgfhe_circuit_run_ct): inputs split on the device, outputs packed on the device
+struct CircuitCt {
+    const uint64_t *in_a, *in_b;   // [n_inputs][blocks][N]
+    size_t blocks, N;
+    uint64_t *out_w, *out_v;       // [n_outputs][blocks][m], or both NULL
+};
 
+// ciphertexts per pack call of sgfhe_circuit_run_ct
+static size_t circuit_pack_cpc(const sgfhe_ctx *c) { return std::max<size_t>(1, SGFHE_CIRCUIT_CALL_ROWS / c->n); }
+
+// `in` / `out`: the LWE form ([wire][instances][n + 1]); with `ct` the inputs come from ct->in_a / in_b instead and
+// `out` is optional.
 static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in,
-                                  uint64_t *out) {
-    const size_t n = c->n, row = n + 1;
+                                  uint64_t *out, const CircuitCt *ct) {
+    const size_t n = c->n, row = n + 1, M = c->M;
     const uint32_t inst = (uint32_t)instances;
     const uint64_t r = c->par.r;
     hipStream_t st = c->stream;
@@ -2943,31 +2991,63 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         const uint64_t rows = P.level_rows(L, instances);
         max_rows = std::max(max_rows, rows < SGFHE_CIRCUIT_CALL_ROWS ? rows : (uint64_t)SGFHE_CIRCUIT_CALL_ROWS);
     }
+    const bool pack = ct && ct->out_w;
+    const size_t n_ct = pack ? (size_t)P.n_outputs * ct->blocks : 0;   // ciphertext q = output * blocks + block
+    const size_t cpc = std::min(circuit_pack_cpc(c), n_ct);             // ciphertexts of the largest pack call
+    const size_t ct_words = ct ? (size_t)P.n_inputs * ct->blocks * ct->N : 0;
     // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller)
-    const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size();
+    const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() +
+                             (ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0);
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, c->circ_wires_words, (size_t)P.slots * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_stage, c->circ_stage_words, (size_t)max_rows * 5 * row))) return rc;
-    if ((rc = circ_grow(c, c->circ_out, c->circ_out_words, (size_t)P.n_outputs * instances * row))) return rc;
+    if (out && (rc = circ_grow(c, c->circ_out, c->circ_out_words, (size_t)P.n_outputs * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_tab, c->circ_tab_words, tab_words))) return rc;
-    if (max_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
-                      // then a no-op and never waits on the host between levels)
+    if ((rc = circ_grow(c, c->circ_ct, c->circ_ct_words, 2 * ct_words))) return rc;
+    if (pack && (rc = pack_grow(c, cpc, n_ct))) return rc;
+    const uint64_t work_rows = std::max<uint64_t>(max_rows, cpc * n);
+    if (work_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
+                       // then a no-op and never waits on the host between levels)
         const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
-        if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(max_rows, chunk0))))) return rc;
+        if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(work_rows, chunk0))))) return rc;
     }
     uint32_t *d_in_ref = c->circ_tab, *d_out_slot = d_in_ref + P.in_ref.size(), *d_out_ref = d_out_slot + P.out_slot.size();
+    uint32_t *d_in_slot = d_out_ref + P.out_ref.size(), *d_pack_ref = d_in_slot + P.input_slot.size();
     HIPCHK(c, hipMemcpyAsync(d_in_ref, P.in_ref.data(), P.in_ref.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_slot, P.out_slot.data(), P.out_slot.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_ref, P.out_ref.data(), P.out_ref.size() * 4, hipMemcpyHostToDevice, st));
-    // inputs straight into their slots; runs of consecutive inputs in consecutive slots as one copy
-    const size_t in_words = instances * row;
-    for (uint32_t i = 0; i < P.n_inputs;) {
-        if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
-        uint32_t k = i + 1;
-        while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
-        HIPCHK(c, hipMemcpyAsync(c->circ_wires + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
-                                 (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
-        i = k;
+    std::vector<uint32_t> pack_ref;   // (outlives the asynchronous copy: the run ends in a synchronisation)
+    if (ct) {
+        // the ciphertexts as they are, and extract() of every bit into the slot of its input wire
+        if (P.n_inputs) {
+            HIPCHK(c, hipMemcpyAsync(d_in_slot, P.input_slot.data(), P.input_slot.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(c->circ_ct, ct->in_a, ct_words * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(c->circ_ct + ct_words, ct->in_b, ct_words * 8, hipMemcpyHostToDevice, st));
+            const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
+            hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(P.n_inputs * ct->blocks * tiles)), dim3(256),
+                               (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct, c->circ_ct + ct_words, d_in_slot,
+                               c->circ_wires, (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (pack) {   // node table of the pack calls: (TRUE, output o), the pair of fhe.jl:669-673
+            pack_ref.resize(2 * P.out_ref.size());
+            for (size_t o = 0; o < P.out_ref.size(); o++) {
+                pack_ref[2 * o] = CIRC_FALSE | CIRC_NOT;
+                pack_ref[2 * o + 1] = P.out_ref[o];
+            }
+            HIPCHK(c, hipMemcpyAsync(d_pack_ref, pack_ref.data(), pack_ref.size() * 4, hipMemcpyHostToDevice, st));
+        }
+    } else {
+        // inputs straight into their slots; runs of consecutive inputs in consecutive slots as one copy
+        const size_t in_words = instances * row;
+        for (uint32_t i = 0; i < P.n_inputs;) {
+            if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
+            uint32_t k = i + 1;
+            while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
+            HIPCHK(c, hipMemcpyAsync(c->circ_wires + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
+                                     (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
+            i = k;
+        }
     }
     uint64_t *a1 = c->circ_stage, *a2 = a1 + max_rows * n, *b1 = a2 + max_rows * n, *b2 = b1 + max_rows,
              *res = b2 + max_rows;
@@ -2987,12 +3067,30 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             HIPCHK(c, hipGetLastError());
         }
     }
-    const size_t total = (size_t)P.n_outputs * instances * row;
-    const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
-    hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires, d_out_ref, c->circ_out,
-                       total, inst, (uint32_t)n, r);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->circ_out, total * 8, hipMemcpyDeviceToHost, st));
+    // the pack stage: ciphertexts q0 .. q0 + cnt of a call are rows q0 * n .. of the "level" whose node o is
+    // (TRUE, output o) -- row = o * instances + block * n + bit -- so the gather of the levels builds the call's
+    // bootstrap inputs, and each call is one sgfhe_pack_encrypted_bits(count = cnt) on the device
+    for (size_t q0 = 0; q0 < n_ct; q0 += cpc) {
+        const size_t cnt = std::min(cpc, n_ct - q0), nb = cnt * n;
+        uint64_t *p1 = c->pack_lwe, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
+        const uint32_t tg = (uint32_t)(nb * row);
+        hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires, d_pack_ref,
+                           p1, q1, p2, q2, (uint32_t)(q0 * n), (uint32_t)nb, inst, (uint32_t)n, r);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = pack_device(c, p1, q1, p2, q2, cnt, c->pack_wv + q0 * M, c->pack_wv + (n_ct + q0) * M, st))) return rc;
+    }
+    if (pack) {
+        HIPCHK(c, hipMemcpyAsync(ct->out_w, c->pack_wv, n_ct * M * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(ct->out_v, c->pack_wv + n_ct * M, n_ct * M * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (out) {
+        const size_t total = (size_t)P.n_outputs * instances * row;
+        const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
+        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires, d_out_ref,
+                           c->circ_out, total, inst, (uint32_t)n, r);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(out, c->circ_out, total * 8, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(c, hipStreamSynchronize(st));
     c->pending = false;
     return SGFHE_OK;
@@ -3013,7 +3111,42 @@ int32_t sgfhe_circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instan
     (void)hipSetDevice(c->device);
     int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
     if (rc) return rc;
-    rc = circuit_run_queued(c, P, instances, in, out);
+    rc = circuit_run_queued(c, P, instances, in, out, nullptr);
+    if (rc) {   // whatever was queued finishes before the buffers can be touched again
+        (void)hipStreamSynchronize(c->stream);
+        c->pending = false;
+    }
+    return rc;
+}
+
+int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
+                             const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    if (!circ || ((!in_a || !in_b) && circ->plan.n_inputs))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: NULL circuit or input pointer");
+    if (!out_w != !out_v || (!out_w && !out_lwe))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: out_w and out_v go together, and one output form is needed");
+    if (N != c->n && N != c->M)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: N must be n (PackedCiphertext) or m (Ciphertext)");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    if (out_w && !(c->rnd ? c->pack_G_rnd : c->pack_G))
+        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
+    const CircuitPlan &P = circ->plan;
+    if (blocks == 0) return SGFHE_OK;
+    // the limits of sgfhe_circuit_run on blocks * n instances; the rows of the pack stage (n_outputs * instances)
+    // and the workgroups of the split kernel must be addressable too
+    const uint64_t instances = (uint64_t)blocks * c->n;
+    const uint64_t tiles = (c->n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS;
+    if (blocks >= 0x80000000u || instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull ||
+        (out_w && (uint64_t)P.n_outputs * instances > 0xFFFFFFFFull) ||
+        (uint64_t)P.n_inputs * blocks * tiles > 0x7FFFFFFFull)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: too many instances for this circuit");
+    (void)hipSetDevice(c->device);
+    int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
+    if (rc) return rc;
+    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v};
+    rc = circuit_run_queued(c, P, (size_t)instances, nullptr, out_lwe, &ct);
     if (rc) {   // whatever was queued finishes before the buffers can be touched again
         (void)hipStreamSynchronize(c->stream);
         c->pending = false;

@@ -1724,6 +1724,47 @@ k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ 
     }
 }
 
+// split_ciphertext (fhe.jl:287-290, extract :237-244) of the input ciphertexts of sgfhe_circuit_run_ct, straight
+// into the wire table.  ct_a / ct_b [n_inputs][blocks][N] (N = n or m); bit i of (input, block) becomes the row of
+// instance block * n + i in the input's slot: word j < n is a[i - j] for j <= i and -a[N - (j - i)] mod r beyond,
+// word n is b[i] -- with ext[d] = a[d] (d >= 0), -a[N + d] (d < 0), word j is ext[i - j].
+// Bound by its stores (n + 1 words written per coefficient read).  A workgroup writes CIRC_SPLIT_ROWS consecutive
+// rows of one ciphertext, which are contiguous in the table: it stages the n + CIRC_SPLIT_ROWS - 1 values of ext
+// those rows read in LDS once (negated where d < 0), then every thread stores one word per step, consecutive
+// threads consecutive words (coalesced 8-byte stores; rows of n + 1 words are not 16-byte aligned).
+// grid = n_inputs * blocks * ceil(n / CIRC_SPLIT_ROWS); dynamic LDS (n + CIRC_SPLIT_ROWS - 1) * 8 bytes.
+constexpr uint32_t CIRC_SPLIT_ROWS = 16;
+
+__global__ void __launch_bounds__(256)
+k_circ_split(const uint64_t *__restrict__ ct_a, const uint64_t *__restrict__ ct_b,
+             const uint32_t *__restrict__ in_slot, uint64_t *__restrict__ wires, uint32_t blocks, uint32_t N,
+             uint32_t n, uint64_t r) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t split_ext[];
+    const uint32_t tiles = (n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS;
+    const uint32_t tile = blockIdx.x % tiles, q = blockIdx.x / tiles;   // q = input * blocks + block
+    const uint32_t input = q / blocks, block = q % blocks;
+    const uint32_t slot = in_slot[input];
+    if (slot == CIRC_SLOT_NONE) return;   // nothing reads this input (uniform over the workgroup)
+    const uint32_t i0 = tile * CIRC_SPLIT_ROWS;
+    const uint32_t rows = min(CIRC_SPLIT_ROWS, n - i0);
+    const uint64_t *a = ct_a + (size_t)q * N, *b = ct_b + (size_t)q * N;
+    // split_ext[k] = ext[i0 - (n - 1) + k], k < n + rows - 1: d runs from i0 - n + 1 to i0 + rows - 1 <= n - 1 < N
+    for (uint32_t k = threadIdx.x; k < n + rows - 1; k += 256) {
+        const int32_t d = (int32_t)(i0 + k) - (int32_t)(n - 1);
+        split_ext[k] = d >= 0 ? a[d] : (r - a[N - (uint32_t)(-d)]) & (r - 1);
+    }
+    __syncthreads();
+    const uint32_t row = n + 1, total = rows * row;
+    uint64_t *dst = wires + ((size_t)slot * blocks * n + (size_t)block * n + i0) * row;
+    uint32_t lr = threadIdx.x / row, e = threadIdx.x % row;
+    for (uint32_t w = threadIdx.x; w < total; w += 256) {
+        // word e of row i0 + lr: ext[i0 + lr - e] = split_ext[lr + n - 1 - e]
+        dst[w] = e < n ? split_ext[lr + n - 1 - e] : b[i0 + lr];
+        e += 256;
+        while (e >= row) { e -= row; lr++; }
+    }
+}
+
 // digits -> canonical accumulators (debug hook)
 __global__ void __launch_bounds__(256)
 k_dump_acc(const uint64_t *__restrict__ dig, ulonglong2 *__restrict__ out,

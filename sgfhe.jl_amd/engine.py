@@ -236,6 +236,31 @@ class Engine:
         self._call("sgfhe_circuit_run", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p))
         return out
 
+    def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False):
+        """A gate circuit with RLWE ciphertexts at both ends (sgfhe_circuit_run_ct): split_ciphertext of the
+        inputs and pack_encrypted_bits of the outputs run on the device inside the one run.
+        a, b: [n_inputs][blocks][N] uint64, rlwe.a / rlwe.b of one ciphertext per (input, block), N = n
+        (PackedCiphertext) or m (Ciphertext); a ciphertext is one wire over n instances.
+        packed: return (w, v), each [n_outputs][blocks][m]; lwe: return the LWE array
+        [n_outputs][blocks * n][n + 1] of circuit_run.  Both: ((w, v), lwe)."""
+        p = self.params
+        a, pa = _c(a)
+        b, pb = _c(b)
+        if a.ndim != 3 or a.shape != b.shape or a.shape[0] != circuit.n_inputs or a.shape[2] not in (p.n, p.m):
+            raise ValueError("circuit_run_ct: a and b must be [n_inputs=%d][blocks][N], N = n = %d or m = %d"
+                             % (circuit.n_inputs, p.n, p.m))
+        if not packed and not lwe:
+            raise ValueError("circuit_run_ct: ask for the packed outputs, the LWE outputs or both")
+        blocks = a.shape[1]
+        w = np.zeros((circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
+        v = np.zeros((circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
+        out = np.zeros((circuit.n_outputs, blocks * p.n, p.n + 1), dtype=np.uint64) if lwe else None
+        ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None else None
+        self._call("sgfhe_circuit_run_ct", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out))
+        if packed and lwe:
+            return (w, v), out
+        return (w, v) if packed else out
+
     def pack_encrypted_bits(self, a, b):
         """pack_encrypted_bits (fhe.jl:660-696) for `count` groups of n LWEs: a [count][n][n],
         b [count][n] -> (w, v), each [count][m] uint64 over Z_r."""

@@ -349,6 +349,17 @@ def split_ciphertext(ct):
             for i in range(1, p.n + 1)]
 
 
+def split_ciphertext_array(a, b, n, r):
+    """split_ciphertext in array form: RLWE polynomials a, b [..., N] over Z_r (N = n or m) ->
+    LWEs [..., n][n + 1] (a then b), bit i (0-based) being extract(a, i + 1, n) and b[i]."""
+    a = np.asarray(a, dtype=np.uint64)
+    b = np.asarray(b, dtype=np.uint64)
+    N = a.shape[-1]
+    d = np.arange(n)[:, None] - np.arange(n)[None, :]                     # i - j
+    ext = np.where(d >= 0, a[..., d % N], (np.uint64(r) - a[..., d % N]) & np.uint64(r - 1))
+    return np.concatenate([ext, b[..., :n, None]], axis=-1)
+
+
 def pack_encrypted_bits(bkey, rng, enc_bits):
     """pack_encrypted_bits(bkey, rng, enc_bits) (src/fhe.jl:660-696): n EncryptedBits -> one
     RLWE Ciphertext, on the HIP engine.  rng = None: deterministic flatten (bit-exact); a numpy

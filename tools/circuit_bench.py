@@ -9,6 +9,15 @@ Engine.bootstrap_batch on host arrays, at Params(1024), deterministic flatten.
       the same circuit run in a child process under `rocprofv3 --kernel-trace --stats`: the share of the
       gather, scatter and collect kernels in the kernel time of the run.
 
+  python tools/circuit_bench.py --ct [--configs 16x1] [--reps 3]
+      ciphertexts in and out (bits x blocks; a block is n = 1024 instances): (A) one circuit_run_ct -- split and
+      pack on the device -- against (B) what a caller composes from host arrays without it: host split
+      (sgfhe_host_split_ciphertext), circuit_run, pack_encrypted_bits in groups of 8 ciphertexts.  The two
+      alternate in one process on two ctxs that share one key (the order swaps every round); the bytes must be
+      equal; prints both times per round, their spread, and the bytes each moves over PCIe each way.
+  python tools/circuit_bench.py --ct --trace [--configs 16x1] [--dir DIR]
+      run (A) alone in a child process under `rocprofv3 --kernel-trace --stats`: the share of k_circ_split.
+
 Inputs are uniform words of [0, r): a bootstrap's time does not depend on what it encrypts."""
 
 import argparse
@@ -71,11 +80,95 @@ def wall(args):
     eng.close()
 
 
+def wall_ct(args):
+    import sgfhe_jl_amd as S
+    import encrypted_adder
+    from sgfhe_jl_amd import circuit as C
+    params = S.Params(1024)
+    n, m = params.n, params.m
+    eng_a = S.Engine(params)
+    rng = np.random.default_rng(1)
+    eng_a.generate_key(rng.integers(0, 2, size=n).astype(np.uint64), 2)
+    eng_b = eng_a.clone()
+    cpc = C.pack_calls(n)
+    print("build %s, Params(1024), deterministic flatten, call rows %d, %d ciphertexts per pack call"
+          % (eng_a.build_id(), C.CALL_ROWS, cpc))
+    warm = encrypted_adder.adder_circuit(S, 2)
+    wa = rng.integers(0, params.r, size=(4, 1, n), dtype=np.uint64)
+    for e in (eng_a, eng_b):
+        e.circuit_run_ct(warm, wa, wa)
+
+    def composed(c, a, b):
+        inputs = np.zeros((c.n_inputs, a.shape[1] * n, n + 1), dtype=np.uint64)
+        for i in range(a.shape[0]):
+            for t in range(a.shape[1]):
+                la, lb = S.host.split_ciphertext(params, a[i, t], b[i, t])
+                inputs[i, t * n:(t + 1) * n, :n], inputs[i, t * n:(t + 1) * n, n] = la, lb
+        lwe = eng_b.circuit_run(c, inputs)
+        g = lwe.reshape(-1, n, n + 1)
+        w = np.zeros((len(g), m), dtype=np.uint64)
+        v = np.zeros((len(g), m), dtype=np.uint64)
+        for q0 in range(0, len(g), cpc):
+            w[q0:q0 + cpc], v[q0:q0 + cpc] = eng_b.pack_encrypted_bits(g[q0:q0 + cpc, :, :n], g[q0:q0 + cpc, :, n])
+        return w.reshape(c.n_outputs, -1, m), v.reshape(c.n_outputs, -1, m)
+
+    for bits, blocks in configs(args.configs):
+        c = encrypted_adder.adder_circuit(S, bits)
+        info = c.info()
+        inst = blocks * n
+        boots = (info["nodes"] + c.n_outputs) * inst
+        a = rng.integers(0, params.r, size=(2 * bits, blocks, n), dtype=np.uint64)
+        b = rng.integers(0, params.r, size=(2 * bits, blocks, n), dtype=np.uint64)
+        lwe_in, lwe_out = c.n_inputs * inst * (n + 1) * 8, c.n_outputs * inst * (n + 1) * 8
+        ct_in, ct_out = 2 * c.n_inputs * blocks * n * 8, 2 * c.n_outputs * blocks * m * 8
+        print("\n%d-bit adder x %d block(s) = %d instances: %d levels, %d nodes per instance, %d outputs, "
+              "%d bootstraps per run (gates + pack)" % (bits, blocks, inst, info["levels"], info["nodes"], c.n_outputs, boots))
+        print("  PCIe bytes  (A) up %d  down %d  |  (B) up %d (LWE inputs %d + LWEs again for the pack %d)  "
+              "down %d (LWE outputs %d + ciphertexts %d)" % (ct_in, ct_out, lwe_in + lwe_out, lwe_in, lwe_out,
+                                                            lwe_out + ct_out, lwe_out, ct_out))
+        ta, tb = [], []
+        for rep in range(args.reps):
+            res = {}
+            order = ("A", "B") if rep % 2 == 0 else ("B", "A")
+            for what in order:
+                t0 = time.perf_counter()
+                out = eng_a.circuit_run_ct(c, a, b) if what == "A" else composed(c, a, b)
+                res[what] = (time.perf_counter() - t0, out)
+            same = all(np.array_equal(x, y) for x, y in zip(res["A"][1], res["B"][1]))
+            ta.append(res["A"][0])
+            tb.append(res["B"][0])
+            print("  round %d (%s first): (A) circuit_run_ct %.3f s = %.0f bootstraps/s | (B) composed from host arrays "
+                  "%.3f s = %.0f bootstraps/s | B / A %.4f | same bytes: %s"
+                  % (rep, order[0], ta[-1], boots / ta[-1], tb[-1], boots / tb[-1], tb[-1] / ta[-1], same))
+            if not same:
+                sys.exit("circuit_run_ct and the composition differ")
+        print("  (A) mean %.3f s, spread %.3f s | (B) mean %.3f s, spread %.3f s | mean B - mean A = %+.3f s"
+              % (np.mean(ta), max(ta) - min(ta), np.mean(tb), max(tb) - min(tb), np.mean(tb) - np.mean(ta)))
+    eng_b.close()
+    eng_a.close()
+
+
+def ct_only(args):
+    import sgfhe_jl_amd as S
+    import encrypted_adder
+    params = S.Params(1024)
+    eng = S.Engine(params)
+    rng = np.random.default_rng(1)
+    eng.generate_key(rng.integers(0, 2, size=params.n).astype(np.uint64), 2)
+    for bits, blocks in configs(args.configs):
+        c = encrypted_adder.adder_circuit(S, bits)
+        a = rng.integers(0, params.r, size=(2 * bits, blocks, params.n), dtype=np.uint64)
+        eng.circuit_run_ct(c, a, a)
+    print("build", eng.build_id())
+    eng.close()
+
+
 def trace(args):
     d = os.path.abspath(args.dir)
     os.makedirs(d, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "circ", "--", sys.executable,
-           os.path.abspath(__file__), "--configs", args.configs, "--reps", "1", "--circuit-only"]
+           os.path.abspath(__file__), "--configs", args.configs, "--reps", "1",
+           "--ct-only" if args.ct else "--circuit-only"]
     rc = subprocess.call(cmd)
     if rc:
         sys.exit("rocprofv3 run failed: %d" % rc)
@@ -92,7 +185,11 @@ def trace(args):
             circ += ns
         print("  %-60s calls %7s  total %10.3f ms  avg %9.1f us  %6.3f %%"
               % (r["Name"][:60], r["Calls"], ns * 1e-6, float(r["AverageNs"]) * 1e-3, 100 * ns / tot))
-    print("gather + scatter + collect: %.3f ms = %.3f %% of the kernel time" % (circ * 1e-6, 100 * circ / tot))
+    print("gather + scatter + collect%s: %.3f ms = %.3f %% of the kernel time"
+          % (" + split" if args.ct else "", circ * 1e-6, 100 * circ / tot))
+    if args.ct:
+        split = sum(float(r["TotalDurationNs"]) for r in rows if "k_circ_split" in r["Name"])
+        print("k_circ_split: %.3f ms = %.4f %% of the kernel time" % (split * 1e-6, 100 * split / tot))
 
 
 def circuit_only(args):
@@ -114,15 +211,23 @@ def main():
     ap.add_argument("--configs", default=None, help="bits x instances, comma-separated")
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--ct", action="store_true", help="ciphertexts in and out: circuit_run_ct against the composition")
     ap.add_argument("--circuit-only", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--ct-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dir", default="circuit_trace", help="where rocprofv3 writes its files")
     args = ap.parse_args()
     if args.configs is None:
-        args.configs = "16x1024" if args.trace else "16x256,16x1024,32x256,32x1024"
+        args.configs = "16x1" if args.ct or args.ct_only else "16x1024" if args.trace else "16x256,16x1024,32x256,32x1024"
+    if args.ct and not args.trace and args.reps == 1:
+        args.reps = 3
     if args.circuit_only:
         circuit_only(args)
+    elif args.ct_only:
+        ct_only(args)
     elif args.trace:
         trace(args)
+    elif args.ct:
+        wall_ct(args)
     else:
         wall(args)
 

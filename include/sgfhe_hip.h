@@ -142,7 +142,9 @@ int32_t sgfhe_ctx_clone(sgfhe_ctx *ctx, sgfhe_ctx **out);
  * affected at all.  A row of the result does not depend on the rows beside it, so every caller gets the bytes its
  * call gives alone -- with the randomised flatten too: every row of a gathered call draws from the stream of the ctx
  * it came in on (that ctx's key, the number of its call, the row's index in its call), and deterministic and
- * randomised requests form separate rounds.  The asynchronous entry point (sgfhe_bootstrap_batch_device) and
+ * randomised requests form separate rounds.  So do SGFHE_FLAG_RAW_RNS2 requests of ctxs whose RNS2 limb moduli differ
+ * (a clone inherits them; sgfhe_rns2_convert sets them on one ctx): each gets its own (v1, v2) order, and a ctx without
+ * moduli its own SGFHE_ERR_INVALID_ARG, whoever calls beside it.  The asynchronous entry point (sgfhe_bootstrap_batch_device) and
  * sgfhe_pack_encrypted_bits are never gathered.
  * The setting belongs to the shared key: it applies to every ctx that shares it.  enable = 0 switches gathering off
  * (SGFHE_COALESCE=0 in the environment does the same at ctx creation); the other arguments are then ignored.

@@ -13,7 +13,9 @@
 // batch-position test), so every caller gets the bytes of its call made alone -- in the randomised flatten too:
 // there every row of the combined call draws from the stream of the ctx it came in on (that ctx's key, the number
 // of its call, the row's index in its call: kernels.h RndRow), and deterministic and randomised requests form
-// separate rounds.
+// separate rounds.  What else of a ctx's state a result depends on is part of the grouping key too: requests for
+// RNS2Number limb pairs (SGFHE_FLAG_RAW_RNS2) carry their ctx's limb moduli -- or that it has none -- and gather only
+// with requests of the same moduli in the same order, so the leader's own moduli are the round's.
 #pragma once
 
 #include <stddef.h>
@@ -39,6 +41,10 @@ struct Coalescer {
         bool rnd = false;              // randomised flatten: the request's own draw stream (key, number of the call)
         uint32_t key[8] = {};
         uint32_t call = 0;
+        // SGFHE_FLAG_RAW_RNS2 requests: the limb moduli of the ctx the request came in on (a ctx without moduli
+        // has have_rns2 = false: its request is refused, by a round of its like); left at their defaults otherwise
+        bool have_rns2 = false;
+        uint64_t m1 = 0, m2 = 0;
         int32_t rc = 0;
         bool done = false;
         std::string err;
@@ -60,6 +66,19 @@ struct Coalescer {
     // statistics (sgfhe_coalesce_stats)
     uint64_t n_calls = 0, n_reqs = 0, n_gates = 0, max_reqs = 0;
 
+    // Requests that may share a round: the combined call runs on the leader's ctx, so everything of a ctx that a
+    // result depends on has to agree.
+    static bool same_group(const Req &a, const Req &b) {
+        return a.flags == b.flags && a.rnd == b.rnd && a.have_rns2 == b.have_rns2 && a.m1 == b.m1 && a.m2 == b.m2;
+    }
+
+    // Entries of the per-row draw-stream table (kernels.h RndRow) that a randomised call of `gates` rows can read.
+    // A call runs in chunks [c0, c0 + cb) and the kernels of a chunk also draw for the rows that pad it to a multiple
+    // of 8 (their results are dropped): the highest index read is c0 + round_up8(cb) - 1.  Whatever the chunk size --
+    // the halves of the latency form are no multiples of 8 -- c0 + cb <= gates and round_up8(cb) <= cb + 7.
+    // (tests/native/coalescer_tsan.cpp holds it against every chunking of every call up to 4096 gates.)
+    static size_t rows_len(size_t gates) { return gates + 7; }
+
     // Is a call of `batch` gates one to gather?  (the knobs may change under a caller's feet: read under the lock)
     bool wants(size_t batch) {
         std::lock_guard<std::mutex> lk(mu);
@@ -68,12 +87,15 @@ struct Coalescer {
 
     // A request arrives.  Returns 0 when another caller's combined call served it (me.rc / me.err hold its outcome);
     // 1 when the caller LEADS a round: `take` holds the requests of the round, `me` among them -- same flags and
-    // flatten mode as `me`, at most gates_max gates (always at least `me`); the caller runs them and then calls
+    // flatten mode and RNS2 moduli as `me` (same_group), at most gates_max gates (always at least `me`), and
+    // `*gates_cap` (where asked for) holds the gates_max that held for the round (the knob may change before the leader is done: it
+    // sizes its buffers from this copy); the caller runs them and then calls
     // finish(); between the two calls no other round starts.  -1 when the host is out of memory: the request is
     // in no queue and nothing else has changed (the entry points of the C ABI must not throw).
-    int arrive(Req &me, std::vector<Req *> &take, size_t &gates) {
+    int arrive(Req &me, std::vector<Req *> &take, size_t &gates, size_t *gates_cap = nullptr) {
         take.clear();
         gates = 0;
+        if (gates_cap) *gates_cap = 0;
         std::unique_lock<std::mutex> lk(mu);
         try {
             pending.push_back(&me);
@@ -108,8 +130,9 @@ struct Coalescer {
             cv.notify_all();                        // the next oldest request leads
             return -1;
         }
+        if (gates_cap) *gates_cap = gates_max;
         for (auto it = pending.begin(); it != pending.end();) {
-            if ((*it)->flags == me.flags && (*it)->rnd == me.rnd && (take.empty() || gates + (*it)->batch <= gates_max)) {
+            if (same_group(**it, me) && (take.empty() || gates + (*it)->batch <= gates_max)) {
                 take.push_back(*it);
                 gates += (*it)->batch;
                 it = pending.erase(it);

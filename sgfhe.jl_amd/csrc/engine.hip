@@ -2323,9 +2323,13 @@ static int32_t coalesced_call(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
         me.call = c->rnd_call++;
         c->last_call = me.call;
     }
+    if (flags & SGFHE_FLAG_RAW_RNS2) {      // limb pairs leave by this ctx's moduli: only its like share its round
+        me.have_rns2 = c->have_rns2;
+        if (c->have_rns2) { me.m1 = c->rns2.m1; me.m2 = c->rns2.m2; }
+    }
     std::vector<Coalescer::Req *> take;
-    size_t gates = 0;
-    const int lead = co.arrive(me, take, gates);
+    size_t gates = 0, gates_cap = 0;
+    const int lead = co.arrive(me, take, gates, &gates_cap);
     if (lead < 0) return fail(c, SGFHE_ERR_OOM, "out of host memory");
     if (lead == 0) {                                // a leader ran it
         if (me.rc) c->err = me.err;
@@ -2346,11 +2350,13 @@ static int32_t coalesced_call(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
             if (me.rnd) {   // the draw stream of every row of the combined call, on the device before its first kernel
                 (void)hipSetDevice(c->device);
                 if ((r = drain(c))) return r;
-                if (gates > c->rows_cap) {
+                // (the kernels draw for the rows that pad a chunk to a multiple of 8 as well: Coalescer::rows_len)
+                const size_t nrows = Coalescer::rows_len(gates);
+                if (nrows > c->rows_cap) {
                     if (c->d_rows) (void)hipFree(c->d_rows);
                     c->d_rows = nullptr;
                     c->rows_cap = 0;
-                    const size_t cap = gates > co.gates_max ? gates : co.gates_max;
+                    const size_t cap = Coalescer::rows_len(gates > gates_cap ? gates : gates_cap);
                     if (hipMalloc(&c->d_rows, cap * sizeof(RndRow)) != hipSuccess)
                         return fail(c, SGFHE_ERR_OOM, "hipMalloc of the gathered call's draw-stream table failed");
                     c->rows_cap = cap;
@@ -2364,7 +2370,8 @@ static int32_t coalesced_call(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
                         row_of.boot = (uint32_t)t;
                         c->h_rows.push_back(row_of);
                     }
-                if (hipMemcpy(c->d_rows, c->h_rows.data(), gates * sizeof(RndRow), hipMemcpyHostToDevice) != hipSuccess)
+                c->h_rows.resize(nrows, RndRow{});      // the padded rows: zeros, not what an earlier round left
+                if (hipMemcpy(c->d_rows, c->h_rows.data(), nrows * sizeof(RndRow), hipMemcpyHostToDevice) != hipSuccess)
                     return fail(c, SGFHE_ERR_HIP, "copy of the gathered call's draw-stream table failed");
                 c->gather_rows = c->d_rows;
             }

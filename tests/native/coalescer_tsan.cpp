@@ -10,8 +10,16 @@
 //   - a round never mixes flags or modes and never exceeds gates_max unless it is a single oversized request;
 //   - the statistics add up, and callers on their own are not delayed by the gathering window;
 //   - an error of the leader's run reaches every request of its round and nobody else;
-//   - the knobs change under the callers' feet (sgfhe_set_coalesce from another thread) while every caller asks
-//     wants() first, as sgfhe_bootstrap_batch does: requests it declines run on their own.
+//   - the knobs change under the callers' feet (sgfhe_set_coalesce from another thread: req_max, window_us and
+//     gates_max) while every caller asks wants() first, as sgfhe_bootstrap_batch does: requests it declines run on
+//     their own; a leader judges its round by the gates_max arrive() hands back, never by a second look at the knob;
+//   - requests for RNS2 limb pairs carry their ctx's moduli: (m1, m2), (m2, m1) and "none" never share a round.  The
+//     stand-in, like the engine, runs a round with the LEADER's moduli and refuses it when the leader has none: a
+//     caller with moduli gets its own order, a caller without gets the refusal, whoever was queued beside them;
+//   - Coalescer::rows_len(gates) covers the highest draw-stream row any chunking of a call of `gates` rows reads
+//     (c0 + round_up8(cb) - 1 over its chunks), by brute force over every call up to 4096 gates and every chunk size,
+//     and wastes nothing.  The read past the table cannot be seen in any output on the device (the padded rows'
+//     results are dropped): this is its test.
 // Prints "ok <rounds> <requests> <requests declined by wants()>".  Any data race, lock-order inversion, use-after-return of a Req (they live on the
 // callers' stacks) or leak aborts the run.
 #if defined(__SANITIZE_THREAD__)
@@ -31,10 +39,39 @@
 
 using sgfhe::Coalescer;
 
-static uint64_t f(uint32_t key0, uint32_t call, uint32_t flags, uint64_t a, size_t row) {
+static uint64_t f(uint32_t key0, uint32_t call, uint32_t flags, uint64_t a, size_t row, uint64_t m1 = 0) {
     uint64_t x = a * 0x9E3779B97F4A7C15ull + key0;
     x ^= (uint64_t)call << 32 | flags;
-    return x * 1099511628211ull + row;
+    return x * 1099511628211ull + row + (m1 << 20);
+}
+
+static const uint32_t FLAG_RNS2 = 3u;      // SGFHE_FLAG_RAW_MODQ | SGFHE_FLAG_RAW_RNS2
+
+// the highest row of the draw-stream table that a call of `gates` rows cut into chunks of `chunk` reads
+// (engine.hip bootstrap_device: chunk [c0, c0 + cb), its kernels run over round_up8(cb) rows from ra.chunk = c0)
+static size_t highest_row(size_t gates, size_t chunk) {
+    size_t hi = 0;
+    for (size_t c0 = 0; c0 < gates; c0 += chunk) {
+        const size_t cb = gates - c0 < chunk ? gates - c0 : chunk;
+        const size_t last = c0 + ((cb + 7) & ~(size_t)7) - 1;
+        if (last > hi) hi = last;
+    }
+    return hi;
+}
+
+static bool rows_len_holds() {
+    for (size_t gates = 1; gates <= 4096; gates++) {
+        size_t hi = 0;
+        for (size_t chunk = 1; chunk <= gates; chunk++) {
+            const size_t h = highest_row(gates, chunk);
+            if (h > hi) hi = h;
+        }
+        if (Coalescer::rows_len(gates) != hi + 1) {
+            printf("FAILED: rows_len(%zu) = %zu, a chunking of the call reads row %zu\n", gates, Coalescer::rows_len(gates), hi);
+            return false;
+        }
+    }
+    return true;
 }
 
 static std::atomic<int> in_round{0};
@@ -43,15 +80,17 @@ static std::atomic<uint64_t> work_ns{0};   // time the stand-in actually slept (
 
 // what engine.hip's coalesced_call does around arrive() / finish(), with the stand-in for the combined call
 static int32_t call(Coalescer &co, const void *owner, uint32_t key0, uint32_t callno, bool rnd, uint32_t flags,
-                    const uint64_t *a1, size_t batch, uint64_t *out, bool fail_if_leading, std::string &err_out) {
+                    const uint64_t *a1, size_t batch, uint64_t *out, bool fail_if_leading, std::string &err_out,
+                    bool have_rns2 = false, uint64_t m1 = 0, uint64_t m2 = 0) {
     Coalescer::Req me;
     me.owner = owner;
     me.a1 = a1; me.b1 = a1; me.a2 = a1; me.b2 = a1;
     me.batch = batch; me.out = out; me.flags = flags;
     me.rnd = rnd; me.key[0] = key0; me.call = callno;
+    if (flags == FLAG_RNS2) { me.have_rns2 = have_rns2; me.m1 = m1; me.m2 = m2; }     // as engine.hip's coalesced_call
     std::vector<Coalescer::Req *> take;
-    size_t gates = 0;
-    const int lead = co.arrive(me, take, gates);
+    size_t gates = 0, gates_cap = 0;
+    const int lead = co.arrive(me, take, gates, &gates_cap);
     if (lead < 0) return -6;
     if (lead == 0) {
         err_out = me.err;
@@ -64,8 +103,9 @@ static int32_t call(Coalescer &co, const void *owner, uint32_t key0, uint32_t ca
         sum += q->batch;
         mine |= q == &me;
         if (q->flags != me.flags || q->rnd != me.rnd) violations++;
+        if (q->have_rns2 != me.have_rns2 || q->m1 != me.m1 || q->m2 != me.m2) violations++;
     }
-    if (!mine || sum != gates || (gates > co.gates_max && take.size() != 1)) violations++;
+    if (!mine || sum != gates || gates_cap == 0 || (gates > gates_cap && take.size() != 1)) violations++;
     const auto w0 = std::chrono::steady_clock::now();
     std::this_thread::sleep_for(std::chrono::microseconds(150 + 20 * gates));
     work_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - w0).count();
@@ -74,9 +114,12 @@ static int32_t call(Coalescer &co, const void *owner, uint32_t key0, uint32_t ca
     if (fail_if_leading) {
         rc = -4;
         err = "stand-in failure";
-    } else {
+    } else if (flags == FLAG_RNS2 && !have_rns2) {     // the LEADER's check, as in bootstrap_device
+        rc = -1;
+        err = "no RNS2 moduli";
+    } else {                                           // ... and the leader's moduli for every row of the round
         for (const Coalescer::Req *q : take)
-            for (size_t i = 0; i < q->batch; i++) q->out[i] = f(q->key[0], q->call, q->flags, q->a1[i], i);
+            for (size_t i = 0; i < q->batch; i++) q->out[i] = f(q->key[0], q->call, q->flags, q->a1[i], i, m1);
     }
     rounds++;
     in_round.fetch_sub(1);
@@ -86,6 +129,7 @@ static int32_t call(Coalescer &co, const void *owner, uint32_t key0, uint32_t ca
 }
 
 int main() {
+    if (!rows_len_holds()) return 1;
     Coalescer co;
     co.gates_max = 24;
     co.window_us = 200;
@@ -98,6 +142,7 @@ int main() {
                 std::lock_guard<std::mutex> lk(co.mu);
                 co.req_max = (i & 1) ? 4 : 32;
                 co.window_us = (i & 2) ? 100 : 200;
+                co.gates_max = (i & 4) ? 9 : 24;
             }
             std::this_thread::sleep_for(std::chrono::microseconds(500));
         }
@@ -110,8 +155,12 @@ int main() {
             int owner_tag = t;                              // stands for the ctx
             for (int k = 0; k < K; k++) {
                 const size_t batch = 1 + rnd64() % (t == 0 ? 30 : 5);          // thread 0 also sends requests above gates_max
-                const bool rnd = (t % 3) == 0;
-                const uint32_t flags = (t % 4) == 1 ? 1u : 0u;
+                // threads 3, 7, 11 ask for RNS2 limb pairs: moduli (5, 7), (7, 5), none -- all three deterministic, so
+                // that nothing but the moduli keeps their requests apart
+                const uint32_t flags = (t % 4) == 1 ? 1u : (t % 4) == 3 ? FLAG_RNS2 : 0u;
+                const bool rnd = (t % 3) == 0 && flags != FLAG_RNS2;
+                const bool have_rns2 = flags == FLAG_RNS2 && t != 11;
+                const uint64_t m1 = !have_rns2 ? 0 : t == 3 ? 5 : 7, m2 = !have_rns2 ? 0 : t == 3 ? 7 : 5;
                 const bool poison = (t == 5 && k % 7 == 3);                     // this caller's run fails when it leads
                 std::vector<uint64_t> a(batch), out(batch, 0xDEADull);
                 for (auto &x : a) x = rnd64();
@@ -120,15 +169,19 @@ int main() {
                     alone++;
                     continue;
                 }
-                const int32_t rc = call(co, &owner_tag, 77u + t, (uint32_t)k, rnd, flags, a.data(), batch, out.data(), poison, err);
+                const int32_t rc = call(co, &owner_tag, 77u + t, (uint32_t)k, rnd, flags, a.data(), batch, out.data(), poison, err,
+                                        have_rns2, m1, m2);
                 if (rc) {
                     failed++;
-                    if (err != "stand-in failure") wrong++;
+                    // a refusal for want of moduli reaches the callers without moduli only; the poisoned round's
+                    // failure the (deterministic, flags 1) callers that can share thread 5's rounds
+                    if (err != (t == 11 ? "no RNS2 moduli" : "stand-in failure")) wrong++;
                     for (auto v : out) if (v != 0xDEADull) wrong++;           // a failed round writes nothing
                 } else {
                     served++;
+                    if (t == 11) wrong++;                   // another caller's moduli served a ctx that has none
                     for (size_t i = 0; i < batch; i++)
-                        if (out[i] != f(77u + t, (uint32_t)k, flags, a[i], i)) wrong++;
+                        if (out[i] != f(77u + t, (uint32_t)k, flags, a[i], i, m1)) wrong++;
                 }
                 if (t % 2) std::this_thread::sleep_for(std::chrono::microseconds(rnd64() % 300));
             }
@@ -139,6 +192,7 @@ int main() {
     tuner.join();
     co.req_max = 32;
     co.window_us = 200;
+    co.gates_max = 24;
     // a caller on its own: no other caller seen in the last rounds, so no waiting for anybody.  What the coalescer adds
     // is the round's time minus the stand-in's measured work: a 0.2 ms window in every round would add at least 40 ms.
     int solo_tag = 0;

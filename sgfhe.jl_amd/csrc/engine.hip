@@ -16,6 +16,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -73,6 +74,37 @@ double u128_dbl(u128 x) { return (double)(uint64_t)(x >> 64) * 18446744073709551
 
 }  // namespace
 
+// wall clock in milliseconds (the SGFHE_DEBUG_IO phase lines)
+static double wall_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// A grow-on-demand buffer that a ctx keeps between calls: device memory, or page-locked host memory
+// (PINNED).  grow() never keeps the contents, and is called only when nothing of the ctx is in flight
+// (after drain()); a failed allocation leaves the buffer empty and no sticky HIP error behind.
+template <typename T, bool PINNED = false>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;   // elements
+    hipError_t grow(size_t words) {
+        if (words <= cap) return hipSuccess;
+        release();
+        const hipError_t e = PINNED ? hipHostMalloc(&p, words * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, words * sizeof(T));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return e;
+        }
+        cap = words;
+        return hipSuccess;
+    }
+    void release() {
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 // ---------------------------------------------------------------- ctx
 
 // Device memory that a ctx and its clones (sgfhe_ctx_clone) have in common: the per-prime records and
@@ -108,27 +140,26 @@ struct sgfhe_ctx {
     // (Params(1024): five against six) the ctx keeps a basis for each mode -- the key in both forms
     // (the form of the smaller basis is the larger one's times a constant per prime, derived on the
     // device), constants for both -- so that `bootstrap(bkey, rng, ...)` works on every ctx and the
-    // deterministic mode never pays for the extra prime.  The fields below (npr ... pack_G_rnd,
-    // d_key) are the ACTIVE basis: a copy of basis[active], switched by sgfhe_set_random_flatten
-    // (activate()); everything that launches kernels reads them.
+    // deterministic mode never pays for the extra prime.  `active` is an index: everything that
+    // launches kernels reads basis[active] through cur(); sgfhe_set_random_flatten sets it to the
+    // mode's basis, and the key writers to the larger one while they work (key_begin / key_finish).
     struct Basis {
-        uint32_t npr = 0;
+        uint32_t npr = 0;  // RNS primes in use: the fewest whose product covers the exactness bound
         uint32_t primes[NPR_MAX] = {};
         PrimeK *d_primes = nullptr;
         CrtConst *d_crt = nullptr;
         CrtConst h_crt;
-        CrtLean *d_lean = nullptr;
+        CrtLean *d_lean = nullptr;  // constants of k_crt_lean (nl = 0: this parameter set keeps k_crt_acc)
         CrtLean h_lean;
-        bool lean_rnd_ok = false;
-        uint32_t pack_G = 1, pack_G_rnd = 0;
+        bool lean_rnd_ok = false;   // k_crt_lean_rnd's width bounds hold for this parameter set (build_basis)
+        uint32_t pack_G = 1, pack_G_rnd = 0;  // key slices per exact-accumulation group of the packing path
+                                              // (deterministic / randomised flatten; 0 = not available)
         int32_t *d_key = nullptr;
         size_t key_bytes = 0;
     } basis[2];
     int nb = 1, active = 0;       // bases in use (basis[0]: deterministic mode, basis[nb - 1]: randomised), active one
     uint32_t npr_max = 0;         // primes of the larger basis: work buffers are sized for it
     uint32_t tw_done = 0;         // primes whose twiddle tables are on the device
-    uint32_t primes[NPR_MAX];
-    uint32_t npr = 0;  // RNS primes in use: the fewest whose product covers the exactness bound
     std::string err;
     // the read-only device memory of this ctx, shared with its clones (use_count() > 1: the key may not
     // be replaced, sgfhe_ctx_clone)
@@ -153,8 +184,6 @@ struct sgfhe_ctx {
     hipStream_t stream_io = nullptr, stream_io2 = nullptr;
     std::vector<hipEvent_t> ev_pool;   // events of the pipelined host-pointer path (created once, reused)
     // device constants
-    PrimeK *d_primes = nullptr;
-    CrtConst *d_crt = nullptr;
     uint32_t *d_bad = nullptr;  // set by k_key_transform when a key residue is >= Q
     int32_t *d_tw = nullptr;  // npr * 4 * M entries
     int32_t *d_twq = nullptr; // quarter form of the latency kernels: per prime 4 blocks [f_q | v_q | fp_q | vp_q] of m / 4 words
@@ -166,16 +195,7 @@ struct sgfhe_ctx {
     uint32_t split_max = 7;   // calls of at most this many gates take the quarter form (SGFHE_SMALL_SPLIT, 0 = never):
                               // 1 / 2 / 4 / 6 / 8 gates 15.1 / 15.9 / 17.8 / 19.7 / 23.5 ms against 17.9 / 18.6 / 20.3 /
                               // 22.0 / 23.3 with one workgroup per transform (profiles/r04_exp_quarter.txt)
-    CrtConst h_crt;
-    CrtLean *d_lean = nullptr;  // constants of k_crt_lean (nl = 0: this parameter set keeps k_crt_acc)
-    CrtLean h_lean;
-    bool lean_rnd_ok = false;   // k_crt_lean_rnd's width bounds hold for this parameter set (build_constants)
-    uint32_t pack_G = 1, pack_G_rnd = 0;  // key slices per exact-accumulation group of the packing path
-                                          // (deterministic / randomised flatten; 0 = not available)
-    // key
-    int32_t *d_key = nullptr;
-    size_t key_bytes = 0;
-    bool have_key = false;
+    bool have_key = false;      // basis[].d_key of every basis in use hold one key
     // work buffers: two lanes, each sized for `cap` bootstraps
     uint32_t chunk = 0, cap = 0, lanes = 2;
     // randomised flatten (rng != nothing, utils.jl:198-241)
@@ -184,8 +204,7 @@ struct sgfhe_ctx {
     uint32_t rnd_call = 0, last_call = 0;
     int64_t call_fixed = -1;              // the number of the next call, when the coalescer has already assigned it
     const RndRow *gather_rows = nullptr;  // set around a gathered randomised call this ctx leads: d_rows
-    RndRow *d_rows = nullptr;             // per-row draw streams of such a call (device), for up to rows_cap rows
-    size_t rows_cap = 0;
+    DevBuf<RndRow> d_rows;                // per-row draw streams of such a call (device)
     std::vector<RndRow> h_rows;
     uint32_t create_flags = 0;
     // RNS2Number form of Z_Q (src/rns.jl): set by sgfhe_bkey_upload_rns2 / sgfhe_rns2_convert
@@ -209,33 +228,28 @@ struct sgfhe_ctx {
     // staging buffers of the host-pointer entry point (sgfhe_bootstrap_batch: the drop-in signature of
     // fhe.jl:608-610, usually called with one gate): grown on demand and kept, so that a call does
     // not pay a hipMalloc / hipFree pair (hipFree synchronises the device)
-    uint64_t *io_in = nullptr, *io_out = nullptr;
-    size_t io_in_words = 0, io_out_words = 0;
+    DevBuf<uint64_t> io_in, io_out;
     // ... and their page-locked host mirrors.  hipMemcpyAsync on pageable memory above about 1 MB
     // pins the caller's pages for the copy, a fixed cost of several milliseconds per copy
     // (profiles/r03_latency.txt: 256 gates 155.6 ms through host pointers against 127.6 ms from
     // device buffers, 64 gates 43.6 against 43.4); below PIN_MAX_BYTES per buffer the engine
     // copies through its own pinned buffers instead (one CPU memcpy + one true DMA).
-    uint64_t *pin_in = nullptr, *pin_out = nullptr;
-    size_t pin_in_words = 0, pin_out_words = 0;
+    DevBuf<uint64_t, true> pin_in, pin_out;
     std::vector<uint64_t> co_buf;   // gathered inputs and results of a combined call this ctx leads (Coalescer)
     bool use_pin = true;   // SGFHE_HOST_PIN=0 in the environment: direct copies (A/B measurements)
     // device buffers of sgfhe_circuit_run, grown on demand and kept like the I/O staging: the wire table
     // [slot][instance][n + 1], one call's staging [a1 | a2 | b1 | b2 | result rows], the plan's node tables,
     // and the collected outputs
-    uint64_t *circ_wires = nullptr, *circ_stage = nullptr, *circ_out = nullptr;
-    uint32_t *circ_tab = nullptr;
-    size_t circ_wires_words = 0, circ_stage_words = 0, circ_out_words = 0, circ_tab_words = 0;
+    DevBuf<uint64_t> circ_wires, circ_stage, circ_out;
+    DevBuf<uint32_t> circ_tab;
     // sgfhe_circuit_run_ct: the uploaded input ciphertexts [a | b], each [n_inputs][blocks][N]
-    uint64_t *circ_ct = nullptr;
-    size_t circ_ct_words = 0;
+    DevBuf<uint64_t> circ_ct;
     // work buffers of the packing path (pack_device), shared by sgfhe_pack_encrypted_bits and the pack stage
     // of sgfhe_circuit_run_ct, grown and freed like the circuit buffers: one call's bootstrap inputs
     // [a1 | a2 | b1 | b2], its un-reduced results, the flattened as_i, the group sums, and (w | v)
-    uint64_t *pack_lwe = nullptr, *pack_pdig = nullptr, *pack_wv = nullptr;
-    ulonglong2 *pack_raw = nullptr;
-    uint32_t *pack_yg = nullptr;
-    size_t pack_lwe_words = 0, pack_pdig_words = 0, pack_wv_words = 0, pack_raw_words = 0, pack_yg_words = 0;
+    DevBuf<uint64_t> pack_lwe, pack_pdig, pack_wv;
+    DevBuf<ulonglong2> pack_raw;
+    DevBuf<uint32_t> pack_yg;
     // timing
     bool timing = false;
     struct EvTriple { hipEvent_t e0, e1, e2; };  // ext = e0 -> e1, crt = e1 -> e2
@@ -318,393 +332,356 @@ int32_t drain(sgfhe_ctx *c) {
     return SGFHE_OK;
 }
 
-// basis[b] -> the active fields
-void activate(sgfhe_ctx *c, int b) {
-    const sgfhe_ctx::Basis &S = c->basis[b];
-    c->active = b;
-    c->npr = S.npr;
-    memcpy(c->primes, S.primes, sizeof c->primes);
-    c->d_primes = S.d_primes;
-    c->d_crt = S.d_crt;
-    c->h_crt = S.h_crt;
-    c->d_lean = S.d_lean;
-    c->h_lean = S.h_lean;
-    c->lean_rnd_ok = S.lean_rnd_ok;
-    c->pack_G = S.pack_G;
-    c->pack_G_rnd = S.pack_G_rnd;
-    c->d_key = S.d_key;
-    c->key_bytes = S.key_bytes;
-}
-// the active fields (as build_basis / key_alloc leave them) -> basis[b]
-void save_basis(sgfhe_ctx *c, int b) {
-    sgfhe_ctx::Basis &S = c->basis[b];
-    S.npr = c->npr;
-    memcpy(S.primes, c->primes, sizeof S.primes);
-    S.d_primes = c->d_primes;
-    S.d_crt = c->d_crt;
-    S.h_crt = c->h_crt;
-    S.d_lean = c->d_lean;
-    S.h_lean = c->h_lean;
-    S.lean_rnd_ok = c->lean_rnd_ok;
-    S.pack_G = c->pack_G;
-    S.pack_G_rnd = c->pack_G_rnd;
-    S.d_key = c->d_key;
-    S.key_bytes = c->key_bytes;
-}
-// the basis of the present flatten mode
+// the basis everything reads: basis[active]
+sgfhe_ctx::Basis &cur(sgfhe_ctx *c) { return c->basis[c->active]; }
+const sgfhe_ctx::Basis &cur(const sgfhe_ctx *c) { return c->basis[c->active]; }
+// the basis of the present flatten mode, and the k-loop's mode word in it
 int mode_basis(const sgfhe_ctx *c) { return c->rnd ? c->nb - 1 : 0; }
+uint32_t flatten_mode(const sgfhe_ctx *c) { return c->rnd ? (MODE_RANDOM | ((c->B >> 46) ? MODE_WIDE : 0u)) : 0u; }
+// key slices per exact-accumulation group of the packing path in the present mode (0 = not available)
+uint32_t pack_group(const sgfhe_ctx *c) { return c->rnd ? cur(c).pack_G_rnd : cur(c).pack_G; }
+
+// ---- which kernels a launch takes ---------------------------------------------------------------
+// Pure functions of the ctx and the launch's own numbers.  The launchers below act on what they
+// return and hold no selection of their own; sgfhe_kernel_names formats the same values.
+
 // The quarter form of the latency kernels exists for m >= 4096 where the lean CRT kernel of the flatten mode does
 // (both modes; not the three-plane digit records of B >= 2^46, MODE_WIDE).
 bool quarter_ok(const sgfhe_ctx *c, uint32_t mode) {
     return c->logm >= 12 && c->split_max &&
-           (mode == 0u ? c->h_lean.nl != 0 : (mode == MODE_RANDOM && c->lean_rnd_ok));
+           (mode == 0u ? cur(c).h_lean.nl != 0 : (mode == MODE_RANDOM && cur(c).lean_rnd_ok));
 }
 // Largest chain the fused quarter kernel takes: one workgroup per (gate, prime, quarter), one round of the
 // device's 256 compute units (12 gates on five primes, 10 on six); 0 where it does not exist (m < 4096,
-// m = 16384: kernels.h) or is switched off.
+// m = 16384, where its workgroup of 1024 threads leaves 128 registers per thread and spills: kernels.h) or
+// is switched off.
 uint32_t fused_cap(const sgfhe_ctx *c, uint32_t mode) {
     if (!c->fused_min || c->small_padded || (c->logm != 12 && c->logm != 13) || !quarter_ok(c, mode)) return 0;
-    return 256u / (c->npr * 4u);
+    return 256u / (cur(c).npr * 4u);
 }
-bool fused_takes(const sgfhe_ctx *c, uint32_t cnt, uint32_t mode) { return cnt >= c->fused_min && cnt <= fused_cap(c, mode); }
+
+// The external product of one chunk of `cb` bootstraps (`cpad`: padded to a multiple of 8).
+enum class ExtKind {
+    Throughput,   // k_extprod: one workgroup per (bootstrap, prime)
+    Small,        // k_fwd_phase + k_inv_column: six
+    Quarter,      // k_fwd_quarter + k_inv_quarter: each transform cut across four workgroups
+    Fused         // k_ext_quarter: the quarter pair as one launch
+};
+struct ExtForm {
+    ExtKind kind;
+    uint32_t cnt;   // gates the grids (the CRT's too) are sized by
+    bool quarter() const { return kind == ExtKind::Quarter || kind == ExtKind::Fused; }
+};
+ExtForm ext_form(const sgfhe_ctx *c, uint32_t mode, uint32_t cb, uint32_t cpad, bool has_zpart) {
+    const bool small = cpad <= c->small_max && has_zpart;
+    // (the small-batch kernels index bootstraps directly: no padding to a multiple of 8, which is
+    // k_extprod's XCD mapping's; a one-gate call then runs one gate's workgroups, not eight's)
+    const uint32_t cnt = small && !c->small_padded ? cb : cpad;
+    if (small && cnt >= c->fused_min && cnt <= fused_cap(c, mode)) return {ExtKind::Fused, cnt};
+    // a few gates, m >= 4096
+    if (small && quarter_ok(c, mode) && cnt <= c->split_max) return {ExtKind::Quarter, cnt};
+    return {small ? ExtKind::Small : ExtKind::Throughput, cnt};
+}
+
+// The CRT of `total` coefficients.
+enum class CrtKind { Lean, LeanRnd, Acc2, Acc };   // k_crt_lean*, k_crt_lean_rnd*, k_crt_acc2, k_crt_acc
+struct CrtForm {
+    CrtKind kind;
+    uint32_t np, nl;   // template arguments: primes, and (lean kinds) 29-bit limbs of Q
+    bool wide;         // LeanRnd: digit records with a third plane
+    bool rows;         // LeanRnd, Acc: a gathered call, every row on the draw stream of the ctx it came in on (RndRow)
+    bool p87;          // Lean: the crt_lean87_one instantiation k_crt_lean<5, 3, true>
+    bool one;          // lean kinds: one coefficient per thread (k_crt_lean1, k_crt_lean_rnd1), not four
+    bool quarter;      // lean kinds: partial residues in, the last two inverse stages inside (k_crt_lean1q, k_crt_lean_rnd1)
+    uint32_t per_thread() const { return kind == CrtKind::Acc2 ? 2u : (kind == CrtKind::Acc || one) ? 1u : 4u; }
+};
+// `quarter`: the chunk's external product took the quarter form (ExtForm::quarter(): the mode's lean kernel exists)
+CrtForm crt_form(const sgfhe_ctx *c, uint32_t mode, uint32_t total, bool rows, bool quarter = false) {
+    const sgfhe_ctx::Basis &S = cur(c);
+    CrtForm f = {CrtKind::Acc, S.npr, S.h_lean.nl, false, false, false, false, quarter};
+    if (quarter) {
+        f.kind = (mode & MODE_RANDOM) ? CrtKind::LeanRnd : CrtKind::Lean;
+        f.one = true;
+    } else if (mode == 0u && S.h_lean.nl != 0) {
+        // the k-loop's own case (deterministic flatten, accumulator present): the integer-only kernel, four
+        // coefficients per thread -- one for a handful of gates (the latency form: four times the threads)
+        f.kind = CrtKind::Lean;
+        f.one = total <= c->crt1_max;
+        f.p87 = !f.one && S.npr == 5 && S.h_lean.p87;
+    } else if ((mode & ~MODE_WIDE) == MODE_RANDOM && S.lean_rnd_ok) {
+        // the same for the randomised flatten (the k-loop's modes MODE_RANDOM and MODE_RANDOM | MODE_WIDE)
+        f.kind = CrtKind::LeanRnd;
+        f.wide = (mode & MODE_WIDE) != 0;
+        f.one = !f.wide && total <= c->crt1_max;
+    } else if (mode == 0u) {
+        f.kind = CrtKind::Acc2;   // parameter sets outside the lean kernel's bounds (B < 2^12, Q < 2^30): two per thread
+    }                             // every other mode: the general kernel
+    f.rows = rows && (f.kind == CrtKind::LeanRnd || f.kind == CrtKind::Acc);
+    return f;
+}
 
 size_t lds_bytes(int logm, int npoly) { return (size_t)npoly * ((size_t)4 << logm); }
 // points per thread of k_extprod: 16, or 8 where 16 would leave half a wavefront idle (m <= 512)
 template <int LOGM> constexpr int ext_loge() { return LOGM <= EXT_LE3_MAX ? 3 : LOGE; }
 template <int LOGM> constexpr int threads_of() { return NttGeom<LOGM, LOGE>::T; }
 
-// ---- per-LOGM dispatch ------------------------------------------------------------------------
+// ---- one dispatcher per template axis -------------------------------------------------------------
+// Each hands the run-time value to a generic lambda as a compile-time constant.  What a lambda
+// instantiates is what the library holds: kernels that exist for part of an axis only are kept out
+// with `if constexpr` at the launch.
 
-#define SGFHE_FOR_LOGM(X) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14)
-
-template <int LOGM>
-int32_t launch_extprod_t(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk,
-                         uint32_t cpad, uint32_t k, uint32_t mode, hipStream_t st) {
-    const size_t lds = lds_bytes(LOGM, 2);  // exchange buffer + z1 accumulator
-    if (!(c->attr_done & ATTR_EXTPROD)) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_extprod<LOGM, ext_loge<LOGM>()>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_extprod<LOGM, ext_loge<LOGM>(), true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->attr_done |= ATTR_EXTPROD;
+template <class F> int32_t with_logm(sgfhe_ctx *c, F &&f) {
+    switch (c->logm) {
+#define X(LM) case LM: return f(std::integral_constant<int, LM>{});
+        X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14)
+#undef X
     }
-    if (mode & MODE_WIDE)   // digit planes with a third plane (randomised flatten, B >= 2^46)
-        hipLaunchKernelGGL((k_extprod<LOGM, ext_loge<LOGM>(), true>), dim3(cpad * c->npr),
-                           dim3(NttGeom<LOGM, ext_loge<LOGM>()>::T), lds, st, L.dig,
-                           keyk, L.yres, L.ua, c->d_primes, k, c->n, mode);
-    else
-        hipLaunchKernelGGL((k_extprod<LOGM, ext_loge<LOGM>()>), dim3(cpad * c->npr),
-                           dim3(NttGeom<LOGM, ext_loge<LOGM>()>::T), lds, st, L.dig,
-                           keyk, L.yres, L.ua, c->d_primes, k, c->n, mode);
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
+    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
 }
+// (the CRT kernels are compiled once per prime count: their residue loops are unrolled)
+template <class F> int32_t with_npr(sgfhe_ctx *c, uint32_t npr, F &&f) {
+    switch (npr) {
+#define X(NP) case NP: return f(std::integral_constant<int, NP>{});
+        X(2) X(3) X(4) X(5) X(6) X(7)
+#undef X
+    }
+    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported number of RNS primes");
+}
+template <class F> void with_nl(uint32_t nl, F &&f) {
+    switch (nl) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+template <class F> void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// ---- launchers --------------------------------------------------------------------------------
+
 int32_t launch_extprod(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cpad,
                        uint32_t k, uint32_t mode, hipStream_t st) {
-    switch (c->logm) {
-#define X(LM) case LM: return launch_extprod_t<LM>(c, L, keyk, cpad, k, mode, st);
-        SGFHE_FOR_LOGM(X)
-#undef X
-    }
-    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
-}
-
-template <int LOGM>
-int32_t launch_small_t(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cpad,
-                       uint32_t k, uint32_t mode, hipStream_t st) {
-    // 8 points per thread while m / 8 threads fit a workgroup, else the engine's 16
-    constexpr int LE = (LOGM - 3 <= 10 && LOGM >= 9) ? 3 : LOGE;
-    constexpr int TH = NttGeom<LOGM, LE>::T;
-    const size_t lds = lds_bytes(LOGM, 1);
-    if (!(c->attr_done & ATTR_SMALL)) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_fwd_phase<LOGM, LE>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_fwd_phase<LOGM, LE, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_inv_column<LOGM, LE>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->attr_done |= ATTR_SMALL;
-    }
-    // (Round 4 measured the per-prime records passed by value in the kernel arguments instead of
-    // through this pointer -- one dependent load less at the head of each launch: 24.75 against
-    // 24.74 ms per call, no change, profiles/r04_exp_small_args.txt.)
-    PrimeSet ps = c->d_primes;
-    if (mode & MODE_WIDE)
-        hipLaunchKernelGGL((k_fwd_phase<LOGM, LE, true>), dim3(cpad * c->npr * 4), dim3(TH), lds, st, L.dig,
-                           keyk, L.zpart, ps, mode);
-    else
-        hipLaunchKernelGGL((k_fwd_phase<LOGM, LE>), dim3(cpad * c->npr * 4), dim3(TH), lds, st, L.dig,
-                           keyk, L.zpart, ps, mode);
-    hipLaunchKernelGGL((k_inv_column<LOGM, LE>), dim3(cpad * c->npr * 2), dim3(TH), lds, st, L.zpart,
-                       L.yres, L.ua, ps, k, c->n);
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
-}
-int32_t launch_small(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cpad,
-                     uint32_t k, uint32_t mode, hipStream_t st) {
-    switch (c->logm) {
-#define X(LM) case LM: return launch_small_t<LM>(c, L, keyk, cpad, k, mode, st);
-        SGFHE_FOR_LOGM(X)
-#undef X
-    }
-    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
-}
-
-// The quarter form of the two transform kernels (kernels.h k_fwd_quarter / k_inv_quarter), m >= 4096.
-template <int LOGM>
-int32_t launch_quarter_t(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cnt,
-                         uint32_t k, uint32_t mode, hipStream_t st) {
-    if constexpr (LOGM >= 12) {
-        constexpr int LE = 3;
-        constexpr int TH = NttGeom<LOGM - 2, LE>::T;
-        // both transform kernels in one launch (kernels.h k_ext_quarter); at m = 16384 its workgroup of 1024
-        // threads leaves 128 registers per thread and spills: that ring keeps the two launches
-        if constexpr (LOGM <= 13) if (fused_takes(c, cnt, mode)) {
-            const size_t ldsf = (size_t)6 * (sizeof(uint32_t) << (LOGM - 2));
-            if (!(c->attr_done & ATTR_FUSED)) {
-                HIPCHK(c, hipFuncSetAttribute((const void *)k_ext_quarter<LOGM, LE>,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf));
-                c->attr_done |= ATTR_FUSED;
-            }
-            hipLaunchKernelGGL((k_ext_quarter<LOGM, LE>), dim3(cnt * c->npr * 4), dim3(2 * TH), ldsf, st, L.dig, keyk,
-                               reinterpret_cast<int32_t *>(L.yres), L.ua, c->d_primes, mode, k, c->n);
-            HIPCHK(c, hipGetLastError());
-            return SGFHE_OK;
+    return with_logm(c, [&](auto lm) -> int32_t {
+        constexpr int LOGM = decltype(lm)::value, LE = ext_loge<LOGM>();
+        const size_t lds = lds_bytes(LOGM, 2);  // exchange buffer + z1 accumulator
+        if (!(c->attr_done & ATTR_EXTPROD)) {
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_extprod<LOGM, LE, false>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_extprod<LOGM, LE, true>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            c->attr_done |= ATTR_EXTPROD;
         }
-        const size_t lds = lds_bytes(LOGM - 2, 1);
-        hipLaunchKernelGGL((k_fwd_quarter<LOGM, LE>), dim3(cnt * c->npr * 16), dim3(TH), lds, st, L.dig, keyk,
-                           L.zpart, c->d_primes, mode);
-        hipLaunchKernelGGL((k_inv_quarter<LOGM, LE>), dim3(cnt * c->npr * 8), dim3(TH), lds, st, L.zpart,
-                           reinterpret_cast<int32_t *>(L.yres), L.ua, c->d_primes, k, c->n);
+        with_bool(mode & MODE_WIDE, [&](auto wide) {   // digit planes with a third plane (randomised flatten, B >= 2^46)
+            hipLaunchKernelGGL((k_extprod<LOGM, LE, decltype(wide)::value>), dim3(cpad * cur(c).npr),
+                               dim3(NttGeom<LOGM, LE>::T), lds, st, L.dig, keyk, L.yres, L.ua, cur(c).d_primes, k,
+                               c->n, mode);
+        });
         HIPCHK(c, hipGetLastError());
         return SGFHE_OK;
-    } else {
-        return fail(c, SGFHE_ERR_UNSUPPORTED, "quarter form needs m >= 4096");
-    }
-}
-int32_t launch_quarter(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cnt, uint32_t k,
-                       uint32_t mode, hipStream_t st) {
-    switch (c->logm) {
-#define X(LM) case LM: return launch_quarter_t<LM>(c, L, keyk, cnt, k, mode, st);
-        SGFHE_FOR_LOGM(X)
-#undef X
-    }
-    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
+    });
 }
 
-template <int LOGM>
-int32_t launch_shortprod_t(sgfhe_ctx *c, const uint64_t *pdig, uint32_t *yg, uint32_t count,
-                           uint32_t G, uint32_t groups, uint32_t mode, hipStream_t st) {
-    const size_t lds = lds_bytes(LOGM, 2);
-    if (!(c->attr_done & ATTR_SHORTPROD)) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k_shortprod<LOGM>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->attr_done |= ATTR_SHORTPROD;
-    }
-    hipLaunchKernelGGL(k_shortprod<LOGM>, dim3(count * groups * c->npr), dim3(threads_of<LOGM>()), lds,
-                       st, pdig, c->d_key, yg, c->d_primes, c->d_crt, c->n, G, groups, mode);
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
+int32_t launch_small(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cnt,
+                     uint32_t k, uint32_t mode, hipStream_t st) {
+    return with_logm(c, [&](auto lm) -> int32_t {
+        constexpr int LOGM = decltype(lm)::value;
+        // 8 points per thread while m / 8 threads fit a workgroup, else the engine's 16
+        constexpr int LE = (LOGM - 3 <= 10 && LOGM >= 9) ? 3 : LOGE;
+        constexpr int TH = NttGeom<LOGM, LE>::T;
+        const size_t lds = lds_bytes(LOGM, 1);
+        if (!(c->attr_done & ATTR_SMALL)) {
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_fwd_phase<LOGM, LE, false>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_fwd_phase<LOGM, LE, true>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_inv_column<LOGM, LE>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            c->attr_done |= ATTR_SMALL;
+        }
+        // (Round 4 measured the per-prime records passed by value in the kernel arguments instead of
+        // through this pointer -- one dependent load less at the head of each launch: 24.75 against
+        // 24.74 ms per call, no change, profiles/r04_exp_small_args.txt.)
+        PrimeSet ps = cur(c).d_primes;
+        const uint32_t npr = cur(c).npr;
+        with_bool(mode & MODE_WIDE, [&](auto wide) {
+            hipLaunchKernelGGL((k_fwd_phase<LOGM, LE, decltype(wide)::value>), dim3(cnt * npr * 4), dim3(TH), lds, st,
+                               L.dig, keyk, L.zpart, ps, mode);
+        });
+        hipLaunchKernelGGL((k_inv_column<LOGM, LE>), dim3(cnt * npr * 2), dim3(TH), lds, st, L.zpart,
+                           L.yres, L.ua, ps, k, c->n);
+        HIPCHK(c, hipGetLastError());
+        return SGFHE_OK;
+    });
 }
+
+// The quarter form of the two transform kernels (kernels.h k_fwd_quarter / k_inv_quarter), m >= 4096;
+// `fused`: both in one launch (kernels.h k_ext_quarter), m = 4096 and 8192.
+int32_t launch_quarter(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, uint32_t cnt, bool fused,
+                       uint32_t k, uint32_t mode, hipStream_t st) {
+    return with_logm(c, [&](auto lm) -> int32_t {
+        constexpr int LOGM = decltype(lm)::value;
+        if constexpr (LOGM >= 12) {
+            constexpr int LE = 3;
+            constexpr int TH = NttGeom<LOGM - 2, LE>::T;
+            const sgfhe_ctx::Basis &S = cur(c);
+            if constexpr (LOGM <= 13) if (fused) {
+                const size_t ldsf = (size_t)6 * (sizeof(uint32_t) << (LOGM - 2));
+                if (!(c->attr_done & ATTR_FUSED)) {
+                    HIPCHK(c, hipFuncSetAttribute((const void *)k_ext_quarter<LOGM, LE>,
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf));
+                    c->attr_done |= ATTR_FUSED;
+                }
+                hipLaunchKernelGGL((k_ext_quarter<LOGM, LE>), dim3(cnt * S.npr * 4), dim3(2 * TH), ldsf, st, L.dig, keyk,
+                                   reinterpret_cast<int32_t *>(L.yres), L.ua, S.d_primes, mode, k, c->n);
+                HIPCHK(c, hipGetLastError());
+                return SGFHE_OK;
+            }
+            const size_t lds = lds_bytes(LOGM - 2, 1);
+            hipLaunchKernelGGL((k_fwd_quarter<LOGM, LE>), dim3(cnt * S.npr * 16), dim3(TH), lds, st, L.dig, keyk,
+                               L.zpart, S.d_primes, mode);
+            hipLaunchKernelGGL((k_inv_quarter<LOGM, LE>), dim3(cnt * S.npr * 8), dim3(TH), lds, st, L.zpart,
+                               reinterpret_cast<int32_t *>(L.yres), L.ua, S.d_primes, k, c->n);
+            HIPCHK(c, hipGetLastError());
+            return SGFHE_OK;
+        } else {
+            return fail(c, SGFHE_ERR_UNSUPPORTED, "quarter form needs m >= 4096");
+        }
+    });
+}
+
+// the external product of one chunk in the form the selector chose
+int32_t launch_ext(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk, ExtForm f, uint32_t k,
+                   uint32_t mode, hipStream_t st) {
+    switch (f.kind) {
+    case ExtKind::Throughput: return launch_extprod(c, L, keyk, f.cnt, k, mode, st);
+    case ExtKind::Small: return launch_small(c, L, keyk, f.cnt, k, mode, st);
+    default: return launch_quarter(c, L, keyk, f.cnt, f.kind == ExtKind::Fused, k, mode, st);
+    }
+}
+
 int32_t launch_shortprod(sgfhe_ctx *c, const uint64_t *pdig, uint32_t *yg, uint32_t count,
                          uint32_t G, uint32_t groups, uint32_t mode, hipStream_t st) {
-    switch (c->logm) {
-#define X(LM) case LM: return launch_shortprod_t<LM>(c, pdig, yg, count, G, groups, mode, st);
-        SGFHE_FOR_LOGM(X)
-#undef X
-    }
-    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
+    return with_logm(c, [&](auto lm) -> int32_t {
+        constexpr int LOGM = decltype(lm)::value;
+        const sgfhe_ctx::Basis &S = cur(c);
+        const size_t lds = lds_bytes(LOGM, 2);
+        if (!(c->attr_done & ATTR_SHORTPROD)) {
+            HIPCHK(c, hipFuncSetAttribute((const void *)k_shortprod<LOGM>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            c->attr_done |= ATTR_SHORTPROD;
+        }
+        hipLaunchKernelGGL(k_shortprod<LOGM>, dim3(count * groups * S.npr), dim3(threads_of<LOGM>()), lds,
+                           st, pdig, S.d_key, yg, S.d_primes, S.d_crt, c->n, G, groups, mode);
+        HIPCHK(c, hipGetLastError());
+        return SGFHE_OK;
+    });
 }
 
-template <int LOGM>
-int32_t launch_keygen_ntt_t(sgfhe_ctx *c, const uint64_t *d_sk, int32_t *d_shat,
-                            const ulonglong2 *d_acan, uint32_t *d_y, uint32_t R, bool shat_pass,
-                            hipStream_t st) {
-    if (shat_pass)
-        hipLaunchKernelGGL(k_shat<LOGM>, dim3(c->npr), dim3(threads_of<LOGM>()), lds_bytes(LOGM, 1), st,
-                           d_sk, d_shat, c->d_primes, c->n);
-    else
-        hipLaunchKernelGGL(k_polymul_s<LOGM>, dim3(R * c->npr), dim3(threads_of<LOGM>()),
-                           lds_bytes(LOGM, 1), st, d_acan, d_shat, d_y, c->d_primes, c->d_crt);
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
-}
 int32_t launch_keygen_ntt(sgfhe_ctx *c, const uint64_t *d_sk, int32_t *d_shat,
                           const ulonglong2 *d_acan, uint32_t *d_y, uint32_t R, bool shat_pass,
                           hipStream_t st) {
-    switch (c->logm) {
-#define X(LM) case LM: return launch_keygen_ntt_t<LM>(c, d_sk, d_shat, d_acan, d_y, R, shat_pass, st);
-        SGFHE_FOR_LOGM(X)
-#undef X
-    }
-    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
-}
-
-template <int LOGM>
-int32_t launch_keytr_t(sgfhe_ctx *c, const ulonglong2 *canon, int32_t *keyhat, uint32_t poly0,
-                       uint32_t npolys, hipStream_t st) {
-    hipLaunchKernelGGL(k_key_transform<LOGM>, dim3(npolys * c->npr), dim3(threads_of<LOGM>()),
-                       lds_bytes(LOGM, 1), st, canon, keyhat, c->d_primes, c->d_crt, poly0,
-                       c->d_bad);
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
-}
-int32_t launch_keytr(sgfhe_ctx *c, const ulonglong2 *canon, int32_t *keyhat, uint32_t poly0,
-                     uint32_t npolys, hipStream_t st) {
-    switch (c->logm) {
-#define X(L) case L: return launch_keytr_t<L>(c, canon, keyhat, poly0, npolys, st);
-        SGFHE_FOR_LOGM(X)
-#undef X
-    }
-    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
-}
-
-template <int LOGM>
-int32_t launch_dbgntt_t(sgfhe_ctx *c, const uint32_t *in, uint32_t *out, uint32_t pi, int inverse,
-                        hipStream_t st) {
-    hipLaunchKernelGGL(k_debug_ntt<LOGM>, dim3(1), dim3(threads_of<LOGM>()), lds_bytes(LOGM, 1), st,
-                       in, out, c->d_primes, pi, (uint32_t)inverse);
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
-}
-int32_t launch_dbgntt(sgfhe_ctx *c, const uint32_t *in, uint32_t *out, uint32_t pi, int inverse,
-                      hipStream_t st) {
-    switch (c->logm) {
-#define X(L) case L: return launch_dbgntt_t<L>(c, in, out, pi, inverse, st);
-        SGFHE_FOR_LOGM(X)
-#undef X
-    }
-    return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported log2(m)");
-}
-
-// k_crt_acc is compiled once per prime count (its residue loops are unrolled)
-#define SGFHE_FOR_NPR(X) X(2) X(3) X(4) X(5) X(6) X(7)
-template <int NP>
-void launch_crt_lean_t(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32_t total, hipStream_t st) {
-    // a handful of gates (the latency form): one coefficient per thread, four times the threads
-    if (total <= c->crt1_max) {
-        const dim3 grid1((total + 255) / 256), block1(256);
-        switch (c->h_lean.nl) {
-        case 2: hipLaunchKernelGGL((k_crt_lean1<NP, 2>), grid1, block1, 0, st, yres, dig, c->d_lean, total, (uint32_t)c->logm); break;
-        case 3: hipLaunchKernelGGL((k_crt_lean1<NP, 3>), grid1, block1, 0, st, yres, dig, c->d_lean, total, (uint32_t)c->logm); break;
-        default: hipLaunchKernelGGL((k_crt_lean1<NP, 4>), grid1, block1, 0, st, yres, dig, c->d_lean, total, (uint32_t)c->logm); break;
-        }
-        return;
-    }
-    const dim3 grid((total / 4 + 255) / 256), block(256);
-    if (NP == 5 && c->h_lean.p87) {
-        hipLaunchKernelGGL((k_crt_lean<5, 3, true>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm);
-        return;
-    }
-    switch (c->h_lean.nl) {
-    case 2: hipLaunchKernelGGL((k_crt_lean<NP, 2>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm); break;
-    case 3: hipLaunchKernelGGL((k_crt_lean<NP, 3>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm); break;
-    default: hipLaunchKernelGGL((k_crt_lean<NP, 4>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm); break;
-    }
-}
-template <int NP, bool WIDE>
-void launch_crt_lean_rnd_t(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32_t total, hipStream_t st,
-                           RndArgs ra, uint32_t iter) {
-    // ROWS: a gathered call, every row on the draw stream of the ctx it came in on (kernels.h RndRow)
-#define SGFHE_RND1(NL, ROWS) hipLaunchKernelGGL((k_crt_lean_rnd1<NP, NL, false, ROWS>), grid1, block1, 0, st, yres, dig, c->d_lean, total, (uint32_t)c->logm, ra, iter, (const PrimeK *)nullptr)
-#define SGFHE_RND4(NL, ROWS) hipLaunchKernelGGL((k_crt_lean_rnd<NP, NL, WIDE, ROWS>), grid, block, 0, st, yres, dig, c->d_lean, total / 4, (uint32_t)c->logm, ra, iter)
-    if (!WIDE && total <= c->crt1_max) {   // the latency form: one coefficient per thread
-        const dim3 grid1((total + 255) / 256), block1(256);
-        switch (c->h_lean.nl) {
-        case 2: if (ra.rows) SGFHE_RND1(2, true); else SGFHE_RND1(2, false); break;
-        case 3: if (ra.rows) SGFHE_RND1(3, true); else SGFHE_RND1(3, false); break;
-        default: if (ra.rows) SGFHE_RND1(4, true); else SGFHE_RND1(4, false); break;
-        }
-        return;
-    }
-    const dim3 grid((total / 4 + 255) / 256), block(256);
-    switch (c->h_lean.nl) {
-    case 2: if (ra.rows) SGFHE_RND4(2, true); else SGFHE_RND4(2, false); break;
-    case 3: if (ra.rows) SGFHE_RND4(3, true); else SGFHE_RND4(3, false); break;
-    default: if (ra.rows) SGFHE_RND4(4, true); else SGFHE_RND4(4, false); break;
-    }
-#undef SGFHE_RND1
-#undef SGFHE_RND4
-}
-int32_t launch_crt_raw(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32_t total,
-                       uint32_t mode, hipStream_t st, RndArgs ra, uint32_t iter) {
-    // the k-loop's own case (deterministic flatten, accumulator present): the integer-only kernel,
-    // four coefficients per thread; every other mode, and parameter sets outside its bounds
-    // (B < 2^12, Q < 2^30), the general one
-    const bool lean = mode == 0u && c->h_lean.nl != 0;
-    // the same for the randomised flatten (the k-loop's modes MODE_RANDOM and MODE_RANDOM | MODE_WIDE)
-    const bool lean_rnd = (mode & ~MODE_WIDE) == MODE_RANDOM && c->lean_rnd_ok;
-    switch (c->npr) {
-#define X(NP)                                                                                     \
-    case NP:                                                                                      \
-        if (lean)                                                                                 \
-            launch_crt_lean_t<NP>(c, yres, dig, total, st);                                       \
-        else if (lean_rnd && (mode & MODE_WIDE))                                                  \
-            launch_crt_lean_rnd_t<NP, true>(c, yres, dig, total, st, ra, iter);                   \
-        else if (lean_rnd)                                                                        \
-            launch_crt_lean_rnd_t<NP, false>(c, yres, dig, total, st, ra, iter);                  \
-        else if (mode == 0u) /* two coefficients per thread */                                   \
-            hipLaunchKernelGGL(k_crt_acc2<NP>, dim3((total / 2 + 255) / 256), dim3(256), 0, st,   \
-                               yres, dig, c->d_crt, total / 2, (uint32_t)c->logm);                \
-        else if (ra.rows)                                                                         \
-            hipLaunchKernelGGL((k_crt_acc<NP, true>), dim3((total + 255) / 256), dim3(256), 0, st, yres, \
-                               dig, c->d_crt, total, (uint32_t)c->logm, mode, ra, iter);          \
-        else                                                                                      \
-            hipLaunchKernelGGL((k_crt_acc<NP, false>), dim3((total + 255) / 256), dim3(256), 0, st, yres, \
-                               dig, c->d_crt, total, (uint32_t)c->logm, mode, ra, iter);          \
-        break;
-        SGFHE_FOR_NPR(X)
-#undef X
-    default: return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported number of RNS primes");
-    }
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
-}
-int32_t launch_crt(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, uint32_t cpad, uint32_t mode,
-                   hipStream_t st, RndArgs ra = RndArgs{}, uint32_t iter = 0) {
-    return launch_crt_raw(c, L.yres, L.dig, cpad * 2 * c->M, mode, st, ra, iter);
-}
-
-// CRT kernel of the quarter form: partial residues in, the last two inverse stages inside
-int32_t launch_crt_quarter(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, uint32_t cnt, uint32_t mode, hipStream_t st,
-                           RndArgs ra, uint32_t iter) {
-    const uint32_t total = cnt * 2 * c->M;
-    const dim3 grid((total + 255) / 256), block(256);
-    const int32_t *yp = reinterpret_cast<const int32_t *>(L.yres);
-    if (mode & MODE_RANDOM) {   // the randomised flatten: one coefficient per thread here too (k_crt_lean_rnd1)
-#define SGFHE_RNDQ(NPQ, NL, ROWS) hipLaunchKernelGGL((k_crt_lean_rnd1<NPQ, NL, true, ROWS>), grid, block, 0, st, L.yres, L.dig, c->d_lean, total, (uint32_t)c->logm, ra, iter, c->d_primes)
-        switch (c->npr) {
-#define X(NP)                                                                                                     \
-        case NP:                                                                                                  \
-            switch (c->h_lean.nl) {                                                                               \
-            case 2: if (ra.rows) SGFHE_RNDQ(NP, 2, true); else SGFHE_RNDQ(NP, 2, false); break;                          \
-            case 3: if (ra.rows) SGFHE_RNDQ(NP, 3, true); else SGFHE_RNDQ(NP, 3, false); break;                          \
-            default: if (ra.rows) SGFHE_RNDQ(NP, 4, true); else SGFHE_RNDQ(NP, 4, false); break;                         \
-            }                                                                                                     \
-            break;
-            SGFHE_FOR_NPR(X)
-#undef X
-        default: return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported number of RNS primes");
-        }
-#undef SGFHE_RNDQ
+    return with_logm(c, [&](auto lm) -> int32_t {
+        constexpr int LOGM = decltype(lm)::value;
+        const sgfhe_ctx::Basis &S = cur(c);
+        if (shat_pass)
+            hipLaunchKernelGGL(k_shat<LOGM>, dim3(S.npr), dim3(threads_of<LOGM>()), lds_bytes(LOGM, 1), st,
+                               d_sk, d_shat, S.d_primes, c->n);
+        else
+            hipLaunchKernelGGL(k_polymul_s<LOGM>, dim3(R * S.npr), dim3(threads_of<LOGM>()),
+                               lds_bytes(LOGM, 1), st, d_acan, d_shat, d_y, S.d_primes, S.d_crt);
         HIPCHK(c, hipGetLastError());
         return SGFHE_OK;
-    }
-    switch (c->npr) {
-#define X(NP)                                                                                                     \
-    case NP:                                                                                                      \
-        switch (c->h_lean.nl) {                                                                                   \
-        case 2: hipLaunchKernelGGL((k_crt_lean1q<NP, 2>), grid, block, 0, st, yp, L.dig, c->d_primes, c->d_lean, total, (uint32_t)c->logm); break; \
-        case 3: hipLaunchKernelGGL((k_crt_lean1q<NP, 3>), grid, block, 0, st, yp, L.dig, c->d_primes, c->d_lean, total, (uint32_t)c->logm); break; \
-        default: hipLaunchKernelGGL((k_crt_lean1q<NP, 4>), grid, block, 0, st, yp, L.dig, c->d_primes, c->d_lean, total, (uint32_t)c->logm); break; \
-        }                                                                                                         \
-        break;
-        SGFHE_FOR_NPR(X)
-#undef X
-    default: return fail(c, SGFHE_ERR_UNSUPPORTED, "unsupported number of RNS primes");
-    }
+    });
+}
+
+int32_t launch_keytr(sgfhe_ctx *c, const ulonglong2 *canon, int32_t *keyhat, uint32_t poly0,
+                     uint32_t npolys, hipStream_t st) {
+    return with_logm(c, [&](auto lm) -> int32_t {
+        constexpr int LOGM = decltype(lm)::value;
+        hipLaunchKernelGGL(k_key_transform<LOGM>, dim3(npolys * cur(c).npr), dim3(threads_of<LOGM>()),
+                           lds_bytes(LOGM, 1), st, canon, keyhat, cur(c).d_primes, cur(c).d_crt, poly0,
+                           c->d_bad);
+        HIPCHK(c, hipGetLastError());
+        return SGFHE_OK;
+    });
+}
+
+int32_t launch_dbgntt(sgfhe_ctx *c, const uint32_t *in, uint32_t *out, uint32_t pi, int inverse,
+                      hipStream_t st) {
+    return with_logm(c, [&](auto lm) -> int32_t {
+        constexpr int LOGM = decltype(lm)::value;
+        hipLaunchKernelGGL(k_debug_ntt<LOGM>, dim3(1), dim3(threads_of<LOGM>()), lds_bytes(LOGM, 1), st,
+                           in, out, cur(c).d_primes, pi, (uint32_t)inverse);
+        HIPCHK(c, hipGetLastError());
+        return SGFHE_OK;
+    });
+}
+
+// The CRT of `total` coefficients in the form crt_form chooses (`quarter`: after a quarter-form external product).
+int32_t launch_crt_raw(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32_t total, uint32_t mode,
+                       hipStream_t st, RndArgs ra, uint32_t iter, bool quarter = false) {
+    const sgfhe_ctx::Basis &S = cur(c);
+    const CrtForm f = crt_form(c, mode, total, ra.rows != nullptr, quarter);
+    const uint32_t logm = (uint32_t)c->logm, work = total / f.per_thread();
+    const dim3 grid((work + 255) / 256), block(256);
+    const int32_t rc = with_npr(c, f.np, [&](auto np) -> int32_t {
+        constexpr int NP = decltype(np)::value;
+        switch (f.kind) {
+        case CrtKind::Acc2:
+            hipLaunchKernelGGL(k_crt_acc2<NP>, grid, block, 0, st, yres, dig, S.d_crt, work, logm);
+            break;
+        case CrtKind::Acc:
+            with_bool(f.rows, [&](auto rows) {
+                hipLaunchKernelGGL((k_crt_acc<NP, decltype(rows)::value>), grid, block, 0, st, yres, dig, S.d_crt, work,
+                                   logm, mode, ra, iter);
+            });
+            break;
+        case CrtKind::Lean:
+            with_nl(f.nl, [&](auto nl) {
+                constexpr int NL = decltype(nl)::value;
+                if (f.quarter)
+                    hipLaunchKernelGGL((k_crt_lean1q<NP, NL>), grid, block, 0, st, reinterpret_cast<const int32_t *>(yres),
+                                       dig, S.d_primes, S.d_lean, work, logm);
+                else if (f.one)
+                    hipLaunchKernelGGL((k_crt_lean1<NP, NL>), grid, block, 0, st, yres, dig, S.d_lean, work, logm);
+                else if (f.p87) {
+                    if constexpr (NP == 5 && NL == 3)
+                        hipLaunchKernelGGL((k_crt_lean<5, 3, true>), grid, block, 0, st, yres, dig, S.d_lean, work, logm);
+                } else
+                    hipLaunchKernelGGL((k_crt_lean<NP, NL>), grid, block, 0, st, yres, dig, S.d_lean, work, logm);
+            });
+            break;
+        case CrtKind::LeanRnd:
+            with_nl(f.nl, [&](auto nl) {
+                with_bool(f.rows, [&](auto rows) {
+                    constexpr int NL = decltype(nl)::value;
+                    constexpr bool ROWS = decltype(rows)::value;
+                    if (f.quarter)
+                        hipLaunchKernelGGL((k_crt_lean_rnd1<NP, NL, true, ROWS>), grid, block, 0, st, yres, dig, S.d_lean,
+                                           work, logm, ra, iter, S.d_primes);
+                    else if (f.one)
+                        hipLaunchKernelGGL((k_crt_lean_rnd1<NP, NL, false, ROWS>), grid, block, 0, st, yres, dig, S.d_lean,
+                                           work, logm, ra, iter, (const PrimeK *)nullptr);
+                    else
+                        with_bool(f.wide, [&](auto wide) {   // (k_crt_lean_rnd1 is never WIDE)
+                            hipLaunchKernelGGL((k_crt_lean_rnd<NP, NL, decltype(wide)::value, ROWS>), grid, block, 0, st,
+                                               yres, dig, S.d_lean, work, logm, ra, iter);
+                        });
+                });
+            });
+            break;
+        }
+        return SGFHE_OK;
+    });
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
     return SGFHE_OK;
+}
+int32_t launch_crt(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, uint32_t cnt, uint32_t mode, hipStream_t st,
+                   RndArgs ra = RndArgs{}, uint32_t iter = 0, bool quarter = false) {
+    return launch_crt_raw(c, L.yres, L.dig, cnt * 2 * c->M, mode, st, ra, iter, quarter);
 }
 
 // ---- buffers ------------------------------------------------------------------------------------
@@ -712,7 +689,7 @@ int32_t launch_crt_quarter(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, uint32_t cnt,
 uint32_t round_up8(uint32_t x) { return (x + 7u) & ~7u; }
 
 size_t per_bootstrap_bytes(const sgfhe_ctx *c) {
-    return (size_t)2 * c->M * sizeof(ulonglong2) + (size_t)2 * c->npr * c->M * 4 + (size_t)c->n * 4;
+    return (size_t)2 * c->M * sizeof(ulonglong2) + (size_t)2 * cur(c).npr * c->M * 4 + (size_t)c->n * 4;
 }
 
 // Default chunk: the per-iteration working set (digits + residues) of a chunk stays near the size
@@ -803,12 +780,12 @@ struct ChunkJob {
 // one-workgroup-per-CU grid-stride "rider" kernel -- costs the external product as much time
 // as the CRT takes alone)
 int32_t run_iterations(sgfhe_ctx *c, ChunkJob *jobs, int njobs, uint64_t n_iters, uint32_t mode) {
-    const size_t slice = (size_t)c->npr * 8 * c->M;
+    const size_t slice = (size_t)cur(c).npr * 8 * c->M;
+    const int32_t *key = cur(c).d_key;
     for (uint64_t k = 0; k < n_iters; k++) {
         for (int j = 0; j < njobs; j++) {
             const ChunkJob &J = jobs[j];
-            // few bootstraps: 6 workgroups per (bootstrap, prime) instead of 1 (k_fwd_phase / k_inv_column)
-            const bool small = J.cpad <= c->small_max && J.L->zpart != nullptr;
+            const ExtForm form = ext_form(c, mode, J.cb, J.cpad, J.L->zpart != nullptr);
             const bool sample = c->timing && J.sampled && (k % 64 == 1) && c->ev.size() < 2048;
             hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
             if (sample) {
@@ -820,19 +797,10 @@ int32_t run_iterations(sgfhe_ctx *c, ChunkJob *jobs, int njobs, uint64_t n_iters
             // (Round 4 also tried warming the next iteration's key slice from a second stream, one iteration
             // ahead, with k_fwd_phase's own workgroup -> XCD mapping: 18.06 / 19.01 / 20.85 ms against 17.94 /
             // 18.80 / 20.24 for 1 / 2 / 4 gates, no gain, profiles/r04_exp_prefetch.txt.)
-            // (the small-batch kernels index bootstraps directly: no padding to a multiple of 8, which is
-            // k_extprod's XCD mapping's; a one-gate call then runs one gate's workgroups, not eight's)
-            const uint32_t cnt = small && !c->small_padded ? J.cb : J.cpad;
-            // a few gates, deterministic flatten, m >= 4096: each transform cut across four workgroups
-            // (both flatten modes; not the three-plane digit records of B >= 2^46, MODE_WIDE)
-            const bool quarter = small && quarter_ok(c, mode) && (cnt <= c->split_max || fused_takes(c, cnt, mode));
-            int32_t rc = quarter ? launch_quarter(c, *J.L, c->d_key + k * slice, cnt, (uint32_t)k, mode, J.st)
-                         : small ? launch_small(c, *J.L, c->d_key + k * slice, cnt, (uint32_t)k, mode, J.st)
-                                 : launch_extprod(c, *J.L, c->d_key + k * slice, J.cpad, (uint32_t)k, mode, J.st);
+            int32_t rc = launch_ext(c, *J.L, key + k * slice, form, (uint32_t)k, mode, J.st);
             if (rc) return rc;
             if (sample) HIPCHK(c, hipEventRecord(e1, J.st));
-            rc = quarter ? launch_crt_quarter(c, *J.L, cnt, mode, J.st, J.ra, (uint32_t)k + 1)
-                         : launch_crt(c, *J.L, cnt, mode, J.st, J.ra, (uint32_t)k + 1);
+            rc = launch_crt(c, *J.L, form.cnt, mode, J.st, J.ra, (uint32_t)k + 1, form.quarter());
             if (rc) return rc;
             if (sample) {
                 HIPCHK(c, hipEventRecord(e2, J.st));
@@ -884,6 +852,7 @@ struct HostPipe {
                                           // [a1 rows | a2 rows | b1 | b2]; result rows as in `out`
     uint64_t *p_in, *p_out;               // page-locked mirrors of both, same layouts
     size_t out_row_words;                 // 3 (n + 1), twice that with SGFHE_FLAG_RAW_MODQ
+    bool dbg;                             // SGFHE_DEBUG_IO is set (read once per call, bootstrap_host)
 };
 
 int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, const uint64_t *a2,
@@ -892,7 +861,8 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
                          uint64_t *dig_out = nullptr, const HostPipe *hp = nullptr) {
     if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
     uint32_t chunk = c->chunk ? c->chunk : default_chunk(c);
-    const uint32_t mode = c->rnd ? (MODE_RANDOM | ((c->B >> 46) ? MODE_WIDE : 0u)) : 0u;
+    const uint32_t mode = flatten_mode(c);
+    CrtConst *const d_crt = cur(c).d_crt;
     if (!c->chunk && c->lanes == 2 && batch > 2 * (size_t)c->small_max) {
         // Automatic chunk size with two lanes: cut the batch into an even number of equal chunks no
         // larger than the default, so that both lanes are busy from the first bootstrap to the last
@@ -1018,12 +988,11 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
         return hipSuccess;
     };
     // SGFHE_DEBUG_IO=1: wall-clock phases of a pipelined host-pointer call
-    const bool dbg_io = hp && getenv("SGFHE_DEBUG_IO") != nullptr;
+    const bool dbg_io = hp && hp->dbg;
     // (Round 4 also measured collecting the results only at the end, all results after the last kernel,
     // and all inputs before the first kernel; this pipeline measured best, 1.003 x the device-resident
     // call: profiles/r04_exp_io_variants.txt.)
-    auto wall = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double tw0 = dbg_io ? wall() : 0.0;
+    const double tw0 = dbg_io ? wall_ms() : 0.0;
     double tw_first = 0.0, tw_wait = 0.0;
     for (size_t g0 = 0; g0 < batch; g0 += stride) {
         ChunkJob jobs[2];
@@ -1057,13 +1026,13 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
             const uint32_t tot = J.cpad * M;
             if (J.ra.rows)
                 hipLaunchKernelGGL(k_init<true>, dim3((tot + 255) / 256), dim3(256), 0, J.st, ja1, jb1, ja2, jb2,
-                                   J.L->dig, J.L->ua, c->d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra);
+                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra);
             else
                 hipLaunchKernelGGL(k_init<false>, dim3((tot + 255) / 256), dim3(256), 0, J.st, ja1, jb1, ja2, jb2,
-                                   J.L->dig, J.L->ua, c->d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra);
+                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra);
             HIPCHK(c, hipGetLastError());
         }
-        if (dbg_io && g0 == 0) tw_first = wall();
+        if (dbg_io && g0 == 0) tw_first = wall_ms();
         int32_t rc = run_iterations(c, jobs, njobs, n_iters, mode);
         if (rc) return rc;
         for (int j = 0; j < njobs; j++) {
@@ -1071,7 +1040,7 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
             if (acc_out) {
                 const uint32_t t2 = J.cb * 2 * M;
                 hipLaunchKernelGGL(k_dump_acc, dim3((t2 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                   acc_out + J.c0 * 2 * M, c->d_crt, t2, (uint32_t)c->logm, mode);
+                                   acc_out + J.c0 * 2 * M, d_crt, t2, (uint32_t)c->logm, mode);
                 HIPCHK(c, hipGetLastError());
             }
             if (dig_out) {
@@ -1083,7 +1052,7 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
             if (out) {
                 const uint32_t t3 = J.cb * (n + 1);
                 hipLaunchKernelGGL(k_final, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                   out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), c->d_crt, J.cb, n,
+                                   out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, J.cb, n,
                                    (uint32_t)c->logm, raw ? 1u : 0u, mode);
                 if (raw && (flags & SGFHE_FLAG_RAW_RNS2))  // residues leave as (v1, v2) pairs (rns.jl:16-18)
                     hipLaunchKernelGGL(k_canon_to_rns2, dim3((3 * t3 + 255) / 256), dim3(256), 0, J.st,
@@ -1108,9 +1077,9 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
         }
         // with this group queued, collect the results of the group before it
         if (hp) {
-            const double t = dbg_io ? wall() : 0.0;
+            const double t = dbg_io ? wall_ms() : 0.0;
             HIPCHK(c, drain_out(out_before));
-            if (dbg_io) tw_wait += wall() - t;
+            if (dbg_io) tw_wait += wall_ms() - t;
         }
     }
     if (two_lanes) {  // join
@@ -1134,17 +1103,17 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
         return SGFHE_OK;
     }
     if (hp) {
-        const double t1 = dbg_io ? wall() : 0.0;
+        const double t1 = dbg_io ? wall_ms() : 0.0;
         double t2 = 0.0;
         if (dbg_io && !outq.empty()) {   // the last chunks' kernels are done when their download may start
             (void)hipEventSynchronize(c->ev_done);
-            t2 = wall();
+            t2 = wall_ms();
         }
         HIPCHK(c, drain_out(outq.size()));
         if (dbg_io)
             fprintf(stderr, "[sgfhe io] pipelined call of %zu: first chunks staged and queued after %.2f ms, all queued after "
                     "%.2f ms (of which %.2f waiting for earlier results), last kernel done at %.2f, results in the "
-                    "caller's array at %.2f\n", batch, tw_first - tw0, t1 - tw0, tw_wait, t2 - tw0, wall() - tw0);
+                    "caller's array at %.2f\n", batch, tw_first - tw0, t1 - tw0, tw_wait, t2 - tw0, wall_ms() - tw0);
     }
     return SGFHE_OK;
 }
@@ -1152,14 +1121,13 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
 // ---- constants -------------------------------------------------------------------------------------
 
 // One basis: everything that depends on which primes are in use -- CRT / flatten constants, the
-// per-prime records, the twiddle tables of primes not yet on the device.  Leaves the result in the
-// ctx's active fields (the caller saves them into basis[b]).
-int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, double log_have, double log_mbq) {
+// per-prime records, the twiddle tables of primes not yet on the device -- into S (its key comes later).
+int32_t build_basis(sgfhe_ctx *c, sgfhe_ctx::Basis &S, uint32_t npr, const uint32_t *cand_primes, double log_have, double log_mbq) {
     const uint32_t M = c->M;
     const int logm = c->logm;
     const u128 Q = c->Q, B = c->B;
-    c->npr = npr;
-    for (uint32_t i = 0; i < npr; i++) c->primes[i] = cand_primes[i];
+    S.npr = npr;
+    for (uint32_t i = 0; i < npr; i++) S.primes[i] = cand_primes[i];
     const int NPR = (int)npr;  // the loops below run over the primes in use
 
     // Packing (fhe.jl:683-687): G slices of two digit polynomials each are summed exactly before a
@@ -1172,8 +1140,8 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
             return G;
         };
         const double lg = log_have + log2(0.8) - log_mbq - 0.001;
-        c->pack_G = group(lg);
-        c->pack_G_rnd = group(lg - 2.0);
+        S.pack_G = group(lg);
+        S.pack_G_rnd = group(lg - 2.0);
     }
 
     // flatten constants (utils.jl:162-169)
@@ -1184,7 +1152,7 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
         return make_ulonglong2((uint64_t)(x % B), (uint64_t)(x / B));
     };
 
-    CrtConst &cc = c->h_crt;
+    CrtConst &cc = S.h_crt;
     memset(&cc, 0, sizeof cc);
     cc.Q = Q;
     cc.B = B;
@@ -1205,15 +1173,15 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
     cc.digP = digits_of(cc.DQ);
     cc.digN = digits_of((Q - cc.DQ) % Q);
     u128 cM = 1 % Q;
-    for (int i = 0; i < NPR; i++) cM = (cM * c->primes[i]) % Q;  // < 2^94 * 2^29
+    for (int i = 0; i < NPR; i++) cM = (cM * S.primes[i]) % Q;  // < 2^94 * 2^29
     for (int i = 0; i < NPR; i++) {
         u128 ci = 1 % Q;
         for (int j = 0; j < NPR; j++)
-            if (j != i) ci = (ci * c->primes[j]) % Q;
+            if (j != i) ci = (ci * S.primes[j]) % Q;
         cc.c[i] = ci;
-        cc.invp[i] = 1.0f / (float)c->primes[i];
+        cc.invp[i] = 1.0f / (float)S.primes[i];
     }
-    const uint32_t plast = c->primes[NPR - 1];
+    const uint32_t plast = S.primes[NPR - 1];
     const u128 cH = (cc.c[NPR - 1] * ((plast - 1) / 2)) % Q;
     for (int a = 0; a < 6 * NPR + 2; a++) cc.T[a] = (Q - (((u128)a * cM) % Q + cH) % Q) % Q;
     auto limbs = [](u128 v, uint32_t *w, int n) {
@@ -1225,7 +1193,7 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
     cc.Bd = u128_dbl(B);
 
     {   // k_crt_lean (kernels.h; tests/rns_model.py::CrtLean derives the same values)
-        CrtLean &K = c->h_lean;
+        CrtLean &K = S.h_lean;
         memset(&K, 0, sizeof K);
         int nq = 0, nb = 0;
         while (nq < 128 && (Q >> nq)) nq++;
@@ -1239,7 +1207,7 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
             };
             for (int i = 0; i < NPR; i++) {
                 lim(cc.c[i], K.c[i]);
-                K.w[i] = (uint32_t)((1ull << 58) / c->primes[i]);
+                K.w[i] = (uint32_t)((1ull << 58) / S.primes[i]);
             }
             lim((Q - cM % Q) % Q, K.cMn);
             K.hoff = (plast - 1) / 2;
@@ -1279,7 +1247,7 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
             // zero; and 6 B^2 has to stay far below the 2^34 Q of the residue sum for the quotient
             // estimate's width (tests/rns_model.py CrtLean.digits asserts both).  Reference
             // parameter sets have three limbs and B ~ sqrt(Q); others fall back to k_crt_acc.
-            c->lean_rnd_ok = (NL >= 3 || ((7 * B) >> 32) == 0 || K.B1 == 0) && B * B <= (Q << 27);
+            S.lean_rnd_ok = (NL >= 3 || ((7 * B) >> 32) == 0 || K.B1 == 0) && B * B <= (Q << 27);
             // crt_lean87_one: five primes, Q of 87 bits, B of 44 bits (Params(1024)); its register
             // widths and quotient estimates hold for every such Q and B
             // (tests/test_crt_lean87_model.py)
@@ -1301,7 +1269,7 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
     std::vector<PrimeK> pk(NPR);
     cc.npr = npr;
     for (int i = 0; i < NPR; i++) {
-        const uint32_t p = c->primes[i];
+        const uint32_t p = S.primes[i];
         if ((uint32_t)i >= c->tw_done) {   // (a second, smaller basis shares the tables of the first)
         uint32_t psi = 0;
         for (uint32_t x = 2; x < 2000 && !psi; x++) {
@@ -1379,7 +1347,7 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
         P.qmodp = centre32((uint32_t)(Q % p), p);
         uint32_t Mi = 1;  // (M_rns / p_i) mod p_i
         for (int j = 0; j < NPR; j++)
-            if (j != i) Mi = mulmod32(Mi, c->primes[j] % p, p);
+            if (j != i) Mi = mulmod32(Mi, S.primes[j] % p, p);
         const uint32_t ei = powmod32(Mi, p - 2, p);
         const uint32_t minv = powmod32(M % p, p - 2, p);
         const uint32_t kappa = mulmod32(mulmod32(R2, minv, p), ei, p);
@@ -1401,15 +1369,15 @@ int32_t build_basis(sgfhe_ctx *c, uint32_t npr, const uint32_t *cand_primes, dou
                             hipMemcpyHostToDevice));
         c->tw_done = npr;
     }
-    HIPCHK(c, hipMalloc(&c->d_primes, NPR * sizeof(PrimeK)));
-    c->shared->own(c->d_primes);
-    HIPCHK(c, hipMemcpy(c->d_primes, pk.data(), NPR * sizeof(PrimeK), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->d_crt, sizeof(CrtConst)));
-    c->shared->own(c->d_crt);
-    HIPCHK(c, hipMemcpy(c->d_crt, &cc, sizeof(CrtConst), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->d_lean, sizeof(CrtLean)));
-    c->shared->own(c->d_lean);
-    HIPCHK(c, hipMemcpy(c->d_lean, &c->h_lean, sizeof(CrtLean), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMalloc(&S.d_primes, NPR * sizeof(PrimeK)));
+    c->shared->own(S.d_primes);
+    HIPCHK(c, hipMemcpy(S.d_primes, pk.data(), NPR * sizeof(PrimeK), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMalloc(&S.d_crt, sizeof(CrtConst)));
+    c->shared->own(S.d_crt);
+    HIPCHK(c, hipMemcpy(S.d_crt, &cc, sizeof(CrtConst), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMalloc(&S.d_lean, sizeof(CrtLean)));
+    c->shared->own(S.d_lean);
+    HIPCHK(c, hipMemcpy(S.d_lean, &S.h_lean, sizeof(CrtLean), hipMemcpyHostToDevice));
     return SGFHE_OK;
 }
 
@@ -1488,26 +1456,25 @@ int32_t build_constants(sgfhe_ctx *c) {
     // the larger basis first: its pass puts every prime's twiddle tables on the device
     for (int b = c->nb - 1; b >= 0; b--) {
         const bool big = b == c->nb - 1 && c->nb == 2;
-        int32_t rc = build_basis(c, big ? npr_rnd : npr_det, cand_primes, big ? have_rnd : have_det, log_mbq);
+        int32_t rc = build_basis(c, c->basis[b], big ? npr_rnd : npr_det, cand_primes, big ? have_rnd : have_det, log_mbq);
         if (rc) return rc;
-        c->d_key = nullptr;
-        c->key_bytes = 0;
-        save_basis(c, b);
     }
-    activate(c, 0);
+    c->active = 0;
     return SGFHE_OK;
 }
 
-// Key uploads, generation and imports work on the LARGER basis (its key determines the other one);
-// key_finish derives the smaller basis's key from it and goes back to the basis of the present mode.
+// Key uploads, generation and imports work on the LARGER basis (its key determines the other one): key_basis().
+// key_begin makes it the active one for the writer's kernels; key_finish derives the smaller basis's key from it
+// and goes back to the basis of the present mode.
 // A key that clones share (sgfhe_ctx_clone) is read-only: their calls may be reading it on the device.
 int32_t key_begin(sgfhe_ctx *c) {
     if (c->shared.use_count() > 1)
         return fail(c, SGFHE_ERR_INVALID_ARG,
                     "the bootstrap key of this ctx is shared with clones (sgfhe_ctx_clone): destroy them before replacing it");
-    activate(c, c->nb - 1);
+    c->active = c->nb - 1;
     return SGFHE_OK;
 }
+sgfhe_ctx::Basis &key_basis(sgfhe_ctx *c) { return c->basis[c->nb - 1]; }
 // A key writer calls this once its arguments are accepted, before the first byte of the key changes:
 // from here to the end of key_finish the ctx has no key, so a writer that fails part-way (or whose second
 // key form cannot be derived) leaves a ctx that refuses to bootstrap instead of one whose two bases hold
@@ -1539,7 +1506,7 @@ int32_t key_finish(sgfhe_ctx *c, int32_t rc) {
         }
         if (e != hipSuccess) { rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); c->have_key = false; }
     }
-    activate(c, mode_basis(c));
+    c->active = mode_basis(c);
     return rc;
 }
 
@@ -1558,32 +1525,32 @@ struct KeyBlobHeader {
 static_assert(sizeof(KeyBlobHeader) == 64, "key blob header is 64 bytes");
 constexpr uint32_t SGFHE_KEY_BLOB_VERSION = 2;
 
-KeyBlobHeader blob_header(const sgfhe_ctx *c) {
+// (of the larger basis: the blob is its key)
+KeyBlobHeader blob_header(sgfhe_ctx *c) {
+    const sgfhe_ctx::Basis &S = key_basis(c);
     KeyBlobHeader h;
     memset(&h, 0, sizeof h);
     memcpy(h.magic, "SGFHEKEY", 8);
     h.version = SGFHE_KEY_BLOB_VERSION;
     h.n = c->n;
     h.m = c->M;
-    h.npr = c->npr;
+    h.npr = S.npr;
     h.Q[0] = (uint64_t)c->Q;
     h.Q[1] = (uint64_t)(c->Q >> 64);
     h.B = (uint64_t)c->B;
     uint64_t f = 0xcbf29ce484222325ull;
-    for (uint32_t i = 0; i < c->npr; i++)
-        for (int b = 0; b < 4; b++) { f ^= (c->primes[i] >> (8 * b)) & 0xffu; f *= 0x100000001b3ull; }
+    for (uint32_t i = 0; i < S.npr; i++)
+        for (int b = 0; b < 4; b++) { f ^= (S.primes[i] >> (8 * b)) & 0xffu; f *= 0x100000001b3ull; }
     h.prime_hash = f;
-    h.payload_bytes = (uint64_t)c->n * c->npr * 8 * c->M * 4;
+    h.payload_bytes = (uint64_t)c->n * S.npr * 8 * c->M * 4;
     return h;
 }
 
-int32_t key_alloc(sgfhe_ctx *c) {
-    if (c->d_key) return SGFHE_OK;
-    c->key_bytes = (size_t)c->n * c->npr * 8 * c->M * 4;
-    HIPCHK(c, hipMalloc(&c->d_key, c->key_bytes));
-    c->shared->own(c->d_key);
-    c->basis[c->active].d_key = c->d_key;
-    c->basis[c->active].key_bytes = c->key_bytes;
+int32_t key_alloc(sgfhe_ctx *c, sgfhe_ctx::Basis &S) {
+    if (S.d_key) return SGFHE_OK;
+    S.key_bytes = (size_t)c->n * S.npr * 8 * c->M * 4;
+    HIPCHK(c, hipMalloc(&S.d_key, S.key_bytes));
+    c->shared->own(S.d_key);
     return SGFHE_OK;
 }
 
@@ -1605,7 +1572,7 @@ int32_t key_transform_host(sgfhe_ctx *c, const uint64_t *canon, uint32_t npolys,
         if (rns2) {  // (v1, v2) limb pairs -> canonical residues, in place (rns.jl:32-40)
             const size_t cnt = (size_t)np * c->M;
             hipLaunchKernelGGL(k_rns2_to_canon, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0,
-                               c->stream, d_stage, cnt, *rns2, c->d_crt, c->d_bad);
+                               c->stream, d_stage, cnt, *rns2, cur(c).d_crt, c->d_bad);
         }
         rc = launch_keytr(c, d_stage, keyhat, p0, np, c->stream);
         if (rc) break;
@@ -1755,9 +1722,8 @@ int32_t sgfhe_ctx_clone(sgfhe_ctx *src, sgfhe_ctx **out) {
     c->split_max = src->split_max;
     c->fused_min = src->fused_min;
     c->use_pin = src->use_pin;
-    // its own: flatten mode (deterministic, call counter 0), lanes' work buffers, streams, events, staging,
-    // timing, the error string and the lock
-    activate(c, 0);
+    // its own: flatten mode (deterministic, call counter 0: active = 0), lanes' work buffers, streams, events,
+    // staging, timing, the error string and the lock
     // The runtime deals streams onto its hardware queues (GPU_MAX_HW_QUEUES = 4) in the order they are created, and
     // packets of one hardware queue run in order: with four streams per ctx, the FIRST stream of every ctx -- the
     // one its calls run on -- would sit on the same queue and calls on different clones could never overlap on the
@@ -1778,44 +1744,33 @@ int32_t sgfhe_ctx_clone(sgfhe_ctx *src, sgfhe_ctx **out) {
     return SGFHE_OK;
 }
 
-// the buffers of sgfhe_circuit_run (the caller has waited for the ctx's work)
+// the buffers of sgfhe_circuit_run[_ct] and of the packing path (the caller has waited for the ctx's work)
 static void free_circuit_buffers(sgfhe_ctx *c) {
-    if (c->circ_wires) (void)hipFree(c->circ_wires);
-    if (c->circ_stage) (void)hipFree(c->circ_stage);
-    if (c->circ_out) (void)hipFree(c->circ_out);
-    if (c->circ_tab) (void)hipFree(c->circ_tab);
-    c->circ_wires = c->circ_stage = c->circ_out = nullptr;
-    c->circ_tab = nullptr;
-    c->circ_wires_words = c->circ_stage_words = c->circ_out_words = c->circ_tab_words = 0;
-    if (c->circ_ct) (void)hipFree(c->circ_ct);
-    c->circ_ct = nullptr;
-    c->circ_ct_words = 0;
-    if (c->pack_lwe) (void)hipFree(c->pack_lwe);
-    if (c->pack_raw) (void)hipFree(c->pack_raw);
-    if (c->pack_pdig) (void)hipFree(c->pack_pdig);
-    if (c->pack_yg) (void)hipFree(c->pack_yg);
-    if (c->pack_wv) (void)hipFree(c->pack_wv);
-    c->pack_lwe = c->pack_pdig = c->pack_wv = nullptr;
-    c->pack_raw = nullptr;
-    c->pack_yg = nullptr;
-    c->pack_lwe_words = c->pack_pdig_words = c->pack_wv_words = c->pack_raw_words = c->pack_yg_words = 0;
+    c->circ_wires.release();
+    c->circ_stage.release();
+    c->circ_out.release();
+    c->circ_tab.release();
+    c->circ_ct.release();
+    c->pack_lwe.release();
+    c->pack_raw.release();
+    c->pack_pdig.release();
+    c->pack_yg.release();
+    c->pack_wv.release();
+}
+// ... and the staging of the host-pointer entry point
+static void free_io_buffers(sgfhe_ctx *c) {
+    c->io_in.release();
+    c->io_out.release();
+    c->pin_in.release();
+    c->pin_out.release();
 }
 
-// a device buffer of the ctx grown to at least `words` elements (its contents are not kept)
+// DevBuf::grow for the circuit and pack paths: out of device memory is their caller's error to handle
 extern "C++" template <typename T>
-static int32_t circ_grow(sgfhe_ctx *c, T *&buf, size_t &cap, size_t words) {
-    if (words <= cap) return SGFHE_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    if (hipMalloc(&buf, words * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run: hipMalloc of " + std::to_string(words * sizeof(T)) +
-                                          " bytes failed");
-    }
-    cap = words;
-    return SGFHE_OK;
+static int32_t circ_grow(sgfhe_ctx *c, DevBuf<T> &buf, size_t words) {
+    if (buf.grow(words) == hipSuccess) return SGFHE_OK;
+    return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run: hipMalloc of " + std::to_string(words * sizeof(T)) +
+                                      " bytes failed");
 }
 
 int32_t sgfhe_ctx_destroy(sgfhe_ctx *c) {
@@ -1837,13 +1792,10 @@ int32_t sgfhe_ctx_destroy(sgfhe_ctx *c) {
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->shared) c->shared->co.forget(c);
     c->shared.reset();   // constants, tables and key: freed with the last ctx that shares them
-    if (c->io_in) (void)hipFree(c->io_in);
-    if (c->io_out) (void)hipFree(c->io_out);
-    if (c->pin_in) (void)hipHostFree(c->pin_in);
-    if (c->pin_out) (void)hipHostFree(c->pin_out);
+    free_io_buffers(c);
     free_circuit_buffers(c);
     if (c->d_bad) (void)hipFree(c->d_bad);
-    if (c->d_rows) (void)hipFree(c->d_rows);
+    c->d_rows.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SGFHE_OK;
@@ -1870,7 +1822,7 @@ static int32_t set_random_flatten(sgfhe_ctx *c, int enable, const ChaChaKey &key
     c->rnd = enable != 0;
     c->rnd_key = key;
     c->rnd_call = 0;
-    activate(c, mode_basis(c));   // constants and key form of the mode's basis (queued work keeps its own)
+    c->active = mode_basis(c);   // constants and key form of the mode's basis (queued work keeps its own)
     return SGFHE_OK;
 }
 
@@ -1922,11 +1874,12 @@ static int32_t sgfhe_bkey_upload_impl(sgfhe_ctx *c, const uint64_t *canonical, s
     SGFHE_QUIESCE(c);
     const size_t expect = (size_t)c->n * 8 * c->M * 2;
     if (n_words != expect) return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload: n_words != n*8*m*2");
-    int32_t rc = key_alloc(c);
+    sgfhe_ctx::Basis &K = key_basis(c);
+    int32_t rc = key_alloc(c, K);
     if (rc) return rc;
     HIPCHK(c, hipMemset(c->d_bad, 0, sizeof(uint32_t)));
     key_dirty(c);
-    rc = key_transform_host(c, canonical, c->n * 8, c->d_key);
+    rc = key_transform_host(c, canonical, c->n * 8, K.d_key);
     if (rc) return rc;
     uint32_t bad = 0;
     HIPCHK(c, hipMemcpy(&bad, c->d_bad, sizeof bad, hipMemcpyDeviceToHost));
@@ -1962,7 +1915,8 @@ static int32_t sgfhe_bkey_generate_impl(sgfhe_ctx *c, const uint64_t *sk, size_t
         return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_generate: noise must be below 2^30 and below Q / 2");
     (void)hipSetDevice(c->device);
     SGFHE_QUIESCE(c);
-    int32_t rc = key_alloc(c);
+    sgfhe_ctx::Basis &K = key_basis(c);   // (the active one: key_begin)
+    int32_t rc = key_alloc(c, K);
     if (rc) return rc;
     key_dirty(c);
     const uint32_t M = c->M, rows = c->n * 4;
@@ -1976,8 +1930,8 @@ static int32_t sgfhe_bkey_generate_impl(sgfhe_ctx *c, const uint64_t *sk, size_t
     hipError_t e = hipSuccess;
     do {
         if ((e = hipMalloc(&d_sk, (size_t)c->n * 8))) break;
-        if ((e = hipMalloc(&d_shat, (size_t)c->npr * M * 4))) break;
-        if ((e = hipMalloc(&d_y, (size_t)R * c->npr * M * 4))) break;
+        if ((e = hipMalloc(&d_shat, (size_t)K.npr * M * 4))) break;
+        if ((e = hipMalloc(&d_y, (size_t)R * K.npr * M * 4))) break;
         if ((e = hipMalloc(&d_acan, (size_t)R * M * 16))) break;
         if ((e = hipMalloc(&d_prod, (size_t)R * M * 16))) break;
         if ((e = hipMalloc(&d_canon, (size_t)R * 2 * M * 16))) break;
@@ -1988,7 +1942,7 @@ static int32_t sgfhe_bkey_generate_impl(sgfhe_ctx *c, const uint64_t *sk, size_t
         for (uint32_t row0 = 0; row0 < rows && rc == SGFHE_OK; row0 += R) {
             const uint32_t tot = R * M;
             hipLaunchKernelGGL(k_keygen_draw, dim3((tot / 4 + 255) / 256), dim3(256), 0, c->stream,
-                               d_acan, d_e, c->d_crt, ck, noise, row0, R, (uint32_t)c->logm);
+                               d_acan, d_e, K.d_crt, ck, noise, row0, R, (uint32_t)c->logm);
             rc = launch_keygen_ntt(c, d_sk, d_shat, d_acan, d_y, R, false, c->stream);
             if (rc) break;
             // CRT of the exact product, canonical residues into d_prod ([row][m] 16-byte values)
@@ -1996,9 +1950,9 @@ static int32_t sgfhe_bkey_generate_impl(sgfhe_ctx *c, const uint64_t *sk, size_t
                                      MODE_NOACC | MODE_CANON, c->stream, RndArgs{}, 0u)))
                 break;
             hipLaunchKernelGGL(k_keygen_finish, dim3((tot + 255) / 256), dim3(256), 0, c->stream, d_acan,
-                               d_prod, d_e, d_sk, d_canon, c->d_crt, row0, R, (uint32_t)c->logm);
+                               d_prod, d_e, d_sk, d_canon, K.d_crt, row0, R, (uint32_t)c->logm);
             if ((e = hipGetLastError())) break;
-            rc = launch_keytr(c, d_canon, c->d_key, row0 * 2, R * 2, c->stream);
+            rc = launch_keytr(c, d_canon, K.d_key, row0 * 2, R * 2, c->stream);
         }
         if (rc || e) break;
         e = hipStreamSynchronize(c->stream);
@@ -2055,11 +2009,12 @@ static int32_t sgfhe_bkey_upload_rns2_impl(sgfhe_ctx *c, const uint64_t *pairs, 
     if (n_words != expect) return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload_rns2: bad n_words");
     int32_t rc = rns2_configure(c, m1, m2);
     if (rc) return rc;
-    rc = key_alloc(c);
+    sgfhe_ctx::Basis &K = key_basis(c);
+    rc = key_alloc(c, K);
     if (rc) return rc;
     HIPCHK(c, hipMemset(c->d_bad, 0, sizeof(uint32_t)));
     key_dirty(c);
-    rc = key_transform_host(c, pairs, c->n * 8, c->d_key, &c->rns2);
+    rc = key_transform_host(c, pairs, c->n * 8, K.d_key, &c->rns2);
     if (rc) return rc;
     uint32_t bad = 0;
     HIPCHK(c, hipMemcpy(&bad, c->d_bad, sizeof bad, hipMemcpyDeviceToHost));
@@ -2101,7 +2056,7 @@ int32_t sgfhe_rns2_convert(sgfhe_ctx *c, int to_pairs, const uint64_t *in, size_
             hipLaunchKernelGGL(k_canon_to_rns2, grid, dim3(256), 0, c->stream, d, count, c->rns2);
         else
             hipLaunchKernelGGL(k_rns2_to_canon, grid, dim3(256), 0, c->stream, d, count, c->rns2,
-                               c->d_crt, c->d_bad);
+                               cur(c).d_crt, c->d_bad);
         if ((e = hipGetLastError())) break;
         if ((e = hipMemcpyAsync(out, d, count * 16, hipMemcpyDeviceToHost, c->stream))) break;
         if ((e = hipMemcpyAsync(&bad, c->d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream))) break;
@@ -2125,27 +2080,19 @@ int32_t sgfhe_bkey_device_form_bytes(const sgfhe_ctx *c, size_t *bytes) {
     return SGFHE_OK;
 }
 
-static int32_t sgfhe_bkey_export_device_form_impl(sgfhe_ctx *c, void *dst) {
+int32_t sgfhe_bkey_export_device_form(sgfhe_ctx *c, void *dst) {
     if (!c || !dst) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
     if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
     (void)hipSetDevice(c->device);
     SGFHE_QUIESCE(c);
+    const sgfhe_ctx::Basis &K = key_basis(c);   // the blob is the key of the larger basis
     const KeyBlobHeader h = blob_header(c);
     HIPCHK(c, hipMemcpy(dst, &h, sizeof h, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpyAsync(static_cast<char *>(dst) + sizeof h, c->d_key, c->key_bytes,
+    HIPCHK(c, hipMemcpyAsync(static_cast<char *>(dst) + sizeof h, K.d_key, K.key_bytes,
                              hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SGFHE_OK;
-}
-
-int32_t sgfhe_bkey_export_device_form(sgfhe_ctx *c, void *dst) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    activate(c, c->nb - 1);   // the blob is the key of the larger basis
-    const int32_t rc = sgfhe_bkey_export_device_form_impl(c, dst);
-    activate(c, mode_basis(c));
-    return rc;
 }
 
 static int32_t sgfhe_bkey_import_device_form_impl(sgfhe_ctx *c, const void *src) {
@@ -2163,10 +2110,11 @@ static int32_t sgfhe_bkey_import_device_form_impl(sgfhe_ctx *c, const void *src)
     if (memcmp(&got, &want, sizeof want) != 0)
         return fail(c, SGFHE_ERR_INVALID_ARG,
                     "bkey_import: the blob belongs to another parameter set (n, m, Q, B or RNS primes differ)");
-    int32_t rc = key_alloc(c);
+    sgfhe_ctx::Basis &K = key_basis(c);
+    int32_t rc = key_alloc(c, K);
     if (rc) return rc;
     key_dirty(c);
-    HIPCHK(c, hipMemcpyAsync(c->d_key, static_cast<const char *>(src) + sizeof got, c->key_bytes,
+    HIPCHK(c, hipMemcpyAsync(K.d_key, static_cast<const char *>(src) + sizeof got, K.key_bytes,
                              hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_key = true;
@@ -2220,57 +2168,34 @@ static int32_t bootstrap_host(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
     const size_t in_words = 2 * batch * (n + 1);
     int32_t rc = drain(c);   // the staging buffers may be regrown: nothing of an earlier call may be in flight
     if (rc) return rc;
-    if (in_words > c->io_in_words) {
-        if (c->io_in) (void)hipFree(c->io_in);
-        c->io_in = nullptr;
-        c->io_in_words = 0;
-        HIPCHK(c, hipMalloc(&c->io_in, in_words * 8));
-        c->io_in_words = in_words;
-    }
-    if (out && out_words > c->io_out_words) {
-        if (c->io_out) (void)hipFree(c->io_out);
-        c->io_out = nullptr;
-        c->io_out_words = 0;
-        HIPCHK(c, hipMalloc(&c->io_out, out_words * 8));
-        c->io_out_words = out_words;
-    }
-    d_in = c->io_in;
-    if (out) d_out = c->io_out;
-    const bool dbg = getenv("SGFHE_DEBUG_IO") != nullptr;
+    HIPCHK(c, c->io_in.grow(in_words));
+    if (out) HIPCHK(c, c->io_out.grow(out_words));
+    d_in = c->io_in.p;
+    if (out) d_out = c->io_out.p;
+    const bool dbg = getenv("SGFHE_DEBUG_IO") != nullptr;   // wall-clock phases of the call on stderr
     // The production call (results only): page-locked mirrors of both staging buffers, grown on demand
     // and kept, and the copies pipelined chunk by chunk beside the kernels (HostPipe).  A failed
     // allocation, a buffer above PIN_MAX_BYTES, SGFHE_HOST_PIN=0 and the debug hooks take direct copies
     // of the caller's arrays.
     const size_t pin_max = pin_max_bytes();
     bool pipe = c->use_pin && out && !acc && !digs && in_words * 8 <= pin_max && out_words * 8 <= pin_max;
-    if (pipe && in_words > c->pin_in_words) {
-        if (c->pin_in) (void)hipHostFree(c->pin_in);
-        c->pin_in = nullptr;
-        c->pin_in_words = 0;
-        const hipError_t pe = hipHostMalloc(&c->pin_in, in_words * 8, hipHostMallocDefault);
-        if (pe == hipSuccess) c->pin_in_words = in_words;
-        else { (void)hipGetLastError(); c->pin_in = nullptr; pipe = false; }
-        if (dbg) fprintf(stderr, "[sgfhe io] pin_in %zu bytes: %s\n", in_words * 8, hipGetErrorString(pe));
-    }
-    if (pipe && out_words > c->pin_out_words) {
-        if (c->pin_out) (void)hipHostFree(c->pin_out);
-        c->pin_out = nullptr;
-        c->pin_out_words = 0;
-        const hipError_t pe = hipHostMalloc(&c->pin_out, out_words * 8, hipHostMallocDefault);
-        if (pe == hipSuccess) c->pin_out_words = out_words;
-        else { (void)hipGetLastError(); c->pin_out = nullptr; pipe = false; }
-        if (dbg) fprintf(stderr, "[sgfhe io] pin_out %zu bytes: %s\n", out_words * 8, hipGetErrorString(pe));
-    }
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
+    auto pin_grow = [&](DevBuf<uint64_t, true> &buf, size_t words, const char *name) {
+        if (!pipe || words <= buf.cap) return;
+        const hipError_t pe = buf.grow(words);
+        if (pe != hipSuccess) pipe = false;
+        if (dbg) fprintf(stderr, "[sgfhe io] %s %zu bytes: %s\n", name, words * 8, hipGetErrorString(pe));
+    };
+    pin_grow(c->pin_in, in_words, "pin_in");
+    pin_grow(c->pin_out, out_words, "pin_out");
+    const double t0 = wall_ms();
     if (pipe) {
-        const HostPipe hp = {a1, b1, a2, b2, out, d_in, d_out, c->pin_in, c->pin_out, out_row};
+        const HostPipe hp = {a1, b1, a2, b2, out, d_in, d_out, c->pin_in.p, c->pin_out.p, out_row, dbg};
         rc = bootstrap_device(c, nullptr, nullptr, nullptr, nullptr, batch, d_out, flags, n_iters, nullptr,
                               c->stream, nullptr, &hp);
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
         if (rc == SGFHE_OK) c->pending = false;
-        if (dbg) fprintf(stderr, "[sgfhe io] batch %zu pipelined: %.2f ms\n", batch, now() - t0);
+        if (dbg) fprintf(stderr, "[sgfhe io] batch %zu pipelined: %.2f ms\n", batch, wall_ms() - t0);
         return rc;
     }
     hipError_t e = hipSuccess;
@@ -2285,11 +2210,11 @@ static int32_t bootstrap_host(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
         if ((e = hipMemcpyAsync(d_a2, a2, a_bytes, hipMemcpyHostToDevice, c->stream))) break;
         if ((e = hipMemcpyAsync(d_b1, b1, batch * 8, hipMemcpyHostToDevice, c->stream))) break;
         if ((e = hipMemcpyAsync(d_b2, b2, batch * 8, hipMemcpyHostToDevice, c->stream))) break;
-        t1 = now();
+        t1 = wall_ms();
         rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, batch, d_out, flags, n_iters, d_acc,
                               c->stream, d_dig);
         if (rc) break;
-        t2 = now();
+        t2 = wall_ms();
         if (digs && (e = hipMemcpyAsync(digs, d_dig, dig_words * 8, hipMemcpyDeviceToHost, c->stream)))
             break;
         if (out && (e = hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, c->stream)))
@@ -2298,7 +2223,7 @@ static int32_t bootstrap_host(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
             break;
         e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) c->pending = false;
-        t3 = now();
+        t3 = wall_ms();
         if (dbg)
             fprintf(stderr, "[sgfhe io] batch %zu direct copies: copy-in %.2f ms, enqueue %.2f, wait + copy-out %.2f\n",
                     batch, t1 - t0, t2 - t1, t3 - t2);
@@ -2352,15 +2277,9 @@ static int32_t coalesced_call(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
                 if ((r = drain(c))) return r;
                 // (the kernels draw for the rows that pad a chunk to a multiple of 8 as well: Coalescer::rows_len)
                 const size_t nrows = Coalescer::rows_len(gates);
-                if (nrows > c->rows_cap) {
-                    if (c->d_rows) (void)hipFree(c->d_rows);
-                    c->d_rows = nullptr;
-                    c->rows_cap = 0;
-                    const size_t cap = Coalescer::rows_len(gates > gates_cap ? gates : gates_cap);
-                    if (hipMalloc(&c->d_rows, cap * sizeof(RndRow)) != hipSuccess)
-                        return fail(c, SGFHE_ERR_OOM, "hipMalloc of the gathered call's draw-stream table failed");
-                    c->rows_cap = cap;
-                }
+                if (nrows > c->d_rows.cap &&   // (for the largest round the coalescer may gather, at once)
+                    c->d_rows.grow(Coalescer::rows_len(gates > gates_cap ? gates : gates_cap)) != hipSuccess)
+                    return fail(c, SGFHE_ERR_OOM, "hipMalloc of the gathered call's draw-stream table failed");
                 c->h_rows.clear();
                 for (const Coalescer::Req *q : take)
                     for (size_t t = 0; t < q->batch; t++) {
@@ -2371,9 +2290,9 @@ static int32_t coalesced_call(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
                         c->h_rows.push_back(row_of);
                     }
                 c->h_rows.resize(nrows, RndRow{});      // the padded rows: zeros, not what an earlier round left
-                if (hipMemcpy(c->d_rows, c->h_rows.data(), nrows * sizeof(RndRow), hipMemcpyHostToDevice) != hipSuccess)
+                if (hipMemcpy(c->d_rows.p, c->h_rows.data(), nrows * sizeof(RndRow), hipMemcpyHostToDevice) != hipSuccess)
                     return fail(c, SGFHE_ERR_HIP, "copy of the gathered call's draw-stream table failed");
-                c->gather_rows = c->d_rows;
+                c->gather_rows = c->d_rows.p;
             }
             std::vector<uint64_t> &g = c->co_buf;                          // [a1 | a2 | b1 | b2 | out] of all requests
             g.resize(gates * (2 * n + 2 + row));
@@ -2478,7 +2397,7 @@ int32_t sgfhe_debug_flatten(sgfhe_ctx *c, const uint64_t *values, uint64_t *digi
     do {
         if ((e = hipMemcpyAsync(d_in, values, (size_t)2 * M * 16, hipMemcpyHostToDevice, c->stream))) break;
         hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_in,
-                           L.dig, c->d_crt, 2 * M, (uint32_t)c->logm);
+                           L.dig, cur(c).d_crt, 2 * M, (uint32_t)c->logm);
         hipLaunchKernelGGL(k_dump_digits, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, L.dig,
                            d_out, 2 * M, (uint32_t)c->logm, 0u);
         if ((e = hipGetLastError())) break;
@@ -2504,7 +2423,7 @@ int32_t sgfhe_external_product(sgfhe_ctx *c, const uint64_t *a, const uint64_t *
     const sgfhe_ctx::Lane &L = c->lane[0];
     int32_t *d_A = nullptr;
     ulonglong2 *d_ab = nullptr;
-    HIPCHK(c, hipMalloc(&d_A, (size_t)c->npr * 8 * M * 4));
+    HIPCHK(c, hipMalloc(&d_A, (size_t)cur(c).npr * 8 * M * 4));
     hipError_t e = hipMalloc(&d_ab, (size_t)2 * M * 16);
     if (e != hipSuccess) { (void)hipFree(d_A); return fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); }
     do {
@@ -2515,7 +2434,7 @@ int32_t sgfhe_external_product(sgfhe_ctx *c, const uint64_t *a, const uint64_t *
         if ((e = hipMemcpyAsync(d_ab, a, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
         if ((e = hipMemcpyAsync(d_ab + M, b, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
         hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_ab,
-                           L.dig, c->d_crt, 2 * M, (uint32_t)c->logm);
+                           L.dig, cur(c).d_crt, 2 * M, (uint32_t)c->logm);
         rc = launch_extprod(c, L, d_A, cpad, 0, MODE_PLAIN, c->stream);
         if (rc) break;
         rc = launch_crt(c, L, cpad, MODE_NOACC | MODE_CANON, c->stream);
@@ -2544,7 +2463,7 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, con
     const sgfhe_ctx::Lane &L = c->lane[0];
     int32_t *d_C = nullptr;
     ulonglong2 *d_ab = nullptr;
-    HIPCHK(c, hipMalloc(&d_C, (size_t)c->npr * 8 * M * 4));
+    HIPCHK(c, hipMalloc(&d_C, (size_t)cur(c).npr * 8 * M * 4));
     hipError_t e = hipMalloc(&d_ab, (size_t)2 * M * 16);
     if (e != hipSuccess) { (void)hipFree(d_C); return fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); }
     const uint32_t jw = (uint32_t)j;
@@ -2557,13 +2476,13 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, con
         if ((e = hipMemcpyAsync(d_ab, a, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
         if ((e = hipMemcpyAsync(d_ab + M, b, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
         hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_ab,
-                           L.dig, c->d_crt, 2 * M, (uint32_t)c->logm);
+                           L.dig, cur(c).d_crt, 2 * M, (uint32_t)c->logm);
         rc = launch_extprod(c, L, d_C, cpad, 0, 0u, c->stream);     // iteration k = 0, with the rotation
         if (rc) break;
         rc = launch_crt(c, L, cpad, 0u, c->stream);                  // acc <- acc + D, flattened again
         if (rc) break;
         hipLaunchKernelGGL(k_dump_acc, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, L.dig, d_ab,
-                           c->d_crt, 2 * M, (uint32_t)c->logm, 0u);
+                           cur(c).d_crt, 2 * M, (uint32_t)c->logm, 0u);
         if ((e = hipGetLastError())) break;
         if ((e = hipMemcpyAsync(a_res, d_ab, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream))) break;
         if ((e = hipMemcpyAsync(b_res, d_ab + M, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream))) break;
@@ -2579,14 +2498,14 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, con
 // (w | v), in the ctx's present flatten mode; before anything is queued (nothing of the ctx in flight).
 static int32_t pack_grow(sgfhe_ctx *c, size_t count, size_t total) {
     const size_t n = c->n, M = c->M, nb = count * n;
-    const uint32_t G = c->rnd ? c->pack_G_rnd : c->pack_G;
+    const uint32_t G = pack_group(c);
     const size_t groups = n / G, len = c->rnd ? M : n;
     int32_t rc;
-    if ((rc = circ_grow(c, c->pack_lwe, c->pack_lwe_words, 2 * nb * n + 2 * nb))) return rc;
-    if ((rc = circ_grow(c, c->pack_raw, c->pack_raw_words, nb * 3 * (n + 1)))) return rc;
-    if ((rc = circ_grow(c, c->pack_pdig, c->pack_pdig_words, count * n * 2 * len))) return rc;
-    if ((rc = circ_grow(c, c->pack_yg, c->pack_yg_words, count * groups * 2 * c->npr * M))) return rc;
-    return circ_grow(c, c->pack_wv, c->pack_wv_words, 2 * total * M);
+    if ((rc = circ_grow(c, c->pack_lwe, 2 * nb * n + 2 * nb))) return rc;
+    if ((rc = circ_grow(c, c->pack_raw, nb * 3 * (n + 1)))) return rc;
+    if ((rc = circ_grow(c, c->pack_pdig, count * n * 2 * len))) return rc;
+    if ((rc = circ_grow(c, c->pack_yg, count * groups * 2 * cur(c).npr * M))) return rc;
+    return circ_grow(c, c->pack_wv, 2 * total * M);
 }
 
 // pack_encrypted_bits (fhe.jl:660-696) of `count` groups of n LWEs resident on the device, queued on `st`:
@@ -2599,28 +2518,26 @@ static int32_t pack_device(sgfhe_ctx *c, const uint64_t *d_a1, const uint64_t *d
     // rng != nothing: the n bootstraps and the flatten of every as_i (all m coefficients of the
     // resized polynomial, utils.jl:253-264) draw from the ctx's ChaCha stream (fhe.jl:673,683-684)
     const uint32_t mode = c->rnd ? MODE_RANDOM : 0u;
-    const uint32_t G = c->rnd ? c->pack_G_rnd : c->pack_G;
+    const sgfhe_ctx::Basis &S = cur(c);
+    const uint32_t G = pack_group(c);
     const uint32_t groups = (uint32_t)(n / G);
     const size_t len = c->rnd ? M : n;  // stored coefficients per digit polynomial
-    int32_t rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, nb, (uint64_t *)c->pack_raw, SGFHE_FLAG_RAW_MODQ,
+    int32_t rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ,
                                   c->n, nullptr, st);
     if (rc) return rc;
     const RndArgs ra = {c->rnd_key, c->last_call, 0u, nullptr};
     const size_t tf = count * n * len;
-    hipLaunchKernelGGL(k_pack_flatten, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, st, c->pack_raw,
-                       c->pack_pdig, c->d_crt, (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, mode, ra);
-    if ((rc = launch_shortprod(c, c->pack_pdig, c->pack_yg, (uint32_t)count, G, groups, mode, st))) return rc;
+    hipLaunchKernelGGL(k_pack_flatten, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, st, c->pack_raw.p,
+                       c->pack_pdig.p, S.d_crt, (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, mode, ra);
+    if ((rc = launch_shortprod(c, c->pack_pdig.p, c->pack_yg.p, (uint32_t)count, G, groups, mode, st))) return rc;
     const size_t tw = count * M;
-    switch (c->npr) {
-#define X(NP)                                                                                     \
-    case NP:                                                                                      \
-        hipLaunchKernelGGL(k_pack_finish<NP>, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0,   \
-                           st, c->pack_yg, c->pack_raw, d_w, d_v, c->d_crt,                       \
-                           (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, groups);              \
-        break;
-        SGFHE_FOR_NPR(X)
-#undef X
-    }
+    if ((rc = with_npr(c, S.npr, [&](auto np) -> int32_t {
+            hipLaunchKernelGGL(k_pack_finish<decltype(np)::value>, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, st,
+                               c->pack_yg.p, c->pack_raw.p, d_w, d_v, S.d_crt, (uint32_t)count, (uint32_t)n,
+                               (uint32_t)c->logm, groups);
+            return SGFHE_OK;
+        })))
+        return rc;
     HIPCHK(c, hipGetLastError());
     return SGFHE_OK;
 }
@@ -2635,15 +2552,15 @@ int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_
     SGFHE_QUIESCE(c);
     const size_t n = c->n, M = c->M;
     const size_t nb = count * n;  // bootstraps
-    if (!(c->rnd ? c->pack_G_rnd : c->pack_G))
+    if (!(pack_group(c)))
         return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
     if (pack_grow(c, count, count)) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(hipErrorOutOfMemory));
     hipError_t e = hipSuccess;
     int32_t rc = SGFHE_OK;
     do {
         // [a1 = 0 | a2 | b1 = Dr | b2]: trivial encryption of 1 paired with every bit (fhe.jl:669-673)
-        uint64_t *d_a1 = c->pack_lwe, *d_a2 = d_a1 + nb * n, *d_b1 = d_a2 + nb * n, *d_b2 = d_b1 + nb;
-        uint64_t *d_w = c->pack_wv, *d_v = d_w + count * M;
+        uint64_t *d_a1 = c->pack_lwe.p, *d_a2 = d_a1 + nb * n, *d_b1 = d_a2 + nb * n, *d_b2 = d_b1 + nb;
+        uint64_t *d_w = c->pack_wv.p, *d_v = d_w + count * M;
         if ((e = hipMemsetAsync(d_a1, 0, nb * n * 8, c->stream))) break;
         std::vector<uint64_t> ones(nb, c->par.r / 4);
         if ((e = hipMemcpyAsync(d_b1, ones.data(), nb * 8, hipMemcpyHostToDevice, c->stream))) break;
@@ -2661,7 +2578,7 @@ int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_
 
 int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const uint32_t *in,
                         uint32_t *out) {
-    if (!c || !in || !out || prime_index >= c->npr) return SGFHE_ERR_INVALID_ARG;
+    if (!c || !in || !out || prime_index >= cur(c).npr) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
     (void)hipSetDevice(c->device);
     SGFHE_QUIESCE(c);
@@ -2684,8 +2601,8 @@ int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const u
 int32_t sgfhe_debug_primes(const sgfhe_ctx *c, uint32_t *count, uint32_t *primes) {
     if (!c || !count || !primes) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
-    *count = c->npr;
-    for (uint32_t i = 0; i < c->npr; i++) primes[i] = c->primes[i];
+    *count = cur(c).npr;
+    for (uint32_t i = 0; i < cur(c).npr; i++) primes[i] = cur(c).primes[i];
     return SGFHE_OK;
 }
 
@@ -2881,20 +2798,19 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
 int32_t sgfhe_kernel_names(const sgfhe_ctx *c, char *extprod, size_t extprod_cap, char *crt, size_t crt_cap) {
     if (!c || !extprod || !crt || !extprod_cap || !crt_cap) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
-    const bool wide = c->rnd && (c->B >> 46);
-    const int le = c->logm <= EXT_LE3_MAX ? 3 : LOGE;
-    snprintf(extprod, extprod_cap, "k_extprod<%d, %d, %s>", c->logm, le, wide ? "true" : "false");
-    // the selection of launch_crt_raw for the k-loop's mode
+    // the throughput form at the ctx's present mode: what ext_form / crt_form give a large chunk
+    const uint32_t mode = flatten_mode(c);
+    const char *wide = (mode & MODE_WIDE) ? "true" : "false";
+    snprintf(extprod, extprod_cap, "k_extprod<%d, %d, %s>", c->logm, c->logm <= EXT_LE3_MAX ? 3 : LOGE, wide);
+    const CrtForm f = crt_form(c, mode, ~0u, false);
     // (k_crt_lean<5, 3, true>, the crt_lean87_one instantiation, reports as k_crt_lean<5, 3>: same
     // function, same memory side)
-    if (!c->rnd && c->h_lean.nl)
-        snprintf(crt, crt_cap, "k_crt_lean<%u, %u>", c->npr, c->h_lean.nl);
-    else if (c->rnd && c->lean_rnd_ok)
-        snprintf(crt, crt_cap, "k_crt_lean_rnd<%u, %u, %s>", c->npr, c->h_lean.nl, wide ? "true" : "false");
-    else if (!c->rnd)
-        snprintf(crt, crt_cap, "k_crt_acc2<%u>", c->npr);
-    else
-        snprintf(crt, crt_cap, "k_crt_acc<%u>", c->npr);
+    switch (f.kind) {
+    case CrtKind::Lean: snprintf(crt, crt_cap, "k_crt_lean<%u, %u>", f.np, f.nl); break;
+    case CrtKind::LeanRnd: snprintf(crt, crt_cap, "k_crt_lean_rnd<%u, %u, %s>", f.np, f.nl, wide); break;
+    case CrtKind::Acc2: snprintf(crt, crt_cap, "k_crt_acc2<%u>", f.np); break;
+    case CrtKind::Acc: snprintf(crt, crt_cap, "k_crt_acc<%u>", f.np); break;
+    }
     return SGFHE_OK;
 }
 
@@ -2904,12 +2820,7 @@ int32_t sgfhe_release_host_staging(sgfhe_ctx *c) {
     (void)hipSetDevice(c->device);
     SGFHE_QUIESCE(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->io_in) (void)hipFree(c->io_in);
-    if (c->io_out) (void)hipFree(c->io_out);
-    if (c->pin_in) (void)hipHostFree(c->pin_in);
-    if (c->pin_out) (void)hipHostFree(c->pin_out);
-    c->io_in = c->io_out = c->pin_in = c->pin_out = nullptr;
-    c->io_in_words = c->io_out_words = c->pin_in_words = c->pin_out_words = 0;
+    free_io_buffers(c);
     free_circuit_buffers(c);
     return SGFHE_OK;
 }
@@ -3006,11 +2917,11 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() +
                              (ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0);
     int32_t rc;
-    if ((rc = circ_grow(c, c->circ_wires, c->circ_wires_words, (size_t)P.slots * instances * row))) return rc;
-    if ((rc = circ_grow(c, c->circ_stage, c->circ_stage_words, (size_t)max_rows * 5 * row))) return rc;
-    if (out && (rc = circ_grow(c, c->circ_out, c->circ_out_words, (size_t)P.n_outputs * instances * row))) return rc;
-    if ((rc = circ_grow(c, c->circ_tab, c->circ_tab_words, tab_words))) return rc;
-    if ((rc = circ_grow(c, c->circ_ct, c->circ_ct_words, 2 * ct_words))) return rc;
+    if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
+    if ((rc = circ_grow(c, c->circ_stage, (size_t)max_rows * 5 * row))) return rc;
+    if (out && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
+    if ((rc = circ_grow(c, c->circ_tab, tab_words))) return rc;
+    if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
     if (pack && (rc = pack_grow(c, cpc, n_ct))) return rc;
     const uint64_t work_rows = std::max<uint64_t>(max_rows, cpc * n);
     if (work_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
@@ -3018,7 +2929,7 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
         if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(work_rows, chunk0))))) return rc;
     }
-    uint32_t *d_in_ref = c->circ_tab, *d_out_slot = d_in_ref + P.in_ref.size(), *d_out_ref = d_out_slot + P.out_slot.size();
+    uint32_t *d_in_ref = c->circ_tab.p, *d_out_slot = d_in_ref + P.in_ref.size(), *d_out_ref = d_out_slot + P.out_slot.size();
     uint32_t *d_in_slot = d_out_ref + P.out_ref.size(), *d_pack_ref = d_in_slot + P.input_slot.size();
     HIPCHK(c, hipMemcpyAsync(d_in_ref, P.in_ref.data(), P.in_ref.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_slot, P.out_slot.data(), P.out_slot.size() * 4, hipMemcpyHostToDevice, st));
@@ -3028,12 +2939,12 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         // the ciphertexts as they are, and extract() of every bit into the slot of its input wire
         if (P.n_inputs) {
             HIPCHK(c, hipMemcpyAsync(d_in_slot, P.input_slot.data(), P.input_slot.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(c->circ_ct, ct->in_a, ct_words * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(c->circ_ct + ct_words, ct->in_b, ct_words * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(c->circ_ct.p, ct->in_a, ct_words * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(c->circ_ct.p + ct_words, ct->in_b, ct_words * 8, hipMemcpyHostToDevice, st));
             const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
             hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(P.n_inputs * ct->blocks * tiles)), dim3(256),
-                               (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct, c->circ_ct + ct_words, d_in_slot,
-                               c->circ_wires, (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
+                               (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct.p, c->circ_ct.p + ct_words, d_in_slot,
+                               c->circ_wires.p, (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
             HIPCHK(c, hipGetLastError());
         }
         if (pack) {   // node table of the pack calls: (TRUE, output o), the pair of fhe.jl:669-673
@@ -3051,12 +2962,12 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
             uint32_t k = i + 1;
             while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
-            HIPCHK(c, hipMemcpyAsync(c->circ_wires + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
+            HIPCHK(c, hipMemcpyAsync(c->circ_wires.p + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
                                      (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
             i = k;
         }
     }
-    uint64_t *a1 = c->circ_stage, *a2 = a1 + max_rows * n, *b1 = a2 + max_rows * n, *b2 = b1 + max_rows,
+    uint64_t *a1 = c->circ_stage.p, *a2 = a1 + max_rows * n, *b1 = a2 + max_rows * n, *b2 = b1 + max_rows,
              *res = b2 + max_rows;
     for (uint32_t L = 1; L <= P.levels; L++) {
         const uint64_t rows_total = P.level_rows(L, instances);
@@ -3064,13 +2975,13 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         for (uint64_t row0 = 0; row0 < rows_total; row0 += SGFHE_CIRCUIT_CALL_ROWS) {
             const uint32_t rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, rows_total - row0);
             const uint32_t tg = rows * (uint32_t)row;
-            hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires,
+            hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires.p,
                                d_in_ref + 2 * (size_t)k0, a1, b1, a2, b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
             HIPCHK(c, hipGetLastError());
             // the k-loop of sgfhe_bootstrap_batch_device: the next call number of the ctx's draw stream
             if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, 0u, c->n, nullptr, st))) return rc;
             hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, res,
-                               d_out_slot + 3 * (size_t)k0, c->circ_wires, (uint32_t)row0, rows, inst, (uint32_t)n);
+                               d_out_slot + 3 * (size_t)k0, c->circ_wires.p, (uint32_t)row0, rows, inst, (uint32_t)n);
             HIPCHK(c, hipGetLastError());
         }
     }
@@ -3079,24 +2990,24 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     // bootstrap inputs, and each call is one sgfhe_pack_encrypted_bits(count = cnt) on the device
     for (size_t q0 = 0; q0 < n_ct; q0 += cpc) {
         const size_t cnt = std::min(cpc, n_ct - q0), nb = cnt * n;
-        uint64_t *p1 = c->pack_lwe, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
+        uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
         const uint32_t tg = (uint32_t)(nb * row);
-        hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires, d_pack_ref,
+        hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires.p, d_pack_ref,
                            p1, q1, p2, q2, (uint32_t)(q0 * n), (uint32_t)nb, inst, (uint32_t)n, r);
         HIPCHK(c, hipGetLastError());
-        if ((rc = pack_device(c, p1, q1, p2, q2, cnt, c->pack_wv + q0 * M, c->pack_wv + (n_ct + q0) * M, st))) return rc;
+        if ((rc = pack_device(c, p1, q1, p2, q2, cnt, c->pack_wv.p + q0 * M, c->pack_wv.p + (n_ct + q0) * M, st))) return rc;
     }
     if (pack) {
-        HIPCHK(c, hipMemcpyAsync(ct->out_w, c->pack_wv, n_ct * M * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(ct->out_v, c->pack_wv + n_ct * M, n_ct * M * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(ct->out_w, c->pack_wv.p, n_ct * M * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(ct->out_v, c->pack_wv.p + n_ct * M, n_ct * M * 8, hipMemcpyDeviceToHost, st));
     }
     if (out) {
         const size_t total = (size_t)P.n_outputs * instances * row;
         const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
-        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires, d_out_ref,
-                           c->circ_out, total, inst, (uint32_t)n, r);
+        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
+                           c->circ_out.p, total, inst, (uint32_t)n, r);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out, c->circ_out, total * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipStreamSynchronize(st));
     c->pending = false;
@@ -3137,7 +3048,7 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blo
     if (N != c->n && N != c->M)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: N must be n (PackedCiphertext) or m (Ciphertext)");
     if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    if (out_w && !(c->rnd ? c->pack_G_rnd : c->pack_G))
+    if (out_w && !(pack_group(c)))
         return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
     const CircuitPlan &P = circ->plan;
     if (blocks == 0) return SGFHE_OK;

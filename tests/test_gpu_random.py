@@ -201,6 +201,77 @@ def test_both_modes_on_every_ctx_at_params1024(S):
         e.close()
 
 
+def test_two_basis_ctx_on_a_small_ring(S, oc):
+    """A ctx with a basis per flatten mode at n = 8, m = 64, where the oracle costs milliseconds:
+    B = 2^43 and Q just below 2^64 give log2(5 m B Q) = 115.32, under the four largest primes'
+    115.996, and log2(20 m B Q) = 117.32, above it, so the deterministic mode runs on four primes and
+    the randomised one on five (2 log B + 2 - log Q = 24 < 50: the mode is allowed).  Key upload while
+    the randomised basis is active, throughput and latency form in both modes, the device-form blob
+    into a ctx in the other mode, and a clone taken while randomised: every result bit for bit
+    against the C restatement, randomised calls on (key, call) counted per ctx."""
+    import torch
+    n, m = 8, 64
+    Q = BO.find_modulus(2 * m, (1 << 64) - (1 << 40))
+    assert Q < 1 << 64
+    params = S.Params.custom(n, Q, 1 << 43)
+    assert params.m == m
+    key = bytes(range(101, 133))
+    o = oc.Oracle.from_params(params)
+    sk = o.private_key(330)
+    bkey = o.bootstrap_key(sk, 331, noise=2)
+    rng = np.random.default_rng(332)
+    big = (rng.integers(0, params.r, size=(24, n), dtype=np.uint64), rng.integers(0, params.r, size=24, dtype=np.uint64),
+           rng.integers(0, params.r, size=(24, n), dtype=np.uint64), rng.integers(0, params.r, size=24, dtype=np.uint64))
+    few = tuple(x[:3] for x in big)
+    names = {False: "k_crt_lean<4, 3>", True: "k_crt_lean_rnd<5, 3, false>"}
+    calls = {}                                          # randomised calls made so far, per ctx
+
+    def check(e, rnd):
+        """both forms, raw and ModRed, in the mode the ctx is in"""
+        assert len(e.primes()) == (5 if rnd else 4)
+        assert e.kernel_names() == ("k_extprod<6, 3, false>", names[rnd])
+        for small_max, w in ((0, big), (24, few)):      # the throughput form; the default threshold: the latency form
+            e.set_small_batch_max(small_max)
+            for raw in (True, False):
+                kw = {}
+                if rnd:
+                    kw["rnd"] = (key, calls[id(e)])
+                    calls[id(e)] += 1
+                assert np.array_equal(e.bootstrap_batch(*w, raw=raw), o.bootstrap_batch(bkey, *w, raw=raw, **kw)), \
+                    (rnd, small_max, raw)
+
+    def switch(e, rnd):
+        e.set_random_flatten(rnd, key)                  # (resets the ctx's call counter)
+        calls[id(e)] = 0
+
+    eng = S.Engine(params)
+    assert len(eng.primes()) == 4
+    switch(eng, True)
+    assert len(eng.primes()) == 5
+    eng.upload_key(bkey)                                # while the randomised basis is the active one
+    check(eng, True)
+    switch(eng, False)
+    check(eng, False)
+    five = 64 + n * 5 * 8 * m * 4
+    assert eng.key_device_form_bytes() == five          # the blob is the five-prime form
+    blob = torch.empty(five, dtype=torch.uint8, device="cuda")
+    eng.export_key_device_form(blob.data_ptr())
+    eng2 = S.Engine(params)                             # deterministic mode
+    eng2.import_key_device_form(blob.data_ptr())
+    check(eng2, False)
+    switch(eng2, True)
+    check(eng2, True)
+    eng2.close()
+    switch(eng, True)
+    cl = eng.clone()                                    # starts deterministic whatever its source is in
+    check(cl, False)
+    check(eng, True)
+    switch(cl, True)
+    check(cl, True)
+    cl.close()
+    eng.close()
+
+
 def test_random_mode_refused_when_its_reductions_would_overflow(S):
     """A parameter set with B^2 far above Q (4 B^2 / Q >= 2^50): the randomised flatten divides
     values up to 4 B^2 by Q with a double-precision quotient estimate, so the mode is refused

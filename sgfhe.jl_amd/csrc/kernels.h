@@ -302,6 +302,114 @@ __device__ __forceinline__ int32_t digit_reduce(uint64_t e, const Mod &md, int32
     return sredc((int64_t)e, md) + sR;
 }
 
+// ---- steps the product kernels share ---------------------------------------------------------------
+// (tests/rns_model.py restates each of them once, too)
+// Offset of the residues handed to the CRT kernels.  |+-v - z| < 2.7 p: + 3 p makes a non-negative
+// representative below 5.7 p (no reduction at all: the CRT kernels take any such residues); + (p - 1) / 2
+// for the last prime, folded into the same wave-uniform constant.
+__device__ __forceinline__ uint32_t handover_offset(const PrimeK &P) { return 3u * (uint32_t)P.p + P.hoff; }
+
+// Products of one transformed key row (E points per thread, slot order) with the row's two key polynomials,
+// kp and kp + M: two int4 key loads, two smont per point, two int4 stores per group of four  -> zpart
+template <int M, int E>
+__device__ __forceinline__ void key_row_products(const int32_t (&x)[1][E], const int32_t *kp, int32_t *zp,
+                                                 const Mod &md) {
+#pragma unroll
+    for (int h = 0; h < E / 4; h++) {
+        const int4 a = reinterpret_cast<const int4 *>(kp)[h];
+        const int4 bq = reinterpret_cast<const int4 *>(kp + M)[h];
+        const int32_t ka[4] = {a.x, a.y, a.z, a.w};
+        const int32_t kb[4] = {bq.x, bq.y, bq.z, bq.w};
+        int32_t r0[4], r1[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int32_t u = x[0][4 * h + t];
+            r0[t] = smont(u, ka[t], md);  // |.| < 0.74 * 2^29
+            r1[t] = smont(u, kb[t], md);
+        }
+        reinterpret_cast<int4 *>(zp)[h] = make_int4(r0[0], r0[1], r0[2], r0[3]);
+        reinterpret_cast<int4 *>(zp + M)[h] = make_int4(r1[0], r1[1], r1[2], r1[3]);
+    }
+}
+// Sum over the four key rows of group h (four slots) of the partial products in zpart: < 2.99 * 2^29
+template <int M>
+__device__ __forceinline__ void zpart_sum4(const int32_t *zp, int h, int32_t (&acc)[4]) {
+    acc[0] = acc[1] = acc[2] = acc[3] = 0;
+#pragma unroll
+    for (int ph = 0; ph < 4; ph++) {
+        const int4 v = reinterpret_cast<const int4 *>(zp + (size_t)ph * 2 * M)[h];
+        acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
+    }
+}
+
+// Radix-4 head of a quarter transform: quarter q of the first two Cooley-Tukey stages.  With X0..X3 the
+// coefficients i, i + m/4, i + m/2, i + 3m/4 of a digit plane (dl, dh: its low and high words),
+//   u = f1 X2;  q < 2: (X0 + u) +- (f2 X1 + fp2 X3);  q >= 2: (X0 - u) +- (f3 X1 + fp3 X3)
+// (the arithmetic of ntt.h fwd_step4), reduced to [0, p].
+struct QuarterHead {
+    uint32_t q;
+    int32_t wB, wP;
+    __device__ __forceinline__ QuarterHead(uint32_t q_, const PrimeK &P)
+        : q(q_), wB((q_ & 2) ? P.f3 : P.f2), wP((q_ & 2) ? P.fp3 : P.fp2) {}
+    template <int MS>
+    __device__ __forceinline__ int32_t point(const uint32_t *dl, const uint16_t *dh, uint32_t i, const PrimeK &P,
+                                             const Mod &md, int32_t sRd) const {
+        int32_t X[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            X[t] = digit_reduce(dl[i + t * MS] | ((uint64_t)dh[i + t * MS] << 32), md, sRd);   // |.| <= p + 2^16
+        const int32_t u = smont(X[2], P.f1, md);                                              // < 0.57 * 2^29
+        const int32_t a = (q & 2) ? X[0] - u : X[0] + u;
+        const int32_t w = sredc((int64_t)X[1] * wB + (int64_t)X[3] * wP, md);                   // < 0.63 * 2^29
+        return sred_floor((q & 1) ? a - w : a + w, md);                                       // [0, p]
+    }
+};
+
+// Rotation factors of the E slots s = q m/4 + E t + e of thread t of quarter q: slot s holds the value at
+// psi^(2 brv(s) + 1), so (x^j - 1) is psi^(j (2 brv(s) + 1) mod 2m) - 1 there.  A gather from the table of
+// psi powers: the callers request it first.
+template <int LOGM, int E>
+__device__ __forceinline__ void rot_factors(int32_t (&dfac)[E], const PrimeK &P, uint32_t j, uint32_t q, int t) {
+    constexpr uint32_t M = 1u << LOGM;
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        const uint32_t sl = q * (M / 4) + (uint32_t)(E * t + e);
+        const uint32_t br = __brev(sl) >> (32 - LOGM);
+        dfac[e] = P.pw[(j * (2u * br + 1u)) & (2u * M - 1u)];
+    }
+}
+// (psi^e - 1) R mod p from two centred residues: in (-p, p), centred again for the product's bound
+__device__ __forceinline__ int32_t rot_centre(int32_t dfac, const PrimeK &P, const Mod &md) {
+    return scentre(dfac - P.r1, md);
+}
+
+// The last two Gentleman-Sande stages of the quarter form, for coefficient i of (bootstrap, c) = bc, on the
+// four partial values Y_0..Y_3 at i mod m/4 of every prime --
+//   C0 = Y0 + Y1, C1 = v2 (Y0 - Y1), C2 = Y2 + Y3, C3 = v3 (Y2 - Y3);
+//   coefficient in quarter 0: C0 + C2;  1: C1 + C3;  2: v1 (C0 - C2);  3: v1 (C1 - C3)
+// (only the one this coefficient needs; the quarter is the same for a whole workgroup) -- then the residue in
+// the form k_extprod hands over: non-negative, below 4.6 p.
+template <int NP>
+__device__ __forceinline__ void quarter_residues(const int32_t *__restrict__ ypart, PrimeSet PS, uint32_t bc,
+                                                 uint32_t i, uint32_t logm, uint32_t (&y)[NP]) {
+    const uint32_t MS = (1u << logm) >> 2, jq = i & (MS - 1), qq = i >> (logm - 2);
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+        const PrimeK P = PS[q];
+        const Mod md = mod_of(P);
+        const int32_t *yp = ypart + (((size_t)bc * NP + q) * 4) * MS + jq;
+        int32_t r;
+        if (qq & 1u) {          // C1, C3
+            const int32_t c1 = smont(yp[0] - yp[MS], P.v2, md), c3 = smont(yp[2 * MS] - yp[3 * MS], P.v3, md);
+            r = (qq & 2u) ? smont(c1 - c3, P.v1, md) : c1 + c3;             // < 0.75 / < 1.5 * 2^29
+        } else {                // C0, C2
+            const int32_t c0 = sred(yp[0] + yp[MS], md), c2 = sred(yp[2 * MS] + yp[3 * MS], md);   // sums < 2.8: reduced to 0.51
+            r = (qq & 2u) ? smont(c0 - c2, P.v1, md) : c0 + c2;             // < 0.75 / < 1.03 * 2^29
+        }
+        y[q] = (uint32_t)r + handover_offset(P);
+    }
+}
+
 // ---- k_extprod ----------------------------------------------------------------------------------
 // grid = chunk * NPR workgroups of T = m / 16 threads; chunk is a multiple of 8.  Workgroups are
 // dealt round-robin to the 8 XCDs (blocks g and g + 8 share an XCD, MI355X_MICROARCH.md), so
@@ -484,7 +592,7 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
         return;
     }
     const uint32_t j = ua[(size_t)b * n + k];
-    const uint32_t yoff = 3u * (uint32_t)P.p + P.hoff;
+    const uint32_t yoff = handover_offset(P);
     // The transform's swizzled layout is kept for this exchange.  Its j-shifted reads collide where
     // the run of 64 source indices crosses a swizzle boundary (2.6 % of the kernel's LDS cycles,
     // profiles/r03_v10_counters.json).  A plain layout (word i of polynomial c at c m + i) has no
@@ -514,9 +622,6 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 const uint32_t v = lds[c * M + addr];
-                // |+-v - z| < 2.7 p: + 3 p makes a non-negative representative below 5.7 p (no
-                // reduction at all: k_crt_acc takes any such residues); + (p - 1) / 2 for the last
-                // prime, folded into the same wave-uniform constant
                 const uint32_t y = (v ^ smask) + (yoe - (uint32_t)z[c][e]);
                 buf_st_u32(ryres, vout + ((uint32_t)(4 * T * e) & 4095u),
                               (c ? sy1 : sy0) + ((uint32_t)(4 * T * e) & ~4095u), y);
@@ -614,6 +719,48 @@ __device__ __forceinline__ U96 crt_reduce(const uint32_t (&y)[NP], const CrtCons
     }
     return a;
 }
+// Residues of coefficient i of (bootstrap, c) = bc, yres[bc][q][i] for q < NP.  ABLATE: the caller is one
+// whose loads the timing-only build SGFHE_ABL_NO_YRES removes (wrong results).
+template <int NP, bool ABLATE = false>
+__device__ __forceinline__ void load_residues(const uint32_t *__restrict__ yres, uint32_t bc, uint32_t i,
+                                              uint32_t logm, uint32_t (&y)[NP]) {
+    const uint32_t yo = 4u * ((bc * NP << logm) + i);  // byte offset
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+#ifdef SGFHE_ABL_NO_YRES
+        if constexpr (ABLATE) { y[q] = (((bc << logm) + i) * 2654435761u + (uint32_t)q * 40503u) >> 3; continue; }
+#endif
+        y[q] = ld_off<uint32_t>(yres, yo + ((uint32_t)(4 * q) << logm));
+    }
+}
+// The same for the four adjacent coefficients i .. i + 3 (i a multiple of 4), 16 bytes per prime.
+// The residues are read exactly once: non-temporal loads keep them from displacing what the other
+// lane's k_extprod re-reads from the caches (key slice, digit planes).  Same call, two lanes of
+// 256 (profiles/r03_exp_cache_policy.txt): 2076 against 2016 bootstraps/s, +3.0 %, and +2.9 % on
+// a second box; the old digits loaded the same way as well: +2.2 % (they are in the caches, the
+// external product of this chunk has just read them), so those stay plain loads.
+// ABLATE: as above, for the timing-only build SGFHE_ABL_NO_YLOAD.
+template <int NP, bool ABLATE = false>
+__device__ __forceinline__ void load_residues4(const uint32_t *__restrict__ yres, uint32_t bc, uint32_t i,
+                                               uint32_t logm, uint4 (&yv)[NP]) {
+    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+    const uint32_t yo = 4u * ((bc * NP << logm) + i);
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+#ifdef SGFHE_ABL_NO_YLOAD
+        if constexpr (ABLATE) { yv[q] = make_uint4((((bc << logm) + i) >> 2) + q, yo, i + 7u * q, bc); continue; }
+#endif
+        const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(
+            reinterpret_cast<const char *>(yres) + yo + ((uint32_t)(4 * q) << logm)));
+        yv[q] = make_uint4(t.x, t.y, t.z, t.w);
+    }
+}
+// coefficient j of the four
+template <int NP>
+__device__ __forceinline__ void residues_of(const uint4 (&yv)[NP], int j, uint32_t (&y)[NP]) {
+#pragma unroll
+    for (int q = 0; q < NP; q++) y[q] = j == 0 ? yv[q].x : j == 1 ? yv[q].y : j == 2 ? yv[q].z : yv[q].w;
+}
 
 template <int NP, bool ROWS = false>
 __global__ void __launch_bounds__(256)
@@ -625,14 +772,8 @@ k_crt_acc(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     const uint32_t M = 1u << logm;
     const uint32_t i = t & (M - 1);
     const uint32_t bc = t >> logm;
-    const uint32_t yo = 4u * ((bc * NP << logm) + i);  // byte offset
     uint32_t y[NP];
-#pragma unroll
-#ifdef SGFHE_ABL_NO_YRES  // timing-only build: no residue loads (wrong results)
-    for (int q = 0; q < NP; q++) y[q] = (t * 2654435761u + (uint32_t)q * 40503u) >> 3;
-#else
-    for (int q = 0; q < NP; q++) y[q] = ld_off<uint32_t>(yres, yo + ((uint32_t)(4 * q) << logm));
-#endif
+    load_residues<NP, true>(yres, bc, i, logm, y);
     const bool have_old = !(mode & MODE_NOACC);
     const bool wide = (mode & MODE_WIDE) != 0;
     const ulonglong2 d = have_old ? load_digits(dig, bc, i, M, wide) : make_ulonglong2(0, 0);
@@ -971,24 +1112,8 @@ k_crt_lean(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     const uint32_t M = 1u << logm;
     const uint32_t i = (4u * t) & (M - 1);  // multiple of 4
     const uint32_t bc = (4u * t) >> logm;
-    const uint32_t yo = 4u * ((bc * NP << logm) + i);
-    // The residues are read exactly once: non-temporal loads keep them from displacing what the other
-    // lane's k_extprod re-reads from the caches (key slice, digit planes).  Same call, two lanes of
-    // 256 (profiles/r03_exp_cache_policy.txt): 2076 against 2016 bootstraps/s, +3.0 %, and +2.9 % on
-    // a second box; the old digits loaded the same way as well: +2.2 % (they are in the caches, the
-    // external product of this chunk has just read them), so those stay plain loads.
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
     uint4 yv[NP];
-#pragma unroll
-    for (int q = 0; q < NP; q++) {
-#ifdef SGFHE_ABL_NO_YLOAD       // timing-only build: no residue loads (wrong results)
-        yv[q] = make_uint4(t + q, yo, i + 7u * q, bc);
-#else
-        const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(
-            reinterpret_cast<const char *>(yres) + yo + ((uint32_t)(4 * q) << logm)));
-        yv[q] = make_uint4(t.x, t.y, t.z, t.w);
-#endif
-    }
+    load_residues4<NP, true>(yres, bc, i, logm, yv);
     const uint32_t rec = bc * 16u * M;
     const uint32_t ol = rec + 4u * i, oh = rec + 8u * M + 2u * i;
     const uint4 l0 = ld_off<uint4>(dig, ol), l1 = ld_off<uint4>(dig, ol + 4u * M);
@@ -1005,8 +1130,7 @@ k_crt_lean(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         uint32_t y[NP];
-#pragma unroll
-        for (int q = 0; q < NP; q++) y[q] = j == 0 ? yv[q].x : j == 1 ? yv[q].y : j == 2 ? yv[q].z : yv[q].w;
+        residues_of(yv, j, y);
         if constexpr (P87)
             crt_lean87_one<NP>(y, l0w[j] | ((uint64_t)h0w[j] << 32), l1w[j], h1w[j], K, W, nlo[j], nhi[j]);
         else
@@ -1034,10 +1158,8 @@ k_crt_lean1(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     const uint32_t M = 1u << logm;
     const uint32_t i = t & (M - 1);
     const uint32_t bc = t >> logm;
-    const uint32_t yo = 4u * ((bc * NP << logm) + i);
     uint32_t y[NP];
-#pragma unroll
-    for (int q = 0; q < NP; q++) y[q] = ld_off<uint32_t>(yres, yo + ((uint32_t)(4 * q) << logm));
+    load_residues<NP>(yres, bc, i, logm, y);
     const ulonglong2 d = load_digits(dig, bc, i, M);
     uint64_t lo, hi;
     crt_lean_one<NP, NL>(y, d.x, d.y, K, lo, hi);
@@ -1061,15 +1183,8 @@ k_crt_lean_rnd(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     const uint32_t M = 1u << logm;
     const uint32_t i = (4u * t) & (M - 1);  // multiple of 4
     const uint32_t bc = (4u * t) >> logm;
-    const uint32_t yo = 4u * ((bc * NP << logm) + i);
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
     uint4 yv[NP];
-#pragma unroll
-    for (int q = 0; q < NP; q++) {
-        const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(
-            reinterpret_cast<const char *>(yres) + yo + ((uint32_t)(4 * q) << logm)));
-        yv[q] = make_uint4(t.x, t.y, t.z, t.w);
-    }
+    load_residues4<NP>(yres, bc, i, logm, yv);
     const uint32_t rec = bc * 16u * M;
     const uint32_t ol = rec + 4u * i, oh = rec + 8u * M + 2u * i, ot = rec + 12u * M + i;
     const uint4 l0 = ld_off<uint4>(dig, ol), l1 = ld_off<uint4>(dig, ol + 4u * M);
@@ -1090,8 +1205,7 @@ k_crt_lean_rnd(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         uint32_t y[NP];
-#pragma unroll
-        for (int q = 0; q < NP; q++) y[q] = j == 0 ? yv[q].x : j == 1 ? yv[q].y : j == 2 ? yv[q].z : yv[q].w;
+        residues_of(yv, j, y);
         const uint64_t r0 = __umul64hi(((uint64_t)rw[4 * j + 1] << 32) | rw[4 * j], span);
         const uint64_t r1 = __umul64hi(((uint64_t)rw[4 * j + 3] << 32) | rw[4 * j + 2], span);
         uint32_t hw0 = h0w[j], hw1 = h1w[j];
@@ -1140,29 +1254,10 @@ k_crt_lean_rnd1(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     const uint32_t i = t & (M - 1);
     const uint32_t bc = t >> logm;
     uint32_t y[NP];
-    if constexpr (QUARTER) {
-        const uint32_t MS = M >> 2, jq = i & (MS - 1), qq = i >> (logm - 2);
-        const int32_t *ypart = reinterpret_cast<const int32_t *>(yres);
-#pragma unroll
-        for (int q = 0; q < NP; q++) {
-            const PrimeK P = PS[q];
-            const Mod md = mod_of(P);
-            const int32_t *yp = ypart + (((size_t)bc * NP + q) * 4) * MS + jq;
-            int32_t r;
-            if (qq & 1u) {
-                const int32_t c1 = smont(yp[0] - yp[MS], P.v2, md), c3 = smont(yp[2 * MS] - yp[3 * MS], P.v3, md);
-                r = (qq & 2u) ? smont(c1 - c3, P.v1, md) : c1 + c3;
-            } else {
-                const int32_t c0 = sred(yp[0] + yp[MS], md), c2 = sred(yp[2 * MS] + yp[3 * MS], md);
-                r = (qq & 2u) ? smont(c0 - c2, P.v1, md) : c0 + c2;
-            }
-            y[q] = (uint32_t)(r + 3 * P.p) + P.hoff;
-        }
-    } else {
-        const uint32_t yo = 4u * ((bc * NP << logm) + i);
-#pragma unroll
-        for (int q = 0; q < NP; q++) y[q] = ld_off<uint32_t>(yres, yo + ((uint32_t)(4 * q) << logm));
-    }
+    if constexpr (QUARTER)
+        quarter_residues<NP>(reinterpret_cast<const int32_t *>(yres), PS, bc, i, logm, y);
+    else
+        load_residues<NP>(yres, bc, i, logm, y);
     const ulonglong2 d = load_digits(dig, bc, i, M);
     const uint64_t xm2 = ((uint64_t)K->xm2hi << 32) | K->xm2lo, span = xm2 + 1;
     const uint32_t cx = ((bc & 1u) << logm) + i;
@@ -1225,22 +1320,7 @@ k_fwd_phase(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
 
     const int32_t *kp = keyk + ((size_t)pi * 8 + ph * 2) * M + E * tid;
     int32_t *zp = zpart + ((((size_t)b * npr + pi) * 4 + ph) * 2) * M + E * tid;
-#pragma unroll
-    for (int h = 0; h < E / 4; h++) {
-        const int4 a = reinterpret_cast<const int4 *>(kp)[h];
-        const int4 bq = reinterpret_cast<const int4 *>(kp + M)[h];
-        const int32_t ka[4] = {a.x, a.y, a.z, a.w};
-        const int32_t kb[4] = {bq.x, bq.y, bq.z, bq.w};
-        int32_t r0[4], r1[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int32_t u = x[0][4 * h + t];
-            r0[t] = smont(u, ka[t], md);  // |.| < 0.74 * 2^29
-            r1[t] = smont(u, kb[t], md);
-        }
-        reinterpret_cast<int4 *>(zp)[h] = make_int4(r0[0], r0[1], r0[2], r0[3]);
-        reinterpret_cast<int4 *>(zp + M)[h] = make_int4(r1[0], r1[1], r1[2], r1[3]);
-    }
+    key_row_products<M, E>(x, kp, zp, md);
 }
 
 template <int LOGM, int LE>
@@ -1262,21 +1342,17 @@ k_inv_column(const int32_t *__restrict__ zpart, uint32_t *__restrict__ yres,
     const int32_t *zp = zpart + ((((size_t)b * npr + pi) * 4) * 2 + c) * M + E * tid;
 #pragma unroll
     for (int h = 0; h < E / 4; h++) {
-        int32_t acc[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int ph = 0; ph < 4; ph++) {
-            const int4 v = reinterpret_cast<const int4 *>(zp + (size_t)ph * 2 * M)[h];
-            acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;  // < 2.99 * 2^29
-        }
+        int32_t acc[4];
+        zpart_sum4<M>(zp, h, acc);
 #pragma unroll
         for (int t = 0; t < 4; t++) z[0][4 * h + t] = sred(acc[t], md);
     }
     ntt_inverse<LOGM, 1, LE>(z, lds, P.twi, tid, md);
 
-    // y = x^j P - P  (as in k_extprod)
+    // y = x^j P - P
     uint32_t *yb = yres + (((size_t)b * 2 + c) * npr + pi) * M;
     const uint32_t j = ua[(size_t)b * n + k];
-    const uint32_t yoff = 3u * (uint32_t)P.p + P.hoff;  // as in k_extprod
+    const uint32_t yoff = handover_offset(P);
     lds_store<LOGM, 1, LE, G::STOP>(z, lds, tid);  // own addresses: the thread's last loads
     SGFHE_SYNC();
     constexpr uint32_t LOWMASK = (1u << G::STOP) - 1u;
@@ -1329,41 +1405,14 @@ k_fwd_quarter(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk
     const int32_t sRd = (mode & MODE_RANDOM) ? P.sRr : P.sR;   // digit offset of the flatten mode
     const uint32_t *dl = digit_lo_plane(dig, (size_t)b * 2 + (ph >> 1), M) + (ph & 1) * M;
     const uint16_t *dh = digit_hi_plane(dig, (size_t)b * 2 + (ph >> 1), M) + (ph & 1) * M;
-    // quarter q of the first two stages: with X0..X3 the coefficients i, i + m/4, i + m/2, i + 3m/4,
-    //   u = f1 X2;  q < 2: (X0 + u) +- (f2 X1 + fp2 X3);  q >= 2: (X0 - u) +- (f3 X1 + fp3 X3)
-    const int32_t wB = (q & 2) ? P.f3 : P.f2, wP = (q & 2) ? P.fp3 : P.fp2;
+    const QuarterHead head(q, P);
     int32_t x[1][E];
 #pragma unroll
-    for (int e = 0; e < E; e++) {
-        const uint32_t i = (uint32_t)tid + (uint32_t)(T * e);
-        int32_t X[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-            X[t] = digit_reduce(dl[i + t * MS] | ((uint64_t)dh[i + t * MS] << 32), md, sRd);   // |.| <= p + 2^16
-        const int32_t u = smont(X[2], P.f1, md);                                              // < 0.57 * 2^29
-        const int32_t a = (q & 2) ? X[0] - u : X[0] + u;
-        const int32_t w = sredc((int64_t)X[1] * wB + (int64_t)X[3] * wP, md);                   // < 0.63 * 2^29
-        x[0][e] = sred_floor((q & 1) ? a - w : a + w, md);                                    // [0, p]
-    }
+    for (int e = 0; e < E; e++) x[0][e] = head.point<MS>(dl, dh, (uint32_t)tid + (uint32_t)(T * e), P, md, sRd);
     ntt_forward<LS, 1, LE>(x, lds, P.twq + (size_t)q * M, tid, md);
     const int32_t *kp = keyk + ((size_t)pi * 8 + ph * 2) * M + q * MS + E * tid;
     int32_t *zp = zpart + ((((size_t)b * npr + pi) * 4 + ph) * 2) * M + q * MS + E * tid;
-#pragma unroll
-    for (int h = 0; h < E / 4; h++) {
-        const int4 a = reinterpret_cast<const int4 *>(kp)[h];
-        const int4 bq = reinterpret_cast<const int4 *>(kp + M)[h];
-        const int32_t ka[4] = {a.x, a.y, a.z, a.w};
-        const int32_t kb[4] = {bq.x, bq.y, bq.z, bq.w};
-        int32_t r0[4], r1[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int32_t u = x[0][4 * h + t];
-            r0[t] = smont(u, ka[t], md);  // |.| < 0.74 * 2^29
-            r1[t] = smont(u, kb[t], md);
-        }
-        reinterpret_cast<int4 *>(zp)[h] = make_int4(r0[0], r0[1], r0[2], r0[3]);
-        reinterpret_cast<int4 *>(zp + M)[h] = make_int4(r1[0], r1[1], r1[2], r1[3]);
-    }
+    key_row_products<M, E>(x, kp, zp, md);
 }
 
 template <int LOGM, int LE>
@@ -1381,30 +1430,17 @@ k_inv_quarter(const int32_t *__restrict__ zpart, int32_t *__restrict__ ypart,
     const PrimeK P = PS[pi];
     const Mod md = mod_of(P);
     const uint32_t j = ua[(size_t)b * n + k];
-    // the factor of slot s = q m/4 + E tid + e: psi^(j (2 brv(s) + 1) mod 2m) - 1, requested first (a gather)
-    int32_t dfac[E];
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-        const uint32_t sl = q * (uint32_t)MS + (uint32_t)(E * tid + e);
-        const uint32_t br = __brev(sl) >> (32 - LOGM);
-        dfac[e] = P.pw[(j * (2u * br + 1u)) & (2u * M - 1u)];
-    }
+    int32_t dfac[E];   // requested first
+    rot_factors<LOGM>(dfac, P, j, q, tid);
     int32_t z[1][E];
     const int32_t *zp = zpart + ((((size_t)b * npr + pi) * 4) * 2 + c) * M + q * MS + E * tid;
 #pragma unroll
     for (int h = 0; h < E / 4; h++) {
-        int32_t acc[4] = {0, 0, 0, 0};
+        int32_t acc[4];
+        zpart_sum4<M>(zp, h, acc);
 #pragma unroll
-        for (int ph = 0; ph < 4; ph++) {
-            const int4 v = reinterpret_cast<const int4 *>(zp + (size_t)ph * 2 * M)[h];
-            acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;  // < 2.99 * 2^29
-        }
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            // (psi^e - 1) R mod p from two centred residues: in (-p, p), centred again for the product's bound
-            const int32_t d = scentre(dfac[4 * h + t] - P.r1, md);
-            z[0][4 * h + t] = smont(acc[t], d, md);                      // < 0.19 + 0.5 = 0.69 * 2^29
-        }
+        for (int t = 0; t < 4; t++)
+            z[0][4 * h + t] = smont(acc[t], rot_centre(dfac[4 * h + t], P, md), md);   // < 0.19 + 0.5 = 0.69 * 2^29
     }
     ntt_inverse<LS, 1, LE>(z, lds, P.twq + (size_t)q * M + MS, tid, md);   // natural order inside the quarter, |.| < 1.4 * 2^29
     int32_t *yb = ypart + ((((size_t)b * 2 + c) * npr + pi) * 4 + q) * MS;
@@ -1445,12 +1481,7 @@ k_ext_quarter(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk
     // requested first: the rotation factors of column g's slots (a gather behind the load of j) and the key
     const uint32_t j = ua[(size_t)b * n + k];
     int32_t dfac[E];
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-        const uint32_t sl = q * (uint32_t)MS + (uint32_t)(E * tl + e);
-        const uint32_t br = __brev(sl) >> (32 - LOGM);
-        dfac[e] = P.pw[(j * (2u * br + 1u)) & (2u * M - 1u)];
-    }
+    rot_factors<LOGM>(dfac, P, j, q, tl);
     int4 kk[2][2][E / 4];                                           // [row of the pair][column][..]
     {
         const int32_t *kp = keyk + ((size_t)pi * 8 + g * 4) * M + q * MS + E * tl;
@@ -1461,25 +1492,14 @@ k_ext_quarter(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk
 #pragma unroll
                 for (int h = 0; h < E / 4; h++) kk[r][c][h] = reinterpret_cast<const int4 *>(kp + (size_t)(r * 2 + c) * M)[h];
     }
-    // head: quarter q of the first two stages of both rows (k_fwd_quarter)
-    const int32_t wB = (q & 2) ? P.f3 : P.f2, wP = (q & 2) ? P.fp3 : P.fp2;
+    const QuarterHead head(q, P);   // of both rows
     int32_t x[2][E];
 #pragma unroll
     for (int r = 0; r < 2; r++) {
         const uint32_t *dl = digit_lo_plane(dig, (size_t)b * 2 + g, M) + r * M;
         const uint16_t *dh = digit_hi_plane(dig, (size_t)b * 2 + g, M) + r * M;
 #pragma unroll
-        for (int e = 0; e < E; e++) {
-            const uint32_t i = (uint32_t)tl + (uint32_t)(T * e);
-            int32_t X[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-                X[t] = digit_reduce(dl[i + t * MS] | ((uint64_t)dh[i + t * MS] << 32), md, sRd);
-            const int32_t u = smont(X[2], P.f1, md);
-            const int32_t a = (q & 2) ? X[0] - u : X[0] + u;
-            const int32_t w = sredc((int64_t)X[1] * wB + (int64_t)X[3] * wP, md);
-            x[r][e] = sred_floor((q & 1) ? a - w : a + w, md);
-        }
+        for (int e = 0; e < E; e++) x[r][e] = head.point<MS>(dl, dh, (uint32_t)tl + (uint32_t)(T * e), P, md, sRd);
     }
     ntt_forward<LS, 2, LE>(x, glds, P.twq + (size_t)q * M, tl, md);
     // products of the pair, both columns; the other group's column goes to the hand-over area
@@ -1507,10 +1527,8 @@ k_ext_quarter(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk
         const int4 o = reinterpret_cast<const int4 *>(hand + (size_t)g * MS + E * tl)[h];
         const int32_t ov[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int32_t d = scentre(dfac[4 * h + t] - P.r1, md);
-            z[0][4 * h + t] = smont(own[4 * h + t] + ov[t], d, md);
-        }
+        for (int t = 0; t < 4; t++)
+            z[0][4 * h + t] = smont(own[4 * h + t] + ov[t], rot_centre(dfac[4 * h + t], P, md), md);
     }
     ntt_inverse<LS, 1, LE>(z, glds, P.twq + (size_t)q * M + MS, tl, md);
     int32_t *yb = ypart + ((((size_t)b * 2 + g) * npr + pi) * 4 + q) * MS;
@@ -1518,38 +1536,18 @@ k_ext_quarter(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk
     for (int e = 0; e < E; e++) yb[tl + T * e] = z[0][e];
 }
 
-// One thread per coefficient i of (bootstrap, c): the last two Gentleman-Sande stages on the four partial
-// values Y_0..Y_3 at i mod m/4 of every prime --
-//   C0 = Y0 + Y1, C1 = v2 (Y0 - Y1), C2 = Y2 + Y3, C3 = v3 (Y2 - Y3);
-//   coefficient in quarter 0: C0 + C2;  1: C1 + C3;  2: v1 (C0 - C2);  3: v1 (C1 - C3)
-// (only the one this coefficient needs; the quarter is the same for a whole workgroup) -- then the residue in
-// the form k_extprod hands over (+ 3 p, + (p - 1) / 2 on the last prime) and crt_lean_one.
+// One thread per coefficient: quarter_residues (the last two inverse stages), then crt_lean_one.
 template <int NP, int NL>
 __global__ void __launch_bounds__(256)
 k_crt_lean1q(const int32_t *__restrict__ ypart, uint64_t *__restrict__ dig, PrimeSet PS,
              const CrtLean *__restrict__ K, uint32_t total, uint32_t logm) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
-    const uint32_t M = 1u << logm, MS = M >> 2;
+    const uint32_t M = 1u << logm;
     const uint32_t i = t & (M - 1);
     const uint32_t bc = t >> logm;
-    const uint32_t jq = i & (MS - 1), qq = i >> (logm - 2);
     uint32_t y[NP];
-#pragma unroll
-    for (int q = 0; q < NP; q++) {
-        const PrimeK P = PS[q];
-        const Mod md = mod_of(P);
-        const int32_t *yp = ypart + (((size_t)bc * NP + q) * 4) * MS + jq;
-        int32_t r;
-        if (qq & 1u) {          // C1, C3
-            const int32_t c1 = smont(yp[0] - yp[MS], P.v2, md), c3 = smont(yp[2 * MS] - yp[3 * MS], P.v3, md);
-            r = (qq & 2u) ? smont(c1 - c3, P.v1, md) : c1 + c3;             // < 0.75 / < 1.5 * 2^29
-        } else {                // C0, C2
-            const int32_t c0 = sred(yp[0] + yp[MS], md), c2 = sred(yp[2 * MS] + yp[3 * MS], md);   // sums < 2.8: reduced to 0.51
-            r = (qq & 2u) ? smont(c0 - c2, P.v1, md) : c0 + c2;             // < 0.75 / < 1.03 * 2^29
-        }
-        y[q] = (uint32_t)(r + 3 * P.p) + P.hoff;                            // non-negative, below 4.6 p
-    }
+    quarter_residues<NP>(ypart, PS, bc, i, logm, y);
     const ulonglong2 d = load_digits(dig, bc, i, M);
     uint64_t lo, hi;
     crt_lean_one<NP, NL>(y, d.x, d.y, K, lo, hi);

@@ -111,6 +111,17 @@ def test_random_mode_equals_oracle_bit_for_bit(S, oc, ring):
     y1, y2 = bits[0::2], bits[1::2]
     for g, fn in enumerate((np.bitwise_and, np.bitwise_or, np.bitwise_xor)):
         assert np.array_equal(o.lwe_decrypt_bits(sk, out[:, g, :n], out[:, g, n]), fn(y1, y2))
+    if ring == "wide base":
+        # the calls above ran 3 gates in the latency form; the throughput form with 8 points per thread and
+        # the third digit plane is otherwise reached only at m >= 4096 (16 points per thread)
+        call += 1
+        eng.set_small_batch_max(0)
+        assert eng.kernel_names()[0] == "k_extprod<6, 3, true>"
+        raw = eng.bootstrap_batch(a1, b1, a2, b2, raw=True)
+        for t in range(batch):
+            ref_raw, _, _ = _oracle_run(bp, bk, a1[t], b1[t], a2[t], b2[t], t, call, set())
+            for g in range(3):
+                assert _ints(raw[t, g]) == ref_raw[g][0] + [ref_raw[g][1]]
     eng.close()
 
 

@@ -267,9 +267,9 @@ int32_t sgfhe_bootstrap_batch_device(sgfhe_ctx *ctx, const uint64_t *a1, const u
                                      uint64_t *out, uint32_t flags, void *stream);
 int32_t sgfhe_sync(sgfhe_ctx *ctx);
 /* Frees the staging buffers sgfhe_bootstrap_batch keeps on the ctx (device and page-locked host
- * memory, sized by the largest batch seen), the wire table and call staging of sgfhe_circuit_run[_ct],
- * and the work buffers of the packing path (sgfhe_pack_encrypted_bits, the pack stage of
- * sgfhe_circuit_run_ct); the next call allocates them again. */
+ * memory, sized by the largest batch seen), the wire table and call staging of sgfhe_circuit_run[_ct], the raw
+ * output table of SGFHE_CIRCUIT_PACK_DIRECT, and the work buffers of the packing path (sgfhe_pack_encrypted_bits,
+ * sgfhe_pack_lwe_modq, the pack stage of sgfhe_circuit_run_ct[_ex]); the next call allocates them again. */
 int32_t sgfhe_release_host_staging(sgfhe_ctx *ctx);
 
 /*
@@ -305,6 +305,24 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, c
  */
 int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *ctx, const uint64_t *a, const uint64_t *b,
                                   size_t count, uint64_t *out_w, uint64_t *out_v);
+/*
+ * The tail of pack_encrypted_bits (src/fhe.jl:675-695) on LWEs that are already over Z_Q: the n half-width
+ * external products, the sums and the ModRed, without the n refresh bootstraps of fhe.jl:669-673.  Those turn an
+ * LWE over Z_r into _bootstrap_internal's LWE over Z_Q (fhe.jl:585-594); a bit that has just left a gate
+ * bootstrap is such an LWE already (sgfhe_bootstrap_batch with SGFHE_FLAG_RAW_MODQ).
+ *   lwe          : [count][n][n + 1][2] uint64: for every bit a[0..n) then b, canonical 16-byte residues -- one
+ *                  gate's rows of a SGFHE_FLAG_RAW_MODQ result
+ *   out_w, out_v : [count][m] uint64 in [0, r)
+ * sgfhe_pack_encrypted_bits(a, b) equals this call on the AND rows of
+ * sgfhe_bootstrap_batch(a1 = 0, b1 = Dr, a, b, SGFHE_FLAG_RAW_MODQ) in the deterministic mode.  Host pointers;
+ * synchronous; upload, tail and download run on the ctx stream.  SGFHE_ERR_NO_KEY as elsewhere; a residue that
+ * is not below Q is SGFHE_ERR_INVALID_ARG, before anything is written; SGFHE_ERR_UNSUPPORTED where
+ * sgfhe_pack_encrypted_bits returns it.
+ * Flatten mode: the ctx's present one.  Randomised: the call takes one call number of the ctx's draw stream,
+ * and ciphertext `ct` draws for the flatten of as_i as in sgfhe_pack_encrypted_bits (y = 2^31 | i, z = ct); no
+ * bootstrap draws are consumed.
+ */
+int32_t sgfhe_pack_lwe_modq(sgfhe_ctx *ctx, const uint64_t *lwe, size_t count, uint64_t *out_w, uint64_t *out_v);
 
 /* Parity / debug hook: run the first n_iters iterations of the k-loop (src/fhe.jl:579-582) and
  * return the accumulator pair (a, b) as canonical residues, acc: [batch][2][m][2]. */
@@ -475,6 +493,34 @@ int32_t sgfhe_circuit_run(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instanc
  */
 int32_t sgfhe_circuit_run_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, const uint64_t *in_a,
                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe);
+/*
+ * The same with flags; flags = 0 is sgfhe_circuit_run_ct, unknown bits are SGFHE_ERR_INVALID_ARG.
+ *   SGFHE_CIRCUIT_PACK_DIRECT  pack the outputs that name a gate wire straight from the gate's un-reduced LWEs
+ *       over Z_Q (sgfhe_pack_lwe_modq), without the n refresh bootstraps per ciphertext.
+ * Ciphertext q = output * blocks + block is DIRECT when its output reference names a gate wire, negated or not,
+ * and REFRESHED when it names an input wire or the constant.  The levels run with the calls, rows and call
+ * numbers of sgfhe_circuit_run_ct, so out_lwe has the bytes of the flags = 0 run in both flatten modes; a level
+ * call that produces a wire some direct output names leaves its rows un-reduced, and its scatter kernel writes
+ * their ModRed (the words the reduced call gives) into the wire table and the named gate's rows into a raw
+ * output table [q][n][n + 1] of 16-byte residues.  NOT over Z_Q is enc_trivial(true) - w: a -> -a,
+ * b -> 2 DQ_tilde - b, mod Q.  The raw table is kept on the ctx like the wire table (grown on demand, freed by
+ * sgfhe_release_host_staging and sgfhe_ctx_destroy): n_outputs * blocks * n * (n + 1) * 16 bytes -- 16.8 MB
+ * per ciphertext at Params(1024), 285 MB per block for the 17 outputs of a 16-bit adder.  An allocation failure
+ * is SGFHE_ERR_OOM before any output is written.
+ * Pack stage -- the contract of the randomised flatten.  The ciphertexts are taken in ascending q, in groups of
+ * max(1, SGFHE_CIRCUIT_CALL_ROWS / n), as in sgfhe_circuit_run_ct.  A group that has refreshed ciphertexts first
+ * runs their bootstraps as ONE call (trivial encryption of 1 paired with every bit, AND branch, un-reduced;
+ * row = rank * n + j, rank = the ciphertext's position among the group's refreshed ones in ascending q), which
+ * takes one call number.  Every group then runs ONE tail (sgfhe_pack_lwe_modq: count = the group's ciphertexts,
+ * z = index within the group), which takes one call number.  So a group equals, on one draw stream, an optional
+ * sgfhe_bootstrap_batch(SGFHE_FLAG_RAW_MODQ) followed by one sgfhe_pack_lwe_modq.  No host synchronisation
+ * before the final download.
+ * With out_w NULL the flag changes nothing; blocks = 0 does nothing.
+ */
+#define SGFHE_CIRCUIT_PACK_DIRECT 1u
+int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, const uint64_t *in_a,
+                                const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
+                                uint32_t flags);
 
 /*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled

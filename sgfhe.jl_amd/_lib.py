@@ -144,6 +144,8 @@ def lib():
         "sgfhe_circuit_destroy": (i32, [vp]),
         "sgfhe_circuit_run": (i32, [vp, vp, sz, vp, vp]),
         "sgfhe_circuit_run_ct": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp]),
+        "sgfhe_circuit_run_ct_ex": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, u32]),
+        "sgfhe_pack_lwe_modq": (i32, [vp, vp, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -167,4 +169,5 @@ EXPORTED_SYMBOLS = (
     "sgfhe_host_decrypt_lwe", "sgfhe_host_decrypt_rlwe", "sgfhe_host_public_key",
     "sgfhe_host_encrypt_public", "sgfhe_host_pack_public", "sgfhe_host_normalize_public", "sgfhe_timing_enable", "sgfhe_timing_read",
     "sgfhe_kernel_names", "sgfhe_release_host_staging", "sgfhe_circuit_create", "sgfhe_circuit_info",
-    "sgfhe_circuit_destroy", "sgfhe_circuit_run", "sgfhe_circuit_run_ct")
+    "sgfhe_circuit_destroy", "sgfhe_circuit_run", "sgfhe_circuit_run_ct", "sgfhe_circuit_run_ct_ex",
+    "sgfhe_pack_lwe_modq")

@@ -256,11 +256,139 @@ def replay_ct(circuit, a, b, params, boot, pack):
     return (w.reshape(shape), v.reshape(shape)), lwe
 
 
-def evaluate_circuit_ct(bkey, rng, circuit, cts):
+# ---- residues mod Q as [..., 2] uint64 {lo, hi}: the few operations the direct replay needs, vectorised --------
+
+def _split128(x):
+    x = np.asarray(x, dtype=np.uint64)
+    return x[..., 0], x[..., 1]
+
+
+def _const128(v):
+    return np.uint64(v & 0xFFFFFFFFFFFFFFFF), np.uint64(v >> 64)
+
+
+def _ge128(al, ah, bl, bh):
+    return (ah > bh) | ((ah == bh) & (al >= bl))
+
+
+def _sub128(al, ah, bl, bh):
+    return al - bl, ah - bh - (al < bl).astype(np.uint64)
+
+
+def _add128(al, ah, bl, bh):
+    lo = al + bl
+    return lo, ah + bh + (lo < al).astype(np.uint64)
+
+
+def modred_words(x, Q, r):
+    """ModRed (src/fhe.jl:616-618,644-648; rescale, utils.jl:78-92) of residues [..., 2] uint64 {lo, hi} in [0, Q),
+    Q < 2^94, to words of [0, r), r a power of two up to 2^15: round(x r / Q) mod r, halves up."""
+    lo, hi = _split128(x)
+    logr = np.uint64(r.bit_length() - 1)
+    nl, nh = lo << logr, (hi << logr) | (lo >> (np.uint64(64) - logr))            # x r < 2^109
+    # the quotient to within one from doubles, then the exact remainder x r - q Q in 128-bit wrap-around words
+    q = np.floor((hi.astype(np.float64) * 2.0 ** 64 + lo.astype(np.float64)) * (float(r) / float(Q))).astype(np.uint64)
+    Ql, Qh = _const128(Q)
+    t0, t1 = q * (Ql & np.uint64(0xFFFFFFFF)), q * (Ql >> np.uint64(32))           # q < 2^16: below 2^48 each
+    pl, ph = _add128(t0, q * Qh, t1 << np.uint64(32), t1 >> np.uint64(32))
+    rl, rh = _sub128(nl, nh, pl, ph)
+    neg = rh >> np.uint64(63) != 0                                                 # q one too large
+    al, ah = _add128(rl, rh, Ql, Qh)
+    rl, rh, q = np.where(neg, al, rl), np.where(neg, ah, rh), np.where(neg, q - np.uint64(1), q)
+    big = _ge128(rl, rh, Ql, Qh)                                                   # q one too small
+    sl, sh = _sub128(rl, rh, Ql, Qh)
+    rl, rh, q = np.where(big, sl, rl), np.where(big, sh, rh), np.where(big, q + np.uint64(1), q)
+    q = q + _ge128(rl, rh, *_const128(Q // 2 + (Q & 1))).astype(np.uint64)         # utils.jl:84
+    return q & np.uint64(r - 1)                                                    # utils.jl:86-88
+
+
+def lwe_not_modq(x, Q, DQ_tilde):
+    """NOT of un-reduced LWEs [..., n + 1][2] over Z_Q: enc_trivial(true) - w with true = (0, 2 DQ_tilde):
+    a -> -a, b -> 2 DQ_tilde - b, mod Q."""
+    lo, hi = _split128(x)
+    Ql, Qh = _const128(Q)
+    ml, mh = _sub128(Ql, Qh, lo, hi)                                               # Q - a, 0 stays 0
+    zero = (lo == 0) & (hi == 0)
+    out = np.stack([np.where(zero, lo, ml), np.where(zero, hi, mh)], axis=-1)
+    Tl, Th = _const128((2 * DQ_tilde) % Q)
+    bl, bh = lo[..., -1], hi[..., -1]
+    dl, dh = _sub128(Tl, Th, bl, bh)
+    under = ~_ge128(Tl, Th, bl, bh)
+    el, eh = _add128(dl, dh, Ql, Qh)
+    out[..., -1, 0], out[..., -1, 1] = np.where(under, el, dl), np.where(under, eh, dh)
+    return out
+
+
+def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
+    """sgfhe_circuit_run_ct_ex with SGFHE_CIRCUIT_PACK_DIRECT composed on the host: a, b [n_inputs][blocks][N] ->
+    ((w, v), lwe) as replay_ct.  `boot_raw(call, a1, b1, a2, b2)` runs one call un-reduced and returns
+    [rows][3][n + 1][2] residues mod Q; the levels run through it in the row and call order of replay_levels, their
+    ModRed (modred_words) being what the next level reads and what `lwe` holds.  The pack stage takes the
+    ciphertexts q = output * blocks + block in ascending order, pack_calls(n) at a time: a group's refreshed
+    ciphertexts (outputs that name an input wire or the constant) are bootstrapped as one call -- trivial 1 paired
+    with every bit, row = rank among them * n + bit, AND rows kept -- and then `tail(call, lwe_q)` (lwe_q
+    [count][n][n + 1][2] -> (w, v), each [count][m]) packs the group: the gate's own rows for a direct output, NOT
+    over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  A checking and measuring aid."""
+    n, m, r, Q = params.n, params.m, params.r, params.Q
+    a = np.asarray(a, dtype=np.uint64)
+    b = np.asarray(b, dtype=np.uint64)
+    blocks = a.shape[1]
+    inst = blocks * n
+    inputs = split_ciphertext_array(a, b, n, r).reshape(circuit.n_inputs, inst, n + 1)
+    raws = []
+
+    def reduced(call, *args):
+        raws.append(np.asarray(boot_raw(call, *args), dtype=np.uint64))
+        return modred_words(raws[-1], Q, r)
+
+    lwe = replay_levels(circuit, inputs, r, reduced)
+    call, k, raw_wire = len(raws), 0, {}
+    for nodes in circuit.schedule():                        # the calls of a level, back into the level's rows
+        calls = -(-len(nodes) * inst // CALL_ROWS)
+        level = np.concatenate(raws[k:k + calls])
+        k += calls
+        for rank, g in enumerate(nodes):
+            for w in range(3):
+                raw_wire[circuit.n_inputs + 3 * g + w] = level[rank * inst:(rank + 1) * inst, w]
+
+    def is_direct(o):
+        i = circuit.outputs[o] & ~NOT_BIT & 0xFFFFFFFF
+        return i != FALSE_ID and i >= circuit.n_inputs
+
+    n_ct, cpc = circuit.n_outputs * blocks, pack_calls(n)
+    w = np.zeros((n_ct, m), dtype=np.uint64)
+    v = np.zeros((n_ct, m), dtype=np.uint64)
+    for q0 in range(0, n_ct, cpc):
+        qs = range(q0, min(q0 + cpc, n_ct))
+        group = np.zeros((len(qs), n, n + 1, 2), dtype=np.uint64)
+        fresh = [q for q in qs if not is_direct(q // blocks)]
+        if fresh:
+            y = np.concatenate([lwe[q // blocks, (q % blocks) * n:(q % blocks + 1) * n] for q in fresh])
+            one = np.zeros_like(y)
+            one[:, n] = r // 4
+            res = np.asarray(boot_raw(call, one[:, :n], one[:, n], y[:, :n], y[:, n]), dtype=np.uint64)
+            call += 1
+            for rank, q in enumerate(fresh):
+                group[q - q0] = res[rank * n:(rank + 1) * n, 0]
+        for q in qs:
+            o, t = q // blocks, q % blocks
+            if is_direct(o):
+                ref = circuit.outputs[o]
+                rows = raw_wire[ref & ~NOT_BIT & 0xFFFFFFFF][t * n:(t + 1) * n]
+                group[q - q0] = lwe_not_modq(rows, Q, params.DQ_tilde) if ref & NOT_BIT else rows
+        w[q0:q0 + cpc], v[q0:q0 + cpc] = tail(call, group)
+        call += 1
+    shape = (circuit.n_outputs, blocks, m)
+    return (w.reshape(shape), v.reshape(shape)), lwe
+
+
+def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False):
     """The circuit on RLWE ciphertexts, the reference's user flow (encrypt -> split_ciphertext -> gates ->
     pack_encrypted_bits -> decrypt) with the split and the pack on the device (Engine.circuit_run_ct).
     cts: [n_inputs][blocks] of PackedCiphertext or Ciphertext (all of one kind); bit i of a ciphertext is
-    instance i of its block.  rng as in evaluate_circuit.  Returns [n_outputs][blocks] of Ciphertext."""
+    instance i of its block.  rng as in evaluate_circuit.  direct=True: outputs that name a gate wire are packed
+    from the gate's LWEs over Z_Q without the refresh bootstraps (SGFHE_CIRCUIT_PACK_DIRECT); they decrypt alike.
+    Returns [n_outputs][blocks] of Ciphertext."""
     p = bkey.params
     if len(cts) != circuit.n_inputs:
         raise ValueError("evaluate_circuit_ct: one row of ciphertexts per input wire")
@@ -280,7 +408,7 @@ def evaluate_circuit_ct(bkey, rng, circuit, cts):
         raise ValueError("evaluate_circuit_ct: ciphertext polynomials of length %d expected" % N)
     with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
         _set_flatten_mode(bkey, rng)
-        w, v = bkey.engine.circuit_run_ct(circuit, a, b)
+        w, v = bkey.engine.circuit_run_ct(circuit, a, b, direct=direct)
     return [[Ciphertext(p, RLWE(w[o, t], v[o, t])) for t in range(blocks)] for o in range(circuit.n_outputs)]
 
 

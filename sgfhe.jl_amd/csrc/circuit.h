@@ -35,6 +35,10 @@ struct CircuitPlan {
     std::vector<uint32_t> in_ref;       // [live][2]: the node's inputs as slot references (CIRC_NOT, CIRC_FALSE)
     std::vector<uint32_t> out_slot;     // [live][3]: slot of its AND / OR / XOR wire, CIRC_NONE if unread
     std::vector<uint32_t> out_ref;      // [n_outputs]: the circuit's outputs as slot references
+    // Host only (SGFHE_CIRCUIT_PACK_DIRECT): where an output that names a gate wire is produced
+    std::vector<uint32_t> out_node;     // [n_outputs]: index in `order` of the producing node, CIRC_NONE for an input
+                                        // wire or the constant
+    std::vector<uint32_t> out_gate;     // [n_outputs]: 0 AND, 1 OR, 2 XOR (0 where out_node is CIRC_NONE)
 
     size_t live() const { return order.size(); }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
@@ -165,6 +169,17 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
         }
         P.out_ref.resize(n_outputs);
         for (size_t o = 0; o < n_outputs; o++) P.out_ref[o] = slot_ref(outputs[o]);
+        std::vector<uint32_t> rank_of(NG, CIRC_NONE);   // node -> index in `order`
+        for (size_t k = 0; k < P.live(); k++) rank_of[P.order[k]] = (uint32_t)k;
+        P.out_node.assign(n_outputs, CIRC_NONE);
+        P.out_gate.assign(n_outputs, 0);
+        for (size_t o = 0; o < n_outputs; o++) {
+            const uint32_t id = wire_id(outputs[o]);
+            const int64_t g = node_of(id);
+            if (g < 0) continue;
+            P.out_node[o] = rank_of[g];
+            P.out_gate[o] = (id - n_inputs) % 3;
+        }
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
         P = CircuitPlan();
         return SGFHE_ERR_OOM;

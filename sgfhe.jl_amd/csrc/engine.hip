@@ -250,6 +250,9 @@ struct sgfhe_ctx {
     DevBuf<uint64_t> pack_lwe, pack_pdig, pack_wv;
     DevBuf<ulonglong2> pack_raw;
     DevBuf<uint32_t> pack_yg;
+    // SGFHE_CIRCUIT_PACK_DIRECT: the raw output table [n_outputs * blocks][n][n + 1] of 16-byte residues over Z_Q,
+    // the un-reduced LWEs of every output ciphertext on their way into the pack tail
+    DevBuf<ulonglong2> circ_raw;
     // timing
     bool timing = false;
     struct EvTriple { hipEvent_t e0, e1, e2; };  // ext = e0 -> e1, crt = e1 -> e2
@@ -1751,6 +1754,7 @@ static void free_circuit_buffers(sgfhe_ctx *c) {
     c->circ_out.release();
     c->circ_tab.release();
     c->circ_ct.release();
+    c->circ_raw.release();
     c->pack_lwe.release();
     c->pack_raw.release();
     c->pack_pdig.release();
@@ -2496,16 +2500,50 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, con
 
 // The pack work buffers of the ctx for calls of at most `count` ciphertexts and `total` ciphertexts of
 // (w | v), in the ctx's present flatten mode; before anything is queued (nothing of the ctx in flight).
-static int32_t pack_grow(sgfhe_ctx *c, size_t count, size_t total) {
-    const size_t n = c->n, M = c->M, nb = count * n;
+// `boots` of the call's ciphertexts are bootstrapped first (all of them in pack_encrypted_bits; the refreshed ones
+// of a direct pack group); compact = true: pack_raw also holds a compact [count * n][n + 1] source (sgfhe_pack_lwe_modq).
+static int32_t pack_grow(sgfhe_ctx *c, size_t count, size_t total, size_t boots, bool compact = false) {
+    const size_t n = c->n, M = c->M, nb = boots * n;
     const uint32_t G = pack_group(c);
     const size_t groups = n / G, len = c->rnd ? M : n;
     int32_t rc;
     if ((rc = circ_grow(c, c->pack_lwe, 2 * nb * n + 2 * nb))) return rc;
-    if ((rc = circ_grow(c, c->pack_raw, nb * 3 * (n + 1)))) return rc;
+    if ((rc = circ_grow(c, c->pack_raw, std::max(nb * 3, compact ? count * n : 0) * (n + 1)))) return rc;
     if ((rc = circ_grow(c, c->pack_pdig, count * n * 2 * len))) return rc;
     if ((rc = circ_grow(c, c->pack_yg, count * groups * 2 * cur(c).npr * M))) return rc;
     return circ_grow(c, c->pack_wv, 2 * total * M);
+}
+
+// The tail of pack_encrypted_bits (fhe.jl:675-695) on `count` groups of n un-reduced LWEs resident on the device,
+// queued on `st`: the flatten of every as_i (drawing as call `call` of the ctx's stream in the randomised mode),
+// the half-width external products and the finish into d_w / d_v [count][m].  The LWE of bit j of group ci is
+// the n + 1 residues at raw + (ci * n + j) * rstride.  The caller has grown the work buffers and checked pack_G.
+static int32_t pack_tail(sgfhe_ctx *c, const ulonglong2 *raw, uint32_t rstride, size_t count, uint64_t *d_w,
+                         uint64_t *d_v, uint32_t call, hipStream_t st) {
+    const size_t n = c->n, M = c->M;
+    // rng != nothing: the flatten of every as_i (all m coefficients of the resized polynomial,
+    // utils.jl:253-264) draws from the ctx's ChaCha stream (fhe.jl:683-684)
+    const uint32_t mode = c->rnd ? MODE_RANDOM : 0u;
+    const sgfhe_ctx::Basis &S = cur(c);
+    const uint32_t G = pack_group(c);
+    const uint32_t groups = (uint32_t)(n / G);
+    const size_t len = c->rnd ? M : n;  // stored coefficients per digit polynomial
+    int32_t rc;
+    const RndArgs ra = {c->rnd_key, call, 0u, nullptr};
+    const size_t tf = count * n * len;
+    hipLaunchKernelGGL(k_pack_flatten, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, st, raw,
+                       c->pack_pdig.p, S.d_crt, (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, mode, ra, rstride);
+    if ((rc = launch_shortprod(c, c->pack_pdig.p, c->pack_yg.p, (uint32_t)count, G, groups, mode, st))) return rc;
+    const size_t tw = count * M;
+    if ((rc = with_npr(c, S.npr, [&](auto np) -> int32_t {
+            hipLaunchKernelGGL(k_pack_finish<decltype(np)::value>, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, st,
+                               c->pack_yg.p, raw, d_w, d_v, S.d_crt, (uint32_t)count, (uint32_t)n,
+                               (uint32_t)c->logm, groups, rstride);
+            return SGFHE_OK;
+        })))
+        return rc;
+    HIPCHK(c, hipGetLastError());
+    return SGFHE_OK;
 }
 
 // pack_encrypted_bits (fhe.jl:660-696) of `count` groups of n LWEs resident on the device, queued on `st`:
@@ -2514,32 +2552,12 @@ static int32_t pack_grow(sgfhe_ctx *c, size_t count, size_t total) {
 // d_w / d_v [count][m].  The caller has grown the work buffers (pack_grow) and checked pack_G.
 static int32_t pack_device(sgfhe_ctx *c, const uint64_t *d_a1, const uint64_t *d_b1, const uint64_t *d_a2,
                            const uint64_t *d_b2, size_t count, uint64_t *d_w, uint64_t *d_v, hipStream_t st) {
-    const size_t n = c->n, M = c->M, nb = count * n;
-    // rng != nothing: the n bootstraps and the flatten of every as_i (all m coefficients of the
-    // resized polynomial, utils.jl:253-264) draw from the ctx's ChaCha stream (fhe.jl:673,683-684)
-    const uint32_t mode = c->rnd ? MODE_RANDOM : 0u;
-    const sgfhe_ctx::Basis &S = cur(c);
-    const uint32_t G = pack_group(c);
-    const uint32_t groups = (uint32_t)(n / G);
-    const size_t len = c->rnd ? M : n;  // stored coefficients per digit polynomial
-    int32_t rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ,
-                                  c->n, nullptr, st);
+    // rng != nothing: the n bootstraps and the flatten of every as_i draw from the ctx's ChaCha stream as one
+    // call (the reference passes the same rng to both, fhe.jl:673,683-684)
+    int32_t rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, count * c->n, (uint64_t *)c->pack_raw.p,
+                                  SGFHE_FLAG_RAW_MODQ, c->n, nullptr, st);
     if (rc) return rc;
-    const RndArgs ra = {c->rnd_key, c->last_call, 0u, nullptr};
-    const size_t tf = count * n * len;
-    hipLaunchKernelGGL(k_pack_flatten, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, st, c->pack_raw.p,
-                       c->pack_pdig.p, S.d_crt, (uint32_t)count, (uint32_t)n, (uint32_t)c->logm, mode, ra);
-    if ((rc = launch_shortprod(c, c->pack_pdig.p, c->pack_yg.p, (uint32_t)count, G, groups, mode, st))) return rc;
-    const size_t tw = count * M;
-    if ((rc = with_npr(c, S.npr, [&](auto np) -> int32_t {
-            hipLaunchKernelGGL(k_pack_finish<decltype(np)::value>, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, st,
-                               c->pack_yg.p, c->pack_raw.p, d_w, d_v, S.d_crt, (uint32_t)count, (uint32_t)n,
-                               (uint32_t)c->logm, groups);
-            return SGFHE_OK;
-        })))
-        return rc;
-    HIPCHK(c, hipGetLastError());
-    return SGFHE_OK;
+    return pack_tail(c, c->pack_raw.p, 3 * (c->n + 1), count, d_w, d_v, c->last_call, st);
 }
 
 int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, size_t count,
@@ -2554,7 +2572,7 @@ int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_
     const size_t nb = count * n;  // bootstraps
     if (!(pack_group(c)))
         return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
-    if (pack_grow(c, count, count)) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(hipErrorOutOfMemory));
+    if (pack_grow(c, count, count, count)) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(hipErrorOutOfMemory));
     hipError_t e = hipSuccess;
     int32_t rc = SGFHE_OK;
     do {
@@ -2567,6 +2585,38 @@ int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_
         if ((e = hipMemcpyAsync(d_a2, a, nb * n * 8, hipMemcpyHostToDevice, c->stream))) break;
         if ((e = hipMemcpyAsync(d_b2, b, nb * 8, hipMemcpyHostToDevice, c->stream))) break;
         if ((rc = pack_device(c, d_a1, d_b1, d_a2, d_b2, count, d_w, d_v, c->stream))) break;
+        if ((e = hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
+        if ((e = hipMemcpyAsync(out_v, d_v, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
+        e = hipStreamSynchronize(c->stream);
+    } while (0);
+    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
+    if (rc) (void)hipStreamSynchronize(c->stream);   // whatever was queued finishes before the buffers are touched again
+    return rc;
+}
+
+int32_t sgfhe_pack_lwe_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uint64_t *out_w, uint64_t *out_v) {
+    if (!c || !lwe || !out_w || !out_v) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    if (count == 0) return SGFHE_OK;
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    const size_t n = c->n, M = c->M;
+    const size_t words = count * n * (n + 1);   // residues
+    for (size_t i = 0; i < words; i++)
+        if ((((u128)lwe[2 * i + 1] << 64) | lwe[2 * i]) >= c->Q)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_pack_lwe_modq: residue " + std::to_string(i) + " is not below Q");
+    (void)hipSetDevice(c->device);
+    SGFHE_QUIESCE(c);
+    if (!(pack_group(c)))
+        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
+    int32_t rc = pack_grow(c, count, count, 0, true);
+    if (rc) return rc;
+    const uint32_t call = c->rnd ? c->rnd_call++ : 0u;   // one call of the draw stream: the flatten of every as_i
+    c->last_call = call;
+    hipError_t e = hipSuccess;
+    do {
+        uint64_t *d_w = c->pack_wv.p, *d_v = d_w + count * M;
+        if ((e = hipMemcpyAsync(c->pack_raw.p, lwe, words * 16, hipMemcpyHostToDevice, c->stream))) break;
+        if ((rc = pack_tail(c, c->pack_raw.p, (uint32_t)(n + 1), count, d_w, d_v, call, c->stream))) break;
         if ((e = hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
         if ((e = hipMemcpyAsync(out_v, d_v, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
         e = hipStreamSynchronize(c->stream);
@@ -2891,6 +2941,7 @@ struct CircuitCt {
     const uint64_t *in_a, *in_b;   // [n_inputs][blocks][N]
     size_t blocks, N;
     uint64_t *out_w, *out_v;       // [n_outputs][blocks][m], or both NULL
+    bool direct;                   // SGFHE_CIRCUIT_PACK_DIRECT
 };
 
 // ciphertexts per pack call of sgfhe_circuit_run_ct
@@ -2913,17 +2964,42 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     const size_t n_ct = pack ? (size_t)P.n_outputs * ct->blocks : 0;   // ciphertext q = output * blocks + block
     const size_t cpc = std::min(circuit_pack_cpc(c), n_ct);             // ciphertexts of the largest pack call
     const size_t ct_words = ct ? (size_t)P.n_inputs * ct->blocks * ct->N : 0;
+    // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire, by producing node (ascending index in `order`,
+    // so the jobs of one level call are a run of the table): job = {output, rank of the node in its level,
+    // gate | CIRC_NOT}; and the most refreshed ciphertexts any pack group has
+    const bool direct = pack && ct->direct;
+    std::vector<uint32_t> jobs, job_k;   // (outlive the asynchronous copy: the run ends in a synchronisation)
+    size_t max_ref = cpc;
+    if (direct) {
+        std::vector<uint32_t> byk;
+        for (uint32_t o = 0; o < P.n_outputs; o++)
+            if (P.out_node[o] != CIRC_NONE) byk.push_back(o);
+        std::stable_sort(byk.begin(), byk.end(), [&](uint32_t x, uint32_t y) { return P.out_node[x] < P.out_node[y]; });
+        for (uint32_t o : byk) {
+            const uint32_t k = P.out_node[o], L = P.level[P.order[k]];
+            job_k.push_back(k);
+            jobs.insert(jobs.end(), {o, k - P.level_start[L], P.out_gate[o] | (P.out_ref[o] & CIRC_NOT)});
+        }
+        max_ref = 0;
+        for (size_t q0 = 0; q0 < n_ct; q0 += cpc) {
+            size_t nref = 0;
+            for (size_t q = q0; q < std::min(q0 + cpc, n_ct); q++) nref += P.out_node[q / ct->blocks] == CIRC_NONE;
+            max_ref = std::max(max_ref, nref);
+        }
+    }
     // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller)
     const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() +
-                             (ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0);
+                             (ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0) + jobs.size();
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
-    if ((rc = circ_grow(c, c->circ_stage, (size_t)max_rows * 5 * row))) return rc;
+    // (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even word offset)
+    if ((rc = circ_grow(c, c->circ_stage, (size_t)max_rows * (direct ? 8 : 5) * row))) return rc;
+    if (direct && (rc = circ_grow(c, c->circ_raw, n_ct * n * row))) return rc;
     if (out && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_tab, tab_words))) return rc;
     if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
-    if (pack && (rc = pack_grow(c, cpc, n_ct))) return rc;
-    const uint64_t work_rows = std::max<uint64_t>(max_rows, cpc * n);
+    if (pack && (rc = pack_grow(c, cpc, n_ct, max_ref))) return rc;
+    const uint64_t work_rows = std::max<uint64_t>(max_rows, max_ref * n);
     if (work_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
                        // then a no-op and never waits on the host between levels)
         const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
@@ -2931,6 +3007,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     }
     uint32_t *d_in_ref = c->circ_tab.p, *d_out_slot = d_in_ref + P.in_ref.size(), *d_out_ref = d_out_slot + P.out_slot.size();
     uint32_t *d_in_slot = d_out_ref + P.out_ref.size(), *d_pack_ref = d_in_slot + P.input_slot.size();
+    uint32_t *d_jobs = d_pack_ref + 2 * P.out_ref.size();
+    if (!jobs.empty()) HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_in_ref, P.in_ref.data(), P.in_ref.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_slot, P.out_slot.data(), P.out_slot.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_ref, P.out_ref.data(), P.out_ref.size() * 4, hipMemcpyHostToDevice, st));
@@ -2978,6 +3056,24 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires.p,
                                d_in_ref + 2 * (size_t)k0, a1, b1, a2, b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
             HIPCHK(c, hipGetLastError());
+            // a call that produces a wire some direct output names leaves its rows un-reduced: the scatter reduces
+            // what the wire table takes (the words k_final writes) and copies the named rows into the raw table
+            const uint32_t ka = k0 + (uint32_t)(row0 / inst), kb = k0 + (uint32_t)((row0 + rows - 1) / inst);
+            const size_t j0 = std::lower_bound(job_k.begin(), job_k.end(), ka) - job_k.begin();
+            const size_t j1 = std::upper_bound(job_k.begin(), job_k.end(), kb) - job_k.begin();
+            if (j1 > j0) {
+                if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, SGFHE_FLAG_RAW_MODQ, c->n, nullptr, st))) return rc;
+                for (size_t j = j0; j < j1;) {   // (a grid holds 65535 rows of workgroups)
+                    const uint32_t wires = j == j0, nj = (uint32_t)std::min<size_t>(j1 - j, 65535u - wires);
+                    hipLaunchKernelGGL(k_circ_scatter_raw, dim3(rows, nj + wires), dim3(256), 0, st,
+                                       reinterpret_cast<const ulonglong2 *>(res), d_out_slot + 3 * (size_t)k0,
+                                       c->circ_wires.p, d_jobs + 3 * j, c->circ_raw.p, cur(c).d_crt, (uint32_t)row0, inst,
+                                       (uint32_t)n, wires);
+                    HIPCHK(c, hipGetLastError());
+                    j += nj;
+                }
+                continue;
+            }
             // the k-loop of sgfhe_bootstrap_batch_device: the next call number of the ctx's draw stream
             if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, 0u, c->n, nullptr, st))) return rc;
             hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, res,
@@ -2988,7 +3084,47 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     // the pack stage: ciphertexts q0 .. q0 + cnt of a call are rows q0 * n .. of the "level" whose node o is
     // (TRUE, output o) -- row = o * instances + block * n + bit -- so the gather of the levels builds the call's
     // bootstrap inputs, and each call is one sgfhe_pack_encrypted_bits(count = cnt) on the device
-    for (size_t q0 = 0; q0 < n_ct; q0 += cpc) {
+    // SGFHE_CIRCUIT_PACK_DIRECT: a group's refreshed ciphertexts (outputs that name an input wire or the constant)
+    // are bootstrapped as one call, row = rank among them * n + bit, and their AND rows join the direct ones in the
+    // raw table; then one tail over the group's rows of that table, a call of its own
+    for (size_t q0 = 0; direct && q0 < n_ct; q0 += cpc) {
+        const size_t cnt = std::min(cpc, n_ct - q0);
+        struct Run { size_t q, rank, len; };   // consecutive refreshed ciphertexts: one gather, one copy
+        std::vector<Run> runs;
+        size_t nref = 0;
+        for (size_t q = q0; q < q0 + cnt; q++) {
+            if (P.out_node[q / ct->blocks] != CIRC_NONE) continue;
+            if (!runs.empty() && runs.back().q + runs.back().len == q) runs.back().len++;
+            else runs.push_back({q, nref, 1});
+            nref++;
+        }
+        if (nref) {
+            const size_t nb = nref * n;
+            uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
+            for (const Run &R : runs) {
+                const size_t off = R.rank * n;
+                const uint32_t tg = (uint32_t)(R.len * n * row);
+                hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires.p, d_pack_ref,
+                                   p1 + off * n, q1 + off, p2 + off * n, q2 + off, (uint32_t)(R.q * n), (uint32_t)(R.len * n),
+                                   inst, (uint32_t)n, r);
+                HIPCHK(c, hipGetLastError());
+            }
+            if ((rc = bootstrap_device(c, p1, q1, p2, q2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ, c->n,
+                                       nullptr, st)))
+                return rc;
+            for (const Run &R : runs) {
+                hipLaunchKernelGGL(k_circ_raw_and, dim3((uint32_t)(R.len * n)), dim3(256), 0, st,
+                                   c->pack_raw.p + R.rank * n * 3 * row, c->circ_raw.p + R.q * n * row, (uint32_t)n);
+                HIPCHK(c, hipGetLastError());
+            }
+        }
+        const uint32_t call = c->rnd ? c->rnd_call++ : 0u;
+        c->last_call = call;
+        if ((rc = pack_tail(c, c->circ_raw.p + q0 * n * row, (uint32_t)row, cnt, c->pack_wv.p + q0 * M,
+                            c->pack_wv.p + (n_ct + q0) * M, call, st)))
+            return rc;
+    }
+    for (size_t q0 = 0; !direct && q0 < n_ct; q0 += cpc) {
         const size_t cnt = std::min(cpc, n_ct - q0), nb = cnt * n;
         uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
         const uint32_t tg = (uint32_t)(nb * row);
@@ -3039,8 +3175,16 @@ int32_t sgfhe_circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instan
 
 int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe) {
+    return sgfhe_circuit_run_ct_ex(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, 0u);
+}
+
+int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
+                                const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
+                                uint32_t flags) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    if (flags & ~SGFHE_CIRCUIT_PACK_DIRECT)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct_ex: unknown flag bits");
     if (!circ || ((!in_a || !in_b) && circ->plan.n_inputs))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: NULL circuit or input pointer");
     if (!out_w != !out_v || (!out_w && !out_lwe))
@@ -3063,7 +3207,7 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blo
     (void)hipSetDevice(c->device);
     int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
     if (rc) return rc;
-    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v};
+    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0};
     rc = circuit_run_queued(c, P, (size_t)instances, nullptr, out_lwe, &ct);
     if (rc) {   // whatever was queued finishes before the buffers can be touched again
         (void)hipStreamSynchronize(c->stream);

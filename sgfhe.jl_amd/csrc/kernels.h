@@ -1708,6 +1708,63 @@ k_circ_scatter(const uint64_t *__restrict__ res, const uint32_t *__restrict__ ou
     wires[((size_t)slot * instances + inst) * (n + 1) + e] = res[t];
 }
 
+// The scatter of a level call whose k-loop left its rows un-reduced ([rows][3][n + 1] 16-byte residues over
+// Z_Q: SGFHE_CIRCUIT_PACK_DIRECT, a call that produces a wire some packed output names).  One workgroup per
+// (row, blockIdx.y); the threads run along the n + 1 axis, so the loads are coalesced 16-byte accesses and the
+// row decode is per workgroup, not per thread.
+//   blockIdx.y == 0 (launches with_wires = 1; a call with more jobs than a grid holds takes further launches
+//                    without): ModRed (the device function of k_final: the same words) of the gate outputs something
+//                    reads into their slots of the wire table, as k_circ_scatter does with reduced rows;
+//   blockIdx.y == with_wires + j: job j = {output o, rank of the producing node in its level, gate | CIRC_REF_NOT}:
+//                    the rows of that node copied as they are into rawout [o][instances][n + 1].  NOT over Z_Q
+//                    is enc_trivial(true) - w with true = (0, 2 DQ_tilde): a -> -a, b -> 2 DQ_tilde - b mod Q.
+__global__ void __launch_bounds__(256)
+k_circ_scatter_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__ out_slot,
+                   uint64_t *__restrict__ wires, const uint32_t *__restrict__ jobs, ulonglong2 *__restrict__ rawout,
+                   const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint32_t with_wires) {
+    const uint32_t lr = blockIdx.x, R = row0 + lr;
+    const uint32_t rank = R / instances, inst = R % instances;   // (uniform over the workgroup)
+    const size_t stride = n + 1;
+    if (with_wires && blockIdx.y == 0) {
+        for (uint32_t g = 0; g < 3; g++) {
+            const uint32_t slot = out_slot[3 * rank + g];
+            if (slot == CIRC_SLOT_NONE) continue;
+            const ulonglong2 *src = res + ((size_t)lr * 3 + g) * stride;
+            uint64_t *dst = wires + ((size_t)slot * instances + inst) * stride;
+            for (uint32_t e = threadIdx.x; e <= n; e += 256) {
+                const ulonglong2 v = src[e];
+                dst[e] = modred(((u128)v.y << 64) | v.x, CC);
+            }
+        }
+        return;
+    }
+    const uint32_t *job = jobs + 3 * (size_t)(blockIdx.y - with_wires);
+    if (job[1] != rank) return;
+    const uint32_t neg = job[2] & CIRC_REF_NOT, g = job[2] & 3u;
+    const ulonglong2 *src = res + ((size_t)lr * 3 + g) * stride;
+    ulonglong2 *dst = rawout + ((size_t)job[0] * instances + inst) * stride;
+    const u128 Q = CC->Q, one = 2 * CC->DQ;
+    for (uint32_t e = threadIdx.x; e <= n; e += 256) {
+        ulonglong2 v = src[e];
+        if (neg) {
+            const u128 x = ((u128)v.y << 64) | v.x;
+            const u128 y = e < n ? (x ? Q - x : 0) : (one >= x ? one - x : one + Q - x);
+            v = make_ulonglong2((uint64_t)y, (uint64_t)(y >> 64));
+        }
+        dst[e] = v;
+    }
+}
+
+// gate 0 (AND) of an un-reduced bootstrap output [rows][3][n + 1] -> compact rows [rows][n + 1] (the refreshed
+// ciphertexts of a direct pack group on their way into the raw output table); one workgroup per row
+__global__ void __launch_bounds__(256)
+k_circ_raw_and(const ulonglong2 *__restrict__ res, ulonglong2 *__restrict__ dst, uint32_t n) {
+    const size_t stride = n + 1;
+    const ulonglong2 *src = res + (size_t)blockIdx.x * 3 * stride;
+    ulonglong2 *d = dst + (size_t)blockIdx.x * stride;
+    for (uint32_t e = threadIdx.x; e <= n; e += 256) d[e] = src[e];
+}
+
 // the circuit's outputs [n_outputs][instances][n + 1], NOT and the constant applied (grid-stride: the
 // array may hold more than 2^32 words)
 __global__ void __launch_bounds__(256)
@@ -1813,15 +1870,17 @@ k_flatten_canon(const ulonglong2 *__restrict__ in, uint64_t *__restrict__ dig,
 //   4. k_pack_finish: CRT of every group, sum mod Q, w = ModRed(-W), v = ModRed(b - V)
 // ==================================================================================================
 
-// raw: [count * n][3][n + 1] 16-byte residues (RAW_MODQ bootstrap output); only gate 0 (AND) is
-// read.  pdig: [count][n slices][2 digits][len] uint64 with len = n coefficients for the
+// raw: the un-reduced LWE of bit j of ciphertext ci is the n + 1 16-byte residues at row
+// (ci * n + j) * rstride -- rstride = 3 (n + 1) for a RAW_MODQ bootstrap output [count * n][3][n + 1],
+// of which only gate 0 (AND) is read, and n + 1 for a compact [count * n][n + 1] source
+// (sgfhe_pack_lwe_modq).  pdig: [count][n slices][2 digits][len] uint64 with len = n coefficients for the
 // deterministic flatten (the zero padding of as_i, fhe.jl:675-677, has the constant digits of 0)
 // and len = m for the randomised one (flatten_poly draws for every coefficient of the resized
 // polynomial, utils.jl:253-264).
 __global__ void __launch_bounds__(256)
 k_pack_flatten(const ulonglong2 *__restrict__ raw, uint64_t *__restrict__ pdig,
                const CrtConst *__restrict__ CC, uint32_t count, uint32_t n, uint32_t logm,
-               uint32_t mode, RndArgs ra) {
+               uint32_t mode, RndArgs ra, uint32_t rstride) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t len = (mode & MODE_RANDOM) ? (1u << logm) : n;
     if (t >= (size_t)count * n * len) return;
@@ -1831,7 +1890,7 @@ k_pack_flatten(const ulonglong2 *__restrict__ raw, uint64_t *__restrict__ pdig,
     const u128 Q = CC->Q;
     u128 x = 0;
     if (j < n) {
-        const ulonglong2 v = raw[(((size_t)ci * n + j) * 3 + 0) * (n + 1) + i];
+        const ulonglong2 v = raw[((size_t)ci * n + j) * rstride + i];
         x = ((u128)v.y << 64) | v.x;
     }
     uint64_t *d = pdig + (((size_t)ci * n + i) * 2) * len + j;
@@ -1929,13 +1988,13 @@ k_shortprod(const uint64_t *__restrict__ pdig, const int32_t *__restrict__ keyha
 
 // One thread per (ciphertext, coefficient k < m): W = sum_g CRT(y_g column 0), V likewise
 // (fhe.jl:686-687); w = ModRed(-W), v = ModRed(b_k - V) (fhe.jl:689-693), b_k = the un-reduced
-// LWE constant of bit k for k < n and 0 beyond (resize, fhe.jl:678).
+// LWE constant of bit k for k < n and 0 beyond (resize, fhe.jl:678).  raw / rstride as in k_pack_flatten.
 template <int NP>
 __global__ void __launch_bounds__(256)
 k_pack_finish(const uint32_t *__restrict__ yg, const ulonglong2 *__restrict__ raw,
               uint64_t *__restrict__ out_w, uint64_t *__restrict__ out_v,
               const CrtConst *__restrict__ CC, uint32_t count, uint32_t n, uint32_t logm,
-              uint32_t groups) {
+              uint32_t groups, uint32_t rstride) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t M = 1u << logm;
     if (t >= (size_t)count * M) return;
@@ -1958,7 +2017,7 @@ k_pack_finish(const uint32_t *__restrict__ yg, const ulonglong2 *__restrict__ ra
     const u128 w1 = acc[0] ? Q - acc[0] : 0;
     u128 bk = 0;
     if (kk < n) {
-        const ulonglong2 v = raw[(((size_t)ci * n + kk) * 3 + 0) * (n + 1) + n];
+        const ulonglong2 v = raw[((size_t)ci * n + kk) * rstride + n];
         bk = ((u128)v.y << 64) | v.x;
     }
     const u128 v1 = bk >= acc[1] ? bk - acc[1] : bk + Q - acc[1];

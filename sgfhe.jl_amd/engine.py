@@ -13,6 +13,7 @@ import numpy as np
 from . import _lib
 
 FLAG_RAW_MODQ = 1
+CIRCUIT_PACK_DIRECT = 1      # SGFHE_CIRCUIT_PACK_DIRECT
 FLAG_RAW_RNS2 = 2
 CTX_RANDOM_FLATTEN = 1          # accepted, without effect since ABI revision 6
 CTX_DETERMINISTIC_ONLY = 2
@@ -236,13 +237,16 @@ class Engine:
         self._call("sgfhe_circuit_run", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p))
         return out
 
-    def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False):
+    def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False, direct=False):
         """A gate circuit with RLWE ciphertexts at both ends (sgfhe_circuit_run_ct): split_ciphertext of the
         inputs and pack_encrypted_bits of the outputs run on the device inside the one run.
         a, b: [n_inputs][blocks][N] uint64, rlwe.a / rlwe.b of one ciphertext per (input, block), N = n
         (PackedCiphertext) or m (Ciphertext); a ciphertext is one wire over n instances.
         packed: return (w, v), each [n_outputs][blocks][m]; lwe: return the LWE array
-        [n_outputs][blocks * n][n + 1] of circuit_run.  Both: ((w, v), lwe)."""
+        [n_outputs][blocks * n][n + 1] of circuit_run.  Both: ((w, v), lwe).
+        direct: SGFHE_CIRCUIT_PACK_DIRECT (sgfhe_circuit_run_ct_ex) -- outputs that name a gate wire are packed
+        from the gate's LWEs over Z_Q, without the n refresh bootstraps per ciphertext; the packed ciphertexts
+        decrypt alike but are other bytes, the LWE outputs are the same bytes."""
         p = self.params
         a, pa = _c(a)
         b, pb = _c(b)
@@ -256,7 +260,11 @@ class Engine:
         v = np.zeros((circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
         out = np.zeros((circuit.n_outputs, blocks * p.n, p.n + 1), dtype=np.uint64) if lwe else None
         ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None else None
-        self._call("sgfhe_circuit_run_ct", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out))
+        if direct:
+            self._call("sgfhe_circuit_run_ct_ex", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out),
+                       CIRCUIT_PACK_DIRECT)
+        else:
+            self._call("sgfhe_circuit_run_ct", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out))
         if packed and lwe:
             return (w, v), out
         return (w, v) if packed else out
@@ -275,6 +283,22 @@ class Engine:
         self._call("sgfhe_pack_encrypted_bits", pa, pb, count,
                                                     w.ctypes.data_as(ctypes.c_void_p),
                                                     v.ctypes.data_as(ctypes.c_void_p))
+        return w, v
+
+    def pack_lwe_modq(self, lwe):
+        """The tail of pack_encrypted_bits (fhe.jl:675-695) on LWEs already over Z_Q (sgfhe_pack_lwe_modq):
+        lwe [count][n][n + 1][2] uint64, a then b as 16-byte residues -- one gate's rows of
+        bootstrap_batch(raw=True) -- -> (w, v), each [count][m] uint64 over Z_r."""
+        p = self.params
+        lwe, pl = _c(lwe)
+        per = p.n * (p.n + 1) * 2
+        if lwe.size % per:
+            raise ValueError("pack_lwe_modq: lwe is [count][n][n + 1][2]")
+        count = lwe.size // per
+        w = np.zeros((count, p.m), dtype=np.uint64)
+        v = np.zeros((count, p.m), dtype=np.uint64)
+        if count:
+            self._call("sgfhe_pack_lwe_modq", pl, count, w.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p))
         return w, v
 
     # ---- parity / debug hooks ---------------------------------------------------------------

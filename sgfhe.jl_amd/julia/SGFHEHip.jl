@@ -263,6 +263,57 @@ function SGFHE.pack_encrypted_bits(hkey::HipBootstrapKey, rng::Union{AbstractRNG
                                    Polynomial(mk.(v), negacyclic_modulus)))
 end
 
+"""
+    pack_lwe_modq(hkey, rng, lwe::Vector{UInt64}, count)
+
+The tail of pack_encrypted_bits (src/fhe.jl:675-695) on LWEs that are already over Z_Q, without the n
+refresh bootstraps: `lwe` holds [count][n][n + 1][2] words, a then b of every bit as 16-byte canonical
+residues -- one gate's rows of a SGFHE_FLAG_RAW_MODQ result.  Returns (w, v), each count * m words over Z_r.
+"""
+function pack_lwe_modq(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing}, lwe::Vector{UInt64},
+                       count::Integer)
+    p = hkey.params
+    @assert length(lwe) == count * p.n * (p.n + 1) * 2
+    w = Vector{UInt64}(undef, count * p.m)
+    v = Vector{UInt64}(undef, count * p.m)
+    fkey = flatten_key(rng)
+    with_slot(hkey) do slot
+        set_flatten_mode(slot.ctx, fkey)
+        rc = ccall((:sgfhe_pack_lwe_modq, libsgfhe_hip), Int32,
+                   (Ptr{Cvoid}, Ptr{UInt64}, Csize_t, Ptr{UInt64}, Ptr{UInt64}),
+                   slot.ctx, lwe, count, w, v)
+        check(slot.ctx, rc)
+    end
+    w, v
+end
+
+const CIRCUIT_PACK_DIRECT = UInt32(1)   # SGFHE_CIRCUIT_PACK_DIRECT
+
+"""
+    circuit_run_ct(hkey, rng, circuit::Ptr{Cvoid}, n_outputs, blocks, in_a, in_b, N; direct=false)
+
+sgfhe_circuit_run_ct_ex on a plan made with sgfhe_circuit_create: in_a, in_b [n_inputs][blocks][N] words
+(N = n or m) -> (w, v), each n_outputs * blocks * m words.  `direct = true` packs the outputs that name a gate
+wire from the gate's LWEs over Z_Q, without the refresh bootstraps (SGFHE_CIRCUIT_PACK_DIRECT).
+"""
+function circuit_run_ct(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing}, circuit::Ptr{Cvoid},
+                        n_outputs::Integer, blocks::Integer, in_a::Vector{UInt64}, in_b::Vector{UInt64},
+                        N::Integer; direct::Bool=false)
+    p = hkey.params
+    w = Vector{UInt64}(undef, n_outputs * blocks * p.m)
+    v = Vector{UInt64}(undef, n_outputs * blocks * p.m)
+    fkey = flatten_key(rng)
+    with_slot(hkey) do slot
+        set_flatten_mode(slot.ctx, fkey)
+        rc = ccall((:sgfhe_circuit_run_ct_ex, libsgfhe_hip), Int32,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Ptr{UInt64}, Ptr{UInt64}, Csize_t, Ptr{UInt64}, Ptr{UInt64},
+                    Ptr{UInt64}, UInt32),
+                   slot.ctx, circuit, blocks, in_a, in_b, N, w, v, C_NULL, direct ? CIRCUIT_PACK_DIRECT : UInt32(0))
+        check(slot.ctx, rc)
+    end
+    w, v
+end
+
 # The drop-in: same signature as src/fhe.jl:608-610, batch of one.
 SGFHE.bootstrap(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing},
                 bit1::EncryptedBit, bit2::EncryptedBit) =

@@ -15,6 +15,10 @@ Engine.bootstrap_batch on host arrays, at Params(1024), deterministic flatten.
       (sgfhe_host_split_ciphertext), circuit_run, pack_encrypted_bits in groups of 8 ciphertexts.  The two
       alternate in one process on two ctxs that share one key (the order swaps every round); the bytes must be
       equal; prints both times per round, their spread, and the bytes each moves over PCIe each way.
+  python tools/circuit_bench.py --ct --direct [--configs 16x1] [--reps 3]
+      (A) as above against (D) the same run with SGFHE_CIRCUIT_PACK_DIRECT -- the outputs packed from the gates' LWEs
+      over Z_Q, without the n refresh bootstraps per output ciphertext -- alternating on one ctx; the LWE outputs
+      must be the same bytes; prints both times per round and the bootstraps each runs.
   python tools/circuit_bench.py --ct --trace [--configs 16x1] [--dir DIR]
       run (A) alone in a child process under `rocprofv3 --kernel-trace --stats`: the share of k_circ_split.
 
@@ -148,6 +152,55 @@ def wall_ct(args):
     eng_a.close()
 
 
+def wall_direct(args):
+    import sgfhe_jl_amd as S
+    import encrypted_adder
+    from sgfhe_jl_amd import circuit as C
+    params = S.Params(1024)
+    n = params.n
+    eng = S.Engine(params)
+    rng = np.random.default_rng(1)
+    eng.generate_key(rng.integers(0, 2, size=n).astype(np.uint64), 2)
+    print("build %s, Params(1024), deterministic flatten, call rows %d, %d ciphertexts per pack group"
+          % (eng.build_id(), C.CALL_ROWS, C.pack_calls(n)))
+    warm = encrypted_adder.adder_circuit(S, 2)
+    wa = rng.integers(0, params.r, size=(4, 1, n), dtype=np.uint64)
+    for d in (False, True):
+        eng.circuit_run_ct(warm, wa, wa, direct=d)
+    for bits, blocks in configs(args.configs):
+        c = encrypted_adder.adder_circuit(S, bits)
+        info = c.info()
+        inst = blocks * n
+        refreshed = sum(1 for ref in c.outputs if (ref & 0x7FFFFFFF) < c.n_inputs or (ref & 0x7FFFFFFF) == C.FALSE_ID)
+        boots = {"A": (info["nodes"] + c.n_outputs) * inst, "D": (info["nodes"] + refreshed) * inst}
+        a = rng.integers(0, params.r, size=(2 * bits, blocks, n), dtype=np.uint64)
+        b = rng.integers(0, params.r, size=(2 * bits, blocks, n), dtype=np.uint64)
+        print("\n%d-bit adder x %d block(s) = %d instances: %d levels, %d nodes per instance, %d outputs (%d refreshed "
+              "in the direct run); bootstraps per run: (A) %d, (D) %d; raw output table %.0f MB"
+              % (bits, blocks, inst, info["levels"], info["nodes"], c.n_outputs, refreshed, boots["A"], boots["D"],
+                 c.n_outputs * blocks * n * (n + 1) * 16 / 1e6))
+        t = {"A": [], "D": []}
+        for rep in range(args.reps):
+            res = {}
+            order = ("A", "D") if rep % 2 == 0 else ("D", "A")
+            for what in order:
+                t0 = time.perf_counter()
+                out = eng.circuit_run_ct(c, a, b, packed=True, lwe=True, direct=what == "D")
+                res[what] = (time.perf_counter() - t0, out)
+                t[what].append(res[what][0])
+            same = np.array_equal(res["A"][1][1], res["D"][1][1])
+            print("  round %d (%s first): (A) refreshed %.3f s = %.0f bootstraps/s | (D) direct %.3f s = %.0f bootstraps/s | "
+                  "D / A %.4f | same LWE outputs: %s"
+                  % (rep, order[0], t["A"][-1], boots["A"] / t["A"][-1], t["D"][-1], boots["D"] / t["D"][-1],
+                     t["D"][-1] / t["A"][-1], same))
+            if not same:
+                sys.exit("the LWE outputs of the direct run differ")
+        print("  (A) mean %.3f s, spread %.3f s | (D) mean %.3f s, spread %.3f s | mean D / mean A = %.4f, by bootstrap "
+              "counts %.4f" % (np.mean(t["A"]), max(t["A"]) - min(t["A"]), np.mean(t["D"]), max(t["D"]) - min(t["D"]),
+                               np.mean(t["D"]) / np.mean(t["A"]), boots["D"] / boots["A"]))
+    eng.close()
+
+
 def ct_only(args):
     import sgfhe_jl_amd as S
     import encrypted_adder
@@ -212,6 +265,7 @@ def main():
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--ct", action="store_true", help="ciphertexts in and out: circuit_run_ct against the composition")
+    ap.add_argument("--direct", action="store_true", help="with --ct: the refreshed run against SGFHE_CIRCUIT_PACK_DIRECT")
     ap.add_argument("--circuit-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--ct-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dir", default="circuit_trace", help="where rocprofv3 writes its files")
@@ -226,6 +280,8 @@ def main():
         ct_only(args)
     elif args.trace:
         trace(args)
+    elif args.ct and args.direct:
+        wall_direct(args)
     elif args.ct:
         wall_ct(args)
     else:

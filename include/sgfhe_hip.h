@@ -268,7 +268,7 @@ int32_t sgfhe_bootstrap_batch_device(sgfhe_ctx *ctx, const uint64_t *a1, const u
 int32_t sgfhe_sync(sgfhe_ctx *ctx);
 /* Frees the staging buffers sgfhe_bootstrap_batch keeps on the ctx (device and page-locked host
  * memory, sized by the largest batch seen), the wire table and call staging of sgfhe_circuit_run[_ct], the raw
- * output table of SGFHE_CIRCUIT_PACK_DIRECT, and the work buffers of the packing path (sgfhe_pack_encrypted_bits,
+ * output table of SGFHE_CIRCUIT_PACK_DIRECT, the tables of the noise probe, and the work buffers of the packing path (sgfhe_pack_encrypted_bits,
  * sgfhe_pack_lwe_modq, the pack stage of sgfhe_circuit_run_ct[_ex]); the next call allocates them again. */
 int32_t sgfhe_release_host_staging(sgfhe_ctx *ctx);
 
@@ -521,6 +521,60 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t bloc
 int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, const uint64_t *in_a,
                                 const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
                                 uint32_t flags);
+
+/*
+ * Noise probe: the LWE error of rows against the SECRET key, reduced on the device to exact integer statistics.
+ * DIAGNOSTICS: the secret key crosses this boundary, so both entry points are for parameter studies and tests (what
+ * the reference's examples/errors.jl and examples/depth.jl show), never part of a deployment.  The key bits are on
+ * the device for the length of the call only.  Every statistic is an integer sum, count or maximum: a record does not
+ * depend on launch geometry or summation order.
+ *
+ * sgfhe_lwe_noise: `count` rows (count < 2^32), host pointers, synchronous; no bootstrap key is needed.
+ *   sk               n words, bit 0 of each is the key bit (as in sgfhe_bkey_generate)
+ *   lwe              flags = 0: rows over Z_r, [n + 1] uint64, a then b;
+ *                    flags = SGFHE_FLAG_RAW_MODQ: rows over Z_Q, [n + 1][2] canonical 16-byte residues, the layout
+ *                    of a SGFHE_FLAG_RAW_MODQ result (and of sgfhe_pack_lwe_modq's input).  A residue that is not
+ *                    below Q is SGFHE_ERR_INVALID_ARG before anything is queued.
+ *   row_stride_words uint64 words from one row to the next, at least the row length (n + 1, or 2 (n + 1) and even over
+ *                    Z_Q): 3 (n + 1) probes one gate of a [batch][3][n + 1] result in place
+ *   expected[count]  the plaintext bit of every row (bit 0)
+ * Z_r.  phase = b - sum a_i s_i mod r; e = the centred representative of phase - expected Dr mod r in (-r/2, r/2],
+ * Dr = r / 4.
+ *   stats[0] rows
+ *   stats[1] rows that decrypt wrongly: ((phase + Dr/2) mod r) div Dr != expected, the rule of decrypt(::EncryptedBit)
+ *            (src/fhe.jl:504-507); quotients 2 and 3 count as wrong
+ *   stats[2] max |e|
+ *   stats[3] sum e, two's-complement int64
+ *   stats[4] sum e^2
+ *   stats[5] rows with |e| >= Dr/4 (the margin of one input of the next gate)
+ *   stats[6], [7] 0
+ * Z_Q.  The codewords are 0 and 2 DQ_tilde (enc_trivial(true) = (0, 2 DQ_tilde)); e = the centred representative of
+ * phase - expected 2 DQ_tilde mod Q in (-Q/2, Q/2].
+ *   stats[0] rows
+ *   stats[1] rows with |e| >= DQ_tilde
+ *   stats[2], [3] max |e| as lo, hi
+ *   stats[4], [5] sum |e| as lo, hi (|e| < 2^93 and count < 2^32: it fits)
+ *   stats[6], [7] 0
+ * count = 0 gives an all-zero record.  SGFHE_ERR_INVALID_ARG for NULL sk / stats (and lwe / expected when count > 0),
+ * other flag bits, a short (or, over Z_Q, odd) stride, count >= 2^32.
+ *
+ * sgfhe_circuit_run_probe: the run of sgfhe_circuit_run -- same calls, rows and call numbers of the draw stream, `out`
+ * has its bytes in both flatten modes -- that also measures every wire.
+ *   in_bits [n_inputs][instances] the plaintext bit of every input LWE (may be NULL when n_inputs is 0)
+ *   stats   [n_inputs + 3 n_gates][8]: one Z_r record per wire id -- inputs 0 .. n_inputs - 1, then AND, OR, XOR of
+ *           node g at n_inputs + 3 g -- over all instances, against the circuit's plaintext evaluation of in_bits.
+ *           Every wire of every live node is measured whether something reads it or not (the probe reads each level
+ *           call's own result rows, after its last kernel and before the next call reuses them); the wires of pruned
+ *           nodes get all-zero records; the constant has none.
+ * The plaintext bits go up once per run as a bit table, the records come down once at the end; no host
+ * synchronisation is added between levels.  The table of records is kept on the ctx like the wire table (grown on
+ * demand, freed by sgfhe_release_host_staging and sgfhe_ctx_destroy).  Errors: those of sgfhe_circuit_run, and
+ * SGFHE_ERR_INVALID_ARG for a NULL sk, in_bits or stats (nothing is written to `out`).
+ */
+int32_t sgfhe_lwe_noise(sgfhe_ctx *ctx, const uint64_t *sk, const uint64_t *lwe, size_t count,
+                        size_t row_stride_words, const uint8_t *expected, uint32_t flags, uint64_t stats[8]);
+int32_t sgfhe_circuit_run_probe(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
+                                uint64_t *out, const uint64_t *sk, const uint8_t *in_bits, uint64_t *stats);
 
 /*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled

@@ -146,6 +146,8 @@ def lib():
         "sgfhe_circuit_run_ct": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp]),
         "sgfhe_circuit_run_ct_ex": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, u32]),
         "sgfhe_pack_lwe_modq": (i32, [vp, vp, sz, vp, vp]),
+        "sgfhe_lwe_noise": (i32, [vp, vp, vp, sz, sz, vp, u32, _u64p]),
+        "sgfhe_circuit_run_probe": (i32, [vp, vp, sz, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -170,4 +172,4 @@ EXPORTED_SYMBOLS = (
     "sgfhe_host_encrypt_public", "sgfhe_host_pack_public", "sgfhe_host_normalize_public", "sgfhe_timing_enable", "sgfhe_timing_read",
     "sgfhe_kernel_names", "sgfhe_release_host_staging", "sgfhe_circuit_create", "sgfhe_circuit_info",
     "sgfhe_circuit_destroy", "sgfhe_circuit_run", "sgfhe_circuit_run_ct", "sgfhe_circuit_run_ct_ex",
-    "sgfhe_pack_lwe_modq")
+    "sgfhe_pack_lwe_modq", "sgfhe_lwe_noise", "sgfhe_circuit_run_probe")

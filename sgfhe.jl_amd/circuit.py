@@ -412,6 +412,59 @@ def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False):
     return [[Ciphertext(p, RLWE(w[o, t], v[o, t])) for t in range(blocks)] for o in range(circuit.n_outputs)]
 
 
+def _input_array(circuit, inputs, n):
+    """[n_inputs][instances] of EncryptedBit -> the array form [n_inputs][instances][n + 1] uint64."""
+    arr = np.zeros((circuit.n_inputs, len(inputs[0]) if circuit.n_inputs else 0, n + 1), dtype=np.uint64)
+    for i, row in enumerate(inputs):
+        if len(row) != arr.shape[1]:
+            raise ValueError("ragged inputs: every input needs one EncryptedBit per instance")
+        for t, e in enumerate(row):
+            arr[i, t, :n] = e.lwe.a
+            arr[i, t, n] = e.lwe.b
+    return arr
+
+
+def probe_circuit(bkey, key, rng, circuit, inputs, bits):
+    """evaluate_circuit that also measures the LWE error of every wire on the device (Engine.circuit_probe,
+    sgfhe_circuit_run_probe).  A DIAGNOSTIC for parameter studies and tests: `key` is the PrivateKey, and its
+    bits cross the library boundary.  inputs as evaluate_circuit; bits [n_inputs][instances]: the plaintext of
+    every input.  Returns (outputs, stats): outputs as evaluate_circuit (the same bytes), stats a list of
+    engine.NoiseStats by wire id (noise_report formats it)."""
+    n = bkey.params.n
+    as_bits = not isinstance(inputs, np.ndarray)
+    if as_bits:
+        inputs = _input_array(circuit, inputs, n)
+    bits = np.asarray(bits).astype(np.uint8).reshape(circuit.n_inputs, -1)
+    with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
+        _set_flatten_mode(bkey, rng)
+        out, stats = bkey.engine.circuit_probe(circuit, inputs, key.key, bits)
+    if as_bits:
+        out = [[EncryptedBit(LWE(out[o, t, :n], out[o, t, n])) for t in range(out.shape[1])]
+               for o in range(out.shape[0])]
+    return out, stats
+
+
+def noise_report(circuit, stats):
+    """The records of probe_circuit by wire: a list of dicts (wire, kind: "input" / "AND" / "OR" / "XOR", node,
+    level (0 for inputs), rows, wrong, max_abs, mean, rms, margin), the wires of pruned nodes left out, sorted
+    by max |e| (largest first), then level."""
+    level = {}
+    for L, nodes in enumerate(circuit.schedule(), start=1):
+        for g in nodes:
+            level[g] = L
+    rows = []
+    for wire, st in enumerate(stats):
+        if st.rows == 0:
+            continue
+        g = (wire - circuit.n_inputs) // 3 if wire >= circuit.n_inputs else None
+        kind = "input" if g is None else ("AND", "OR", "XOR")[(wire - circuit.n_inputs) % 3]
+        rows.append(dict(wire=wire, kind=kind, node=g, level=0 if g is None else level[g], rows=st.rows,
+                         wrong=st.wrong, max_abs=st.max_abs, mean=st.sum / st.rows,
+                         rms=(st.sum_sq / st.rows) ** 0.5, margin=st.margin))
+    rows.sort(key=lambda d: (-d["max_abs"], d["level"], d["wire"]))
+    return rows
+
+
 def evaluate_circuit(bkey, rng, circuit, inputs):
     """The circuit over many instances on the HIP engine.  rng = None: deterministic flatten; a numpy
     Generator: randomised flatten (its ChaCha8 key drawn from `rng`, call counter from 0).

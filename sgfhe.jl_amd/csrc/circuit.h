@@ -1,7 +1,8 @@
 // Host-side planner of sgfhe_circuit_* (include/sgfhe_hip.h): validates a gate
 // graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
-// slot of the device wire table by liveness, and fixes the row and call numbering of a run.  Plain C++,
-// no HIP: tests/native/circuit_plan_sanitized.cpp drives it under ASan / UBSan on the CPU.
+// slot of the device wire table by liveness, and fixes the row and call numbering of a run; circuit_plain_bits
+// evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp
+// and circuit_bits_sanitized.cpp drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -39,6 +40,9 @@ struct CircuitPlan {
     std::vector<uint32_t> out_node;     // [n_outputs]: index in `order` of the producing node, CIRC_NONE for an input
                                         // wire or the constant
     std::vector<uint32_t> out_gate;     // [n_outputs]: 0 AND, 1 OR, 2 XOR (0 where out_node is CIRC_NONE)
+    // Host only (sgfhe_circuit_run_probe): the node's inputs as PROBE ROWS -- row i < n_inputs is input wire i, row
+    // n_inputs + 3 k + w is wire w of the k-th live node in `order` -- with CIRC_NOT and CIRC_FALSE as in a reference
+    std::vector<uint32_t> in_row;       // [live][2]
 
     size_t live() const { return order.size(); }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
@@ -171,6 +175,14 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
         for (size_t o = 0; o < n_outputs; o++) P.out_ref[o] = slot_ref(outputs[o]);
         std::vector<uint32_t> rank_of(NG, CIRC_NONE);   // node -> index in `order`
         for (size_t k = 0; k < P.live(); k++) rank_of[P.order[k]] = (uint32_t)k;
+        auto row_ref = [&](uint32_t ref) -> uint32_t {
+            const uint32_t id = wire_id(ref);
+            const int64_t g = node_of(id);
+            return (g < 0 ? id : n_inputs + 3 * rank_of[g] + (id - n_inputs) % 3) | (ref & CIRC_NOT);
+        };
+        P.in_row.resize(2 * P.live());
+        for (size_t k = 0; k < P.live(); k++)
+            for (int j = 0; j < 2; j++) P.in_row[2 * k + j] = row_ref(gates[2 * P.order[k] + j]);
         P.out_node.assign(n_outputs, CIRC_NONE);
         P.out_gate.assign(n_outputs, 0);
         for (size_t o = 0; o < n_outputs; o++) {
@@ -183,6 +195,49 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
         P = CircuitPlan();
         return SGFHE_ERR_OOM;
+    }
+    return SGFHE_OK;
+}
+
+// The circuit in clear over `instances`, for the noise probe (sgfhe_circuit_run_probe): the plaintext bit of every
+// probe row -- the n_inputs input wires, then AND, OR, XOR of every live node in `order` -- as a bit table of
+// circuit_probe_rows(P) rows of circuit_bit_words(instances) uint64 words each: bit (t & 63) of word t / 64 of a row
+// is instance t (the bits past `instances` in a row's last word are unspecified).  in_bits [n_inputs][instances],
+// bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances).  SGFHE_ERR_OOM when the table
+// cannot be allocated; nothing throws out of it.
+inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * P.live(); }
+inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
+// wire id of a probe row (the inverse of CircuitPlan::in_row's numbering)
+inline uint32_t circuit_probe_wire(const CircuitPlan &P, size_t row) {
+    if (row < P.n_inputs) return (uint32_t)row;
+    const size_t k = (row - P.n_inputs) / 3, w = (row - P.n_inputs) % 3;
+    return (uint32_t)(P.n_inputs + 3 * (size_t)P.order[k] + w);
+}
+inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, size_t instances,
+                                  std::vector<uint64_t> &table) noexcept {
+    if (!in_bits && P.n_inputs && instances) return SGFHE_ERR_INVALID_ARG;
+    const size_t wpr = circuit_bit_words(instances);
+    try {
+        table.assign(circuit_probe_rows(P) * wpr, 0);
+    } catch (...) {
+        return SGFHE_ERR_OOM;
+    }
+    for (size_t i = 0; i < P.n_inputs; i++)
+        for (size_t t = 0; t < instances; t++)
+            table[i * wpr + t / 64] |= (uint64_t)(in_bits[i * instances + t] & 1u) << (t % 64);
+    auto word = [&](uint32_t ref, size_t w) -> uint64_t {
+        const uint32_t row = circuit_detail::wire_id(ref);
+        const uint64_t v = row == CIRC_FALSE ? 0ull : table[(size_t)row * wpr + w];
+        return ref & CIRC_NOT ? ~v : v;
+    };
+    for (size_t k = 0; k < P.live(); k++) {   // `order` is a topological order: inputs are rows filled before
+        uint64_t *o = table.data() + ((size_t)P.n_inputs + 3 * k) * wpr;
+        for (size_t w = 0; w < wpr; w++) {
+            const uint64_t x = word(P.in_row[2 * k], w), y = word(P.in_row[2 * k + 1], w);
+            o[w] = x & y;
+            o[wpr + w] = x | y;
+            o[2 * wpr + w] = x ^ y;
+        }
     }
     return SGFHE_OK;
 }

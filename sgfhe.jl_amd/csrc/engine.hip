@@ -253,6 +253,10 @@ struct sgfhe_ctx {
     // SGFHE_CIRCUIT_PACK_DIRECT: the raw output table [n_outputs * blocks][n][n + 1] of 16-byte residues over Z_Q,
     // the un-reduced LWEs of every output ciphertext on their way into the pack tail
     DevBuf<ulonglong2> circ_raw;
+    // noise probe (sgfhe_lwe_noise, sgfhe_circuit_run_probe), grown and freed like the circuit buffers: the per-wire
+    // records, the partial records of k_lwe_noise_q, the key mask and the plaintext bit table (noise_layout); and the
+    // rows the probe reads that no other buffer holds (the primitive's LWEs, a probed run's unread inputs)
+    DevBuf<uint64_t> noise_tab, noise_lwe;
     // timing
     bool timing = false;
     struct EvTriple { hipEvent_t e0, e1, e2; };  // ext = e0 -> e1, crt = e1 -> e2
@@ -1755,6 +1759,8 @@ static void free_circuit_buffers(sgfhe_ctx *c) {
     c->circ_tab.release();
     c->circ_ct.release();
     c->circ_raw.release();
+    c->noise_tab.release();
+    c->noise_lwe.release();
     c->pack_lwe.release();
     c->pack_raw.release();
     c->pack_pdig.release();
@@ -2944,13 +2950,46 @@ struct CircuitCt {
     bool direct;                   // SGFHE_CIRCUIT_PACK_DIRECT
 };
 
+// ---- noise probe: LWE error statistics against the secret key, on the device -------------
+
+static constexpr uint32_t NOISE_Q_GRID = 1024;   // workgroups (partial records) of k_lwe_noise_q
+
+// noise_tab: [wires][8] records | [NOISE_Q_GRID][8] partial records | key mask | [wires][bit_words] plaintext bits
+struct NoiseLayout {
+    uint64_t *stats, *partial, *mask, *bits;
+};
+static NoiseLayout noise_layout(sgfhe_ctx *c, size_t wires) {
+    uint64_t *p = c->noise_tab.p;
+    return {p, p + wires * 8, p + wires * 8 + (size_t)NOISE_Q_GRID * 8, p + wires * 8 + (size_t)NOISE_Q_GRID * 8 + NOISE_MASK_WORDS};
+}
+static int32_t noise_grow(sgfhe_ctx *c, size_t wires, size_t bit_words, size_t lwe_words) {
+    int32_t rc = circ_grow(c, c->noise_tab, wires * 8 + (size_t)NOISE_Q_GRID * 8 + NOISE_MASK_WORDS + wires * bit_words);
+    return rc ? rc : circ_grow(c, c->noise_lwe, lwe_words);
+}
+// host image of [key mask | bit table]: bit l of mask word j is the key bit s[64 j + l] (k_lwe_noise's lane order)
+static void noise_key_mask(const sgfhe_ctx *c, const uint64_t *sk, uint64_t *mask) {
+    std::fill(mask, mask + NOISE_MASK_WORDS, 0ull);
+    for (uint32_t i = 0; i < c->n; i++) mask[i / 64] |= (sk[i] & 1ull) << (i % 64);
+}
+static uint32_t noise_tiles(uint64_t instances) { return (uint32_t)((instances + NOISE_ROWS - 1) / NOISE_ROWS); }
+
+// the probe of a run (sgfhe_circuit_run_probe): host images that outlive the run's asynchronous copies
+struct CircuitProbe {
+    const uint64_t *sk;
+    const uint8_t *in_bits;
+    uint64_t *stats;                  // [n_inputs + 3 n_gates][8], by wire id
+    std::vector<uint64_t> up, down;   // [key mask | bit table]; the records by probe row
+};
+
 // ciphertexts per pack call of sgfhe_circuit_run_ct
 static size_t circuit_pack_cpc(const sgfhe_ctx *c) { return std::max<size_t>(1, SGFHE_CIRCUIT_CALL_ROWS / c->n); }
 
 // `in` / `out`: the LWE form ([wire][instances][n + 1]); with `ct` the inputs come from ct->in_a / in_b instead and
 // `out` is optional.
+// `probe` (LWE form only): the noise records of every input wire and of every live node's three wires, taken from
+// the uploaded inputs and from each level call's own result rows.
 static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in,
-                                  uint64_t *out, const CircuitCt *ct) {
+                                  uint64_t *out, const CircuitCt *ct, CircuitProbe *probe = nullptr) {
     const size_t n = c->n, row = n + 1, M = c->M;
     const uint32_t inst = (uint32_t)instances;
     const uint64_t r = c->par.r;
@@ -2999,6 +3038,25 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     if ((rc = circ_grow(c, c->circ_tab, tab_words))) return rc;
     if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
     if (pack && (rc = pack_grow(c, cpc, n_ct, max_ref))) return rc;
+    const size_t probe_rows = probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
+    NoiseLayout NL = {};
+    if (probe) {
+        size_t unread = 0;   // inputs nothing reads have no slot: the probe uploads them for itself
+        for (uint32_t i = 0; i < P.n_inputs; i++) unread += P.input_slot[i] == CIRC_NONE;
+        if ((rc = noise_grow(c, probe_rows, bit_words, unread * instances * row))) return rc;
+        std::vector<uint64_t> table;
+        if ((rc = circuit_plain_bits(P, probe->in_bits, instances, table)))
+            return fail(c, rc, "sgfhe_circuit_run_probe: no memory for the plaintext bit table");
+        try {
+            probe->up.assign(NOISE_MASK_WORDS, 0);
+            probe->up.insert(probe->up.end(), table.begin(), table.end());
+            probe->down.assign(probe_rows * 8, 0);
+        } catch (...) {
+            return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run_probe: no memory for the plaintext bit table");
+        }
+        noise_key_mask(c, probe->sk, probe->up.data());
+        NL = noise_layout(c, probe_rows);
+    }
     const uint64_t work_rows = std::max<uint64_t>(max_rows, max_ref * n);
     if (work_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
                        // then a no-op and never waits on the host between levels)
@@ -3012,6 +3070,10 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     HIPCHK(c, hipMemcpyAsync(d_in_ref, P.in_ref.data(), P.in_ref.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_slot, P.out_slot.data(), P.out_slot.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_ref, P.out_ref.data(), P.out_ref.size() * 4, hipMemcpyHostToDevice, st));
+    if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
+        HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
+        if (probe_rows) HIPCHK(c, hipMemsetAsync(NL.stats, 0, probe_rows * 64, st));
+    }
     std::vector<uint32_t> pack_ref;   // (outlives the asynchronous copy: the run ends in a synchronisation)
     if (ct) {
         // the ciphertexts as they are, and extract() of every bit into the slot of its input wire
@@ -3043,6 +3105,21 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             HIPCHK(c, hipMemcpyAsync(c->circ_wires.p + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
                                      (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
             i = k;
+        }
+        // the probe of the input wires, from the rows as uploaded (before a level reuses a slot)
+        for (uint32_t i = 0, u = 0; probe && i < P.n_inputs; i++) {
+            const uint64_t *rows_i;
+            if (P.input_slot[i] == CIRC_NONE) {
+                uint64_t *dst = c->noise_lwe.p + (size_t)u++ * in_words;
+                HIPCHK(c, hipMemcpyAsync(dst, in + (size_t)i * in_words, in_words * 8, hipMemcpyHostToDevice, st));
+                rows_i = dst;
+            } else {
+                rows_i = c->circ_wires.p + (size_t)P.input_slot[i] * in_words;
+            }
+            const NoiseGeom G = {row, 0, i, 0, 0, inst, inst, 0, noise_tiles(inst), (uint32_t)bit_words, (uint32_t)n};
+            hipLaunchKernelGGL(k_lwe_noise, dim3(G.tiles), dim3(64 * NOISE_WAVES), 0, st, rows_i, NL.mask, NL.bits,
+                               (unsigned long long *)NL.stats, G, (uint32_t)cur(c).h_crt.logr);
+            HIPCHK(c, hipGetLastError());
         }
     }
     uint64_t *a1 = c->circ_stage.p, *a2 = a1 + max_rows * n, *b1 = a2 + max_rows * n, *b2 = b1 + max_rows,
@@ -3079,6 +3156,18 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, res,
                                d_out_slot + 3 * (size_t)k0, c->circ_wires.p, (uint32_t)row0, rows, inst, (uint32_t)n);
             HIPCHK(c, hipGetLastError());
+            if (probe) {
+                // the call's own result rows [rows][3][n + 1], read or not, before the next call overwrites them (same
+                // stream).  A call inside one node: tiles over its rows; a call over several nodes: tiles over every
+                // node's instances (a tile never straddles two nodes; rows outside the call are skipped)
+                const uint32_t nodes = kb - ka + 1;
+                const uint32_t inst0 = nodes == 1 ? (uint32_t)(row0 - (uint64_t)(ka - k0) * inst) : 0u;
+                const NoiseGeom G = {3 * row, row, (uint32_t)(P.n_inputs + 3 * (size_t)ka), ka - k0, (uint32_t)row0, rows, inst,
+                                     inst0, noise_tiles(nodes == 1 ? rows : inst), (uint32_t)bit_words, (uint32_t)n};
+                hipLaunchKernelGGL(k_lwe_noise, dim3(nodes * G.tiles, 3), dim3(64 * NOISE_WAVES), 0, st, res, NL.mask,
+                                   NL.bits, (unsigned long long *)NL.stats, G, (uint32_t)cur(c).h_crt.logr);
+                HIPCHK(c, hipGetLastError());
+            }
         }
     }
     // the pack stage: ciphertexts q0 .. q0 + cnt of a call are rows q0 * n .. of the "level" whose node o is
@@ -3145,8 +3234,140 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(out, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
     }
+    if (probe && probe_rows)
+        HIPCHK(c, hipMemcpyAsync(probe->down.data(), NL.stats, probe_rows * 64, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     c->pending = false;
+    if (probe) {   // records by wire id; the wires of pruned nodes stay zero
+        std::fill(probe->stats, probe->stats + ((size_t)P.n_inputs + 3 * (size_t)P.n_gates) * 8, 0ull);
+        for (size_t w = 0; w < probe_rows; w++)
+            std::copy(probe->down.begin() + w * 8, probe->down.begin() + w * 8 + 8,
+                      probe->stats + (size_t)circuit_probe_wire(P, w) * 8);
+    }
+    return SGFHE_OK;
+}
+
+// sgfhe_circuit_run, with `probe` the run of sgfhe_circuit_run_probe
+static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                               uint64_t *out, CircuitProbe *probe) {
+    if (!circ || !out || (!in && circ->plan.n_inputs))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: NULL circuit, input or output pointer");
+    if (probe && (!probe->sk || !probe->stats || (!probe->in_bits && circ->plan.n_inputs)))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_probe: NULL secret key, input bits or statistics pointer");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    const CircuitPlan &P = circ->plan;
+    if (instances == 0) {
+        if (probe) std::fill(probe->stats, probe->stats + ((size_t)P.n_inputs + 3 * (size_t)P.n_gates) * 8, 0ull);
+        return SGFHE_OK;
+    }
+    // rows of a level, and words of every table, must be addressable by the kernels' indices
+    if (instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
+    (void)hipSetDevice(c->device);
+    int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
+    if (rc) return rc;
+    rc = circuit_run_queued(c, P, instances, in, out, nullptr, probe);
+    if (rc) {   // whatever was queued finishes before the buffers can be touched again
+        (void)hipStreamSynchronize(c->stream);
+        c->pending = false;
+    }
+    return rc;
+}
+
+int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                                uint64_t *out, const uint64_t *sk, const uint8_t *in_bits, uint64_t *stats) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    CircuitProbe probe = {sk, in_bits, stats, {}, {}};
+    return circuit_run_lwe(c, circ, instances, in, out, &probe);
+}
+
+// everything sgfhe_lwe_noise queues (its caller waits for the stream when a step fails)
+static int32_t lwe_noise_queued(sgfhe_ctx *c, const uint64_t *lwe, size_t count, size_t stride, bool raw,
+                                const std::vector<uint64_t> &up, std::vector<uint64_t> &down) {
+    const size_t n = c->n, rowlen = (n + 1) * (raw ? 2 : 1), bit_words = circuit_bit_words(count);
+    hipStream_t st = c->stream;
+    const NoiseLayout NL = noise_layout(c, 1);
+    HIPCHK(c, hipMemcpyAsync(NL.mask, up.data(), up.size() * 8, hipMemcpyHostToDevice, st));
+    // the rows, compact on the device whatever the caller's stride
+    if (stride == rowlen) HIPCHK(c, hipMemcpyAsync(c->noise_lwe.p, lwe, count * rowlen * 8, hipMemcpyHostToDevice, st));
+    else HIPCHK(c, hipMemcpy2DAsync(c->noise_lwe.p, rowlen * 8, lwe, stride * 8, rowlen * 8, count, hipMemcpyHostToDevice, st));
+    const NoiseGeom G = {n + 1, 0, 0, 0, 0, (uint32_t)count, (uint32_t)count, 0, noise_tiles(count), (uint32_t)bit_words, (uint32_t)n};
+    if (raw) {
+        const uint32_t grid = std::min(G.tiles, NOISE_Q_GRID);
+        hipLaunchKernelGGL(k_lwe_noise_q, dim3(grid), dim3(64 * NOISE_WAVES), 0, st,
+                           reinterpret_cast<const ulonglong2 *>(c->noise_lwe.p), NL.mask, NL.bits,
+                           (unsigned long long *)NL.partial, cur(c).d_crt, G);
+        HIPCHK(c, hipGetLastError());
+        down.assign((size_t)grid * 8, 0);
+        HIPCHK(c, hipMemcpyAsync(down.data(), NL.partial, down.size() * 8, hipMemcpyDeviceToHost, st));
+    } else {
+        HIPCHK(c, hipMemsetAsync(NL.stats, 0, 64, st));
+        hipLaunchKernelGGL(k_lwe_noise, dim3(G.tiles), dim3(64 * NOISE_WAVES), 0, st, c->noise_lwe.p, NL.mask, NL.bits,
+                           (unsigned long long *)NL.stats, G, (uint32_t)cur(c).h_crt.logr);
+        HIPCHK(c, hipGetLastError());
+        down.assign(8, 0);
+        HIPCHK(c, hipMemcpyAsync(down.data(), NL.stats, 64, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    return SGFHE_OK;
+}
+
+int32_t sgfhe_lwe_noise(sgfhe_ctx *c, const uint64_t *sk, const uint64_t *lwe, size_t count, size_t row_stride_words,
+                        const uint8_t *expected, uint32_t flags, uint64_t stats[8]) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    if (!sk || !stats || (count && (!lwe || !expected)))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_noise: NULL secret key, row, expected-bit or statistics pointer");
+    if (flags & ~SGFHE_FLAG_RAW_MODQ) return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_noise: flags are 0 or SGFHE_FLAG_RAW_MODQ");
+    const bool raw = (flags & SGFHE_FLAG_RAW_MODQ) != 0;
+    const size_t n = c->n, rowlen = (n + 1) * (raw ? 2 : 1);
+    if (row_stride_words < rowlen || (raw && (row_stride_words & 1)))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_noise: row_stride_words below the row length (or odd, for rows over Z_Q)");
+    if (count > 0xFFFFFFFFull) return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_noise: count must be below 2^32");
+    for (size_t i = 0; raw && i < count; i++)
+        for (size_t e = 0; e <= n; e++)
+            if (ld128(lwe + i * row_stride_words + 2 * e) >= c->Q)
+                return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_noise: residue " + std::to_string(e) + " of row " +
+                                                          std::to_string(i) + " is not below Q");
+    std::fill(stats, stats + 8, 0ull);
+    if (count == 0) return SGFHE_OK;
+    (void)hipSetDevice(c->device);
+    SGFHE_QUIESCE(c);
+    const size_t bit_words = circuit_bit_words(count);
+    int32_t rc = noise_grow(c, 1, bit_words, count * rowlen);
+    if (rc) return rc;
+    std::vector<uint64_t> up, down;   // [key mask | expected bits]; the record or the partial records
+    try {
+        up.assign(NOISE_MASK_WORDS + bit_words, 0);
+    } catch (...) {
+        return fail(c, SGFHE_ERR_OOM, "sgfhe_lwe_noise: no memory for the expected-bit table");
+    }
+    noise_key_mask(c, sk, up.data());
+    for (size_t i = 0; i < count; i++) up[NOISE_MASK_WORDS + i / 64] |= (uint64_t)(expected[i] & 1u) << (i % 64);
+    try {
+        rc = lwe_noise_queued(c, lwe, count, row_stride_words, raw, up, down);
+    } catch (...) {
+        rc = fail(c, SGFHE_ERR_OOM, "sgfhe_lwe_noise: no memory for the partial records");
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    if (!raw) {
+        std::copy(down.begin(), down.end(), stats);
+        return SGFHE_OK;
+    }
+    u128 emax = 0, esum = 0;   // fold the workgroups' partial records (there is no 128-bit atomic)
+    for (size_t g = 0; g < down.size() / 8; g++) {
+        const uint64_t *rec = down.data() + g * 8;
+        stats[0] += rec[0];
+        stats[1] += rec[1];
+        emax = std::max(emax, ld128(rec + 2));
+        esum += ld128(rec + 4);
+    }
+    stats[2] = (uint64_t)emax, stats[3] = (uint64_t)(emax >> 64);
+    stats[4] = (uint64_t)esum, stats[5] = (uint64_t)(esum >> 64);
     return SGFHE_OK;
 }
 
@@ -3154,23 +3375,7 @@ int32_t sgfhe_circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instan
                           uint64_t *out) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    if (!circ || !out || (!in && circ->plan.n_inputs))
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: NULL circuit, input or output pointer");
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    const CircuitPlan &P = circ->plan;
-    if (instances == 0) return SGFHE_OK;
-    // rows of a level, and words of every table, must be addressable by the kernels' indices
-    if (instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
-    (void)hipSetDevice(c->device);
-    int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
-    if (rc) return rc;
-    rc = circuit_run_queued(c, P, instances, in, out, nullptr);
-    if (rc) {   // whatever was queued finishes before the buffers can be touched again
-        (void)hipStreamSynchronize(c->stream);
-        c->pending = false;
-    }
-    return rc;
+    return circuit_run_lwe(c, circ, instances, in, out, nullptr);
 }
 
 int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,

@@ -1820,6 +1820,175 @@ k_circ_split(const uint64_t *__restrict__ ct_a, const uint64_t *__restrict__ ct_
     }
 }
 
+// ---- noise probe (sgfhe_lwe_noise, sgfhe_circuit_run_probe) -----------------------------------------
+// The error of LWE rows against the secret key, reduced to integer statistics per wire.  A diagnostic: the
+// key bits are on the device only for the length of the call.
+// One wave64 per row: lane l adds the words l, l + 64, ... of a whose key bit is set (coalesced 8-byte loads;
+// rows are not 16-byte aligned), the wave sums by shuffles, and every lane then holds the row's phase.  The n
+// key bits are a bit mask in LDS, loaded once per workgroup: bit l of word j is s[64 j + l], so a wave reads one
+// word per step (a broadcast) and each lane its own bit.  A workgroup of NOISE_WAVES waves covers NOISE_ROWS
+// consecutive instances of ONE wire (wave w takes instances w, w + NOISE_WAVES, ... of the tile), sums its
+// rows' statistics in LDS and issues one 64-bit atomic per statistic into the wire's record: integer sums and a
+// maximum, so the record does not depend on the launch geometry or on the order of arrival.
+// Geometry, shared by both kernels: row R = node * instances + instance of a level (sgfhe_circuit_run's
+// numbering); a launch covers the rows [row0, row0 + rows) of a call, whose LWEs are at lwe + (R - row0) *
+// row_stride + gate * gate_stride words; blockIdx.x = node_in_launch * tiles + tile, the tile's instances start
+// at inst0 + tile * NOISE_ROWS, blockIdx.y = gate; the wire's record and its row of the bit table are
+// wire0 + node_in_launch * gridDim.y + gate.  A tile never leaves its node; rows of the node outside the call
+// are skipped.  The primitive is one node of `count` instances, one gate.
+// bits: [wire][bit_words] uint64, instance t at bit t & 63 of word t / 64 (circuit_plain_bits of circuit.h).
+constexpr uint32_t NOISE_WAVES = 4, NOISE_ROWS = 16, NOISE_MASK_WORDS = 64;   // n <= 4096 (sgfhe_ctx_create)
+
+struct NoiseGeom {
+    size_t row_stride, gate_stride;   // in words of the row type
+    uint32_t wire0, node0, row0, rows, instances, inst0, tiles, bit_words, n;
+};
+
+__device__ __forceinline__ void noise_load_mask(uint64_t *smask, const uint64_t *__restrict__ keymask, uint32_t n) {
+    const uint32_t words = (n + 63) / 64;
+    if (threadIdx.x < words) smask[threadIdx.x] = keymask[threadIdx.x];
+    __syncthreads();
+}
+// local row (R - row0) of instance i of this workgroup's node, or -1 when the call does not hold it
+__device__ __forceinline__ int64_t noise_row(const NoiseGeom &G, uint32_t node, uint32_t i) {
+    if (i >= G.instances) return -1;
+    const uint64_t R = (uint64_t)(G.node0 + node) * G.instances + i;
+    return R >= G.row0 && R < (uint64_t)G.row0 + G.rows ? (int64_t)(R - G.row0) : -1;
+}
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// Rows over Z_r (r = 2^logr, Dr = r / 4): phase = b - sum a_i s_i, e = centred (phase - bit * Dr) in (-r/2, r/2].
+// stats[wire][8] = {rows, rows that decrypt wrongly ((phase + Dr/2) mod r div Dr != bit, fhe.jl:504-507), max |e|,
+// sum e (two's complement), sum e^2, rows with |e| >= Dr/4, 0, 0}.
+__global__ void __launch_bounds__(64 * NOISE_WAVES)
+k_lwe_noise(const uint64_t *__restrict__ lwe, const uint64_t *__restrict__ keymask, const uint64_t *__restrict__ bits,
+            unsigned long long *__restrict__ stats, NoiseGeom G, uint32_t logr) {
+    __shared__ uint64_t smask[NOISE_MASK_WORDS];
+    __shared__ uint64_t part[NOISE_WAVES][6];
+    noise_load_mask(smask, keymask, G.n);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t node = blockIdx.x / G.tiles, tile = blockIdx.x % G.tiles;
+    const uint32_t wire = G.wire0 + node * gridDim.y + blockIdx.y;
+    const uint64_t rmask = (1ull << logr) - 1, Dr = 1ull << (logr - 2);
+    const uint64_t *wbits = bits + (size_t)wire * G.bit_words;
+    uint64_t cnt = 0, wrong = 0, emax = 0, esum = 0, esq = 0, margin = 0;
+    for (uint32_t t = wave; t < NOISE_ROWS; t += NOISE_WAVES) {
+        const uint32_t i = G.inst0 + tile * NOISE_ROWS + t;
+        const int64_t lr = noise_row(G, node, i);   // (uniform over the wave)
+        if (lr < 0) continue;
+        const uint64_t *row = lwe + (size_t)lr * G.row_stride + (size_t)blockIdx.y * G.gate_stride;
+        uint64_t s = 0;
+#pragma unroll 4
+        for (uint32_t w = lane, j = 0; w < G.n; w += 64, j++) {
+            const uint64_t a = row[w];
+            s += (smask[j] >> lane) & 1 ? a : 0ull;
+        }
+        s = wave_sum64(s);
+        const uint64_t bit = (wbits[i >> 6] >> (i & 63)) & 1;
+        const uint64_t phase = (row[G.n] - s) & rmask;
+        const uint64_t d = (phase - bit * Dr) & rmask;
+        const int64_t e = d > (rmask >> 1) + 1 ? (int64_t)d - (int64_t)(rmask + 1) : (int64_t)d;
+        const uint64_t ae = e < 0 ? (uint64_t)(-e) : (uint64_t)e;
+        cnt++;
+        wrong += (((phase + Dr / 2) & rmask) >> (logr - 2)) != bit;
+        emax = ae > emax ? ae : emax;
+        esum += (uint64_t)e;
+        esq += ae * ae;
+        margin += ae >= Dr / 4;
+    }
+    if (lane == 0) {
+        part[wave][0] = cnt, part[wave][1] = wrong, part[wave][2] = emax;
+        part[wave][3] = esum, part[wave][4] = esq, part[wave][5] = margin;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const uint32_t k = threadIdx.x;
+        uint64_t v = part[0][k], held = part[0][0];
+        for (uint32_t w = 1; w < NOISE_WAVES; w++) {
+            v = k == 2 ? (part[w][k] > v ? part[w][k] : v) : v + part[w][k];
+            held += part[w][0];
+        }
+        unsigned long long *rec = stats + (size_t)wire * 8;
+        if (held) {   // a tile outside the call adds nothing
+            if (k == 2) atomicMax(rec + k, (unsigned long long)v);
+            else atomicAdd(rec + k, (unsigned long long)v);
+        }
+    }
+}
+
+// Rows over Z_Q ([n + 1] 16-byte canonical residues, a RAW_MODQ result): the lanes' sums stay below n Q < 2^106,
+// are added as 128-bit values and reduced mod Q once per row (mod_wide).  The codewords are 0 and 2 DQ_tilde
+// (enc_trivial(true) over Z_Q): e = centred (phase - bit * 2 DQ_tilde) in (-Q/2, Q/2].  There is no 128-bit atomic:
+// every workgroup walks its tiles in a grid-stride loop and writes one partial record
+// partial[blockIdx.x][8] = {rows, rows with |e| >= DQ_tilde, max |e| lo, hi, sum |e| lo, hi, 0, 0}; the host folds them.
+__global__ void __launch_bounds__(64 * NOISE_WAVES)
+k_lwe_noise_q(const ulonglong2 *__restrict__ lwe, const uint64_t *__restrict__ keymask,
+              const uint64_t *__restrict__ bits, unsigned long long *__restrict__ partial,
+              const CrtConst *__restrict__ CC, NoiseGeom G) {
+    __shared__ uint64_t smask[NOISE_MASK_WORDS];
+    __shared__ uint64_t part[NOISE_WAVES][6];
+    noise_load_mask(smask, keymask, G.n);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u128 Q = CC->Q, DQ = CC->DQ;
+    u128 one = 2 * DQ;
+    if (one >= Q) one -= Q;
+    uint64_t cnt = 0, wrong = 0;
+    u128 emax = 0, esum = 0;
+    for (uint32_t tile = blockIdx.x; tile < G.tiles; tile += gridDim.x)
+        for (uint32_t t = wave; t < NOISE_ROWS; t += NOISE_WAVES) {
+            const uint32_t i = G.inst0 + tile * NOISE_ROWS + t;
+            const int64_t lr = noise_row(G, 0, i);   // (uniform over the wave)
+            if (lr < 0) continue;
+            const ulonglong2 *row = lwe + (size_t)lr * G.row_stride;
+            u128 s = 0;
+#pragma unroll 4
+            for (uint32_t w = lane, j = 0; w < G.n; w += 64, j++) {
+                const ulonglong2 a = row[w];
+                if ((smask[j] >> lane) & 1) s += ((u128)a.y << 64) | a.x;
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const uint64_t lo = __shfl_xor((uint64_t)s, d, 64), hi = __shfl_xor((uint64_t)(s >> 64), d, 64);
+                s += ((u128)hi << 64) | lo;
+            }
+            s = mod_wide(s, Q, CC->invQ, nullptr);
+            const ulonglong2 bv = row[G.n];
+            const u128 b = ((u128)bv.y << 64) | bv.x;
+            const u128 phase = b >= s ? b - s : b + Q - s;
+            const bool bit = (bits[i >> 6] >> (i & 63)) & 1;
+            const u128 code = bit ? one : 0;
+            const u128 d = phase >= code ? phase - code : phase + Q - code;
+            const u128 ae = d > (Q >> 1) ? Q - d : d;
+            cnt++;
+            wrong += ae >= DQ;
+            emax = ae > emax ? ae : emax;
+            esum += ae;
+        }
+    if (lane == 0) {
+        part[wave][0] = cnt, part[wave][1] = wrong;
+        part[wave][2] = (uint64_t)emax, part[wave][3] = (uint64_t)(emax >> 64);
+        part[wave][4] = (uint64_t)esum, part[wave][5] = (uint64_t)(esum >> 64);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < NOISE_WAVES; w++) {
+            cnt += part[w][0], wrong += part[w][1];
+            const u128 m = ((u128)part[w][3] << 64) | part[w][2];
+            emax = m > emax ? m : emax;
+            esum += ((u128)part[w][5] << 64) | part[w][4];
+        }
+        unsigned long long *rec = partial + (size_t)blockIdx.x * 8;
+        rec[0] = cnt, rec[1] = wrong;
+        rec[2] = (uint64_t)emax, rec[3] = (uint64_t)(emax >> 64);
+        rec[4] = (uint64_t)esum, rec[5] = (uint64_t)(esum >> 64);
+        rec[6] = 0, rec[7] = 0;
+    }
+}
+
 // digits -> canonical accumulators (debug hook)
 __global__ void __launch_bounds__(256)
 k_dump_acc(const uint64_t *__restrict__ dig, ulonglong2 *__restrict__ out,

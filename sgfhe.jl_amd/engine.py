@@ -5,6 +5,7 @@ Device-resident entry points take raw device pointers (e.g. `torch.Tensor.data_p
 is only plumbing for device memory and torch.distributed (RCCL), never the compute path.
 """
 
+import collections
 import ctypes
 import threading
 
@@ -17,6 +18,21 @@ CIRCUIT_PACK_DIRECT = 1      # SGFHE_CIRCUIT_PACK_DIRECT
 FLAG_RAW_RNS2 = 2
 CTX_RANDOM_FLATTEN = 1          # accepted, without effect since ABI revision 6
 CTX_DETERMINISTIC_ONLY = 2
+
+
+# The records of the noise probe (sgfhe_lwe_noise, sgfhe_circuit_run_probe), all exact integers.
+# Z_r: e = centred (phase - bit Dr); wrong = rows that decrypt wrongly; margin = rows with |e| >= Dr/4.
+NoiseStats = collections.namedtuple("NoiseStats", "rows wrong max_abs sum sum_sq margin")
+# Z_Q: e = centred (phase - bit 2 DQ_tilde); wrong = rows with |e| >= DQ_tilde.
+NoiseStatsQ = collections.namedtuple("NoiseStatsQ", "rows wrong max_abs sum_abs")
+
+
+def noise_record(words, raw=False):
+    """One stats[8] record of the noise probe as a named tuple of Python ints."""
+    w = [int(x) for x in words]
+    if raw:
+        return NoiseStatsQ(w[0], w[1], w[2] | (w[3] << 64), w[4] | (w[5] << 64))
+    return NoiseStats(w[0], w[1], w[2], w[3] - (1 << 64) if w[3] >> 63 else w[3], w[4], w[5])
 
 
 class SgfheError(RuntimeError):
@@ -236,6 +252,48 @@ class Engine:
         out = np.zeros((circuit.n_outputs, a.shape[1], n + 1), dtype=np.uint64)
         self._call("sgfhe_circuit_run", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p))
         return out
+
+    def circuit_probe(self, circuit, inputs, sk, in_bits):
+        """circuit_run that also measures every wire against the secret key (sgfhe_circuit_run_probe; a
+        DIAGNOSTIC: the key crosses the boundary).  sk: n key bits; in_bits [n_inputs][instances]: the plaintext
+        bit of every input LWE.  Returns (out, stats): out as circuit_run (the same bytes), stats a list of
+        NoiseStats by wire id -- inputs, then AND, OR, XOR of every node; all-zero records for pruned nodes."""
+        n = self.params.n
+        a, ptr = _c(inputs)
+        if a.ndim != 3 or a.shape[0] != circuit.n_inputs or a.shape[2] != n + 1:
+            raise ValueError("circuit_probe: inputs must be [n_inputs=%d][instances][n+1=%d]" % (circuit.n_inputs, n + 1))
+        sk, psk = _c(sk)
+        bits, pbits = _c(in_bits, np.uint8)
+        if sk.size != n or bits.size != circuit.n_inputs * a.shape[1]:
+            raise ValueError("circuit_probe: sk holds n key bits, in_bits is [n_inputs][instances]")
+        out = np.zeros((circuit.n_outputs, a.shape[1], n + 1), dtype=np.uint64)
+        stats = np.zeros((circuit.n_inputs + 3 * circuit.n_gates, 8), dtype=np.uint64)
+        self._call("sgfhe_circuit_run_probe", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p),
+                   psk, pbits, stats.ctypes.data_as(ctypes.c_void_p))
+        return out, [noise_record(rec) for rec in stats]
+
+    def lwe_noise(self, sk, lwe, expected, raw=False, stride=None):
+        """The error of LWE rows against the secret key, reduced on the device (sgfhe_lwe_noise; a DIAGNOSTIC: the
+        key crosses the boundary; no bootstrap key is needed).  sk: n key bits; expected: one plaintext bit per row.
+        lwe: uint64 words -- rows of n + 1 (a then b) over Z_r, or with raw=True rows of [n + 1][2] residues mod Q (a
+        bootstrap_batch(raw=True) result).  stride: words from one row to the next (default: the row length);
+        3 (n + 1) with lwe = out[:, g] of a [batch][3][n + 1] result probes gate g in place -- pass the flat array
+        from the first row on.  Returns NoiseStats (NoiseStatsQ with raw=True)."""
+        n = self.params.n
+        rowlen = (n + 1) * (2 if raw else 1)
+        stride = rowlen if stride is None else int(stride)
+        exp, pexp = _c(expected, np.uint8)
+        count = exp.size
+        arr, parr = _c(lwe)
+        sk, psk = _c(sk)
+        if sk.size != n:
+            raise ValueError("lwe_noise: sk holds n key bits")
+        if count and arr.size < (count - 1) * stride + rowlen:
+            raise ValueError("lwe_noise: %d rows of stride %d need %d words, got %d"
+                             % (count, stride, (count - 1) * stride + rowlen, arr.size))
+        st = (ctypes.c_uint64 * 8)()
+        self._call("sgfhe_lwe_noise", psk, parr, count, stride, pexp, FLAG_RAW_MODQ if raw else 0, st)
+        return noise_record(st, raw)
 
     def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False, direct=False):
         """A gate circuit with RLWE ciphertexts at both ends (sgfhe_circuit_run_ct): split_ciphertext of the

@@ -19,6 +19,10 @@ Engine.bootstrap_batch on host arrays, at Params(1024), deterministic flatten.
       (A) as above against (D) the same run with SGFHE_CIRCUIT_PACK_DIRECT -- the outputs packed from the gates' LWEs
       over Z_Q, without the n refresh bootstraps per output ciphertext -- alternating on one ctx; the LWE outputs
       must be the same bytes; prints both times per round and the bootstraps each runs.
+  python tools/circuit_bench.py --probe [--configs 16x1024] [--reps 3]
+      (R) circuit_run against (P) circuit_probe -- the same run with the noise probe of every wire -- alternating on
+      one ctx (the order swaps every round); the outputs must be the same bytes; prints both times per round and
+      the worst record of the probed run.  --run-only: (R) alone, the same rounds (what an older build can run).
   python tools/circuit_bench.py --ct --trace [--configs 16x1] [--dir DIR]
       run (A) alone in a child process under `rocprofv3 --kernel-trace --stats`: the share of k_circ_split.
 
@@ -201,6 +205,66 @@ def wall_direct(args):
     eng.close()
 
 
+def wall_probe(args):
+    import sgfhe_jl_amd as S
+    import encrypted_adder
+    from sgfhe_jl_amd import circuit as C
+    params = S.Params(1024)
+    n = params.n
+    eng = S.Engine(params)
+    rng = np.random.default_rng(1)
+    sk = rng.integers(0, 2, size=n).astype(np.uint64)
+    eng.generate_key(sk, 2)
+    print("build %s, Params(1024), deterministic flatten, call rows %d" % (eng.build_id(), C.CALL_ROWS))
+    warm = encrypted_adder.adder_circuit(S, 2)
+    wi = rng.integers(0, params.r, size=(4, 64, n + 1), dtype=np.uint64)
+    eng.circuit_run(warm, wi)
+    if not args.run_only:
+        eng.circuit_probe(warm, wi, sk, np.zeros((4, 64), dtype=np.uint8))
+    for bits, inst in configs(args.configs):
+        c = encrypted_adder.adder_circuit(S, bits)
+        info = c.info()
+        gates = info["nodes"] * inst
+        # valid encryptions (uniform a, b = <a, s> + bit Dr + small e), so that the records mean something
+        plain = rng.integers(0, 2, size=(2 * bits, inst)).astype(np.uint8)
+        inputs = rng.integers(0, params.r, size=(2 * bits, inst, n + 1), dtype=np.uint64)
+        dot = (inputs[:, :, :n] * sk[None, None, :]).sum(axis=2, dtype=np.uint64)
+        e = rng.integers(-(params.Dr // 16), params.Dr // 16 + 1, size=plain.shape)
+        inputs[:, :, n] = (dot.astype(np.int64) + plain.astype(np.int64) * params.Dr + e) % params.r
+        print("\n%d-bit adder x %d instances: %d levels, %d nodes per instance, %d gates per run; the probe reads "
+              "%.1f MB of result rows and %.1f MB of inputs"
+              % (bits, inst, info["levels"], info["nodes"], gates, gates * 3 * (n + 1) * 8 / 1e6,
+                 2 * bits * inst * (n + 1) * 8 / 1e6))
+        t = {"R": [], "P": []}
+        for rep in range(args.reps):
+            res = {}
+            order = ("R",) if args.run_only else ("R", "P") if rep % 2 == 0 else ("P", "R")
+            for what in order:
+                t0 = time.perf_counter()
+                out = eng.circuit_run(c, inputs) if what == "R" else eng.circuit_probe(c, inputs, sk, plain)
+                res[what] = (time.perf_counter() - t0, out)
+                t[what].append(res[what][0])
+            if args.run_only:
+                print("  round %d: (R) circuit_run %.3f s = %.0f gates/s" % (rep, t["R"][-1], gates / t["R"][-1]))
+                continue
+            same = np.array_equal(res["R"][1], res["P"][1][0])
+            print("  round %d (%s first): (R) circuit_run %.3f s = %.0f gates/s | (P) circuit_probe %.3f s = %.0f gates/s | "
+                  "P / R %.4f | same outputs: %s"
+                  % (rep, order[0], t["R"][-1], gates / t["R"][-1], t["P"][-1], gates / t["P"][-1],
+                     t["P"][-1] / t["R"][-1], same))
+            if not same:
+                sys.exit("the outputs of the probed run differ")
+        print("  (R) mean %.3f s, spread %.3f s" % (np.mean(t["R"]), max(t["R"]) - min(t["R"])))
+        if not args.run_only:
+            print("  (P) mean %.3f s, spread %.3f s | mean P / mean R = %.4f"
+                  % (np.mean(t["P"]), max(t["P"]) - min(t["P"]), np.mean(t["P"]) / np.mean(t["R"])))
+            rep = C.noise_report(c, res["P"][1][1])
+            print("  records: %d wires, wrong rows %d, worst max |e| %d on wire %d (%s of node %s, level %d) against "
+                  "Dr/4 = %d" % (len(rep), sum(d["wrong"] for d in rep), rep[0]["max_abs"], rep[0]["wire"], rep[0]["kind"],
+                                 rep[0]["node"], rep[0]["level"], params.Dr // 4))
+    eng.close()
+
+
 def ct_only(args):
     import sgfhe_jl_amd as S
     import encrypted_adder
@@ -266,13 +330,16 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--ct", action="store_true", help="ciphertexts in and out: circuit_run_ct against the composition")
     ap.add_argument("--direct", action="store_true", help="with --ct: the refreshed run against SGFHE_CIRCUIT_PACK_DIRECT")
+    ap.add_argument("--probe", action="store_true", help="circuit_run against circuit_probe (the noise probe of every wire)")
+    ap.add_argument("--run-only", action="store_true", help="with --probe: circuit_run alone, the same rounds")
     ap.add_argument("--circuit-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--ct-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dir", default="circuit_trace", help="where rocprofv3 writes its files")
     args = ap.parse_args()
     if args.configs is None:
-        args.configs = "16x1" if args.ct or args.ct_only else "16x1024" if args.trace else "16x256,16x1024,32x256,32x1024"
-    if args.ct and not args.trace and args.reps == 1:
+        args.configs = "16x1" if args.ct or args.ct_only else "16x1024" if args.trace or args.probe else \
+            "16x256,16x1024,32x256,32x1024"
+    if (args.ct or args.probe) and not args.trace and args.reps == 1:
         args.reps = 3
     if args.circuit_only:
         circuit_only(args)
@@ -280,6 +347,8 @@ def main():
         ct_only(args)
     elif args.trace:
         trace(args)
+    elif args.probe:
+        wall_probe(args)
     elif args.ct and args.direct:
         wall_direct(args)
     elif args.ct:

@@ -449,6 +449,24 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * table and the per-call staging are kept on the ctx, grown on demand, and freed by
  * sgfhe_release_host_staging and sgfhe_ctx_destroy.  SGFHE_ERR_NO_KEY before a key is uploaded (nothing is
  * written to `out`).
+ *
+ * Lanes (sgfhe_circuit_create_lanes).  The model above is strictly SIMD: instance t of a node reads instance t of
+ * its inputs.  A plan with a LANE GROUP SIZE `group` = G >= 1 partitions the instances into consecutive groups of G
+ * -- instance t is lane t mod G of group t div G -- and gives every gate input (gate_shift [n_gates][2]) and every
+ * output reference (out_shift [n_outputs]) a signed LANE SHIFT d, |d| < G.  The value of the reference
+ * (wire w, NOT, d) at instance t is w at instance t + d where 0 <= (t mod G) + d < G, and the constant FALSE (the
+ * trivial LWE (0, 0)) elsewhere; NOT is applied afterwards as above, so a negated reference fills with TRUE.
+ * Shifts never cross a group: with G a power of two dividing n, a ciphertext of sgfhe_circuit_run_ct holds n / G
+ * independent G-bit words.  A shift costs no bootstrap -- the gather and collect kernels read another row of the
+ * same slot -- and changes nothing else: node numbering, pruning, levels, slots, rows, calls and call numbers are
+ * those of the same arrays without shifts (a shifted read names a wire of an earlier level, whose rows are all
+ * written and whose slot is held until the reading level ends).  A NULL shift array is all 0; a shift on a
+ * reference to the constant is accepted and has no effect.  Validation: everything sgfhe_circuit_create checks,
+ * group >= 1 and every |d| < group (so group = 1 admits no shift but 0); anything else is SGFHE_ERR_INVALID_ARG
+ * with *out NULL.  sgfhe_circuit_create is group = 1 with NULL shifts; sgfhe_circuit_group reports G.
+ * Every run entry point takes such a plan.  Before anything is queued or written, SGFHE_ERR_INVALID_ARG when
+ * `instances` is not a multiple of G and, in the ciphertext forms, when n is not (a group must not straddle two
+ * ciphertexts).  The probe's plaintext evaluation applies the shifts; a wire's record is over its own rows.
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -456,6 +474,11 @@ typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_CALL_ROWS 8192u
 int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates /* [n_gates][2] */, size_t n_gates,
                              const uint32_t *outputs, size_t n_outputs, sgfhe_circuit **out);
+int32_t sgfhe_circuit_create_lanes(uint32_t n_inputs, const uint32_t *gates /* [n_gates][2] */,
+                                   const int32_t *gate_shift /* [n_gates][2], NULL = all 0 */, size_t n_gates,
+                                   const uint32_t *outputs, const int32_t *out_shift /* [n_outputs], NULL = all 0 */,
+                                   size_t n_outputs, uint32_t group, sgfhe_circuit **out);
+int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
 int32_t sgfhe_circuit_run(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
@@ -497,8 +520,9 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t bloc
  * The same with flags; flags = 0 is sgfhe_circuit_run_ct, unknown bits are SGFHE_ERR_INVALID_ARG.
  *   SGFHE_CIRCUIT_PACK_DIRECT  pack the outputs that name a gate wire straight from the gate's un-reduced LWEs
  *       over Z_Q (sgfhe_pack_lwe_modq), without the n refresh bootstraps per ciphertext.
- * Ciphertext q = output * blocks + block is DIRECT when its output reference names a gate wire, negated or not,
- * and REFRESHED when it names an input wire or the constant.  The levels run with the calls, rows and call
+ * Ciphertext q = output * blocks + block is DIRECT when its output reference names a gate wire with lane shift 0,
+ * negated or not, and REFRESHED when it names an input wire or the constant, or carries a non-zero lane shift
+ * (sgfhe_circuit_create_lanes: its rows are not the gate's own rows in order).  The levels run with the calls, rows and call
  * numbers of sgfhe_circuit_run_ct, so out_lwe has the bytes of the flags = 0 run in both flatten modes; a level
  * call that produces a wire some direct output names leaves its rows un-reduced, and its scatter kernel writes
  * their ModRed (the words the reduced call gives) into the wire table and the named gate's rows into a raw

@@ -148,6 +148,8 @@ def lib():
         "sgfhe_pack_lwe_modq": (i32, [vp, vp, sz, vp, vp]),
         "sgfhe_lwe_noise": (i32, [vp, vp, vp, sz, sz, vp, u32, _u64p]),
         "sgfhe_circuit_run_probe": (i32, [vp, vp, sz, vp, vp, vp, vp, vp]),
+        "sgfhe_circuit_create_lanes": (i32, [u32, vp, vp, sz, vp, vp, sz, u32, ctypes.POINTER(vp)]),
+        "sgfhe_circuit_group": (i32, [vp, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -172,4 +174,5 @@ EXPORTED_SYMBOLS = (
     "sgfhe_host_encrypt_public", "sgfhe_host_pack_public", "sgfhe_host_normalize_public", "sgfhe_timing_enable", "sgfhe_timing_read",
     "sgfhe_kernel_names", "sgfhe_release_host_staging", "sgfhe_circuit_create", "sgfhe_circuit_info",
     "sgfhe_circuit_destroy", "sgfhe_circuit_run", "sgfhe_circuit_run_ct", "sgfhe_circuit_run_ct_ex",
-    "sgfhe_pack_lwe_modq", "sgfhe_lwe_noise", "sgfhe_circuit_run_probe")
+    "sgfhe_pack_lwe_modq", "sgfhe_lwe_noise", "sgfhe_circuit_run_probe",
+    "sgfhe_circuit_create_lanes", "sgfhe_circuit_group")

@@ -11,6 +11,12 @@ every level a wide batch: the throughput form of the engine.
     and_, or_, xor_ = c.gate(x, y)
     c.output(~and_, xor_)                         # NAND, XOR
     outs = evaluate_circuit(bkey, None, c, [[e_x0, e_x1], [e_y0, e_y1]])   # 2 instances
+
+Lanes (sgfhe_circuit_create_lanes).  Circuit(n_inputs, group=G) partitions the instances into consecutive groups
+of G lanes, and `w.lane(d)` is the reference that reads lane t + d of `w` at lane t -- FALSE where t + d leaves the
+group, before `~`.  A shift costs no bootstrap.  In the ciphertext form a ciphertext of n bits then holds n / G
+words of G bits, and gates can be wired between bits of one ciphertext: packed_adder(16) adds n / 16 pairs of 16-bit
+numbers per ciphertext pair.
 """
 
 import ctypes
@@ -26,15 +32,21 @@ CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
 
 
 class Wire:
-    """A wire reference: the wire id, plus bit 31 for its negation (`~w`)."""
+    """A wire reference: the wire id, plus bit 31 for its negation (`~w`), and a lane shift (`w.lane(d)`)."""
 
-    __slots__ = ("ref",)
+    __slots__ = ("ref", "shift")
 
-    def __init__(self, ref):
+    def __init__(self, ref, shift=0):
         self.ref = int(ref) & 0xFFFFFFFF
+        self.shift = int(shift)
 
     def __invert__(self):
-        return Wire(self.ref ^ NOT_BIT)
+        return Wire(self.ref ^ NOT_BIT, self.shift)
+
+    def lane(self, d):
+        """The reference that reads lane t + d of this one at lane t of every group (FALSE, or TRUE for a negated
+        reference, where t + d leaves the group).  Shifts add up."""
+        return Wire(self.ref, self.shift + int(d))
 
     @property
     def id(self):
@@ -45,40 +57,51 @@ class Wire:
         return bool(self.ref & NOT_BIT)
 
     def __eq__(self, other):
-        return isinstance(other, Wire) and other.ref == self.ref
+        return isinstance(other, Wire) and other.ref == self.ref and other.shift == self.shift
 
     def __hash__(self):
-        return hash(self.ref)
+        return hash((self.ref, self.shift))
 
     def __repr__(self):
-        return "%sWire(%s)" % ("~" if self.negated else "", "FALSE" if self.id == FALSE_ID else self.id)
+        return "%sWire(%s)%s" % ("~" if self.negated else "", "FALSE" if self.id == FALSE_ID else self.id,
+                                 ".lane(%+d)" % self.shift if self.shift else "")
 
 
 class Circuit:
     """Builder of a gate circuit: `n_inputs` input wires, nodes added with gate(), outputs set with
-    output().  The C plan (sgfhe_circuit_create) is made on first use and freed with the object."""
+    output().  `group`: the lane group size (instances form consecutive groups of `group` lanes; a reference may be
+    shifted by |d| < group lanes, Wire.lane).  The C plan (sgfhe_circuit_create, or sgfhe_circuit_create_lanes when
+    the group is above 1) is made on first use and freed with the object."""
 
     FALSE = Wire(FALSE_ID)
     TRUE = Wire(FALSE_ID | NOT_BIT)
 
-    def __init__(self, n_inputs):
+    def __init__(self, n_inputs, group=1):
         if not 0 <= int(n_inputs) < FALSE_ID:
             raise ValueError("n_inputs out of range")
+        if not 1 <= int(group) <= 0xFFFFFFFF:
+            raise ValueError("group out of range")
         self.n_inputs = int(n_inputs)
+        self.group = int(group)
         self.inputs = [Wire(i) for i in range(self.n_inputs)]
         self.gates = []            # [(x ref, y ref)]
         self.outputs = []          # [ref]
+        self.gate_shifts = []      # [(x lane shift, y lane shift)], beside gates
+        self.output_shifts = []    # [lane shift], beside outputs
         self._plan = None
         self._L = None
 
     def _ref(self, w):
         if not isinstance(w, Wire):
             raise TypeError("expected a Wire, got %r" % (w,))
+        if abs(w.shift) >= self.group:
+            raise ValueError("%r: a lane shift must be inside the group of %d" % (w, self.group))
         return w.ref
 
     def gate(self, x, y):
         """One node: bootstrap(x, y).  Returns its (AND, OR, XOR) wires."""
         self.gates.append((self._ref(x), self._ref(y)))
+        self.gate_shifts.append((x.shift, y.shift))
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
@@ -86,6 +109,7 @@ class Circuit:
     def output(self, *wires):
         """Set the circuit's outputs (wire references: inputs, constants and negated wires allowed)."""
         self.outputs = [self._ref(w) for w in wires]
+        self.output_shifts = [w.shift for w in wires]
         self._invalidate()
 
     @property
@@ -110,11 +134,20 @@ class Circuit:
             g = np.ascontiguousarray(np.array(self.gates, dtype=np.uint32).reshape(-1, 2))
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
             h = ctypes.c_void_p()
-            rc = L.sgfhe_circuit_create(self.n_inputs, g.ctypes.data_as(ctypes.c_void_p), len(self.gates),
-                                        o.ctypes.data_as(ctypes.c_void_p), len(self.outputs), ctypes.byref(h))
+            if self.group > 1 or any(d for pair in self.gate_shifts for d in pair) or any(self.output_shifts):
+                gs = np.ascontiguousarray(np.array(self.gate_shifts, dtype=np.int32).reshape(-1, 2))
+                os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
+                rc = L.sgfhe_circuit_create_lanes(self.n_inputs, g.ctypes.data_as(ctypes.c_void_p),
+                                                  gs.ctypes.data_as(ctypes.c_void_p), len(self.gates),
+                                                  o.ctypes.data_as(ctypes.c_void_p), os_.ctypes.data_as(ctypes.c_void_p),
+                                                  len(self.outputs), self.group, ctypes.byref(h))
+            else:
+                rc = L.sgfhe_circuit_create(self.n_inputs, g.ctypes.data_as(ctypes.c_void_p), len(self.gates),
+                                            o.ctypes.data_as(ctypes.c_void_p), len(self.outputs), ctypes.byref(h))
             if rc != 0:
                 raise SgfheError(rc, "sgfhe_circuit_create: %s" % (
-                    "malformed circuit (ids, topological order, at least one output)" if rc == -1 else "out of memory"))
+                    "malformed circuit (ids, topological order, at least one output, lane shifts inside the group)"
+                    if rc == -1 else "out of memory"))
             self._L, self._plan = L, h
         return self._plan
 
@@ -165,19 +198,56 @@ class Circuit:
         inst = bits.shape[1]
         wires = {}
 
-        def val(ref):
+        def val(ref, d):
             i = ref & ~NOT_BIT & 0xFFFFFFFF
             v = np.zeros(inst, dtype=bool) if i == FALSE_ID else (bits[i] if i < self.n_inputs else wires[i])
+            v = lane_shift(v, d, self.group)
             return ~v if ref & NOT_BIT else v
 
         for levelnodes in self.schedule():
             for g in levelnodes:
-                x, y = val(self.gates[g][0]), val(self.gates[g][1])
+                x, y = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
                 base = self.n_inputs + 3 * g
                 wires[base], wires[base + 1], wires[base + 2] = x & y, x | y, x ^ y
         if not self.outputs:
             raise ValueError("circuit has no outputs")
-        return np.stack([val(ref) for ref in self.outputs])
+        return np.stack([val(ref, d) for ref, d in zip(self.outputs, self.output_shifts)])
+
+
+def lane_shift(v, d, group):
+    """The lane-shifted read of a wire: v [instances, ...] -> the array whose entry t is v[t + d] where
+    0 <= t % group + d < group, and zero (the constant FALSE, the trivial LWE (0, 0)) elsewhere."""
+    if d == 0:
+        return v
+    if v.shape[0] % group:
+        raise ValueError("the instances (%d) must be a multiple of the lane group (%d)" % (v.shape[0], group))
+    t = np.arange(v.shape[0])
+    ok = (t % group + d >= 0) & (t % group + d < group)
+    out = np.zeros_like(v)
+    out[ok] = v[t[ok] + d]
+    return out
+
+
+def packed_adder(width):
+    """A Kogge-Stone adder over lanes: Circuit(2, group=width) whose two input wires hold words of `width` bits,
+    LSB at lane 0 of each group.  Level 1 is one node (x, y) giving generate g = AND and propagate p = XOR; each of
+    the ceil(log2(width)) prefix stages s = 1, 2, 4 ... is two levels -- the nodes (p, g.lane(-s)) and
+    (p, p.lane(-s)), then g = g OR (p AND g.lane(-s)) -- and the last node is p XOR carry.lane(-1).  Outputs: the sum
+    word, and the carry wire, whose lane width - 1 is the carry-out of the word.  1 + 3 stages nodes per instance
+    (the last stage's (p, p) node is pruned), 2 + 2 stages levels."""
+    if int(width) < 1:
+        raise ValueError("width must be at least 1")
+    c = Circuit(2, group=int(width))
+    x, y = c.inputs
+    g, _, p0 = c.gate(x, y)
+    p, s = p0, 1
+    while s < width:
+        pg = c.gate(p, g.lane(-s))[0]
+        pp = c.gate(p, p.lane(-s))[0]
+        g, p = c.gate(g, pg)[1], pp
+        s *= 2
+    c.output(c.gate(p0, g.lane(-1))[2], g)
+    return c
 
 
 def lwe_not(words, r):
@@ -199,16 +269,18 @@ def replay_levels(circuit, inputs, r, boot):
     n = row - 1
     wires = {}
 
-    def val(ref):
+    def val(ref, d):
         i = ref & ~NOT_BIT & 0xFFFFFFFF
         v = np.zeros((inst, row), dtype=np.uint64) if i == FALSE_ID else \
             (inputs[i] if i < circuit.n_inputs else wires[i])
+        v = lane_shift(v, d, circuit.group)
         return lwe_not(v, r) if ref & NOT_BIT else v
 
     call = 0
     for nodes in circuit.schedule():
-        x = np.concatenate([val(circuit.gates[g][0]) for g in nodes])    # row = rank * instances + instance
-        y = np.concatenate([val(circuit.gates[g][1]) for g in nodes])
+        # row = rank * instances + instance
+        x = np.concatenate([val(circuit.gates[g][0], circuit.gate_shifts[g][0]) for g in nodes])
+        y = np.concatenate([val(circuit.gates[g][1], circuit.gate_shifts[g][1]) for g in nodes])
         res = np.zeros((len(x), 3, row), dtype=np.uint64)
         for r0 in range(0, len(x), CALL_ROWS):
             sl = slice(r0, r0 + CALL_ROWS)
@@ -217,7 +289,8 @@ def replay_levels(circuit, inputs, r, boot):
         for k, g in enumerate(nodes):
             for w in range(3):
                 wires[circuit.n_inputs + 3 * g + w] = res[k * inst:(k + 1) * inst, w]
-    return np.stack([val(ref) for ref in circuit.outputs]) if circuit.outputs else np.zeros((0, inst, row), np.uint64)
+    return np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
+        else np.zeros((0, inst, row), np.uint64)
 
 
 def pack_calls(n):
@@ -325,7 +398,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
     [rows][3][n + 1][2] residues mod Q; the levels run through it in the row and call order of replay_levels, their
     ModRed (modred_words) being what the next level reads and what `lwe` holds.  The pack stage takes the
     ciphertexts q = output * blocks + block in ascending order, pack_calls(n) at a time: a group's refreshed
-    ciphertexts (outputs that name an input wire or the constant) are bootstrapped as one call -- trivial 1 paired
+    ciphertexts (outputs that name an input wire or the constant, or carry a lane shift) are bootstrapped as one call -- trivial 1 paired
     with every bit, row = rank among them * n + bit, AND rows kept -- and then `tail(call, lwe_q)` (lwe_q
     [count][n][n + 1][2] -> (w, v), each [count][m]) packs the group: the gate's own rows for a direct output, NOT
     over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  A checking and measuring aid."""
@@ -353,7 +426,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
 
     def is_direct(o):
         i = circuit.outputs[o] & ~NOT_BIT & 0xFFFFFFFF
-        return i != FALSE_ID and i >= circuit.n_inputs
+        return i != FALSE_ID and i >= circuit.n_inputs and circuit.output_shifts[o] == 0
 
     n_ct, cpc = circuit.n_outputs * blocks, pack_calls(n)
     w = np.zeros((n_ct, m), dtype=np.uint64)
@@ -388,6 +461,7 @@ def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False):
     cts: [n_inputs][blocks] of PackedCiphertext or Ciphertext (all of one kind); bit i of a ciphertext is
     instance i of its block.  rng as in evaluate_circuit.  direct=True: outputs that name a gate wire are packed
     from the gate's LWEs over Z_Q without the refresh bootstraps (SGFHE_CIRCUIT_PACK_DIRECT); they decrypt alike.
+    A circuit with lane groups needs n to be a multiple of its group: a ciphertext then holds n / group words.
     Returns [n_outputs][blocks] of Ciphertext."""
     p = bkey.params
     if len(cts) != circuit.n_inputs:

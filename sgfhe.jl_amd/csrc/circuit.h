@@ -1,8 +1,8 @@
 // Host-side planner of sgfhe_circuit_* (include/sgfhe_hip.h): validates a gate
 // graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
 // slot of the device wire table by liveness, and fixes the row and call numbering of a run; circuit_plain_bits
-// evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp
-// and circuit_bits_sanitized.cpp drive it under ASan / UBSan on the CPU.
+// evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp,
+// circuit_bits_sanitized.cpp and circuit_lanes_sanitized.cpp drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -27,6 +27,7 @@ constexpr uint32_t CIRC_NONE = 0xFFFFFFFFu;     // out_slot of a gate output not
 struct CircuitPlan {
     uint32_t n_inputs = 0, n_gates = 0, n_outputs = 0;
     uint32_t levels = 0, widest = 0, slots = 0;
+    uint32_t group = 1;                 // lane group size G (sgfhe_circuit_create_lanes); 1: no reference is shifted
     std::vector<uint32_t> level;        // [n_gates]: level of every node, 0 = pruned
     std::vector<uint32_t> order;        // live nodes, level by level, ascending index within a level
     std::vector<uint32_t> level_start;  // [levels + 2]: level L's nodes are order[level_start[L] .. level_start[L + 1])
@@ -36,15 +37,21 @@ struct CircuitPlan {
     std::vector<uint32_t> in_ref;       // [live][2]: the node's inputs as slot references (CIRC_NOT, CIRC_FALSE)
     std::vector<uint32_t> out_slot;     // [live][3]: slot of its AND / OR / XOR wire, CIRC_NONE if unread
     std::vector<uint32_t> out_ref;      // [n_outputs]: the circuit's outputs as slot references
+    // Lane shifts, beside in_ref / out_ref (uploaded when lanes()): the reference reads instance t + d of its slot
+    // where 0 <= t % group + d < group, the constant FALSE elsewhere; 0 on every reference to the constant
+    std::vector<int32_t> in_shift;      // [live][2]
+    std::vector<int32_t> out_shift;     // [n_outputs]
     // Host only (SGFHE_CIRCUIT_PACK_DIRECT): where an output that names a gate wire is produced
     std::vector<uint32_t> out_node;     // [n_outputs]: index in `order` of the producing node, CIRC_NONE for an input
-                                        // wire or the constant
+                                        // wire, the constant or a lane-shifted reference (those are refreshed)
     std::vector<uint32_t> out_gate;     // [n_outputs]: 0 AND, 1 OR, 2 XOR (0 where out_node is CIRC_NONE)
     // Host only (sgfhe_circuit_run_probe): the node's inputs as PROBE ROWS -- row i < n_inputs is input wire i, row
     // n_inputs + 3 k + w is wire w of the k-th live node in `order` -- with CIRC_NOT and CIRC_FALSE as in a reference
     std::vector<uint32_t> in_row;       // [live][2]
 
     size_t live() const { return order.size(); }
+    // the run takes the lane kernels (group 1 admits no shift but 0)
+    bool lanes() const { return group > 1; }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
     uint64_t level_rows(uint32_t L, uint64_t instances) const {
         return (uint64_t)(level_start[L + 1] - level_start[L]) * instances;
@@ -55,13 +62,16 @@ namespace circuit_detail {
 inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
 }  // namespace circuit_detail
 
-// Builds `P` from the arrays of sgfhe_circuit_create.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
-// malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it.
-inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
-                            size_t n_outputs, CircuitPlan &P) noexcept {
+// Builds `P` from the arrays of sgfhe_circuit_create_lanes (gate_shift / out_shift NULL: all 0).  Returns SGFHE_OK,
+// SGFHE_ERR_INVALID_ARG for a malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it.
+inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                            const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                            CircuitPlan &P) noexcept {
     using circuit_detail::wire_id;
-    // ---- validate: every size below 2^31, wire ids below the constant, inputs name earlier wires only
-    if (n_outputs < 1 || !outputs || (n_gates && !gates)) return SGFHE_ERR_INVALID_ARG;
+    // ---- validate: every size below 2^31, wire ids below the constant, inputs name earlier wires only,
+    // every shift inside the group (in 64 bits: -INT32_MIN does not exist)
+    if (n_outputs < 1 || !outputs || (n_gates && !gates) || group < 1) return SGFHE_ERR_INVALID_ARG;
+    auto shift_ok = [&](int32_t d) { return (d < 0 ? -(int64_t)d : (int64_t)d) < (int64_t)group; };
     if (n_inputs >= 0x80000000u || n_gates >= 0x80000000u || n_outputs >= 0x80000000u) return SGFHE_ERR_INVALID_ARG;
     const uint64_t n_wires = (uint64_t)n_inputs + 3 * (uint64_t)n_gates;
     if (n_wires >= CIRC_FALSE) return SGFHE_ERR_INVALID_ARG;
@@ -75,11 +85,16 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
         const uint32_t id = wire_id(outputs[o]);
         if (id != CIRC_FALSE && id >= n_wires) return SGFHE_ERR_INVALID_ARG;
     }
+    for (size_t i = 0; gate_shift && i < 2 * n_gates; i++)
+        if (!shift_ok(gate_shift[i])) return SGFHE_ERR_INVALID_ARG;
+    for (size_t o = 0; out_shift && o < n_outputs; o++)
+        if (!shift_ok(out_shift[o])) return SGFHE_ERR_INVALID_ARG;
     try {
         P = CircuitPlan();
         P.n_inputs = n_inputs;
         P.n_gates = (uint32_t)n_gates;
         P.n_outputs = (uint32_t)n_outputs;
+        P.group = group;
         const uint32_t NG = (uint32_t)n_gates;
         auto node_of = [&](uint32_t id) -> int64_t {   // producing node of a wire, -1 for inputs and the constant
             return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
@@ -173,6 +188,21 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
         }
         P.out_ref.resize(n_outputs);
         for (size_t o = 0; o < n_outputs; o++) P.out_ref[o] = slot_ref(outputs[o]);
+        // ---- lane shifts.  A shifted reference reads other ROWS of the slot it names, nothing else: the wire is of
+        // an earlier level (or an input), so all its rows are written before the reading level's first call in stream
+        // order, and its slot is held until the last level that reads the wire ends, whichever instance is read.  The
+        // slot rule above therefore needs no change.
+        auto shift_of = [&](uint32_t ref, const int32_t *tab, size_t i) -> int32_t {
+            return tab && wire_id(ref) != CIRC_FALSE ? tab[i] : 0;
+        };
+        P.in_shift.resize(2 * P.live());
+        for (size_t k = 0; k < P.live(); k++)
+            for (int j = 0; j < 2; j++) {
+                const size_t i = 2 * (size_t)P.order[k] + j;
+                P.in_shift[2 * k + j] = shift_of(gates[i], gate_shift, i);
+            }
+        P.out_shift.resize(n_outputs);
+        for (size_t o = 0; o < n_outputs; o++) P.out_shift[o] = shift_of(outputs[o], out_shift, o);
         std::vector<uint32_t> rank_of(NG, CIRC_NONE);   // node -> index in `order`
         for (size_t k = 0; k < P.live(); k++) rank_of[P.order[k]] = (uint32_t)k;
         auto row_ref = [&](uint32_t ref) -> uint32_t {
@@ -188,7 +218,7 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
         for (size_t o = 0; o < n_outputs; o++) {
             const uint32_t id = wire_id(outputs[o]);
             const int64_t g = node_of(id);
-            if (g < 0) continue;
+            if (g < 0 || P.out_shift[o] != 0) continue;
             P.out_node[o] = rank_of[g];
             P.out_gate[o] = (id - n_inputs) % 3;
         }
@@ -199,12 +229,20 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
     return SGFHE_OK;
 }
 
+// The arrays of sgfhe_circuit_create: no shifts, group 1.
+inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
+                            size_t n_outputs, CircuitPlan &P) noexcept {
+    return circuit_plan(n_inputs, gates, nullptr, n_gates, outputs, nullptr, n_outputs, 1u, P);
+}
+
 // The circuit in clear over `instances`, for the noise probe (sgfhe_circuit_run_probe): the plaintext bit of every
 // probe row -- the n_inputs input wires, then AND, OR, XOR of every live node in `order` -- as a bit table of
 // circuit_probe_rows(P) rows of circuit_bit_words(instances) uint64 words each: bit (t & 63) of word t / 64 of a row
 // is instance t (the bits past `instances` in a row's last word are unspecified).  in_bits [n_inputs][instances],
-// bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances).  SGFHE_ERR_OOM when the table
-// cannot be allocated; nothing throws out of it.
+// bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances); a lane-shifted input is first
+// laid out as a row of its own, instance by instance (instance t reads bit t + d where its lane allows, 0 elsewhere;
+// `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  SGFHE_ERR_OOM when the table cannot
+// be allocated; nothing throws out of it.
 inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * P.live(); }
 inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
 // wire id of a probe row (the inverse of CircuitPlan::in_row's numbering)
@@ -216,24 +254,45 @@ inline uint32_t circuit_probe_wire(const CircuitPlan &P, size_t row) {
 inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, size_t instances,
                                   std::vector<uint64_t> &table) noexcept {
     if (!in_bits && P.n_inputs && instances) return SGFHE_ERR_INVALID_ARG;
+    if (instances % P.group) return SGFHE_ERR_INVALID_ARG;
     const size_t wpr = circuit_bit_words(instances);
+    std::vector<uint64_t> shifted[2];
     try {
         table.assign(circuit_probe_rows(P) * wpr, 0);
+        if (P.lanes())
+            for (auto &s : shifted) s.assign(wpr, 0);
     } catch (...) {
         return SGFHE_ERR_OOM;
     }
     for (size_t i = 0; i < P.n_inputs; i++)
         for (size_t t = 0; t < instances; t++)
             table[i * wpr + t / 64] |= (uint64_t)(in_bits[i * instances + t] & 1u) << (t % 64);
-    auto word = [&](uint32_t ref, size_t w) -> uint64_t {
+    const int64_t G = P.group;
+    // the row a reference reads, before NOT: the table's own row, or that row shifted by d inside every group
+    auto source = [&](uint32_t ref, int32_t d, std::vector<uint64_t> &tmp) -> const uint64_t * {
         const uint32_t row = circuit_detail::wire_id(ref);
-        const uint64_t v = row == CIRC_FALSE ? 0ull : table[(size_t)row * wpr + w];
+        if (row == CIRC_FALSE) return nullptr;
+        const uint64_t *src = table.data() + (size_t)row * wpr;
+        if (d == 0) return src;
+        std::fill(tmp.begin(), tmp.end(), 0ull);
+        for (size_t t = 0; t < instances; t++) {
+            const int64_t lane = (int64_t)(t % (size_t)G) + d;
+            if (lane < 0 || lane >= G) continue;
+            const size_t u = (size_t)((int64_t)t + d);   // same group: 0 <= u < instances
+            tmp[t / 64] |= (src[u / 64] >> (u % 64) & 1ull) << (t % 64);
+        }
+        return tmp.data();
+    };
+    auto word = [&](const uint64_t *src, uint32_t ref, size_t w) -> uint64_t {
+        const uint64_t v = src ? src[w] : 0ull;
         return ref & CIRC_NOT ? ~v : v;
     };
     for (size_t k = 0; k < P.live(); k++) {   // `order` is a topological order: inputs are rows filled before
         uint64_t *o = table.data() + ((size_t)P.n_inputs + 3 * k) * wpr;
+        const uint32_t rx = P.in_row[2 * k], ry = P.in_row[2 * k + 1];
+        const uint64_t *sx = source(rx, P.in_shift[2 * k], shifted[0]), *sy = source(ry, P.in_shift[2 * k + 1], shifted[1]);
         for (size_t w = 0; w < wpr; w++) {
-            const uint64_t x = word(P.in_row[2 * k], w), y = word(P.in_row[2 * k + 1], w);
+            const uint64_t x = word(sx, rx, w), y = word(sy, ry, w);
             o[w] = x & y;
             o[wpr + w] = x | y;
             o[2 * wpr + w] = x ^ y;

@@ -2913,18 +2913,30 @@ int32_t sgfhe_timing_read(sgfhe_ctx *c, double *stats, int reset) {
 
 // ---- gate circuits (csrc/circuit.h plans) ---------------------------------------
 
-int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
-                             size_t n_outputs, sgfhe_circuit **out) {
+int32_t sgfhe_circuit_create_lanes(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                                   const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                                   sgfhe_circuit **out) {
     if (!out) return SGFHE_ERR_INVALID_ARG;
     *out = nullptr;
     sgfhe_circuit *c = new (std::nothrow) sgfhe_circuit();
     if (!c) return SGFHE_ERR_OOM;
-    const int32_t rc = circuit_plan(n_inputs, gates, n_gates, outputs, n_outputs, c->plan);
+    const int32_t rc = circuit_plan(n_inputs, gates, gate_shift, n_gates, outputs, out_shift, n_outputs, group, c->plan);
     if (rc) {
         delete c;
         return rc;
     }
     *out = c;
+    return SGFHE_OK;
+}
+
+int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
+                             size_t n_outputs, sgfhe_circuit **out) {
+    return sgfhe_circuit_create_lanes(n_inputs, gates, nullptr, n_gates, outputs, nullptr, n_outputs, 1u, out);
+}
+
+int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group) {
+    if (!c || !group) return SGFHE_ERR_INVALID_ARG;
+    *group = c->plan.group;
     return SGFHE_OK;
 }
 
@@ -2984,6 +2996,20 @@ struct CircuitProbe {
 // ciphertexts per pack call of sgfhe_circuit_run_ct
 static size_t circuit_pack_cpc(const sgfhe_ctx *c) { return std::max<size_t>(1, SGFHE_CIRCUIT_CALL_ROWS / c->n); }
 
+// The gather of one call (a level's, or a pack call's with the pseudo-level table): rows row0 .. row0 + rows of the
+// level whose node table is `ref`.  A plan with lane groups takes k_circ_gather_lanes with `shift` beside `ref`;
+// every other plan takes k_circ_gather as it always did.
+static void circuit_gather(const CircuitPlan &P, hipStream_t st, const uint64_t *wires, const uint32_t *ref,
+                           const int32_t *shift, uint64_t *a1, uint64_t *b1, uint64_t *a2, uint64_t *b2, uint32_t row0,
+                           uint32_t rows, uint32_t inst, uint32_t n, uint64_t r) {
+    const dim3 grid((rows * (n + 1) + 255) / 256, 2);
+    if (P.lanes())
+        hipLaunchKernelGGL(k_circ_gather_lanes, grid, dim3(256), 0, st, wires, ref, shift, a1, b1, a2, b2, row0, rows,
+                           inst, n, r, P.group);
+    else
+        hipLaunchKernelGGL(k_circ_gather, grid, dim3(256), 0, st, wires, ref, a1, b1, a2, b2, row0, rows, inst, n, r);
+}
+
 // `in` / `out`: the LWE form ([wire][instances][n + 1]); with `ct` the inputs come from ct->in_a / in_b instead and
 // `out` is optional.
 // `probe` (LWE form only): the noise records of every input wire and of every live node's three wires, taken from
@@ -3027,8 +3053,9 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         }
     }
     // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller)
-    const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() +
-                             (ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0) + jobs.size();
+    const size_t ct_tab = ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0;
+    const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() + ct_tab + jobs.size() +
+                             (P.lanes() ? P.in_shift.size() + 3 * P.out_shift.size() : 0);
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
     // (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even word offset)
@@ -3066,6 +3093,21 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     uint32_t *d_in_ref = c->circ_tab.p, *d_out_slot = d_in_ref + P.in_ref.size(), *d_out_ref = d_out_slot + P.out_slot.size();
     uint32_t *d_in_slot = d_out_ref + P.out_ref.size(), *d_pack_ref = d_in_slot + P.input_slot.size();
     uint32_t *d_jobs = d_pack_ref + 2 * P.out_ref.size();
+    // lane shifts (plans with lane groups only), beside their reference tables: in_shift, out_shift, and the pack
+    // calls' (0, shift of output o)
+    int32_t *d_in_shift = reinterpret_cast<int32_t *>(d_out_ref + P.out_ref.size() + ct_tab + jobs.size());
+    int32_t *d_out_shift = d_in_shift + P.in_shift.size(), *d_pack_shift = d_out_shift + P.out_shift.size();
+    std::vector<int32_t> pack_shift;   // (outlives the asynchronous copy: the run ends in a synchronisation)
+    if (P.lanes()) {
+        if (!P.in_shift.empty())
+            HIPCHK(c, hipMemcpyAsync(d_in_shift, P.in_shift.data(), P.in_shift.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(d_out_shift, P.out_shift.data(), P.out_shift.size() * 4, hipMemcpyHostToDevice, st));
+        if (pack) {
+            pack_shift.assign(2 * P.out_shift.size(), 0);
+            for (size_t o = 0; o < P.out_shift.size(); o++) pack_shift[2 * o + 1] = P.out_shift[o];
+            HIPCHK(c, hipMemcpyAsync(d_pack_shift, pack_shift.data(), pack_shift.size() * 4, hipMemcpyHostToDevice, st));
+        }
+    }
     if (!jobs.empty()) HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_in_ref, P.in_ref.data(), P.in_ref.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_out_slot, P.out_slot.data(), P.out_slot.size() * 4, hipMemcpyHostToDevice, st));
@@ -3130,8 +3172,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         for (uint64_t row0 = 0; row0 < rows_total; row0 += SGFHE_CIRCUIT_CALL_ROWS) {
             const uint32_t rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, rows_total - row0);
             const uint32_t tg = rows * (uint32_t)row;
-            hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires.p,
-                               d_in_ref + 2 * (size_t)k0, a1, b1, a2, b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
+            circuit_gather(P, st, c->circ_wires.p, d_in_ref + 2 * (size_t)k0, d_in_shift + 2 * (size_t)k0, a1, b1, a2, b2,
+                           (uint32_t)row0, rows, inst, (uint32_t)n, r);
             HIPCHK(c, hipGetLastError());
             // a call that produces a wire some direct output names leaves its rows un-reduced: the scatter reduces
             // what the wire table takes (the words k_final writes) and copies the named rows into the raw table
@@ -3192,10 +3234,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
             for (const Run &R : runs) {
                 const size_t off = R.rank * n;
-                const uint32_t tg = (uint32_t)(R.len * n * row);
-                hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires.p, d_pack_ref,
-                                   p1 + off * n, q1 + off, p2 + off * n, q2 + off, (uint32_t)(R.q * n), (uint32_t)(R.len * n),
-                                   inst, (uint32_t)n, r);
+                circuit_gather(P, st, c->circ_wires.p, d_pack_ref, d_pack_shift, p1 + off * n, q1 + off, p2 + off * n,
+                               q2 + off, (uint32_t)(R.q * n), (uint32_t)(R.len * n), inst, (uint32_t)n, r);
                 HIPCHK(c, hipGetLastError());
             }
             if ((rc = bootstrap_device(c, p1, q1, p2, q2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ, c->n,
@@ -3216,9 +3256,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     for (size_t q0 = 0; !direct && q0 < n_ct; q0 += cpc) {
         const size_t cnt = std::min(cpc, n_ct - q0), nb = cnt * n;
         uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
-        const uint32_t tg = (uint32_t)(nb * row);
-        hipLaunchKernelGGL(k_circ_gather, dim3((tg + 255) / 256, 2), dim3(256), 0, st, c->circ_wires.p, d_pack_ref,
-                           p1, q1, p2, q2, (uint32_t)(q0 * n), (uint32_t)nb, inst, (uint32_t)n, r);
+        circuit_gather(P, st, c->circ_wires.p, d_pack_ref, d_pack_shift, p1, q1, p2, q2, (uint32_t)(q0 * n), (uint32_t)nb,
+                       inst, (uint32_t)n, r);
         HIPCHK(c, hipGetLastError());
         if ((rc = pack_device(c, p1, q1, p2, q2, cnt, c->pack_wv.p + q0 * M, c->pack_wv.p + (n_ct + q0) * M, st))) return rc;
     }
@@ -3229,8 +3268,12 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     if (out) {
         const size_t total = (size_t)P.n_outputs * instances * row;
         const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
-        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
-                           c->circ_out.p, total, inst, (uint32_t)n, r);
+        if (P.lanes())
+            hipLaunchKernelGGL(k_circ_collect_lanes, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
+                               d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
+        else
+            hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
+                               c->circ_out.p, total, inst, (uint32_t)n, r);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(out, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
     }
@@ -3263,6 +3306,8 @@ static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t i
     // rows of a level, and words of every table, must be addressable by the kernels' indices
     if (instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
+    if (instances % P.group)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: instances must be a multiple of the circuit's lane group");
     (void)hipSetDevice(c->device);
     int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
     if (rc) return rc;
@@ -3409,6 +3454,8 @@ int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
         (out_w && (uint64_t)P.n_outputs * instances > 0xFFFFFFFFull) ||
         (uint64_t)P.n_inputs * blocks * tiles > 0x7FFFFFFFull)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: too many instances for this circuit");
+    if (c->n % P.group)   // (a group must not straddle two ciphertexts)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: n must be a multiple of the circuit's lane group");
     (void)hipSetDevice(c->device);
     int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
     if (rc) return rc;

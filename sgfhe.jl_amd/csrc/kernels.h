@@ -1678,6 +1678,20 @@ __device__ __forceinline__ uint64_t circ_word(const uint64_t *__restrict__ wires
     return ((e < n ? 0ull : r / 4) + r - v) & (r - 1);
 }
 
+// A lane-shifted reference (sgfhe_circuit_create_lanes): instances form consecutive groups of `group`, and the
+// reference reads row inst + d of its slot where the lane (inst % group) + d stays inside the group, the constant
+// FALSE elsewhere (NOT applied afterwards, so a negated reference fills with TRUE).  The lane sum is signed and 64 bits
+// wide -- d < 0 must not wrap -- and the test is uniform over a row, so a wave diverges only where it straddles rows.
+// instances is a multiple of group (checked before a run is queued): row inst + d is inside the slot.
+__device__ __forceinline__ uint64_t circ_word_lane(const uint64_t *__restrict__ wires, uint32_t ref, int32_t d,
+                                                   uint32_t group, uint32_t instances, uint32_t inst, uint32_t e,
+                                                   uint32_t n, uint64_t r) {
+    const int64_t lane = (int64_t)(inst % group) + d;
+    if (lane < 0 || lane >= (int64_t)group) ref = CIRC_REF_FALSE | (ref & CIRC_REF_NOT);
+    const size_t src = (size_t)((int64_t)inst + d);   // (not read for the constant)
+    return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + src, e, n, r);
+}
+
 // a1 / a2 [rows][n], b1 / b2 [rows] of one call: blockIdx.y selects the input (0: x, 1: y)
 __global__ void __launch_bounds__(256)
 k_circ_gather(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref, uint64_t *__restrict__ a1,
@@ -1689,6 +1703,23 @@ k_circ_gather(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ i
     const uint32_t rank = R / instances, inst = R % instances, j = blockIdx.y;
     const uint32_t ref = in_ref[2 * rank + j];
     const uint64_t v = circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    uint64_t *a = j ? a2 : a1, *b = j ? b2 : b1;
+    if (e < n) a[(size_t)lr * n + e] = v;
+    else b[lr] = v;
+}
+
+// k_circ_gather of a plan with lane groups: in_shift [nodes][2] beside in_ref.  Same thread-to-word map, so the
+// loads stay coalesced 8-byte accesses along the (shifted) source row.
+__global__ void __launch_bounds__(256)
+k_circ_gather_lanes(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref,
+                    const int32_t *__restrict__ in_shift, uint64_t *__restrict__ a1, uint64_t *__restrict__ b1,
+                    uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0, uint32_t rows,
+                    uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * (n + 1)) return;
+    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
+    const uint32_t rank = R / instances, inst = R % instances, j = blockIdx.y;
+    const uint64_t v = circ_word_lane(wires, in_ref[2 * rank + j], in_shift[2 * rank + j], group, instances, inst, e, n, r);
     uint64_t *a = j ? a2 : a1, *b = j ? b2 : b1;
     if (e < n) a[(size_t)lr * n + e] = v;
     else b[lr] = v;
@@ -1776,6 +1807,19 @@ k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ 
         const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
         const uint32_t ref = out_ref[o];
         out[t] = circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    }
+}
+
+// k_circ_collect of a plan with lane groups: out_shift [n_outputs] beside out_ref
+__global__ void __launch_bounds__(256)
+k_circ_collect_lanes(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
+                     const int32_t *__restrict__ out_shift, uint64_t *__restrict__ out, size_t total,
+                     uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+    const size_t per_out = (size_t)instances * (n + 1);
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t o = t / per_out, w = t % per_out;
+        const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
+        out[t] = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r);
     }
 }
 

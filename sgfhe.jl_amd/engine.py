@@ -244,7 +244,9 @@ class Engine:
 
     def circuit_run(self, circuit, inputs):
         """A gate circuit (circuit.Circuit) over many instances on the device (sgfhe_circuit_run):
-        inputs [n_inputs][instances][n+1] uint64 (a then b) -> outputs [n_outputs][instances][n+1]."""
+        inputs [n_inputs][instances][n+1] uint64 (a then b) -> outputs [n_outputs][instances][n+1].
+        A circuit with lane groups (Circuit(group=G)) needs instances to be a multiple of G; in the ciphertext
+        form (circuit_run_ct) n must be one, so that no group straddles two ciphertexts."""
         n = self.params.n
         a, ptr = _c(inputs)
         if a.ndim != 3 or a.shape[0] != circuit.n_inputs or a.shape[2] != n + 1:

@@ -467,9 +467,41 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * Every run entry point takes such a plan.  Before anything is queued or written, SGFHE_ERR_INVALID_ARG when
  * `instances` is not a multiple of G and, in the ciphertext forms, when n is not (a group must not straddle two
  * ciphertexts).  The probe's plaintext evaluation applies the shifts; a wire's record is over its own rows.
+ *
+ * Three-input nodes (sgfhe_circuit_create3).  gates and gate_shift are [n_gates][3].  gates[g][2] ==
+ * SGFHE_CIRCUIT_NONE makes node g the two-input node above (the shift beside it is ignored); a plan whose third
+ * references are all NONE is the sgfhe_circuit_create_lanes plan of the same arrays: info, rows, calls, output bytes,
+ * and the kernels it runs.  Any other third reference makes g a THREE-INPUT node; that reference is validated like the
+ * other two, may name the constant, carry NOT and a lane shift.  NONE anywhere else -- gates[g][0], gates[g][1],
+ * outputs, or with the NOT bit -- is SGFHE_ERR_INVALID_ARG (it is no wire id: ids are below 2^31 - 2).
+ * With X, Y, Z the three referenced LWEs at one instance (lane shift, constant fill and NOT applied as above), the
+ * node is ONE row of its level call -- pruning, levels, slots, row and call numbering and the draws are those of a
+ * two-input node -- whose bootstrap inputs are (a1, b1) = X + Y mod r and (a2, b2) = Z.  The bootstrap rotates the
+ * test polynomial by the phase of the sum of its inputs, here near s Dr, s = x + y + z in {0, 1, 2, 3}: four distinct
+ * values mod r = 4 Dr, each Dr/2 from the nearest sign change, as for two inputs.  Wires of the node:
+ *   n_inputs + 3 g + 0  MAJ         the AND row: 0, 0, 1, 1 for s = 0 .. 3
+ *   n_inputs + 3 g + 1  ONE_OR_TWO  the OR row:  0, 1, 1, 0 (not all equal)
+ *   n_inputs + 3 g + 2  XOR3        (X + Y + Z - 2 MAJ) mod r, word by word, b included, MAJ being the reduced row
+ *                                   (the words k_final gives): 0, 1, 0, 1.  NOT the bootstrap's XOR row, which means
+ *                                   nothing at s = 3.
+ * So a full adder (sum = XOR3, carry = MAJ) is one bootstrap.  With the third input FALSE the node is AND, OR, XOR;
+ * with TRUE, MAJ is OR and ONE_OR_TWO is NAND.
+ * Every run entry point takes such a plan.  Under SGFHE_CIRCUIT_PACK_DIRECT an output naming a MAJ or ONE_OR_TWO wire
+ * with shift 0 is DIRECT (NOT over Z_Q as for any gate row); an output naming an XOR3 wire is REFRESHED -- it is no
+ * gate row over Z_Q -- and out_lwe keeps the bytes of the flags = 0 run.  The probe's plaintext evaluation knows the
+ * three wires; XOR3 wires get Z_r records like any other.
+ * Noise -- a MEASURED rule, not a theorem of the scheme.  XOR3 is not bootstrapped: its error is
+ * e_X + e_Y + e_Z - 2 e_MAJ, so it carries the errors of the node's inputs on.  A node (two- or three-input) is
+ * correct while the error of the SUM of its inputs stays below Dr/2.  Three fresh encryptions (|e| <= Dr/8 each) are
+ * within that; the reference's bound for two gate outputs does not cover three, and at Params(1024) the evidence is
+ * the probe (sgfhe_circuit_run_probe) -- the one recorded figure there is a worst packed phase error of 22 against
+ * Dr/2 = 2048 (RESULTS.md).  An XOR3 wire that feeds a node counts with the sum of its own three inputs' errors:
+ * feed it together with bootstrapped wires or constants, as the carry chain of a ripple adder does (sum bits are
+ * outputs, only MAJ is carried on).
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
+#define SGFHE_CIRCUIT_NONE 0x7FFFFFFEu   /* gates[g][2] of sgfhe_circuit_create3: node g has two inputs */
 #define SGFHE_CIRCUIT_NOT 0x80000000u
 #define SGFHE_CIRCUIT_CALL_ROWS 8192u
 int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates /* [n_gates][2] */, size_t n_gates,
@@ -478,6 +510,10 @@ int32_t sgfhe_circuit_create_lanes(uint32_t n_inputs, const uint32_t *gates /* [
                                    const int32_t *gate_shift /* [n_gates][2], NULL = all 0 */, size_t n_gates,
                                    const uint32_t *outputs, const int32_t *out_shift /* [n_outputs], NULL = all 0 */,
                                    size_t n_outputs, uint32_t group, sgfhe_circuit **out);
+int32_t sgfhe_circuit_create3(uint32_t n_inputs, const uint32_t *gates /* [n_gates][3] */,
+                              const int32_t *gate_shift /* [n_gates][3], NULL = all 0 */, size_t n_gates,
+                              const uint32_t *outputs, const int32_t *out_shift /* [n_outputs], NULL = all 0 */,
+                              size_t n_outputs, uint32_t group, sgfhe_circuit **out);
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
@@ -522,7 +558,8 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t bloc
  *       over Z_Q (sgfhe_pack_lwe_modq), without the n refresh bootstraps per ciphertext.
  * Ciphertext q = output * blocks + block is DIRECT when its output reference names a gate wire with lane shift 0,
  * negated or not, and REFRESHED when it names an input wire or the constant, or carries a non-zero lane shift
- * (sgfhe_circuit_create_lanes: its rows are not the gate's own rows in order).  The levels run with the calls, rows and call
+ * (sgfhe_circuit_create_lanes: its rows are not the gate's own rows in order) or names the XOR3 wire of a three-input
+ * node (sgfhe_circuit_create3: linear over Z_r, no gate row).  The levels run with the calls, rows and call
  * numbers of sgfhe_circuit_run_ct, so out_lwe has the bytes of the flags = 0 run in both flatten modes; a level
  * call that produces a wire some direct output names leaves its rows un-reduced, and its scatter kernel writes
  * their ModRed (the words the reduced call gives) into the wire table and the named gate's rows into a raw

@@ -17,6 +17,11 @@ of G lanes, and `w.lane(d)` is the reference that reads lane t + d of `w` at lan
 group, before `~`.  A shift costs no bootstrap.  In the ciphertext form a ciphertext of n bits then holds n / G
 words of G bits, and gates can be wired between bits of one ciphertext: packed_adder(16) adds n / 16 pairs of 16-bit
 numbers per ciphertext pair.
+
+Three-input nodes (sgfhe_circuit_create3).  `gate3(x, y, z)` is ONE bootstrap, on (x + y, z): the rotation by the
+phase of the sum of three bits yields MAJ (the AND row) and "one or two true" (the OR row), and XOR3 =
+x + y + z - 2 MAJ over Z_r is linear.  `full_adder(x, y, c)` is therefore one node and ripple_adder(16) sixteen.
+XOR3 is not bootstrapped and carries its inputs' errors on: see the noise rule in include/sgfhe_hip.h.
 """
 
 import ctypes
@@ -27,6 +32,7 @@ from . import _lib
 from .scheme import LWE, RLWE, Ciphertext, EncryptedBit, PackedCiphertext, _set_flatten_mode, split_ciphertext_array
 
 FALSE_ID = 0x7FFFFFFF      # SGFHE_CIRCUIT_FALSE
+NONE_ID = 0x7FFFFFFE       # SGFHE_CIRCUIT_NONE: the third reference of a two-input node
 NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
 CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
 
@@ -70,8 +76,8 @@ class Wire:
 class Circuit:
     """Builder of a gate circuit: `n_inputs` input wires, nodes added with gate(), outputs set with
     output().  `group`: the lane group size (instances form consecutive groups of `group` lanes; a reference may be
-    shifted by |d| < group lanes, Wire.lane).  The C plan (sgfhe_circuit_create, or sgfhe_circuit_create_lanes when
-    the group is above 1) is made on first use and freed with the object."""
+    shifted by |d| < group lanes, Wire.lane).  The C plan (sgfhe_circuit_create, sgfhe_circuit_create_lanes when
+    the group is above 1, sgfhe_circuit_create3 when a gate3 exists) is made on first use and freed with the object."""
 
     FALSE = Wire(FALSE_ID)
     TRUE = Wire(FALSE_ID | NOT_BIT)
@@ -84,9 +90,9 @@ class Circuit:
         self.n_inputs = int(n_inputs)
         self.group = int(group)
         self.inputs = [Wire(i) for i in range(self.n_inputs)]
-        self.gates = []            # [(x ref, y ref)]
+        self.gates = []            # [(x ref, y ref)], or (x ref, y ref, z ref) for a three-input node
         self.outputs = []          # [ref]
-        self.gate_shifts = []      # [(x lane shift, y lane shift)], beside gates
+        self.gate_shifts = []      # [(x lane shift, y lane shift)] or (x, y, z lane shift), beside gates
         self.output_shifts = []    # [lane shift], beside outputs
         self._plan = None
         self._L = None
@@ -105,6 +111,25 @@ class Circuit:
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
+
+    def gate3(self, x, y, z):
+        """One three-input node: bootstrap(x + y, z).  Returns its (MAJ, ONE_OR_TWO, XOR3) wires: the majority, "one
+        or two of the inputs true" (not all equal), and the parity x + y + z - 2 MAJ over Z_r, which is linear and
+        carries the errors of x, y and z on."""
+        self.gates.append((self._ref(x), self._ref(y), self._ref(z)))
+        self.gate_shifts.append((x.shift, y.shift, z.shift))
+        self._invalidate()
+        base = self.n_inputs + 3 * (len(self.gates) - 1)
+        return Wire(base), Wire(base + 1), Wire(base + 2)
+
+    def full_adder(self, x, y, c):
+        """x + y + c in one bootstrap: returns (sum, carry) = (XOR3, MAJ) of gate3(x, y, c)."""
+        maj, _, xor3 = self.gate3(x, y, c)
+        return xor3, maj
+
+    @property
+    def has_gate3(self):
+        return any(len(g) == 3 for g in self.gates)
 
     def output(self, *wires):
         """Set the circuit's outputs (wire references: inputs, constants and negated wires allowed)."""
@@ -131,19 +156,26 @@ class Circuit:
         if self._plan is None:
             from .engine import SgfheError
             L = _lib.lib()
-            g = np.ascontiguousarray(np.array(self.gates, dtype=np.uint32).reshape(-1, 2))
+            vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
+            os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
             h = ctypes.c_void_p()
-            if self.group > 1 or any(d for pair in self.gate_shifts for d in pair) or any(self.output_shifts):
+            if self.has_gate3:      # two-input nodes padded with SGFHE_CIRCUIT_NONE (and a shift of 0)
+                g = np.ascontiguousarray(np.array([tuple(x) + (NONE_ID,) * (3 - len(x)) for x in self.gates],
+                                                  dtype=np.uint32).reshape(-1, 3))
+                gs = np.ascontiguousarray(np.array([tuple(x) + (0,) * (3 - len(x)) for x in self.gate_shifts],
+                                                   dtype=np.int32).reshape(-1, 3))
+                rc = L.sgfhe_circuit_create3(self.n_inputs, vp(g), vp(gs), len(self.gates), vp(o), vp(os_),
+                                             len(self.outputs), self.group, ctypes.byref(h))
+            elif self.group > 1 or any(d for pair in self.gate_shifts for d in pair) or any(self.output_shifts):
+                g = np.ascontiguousarray(np.array(self.gates, dtype=np.uint32).reshape(-1, 2))
                 gs = np.ascontiguousarray(np.array(self.gate_shifts, dtype=np.int32).reshape(-1, 2))
-                os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
-                rc = L.sgfhe_circuit_create_lanes(self.n_inputs, g.ctypes.data_as(ctypes.c_void_p),
-                                                  gs.ctypes.data_as(ctypes.c_void_p), len(self.gates),
-                                                  o.ctypes.data_as(ctypes.c_void_p), os_.ctypes.data_as(ctypes.c_void_p),
+                rc = L.sgfhe_circuit_create_lanes(self.n_inputs, vp(g), vp(gs), len(self.gates), vp(o), vp(os_),
                                                   len(self.outputs), self.group, ctypes.byref(h))
             else:
-                rc = L.sgfhe_circuit_create(self.n_inputs, g.ctypes.data_as(ctypes.c_void_p), len(self.gates),
-                                            o.ctypes.data_as(ctypes.c_void_p), len(self.outputs), ctypes.byref(h))
+                g = np.ascontiguousarray(np.array(self.gates, dtype=np.uint32).reshape(-1, 2))
+                rc = L.sgfhe_circuit_create(self.n_inputs, vp(g), len(self.gates), vp(o), len(self.outputs),
+                                            ctypes.byref(h))
             if rc != 0:
                 raise SgfheError(rc, "sgfhe_circuit_create: %s" % (
                     "malformed circuit (ids, topological order, at least one output, lane shifts inside the group)"
@@ -183,9 +215,9 @@ class Circuit:
                     if node(ref) >= 0:
                         live[node(ref)] = True
         level = [0] * len(self.gates)
-        for g, (x, y) in enumerate(self.gates):
+        for g, refs in enumerate(self.gates):
             if live[g]:
-                level[g] = 1 + max(level[node(x)] if node(x) >= 0 else 0, level[node(y)] if node(y) >= 0 else 0)
+                level[g] = 1 + max(level[node(ref)] if node(ref) >= 0 else 0 for ref in refs)
         levels = [[] for _ in range(max(level, default=0))]
         for g in range(len(self.gates)):
             if level[g]:
@@ -206,8 +238,13 @@ class Circuit:
 
         for levelnodes in self.schedule():
             for g in levelnodes:
-                x, y = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
                 base = self.n_inputs + 3 * g
+                if len(self.gates[g]) == 3:
+                    x, y, z = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
+                    wires[base], wires[base + 1], wires[base + 2] = (x & y) | (z & (x | y)), (x | y | z) & ~(x & y & z), \
+                        x ^ y ^ z
+                    continue
+                x, y = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
                 wires[base], wires[base + 1], wires[base + 2] = x & y, x | y, x ^ y
         if not self.outputs:
             raise ValueError("circuit has no outputs")
@@ -250,6 +287,23 @@ def packed_adder(width):
     return c
 
 
+def ripple_adder(width):
+    """A bit-sliced ripple-carry adder of full adders: Circuit(2 * width) whose inputs are x_0 .. x_{width-1} then
+    y_0 .. y_{width-1} (LSB first), one full_adder -- one bootstrap -- per bit, the first carry-in FALSE.  Outputs:
+    the width sum bits, then the carry-out.  width nodes in width levels.  Only MAJ is carried on; every sum bit
+    (XOR3) is an output, so no node reads a wire that was not bootstrapped or freshly encrypted."""
+    if int(width) < 1:
+        raise ValueError("width must be at least 1")
+    width = int(width)
+    c = Circuit(2 * width)
+    carry, sums = Circuit.FALSE, []
+    for i in range(width):
+        s, carry = c.full_adder(c.inputs[i], c.inputs[width + i], carry)
+        sums.append(s)
+    c.output(*(sums + [carry]))
+    return c
+
+
 def lwe_not(words, r):
     """NOT of LWEs [..., n + 1] over Z_r: enc_trivial(true) - w (a -> -a, b -> Dr - b, mod r)."""
     words = np.asarray(words, dtype=np.uint64)
@@ -262,7 +316,8 @@ def replay_levels(circuit, inputs, r, boot):
     """The circuit composed on the host from whole-level bootstrap calls, in the row and call order of
     sgfhe_circuit_run: inputs [n_inputs][instances][n + 1] -> outputs [n_outputs][instances][n + 1].
     `boot(call, a1, b1, a2, b2)` runs one call (rows of at most CALL_ROWS) and returns [rows][3][n + 1];
-    `call` counts the calls from 0.  A checking and measuring aid: the engine's circuit path does this on
+    `call` counts the calls from 0.  A three-input node is the row (x + y mod r, z); its third wire is
+    x + y + z - 2 * (row 0 of the result) mod r.  A checking and measuring aid: the engine's circuit path does this on
     the device (Engine.circuit_run)."""
     inputs = np.asarray(inputs, dtype=np.uint64)
     inst, row = inputs.shape[1], inputs.shape[2]
@@ -279,16 +334,27 @@ def replay_levels(circuit, inputs, r, boot):
     call = 0
     for nodes in circuit.schedule():
         # row = rank * instances + instance
-        x = np.concatenate([val(circuit.gates[g][0], circuit.gate_shifts[g][0]) for g in nodes])
-        y = np.concatenate([val(circuit.gates[g][1], circuit.gate_shifts[g][1]) for g in nodes])
+        mask = np.uint64(r - 1)
+
+        def first(g):   # the first bootstrap input of node g: x, or x + y mod r of a three-input node
+            x = val(circuit.gates[g][0], circuit.gate_shifts[g][0])
+            if len(circuit.gates[g]) == 3:
+                x = (x + val(circuit.gates[g][1], circuit.gate_shifts[g][1])) & mask
+            return x
+
+        x = np.concatenate([first(g) for g in nodes])
+        y = np.concatenate([val(circuit.gates[g][-1], circuit.gate_shifts[g][-1]) for g in nodes])
         res = np.zeros((len(x), 3, row), dtype=np.uint64)
         for r0 in range(0, len(x), CALL_ROWS):
             sl = slice(r0, r0 + CALL_ROWS)
             res[sl] = boot(call, x[sl, :n], x[sl, n], y[sl, :n], y[sl, n])
             call += 1
         for k, g in enumerate(nodes):
+            sl = slice(k * inst, (k + 1) * inst)
             for w in range(3):
-                wires[circuit.n_inputs + 3 * g + w] = res[k * inst:(k + 1) * inst, w]
+                wires[circuit.n_inputs + 3 * g + w] = res[sl, w]
+            if len(circuit.gates[g]) == 3:
+                wires[circuit.n_inputs + 3 * g + 2] = (x[sl] + y[sl] - np.uint64(2) * res[sl, 0]) & mask
     return np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
         else np.zeros((0, inst, row), np.uint64)
 
@@ -398,7 +464,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
     [rows][3][n + 1][2] residues mod Q; the levels run through it in the row and call order of replay_levels, their
     ModRed (modred_words) being what the next level reads and what `lwe` holds.  The pack stage takes the
     ciphertexts q = output * blocks + block in ascending order, pack_calls(n) at a time: a group's refreshed
-    ciphertexts (outputs that name an input wire or the constant, or carry a lane shift) are bootstrapped as one call -- trivial 1 paired
+    ciphertexts (outputs that name an input wire, the constant or an XOR3 wire, or carry a lane shift) are bootstrapped as one call -- trivial 1 paired
     with every bit, row = rank among them * n + bit, AND rows kept -- and then `tail(call, lwe_q)` (lwe_q
     [count][n][n + 1][2] -> (w, v), each [count][m]) packs the group: the gate's own rows for a direct output, NOT
     over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  A checking and measuring aid."""
@@ -426,7 +492,10 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
 
     def is_direct(o):
         i = circuit.outputs[o] & ~NOT_BIT & 0xFFFFFFFF
-        return i != FALSE_ID and i >= circuit.n_inputs and circuit.output_shifts[o] == 0
+        if i == FALSE_ID or i < circuit.n_inputs or circuit.output_shifts[o] != 0:
+            return False
+        g, w = divmod(i - circuit.n_inputs, 3)
+        return not (w == 2 and len(circuit.gates[g]) == 3)   # XOR3 is linear over Z_r: no gate row over Z_Q
 
     n_ct, cpc = circuit.n_outputs * blocks, pack_calls(n)
     w = np.zeros((n_ct, m), dtype=np.uint64)
@@ -519,7 +588,8 @@ def probe_circuit(bkey, key, rng, circuit, inputs, bits):
 
 
 def noise_report(circuit, stats):
-    """The records of probe_circuit by wire: a list of dicts (wire, kind: "input" / "AND" / "OR" / "XOR", node,
+    """The records of probe_circuit by wire: a list of dicts (wire, kind: "input" / "AND" / "OR" / "XOR", or "MAJ" /
+    "ONE_OR_TWO" / "XOR3" for the wires of a three-input node, node,
     level (0 for inputs), rows, wrong, max_abs, mean, rms, margin), the wires of pruned nodes left out, sorted
     by max |e| (largest first), then level."""
     level = {}
@@ -531,7 +601,8 @@ def noise_report(circuit, stats):
         if st.rows == 0:
             continue
         g = (wire - circuit.n_inputs) // 3 if wire >= circuit.n_inputs else None
-        kind = "input" if g is None else ("AND", "OR", "XOR")[(wire - circuit.n_inputs) % 3]
+        names = ("MAJ", "ONE_OR_TWO", "XOR3") if g is not None and len(circuit.gates[g]) == 3 else ("AND", "OR", "XOR")
+        kind = "input" if g is None else names[(wire - circuit.n_inputs) % 3]
         rows.append(dict(wire=wire, kind=kind, node=g, level=0 if g is None else level[g], rows=st.rows,
                          wrong=st.wrong, max_abs=st.max_abs, mean=st.sum / st.rows,
                          rms=(st.sum_sq / st.rows) ** 0.5, margin=st.margin))

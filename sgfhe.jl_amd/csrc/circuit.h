@@ -2,7 +2,8 @@
 // graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
 // slot of the device wire table by liveness, and fixes the row and call numbering of a run; circuit_plain_bits
 // evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp,
-// circuit_bits_sanitized.cpp and circuit_lanes_sanitized.cpp drive it under ASan / UBSan on the CPU.
+// circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp and circuit_gate3_sanitized.cpp drive it under ASan / UBSan
+// on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -23,6 +24,7 @@ namespace sgfhe {
 constexpr uint32_t CIRC_FALSE = SGFHE_CIRCUIT_FALSE;
 constexpr uint32_t CIRC_NOT = SGFHE_CIRCUIT_NOT;
 constexpr uint32_t CIRC_NONE = 0xFFFFFFFFu;     // out_slot of a gate output nothing reads
+constexpr uint32_t CIRC_NO_INPUT = SGFHE_CIRCUIT_NONE;   // third reference of a two-input node (never a wire id)
 
 struct CircuitPlan {
     uint32_t n_inputs = 0, n_gates = 0, n_outputs = 0;
@@ -36,14 +38,24 @@ struct CircuitPlan {
     // Device tables, one entry per live node in `order`, uploaded once per run:
     std::vector<uint32_t> in_ref;       // [live][2]: the node's inputs as slot references (CIRC_NOT, CIRC_FALSE)
     std::vector<uint32_t> out_slot;     // [live][3]: slot of its AND / OR / XOR wire, CIRC_NONE if unread
+                                        // (MAJ / ONE_OR_TWO / XOR3 of a three-input node)
     std::vector<uint32_t> out_ref;      // [n_outputs]: the circuit's outputs as slot references
     // Lane shifts, beside in_ref / out_ref (uploaded when lanes()): the reference reads instance t + d of its slot
     // where 0 <= t % group + d < group, the constant FALSE elsewhere; 0 on every reference to the constant
     std::vector<int32_t> in_shift;      // [live][2]
     std::vector<int32_t> out_shift;     // [n_outputs]
+    // Three-input nodes (sgfhe_circuit_create3), beside in_ref / in_shift / in_row and uploaded when three > 0: the
+    // third reference of every live node, CIRC_NO_INPUT for a two-input node (its shift and probe row are then 0 and
+    // CIRC_NO_INPUT)
+    uint32_t three = 0;                 // live three-input nodes
+    std::vector<uint32_t> in_ref3;      // [live]
+    std::vector<int32_t> in_shift3;     // [live]
+    std::vector<uint32_t> in_row3;      // [live]
+    std::vector<uint32_t> three_before; // [live + 1]: three-input nodes among order[0 .. k)
     // Host only (SGFHE_CIRCUIT_PACK_DIRECT): where an output that names a gate wire is produced
     std::vector<uint32_t> out_node;     // [n_outputs]: index in `order` of the producing node, CIRC_NONE for an input
-                                        // wire, the constant or a lane-shifted reference (those are refreshed)
+                                        // wire, the constant, a lane-shifted reference or the XOR3 wire of a
+                                        // three-input node, which is no gate row over Z_Q (those are refreshed)
     std::vector<uint32_t> out_gate;     // [n_outputs]: 0 AND, 1 OR, 2 XOR (0 where out_node is CIRC_NONE)
     // Host only (sgfhe_circuit_run_probe): the node's inputs as PROBE ROWS -- row i < n_inputs is input wire i, row
     // n_inputs + 3 k + w is wire w of the k-th live node in `order` -- with CIRC_NOT and CIRC_FALSE as in a reference
@@ -52,6 +64,10 @@ struct CircuitPlan {
     size_t live() const { return order.size(); }
     // the run takes the lane kernels (group 1 admits no shift but 0)
     bool lanes() const { return group > 1; }
+    // the run takes the three-reference gather and the XOR3 kernels
+    bool gate3() const { return three > 0; }
+    // live nodes order[ka .. kb] hold a three-input node
+    bool gate3_in(uint32_t ka, uint32_t kb) const { return three && three_before[kb + 1] != three_before[ka]; }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
     uint64_t level_rows(uint32_t L, uint64_t instances) const {
         return (uint64_t)(level_start[L + 1] - level_start[L]) * instances;
@@ -62,12 +78,18 @@ namespace circuit_detail {
 inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
 }  // namespace circuit_detail
 
-// Builds `P` from the arrays of sgfhe_circuit_create_lanes (gate_shift / out_shift NULL: all 0).  Returns SGFHE_OK,
-// SGFHE_ERR_INVALID_ARG for a malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it.
-inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
-                            const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
-                            CircuitPlan &P) noexcept {
+// Builds `P` from the arrays of sgfhe_circuit_create3 (`arity` 3: gates and gate_shift are [n_gates][3], and a third
+// reference CIRC_NO_INPUT makes the node a two-input node) or of sgfhe_circuit_create_lanes (`arity` 2: [n_gates][2],
+// every node a two-input node); gate_shift / out_shift NULL: all 0.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
+// malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it.
+inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                                  int arity, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
+                                  uint32_t group, CircuitPlan &P) noexcept {
     using circuit_detail::wire_id;
+    const size_t A = (size_t)arity;
+    // inputs of node g: 3 when it carries a third reference, 2 otherwise.  CIRC_NO_INPUT is above every wire id, so
+    // anywhere else -- a first or second input, an output, with NOT set -- it fails the id checks below.
+    auto fan_in = [&](size_t g) { return arity == 3 && gates[3 * g + 2] != CIRC_NO_INPUT ? 3 : 2; };
     // ---- validate: every size below 2^31, wire ids below the constant, inputs name earlier wires only,
     // every shift inside the group (in 64 bits: -INT32_MIN does not exist)
     if (n_outputs < 1 || !outputs || (n_gates && !gates) || group < 1) return SGFHE_ERR_INVALID_ARG;
@@ -76,8 +98,8 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
     const uint64_t n_wires = (uint64_t)n_inputs + 3 * (uint64_t)n_gates;
     if (n_wires >= CIRC_FALSE) return SGFHE_ERR_INVALID_ARG;
     for (size_t g = 0; g < n_gates; g++)
-        for (int j = 0; j < 2; j++) {
-            const uint32_t id = wire_id(gates[2 * g + j]);
+        for (int j = 0, nj = fan_in(g); j < nj; j++) {
+            const uint32_t id = wire_id(gates[A * g + j]);
             if (id == CIRC_FALSE || id < n_inputs) continue;
             if (id >= n_wires || (id - n_inputs) / 3 >= g) return SGFHE_ERR_INVALID_ARG;   // own or later node
         }
@@ -85,8 +107,9 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         const uint32_t id = wire_id(outputs[o]);
         if (id != CIRC_FALSE && id >= n_wires) return SGFHE_ERR_INVALID_ARG;
     }
-    for (size_t i = 0; gate_shift && i < 2 * n_gates; i++)
-        if (!shift_ok(gate_shift[i])) return SGFHE_ERR_INVALID_ARG;
+    for (size_t g = 0; gate_shift && g < n_gates; g++)   // (the shift beside CIRC_NO_INPUT is ignored)
+        for (int j = 0, nj = fan_in(g); j < nj; j++)
+            if (!shift_ok(gate_shift[A * g + j])) return SGFHE_ERR_INVALID_ARG;
     for (size_t o = 0; out_shift && o < n_outputs; o++)
         if (!shift_ok(out_shift[o])) return SGFHE_ERR_INVALID_ARG;
     try {
@@ -107,8 +130,8 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         }
         for (uint32_t g = NG; g-- > 0;) {
             if (!live[g]) continue;
-            for (int j = 0; j < 2; j++) {
-                const int64_t h = node_of(wire_id(gates[2 * g + j]));
+            for (int j = 0, nj = fan_in(g); j < nj; j++) {
+                const int64_t h = node_of(wire_id(gates[A * g + j]));
                 if (h >= 0) live[h] = 1;
             }
         }
@@ -117,8 +140,8 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         for (uint32_t g = 0; g < NG; g++) {
             if (!live[g]) continue;
             uint32_t L = 0;
-            for (int j = 0; j < 2; j++) {
-                const int64_t h = node_of(wire_id(gates[2 * g + j]));
+            for (int j = 0, nj = fan_in(g); j < nj; j++) {
+                const int64_t h = node_of(wire_id(gates[A * g + j]));
                 if (h >= 0) L = std::max(L, P.level[h]);
             }
             P.level[g] = L + 1;
@@ -143,8 +166,8 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         constexpr uint32_t UNREAD = 0;   // no wire is read at level 0
         std::vector<uint32_t> last_read((size_t)n_wires, UNREAD);
         for (uint32_t g : P.order)
-            for (int j = 0; j < 2; j++) {
-                const uint32_t id = wire_id(gates[2 * g + j]);
+            for (int j = 0, nj = fan_in(g); j < nj; j++) {
+                const uint32_t id = wire_id(gates[A * g + j]);
                 if (id != CIRC_FALSE) last_read[id] = std::max(last_read[id], P.level[g]);
             }
         for (size_t o = 0; o < n_outputs; o++) {
@@ -183,7 +206,7 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         P.out_slot.resize(3 * P.live());
         for (size_t k = 0; k < P.live(); k++) {
             const uint32_t g = P.order[k];
-            for (int j = 0; j < 2; j++) P.in_ref[2 * k + j] = slot_ref(gates[2 * g + j]);
+            for (int j = 0; j < 2; j++) P.in_ref[2 * k + j] = slot_ref(gates[A * g + j]);
             for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
         }
         P.out_ref.resize(n_outputs);
@@ -198,7 +221,7 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         P.in_shift.resize(2 * P.live());
         for (size_t k = 0; k < P.live(); k++)
             for (int j = 0; j < 2; j++) {
-                const size_t i = 2 * (size_t)P.order[k] + j;
+                const size_t i = A * (size_t)P.order[k] + j;
                 P.in_shift[2 * k + j] = shift_of(gates[i], gate_shift, i);
             }
         P.out_shift.resize(n_outputs);
@@ -212,13 +235,30 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         };
         P.in_row.resize(2 * P.live());
         for (size_t k = 0; k < P.live(); k++)
-            for (int j = 0; j < 2; j++) P.in_row[2 * k + j] = row_ref(gates[2 * P.order[k] + j]);
+            for (int j = 0; j < 2; j++) P.in_row[2 * k + j] = row_ref(gates[A * P.order[k] + j]);
+        // ---- three-input nodes: the third reference in tables of their own, so that in_ref, in_shift and in_row keep
+        // the layout the two-input kernels read
+        P.in_ref3.assign(P.live(), CIRC_NO_INPUT);
+        P.in_shift3.assign(P.live(), 0);
+        P.in_row3.assign(P.live(), CIRC_NO_INPUT);
+        P.three_before.assign(P.live() + 1, 0);
+        for (size_t k = 0; k < P.live(); k++) {
+            const size_t g = P.order[k];
+            if (fan_in(g) == 3) {
+                P.in_ref3[k] = slot_ref(gates[3 * g + 2]);
+                P.in_shift3[k] = shift_of(gates[3 * g + 2], gate_shift, 3 * g + 2);
+                P.in_row3[k] = row_ref(gates[3 * g + 2]);
+                P.three++;
+            }
+            P.three_before[k + 1] = P.three;
+        }
         P.out_node.assign(n_outputs, CIRC_NONE);
         P.out_gate.assign(n_outputs, 0);
         for (size_t o = 0; o < n_outputs; o++) {
             const uint32_t id = wire_id(outputs[o]);
             const int64_t g = node_of(id);
             if (g < 0 || P.out_shift[o] != 0) continue;
+            if ((id - n_inputs) % 3 == 2 && fan_in((size_t)g) == 3) continue;   // XOR3: linear over Z_r, no gate row
             P.out_node[o] = rank_of[g];
             P.out_gate[o] = (id - n_inputs) % 3;
         }
@@ -227,6 +267,20 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int3
         return SGFHE_ERR_OOM;
     }
     return SGFHE_OK;
+}
+
+// The arrays of sgfhe_circuit_create_lanes.
+inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                            const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                            CircuitPlan &P) noexcept {
+    return circuit_plan_arity(n_inputs, gates, gate_shift, n_gates, 2, outputs, out_shift, n_outputs, group, P);
+}
+
+// The arrays of sgfhe_circuit_create3.
+inline int32_t circuit_plan3(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                             const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                             CircuitPlan &P) noexcept {
+    return circuit_plan_arity(n_inputs, gates, gate_shift, n_gates, 3, outputs, out_shift, n_outputs, group, P);
 }
 
 // The arrays of sgfhe_circuit_create: no shifts, group 1.
@@ -241,8 +295,9 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
 // is instance t (the bits past `instances` in a row's last word are unspecified).  in_bits [n_inputs][instances],
 // bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances); a lane-shifted input is first
 // laid out as a row of its own, instance by instance (instance t reads bit t + d where its lane allows, 0 elsewhere;
-// `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  SGFHE_ERR_OOM when the table cannot
-// be allocated; nothing throws out of it.
+// `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  A three-input node's rows are MAJ,
+// ONE_OR_TWO (one or two of its inputs true) and XOR3.  SGFHE_ERR_OOM when the table cannot be allocated; nothing
+// throws out of it.
 inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * P.live(); }
 inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
 // wire id of a probe row (the inverse of CircuitPlan::in_row's numbering)
@@ -256,7 +311,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
     if (!in_bits && P.n_inputs && instances) return SGFHE_ERR_INVALID_ARG;
     if (instances % P.group) return SGFHE_ERR_INVALID_ARG;
     const size_t wpr = circuit_bit_words(instances);
-    std::vector<uint64_t> shifted[2];
+    std::vector<uint64_t> shifted[3];
     try {
         table.assign(circuit_probe_rows(P) * wpr, 0);
         if (P.lanes())
@@ -291,6 +346,17 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
         uint64_t *o = table.data() + ((size_t)P.n_inputs + 3 * k) * wpr;
         const uint32_t rx = P.in_row[2 * k], ry = P.in_row[2 * k + 1];
         const uint64_t *sx = source(rx, P.in_shift[2 * k], shifted[0]), *sy = source(ry, P.in_shift[2 * k + 1], shifted[1]);
+        const uint32_t rz = P.in_row3[k];
+        if (rz != CIRC_NO_INPUT) {
+            const uint64_t *sz = source(rz, P.in_shift3[k], shifted[2]);
+            for (size_t w = 0; w < wpr; w++) {
+                const uint64_t x = word(sx, rx, w), y = word(sy, ry, w), z = word(sz, rz, w);
+                o[w] = (x & y) | (z & (x | y));
+                o[wpr + w] = (x | y | z) & ~(x & y & z);
+                o[2 * wpr + w] = x ^ y ^ z;
+            }
+            continue;
+        }
         for (size_t w = 0; w < wpr; w++) {
             const uint64_t x = word(sx, rx, w), y = word(sy, ry, w);
             o[w] = x & y;

@@ -2913,20 +2913,34 @@ int32_t sgfhe_timing_read(sgfhe_ctx *c, double *stats, int reset) {
 
 // ---- gate circuits (csrc/circuit.h plans) ---------------------------------------
 
-int32_t sgfhe_circuit_create_lanes(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
-                                   const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
-                                   sgfhe_circuit **out) {
+// gates / gate_shift [n_gates][arity]: 2 for sgfhe_circuit_create_lanes, 3 for sgfhe_circuit_create3
+static int32_t circuit_create(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                              int arity, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
+                              uint32_t group, sgfhe_circuit **out) {
     if (!out) return SGFHE_ERR_INVALID_ARG;
     *out = nullptr;
     sgfhe_circuit *c = new (std::nothrow) sgfhe_circuit();
     if (!c) return SGFHE_ERR_OOM;
-    const int32_t rc = circuit_plan(n_inputs, gates, gate_shift, n_gates, outputs, out_shift, n_outputs, group, c->plan);
+    const int32_t rc = circuit_plan_arity(n_inputs, gates, gate_shift, n_gates, arity, outputs, out_shift, n_outputs,
+                                          group, c->plan);
     if (rc) {
         delete c;
         return rc;
     }
     *out = c;
     return SGFHE_OK;
+}
+
+int32_t sgfhe_circuit_create_lanes(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                                   const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                                   sgfhe_circuit **out) {
+    return circuit_create(n_inputs, gates, gate_shift, n_gates, 2, outputs, out_shift, n_outputs, group, out);
+}
+
+int32_t sgfhe_circuit_create3(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                              const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                              sgfhe_circuit **out) {
+    return circuit_create(n_inputs, gates, gate_shift, n_gates, 3, outputs, out_shift, n_outputs, group, out);
 }
 
 int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
@@ -2998,12 +3012,21 @@ static size_t circuit_pack_cpc(const sgfhe_ctx *c) { return std::max<size_t>(1, 
 
 // The gather of one call (a level's, or a pack call's with the pseudo-level table): rows row0 .. row0 + rows of the
 // level whose node table is `ref`.  A plan with lane groups takes k_circ_gather_lanes with `shift` beside `ref`;
-// every other plan takes k_circ_gather as it always did.
+// every other plan takes k_circ_gather as it always did.  The levels of a plan with three-input nodes pass the third
+// references `ref3` / `shift3` and take k_circ_gather3 (the pack calls of such a plan pass none: their pseudo-level
+// has two-input nodes only).
 static void circuit_gather(const CircuitPlan &P, hipStream_t st, const uint64_t *wires, const uint32_t *ref,
                            const int32_t *shift, uint64_t *a1, uint64_t *b1, uint64_t *a2, uint64_t *b2, uint32_t row0,
-                           uint32_t rows, uint32_t inst, uint32_t n, uint64_t r) {
+                           uint32_t rows, uint32_t inst, uint32_t n, uint64_t r, const uint32_t *ref3 = nullptr,
+                           const int32_t *shift3 = nullptr) {
     const dim3 grid((rows * (n + 1) + 255) / 256, 2);
-    if (P.lanes())
+    if (ref3 && P.lanes())
+        hipLaunchKernelGGL(k_circ_gather3<true>, grid, dim3(256), 0, st, wires, ref, shift, ref3, shift3, a1, b1, a2, b2,
+                           row0, rows, inst, n, r, P.group);
+    else if (ref3)
+        hipLaunchKernelGGL(k_circ_gather3<false>, grid, dim3(256), 0, st, wires, ref, (const int32_t *)nullptr, ref3,
+                           (const int32_t *)nullptr, a1, b1, a2, b2, row0, rows, inst, n, r, 1u);
+    else if (P.lanes())
         hipLaunchKernelGGL(k_circ_gather_lanes, grid, dim3(256), 0, st, wires, ref, shift, a1, b1, a2, b2, row0, rows,
                            inst, n, r, P.group);
     else
@@ -3055,7 +3078,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller)
     const size_t ct_tab = ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0;
     const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() + ct_tab + jobs.size() +
-                             (P.lanes() ? P.in_shift.size() + 3 * P.out_shift.size() : 0);
+                             (P.lanes() ? P.in_shift.size() + 3 * P.out_shift.size() : 0) +
+                             (P.gate3() ? 2 * P.in_ref3.size() : 0);
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
     // (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even word offset)
@@ -3097,6 +3121,16 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     // calls' (0, shift of output o)
     int32_t *d_in_shift = reinterpret_cast<int32_t *>(d_out_ref + P.out_ref.size() + ct_tab + jobs.size());
     int32_t *d_out_shift = d_in_shift + P.in_shift.size(), *d_pack_shift = d_out_shift + P.out_shift.size();
+    // third references (plans with three-input nodes only), past everything above: in_ref3, in_shift3
+    uint32_t *d_in_ref3 = nullptr;
+    int32_t *d_in_shift3 = nullptr;
+    if (P.gate3()) {
+        d_in_ref3 = c->circ_tab.p + tab_words - 2 * P.in_ref3.size();
+        d_in_shift3 = reinterpret_cast<int32_t *>(d_in_ref3 + P.in_ref3.size());
+        HIPCHK(c, hipMemcpyAsync(d_in_ref3, P.in_ref3.data(), P.in_ref3.size() * 4, hipMemcpyHostToDevice, st));
+        if (P.lanes())
+            HIPCHK(c, hipMemcpyAsync(d_in_shift3, P.in_shift3.data(), P.in_shift3.size() * 4, hipMemcpyHostToDevice, st));
+    }
     std::vector<int32_t> pack_shift;   // (outlives the asynchronous copy: the run ends in a synchronisation)
     if (P.lanes()) {
         if (!P.in_shift.empty())
@@ -3173,13 +3207,16 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             const uint32_t rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, rows_total - row0);
             const uint32_t tg = rows * (uint32_t)row;
             circuit_gather(P, st, c->circ_wires.p, d_in_ref + 2 * (size_t)k0, d_in_shift + 2 * (size_t)k0, a1, b1, a2, b2,
-                           (uint32_t)row0, rows, inst, (uint32_t)n, r);
+                           (uint32_t)row0, rows, inst, (uint32_t)n, r, P.gate3() ? d_in_ref3 + k0 : nullptr,
+                           P.gate3() ? d_in_shift3 + k0 : nullptr);
             HIPCHK(c, hipGetLastError());
             // a call that produces a wire some direct output names leaves its rows un-reduced: the scatter reduces
             // what the wire table takes (the words k_final writes) and copies the named rows into the raw table
             const uint32_t ka = k0 + (uint32_t)(row0 / inst), kb = k0 + (uint32_t)((row0 + rows - 1) / inst);
             const size_t j0 = std::lower_bound(job_k.begin(), job_k.end(), ka) - job_k.begin();
             const size_t j1 = std::upper_bound(job_k.begin(), job_k.end(), kb) - job_k.begin();
+            // a call that holds a three-input node: its XOR3 rows, from the staging the bootstrap consumed
+            const bool xor3 = P.gate3_in(ka, kb);
             if (j1 > j0) {
                 if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, SGFHE_FLAG_RAW_MODQ, c->n, nullptr, st))) return rc;
                 for (size_t j = j0; j < j1;) {   // (a grid holds 65535 rows of workgroups)
@@ -3191,10 +3228,22 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
                     HIPCHK(c, hipGetLastError());
                     j += nj;
                 }
+                if (xor3) {   // (after the scatter: over the XOR row's words in the wire table)
+                    hipLaunchKernelGGL(k_circ_xor3_raw, dim3(rows), dim3(256), 0, st,
+                                       reinterpret_cast<const ulonglong2 *>(res), d_in_ref3 + k0,
+                                       d_out_slot + 3 * (size_t)k0, c->circ_wires.p, a1, b1, a2, b2, cur(c).d_crt,
+                                       (uint32_t)row0, inst, (uint32_t)n, r);
+                    HIPCHK(c, hipGetLastError());
+                }
                 continue;
             }
             // the k-loop of sgfhe_bootstrap_batch_device: the next call number of the ctx's draw stream
             if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, 0u, c->n, nullptr, st))) return rc;
+            if (xor3) {   // (before the scatter and the probe read the result rows)
+                hipLaunchKernelGGL(k_circ_xor3, dim3((tg + 255) / 256), dim3(256), 0, st, res, d_in_ref3 + k0, a1, b1, a2,
+                                   b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
+                HIPCHK(c, hipGetLastError());
+            }
             hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, res,
                                d_out_slot + 3 * (size_t)k0, c->circ_wires.p, (uint32_t)row0, rows, inst, (uint32_t)n);
             HIPCHK(c, hipGetLastError());

@@ -1725,6 +1725,82 @@ k_circ_gather_lanes(const uint64_t *__restrict__ wires, const uint32_t *__restri
     else b[lr] = v;
 }
 
+// ---- three-input nodes (sgfhe_circuit_create3) --------------------------------------------------------------------
+// A node with a third reference Z is bootstrapped on (X + Y mod r, Z): the rotation is by the phase of the sum of three
+// bits, its AND row is MAJ(X, Y, Z), its OR row "one or two true", and XOR3 = X + Y + Z - 2 MAJ over Z_r needs no
+// bootstrap.  in_ref3 / in_shift3 [nodes] beside in_ref / in_shift; CIRC_REF_NO_INPUT marks a two-input node.
+constexpr uint32_t CIRC_REF_NO_INPUT = 0x7FFFFFFEu;
+
+// k_circ_gather / k_circ_gather_lanes (LANES: the plan has lane groups, and the shift tables exist) of a plan with
+// three-input nodes: blockIdx.y = 0 writes a1 = X + Y mod r (X for a two-input node), blockIdx.y = 1 writes a2 = Z (Y).
+// Same thread-to-word map: every load is a coalesced 8-byte access along a source row, the node decode is uniform over
+// a row, and r is a power of two, so the sum is reduced with one mask.
+template <bool LANES>
+__global__ void __launch_bounds__(256)
+k_circ_gather3(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref,
+               const int32_t *__restrict__ in_shift, const uint32_t *__restrict__ in_ref3,
+               const int32_t *__restrict__ in_shift3, uint64_t *__restrict__ a1, uint64_t *__restrict__ b1,
+               uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0, uint32_t rows, uint32_t instances,
+               uint32_t n, uint64_t r, uint32_t group) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * (n + 1)) return;
+    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
+    const uint32_t rank = R / instances, inst = R % instances, j = blockIdx.y;
+    auto read = [&](uint32_t ref, const int32_t *shift, uint32_t i) -> uint64_t {
+        if (LANES) return circ_word_lane(wires, ref, shift[i], group, instances, inst, e, n, r);
+        return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    };
+    const uint32_t ref3 = in_ref3[rank];
+    uint64_t v;
+    if (ref3 == CIRC_REF_NO_INPUT) v = read(in_ref[2 * rank + j], in_shift, 2 * rank + j);
+    else if (j) v = read(ref3, in_shift3, rank);
+    else v = (read(in_ref[2 * rank], in_shift, 2 * rank) + read(in_ref[2 * rank + 1], in_shift, 2 * rank + 1)) & (r - 1);
+    uint64_t *a = j ? a2 : a1, *b = j ? b2 : b1;
+    if (e < n) a[(size_t)lr * n + e] = v;
+    else b[lr] = v;
+}
+
+// XOR3 of the three-input nodes of a call, after its k-loop and before anything reads its result rows
+// [rows][3][n + 1]: row 2 = a1 + a2 - 2 row 0 mod r, word by word, b included -- a1 + a2 is X + Y + Z as the bootstrap
+// consumed it (the staging is not written between the gather and here), row 0 the reduced MAJ.  The rows of two-input
+// nodes are left alone.  One thread per word, as the gather.
+__global__ void __launch_bounds__(256)
+k_circ_xor3(uint64_t *__restrict__ res, const uint32_t *__restrict__ in_ref3, const uint64_t *__restrict__ a1,
+            const uint64_t *__restrict__ b1, const uint64_t *__restrict__ a2, const uint64_t *__restrict__ b2,
+            uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * (n + 1)) return;
+    const uint32_t lr = t / (n + 1), e = t % (n + 1);
+    if (in_ref3[(row0 + lr) / instances] == CIRC_REF_NO_INPUT) return;
+    const uint64_t s = e < n ? a1[(size_t)lr * n + e] + a2[(size_t)lr * n + e] : b1[lr] + b2[lr];
+    uint64_t *o = res + (size_t)lr * 3 * (n + 1) + e;
+    o[2 * (size_t)(n + 1)] = (s - 2 * o[0]) & (r - 1);
+}
+
+// The same after k_circ_scatter_raw, for a call whose rows stay un-reduced (16-byte residues over Z_Q): the XOR3 words
+// over Z_r go straight into the wire's slot, over the ModRed of the meaningless XOR row the scatter put there, with
+// row 0 reduced by the device function of k_final -- the words the reduced call gives.  The raw rows are not touched
+// (an output naming an XOR3 wire is refreshed, never direct).  One workgroup per row, as k_circ_scatter_raw.
+__global__ void __launch_bounds__(256)
+k_circ_xor3_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__ in_ref3,
+                const uint32_t *__restrict__ out_slot, uint64_t *__restrict__ wires, const uint64_t *__restrict__ a1,
+                const uint64_t *__restrict__ b1, const uint64_t *__restrict__ a2, const uint64_t *__restrict__ b2,
+                const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint64_t r) {
+    const uint32_t lr = blockIdx.x, R = row0 + lr;
+    const uint32_t rank = R / instances, inst = R % instances;   // (uniform over the workgroup)
+    if (in_ref3[rank] == CIRC_REF_NO_INPUT) return;
+    const uint32_t slot = out_slot[3 * rank + 2];
+    if (slot == CIRC_SLOT_NONE) return;
+    const size_t stride = n + 1;
+    const ulonglong2 *src = res + (size_t)lr * 3 * stride;
+    uint64_t *dst = wires + ((size_t)slot * instances + inst) * stride;
+    for (uint32_t e = threadIdx.x; e <= n; e += 256) {
+        const ulonglong2 v = src[e];
+        const uint64_t s = e < n ? a1[(size_t)lr * n + e] + a2[(size_t)lr * n + e] : b1[lr] + b2[lr];
+        dst[e] = (s - 2 * modred(((u128)v.y << 64) | v.x, CC)) & (r - 1);
+    }
+}
+
 // bootstrap output [rows][3][n + 1] -> the slots of the gate outputs something reads
 __global__ void __launch_bounds__(256)
 k_circ_scatter(const uint64_t *__restrict__ res, const uint32_t *__restrict__ out_slot, uint64_t *__restrict__ wires,

@@ -23,6 +23,12 @@ Engine.bootstrap_batch on host arrays, at Params(1024), deterministic flatten.
       (R) circuit_run against (P) circuit_probe -- the same run with the noise probe of every wire -- alternating on
       one ctx (the order swaps every round); the outputs must be the same bytes; prints both times per round and
       the worst record of the probed run.  --run-only: (R) alone, the same rounds (what an older build can run).
+  python tools/circuit_bench.py --gate3 [--configs 16x1024] [--reps 3]
+      (T) the adder of 3 two-input nodes per bit against (F) ripple_adder -- one three-input node, one bootstrap, per
+      bit (sgfhe_circuit_create3) -- alternating on one ctx (the order swaps every round), on valid encryptions; both
+      must decrypt to the integer sums; prints both times per round and the bootstraps each runs.  Then, in a run of
+      its own, the noise probe of (F): the worst max |e| per wire kind and the largest error of the sum of a node's
+      three inputs.
   python tools/circuit_bench.py --ct --trace [--configs 16x1] [--dir DIR]
       run (A) alone in a child process under `rocprofv3 --kernel-trace --stats`: the share of k_circ_split.
 
@@ -265,6 +271,83 @@ def wall_probe(args):
     eng.close()
 
 
+def wall_gate3(args):
+    import sgfhe_jl_amd as S
+    import encrypted_adder
+    from sgfhe_jl_amd import circuit as C
+    params = S.Params(1024)
+    n, r, Dr = params.n, params.r, params.Dr
+    eng = S.Engine(params)
+    rng = np.random.default_rng(1)
+    sk = rng.integers(0, 2, size=n).astype(np.uint64)
+    eng.generate_key(sk, 2)
+    print("build %s, Params(1024), deterministic flatten, call rows %d" % (eng.build_id(), C.CALL_ROWS))
+    wi = rng.integers(0, r, size=(4, 64, n + 1), dtype=np.uint64)
+    for warm in (encrypted_adder.adder_circuit(S, 2), C.ripple_adder(2)):
+        eng.circuit_run(warm, wi)
+    eng.circuit_probe(C.ripple_adder(2), wi, sk, np.zeros((4, 64), dtype=np.uint8))
+
+    def phase_error(lwe, bits):   # centred error of LWEs [..., n + 1] that encrypt the integers `bits` (times Dr)
+        ph = lwe[..., n] - (lwe[..., :n] * sk).sum(axis=-1, dtype=np.uint64)
+        e = (ph.astype(np.int64) - bits.astype(np.int64) * Dr) % r
+        return np.where(e > r // 2, e - r, e)
+
+    for bits, inst in configs(args.configs):
+        circ = {"T": encrypted_adder.adder_circuit(S, bits), "F": C.ripple_adder(bits)}
+        info = {k: c.info() for k, c in circ.items()}
+        boots = {k: info[k]["nodes"] * inst for k in circ}
+        # valid encryptions (uniform a, b = <a, s> + bit Dr + e, |e| <= Dr/16), so that the sums decrypt
+        xs, ys = rng.integers(0, 1 << bits, size=inst), rng.integers(0, 1 << bits, size=inst)
+        plain = np.array([(xs >> i) & 1 for i in range(bits)] + [(ys >> i) & 1 for i in range(bits)], dtype=np.uint8)
+        inputs = rng.integers(0, r, size=(2 * bits, inst, n + 1), dtype=np.uint64)
+        dot = (inputs[:, :, :n] * sk[None, None, :]).sum(axis=2, dtype=np.uint64)
+        e = rng.integers(-(Dr // 16), Dr // 16 + 1, size=plain.shape)
+        inputs[:, :, n] = (dot.astype(np.int64) + plain.astype(np.int64) * Dr + e) % r
+        print("\n%d-bit adder x %d instances: (T) two-input nodes: %d levels, %d nodes per instance, %d bootstraps | "
+              "(F) full adders: %d levels, %d nodes per instance, %d bootstraps | F / T by bootstrap counts %.4f"
+              % (bits, inst, info["T"]["levels"], info["T"]["nodes"], boots["T"], info["F"]["levels"], info["F"]["nodes"],
+                 boots["F"], boots["F"] / boots["T"]))
+        t = {"T": [], "F": []}
+        for rep in range(args.reps):
+            order = ("T", "F") if rep % 2 == 0 else ("F", "T")
+            for what in order:
+                t0 = time.perf_counter()
+                out = eng.circuit_run(circ[what], inputs)
+                t[what].append(time.perf_counter() - t0)
+                dec = ((phase_error(out, np.zeros(out.shape[:2], np.int64)) + Dr // 2) % r) // Dr
+                if not np.array_equal((dec << np.arange(bits + 1)[:, None]).sum(axis=0), xs + ys):
+                    sys.exit("(%s) does not decrypt to the sums" % what)
+            print("  round %d (%s first): (T) %.3f s = %.0f bootstraps/s | (F) %.3f s = %.0f bootstraps/s | F / T %.4f | "
+                  "both decrypt to x + y" % (rep, order[0], t["T"][-1], boots["T"] / t["T"][-1], t["F"][-1],
+                                             boots["F"] / t["F"][-1], t["F"][-1] / t["T"][-1]))
+        print("  (T) mean %.3f s, spread %.3f s | (F) mean %.3f s, spread %.3f s | mean F / mean T = %.4f, by bootstrap "
+              "counts %.4f" % (np.mean(t["T"]), max(t["T"]) - min(t["T"]), np.mean(t["F"]), max(t["F"]) - min(t["F"]),
+                               np.mean(t["F"]) / np.mean(t["T"]), boots["F"] / boots["T"]))
+        # the probe of (F), a run of its own; its outputs are every sum bit and every carry, so that the error of the
+        # sum of each node's inputs can be taken on the host from the LWEs the node read
+        f = C.ripple_adder(bits)
+        carries = [C.Wire(f.n_inputs + 3 * g) for g in range(bits)]
+        f.output(*([C.Wire(f.n_inputs + 3 * g + 2) for g in range(bits)] + carries))
+        out, stats = eng.circuit_probe(f, inputs, sk, plain)
+        recs = C.noise_report(f, stats)
+        print("  probe of (F): %d wires, wrong rows %d; against Dr/4 = %d and Dr/2 = %d:"
+              % (len(recs), sum(d["wrong"] for d in recs), Dr // 4, Dr // 2))
+        for kind in ("input", "MAJ", "ONE_OR_TWO", "XOR3"):
+            worst = max((d for d in recs if d["kind"] == kind), key=lambda d: d["max_abs"])
+            print("    %-10s worst max |e| %5d (wire %d, level %d), rms there %.1f"
+                  % (kind, worst["max_abs"], worst["wire"], worst["level"], worst["rms"]))
+        carry_bits = np.zeros(inst, dtype=np.int64)
+        carry_lwe = np.zeros((inst, n + 1), dtype=np.uint64)
+        worst_sum = 0
+        for g in range(bits):
+            total = (inputs[g] + inputs[bits + g] + carry_lwe) & np.uint64(r - 1)
+            s = plain[g].astype(np.int64) + plain[bits + g] + carry_bits
+            worst_sum = max(worst_sum, int(np.abs(phase_error(total, s)).max()))
+            carry_bits, carry_lwe = s >> 1, out[bits + g]
+        print("    largest error of the sum of a node's three inputs: %d against Dr/2 = %d" % (worst_sum, Dr // 2))
+    eng.close()
+
+
 def ct_only(args):
     import sgfhe_jl_amd as S
     import encrypted_adder
@@ -331,15 +414,16 @@ def main():
     ap.add_argument("--ct", action="store_true", help="ciphertexts in and out: circuit_run_ct against the composition")
     ap.add_argument("--direct", action="store_true", help="with --ct: the refreshed run against SGFHE_CIRCUIT_PACK_DIRECT")
     ap.add_argument("--probe", action="store_true", help="circuit_run against circuit_probe (the noise probe of every wire)")
+    ap.add_argument("--gate3", action="store_true", help="the adder of two-input nodes against ripple_adder (full adders)")
     ap.add_argument("--run-only", action="store_true", help="with --probe: circuit_run alone, the same rounds")
     ap.add_argument("--circuit-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--ct-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dir", default="circuit_trace", help="where rocprofv3 writes its files")
     args = ap.parse_args()
     if args.configs is None:
-        args.configs = "16x1" if args.ct or args.ct_only else "16x1024" if args.trace or args.probe else \
+        args.configs = "16x1" if args.ct or args.ct_only else "16x1024" if args.trace or args.probe or args.gate3 else \
             "16x256,16x1024,32x256,32x1024"
-    if (args.ct or args.probe) and not args.trace and args.reps == 1:
+    if (args.ct or args.probe or args.gate3) and not args.trace and args.reps == 1:
         args.reps = 3
     if args.circuit_only:
         circuit_only(args)
@@ -347,6 +431,8 @@ def main():
         ct_only(args)
     elif args.trace:
         trace(args)
+    elif args.gate3:
+        wall_gate3(args)
     elif args.probe:
         wall_probe(args)
     elif args.ct and args.direct:

@@ -487,13 +487,18 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * So a full adder (sum = XOR3, carry = MAJ) is one bootstrap.  With the third input FALSE the node is AND, OR, XOR;
  * with TRUE, MAJ is OR and ONE_OR_TWO is NAND.
  * Every run entry point takes such a plan.  Under SGFHE_CIRCUIT_PACK_DIRECT an output naming a MAJ or ONE_OR_TWO wire
- * with shift 0 is DIRECT (NOT over Z_Q as for any gate row); an output naming an XOR3 wire is REFRESHED -- it is no
- * gate row over Z_Q -- and out_lwe keeps the bytes of the flags = 0 run.  The probe's plaintext evaluation knows the
+ * with shift 0 is DIRECT (NOT over Z_Q as for any gate row); an output naming an XOR3 wire is REFRESHED (LIFTED under
+ * SGFHE_CIRCUIT_PACK_LIFT) -- it is no gate row over Z_Q -- and out_lwe keeps the bytes of the flags = 0 run.  The probe's plaintext evaluation knows the
  * three wires; XOR3 wires get Z_r records like any other.
  * Noise -- a MEASURED rule, not a theorem of the scheme.  XOR3 is not bootstrapped: its error is
  * e_X + e_Y + e_Z - 2 e_MAJ, so it carries the errors of the node's inputs on.  A node (two- or three-input) is
- * correct while the error of the SUM of its inputs stays below Dr/2.  Three fresh encryptions (|e| <= Dr/8 each) are
- * within that; the reference's bound for two gate outputs does not cover three, and at Params(1024) the evidence is
+ * correct while the error of the SUM of its inputs stays below Dr/2.  A fresh encryption that was SPLIT
+ * (sgfhe_host_encrypt_private, then split_ciphertext) has an LWE error of up to Dr/4 - 1, not the Dr/8 of its draws:
+ * encrypt_private rounds b -- with zero draws the error is already Dr/8 - 1 -- and the measured worst over a few
+ * thousand bits is 63 of Dr = 256 at Params(64), 123 of 512 at Params(128), 1006 of 4096 at Params(1024): 0.24 Dr.
+ * Three of those can reach 0.75 Dr, past Dr/2: a node fed by three such encryptions is not covered by a bound, only
+ * by the measured distribution;
+ * the reference's bound for two gate outputs does not cover three either, and at Params(1024) the evidence is
  * the probe (sgfhe_circuit_run_probe) -- the one recorded figure there is a worst packed phase error of 22 against
  * Dr/2 = 2048 (RESULTS.md).  An XOR3 wire that feeds a node counts with the sum of its own three inputs' errors:
  * feed it together with bootstrapped wires or constants, as the carry chain of a ripple adder does (sum bits are
@@ -577,11 +582,50 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t bloc
  * sgfhe_bootstrap_batch(SGFHE_FLAG_RAW_MODQ) followed by one sgfhe_pack_lwe_modq.  No host synchronisation
  * before the final download.
  * With out_w NULL the flag changes nothing; blocks = 0 does nothing.
+ *   SGFHE_CIRCUIT_PACK_LIFT  pack EVERY output without a refresh bootstrap.  It refines SGFHE_CIRCUIT_PACK_DIRECT and
+ *       is given TOGETHER with it (flags = SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT = 3); bit 1 on its own
+ *       was an unknown bit before this flag existed and stays SGFHE_ERR_INVALID_ARG, as do bit 2 and above.  A
+ *       ciphertext that is DIRECT above stays DIRECT (its raw gate rows are better than its reduced ones), and every
+ *       other ciphertext -- an input wire, the constant, an XOR3 wire, any lane-shifted reference -- is LIFTED instead
+ *       of REFRESHED.
+ * A LIFTED ciphertext takes its n rows from the wire table as the pack stage's gather reads them (NOT, constant fill
+ * and lane shift applied over Z_r), and one kernel per run of consecutive lifted ciphertexts of a group writes
+ * sgfhe_lwe_lift_modq of every word into their rows of the raw output table.  Pack stage: the groups of
+ * SGFHE_CIRCUIT_PACK_DIRECT, each being ONE tail and nothing else -- no bootstrap runs in the pack stage, and the pack
+ * buffers hold no refresh rows.  Randomised flatten: the level calls as in sgfhe_circuit_run_ct, then exactly one call
+ * number per group, the tail's, with z = the ciphertext's index within its group; a group equals one
+ * sgfhe_pack_lwe_modq on the draw stream.  out_lwe keeps the bytes of the flags = 0 run in both modes; the wire table
+ * is not touched.  With out_w NULL the flag changes nothing.  For ripple_adder(16) at Params(1024), one block: 16 n
+ * level bootstraps, and 17 n refresh bootstraps with flags = 0, 16 n with PACK_DIRECT (only the carry-out is a gate
+ * row), none with PACK_LIFT.
+ * Noise -- why this is a flag of its own.  A lifted ciphertext is not bootstrapped.  Its bit error is the wire's Z_r
+ * error plus the tail's.  For an XOR3 wire that is e_X + e_Y + e_Z - 2 e_MAJ.  The lift scales an error e over Z_r to
+ * e Q / r over Z_Q (plus at most 1/2 per word of rounding) and cleans nothing, so the packed bit decrypts only while
+ * the wire's own error plus the tail's stays below Dr/2.  Measure it with sgfhe_lwe_noise(SGFHE_FLAG_RAW_MODQ) on
+ * sgfhe_lwe_lift_modq's output, or with the packed phase error after packing.  Measured on the CPU oracles,
+ * ripple_adder(3) at Params(64): with inputs of error |e| <= Dr/16 the worst packed phase error of a sum bit is 39
+ * and of the carry 6, against Dr/2 = 128; with split fresh encryptions (error up to Dr/4 - 1 each, see the noise
+ * rule of three-input nodes above) the sum bits still decrypt but sit at 86 - 108 of 128.  So the flag is meant for inputs
+ * that are themselves packed outputs (error about 22 of 2048 at Params(1024), RESULTS.md), or wherever the probe shows
+ * room -- not for sums of freshly encrypted bits.  ripple_adder(16) at Params(1024) on inputs of |e| <= Dr/16: worst
+ * packed phase error of a sum bit 538 lifted against 26 refreshed, of 2048 (RESULTS.md).
  */
 #define SGFHE_CIRCUIT_PACK_DIRECT 1u
+#define SGFHE_CIRCUIT_PACK_LIFT 2u
 int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, const uint64_t *in_a,
                                 const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
                                 uint32_t flags);
+
+/*
+ * The lift of LWEs from Z_r to Z_Q by exact scaling: out = L(word), L(x) = floor((x Q + r/2) / r), word by word, a and
+ * b alike.  L maps a wrap of r to a wrap of Q, the codeword Dr to Q/4 (2 DQ_tilde to within 1) and adds at most 1/2
+ * per word of rounding; ModRed of L(x) is x.  It does not clean the error (see SGFHE_CIRCUIT_PACK_LIFT).
+ *   lwe [count][n + 1] uint64 in [0, r), a then b; out [count][n + 1][2] canonical 16-byte residues {lo, hi} -- the
+ *   input layout of sgfhe_pack_lwe_modq and of sgfhe_lwe_noise(SGFHE_FLAG_RAW_MODQ).
+ * Host pointers, synchronous, on the ctx stream; no bootstrap key is needed and the draw stream is not touched.
+ * count = 0 does nothing.  A word that is not below r is SGFHE_ERR_INVALID_ARG before anything is queued.
+ */
+int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *ctx, const uint64_t *lwe, size_t count, uint64_t *out);
 
 /*
  * Noise probe: the LWE error of rows against the SECRET key, reduced on the device to exact integer statistics.

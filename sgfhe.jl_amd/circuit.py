@@ -441,6 +441,19 @@ def modred_words(x, Q, r):
     return q & np.uint64(r - 1)                                                    # utils.jl:86-88
 
 
+def lift_words(x, Q, r):
+    """The lift of words of Z_r to residues of Z_Q by exact scaling (sgfhe_lwe_lift_modq, k_circ_lift): x [...] uint64
+    in [0, r), r a power of two up to 2^15, Q < 2^94 -> floor((x Q + r/2) / r) as [..., 2] uint64 {lo, hi}.  It maps a
+    wrap of r to a wrap of Q and Dr to Q/4, and modred_words of it is x; the error of an LWE is carried on."""
+    x = np.asarray(x, dtype=np.uint64)
+    logr = np.uint64(r.bit_length() - 1)
+    Ql, Qh = _const128(Q)
+    t0, t1 = x * (Ql & np.uint64(0xFFFFFFFF)), x * (Ql >> np.uint64(32))           # x < 2^15: below 2^47 each
+    pl, ph = _add128(t0, x * Qh, t1 << np.uint64(32), t1 >> np.uint64(32))         # x Q < 2^109
+    pl, ph = _add128(pl, ph, np.uint64(r // 2), np.uint64(0))
+    return np.stack([(pl >> logr) | (ph << (np.uint64(64) - logr)), ph >> logr], axis=-1)
+
+
 def lwe_not_modq(x, Q, DQ_tilde):
     """NOT of un-reduced LWEs [..., n + 1][2] over Z_Q: enc_trivial(true) - w with true = (0, 2 DQ_tilde):
     a -> -a, b -> 2 DQ_tilde - b, mod Q."""
@@ -458,7 +471,7 @@ def lwe_not_modq(x, Q, DQ_tilde):
     return out
 
 
-def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
+def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False):
     """sgfhe_circuit_run_ct_ex with SGFHE_CIRCUIT_PACK_DIRECT composed on the host: a, b [n_inputs][blocks][N] ->
     ((w, v), lwe) as replay_ct.  `boot_raw(call, a1, b1, a2, b2)` runs one call un-reduced and returns
     [rows][3][n + 1][2] residues mod Q; the levels run through it in the row and call order of replay_levels, their
@@ -467,7 +480,9 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
     ciphertexts (outputs that name an input wire, the constant or an XOR3 wire, or carry a lane shift) are bootstrapped as one call -- trivial 1 paired
     with every bit, row = rank among them * n + bit, AND rows kept -- and then `tail(call, lwe_q)` (lwe_q
     [count][n][n + 1][2] -> (w, v), each [count][m]) packs the group: the gate's own rows for a direct output, NOT
-    over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  A checking and measuring aid."""
+    over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  lift=True (SGFHE_CIRCUIT_PACK_LIFT): the
+    ciphertexts that are not direct take lift_words of their `lwe` rows instead -- no `boot_raw` call in the pack stage,
+    one call number per group.  A checking and measuring aid."""
     n, m, r, Q = params.n, params.m, params.r, params.Q
     a = np.asarray(a, dtype=np.uint64)
     b = np.asarray(b, dtype=np.uint64)
@@ -504,7 +519,10 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
         qs = range(q0, min(q0 + cpc, n_ct))
         group = np.zeros((len(qs), n, n + 1, 2), dtype=np.uint64)
         fresh = [q for q in qs if not is_direct(q // blocks)]
-        if fresh:
+        if lift:
+            for q in fresh:
+                group[q - q0] = lift_words(lwe[q // blocks, (q % blocks) * n:(q % blocks + 1) * n], Q, r)
+        elif fresh:
             y = np.concatenate([lwe[q // blocks, (q % blocks) * n:(q % blocks + 1) * n] for q in fresh])
             one = np.zeros_like(y)
             one[:, n] = r // 4
@@ -524,12 +542,15 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail):
     return (w.reshape(shape), v.reshape(shape)), lwe
 
 
-def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False):
+def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False, lift=False):
     """The circuit on RLWE ciphertexts, the reference's user flow (encrypt -> split_ciphertext -> gates ->
     pack_encrypted_bits -> decrypt) with the split and the pack on the device (Engine.circuit_run_ct).
     cts: [n_inputs][blocks] of PackedCiphertext or Ciphertext (all of one kind); bit i of a ciphertext is
     instance i of its block.  rng as in evaluate_circuit.  direct=True: outputs that name a gate wire are packed
     from the gate's LWEs over Z_Q without the refresh bootstraps (SGFHE_CIRCUIT_PACK_DIRECT); they decrypt alike.
+    lift=True: that, and every other output is lifted from Z_r instead of refreshed (SGFHE_CIRCUIT_PACK_LIFT): no
+    bootstrap in the pack stage, but such an output carries its wire's error on -- meant for inputs that are themselves
+    packed outputs, not for sums of freshly encrypted bits (the noise rule in include/sgfhe_hip.h).
     A circuit with lane groups needs n to be a multiple of its group: a ciphertext then holds n / group words.
     Returns [n_outputs][blocks] of Ciphertext."""
     p = bkey.params
@@ -551,7 +572,7 @@ def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False):
         raise ValueError("evaluate_circuit_ct: ciphertext polynomials of length %d expected" % N)
     with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
         _set_flatten_mode(bkey, rng)
-        w, v = bkey.engine.circuit_run_ct(circuit, a, b, direct=direct)
+        w, v = bkey.engine.circuit_run_ct(circuit, a, b, direct=direct, lift=lift)
     return [[Ciphertext(p, RLWE(w[o, t], v[o, t])) for t in range(blocks)] for o in range(circuit.n_outputs)]
 
 

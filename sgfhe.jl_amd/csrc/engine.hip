@@ -2632,6 +2632,41 @@ int32_t sgfhe_pack_lwe_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uin
     return rc;
 }
 
+int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uint64_t *out) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    if (count == 0) return SGFHE_OK;
+    if (!lwe || !out) return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_lift_modq: NULL row or output pointer");
+    const size_t row = c->n + 1;
+    if (count > ((size_t)1 << 40) / row)   // (the byte counts below stay far inside 64 bits)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_lift_modq: too many rows");
+    const size_t words = count * row;
+    for (size_t i = 0; i < words; i++)
+        if (lwe[i] >= c->par.r)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_lift_modq: word " + std::to_string(i) + " is not below r");
+    (void)hipSetDevice(c->device);
+    SGFHE_QUIESCE(c);
+    // (the pack path's buffers: its LWE staging takes the rows, its un-reduced rows the residues)
+    int32_t rc;
+    if ((rc = circ_grow(c, c->pack_lwe, words))) return rc;
+    if ((rc = circ_grow(c, c->pack_raw, words))) return rc;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = hipMemcpyAsync(c->pack_lwe.p, lwe, words * 8, hipMemcpyHostToDevice, c->stream))) break;
+        const size_t blocks = std::min<size_t>((words + 255) / 256, (size_t)1 << 20);
+        hipLaunchKernelGGL(k_lwe_lift, dim3((uint32_t)blocks), dim3(256), 0, c->stream, c->pack_lwe.p, c->pack_raw.p,
+                           cur(c).d_crt, words);
+        if ((e = hipGetLastError())) break;
+        if ((e = hipMemcpyAsync(out, c->pack_raw.p, words * 16, hipMemcpyDeviceToHost, c->stream))) break;
+        e = hipStreamSynchronize(c->stream);
+    } while (0);
+    if (e != hipSuccess) {
+        rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
+        (void)hipStreamSynchronize(c->stream);   // whatever was queued finishes before the buffers are touched again
+    }
+    return rc;
+}
+
 int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const uint32_t *in,
                         uint32_t *out) {
     if (!c || !in || !out || prime_index >= cur(c).npr) return SGFHE_ERR_INVALID_ARG;
@@ -2974,6 +3009,7 @@ struct CircuitCt {
     size_t blocks, N;
     uint64_t *out_w, *out_v;       // [n_outputs][blocks][m], or both NULL
     bool direct;                   // SGFHE_CIRCUIT_PACK_DIRECT
+    bool lift;                     // SGFHE_CIRCUIT_PACK_LIFT (with direct): what is not direct is lifted, not refreshed
 };
 
 // ---- noise probe: LWE error statistics against the secret key, on the device -------------
@@ -3055,6 +3091,9 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire, by producing node (ascending index in `order`,
     // so the jobs of one level call are a run of the table): job = {output, rank of the node in its level,
     // gate | CIRC_NOT}; and the most refreshed ciphertexts any pack group has
+    // SGFHE_CIRCUIT_PACK_LIFT: the same direct outputs; every other ciphertext is lifted from the wire table into the
+    // raw table (k_circ_lift), so no group has a refreshed one
+    const bool lift = pack && ct->direct && ct->lift;
     const bool direct = pack && ct->direct;
     std::vector<uint32_t> jobs, job_k;   // (outlive the asynchronous copy: the run ends in a synchronisation)
     size_t max_ref = cpc;
@@ -3069,7 +3108,7 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             jobs.insert(jobs.end(), {o, k - P.level_start[L], P.out_gate[o] | (P.out_ref[o] & CIRC_NOT)});
         }
         max_ref = 0;
-        for (size_t q0 = 0; q0 < n_ct; q0 += cpc) {
+        for (size_t q0 = 0; !lift && q0 < n_ct; q0 += cpc) {
             size_t nref = 0;
             for (size_t q = q0; q < std::min(q0 + cpc, n_ct); q++) nref += P.out_node[q / ct->blocks] == CIRC_NONE;
             max_ref = std::max(max_ref, nref);
@@ -3267,9 +3306,11 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     // SGFHE_CIRCUIT_PACK_DIRECT: a group's refreshed ciphertexts (outputs that name an input wire or the constant)
     // are bootstrapped as one call, row = rank among them * n + bit, and their AND rows join the direct ones in the
     // raw table; then one tail over the group's rows of that table, a call of its own
+    // SGFHE_CIRCUIT_PACK_LIFT: those ciphertexts are lifted instead -- one k_circ_lift per run of consecutive ones,
+    // from the wire table straight into their rows of the raw table -- and the group is its tail alone
     for (size_t q0 = 0; direct && q0 < n_ct; q0 += cpc) {
         const size_t cnt = std::min(cpc, n_ct - q0);
-        struct Run { size_t q, rank, len; };   // consecutive refreshed ciphertexts: one gather, one copy
+        struct Run { size_t q, rank, len; };   // consecutive refreshed (lifted) ciphertexts: one gather, one copy
         std::vector<Run> runs;
         size_t nref = 0;
         for (size_t q = q0; q < q0 + cnt; q++) {
@@ -3278,7 +3319,20 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             else runs.push_back({q, nref, 1});
             nref++;
         }
-        if (nref) {
+        for (size_t i = 0; lift && i < runs.size(); i++) {
+            const Run &R = runs[i];
+            const uint32_t rows = (uint32_t)(R.len * n);
+            const dim3 grid((rows * (uint32_t)row + 255) / 256);
+            if (P.lanes())
+                hipLaunchKernelGGL(k_circ_lift<true>, grid, dim3(256), 0, st, c->circ_wires.p, d_pack_ref, d_pack_shift,
+                                   c->circ_raw.p, cur(c).d_crt, (uint32_t)(R.q * n), rows, inst, (uint32_t)n, r, P.group);
+            else
+                hipLaunchKernelGGL(k_circ_lift<false>, grid, dim3(256), 0, st, c->circ_wires.p, d_pack_ref,
+                                   (const int32_t *)nullptr, c->circ_raw.p, cur(c).d_crt, (uint32_t)(R.q * n), rows, inst,
+                                   (uint32_t)n, r, 1u);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (nref && !lift) {
             const size_t nb = nref * n;
             uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
             for (const Run &R : runs) {
@@ -3482,8 +3536,9 @@ int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
                                 uint32_t flags) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    if (flags & ~SGFHE_CIRCUIT_PACK_DIRECT)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct_ex: unknown flag bits");
+    // (bit 1 without bit 0 was an unknown bit before SGFHE_CIRCUIT_PACK_LIFT existed, and stays refused)
+    if ((flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || flags == SGFHE_CIRCUIT_PACK_LIFT)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct_ex: unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
     if (!circ || ((!in_a || !in_b) && circ->plan.n_inputs))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: NULL circuit or input pointer");
     if (!out_w != !out_v || (!out_w && !out_lwe))
@@ -3508,7 +3563,8 @@ int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
     (void)hipSetDevice(c->device);
     int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
     if (rc) return rc;
-    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0};
+    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
+                          (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
     rc = circuit_run_queued(c, P, (size_t)instances, nullptr, out_lwe, &ct);
     if (rc) {   // whatever was queued finishes before the buffers can be touched again
         (void)hipStreamSynchronize(c->stream);

@@ -1780,7 +1780,7 @@ k_circ_xor3(uint64_t *__restrict__ res, const uint32_t *__restrict__ in_ref3, co
 // The same after k_circ_scatter_raw, for a call whose rows stay un-reduced (16-byte residues over Z_Q): the XOR3 words
 // over Z_r go straight into the wire's slot, over the ModRed of the meaningless XOR row the scatter put there, with
 // row 0 reduced by the device function of k_final -- the words the reduced call gives.  The raw rows are not touched
-// (an output naming an XOR3 wire is refreshed, never direct).  One workgroup per row, as k_circ_scatter_raw.
+// (an output naming an XOR3 wire is refreshed or lifted, never direct).  One workgroup per row, as k_circ_scatter_raw.
 __global__ void __launch_bounds__(256)
 k_circ_xor3_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__ in_ref3,
                 const uint32_t *__restrict__ out_slot, uint64_t *__restrict__ wires, const uint64_t *__restrict__ a1,
@@ -1870,6 +1870,45 @@ k_circ_raw_and(const ulonglong2 *__restrict__ res, ulonglong2 *__restrict__ dst,
     const ulonglong2 *src = res + (size_t)blockIdx.x * 3 * stride;
     ulonglong2 *d = dst + (size_t)blockIdx.x * stride;
     for (uint32_t e = threadIdx.x; e <= n; e += 256) d[e] = src[e];
+}
+
+// ---- lift to Z_Q (sgfhe_lwe_lift_modq, SGFHE_CIRCUIT_PACK_LIFT) ----------------------------------------------------
+// L(x) = floor((x Q + r/2) / r), r = 2^logr: the exact scaling of a word of Z_r to a canonical residue of Z_Q.  It
+// maps a wrap of r to a wrap of Q and the codeword Dr to Q/4 (2 DQ_tilde to within 1), and adds at most 1/2 of
+// rounding per word; the error of the LWE is carried on, scaled, not cleaned.  x < r <= 2^15 and Q < 2^94: the
+// product is below 2^109, and the result below Q because x <= r - 1.
+__device__ __forceinline__ ulonglong2 lift_word(uint64_t x, const CrtConst *CC) {
+    const u128 y = ((u128)x * CC->Q + (1ull << (CC->logr - 1))) >> CC->logr;
+    return make_ulonglong2((uint64_t)y, (uint64_t)(y >> 64));
+}
+
+// The lifted ciphertexts of a pack group (SGFHE_CIRCUIT_PACK_LIFT): rows row0 .. row0 + rows of the pack stage's
+// pseudo-level, whose node o is (TRUE, output o) -- row R = q n + bit is output R / instances at instance R % instances
+// -- read from the wire table as that level's gather reads its second input (pack_ref / pack_shift [n_outputs][2]; NOT,
+// the constant and, with LANES, the lane shift applied over Z_r), lifted word by word into row R of the raw output
+// table [q][n][n + 1].  Thread-to-word map of the gathers: coalesced 8-byte loads along a source row, 16-byte stores
+// (raw rows are 16-byte aligned), the row decode uniform over a row.
+template <bool LANES>
+__global__ void __launch_bounds__(256)
+k_circ_lift(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ pack_ref,
+            const int32_t *__restrict__ pack_shift, ulonglong2 *__restrict__ rawout, const CrtConst *__restrict__ CC,
+            uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * (n + 1)) return;
+    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
+    const uint32_t o = R / instances, inst = R % instances;
+    const uint32_t ref = pack_ref[2 * o + 1];
+    const uint64_t v = LANES ? circ_word_lane(wires, ref, pack_shift[2 * o + 1], group, instances, inst, e, n, r)
+                             : circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    rawout[(size_t)R * (n + 1) + e] = lift_word(v, CC);
+}
+
+// sgfhe_lwe_lift_modq: the same device function on plain rows, `total` words (grid-stride: the array may hold more
+// than 2^32 words)
+__global__ void __launch_bounds__(256)
+k_lwe_lift(const uint64_t *__restrict__ in, ulonglong2 *__restrict__ out, const CrtConst *__restrict__ CC, size_t total) {
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256)
+        out[t] = lift_word(in[t], CC);
 }
 
 // the circuit's outputs [n_outputs][instances][n + 1], NOT and the constant applied (grid-stride: the

@@ -15,6 +15,7 @@ from . import _lib
 
 FLAG_RAW_MODQ = 1
 CIRCUIT_PACK_DIRECT = 1      # SGFHE_CIRCUIT_PACK_DIRECT
+CIRCUIT_PACK_LIFT = 2        # SGFHE_CIRCUIT_PACK_LIFT
 FLAG_RAW_RNS2 = 2
 CTX_RANDOM_FLATTEN = 1          # accepted, without effect since ABI revision 6
 CTX_DETERMINISTIC_ONLY = 2
@@ -297,7 +298,7 @@ class Engine:
         self._call("sgfhe_lwe_noise", psk, parr, count, stride, pexp, FLAG_RAW_MODQ if raw else 0, st)
         return noise_record(st, raw)
 
-    def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False, direct=False):
+    def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False, direct=False, lift=False):
         """A gate circuit with RLWE ciphertexts at both ends (sgfhe_circuit_run_ct): split_ciphertext of the
         inputs and pack_encrypted_bits of the outputs run on the device inside the one run.
         a, b: [n_inputs][blocks][N] uint64, rlwe.a / rlwe.b of one ciphertext per (input, block), N = n
@@ -306,7 +307,11 @@ class Engine:
         [n_outputs][blocks * n][n + 1] of circuit_run.  Both: ((w, v), lwe).
         direct: SGFHE_CIRCUIT_PACK_DIRECT (sgfhe_circuit_run_ct_ex) -- outputs that name a gate wire are packed
         from the gate's LWEs over Z_Q, without the n refresh bootstraps per ciphertext; the packed ciphertexts
-        decrypt alike but are other bytes, the LWE outputs are the same bytes."""
+        decrypt alike but are other bytes, the LWE outputs are the same bytes.
+        lift: SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT, with or without direct=True (the C ABI takes the
+        lift bit only together with the direct bit) -- direct as above, and every other output (an input, the constant, an XOR3
+        wire, a lane-shifted reference) is lifted from Z_r (lwe_lift) instead of refreshed: no bootstrap in the pack
+        stage, but such an output carries its wire's error on (see the noise rule in include/sgfhe_hip.h)."""
         p = self.params
         a, pa = _c(a)
         b, pb = _c(b)
@@ -320,9 +325,9 @@ class Engine:
         v = np.zeros((circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
         out = np.zeros((circuit.n_outputs, blocks * p.n, p.n + 1), dtype=np.uint64) if lwe else None
         ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None else None
-        if direct:
+        if direct or lift:
             self._call("sgfhe_circuit_run_ct_ex", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out),
-                       CIRCUIT_PACK_DIRECT)
+                       CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0))
         else:
             self._call("sgfhe_circuit_run_ct", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out))
         if packed and lwe:
@@ -344,6 +349,19 @@ class Engine:
                                                     w.ctypes.data_as(ctypes.c_void_p),
                                                     v.ctypes.data_as(ctypes.c_void_p))
         return w, v
+
+    def lwe_lift(self, lwe):
+        """LWEs over Z_r lifted to Z_Q by exact scaling, floor((x Q + r/2) / r) word by word (sgfhe_lwe_lift_modq):
+        lwe [..., n + 1] uint64, a then b -> [..., n + 1][2] residues {lo, hi}, the input of pack_lwe_modq and of
+        lwe_noise(raw=True).  No bootstrap and no key: the error of the LWEs is carried on, not cleaned."""
+        n = self.params.n
+        lwe, pl = _c(lwe)
+        if lwe.ndim < 1 or lwe.shape[-1] != n + 1:
+            raise ValueError("lwe_lift: lwe is [...][n + 1]")
+        out = np.zeros(lwe.shape + (2,), dtype=np.uint64)
+        if lwe.size:
+            self._call("sgfhe_lwe_lift_modq", pl, lwe.size // (n + 1), out.ctypes.data_as(ctypes.c_void_p))
+        return out
 
     def pack_lwe_modq(self, lwe):
         """The tail of pack_encrypted_bits (fhe.jl:675-695) on LWEs already over Z_Q (sgfhe_pack_lwe_modq):

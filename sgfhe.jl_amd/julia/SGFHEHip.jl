@@ -287,18 +287,41 @@ function pack_lwe_modq(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing}, l
     w, v
 end
 
+"""
+    lwe_lift_modq(hkey, lwe::Vector{UInt64}, count)
+
+The exact scaling of LWEs from Z_r to Z_Q, floor((x Q + r/2) / r) word by word (sgfhe_lwe_lift_modq): `lwe` holds
+[count][n + 1] words, a then b -> [count][n + 1][2] words, 16-byte canonical residues, the input layout of
+pack_lwe_modq.  No bootstrap: the error of the LWEs is carried on.
+"""
+function lwe_lift_modq(hkey::HipBootstrapKey, lwe::Vector{UInt64}, count::Integer)
+    p = hkey.params
+    @assert length(lwe) == count * (p.n + 1)
+    out = Vector{UInt64}(undef, count * (p.n + 1) * 2)
+    with_slot(hkey) do slot
+        rc = ccall((:sgfhe_lwe_lift_modq, libsgfhe_hip), Int32,
+                   (Ptr{Cvoid}, Ptr{UInt64}, Csize_t, Ptr{UInt64}),
+                   slot.ctx, lwe, count, out)
+        check(slot.ctx, rc)
+    end
+    out
+end
+
 const CIRCUIT_PACK_DIRECT = UInt32(1)   # SGFHE_CIRCUIT_PACK_DIRECT
+const CIRCUIT_PACK_LIFT = UInt32(2)     # SGFHE_CIRCUIT_PACK_LIFT (given together with CIRCUIT_PACK_DIRECT)
 
 """
-    circuit_run_ct(hkey, rng, circuit::Ptr{Cvoid}, n_outputs, blocks, in_a, in_b, N; direct=false)
+    circuit_run_ct(hkey, rng, circuit::Ptr{Cvoid}, n_outputs, blocks, in_a, in_b, N; direct=false, lift=false)
 
 sgfhe_circuit_run_ct_ex on a plan made with sgfhe_circuit_create: in_a, in_b [n_inputs][blocks][N] words
 (N = n or m) -> (w, v), each n_outputs * blocks * m words.  `direct = true` packs the outputs that name a gate
-wire from the gate's LWEs over Z_Q, without the refresh bootstraps (SGFHE_CIRCUIT_PACK_DIRECT).
+wire from the gate's LWEs over Z_Q, without the refresh bootstraps (SGFHE_CIRCUIT_PACK_DIRECT).  `lift = true` also
+lifts every other output from Z_r instead of refreshing it (SGFHE_CIRCUIT_PACK_LIFT): no bootstrap in the pack stage,
+and those outputs carry their wire's error on.
 """
 function circuit_run_ct(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing}, circuit::Ptr{Cvoid},
                         n_outputs::Integer, blocks::Integer, in_a::Vector{UInt64}, in_b::Vector{UInt64},
-                        N::Integer; direct::Bool=false)
+                        N::Integer; direct::Bool=false, lift::Bool=false)
     p = hkey.params
     w = Vector{UInt64}(undef, n_outputs * blocks * p.m)
     v = Vector{UInt64}(undef, n_outputs * blocks * p.m)
@@ -308,7 +331,8 @@ function circuit_run_ct(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing}, 
         rc = ccall((:sgfhe_circuit_run_ct_ex, libsgfhe_hip), Int32,
                    (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Ptr{UInt64}, Ptr{UInt64}, Csize_t, Ptr{UInt64}, Ptr{UInt64},
                     Ptr{UInt64}, UInt32),
-                   slot.ctx, circuit, blocks, in_a, in_b, N, w, v, C_NULL, direct ? CIRCUIT_PACK_DIRECT : UInt32(0))
+                   slot.ctx, circuit, blocks, in_a, in_b, N, w, v, C_NULL,
+                   lift ? (CIRCUIT_PACK_DIRECT | CIRCUIT_PACK_LIFT) : direct ? CIRCUIT_PACK_DIRECT : UInt32(0))
         check(slot.ctx, rc)
     end
     w, v

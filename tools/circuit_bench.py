@@ -29,6 +29,12 @@ Engine.bootstrap_batch on host arrays, at Params(1024), deterministic flatten.
       must decrypt to the integer sums; prints both times per round and the bootstraps each runs.  Then, in a run of
       its own, the noise probe of (F): the worst max |e| per wire kind and the largest error of the sum of a node's
       three inputs.
+  python tools/circuit_bench.py --ct --gate3 --lift [--configs 16x1] [--reps 3]
+      ripple_adder (one full adder per bit: every sum bit an XOR3 wire) with ciphertexts in and out: (A) refreshed,
+      (D) SGFHE_CIRCUIT_PACK_DIRECT -- only the carry-out is a gate row -- and (L) SGFHE_CIRCUIT_PACK_LIFT -- no
+      bootstrap in the pack stage -- interleaved on one ctx (the order rotates every round), on valid encryptions
+      (|e| <= Dr/16); the LWE outputs must be the same bytes and all three must decrypt to the sums; prints the times
+      beside the bootstraps each runs, and the worst packed phase error of each.
   python tools/circuit_bench.py --ct --trace [--configs 16x1] [--dir DIR]
       run (A) alone in a child process under `rocprofv3 --kernel-trace --stats`: the share of k_circ_split.
 
@@ -348,6 +354,80 @@ def wall_gate3(args):
     eng.close()
 
 
+def wall_lift(args):
+    import sgfhe_jl_amd as S
+    from sgfhe_jl_amd import circuit as C
+    params = S.Params(1024)
+    n, r, Dr = params.n, params.r, params.Dr
+    eng = S.Engine(params)
+    rng = np.random.default_rng(1)
+    sk = rng.integers(0, 2, size=n).astype(np.uint64)
+    eng.generate_key(sk, 2)
+    print("build %s, Params(1024), deterministic flatten, call rows %d, %d ciphertexts per pack group"
+          % (eng.build_id(), C.CALL_ROWS, C.pack_calls(n)))
+    kw = {"A": {}, "D": {"direct": True}, "L": {"lift": True}}
+    names = {"A": "refreshed", "D": "direct", "L": "lift"}
+    wa = rng.integers(0, r, size=(4, 1, n), dtype=np.uint64)
+    for k in "ADL":
+        eng.circuit_run_ct(C.ripple_adder(2), wa, wa, **kw[k])
+
+    def errors(a, b, bits):   # centred error of every message coefficient of RLWEs [..., N] against bits [..., n]
+        lwe = C.split_ciphertext_array(a, b, n, r)
+        ph = lwe[..., n] - (lwe[..., :n] * sk).sum(axis=-1, dtype=np.uint64)
+        e = (ph.astype(np.int64) - bits.astype(np.int64) * Dr) % r
+        return np.where(e > r // 2, e - r, e)
+
+    for bits, blocks in configs(args.configs):
+        c = C.ripple_adder(bits)
+        info = c.info()
+        inst = blocks * n
+        level = info["nodes"] * inst
+        boots = {"A": level + c.n_outputs * inst, "D": level + bits * inst, "L": level}   # (the sum bits are XOR3 wires)
+        # valid encryptions: a uniform, b = a s + bit Dr + e with |e| <= Dr/16 on the message coefficients
+        xs, ys = rng.integers(0, 1 << bits, size=inst), rng.integers(0, 1 << bits, size=inst)
+        plain = np.array([(xs >> i) & 1 for i in range(bits)] + [(ys >> i) & 1 for i in range(bits)],
+                         dtype=np.int64).reshape(2 * bits, blocks, n)
+        a = rng.integers(0, r, size=(2 * bits, blocks, n), dtype=np.uint64)
+        e0 = rng.integers(-(Dr // 16), Dr // 16 + 1, size=plain.shape)
+        b = ((errors(a, np.zeros_like(a), np.zeros_like(plain)) * -1 + plain * Dr + e0) % r).astype(np.uint64)
+        want = np.array([((xs + ys) >> i) & 1 for i in range(bits + 1)], dtype=np.int64).reshape(bits + 1, blocks, n)
+        print("\n%d-bit ripple adder x %d block(s) = %d instances: %d levels, %d nodes per instance, %d outputs (%d XOR3 "
+              "wires); bootstraps per run: (A) %d, (D) %d, (L) %d; raw output table %.0f MB"
+              % (bits, blocks, inst, info["levels"], info["nodes"], c.n_outputs, bits, boots["A"], boots["D"], boots["L"],
+                 c.n_outputs * blocks * n * (n + 1) * 16 / 1e6))
+        t = {k: [] for k in "ADL"}
+        worst = {}
+        for rep in range(args.reps):
+            res = {}
+            order = "ADL"[rep % 3:] + "ADL"[:rep % 3]
+            for what in order:
+                t0 = time.perf_counter()
+                res[what] = eng.circuit_run_ct(c, a, b, packed=True, lwe=True, **kw[what])
+                t[what].append(time.perf_counter() - t0)
+            same = all(np.array_equal(res["A"][1], res[k][1]) for k in "DL")
+            print("  round %d (order %s): " % (rep, order) +
+                  " | ".join("(%s) %s %.3f s, %d bootstraps = %.0f bootstraps/s"
+                             % (k, names[k], t[k][-1], boots[k], boots[k] / t[k][-1]) for k in "ADL") +
+                  " | L / A %.4f, L / D %.4f | same LWE outputs: %s"
+                  % (t["L"][-1] / t["A"][-1], t["L"][-1] / t["D"][-1], same))
+            if not same:
+                sys.exit("the LWE outputs of the three runs differ")
+            for k in "ADL":
+                err = np.abs(errors(res[k][0][0], res[k][0][1], want))
+                if err.max() >= Dr // 2:
+                    sys.exit("(%s) does not decrypt to the sums" % k)
+                worst[k] = (int(err[:bits].max()), int(err[bits].max()))
+        mean = {k: np.mean(t[k]) for k in "ADL"}
+        print("  " + " | ".join("(%s) mean %.3f s, spread %.3f s" % (k, mean[k], max(t[k]) - min(t[k])) for k in "ADL"))
+        print("  mean L / mean A = %.4f, by bootstrap counts %.4f | mean L / mean D = %.4f, by bootstrap counts %.4f"
+              % (mean["L"] / mean["A"], boots["L"] / boots["A"], mean["L"] / mean["D"], boots["L"] / boots["D"]))
+        print("  seconds per 1000 bootstraps: " + ", ".join("(%s) %.4f" % (k, 1e3 * mean[k] / boots[k]) for k in "ADL") +
+              "; L minus its share of A's rate: %+.3f s" % (mean["L"] - mean["A"] * boots["L"] / boots["A"]))
+        print("  worst packed phase error against Dr/2 = %d (all decrypt to x + y): " % (Dr // 2) +
+              ", ".join("(%s) %s: sum bits %d, carry-out %d" % (k, names[k], worst[k][0], worst[k][1]) for k in "ADL"))
+    eng.close()
+
+
 def ct_only(args):
     import sgfhe_jl_amd as S
     import encrypted_adder
@@ -415,6 +495,8 @@ def main():
     ap.add_argument("--direct", action="store_true", help="with --ct: the refreshed run against SGFHE_CIRCUIT_PACK_DIRECT")
     ap.add_argument("--probe", action="store_true", help="circuit_run against circuit_probe (the noise probe of every wire)")
     ap.add_argument("--gate3", action="store_true", help="the adder of two-input nodes against ripple_adder (full adders)")
+    ap.add_argument("--lift", action="store_true",
+                    help="with --ct --gate3: ripple_adder refreshed, direct and with SGFHE_CIRCUIT_PACK_LIFT")
     ap.add_argument("--run-only", action="store_true", help="with --probe: circuit_run alone, the same rounds")
     ap.add_argument("--circuit-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--ct-only", action="store_true", help=argparse.SUPPRESS)
@@ -431,6 +513,10 @@ def main():
         ct_only(args)
     elif args.trace:
         trace(args)
+    elif args.lift:
+        if not (args.ct and args.gate3):
+            sys.exit("--lift goes with --ct --gate3")
+        wall_lift(args)
     elif args.gate3:
         wall_gate3(args)
     elif args.probe:

@@ -503,6 +503,47 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * Dr/2 = 2048 (RESULTS.md).  An XOR3 wire that feeds a node counts with the sum of its own three inputs' errors:
  * feed it together with bootstrapped wires or constants, as the carry chain of a ripple adder does (sum bits are
  * outputs, only MAJ is carried on).
+ *
+ * Weighted-sum nodes (sgfhe_circuit_create_w).  The rotation depends on the SUM of the bootstrap's inputs only, and
+ * its two sign reads on that sum's multiple of Dr mod 4; three terms of weight 1 are one case.  The nodes come as CSR
+ * arrays: node g's terms are term_ref / term_shift / term_weight [node_start[g] .. node_start[g + 1]), node_start[0]
+ * = 0.  node_kind[g] = 0 is the CLASSIC two-input node above (exactly two terms of weight 1, its XOR wire the
+ * bootstrap's own row); node_kind[g] = 1 is a SUM NODE of 1 to SGFHE_CIRCUIT_MAX_TERMS terms, every weight w_i in
+ * {-2, -1, 1, 2}.  A term's reference is validated like any node input: an input wire, the constant or a wire of an
+ * earlier node, with NOT and a lane shift, both applied before the weight.  With X_i the referenced LWEs at one
+ * instance, the node is ONE row of its level call -- pruning, levels, slots, row and call numbering and the draws
+ * are those of any node -- whose bootstrap inputs are (a1, b1) = U = sum of w_i X_i mod r, word by word, b included,
+ * and (a2, b2) = 0 (the bootstrap adds its two inputs first: (U, 0) gives the words (X + Y, Z) gives when U =
+ * X + Y + Z).  TRUE (FALSE | NOT) with weight c adds the constant c Dr.  With s = sum of w_i x_i mod 4 over the
+ * plaintext bits, the wires of the node are
+ *   n_inputs + 3 g + 0  HI   the AND row: s in {2, 3}
+ *   n_inputs + 3 g + 1  MID  the OR row:  s in {1, 2}
+ *   n_inputs + 3 g + 2  LOW  (U - 2 HI) mod r, word by word, b included, HI being the reduced row (the words k_final
+ *                            gives): s mod 2.  Linear, not bootstrapped -- what XOR3 is for a three-input node.
+ * So weights (1, 1, 1) are the three-input node (the same bytes on all three wires, and a plan whose sum nodes all
+ * have two or three unit weights runs the kernels of the sgfhe_circuit_create3 plan: two unit terms are (x, y,
+ * FALSE)); all weights 2 give HI = the XOR of all terms, ONE bootstrap for a parity of up to 64 wires -- a doubled
+ * wire encodes its bit as 0 or 2 Dr = r / 2, and sums of those are XORs; one term of weight 1 gives MID = a refresh
+ * of that wire; 2x + y + z gives HI = s >= 2 and MID = s in {1, 2} for s = 0 .. 3 (s = 4 wraps to 0).
+ * Validation: everything sgfhe_circuit_create3 checks, and node_start non-decreasing from 0, node_kind 0 or 1, the
+ * term counts and weights above; SGFHE_CIRCUIT_NONE never appears.  Anything else is SGFHE_ERR_INVALID_ARG with
+ * *out NULL, and nothing is allocated.  A NULL term_shift is all 0.
+ * Every run entry point takes such a plan.  A plan with a sum node of something other than two or three unit weights
+ * gathers its level calls with k_circ_gather_w (one pass over the node's terms per word); every other plan runs the
+ * kernels it ran.  Under SGFHE_CIRCUIT_PACK_DIRECT an output naming HI or MID with shift 0 is DIRECT; one naming LOW
+ * is REFRESHED (LIFTED under SGFHE_CIRCUIT_PACK_LIFT), as XOR3 is.  The probe's plaintext evaluation knows the three
+ * wires; the record of a LOW wire is, up to 2 e_HI, the error of the node's input sum.
+ * Noise -- a MEASURED rule, as for three inputs.  A node is correct while |sum of w_i e_i| < Dr/2, and LOW carries
+ * that error on.  A weight of 2 doubles its wire's error: a split sgfhe_host_encrypt_private bit has an error of up
+ * to Dr/4 - 1, which doubled is already at the limit, so weight-2 terms are for gate rows, refreshed wires (MID of
+ * a one-term node) and packed outputs, never for fresh encryptions.  Measured on the C oracle at Params(64), 64
+ * instances, inputs refreshed first (max |e| = 4): for k = 2 .. 8 the AND row of 2 (X_1 + ... + X_k) decrypts to the
+ * parity in every instance, the error of the doubled sum is at most 28 against Dr/2 = 128, the output error at most
+ * 6; a node 2x + y + z gives s >= 2 on the AND row and s in {1, 2} on the OR row for all four values of s.
+ * At Params(1024) (Dr/2 = 2048), with the probe over 256 instances: refreshed wires have max |e| = 26, and the LOW wire
+ * of a parity node of 8, 16 and 32 refreshed wires max |e| = 146, 202 and 256 -- an eighth of the margin at 32 terms,
+ * the errors adding like independent ones; CRC-16 of 32-bit messages (examples/encrypted_crc.py --direct, one block)
+ * has a worst packed phase error of 33 (RESULTS.md, profiles/r13_circuit_wsum.txt).
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -519,6 +560,14 @@ int32_t sgfhe_circuit_create3(uint32_t n_inputs, const uint32_t *gates /* [n_gat
                               const int32_t *gate_shift /* [n_gates][3], NULL = all 0 */, size_t n_gates,
                               const uint32_t *outputs, const int32_t *out_shift /* [n_outputs], NULL = all 0 */,
                               size_t n_outputs, uint32_t group, sgfhe_circuit **out);
+#define SGFHE_CIRCUIT_MAX_TERMS 64u
+int32_t sgfhe_circuit_create_w(uint32_t n_inputs,
+                               const uint32_t *node_kind /* [n_gates]: 0 = classic two-input node, 1 = sum node */,
+                               const uint32_t *node_start /* [n_gates + 1], CSR into the term arrays, [0] = 0 */,
+                               const uint32_t *term_ref, const int32_t *term_shift /* NULL = all 0 */,
+                               const int32_t *term_weight, size_t n_gates, const uint32_t *outputs,
+                               const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
+                               uint32_t group, sgfhe_circuit **out);
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
@@ -564,7 +613,7 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t bloc
  * Ciphertext q = output * blocks + block is DIRECT when its output reference names a gate wire with lane shift 0,
  * negated or not, and REFRESHED when it names an input wire or the constant, or carries a non-zero lane shift
  * (sgfhe_circuit_create_lanes: its rows are not the gate's own rows in order) or names the XOR3 wire of a three-input
- * node (sgfhe_circuit_create3: linear over Z_r, no gate row).  The levels run with the calls, rows and call
+ * node or the LOW wire of a sum node (sgfhe_circuit_create3, sgfhe_circuit_create_w: linear over Z_r, no gate row).  The levels run with the calls, rows and call
  * numbers of sgfhe_circuit_run_ct, so out_lwe has the bytes of the flags = 0 run in both flatten modes; a level
  * call that produces a wire some direct output names leaves its rows un-reduced, and its scatter kernel writes
  * their ModRed (the words the reduced call gives) into the wire table and the named gate's rows into a raw

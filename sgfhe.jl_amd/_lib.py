@@ -151,6 +151,7 @@ def lib():
         "sgfhe_circuit_create_lanes": (i32, [u32, vp, vp, sz, vp, vp, sz, u32, ctypes.POINTER(vp)]),
         "sgfhe_circuit_group": (i32, [vp, _u32p]),
         "sgfhe_circuit_create3": (i32, [u32, vp, vp, sz, vp, vp, sz, u32, ctypes.POINTER(vp)]),
+        "sgfhe_circuit_create_w": (i32, [u32, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, ctypes.POINTER(vp)]),
         "sgfhe_lwe_lift_modq": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
@@ -177,4 +178,5 @@ EXPORTED_SYMBOLS = (
     "sgfhe_kernel_names", "sgfhe_release_host_staging", "sgfhe_circuit_create", "sgfhe_circuit_info",
     "sgfhe_circuit_destroy", "sgfhe_circuit_run", "sgfhe_circuit_run_ct", "sgfhe_circuit_run_ct_ex",
     "sgfhe_pack_lwe_modq", "sgfhe_lwe_noise", "sgfhe_circuit_run_probe",
-    "sgfhe_circuit_create_lanes", "sgfhe_circuit_group", "sgfhe_circuit_create3", "sgfhe_lwe_lift_modq")
+    "sgfhe_circuit_create_lanes", "sgfhe_circuit_group", "sgfhe_circuit_create3", "sgfhe_lwe_lift_modq",
+    "sgfhe_circuit_create_w")

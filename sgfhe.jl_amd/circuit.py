@@ -22,6 +22,12 @@ Three-input nodes (sgfhe_circuit_create3).  `gate3(x, y, z)` is ONE bootstrap, o
 phase of the sum of three bits yields MAJ (the AND row) and "one or two true" (the OR row), and XOR3 =
 x + y + z - 2 MAJ over Z_r is linear.  `full_adder(x, y, c)` is therefore one node and ripple_adder(16) sixteen.
 XOR3 is not bootstrapped and carries its inputs' errors on: see the noise rule in include/sgfhe_hip.h.
+
+Weighted-sum nodes (sgfhe_circuit_create_w).  `sum_node([(w, wire), ...])` is ONE bootstrap on U = sum of w X mod r,
+w in {-2, -1, 1, 2}, up to 64 terms: with s = the sum of w x mod 4 its wires are HI (s in {2, 3}), MID (s in {1, 2}) and
+the linear LOW = U - 2 HI (s mod 2).  All weights 2 make HI the XOR of all terms -- `xor(*wires)` -- so a GF(2)-linear
+map is one node per output bit (gf2_matvec, crc16_ccitt); one term of weight 1 makes MID a refresh (`refresh(w)`).  A
+weight of 2 doubles the wire's error: use it on bootstrapped wires, not on fresh encryptions.
 """
 
 import ctypes
@@ -34,6 +40,7 @@ from .scheme import LWE, RLWE, Ciphertext, EncryptedBit, PackedCiphertext, _set_
 FALSE_ID = 0x7FFFFFFF      # SGFHE_CIRCUIT_FALSE
 NONE_ID = 0x7FFFFFFE       # SGFHE_CIRCUIT_NONE: the third reference of a two-input node
 NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
+MAX_TERMS = 64             # SGFHE_CIRCUIT_MAX_TERMS
 CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
 
 
@@ -77,7 +84,8 @@ class Circuit:
     """Builder of a gate circuit: `n_inputs` input wires, nodes added with gate(), outputs set with
     output().  `group`: the lane group size (instances form consecutive groups of `group` lanes; a reference may be
     shifted by |d| < group lanes, Wire.lane).  The C plan (sgfhe_circuit_create, sgfhe_circuit_create_lanes when
-    the group is above 1, sgfhe_circuit_create3 when a gate3 exists) is made on first use and freed with the object."""
+    the group is above 1, sgfhe_circuit_create3 when a gate3 exists, sgfhe_circuit_create_w when a sum node exists that
+    is no three-input node) is made on first use and freed with the object."""
 
     FALSE = Wire(FALSE_ID)
     TRUE = Wire(FALSE_ID | NOT_BIT)
@@ -93,6 +101,7 @@ class Circuit:
         self.gates = []            # [(x ref, y ref)], or (x ref, y ref, z ref) for a three-input node
         self.outputs = []          # [ref]
         self.gate_shifts = []      # [(x lane shift, y lane shift)] or (x, y, z lane shift), beside gates
+        self.gate_weights = {}     # node -> (weight, ...) beside its references: the sum nodes (sum_node)
         self.output_shifts = []    # [lane shift], beside outputs
         self._plan = None
         self._L = None
@@ -122,6 +131,52 @@ class Circuit:
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
 
+    def sum_node(self, terms):
+        """One weighted-sum node: ONE bootstrap on U = the sum of weight * wire over Z_r.  terms: [(weight, wire), ...],
+        1 to 64 of them, weight in {-2, -1, 1, 2}; TRUE with weight c adds the constant c Dr.  Returns its (HI, MID, LOW)
+        wires: with s = the sum of weight * bit mod 4, HI is s in {2, 3} (the AND row), MID is s in {1, 2} (the OR row)
+        and LOW is s mod 2 = U - 2 HI over Z_r, which is linear and carries the error of the sum on.  Weights (1, 1, 1)
+        are gate3."""
+        terms = list(terms)
+        if not 1 <= len(terms) <= MAX_TERMS:
+            raise ValueError("a sum node has 1 to %d terms" % MAX_TERMS)
+        if any(int(w) not in (-2, -1, 1, 2) for w, _ in terms):
+            raise ValueError("the weights of a sum node are -2, -1, 1 or 2")
+        self.gates.append(tuple(self._ref(x) for _, x in terms))
+        self.gate_shifts.append(tuple(x.shift for _, x in terms))
+        self.gate_weights[len(self.gates) - 1] = tuple(int(w) for w, _ in terms)
+        self._invalidate()
+        base = self.n_inputs + 3 * (len(self.gates) - 1)
+        return Wire(base), Wire(base + 1), Wire(base + 2)
+
+    def xor(self, *wires):
+        """The XOR of any number of wires (up to 64) in ONE bootstrap: HI of the sum node with every weight 2.  The
+        wires should be bootstrapped ones (gate rows, refreshed wires): the node doubles their errors.  No wire at
+        all is the constant FALSE."""
+        if not wires:
+            return Circuit.FALSE
+        return self.sum_node([(2, w) for w in wires])[0]
+
+    def refresh(self, w):
+        """A bootstrapped copy of `w`: MID of the sum node with the one term (1, w)."""
+        return self.sum_node([(1, w)])[1]
+
+    def kind(self, g):
+        """Node g: "classic" (gate), "gate3" or "sum" (sum_node)."""
+        return "sum" if g in self.gate_weights else ("gate3" if len(self.gates[g]) == 3 else "classic")
+
+    def weights(self, g):
+        """The weights of node g's inputs (all 1 for gate and gate3 nodes)."""
+        return self.gate_weights.get(g, (1,) * len(self.gates[g]))
+
+    def _wide(self, g):
+        """Node g is a sum node that sgfhe_circuit_create3 cannot express: not two or three unit weights."""
+        return g in self.gate_weights and not (len(self.gates[g]) in (2, 3) and set(self.gate_weights[g]) == {1})
+
+    @property
+    def has_wsum(self):
+        return any(self._wide(g) for g in self.gate_weights)
+
     def full_adder(self, x, y, c):
         """x + y + c in one bootstrap: returns (sum, carry) = (XOR3, MAJ) of gate3(x, y, c)."""
         maj, _, xor3 = self.gate3(x, y, c)
@@ -129,7 +184,7 @@ class Circuit:
 
     @property
     def has_gate3(self):
-        return any(len(g) == 3 for g in self.gates)
+        return any(len(g) == 3 for i, g in enumerate(self.gates) if i not in self.gate_weights)
 
     def output(self, *wires):
         """Set the circuit's outputs (wire references: inputs, constants and negated wires allowed)."""
@@ -160,8 +215,19 @@ class Circuit:
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
             os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
             h = ctypes.c_void_p()
-            if self.has_gate3:      # two-input nodes padded with SGFHE_CIRCUIT_NONE (and a shift of 0)
-                g = np.ascontiguousarray(np.array([tuple(x) + (NONE_ID,) * (3 - len(x)) for x in self.gates],
+            if self.has_wsum:       # CSR: every node's terms, kind 1 for gate3 and sum nodes
+                kind = np.array([self.kind(g) != "classic" for g in range(len(self.gates))], dtype=np.uint32)
+                start = np.cumsum([0] + [len(x) for x in self.gates]).astype(np.uint32)
+                tr = np.array([ref for x in self.gates for ref in x], dtype=np.uint32)
+                ts = np.array([d for x in self.gate_shifts for d in x], dtype=np.int32)
+                tw = np.array([w for g in range(len(self.gates)) for w in self.weights(g)], dtype=np.int32)
+                rc = L.sgfhe_circuit_create_w(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), len(self.gates),
+                                              vp(o), vp(os_), len(self.outputs), self.group, ctypes.byref(h))
+            elif self.has_gate3 or self.gate_weights:
+                # two-input nodes padded with SGFHE_CIRCUIT_NONE (and a shift of 0); a sum node of two unit weights is
+                # the three-input node (x, y, FALSE)
+                pad = lambda i: FALSE_ID if i in self.gate_weights else NONE_ID
+                g = np.ascontiguousarray(np.array([tuple(x) + (pad(i),) * (3 - len(x)) for i, x in enumerate(self.gates)],
                                                   dtype=np.uint32).reshape(-1, 3))
                 gs = np.ascontiguousarray(np.array([tuple(x) + (0,) * (3 - len(x)) for x in self.gate_shifts],
                                                    dtype=np.int32).reshape(-1, 3))
@@ -239,6 +305,11 @@ class Circuit:
         for levelnodes in self.schedule():
             for g in levelnodes:
                 base = self.n_inputs + 3 * g
+                if g in self.gate_weights:
+                    s = sum(w * val(ref, d).astype(np.int64)
+                            for w, ref, d in zip(self.gate_weights[g], self.gates[g], self.gate_shifts[g])) % 4
+                    wires[base], wires[base + 1], wires[base + 2] = s >= 2, (s == 1) | (s == 2), s % 2 == 1
+                    continue
                 if len(self.gates[g]) == 3:
                     x, y, z = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
                     wires[base], wires[base + 1], wires[base + 2] = (x & y) | (z & (x | y)), (x | y | z) & ~(x & y & z), \
@@ -304,6 +375,48 @@ def ripple_adder(width):
     return c
 
 
+def gf2_matvec(M, refresh_inputs=True):
+    """y = M x over GF(2) with ONE sum node per output bit: Circuit(columns of M) whose output i is the XOR of the inputs
+    j with M[i][j] = 1 (Circuit.xor: HI of all weights 2; an empty row is the constant FALSE).  refresh_inputs: every
+    input some row uses is first refreshed (Circuit.refresh, one bootstrap each), as it must be when the inputs are
+    fresh encryptions -- a weight of 2 doubles the error, and a split encrypt_private bit is already at the limit;
+    False for inputs that are gate rows or packed outputs.  Rows of at most 64 ones.  Two levels (one without the
+    refreshes); every output is a gate row, so SGFHE_CIRCUIT_PACK_DIRECT packs them all without a refresh."""
+    M = np.asarray(M)
+    if M.ndim != 2 or not np.isin(M, (0, 1)).all():
+        raise ValueError("gf2_matvec: a two-dimensional 0/1 matrix is expected")
+    M = M.astype(bool)
+    if M.sum(axis=1).max(initial=0) > MAX_TERMS:
+        raise ValueError("gf2_matvec: a row has more than %d ones" % MAX_TERMS)
+    c = Circuit(M.shape[1])
+    src = {j: (c.refresh(c.inputs[j]) if refresh_inputs else c.inputs[j]) for j in range(M.shape[1]) if M[:, j].any()}
+    c.output(*[c.xor(*[src[j] for j in np.flatnonzero(row)]) for row in M])
+    return c
+
+
+def crc16_matrix(message_bits):
+    """The 16 x message_bits 0/1 matrix of CRC-16/XMODEM (polynomial 0x1021, initial value 0: binascii.crc_hqx(msg, 0)),
+    which is GF(2)-linear in the message.  Column j is message bit j, the bits in the order the CRC consumes them (bit 7
+    of byte 0 first); row k is bit k of the CRC (LSB first).  message_bits: a multiple of 8."""
+    import binascii
+    if message_bits < 8 or message_bits % 8:
+        raise ValueError("crc16: the message is a whole number of bytes")
+    M = np.zeros((16, message_bits), dtype=np.uint8)
+    for j in range(message_bits):
+        msg = bytearray(message_bits // 8)
+        msg[j // 8] = 0x80 >> (j % 8)
+        crc = binascii.crc_hqx(bytes(msg), 0)
+        M[:, j] = [(crc >> k) & 1 for k in range(16)]
+    return M
+
+
+def crc16_ccitt(message_bits, refresh_inputs=True):
+    """CRC-16 (CCITT polynomial 0x1021, initial value 0: binascii.crc_hqx(msg, 0)) of a message of `message_bits` bits
+    as gf2_matvec(crc16_matrix(message_bits)): 16 sum nodes, plus one refresh per message bit when asked.  Inputs and
+    outputs in the bit orders of crc16_matrix."""
+    return gf2_matvec(crc16_matrix(message_bits), refresh_inputs=refresh_inputs)
+
+
 def lwe_not(words, r):
     """NOT of LWEs [..., n + 1] over Z_r: enc_trivial(true) - w (a -> -a, b -> Dr - b, mod r)."""
     words = np.asarray(words, dtype=np.uint64)
@@ -317,7 +430,9 @@ def replay_levels(circuit, inputs, r, boot):
     sgfhe_circuit_run: inputs [n_inputs][instances][n + 1] -> outputs [n_outputs][instances][n + 1].
     `boot(call, a1, b1, a2, b2)` runs one call (rows of at most CALL_ROWS) and returns [rows][3][n + 1];
     `call` counts the calls from 0.  A three-input node is the row (x + y mod r, z); its third wire is
-    x + y + z - 2 * (row 0 of the result) mod r.  A checking and measuring aid: the engine's circuit path does this on
+    x + y + z - 2 * (row 0 of the result) mod r.  A sum node is the row (U, FALSE), U = the sum of weight * term mod r
+    -- the bootstrap adds its two inputs first, so this is also what (x + y, z) gives for unit weights -- and its third
+    wire U - 2 * (row 0 of the result) mod r.  A checking and measuring aid: the engine's circuit path does this on
     the device (Engine.circuit_run)."""
     inputs = np.asarray(inputs, dtype=np.uint64)
     inst, row = inputs.shape[1], inputs.shape[2]
@@ -336,14 +451,18 @@ def replay_levels(circuit, inputs, r, boot):
         # row = rank * instances + instance
         mask = np.uint64(r - 1)
 
-        def first(g):   # the first bootstrap input of node g: x, or x + y mod r of a three-input node
-            x = val(circuit.gates[g][0], circuit.gate_shifts[g][0])
-            if len(circuit.gates[g]) == 3:
-                x = (x + val(circuit.gates[g][1], circuit.gate_shifts[g][1])) & mask
-            return x
+        def pair(g):   # the bootstrap inputs of node g: (x, y), (x + y mod r, z) of a three-input node, (U, FALSE)
+            vals = [val(ref, d) for ref, d in zip(circuit.gates[g], circuit.gate_shifts[g])]
+            if circuit.kind(g) == "sum":
+                u = sum(w * v.astype(np.int64) for w, v in zip(circuit.gate_weights[g], vals)) % r
+                return u.astype(np.uint64), np.zeros_like(vals[0])
+            if len(vals) == 3:
+                return (vals[0] + vals[1]) & mask, vals[2]
+            return vals[0], vals[1]
 
-        x = np.concatenate([first(g) for g in nodes])
-        y = np.concatenate([val(circuit.gates[g][-1], circuit.gate_shifts[g][-1]) for g in nodes])
+        pairs = [pair(g) for g in nodes]
+        x = np.concatenate([p[0] for p in pairs])
+        y = np.concatenate([p[1] for p in pairs])
         res = np.zeros((len(x), 3, row), dtype=np.uint64)
         for r0 in range(0, len(x), CALL_ROWS):
             sl = slice(r0, r0 + CALL_ROWS)
@@ -353,7 +472,7 @@ def replay_levels(circuit, inputs, r, boot):
             sl = slice(k * inst, (k + 1) * inst)
             for w in range(3):
                 wires[circuit.n_inputs + 3 * g + w] = res[sl, w]
-            if len(circuit.gates[g]) == 3:
+            if circuit.kind(g) != "classic":
                 wires[circuit.n_inputs + 3 * g + 2] = (x[sl] + y[sl] - np.uint64(2) * res[sl, 0]) & mask
     return np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
         else np.zeros((0, inst, row), np.uint64)
@@ -477,7 +596,8 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False):
     [rows][3][n + 1][2] residues mod Q; the levels run through it in the row and call order of replay_levels, their
     ModRed (modred_words) being what the next level reads and what `lwe` holds.  The pack stage takes the
     ciphertexts q = output * blocks + block in ascending order, pack_calls(n) at a time: a group's refreshed
-    ciphertexts (outputs that name an input wire, the constant or an XOR3 wire, or carry a lane shift) are bootstrapped as one call -- trivial 1 paired
+    ciphertexts (outputs that name an input wire, the constant, an XOR3 wire or the LOW wire of a sum node, or carry a
+    lane shift) are bootstrapped as one call -- trivial 1 paired
     with every bit, row = rank among them * n + bit, AND rows kept -- and then `tail(call, lwe_q)` (lwe_q
     [count][n][n + 1][2] -> (w, v), each [count][m]) packs the group: the gate's own rows for a direct output, NOT
     over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  lift=True (SGFHE_CIRCUIT_PACK_LIFT): the
@@ -510,7 +630,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False):
         if i == FALSE_ID or i < circuit.n_inputs or circuit.output_shifts[o] != 0:
             return False
         g, w = divmod(i - circuit.n_inputs, 3)
-        return not (w == 2 and len(circuit.gates[g]) == 3)   # XOR3 is linear over Z_r: no gate row over Z_Q
+        return not (w == 2 and circuit.kind(g) != "classic")   # XOR3 / LOW is linear over Z_r: no gate row over Z_Q
 
     n_ct, cpc = circuit.n_outputs * blocks, pack_calls(n)
     w = np.zeros((n_ct, m), dtype=np.uint64)
@@ -610,7 +730,7 @@ def probe_circuit(bkey, key, rng, circuit, inputs, bits):
 
 def noise_report(circuit, stats):
     """The records of probe_circuit by wire: a list of dicts (wire, kind: "input" / "AND" / "OR" / "XOR", or "MAJ" /
-    "ONE_OR_TWO" / "XOR3" for the wires of a three-input node, node,
+    "ONE_OR_TWO" / "XOR3" for the wires of a three-input node, "HI" / "MID" / "LOW" for those of a sum node, node,
     level (0 for inputs), rows, wrong, max_abs, mean, rms, margin), the wires of pruned nodes left out, sorted
     by max |e| (largest first), then level."""
     level = {}
@@ -622,7 +742,8 @@ def noise_report(circuit, stats):
         if st.rows == 0:
             continue
         g = (wire - circuit.n_inputs) // 3 if wire >= circuit.n_inputs else None
-        names = ("MAJ", "ONE_OR_TWO", "XOR3") if g is not None and len(circuit.gates[g]) == 3 else ("AND", "OR", "XOR")
+        names = ("AND", "OR", "XOR") if g is None else \
+            {"classic": ("AND", "OR", "XOR"), "gate3": ("MAJ", "ONE_OR_TWO", "XOR3"), "sum": ("HI", "MID", "LOW")}[circuit.kind(g)]
         kind = "input" if g is None else names[(wire - circuit.n_inputs) % 3]
         rows.append(dict(wire=wire, kind=kind, node=g, level=0 if g is None else level[g], rows=st.rows,
                          wrong=st.wrong, max_abs=st.max_abs, mean=st.sum / st.rows,

@@ -2,8 +2,8 @@
 // graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
 // slot of the device wire table by liveness, and fixes the row and call numbering of a run; circuit_plain_bits
 // evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp,
-// circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp and circuit_gate3_sanitized.cpp drive it under ASan / UBSan
-// on the CPU.
+// circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp, circuit_gate3_sanitized.cpp and circuit_wsum_sanitized.cpp
+// drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -52,10 +52,23 @@ struct CircuitPlan {
     std::vector<int32_t> in_shift3;     // [live]
     std::vector<uint32_t> in_row3;      // [live]
     std::vector<uint32_t> three_before; // [live + 1]: three-input nodes among order[0 .. k)
+    // Weighted-sum nodes (sgfhe_circuit_create_w).  A sum node of two or three unit weights IS a three-input node
+    // (x, y, FALSE) or (x, y, z) and is planned as one.  Every other sum node is a WIDE node: in_ref / in_shift /
+    // in_row name the constant FALSE twice and in_ref3 names it once -- any reference but CIRC_NO_INPUT marks the
+    // node for the XOR3 kernels, which compute its LOW wire -- and its terms are in the CSR tables below.  Those
+    // exist when wide > 0 and then cover EVERY live node, a classic or three-input one with its two or three unit
+    // terms, so that one gather (k_circ_gather_w) serves a whole level.
+    uint32_t wide = 0;                  // live wide nodes
+    std::vector<uint32_t> w_start;      // [live + 1]: node k's terms are w_ref[w_start[k] .. w_start[k + 1])
+    std::vector<uint32_t> w_ref;        // [terms]: slot references
+    std::vector<int32_t> w_shift;       // [terms]
+    std::vector<int32_t> w_weight;      // [terms]: -2, -1, 1, 2
+    std::vector<uint32_t> w_row;        // [terms], host only: the terms as probe rows (as in_row)
     // Host only (SGFHE_CIRCUIT_PACK_DIRECT): where an output that names a gate wire is produced
     std::vector<uint32_t> out_node;     // [n_outputs]: index in `order` of the producing node, CIRC_NONE for an input
                                         // wire, the constant, a lane-shifted reference or the XOR3 wire of a
-                                        // three-input node, which is no gate row over Z_Q (those are refreshed)
+                                        // three-input node (the LOW wire of a sum node), which is no gate row over
+                                        // Z_Q (those are refreshed)
     std::vector<uint32_t> out_gate;     // [n_outputs]: 0 AND, 1 OR, 2 XOR (0 where out_node is CIRC_NONE)
     // Host only (sgfhe_circuit_run_probe): the node's inputs as PROBE ROWS -- row i < n_inputs is input wire i, row
     // n_inputs + 3 k + w is wire w of the k-th live node in `order` -- with CIRC_NOT and CIRC_FALSE as in a reference
@@ -66,6 +79,8 @@ struct CircuitPlan {
     bool lanes() const { return group > 1; }
     // the run takes the three-reference gather and the XOR3 kernels
     bool gate3() const { return three > 0; }
+    // the levels of the run take the CSR gather
+    bool wsum() const { return wide > 0; }
     // live nodes order[ka .. kb] hold a three-input node
     bool gate3_in(uint32_t ka, uint32_t kb) const { return three && three_before[kb + 1] != three_before[ka]; }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
@@ -78,28 +93,67 @@ namespace circuit_detail {
 inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
 }  // namespace circuit_detail
 
-// Builds `P` from the arrays of sgfhe_circuit_create3 (`arity` 3: gates and gate_shift are [n_gates][3], and a third
-// reference CIRC_NO_INPUT makes the node a two-input node) or of sgfhe_circuit_create_lanes (`arity` 2: [n_gates][2],
-// every node a two-input node); gate_shift / out_shift NULL: all 0.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
-// malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it.
-inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
-                                  int arity, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
-                                  uint32_t group, CircuitPlan &P) noexcept {
+// One view of the nodes' inputs behind every entry.  `arity` 2 or 3: the [n_gates][arity] arrays of
+// sgfhe_circuit_create_lanes / sgfhe_circuit_create3 (a third reference CIRC_NO_INPUT leaves a two-input node; with
+// one, the node is the sum node of three unit weights).  `arity` 0: the CSR arrays of sgfhe_circuit_create_w.  Term i
+// of the circuit is refs[i], shifts[i] (NULL: 0), weights[i] (NULL: 1); node g's terms are first(g) .. first(g) +
+// count(g).
+struct CircuitNodes {
+    int arity;
+    const uint32_t *refs;
+    const int32_t *shifts;
+    const uint32_t *kind = nullptr, *start = nullptr;
+    const int32_t *weights = nullptr;
+
+    size_t first(size_t g) const { return arity ? (size_t)arity * g : start[g]; }
+    size_t count(size_t g) const {
+        if (!arity) return (size_t)start[g + 1] - start[g];
+        return arity == 3 && refs[3 * g + 2] != CIRC_NO_INPUT ? 3 : 2;
+    }
+    bool classic(size_t g) const { return arity ? count(g) == 2 : kind[g] == 0; }
+    int32_t weight(size_t i) const { return weights ? weights[i] : 1; }
+    // a sum node that is no three-input node: something other than two or three unit weights
+    bool wide(size_t g) const {
+        if (classic(g)) return false;
+        const size_t n = count(g);
+        if (n != 2 && n != 3) return true;
+        for (size_t i = first(g); i < first(g) + n; i++)
+            if (weight(i) != 1) return true;
+        return false;
+    }
+};
+
+// Builds `P` from the nodes `N` (gate shifts / out_shift NULL: all 0).  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
+// malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it, and a refused circuit costs no
+// allocation.
+inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
+                                  const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
     using circuit_detail::wire_id;
-    const size_t A = (size_t)arity;
-    // inputs of node g: 3 when it carries a third reference, 2 otherwise.  CIRC_NO_INPUT is above every wire id, so
-    // anywhere else -- a first or second input, an output, with NOT set -- it fails the id checks below.
-    auto fan_in = [&](size_t g) { return arity == 3 && gates[3 * g + 2] != CIRC_NO_INPUT ? 3 : 2; };
+    const uint32_t *refs = N.refs;
+    const int32_t *gate_shift = N.shifts;
     // ---- validate: every size below 2^31, wire ids below the constant, inputs name earlier wires only,
-    // every shift inside the group (in 64 bits: -INT32_MIN does not exist)
-    if (n_outputs < 1 || !outputs || (n_gates && !gates) || group < 1) return SGFHE_ERR_INVALID_ARG;
+    // every shift inside the group (in 64 bits: -INT32_MIN does not exist).  CIRC_NO_INPUT is above every wire id, so
+    // anywhere but beside a two-input node of the [n_gates][3] arrays it fails the id checks below.
+    if (n_outputs < 1 || !outputs || (n_gates && !refs) || group < 1) return SGFHE_ERR_INVALID_ARG;
     auto shift_ok = [&](int32_t d) { return (d < 0 ? -(int64_t)d : (int64_t)d) < (int64_t)group; };
     if (n_inputs >= 0x80000000u || n_gates >= 0x80000000u || n_outputs >= 0x80000000u) return SGFHE_ERR_INVALID_ARG;
     const uint64_t n_wires = (uint64_t)n_inputs + 3 * (uint64_t)n_gates;
     if (n_wires >= CIRC_FALSE) return SGFHE_ERR_INVALID_ARG;
+    if (!N.arity) {   // the CSR itself, node by node, before a term of the node is read
+        if (n_gates && (!N.kind || !N.start || !N.weights || N.start[0] != 0)) return SGFHE_ERR_INVALID_ARG;
+        for (size_t g = 0; g < n_gates; g++) {
+            if (N.kind[g] > 1 || N.start[g + 1] < N.start[g]) return SGFHE_ERR_INVALID_ARG;
+            const size_t nj = N.count(g);
+            if (N.kind[g] == 0 ? nj != 2 : (nj < 1 || nj > SGFHE_CIRCUIT_MAX_TERMS)) return SGFHE_ERR_INVALID_ARG;
+            for (size_t i = N.first(g); i < N.first(g) + nj; i++) {
+                const int32_t w = N.weights[i];
+                if (N.kind[g] == 0 ? w != 1 : (w == 0 || w < -2 || w > 2)) return SGFHE_ERR_INVALID_ARG;
+            }
+        }
+    }
     for (size_t g = 0; g < n_gates; g++)
-        for (int j = 0, nj = fan_in(g); j < nj; j++) {
-            const uint32_t id = wire_id(gates[A * g + j]);
+        for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
+            const uint32_t id = wire_id(refs[i]);
             if (id == CIRC_FALSE || id < n_inputs) continue;
             if (id >= n_wires || (id - n_inputs) / 3 >= g) return SGFHE_ERR_INVALID_ARG;   // own or later node
         }
@@ -108,8 +162,8 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         if (id != CIRC_FALSE && id >= n_wires) return SGFHE_ERR_INVALID_ARG;
     }
     for (size_t g = 0; gate_shift && g < n_gates; g++)   // (the shift beside CIRC_NO_INPUT is ignored)
-        for (int j = 0, nj = fan_in(g); j < nj; j++)
-            if (!shift_ok(gate_shift[A * g + j])) return SGFHE_ERR_INVALID_ARG;
+        for (size_t i = N.first(g), end = i + N.count(g); i < end; i++)
+            if (!shift_ok(gate_shift[i])) return SGFHE_ERR_INVALID_ARG;
     for (size_t o = 0; out_shift && o < n_outputs; o++)
         if (!shift_ok(out_shift[o])) return SGFHE_ERR_INVALID_ARG;
     try {
@@ -130,8 +184,8 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         }
         for (uint32_t g = NG; g-- > 0;) {
             if (!live[g]) continue;
-            for (int j = 0, nj = fan_in(g); j < nj; j++) {
-                const int64_t h = node_of(wire_id(gates[A * g + j]));
+            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
+                const int64_t h = node_of(wire_id(refs[i]));
                 if (h >= 0) live[h] = 1;
             }
         }
@@ -140,8 +194,8 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         for (uint32_t g = 0; g < NG; g++) {
             if (!live[g]) continue;
             uint32_t L = 0;
-            for (int j = 0, nj = fan_in(g); j < nj; j++) {
-                const int64_t h = node_of(wire_id(gates[A * g + j]));
+            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
+                const int64_t h = node_of(wire_id(refs[i]));
                 if (h >= 0) L = std::max(L, P.level[h]);
             }
             P.level[g] = L + 1;
@@ -166,8 +220,8 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         constexpr uint32_t UNREAD = 0;   // no wire is read at level 0
         std::vector<uint32_t> last_read((size_t)n_wires, UNREAD);
         for (uint32_t g : P.order)
-            for (int j = 0, nj = fan_in(g); j < nj; j++) {
-                const uint32_t id = wire_id(gates[A * g + j]);
+            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
+                const uint32_t id = wire_id(refs[i]);
                 if (id != CIRC_FALSE) last_read[id] = std::max(last_read[id], P.level[g]);
             }
         for (size_t o = 0; o < n_outputs; o++) {
@@ -197,7 +251,11 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
                     if (last_read[id] != UNREAD) take(id);
                 }
         }
-        // ---- device tables
+        // ---- device tables.  The term a table entry comes from: term j of node g, or none (SIZE_MAX: the constant
+        // FALSE) -- both entries of a wide node, whose terms are in the CSR tables alone
+        auto term_of = [&](size_t g, int j) -> size_t {
+            return N.wide(g) || (size_t)j >= N.count(g) ? SIZE_MAX : N.first(g) + (size_t)j;
+        };
         auto slot_ref = [&](uint32_t ref) -> uint32_t {
             const uint32_t id = wire_id(ref);
             return (id == CIRC_FALSE ? CIRC_FALSE : slot_of[id]) | (ref & CIRC_NOT);
@@ -206,7 +264,10 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         P.out_slot.resize(3 * P.live());
         for (size_t k = 0; k < P.live(); k++) {
             const uint32_t g = P.order[k];
-            for (int j = 0; j < 2; j++) P.in_ref[2 * k + j] = slot_ref(gates[A * g + j]);
+            for (int j = 0; j < 2; j++) {
+                const size_t i = term_of(g, j);
+                P.in_ref[2 * k + j] = i == SIZE_MAX ? CIRC_FALSE : slot_ref(refs[i]);
+            }
             for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
         }
         P.out_ref.resize(n_outputs);
@@ -221,8 +282,8 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         P.in_shift.resize(2 * P.live());
         for (size_t k = 0; k < P.live(); k++)
             for (int j = 0; j < 2; j++) {
-                const size_t i = A * (size_t)P.order[k] + j;
-                P.in_shift[2 * k + j] = shift_of(gates[i], gate_shift, i);
+                const size_t i = term_of(P.order[k], j);
+                P.in_shift[2 * k + j] = i == SIZE_MAX ? 0 : shift_of(refs[i], gate_shift, i);
             }
         P.out_shift.resize(n_outputs);
         for (size_t o = 0; o < n_outputs; o++) P.out_shift[o] = shift_of(outputs[o], out_shift, o);
@@ -235,22 +296,48 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         };
         P.in_row.resize(2 * P.live());
         for (size_t k = 0; k < P.live(); k++)
-            for (int j = 0; j < 2; j++) P.in_row[2 * k + j] = row_ref(gates[A * P.order[k] + j]);
+            for (int j = 0; j < 2; j++) {
+                const size_t i = term_of(P.order[k], j);
+                P.in_row[2 * k + j] = i == SIZE_MAX ? CIRC_FALSE : row_ref(refs[i]);
+            }
         // ---- three-input nodes: the third reference in tables of their own, so that in_ref, in_shift and in_row keep
-        // the layout the two-input kernels read
+        // the layout the two-input kernels read.  Every sum node has one: its third term, or the constant FALSE
         P.in_ref3.assign(P.live(), CIRC_NO_INPUT);
         P.in_shift3.assign(P.live(), 0);
         P.in_row3.assign(P.live(), CIRC_NO_INPUT);
         P.three_before.assign(P.live() + 1, 0);
+        size_t terms = 0;
         for (size_t k = 0; k < P.live(); k++) {
             const size_t g = P.order[k];
-            if (fan_in(g) == 3) {
-                P.in_ref3[k] = slot_ref(gates[3 * g + 2]);
-                P.in_shift3[k] = shift_of(gates[3 * g + 2], gate_shift, 3 * g + 2);
-                P.in_row3[k] = row_ref(gates[3 * g + 2]);
+            if (!N.classic(g)) {
+                const size_t i = term_of(g, 2);
+                P.in_ref3[k] = i == SIZE_MAX ? CIRC_FALSE : slot_ref(refs[i]);
+                P.in_shift3[k] = i == SIZE_MAX ? 0 : shift_of(refs[i], gate_shift, i);
+                P.in_row3[k] = i == SIZE_MAX ? CIRC_FALSE : row_ref(refs[i]);
                 P.three++;
             }
             P.three_before[k + 1] = P.three;
+            P.wide += N.wide(g);
+            terms += N.count(g);
+        }
+        // ---- wide nodes: the terms of every live node as CSR tables of their own
+        if (P.wide) {
+            P.w_start.reserve(P.live() + 1);
+            P.w_ref.reserve(terms);
+            P.w_shift.reserve(terms);
+            P.w_weight.reserve(terms);
+            P.w_row.reserve(terms);
+            for (size_t k = 0; k < P.live(); k++) {
+                const size_t g = P.order[k];
+                P.w_start.push_back((uint32_t)P.w_ref.size());
+                for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
+                    P.w_ref.push_back(slot_ref(refs[i]));
+                    P.w_shift.push_back(shift_of(refs[i], gate_shift, i));
+                    P.w_weight.push_back(N.weight(i));
+                    P.w_row.push_back(row_ref(refs[i]));
+                }
+            }
+            P.w_start.push_back((uint32_t)P.w_ref.size());
         }
         P.out_node.assign(n_outputs, CIRC_NONE);
         P.out_gate.assign(n_outputs, 0);
@@ -258,7 +345,7 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
             const uint32_t id = wire_id(outputs[o]);
             const int64_t g = node_of(id);
             if (g < 0 || P.out_shift[o] != 0) continue;
-            if ((id - n_inputs) % 3 == 2 && fan_in((size_t)g) == 3) continue;   // XOR3: linear over Z_r, no gate row
+            if ((id - n_inputs) % 3 == 2 && !N.classic((size_t)g)) continue;   // XOR3 / LOW: linear over Z_r, no gate row
             P.out_node[o] = rank_of[g];
             P.out_gate[o] = (id - n_inputs) % 3;
         }
@@ -267,6 +354,25 @@ inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, cons
         return SGFHE_ERR_OOM;
     }
     return SGFHE_OK;
+}
+
+// The arrays of sgfhe_circuit_create3 (`arity` 3: gates and gate_shift are [n_gates][3], and a third reference
+// CIRC_NO_INPUT makes the node a two-input node) or of sgfhe_circuit_create_lanes (`arity` 2: [n_gates][2], every node
+// a two-input node).
+inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
+                                  int arity, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
+                                  uint32_t group, CircuitPlan &P) noexcept {
+    const CircuitNodes N = {arity, gates, gate_shift};
+    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
+}
+
+// The arrays of sgfhe_circuit_create_w.
+inline int32_t circuit_plan_w(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
+                              const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                              size_t n_gates, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
+                              uint32_t group, CircuitPlan &P) noexcept {
+    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight};
+    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
 }
 
 // The arrays of sgfhe_circuit_create_lanes.
@@ -296,7 +402,7 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
 // bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances); a lane-shifted input is first
 // laid out as a row of its own, instance by instance (instance t reads bit t + d where its lane allows, 0 elsewhere;
 // `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  A three-input node's rows are MAJ,
-// ONE_OR_TWO (one or two of its inputs true) and XOR3.  SGFHE_ERR_OOM when the table cannot be allocated; nothing
+// ONE_OR_TWO (one or two of its inputs true) and XOR3; a sum node's are HI, MID and LOW of s = sum of w x mod 4.  SGFHE_ERR_OOM when the table cannot be allocated; nothing
 // throws out of it.
 inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * P.live(); }
 inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
@@ -344,6 +450,26 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
     };
     for (size_t k = 0; k < P.live(); k++) {   // `order` is a topological order: inputs are rows filled before
         uint64_t *o = table.data() + ((size_t)P.n_inputs + 3 * k) * wpr;
+        if (P.wsum() && P.in_ref3[k] != CIRC_NO_INPUT) {
+            // a sum node: s = sum of w x mod 4 as two bit planes, (lo, hi) = (o[2 wpr ..], o[0 ..]), term by term
+            // (-1 = 3 and -2 = 2 mod 4); then HI = s in {2, 3} = hi, MID = s in {1, 2} = lo ^ hi, LOW = s mod 2 = lo
+            uint64_t *hi = o, *lo = o + 2 * wpr;
+            for (uint32_t i = P.w_start[k]; i < P.w_start[k + 1]; i++) {
+                const uint64_t *sx = source(P.w_row[i], P.w_shift[i], shifted[0]);
+                const int32_t wt = P.w_weight[i];
+                for (size_t w = 0; w < wpr; w++) {
+                    const uint64_t x = word(sx, P.w_row[i], w);
+                    if (wt & 1) {
+                        hi[w] ^= (lo[w] & x) ^ (wt < 0 ? x : 0ull);
+                        lo[w] ^= x;
+                    } else {
+                        hi[w] ^= x;
+                    }
+                }
+            }
+            for (size_t w = 0; w < wpr; w++) o[wpr + w] = lo[w] ^ hi[w];
+            continue;
+        }
         const uint32_t rx = P.in_row[2 * k], ry = P.in_row[2 * k + 1];
         const uint64_t *sx = source(rx, P.in_shift[2 * k], shifted[0]), *sy = source(ry, P.in_shift[2 * k + 1], shifted[1]);
         const uint32_t rz = P.in_row3[k];

@@ -2948,20 +2948,18 @@ int32_t sgfhe_timing_read(sgfhe_ctx *c, double *stats, int reset) {
 
 // ---- gate circuits (csrc/circuit.h plans) ---------------------------------------
 
-// gates / gate_shift [n_gates][arity]: 2 for sgfhe_circuit_create_lanes, 3 for sgfhe_circuit_create3
-static int32_t circuit_create(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
-                              int arity, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
-                              uint32_t group, sgfhe_circuit **out) {
+// every entry: `N` views its node arrays (csrc/circuit.h).  A refused circuit allocates nothing: the plan is
+// validated into a local first
+static int32_t circuit_create(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
+                              const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out) {
     if (!out) return SGFHE_ERR_INVALID_ARG;
     *out = nullptr;
+    CircuitPlan plan;
+    const int32_t rc = circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, plan);
+    if (rc) return rc;
     sgfhe_circuit *c = new (std::nothrow) sgfhe_circuit();
     if (!c) return SGFHE_ERR_OOM;
-    const int32_t rc = circuit_plan_arity(n_inputs, gates, gate_shift, n_gates, arity, outputs, out_shift, n_outputs,
-                                          group, c->plan);
-    if (rc) {
-        delete c;
-        return rc;
-    }
+    c->plan = std::move(plan);
     *out = c;
     return SGFHE_OK;
 }
@@ -2969,13 +2967,21 @@ static int32_t circuit_create(uint32_t n_inputs, const uint32_t *gates, const in
 int32_t sgfhe_circuit_create_lanes(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                                    const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
                                    sgfhe_circuit **out) {
-    return circuit_create(n_inputs, gates, gate_shift, n_gates, 2, outputs, out_shift, n_outputs, group, out);
+    return circuit_create(n_inputs, {2, gates, gate_shift}, n_gates, outputs, out_shift, n_outputs, group, out);
 }
 
 int32_t sgfhe_circuit_create3(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                               const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
                               sgfhe_circuit **out) {
-    return circuit_create(n_inputs, gates, gate_shift, n_gates, 3, outputs, out_shift, n_outputs, group, out);
+    return circuit_create(n_inputs, {3, gates, gate_shift}, n_gates, outputs, out_shift, n_outputs, group, out);
+}
+
+int32_t sgfhe_circuit_create_w(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
+                               const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                               size_t n_gates, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
+                               uint32_t group, sgfhe_circuit **out) {
+    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight};
+    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
 }
 
 int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
@@ -3046,17 +3052,30 @@ struct CircuitProbe {
 // ciphertexts per pack call of sgfhe_circuit_run_ct
 static size_t circuit_pack_cpc(const sgfhe_ctx *c) { return std::max<size_t>(1, SGFHE_CIRCUIT_CALL_ROWS / c->n); }
 
+// The CSR tables of a plan with wide sum nodes on the device (CircuitPlan::w_start ..): w_start is offset to the
+// level's first node by the caller, the term tables are whole.
+struct CircuitTerms {
+    const uint32_t *start, *ref;
+    const int32_t *shift, *weight;
+};
+
 // The gather of one call (a level's, or a pack call's with the pseudo-level table): rows row0 .. row0 + rows of the
 // level whose node table is `ref`.  A plan with lane groups takes k_circ_gather_lanes with `shift` beside `ref`;
 // every other plan takes k_circ_gather as it always did.  The levels of a plan with three-input nodes pass the third
 // references `ref3` / `shift3` and take k_circ_gather3 (the pack calls of such a plan pass none: their pseudo-level
-// has two-input nodes only).
+// has two-input nodes only); those of a plan with wide sum nodes pass `terms` as well and take k_circ_gather_w.
 static void circuit_gather(const CircuitPlan &P, hipStream_t st, const uint64_t *wires, const uint32_t *ref,
                            const int32_t *shift, uint64_t *a1, uint64_t *b1, uint64_t *a2, uint64_t *b2, uint32_t row0,
                            uint32_t rows, uint32_t inst, uint32_t n, uint64_t r, const uint32_t *ref3 = nullptr,
-                           const int32_t *shift3 = nullptr) {
+                           const int32_t *shift3 = nullptr, const CircuitTerms *terms = nullptr) {
     const dim3 grid((rows * (n + 1) + 255) / 256, 2);
-    if (ref3 && P.lanes())
+    if (terms && P.lanes())
+        hipLaunchKernelGGL(k_circ_gather_w<true>, dim3(grid.x), dim3(256), 0, st, wires, ref3, terms->start, terms->ref,
+                           terms->shift, terms->weight, a1, b1, a2, b2, row0, rows, inst, n, r, P.group);
+    else if (terms)
+        hipLaunchKernelGGL(k_circ_gather_w<false>, dim3(grid.x), dim3(256), 0, st, wires, ref3, terms->start, terms->ref,
+                           terms->shift, terms->weight, a1, b1, a2, b2, row0, rows, inst, n, r, 1u);
+    else if (ref3 && P.lanes())
         hipLaunchKernelGGL(k_circ_gather3<true>, grid, dim3(256), 0, st, wires, ref, shift, ref3, shift3, a1, b1, a2, b2,
                            row0, rows, inst, n, r, P.group);
     else if (ref3)
@@ -3118,7 +3137,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     const size_t ct_tab = ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0;
     const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() + ct_tab + jobs.size() +
                              (P.lanes() ? P.in_shift.size() + 3 * P.out_shift.size() : 0) +
-                             (P.gate3() ? 2 * P.in_ref3.size() : 0);
+                             (P.gate3() ? 2 * P.in_ref3.size() : 0) +
+                             (P.wsum() ? P.w_start.size() + 3 * P.w_ref.size() : 0);
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
     // (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even word offset)
@@ -3164,11 +3184,23 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     uint32_t *d_in_ref3 = nullptr;
     int32_t *d_in_shift3 = nullptr;
     if (P.gate3()) {
-        d_in_ref3 = c->circ_tab.p + tab_words - 2 * P.in_ref3.size();
+        d_in_ref3 = c->circ_tab.p + tab_words - 2 * P.in_ref3.size() - (P.wsum() ? P.w_start.size() + 3 * P.w_ref.size() : 0);
         d_in_shift3 = reinterpret_cast<int32_t *>(d_in_ref3 + P.in_ref3.size());
         HIPCHK(c, hipMemcpyAsync(d_in_ref3, P.in_ref3.data(), P.in_ref3.size() * 4, hipMemcpyHostToDevice, st));
         if (P.lanes())
             HIPCHK(c, hipMemcpyAsync(d_in_shift3, P.in_shift3.data(), P.in_shift3.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    // the terms of every live node (plans with wide sum nodes only), last: w_start, w_ref, w_shift, w_weight
+    CircuitTerms d_terms = {};
+    if (P.wsum()) {
+        const size_t T = P.w_ref.size();
+        uint32_t *d_w_start = c->circ_tab.p + tab_words - P.w_start.size() - 3 * T, *d_w_ref = d_w_start + P.w_start.size();
+        int32_t *d_w_shift = reinterpret_cast<int32_t *>(d_w_ref + T), *d_w_weight = d_w_shift + T;
+        HIPCHK(c, hipMemcpyAsync(d_w_start, P.w_start.data(), P.w_start.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(d_w_ref, P.w_ref.data(), T * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(d_w_shift, P.w_shift.data(), T * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(d_w_weight, P.w_weight.data(), T * 4, hipMemcpyHostToDevice, st));
+        d_terms = {d_w_start, d_w_ref, d_w_shift, d_w_weight};
     }
     std::vector<int32_t> pack_shift;   // (outlives the asynchronous copy: the run ends in a synchronisation)
     if (P.lanes()) {
@@ -3245,9 +3277,10 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         for (uint64_t row0 = 0; row0 < rows_total; row0 += SGFHE_CIRCUIT_CALL_ROWS) {
             const uint32_t rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, rows_total - row0);
             const uint32_t tg = rows * (uint32_t)row;
+            const CircuitTerms level_terms = {P.wsum() ? d_terms.start + k0 : nullptr, d_terms.ref, d_terms.shift, d_terms.weight};
             circuit_gather(P, st, c->circ_wires.p, d_in_ref + 2 * (size_t)k0, d_in_shift + 2 * (size_t)k0, a1, b1, a2, b2,
                            (uint32_t)row0, rows, inst, (uint32_t)n, r, P.gate3() ? d_in_ref3 + k0 : nullptr,
-                           P.gate3() ? d_in_shift3 + k0 : nullptr);
+                           P.gate3() ? d_in_shift3 + k0 : nullptr, P.wsum() ? &level_terms : nullptr);
             HIPCHK(c, hipGetLastError());
             // a call that produces a wire some direct output names leaves its rows un-reduced: the scatter reduces
             // what the wire table takes (the words k_final writes) and copies the named rows into the raw table

@@ -1760,7 +1760,51 @@ k_circ_gather3(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ 
     else b[lr] = v;
 }
 
-// XOR3 of the three-input nodes of a call, after its k-loop and before anything reads its result rows
+// ---- weighted-sum nodes (sgfhe_circuit_create_w) -----------------------------------------------------------------
+// The gather of a plan that holds a sum node with something other than two or three unit weights: the terms of EVERY
+// node of the level as CSR tables (w_start [nodes + 1] into w_ref / w_shift / w_weight), in_ref3 telling the kinds
+// apart.  A classic node (CIRC_REF_NO_INPUT) writes (a1, a2) = (X, Y), its two terms; a sum node writes a1 = U = the
+// sum of w X over its terms mod r and a2 = 0 -- the bootstrap adds its two inputs first, so (U, 0) gives what
+// (X + Y, Z) gives.  One thread per word of a row and BOTH outputs; the node decode and the term range are uniform
+// over a row, every load is a coalesced 8-byte access along a source row.  The sum runs in wrapping uint64 arithmetic
+// with a signed multiply (w in {-2, -1, 1, 2}) and is reduced with one mask: r is a power of two (at most 2^15), so
+// 2^64 is a multiple of it, and 64 terms of weight 2 stay far below 2^64 anyway.
+template <bool LANES>
+__global__ void __launch_bounds__(256)
+k_circ_gather_w(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref3,
+                const uint32_t *__restrict__ w_start, const uint32_t *__restrict__ w_ref,
+                const int32_t *__restrict__ w_shift, const int32_t *__restrict__ w_weight, uint64_t *__restrict__ a1,
+                uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
+                uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * (n + 1)) return;
+    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
+    const uint32_t rank = R / instances, inst = R % instances;
+    auto read = [&](uint32_t i) -> uint64_t {
+        const uint32_t ref = w_ref[i];
+        if (LANES) return circ_word_lane(wires, ref, w_shift[i], group, instances, inst, e, n, r);
+        return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    };
+    const uint32_t t0 = w_start[rank], t1 = w_start[rank + 1];
+    uint64_t u = 0, v = 0;
+    if (in_ref3[rank] == CIRC_REF_NO_INPUT) {
+        u = read(t0);
+        v = read(t0 + 1);
+    } else {
+        for (uint32_t i = t0; i < t1; i++) u += (uint64_t)((int64_t)w_weight[i] * (int64_t)read(i));
+        u &= r - 1;
+    }
+    if (e < n) {
+        a1[(size_t)lr * n + e] = u;
+        a2[(size_t)lr * n + e] = v;
+    } else {
+        b1[lr] = u;
+        b2[lr] = v;
+    }
+}
+
+// XOR3 of the three-input nodes of a call (LOW of its sum nodes: any in_ref3 but CIRC_REF_NO_INPUT marks them), after
+// its k-loop and before anything reads its result rows
 // [rows][3][n + 1]: row 2 = a1 + a2 - 2 row 0 mod r, word by word, b included -- a1 + a2 is X + Y + Z as the bootstrap
 // consumed it (the staging is not written between the gather and here), row 0 the reduced MAJ.  The rows of two-input
 // nodes are left alone.  One thread per word, as the gather.

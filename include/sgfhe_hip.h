@@ -476,7 +476,8 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * outputs, or with the NOT bit -- is SGFHE_ERR_INVALID_ARG (it is no wire id: ids are below 2^31 - 2).
  * With X, Y, Z the three referenced LWEs at one instance (lane shift, constant fill and NOT applied as above), the
  * node is ONE row of its level call -- pruning, levels, slots, row and call numbering and the draws are those of a
- * two-input node -- whose bootstrap inputs are (a1, b1) = X + Y mod r and (a2, b2) = Z.  The bootstrap rotates the
+ * two-input node -- whose bootstrap inputs are (a1, b1) = X + Y + Z mod r and (a2, b2) = 0; the bootstrap adds its two
+ * inputs first, so this is bootstrap(X + Y mod r, Z) byte for byte.  The bootstrap rotates the
  * test polynomial by the phase of the sum of its inputs, here near s Dr, s = x + y + z in {0, 1, 2, 3}: four distinct
  * values mod r = 4 Dr, each Dr/2 from the nearest sign change, as for two inputs.  Wires of the node:
  *   n_inputs + 3 g + 0  MAJ         the AND row: 0, 0, 1, 1 for s = 0 .. 3
@@ -520,17 +521,15 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  *   n_inputs + 3 g + 1  MID  the OR row:  s in {1, 2}
  *   n_inputs + 3 g + 2  LOW  (U - 2 HI) mod r, word by word, b included, HI being the reduced row (the words k_final
  *                            gives): s mod 2.  Linear, not bootstrapped -- what XOR3 is for a three-input node.
- * So weights (1, 1, 1) are the three-input node (the same bytes on all three wires, and a plan whose sum nodes all
- * have two or three unit weights runs the kernels of the sgfhe_circuit_create3 plan: two unit terms are (x, y,
+ * So weights (1, 1, 1) are the three-input node (the same bytes on all three wires; two unit terms are (x, y,
  * FALSE)); all weights 2 give HI = the XOR of all terms, ONE bootstrap for a parity of up to 64 wires -- a doubled
  * wire encodes its bit as 0 or 2 Dr = r / 2, and sums of those are XORs; one term of weight 1 gives MID = a refresh
  * of that wire; 2x + y + z gives HI = s >= 2 and MID = s in {1, 2} for s = 0 .. 3 (s = 4 wraps to 0).
  * Validation: everything sgfhe_circuit_create3 checks, and node_start non-decreasing from 0, node_kind 0 or 1, the
  * term counts and weights above; SGFHE_CIRCUIT_NONE never appears.  Anything else is SGFHE_ERR_INVALID_ARG with
  * *out NULL, and nothing is allocated.  A NULL term_shift is all 0.
- * Every run entry point takes such a plan.  A plan with a sum node of something other than two or three unit weights
- * gathers its level calls with k_circ_gather_w (one pass over the node's terms per word); every other plan runs the
- * kernels it ran.  Under SGFHE_CIRCUIT_PACK_DIRECT an output naming HI or MID with shift 0 is DIRECT; one naming LOW
+ * Every run entry point takes such a plan, and every plan, whichever entry made it, is gathered by the one
+ * k_circ_gather (one pass over the node's terms per word).  Under SGFHE_CIRCUIT_PACK_DIRECT an output naming HI or MID with shift 0 is DIRECT; one naming LOW
  * is REFRESHED (LIFTED under SGFHE_CIRCUIT_PACK_LIFT), as XOR3 is.  The probe's plaintext evaluation knows the three
  * wires; the record of a LOW wire is, up to 2 e_HI, the error of the node's input sum.
  * Noise -- a MEASURED rule, as for three inputs.  A node is correct while |sum of w_i e_i| < Dr/2, and LOW carries

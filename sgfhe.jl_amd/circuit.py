@@ -760,14 +760,7 @@ def evaluate_circuit(bkey, rng, circuit, inputs):
     n = bkey.params.n
     as_bits = not isinstance(inputs, np.ndarray)
     if as_bits:
-        arr = np.zeros((circuit.n_inputs, len(inputs[0]) if circuit.n_inputs else 0, n + 1), dtype=np.uint64)
-        for i, row in enumerate(inputs):
-            if len(row) != arr.shape[1]:
-                raise ValueError("ragged inputs: every input needs one EncryptedBit per instance")
-            for t, e in enumerate(row):
-                arr[i, t, :n] = e.lwe.a
-                arr[i, t, n] = e.lwe.b
-        inputs = arr
+        inputs = _input_array(circuit, inputs, n)
     with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
         _set_flatten_mode(bkey, rng)
         out = bkey.engine.circuit_run(circuit, inputs)

@@ -1,7 +1,8 @@
 // Host-side planner of sgfhe_circuit_* (include/sgfhe_hip.h): validates a gate
 // graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
-// slot of the device wire table by liveness, and fixes the row and call numbering of a run; circuit_plain_bits
-// evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp,
+// slot of the device wire table by liveness, fixes the row and call numbering of a run, and writes every node's inputs
+// -- whichever entry the arrays came through -- into one CSR node table, which it lays with the other device tables
+// into the one image a run uploads; circuit_plain_bits evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp,
 // circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp, circuit_gate3_sanitized.cpp and circuit_wsum_sanitized.cpp
 // drive it under ASan / UBSan on the CPU.
 #pragma once
@@ -13,6 +14,7 @@
 #include <functional>
 #include <new>
 #include <queue>
+#include <stdexcept>
 #include <vector>
 
 #include "../../include/sgfhe_hip.h"
@@ -26,6 +28,12 @@ constexpr uint32_t CIRC_NOT = SGFHE_CIRCUIT_NOT;
 constexpr uint32_t CIRC_NONE = 0xFFFFFFFFu;     // out_slot of a gate output nothing reads
 constexpr uint32_t CIRC_NO_INPUT = SGFHE_CIRCUIT_NONE;   // third reference of a two-input node (never a wire id)
 
+// Word offsets of the device tables in CircuitPlan::image (int32_t tables by bit pattern); `words` is its length.
+struct CircuitImage {
+    uint32_t node_kind = 0, term_start = 0, term_ref = 0, term_shift = 0, term_weight = 0;
+    uint32_t out_slot = 0, out_ref = 0, out_shift = 0, input_slot = 0, jobs = 0, words = 0;
+};
+
 struct CircuitPlan {
     uint32_t n_inputs = 0, n_gates = 0, n_outputs = 0;
     uint32_t levels = 0, widest = 0, slots = 0;
@@ -35,54 +43,42 @@ struct CircuitPlan {
     std::vector<uint32_t> level_start;  // [levels + 2]: level L's nodes are order[level_start[L] .. level_start[L + 1])
                                         // (level 0 holds none: level_start[0] == level_start[1] == 0)
     std::vector<uint32_t> input_slot;   // [n_inputs]: slot of every input wire, CIRC_NONE if nothing reads it
-    // Device tables, one entry per live node in `order`, uploaded once per run:
-    std::vector<uint32_t> in_ref;       // [live][2]: the node's inputs as slot references (CIRC_NOT, CIRC_FALSE)
-    std::vector<uint32_t> out_slot;     // [live][3]: slot of its AND / OR / XOR wire, CIRC_NONE if unread
-                                        // (MAJ / ONE_OR_TWO / XOR3 of a three-input node)
+    // The node table: one CSR over the live nodes in `order`, then the n_outputs nodes of the pack stage's
+    // pseudo-level (node live() + o is the classic node (TRUE, output o)).  A term is a slot reference (CIRC_NOT,
+    // CIRC_FALSE), a lane shift -- the term reads instance t + d of its slot where 0 <= t % group + d < group, the
+    // constant FALSE elsewhere; 0 on every reference to the constant -- and a weight.  A three-input node is the sum
+    // node of its three unit weights.
+    std::vector<uint32_t> node_kind;    // [live + n_outputs]: 0 classic (two unit terms), 1 sum node
+    std::vector<uint32_t> term_start;   // [live + n_outputs + 1]: node k's terms are term_start[k] .. term_start[k + 1]
+    std::vector<uint32_t> term_ref;     // [terms + 2 n_outputs]
+    std::vector<int32_t> term_shift;    // [terms + 2 n_outputs]
+    std::vector<int32_t> term_weight;   // [terms + 2 n_outputs]: -2, -1, 1, 2
+    std::vector<uint32_t> out_slot;     // [live][3]: slot of the node's AND / OR / XOR wire, CIRC_NONE if unread
+                                        // (HI / MID / LOW of a sum node)
     std::vector<uint32_t> out_ref;      // [n_outputs]: the circuit's outputs as slot references
-    // Lane shifts, beside in_ref / out_ref (uploaded when lanes()): the reference reads instance t + d of its slot
-    // where 0 <= t % group + d < group, the constant FALSE elsewhere; 0 on every reference to the constant
-    std::vector<int32_t> in_shift;      // [live][2]
     std::vector<int32_t> out_shift;     // [n_outputs]
-    // Three-input nodes (sgfhe_circuit_create3), beside in_ref / in_shift / in_row and uploaded when three > 0: the
-    // third reference of every live node, CIRC_NO_INPUT for a two-input node (its shift and probe row are then 0 and
-    // CIRC_NO_INPUT)
-    uint32_t three = 0;                 // live three-input nodes
-    std::vector<uint32_t> in_ref3;      // [live]
-    std::vector<int32_t> in_shift3;     // [live]
-    std::vector<uint32_t> in_row3;      // [live]
-    std::vector<uint32_t> three_before; // [live + 1]: three-input nodes among order[0 .. k)
-    // Weighted-sum nodes (sgfhe_circuit_create_w).  A sum node of two or three unit weights IS a three-input node
-    // (x, y, FALSE) or (x, y, z) and is planned as one.  Every other sum node is a WIDE node: in_ref / in_shift /
-    // in_row name the constant FALSE twice and in_ref3 names it once -- any reference but CIRC_NO_INPUT marks the
-    // node for the XOR3 kernels, which compute its LOW wire -- and its terms are in the CSR tables below.  Those
-    // exist when wide > 0 and then cover EVERY live node, a classic or three-input one with its two or three unit
-    // terms, so that one gather (k_circ_gather_w) serves a whole level.
-    uint32_t wide = 0;                  // live wide nodes
-    std::vector<uint32_t> w_start;      // [live + 1]: node k's terms are w_ref[w_start[k] .. w_start[k + 1])
-    std::vector<uint32_t> w_ref;        // [terms]: slot references
-    std::vector<int32_t> w_shift;       // [terms]
-    std::vector<int32_t> w_weight;      // [terms]: -2, -1, 1, 2
-    std::vector<uint32_t> w_row;        // [terms], host only: the terms as probe rows (as in_row)
-    // Host only (SGFHE_CIRCUIT_PACK_DIRECT): where an output that names a gate wire is produced
-    std::vector<uint32_t> out_node;     // [n_outputs]: index in `order` of the producing node, CIRC_NONE for an input
-                                        // wire, the constant, a lane-shifted reference or the XOR3 wire of a
-                                        // three-input node (the LOW wire of a sum node), which is no gate row over
-                                        // Z_Q (those are refreshed)
-    std::vector<uint32_t> out_gate;     // [n_outputs]: 0 AND, 1 OR, 2 XOR (0 where out_node is CIRC_NONE)
-    // Host only (sgfhe_circuit_run_probe): the node's inputs as PROBE ROWS -- row i < n_inputs is input wire i, row
+    // SGFHE_CIRCUIT_PACK_DIRECT: where an output that names a gate wire is produced
+    std::vector<uint32_t> out_node;     // [n_outputs], host only: index in `order` of the producing node, CIRC_NONE for
+                                        // an input wire, the constant, a lane-shifted reference or the LOW wire of a sum
+                                        // node, which is no gate row over Z_Q (those are refreshed)
+    std::vector<uint32_t> out_gate;     // [n_outputs], host only: 0 AND, 1 OR, 2 XOR (0 where out_node is CIRC_NONE)
+    // the direct outputs by producing node (ascending index in `order`, so the jobs of one level call are a run of the
+    // table): job = {output, rank of the node in its level, gate | CIRC_NOT of the output}
+    std::vector<uint32_t> jobs;         // [direct outputs][3]
+    std::vector<uint32_t> job_k;        // [direct outputs], host only: the producing node's index in `order`
+    // Host only (sgfhe_circuit_run_probe): the live nodes' terms as PROBE ROWS -- row i < n_inputs is input wire i, row
     // n_inputs + 3 k + w is wire w of the k-th live node in `order` -- with CIRC_NOT and CIRC_FALSE as in a reference
-    std::vector<uint32_t> in_row;       // [live][2]
+    std::vector<uint32_t> term_row;     // [terms]
+    std::vector<uint32_t> sum_before;   // [live + 1], host only: sum nodes among order[0 .. k)
+    // Every device table above in one array, uploaded once per run: node_kind, term_start, term_ref, term_shift,
+    // term_weight, out_slot, out_ref, out_shift, input_slot, jobs, each at its offset `at`
+    std::vector<uint32_t> image;
+    CircuitImage at;
 
     size_t live() const { return order.size(); }
-    // the run takes the lane kernels (group 1 admits no shift but 0)
-    bool lanes() const { return group > 1; }
-    // the run takes the three-reference gather and the XOR3 kernels
-    bool gate3() const { return three > 0; }
-    // the levels of the run take the CSR gather
-    bool wsum() const { return wide > 0; }
-    // live nodes order[ka .. kb] hold a three-input node
-    bool gate3_in(uint32_t ka, uint32_t kb) const { return three && three_before[kb + 1] != three_before[ka]; }
+    bool lanes() const { return group > 1; }   // (group 1 admits no shift but 0)
+    // live nodes order[ka .. kb] hold a sum node: the call takes an XOR3 kernel for its LOW rows
+    bool gate3_in(uint32_t ka, uint32_t kb) const { return sum_before[kb + 1] != sum_before[ka]; }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
     uint64_t level_rows(uint32_t L, uint64_t instances) const {
         return (uint64_t)(level_start[L + 1] - level_start[L]) * instances;
@@ -112,15 +108,6 @@ struct CircuitNodes {
     }
     bool classic(size_t g) const { return arity ? count(g) == 2 : kind[g] == 0; }
     int32_t weight(size_t i) const { return weights ? weights[i] : 1; }
-    // a sum node that is no three-input node: something other than two or three unit weights
-    bool wide(size_t g) const {
-        if (classic(g)) return false;
-        const size_t n = count(g);
-        if (n != 2 && n != 3) return true;
-        for (size_t i = first(g); i < first(g) + n; i++)
-            if (weight(i) != 1) return true;
-        return false;
-    }
 };
 
 // Builds `P` from the nodes `N` (gate shifts / out_shift NULL: all 0).  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
@@ -251,42 +238,17 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
                     if (last_read[id] != UNREAD) take(id);
                 }
         }
-        // ---- device tables.  The term a table entry comes from: term j of node g, or none (SIZE_MAX: the constant
-        // FALSE) -- both entries of a wide node, whose terms are in the CSR tables alone
-        auto term_of = [&](size_t g, int j) -> size_t {
-            return N.wide(g) || (size_t)j >= N.count(g) ? SIZE_MAX : N.first(g) + (size_t)j;
-        };
+        // ---- the node table: every live node's terms in the caller's order.  A shifted reference reads other ROWS of
+        // the slot it names, nothing else: the wire is of an earlier level (or an input), so all its rows are written
+        // before the reading level's first call in stream order, and its slot is held until the last level that reads
+        // the wire ends, whichever instance is read.  The slot rule above therefore needs no change.
         auto slot_ref = [&](uint32_t ref) -> uint32_t {
             const uint32_t id = wire_id(ref);
             return (id == CIRC_FALSE ? CIRC_FALSE : slot_of[id]) | (ref & CIRC_NOT);
         };
-        P.in_ref.resize(2 * P.live());
-        P.out_slot.resize(3 * P.live());
-        for (size_t k = 0; k < P.live(); k++) {
-            const uint32_t g = P.order[k];
-            for (int j = 0; j < 2; j++) {
-                const size_t i = term_of(g, j);
-                P.in_ref[2 * k + j] = i == SIZE_MAX ? CIRC_FALSE : slot_ref(refs[i]);
-            }
-            for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
-        }
-        P.out_ref.resize(n_outputs);
-        for (size_t o = 0; o < n_outputs; o++) P.out_ref[o] = slot_ref(outputs[o]);
-        // ---- lane shifts.  A shifted reference reads other ROWS of the slot it names, nothing else: the wire is of
-        // an earlier level (or an input), so all its rows are written before the reading level's first call in stream
-        // order, and its slot is held until the last level that reads the wire ends, whichever instance is read.  The
-        // slot rule above therefore needs no change.
         auto shift_of = [&](uint32_t ref, const int32_t *tab, size_t i) -> int32_t {
             return tab && wire_id(ref) != CIRC_FALSE ? tab[i] : 0;
         };
-        P.in_shift.resize(2 * P.live());
-        for (size_t k = 0; k < P.live(); k++)
-            for (int j = 0; j < 2; j++) {
-                const size_t i = term_of(P.order[k], j);
-                P.in_shift[2 * k + j] = i == SIZE_MAX ? 0 : shift_of(refs[i], gate_shift, i);
-            }
-        P.out_shift.resize(n_outputs);
-        for (size_t o = 0; o < n_outputs; o++) P.out_shift[o] = shift_of(outputs[o], out_shift, o);
         std::vector<uint32_t> rank_of(NG, CIRC_NONE);   // node -> index in `order`
         for (size_t k = 0; k < P.live(); k++) rank_of[P.order[k]] = (uint32_t)k;
         auto row_ref = [&](uint32_t ref) -> uint32_t {
@@ -294,61 +256,77 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             const int64_t g = node_of(id);
             return (g < 0 ? id : n_inputs + 3 * rank_of[g] + (id - n_inputs) % 3) | (ref & CIRC_NOT);
         };
-        P.in_row.resize(2 * P.live());
-        for (size_t k = 0; k < P.live(); k++)
-            for (int j = 0; j < 2; j++) {
-                const size_t i = term_of(P.order[k], j);
-                P.in_row[2 * k + j] = i == SIZE_MAX ? CIRC_FALSE : row_ref(refs[i]);
-            }
-        // ---- three-input nodes: the third reference in tables of their own, so that in_ref, in_shift and in_row keep
-        // the layout the two-input kernels read.  Every sum node has one: its third term, or the constant FALSE
-        P.in_ref3.assign(P.live(), CIRC_NO_INPUT);
-        P.in_shift3.assign(P.live(), 0);
-        P.in_row3.assign(P.live(), CIRC_NO_INPUT);
-        P.three_before.assign(P.live() + 1, 0);
-        size_t terms = 0;
+        auto term = [&](uint32_t ref, int32_t shift, int32_t weight) {
+            P.term_ref.push_back(ref);
+            P.term_shift.push_back(shift);
+            P.term_weight.push_back(weight);
+        };
+        P.out_slot.resize(3 * P.live());
+        P.sum_before.assign(P.live() + 1, 0);
         for (size_t k = 0; k < P.live(); k++) {
             const size_t g = P.order[k];
-            if (!N.classic(g)) {
-                const size_t i = term_of(g, 2);
-                P.in_ref3[k] = i == SIZE_MAX ? CIRC_FALSE : slot_ref(refs[i]);
-                P.in_shift3[k] = i == SIZE_MAX ? 0 : shift_of(refs[i], gate_shift, i);
-                P.in_row3[k] = i == SIZE_MAX ? CIRC_FALSE : row_ref(refs[i]);
-                P.three++;
+            P.node_kind.push_back(N.classic(g) ? 0u : 1u);
+            P.term_start.push_back((uint32_t)P.term_ref.size());
+            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
+                term(slot_ref(refs[i]), shift_of(refs[i], gate_shift, i), N.weight(i));
+                P.term_row.push_back(row_ref(refs[i]));
             }
-            P.three_before[k + 1] = P.three;
-            P.wide += N.wide(g);
-            terms += N.count(g);
+            for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
+            P.sum_before[k + 1] = P.sum_before[k] + P.node_kind[k];
         }
-        // ---- wide nodes: the terms of every live node as CSR tables of their own
-        if (P.wide) {
-            P.w_start.reserve(P.live() + 1);
-            P.w_ref.reserve(terms);
-            P.w_shift.reserve(terms);
-            P.w_weight.reserve(terms);
-            P.w_row.reserve(terms);
-            for (size_t k = 0; k < P.live(); k++) {
-                const size_t g = P.order[k];
-                P.w_start.push_back((uint32_t)P.w_ref.size());
-                for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
-                    P.w_ref.push_back(slot_ref(refs[i]));
-                    P.w_shift.push_back(shift_of(refs[i], gate_shift, i));
-                    P.w_weight.push_back(N.weight(i));
-                    P.w_row.push_back(row_ref(refs[i]));
-                }
-            }
-            P.w_start.push_back((uint32_t)P.w_ref.size());
-        }
+        // ---- outputs, and the pack stage's pseudo-level: node live() + o is (TRUE, output o), the pair of
+        // fhe.jl:669-673
+        P.out_ref.resize(n_outputs);
+        P.out_shift.resize(n_outputs);
         P.out_node.assign(n_outputs, CIRC_NONE);
         P.out_gate.assign(n_outputs, 0);
         for (size_t o = 0; o < n_outputs; o++) {
+            P.out_ref[o] = slot_ref(outputs[o]);
+            P.out_shift[o] = shift_of(outputs[o], out_shift, o);
+            P.node_kind.push_back(0u);
+            P.term_start.push_back((uint32_t)P.term_ref.size());
+            term(CIRC_FALSE | CIRC_NOT, 0, 1);
+            term(P.out_ref[o], P.out_shift[o], 1);
             const uint32_t id = wire_id(outputs[o]);
             const int64_t g = node_of(id);
             if (g < 0 || P.out_shift[o] != 0) continue;
-            if ((id - n_inputs) % 3 == 2 && !N.classic((size_t)g)) continue;   // XOR3 / LOW: linear over Z_r, no gate row
+            if ((id - n_inputs) % 3 == 2 && !N.classic((size_t)g)) continue;   // LOW: linear over Z_r, no gate row
             P.out_node[o] = rank_of[g];
             P.out_gate[o] = (id - n_inputs) % 3;
         }
+        P.term_start.push_back((uint32_t)P.term_ref.size());
+        // ---- the direct-pack jobs, by producing node
+        std::vector<uint32_t> byk;
+        for (uint32_t o = 0; o < n_outputs; o++)
+            if (P.out_node[o] != CIRC_NONE) byk.push_back(o);
+        std::sort(byk.begin(), byk.end(), [&](uint32_t x, uint32_t y) {   // (outputs of one node in ascending index)
+            return P.out_node[x] != P.out_node[y] ? P.out_node[x] < P.out_node[y] : x < y;
+        });
+        for (uint32_t o : byk) {
+            const uint32_t k = P.out_node[o], L = P.level[P.order[k]];
+            P.job_k.push_back(k);
+            P.jobs.insert(P.jobs.end(), {o, k - P.level_start[L], P.out_gate[o] | (P.out_ref[o] & CIRC_NOT)});
+        }
+        // ---- the image of the device tables
+        auto place = [&](const auto &tab) -> uint32_t {
+            const size_t at = P.image.size();
+            if (at + tab.size() >= 0x100000000ull) throw std::length_error("circuit image");
+            for (auto v : tab) P.image.push_back((uint32_t)v);
+            return (uint32_t)at;
+        };
+        P.image.reserve(P.node_kind.size() + P.term_start.size() + 3 * P.term_ref.size() + P.out_slot.size() +
+                        2 * n_outputs + n_inputs + P.jobs.size());
+        P.at.node_kind = place(P.node_kind);
+        P.at.term_start = place(P.term_start);
+        P.at.term_ref = place(P.term_ref);
+        P.at.term_shift = place(P.term_shift);
+        P.at.term_weight = place(P.term_weight);
+        P.at.out_slot = place(P.out_slot);
+        P.at.out_ref = place(P.out_ref);
+        P.at.out_shift = place(P.out_shift);
+        P.at.input_slot = place(P.input_slot);
+        P.at.jobs = place(P.jobs);
+        P.at.words = (uint32_t)P.image.size();
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
         P = CircuitPlan();
         return SGFHE_ERR_OOM;
@@ -401,12 +379,12 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
 // is instance t (the bits past `instances` in a row's last word are unspecified).  in_bits [n_inputs][instances],
 // bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances); a lane-shifted input is first
 // laid out as a row of its own, instance by instance (instance t reads bit t + d where its lane allows, 0 elsewhere;
-// `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  A three-input node's rows are MAJ,
-// ONE_OR_TWO (one or two of its inputs true) and XOR3; a sum node's are HI, MID and LOW of s = sum of w x mod 4.  SGFHE_ERR_OOM when the table cannot be allocated; nothing
-// throws out of it.
+// `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  A sum node's rows are HI, MID and LOW
+// of s = sum of w x mod 4: MAJ, ONE_OR_TWO (one or two of its inputs true) and XOR3 of a three-input node.
+// SGFHE_ERR_OOM when the table cannot be allocated; nothing throws out of it.
 inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * P.live(); }
 inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
-// wire id of a probe row (the inverse of CircuitPlan::in_row's numbering)
+// wire id of a probe row (the inverse of CircuitPlan::term_row's numbering)
 inline uint32_t circuit_probe_wire(const CircuitPlan &P, size_t row) {
     if (row < P.n_inputs) return (uint32_t)row;
     const size_t k = (row - P.n_inputs) / 3, w = (row - P.n_inputs) % 3;
@@ -417,7 +395,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
     if (!in_bits && P.n_inputs && instances) return SGFHE_ERR_INVALID_ARG;
     if (instances % P.group) return SGFHE_ERR_INVALID_ARG;
     const size_t wpr = circuit_bit_words(instances);
-    std::vector<uint64_t> shifted[3];
+    std::vector<uint64_t> shifted[2];
     try {
         table.assign(circuit_probe_rows(P) * wpr, 0);
         if (P.lanes())
@@ -450,15 +428,17 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
     };
     for (size_t k = 0; k < P.live(); k++) {   // `order` is a topological order: inputs are rows filled before
         uint64_t *o = table.data() + ((size_t)P.n_inputs + 3 * k) * wpr;
-        if (P.wsum() && P.in_ref3[k] != CIRC_NO_INPUT) {
+        const uint32_t t0 = P.term_start[k], t1 = P.term_start[k + 1];
+        if (P.node_kind[k]) {
             // a sum node: s = sum of w x mod 4 as two bit planes, (lo, hi) = (o[2 wpr ..], o[0 ..]), term by term
             // (-1 = 3 and -2 = 2 mod 4); then HI = s in {2, 3} = hi, MID = s in {1, 2} = lo ^ hi, LOW = s mod 2 = lo
+            // (of three unit weights: MAJ, ONE_OR_TWO, XOR3)
             uint64_t *hi = o, *lo = o + 2 * wpr;
-            for (uint32_t i = P.w_start[k]; i < P.w_start[k + 1]; i++) {
-                const uint64_t *sx = source(P.w_row[i], P.w_shift[i], shifted[0]);
-                const int32_t wt = P.w_weight[i];
+            for (uint32_t i = t0; i < t1; i++) {
+                const uint64_t *sx = source(P.term_row[i], P.term_shift[i], shifted[0]);
+                const int32_t wt = P.term_weight[i];
                 for (size_t w = 0; w < wpr; w++) {
-                    const uint64_t x = word(sx, P.w_row[i], w);
+                    const uint64_t x = word(sx, P.term_row[i], w);
                     if (wt & 1) {
                         hi[w] ^= (lo[w] & x) ^ (wt < 0 ? x : 0ull);
                         lo[w] ^= x;
@@ -470,19 +450,8 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
             for (size_t w = 0; w < wpr; w++) o[wpr + w] = lo[w] ^ hi[w];
             continue;
         }
-        const uint32_t rx = P.in_row[2 * k], ry = P.in_row[2 * k + 1];
-        const uint64_t *sx = source(rx, P.in_shift[2 * k], shifted[0]), *sy = source(ry, P.in_shift[2 * k + 1], shifted[1]);
-        const uint32_t rz = P.in_row3[k];
-        if (rz != CIRC_NO_INPUT) {
-            const uint64_t *sz = source(rz, P.in_shift3[k], shifted[2]);
-            for (size_t w = 0; w < wpr; w++) {
-                const uint64_t x = word(sx, rx, w), y = word(sy, ry, w), z = word(sz, rz, w);
-                o[w] = (x & y) | (z & (x | y));
-                o[wpr + w] = (x | y | z) & ~(x & y & z);
-                o[2 * wpr + w] = x ^ y ^ z;
-            }
-            continue;
-        }
+        const uint32_t rx = P.term_row[t0], ry = P.term_row[t0 + 1];
+        const uint64_t *sx = source(rx, P.term_shift[t0], shifted[0]), *sy = source(ry, P.term_shift[t0 + 1], shifted[1]);
         for (size_t w = 0; w < wpr; w++) {
             const uint64_t x = word(sx, rx, w), y = word(sy, ry, w);
             o[w] = x & y;

@@ -3052,40 +3052,13 @@ struct CircuitProbe {
 // ciphertexts per pack call of sgfhe_circuit_run_ct
 static size_t circuit_pack_cpc(const sgfhe_ctx *c) { return std::max<size_t>(1, SGFHE_CIRCUIT_CALL_ROWS / c->n); }
 
-// The CSR tables of a plan with wide sum nodes on the device (CircuitPlan::w_start ..): w_start is offset to the
-// level's first node by the caller, the term tables are whole.
-struct CircuitTerms {
-    const uint32_t *start, *ref;
-    const int32_t *shift, *weight;
-};
-
-// The gather of one call (a level's, or a pack call's with the pseudo-level table): rows row0 .. row0 + rows of the
-// level whose node table is `ref`.  A plan with lane groups takes k_circ_gather_lanes with `shift` beside `ref`;
-// every other plan takes k_circ_gather as it always did.  The levels of a plan with three-input nodes pass the third
-// references `ref3` / `shift3` and take k_circ_gather3 (the pack calls of such a plan pass none: their pseudo-level
-// has two-input nodes only); those of a plan with wide sum nodes pass `terms` as well and take k_circ_gather_w.
-static void circuit_gather(const CircuitPlan &P, hipStream_t st, const uint64_t *wires, const uint32_t *ref,
-                           const int32_t *shift, uint64_t *a1, uint64_t *b1, uint64_t *a2, uint64_t *b2, uint32_t row0,
-                           uint32_t rows, uint32_t inst, uint32_t n, uint64_t r, const uint32_t *ref3 = nullptr,
-                           const int32_t *shift3 = nullptr, const CircuitTerms *terms = nullptr) {
-    const dim3 grid((rows * (n + 1) + 255) / 256, 2);
-    if (terms && P.lanes())
-        hipLaunchKernelGGL(k_circ_gather_w<true>, dim3(grid.x), dim3(256), 0, st, wires, ref3, terms->start, terms->ref,
-                           terms->shift, terms->weight, a1, b1, a2, b2, row0, rows, inst, n, r, P.group);
-    else if (terms)
-        hipLaunchKernelGGL(k_circ_gather_w<false>, dim3(grid.x), dim3(256), 0, st, wires, ref3, terms->start, terms->ref,
-                           terms->shift, terms->weight, a1, b1, a2, b2, row0, rows, inst, n, r, 1u);
-    else if (ref3 && P.lanes())
-        hipLaunchKernelGGL(k_circ_gather3<true>, grid, dim3(256), 0, st, wires, ref, shift, ref3, shift3, a1, b1, a2, b2,
-                           row0, rows, inst, n, r, P.group);
-    else if (ref3)
-        hipLaunchKernelGGL(k_circ_gather3<false>, grid, dim3(256), 0, st, wires, ref, (const int32_t *)nullptr, ref3,
-                           (const int32_t *)nullptr, a1, b1, a2, b2, row0, rows, inst, n, r, 1u);
-    else if (P.lanes())
-        hipLaunchKernelGGL(k_circ_gather_lanes, grid, dim3(256), 0, st, wires, ref, shift, a1, b1, a2, b2, row0, rows,
-                           inst, n, r, P.group);
-    else
-        hipLaunchKernelGGL(k_circ_gather, grid, dim3(256), 0, st, wires, ref, a1, b1, a2, b2, row0, rows, inst, n, r);
+// The gather of one call: rows row0 .. row0 + rows of the level whose first node is `node0` of the plan's node table
+// (a level's first node, or live() for the pack stage's pseudo-level).
+static void circuit_gather(const CircuitPlan &P, hipStream_t st, const uint64_t *wires, const CircNodes &nodes,
+                           uint32_t node0, uint64_t *a1, uint64_t *b1, uint64_t *a2, uint64_t *b2, uint32_t row0,
+                           uint32_t rows, uint32_t inst, uint32_t n, uint64_t r) {
+    hipLaunchKernelGGL(k_circ_gather, dim3((rows * (n + 1) + 255) / 256), dim3(256), 0, st, wires, nodes, node0, a1, b1,
+                       a2, b2, row0, rows, inst, n, r, P.group);
 }
 
 // `in` / `out`: the LWE form ([wire][instances][n + 1]); with `ct` the inputs come from ct->in_a / in_b instead and
@@ -3107,25 +3080,14 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     const size_t n_ct = pack ? (size_t)P.n_outputs * ct->blocks : 0;   // ciphertext q = output * blocks + block
     const size_t cpc = std::min(circuit_pack_cpc(c), n_ct);             // ciphertexts of the largest pack call
     const size_t ct_words = ct ? (size_t)P.n_inputs * ct->blocks * ct->N : 0;
-    // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire, by producing node (ascending index in `order`,
-    // so the jobs of one level call are a run of the table): job = {output, rank of the node in its level,
-    // gate | CIRC_NOT}; and the most refreshed ciphertexts any pack group has
+    // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire are the plan's jobs; the most refreshed ciphertexts
+    // any pack group has
     // SGFHE_CIRCUIT_PACK_LIFT: the same direct outputs; every other ciphertext is lifted from the wire table into the
     // raw table (k_circ_lift), so no group has a refreshed one
     const bool lift = pack && ct->direct && ct->lift;
     const bool direct = pack && ct->direct;
-    std::vector<uint32_t> jobs, job_k;   // (outlive the asynchronous copy: the run ends in a synchronisation)
     size_t max_ref = cpc;
     if (direct) {
-        std::vector<uint32_t> byk;
-        for (uint32_t o = 0; o < P.n_outputs; o++)
-            if (P.out_node[o] != CIRC_NONE) byk.push_back(o);
-        std::stable_sort(byk.begin(), byk.end(), [&](uint32_t x, uint32_t y) { return P.out_node[x] < P.out_node[y]; });
-        for (uint32_t o : byk) {
-            const uint32_t k = P.out_node[o], L = P.level[P.order[k]];
-            job_k.push_back(k);
-            jobs.insert(jobs.end(), {o, k - P.level_start[L], P.out_gate[o] | (P.out_ref[o] & CIRC_NOT)});
-        }
         max_ref = 0;
         for (size_t q0 = 0; !lift && q0 < n_ct; q0 += cpc) {
             size_t nref = 0;
@@ -3134,18 +3096,13 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         }
     }
     // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller)
-    const size_t ct_tab = ct ? P.input_slot.size() + 2 * P.out_ref.size() : 0;
-    const size_t tab_words = P.in_ref.size() + P.out_slot.size() + P.out_ref.size() + ct_tab + jobs.size() +
-                             (P.lanes() ? P.in_shift.size() + 3 * P.out_shift.size() : 0) +
-                             (P.gate3() ? 2 * P.in_ref3.size() : 0) +
-                             (P.wsum() ? P.w_start.size() + 3 * P.w_ref.size() : 0);
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
     // (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even word offset)
     if ((rc = circ_grow(c, c->circ_stage, (size_t)max_rows * (direct ? 8 : 5) * row))) return rc;
     if (direct && (rc = circ_grow(c, c->circ_raw, n_ct * n * row))) return rc;
     if (out && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
-    if ((rc = circ_grow(c, c->circ_tab, tab_words))) return rc;
+    if ((rc = circ_grow(c, c->circ_tab, P.at.words))) return rc;
     if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
     if (pack && (rc = pack_grow(c, cpc, n_ct, max_ref))) return rc;
     const size_t probe_rows = probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
@@ -3173,59 +3130,22 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
         if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(work_rows, chunk0))))) return rc;
     }
-    uint32_t *d_in_ref = c->circ_tab.p, *d_out_slot = d_in_ref + P.in_ref.size(), *d_out_ref = d_out_slot + P.out_slot.size();
-    uint32_t *d_in_slot = d_out_ref + P.out_ref.size(), *d_pack_ref = d_in_slot + P.input_slot.size();
-    uint32_t *d_jobs = d_pack_ref + 2 * P.out_ref.size();
-    // lane shifts (plans with lane groups only), beside their reference tables: in_shift, out_shift, and the pack
-    // calls' (0, shift of output o)
-    int32_t *d_in_shift = reinterpret_cast<int32_t *>(d_out_ref + P.out_ref.size() + ct_tab + jobs.size());
-    int32_t *d_out_shift = d_in_shift + P.in_shift.size(), *d_pack_shift = d_out_shift + P.out_shift.size();
-    // third references (plans with three-input nodes only), past everything above: in_ref3, in_shift3
-    uint32_t *d_in_ref3 = nullptr;
-    int32_t *d_in_shift3 = nullptr;
-    if (P.gate3()) {
-        d_in_ref3 = c->circ_tab.p + tab_words - 2 * P.in_ref3.size() - (P.wsum() ? P.w_start.size() + 3 * P.w_ref.size() : 0);
-        d_in_shift3 = reinterpret_cast<int32_t *>(d_in_ref3 + P.in_ref3.size());
-        HIPCHK(c, hipMemcpyAsync(d_in_ref3, P.in_ref3.data(), P.in_ref3.size() * 4, hipMemcpyHostToDevice, st));
-        if (P.lanes())
-            HIPCHK(c, hipMemcpyAsync(d_in_shift3, P.in_shift3.data(), P.in_shift3.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    // the terms of every live node (plans with wide sum nodes only), last: w_start, w_ref, w_shift, w_weight
-    CircuitTerms d_terms = {};
-    if (P.wsum()) {
-        const size_t T = P.w_ref.size();
-        uint32_t *d_w_start = c->circ_tab.p + tab_words - P.w_start.size() - 3 * T, *d_w_ref = d_w_start + P.w_start.size();
-        int32_t *d_w_shift = reinterpret_cast<int32_t *>(d_w_ref + T), *d_w_weight = d_w_shift + T;
-        HIPCHK(c, hipMemcpyAsync(d_w_start, P.w_start.data(), P.w_start.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(d_w_ref, P.w_ref.data(), T * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(d_w_shift, P.w_shift.data(), T * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(d_w_weight, P.w_weight.data(), T * 4, hipMemcpyHostToDevice, st));
-        d_terms = {d_w_start, d_w_ref, d_w_shift, d_w_weight};
-    }
-    std::vector<int32_t> pack_shift;   // (outlives the asynchronous copy: the run ends in a synchronisation)
-    if (P.lanes()) {
-        if (!P.in_shift.empty())
-            HIPCHK(c, hipMemcpyAsync(d_in_shift, P.in_shift.data(), P.in_shift.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(d_out_shift, P.out_shift.data(), P.out_shift.size() * 4, hipMemcpyHostToDevice, st));
-        if (pack) {
-            pack_shift.assign(2 * P.out_shift.size(), 0);
-            for (size_t o = 0; o < P.out_shift.size(); o++) pack_shift[2 * o + 1] = P.out_shift[o];
-            HIPCHK(c, hipMemcpyAsync(d_pack_shift, pack_shift.data(), pack_shift.size() * 4, hipMemcpyHostToDevice, st));
-        }
-    }
-    if (!jobs.empty()) HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_in_ref, P.in_ref.data(), P.in_ref.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_out_slot, P.out_slot.data(), P.out_slot.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_out_ref, P.out_ref.data(), P.out_ref.size() * 4, hipMemcpyHostToDevice, st));
+    // the plan's tables (the image outlives the asynchronous copy: it belongs to the circuit)
+    HIPCHK(c, hipMemcpyAsync(c->circ_tab.p, P.image.data(), (size_t)P.at.words * 4, hipMemcpyHostToDevice, st));
+    const uint32_t *tab = c->circ_tab.p;
+    const CircNodes nodes = {tab + P.at.node_kind, tab + P.at.term_start, tab + P.at.term_ref,
+                             reinterpret_cast<const int32_t *>(tab + P.at.term_shift),
+                             reinterpret_cast<const int32_t *>(tab + P.at.term_weight)};
+    const uint32_t *d_out_slot = tab + P.at.out_slot, *d_out_ref = tab + P.at.out_ref, *d_in_slot = tab + P.at.input_slot;
+    const uint32_t *d_jobs = tab + P.at.jobs;
+    const int32_t *d_out_shift = reinterpret_cast<const int32_t *>(tab + P.at.out_shift);
     if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
         HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
         if (probe_rows) HIPCHK(c, hipMemsetAsync(NL.stats, 0, probe_rows * 64, st));
     }
-    std::vector<uint32_t> pack_ref;   // (outlives the asynchronous copy: the run ends in a synchronisation)
     if (ct) {
         // the ciphertexts as they are, and extract() of every bit into the slot of its input wire
         if (P.n_inputs) {
-            HIPCHK(c, hipMemcpyAsync(d_in_slot, P.input_slot.data(), P.input_slot.size() * 4, hipMemcpyHostToDevice, st));
             HIPCHK(c, hipMemcpyAsync(c->circ_ct.p, ct->in_a, ct_words * 8, hipMemcpyHostToDevice, st));
             HIPCHK(c, hipMemcpyAsync(c->circ_ct.p + ct_words, ct->in_b, ct_words * 8, hipMemcpyHostToDevice, st));
             const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
@@ -3233,14 +3153,6 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
                                (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct.p, c->circ_ct.p + ct_words, d_in_slot,
                                c->circ_wires.p, (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
             HIPCHK(c, hipGetLastError());
-        }
-        if (pack) {   // node table of the pack calls: (TRUE, output o), the pair of fhe.jl:669-673
-            pack_ref.resize(2 * P.out_ref.size());
-            for (size_t o = 0; o < P.out_ref.size(); o++) {
-                pack_ref[2 * o] = CIRC_FALSE | CIRC_NOT;
-                pack_ref[2 * o + 1] = P.out_ref[o];
-            }
-            HIPCHK(c, hipMemcpyAsync(d_pack_ref, pack_ref.data(), pack_ref.size() * 4, hipMemcpyHostToDevice, st));
         }
     } else {
         // inputs straight into their slots; runs of consecutive inputs in consecutive slots as one copy
@@ -3277,19 +3189,16 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         for (uint64_t row0 = 0; row0 < rows_total; row0 += SGFHE_CIRCUIT_CALL_ROWS) {
             const uint32_t rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, rows_total - row0);
             const uint32_t tg = rows * (uint32_t)row;
-            const CircuitTerms level_terms = {P.wsum() ? d_terms.start + k0 : nullptr, d_terms.ref, d_terms.shift, d_terms.weight};
-            circuit_gather(P, st, c->circ_wires.p, d_in_ref + 2 * (size_t)k0, d_in_shift + 2 * (size_t)k0, a1, b1, a2, b2,
-                           (uint32_t)row0, rows, inst, (uint32_t)n, r, P.gate3() ? d_in_ref3 + k0 : nullptr,
-                           P.gate3() ? d_in_shift3 + k0 : nullptr, P.wsum() ? &level_terms : nullptr);
+            circuit_gather(P, st, c->circ_wires.p, nodes, k0, a1, b1, a2, b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
             HIPCHK(c, hipGetLastError());
             // a call that produces a wire some direct output names leaves its rows un-reduced: the scatter reduces
             // what the wire table takes (the words k_final writes) and copies the named rows into the raw table
             const uint32_t ka = k0 + (uint32_t)(row0 / inst), kb = k0 + (uint32_t)((row0 + rows - 1) / inst);
-            const size_t j0 = std::lower_bound(job_k.begin(), job_k.end(), ka) - job_k.begin();
-            const size_t j1 = std::upper_bound(job_k.begin(), job_k.end(), kb) - job_k.begin();
-            // a call that holds a three-input node: its XOR3 rows, from the staging the bootstrap consumed
+            const size_t j0 = std::lower_bound(P.job_k.begin(), P.job_k.end(), ka) - P.job_k.begin();
+            const size_t j1 = std::upper_bound(P.job_k.begin(), P.job_k.end(), kb) - P.job_k.begin();
+            // a call that holds a sum node: its LOW rows, from the staging the bootstrap consumed
             const bool xor3 = P.gate3_in(ka, kb);
-            if (j1 > j0) {
+            if (direct && j1 > j0) {
                 if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, SGFHE_FLAG_RAW_MODQ, c->n, nullptr, st))) return rc;
                 for (size_t j = j0; j < j1;) {   // (a grid holds 65535 rows of workgroups)
                     const uint32_t wires = j == j0, nj = (uint32_t)std::min<size_t>(j1 - j, 65535u - wires);
@@ -3302,7 +3211,7 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
                 }
                 if (xor3) {   // (after the scatter: over the XOR row's words in the wire table)
                     hipLaunchKernelGGL(k_circ_xor3_raw, dim3(rows), dim3(256), 0, st,
-                                       reinterpret_cast<const ulonglong2 *>(res), d_in_ref3 + k0,
+                                       reinterpret_cast<const ulonglong2 *>(res), nodes.kind + k0,
                                        d_out_slot + 3 * (size_t)k0, c->circ_wires.p, a1, b1, a2, b2, cur(c).d_crt,
                                        (uint32_t)row0, inst, (uint32_t)n, r);
                     HIPCHK(c, hipGetLastError());
@@ -3312,7 +3221,7 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             // the k-loop of sgfhe_bootstrap_batch_device: the next call number of the ctx's draw stream
             if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, 0u, c->n, nullptr, st))) return rc;
             if (xor3) {   // (before the scatter and the probe read the result rows)
-                hipLaunchKernelGGL(k_circ_xor3, dim3((tg + 255) / 256), dim3(256), 0, st, res, d_in_ref3 + k0, a1, b1, a2,
+                hipLaunchKernelGGL(k_circ_xor3, dim3((tg + 255) / 256), dim3(256), 0, st, res, nodes.kind + k0, a1, b1, a2,
                                    b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
                 HIPCHK(c, hipGetLastError());
             }
@@ -3356,13 +3265,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             const Run &R = runs[i];
             const uint32_t rows = (uint32_t)(R.len * n);
             const dim3 grid((rows * (uint32_t)row + 255) / 256);
-            if (P.lanes())
-                hipLaunchKernelGGL(k_circ_lift<true>, grid, dim3(256), 0, st, c->circ_wires.p, d_pack_ref, d_pack_shift,
-                                   c->circ_raw.p, cur(c).d_crt, (uint32_t)(R.q * n), rows, inst, (uint32_t)n, r, P.group);
-            else
-                hipLaunchKernelGGL(k_circ_lift<false>, grid, dim3(256), 0, st, c->circ_wires.p, d_pack_ref,
-                                   (const int32_t *)nullptr, c->circ_raw.p, cur(c).d_crt, (uint32_t)(R.q * n), rows, inst,
-                                   (uint32_t)n, r, 1u);
+            hipLaunchKernelGGL(k_circ_lift, grid, dim3(256), 0, st, c->circ_wires.p, d_out_ref, d_out_shift, c->circ_raw.p,
+                               cur(c).d_crt, (uint32_t)(R.q * n), rows, inst, (uint32_t)n, r, P.group);
             HIPCHK(c, hipGetLastError());
         }
         if (nref && !lift) {
@@ -3370,7 +3274,7 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
             uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
             for (const Run &R : runs) {
                 const size_t off = R.rank * n;
-                circuit_gather(P, st, c->circ_wires.p, d_pack_ref, d_pack_shift, p1 + off * n, q1 + off, p2 + off * n,
+                circuit_gather(P, st, c->circ_wires.p, nodes, (uint32_t)P.live(), p1 + off * n, q1 + off, p2 + off * n,
                                q2 + off, (uint32_t)(R.q * n), (uint32_t)(R.len * n), inst, (uint32_t)n, r);
                 HIPCHK(c, hipGetLastError());
             }
@@ -3392,8 +3296,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     for (size_t q0 = 0; !direct && q0 < n_ct; q0 += cpc) {
         const size_t cnt = std::min(cpc, n_ct - q0), nb = cnt * n;
         uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
-        circuit_gather(P, st, c->circ_wires.p, d_pack_ref, d_pack_shift, p1, q1, p2, q2, (uint32_t)(q0 * n), (uint32_t)nb,
-                       inst, (uint32_t)n, r);
+        circuit_gather(P, st, c->circ_wires.p, nodes, (uint32_t)P.live(), p1, q1, p2, q2, (uint32_t)(q0 * n),
+                       (uint32_t)nb, inst, (uint32_t)n, r);
         HIPCHK(c, hipGetLastError());
         if ((rc = pack_device(c, p1, q1, p2, q2, cnt, c->pack_wv.p + q0 * M, c->pack_wv.p + (n_ct + q0) * M, st))) return rc;
     }
@@ -3404,12 +3308,8 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
     if (out) {
         const size_t total = (size_t)P.n_outputs * instances * row;
         const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
-        if (P.lanes())
-            hipLaunchKernelGGL(k_circ_collect_lanes, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
-                               d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
-        else
-            hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
-                               c->circ_out.p, total, inst, (uint32_t)n, r);
+        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref, d_out_shift,
+                           c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(out, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
     }

@@ -1692,106 +1692,40 @@ __device__ __forceinline__ uint64_t circ_word_lane(const uint64_t *__restrict__ 
     return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + src, e, n, r);
 }
 
-// a1 / a2 [rows][n], b1 / b2 [rows] of one call: blockIdx.y selects the input (0: x, 1: y)
+// The node table of a plan on the device (CircuitPlan::node_kind ..): one CSR over the live nodes and the pack stage's
+// pseudo-level, node k's terms term_start[k] .. term_start[k + 1] of ref / shift / weight.
+struct CircNodes {
+    const uint32_t *kind, *start, *ref;
+    const int32_t *shift, *weight;
+};
+
+// The staged inputs of one call, a1 / a2 [rows][n], b1 / b2 [rows]: rows row0 .. row0 + rows of the level whose first
+// node is `node0` of the table.  A classic node (kind 0) writes (a1, a2) = (X, Y), its two terms.  A sum node writes
+// a1 = U = the sum of w X over its terms mod r and a2 = 0 -- the bootstrap adds its two inputs first, so (U, 0) gives
+// what (X + Y, Z) gives: the rotation is by the phase of the sum, the AND row of three unit weights is MAJ(X, Y, Z), the
+// OR row "one or two true", and LOW = U - 2 HI over Z_r needs no bootstrap (k_circ_xor3).  One thread per word of a row
+// and BOTH outputs; the node decode and the term range are uniform over a row, every load is a coalesced 8-byte access
+// along a (shifted) source row.  The sum runs in wrapping uint64 arithmetic with a signed multiply (w in {-2, -1, 1, 2})
+// and is reduced with one mask: r is a power of two (at most 2^15), so 2^64 is a multiple of it, and 64 terms of weight
+// 2 stay far below 2^64 anyway.  A plan without lane groups has group 1 and no shift but 0.
 __global__ void __launch_bounds__(256)
-k_circ_gather(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref, uint64_t *__restrict__ a1,
+k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node0, uint64_t *__restrict__ a1,
               uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
-              uint32_t rows, uint32_t instances, uint32_t n, uint64_t r) {
+              uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
-    const uint32_t rank = R / instances, inst = R % instances, j = blockIdx.y;
-    const uint32_t ref = in_ref[2 * rank + j];
-    const uint64_t v = circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
-    uint64_t *a = j ? a2 : a1, *b = j ? b2 : b1;
-    if (e < n) a[(size_t)lr * n + e] = v;
-    else b[lr] = v;
-}
-
-// k_circ_gather of a plan with lane groups: in_shift [nodes][2] beside in_ref.  Same thread-to-word map, so the
-// loads stay coalesced 8-byte accesses along the (shifted) source row.
-__global__ void __launch_bounds__(256)
-k_circ_gather_lanes(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref,
-                    const int32_t *__restrict__ in_shift, uint64_t *__restrict__ a1, uint64_t *__restrict__ b1,
-                    uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0, uint32_t rows,
-                    uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= rows * (n + 1)) return;
-    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
-    const uint32_t rank = R / instances, inst = R % instances, j = blockIdx.y;
-    const uint64_t v = circ_word_lane(wires, in_ref[2 * rank + j], in_shift[2 * rank + j], group, instances, inst, e, n, r);
-    uint64_t *a = j ? a2 : a1, *b = j ? b2 : b1;
-    if (e < n) a[(size_t)lr * n + e] = v;
-    else b[lr] = v;
-}
-
-// ---- three-input nodes (sgfhe_circuit_create3) --------------------------------------------------------------------
-// A node with a third reference Z is bootstrapped on (X + Y mod r, Z): the rotation is by the phase of the sum of three
-// bits, its AND row is MAJ(X, Y, Z), its OR row "one or two true", and XOR3 = X + Y + Z - 2 MAJ over Z_r needs no
-// bootstrap.  in_ref3 / in_shift3 [nodes] beside in_ref / in_shift; CIRC_REF_NO_INPUT marks a two-input node.
-constexpr uint32_t CIRC_REF_NO_INPUT = 0x7FFFFFFEu;
-
-// k_circ_gather / k_circ_gather_lanes (LANES: the plan has lane groups, and the shift tables exist) of a plan with
-// three-input nodes: blockIdx.y = 0 writes a1 = X + Y mod r (X for a two-input node), blockIdx.y = 1 writes a2 = Z (Y).
-// Same thread-to-word map: every load is a coalesced 8-byte access along a source row, the node decode is uniform over
-// a row, and r is a power of two, so the sum is reduced with one mask.
-template <bool LANES>
-__global__ void __launch_bounds__(256)
-k_circ_gather3(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref,
-               const int32_t *__restrict__ in_shift, const uint32_t *__restrict__ in_ref3,
-               const int32_t *__restrict__ in_shift3, uint64_t *__restrict__ a1, uint64_t *__restrict__ b1,
-               uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0, uint32_t rows, uint32_t instances,
-               uint32_t n, uint64_t r, uint32_t group) {
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= rows * (n + 1)) return;
-    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
-    const uint32_t rank = R / instances, inst = R % instances, j = blockIdx.y;
-    auto read = [&](uint32_t ref, const int32_t *shift, uint32_t i) -> uint64_t {
-        if (LANES) return circ_word_lane(wires, ref, shift[i], group, instances, inst, e, n, r);
-        return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
-    };
-    const uint32_t ref3 = in_ref3[rank];
-    uint64_t v;
-    if (ref3 == CIRC_REF_NO_INPUT) v = read(in_ref[2 * rank + j], in_shift, 2 * rank + j);
-    else if (j) v = read(ref3, in_shift3, rank);
-    else v = (read(in_ref[2 * rank], in_shift, 2 * rank) + read(in_ref[2 * rank + 1], in_shift, 2 * rank + 1)) & (r - 1);
-    uint64_t *a = j ? a2 : a1, *b = j ? b2 : b1;
-    if (e < n) a[(size_t)lr * n + e] = v;
-    else b[lr] = v;
-}
-
-// ---- weighted-sum nodes (sgfhe_circuit_create_w) -----------------------------------------------------------------
-// The gather of a plan that holds a sum node with something other than two or three unit weights: the terms of EVERY
-// node of the level as CSR tables (w_start [nodes + 1] into w_ref / w_shift / w_weight), in_ref3 telling the kinds
-// apart.  A classic node (CIRC_REF_NO_INPUT) writes (a1, a2) = (X, Y), its two terms; a sum node writes a1 = U = the
-// sum of w X over its terms mod r and a2 = 0 -- the bootstrap adds its two inputs first, so (U, 0) gives what
-// (X + Y, Z) gives.  One thread per word of a row and BOTH outputs; the node decode and the term range are uniform
-// over a row, every load is a coalesced 8-byte access along a source row.  The sum runs in wrapping uint64 arithmetic
-// with a signed multiply (w in {-2, -1, 1, 2}) and is reduced with one mask: r is a power of two (at most 2^15), so
-// 2^64 is a multiple of it, and 64 terms of weight 2 stay far below 2^64 anyway.
-template <bool LANES>
-__global__ void __launch_bounds__(256)
-k_circ_gather_w(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ in_ref3,
-                const uint32_t *__restrict__ w_start, const uint32_t *__restrict__ w_ref,
-                const int32_t *__restrict__ w_shift, const int32_t *__restrict__ w_weight, uint64_t *__restrict__ a1,
-                uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
-                uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= rows * (n + 1)) return;
-    const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
-    const uint32_t rank = R / instances, inst = R % instances;
+    const uint32_t k = node0 + R / instances, inst = R % instances;
     auto read = [&](uint32_t i) -> uint64_t {
-        const uint32_t ref = w_ref[i];
-        if (LANES) return circ_word_lane(wires, ref, w_shift[i], group, instances, inst, e, n, r);
-        return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+        return circ_word_lane(wires, nodes.ref[i], nodes.shift[i], group, instances, inst, e, n, r);
     };
-    const uint32_t t0 = w_start[rank], t1 = w_start[rank + 1];
+    const uint32_t t0 = nodes.start[k], t1 = nodes.start[k + 1];
     uint64_t u = 0, v = 0;
-    if (in_ref3[rank] == CIRC_REF_NO_INPUT) {
+    if (nodes.kind[k] == 0) {
         u = read(t0);
         v = read(t0 + 1);
     } else {
-        for (uint32_t i = t0; i < t1; i++) u += (uint64_t)((int64_t)w_weight[i] * (int64_t)read(i));
+        for (uint32_t i = t0; i < t1; i++) u += (uint64_t)((int64_t)nodes.weight[i] * (int64_t)read(i));
         u &= r - 1;
     }
     if (e < n) {
@@ -1803,19 +1737,19 @@ k_circ_gather_w(const uint64_t *__restrict__ wires, const uint32_t *__restrict__
     }
 }
 
-// XOR3 of the three-input nodes of a call (LOW of its sum nodes: any in_ref3 but CIRC_REF_NO_INPUT marks them), after
-// its k-loop and before anything reads its result rows
-// [rows][3][n + 1]: row 2 = a1 + a2 - 2 row 0 mod r, word by word, b included -- a1 + a2 is X + Y + Z as the bootstrap
-// consumed it (the staging is not written between the gather and here), row 0 the reduced MAJ.  The rows of two-input
+// LOW of the sum nodes of a call (XOR3 of a three-input node; node_kind [nodes] of the level marks them), after its
+// k-loop and before anything reads its result rows
+// [rows][3][n + 1]: row 2 = a1 + a2 - 2 row 0 mod r, word by word, b included -- a1 + a2 is the sum U as the bootstrap
+// consumed it (the staging is not written between the gather and here), row 0 the reduced HI.  The rows of classic
 // nodes are left alone.  One thread per word, as the gather.
 __global__ void __launch_bounds__(256)
-k_circ_xor3(uint64_t *__restrict__ res, const uint32_t *__restrict__ in_ref3, const uint64_t *__restrict__ a1,
+k_circ_xor3(uint64_t *__restrict__ res, const uint32_t *__restrict__ node_kind, const uint64_t *__restrict__ a1,
             const uint64_t *__restrict__ b1, const uint64_t *__restrict__ a2, const uint64_t *__restrict__ b2,
             uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1);
-    if (in_ref3[(row0 + lr) / instances] == CIRC_REF_NO_INPUT) return;
+    if (node_kind[(row0 + lr) / instances] == 0) return;
     const uint64_t s = e < n ? a1[(size_t)lr * n + e] + a2[(size_t)lr * n + e] : b1[lr] + b2[lr];
     uint64_t *o = res + (size_t)lr * 3 * (n + 1) + e;
     o[2 * (size_t)(n + 1)] = (s - 2 * o[0]) & (r - 1);
@@ -1826,13 +1760,13 @@ k_circ_xor3(uint64_t *__restrict__ res, const uint32_t *__restrict__ in_ref3, co
 // row 0 reduced by the device function of k_final -- the words the reduced call gives.  The raw rows are not touched
 // (an output naming an XOR3 wire is refreshed or lifted, never direct).  One workgroup per row, as k_circ_scatter_raw.
 __global__ void __launch_bounds__(256)
-k_circ_xor3_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__ in_ref3,
+k_circ_xor3_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__ node_kind,
                 const uint32_t *__restrict__ out_slot, uint64_t *__restrict__ wires, const uint64_t *__restrict__ a1,
                 const uint64_t *__restrict__ b1, const uint64_t *__restrict__ a2, const uint64_t *__restrict__ b2,
                 const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint64_t r) {
     const uint32_t lr = blockIdx.x, R = row0 + lr;
     const uint32_t rank = R / instances, inst = R % instances;   // (uniform over the workgroup)
-    if (in_ref3[rank] == CIRC_REF_NO_INPUT) return;
+    if (node_kind[rank] == 0) return;
     const uint32_t slot = out_slot[3 * rank + 2];
     if (slot == CIRC_SLOT_NONE) return;
     const size_t stride = n + 1;
@@ -1928,22 +1862,19 @@ __device__ __forceinline__ ulonglong2 lift_word(uint64_t x, const CrtConst *CC) 
 
 // The lifted ciphertexts of a pack group (SGFHE_CIRCUIT_PACK_LIFT): rows row0 .. row0 + rows of the pack stage's
 // pseudo-level, whose node o is (TRUE, output o) -- row R = q n + bit is output R / instances at instance R % instances
-// -- read from the wire table as that level's gather reads its second input (pack_ref / pack_shift [n_outputs][2]; NOT,
-// the constant and, with LANES, the lane shift applied over Z_r), lifted word by word into row R of the raw output
-// table [q][n][n + 1].  Thread-to-word map of the gathers: coalesced 8-byte loads along a source row, 16-byte stores
+// -- read from the wire table as that level's gather reads its second input (out_ref / out_shift [n_outputs]; NOT,
+// the constant and the lane shift applied over Z_r), lifted word by word into row R of the raw output table
+// [q][n][n + 1].  Thread-to-word map of the gathers: coalesced 8-byte loads along a source row, 16-byte stores
 // (raw rows are 16-byte aligned), the row decode uniform over a row.
-template <bool LANES>
 __global__ void __launch_bounds__(256)
-k_circ_lift(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ pack_ref,
-            const int32_t *__restrict__ pack_shift, ulonglong2 *__restrict__ rawout, const CrtConst *__restrict__ CC,
+k_circ_lift(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
+            const int32_t *__restrict__ out_shift, ulonglong2 *__restrict__ rawout, const CrtConst *__restrict__ CC,
             uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
     const uint32_t o = R / instances, inst = R % instances;
-    const uint32_t ref = pack_ref[2 * o + 1];
-    const uint64_t v = LANES ? circ_word_lane(wires, ref, pack_shift[2 * o + 1], group, instances, inst, e, n, r)
-                             : circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
+    const uint64_t v = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r);
     rawout[(size_t)R * (n + 1) + e] = lift_word(v, CC);
 }
 
@@ -1955,25 +1886,12 @@ k_lwe_lift(const uint64_t *__restrict__ in, ulonglong2 *__restrict__ out, const 
         out[t] = lift_word(in[t], CC);
 }
 
-// the circuit's outputs [n_outputs][instances][n + 1], NOT and the constant applied (grid-stride: the
-// array may hold more than 2^32 words)
+// the circuit's outputs [n_outputs][instances][n + 1], NOT, the constant and the lane shift (out_shift [n_outputs]
+// beside out_ref) applied (grid-stride: the array may hold more than 2^32 words)
 __global__ void __launch_bounds__(256)
-k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref, uint64_t *__restrict__ out,
-               size_t total, uint32_t instances, uint32_t n, uint64_t r) {
-    const size_t per_out = (size_t)instances * (n + 1);
-    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
-        const size_t o = t / per_out, w = t % per_out;
-        const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
-        const uint32_t ref = out_ref[o];
-        out[t] = circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + inst, e, n, r);
-    }
-}
-
-// k_circ_collect of a plan with lane groups: out_shift [n_outputs] beside out_ref
-__global__ void __launch_bounds__(256)
-k_circ_collect_lanes(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
-                     const int32_t *__restrict__ out_shift, uint64_t *__restrict__ out, size_t total,
-                     uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
+               const int32_t *__restrict__ out_shift, uint64_t *__restrict__ out, size_t total, uint32_t instances,
+               uint32_t n, uint64_t r, uint32_t group) {
     const size_t per_out = (size_t)instances * (n + 1);
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t o = t / per_out, w = t % per_out;

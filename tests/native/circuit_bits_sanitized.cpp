@@ -5,7 +5,7 @@
 //   n_gates lines "x y" (wire references, decimal uint32), one line of n_outputs references,
 //   n_inputs lines of `instances` characters 0 / 1
 // and prints one line per probe row: "<wire id> <bits of the instances>".  It also checks, on its own, the
-// numbering of the probe rows against the plan (in_row names the row of the wire the node reads) and that an
+// numbering of the probe rows against the plan (term_row names the row of the wire the node reads) and that an
 // instance count of 0 and NULL bits are handled.
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "circuit.h"
+#include "circuit_tables.h"
 
 using namespace sgfhe;
 
@@ -41,19 +42,9 @@ int main() {
     }
     CircuitPlan P;
     CHECK(circuit_plan(n_inputs, gates.data(), n_gates, outs.data(), n_outputs, P) == SGFHE_OK);
-    // the probe rows: inputs, then the three wires of every live node in `order`; in_row names them
-    CHECK(P.in_row.size() == 2 * P.live());
-    for (size_t k = 0; k < P.live(); k++)
-        for (int j = 0; j < 2; j++) {
-            const uint32_t ref = gates[2 * P.order[k] + j], row = P.in_row[2 * k + j];
-            CHECK((ref & CIRC_NOT) == (row & CIRC_NOT));
-            const uint32_t id = ref & ~CIRC_NOT, rid = row & ~CIRC_NOT;
-            if (id == CIRC_FALSE) CHECK(rid == CIRC_FALSE);
-            else {
-                CHECK(rid < circuit_probe_rows(P) && circuit_probe_wire(P, rid) == id);
-                if (rid >= n_inputs) CHECK((rid - n_inputs) / 3 < k);   // an earlier node of `order`
-            }
-        }
+    // the probe rows: inputs, then the three wires of every live node in `order`; term_row names them
+    check_plan_tables(P);
+    for (size_t k = 0; k < P.live(); k++) check_node_terms(P, k, 0, 2, &gates[2 * P.order[k]], nullptr, nullptr);
     std::vector<uint64_t> table;
     CHECK(circuit_plain_bits(P, bits.data(), instances, table) == SGFHE_OK);
     const size_t wpr = circuit_bit_words(instances);

@@ -3,7 +3,8 @@
 //   - random circuits that mix two- and three-input nodes, with NOTs, constants and (for G = 8) lane shifts on all
 //     three inputs, are planned for (group, instances) = (1, 5) and (8, 72), and circuit_plain_bits is compared, bit
 //     by bit, with an evaluation of the ORIGINAL arrays one instance at a time -- MAJ, ONE_OR_TWO, XOR3 from the count
-//     of true inputs; the plan's third-reference tables are compared with the arrays;
+//     of true inputs; the plan's node table is compared with the arrays, term by term -- a node with a third
+//     reference is a sum node of three unit weights -- and its image checked (tests/native/circuit_tables.h);
 //   - an output that names an XOR3 wire is never direct, one that names MAJ or ONE_OR_TWO unshifted is;
 //   - the plan whose third references are all SGFHE_CIRCUIT_NONE equals the plan of the [n_gates][2] arrays;
 //   - the inputs the planner must refuse return SGFHE_ERR_INVALID_ARG without a single allocation (the global
@@ -22,12 +23,18 @@ void *operator new(size_t n) {
     throw std::bad_alloc();
 }
 void *operator new[](size_t n) { return operator new(n); }
+void *operator new(size_t n, const std::nothrow_t &) noexcept {   // (std::stable_sort's buffer)
+    g_allocs++;
+    return malloc(n ? n : 1);
+}
+void *operator new[](size_t n, const std::nothrow_t &t) noexcept { return operator new(n, t); }
 void operator delete(void *p) noexcept { free(p); }
 void operator delete[](void *p) noexcept { free(p); }
 void operator delete(void *p, size_t) noexcept { free(p); }
 void operator delete[](void *p, size_t) noexcept { free(p); }
 
 #include "circuit.h"
+#include "circuit_tables.h"
 
 using namespace sgfhe;
 
@@ -103,26 +110,16 @@ static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32
     CircuitPlan P;
     CHECK(circuit_plan3(n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G,
                         P) == SGFHE_OK);
-    CHECK(P.group == G && P.in_ref.size() == 2 * P.live() && P.in_shift.size() == 2 * P.live());
-    CHECK(P.in_ref3.size() == P.live() && P.in_shift3.size() == P.live() && P.in_row3.size() == P.live());
-    CHECK(P.three_before.size() == P.live() + 1 && P.three_before[P.live()] == P.three);
+    CHECK(P.group == G);
+    check_plan_tables(P);
     uint32_t three = 0;
-    for (size_t k = 0; k < P.live(); k++) {
+    for (size_t k = 0; k < P.live(); k++) {   // the caller's kind: a third reference is present
         const size_t g = P.order[k];
-        const uint32_t z = A.gates[3 * g + 2];
-        if (z == CIRC_NO_INPUT) {
-            CHECK(P.in_ref3[k] == CIRC_NO_INPUT && P.in_shift3[k] == 0 && P.in_row3[k] == CIRC_NO_INPUT);
-        } else {
-            three++;
-            CHECK(P.in_ref3[k] != CIRC_NO_INPUT && (P.in_ref3[k] & CIRC_NOT) == (z & CIRC_NOT));
-            CHECK(P.in_shift3[k] == ((z & ~CIRC_NOT) == CIRC_FALSE ? 0 : A.gshift[3 * g + 2]));
-        }
-        CHECK(P.three_before[k + 1] == three);
-        CHECK(P.gate3_in((uint32_t)k, (uint32_t)k) == (z != CIRC_NO_INPUT));
-        for (int j = 0; j < 2; j++)
-            CHECK(P.in_shift[2 * k + j] == ((A.gates[3 * g + j] & ~CIRC_NOT) == CIRC_FALSE ? 0 : A.gshift[3 * g + j]));
+        const bool sum = A.gates[3 * g + 2] != CIRC_NO_INPUT;
+        three += sum;
+        check_node_terms(P, k, sum, sum ? 3 : 2, &A.gates[3 * g], &A.gshift[3 * g], nullptr);
     }
-    CHECK(P.three == three && P.gate3() == (three > 0));
+    CHECK(P.sum_before[P.live()] == three);
     for (size_t o = 0; o < n_outputs; o++) {
         const uint32_t id = A.outs[o] & ~CIRC_NOT;
         if (id == CIRC_FALSE || id < n_inputs || P.out_shift[o]) {
@@ -193,12 +190,7 @@ static void check_all_none(uint32_t G) {
     CHECK(circuit_plan3(n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G,
                         P) == SGFHE_OK);
     CHECK(circuit_plan(n_inputs, g2.data(), s2.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G, Z) == SGFHE_OK);
-    CHECK(!P.gate3() && !Z.gate3() && P.three == 0);
-    CHECK(P.levels == Z.levels && P.widest == Z.widest && P.slots == Z.slots && P.group == Z.group);
-    CHECK(P.level == Z.level && P.order == Z.order && P.level_start == Z.level_start && P.input_slot == Z.input_slot);
-    CHECK(P.in_ref == Z.in_ref && P.out_slot == Z.out_slot && P.out_ref == Z.out_ref && P.in_row == Z.in_row);
-    CHECK(P.in_shift == Z.in_shift && P.out_shift == Z.out_shift && P.out_node == Z.out_node && P.out_gate == Z.out_gate);
-    CHECK(P.in_ref3 == Z.in_ref3 && P.in_shift3 == Z.in_shift3 && P.in_row3 == Z.in_row3);
+    CHECK(P.sum_before[P.live()] == 0 && same_tables(P, Z));
 }
 
 static void check_rejected() {
@@ -229,12 +221,13 @@ static void check_rejected() {
     refused(good, nullptr, outs, 0);
     // accepted: the largest shifts on a third input, anything beside NONE, a shift on a constant third input (dropped)
     const int32_t edge[6] = {0, 0, -7, 0, 0, 7};
-    CHECK(circuit_plan3(2, good, edge, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.three == 2 && P.n_inputs == 2);
-    CHECK(P.in_shift3[0] == -7 && P.in_shift3[1] == 7 && P.levels == 2);
+    CHECK(circuit_plan3(2, good, edge, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.sum_before[2] == 2 && P.n_inputs == 2);
+    CHECK(P.term_shift[2] == -7 && P.term_shift[5] == 7 && P.levels == 2);
     const uint32_t mixed[6] = {0, 1, N, 2, 0, CIRC_FALSE | CIRC_NOT};
     const int32_t wild[6] = {0, 0, INT32_MAX, 0, 0, 5};
-    CHECK(circuit_plan3(2, mixed, wild, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.three == 1);
-    CHECK(P.in_ref3[0] == N && P.in_ref3[1] == (CIRC_FALSE | CIRC_NOT) && P.in_shift3[1] == 0);
+    CHECK(circuit_plan3(2, mixed, wild, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.sum_before[2] == 1);
+    CHECK(P.node_kind[0] == 0 && P.node_kind[1] == 1 && P.term_start[1] == 2 && P.term_start[2] == 5);
+    CHECK(P.term_ref[4] == (CIRC_FALSE | CIRC_NOT) && P.term_shift[4] == 0);
     // a third input alone keeps its node alive and sets the level
     const uint32_t chain[9] = {0, 1, N, 0, 1, N, 0, 0, 5 | CIRC_NOT}, last[1] = {2 + 3 * 2 + 2};
     CHECK(circuit_plan3(2, chain, nullptr, 3, last, nullptr, 1, 1, P) == SGFHE_OK);

@@ -3,7 +3,8 @@
 //   - random circuits with random lane shifts and NOTs are planned for (group, instances) = (8, 72), (24, 120),
 //     (64, 192) and (1, 5) -- groups that divide a 64-bit word, straddle words and fill one, rows whose last word is
 //     ragged -- and circuit_plain_bits is compared, bit by bit, with an evaluation of the ORIGINAL arrays one
-//     instance at a time; the plan's shift tables are compared with the arrays;
+//     instance at a time; the plan's node table is compared with the arrays, term by term, and its image checked
+//     (tests/native/circuit_tables.h);
 //   - the zero-shift lanes plan equals the plan of the old entry;
 //   - the inputs the planner must refuse return SGFHE_ERR_INVALID_ARG without a single allocation (the global
 //     operator new is counted) and leave the plan they were given untouched.
@@ -21,12 +22,18 @@ void *operator new(size_t n) {
     throw std::bad_alloc();
 }
 void *operator new[](size_t n) { return operator new(n); }
+void *operator new(size_t n, const std::nothrow_t &) noexcept {   // (std::stable_sort's buffer)
+    g_allocs++;
+    return malloc(n ? n : 1);
+}
+void *operator new[](size_t n, const std::nothrow_t &t) noexcept { return operator new(n, t); }
 void operator delete(void *p) noexcept { free(p); }
 void operator delete[](void *p) noexcept { free(p); }
 void operator delete(void *p, size_t) noexcept { free(p); }
 void operator delete[](void *p, size_t) noexcept { free(p); }
 
 #include "circuit.h"
+#include "circuit_tables.h"
 
 using namespace sgfhe;
 
@@ -98,12 +105,9 @@ static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32
     CHECK(circuit_plan(n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G,
                        P) == SGFHE_OK);
     CHECK(P.group == G && P.lanes() == (G > 1));
-    CHECK(P.in_shift.size() == 2 * P.live() && P.out_shift.size() == n_outputs);
+    check_plan_tables(P);
     for (size_t k = 0; k < P.live(); k++)
-        for (int j = 0; j < 2; j++) {
-            const size_t i = 2 * (size_t)P.order[k] + j;
-            CHECK(P.in_shift[2 * k + j] == ((A.gates[i] & ~CIRC_NOT) == CIRC_FALSE ? 0 : A.gshift[i]));
-        }
+        check_node_terms(P, k, 0, 2, &A.gates[2 * (size_t)P.order[k]], &A.gshift[2 * (size_t)P.order[k]], nullptr);
     for (size_t o = 0; o < n_outputs; o++) {
         CHECK(P.out_shift[o] == ((A.outs[o] & ~CIRC_NOT) == CIRC_FALSE ? 0 : A.oshift[o]));
         if (P.out_shift[o]) CHECK(P.out_node[o] == CIRC_NONE);   // a shifted output is refreshed, never direct
@@ -112,7 +116,14 @@ static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32
     CircuitPlan Z;
     CHECK(circuit_plan(n_inputs, A.gates.data(), n_gates, A.outs.data(), n_outputs, Z) == SGFHE_OK);
     CHECK(Z.level == P.level && Z.order == P.order && Z.level_start == P.level_start && Z.slots == P.slots);
-    CHECK(Z.in_ref == P.in_ref && Z.out_slot == P.out_slot && Z.out_ref == P.out_ref && Z.in_row == P.in_row);
+    CHECK(Z.node_kind == P.node_kind && Z.term_start == P.term_start && Z.term_ref == P.term_ref && Z.term_row == P.term_row);
+    CHECK(Z.term_weight == P.term_weight && Z.out_slot == P.out_slot && Z.out_ref == P.out_ref);
+    // and with every shift zero the lanes plan IS the plan of the old entry, table by table
+    const std::vector<int32_t> gz(A.gshift.size(), 0), oz(A.oshift.size(), 0);
+    CircuitPlan ZL;
+    CHECK(circuit_plan(n_inputs, A.gates.data(), gz.data(), n_gates, A.outs.data(), oz.data(), n_outputs, G, ZL) == SGFHE_OK);
+    ZL.group = Z.group;   // (the group is the one thing the entries give differently)
+    CHECK(same_tables(ZL, Z));
 
     std::vector<uint8_t> bits((size_t)n_inputs * instances);
     for (auto &b : bits) b = (uint8_t)rnd(2);
@@ -177,8 +188,9 @@ static void check_rejected() {
     // accepted: the largest shifts, NULL arrays, a shift on the constant (dropped)
     const int32_t edge[4] = {7, -7, 0, 0}, oedge[2] = {-7, 7};
     CHECK(circuit_plan(2, gates, edge, 2, outs, oedge, 2, 8, P) == SGFHE_OK && P.group == 8 && P.n_inputs == 2);
+    CHECK(P.term_shift[0] == 7 && P.term_shift[1] == -7 && P.out_shift[0] == -7 && P.out_shift[1] == 7);
     CHECK(circuit_plan(2, gates, nullptr, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.lanes());
-    for (int32_t d : P.in_shift) CHECK(d == 0);
+    for (int32_t d : P.term_shift) CHECK(d == 0);
     const uint32_t cgates[2] = {CIRC_FALSE | CIRC_NOT, 0}, couts[1] = {CIRC_FALSE};
     const int32_t cs[2] = {3, 0}, cos_[1] = {-3};
     CHECK(circuit_plan(1, cgates, cs, 1, couts, cos_, 1, 4, P) == SGFHE_OK);

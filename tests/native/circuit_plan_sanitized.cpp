@@ -8,6 +8,8 @@
 //     the wire in it is still to be read, every read finds the wire it expects, output wires survive to
 //     the end, and only wires something reads have a slot;
 //   - rows and calls: row = rank * instances + instance, calls of at most SGFHE_CIRCUIT_CALL_ROWS rows;
+//   - tables: every live node is a classic node of the caller's two terms, and the node table, the pack stage's
+//     pseudo-level, the job table and the image hold together (tests/native/circuit_tables.h);
 //   - malformed circuits are refused.
 // Prints a digest of all plans (the plain build must print the same).
 #include <stdio.h>
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "circuit.h"
+#include "circuit_tables.h"
 
 using namespace sgfhe;
 
@@ -129,6 +132,9 @@ int main() {
             }
         }
         CHECK(P.widest == widest);
+        // ---- tables
+        check_plan_tables(P);
+        for (size_t k = 0; k < P.live(); k++) check_node_terms(P, k, 0, 2, &gates[2 * P.order[k]], nullptr, nullptr);
         // ---- which wires are read, and until when
         std::vector<uint32_t> readers_left(n_wires, 0);
         std::vector<uint8_t> is_out(n_wires, 0);
@@ -171,7 +177,8 @@ int main() {
                 const uint32_t r0 = (uint32_t)(row0 / inst), r1 = (uint32_t)((row0 + rows - 1) / inst);
                 CHECK(r1 < P.level_start[L + 1] - k0);
                 for (uint32_t rk = r0; rk <= r1; rk++)   // gather
-                    for (int j = 0; j < 2; j++) expect_ref(P.in_ref[2 * (k0 + rk) + j], gates[2 * P.order[k0 + rk] + j]);
+                    for (int j = 0; j < 2; j++)
+                        expect_ref(P.term_ref[P.term_start[k0 + rk] + j], gates[2 * P.order[k0 + rk] + j]);
                 for (uint32_t rk = r0; rk <= r1; rk++)   // scatter: the slot may not hold a wire still to be read
                     for (uint32_t w = 0; w < 3; w++) {
                         const uint32_t s = P.out_slot[3 * (k0 + rk) + w];
@@ -191,7 +198,7 @@ int main() {
         }
         for (size_t o = 0; o < n_outputs; o++) expect_ref(P.out_ref[o], outs[o]);   // outputs survive to the end
         mix(P.levels); mix(P.live()); mix(P.widest); mix(P.slots); mix(calls);
-        for (uint32_t v : P.in_ref) mix(v);
+        for (uint32_t v : P.term_ref) mix(v);
         for (uint32_t v : P.out_slot) mix(v);
     }
     printf("%016llx\n", (unsigned long long)digest);

@@ -4,8 +4,10 @@
 //     weights -2, -1, 1, 2, with NOTs, constants and (for G > 1) lane shifts on every term, are planned for
 //     (group, instances) = (1, 5), (8, 72) and (64, 192), and circuit_plain_bits is compared, bit by bit, with an
 //     evaluation of the ORIGINAL arrays one instance at a time -- HI, MID, LOW from s = the sum of w x mod 4;
-//   - the plan's CSR tables are compared with the arrays, its in_ref3 marks with the node kinds, and a plan whose sum
-//     nodes all have two or three unit weights has no CSR tables and equals the sgfhe_circuit_create3 plan;
+//   - the plan's node table is compared with the arrays, term by term, its kinds with the node kinds, and its image
+//     checked (tests/native/circuit_tables.h); a plan whose sum nodes all have two or three unit weights equals the
+//     sgfhe_circuit_create3 plan -- whose two-term sum nodes carry one more term, the constant FALSE -- and gives the
+//     same circuit_plain_bits word for word;
 //   - an output that names a LOW wire is never direct, one that names HI or MID unshifted is;
 //   - the inputs the planner must refuse return SGFHE_ERR_INVALID_ARG without a single allocation (the global
 //     operator new is counted) and leave the plan they were given untouched.
@@ -23,12 +25,18 @@ void *operator new(size_t n) {
     throw std::bad_alloc();
 }
 void *operator new[](size_t n) { return operator new(n); }
+void *operator new(size_t n, const std::nothrow_t &) noexcept {   // (std::stable_sort's buffer)
+    g_allocs++;
+    return malloc(n ? n : 1);
+}
+void *operator new[](size_t n, const std::nothrow_t &t) noexcept { return operator new(n, t); }
 void operator delete(void *p) noexcept { free(p); }
 void operator delete[](void *p) noexcept { free(p); }
 void operator delete(void *p, size_t) noexcept { free(p); }
 void operator delete[](void *p, size_t) noexcept { free(p); }
 
 #include "circuit.h"
+#include "circuit_tables.h"
 
 using namespace sgfhe;
 
@@ -105,15 +113,6 @@ static int32_t plan_w(const Arrays &A, uint32_t G, CircuitPlan &P) {
                           A.gates(), A.outs.data(), A.oshift.data(), A.outs.size(), G, P);
 }
 
-static bool is_wide(const Arrays &A, size_t g) {
-    if (!A.kind[g]) return false;
-    const uint32_t fan = A.start[g + 1] - A.start[g];
-    if (fan != 2 && fan != 3) return true;
-    for (uint32_t i = A.start[g]; i < A.start[g + 1]; i++)
-        if (A.weight[i] != 1) return true;
-    return false;
-}
-
 // the model of include/sgfhe_hip.h, one instance at a time
 static int lane_read(const std::vector<uint8_t> &wire, uint32_t ref, int32_t d, size_t t, uint32_t G) {
     int v = 0;
@@ -126,33 +125,15 @@ static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32
     const Arrays A = random_circuit(n_inputs, n_gates, n_outputs, G, false);
     CircuitPlan P;
     CHECK(plan_w(A, G, P) == SGFHE_OK);
-    CHECK(P.group == G && P.in_ref.size() == 2 * P.live() && P.in_ref3.size() == P.live());
-    uint32_t wide = 0, marked = 0;
-    for (size_t k = 0; k < P.live(); k++) {
-        const size_t g = P.order[k];
-        wide += is_wide(A, g);
-        marked += A.kind[g] != 0;
-        CHECK((P.in_ref3[k] == CIRC_NO_INPUT) == (A.kind[g] == 0));
-        CHECK(P.gate3_in((uint32_t)k, (uint32_t)k) == (A.kind[g] != 0));
-        if (is_wide(A, g)) CHECK(P.in_ref[2 * k] == CIRC_FALSE && P.in_ref[2 * k + 1] == CIRC_FALSE && P.in_ref3[k] == CIRC_FALSE);
+    CHECK(P.group == G);
+    check_plan_tables(P);
+    uint32_t sums = 0;
+    for (size_t k = 0; k < P.live(); k++) {   // every live node's terms in order
+        const size_t g = P.order[k], i = A.start[g];
+        sums += A.kind[g];
+        check_node_terms(P, k, A.kind[g], A.start[g + 1] - i, &A.refs[i], &A.shift[i], &A.weight[i]);
     }
-    CHECK(P.wide == wide && P.three == marked && P.wsum() == (wide > 0));
-    if (P.wsum()) {   // the CSR tables: every live node's terms in order
-        CHECK(P.w_start.size() == P.live() + 1 && P.w_start[0] == 0 && P.w_start[P.live()] == P.w_ref.size());
-        CHECK(P.w_shift.size() == P.w_ref.size() && P.w_weight.size() == P.w_ref.size() && P.w_row.size() == P.w_ref.size());
-        for (size_t k = 0; k < P.live(); k++) {
-            const size_t g = P.order[k];
-            CHECK(P.w_start[k + 1] - P.w_start[k] == A.start[g + 1] - A.start[g]);
-            for (uint32_t j = 0; j < A.start[g + 1] - A.start[g]; j++) {
-                const uint32_t i = A.start[g] + j, q = P.w_start[k] + j;
-                CHECK(P.w_weight[q] == A.weight[i] && (P.w_ref[q] & CIRC_NOT) == (A.refs[i] & CIRC_NOT));
-                CHECK(P.w_shift[q] == ((A.refs[i] & ~CIRC_NOT) == CIRC_FALSE ? 0 : A.shift[i]));
-                CHECK(((P.w_ref[q] & ~CIRC_NOT) == CIRC_FALSE) == ((A.refs[i] & ~CIRC_NOT) == CIRC_FALSE));
-            }
-        }
-    } else {
-        CHECK(P.w_start.empty() && P.w_ref.empty());
-    }
+    CHECK(P.sum_before[P.live()] == sums);
     for (size_t o = 0; o < n_outputs; o++) {
         const uint32_t id = A.outs[o] & ~CIRC_NOT;
         if (id == CIRC_FALSE || id < n_inputs || P.out_shift[o]) {
@@ -206,7 +187,8 @@ static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32
     return compared;
 }
 
-// sum nodes of two or three unit weights only: no CSR tables, and the plan of the [n_gates][3] arrays, table by table
+// sum nodes of two or three unit weights only: the plan of the [n_gates][3] arrays, table by table -- but for the third
+// term (FALSE, shift 0, weight 1) those arrays give a sum node of two terms -- and the same plaintext bits
 static void check_unit_is_create3(uint32_t G) {
     const uint32_t n_inputs = 3, n_gates = 14, n_outputs = 5;
     const Arrays A = random_circuit(n_inputs, n_gates, n_outputs, G, true);
@@ -221,12 +203,34 @@ static void check_unit_is_create3(uint32_t G) {
     CircuitPlan P, Z;
     CHECK(plan_w(A, G, P) == SGFHE_OK);
     CHECK(circuit_plan3(n_inputs, g3.data(), s3.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G, Z) == SGFHE_OK);
-    CHECK(!P.wsum() && !Z.wsum() && P.w_start.empty() && P.three == Z.three);
+    check_plan_tables(P);
+    check_plan_tables(Z);
     CHECK(P.levels == Z.levels && P.widest == Z.widest && P.slots == Z.slots && P.group == Z.group);
     CHECK(P.level == Z.level && P.order == Z.order && P.level_start == Z.level_start && P.input_slot == Z.input_slot);
-    CHECK(P.in_ref == Z.in_ref && P.out_slot == Z.out_slot && P.out_ref == Z.out_ref && P.in_row == Z.in_row);
-    CHECK(P.in_shift == Z.in_shift && P.out_shift == Z.out_shift && P.out_node == Z.out_node && P.out_gate == Z.out_gate);
-    CHECK(P.in_ref3 == Z.in_ref3 && P.in_shift3 == Z.in_shift3 && P.in_row3 == Z.in_row3 && P.three_before == Z.three_before);
+    CHECK(P.node_kind == Z.node_kind && P.sum_before == Z.sum_before && P.out_slot == Z.out_slot && P.out_ref == Z.out_ref);
+    CHECK(P.out_shift == Z.out_shift && P.out_node == Z.out_node && P.out_gate == Z.out_gate);
+    CHECK(P.jobs == Z.jobs && P.job_k == Z.job_k);
+    size_t padded = 0;
+    for (size_t k = 0; k < P.node_kind.size(); k++) {   // (the pseudo-level's nodes included)
+        const uint32_t p0 = P.term_start[k], np = P.term_start[k + 1] - p0, z0 = Z.term_start[k], nz = Z.term_start[k + 1] - z0;
+        CHECK(nz == np || (nz == np + 1 && np == 2 && P.node_kind[k] == 1));
+        for (uint32_t j = 0; j < np; j++) {
+            CHECK(P.term_ref[p0 + j] == Z.term_ref[z0 + j] && P.term_shift[p0 + j] == Z.term_shift[z0 + j]);
+            CHECK(P.term_weight[p0 + j] == Z.term_weight[z0 + j]);
+            if (k < P.live()) CHECK(P.term_row[p0 + j] == Z.term_row[z0 + j]);
+        }
+        if (nz == np) continue;
+        padded++;
+        CHECK(Z.term_ref[z0 + 2] == CIRC_FALSE && Z.term_shift[z0 + 2] == 0 && Z.term_weight[z0 + 2] == 1);
+        CHECK(Z.term_row[z0 + 2] == CIRC_FALSE);
+    }
+    CHECK(Z.term_ref.size() == P.term_ref.size() + padded);
+    const size_t instances = 3 * (size_t)(G > 1 ? G * 9 : 70);   // (ragged last word)
+    std::vector<uint8_t> bits((size_t)n_inputs * instances);
+    for (auto &b : bits) b = (uint8_t)rnd(2);
+    std::vector<uint64_t> tp, tz;
+    CHECK(circuit_plain_bits(P, bits.data(), instances, tp) == SGFHE_OK);
+    CHECK(circuit_plain_bits(Z, bits.data(), instances, tz) == SGFHE_OK && tp == tz && !tp.empty());
 }
 
 static void check_rejected() {
@@ -285,11 +289,13 @@ static void check_rejected() {
         r65[4] = CIRC_FALSE | CIRC_NOT, sh64[4] = 5;
         for (size_t i = 2; i < 66; i++) w65[i] = (i & 1) ? -2 : 2;
         CHECK(circuit_plan_w(2, kind, s64, r65.data(), sh64.data(), w65.data(), 2, outs, nullptr, 2, 8, P) == SGFHE_OK);
-        CHECK(P.wide == 1 && P.n_inputs == 2 && P.live() == 1 && P.w_ref.size() == 64);   // (node 0 is pruned)
-        CHECK(P.w_shift[0] == 7 && P.w_shift[1] == -7 && P.w_shift[2] == 0 && P.out_node[0] == 0 && P.out_node[1] == CIRC_NONE);
+        CHECK(P.node_kind[0] == 1 && P.n_inputs == 2 && P.live() == 1 && P.term_row.size() == 64);   // (node 0 is pruned)
+        CHECK(P.term_shift[0] == 7 && P.term_shift[1] == -7 && P.term_shift[2] == 0 && P.out_node[0] == 0 && P.out_node[1] == CIRC_NONE);
+        for (size_t i = 0; i < 64; i++) CHECK(P.term_weight[i] == w65[2 + i]);
+        check_plan_tables(P);
     }
     CHECK(circuit_plan_w(2, kind, start, refs, nullptr, weight, 2, outs, nullptr, 2, 1, P) == SGFHE_OK);
-    CHECK(P.wide == 1 && P.three == 1 && P.levels == 2 && P.w_start.size() == 3 && P.w_ref.size() == 5);
+    CHECK(P.sum_before[2] == 1 && P.levels == 2 && P.live() == 2 && P.term_start[2] == 5 && P.term_row.size() == 5);
 }
 
 int main() {

@@ -231,7 +231,7 @@ def test_crc16_ccitt_against_binascii(S):
 
 def test_wsum_planner_under_asan_and_ubsan(tmp_path):
     """tests/native/circuit_wsum_sanitized.cpp: circuit_plain_bits of plans with sum nodes of fan-in 1 to 64 and
-    shifted terms against a per-instance evaluation at (G, instances) = (1, 5), (8, 72), (64, 192); the CSR tables;
+    shifted terms against a per-instance evaluation at (G, instances) = (1, 5), (8, 72), (64, 192); the node table and its image;
     refused inputs return without allocating.  A child process of its own; the same program without the sanitizers
     compares as many bits."""
     gxx = shutil.which("g++")

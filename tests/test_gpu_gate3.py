@@ -1,5 +1,5 @@
-"""Three-input nodes on the device (sgfhe_circuit_create3): k_circ_gather3 and the XOR3
-kernels against the host model -- `circuit.replay_levels` / `replay_ct` / `replay_ct_direct` -- driven by the oracle's
+"""Three-input nodes on the device (sgfhe_circuit_create3): k_circ_gather, which stages such a
+node as the sum node of three unit weights, (x + y + z, 0), and the XOR3 kernels against the host model -- `circuit.replay_levels` / `replay_ct` / `replay_ct_direct` -- driven by the oracle's
 two-input bootstrap on (x + y, z), or by a second ctx's own bootstrap calls, in both flatten modes; decryption
 against `evaluate_plain`; lanes with a call boundary inside a level; the ciphertext form refreshed and direct; the
 probe; the all-NONE plan against the plain plan; Params(1024).  Every comparison is for equality of every word.

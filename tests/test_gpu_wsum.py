@@ -1,4 +1,4 @@
-"""Weighted-sum nodes on the device (sgfhe_circuit_create_w): k_circ_gather_w and the reused
+"""Weighted-sum nodes on the device (sgfhe_circuit_create_w): k_circ_gather and the
 XOR3 kernels against the host model -- `circuit.replay_levels` / `replay_ct` / `replay_ct_direct` -- driven by the
 oracle's two-input bootstrap on (U, FALSE), or by a second ctx's own bootstrap calls, in both flatten modes; decryption
 against `evaluate_plain`; lanes with a call boundary inside a level; fan-in 64; the ciphertext form refreshed, direct and
@@ -132,7 +132,7 @@ def test_truth_table_every_weight_tuple_p64(S, oc):
 
 def test_unit_weight_sum_node_gives_the_bytes_of_gate3(S, oc):
     """(1, x), (1, y), (1, z) against gate3(x, y, z), on all three wires in both modes: as a plan of its own (it takes
-    sgfhe_circuit_create3) and inside a plan that holds a wide node as well, which takes k_circ_gather_w."""
+    sgfhe_circuit_create3) and inside a plan that holds a sum node of another shape as well."""
     params, o, sk, bkey, (eng,) = _setup64(S, oc, 511)
     a = S.Circuit(3)
     x, y, z = a.inputs
@@ -403,6 +403,72 @@ def test_gf2_matvec_ciphertext_form_refreshed_direct_and_lifted(S, oc, N):
     ref.close()
 
 
+def test_lanes_every_node_kind_and_the_pack_level_through_one_gather(S, oc):
+    """G = 8, one block of PackedCiphertexts (64 instances): a classic node and a gate3 on the inputs share level 1, a
+    sum node of five terms on their bootstrapped wires -- weights 2, -2, 1, -1, 1, lane shifts -1, +7, +1, -7 -- is
+    level 2, and the outputs take every path of the pack stage: a negated, shifted gate wire, the LOW wire, the
+    unshifted HI wire (direct), an input wire and TRUE.  Level calls and the pack stage's pseudo-level go through the
+    one k_circ_gather.  flags = 0 against replay_ct, PACK_DIRECT and PACK_DIRECT | PACK_LIFT against replay_ct_direct on
+    a second ctx with the calls each makes, in both flatten modes; every form decrypts to evaluate_plain.  Inputs are
+    crafted with |e| <= Dr/16 = 16, so three of them stay below Dr/2 = 128; every node's input-sum error is measured
+    from the replay with the secret key before anything is compared."""
+    from sgfhe_jl_amd import circuit as C
+    from sgfhe_jl_amd.scheme import split_ciphertext_array
+    params, o, sk, bkey, (eng, ref) = _setup64(S, oc, 591, engines=2)
+    n, G = params.n, 8
+    c = S.Circuit(3, group=G)
+    x, y, z = c.inputs
+    g = c.gate(x, ~y.lane(1))
+    m = c.gate3(x, y, z.lane(-1))
+    hi, mid, low = c.sum_node([(2, g[0].lane(-1)), (-2, ~g[1].lane(7)), (1, m[0].lane(1)), (-1, m[1].lane(-7)), (1, ~g[2])])
+    c.output(~g[1].lane(-1), low, hi, x, S.Circuit.TRUE)
+    assert c.has_wsum and c.has_gate3 and c.schedule() == [[0, 1], [2]] and [c.kind(k) for k in range(3)] == ["classic", "gate3", "sum"]
+    bits = np.random.default_rng(592).integers(0, 2, size=(3, 1, n)).astype(bool)
+    plain = c.evaluate_plain(bits.reshape(3, -1))
+    assert all(0 < plain[q].sum() < n for q in range(4)) and plain[4].all()
+    a, b = LR.craft_cts(S, params, sk, bits, 593)
+    inputs = split_ciphertext_array(a, b, n, params.r).reshape(3, n, n + 1)
+    _set_mode([ref], None)
+    worst = WR.input_sum_errors(S, params, sk, c, inputs, bits.reshape(3, -1),
+                                lambda call, a1, b1, a2, b2: ref.bootstrap_batch(a1, b1, a2, b2))
+    print("largest input-sum error per node:", worst, "against Dr/2 =", params.Dr // 2)
+    assert len(worst) == 3 and max(worst.values()) < params.Dr // 2, worst
+    for key in (None, KEY32):
+        what = "randomised" if key else "deterministic"
+        _set_mode([eng, ref], key)
+        (w, v), lwe = eng.circuit_run_ct(c, a, b, packed=True, lwe=True)
+        calls = []
+        (rw, rv), rlwe = C.replay_ct(c, a, b, params,
+                                     lambda call, a1, b1, a2, b2: (calls.append(len(b1)), ref.bootstrap_batch(a1, b1, a2, b2))[1],
+                                     lambda call, pa, pb: (calls.append(-len(pb)), ref.pack_encrypted_bits(pa, pb))[1])
+        assert calls == [2 * n, n, -5]
+        assert np.array_equal(lwe, rlwe), "out_lwe differs from replay_ct (%s)" % what
+        assert np.array_equal(w, rw) and np.array_equal(v, rv), "(w, v) differ from replay_ct (%s)" % what
+        assert np.array_equal(_decrypt_ct(S, params, sk, w, v), plain) and np.array_equal(_decrypt(S, params, sk, lwe), plain)
+        for lift in (False, True):
+            _set_mode([eng, ref], key)
+            (dw, dv), dlwe = eng.circuit_run_ct(c, a, b, packed=True, lwe=True, direct=True, lift=lift)
+            assert np.array_equal(dlwe, lwe), "direct out_lwe differs from the flags = 0 run (%s)" % what
+            raw_calls, tails = [], []
+
+            def boot_raw(call, a1, b1, a2, b2):
+                raw_calls.append(len(b1))
+                return ref.bootstrap_batch(a1, b1, a2, b2, raw=True)
+
+            def tail(call, group):
+                tails.append(len(group))
+                return ref.pack_lwe_modq(group)
+
+            (rw, rv), rlwe = C.replay_ct_direct(c, a, b, params, boot_raw, tail, lift=lift)
+            assert raw_calls == [2 * n, n] + ([] if lift else [4 * n]) and tails == [5]     # (HI alone is direct)
+            assert np.array_equal(rlwe, lwe)
+            assert np.array_equal(dw, rw) and np.array_equal(dv, rv), "(w, v) differ from replay_ct_direct (%s, lift %s)" % (what, lift)
+            assert not np.array_equal(dw[2], w[2])                        # HI took the direct path
+            assert np.array_equal(_decrypt_ct(S, params, sk, dw, dv), plain), (what, lift)
+    eng.close()
+    ref.close()
+
+
 def test_probe_records_of_a_sum_node_run(S, oc):
     """The records of sgfhe_circuit_run_probe equal tests/noise_ref.py on the rows of a second run that outputs every
     wire; no row is wrong; the record of a LOW wire is the node's input-sum error (against s mod 2) up to 2 e_HI."""
@@ -456,7 +522,7 @@ def test_probe_records_of_a_sum_node_run(S, oc):
 def test_plans_without_sum_nodes_keep_their_entry_points_and_bytes(S, oc):
     """A circuit of classic and three-input nodes still takes sgfhe_circuit_create3 and gives the oracle's bytes; the
     same arrays restated through sgfhe_circuit_create_w -- classic nodes classic, three-input nodes three unit weights
-    -- give those bytes too (no wide node: the kernels of the create3 plan)."""
+    -- give those bytes too."""
     params, o, sk, bkey, (eng,) = _setup64(S, oc, 571)
     rng = np.random.default_rng(572)
     c = S.Circuit(3)

@@ -6,7 +6,7 @@
       every parity node's HI and LOW wire -- LOW = U - 2 HI carries the error of the doubled sum -- against Dr/2.
   python tools/wsum_noise.py --trace [--dir DIR]
       examples/encrypted_crc.py --direct (one block) in a child process under `rocprofv3 --kernel-trace --stats`: the
-      share of k_circ_gather_w in the kernel time of the run."""
+      share of k_circ_gather in the kernel time of the run."""
 
 import argparse
 import csv
@@ -72,8 +72,8 @@ def trace(args):
         if "k_circ" in r["Name"] or ns > 0.01 * tot:
             print("  %-60s calls %7s  total %10.3f ms  avg %9.1f us  %6.3f %%"
                   % (r["Name"][:60], r["Calls"], ns * 1e-6, float(r["AverageNs"]) * 1e-3, 100 * ns / tot))
-    g = sum(float(r["TotalDurationNs"]) for r in rows if "k_circ_gather_w" in r["Name"])
-    print("k_circ_gather_w: %.3f ms = %.4f %% of the kernel time" % (g * 1e-6, 100 * g / tot))
+    g = sum(float(r["TotalDurationNs"]) for r in rows if "k_circ_gather" in r["Name"])
+    print("k_circ_gather: %.3f ms = %.4f %% of the kernel time" % (g * 1e-6, 100 * g / tot))
 
 
 def main():

@@ -2,9 +2,12 @@
 // graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
 // slot of the device wire table by liveness, fixes the row and call numbering of a run, and writes every node's inputs
 // -- whichever entry the arrays came through -- into one CSR node table, which it lays with the other device tables
-// into the one image a run uploads; circuit_plain_bits evaluates a planned circuit in clear for the noise probe.  Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp,
-// circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp, circuit_gate3_sanitized.cpp and circuit_wsum_sanitized.cpp
-// drive it under ASan / UBSan on the CPU.
+// into the one image a run uploads; circuit_plain_bits evaluates a planned circuit in clear for the noise probe.
+// The call arithmetic of a run lives here too (at the end): circuit_level_call, circuit_job_chunk, circuit_pack_runs and
+// circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
+// Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
+// circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp and circuit_calls_sanitized.cpp drive it under ASan / UBSan
+// on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -460,6 +463,93 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
         }
     }
     return SGFHE_OK;
+}
+
+// ---- the call arithmetic of a run (sgfhe_circuit_run, _run_ct[_ex], _run_probe) ----------------------------------
+// Which rows, nodes and direct-pack jobs a level call covers, how a long job range is cut into grids, which
+// ciphertexts of a pack group are bootstrapped (or lifted) first, and what a run's buffers must hold.  Pure functions
+// of the plan: the engine walks them in this order -- every level L = 1 .. levels in calls of SGFHE_CIRCUIT_CALL_ROWS
+// rows from row 0, then the pack groups of `cpc` ciphertexts from ciphertext 0 -- and that walk is the run's call
+// numbering (tests/native/circuit_calls_sanitized.cpp restates it row by row).
+
+// The call of level L that starts at row `row0` (a multiple of SGFHE_CIRCUIT_CALL_ROWS below the level's rows).
+struct CircuitCall {
+    uint32_t k0;       // the level's first node in `order`
+    uint32_t rows;     // rows row0 .. row0 + rows of the level
+    uint32_t ka, kb;   // the live nodes order[ka .. kb] (inclusive) those rows belong to
+    size_t j0, j1;     // the direct-pack jobs [j0, j1) those nodes produce: with any, a direct run leaves the call
+                       // un-reduced
+    bool sum;          // one of the nodes is a sum node: the call takes an XOR3 kernel for its LOW rows
+};
+inline CircuitCall circuit_level_call(const CircuitPlan &P, uint32_t L, uint64_t row0, uint64_t instances) noexcept {
+    CircuitCall C;
+    C.k0 = P.level_start[L];
+    C.rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, P.level_rows(L, instances) - row0);
+    C.ka = C.k0 + (uint32_t)(row0 / instances);
+    C.kb = C.k0 + (uint32_t)((row0 + C.rows - 1) / instances);
+    C.j0 = (size_t)(std::lower_bound(P.job_k.begin(), P.job_k.end(), C.ka) - P.job_k.begin());
+    C.j1 = (size_t)(std::upper_bound(P.job_k.begin(), P.job_k.end(), C.kb) - P.job_k.begin());
+    C.sum = P.gate3_in(C.ka, C.kb);
+    return C;
+}
+
+// The grid that takes the jobs from `j` on of a call's range [j0, j1): a grid holds CIRCUIT_GRID_Y rows of workgroups,
+// one per job, and the first grid of a call one more -- the block that scatters the call's rows into the wire table
+// (`wires`).  The next grid starts at j + nj.
+constexpr uint32_t CIRCUIT_GRID_Y = 65535;
+struct CircuitJobChunk {
+    uint32_t nj, wires;   // jobs j .. j + nj; 1 when the wire block rides along: gridDim.y = nj + wires
+};
+inline CircuitJobChunk circuit_job_chunk(size_t j, size_t j0, size_t j1) noexcept {
+    const uint32_t wires = j == j0;
+    return {(uint32_t)std::min<size_t>(j1 - j, CIRCUIT_GRID_Y - wires), wires};
+}
+
+// The ciphertexts q0 .. q0 + cnt of a pack group (q = output * blocks + block) that are not direct -- their output
+// has no out_node -- as maximal runs of consecutive ones, `rank` counting them from 0 within the group: they are
+// bootstrapped as one call (row = rank * n + bit) or lifted, one gather or lift per run.  `all`: every ciphertext
+// counts (the plain form refreshes the whole group: one run).  Returns how many ciphertexts the runs hold; `runs` may
+// be NULL to count only, otherwise it is cleared first (and is what may allocate here).
+struct CircuitPackRun {
+    size_t q, rank, len;
+};
+inline size_t circuit_pack_runs(const CircuitPlan &P, size_t blocks, size_t q0, size_t cnt, bool all,
+                                std::vector<CircuitPackRun> *runs) {
+    if (runs) runs->clear();
+    size_t rank = 0;
+    for (size_t q = q0; q < q0 + cnt; q++) {
+        if (!all && P.out_node[q / blocks] != CIRC_NONE) continue;
+        if (runs) {
+            if (!runs->empty() && runs->back().q + runs->back().len == q) runs->back().len++;
+            else runs->push_back({q, rank, 1});
+        }
+        rank++;
+    }
+    return rank;
+}
+
+// What the buffers of a run over `instances` hold at most, for rows of n + 1 words.  `pack`: `blocks` ciphertexts per
+// output are packed (instances = blocks * n); `direct` (with pack) and `lift` (with direct) as the flags of
+// sgfhe_circuit_run_ct_ex.
+struct CircuitRunSizes {
+    uint64_t max_rows;    // rows of the largest level call
+    size_t n_ct;          // ciphertexts packed: n_outputs * blocks, 0 without pack
+    size_t cpc;           // ciphertexts of the largest pack group: min(max(1, SGFHE_CIRCUIT_CALL_ROWS / n), n_ct)
+    size_t max_ref;       // the most ciphertexts any group bootstraps first (circuit_pack_runs); 0 with lift
+    uint64_t work_rows;   // rows of the largest bootstrap call of the run
+};
+inline CircuitRunSizes circuit_run_sizes(const CircuitPlan &P, uint64_t instances, size_t n, size_t blocks, bool pack,
+                                         bool direct, bool lift) noexcept {
+    CircuitRunSizes S = {};
+    for (uint32_t L = 1; L <= P.levels; L++)
+        S.max_rows = std::max(S.max_rows, std::min<uint64_t>(P.level_rows(L, instances), SGFHE_CIRCUIT_CALL_ROWS));
+    direct = direct && pack;
+    S.n_ct = pack ? (size_t)P.n_outputs * blocks : 0;
+    S.cpc = std::min(std::max<size_t>(1, SGFHE_CIRCUIT_CALL_ROWS / n), S.n_ct);
+    for (size_t q0 = 0; !(lift && direct) && q0 < S.n_ct; q0 += S.cpc)
+        S.max_ref = std::max(S.max_ref, circuit_pack_runs(P, blocks, q0, std::min(S.cpc, S.n_ct - q0), !direct, nullptr));
+    S.work_rows = std::max<uint64_t>(S.max_rows, (uint64_t)S.max_ref * n);
+    return S;
 }
 
 }  // namespace sgfhe

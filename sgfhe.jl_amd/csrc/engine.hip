@@ -244,7 +244,7 @@ struct sgfhe_ctx {
     DevBuf<uint32_t> circ_tab;
     // sgfhe_circuit_run_ct: the uploaded input ciphertexts [a | b], each [n_inputs][blocks][N]
     DevBuf<uint64_t> circ_ct;
-    // work buffers of the packing path (pack_device), shared by sgfhe_pack_encrypted_bits and the pack stage
+    // work buffers of the packing path (pack_tail), shared by sgfhe_pack_encrypted_bits and the pack stage
     // of sgfhe_circuit_run_ct, grown and freed like the circuit buffers: one call's bootstrap inputs
     // [a1 | a2 | b1 | b2], its un-reduced results, the flattened as_i, the group sums, and (w | v)
     DevBuf<uint64_t> pack_lwe, pack_pdig, pack_wv;
@@ -1783,6 +1783,32 @@ static int32_t circ_grow(sgfhe_ctx *c, DevBuf<T> &buf, size_t words) {
                                       " bytes failed");
 }
 
+// A synchronous entry of the circuit and pack paths: nothing of an earlier call is in flight when `queued` runs (it
+// may regrow ctx buffers, then queues on the ctx stream and waits for it); should it fail, whatever it queued finishes
+// before the buffers can be touched again.
+extern "C++" template <class F>
+static int32_t run_drained(sgfhe_ctx *c, F &&queued) {
+    (void)hipSetDevice(c->device);
+    int32_t rc = drain(c);
+    if (rc) return rc;
+    if ((rc = queued())) {
+        (void)hipStreamSynchronize(c->stream);
+        c->pending = false;
+    }
+    return rc;
+}
+
+// [a1 | a2 | b1 | b2 | res]: the bootstrap inputs of `rows` rows (a: n words, b: one) carved out of `base`, and what
+// follows them (the result rows, where the buffer holds them)
+struct Staging {
+    uint64_t *a1, *a2, *b1, *b2, *res;
+    Staging from_row(size_t off, size_t n) const { return {a1 + off * n, a2 + off * n, b1 + off, b2 + off, res}; }
+};
+static Staging staging(uint64_t *base, size_t rows, size_t n) {
+    uint64_t *a2 = base + rows * n, *b1 = a2 + rows * n;
+    return {base, a2, b1, b1 + rows, b1 + 2 * rows};
+}
+
 int32_t sgfhe_ctx_destroy(sgfhe_ctx *c) {
     if (!c) return SGFHE_OK;
     (void)hipSetDevice(c->device);
@@ -2552,18 +2578,34 @@ static int32_t pack_tail(sgfhe_ctx *c, const ulonglong2 *raw, uint32_t rstride, 
     return SGFHE_OK;
 }
 
-// pack_encrypted_bits (fhe.jl:660-696) of `count` groups of n LWEs resident on the device, queued on `st`:
-// the count * n bootstraps of (a1, b1) = trivial encryption of 1 with (a2, b2) = the bits (one call of the
-// ctx's draw stream), the flatten of every as_i, the half-width external products and the finish into
-// d_w / d_v [count][m].  The caller has grown the work buffers (pack_grow) and checked pack_G.
-static int32_t pack_device(sgfhe_ctx *c, const uint64_t *d_a1, const uint64_t *d_b1, const uint64_t *d_a2,
-                           const uint64_t *d_b2, size_t count, uint64_t *d_w, uint64_t *d_v, hipStream_t st) {
-    // rng != nothing: the n bootstraps and the flatten of every as_i draw from the ctx's ChaCha stream as one
-    // call (the reference passes the same rng to both, fhe.jl:673,683-684)
-    int32_t rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, count * c->n, (uint64_t *)c->pack_raw.p,
-                                  SGFHE_FLAG_RAW_MODQ, c->n, nullptr, st);
+// Everything sgfhe_pack_encrypted_bits does on the device (run_drained waits for the stream when a step fails):
+// pack_encrypted_bits (fhe.jl:660-696) of `count` groups of n LWEs -- the count * n bootstraps of the trivial encryption
+// of 1 with the bits, then the tail as the SAME call of the ctx's draw stream (rng != nothing: the reference passes one
+// rng to both, fhe.jl:673,683-684)
+static int32_t pack_bits_queued(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out_w,
+                                uint64_t *out_v) {
+    const size_t n = c->n, M = c->M;
+    const size_t nb = count * n;  // bootstraps
+    hipStream_t st = c->stream;
+    if (!(pack_group(c)))
+        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
+    if (pack_grow(c, count, count, count)) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(hipErrorOutOfMemory));
+    // [a1 = 0 | a2 | b1 = Dr | b2]: trivial encryption of 1 paired with every bit (fhe.jl:669-673)
+    const Staging S = staging(c->pack_lwe.p, nb, n);
+    uint64_t *d_w = c->pack_wv.p, *d_v = d_w + count * M;
+    HIPCHK(c, hipMemsetAsync(S.a1, 0, nb * n * 8, st));
+    std::vector<uint64_t> ones(nb, c->par.r / 4);
+    HIPCHK(c, hipMemcpyAsync(S.b1, ones.data(), nb * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.a2, a, nb * n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.b2, b, nb * 8, hipMemcpyHostToDevice, st));
+    int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ, c->n,
+                                  nullptr, st);
     if (rc) return rc;
-    return pack_tail(c, c->pack_raw.p, 3 * (c->n + 1), count, d_w, d_v, c->last_call, st);
+    if ((rc = pack_tail(c, c->pack_raw.p, 3 * (uint32_t)(n + 1), count, d_w, d_v, c->last_call, st))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_v, d_v, count * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return SGFHE_OK;
 }
 
 int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, size_t count,
@@ -2572,32 +2614,27 @@ int32_t sgfhe_pack_encrypted_bits(sgfhe_ctx *c, const uint64_t *a, const uint64_
     SGFHE_LOCK(c);
     if (count == 0) return SGFHE_OK;
     if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    const size_t n = c->n, M = c->M;
-    const size_t nb = count * n;  // bootstraps
+    return run_drained(c, [&] { return pack_bits_queued(c, a, b, count, out_w, out_v); });
+}
+
+// everything sgfhe_pack_lwe_modq does on the device: `words` residues up, the tail, (w, v) down
+static int32_t pack_modq_queued(sgfhe_ctx *c, const uint64_t *lwe, size_t count, size_t words, uint64_t *out_w,
+                                uint64_t *out_v) {
+    const size_t M = c->M;
+    hipStream_t st = c->stream;
     if (!(pack_group(c)))
         return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
-    if (pack_grow(c, count, count, count)) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(hipErrorOutOfMemory));
-    hipError_t e = hipSuccess;
-    int32_t rc = SGFHE_OK;
-    do {
-        // [a1 = 0 | a2 | b1 = Dr | b2]: trivial encryption of 1 paired with every bit (fhe.jl:669-673)
-        uint64_t *d_a1 = c->pack_lwe.p, *d_a2 = d_a1 + nb * n, *d_b1 = d_a2 + nb * n, *d_b2 = d_b1 + nb;
-        uint64_t *d_w = c->pack_wv.p, *d_v = d_w + count * M;
-        if ((e = hipMemsetAsync(d_a1, 0, nb * n * 8, c->stream))) break;
-        std::vector<uint64_t> ones(nb, c->par.r / 4);
-        if ((e = hipMemcpyAsync(d_b1, ones.data(), nb * 8, hipMemcpyHostToDevice, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_a2, a, nb * n * 8, hipMemcpyHostToDevice, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_b2, b, nb * 8, hipMemcpyHostToDevice, c->stream))) break;
-        if ((rc = pack_device(c, d_a1, d_b1, d_a2, d_b2, count, d_w, d_v, c->stream))) break;
-        if ((e = hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
-        if ((e = hipMemcpyAsync(out_v, d_v, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    if (rc) (void)hipStreamSynchronize(c->stream);   // whatever was queued finishes before the buffers are touched again
-    return rc;
+    int32_t rc = pack_grow(c, count, count, 0, true);
+    if (rc) return rc;
+    const uint32_t call = c->rnd ? c->rnd_call++ : 0u;   // one call of the draw stream: the flatten of every as_i
+    c->last_call = call;
+    uint64_t *d_w = c->pack_wv.p, *d_v = d_w + count * M;
+    HIPCHK(c, hipMemcpyAsync(c->pack_raw.p, lwe, words * 16, hipMemcpyHostToDevice, st));
+    if ((rc = pack_tail(c, c->pack_raw.p, (uint32_t)(c->n + 1), count, d_w, d_v, call, st))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_v, d_v, count * M * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return SGFHE_OK;
 }
 
 int32_t sgfhe_pack_lwe_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uint64_t *out_w, uint64_t *out_v) {
@@ -2605,31 +2642,28 @@ int32_t sgfhe_pack_lwe_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uin
     SGFHE_LOCK(c);
     if (count == 0) return SGFHE_OK;
     if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    const size_t n = c->n, M = c->M;
-    const size_t words = count * n * (n + 1);   // residues
+    const size_t words = count * c->n * (c->n + 1);   // residues
     for (size_t i = 0; i < words; i++)
         if ((((u128)lwe[2 * i + 1] << 64) | lwe[2 * i]) >= c->Q)
             return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_pack_lwe_modq: residue " + std::to_string(i) + " is not below Q");
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    if (!(pack_group(c)))
-        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
-    int32_t rc = pack_grow(c, count, count, 0, true);
-    if (rc) return rc;
-    const uint32_t call = c->rnd ? c->rnd_call++ : 0u;   // one call of the draw stream: the flatten of every as_i
-    c->last_call = call;
-    hipError_t e = hipSuccess;
-    do {
-        uint64_t *d_w = c->pack_wv.p, *d_v = d_w + count * M;
-        if ((e = hipMemcpyAsync(c->pack_raw.p, lwe, words * 16, hipMemcpyHostToDevice, c->stream))) break;
-        if ((rc = pack_tail(c, c->pack_raw.p, (uint32_t)(n + 1), count, d_w, d_v, call, c->stream))) break;
-        if ((e = hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
-        if ((e = hipMemcpyAsync(out_v, d_v, count * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    if (rc) (void)hipStreamSynchronize(c->stream);   // whatever was queued finishes before the buffers are touched again
-    return rc;
+    return run_drained(c, [&] { return pack_modq_queued(c, lwe, count, words, out_w, out_v); });
+}
+
+// everything sgfhe_lwe_lift_modq does on the device
+// (the pack path's buffers: its LWE staging takes the rows, its un-reduced rows the residues)
+static int32_t lwe_lift_queued(sgfhe_ctx *c, const uint64_t *lwe, size_t words, uint64_t *out) {
+    hipStream_t st = c->stream;
+    int32_t rc;
+    if ((rc = circ_grow(c, c->pack_lwe, words))) return rc;
+    if ((rc = circ_grow(c, c->pack_raw, words))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->pack_lwe.p, lwe, words * 8, hipMemcpyHostToDevice, st));
+    const size_t blocks = std::min<size_t>((words + 255) / 256, (size_t)1 << 20);
+    hipLaunchKernelGGL(k_lwe_lift, dim3((uint32_t)blocks), dim3(256), 0, st, c->pack_lwe.p, c->pack_raw.p, cur(c).d_crt,
+                       words);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->pack_raw.p, words * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return SGFHE_OK;
 }
 
 int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uint64_t *out) {
@@ -2644,27 +2678,7 @@ int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uin
     for (size_t i = 0; i < words; i++)
         if (lwe[i] >= c->par.r)
             return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_lwe_lift_modq: word " + std::to_string(i) + " is not below r");
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    // (the pack path's buffers: its LWE staging takes the rows, its un-reduced rows the residues)
-    int32_t rc;
-    if ((rc = circ_grow(c, c->pack_lwe, words))) return rc;
-    if ((rc = circ_grow(c, c->pack_raw, words))) return rc;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = hipMemcpyAsync(c->pack_lwe.p, lwe, words * 8, hipMemcpyHostToDevice, c->stream))) break;
-        const size_t blocks = std::min<size_t>((words + 255) / 256, (size_t)1 << 20);
-        hipLaunchKernelGGL(k_lwe_lift, dim3((uint32_t)blocks), dim3(256), 0, c->stream, c->pack_lwe.p, c->pack_raw.p,
-                           cur(c).d_crt, words);
-        if ((e = hipGetLastError())) break;
-        if ((e = hipMemcpyAsync(out, c->pack_raw.p, words * 16, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess) {
-        rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-        (void)hipStreamSynchronize(c->stream);   // whatever was queued finishes before the buffers are touched again
-    }
-    return rc;
+    return run_drained(c, [&] { return lwe_lift_queued(c, lwe, words, out); });
 }
 
 int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const uint32_t *in,
@@ -3041,6 +3055,43 @@ static void noise_key_mask(const sgfhe_ctx *c, const uint64_t *sk, uint64_t *mas
 }
 static uint32_t noise_tiles(uint64_t instances) { return (uint32_t)((instances + NOISE_ROWS - 1) / NOISE_ROWS); }
 
+// The geometries in use (kernels.h, NoiseGeom).  `count` compact rows of n + 1 words, all of one wire, whose record and
+// row of the bit table is `wire`; the plain rows of sgfhe_lwe_noise are wire 0 of a table of one row
+static NoiseGeom noise_wire_rows(size_t n, uint32_t wire, uint32_t count, size_t bit_words) {
+    NoiseGeom G = {};
+    G.row_stride = n + 1;
+    G.wire0 = wire;
+    G.rows = G.instances = count;
+    G.tiles = noise_tiles(count);
+    G.bit_words = (uint32_t)bit_words;
+    G.n = (uint32_t)n;
+    return G;
+}
+// The result rows [rows][3][n + 1] of the level call `C` that starts at row `row0`: C.kb - C.ka + 1 nodes of three wires.
+// A call inside one node: tiles over its rows; a call over several nodes: tiles over every node's instances (a tile
+// never straddles two nodes; rows outside the call are skipped)
+static NoiseGeom noise_call_rows(size_t n, uint32_t n_inputs, const CircuitCall &C, uint64_t row0, uint32_t inst,
+                                 size_t bit_words) {
+    const bool one = C.ka == C.kb;
+    NoiseGeom G = noise_wire_rows(n, (uint32_t)(n_inputs + 3 * (size_t)C.ka), C.rows, bit_words);
+    G.row_stride = 3 * (n + 1);
+    G.gate_stride = n + 1;
+    G.node0 = C.ka - C.k0;
+    G.row0 = (uint32_t)row0;
+    G.instances = inst;
+    G.inst0 = one ? (uint32_t)(row0 - (uint64_t)G.node0 * inst) : 0u;
+    G.tiles = noise_tiles(one ? C.rows : inst);
+    return G;
+}
+// k_lwe_noise over `nodes` nodes of `gates` wires each, into the records NL.stats
+static int32_t launch_lwe_noise(sgfhe_ctx *c, hipStream_t st, const uint64_t *rows, const NoiseLayout &NL,
+                                const NoiseGeom &G, uint32_t nodes = 1, uint32_t gates = 1) {
+    hipLaunchKernelGGL(k_lwe_noise, dim3(nodes * G.tiles, gates), dim3(64 * NOISE_WAVES), 0, st, rows, NL.mask, NL.bits,
+                       (unsigned long long *)NL.stats, G, (uint32_t)cur(c).h_crt.logr);
+    HIPCHK(c, hipGetLastError());
+    return SGFHE_OK;
+}
+
 // the probe of a run (sgfhe_circuit_run_probe): host images that outlive the run's asynchronous copies
 struct CircuitProbe {
     const uint64_t *sk;
@@ -3049,64 +3100,70 @@ struct CircuitProbe {
     std::vector<uint64_t> up, down;   // [key mask | bit table]; the records by probe row
 };
 
-// ciphertexts per pack call of sgfhe_circuit_run_ct
-static size_t circuit_pack_cpc(const sgfhe_ctx *c) { return std::max<size_t>(1, SGFHE_CIRCUIT_CALL_ROWS / c->n); }
-
-// The gather of one call: rows row0 .. row0 + rows of the level whose first node is `node0` of the plan's node table
-// (a level's first node, or live() for the pack stage's pseudo-level).
-static void circuit_gather(const CircuitPlan &P, hipStream_t st, const uint64_t *wires, const CircNodes &nodes,
-                           uint32_t node0, uint64_t *a1, uint64_t *b1, uint64_t *a2, uint64_t *b2, uint32_t row0,
-                           uint32_t rows, uint32_t inst, uint32_t n, uint64_t r) {
-    hipLaunchKernelGGL(k_circ_gather, dim3((rows * (n + 1) + 255) / 256), dim3(256), 0, st, wires, nodes, node0, a1, b1,
-                       a2, b2, row0, rows, inst, n, r, P.group);
-}
-
+// One run: what its stages share, and the stages in the order run() queues them on `st`.  Which rows, nodes, jobs and
+// ciphertexts a call covers is csrc/circuit.h's (circuit_level_call, circuit_pack_runs, circuit_run_sizes).
 // `in` / `out`: the LWE form ([wire][instances][n + 1]); with `ct` the inputs come from ct->in_a / in_b instead and
-// `out` is optional.
-// `probe` (LWE form only): the noise records of every input wire and of every live node's three wires, taken from
-// the uploaded inputs and from each level call's own result rows.
-static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in,
-                                  uint64_t *out, const CircuitCt *ct, CircuitProbe *probe = nullptr) {
-    const size_t n = c->n, row = n + 1, M = c->M;
+// `out` is optional.  `probe` (LWE form only): the noise records of every input wire and of every live node's three
+// wires, taken from the uploaded inputs and from each level call's own result rows.
+struct CircuitRun {
+    sgfhe_ctx *c;
+    const CircuitPlan &P;
+    const size_t instances;
+    const uint64_t *in;
+    uint64_t *out;
+    const CircuitCt *ct;
+    CircuitProbe *probe;
+    const hipStream_t st = c->stream;
+    const size_t n = c->n, row = n + 1, M = c->M;   // row: words of an LWE
     const uint32_t inst = (uint32_t)instances;
     const uint64_t r = c->par.r;
-    hipStream_t st = c->stream;
-    uint64_t max_rows = 0;   // the largest call
-    for (uint32_t L = 1; L <= P.levels; L++) {
-        const uint64_t rows = P.level_rows(L, instances);
-        max_rows = std::max(max_rows, rows < SGFHE_CIRCUIT_CALL_ROWS ? rows : (uint64_t)SGFHE_CIRCUIT_CALL_ROWS);
-    }
-    const bool pack = ct && ct->out_w;
-    const size_t n_ct = pack ? (size_t)P.n_outputs * ct->blocks : 0;   // ciphertext q = output * blocks + block
-    const size_t cpc = std::min(circuit_pack_cpc(c), n_ct);             // ciphertexts of the largest pack call
-    const size_t ct_words = ct ? (size_t)P.n_inputs * ct->blocks * ct->N : 0;
-    // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire are the plan's jobs; the most refreshed ciphertexts
-    // any pack group has
-    // SGFHE_CIRCUIT_PACK_LIFT: the same direct outputs; every other ciphertext is lifted from the wire table into the
+    // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire are the plan's jobs, and their rows go from the level
+    // calls into the raw table.  SGFHE_CIRCUIT_PACK_LIFT: every other ciphertext is lifted from the wire table into the
     // raw table (k_circ_lift), so no group has a refreshed one
-    const bool lift = pack && ct->direct && ct->lift;
-    const bool direct = pack && ct->direct;
-    size_t max_ref = cpc;
-    if (direct) {
-        max_ref = 0;
-        for (size_t q0 = 0; !lift && q0 < n_ct; q0 += cpc) {
-            size_t nref = 0;
-            for (size_t q = q0; q < std::min(q0 + cpc, n_ct); q++) nref += P.out_node[q / ct->blocks] == CIRC_NONE;
-            max_ref = std::max(max_ref, nref);
-        }
+    const bool pack = ct && ct->out_w, direct = pack && ct->direct, lift = direct && ct->lift;
+    const CircuitRunSizes sz = circuit_run_sizes(P, instances, n, ct ? ct->blocks : 0, pack, direct, lift);
+    const size_t ct_words = ct ? (size_t)P.n_inputs * ct->blocks * ct->N : 0;
+    const size_t probe_rows = probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
+    // the plan's tables on the device (views into circ_tab), and the probe's
+    CircNodes nodes = {};
+    const uint32_t *d_out_slot = nullptr, *d_out_ref = nullptr, *d_in_slot = nullptr, *d_jobs = nullptr;
+    const int32_t *d_out_shift = nullptr;
+    NoiseLayout NL = {};
+    std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
+
+    CircuitRun(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in, uint64_t *out,
+               const CircuitCt *ct, CircuitProbe *probe)
+        : c(c), P(P), instances(instances), in(in), out(out), ct(ct), probe(probe) {}
+
+    int32_t grow();
+    int32_t upload_tables();
+    int32_t upload_ct();
+    int32_t upload_lwe();
+    int32_t level_call(uint32_t L, uint64_t row0);
+    int32_t pack_group(size_t q0);
+    int32_t download();
+    int32_t run();
+    // the gather of one call: rows row0 .. row0 + rows of the level whose first node is `node0` of the plan's node table
+    // (a level's first node, or live() for the pack stage's pseudo-level)
+    void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows) const {
+        hipLaunchKernelGGL(k_circ_gather, dim3(((uint32_t)rows * (uint32_t)row + 255) / 256), dim3(256), 0, st,
+                           c->circ_wires.p, nodes, node0, S.a1, S.b1, S.a2, S.b2, (uint32_t)row0, (uint32_t)rows, inst,
+                           (uint32_t)n, r, P.group);
     }
-    // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller)
+};
+
+// every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller), and the probe's
+// host images
+int32_t CircuitRun::grow() {
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
     // (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even word offset)
-    if ((rc = circ_grow(c, c->circ_stage, (size_t)max_rows * (direct ? 8 : 5) * row))) return rc;
-    if (direct && (rc = circ_grow(c, c->circ_raw, n_ct * n * row))) return rc;
+    if ((rc = circ_grow(c, c->circ_stage, (size_t)sz.max_rows * (direct ? 8 : 5) * row))) return rc;
+    if (direct && (rc = circ_grow(c, c->circ_raw, sz.n_ct * n * row))) return rc;
     if (out && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_tab, P.at.words))) return rc;
     if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
-    if (pack && (rc = pack_grow(c, cpc, n_ct, max_ref))) return rc;
-    const size_t probe_rows = probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
-    NoiseLayout NL = {};
+    if (pack && (rc = pack_grow(c, sz.cpc, sz.n_ct, sz.max_ref))) return rc;
     if (probe) {
         size_t unread = 0;   // inputs nothing reads have no slot: the probe uploads them for itself
         for (uint32_t i = 0; i < P.n_inputs; i++) unread += P.input_slot[i] == CIRC_NONE;
@@ -3124,192 +3181,170 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
         noise_key_mask(c, probe->sk, probe->up.data());
         NL = noise_layout(c, probe_rows);
     }
-    const uint64_t work_rows = std::max<uint64_t>(max_rows, max_ref * n);
-    if (work_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
-                       // then a no-op and never waits on the host between levels)
-        const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
-        if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(work_rows, chunk0))))) return rc;
+    try {
+        runs.reserve(sz.cpc);   // (no pack group allocates)
+    } catch (...) {
+        return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run_ct: no memory for the runs of a pack group");
     }
-    // the plan's tables (the image outlives the asynchronous copy: it belongs to the circuit)
+    if (sz.work_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
+                          // then a no-op and never waits on the host between levels)
+        const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
+        if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(sz.work_rows, chunk0))))) return rc;
+    }
+    return SGFHE_OK;
+}
+
+// the plan's tables (the image outlives the asynchronous copy: it belongs to the circuit), and the probe's
+int32_t CircuitRun::upload_tables() {
     HIPCHK(c, hipMemcpyAsync(c->circ_tab.p, P.image.data(), (size_t)P.at.words * 4, hipMemcpyHostToDevice, st));
     const uint32_t *tab = c->circ_tab.p;
-    const CircNodes nodes = {tab + P.at.node_kind, tab + P.at.term_start, tab + P.at.term_ref,
-                             reinterpret_cast<const int32_t *>(tab + P.at.term_shift),
-                             reinterpret_cast<const int32_t *>(tab + P.at.term_weight)};
-    const uint32_t *d_out_slot = tab + P.at.out_slot, *d_out_ref = tab + P.at.out_ref, *d_in_slot = tab + P.at.input_slot;
-    const uint32_t *d_jobs = tab + P.at.jobs;
-    const int32_t *d_out_shift = reinterpret_cast<const int32_t *>(tab + P.at.out_shift);
+    nodes = {tab + P.at.node_kind, tab + P.at.term_start, tab + P.at.term_ref,
+             reinterpret_cast<const int32_t *>(tab + P.at.term_shift),
+             reinterpret_cast<const int32_t *>(tab + P.at.term_weight)};
+    d_out_slot = tab + P.at.out_slot, d_out_ref = tab + P.at.out_ref, d_in_slot = tab + P.at.input_slot;
+    d_jobs = tab + P.at.jobs;
+    d_out_shift = reinterpret_cast<const int32_t *>(tab + P.at.out_shift);
     if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
         HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
         if (probe_rows) HIPCHK(c, hipMemsetAsync(NL.stats, 0, probe_rows * 64, st));
     }
-    if (ct) {
-        // the ciphertexts as they are, and extract() of every bit into the slot of its input wire
-        if (P.n_inputs) {
-            HIPCHK(c, hipMemcpyAsync(c->circ_ct.p, ct->in_a, ct_words * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(c->circ_ct.p + ct_words, ct->in_b, ct_words * 8, hipMemcpyHostToDevice, st));
-            const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
-            hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(P.n_inputs * ct->blocks * tiles)), dim3(256),
-                               (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct.p, c->circ_ct.p + ct_words, d_in_slot,
-                               c->circ_wires.p, (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
-            HIPCHK(c, hipGetLastError());
-        }
-    } else {
-        // inputs straight into their slots; runs of consecutive inputs in consecutive slots as one copy
-        const size_t in_words = instances * row;
-        for (uint32_t i = 0; i < P.n_inputs;) {
-            if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
-            uint32_t k = i + 1;
-            while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
-            HIPCHK(c, hipMemcpyAsync(c->circ_wires.p + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
-                                     (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
-            i = k;
-        }
-        // the probe of the input wires, from the rows as uploaded (before a level reuses a slot)
-        for (uint32_t i = 0, u = 0; probe && i < P.n_inputs; i++) {
-            const uint64_t *rows_i;
-            if (P.input_slot[i] == CIRC_NONE) {
-                uint64_t *dst = c->noise_lwe.p + (size_t)u++ * in_words;
-                HIPCHK(c, hipMemcpyAsync(dst, in + (size_t)i * in_words, in_words * 8, hipMemcpyHostToDevice, st));
-                rows_i = dst;
-            } else {
-                rows_i = c->circ_wires.p + (size_t)P.input_slot[i] * in_words;
-            }
-            const NoiseGeom G = {row, 0, i, 0, 0, inst, inst, 0, noise_tiles(inst), (uint32_t)bit_words, (uint32_t)n};
-            hipLaunchKernelGGL(k_lwe_noise, dim3(G.tiles), dim3(64 * NOISE_WAVES), 0, st, rows_i, NL.mask, NL.bits,
-                               (unsigned long long *)NL.stats, G, (uint32_t)cur(c).h_crt.logr);
-            HIPCHK(c, hipGetLastError());
-        }
+    return SGFHE_OK;
+}
+
+// ciphertext form: the ciphertexts as they are, and extract() of every bit into the slot of its input wire
+int32_t CircuitRun::upload_ct() {
+    if (!P.n_inputs) return SGFHE_OK;
+    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p, ct->in_a, ct_words * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p + ct_words, ct->in_b, ct_words * 8, hipMemcpyHostToDevice, st));
+    const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
+    hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(P.n_inputs * ct->blocks * tiles)), dim3(256),
+                       (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct.p, c->circ_ct.p + ct_words, d_in_slot,
+                       c->circ_wires.p, (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
+    HIPCHK(c, hipGetLastError());
+    return SGFHE_OK;
+}
+
+// LWE form: inputs straight into their slots; runs of consecutive inputs in consecutive slots as one copy
+int32_t CircuitRun::upload_lwe() {
+    const size_t in_words = instances * row;
+    for (uint32_t i = 0; i < P.n_inputs;) {
+        if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
+        uint32_t k = i + 1;
+        while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
+        HIPCHK(c, hipMemcpyAsync(c->circ_wires.p + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
+                                 (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
+        i = k;
     }
-    uint64_t *a1 = c->circ_stage.p, *a2 = a1 + max_rows * n, *b1 = a2 + max_rows * n, *b2 = b1 + max_rows,
-             *res = b2 + max_rows;
-    for (uint32_t L = 1; L <= P.levels; L++) {
-        const uint64_t rows_total = P.level_rows(L, instances);
-        const uint32_t k0 = P.level_start[L];
-        for (uint64_t row0 = 0; row0 < rows_total; row0 += SGFHE_CIRCUIT_CALL_ROWS) {
-            const uint32_t rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, rows_total - row0);
-            const uint32_t tg = rows * (uint32_t)row;
-            circuit_gather(P, st, c->circ_wires.p, nodes, k0, a1, b1, a2, b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
-            HIPCHK(c, hipGetLastError());
-            // a call that produces a wire some direct output names leaves its rows un-reduced: the scatter reduces
-            // what the wire table takes (the words k_final writes) and copies the named rows into the raw table
-            const uint32_t ka = k0 + (uint32_t)(row0 / inst), kb = k0 + (uint32_t)((row0 + rows - 1) / inst);
-            const size_t j0 = std::lower_bound(P.job_k.begin(), P.job_k.end(), ka) - P.job_k.begin();
-            const size_t j1 = std::upper_bound(P.job_k.begin(), P.job_k.end(), kb) - P.job_k.begin();
-            // a call that holds a sum node: its LOW rows, from the staging the bootstrap consumed
-            const bool xor3 = P.gate3_in(ka, kb);
-            if (direct && j1 > j0) {
-                if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, SGFHE_FLAG_RAW_MODQ, c->n, nullptr, st))) return rc;
-                for (size_t j = j0; j < j1;) {   // (a grid holds 65535 rows of workgroups)
-                    const uint32_t wires = j == j0, nj = (uint32_t)std::min<size_t>(j1 - j, 65535u - wires);
-                    hipLaunchKernelGGL(k_circ_scatter_raw, dim3(rows, nj + wires), dim3(256), 0, st,
-                                       reinterpret_cast<const ulonglong2 *>(res), d_out_slot + 3 * (size_t)k0,
-                                       c->circ_wires.p, d_jobs + 3 * j, c->circ_raw.p, cur(c).d_crt, (uint32_t)row0, inst,
-                                       (uint32_t)n, wires);
-                    HIPCHK(c, hipGetLastError());
-                    j += nj;
-                }
-                if (xor3) {   // (after the scatter: over the XOR row's words in the wire table)
-                    hipLaunchKernelGGL(k_circ_xor3_raw, dim3(rows), dim3(256), 0, st,
-                                       reinterpret_cast<const ulonglong2 *>(res), nodes.kind + k0,
-                                       d_out_slot + 3 * (size_t)k0, c->circ_wires.p, a1, b1, a2, b2, cur(c).d_crt,
-                                       (uint32_t)row0, inst, (uint32_t)n, r);
-                    HIPCHK(c, hipGetLastError());
-                }
-                continue;
-            }
-            // the k-loop of sgfhe_bootstrap_batch_device: the next call number of the ctx's draw stream
-            if ((rc = bootstrap_device(c, a1, b1, a2, b2, rows, res, 0u, c->n, nullptr, st))) return rc;
-            if (xor3) {   // (before the scatter and the probe read the result rows)
-                hipLaunchKernelGGL(k_circ_xor3, dim3((tg + 255) / 256), dim3(256), 0, st, res, nodes.kind + k0, a1, b1, a2,
-                                   b2, (uint32_t)row0, rows, inst, (uint32_t)n, r);
-                HIPCHK(c, hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, res,
-                               d_out_slot + 3 * (size_t)k0, c->circ_wires.p, (uint32_t)row0, rows, inst, (uint32_t)n);
-            HIPCHK(c, hipGetLastError());
-            if (probe) {
-                // the call's own result rows [rows][3][n + 1], read or not, before the next call overwrites them (same
-                // stream).  A call inside one node: tiles over its rows; a call over several nodes: tiles over every
-                // node's instances (a tile never straddles two nodes; rows outside the call are skipped)
-                const uint32_t nodes = kb - ka + 1;
-                const uint32_t inst0 = nodes == 1 ? (uint32_t)(row0 - (uint64_t)(ka - k0) * inst) : 0u;
-                const NoiseGeom G = {3 * row, row, (uint32_t)(P.n_inputs + 3 * (size_t)ka), ka - k0, (uint32_t)row0, rows, inst,
-                                     inst0, noise_tiles(nodes == 1 ? rows : inst), (uint32_t)bit_words, (uint32_t)n};
-                hipLaunchKernelGGL(k_lwe_noise, dim3(nodes * G.tiles, 3), dim3(64 * NOISE_WAVES), 0, st, res, NL.mask,
-                                   NL.bits, (unsigned long long *)NL.stats, G, (uint32_t)cur(c).h_crt.logr);
-                HIPCHK(c, hipGetLastError());
-            }
-        }
+    // the probe of the input wires, from the rows as uploaded (before a level reuses a slot)
+    for (uint32_t i = 0, u = 0; probe && i < P.n_inputs; i++) {
+        const bool own = P.input_slot[i] == CIRC_NONE;
+        uint64_t *rows_i = own ? c->noise_lwe.p + (size_t)u++ * in_words : c->circ_wires.p + (size_t)P.input_slot[i] * in_words;
+        if (own) HIPCHK(c, hipMemcpyAsync(rows_i, in + (size_t)i * in_words, in_words * 8, hipMemcpyHostToDevice, st));
+        const int32_t rc = launch_lwe_noise(c, st, rows_i, NL, noise_wire_rows(n, i, inst, bit_words));
+        if (rc) return rc;
     }
-    // the pack stage: ciphertexts q0 .. q0 + cnt of a call are rows q0 * n .. of the "level" whose node o is
-    // (TRUE, output o) -- row = o * instances + block * n + bit -- so the gather of the levels builds the call's
-    // bootstrap inputs, and each call is one sgfhe_pack_encrypted_bits(count = cnt) on the device
-    // SGFHE_CIRCUIT_PACK_DIRECT: a group's refreshed ciphertexts (outputs that name an input wire or the constant)
-    // are bootstrapped as one call, row = rank among them * n + bit, and their AND rows join the direct ones in the
-    // raw table; then one tail over the group's rows of that table, a call of its own
-    // SGFHE_CIRCUIT_PACK_LIFT: those ciphertexts are lifted instead -- one k_circ_lift per run of consecutive ones,
-    // from the wire table straight into their rows of the raw table -- and the group is its tail alone
-    for (size_t q0 = 0; direct && q0 < n_ct; q0 += cpc) {
-        const size_t cnt = std::min(cpc, n_ct - q0);
-        struct Run { size_t q, rank, len; };   // consecutive refreshed (lifted) ciphertexts: one gather, one copy
-        std::vector<Run> runs;
-        size_t nref = 0;
-        for (size_t q = q0; q < q0 + cnt; q++) {
-            if (P.out_node[q / ct->blocks] != CIRC_NONE) continue;
-            if (!runs.empty() && runs.back().q + runs.back().len == q) runs.back().len++;
-            else runs.push_back({q, nref, 1});
-            nref++;
+    return SGFHE_OK;
+}
+
+// One level call: gather, the k-loop of sgfhe_bootstrap_batch_device (the next call number of the ctx's draw stream),
+// scatter.  In a direct run, a call that produces a wire some direct output names leaves its rows un-reduced: the
+// scatter reduces what the wire table takes (the words k_final writes) and copies the named rows into the raw table.
+int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
+    const CircuitCall C = circuit_level_call(P, L, row0, instances);
+    const Staging S = staging(c->circ_stage.p, sz.max_rows, n);
+    const uint32_t *out_slot = d_out_slot + 3 * (size_t)C.k0, *kind = nodes.kind + C.k0;
+    const uint32_t un = (uint32_t)n, r0 = (uint32_t)row0;
+    const bool raw = direct && C.j1 > C.j0;
+    gather(C.k0, S, row0, C.rows);
+    HIPCHK(c, hipGetLastError());
+    int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, C.rows, S.res, raw ? SGFHE_FLAG_RAW_MODQ : 0u, c->n, nullptr, st);
+    if (rc) return rc;
+    if (raw) {
+        const ulonglong2 *res = reinterpret_cast<const ulonglong2 *>(S.res);
+        for (size_t j = C.j0; j < C.j1;) {
+            const CircuitJobChunk ch = circuit_job_chunk(j, C.j0, C.j1);
+            hipLaunchKernelGGL(k_circ_scatter_raw, dim3(C.rows, ch.nj + ch.wires), dim3(256), 0, st, res, out_slot,
+                               c->circ_wires.p, d_jobs + 3 * j, c->circ_raw.p, cur(c).d_crt, r0, inst, un, ch.wires);
+            HIPCHK(c, hipGetLastError());
+            j += ch.nj;
         }
-        for (size_t i = 0; lift && i < runs.size(); i++) {
-            const Run &R = runs[i];
-            const uint32_t rows = (uint32_t)(R.len * n);
-            const dim3 grid((rows * (uint32_t)row + 255) / 256);
-            hipLaunchKernelGGL(k_circ_lift, grid, dim3(256), 0, st, c->circ_wires.p, d_out_ref, d_out_shift, c->circ_raw.p,
-                               cur(c).d_crt, (uint32_t)(R.q * n), rows, inst, (uint32_t)n, r, P.group);
+        if (C.sum) {   // a sum node's LOW rows, from the staging the bootstrap consumed (after the scatter: over the XOR
+                       // row's words in the wire table)
+            hipLaunchKernelGGL(k_circ_xor3_raw, dim3(C.rows), dim3(256), 0, st, res, kind, out_slot, c->circ_wires.p,
+                               S.a1, S.b1, S.a2, S.b2, cur(c).d_crt, r0, inst, un, r);
             HIPCHK(c, hipGetLastError());
         }
-        if (nref && !lift) {
-            const size_t nb = nref * n;
-            uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
-            for (const Run &R : runs) {
-                const size_t off = R.rank * n;
-                circuit_gather(P, st, c->circ_wires.p, nodes, (uint32_t)P.live(), p1 + off * n, q1 + off, p2 + off * n,
-                               q2 + off, (uint32_t)(R.q * n), (uint32_t)(R.len * n), inst, (uint32_t)n, r);
-                HIPCHK(c, hipGetLastError());
-            }
-            if ((rc = bootstrap_device(c, p1, q1, p2, q2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ, c->n,
-                                       nullptr, st)))
-                return rc;
-            for (const Run &R : runs) {
-                hipLaunchKernelGGL(k_circ_raw_and, dim3((uint32_t)(R.len * n)), dim3(256), 0, st,
-                                   c->pack_raw.p + R.rank * n * 3 * row, c->circ_raw.p + R.q * n * row, (uint32_t)n);
-                HIPCHK(c, hipGetLastError());
-            }
-        }
-        const uint32_t call = c->rnd ? c->rnd_call++ : 0u;
-        c->last_call = call;
-        if ((rc = pack_tail(c, c->circ_raw.p + q0 * n * row, (uint32_t)row, cnt, c->pack_wv.p + q0 * M,
-                            c->pack_wv.p + (n_ct + q0) * M, call, st)))
-            return rc;
+        return SGFHE_OK;
     }
-    for (size_t q0 = 0; !direct && q0 < n_ct; q0 += cpc) {
-        const size_t cnt = std::min(cpc, n_ct - q0), nb = cnt * n;
-        uint64_t *p1 = c->pack_lwe.p, *p2 = p1 + nb * n, *q1 = p2 + nb * n, *q2 = q1 + nb;
-        circuit_gather(P, st, c->circ_wires.p, nodes, (uint32_t)P.live(), p1, q1, p2, q2, (uint32_t)(q0 * n),
-                       (uint32_t)nb, inst, (uint32_t)n, r);
+    const uint32_t tg = C.rows * (uint32_t)row;
+    if (C.sum) {   // (before the scatter and the probe read the result rows)
+        hipLaunchKernelGGL(k_circ_xor3, dim3((tg + 255) / 256), dim3(256), 0, st, S.res, kind, S.a1, S.b1, S.a2, S.b2, r0,
+                           C.rows, inst, un, r);
         HIPCHK(c, hipGetLastError());
-        if ((rc = pack_device(c, p1, q1, p2, q2, cnt, c->pack_wv.p + q0 * M, c->pack_wv.p + (n_ct + q0) * M, st))) return rc;
     }
+    hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, S.res, out_slot, c->circ_wires.p, r0,
+                       C.rows, inst, un);
+    HIPCHK(c, hipGetLastError());
+    // the probe: the call's own result rows, read or not, before the next call overwrites them (same stream)
+    if (probe) return launch_lwe_noise(c, st, S.res, NL, noise_call_rows(n, P.n_inputs, C, row0, inst, bit_words),
+                                       C.kb - C.ka + 1, 3);
+    return SGFHE_OK;
+}
+
+// One pack group: ciphertexts q0 .. q0 + cnt are rows q0 * n .. of the "level" whose node o is (TRUE, output o) --
+// row = o * instances + block * n + bit -- so the gather of the levels builds their bootstrap inputs.  The group's
+// runs (every ciphertext in the plain form, those that are not direct otherwise) are lifted into the raw table -- one
+// k_circ_lift per run, straight from the wire table -- or gathered (row = rank among them * n + bit) and bootstrapped
+// un-reduced as ONE call.  Then the tail.  Direct: the AND rows join the direct ones in the raw table, and the tail
+// over the group's rows of that table is a call of its own, so a group is an optional sgfhe_bootstrap_batch(RAW_MODQ)
+// plus one sgfhe_pack_lwe_modq on the draw stream.  Plain: the tail reads gate 0 of the bootstrap's result under the
+// bootstrap's own call number, which is one sgfhe_pack_encrypted_bits(count = cnt).
+int32_t CircuitRun::pack_group(size_t q0) {
+    const size_t cnt = std::min(sz.cpc, sz.n_ct - q0);
+    const size_t nb = circuit_pack_runs(P, ct->blocks, q0, cnt, !direct, &runs) * n;
+    if (lift) {
+        for (const CircuitPackRun &U : runs) {
+            const uint32_t rows = (uint32_t)(U.len * n);
+            hipLaunchKernelGGL(k_circ_lift, dim3((rows * (uint32_t)row + 255) / 256), dim3(256), 0, st, c->circ_wires.p,
+                               d_out_ref, d_out_shift, c->circ_raw.p, cur(c).d_crt, (uint32_t)(U.q * n), rows, inst,
+                               (uint32_t)n, r, P.group);
+            HIPCHK(c, hipGetLastError());
+        }
+    } else if (nb) {
+        const Staging S = staging(c->pack_lwe.p, nb, n);
+        for (const CircuitPackRun &U : runs) {
+            gather((uint32_t)P.live(), S.from_row(U.rank * n, n), U.q * n, U.len * n);
+            HIPCHK(c, hipGetLastError());
+        }
+        const int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ,
+                                            c->n, nullptr, st);
+        if (rc) return rc;
+        for (size_t i = 0; direct && i < runs.size(); i++) {
+            const CircuitPackRun &U = runs[i];
+            hipLaunchKernelGGL(k_circ_raw_and, dim3((uint32_t)(U.len * n)), dim3(256), 0, st,
+                               c->pack_raw.p + U.rank * n * 3 * row, c->circ_raw.p + U.q * n * row, (uint32_t)n);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    uint64_t *d_w = c->pack_wv.p + q0 * M, *d_v = c->pack_wv.p + (sz.n_ct + q0) * M;
+    if (!direct) return pack_tail(c, c->pack_raw.p, 3 * (uint32_t)row, cnt, d_w, d_v, c->last_call, st);
+    const uint32_t call = c->rnd ? c->rnd_call++ : 0u;
+    c->last_call = call;
+    return pack_tail(c, c->circ_raw.p + q0 * n * row, (uint32_t)row, cnt, d_w, d_v, call, st);
+}
+
+// (w, v) of every ciphertext, the outputs in the LWE form, the probe's records; then the host waits
+int32_t CircuitRun::download() {
     if (pack) {
-        HIPCHK(c, hipMemcpyAsync(ct->out_w, c->pack_wv.p, n_ct * M * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(ct->out_v, c->pack_wv.p + n_ct * M, n_ct * M * 8, hipMemcpyDeviceToHost, st));
+        const size_t wv = sz.n_ct * M;
+        HIPCHK(c, hipMemcpyAsync(ct->out_w, c->pack_wv.p, wv * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(ct->out_v, c->pack_wv.p + wv, wv * 8, hipMemcpyDeviceToHost, st));
     }
     if (out) {
         const size_t total = (size_t)P.n_outputs * instances * row;
         const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
-        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref, d_out_shift,
-                           c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
+        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
+                           d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(out, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
     }
@@ -3324,6 +3359,19 @@ static int32_t circuit_run_queued(sgfhe_ctx *c, const CircuitPlan &P, size_t ins
                       probe->stats + (size_t)circuit_probe_wire(P, w) * 8);
     }
     return SGFHE_OK;
+}
+
+int32_t CircuitRun::run() {
+    int32_t rc;
+    if ((rc = grow())) return rc;
+    if ((rc = upload_tables())) return rc;
+    if ((rc = ct ? upload_ct() : upload_lwe())) return rc;
+    for (uint32_t L = 1; L <= P.levels; L++)
+        for (uint64_t row0 = 0; row0 < P.level_rows(L, instances); row0 += SGFHE_CIRCUIT_CALL_ROWS)
+            if ((rc = level_call(L, row0))) return rc;
+    for (size_t q0 = 0; q0 < sz.n_ct; q0 += sz.cpc)
+        if ((rc = pack_group(q0))) return rc;
+    return download();
 }
 
 // sgfhe_circuit_run, with `probe` the run of sgfhe_circuit_run_probe
@@ -3344,15 +3392,7 @@ static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t i
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
     if (instances % P.group)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: instances must be a multiple of the circuit's lane group");
-    (void)hipSetDevice(c->device);
-    int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
-    if (rc) return rc;
-    rc = circuit_run_queued(c, P, instances, in, out, nullptr, probe);
-    if (rc) {   // whatever was queued finishes before the buffers can be touched again
-        (void)hipStreamSynchronize(c->stream);
-        c->pending = false;
-    }
-    return rc;
+    return run_drained(c, [&] { return CircuitRun(c, P, instances, in, out, nullptr, probe).run(); });
 }
 
 int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
@@ -3363,17 +3403,17 @@ int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
     return circuit_run_lwe(c, circ, instances, in, out, &probe);
 }
 
-// everything sgfhe_lwe_noise queues (its caller waits for the stream when a step fails)
+// everything sgfhe_lwe_noise queues (run_drained waits for the stream when a step fails)
 static int32_t lwe_noise_queued(sgfhe_ctx *c, const uint64_t *lwe, size_t count, size_t stride, bool raw,
                                 const std::vector<uint64_t> &up, std::vector<uint64_t> &down) {
-    const size_t n = c->n, rowlen = (n + 1) * (raw ? 2 : 1), bit_words = circuit_bit_words(count);
+    const size_t n = c->n, rowlen = (n + 1) * (raw ? 2 : 1);
     hipStream_t st = c->stream;
     const NoiseLayout NL = noise_layout(c, 1);
     HIPCHK(c, hipMemcpyAsync(NL.mask, up.data(), up.size() * 8, hipMemcpyHostToDevice, st));
     // the rows, compact on the device whatever the caller's stride
     if (stride == rowlen) HIPCHK(c, hipMemcpyAsync(c->noise_lwe.p, lwe, count * rowlen * 8, hipMemcpyHostToDevice, st));
     else HIPCHK(c, hipMemcpy2DAsync(c->noise_lwe.p, rowlen * 8, lwe, stride * 8, rowlen * 8, count, hipMemcpyHostToDevice, st));
-    const NoiseGeom G = {n + 1, 0, 0, 0, 0, (uint32_t)count, (uint32_t)count, 0, noise_tiles(count), (uint32_t)bit_words, (uint32_t)n};
+    const NoiseGeom G = noise_wire_rows(n, 0, (uint32_t)count, circuit_bit_words(count));
     if (raw) {
         const uint32_t grid = std::min(G.tiles, NOISE_Q_GRID);
         hipLaunchKernelGGL(k_lwe_noise_q, dim3(grid), dim3(64 * NOISE_WAVES), 0, st,
@@ -3384,9 +3424,8 @@ static int32_t lwe_noise_queued(sgfhe_ctx *c, const uint64_t *lwe, size_t count,
         HIPCHK(c, hipMemcpyAsync(down.data(), NL.partial, down.size() * 8, hipMemcpyDeviceToHost, st));
     } else {
         HIPCHK(c, hipMemsetAsync(NL.stats, 0, 64, st));
-        hipLaunchKernelGGL(k_lwe_noise, dim3(G.tiles), dim3(64 * NOISE_WAVES), 0, st, c->noise_lwe.p, NL.mask, NL.bits,
-                           (unsigned long long *)NL.stats, G, (uint32_t)cur(c).h_crt.logr);
-        HIPCHK(c, hipGetLastError());
+        const int32_t rc = launch_lwe_noise(c, st, c->noise_lwe.p, NL, G);
+        if (rc) return rc;
         down.assign(8, 0);
         HIPCHK(c, hipMemcpyAsync(down.data(), NL.stats, 64, hipMemcpyDeviceToHost, st));
     }
@@ -3413,28 +3452,25 @@ int32_t sgfhe_lwe_noise(sgfhe_ctx *c, const uint64_t *sk, const uint64_t *lwe, s
                                                           std::to_string(i) + " is not below Q");
     std::fill(stats, stats + 8, 0ull);
     if (count == 0) return SGFHE_OK;
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    const size_t bit_words = circuit_bit_words(count);
-    int32_t rc = noise_grow(c, 1, bit_words, count * rowlen);
-    if (rc) return rc;
     std::vector<uint64_t> up, down;   // [key mask | expected bits]; the record or the partial records
-    try {
-        up.assign(NOISE_MASK_WORDS + bit_words, 0);
-    } catch (...) {
-        return fail(c, SGFHE_ERR_OOM, "sgfhe_lwe_noise: no memory for the expected-bit table");
-    }
-    noise_key_mask(c, sk, up.data());
-    for (size_t i = 0; i < count; i++) up[NOISE_MASK_WORDS + i / 64] |= (uint64_t)(expected[i] & 1u) << (i % 64);
-    try {
-        rc = lwe_noise_queued(c, lwe, count, row_stride_words, raw, up, down);
-    } catch (...) {
-        rc = fail(c, SGFHE_ERR_OOM, "sgfhe_lwe_noise: no memory for the partial records");
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
+        const size_t bit_words = circuit_bit_words(count);
+        const int32_t rg = noise_grow(c, 1, bit_words, count * rowlen);
+        if (rg) return rg;
+        try {
+            up.assign(NOISE_MASK_WORDS + bit_words, 0);
+        } catch (...) {
+            return fail(c, SGFHE_ERR_OOM, "sgfhe_lwe_noise: no memory for the expected-bit table");
+        }
+        noise_key_mask(c, sk, up.data());
+        for (size_t i = 0; i < count; i++) up[NOISE_MASK_WORDS + i / 64] |= (uint64_t)(expected[i] & 1u) << (i % 64);
+        try {
+            return lwe_noise_queued(c, lwe, count, row_stride_words, raw, up, down);
+        } catch (...) {
+            return fail(c, SGFHE_ERR_OOM, "sgfhe_lwe_noise: no memory for the partial records");
+        }
+    });
+    if (rc) return rc;
     if (!raw) {
         std::copy(down.begin(), down.end(), stats);
         return SGFHE_OK;
@@ -3493,17 +3529,9 @@ int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: too many instances for this circuit");
     if (c->n % P.group)   // (a group must not straddle two ciphertexts)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: n must be a multiple of the circuit's lane group");
-    (void)hipSetDevice(c->device);
-    int32_t rc = drain(c);   // buffers may be regrown: nothing of an earlier call may be in flight
-    if (rc) return rc;
     const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
                           (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
-    rc = circuit_run_queued(c, P, (size_t)instances, nullptr, out_lwe, &ct);
-    if (rc) {   // whatever was queued finishes before the buffers can be touched again
-        (void)hipStreamSynchronize(c->stream);
-        c->pending = false;
-    }
-    return rc;
+    return run_drained(c, [&] { return CircuitRun(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr).run(); });
 }
 
 }  // extern "C"

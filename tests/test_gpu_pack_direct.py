@@ -260,3 +260,68 @@ def test_edge_cases(S, oc):
     assert np.array_equal(again[0], refreshed[0]) and np.array_equal(again[1], refreshed[1])
     assert np.array_equal(_decrypt_ct(S, params, sk, w, v), c.evaluate_plain(bits.reshape(3, -1)))
     eng.close()
+
+
+@pytest.fixture(scope="module")
+def straddle(S, oc):
+    """Shared by the four cases below, built once and left unchanged: two ctxs under one key, the circuit, its
+    encrypted inputs and its plain evaluation."""
+    params, o, sk, bkey, engs = _setup64(S, oc, 161, engines=2)
+    c = S.Circuit(2)
+    x, y = c.inputs
+    g0, g1, g2 = c.gate(x, y), c.gate(x, ~y), c.gate(~x, y)
+    c.output(g2[1], g0[0], x, ~g1[2])
+    blocks = 44
+    bits = np.random.default_rng(162).integers(0, 2, size=(2, blocks, params.n)).astype(bool)
+    a, b = _encrypt_cts(S, params, sk, bits, 163)
+    yield dict(params=params, o=o, sk=sk, bkey=bkey, engs=engs, c=c, a=a, b=b,
+               plain=c.evaluate_plain(bits.reshape(2, -1)))
+    for e in engs:
+        e.close()
+
+
+@pytest.mark.parametrize("mode", ["deterministic", "randomised"])
+@pytest.mark.parametrize("lift", [False, True], ids=["direct", "direct+lift"])
+def test_unreduced_level_call_split_inside_a_producing_node(S, oc, straddle, mode, lift):
+    """Params(64), 44 blocks = 2816 instances, one level of 3 nodes = 8448 rows: the level is two calls, both un-reduced,
+    and call 0 ends at row 8192, inside node 2 (rows 5632 .. 8447), whose OR wire is output 0 -- its job belongs to both
+    calls, each copying the rows it holds.  Outputs: OR of node 2, AND of node 0, input x, ~XOR of node 1: 176
+    ciphertexts = groups of 128 and 48; the first ends with 40 refreshed (lifted) ciphertexts of x, the second opens
+    with the other 4 and goes on with 44 direct ones.  (w, v) and out_lwe byte for byte against
+    circuit.replay_ct_direct on a second ctx's own un-reduced bootstrap_batch and pack_lwe_modq, which number their
+    calls themselves.  Call numbers consumed, by the closed form: 2 level calls (ceil(8448 / 8192)); direct: 2 per
+    group (both refresh something), 6 in all; lifted: 1 per group, 4 in all.  The replay makes exactly that many
+    calls; randomised, the next bootstrap on the run's ctx is the oracle's call of that number (deterministic runs draw
+    nothing: every call is number 0 and the counter cannot be observed)."""
+    from sgfhe_jl_amd import circuit as C
+    key = KEY32 if mode == "randomised" else None
+    K = straddle
+    params, o, bkey, c, a, b = K["params"], K["o"], K["bkey"], K["c"], K["a"], K["b"]
+    eng, ref = K["engs"]
+    n, blocks = params.n, a.shape[1]
+    assert blocks * n == 2816 and c.info()["levels"] == 1 and c.info()["nodes"] == 3
+    assert 3 * blocks * n == 8448 and c.n_outputs * blocks == 176 and C.pack_calls(n) == 128
+    level_calls = -(-3 * blocks * n // 8192)
+    want_calls = level_calls + (2 if lift else 2 * 2)
+    calls = []
+    _set_mode([eng, ref], key)
+    (w, v), lwe = eng.circuit_run_ct(c, a, b, packed=True, lwe=True, direct=True, lift=lift)
+    (rw, rv), rlwe = C.replay_ct_direct(
+        c, a, b, params,
+        lambda call, a1, b1, a2, b2: (calls.append(call), ref.bootstrap_batch(a1, b1, a2, b2, raw=True))[1],
+        lambda call, group: (calls.append(call), ref.pack_lwe_modq(group))[1], lift=lift)
+    # (what the REPLAY numbered, a property of replay_ct_direct: it says the composition the bytes are compared with
+    # makes the closed-form number of calls, and is no evidence about the engine's own counter.  The engine's counter
+    # is pinned below, in the randomised mode only: a deterministic run numbers every call 0 and the counter is not
+    # exposed by the ABI.)
+    assert calls == list(range(want_calls))
+    assert np.array_equal(lwe, rlwe)
+    assert np.array_equal(w, rw) and np.array_equal(v, rv), "packed outputs differ from the replay (%s)" % mode
+    # (decryption of two ciphertexts per output, one of each group where the output has both)
+    for q, t in ((0, 0), (0, 43), (1, 0), (2, 39), (2, 40), (3, 43)):
+        assert np.array_equal(S.host.decrypt_rlwe(params, K["sk"], w[q, t], v[q, t]), K["plain"][q, t * n:(t + 1) * n])
+    if key:     # the engine's counter: its next call draws as call number `want_calls` of the stream
+        x3, y3 = lwe[0, :3], lwe[1, :3]
+        got = eng.bootstrap_batch(x3[:, :n], x3[:, n], y3[:, :n], y3[:, n])
+        assert np.array_equal(got, o.bootstrap_batch(bkey, x3[:, :n], x3[:, n], y3[:, :n], y3[:, n],
+                                                     rnd=(key, want_calls)))

@@ -104,6 +104,17 @@ struct DevBuf {
         cap = 0;
     }
 };
+// Call-local device scratch: a DevBuf that frees itself.  An entry declares it BEFORE run_drained, so that it goes
+// after run_drained has waited for the stream of a body that failed: no queued work outlives a buffer it uses.
+namespace {
+template <typename T>
+struct Scratch : DevBuf<T> {
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() { this->release(); }
+};
+}  // namespace
 
 // ---------------------------------------------------------------- ctx
 
@@ -128,7 +139,12 @@ struct SharedDev {
     }
 };
 
-struct sgfhe_ctx {
+// sgfhe_ctx is three groups of members and what is the ctx's own.  sgfhe_ctx_clone assigns the groups; a member
+// added to one of them is cloned without another line anywhere.
+
+// What a clone SHARES with the ctx it is taken from and only reads: the parameter set and its geometry, the RNS
+// bases with their device constants and key forms, the twiddle tables, and the handle on the shared device memory.
+struct CtxShared {
     sgfhe_params par;
     int device = 0;
     int logm = 0;
@@ -157,13 +173,57 @@ struct sgfhe_ctx {
         int32_t *d_key = nullptr;
         size_t key_bytes = 0;
     } basis[2];
-    int nb = 1, active = 0;       // bases in use (basis[0]: deterministic mode, basis[nb - 1]: randomised), active one
+    int nb = 1;                   // bases in use (basis[0]: deterministic mode, basis[nb - 1]: randomised)
     uint32_t npr_max = 0;         // primes of the larger basis: work buffers are sized for it
     uint32_t tw_done = 0;         // primes whose twiddle tables are on the device
-    std::string err;
     // the read-only device memory of this ctx, shared with its clones (use_count() > 1: the key may not
     // be replaced, sgfhe_ctx_clone)
     std::shared_ptr<SharedDev> shared;
+    // device constants
+    int32_t *d_tw = nullptr;  // npr * 4 * M entries
+    int32_t *d_twq = nullptr; // quarter form of the latency kernels: per prime 4 blocks [f_q | v_q | fp_q | vp_q] of m / 4 words
+    int32_t *d_pow = nullptr; //   and psi^e * R mod p, e in [0, 2 m)
+    int32_t tw_head[NPR_MAX][8] = {};   // f[1..3], fp[2], fp[3], v[1..3] of every prime (PrimeK::f1 ... v3)
+    bool rnd_ok = false;      // the randomised flatten (rng != nothing, utils.jl:198-241) is available on this ctx
+    uint32_t create_flags = 0;
+};
+
+// The scheduling knobs (sgfhe_set_chunk / _lanes / _small_batch_max and the environment): a clone STARTS with the
+// values they have on the ctx it is taken from, and is then set on its own.
+struct CtxKnobs {
+    uint32_t chunk = 0, lanes = 2;   // work buffers: two lanes, each sized for `cap` bootstraps
+    // the quarter form's two transform kernels as one launch (k_ext_quarter) from this many gates per chain, up to
+    // what fills the device once (fused_cap below); SGFHE_SMALL_FUSED=0: never, =n: from n gates
+    uint32_t fused_min = 7;
+    uint32_t split_max = 7;   // calls of at most this many gates take the quarter form (SGFHE_SMALL_SPLIT, 0 = never):
+                              // 1 / 2 / 4 / 6 / 8 gates 15.1 / 15.9 / 17.8 / 19.7 / 23.5 ms against 17.9 / 18.6 / 20.3 /
+                              // 22.0 / 23.3 with one workgroup per transform (profiles/r04_exp_quarter.txt)
+    bool small_padded = false;  // SGFHE_SMALL_PADDED=1: small-batch grids padded to 8 bootstraps as up to round 3 (A/B)
+    bool small_lanes = true;    // SGFHE_SMALL_LANES=0: a call of a few gates as one chunk on one stream (A/B)
+    uint32_t small_lanes_max = 24;   // ... up to this many gates (SGFHE_SMALL_LANES=<n>)
+    uint32_t crt1_max = 0;      // k_crt_lean launches of at most this many coefficients take one per thread
+                                // (SGFHE_CRT1_GATES gates' worth: default 8; 0 = never.  Same call, 1 / 2 / 4 / 8
+                                // gates: 18.6 / 19.4 / 20.8 / 23.9 ms with four per thread, 17.9 / 18.6 / 20.2 / 23.4
+                                // with one, profiles/r04_exp_crt1.txt)
+    uint32_t small_max = 24;  // chunks of at most this many bootstraps take the small-batch form
+                              // (measured crossover at Params(1024): 24 -> 32.3 vs 40.9 ms, 32 -> 44.0 vs 42.3 ms)
+    bool use_pin = true;   // SGFHE_HOST_PIN=0 in the environment: direct copies (A/B measurements)
+};
+
+// The state of the key in the shared memory; a clone starts with the state it finds (a ctx without a key is not
+// cloned) and, like every sharer, may not change it while the key is shared (key_begin).
+struct CtxKeyState {
+    bool have_key = false;      // basis[].d_key of every basis in use hold one key
+    // RNS2Number form of Z_Q (src/rns.jl): set by sgfhe_bkey_upload_rns2 / sgfhe_rns2_convert
+    bool have_rns2 = false;
+    Rns2Const rns2;
+};
+
+// The ctx's OWN: everything below starts from its initialiser on a clone too -- flatten mode and call counters,
+// the active basis, streams, events, work and staging buffers, timing, the error string and the lock.
+struct sgfhe_ctx : CtxShared, CtxKnobs, CtxKeyState {
+    int active = 0;               // the basis everything reads: cur()
+    std::string err;
     // Every C-ABI entry point that takes a ctx holds this lock for the whole call: a ctx may be
     // shared by host threads (their calls are serialised), different ctxs run concurrently.
     mutable std::recursive_mutex mu;
@@ -183,48 +243,22 @@ struct sgfhe_ctx {
     // download of the present ones, which waits for their last kernel)
     hipStream_t stream_io = nullptr, stream_io2 = nullptr;
     std::vector<hipEvent_t> ev_pool;   // events of the pipelined host-pointer path (created once, reused)
-    // device constants
     uint32_t *d_bad = nullptr;  // set by k_key_transform when a key residue is >= Q
-    int32_t *d_tw = nullptr;  // npr * 4 * M entries
-    int32_t *d_twq = nullptr; // quarter form of the latency kernels: per prime 4 blocks [f_q | v_q | fp_q | vp_q] of m / 4 words
-    int32_t *d_pow = nullptr; //   and psi^e * R mod p, e in [0, 2 m)
-    int32_t tw_head[NPR_MAX][8] = {};   // f[1..3], fp[2], fp[3], v[1..3] of every prime (PrimeK::f1 ... v3)
-    // the quarter form's two transform kernels as one launch (k_ext_quarter) from this many gates per chain, up to
-    // what fills the device once (fused_cap below); SGFHE_SMALL_FUSED=0: never, =n: from n gates
-    uint32_t fused_min = 7;
-    uint32_t split_max = 7;   // calls of at most this many gates take the quarter form (SGFHE_SMALL_SPLIT, 0 = never):
-                              // 1 / 2 / 4 / 6 / 8 gates 15.1 / 15.9 / 17.8 / 19.7 / 23.5 ms against 17.9 / 18.6 / 20.3 /
-                              // 22.0 / 23.3 with one workgroup per transform (profiles/r04_exp_quarter.txt)
-    bool have_key = false;      // basis[].d_key of every basis in use hold one key
-    // work buffers: two lanes, each sized for `cap` bootstraps
-    uint32_t chunk = 0, cap = 0, lanes = 2;
+    uint32_t cap = 0;           // bootstraps the lanes' work buffers are sized for
     // randomised flatten (rng != nothing, utils.jl:198-241)
-    bool rnd = false, rnd_ok = false;
+    bool rnd = false;
     ChaChaKey rnd_key = {};   // 32-byte key of the draw stream (sgfhe_set_random_flatten[_key])
     uint32_t rnd_call = 0, last_call = 0;
     int64_t call_fixed = -1;              // the number of the next call, when the coalescer has already assigned it
     const RndRow *gather_rows = nullptr;  // set around a gathered randomised call this ctx leads: d_rows
     DevBuf<RndRow> d_rows;                // per-row draw streams of such a call (device)
     std::vector<RndRow> h_rows;
-    uint32_t create_flags = 0;
-    // RNS2Number form of Z_Q (src/rns.jl): set by sgfhe_bkey_upload_rns2 / sgfhe_rns2_convert
-    bool have_rns2 = false;
-    Rns2Const rns2;
     struct Lane {
         uint64_t *dig = nullptr;
         uint32_t *yres = nullptr;
         uint32_t *ua = nullptr;
         int32_t *zpart = nullptr;  // small-batch form only: [cap_small][npr][4][2][m]
     } lane[2];
-    bool small_padded = false;  // SGFHE_SMALL_PADDED=1: small-batch grids padded to 8 bootstraps as up to round 3 (A/B)
-    bool small_lanes = true;    // SGFHE_SMALL_LANES=0: a call of a few gates as one chunk on one stream (A/B)
-    uint32_t small_lanes_max = 24;   // ... up to this many gates (SGFHE_SMALL_LANES=<n>)
-    uint32_t crt1_max = 0;      // k_crt_lean launches of at most this many coefficients take one per thread
-                                // (SGFHE_CRT1_GATES gates' worth: default 8; 0 = never.  Same call, 1 / 2 / 4 / 8
-                                // gates: 18.6 / 19.4 / 20.8 / 23.9 ms with four per thread, 17.9 / 18.6 / 20.2 / 23.4
-                                // with one, profiles/r04_exp_crt1.txt)
-    uint32_t small_max = 24;  // chunks of at most this many bootstraps take the small-batch form
-                              // (measured crossover at Params(1024): 24 -> 32.3 vs 40.9 ms, 32 -> 44.0 vs 42.3 ms)
     // staging buffers of the host-pointer entry point (sgfhe_bootstrap_batch: the drop-in signature of
     // fhe.jl:608-610, usually called with one gate): grown on demand and kept, so that a call does
     // not pay a hipMalloc / hipFree pair (hipFree synchronises the device)
@@ -236,7 +270,6 @@ struct sgfhe_ctx {
     // copies through its own pinned buffers instead (one CPU memcpy + one true DMA).
     DevBuf<uint64_t, true> pin_in, pin_out;
     std::vector<uint64_t> co_buf;   // gathered inputs and results of a combined call this ctx leads (Coalescer)
-    bool use_pin = true;   // SGFHE_HOST_PIN=0 in the environment: direct copies (A/B measurements)
     // device buffers of sgfhe_circuit_run, grown on demand and kept like the I/O staging: the wire table
     // [slot][instance][n + 1], one call's staging [a1 | a2 | b1 | b2 | result rows], the plan's node tables,
     // and the collected outputs
@@ -1487,32 +1520,35 @@ sgfhe_ctx::Basis &key_basis(sgfhe_ctx *c) { return c->basis[c->nb - 1]; }
 // key form cannot be derived) leaves a ctx that refuses to bootstrap instead of one whose two bases hold
 // different keys.
 void key_dirty(sgfhe_ctx *c) { c->have_key = false; }
-int32_t key_finish(sgfhe_ctx *c, int32_t rc) {
-    if (rc == SGFHE_OK && c->nb == 2) {
-        const sgfhe_ctx::Basis &Bg = c->basis[1];
-        sgfhe_ctx::Basis &Sm = c->basis[0];
-        hipError_t e = hipSuccess;
-        if (!Sm.d_key) {
-            Sm.key_bytes = (size_t)c->n * Sm.npr * 8 * c->M * 4;
-            e = hipMalloc(&Sm.d_key, Sm.key_bytes);
-            if (e == hipSuccess) c->shared->own(Sm.d_key);
-        }
-        if (e == hipSuccess) {
-            KeyFactors fac = {};
-            for (uint32_t i = 0; i < Sm.npr; i++) {
-                const uint32_t p = Sm.primes[i];
-                uint32_t f = (uint32_t)((1ull << 32) % p);                   // R: Montgomery form
-                for (uint32_t j = Sm.npr; j < Bg.npr; j++) f = mulmod32(f, Bg.primes[j] % p, p);
-                fac.f[i] = centre32(f, p);
-            }
-            const size_t total = Sm.key_bytes / 4;
-            hipLaunchKernelGGL(k_key_derive, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                               Bg.d_key, Sm.d_key, Sm.d_primes, fac, Bg.npr, Sm.npr, (uint32_t)c->logm, total);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        }
-        if (e != hipSuccess) { rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); c->have_key = false; }
+int32_t key_alloc(sgfhe_ctx *c, sgfhe_ctx::Basis &S) {
+    if (S.d_key) return SGFHE_OK;
+    S.key_bytes = (size_t)c->n * S.npr * 8 * c->M * 4;
+    HIPCHK(c, hipMalloc(&S.d_key, S.key_bytes));
+    c->shared->own(S.d_key);
+    return SGFHE_OK;
+}
+// the smaller basis's key from the larger one's (a ctx with two bases), waited for
+int32_t key_derive(sgfhe_ctx *c) {
+    const sgfhe_ctx::Basis &Bg = c->basis[1];
+    sgfhe_ctx::Basis &Sm = c->basis[0];
+    const int32_t rc = key_alloc(c, Sm);
+    if (rc) return rc;
+    KeyFactors fac = {};
+    for (uint32_t i = 0; i < Sm.npr; i++) {
+        const uint32_t p = Sm.primes[i];
+        uint32_t f = (uint32_t)((1ull << 32) % p);                   // R: Montgomery form
+        for (uint32_t j = Sm.npr; j < Bg.npr; j++) f = mulmod32(f, Bg.primes[j] % p, p);
+        fac.f[i] = centre32(f, p);
     }
+    const size_t total = Sm.key_bytes / 4;
+    hipLaunchKernelGGL(k_key_derive, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
+                       Bg.d_key, Sm.d_key, Sm.d_primes, fac, Bg.npr, Sm.npr, (uint32_t)c->logm, total);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SGFHE_OK;
+}
+int32_t key_finish(sgfhe_ctx *c, int32_t rc) {
+    if (rc == SGFHE_OK && c->nb == 2 && (rc = key_derive(c))) c->have_key = false;
     c->active = mode_basis(c);
     return rc;
 }
@@ -1551,43 +1587,6 @@ KeyBlobHeader blob_header(sgfhe_ctx *c) {
     h.prime_hash = f;
     h.payload_bytes = (uint64_t)c->n * S.npr * 8 * c->M * 4;
     return h;
-}
-
-int32_t key_alloc(sgfhe_ctx *c, sgfhe_ctx::Basis &S) {
-    if (S.d_key) return SGFHE_OK;
-    S.key_bytes = (size_t)c->n * S.npr * 8 * c->M * 4;
-    HIPCHK(c, hipMalloc(&S.d_key, S.key_bytes));
-    c->shared->own(S.d_key);
-    return SGFHE_OK;
-}
-
-// canonical [npolys][m][2 words] in host memory -> NTT-domain key polys poly0.. in keyhat
-int32_t key_transform_host(sgfhe_ctx *c, const uint64_t *canon, uint32_t npolys, int32_t *keyhat,
-                           const Rns2Const *rns2 = nullptr) {
-    const size_t poly_bytes = (size_t)c->M * 16;
-    uint32_t stage_polys = (uint32_t)(((size_t)64 << 20) / poly_bytes);
-    if (stage_polys < 8) stage_polys = 8;
-    if (stage_polys > npolys) stage_polys = npolys;
-    ulonglong2 *d_stage = nullptr;
-    HIPCHK(c, hipMalloc(&d_stage, (size_t)stage_polys * poly_bytes));
-    int32_t rc = SGFHE_OK;
-    for (uint32_t p0 = 0; p0 < npolys && rc == SGFHE_OK; p0 += stage_polys) {
-        const uint32_t np = (npolys - p0 < stage_polys) ? npolys - p0 : stage_polys;
-        hipError_t e = hipMemcpyAsync(d_stage, canon + (size_t)p0 * c->M * 2, (size_t)np * poly_bytes,
-                                      hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); break; }
-        if (rns2) {  // (v1, v2) limb pairs -> canonical residues, in place (rns.jl:32-40)
-            const size_t cnt = (size_t)np * c->M;
-            hipLaunchKernelGGL(k_rns2_to_canon, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0,
-                               c->stream, d_stage, cnt, *rns2, cur(c).d_crt, c->d_bad);
-        }
-        rc = launch_keytr(c, d_stage, keyhat, p0, np, c->stream);
-        if (rc) break;
-        e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    }
-    (void)hipFree(d_stage);
-    return rc;
 }
 
 int32_t create_streams(sgfhe_ctx *c) {
@@ -1696,41 +1695,11 @@ int32_t sgfhe_ctx_clone(sgfhe_ctx *src, sgfhe_ctx **out) {
     sgfhe_ctx *c = new (std::nothrow) sgfhe_ctx();
     if (!c) return fail(src, SGFHE_ERR_OOM, "out of host memory");
     *out = c;  // returned even on failure so that the caller can read the error string (and destroys it)
-    // what a bootstrap only reads: parameter set, bases with their device constants and key forms, tables
-    c->par = src->par;
-    c->device = src->device;
-    c->logm = src->logm;
-    c->M = src->M;
-    c->n = src->n;
-    c->Q = src->Q;
-    c->B = src->B;
-    c->create_flags = src->create_flags;
-    c->shared = src->shared;
-    for (int b = 0; b < 2; b++) c->basis[b] = src->basis[b];
-    c->nb = src->nb;
-    c->npr_max = src->npr_max;
-    c->tw_done = src->tw_done;
-    c->d_tw = src->d_tw;
-    c->d_twq = src->d_twq;
-    c->d_pow = src->d_pow;
-    memcpy(c->tw_head, src->tw_head, sizeof c->tw_head);
-    c->rnd_ok = src->rnd_ok;
-    c->have_rns2 = src->have_rns2;
-    c->rns2 = src->rns2;
-    c->have_key = true;
-    // the scheduling knobs as they stand (sgfhe_set_chunk / _lanes / _small_batch_max and the environment)
-    c->chunk = src->chunk;
-    c->lanes = src->lanes;
-    c->small_max = src->small_max;
-    c->small_lanes = src->small_lanes;
-    c->small_lanes_max = src->small_lanes_max;
-    c->small_padded = src->small_padded;
-    c->crt1_max = src->crt1_max;
-    c->split_max = src->split_max;
-    c->fused_min = src->fused_min;
-    c->use_pin = src->use_pin;
-    // its own: flatten mode (deterministic, call counter 0: active = 0), lanes' work buffers, streams, events,
-    // staging, timing, the error string and the lock
+    // the groups a clone takes over; its own -- flatten mode (deterministic, call counter 0: active = 0), lanes' work
+    // buffers, streams, events, staging, timing, the error string and the lock -- starts as in a new ctx
+    static_cast<CtxShared &>(*c) = *src;
+    static_cast<CtxKnobs &>(*c) = *src;
+    static_cast<CtxKeyState &>(*c) = *src;
     // The runtime deals streams onto its hardware queues (GPU_MAX_HW_QUEUES = 4) in the order they are created, and
     // packets of one hardware queue run in order: with four streams per ctx, the FIRST stream of every ctx -- the
     // one its calls run on -- would sit on the same queue and calls on different clones could never overlap on the
@@ -1783,9 +1752,9 @@ static int32_t circ_grow(sgfhe_ctx *c, DevBuf<T> &buf, size_t words) {
                                       " bytes failed");
 }
 
-// A synchronous entry of the circuit and pack paths: nothing of an earlier call is in flight when `queued` runs (it
-// may regrow ctx buffers, then queues on the ctx stream and waits for it); should it fail, whatever it queued finishes
-// before the buffers can be touched again.
+// A synchronous entry, after its checks: nothing of an earlier call is in flight when `queued` runs (it may regrow ctx
+// buffers, then queues on the ctx stream and waits for it); should it fail, whatever it queued finishes before the
+// buffers -- the ctx's, and the entry's own Scratch -- can be touched again.
 extern "C++" template <class F>
 static int32_t run_drained(sgfhe_ctx *c, F &&queued) {
     (void)hipSetDevice(c->device);
@@ -1796,6 +1765,41 @@ static int32_t run_drained(sgfhe_ctx *c, F &&queued) {
         c->pending = false;
     }
     return rc;
+}
+
+// DevBuf::grow for call-local scratch (struct Scratch): a failed allocation is the HIP error of the entry
+extern "C++" template <typename T>
+static int32_t scratch_alloc(sgfhe_ctx *c, Scratch<T> &buf, size_t words) {
+    const hipError_t e = buf.grow(words);
+    return e == hipSuccess ? SGFHE_OK : fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
+}
+
+// canonical [npolys][m][2 words] in host memory -> NTT-domain key polys poly0.. in keyhat, through a staging buffer
+// of at most 64 MiB, each stage waited for (rns2: the words are (v1, v2) limb pairs)
+static int32_t key_transform_host(sgfhe_ctx *c, const uint64_t *canon, uint32_t npolys, int32_t *keyhat,
+                                  const Rns2Const *rns2 = nullptr) {
+    const size_t poly_bytes = (size_t)c->M * 16;
+    uint32_t stage_polys = (uint32_t)(((size_t)64 << 20) / poly_bytes);
+    if (stage_polys < 8) stage_polys = 8;
+    if (stage_polys > npolys) stage_polys = npolys;
+    Scratch<ulonglong2> stage;
+    return run_drained(c, [&]() -> int32_t {
+        int32_t rc = scratch_alloc(c, stage, (size_t)stage_polys * c->M);
+        if (rc) return rc;
+        for (uint32_t p0 = 0; p0 < npolys; p0 += stage_polys) {
+            const uint32_t np = (npolys - p0 < stage_polys) ? npolys - p0 : stage_polys;
+            HIPCHK(c, hipMemcpyAsync(stage.p, canon + (size_t)p0 * c->M * 2, (size_t)np * poly_bytes,
+                                     hipMemcpyHostToDevice, c->stream));
+            if (rns2) {  // (v1, v2) limb pairs -> canonical residues, in place (rns.jl:32-40)
+                const size_t cnt = (size_t)np * c->M;
+                hipLaunchKernelGGL(k_rns2_to_canon, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0,
+                                   c->stream, stage.p, cnt, *rns2, cur(c).d_crt, c->d_bad);
+            }
+            if ((rc = launch_keytr(c, stage.p, keyhat, p0, np, c->stream))) return rc;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        return SGFHE_OK;
+    });
 }
 
 // [a1 | a2 | b1 | b2 | res]: the bootstrap inputs of `rows` rows (a: n words, b: one) carved out of `base`, and what
@@ -1903,42 +1907,61 @@ int32_t sgfhe_set_lanes(sgfhe_ctx *c, uint32_t lanes) {
     return SGFHE_OK;
 }
 
-static int32_t sgfhe_bkey_upload_impl(sgfhe_ctx *c, const uint64_t *canonical, size_t n_words) {
-    if (!c || !canonical) return SGFHE_ERR_INVALID_ARG;
+// One key writer (sgfhe_bkey_upload, _upload_rns2, _generate, _import_device_form): the lock; key_begin, which refuses
+// a key shared with clones and makes the larger basis the active one (the other basis's key is derived from it);
+// nothing of the ctx in flight; `body`; key_finish.  The body checks EVERY argument first, then calls key_alloc and
+// key_dirty, then writes: a call refused for its arguments leaves the previous key in place and usable, a call
+// that fails after key_dirty a ctx that refuses to bootstrap (SGFHE_ERR_NO_KEY), and it sets have_key at its end.
+extern "C++" template <class F>
+static int32_t key_write(sgfhe_ctx *c, F &&body) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    const size_t expect = (size_t)c->n * 8 * c->M * 2;
-    if (n_words != expect) return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload: n_words != n*8*m*2");
-    sgfhe_ctx::Basis &K = key_basis(c);
-    int32_t rc = key_alloc(c, K);
-    if (rc) return rc;
+    const int32_t rb = key_begin(c);
+    if (rb) return rb;
+    return key_finish(c, run_drained(c, body));
+}
+
+// the arguments are accepted: from here on the ctx has no key until the writer sets have_key
+static int32_t key_open(sgfhe_ctx *c) {
+    const int32_t rc = key_alloc(c, key_basis(c));
+    if (rc == SGFHE_OK) key_dirty(c);
+    return rc;
+}
+
+// sgfhe_bkey_upload and sgfhe_bkey_upload_rns2 once their arguments are accepted: [n][4][2][m] residues (rns2: limb
+// pairs) into the key; a word out of range, found on the device, refuses the key with `bad_msg`
+static int32_t key_upload(sgfhe_ctx *c, const uint64_t *words, const Rns2Const *rns2, const char *bad_msg) {
     HIPCHK(c, hipMemset(c->d_bad, 0, sizeof(uint32_t)));
-    key_dirty(c);
-    rc = key_transform_host(c, canonical, c->n * 8, K.d_key);
+    int32_t rc = key_open(c);
     if (rc) return rc;
+    if ((rc = key_transform_host(c, words, c->n * 8, key_basis(c).d_key, rns2))) return rc;
     uint32_t bad = 0;
     HIPCHK(c, hipMemcpy(&bad, c->d_bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad) {
-        c->have_key = false;
-        return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload: a residue is not in [0, Q)");
-    }
+    if (bad) return fail(c, SGFHE_ERR_INVALID_ARG, bad_msg);   // (no key: key_dirty)
     c->have_key = true;
     return SGFHE_OK;
 }
 
 int32_t sgfhe_bkey_upload(sgfhe_ctx *c, const uint64_t *canonical, size_t n_words) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    const int32_t rb = key_begin(c);   // on the larger basis; the other basis's key is derived from it
-    if (rb) return rb;
-    return key_finish(c, sgfhe_bkey_upload_impl(c, canonical, n_words));
+    return key_write(c, [&]() -> int32_t {
+        if (!canonical) return SGFHE_ERR_INVALID_ARG;
+        if (n_words != (size_t)c->n * 8 * c->M * 2) return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload: n_words != n*8*m*2");
+        return key_upload(c, canonical, nullptr, "bkey_upload: a residue is not in [0, Q)");
+    });
 }
 
-static int32_t sgfhe_bkey_generate_impl(sgfhe_ctx *c, const uint64_t *sk, size_t n_sk, const uint8_t *seed32,
-                            uint32_t noise) {
-    if (!c || !sk || !seed32) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
+namespace {
+struct KeygenScratch {   // the work buffers of sgfhe_bkey_generate
+    Scratch<uint64_t> sk;
+    Scratch<int32_t> shat, e;
+    Scratch<uint32_t> y;
+    Scratch<ulonglong2> acan, prod, canon;
+};
+}  // namespace
+
+static int32_t keygen_queued(sgfhe_ctx *c, const uint64_t *sk, size_t n_sk, const uint8_t *seed32, uint32_t noise,
+                             KeygenScratch &d) {
+    if (!sk || !seed32) return SGFHE_ERR_INVALID_ARG;
     if (c->M < 8) return fail(c, SGFHE_ERR_UNSUPPORTED, "bkey_generate needs m >= 8");
     ChaChaKey ck;
     for (int i = 0; i < 8; i++)
@@ -1949,65 +1972,44 @@ static int32_t sgfhe_bkey_generate_impl(sgfhe_ctx *c, const uint64_t *sk, size_t
     // e in [-noise, noise] is formed in int32 and lifted as Q - |e| (k_keygen_draw / k_keygen_finish)
     if (noise >= (1u << 30) || (u128)noise * 2 >= c->Q)
         return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_generate: noise must be below 2^30 and below Q / 2");
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    sgfhe_ctx::Basis &K = key_basis(c);   // (the active one: key_begin)
-    int32_t rc = key_alloc(c, K);
+    int32_t rc = key_open(c);
     if (rc) return rc;
-    key_dirty(c);
+    const sgfhe_ctx::Basis &K = key_basis(c);   // (the active one: key_begin)
     const uint32_t M = c->M, rows = c->n * 4;
     uint32_t R = 64;  // rows per batch (16 key slices)
     if (R > rows) R = rows;
-    uint64_t *d_sk = nullptr;
-    int32_t *d_shat = nullptr;
-    uint32_t *d_y = nullptr;
-    ulonglong2 *d_acan = nullptr, *d_prod = nullptr, *d_canon = nullptr;
-    int32_t *d_e = nullptr;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = hipMalloc(&d_sk, (size_t)c->n * 8))) break;
-        if ((e = hipMalloc(&d_shat, (size_t)K.npr * M * 4))) break;
-        if ((e = hipMalloc(&d_y, (size_t)R * K.npr * M * 4))) break;
-        if ((e = hipMalloc(&d_acan, (size_t)R * M * 16))) break;
-        if ((e = hipMalloc(&d_prod, (size_t)R * M * 16))) break;
-        if ((e = hipMalloc(&d_canon, (size_t)R * 2 * M * 16))) break;
-        if ((e = hipMalloc(&d_e, (size_t)R * M * 4))) break;
-        if ((e = hipMemcpyAsync(d_sk, sk, (size_t)c->n * 8, hipMemcpyHostToDevice, c->stream))) break;
-        rc = launch_keygen_ntt(c, d_sk, d_shat, nullptr, nullptr, 0, true, c->stream);
-        if (rc) break;
-        for (uint32_t row0 = 0; row0 < rows && rc == SGFHE_OK; row0 += R) {
-            const uint32_t tot = R * M;
-            hipLaunchKernelGGL(k_keygen_draw, dim3((tot / 4 + 255) / 256), dim3(256), 0, c->stream,
-                               d_acan, d_e, K.d_crt, ck, noise, row0, R, (uint32_t)c->logm);
-            rc = launch_keygen_ntt(c, d_sk, d_shat, d_acan, d_y, R, false, c->stream);
-            if (rc) break;
-            // CRT of the exact product, canonical residues into d_prod ([row][m] 16-byte values)
-            if ((rc = launch_crt_raw(c, d_y, reinterpret_cast<uint64_t *>(d_prod), tot,
-                                     MODE_NOACC | MODE_CANON, c->stream, RndArgs{}, 0u)))
-                break;
-            hipLaunchKernelGGL(k_keygen_finish, dim3((tot + 255) / 256), dim3(256), 0, c->stream, d_acan,
-                               d_prod, d_e, d_sk, d_canon, K.d_crt, row0, R, (uint32_t)c->logm);
-            if ((e = hipGetLastError())) break;
-            rc = launch_keytr(c, d_canon, K.d_key, row0 * 2, R * 2, c->stream);
-        }
-        if (rc || e) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    for (void *ptr : {(void *)d_sk, (void *)d_shat, (void *)d_y, (void *)d_acan, (void *)d_prod,
-                      (void *)d_canon, (void *)d_e})
-        if (ptr) (void)hipFree(ptr);
-    if (rc == SGFHE_OK) c->have_key = true;
-    return rc;
+    if ((rc = scratch_alloc(c, d.sk, c->n))) return rc;
+    if ((rc = scratch_alloc(c, d.shat, (size_t)K.npr * M))) return rc;
+    if ((rc = scratch_alloc(c, d.y, (size_t)R * K.npr * M))) return rc;
+    if ((rc = scratch_alloc(c, d.acan, (size_t)R * M))) return rc;
+    if ((rc = scratch_alloc(c, d.prod, (size_t)R * M))) return rc;
+    if ((rc = scratch_alloc(c, d.canon, (size_t)R * 2 * M))) return rc;
+    if ((rc = scratch_alloc(c, d.e, (size_t)R * M))) return rc;
+    HIPCHK(c, hipMemcpyAsync(d.sk.p, sk, (size_t)c->n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_keygen_ntt(c, d.sk.p, d.shat.p, nullptr, nullptr, 0, true, c->stream))) return rc;
+    for (uint32_t row0 = 0; row0 < rows; row0 += R) {
+        const uint32_t tot = R * M;
+        hipLaunchKernelGGL(k_keygen_draw, dim3((tot / 4 + 255) / 256), dim3(256), 0, c->stream,
+                           d.acan.p, d.e.p, K.d_crt, ck, noise, row0, R, (uint32_t)c->logm);
+        if ((rc = launch_keygen_ntt(c, d.sk.p, d.shat.p, d.acan.p, d.y.p, R, false, c->stream))) return rc;
+        // CRT of the exact product, canonical residues into d.prod ([row][m] 16-byte values)
+        if ((rc = launch_crt_raw(c, d.y.p, reinterpret_cast<uint64_t *>(d.prod.p), tot, MODE_NOACC | MODE_CANON,
+                                 c->stream, RndArgs{}, 0u)))
+            return rc;
+        hipLaunchKernelGGL(k_keygen_finish, dim3((tot + 255) / 256), dim3(256), 0, c->stream, d.acan.p,
+                           d.prod.p, d.e.p, d.sk.p, d.canon.p, K.d_crt, row0, R, (uint32_t)c->logm);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = launch_keytr(c, d.canon.p, K.d_key, row0 * 2, R * 2, c->stream))) return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_key = true;
+    return SGFHE_OK;
 }
 
 int32_t sgfhe_bkey_generate(sgfhe_ctx *c, const uint64_t *sk, size_t n_sk, const uint8_t *seed32,
                             uint32_t noise) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    const int32_t rb = key_begin(c);   // on the larger basis; the other basis's key is derived from it
-    if (rb) return rb;
-    return key_finish(c, sgfhe_bkey_generate_impl(c, sk, n_sk, seed32, noise));
+    KeygenScratch d;
+    return key_write(c, [&] { return keygen_queued(c, sk, n_sk, seed32, noise, d); });
 }
 
 static int32_t rns2_configure(sgfhe_ctx *c, uint64_t m1, uint64_t m2) {
@@ -2035,40 +2037,15 @@ static int32_t rns2_configure(sgfhe_ctx *c, uint64_t m1, uint64_t m2) {
     return SGFHE_OK;
 }
 
-static int32_t sgfhe_bkey_upload_rns2_impl(sgfhe_ctx *c, const uint64_t *pairs, size_t n_words, uint64_t m1,
-                               uint64_t m2) {
-    if (!c || !pairs) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    const size_t expect = (size_t)c->n * 8 * c->M * 2;
-    if (n_words != expect) return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload_rns2: bad n_words");
-    int32_t rc = rns2_configure(c, m1, m2);
-    if (rc) return rc;
-    sgfhe_ctx::Basis &K = key_basis(c);
-    rc = key_alloc(c, K);
-    if (rc) return rc;
-    HIPCHK(c, hipMemset(c->d_bad, 0, sizeof(uint32_t)));
-    key_dirty(c);
-    rc = key_transform_host(c, pairs, c->n * 8, K.d_key, &c->rns2);
-    if (rc) return rc;
-    uint32_t bad = 0;
-    HIPCHK(c, hipMemcpy(&bad, c->d_bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad) {
-        c->have_key = false;
-        return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload_rns2: a limb is not in [0, m_i)");
-    }
-    c->have_key = true;
-    return SGFHE_OK;
-}
-
 int32_t sgfhe_bkey_upload_rns2(sgfhe_ctx *c, const uint64_t *pairs, size_t n_words, uint64_t m1,
                                uint64_t m2) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    const int32_t rb = key_begin(c);   // on the larger basis; the other basis's key is derived from it
-    if (rb) return rb;
-    return key_finish(c, sgfhe_bkey_upload_rns2_impl(c, pairs, n_words, m1, m2));
+    return key_write(c, [&]() -> int32_t {
+        if (!pairs) return SGFHE_ERR_INVALID_ARG;
+        if (n_words != (size_t)c->n * 8 * c->M * 2) return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_upload_rns2: bad n_words");
+        const int32_t rc = rns2_configure(c, m1, m2);
+        if (rc) return rc;
+        return key_upload(c, pairs, &c->rns2, "bkey_upload_rns2: a limb is not in [0, m_i)");
+    });
 }
 
 int32_t sgfhe_rns2_convert(sgfhe_ctx *c, int to_pairs, const uint64_t *in, size_t count, uint64_t m1,
@@ -2076,30 +2053,28 @@ int32_t sgfhe_rns2_convert(sgfhe_ctx *c, int to_pairs, const uint64_t *in, size_
     if (!c || !in || !out) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
     if (count == 0) return SGFHE_OK;
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    int32_t rc = rns2_configure(c, m1, m2);
-    if (rc) return rc;
-    ulonglong2 *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, count * 16));
-    hipError_t e = hipSuccess;
+    Scratch<ulonglong2> d;
     uint32_t bad = 0;
-    do {
-        if ((e = hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream))) break;
-        if ((e = hipMemcpyAsync(d, in, count * 16, hipMemcpyHostToDevice, c->stream))) break;
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
+        int32_t r = rns2_configure(c, m1, m2);
+        if (r) return r;
+        if ((r = scratch_alloc(c, d, count))) return r;
+        HIPCHK(c, hipMemsetAsync(c->d_bad, 0, sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemcpyAsync(d.p, in, count * 16, hipMemcpyHostToDevice, c->stream));
         const dim3 grid((unsigned)((count + 255) / 256));
         if (to_pairs)
-            hipLaunchKernelGGL(k_canon_to_rns2, grid, dim3(256), 0, c->stream, d, count, c->rns2);
+            hipLaunchKernelGGL(k_canon_to_rns2, grid, dim3(256), 0, c->stream, d.p, count, c->rns2);
         else
-            hipLaunchKernelGGL(k_rns2_to_canon, grid, dim3(256), 0, c->stream, d, count, c->rns2,
+            hipLaunchKernelGGL(k_rns2_to_canon, grid, dim3(256), 0, c->stream, d.p, count, c->rns2,
                                cur(c).d_crt, c->d_bad);
-        if ((e = hipGetLastError())) break;
-        if ((e = hipMemcpyAsync(out, d, count * 16, hipMemcpyDeviceToHost, c->stream))) break;
-        if ((e = hipMemcpyAsync(&bad, c->d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(out, d.p, count * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&bad, c->d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SGFHE_OK;
+    });
+    if (rc) return rc;
+    // (after the device work, with `out` written: what a refused call leaves there is part of the interface)
     if (to_pairs) {  // canonical inputs must be below Q (checked on the host copy: debug hook)
         for (size_t i = 0; i < count; i++)
             if (ld128(in + 2 * i) >= c->Q) return fail(c, SGFHE_ERR_INVALID_ARG, "rns2_convert: value >= Q");
@@ -2131,38 +2106,28 @@ int32_t sgfhe_bkey_export_device_form(sgfhe_ctx *c, void *dst) {
     return SGFHE_OK;
 }
 
-static int32_t sgfhe_bkey_import_device_form_impl(sgfhe_ctx *c, const void *src) {
-    if (!c || !src) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    KeyBlobHeader got;
-    HIPCHK(c, hipMemcpy(&got, src, sizeof got, hipMemcpyDeviceToHost));
-    const KeyBlobHeader want = blob_header(c);
-    if (memcmp(got.magic, want.magic, sizeof want.magic) != 0)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_import: not a device-form key blob (bad magic)");
-    if (got.version != want.version)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_import: blob format version differs from this library");
-    if (memcmp(&got, &want, sizeof want) != 0)
-        return fail(c, SGFHE_ERR_INVALID_ARG,
-                    "bkey_import: the blob belongs to another parameter set (n, m, Q, B or RNS primes differ)");
-    sgfhe_ctx::Basis &K = key_basis(c);
-    int32_t rc = key_alloc(c, K);
-    if (rc) return rc;
-    key_dirty(c);
-    HIPCHK(c, hipMemcpyAsync(K.d_key, static_cast<const char *>(src) + sizeof got, K.key_bytes,
-                             hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->have_key = true;
-    return SGFHE_OK;
-}
-
 int32_t sgfhe_bkey_import_device_form(sgfhe_ctx *c, const void *src) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    const int32_t rb = key_begin(c);   // on the larger basis; the other basis's key is derived from it
-    if (rb) return rb;
-    return key_finish(c, sgfhe_bkey_import_device_form_impl(c, src));
+    return key_write(c, [&]() -> int32_t {
+        if (!src) return SGFHE_ERR_INVALID_ARG;
+        KeyBlobHeader got;
+        HIPCHK(c, hipMemcpy(&got, src, sizeof got, hipMemcpyDeviceToHost));
+        const KeyBlobHeader want = blob_header(c);
+        if (memcmp(got.magic, want.magic, sizeof want.magic) != 0)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_import: not a device-form key blob (bad magic)");
+        if (got.version != want.version)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "bkey_import: blob format version differs from this library");
+        if (memcmp(&got, &want, sizeof want) != 0)
+            return fail(c, SGFHE_ERR_INVALID_ARG,
+                        "bkey_import: the blob belongs to another parameter set (n, m, Q, B or RNS primes differ)");
+        const int32_t rc = key_open(c);
+        if (rc) return rc;
+        const sgfhe_ctx::Basis &K = key_basis(c);
+        HIPCHK(c, hipMemcpyAsync(K.d_key, static_cast<const char *>(src) + sizeof got, K.key_bytes,
+                                 hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->have_key = true;
+        return SGFHE_OK;
+    });
 }
 
 int32_t sgfhe_bootstrap_batch_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1,
@@ -2198,8 +2163,7 @@ static int32_t bootstrap_host(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
     const size_t out_row = 3 * (n + 1) * ((flags & SGFHE_FLAG_RAW_MODQ) ? 2 : 1);
     const size_t out_words = batch * out_row;
     const size_t acc_words = batch * 2 * (size_t)c->M * 2;
-    uint64_t *d_in = nullptr, *d_out = nullptr, *d_dig = nullptr;
-    ulonglong2 *d_acc = nullptr;
+    uint64_t *d_in = nullptr, *d_out = nullptr;
     const size_t dig_words = batch * 4 * (size_t)c->M;
     const size_t in_words = 2 * batch * (n + 1);
     int32_t rc = drain(c);   // the staging buffers may be regrown: nothing of an earlier call may be in flight
@@ -2234,40 +2198,32 @@ static int32_t bootstrap_host(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
         if (dbg) fprintf(stderr, "[sgfhe io] batch %zu pipelined: %.2f ms\n", batch, wall_ms() - t0);
         return rc;
     }
-    hipError_t e = hipSuccess;
-    uint64_t *d_a1 = d_in, *d_a2 = d_in + batch * n, *d_b1 = d_in + 2 * batch * n,
-             *d_b2 = d_b1 + batch;
-    const size_t a_bytes = batch * n * 8;
-    double t1 = 0, t2 = 0, t3 = 0;
-    do {
-        if (acc && (e = hipMalloc(&d_acc, acc_words * 8)) != hipSuccess) break;
-        if (digs && (e = hipMalloc(&d_dig, dig_words * 8)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_a1, a1, a_bytes, hipMemcpyHostToDevice, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_a2, a2, a_bytes, hipMemcpyHostToDevice, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_b1, b1, batch * 8, hipMemcpyHostToDevice, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_b2, b2, batch * 8, hipMemcpyHostToDevice, c->stream))) break;
-        t1 = wall_ms();
-        rc = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, batch, d_out, flags, n_iters, d_acc,
-                              c->stream, d_dig);
-        if (rc) break;
-        t2 = wall_ms();
-        if (digs && (e = hipMemcpyAsync(digs, d_dig, dig_words * 8, hipMemcpyDeviceToHost, c->stream)))
-            break;
-        if (out && (e = hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, c->stream)))
-            break;
-        if (acc && (e = hipMemcpyAsync(acc, d_acc, acc_words * 8, hipMemcpyDeviceToHost, c->stream)))
-            break;
-        e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) c->pending = false;
-        t3 = wall_ms();
+    Scratch<ulonglong2> d_acc;   // debug hooks only
+    Scratch<uint64_t> d_dig;
+    return run_drained(c, [&]() -> int32_t {
+        uint64_t *d_a1 = d_in, *d_a2 = d_in + batch * n, *d_b1 = d_in + 2 * batch * n, *d_b2 = d_b1 + batch;
+        const size_t a_bytes = batch * n * 8;
+        int32_t rq;
+        if (acc && (rq = scratch_alloc(c, d_acc, acc_words / 2))) return rq;
+        if (digs && (rq = scratch_alloc(c, d_dig, dig_words))) return rq;
+        HIPCHK(c, hipMemcpyAsync(d_a1, a1, a_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_a2, a2, a_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_b1, b1, batch * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_b2, b2, batch * 8, hipMemcpyHostToDevice, c->stream));
+        const double t1 = wall_ms();
+        if ((rq = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, batch, d_out, flags, n_iters, d_acc.p, c->stream, d_dig.p)))
+            return rq;
+        const double t2 = wall_ms();
+        if (digs) HIPCHK(c, hipMemcpyAsync(digs, d_dig.p, dig_words * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out) HIPCHK(c, hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, c->stream));
+        if (acc) HIPCHK(c, hipMemcpyAsync(acc, d_acc.p, acc_words * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->pending = false;
         if (dbg)
             fprintf(stderr, "[sgfhe io] batch %zu direct copies: copy-in %.2f ms, enqueue %.2f, wait + copy-out %.2f\n",
-                    batch, t1 - t0, t2 - t1, t3 - t2);
-    } while (0);
-    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    if (d_acc) (void)hipFree(d_acc);   // debug hooks only
-    if (d_dig) (void)hipFree(d_dig);
-    return rc;
+                    batch, t1 - t0, t2 - t1, wall_ms() - t2);
+        return SGFHE_OK;
+    });
 }
 
 // One request through the coalescer of the ctxs that share this key (csrc/coalescer.h).
@@ -2416,73 +2372,72 @@ int32_t sgfhe_debug_digits(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1,
 int32_t sgfhe_debug_flatten(sgfhe_ctx *c, const uint64_t *values, uint64_t *digits) {
     if (!c || !values || !digits) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
     const uint32_t M = c->M;
-    int32_t rc = ensure_work(c, 8);
-    if (rc) return rc;
-    const sgfhe_ctx::Lane &L = c->lane[0];
     for (uint32_t i = 0; i < 2 * M; i++)
         if (ld128(values + 2 * (size_t)i) >= c->Q)
             return fail(c, SGFHE_ERR_INVALID_ARG, "debug_flatten: a value is not in [0, Q)");
-    ulonglong2 *d_in = nullptr;
-    uint64_t *d_out = nullptr;
-    HIPCHK(c, hipMalloc(&d_in, (size_t)2 * M * 16));
-    hipError_t e = hipMalloc(&d_out, (size_t)4 * M * 8);
-    if (e != hipSuccess) { (void)hipFree(d_in); return fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); }
-    do {
-        if ((e = hipMemcpyAsync(d_in, values, (size_t)2 * M * 16, hipMemcpyHostToDevice, c->stream))) break;
-        hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_in,
+    Scratch<ulonglong2> d_in;
+    Scratch<uint64_t> d_out;
+    return run_drained(c, [&]() -> int32_t {
+        int32_t rc = ensure_work(c, 8);
+        if (rc) return rc;
+        const sgfhe_ctx::Lane &L = c->lane[0];
+        if ((rc = scratch_alloc(c, d_in, (size_t)2 * M))) return rc;
+        if ((rc = scratch_alloc(c, d_out, (size_t)4 * M))) return rc;
+        HIPCHK(c, hipMemcpyAsync(d_in.p, values, (size_t)2 * M * 16, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_in.p,
                            L.dig, cur(c).d_crt, 2 * M, (uint32_t)c->logm);
         hipLaunchKernelGGL(k_dump_digits, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, L.dig,
-                           d_out, 2 * M, (uint32_t)c->logm, 0u);
-        if ((e = hipGetLastError())) break;
-        if ((e = hipMemcpyAsync(digits, d_out, (size_t)4 * M * 8, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    return SGFHE_OK;
+                           d_out.p, 2 * M, (uint32_t)c->logm, 0u);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(digits, d_out.p, (size_t)4 * M * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SGFHE_OK;
+    });
+}
+
+// sgfhe_external_product and sgfhe_debug_cmux: one key slice [4][2][m] transformed into scratch, lane 0's digits
+// zeroed, (a | b) uploaded and flattened into them; then `middle(L, slice, ab, &src)`, the entry's own launches on
+// the ctx stream, which names the two polynomials [2][m] of 16-byte residues that go back as a_res and b_res.
+extern "C++" template <class F>
+static int32_t one_slice(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint64_t *slice, uint64_t *a_res,
+                         uint64_t *b_res, F &&middle) {
+    Scratch<int32_t> d_slice;
+    Scratch<ulonglong2> d_ab;
+    return run_drained(c, [&]() -> int32_t {
+        const uint32_t M = c->M, cpad = 8;
+        int32_t rc = ensure_work(c, cpad);
+        if (rc) return rc;
+        const sgfhe_ctx::Lane &L = c->lane[0];
+        if ((rc = scratch_alloc(c, d_slice, (size_t)cur(c).npr * 8 * M))) return rc;
+        if ((rc = scratch_alloc(c, d_ab, (size_t)2 * M))) return rc;
+        if ((rc = key_transform_host(c, slice, 8, d_slice.p))) return rc;
+        HIPCHK(c, hipMemsetAsync(L.dig, 0, (size_t)cpad * 2 * M * 16, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_ab.p, a, (size_t)M * 16, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_ab.p + M, b, (size_t)M * 16, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_ab.p,
+                           L.dig, cur(c).d_crt, 2 * M, (uint32_t)c->logm);
+        const ulonglong2 *src = nullptr;
+        if ((rc = middle(L, d_slice.p, d_ab.p, &src))) return rc;
+        HIPCHK(c, hipMemcpyAsync(a_res, src, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b_res, src + M, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SGFHE_OK;
+    });
 }
 
 int32_t sgfhe_external_product(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b,
                                const uint64_t *A, uint64_t *a_res, uint64_t *b_res) {
     if (!c || !a || !b || !A || !a_res || !b_res) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    const uint32_t M = c->M;
-    const uint32_t cpad = 8;
-    int32_t rc = ensure_work(c, cpad);
-    if (rc) return rc;
-    const sgfhe_ctx::Lane &L = c->lane[0];
-    int32_t *d_A = nullptr;
-    ulonglong2 *d_ab = nullptr;
-    HIPCHK(c, hipMalloc(&d_A, (size_t)cur(c).npr * 8 * M * 4));
-    hipError_t e = hipMalloc(&d_ab, (size_t)2 * M * 16);
-    if (e != hipSuccess) { (void)hipFree(d_A); return fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); }
-    do {
-        // A[4][2][m] is exactly one key slice (k = 0)
-        rc = key_transform_host(c, A, 8, d_A);
-        if (rc) break;
-        if ((e = hipMemsetAsync(L.dig, 0, (size_t)cpad * 2 * M * 16, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_ab, a, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_ab + M, b, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
-        hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_ab,
-                           L.dig, cur(c).d_crt, 2 * M, (uint32_t)c->logm);
-        rc = launch_extprod(c, L, d_A, cpad, 0, MODE_PLAIN, c->stream);
-        if (rc) break;
-        rc = launch_crt(c, L, cpad, MODE_NOACC | MODE_CANON, c->stream);
-        if (rc) break;
-        if ((e = hipMemcpyAsync(a_res, L.dig, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream))) break;
-        if ((e = hipMemcpyAsync(b_res, L.dig + 2 * (size_t)M, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d_A);
-    (void)hipFree(d_ab);
-    return rc;
+    // A[4][2][m] is exactly one key slice (k = 0)
+    return one_slice(c, a, b, A, a_res, b_res,
+                     [&](const sgfhe_ctx::Lane &L, const int32_t *d_A, ulonglong2 *, const ulonglong2 **src) -> int32_t {
+        int32_t rc = launch_extprod(c, L, d_A, 8, 0, MODE_PLAIN, c->stream);
+        if (rc) return rc;
+        *src = reinterpret_cast<const ulonglong2 *>(L.dig);     // canonical residues, in place of the digits
+        return launch_crt(c, L, 8, MODE_NOACC | MODE_CANON, c->stream);
+    });
 }
 
 int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint64_t *C,
@@ -2490,44 +2445,22 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, con
     if (!c || !a || !b || !C || !a_res || !b_res) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
     if (j >= 2 * (uint64_t)c->M) return fail(c, SGFHE_ERR_INVALID_ARG, "debug_cmux: j must be in [0, 2 m)");
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    const uint32_t M = c->M;
-    const uint32_t cpad = 8;
-    int32_t rc = ensure_work(c, cpad);
-    if (rc) return rc;
-    const sgfhe_ctx::Lane &L = c->lane[0];
-    int32_t *d_C = nullptr;
-    ulonglong2 *d_ab = nullptr;
-    HIPCHK(c, hipMalloc(&d_C, (size_t)cur(c).npr * 8 * M * 4));
-    hipError_t e = hipMalloc(&d_ab, (size_t)2 * M * 16);
-    if (e != hipSuccess) { (void)hipFree(d_C); return fail(c, SGFHE_ERR_HIP, hipGetErrorString(e)); }
     const uint32_t jw = (uint32_t)j;
-    do {
-        rc = key_transform_host(c, C, 8, d_C);  // C[4][2][m] is one key slice
-        if (rc) break;
-        if ((e = hipMemsetAsync(L.dig, 0, (size_t)cpad * 2 * M * 16, c->stream))) break;
-        if ((e = hipMemsetAsync(L.ua, 0, (size_t)cpad * c->n * 4, c->stream))) break;
-        if ((e = hipMemcpyAsync(L.ua, &jw, 4, hipMemcpyHostToDevice, c->stream))) break;  // u.a[0] of bootstrap 0
-        if ((e = hipMemcpyAsync(d_ab, a, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
-        if ((e = hipMemcpyAsync(d_ab + M, b, (size_t)M * 16, hipMemcpyHostToDevice, c->stream))) break;
-        hipLaunchKernelGGL(k_flatten_canon, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, d_ab,
-                           L.dig, cur(c).d_crt, 2 * M, (uint32_t)c->logm);
-        rc = launch_extprod(c, L, d_C, cpad, 0, 0u, c->stream);     // iteration k = 0, with the rotation
-        if (rc) break;
-        rc = launch_crt(c, L, cpad, 0u, c->stream);                  // acc <- acc + D, flattened again
-        if (rc) break;
+    // C[4][2][m] is one key slice
+    return one_slice(c, a, b, C, a_res, b_res,
+                     [&](const sgfhe_ctx::Lane &L, const int32_t *d_C, ulonglong2 *d_ab, const ulonglong2 **src) -> int32_t {
+        const uint32_t M = c->M;
+        HIPCHK(c, hipMemsetAsync(L.ua, 0, (size_t)8 * c->n * 4, c->stream));
+        HIPCHK(c, hipMemcpyAsync(L.ua, &jw, 4, hipMemcpyHostToDevice, c->stream));  // u.a[0] of bootstrap 0
+        int32_t rc = launch_extprod(c, L, d_C, 8, 0, 0u, c->stream);     // iteration k = 0, with the rotation
+        if (rc) return rc;
+        if ((rc = launch_crt(c, L, 8, 0u, c->stream))) return rc;        // acc <- acc + D, flattened again
         hipLaunchKernelGGL(k_dump_acc, dim3((2 * M + 255) / 256), dim3(256), 0, c->stream, L.dig, d_ab,
                            cur(c).d_crt, 2 * M, (uint32_t)c->logm, 0u);
-        if ((e = hipGetLastError())) break;
-        if ((e = hipMemcpyAsync(a_res, d_ab, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream))) break;
-        if ((e = hipMemcpyAsync(b_res, d_ab + M, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d_C);
-    (void)hipFree(d_ab);
-    return rc;
+        HIPCHK(c, hipGetLastError());
+        *src = d_ab;
+        return SGFHE_OK;
+    });
 }
 
 // The pack work buffers of the ctx for calls of at most `count` ciphertexts and `total` ciphertexts of
@@ -2683,24 +2616,20 @@ int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uin
 
 int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const uint32_t *in,
                         uint32_t *out) {
-    if (!c || !in || !out || prime_index >= cur(c).npr) return SGFHE_ERR_INVALID_ARG;
+    if (!c || !in || !out) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);
-    (void)hipSetDevice(c->device);
-    SGFHE_QUIESCE(c);
-    uint32_t *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, (size_t)2 * c->M * 4));
-    int32_t rc = SGFHE_OK;
-    hipError_t e;
-    do {
-        if ((e = hipMemcpyAsync(d, in, (size_t)c->M * 4, hipMemcpyHostToDevice, c->stream))) break;
-        rc = launch_dbgntt(c, d, d + c->M, prime_index, inverse, c->stream);
-        if (rc) break;
-        if ((e = hipMemcpyAsync(out, d + c->M, (size_t)c->M * 4, hipMemcpyDeviceToHost, c->stream))) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    if (prime_index >= cur(c).npr) return SGFHE_ERR_INVALID_ARG;
+    Scratch<uint32_t> d;
+    return run_drained(c, [&]() -> int32_t {
+        const size_t M = c->M;
+        int32_t rc = scratch_alloc(c, d, 2 * M);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(d.p, in, M * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = launch_dbgntt(c, d.p, d.p + M, prime_index, inverse, c->stream))) return rc;
+        HIPCHK(c, hipMemcpyAsync(out, d.p + M, M * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SGFHE_OK;
+    });
 }
 
 int32_t sgfhe_debug_primes(const sgfhe_ctx *c, uint32_t *count, uint32_t *primes) {

@@ -543,6 +543,27 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * of a parity node of 8, 16 and 32 refreshed wires max |e| = 146, 202 and 256 -- an eighth of the margin at 32 terms,
  * the errors adding like independent ones; CRC-16 of 32-bit messages (examples/encrypted_crc.py --direct, one block)
  * has a worst packed phase error of 33 (RESULTS.md, profiles/r13_circuit_wsum.txt).
+ *
+ * LUT nodes (sgfhe_circuit_create_lut): any function of three wires in one bootstrap, the node form of
+ * sgfhe_bootstrap_lut_batch (its contract and noise rule are with its declaration below).  The arrays are those of
+ * sgfhe_circuit_create_w plus node_table[n_gates] (read for LUT nodes only, must be below 256); node_kind[g] = 2 marks
+ * a LUT NODE.  sgfhe_circuit_create_w itself keeps rejecting kinds other than 0 and 1.
+ * A LUT node has exactly three terms, at positions 0, 1 and 2, all of weight 1.  Every wire has a SCALE: scale 0 is
+ * the codeword Dr -- input wires, every wire of a kind-0 or kind-1 node, and wire +0 of a LUT node; wires +1 and +2 of
+ * a LUT node have scales 1 and 2, codewords Dr/2 and Dr/4.  Position i of a LUT node must reference the constant or a
+ * wire of scale 2 - i; every other reference in the plan -- the terms of the other node kinds and all outputs -- must
+ * have scale 0.  Anything else is SGFHE_ERR_INVALID_ARG with *out NULL.  NOT at position i is a -> -a,
+ * b -> (Dr >> (2 - i)) - b mod r; lane shifts work as everywhere, filling with FALSE and applying NOT afterwards.
+ * The node is one row of its level call -- pruning, levels, slots, row and call numbering and the draws are those of
+ * any node -- with bootstrap inputs (a1, b1) = U = X0 + X1 + X2 mod r and (a2, b2) = 0; its three wires are the three
+ * rows of sgfhe_bootstrap_lut_batch for node_table[g], with s = x0 + 2 x1 + 4 x2.  A level call may mix all three
+ * kinds: LUT rows start at amplitude A0 and leave through the LUT extraction, the other rows take exactly the path
+ * they take without LUT nodes.  In an un-reduced call (SGFHE_CIRCUIT_PACK_DIRECT) the LUT rows are the scaled
+ * residues, and their ModRed gives the words of the reduced call.  An output naming wire +0 of a LUT node is
+ * REFRESHED, or LIFTED under SGFHE_CIRCUIT_PACK_LIFT, as a LOW wire is.  `fan` -- the LUT node (FALSE, FALSE, x) of
+ * table 0xF0 -- brings a scale-0 wire to all three scales in one bootstrap.  Every run entry point takes such a plan.
+ * The probe's plaintext evaluation knows LUT nodes, and the record of a wire of scale k is taken against its own
+ * codeword C = Dr >> k: e is centred against bit C, stats[1] counts |e| >= C/2 and stats[5] counts |e| >= C/4.
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -567,6 +588,15 @@ int32_t sgfhe_circuit_create_w(uint32_t n_inputs,
                                const int32_t *term_weight, size_t n_gates, const uint32_t *outputs,
                                const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
                                uint32_t group, sgfhe_circuit **out);
+int32_t sgfhe_circuit_create_lut(uint32_t n_inputs,
+                                 const uint32_t *node_kind /* [n_gates]: 0 classic, 1 sum node, 2 = LUT node */,
+                                 const uint32_t *node_start /* [n_gates + 1], CSR into the term arrays, [0] = 0 */,
+                                 const uint32_t *term_ref, const int32_t *term_shift /* NULL = all 0 */,
+                                 const int32_t *term_weight,
+                                 const uint32_t *node_table /* [n_gates]: the truth table of a LUT node, below 256 */,
+                                 size_t n_gates, const uint32_t *outputs,
+                                 const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
+                                 uint32_t group, sgfhe_circuit **out);
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
@@ -674,6 +704,60 @@ int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t b
  * count = 0 does nothing.  A word that is not below r is SGFHE_ERR_INVALID_ARG before anything is queued.
  */
 int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *ctx, const uint64_t *lwe, size_t count, uint64_t *out);
+
+/*
+ * LUT bootstraps: any function of three bits in one bootstrap.
+ *
+ * A gate bootstrap separates the four phases 0, Dr, 2 Dr, 3 Dr of a sum of wires at codeword Dr = r/4, and the test
+ * polynomial is antiperiodic with period r = 4 Dr, so only threshold functions of the sum come out of it.  Here the
+ * three inputs arrive at the codewords Dr/4, Dr/2 and Dr: their sum has phase s Dr/4 + e with s = x0 + 2 x1 + 4 x2 in
+ * 0..7, eight phases that fill exactly one half period, and ANY 8-entry truth table is an antiperiodic sign pattern
+ * over them -- a +-1 combination of at most seven shifted copies of the step the accumulator holds.  The k-loop is the
+ * one of sgfhe_bootstrap_batch; only its two ends differ.
+ *
+ *   a [batch][n], b [batch]   the rows over Z_r, already the sum X0 + X1 + X2 of the three inputs
+ *   table [batch]             bit s of table[t] is the function value of row t at input sum s
+ *   out [batch][3][n + 1]     (with SGFHE_FLAG_RAW_MODQ: [batch][3][n + 1][2], residues mod Q)
+ *                             row 0 carries f at codeword Dr -- an ordinary wire --, row 1 at Dr/2, row 2 at Dr/4: a
+ *                             division is impossible on an LWE and a multiplication is free, so the accumulator starts
+ *                             at a quarter of the usual amplitude and the result leaves at x4, x2 and x1.  Any row can
+ *                             feed the input position of its scale of a later LUT bootstrap.
+ *
+ * The contract, with A0 = DQ_tilde >> 2 and sigma(s) = +1 if bit s of the table is set, else -1, for s = 0..7:
+ *   1. Init: the accumulator of sgfhe_bootstrap_batch for (a1, b1) = (a, b), (a2, b2) = 0 with A0 in place of DQ_tilde
+ *      (in the randomised mode the draws are unchanged).
+ *   2. The k-loop as it stands: the accumulators are those of sgfhe_debug_accumulators on a ctx whose
+ *      sgfhe_params.DQ_tilde is A0.
+ *   3. Extraction.  For a polynomial p of length m and i taken mod 2 m, P(p, i) = p[i] for i < m and -p[i - m] mod Q
+ *      otherwise.  Set sigma(8) := -sigma(0); let j_0 < j_1 < ... be the j in 1..8 with sigma(j) != sigma(j - 1) (an
+ *      odd number of them, at most 7), c(j) = (3 Dr - (2 j - 1) Dr/8) mod 2 m and kappa_i = -sigma(0) (-1)^i.  The base
+ *      LWE over Z_Q is alpha[e] = sum_i kappa_i P(acc_a, c(j_i) - e) for e in 0..n-1 and
+ *      beta = A0 + sum_i kappa_i P(acc_b, c(j_i)), all mod Q; its phase is A0 (1 + sigma(s)) when the phase of the
+ *      input row is s Dr/4 + e with |e| < Dr/8.  Row k of `out` (k = 0, 1, 2) is 2^(2 - k) (alpha, beta) mod Q, written
+ *      as 16-byte residues under SGFHE_FLAG_RAW_MODQ and through ModRed otherwise.
+ *
+ * Host pointers, synchronous, on the ctx stream; the ctx is locked for the call, and the call is never gathered with
+ * other callers'.  The call takes the next call number of the ctx's draw stream, and row t draws as bootstrap t of that
+ * call, exactly as in sgfhe_bootstrap_batch_device.  flags is 0 or SGFHE_FLAG_RAW_MODQ; anything else,
+ * SGFHE_FLAG_RAW_RNS2 included, is SGFHE_ERR_INVALID_ARG, as are a NULL pointer and a word that is not below r (before
+ * anything is queued, nothing written).  batch = 0 does nothing.  SGFHE_ERR_NO_KEY as elsewhere.
+ *
+ * The noise rule (MEASURED, as the rules of three-input and sum nodes are): a row is correct while the error of its
+ * phase against s Dr/4 is below Dr/8 in absolute value -- the test polynomial is 0 exactly on the midpoint, so Dr/8
+ * itself is not safe.  The errors of three summed inputs add un-weighted, so |e0 + e1 + e2| < Dr/8; a scaled row's own
+ * error is its ModRed rounding, about the size of any bootstrapped wire's, whatever its scale.  The inputs must
+ * therefore be bootstrapped rows: a fresh encryption after split is up to Dr/4 - 1 off and the oracle's
+ * lwe_encrypt_bits up to Dr/8, and neither may enter, not even at the Dr/4 position.  Measured on the CPU oracles with
+ * input errors up to +-(Dr/8 - 1), 16 rows and 18 tables, both flatten modes: every row decrypts at all three scales;
+ * the Z_Q error of the combination is at most 8e-4 of the codeword; the Z_r error after ModRed at most 5 of Dr = 256
+ * at Params(64) and 9 of Dr = 512 at Params(128).  At Params(1024) (Dr/8 = 512), 256 instances, inputs refreshed, then
+ * fanned, then LUT bootstraps two levels deep, both flatten modes: max |e| of the rows 23 of Dr = 4096, 25 of Dr/2 and
+ * 27 of Dr/4, the worst |e0 + e1 + e2| of a LUT input 36 -- a fourteenth of Dr/8; no row past a quarter of its
+ * codeword (RESULTS.md, profiles/r14_circuit_lut.txt, tools/lut_bench.py).
+ */
+int32_t sgfhe_bootstrap_lut_batch(sgfhe_ctx *ctx, const uint64_t *a /* [batch][n] */, const uint64_t *b /* [batch] */,
+                                  const uint8_t *table /* [batch] */, size_t batch,
+                                  uint64_t *out /* [batch][3][n + 1], x2 words with SGFHE_FLAG_RAW_MODQ */, uint32_t flags);
 
 /*
  * Noise probe: the LWE error of rows against the SECRET key, reduced on the device to exact integer statistics.

@@ -28,6 +28,14 @@ w in {-2, -1, 1, 2}, up to 64 terms: with s = the sum of w x mod 4 its wires are
 the linear LOW = U - 2 HI (s mod 2).  All weights 2 make HI the XOR of all terms -- `xor(*wires)` -- so a GF(2)-linear
 map is one node per output bit (gf2_matvec, crc16_ccitt); one term of weight 1 makes MID a refresh (`refresh(w)`).  A
 weight of 2 doubles the wire's error: use it on bootstrapped wires, not on fresh encryptions.
+
+LUT nodes (sgfhe_circuit_create_lut).  `lut(table, x0, x1, x2)` is ONE bootstrap that evaluates ANY function of three
+bits: bit s of `table` is its value at s = x0 + 2 x1 + 4 x2.  The three inputs arrive at the codewords Dr/4, Dr/2 and Dr,
+so a wire has a SCALE (0: Dr, 1: Dr/2, 2: Dr/4) and position i of a LUT node reads scale 2 - i; the node returns its bit
+at all three scales, (f, f_half, f_quarter), so any LUT output can feed any position of a later LUT node.  Everything
+else -- inputs, the wires of the other nodes, outputs -- is scale 0; `fan(x)` brings a scale-0 wire to all three scales
+in one bootstrap.  The inputs of a LUT node must be bootstrapped wires (refresh, then fan): the sum of their errors has
+to stay below Dr/8 (the noise rule in include/sgfhe_hip.h).
 """
 
 import ctypes
@@ -102,15 +110,28 @@ class Circuit:
         self.outputs = []          # [ref]
         self.gate_shifts = []      # [(x lane shift, y lane shift)] or (x, y, z lane shift), beside gates
         self.gate_weights = {}     # node -> (weight, ...) beside its references: the sum nodes (sum_node)
+        self.gate_tables = {}      # node -> truth table: the LUT nodes (lut)
         self.output_shifts = []    # [lane shift], beside outputs
         self._plan = None
         self._L = None
 
-    def _ref(self, w):
+    def scale(self, w):
+        """The scale of a wire: 0 (codeword Dr) but for wires +1 and +2 of a LUT node (1: Dr/2, 2: Dr/4); None for the
+        constant, which fits every scale."""
+        if w.id == FALSE_ID:
+            return None
+        if w.id < self.n_inputs:
+            return 0
+        g, k = divmod(w.id - self.n_inputs, 3)
+        return k if g in self.gate_tables else 0
+
+    def _ref(self, w, scale=0):
         if not isinstance(w, Wire):
             raise TypeError("expected a Wire, got %r" % (w,))
         if abs(w.shift) >= self.group:
             raise ValueError("%r: a lane shift must be inside the group of %d" % (w, self.group))
+        if self.scale(w) not in (None, scale):
+            raise ValueError("%r has scale %d where scale %d is read (Circuit.lut, Circuit.fan)" % (w, self.scale(w), scale))
         return w.ref
 
     def gate(self, x, y):
@@ -149,6 +170,27 @@ class Circuit:
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
 
+    def lut(self, table, x0, x1, x2):
+        """One LUT node: ONE bootstrap for any function of three bits.  Bit s of `table` (0 .. 255) is the value at
+        s = x0 + 2 x1 + 4 x2.  x0 must be a wire of scale 2 (codeword Dr/4), x1 of scale 1, x2 of scale 0, or the
+        constants.  Returns (f, f_half, f_quarter): the result at scales 0, 1 and 2."""
+        if not 0 <= int(table) < 256:
+            raise ValueError("a LUT node's table has 8 entries: 0 .. 255")
+        self.gates.append((self._ref(x0, 2), self._ref(x1, 1), self._ref(x2, 0)))
+        self.gate_shifts.append((x0.shift, x1.shift, x2.shift))
+        self.gate_tables[len(self.gates) - 1] = int(table)
+        self._invalidate()
+        base = self.n_inputs + 3 * (len(self.gates) - 1)
+        return Wire(base), Wire(base + 1), Wire(base + 2)
+
+    def fan(self, x):
+        """A scale-0 wire at all three scales in one bootstrap: lut(0xF0, FALSE, FALSE, x)."""
+        return self.lut(0xF0, Circuit.FALSE, Circuit.FALSE, x)
+
+    @property
+    def has_lut(self):
+        return bool(self.gate_tables)
+
     def xor(self, *wires):
         """The XOR of any number of wires (up to 64) in ONE bootstrap: HI of the sum node with every weight 2.  The
         wires should be bootstrapped ones (gate rows, refreshed wires): the node doubles their errors.  No wire at
@@ -162,7 +204,9 @@ class Circuit:
         return self.sum_node([(1, w)])[1]
 
     def kind(self, g):
-        """Node g: "classic" (gate), "gate3" or "sum" (sum_node)."""
+        """Node g: "classic" (gate), "gate3", "sum" (sum_node) or "lut"."""
+        if g in self.gate_tables:
+            return "lut"
         return "sum" if g in self.gate_weights else ("gate3" if len(self.gates[g]) == 3 else "classic")
 
     def weights(self, g):
@@ -184,7 +228,7 @@ class Circuit:
 
     @property
     def has_gate3(self):
-        return any(len(g) == 3 for i, g in enumerate(self.gates) if i not in self.gate_weights)
+        return any(len(g) == 3 for i, g in enumerate(self.gates) if i not in self.gate_weights and i not in self.gate_tables)
 
     def output(self, *wires):
         """Set the circuit's outputs (wire references: inputs, constants and negated wires allowed)."""
@@ -215,14 +259,21 @@ class Circuit:
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
             os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
             h = ctypes.c_void_p()
-            if self.has_wsum:       # CSR: every node's terms, kind 1 for gate3 and sum nodes
-                kind = np.array([self.kind(g) != "classic" for g in range(len(self.gates))], dtype=np.uint32)
+            if self.has_wsum or self.has_lut:   # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes
+                kind = np.array([{"classic": 0, "lut": 2}.get(self.kind(g), 1) for g in range(len(self.gates))],
+                                dtype=np.uint32)
                 start = np.cumsum([0] + [len(x) for x in self.gates]).astype(np.uint32)
                 tr = np.array([ref for x in self.gates for ref in x], dtype=np.uint32)
                 ts = np.array([d for x in self.gate_shifts for d in x], dtype=np.int32)
                 tw = np.array([w for g in range(len(self.gates)) for w in self.weights(g)], dtype=np.int32)
-                rc = L.sgfhe_circuit_create_w(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), len(self.gates),
-                                              vp(o), vp(os_), len(self.outputs), self.group, ctypes.byref(h))
+                if self.has_lut:
+                    tb = np.array([self.gate_tables.get(g, 0) for g in range(len(self.gates))], dtype=np.uint32)
+                    rc = L.sgfhe_circuit_create_lut(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), vp(tb),
+                                                    len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
+                                                    ctypes.byref(h))
+                else:
+                    rc = L.sgfhe_circuit_create_w(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), len(self.gates),
+                                                  vp(o), vp(os_), len(self.outputs), self.group, ctypes.byref(h))
             elif self.has_gate3 or self.gate_weights:
                 # two-input nodes padded with SGFHE_CIRCUIT_NONE (and a shift of 0); a sum node of two unit weights is
                 # the three-input node (x, y, FALSE)
@@ -305,6 +356,11 @@ class Circuit:
         for levelnodes in self.schedule():
             for g in levelnodes:
                 base = self.n_inputs + 3 * g
+                if g in self.gate_tables:
+                    x = [val(ref, d).astype(np.int64) for ref, d in zip(self.gates[g], self.gate_shifts[g])]
+                    f = ((self.gate_tables[g] >> (x[0] + 2 * x[1] + 4 * x[2])) & 1).astype(bool)
+                    wires[base], wires[base + 1], wires[base + 2] = f, f, f
+                    continue
                 if g in self.gate_weights:
                     s = sum(w * val(ref, d).astype(np.int64)
                             for w, ref, d in zip(self.gate_weights[g], self.gates[g], self.gate_shifts[g])) % 4
@@ -417,34 +473,39 @@ def crc16_ccitt(message_bits, refresh_inputs=True):
     return gf2_matvec(crc16_matrix(message_bits), refresh_inputs=refresh_inputs)
 
 
-def lwe_not(words, r):
-    """NOT of LWEs [..., n + 1] over Z_r: enc_trivial(true) - w (a -> -a, b -> Dr - b, mod r)."""
+def lwe_not(words, r, one=None):
+    """NOT of LWEs [..., n + 1] over Z_r: enc_trivial(true) - w (a -> -a, b -> Dr - b, mod r).  one: the codeword of
+    the wire in place of Dr (positions 0 and 1 of a LUT node read wires at Dr/4 and Dr/2)."""
     words = np.asarray(words, dtype=np.uint64)
     t = np.zeros(words.shape[-1], dtype=np.uint64)
-    t[-1] = r // 4
+    t[-1] = r // 4 if one is None else one
     return (t + np.uint64(r) - words) & np.uint64(r - 1)
 
 
-def replay_levels(circuit, inputs, r, boot):
+def replay_levels(circuit, inputs, r, boot, boot_lut=None):
     """The circuit composed on the host from whole-level bootstrap calls, in the row and call order of
     sgfhe_circuit_run: inputs [n_inputs][instances][n + 1] -> outputs [n_outputs][instances][n + 1].
     `boot(call, a1, b1, a2, b2)` runs one call (rows of at most CALL_ROWS) and returns [rows][3][n + 1];
     `call` counts the calls from 0.  A three-input node is the row (x + y mod r, z); its third wire is
     x + y + z - 2 * (row 0 of the result) mod r.  A sum node is the row (U, FALSE), U = the sum of weight * term mod r
     -- the bootstrap adds its two inputs first, so this is also what (x + y, z) gives for unit weights -- and its third
-    wire U - 2 * (row 0 of the result) mod r.  A checking and measuring aid: the engine's circuit path does this on
-    the device (Engine.circuit_run)."""
+    wire U - 2 * (row 0 of the result) mod r.  A LUT node is the row (X0 + X1 + X2, FALSE); the LUT rows of a call
+    are run by `boot_lut(call, a, b, tables, idx)` -- their rows, their tables and their indices within the call, so
+    that a test can drive them from a second oracle -- which returns [rows][3][n + 1], the node's three wires; `boot`
+    sees every row of a call that holds other rows too (its results for the LUT rows are dropped) and is not called
+    for a call of LUT rows only.  A checking and measuring aid: the engine's circuit path does this on the device
+    (Engine.circuit_run)."""
     inputs = np.asarray(inputs, dtype=np.uint64)
     inst, row = inputs.shape[1], inputs.shape[2]
     n = row - 1
     wires = {}
 
-    def val(ref, d):
+    def val(ref, d, one=None):
         i = ref & ~NOT_BIT & 0xFFFFFFFF
         v = np.zeros((inst, row), dtype=np.uint64) if i == FALSE_ID else \
             (inputs[i] if i < circuit.n_inputs else wires[i])
         v = lane_shift(v, d, circuit.group)
-        return lwe_not(v, r) if ref & NOT_BIT else v
+        return lwe_not(v, r, one) if ref & NOT_BIT else v
 
     call = 0
     for nodes in circuit.schedule():
@@ -452,6 +513,10 @@ def replay_levels(circuit, inputs, r, boot):
         mask = np.uint64(r - 1)
 
         def pair(g):   # the bootstrap inputs of node g: (x, y), (x + y mod r, z) of a three-input node, (U, FALSE)
+            if circuit.kind(g) == "lut":   # position p reads a wire at the codeword Dr >> (2 - p)
+                vals = [val(ref, d, (r // 4) >> (2 - p))
+                        for p, (ref, d) in enumerate(zip(circuit.gates[g], circuit.gate_shifts[g]))]
+                return (vals[0] + vals[1] + vals[2]) & mask, np.zeros_like(vals[0])
             vals = [val(ref, d) for ref, d in zip(circuit.gates[g], circuit.gate_shifts[g])]
             if circuit.kind(g) == "sum":
                 u = sum(w * v.astype(np.int64) for w, v in zip(circuit.gate_weights[g], vals)) % r
@@ -464,15 +529,20 @@ def replay_levels(circuit, inputs, r, boot):
         x = np.concatenate([p[0] for p in pairs])
         y = np.concatenate([p[1] for p in pairs])
         res = np.zeros((len(x), 3, row), dtype=np.uint64)
+        tables = np.repeat(np.array([circuit.gate_tables.get(g, -1) for g in nodes], dtype=np.int64), inst)
         for r0 in range(0, len(x), CALL_ROWS):
             sl = slice(r0, r0 + CALL_ROWS)
-            res[sl] = boot(call, x[sl, :n], x[sl, n], y[sl, :n], y[sl, n])
+            idx = np.flatnonzero(tables[sl] >= 0)
+            if len(idx) < len(tables[sl]):
+                res[sl] = boot(call, x[sl, :n], x[sl, n], y[sl, :n], y[sl, n])
+            if len(idx):
+                res[r0 + idx] = boot_lut(call, x[sl, :n][idx], x[sl, n][idx], tables[sl][idx].astype(np.uint8), idx)
             call += 1
         for k, g in enumerate(nodes):
             sl = slice(k * inst, (k + 1) * inst)
             for w in range(3):
                 wires[circuit.n_inputs + 3 * g + w] = res[sl, w]
-            if circuit.kind(g) != "classic":
+            if circuit.kind(g) not in ("classic", "lut"):
                 wires[circuit.n_inputs + 3 * g + 2] = (x[sl] + y[sl] - np.uint64(2) * res[sl, 0]) & mask
     return np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
         else np.zeros((0, inst, row), np.uint64)
@@ -483,13 +553,14 @@ def pack_calls(n):
     return max(1, CALL_ROWS // n)
 
 
-def replay_ct(circuit, a, b, params, boot, pack):
+def replay_ct(circuit, a, b, params, boot, pack, boot_lut=None):
     """sgfhe_circuit_run_ct composed on the host: a, b [n_inputs][blocks][N] (N = n or m) -> ((w, v), lwe) with
     w, v [n_outputs][blocks][m] and lwe [n_outputs][blocks * n][n + 1].  The inputs are split with
     scheme.split_ciphertext_array (instance block * n + i = bit i of the block's ciphertext), the levels run
     through replay_levels and `boot`, and the ciphertexts q = output * blocks + block are packed in ascending
     order, pack_calls(n) at a time, by `pack(call, a, b)` (a [count][n][n], b [count][n] -> (w, v), each
-    [count][m]); `call` goes on counting after the levels' calls.  A checking and measuring aid."""
+    [count][m]); `call` goes on counting after the levels' calls.  boot_lut: as in replay_levels.  A checking and
+    measuring aid."""
     n, m = params.n, params.m
     a = np.asarray(a, dtype=np.uint64)
     b = np.asarray(b, dtype=np.uint64)
@@ -501,7 +572,11 @@ def replay_ct(circuit, a, b, params, boot, pack):
         calls[0] = call + 1
         return boot(call, *args)
 
-    lwe = replay_levels(circuit, inputs, params.r, counted)
+    def counted_lut(call, *args):
+        calls[0] = call + 1
+        return boot_lut(call, *args)
+
+    lwe = replay_levels(circuit, inputs, params.r, counted, counted_lut)
     groups = lwe.reshape(circuit.n_outputs * blocks, n, n + 1)
     w = np.zeros((len(groups), m), dtype=np.uint64)
     v = np.zeros((len(groups), m), dtype=np.uint64)
@@ -590,7 +665,7 @@ def lwe_not_modq(x, Q, DQ_tilde):
     return out
 
 
-def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False):
+def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut_raw=None):
     """sgfhe_circuit_run_ct_ex with SGFHE_CIRCUIT_PACK_DIRECT composed on the host: a, b [n_inputs][blocks][N] ->
     ((w, v), lwe) as replay_ct.  `boot_raw(call, a1, b1, a2, b2)` runs one call un-reduced and returns
     [rows][3][n + 1][2] residues mod Q; the levels run through it in the row and call order of replay_levels, their
@@ -602,25 +677,34 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False):
     [count][n][n + 1][2] -> (w, v), each [count][m]) packs the group: the gate's own rows for a direct output, NOT
     over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  lift=True (SGFHE_CIRCUIT_PACK_LIFT): the
     ciphertexts that are not direct take lift_words of their `lwe` rows instead -- no `boot_raw` call in the pack stage,
-    one call number per group.  A checking and measuring aid."""
+    one call number per group.  boot_lut_raw(call, a, b, tables, idx): the LUT rows of a call as in replay_levels,
+    un-reduced ([rows][3][n + 1][2]); an output naming wire +0 of a LUT node is refreshed or lifted.  A checking and
+    measuring aid."""
     n, m, r, Q = params.n, params.m, params.r, params.Q
     a = np.asarray(a, dtype=np.uint64)
     b = np.asarray(b, dtype=np.uint64)
     blocks = a.shape[1]
     inst = blocks * n
     inputs = split_ciphertext_array(a, b, n, r).reshape(circuit.n_inputs, inst, n + 1)
-    raws = []
+    raws = {}           # by call: a call of LUT rows only has none (and no direct output names its rows)
 
     def reduced(call, *args):
-        raws.append(np.asarray(boot_raw(call, *args), dtype=np.uint64))
-        return modred_words(raws[-1], Q, r)
+        raws[call] = np.asarray(boot_raw(call, *args), dtype=np.uint64)
+        return modred_words(raws[call], Q, r)
 
-    lwe = replay_levels(circuit, inputs, r, reduced)
-    call, k, raw_wire = len(raws), 0, {}
+    def reduced_lut(call, *args):
+        return modred_words(np.asarray(boot_lut_raw(call, *args), dtype=np.uint64), Q, r)
+
+    lwe = replay_levels(circuit, inputs, r, reduced, reduced_lut)
+    call, k, raw_wire = 0, 0, {}
     for nodes in circuit.schedule():                        # the calls of a level, back into the level's rows
-        calls = -(-len(nodes) * inst // CALL_ROWS)
-        level = np.concatenate(raws[k:k + calls])
+        rows = len(nodes) * inst
+        calls = -(-rows // CALL_ROWS)
+        level = np.concatenate([raws[k + j] if k + j in raws else
+                                np.zeros((min(CALL_ROWS, rows - j * CALL_ROWS), 3, n + 1, 2), dtype=np.uint64)
+                                for j in range(calls)])
         k += calls
+        call = k
         for rank, g in enumerate(nodes):
             for w in range(3):
                 raw_wire[circuit.n_inputs + 3 * g + w] = level[rank * inst:(rank + 1) * inst, w]
@@ -630,6 +714,8 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False):
         if i == FALSE_ID or i < circuit.n_inputs or circuit.output_shifts[o] != 0:
             return False
         g, w = divmod(i - circuit.n_inputs, 3)
+        if circuit.kind(g) == "lut":                            # wire +0 of a LUT node: refreshed or lifted
+            return False
         return not (w == 2 and circuit.kind(g) != "classic")   # XOR3 / LOW is linear over Z_r: no gate row over Z_Q
 
     n_ct, cpc = circuit.n_outputs * blocks, pack_calls(n)
@@ -743,7 +829,8 @@ def noise_report(circuit, stats):
             continue
         g = (wire - circuit.n_inputs) // 3 if wire >= circuit.n_inputs else None
         names = ("AND", "OR", "XOR") if g is None else \
-            {"classic": ("AND", "OR", "XOR"), "gate3": ("MAJ", "ONE_OR_TWO", "XOR3"), "sum": ("HI", "MID", "LOW")}[circuit.kind(g)]
+            {"classic": ("AND", "OR", "XOR"), "gate3": ("MAJ", "ONE_OR_TWO", "XOR3"), "sum": ("HI", "MID", "LOW"),
+             "lut": ("F", "F_HALF", "F_QUARTER")}[circuit.kind(g)]
         kind = "input" if g is None else names[(wire - circuit.n_inputs) % 3]
         rows.append(dict(wire=wire, kind=kind, node=g, level=0 if g is None else level[g], rows=st.rows,
                          wrong=st.wrong, max_abs=st.max_abs, mean=st.sum / st.rows,

@@ -6,8 +6,8 @@
 // The call arithmetic of a run lives here too (at the end): circuit_level_call, circuit_job_chunk, circuit_pack_runs and
 // circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
-// circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp and circuit_calls_sanitized.cpp drive it under ASan / UBSan
-// on the CPU.
+// circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp and circuit_calls_sanitized.cpp
+// drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -51,7 +51,9 @@ struct CircuitPlan {
     // CIRC_FALSE), a lane shift -- the term reads instance t + d of its slot where 0 <= t % group + d < group, the
     // constant FALSE elsewhere; 0 on every reference to the constant -- and a weight.  A three-input node is the sum
     // node of its three unit weights.
-    std::vector<uint32_t> node_kind;    // [live + n_outputs]: 0 classic (two unit terms), 1 sum node
+    std::vector<uint32_t> node_kind;    // [live + n_outputs]: bits 0..7 the kind -- 0 classic (two unit terms), 1 sum
+                                        // node, 2 LUT node (sgfhe_circuit_create_lut) -- and for a LUT node bits 8..15
+                                        // its truth table
     std::vector<uint32_t> term_start;   // [live + n_outputs + 1]: node k's terms are term_start[k] .. term_start[k + 1]
     std::vector<uint32_t> term_ref;     // [terms + 2 n_outputs]
     std::vector<int32_t> term_shift;    // [terms + 2 n_outputs]
@@ -73,6 +75,7 @@ struct CircuitPlan {
     // n_inputs + 3 k + w is wire w of the k-th live node in `order` -- with CIRC_NOT and CIRC_FALSE as in a reference
     std::vector<uint32_t> term_row;     // [terms]
     std::vector<uint32_t> sum_before;   // [live + 1], host only: sum nodes among order[0 .. k)
+    std::vector<uint32_t> lut_before;   // [live + 1], host only: LUT nodes among order[0 .. k)
     // Every device table above in one array, uploaded once per run: node_kind, term_start, term_ref, term_shift,
     // term_weight, out_slot, out_ref, out_shift, input_slot, jobs, each at its offset `at`
     std::vector<uint32_t> image;
@@ -82,6 +85,10 @@ struct CircuitPlan {
     bool lanes() const { return group > 1; }   // (group 1 admits no shift but 0)
     // live nodes order[ka .. kb] hold a sum node: the call takes an XOR3 kernel for its LOW rows
     bool gate3_in(uint32_t ka, uint32_t kb) const { return sum_before[kb + 1] != sum_before[ka]; }
+    // live nodes order[ka .. kb] hold a LUT node: the call carries a LUT descriptor
+    bool lut_in(uint32_t ka, uint32_t kb) const { return lut_before[kb + 1] != lut_before[ka]; }
+    uint32_t kind(size_t k) const { return node_kind[k] & 0xFFu; }
+    uint32_t table(size_t k) const { return (node_kind[k] >> 8) & 0xFFu; }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
     uint64_t level_rows(uint32_t L, uint64_t instances) const {
         return (uint64_t)(level_start[L + 1] - level_start[L]) * instances;
@@ -96,13 +103,15 @@ inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
 // sgfhe_circuit_create_lanes / sgfhe_circuit_create3 (a third reference CIRC_NO_INPUT leaves a two-input node; with
 // one, the node is the sum node of three unit weights).  `arity` 0: the CSR arrays of sgfhe_circuit_create_w.  Term i
 // of the circuit is refs[i], shifts[i] (NULL: 0), weights[i] (NULL: 1); node g's terms are first(g) .. first(g) +
-// count(g).
+// count(g).  `lut`: the arrays of sgfhe_circuit_create_lut, whose kind 2 marks a LUT node of table tables[g].
 struct CircuitNodes {
     int arity;
     const uint32_t *refs;
     const int32_t *shifts;
     const uint32_t *kind = nullptr, *start = nullptr;
     const int32_t *weights = nullptr;
+    const uint32_t *tables = nullptr;
+    bool lut = false;
 
     size_t first(size_t g) const { return arity ? (size_t)arity * g : start[g]; }
     size_t count(size_t g) const {
@@ -110,6 +119,8 @@ struct CircuitNodes {
         return arity == 3 && refs[3 * g + 2] != CIRC_NO_INPUT ? 3 : 2;
     }
     bool classic(size_t g) const { return arity ? count(g) == 2 : kind[g] == 0; }
+    bool is_lut(size_t g) const { return !arity && kind[g] == 2; }
+    uint32_t kind_of(size_t g) const { return classic(g) ? 0u : (is_lut(g) ? 2u : 1u); }
     int32_t weight(size_t i) const { return weights ? weights[i] : 1; }
 };
 
@@ -131,13 +142,18 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
     if (n_wires >= CIRC_FALSE) return SGFHE_ERR_INVALID_ARG;
     if (!N.arity) {   // the CSR itself, node by node, before a term of the node is read
         if (n_gates && (!N.kind || !N.start || !N.weights || N.start[0] != 0)) return SGFHE_ERR_INVALID_ARG;
+        if (n_gates && N.lut && !N.tables) return SGFHE_ERR_INVALID_ARG;
         for (size_t g = 0; g < n_gates; g++) {
-            if (N.kind[g] > 1 || N.start[g + 1] < N.start[g]) return SGFHE_ERR_INVALID_ARG;
+            if (N.kind[g] > (N.lut ? 2u : 1u) || N.start[g + 1] < N.start[g]) return SGFHE_ERR_INVALID_ARG;
             const size_t nj = N.count(g);
-            if (N.kind[g] == 0 ? nj != 2 : (nj < 1 || nj > SGFHE_CIRCUIT_MAX_TERMS)) return SGFHE_ERR_INVALID_ARG;
+            if (N.kind[g] == 2) {   // a LUT node: three unit terms (positions 0, 1, 2), a table of 8 entries
+                if (nj != 3 || N.tables[g] >= 256) return SGFHE_ERR_INVALID_ARG;
+            } else if (N.kind[g] == 0 ? nj != 2 : (nj < 1 || nj > SGFHE_CIRCUIT_MAX_TERMS)) {
+                return SGFHE_ERR_INVALID_ARG;
+            }
             for (size_t i = N.first(g); i < N.first(g) + nj; i++) {
                 const int32_t w = N.weights[i];
-                if (N.kind[g] == 0 ? w != 1 : (w == 0 || w < -2 || w > 2)) return SGFHE_ERR_INVALID_ARG;
+                if (N.kind[g] != 1 ? w != 1 : (w == 0 || w < -2 || w > 2)) return SGFHE_ERR_INVALID_ARG;
             }
         }
     }
@@ -150,6 +166,22 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
     for (size_t o = 0; o < n_outputs; o++) {
         const uint32_t id = wire_id(outputs[o]);
         if (id != CIRC_FALSE && id >= n_wires) return SGFHE_ERR_INVALID_ARG;
+    }
+    if (N.lut) {
+        // ---- the scale rule: a wire carries its bit at the codeword Dr >> scale.  Scale 0: inputs, every wire of a
+        // classic or sum node, wire +0 of a LUT node; wires +1 and +2 of a LUT node have scales 1 and 2.  Position i of
+        // a LUT node reads the constant or a wire of scale 2 - i; every other reference reads scale 0.
+        auto scale_ok = [&](uint32_t ref, uint32_t want) {
+            const uint32_t id = wire_id(ref);
+            if (id == CIRC_FALSE) return true;
+            const uint32_t have = id < n_inputs || !N.is_lut((id - n_inputs) / 3) ? 0u : (id - n_inputs) % 3;
+            return have == want;
+        };
+        for (size_t g = 0; g < n_gates; g++)
+            for (size_t i = N.first(g), end = i + N.count(g), p = 0; i < end; i++, p++)
+                if (!scale_ok(refs[i], N.is_lut(g) ? 2u - (uint32_t)p : 0u)) return SGFHE_ERR_INVALID_ARG;
+        for (size_t o = 0; o < n_outputs; o++)
+            if (!scale_ok(outputs[o], 0u)) return SGFHE_ERR_INVALID_ARG;
     }
     for (size_t g = 0; gate_shift && g < n_gates; g++)   // (the shift beside CIRC_NO_INPUT is ignored)
         for (size_t i = N.first(g), end = i + N.count(g); i < end; i++)
@@ -266,16 +298,18 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         };
         P.out_slot.resize(3 * P.live());
         P.sum_before.assign(P.live() + 1, 0);
+        P.lut_before.assign(P.live() + 1, 0);
         for (size_t k = 0; k < P.live(); k++) {
             const size_t g = P.order[k];
-            P.node_kind.push_back(N.classic(g) ? 0u : 1u);
+            P.node_kind.push_back(N.kind_of(g) | (N.is_lut(g) ? N.tables[g] << 8 : 0u));
             P.term_start.push_back((uint32_t)P.term_ref.size());
             for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
                 term(slot_ref(refs[i]), shift_of(refs[i], gate_shift, i), N.weight(i));
                 P.term_row.push_back(row_ref(refs[i]));
             }
             for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
-            P.sum_before[k + 1] = P.sum_before[k] + P.node_kind[k];
+            P.sum_before[k + 1] = P.sum_before[k] + (P.kind(k) == 1);
+            P.lut_before[k + 1] = P.lut_before[k] + (P.kind(k) == 2);
         }
         // ---- outputs, and the pack stage's pseudo-level: node live() + o is (TRUE, output o), the pair of
         // fhe.jl:669-673
@@ -294,6 +328,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             const int64_t g = node_of(id);
             if (g < 0 || P.out_shift[o] != 0) continue;
             if ((id - n_inputs) % 3 == 2 && !N.classic((size_t)g)) continue;   // LOW: linear over Z_r, no gate row
+            if (N.is_lut((size_t)g)) continue;   // wire +0 of a LUT node: refreshed or lifted, as a LOW wire is
             P.out_node[o] = rank_of[g];
             P.out_gate[o] = (id - n_inputs) % 3;
         }
@@ -356,6 +391,15 @@ inline int32_t circuit_plan_w(uint32_t n_inputs, const uint32_t *node_kind, cons
     return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
 }
 
+// The arrays of sgfhe_circuit_create_lut: those of sgfhe_circuit_create_w, kind 2 for a LUT node, and node_table.
+inline int32_t circuit_plan_lut(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
+                                const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
+                                const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
+    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true};
+    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
+}
+
 // The arrays of sgfhe_circuit_create_lanes.
 inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                             const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
@@ -398,7 +442,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
     if (!in_bits && P.n_inputs && instances) return SGFHE_ERR_INVALID_ARG;
     if (instances % P.group) return SGFHE_ERR_INVALID_ARG;
     const size_t wpr = circuit_bit_words(instances);
-    std::vector<uint64_t> shifted[2];
+    std::vector<uint64_t> shifted[3];
     try {
         table.assign(circuit_probe_rows(P) * wpr, 0);
         if (P.lanes())
@@ -432,7 +476,23 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
     for (size_t k = 0; k < P.live(); k++) {   // `order` is a topological order: inputs are rows filled before
         uint64_t *o = table.data() + ((size_t)P.n_inputs + 3 * k) * wpr;
         const uint32_t t0 = P.term_start[k], t1 = P.term_start[k + 1];
-        if (P.node_kind[k]) {
+        if (P.kind(k) == 2) {
+            // a LUT node: all three wires carry bit s of the table, s = x0 + 2 x1 + 4 x2 -- the OR over the set table
+            // entries of their minterms
+            const uint64_t *sx[3];
+            for (uint32_t p = 0; p < 3; p++) sx[p] = source(P.term_row[t0 + p], P.term_shift[t0 + p], shifted[p]);
+            const uint32_t tb = P.table(k);
+            for (size_t w = 0; w < wpr; w++) {
+                uint64_t x[3], f = 0;
+                for (uint32_t p = 0; p < 3; p++) x[p] = word(sx[p], P.term_row[t0 + p], w);
+                for (uint32_t sv = 0; sv < 8; sv++)
+                    if ((tb >> sv) & 1u)
+                        f |= (sv & 1 ? x[0] : ~x[0]) & (sv & 2 ? x[1] : ~x[1]) & (sv & 4 ? x[2] : ~x[2]);
+                o[w] = o[wpr + w] = o[2 * wpr + w] = f;
+            }
+            continue;
+        }
+        if (P.kind(k) == 1) {
             // a sum node: s = sum of w x mod 4 as two bit planes, (lo, hi) = (o[2 wpr ..], o[0 ..]), term by term
             // (-1 = 3 and -2 = 2 mod 4); then HI = s in {2, 3} = hi, MID = s in {1, 2} = lo ^ hi, LOW = s mod 2 = lo
             // (of three unit weights: MAJ, ONE_OR_TWO, XOR3)
@@ -480,6 +540,7 @@ struct CircuitCall {
     size_t j0, j1;     // the direct-pack jobs [j0, j1) those nodes produce: with any, a direct run leaves the call
                        // un-reduced
     bool sum;          // one of the nodes is a sum node: the call takes an XOR3 kernel for its LOW rows
+    bool lut;          // one of the nodes is a LUT node: the call carries a LUT descriptor
 };
 inline CircuitCall circuit_level_call(const CircuitPlan &P, uint32_t L, uint64_t row0, uint64_t instances) noexcept {
     CircuitCall C;
@@ -490,6 +551,7 @@ inline CircuitCall circuit_level_call(const CircuitPlan &P, uint32_t L, uint64_t
     C.j0 = (size_t)(std::lower_bound(P.job_k.begin(), P.job_k.end(), C.ka) - P.job_k.begin());
     C.j1 = (size_t)(std::upper_bound(P.job_k.begin(), P.job_k.end(), C.kb) - P.job_k.begin());
     C.sum = P.gate3_in(C.ka, C.kb);
+    C.lut = P.lut_in(C.ka, C.kb);
     return C;
 }
 

@@ -895,10 +895,18 @@ struct HostPipe {
     bool dbg;                             // SGFHE_DEBUG_IO is set (read once per call, bootstrap_host)
 };
 
+// The LUT rows of a call (sgfhe_bootstrap_lut_batch): `rows` is a device array of one word per row of the call,
+// LUT_ROW | truth table for a LUT row and 0 for a row of the classic path.  A LUT row starts at amplitude A0 (k_init)
+// and leaves through k_final_lut; `all` says that every row is one, so that k_final has nothing to write.
+struct LutDesc {
+    const uint32_t *rows;
+    bool all;
+};
+
 int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, const uint64_t *a2,
                          const uint64_t *b2, size_t batch, uint64_t *out, uint32_t flags,
                          uint64_t n_iters, ulonglong2 *acc_out, hipStream_t st,
-                         uint64_t *dig_out = nullptr, const HostPipe *hp = nullptr) {
+                         uint64_t *dig_out = nullptr, const HostPipe *hp = nullptr, const LutDesc *lut = nullptr) {
     if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
     uint32_t chunk = c->chunk ? c->chunk : default_chunk(c);
     const uint32_t mode = flatten_mode(c);
@@ -1064,12 +1072,13 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
                 ja1 = di; ja2 = di + cb * n; jb1 = di + 2 * cb * n; jb2 = jb1 + cb;
             }
             const uint32_t tot = J.cpad * M;
+            const uint32_t *jlut = lut ? lut->rows + c0 : nullptr;
             if (J.ra.rows)
                 hipLaunchKernelGGL(k_init<true>, dim3((tot + 255) / 256), dim3(256), 0, J.st, ja1, jb1, ja2, jb2,
-                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra);
+                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra, jlut);
             else
                 hipLaunchKernelGGL(k_init<false>, dim3((tot + 255) / 256), dim3(256), 0, J.st, ja1, jb1, ja2, jb2,
-                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra);
+                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra, jlut);
             HIPCHK(c, hipGetLastError());
         }
         if (dbg_io && g0 == 0) tw_first = wall_ms();
@@ -1091,9 +1100,14 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
             }
             if (out) {
                 const uint32_t t3 = J.cb * (n + 1);
-                hipLaunchKernelGGL(k_final, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                   out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, J.cb, n,
-                                   (uint32_t)c->logm, raw ? 1u : 0u, mode);
+                if (!lut || !lut->all)
+                    hipLaunchKernelGGL(k_final, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
+                                       out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, J.cb, n,
+                                       (uint32_t)c->logm, raw ? 1u : 0u, mode);
+                if (lut)   // the LUT rows of the chunk, over what k_final wrote for them
+                    hipLaunchKernelGGL(k_final_lut, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
+                                       out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, lut->rows + J.c0, J.cb, n,
+                                       (uint32_t)c->logm, raw ? 1u : 0u, mode);
                 if (raw && (flags & SGFHE_FLAG_RAW_RNS2))  // residues leave as (v1, v2) pairs (rns.jl:16-18)
                     hipLaunchKernelGGL(k_canon_to_rns2, dim3((3 * t3 + 255) / 256), dim3(256), 0, J.st,
                                        reinterpret_cast<ulonglong2 *>(out) + J.c0 * 3 * (n + 1),
@@ -1212,6 +1226,9 @@ int32_t build_basis(sgfhe_ctx *c, sgfhe_ctx::Basis &S, uint32_t npr, const uint3
     cc.dig0 = digits_of(0);
     cc.digP = digits_of(cc.DQ);
     cc.digN = digits_of((Q - cc.DQ) % Q);
+    cc.DQL = ld128(c->par.DQ_tilde) >> 2;   // LUT rows: A0 (DQ_tilde < Q is checked at ctx creation)
+    cc.digPL = digits_of(cc.DQL);
+    cc.digNL = digits_of((Q - cc.DQL) % Q);
     u128 cM = 1 % Q;
     for (int i = 0; i < NPR; i++) cM = (cM * S.primes[i]) % Q;  // < 2^94 * 2^29
     for (int i = 0; i < NPR; i++) {
@@ -2614,6 +2631,64 @@ int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uin
     return run_drained(c, [&] { return lwe_lift_queued(c, lwe, words, out); });
 }
 
+// everything sgfhe_bootstrap_lut_batch does on the device
+// (the pack path's buffers: its LWE staging takes the rows, zeros for the second input and the descriptor, its
+//  un-reduced rows the result in either form)
+static int32_t bootstrap_lut_queued(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const std::vector<uint32_t> &words,
+                                    size_t batch, uint64_t *out, uint32_t flags) {
+    const size_t n = c->n;
+    hipStream_t st = c->stream;
+    const bool raw = flags & SGFHE_FLAG_RAW_MODQ;
+    const size_t out_words = batch * 3 * (n + 1) * (raw ? 2 : 1);
+    int32_t rc;
+    // [a1 | a2 = 0 | b1 | b2 = 0 | descriptor words, two to a uint64]
+    if ((rc = circ_grow(c, c->pack_lwe, 2 * batch * n + 2 * batch + (batch + 1) / 2))) return rc;
+    if ((rc = circ_grow(c, c->pack_raw, batch * 3 * (n + 1)))) return rc;
+    const Staging S = staging(c->pack_lwe.p, batch, n);
+    uint32_t *d_lut = reinterpret_cast<uint32_t *>(c->pack_lwe.p + 2 * batch * n + 2 * batch);
+    HIPCHK(c, hipMemcpyAsync(S.a1, a, batch * n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.b1, b, batch * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(S.a2, 0, batch * n * 8, st));
+    HIPCHK(c, hipMemsetAsync(S.b2, 0, batch * 8, st));
+    HIPCHK(c, hipMemcpyAsync(d_lut, words.data(), batch * 4, hipMemcpyHostToDevice, st));
+    const LutDesc lut = {d_lut, true};
+    uint64_t *d_out = reinterpret_cast<uint64_t *>(c->pack_raw.p);
+    if ((rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, batch, d_out, flags, c->n, nullptr, st, nullptr, nullptr, &lut)))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->pending = false;
+    return SGFHE_OK;
+}
+
+int32_t sgfhe_bootstrap_lut_batch(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint8_t *table, size_t batch,
+                                  uint64_t *out, uint32_t flags) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    if (batch == 0) return SGFHE_OK;
+    if (!a || !b || !table || !out)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: NULL row, table or output pointer");
+    if (flags & ~SGFHE_FLAG_RAW_MODQ)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: flags is 0 or SGFHE_FLAG_RAW_MODQ");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    if (batch > ((size_t)1 << 31) / (c->n + 1))   // (row counts are 32-bit on the device)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: too many rows");
+    for (size_t i = 0; i < batch * c->n; i++)
+        if (a[i] >= c->par.r)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: word " + std::to_string(i) + " of a is not below r");
+    for (size_t i = 0; i < batch; i++)
+        if (b[i] >= c->par.r)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: b of row " + std::to_string(i) + " is not below r");
+    std::vector<uint32_t> words;   // the descriptor: LUT_ROW | table for every row
+    try {
+        words.resize(batch);
+    } catch (...) {
+        return fail(c, SGFHE_ERR_OOM, "out of host memory");
+    }
+    for (size_t t = 0; t < batch; t++) words[t] = LUT_ROW | table[t];
+    return run_drained(c, [&] { return bootstrap_lut_queued(c, a, b, words, batch, out, flags); });
+}
+
 int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const uint32_t *in,
                         uint32_t *out) {
     if (!c || !in || !out) return SGFHE_ERR_INVALID_ARG;
@@ -2927,6 +3002,14 @@ int32_t sgfhe_circuit_create_w(uint32_t n_inputs, const uint32_t *node_kind, con
     return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
 }
 
+int32_t sgfhe_circuit_create_lut(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
+                                 const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                 const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
+                                 const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out) {
+    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true};
+    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
+}
+
 int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
                              size_t n_outputs, sgfhe_circuit **out) {
     return sgfhe_circuit_create_lanes(n_inputs, gates, nullptr, n_gates, outputs, nullptr, n_outputs, 1u, out);
@@ -2999,8 +3082,9 @@ static NoiseGeom noise_wire_rows(size_t n, uint32_t wire, uint32_t count, size_t
 // The result rows [rows][3][n + 1] of the level call `C` that starts at row `row0`: C.kb - C.ka + 1 nodes of three wires.
 // A call inside one node: tiles over its rows; a call over several nodes: tiles over every node's instances (a tile
 // never straddles two nodes; rows outside the call are skipped)
+// (`kinds`: the device node kinds from node C.ka on when the call holds a LUT node, whose wires have their own codewords)
 static NoiseGeom noise_call_rows(size_t n, uint32_t n_inputs, const CircuitCall &C, uint64_t row0, uint32_t inst,
-                                 size_t bit_words) {
+                                 size_t bit_words, const uint32_t *kinds) {
     const bool one = C.ka == C.kb;
     NoiseGeom G = noise_wire_rows(n, (uint32_t)(n_inputs + 3 * (size_t)C.ka), C.rows, bit_words);
     G.row_stride = 3 * (n + 1);
@@ -3010,6 +3094,7 @@ static NoiseGeom noise_call_rows(size_t n, uint32_t n_inputs, const CircuitCall 
     G.instances = inst;
     G.inst0 = one ? (uint32_t)(row0 - (uint64_t)G.node0 * inst) : 0u;
     G.tiles = noise_tiles(one ? C.rows : inst);
+    G.kind = C.lut ? kinds : nullptr;
     return G;
 }
 // k_lwe_noise over `nodes` nodes of `gates` wires each, into the records NL.stats
@@ -3074,11 +3159,16 @@ struct CircuitRun {
     int32_t run();
     // the gather of one call: rows row0 .. row0 + rows of the level whose first node is `node0` of the plan's node table
     // (a level's first node, or live() for the pack stage's pseudo-level)
-    void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows) const {
+    // `lutw`: the call's LUT descriptor, for a level call that holds a LUT node
+    void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows, uint32_t *lutw = nullptr) const {
         hipLaunchKernelGGL(k_circ_gather, dim3(((uint32_t)rows * (uint32_t)row + 255) / 256), dim3(256), 0, st,
                            c->circ_wires.p, nodes, node0, S.a1, S.b1, S.a2, S.b2, (uint32_t)row0, (uint32_t)rows, inst,
-                           (uint32_t)n, r, P.group);
+                           (uint32_t)n, r, P.group, lutw);
     }
+    // words of the staging's rows (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even
+    // word offset); the LUT descriptor of a call lies behind them, one 32-bit word per row
+    size_t stage_words() const { return (size_t)sz.max_rows * (direct ? 8 : 5) * row; }
+    bool has_lut() const { return P.lut_before[P.live()] != 0; }
 };
 
 // every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller), and the probe's
@@ -3086,8 +3176,7 @@ struct CircuitRun {
 int32_t CircuitRun::grow() {
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
-    // (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even word offset)
-    if ((rc = circ_grow(c, c->circ_stage, (size_t)sz.max_rows * (direct ? 8 : 5) * row))) return rc;
+    if ((rc = circ_grow(c, c->circ_stage, stage_words() + (has_lut() ? ((size_t)sz.max_rows + 1) / 2 : 0)))) return rc;
     if (direct && (rc = circ_grow(c, c->circ_raw, sz.n_ct * n * row))) return rc;
     if (out && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_tab, P.at.words))) return rc;
@@ -3184,9 +3273,12 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
     const uint32_t *out_slot = d_out_slot + 3 * (size_t)C.k0, *kind = nodes.kind + C.k0;
     const uint32_t un = (uint32_t)n, r0 = (uint32_t)row0;
     const bool raw = direct && C.j1 > C.j0;
-    gather(C.k0, S, row0, C.rows);
+    // a call that holds a LUT node: its rows start at amplitude A0 and leave through k_final_lut (LutDesc)
+    const LutDesc lut = {reinterpret_cast<uint32_t *>(c->circ_stage.p + stage_words()), false};
+    gather(C.k0, S, row0, C.rows, C.lut ? const_cast<uint32_t *>(lut.rows) : nullptr);
     HIPCHK(c, hipGetLastError());
-    int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, C.rows, S.res, raw ? SGFHE_FLAG_RAW_MODQ : 0u, c->n, nullptr, st);
+    int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, C.rows, S.res, raw ? SGFHE_FLAG_RAW_MODQ : 0u, c->n, nullptr, st,
+                                  nullptr, nullptr, C.lut ? &lut : nullptr);
     if (rc) return rc;
     if (raw) {
         const ulonglong2 *res = reinterpret_cast<const ulonglong2 *>(S.res);
@@ -3215,7 +3307,8 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
                        C.rows, inst, un);
     HIPCHK(c, hipGetLastError());
     // the probe: the call's own result rows, read or not, before the next call overwrites them (same stream)
-    if (probe) return launch_lwe_noise(c, st, S.res, NL, noise_call_rows(n, P.n_inputs, C, row0, inst, bit_words),
+    if (probe) return launch_lwe_noise(c, st, S.res, NL,
+                                       noise_call_rows(n, P.n_inputs, C, row0, inst, bit_words, nodes.kind + C.ka),
                                        C.kb - C.ka + 1, 3);
     return SGFHE_OK;
 }

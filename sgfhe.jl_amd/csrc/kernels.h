@@ -75,7 +75,14 @@ struct CrtConst {
     uint32_t npr;        // number of primes in use
     uint32_t logr;
     ulonglong2 dig0, digP, digN;  // (lo, hi) digits of x' for acc = 0, DQ_tilde, Q - DQ_tilde
+    // LUT rows (sgfhe_bootstrap_lut_batch) start at a quarter of the amplitude
+    u128 DQL;                     // A0 = DQ_tilde >> 2
+    ulonglong2 digPL, digNL;      // digits of x' for acc = A0, Q - A0
 };
+
+// A call's optional per-row LUT descriptor (bootstrap_device): one word per row of the call, LUT_ROW | truth table for
+// a LUT row, 0 for a row of the classic path.
+constexpr uint32_t LUT_ROW = 0x100u;
 
 enum : uint32_t {
     MODE_PLAIN = 1u,  // k_extprod: no (x^j - 1) factor (external_product debug hook)
@@ -1564,7 +1571,8 @@ __global__ void __launch_bounds__(256)
 k_init(const uint64_t *__restrict__ a1, const uint64_t *__restrict__ b1,
        const uint64_t *__restrict__ a2, const uint64_t *__restrict__ b2,
        uint64_t *__restrict__ dig, uint32_t *__restrict__ ua, const CrtConst *__restrict__ CC,
-       uint32_t nvalid, uint32_t chunk, uint32_t n, uint32_t logm, uint32_t mode, RndArgs ra) {
+       uint32_t nvalid, uint32_t chunk, uint32_t n, uint32_t logm, uint32_t mode, RndArgs ra,
+       const uint32_t *__restrict__ lut = nullptr) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     const uint32_t M = 1u << logm;
     if (t >= chunk * M) return;
@@ -1572,6 +1580,8 @@ k_init(const uint64_t *__restrict__ a1, const uint64_t *__restrict__ b1,
     const uint32_t b = t >> logm;
     const uint32_t rmask = 2 * M - 1;  // r = 2 m
     const bool valid = b < nvalid;
+    // a LUT row of the chunk (lut: the descriptor from this chunk's first row on, or nullptr) starts at amplitude A0
+    const bool low = lut && valid && (lut[b] & LUT_ROW);
     if (i < n) ua[(size_t)b * n + i] =
         valid ? (uint32_t)((a1[(size_t)b * n + i] + a2[(size_t)b * n + i]) & rmask) : 0u;
     int tv = 0;
@@ -1586,7 +1596,8 @@ k_init(const uint64_t *__restrict__ a1, const uint64_t *__restrict__ b1,
     if (mode & MODE_RANDOM) {  // flatten(rng, .) of a = 0 and of b in {0, +-DQ_tilde}
         const u128 Q = CC->Q;
         const u128 offr = CC->offneg_rnd ? Q - CC->offneg_rnd : 0;
-        u128 xb = offr + (tv > 0 ? CC->DQ : (tv < 0 ? Q - CC->DQ : 0));
+        const u128 amp = low ? CC->DQL : CC->DQ;
+        u128 xb = offr + (tv > 0 ? amp : (tv < 0 ? Q - amp : 0));
         if (xb >= Q) xb -= Q;
         ChaChaKey key;
         uint32_t cz, cw;
@@ -1599,7 +1610,7 @@ k_init(const uint64_t *__restrict__ a1, const uint64_t *__restrict__ b1,
     }
     store_digits(dig, (size_t)b * 2 + 0, i, M, CC->dig0.x, CC->dig0.y);
     ulonglong2 d = CC->dig0;
-    if (valid) d = tv > 0 ? CC->digP : (tv < 0 ? CC->digN : CC->dig0);
+    if (valid) d = tv > 0 ? (low ? CC->digPL : CC->digP) : (tv < 0 ? (low ? CC->digNL : CC->digN) : CC->dig0);
     store_digits(dig, (size_t)b * 2 + 1, i, M, d.x, d.y);
 }
 
@@ -1661,6 +1672,65 @@ k_final(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out,
     }
 }
 
+// ---- k_final_lut --------------------------------------------------------------------------------
+// The extraction of a LUT row (sgfhe_bootstrap_lut_batch, include/sgfhe_hip.h): the accumulator started at A0, so
+// P(acc, c) = A0 T(c + phase) with T the antiperiodic test polynomial, and the coefficient at
+// c(j) = 3 Dr - (2 j - 1) Dr/8 is the step "+A0 for s >= j, -A0 below" of the input sum s = phase / (Dr/4).  The truth
+// table is the +-1 combination of the steps at its transitions (sigma(j) != sigma(j - 1), j in 1..8, sigma(8) =
+// -sigma(0)): base = A0 [b word only] + sum_i kappa_i P(acc, c(j_i) - e), kappa_i = -sigma(0) (-1)^i, and the three
+// rows are 4, 2 and 1 times the base: the table's bit at the codewords Dr, Dr/2, Dr/4.
+// One thread per (row of the chunk, word e in [0, n]) computes the base once and writes the three rows; rows of the
+// chunk that are not LUT rows are left alone (k_final has written them).  The table decode is uniform over a row;
+// consecutive threads read consecutive (descending) coefficients.  c(j) - e is taken mod 2 m: c(j) >= m for j <= 4
+// (the negated half), and c(4) - m = Dr/8 < n, so the index does wrap below 0 into the other half, negating again.
+__global__ void __launch_bounds__(256)
+k_final_lut(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, const CrtConst *__restrict__ CC,
+            const uint32_t *__restrict__ lut, uint32_t nvalid, uint32_t n, uint32_t logm, uint32_t raw, uint32_t mode) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nvalid * (n + 1)) return;
+    const uint32_t M = 1u << logm;
+    const uint32_t b = t / (n + 1), e = t % (n + 1);
+    const uint32_t word = lut[b];
+    if (!(word & LUT_ROW)) return;
+    const u128 Q = CC->Q;
+    const bool wide = (mode & MODE_WIDE) != 0;
+    const size_t bc = (size_t)b * 2 + (e < n ? 0 : 1);
+    const uint32_t shift = e < n ? e : 0u;
+    // bit j of `ext` is sigma(j) for j in 0..8; bit j of `edge` marks a transition at j
+    const uint32_t ext = (word & 0xFFu) | ((~word & 1u) << 8);
+    const uint32_t edge = (ext ^ (ext << 1)) & 0x1FEu;
+    bool minus = (word & 1u) != 0;      // kappa_0 = -sigma(0)
+    u128 v = e < n ? (u128)0 : CC->DQL;
+    for (uint32_t j = 1; j <= 8; j++) {
+        if (!((edge >> j) & 1u)) continue;
+        const uint32_t c = 3 * (M / 2) - (2 * j - 1) * (M / 16);          // below 3 m / 2
+        uint32_t idx = (c + 2 * M - shift) & (2 * M - 1);
+        bool neg = minus;
+        if (idx >= M) { idx -= M; neg = !neg; }
+        u128 w = acc_from_digits(load_digits(dig, bc, idx, M, wide), CC, mode);
+        if (neg) w = w ? Q - w : 0;
+        v += w;
+        if (v >= Q) v -= Q;
+        minus = !minus;
+    }
+    const size_t stride = n + 1;
+    u128 v2 = v + v;
+    if (v2 >= Q) v2 -= Q;
+    u128 v4 = v2 + v2;
+    if (v4 >= Q) v4 -= Q;
+    if (raw) {
+        ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out) + (size_t)b * 3 * stride + e;
+        o[0] = make_ulonglong2((uint64_t)v4, (uint64_t)(v4 >> 64));
+        o[stride] = make_ulonglong2((uint64_t)v2, (uint64_t)(v2 >> 64));
+        o[2 * stride] = make_ulonglong2((uint64_t)v, (uint64_t)(v >> 64));
+    } else {
+        uint64_t *o = out + (size_t)b * 3 * stride + e;
+        o[0] = modred(v4, CC);
+        o[stride] = modred(v2, CC);
+        o[2 * stride] = modred(v, CC);
+    }
+}
+
 // ---- gate circuits (sgfhe_circuit_run, csrc/circuit.h) ---------------------------------------------
 // Memory-bound copies of rows of n + 1 uint64 words (a[0..n) then b) between the wire table
 // ([slot][instances][n + 1]) and the staging of one bootstrap call, one thread per word: consecutive
@@ -1670,12 +1740,14 @@ k_final(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out,
 // NOT w = enc_trivial(true) - w (fhe.jl:221-223,669-670), a -> -a mod r, b -> (Dr - b) mod r.
 constexpr uint32_t CIRC_REF_FALSE = 0x7FFFFFFFu, CIRC_REF_NOT = 0x80000000u, CIRC_SLOT_NONE = 0xFFFFFFFFu;
 
+// `one`: the codeword of the wire, b of its trivial TRUE -- Dr = r / 4 everywhere but at positions 0 and 1 of a LUT node,
+// which read wires at Dr/4 and Dr/2.
 __device__ __forceinline__ uint64_t circ_word(const uint64_t *__restrict__ wires, uint32_t ref, size_t inst_row,
-                                              uint32_t e, uint32_t n, uint64_t r) {
+                                              uint32_t e, uint32_t n, uint64_t r, uint64_t one) {
     // inst_row = slot * instances + instance (not read for the constant)
     const uint64_t v = (ref & ~CIRC_REF_NOT) == CIRC_REF_FALSE ? 0ull : wires[inst_row * (n + 1) + e];
     if (!(ref & CIRC_REF_NOT)) return v;
-    return ((e < n ? 0ull : r / 4) + r - v) & (r - 1);
+    return ((e < n ? 0ull : one) + r - v) & (r - 1);
 }
 
 // A lane-shifted reference (sgfhe_circuit_create_lanes): instances form consecutive groups of `group`, and the
@@ -1685,11 +1757,11 @@ __device__ __forceinline__ uint64_t circ_word(const uint64_t *__restrict__ wires
 // instances is a multiple of group (checked before a run is queued): row inst + d is inside the slot.
 __device__ __forceinline__ uint64_t circ_word_lane(const uint64_t *__restrict__ wires, uint32_t ref, int32_t d,
                                                    uint32_t group, uint32_t instances, uint32_t inst, uint32_t e,
-                                                   uint32_t n, uint64_t r) {
+                                                   uint32_t n, uint64_t r, uint64_t one) {
     const int64_t lane = (int64_t)(inst % group) + d;
     if (lane < 0 || lane >= (int64_t)group) ref = CIRC_REF_FALSE | (ref & CIRC_REF_NOT);
     const size_t src = (size_t)((int64_t)inst + d);   // (not read for the constant)
-    return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + src, e, n, r);
+    return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + src, e, n, r, one);
 }
 
 // The node table of a plan on the device (CircuitPlan::node_kind ..): one CSR over the live nodes and the pack stage's
@@ -1708,24 +1780,32 @@ struct CircNodes {
 // along a (shifted) source row.  The sum runs in wrapping uint64 arithmetic with a signed multiply (w in {-2, -1, 1, 2})
 // and is reduced with one mask: r is a power of two (at most 2^15), so 2^64 is a multiple of it, and 64 terms of weight
 // 2 stay far below 2^64 anyway.  A plan without lane groups has group 1 and no shift but 0.
+// A LUT node (kind 2, its table in bits 8..15 of the kind word; sgfhe_circuit_create_lut) writes a1 = U = X0 + X1 + X2
+// and a2 = 0 as a sum node of unit weights does, but position i reads a wire at the codeword Dr >> (2 - i), so NOT at
+// position i is b -> (Dr >> (2 - i)) - b.  `lutw` (NULL for a call without LUT nodes): the call's LUT descriptor, one
+// word per row, LUT_ROW | table for the rows of a LUT node and 0 for the others (bootstrap_device's LutDesc).
 __global__ void __launch_bounds__(256)
 k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node0, uint64_t *__restrict__ a1,
               uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
-              uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+              uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group,
+              uint32_t *__restrict__ lutw = nullptr) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
     const uint32_t k = node0 + R / instances, inst = R % instances;
-    auto read = [&](uint32_t i) -> uint64_t {
-        return circ_word_lane(wires, nodes.ref[i], nodes.shift[i], group, instances, inst, e, n, r);
+    auto read = [&](uint32_t i, uint64_t one) -> uint64_t {
+        return circ_word_lane(wires, nodes.ref[i], nodes.shift[i], group, instances, inst, e, n, r, one);
     };
     const uint32_t t0 = nodes.start[k], t1 = nodes.start[k + 1];
+    const uint32_t kw = nodes.kind[k], kd = kw & 0xFFu;
     uint64_t u = 0, v = 0;
-    if (nodes.kind[k] == 0) {
-        u = read(t0);
-        v = read(t0 + 1);
+    if (kd == 0) {
+        u = read(t0, r / 4);
+        v = read(t0 + 1, r / 4);
+    } else if (kd == 2) {
+        u = (read(t0, r / 16) + read(t0 + 1, r / 8) + read(t0 + 2, r / 4)) & (r - 1);
     } else {
-        for (uint32_t i = t0; i < t1; i++) u += (uint64_t)((int64_t)nodes.weight[i] * (int64_t)read(i));
+        for (uint32_t i = t0; i < t1; i++) u += (uint64_t)((int64_t)nodes.weight[i] * (int64_t)read(i, r / 4));
         u &= r - 1;
     }
     if (e < n) {
@@ -1734,6 +1814,7 @@ k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node
     } else {
         b1[lr] = u;
         b2[lr] = v;
+        if (lutw) lutw[lr] = kd == 2 ? LUT_ROW | ((kw >> 8) & 0xFFu) : 0u;
     }
 }
 
@@ -1749,7 +1830,7 @@ k_circ_xor3(uint64_t *__restrict__ res, const uint32_t *__restrict__ node_kind, 
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1);
-    if (node_kind[(row0 + lr) / instances] == 0) return;
+    if ((node_kind[(row0 + lr) / instances] & 0xFFu) != 1) return;   // a sum node's rows only
     const uint64_t s = e < n ? a1[(size_t)lr * n + e] + a2[(size_t)lr * n + e] : b1[lr] + b2[lr];
     uint64_t *o = res + (size_t)lr * 3 * (n + 1) + e;
     o[2 * (size_t)(n + 1)] = (s - 2 * o[0]) & (r - 1);
@@ -1766,7 +1847,7 @@ k_circ_xor3_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__
                 const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint64_t r) {
     const uint32_t lr = blockIdx.x, R = row0 + lr;
     const uint32_t rank = R / instances, inst = R % instances;   // (uniform over the workgroup)
-    if (node_kind[rank] == 0) return;
+    if ((node_kind[rank] & 0xFFu) != 1) return;   // a sum node's rows only
     const uint32_t slot = out_slot[3 * rank + 2];
     if (slot == CIRC_SLOT_NONE) return;
     const size_t stride = n + 1;
@@ -1874,7 +1955,7 @@ k_circ_lift(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
     const uint32_t o = R / instances, inst = R % instances;
-    const uint64_t v = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r);
+    const uint64_t v = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r, r / 4);
     rawout[(size_t)R * (n + 1) + e] = lift_word(v, CC);
 }
 
@@ -1896,7 +1977,7 @@ k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ 
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t o = t / per_out, w = t % per_out;
         const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
-        out[t] = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r);
+        out[t] = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r, r / 4);
     }
 }
 
@@ -1963,6 +2044,8 @@ constexpr uint32_t NOISE_WAVES = 4, NOISE_ROWS = 16, NOISE_MASK_WORDS = 64;   //
 struct NoiseGeom {
     size_t row_stride, gate_stride;   // in words of the row type
     uint32_t wire0, node0, row0, rows, instances, inst0, tiles, bit_words, n;
+    const uint32_t *kind;             // the node kinds of the launch, by node_in_launch (device; NULL: no LUT node) --
+                                      // gate g of a LUT node is measured against its own codeword Dr >> g
 };
 
 __device__ __forceinline__ void noise_load_mask(uint64_t *smask, const uint64_t *__restrict__ keymask, uint32_t n) {
@@ -1995,6 +2078,9 @@ k_lwe_noise(const uint64_t *__restrict__ lwe, const uint64_t *__restrict__ keyma
     const uint32_t node = blockIdx.x / G.tiles, tile = blockIdx.x % G.tiles;
     const uint32_t wire = G.wire0 + node * gridDim.y + blockIdx.y;
     const uint64_t rmask = (1ull << logr) - 1, Dr = 1ull << (logr - 2);
+    // the wire's codeword C = Dr >> scale (uniform over the workgroup): scale 0 but for wires +1, +2 of a LUT node
+    const uint32_t scale = G.kind && (G.kind[node] & 0xFFu) == 2 ? blockIdx.y : 0u;
+    const uint64_t C = Dr >> scale;
     const uint64_t *wbits = bits + (size_t)wire * G.bit_words;
     uint64_t cnt = 0, wrong = 0, emax = 0, esum = 0, esq = 0, margin = 0;
     for (uint32_t t = wave; t < NOISE_ROWS; t += NOISE_WAVES) {
@@ -2011,15 +2097,15 @@ k_lwe_noise(const uint64_t *__restrict__ lwe, const uint64_t *__restrict__ keyma
         s = wave_sum64(s);
         const uint64_t bit = (wbits[i >> 6] >> (i & 63)) & 1;
         const uint64_t phase = (row[G.n] - s) & rmask;
-        const uint64_t d = (phase - bit * Dr) & rmask;
+        const uint64_t d = (phase - bit * C) & rmask;
         const int64_t e = d > (rmask >> 1) + 1 ? (int64_t)d - (int64_t)(rmask + 1) : (int64_t)d;
         const uint64_t ae = e < 0 ? (uint64_t)(-e) : (uint64_t)e;
         cnt++;
-        wrong += (((phase + Dr / 2) & rmask) >> (logr - 2)) != bit;
+        wrong += scale ? ae >= C / 2 : (((phase + Dr / 2) & rmask) >> (logr - 2)) != bit;
         emax = ae > emax ? ae : emax;
         esum += (uint64_t)e;
         esq += ae * ae;
-        margin += ae >= Dr / 4;
+        margin += ae >= C / 4;
     }
     if (lane == 0) {
         part[wave][0] = cnt, part[wave][1] = wrong, part[wave][2] = emax;

@@ -233,6 +233,27 @@ class Engine:
                 (FLAG_RAW_MODQ if raw else 0) | (FLAG_RAW_RNS2 if rns2 else 0))
         return out
 
+    def bootstrap_lut_batch(self, a, b, tables, raw=False):
+        """LUT bootstraps (sgfhe_bootstrap_lut_batch): any function of three bits in one bootstrap.  a [batch][n],
+        b [batch]: rows over Z_r whose phase is s Dr/4 + e, s = x0 + 2 x1 + 4 x2 the sum of three inputs at the
+        codewords Dr/4, Dr/2, Dr and |e| < Dr/8 (bootstrapped inputs only: see the noise rule in
+        include/sgfhe_hip.h); tables [batch]: bit s of a row's table is its function value at s.
+        Returns [batch][3][n+1] uint64 -- row 0 the result at codeword Dr (an ordinary wire), row 1 at Dr/2, row 2 at
+        Dr/4 -- or [batch][3][n+1][2] residues mod Q with raw=True."""
+        n = self.params.n
+        a, pa = _c(a)
+        b, pb = _c(b)
+        t, pt = _c(tables, np.uint8)
+        a = a.reshape(-1, n)
+        batch = a.shape[0]
+        if b.size != batch or t.size != batch:
+            raise ValueError("bootstrap_lut_batch: a is [batch][n], b and tables are [batch]")
+        out = np.zeros((batch, 3, n + 1, 2) if raw else (batch, 3, n + 1), dtype=np.uint64)
+        if batch:
+            self._call("sgfhe_bootstrap_lut_batch", pa, pb, pt, batch, out.ctypes.data_as(ctypes.c_void_p),
+                       FLAG_RAW_MODQ if raw else 0)
+        return out
+
     def bootstrap_batch_device(self, a1_ptr, b1_ptr, a2_ptr, b2_ptr, batch, out_ptr, raw=False,
                                stream=None):
         """Asynchronous, all buffers device-resident (raw pointers)."""

@@ -1909,7 +1909,9 @@ k_circ_scatter_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restric
     const uint32_t neg = job[2] & CIRC_REF_NOT, g = job[2] & 3u;
     const ulonglong2 *src = res + ((size_t)lr * 3 + g) * stride;
     ulonglong2 *dst = rawout + ((size_t)job[0] * instances + inst) * stride;
-    const u128 Q = CC->Q, one = 2 * CC->DQ;
+    const u128 Q = CC->Q;
+    u128 one = 2 * CC->DQ;   // reduced as k_lwe_noise_q reduces it: the ctx accepts any DQ_tilde < Q
+    if (one >= Q) one -= Q;
     for (uint32_t e = threadIdx.x; e <= n; e += 256) {
         ulonglong2 v = src[e];
         if (neg) {

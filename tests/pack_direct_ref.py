@@ -42,11 +42,27 @@ def tail_bigint(bp, bk, lwe_q, seed=None, ct=0, call=0):
             np.array(BO.reduce_modulus_poly(bp.r, v1, Q), dtype=np.uint64))
 
 
+def extreme_residue(p, sign):
+    """The residue whose deterministic flatten digits are both as large (sign > 0) or both as small (sign < 0) as a
+    residue of Z_Q allows: x' = value + off at the top / bottom of [0, Q) (tests/test_gpu_worstcase.py drives the k-loop's
+    CRT with it, tests/test_gpu_pack_bound.py the pack stage's)."""
+    s = p.B // 2 - 1 if p.B % 2 == 0 else (p.B - 1) // 2
+    off = (1 + p.B) * s % p.Q
+    if sign > 0:
+        hi_max = (p.Q - 1) // p.B
+        xp = (hi_max - 1) * p.B + (p.B - 1)           # digits (B - 1 - s, hi_max - 1 - s)
+    else:
+        xp = 0                                         # digits (-s, -s)
+    return (xp - off) % p.Q
+
+
 class FastTail:
     """tail_bigint in exact integer arithmetic, an order of magnitude faster (tests/test_pack_direct_host.py checks the
     two against each other): the digits of flatten / flatten_random (src/utils.jl:155-241) as SIGNED integers on whole
     polynomials at once, and all 2 n products of a column summed as one Kronecker integer before it is unpacked and
-    reduced mod (x^m + 1, Q).  The key rows are packed once."""
+    reduced mod (x^m + 1, Q).  The key rows are packed once, lifted to (-Q/2, Q/2] as k_key_transform lifts them, so the
+    integers summed here are the ones the pack stage's CRT has to recover.  `exact=G` also returns them: the sums of every
+    group of G slices, [n / G][2][m] Python integers, before the reduction mod Q (tests/test_gpu_pack_bound.py)."""
 
     def __init__(self, bp, bk):
         self.bp = bp
@@ -55,10 +71,22 @@ class FastTail:
         self.slot = (Q.bit_length() + (2 * B).bit_length() + (2 * n * m).bit_length() + 2 + 7) // 8
         self.half = 1 << (8 * self.slot - 1)
         self.off = sum(self.half << (8 * self.slot * k) for k in range(2 * m))
-        self.K = [[[self._pack(bk[i][bp.ell + d][c]) for c in range(2)] for d in range(2)] for i in range(n)]
+        centred = lambda row: [x - Q if x > Q // 2 else x for x in row]
+        self.K = [[[self._pack_signed(centred(bk[i][bp.ell + d][c])) for c in range(2)] for d in range(2)]
+                  for i in range(n)]
 
     def _pack(self, coeffs):
         return int.from_bytes(b"".join(int(x).to_bytes(self.slot, "little") for x in coeffs), "little")
+
+    def _pack_signed(self, coeffs):
+        return self._pack([v if v > 0 else 0 for v in coeffs]) - self._pack([-v if v < 0 else 0 for v in coeffs])
+
+    def _unpack(self, acc):
+        """A Kronecker product of two packed polynomials -> its m signed coefficients mod x^m + 1."""
+        m = self.bp.m
+        raw = (acc + self.off).to_bytes(2 * m * self.slot + 1, "little")
+        co = [int.from_bytes(raw[k * self.slot:(k + 1) * self.slot], "little") - self.half for k in range(2 * m)]
+        return [co[k] - co[k + m] for k in range(m)]
 
     def _digits(self, a, x):
         """a: object array of residues; x: None, or the draws (x0, x1) as object arrays -> signed digits (d0, d1)."""
@@ -70,13 +98,15 @@ class FastTail:
         d0, d1 = a % B - s, a // B - s                             # utils.jl:170-185
         return (d0, d1) if x is None else (d0 + x[0], d1 + x[1])   # utils.jl:237-239
 
-    def __call__(self, lwe_q, seed=None, ct=0, call=0):
+    def __call__(self, lwe_q, seed=None, ct=0, call=0, exact=None):
         bp = self.bp
         n, m, Q = bp.n, bp.m, bp.Q
+        G = n if exact is None else exact
+        assert n % G == 0
         vals = np.asarray(lwe_q, dtype=np.uint64).reshape(n, n + 1, 2)
         ints = np.array([[int(lo) | (int(hi) << 64) for lo, hi in row] for row in vals], dtype=object)   # [bit][n + 1]
         rng = None if seed is None else BO.ChaChaFlatten(bp, seed, ct, call)
-        acc = [0, 0]
+        acc = [[0, 0] for _ in range(n // G)]
         zero = np.array([0] * (m - n), dtype=object)
         for i in range(n):
             a = np.concatenate([ints[:, i], zero])                 # as_i, resized (fhe.jl:675-677)
@@ -85,19 +115,17 @@ class FastTail:
                 f = rng.draws(0, (1 << 31) | i)
                 x = tuple(np.array([f(j, d) for j in range(m)], dtype=object) for d in range(2))
             for d, dig in enumerate(self._digits(a, x)):
-                P = self._pack([v if v > 0 else 0 for v in dig]) - self._pack([-v if v < 0 else 0 for v in dig])
-                acc[0] += P * self.K[i][d][0]
-                acc[1] += P * self.K[i][d][1]
-        cols = []
-        for c in range(2):
-            raw = (acc[c] + self.off).to_bytes(2 * m * self.slot + 1, "little")
-            co = [int.from_bytes(raw[k * self.slot:(k + 1) * self.slot], "little") - self.half for k in range(2 * m)]
-            cols.append([(co[k] - co[k + m]) % Q for k in range(m)])
+                P = self._pack_signed(dig)
+                acc[i // G][0] += P * self.K[i][d][0]
+                acc[i // G][1] += P * self.K[i][d][1]
+        sums = [[self._unpack(a[c]) for c in range(2)] for a in acc]
+        cols = [[sum(s[c][k] for s in sums) % Q for k in range(m)] for c in range(2)]
         b = BO.resize([int(ints[j, n]) for j in range(n)], m)                           # fhe.jl:678
         w1 = [(Q - x) % Q for x in cols[0]]                                             # fhe.jl:689
         v1 = BO.poly_sub(b, cols[1], Q)                                                 # fhe.jl:690
-        return (np.array(BO.reduce_modulus_poly(bp.r, w1, Q), dtype=np.uint64),         # fhe.jl:692-693
-                np.array(BO.reduce_modulus_poly(bp.r, v1, Q), dtype=np.uint64))
+        out = (np.array(BO.reduce_modulus_poly(bp.r, w1, Q), dtype=np.uint64),          # fhe.jl:692-693
+               np.array(BO.reduce_modulus_poly(bp.r, v1, Q), dtype=np.uint64))
+        return out if exact is None else out + (sums,)
 
 
 def oracle_tail(bp, bk, key):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import bigint_oracle as BO
+from pack_direct_ref import extreme_residue as _extreme_acc
 
 pytestmark = pytest.mark.gpu
 
@@ -35,19 +36,6 @@ def _params(S, name):
     if name == "synth64":
         return bench.make_params(S, "synth64")
     return S.Params(int(name))
-
-
-def _extreme_acc(p, sign):
-    """Accumulator value whose deterministic flatten digits are as large (sign > 0) or as small
-    (sign < 0) as a residue of Z_Q allows: x' = acc + off at the top / bottom of [0, Q)."""
-    s = p.B // 2 - 1 if p.B % 2 == 0 else (p.B - 1) // 2
-    off = (1 + p.B) * s % p.Q
-    if sign > 0:
-        hi_max = (p.Q - 1) // p.B
-        xp = (hi_max - 1) * p.B + (p.B - 1)           # digits (B - 1 - s, hi_max - 1 - s)
-    else:
-        xp = 0                                         # digits (-s, -s)
-    return (xp - off) % p.Q
 
 
 @pytest.mark.parametrize("name", ["1024", "rns2", "512", "64", "2048", "synth64"])

@@ -564,6 +564,28 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * table 0xF0 -- brings a scale-0 wire to all three scales in one bootstrap.  Every run entry point takes such a plan.
  * The probe's plaintext evaluation knows LUT nodes, and the record of a wire of scale k is taken against its own
  * codeword C = Dr >> k: e is centred against bit C, stats[1] counts |e| >= C/2 and stats[5] counts |e| >= C/4.
+ *
+ * LUT families (sgfhe_circuit_create_lut_multi): several truth tables on ONE bootstrap, the node form of
+ * sgfhe_bootstrap_lut_multi_batch (declared below).  The arrays are those of sgfhe_circuit_create_lut, and
+ * node_kind[g] = 3 marks a SIBLING: a further table, node_table[g] (below 256), on the bootstrap of its LEADER, the
+ * nearest earlier kind-2 node.  sgfhe_circuit_create_lut and sgfhe_circuit_create_w keep rejecting kind 3.  A sibling
+ * has no terms (node_start[g + 1] == node_start[g]), node g - 1 must be of kind 2 or 3, and a leader with its siblings
+ * has at most SGFHE_LUT_MAX_TABLES members; anything else is SGFHE_ERR_INVALID_ARG with *out NULL.  Wire numbering stays
+ * n_inputs + 3 g + w: a sibling's three wires have scales 0, 1, 2, and the scale rule and the output rule treat it as a
+ * LUT node (an output naming its wire +0 is refreshed, or lifted).
+ * A sibling is live when an output reaches one of its wires, and a leader is live when an output reaches it or any of
+ * its siblings is live; a dead sibling is not extracted.  A sibling has its leader's level and TAKES NO ROW: within a
+ * level the live nodes that are no siblings take the ranks in ascending index, row = rank * instances + instance, so
+ * rows, calls, call numbers and draws are those of the same arrays with every kind-3 node deleted.  At every instance
+ * the three wires of a live sibling are the bytes the leader's three wires would have with node_table[leader] replaced
+ * by the sibling's table -- the terms, lane shifts and NOTs are the leader's -- in an un-reduced level call
+ * (SGFHE_CIRCUIT_PACK_DIRECT) too, where they reach the wire table as the ModRed words of the reduced call.
+ * sgfhe_circuit_info: info[1] and info[2] count BOOTSTRAPS -- the live nodes that take a row --, info[3] counts slots,
+ * those of sibling wires included; a plan without siblings reports what it always did.  Every run entry point takes
+ * such a plan.  The probe's plaintext evaluation knows siblings; `stats` stays indexed by wire id.  A live sibling's
+ * wire is measured, against its own codeword, WHEN IT HAS A SLOT -- when a node or an output reads it -- from the
+ * slot's rows of that call.  A sibling wire that nothing reads is never written anywhere and gets an all-zero record,
+ * as the wires of dead siblings do: the one place where "every wire of every live node" does not extend.
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -597,6 +619,15 @@ int32_t sgfhe_circuit_create_lut(uint32_t n_inputs,
                                  size_t n_gates, const uint32_t *outputs,
                                  const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
                                  uint32_t group, sgfhe_circuit **out);
+int32_t sgfhe_circuit_create_lut_multi(uint32_t n_inputs,
+                                       const uint32_t *node_kind /* [n_gates]: 0, 1, 2 as above, 3 = LUT sibling */,
+                                       const uint32_t *node_start /* [n_gates + 1], CSR into the term arrays, [0] = 0 */,
+                                       const uint32_t *term_ref, const int32_t *term_shift /* NULL = all 0 */,
+                                       const int32_t *term_weight,
+                                       const uint32_t *node_table /* [n_gates]: read for kinds 2 and 3, below 256 */,
+                                       size_t n_gates, const uint32_t *outputs,
+                                       const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
+                                       uint32_t group, sgfhe_circuit **out);
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
@@ -758,6 +789,39 @@ int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *ctx, const uint64_t *lwe, size_t count, u
 int32_t sgfhe_bootstrap_lut_batch(sgfhe_ctx *ctx, const uint64_t *a /* [batch][n] */, const uint64_t *b /* [batch] */,
                                   const uint8_t *table /* [batch] */, size_t batch,
                                   uint64_t *out /* [batch][3][n + 1], x2 words with SGFHE_FLAG_RAW_MODQ */, uint32_t flags);
+
+/*
+ * LUT families: several truth tables on one bootstrap's accumulator.
+ *
+ * The k-loop of a LUT bootstrap does not depend on the truth table: the table enters in step 3 of the contract above
+ * alone, where it picks which of the eight coefficients P(acc, c(j) - e), j = 1..8, are combined with +-1.  Every
+ * further function of the same three inputs therefore costs one more combination of eight values that are already
+ * there, and its three output rows.
+ *
+ *   a [batch][n], b [batch]          as in sgfhe_bootstrap_lut_batch
+ *   tables [batch][n_tables]         row t is evaluated under each of tables[t][0 .. n_tables)
+ *   out [batch][n_tables][3][n + 1]  (with SGFHE_FLAG_RAW_MODQ: [batch][n_tables][3][n + 1][2], residues mod Q)
+ *
+ * The contract: out[t][j] is byte for byte out[t] of sgfhe_bootstrap_lut_batch called with table[t] = tables[t][j] at
+ * the SAME call number of the same draw stream -- in both flatten modes, reduced and un-reduced, in every chunk, lane
+ * and small-batch form.  The call takes ONE call number, and row t draws as bootstrap t of that call; n_tables = 1 is
+ * sgfhe_bootstrap_lut_batch.  Each coefficient is reconstructed from the accumulator at most once per output word,
+ * whatever the number of tables.
+ *
+ * Host pointers, synchronous, on the ctx stream; the ctx is locked for the call, and the call is never gathered with
+ * other callers'.  Before anything is queued or written, SGFHE_ERR_INVALID_ARG: n_tables outside
+ * 1..SGFHE_LUT_MAX_TABLES, flags other than 0 or SGFHE_FLAG_RAW_MODQ, a NULL pointer, a word that is not below r, and
+ * batch * n_tables * (n + 1) above 2^31 (the device indexes rows and tables with 32 bits).  batch = 0 does nothing.
+ * SGFHE_ERR_NO_KEY and SGFHE_ERR_OOM as elsewhere; nothing is written to `out` then.
+ *
+ * The noise rule is that of sgfhe_bootstrap_lut_batch, table by table.  The outputs of one row share an accumulator,
+ * so their errors are correlated; each of them obeys the rule on its own, which is all that correctness needs.
+ */
+#define SGFHE_LUT_MAX_TABLES 256u
+int32_t sgfhe_bootstrap_lut_multi_batch(sgfhe_ctx *ctx, const uint64_t *a /* [batch][n] */, const uint64_t *b /* [batch] */,
+                                        const uint8_t *tables /* [batch][n_tables] */, size_t n_tables, size_t batch,
+                                        uint64_t *out /* [batch][n_tables][3][n + 1], x2 words with SGFHE_FLAG_RAW_MODQ */,
+                                        uint32_t flags);
 
 /*
  * Noise probe: the LWE error of rows against the SECRET key, reduced on the device to exact integer statistics.

@@ -155,6 +155,8 @@ def lib():
         "sgfhe_lwe_lift_modq": (i32, [vp, vp, sz, vp]),
         "sgfhe_bootstrap_lut_batch": (i32, [vp, vp, vp, vp, sz, vp, u32]),
         "sgfhe_circuit_create_lut": (i32, [u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, ctypes.POINTER(vp)]),
+        "sgfhe_bootstrap_lut_multi_batch": (i32, [vp, vp, vp, vp, sz, sz, vp, u32]),
+        "sgfhe_circuit_create_lut_multi": (i32, [u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, ctypes.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -181,4 +183,5 @@ EXPORTED_SYMBOLS = (
     "sgfhe_circuit_destroy", "sgfhe_circuit_run", "sgfhe_circuit_run_ct", "sgfhe_circuit_run_ct_ex",
     "sgfhe_pack_lwe_modq", "sgfhe_lwe_noise", "sgfhe_circuit_run_probe",
     "sgfhe_circuit_create_lanes", "sgfhe_circuit_group", "sgfhe_circuit_create3", "sgfhe_lwe_lift_modq",
-    "sgfhe_circuit_create_w", "sgfhe_bootstrap_lut_batch", "sgfhe_circuit_create_lut")
+    "sgfhe_circuit_create_w", "sgfhe_bootstrap_lut_batch", "sgfhe_circuit_create_lut",
+    "sgfhe_bootstrap_lut_multi_batch", "sgfhe_circuit_create_lut_multi")

@@ -36,6 +36,12 @@ at all three scales, (f, f_half, f_quarter), so any LUT output can feed any posi
 else -- inputs, the wires of the other nodes, outputs -- is scale 0; `fan(x)` brings a scale-0 wire to all three scales
 in one bootstrap.  The inputs of a LUT node must be bootstrapped wires (refresh, then fan): the sum of their errors has
 to stay below Dr/8 (the noise rule in include/sgfhe_hip.h).
+
+LUT families (sgfhe_circuit_create_lut_multi).  `lut_multi(tables, x0, x1, x2)` evaluates up to 256 functions of the
+same three wires on ONE bootstrap: the k-loop does not depend on the table, so every further table costs one more
+extraction of the same accumulator and no row.  The first table is the family's leader, a LUT node; each other is a
+SIBLING, a node with no inputs of its own whose three wires are numbered like any node's.  `shannon(c, tables, xs)`
+builds any functions of k >= 3 wires this way: all cofactors on (x0, x1, x2) are one family, a mux tree follows.
 """
 
 import ctypes
@@ -49,6 +55,7 @@ FALSE_ID = 0x7FFFFFFF      # SGFHE_CIRCUIT_FALSE
 NONE_ID = 0x7FFFFFFE       # SGFHE_CIRCUIT_NONE: the third reference of a two-input node
 NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
 MAX_TERMS = 64             # SGFHE_CIRCUIT_MAX_TERMS
+LUT_MAX_TABLES = 256       # SGFHE_LUT_MAX_TABLES
 CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
 
 
@@ -93,7 +100,8 @@ class Circuit:
     output().  `group`: the lane group size (instances form consecutive groups of `group` lanes; a reference may be
     shifted by |d| < group lanes, Wire.lane).  The C plan (sgfhe_circuit_create, sgfhe_circuit_create_lanes when
     the group is above 1, sgfhe_circuit_create3 when a gate3 exists, sgfhe_circuit_create_w when a sum node exists that
-    is no three-input node) is made on first use and freed with the object."""
+    is no three-input node, sgfhe_circuit_create_lut when a LUT node exists, sgfhe_circuit_create_lut_multi when a LUT
+    sibling exists) is made on first use and freed with the object."""
 
     FALSE = Wire(FALSE_ID)
     TRUE = Wire(FALSE_ID | NOT_BIT)
@@ -110,7 +118,8 @@ class Circuit:
         self.outputs = []          # [ref]
         self.gate_shifts = []      # [(x lane shift, y lane shift)] or (x, y, z lane shift), beside gates
         self.gate_weights = {}     # node -> (weight, ...) beside its references: the sum nodes (sum_node)
-        self.gate_tables = {}      # node -> truth table: the LUT nodes (lut)
+        self.gate_tables = {}      # node -> truth table: the LUT nodes (lut) and their siblings (lut_multi)
+        self.gate_leader = {}      # sibling -> its leader, a LUT node: no inputs of its own, () in gates and gate_shifts
         self.output_shifts = []    # [lane shift], beside outputs
         self._plan = None
         self._L = None
@@ -183,6 +192,40 @@ class Circuit:
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
 
+    def lut_multi(self, tables, x0, x1, x2):
+        """A LUT family: 1 to 256 functions of the same three wires on ONE bootstrap.  tables[0] is the table of the
+        LUT node lut(tables[0], x0, x1, x2), the family's leader; every further table is a sibling -- a node that takes
+        no row of its level, whose wires are extracted from the leader's accumulator.  Returns one (f, f_half,
+        f_quarter) triple per table, the leader's first."""
+        tables = [int(t) for t in tables]
+        if not 1 <= len(tables) <= LUT_MAX_TABLES:
+            raise ValueError("a LUT family has 1 to %d tables" % LUT_MAX_TABLES)
+        if any(not 0 <= t < 256 for t in tables):
+            raise ValueError("a LUT node's table has 8 entries: 0 .. 255")
+        out = [self.lut(tables[0], x0, x1, x2)]
+        leader = len(self.gates) - 1
+        for t in tables[1:]:
+            self.gates.append(())
+            self.gate_shifts.append(())
+            self.gate_tables[len(self.gates) - 1] = t
+            self.gate_leader[len(self.gates) - 1] = leader
+            base = self.n_inputs + 3 * (len(self.gates) - 1)
+            out.append((Wire(base), Wire(base + 1), Wire(base + 2)))
+        self._invalidate()
+        return out
+
+    def siblings(self, g):
+        """The siblings of LUT node g, in ascending index."""
+        out, h = [], g + 1
+        while self.gate_leader.get(h) == g:
+            out.append(h)
+            h += 1
+        return out
+
+    @property
+    def has_sibling(self):
+        return bool(self.gate_leader)
+
     def fan(self, x):
         """A scale-0 wire at all three scales in one bootstrap: lut(0xF0, FALSE, FALSE, x)."""
         return self.lut(0xF0, Circuit.FALSE, Circuit.FALSE, x)
@@ -204,7 +247,10 @@ class Circuit:
         return self.sum_node([(1, w)])[1]
 
     def kind(self, g):
-        """Node g: "classic" (gate), "gate3", "sum" (sum_node) or "lut"."""
+        """Node g: "classic" (gate), "gate3", "sum" (sum_node), "lut" or "sibling" (a further table of a LUT node,
+        lut_multi)."""
+        if g in self.gate_leader:
+            return "sibling"
         if g in self.gate_tables:
             return "lut"
         return "sum" if g in self.gate_weights else ("gate3" if len(self.gates[g]) == 3 else "classic")
@@ -259,8 +305,9 @@ class Circuit:
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
             os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
             h = ctypes.c_void_p()
-            if self.has_wsum or self.has_lut:   # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes
-                kind = np.array([{"classic": 0, "lut": 2}.get(self.kind(g), 1) for g in range(len(self.gates))],
+            if self.has_wsum or self.has_lut:   # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes,
+                                                # 3 for their siblings
+                kind = np.array([{"classic": 0, "lut": 2, "sibling": 3}.get(self.kind(g), 1) for g in range(len(self.gates))],
                                 dtype=np.uint32)
                 start = np.cumsum([0] + [len(x) for x in self.gates]).astype(np.uint32)
                 tr = np.array([ref for x in self.gates for ref in x], dtype=np.uint32)
@@ -268,9 +315,10 @@ class Circuit:
                 tw = np.array([w for g in range(len(self.gates)) for w in self.weights(g)], dtype=np.int32)
                 if self.has_lut:
                     tb = np.array([self.gate_tables.get(g, 0) for g in range(len(self.gates))], dtype=np.uint32)
-                    rc = L.sgfhe_circuit_create_lut(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), vp(tb),
-                                                    len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
-                                                    ctypes.byref(h))
+                    # (the new entry only when a sibling exists: every other circuit takes the entry it always took)
+                    create = L.sgfhe_circuit_create_lut_multi if self.has_sibling else L.sgfhe_circuit_create_lut
+                    rc = create(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), vp(tb), len(self.gates), vp(o),
+                                vp(os_), len(self.outputs), self.group, ctypes.byref(h))
                 else:
                     rc = L.sgfhe_circuit_create_w(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), len(self.gates),
                                                   vp(o), vp(os_), len(self.outputs), self.group, ctypes.byref(h))
@@ -301,7 +349,8 @@ class Circuit:
         return self._plan
 
     def info(self):
-        """dict(levels, nodes (evaluated per instance), widest (nodes in the widest level), slots)."""
+        """dict(levels, nodes (bootstraps per instance: the live nodes that take a row, so no LUT sibling), widest (such
+        nodes in the widest level), slots (those of sibling wires included))."""
         info = (ctypes.c_uint64 * 4)()
         h = self.handle()
         rc = self._L.sgfhe_circuit_info(h, info)
@@ -315,9 +364,9 @@ class Circuit:
             pass
 
     # ---- host statements of the model -------------------------------------------------------------
-    def schedule(self):
-        """The levels the planner runs: a list (level 1, 2, ...) of lists of node indices in ascending
-        order, after pruning the nodes no output depends on (the C planner's rule, in Python)."""
+    def node_levels(self):
+        """The level of every node, 0 for a pruned one (the C planner's rule, in Python): a node is live when an output
+        reaches it, a leader also when one of its siblings is live; a sibling has its leader's level."""
         def node(ref):   # producing node of a wire, -1 for inputs and the constant
             i = ref & ~NOT_BIT & 0xFFFFFFFF
             return -1 if i == FALSE_ID or i < self.n_inputs else (i - self.n_inputs) // 3
@@ -328,16 +377,32 @@ class Circuit:
                 live[node(ref)] = True
         for g in range(len(self.gates) - 1, -1, -1):
             if live[g]:
+                if g in self.gate_leader:
+                    live[self.gate_leader[g]] = True
                 for ref in self.gates[g]:
                     if node(ref) >= 0:
                         live[node(ref)] = True
         level = [0] * len(self.gates)
         for g, refs in enumerate(self.gates):
-            if live[g]:
+            if live[g] and g in self.gate_leader:
+                level[g] = level[self.gate_leader[g]]
+            elif live[g]:
                 level[g] = 1 + max(level[node(ref)] if node(ref) >= 0 else 0 for ref in refs)
+        return level
+
+    def live_siblings(self, g):
+        """The siblings of node g that an output reaches, in ascending index."""
+        level = self.node_levels()
+        return [h for h in self.siblings(g) if level[h]]
+
+    def schedule(self):
+        """The levels the planner runs: a list (level 1, 2, ...) of lists of node indices in ascending
+        order, after pruning the nodes no output depends on -- the nodes that take a row: a LUT sibling rides on its
+        leader's row and is not listed (live_siblings)."""
+        level = self.node_levels()
         levels = [[] for _ in range(max(level, default=0))]
         for g in range(len(self.gates)):
-            if level[g]:
+            if level[g] and g not in self.gate_leader:
                 levels[level[g] - 1].append(g)
         return levels
 
@@ -358,8 +423,10 @@ class Circuit:
                 base = self.n_inputs + 3 * g
                 if g in self.gate_tables:
                     x = [val(ref, d).astype(np.int64) for ref, d in zip(self.gates[g], self.gate_shifts[g])]
-                    f = ((self.gate_tables[g] >> (x[0] + 2 * x[1] + 4 * x[2])) & 1).astype(bool)
-                    wires[base], wires[base + 1], wires[base + 2] = f, f, f
+                    for h in [g] + self.siblings(g):   # (a sibling: its own table at the leader's inputs)
+                        f = ((self.gate_tables[h] >> (x[0] + 2 * x[1] + 4 * x[2])) & 1).astype(bool)
+                        hb = self.n_inputs + 3 * h
+                        wires[hb], wires[hb + 1], wires[hb + 2] = f, f, f
                     continue
                 if g in self.gate_weights:
                     s = sum(w * val(ref, d).astype(np.int64)
@@ -473,6 +540,65 @@ def crc16_ccitt(message_bits, refresh_inputs=True):
     return gf2_matvec(crc16_matrix(message_bits), refresh_inputs=refresh_inputs)
 
 
+def shannon(circuit, tables, xs, refresh=False, family=True):
+    """Any functions of k >= 3 wires by Shannon expansion.  tables: one integer per function, bit s of which is its value
+    at s = x_0 + 2 x_1 + ... + 2^(k-1) x_(k-1); xs: the k wires, bootstrapped ones (refresh=True refreshes each first,
+    as fresh encryptions need: the noise rule in include/sgfhe_hip.h).  The 2^(k-3) cofactors of every function on
+    (x_0, x_1, x_2) are 8-entry tables: all of them, equal ones merged and the constants left out, form ONE family
+    (Circuit.lut_multi) -- one bootstrap, whatever their number, as there are only 256 tables.  A mux tree of LUT nodes
+    follows, lut(0xCA, lo[2], hi[1], x_j) for j = 3 .. k - 1, equal nodes merged and a mux of two equal halves left out.
+    The wires are brought to the scale they are read at only where needed: x_0 and x_1 through one LUT node each (fan,
+    for a scale-0 wire), x_2 and the selectors only if they are not of scale 0.  family=False builds one LUT node per
+    cofactor table instead, for comparison.  Returns one scale-0 wire per function (a constant function: the constant)."""
+    xs = list(xs)
+    k = len(xs)
+    if k < 3:
+        raise ValueError("shannon: at least three wires")
+    tables = [int(t) for t in tables]
+    if any(not 0 <= t < 1 << (1 << k) for t in tables):
+        raise ValueError("shannon: a function of %d wires has a table of %d bits" % (k, 1 << k))
+    if refresh:
+        xs = [circuit.refresh(x) for x in xs]
+    IDENTITY = (0xAA, 0xCC, 0xF0)        # the table of "the input at position p"
+
+    def at_scale(w, want):               # w at scale `want`: as it is, or through one LUT node at its own position
+        have = circuit.scale(w)
+        if have in (None, want):
+            return w
+        p = 2 - have
+        args = [Circuit.FALSE] * 3
+        args[p] = w
+        return circuit.lut(IDENTITY[p], *args)[want]
+
+    const = {0x00: (Circuit.FALSE,) * 3, 0xFF: (Circuit.TRUE,) * 3}
+    cof = [[(t >> (8 * h)) & 0xFF for h in range(1 << (k - 3))] for t in tables]
+    distinct = sorted({c for row in cof for c in row if c not in const})
+    triple = dict(const)
+    if distinct:
+        x0, x1, x2 = at_scale(xs[0], 2), at_scale(xs[1], 1), at_scale(xs[2], 0)
+        if family:
+            triple.update(zip(distinct, circuit.lut_multi(distinct, x0, x1, x2)))
+        else:
+            triple.update((c, circuit.lut(c, x0, x1, x2)) for c in distinct)
+    layer = [[triple[c] for c in row] for row in cof]
+    for j in range(3, k):
+        sel, muxes = None, {}
+        nxt = []
+        for row in layer:
+            out = []
+            for lo, hi in zip(row[0::2], row[1::2]):
+                if lo == hi:
+                    out.append(lo)
+                    continue
+                if (lo, hi) not in muxes:
+                    sel = at_scale(xs[j], 0) if sel is None else sel
+                    muxes[(lo, hi)] = circuit.lut(0xCA, lo[2], hi[1], sel)
+                out.append(muxes[(lo, hi)])
+            nxt.append(out)
+        layer = nxt
+    return [row[0][0] for row in layer]
+
+
 def lwe_not(words, r, one=None):
     """NOT of LWEs [..., n + 1] over Z_r: enc_trivial(true) - w (a -> -a, b -> Dr - b, mod r).  one: the codeword of
     the wire in place of Dr (positions 0 and 1 of a LUT node read wires at Dr/4 and Dr/2)."""
@@ -493,8 +619,10 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
     are run by `boot_lut(call, a, b, tables, idx)` -- their rows, their tables and their indices within the call, so
     that a test can drive them from a second oracle -- which returns [rows][3][n + 1], the node's three wires; `boot`
     sees every row of a call that holds other rows too (its results for the LUT rows are dropped) and is not called
-    for a call of LUT rows only.  A checking and measuring aid: the engine's circuit path does this on the device
-    (Engine.circuit_run)."""
+    for a call of LUT rows only.  The wires of a live LUT sibling are boot_lut of its leader's rows and indices with the
+    sibling's table -- boot_lut is a function of (call, row, index, table) --, all siblings of a call in one further
+    boot_lut(call, ...) whose rows and indices repeat.  A checking and measuring aid: the engine's circuit path does
+    this on the device (Engine.circuit_run)."""
     inputs = np.asarray(inputs, dtype=np.uint64)
     inst, row = inputs.shape[1], inputs.shape[2]
     n = row - 1
@@ -530,6 +658,10 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
         y = np.concatenate([p[1] for p in pairs])
         res = np.zeros((len(x), 3, row), dtype=np.uint64)
         tables = np.repeat(np.array([circuit.gate_tables.get(g, -1) for g in nodes], dtype=np.int64), inst)
+        sibs = [(k, h) for k, g in enumerate(nodes) for h in circuit.live_siblings(g)]   # (rank of the leader, sibling)
+        for _, h in sibs:
+            for w in range(3):
+                wires[circuit.n_inputs + 3 * h + w] = np.zeros((inst, row), dtype=np.uint64)
         for r0 in range(0, len(x), CALL_ROWS):
             sl = slice(r0, r0 + CALL_ROWS)
             idx = np.flatnonzero(tables[sl] >= 0)
@@ -537,6 +669,18 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
                 res[sl] = boot(call, x[sl, :n], x[sl, n], y[sl, :n], y[sl, n])
             if len(idx):
                 res[r0 + idx] = boot_lut(call, x[sl, :n][idx], x[sl, n][idx], tables[sl][idx].astype(np.uint8), idx)
+            rows_in_call = len(x[sl])
+            part = [(k, h, np.arange(max(r0, k * inst), min(r0 + rows_in_call, (k + 1) * inst)) - r0) for k, h in sibs]
+            part = [(k, h, sel) for k, h, sel in part if len(sel)]
+            if part:
+                sel = np.concatenate([s_ for _, _, s_ in part])
+                tab = np.concatenate([np.full(len(s_), circuit.gate_tables[h], dtype=np.uint8) for _, h, s_ in part])
+                got = boot_lut(call, x[sl, :n][sel], x[sl, n][sel], tab, sel)
+                at = 0
+                for k, h, s_ in part:
+                    for w in range(3):
+                        wires[circuit.n_inputs + 3 * h + w][r0 + s_ - k * inst] = got[at:at + len(s_), w]
+                    at += len(s_)
             call += 1
         for k, g in enumerate(nodes):
             sl = slice(k * inst, (k + 1) * inst)
@@ -714,7 +858,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
         if i == FALSE_ID or i < circuit.n_inputs or circuit.output_shifts[o] != 0:
             return False
         g, w = divmod(i - circuit.n_inputs, 3)
-        if circuit.kind(g) == "lut":                            # wire +0 of a LUT node: refreshed or lifted
+        if circuit.kind(g) in ("lut", "sibling"):               # wire +0 of a LUT node: refreshed or lifted
             return False
         return not (w == 2 and circuit.kind(g) != "classic")   # XOR3 / LOW is linear over Z_r: no gate row over Z_Q
 
@@ -823,6 +967,8 @@ def noise_report(circuit, stats):
     for L, nodes in enumerate(circuit.schedule(), start=1):
         for g in nodes:
             level[g] = L
+            for h in circuit.siblings(g):
+                level[h] = L
     rows = []
     for wire, st in enumerate(stats):
         if st.rows == 0:
@@ -830,7 +976,7 @@ def noise_report(circuit, stats):
         g = (wire - circuit.n_inputs) // 3 if wire >= circuit.n_inputs else None
         names = ("AND", "OR", "XOR") if g is None else \
             {"classic": ("AND", "OR", "XOR"), "gate3": ("MAJ", "ONE_OR_TWO", "XOR3"), "sum": ("HI", "MID", "LOW"),
-             "lut": ("F", "F_HALF", "F_QUARTER")}[circuit.kind(g)]
+             "lut": ("F", "F_HALF", "F_QUARTER"), "sibling": ("F", "F_HALF", "F_QUARTER")}[circuit.kind(g)]
         kind = "input" if g is None else names[(wire - circuit.n_inputs) % 3]
         rows.append(dict(wire=wire, kind=kind, node=g, level=0 if g is None else level[g], rows=st.rows,
                          wrong=st.wrong, max_abs=st.max_abs, mean=st.sum / st.rows,

@@ -6,8 +6,8 @@
 // The call arithmetic of a run lives here too (at the end): circuit_level_call, circuit_job_chunk, circuit_pack_runs and
 // circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
-// circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp and circuit_calls_sanitized.cpp
-// drive it under ASan / UBSan on the CPU.
+// circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp, circuit_lut_multi_sanitized.cpp and
+// circuit_calls_sanitized.cpp drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -35,6 +35,7 @@ constexpr uint32_t CIRC_NO_INPUT = SGFHE_CIRCUIT_NONE;   // third reference of a
 struct CircuitImage {
     uint32_t node_kind = 0, term_start = 0, term_ref = 0, term_shift = 0, term_weight = 0;
     uint32_t out_slot = 0, out_ref = 0, out_shift = 0, input_slot = 0, jobs = 0, words = 0;
+    uint32_t fam_start = 0, fam_entry = 0;   // behind `jobs`, and only in a plan that has live siblings
 };
 
 struct CircuitPlan {
@@ -76,8 +77,16 @@ struct CircuitPlan {
     std::vector<uint32_t> term_row;     // [terms]
     std::vector<uint32_t> sum_before;   // [live + 1], host only: sum nodes among order[0 .. k)
     std::vector<uint32_t> lut_before;   // [live + 1], host only: LUT nodes among order[0 .. k)
+    // LUT families (sgfhe_circuit_create_lut_multi): a SIBLING (kind 3) is a further table on its leader's bootstrap.
+    // It takes no row and is not in `order`; the live siblings of the live node k are entries fam_start[k] ..
+    // fam_start[k + 1] of one CSR (empty in a plan without live siblings, and then not in the image).
+    std::vector<uint32_t> fam_start;    // [live + 1]
+    std::vector<uint32_t> fam_entry;    // [live siblings][4]: truth table, then the slots of its three wires (CIRC_NONE
+                                        // if unread)
+    std::vector<uint32_t> fam_node;     // [live siblings], host only: the sibling's node index; its wires are the probe
+                                        // rows n_inputs + 3 live() + 3 i + w
     // Every device table above in one array, uploaded once per run: node_kind, term_start, term_ref, term_shift,
-    // term_weight, out_slot, out_ref, out_shift, input_slot, jobs, each at its offset `at`
+    // term_weight, out_slot, out_ref, out_shift, input_slot, jobs (then fam_start, fam_entry), each at its offset `at`
     std::vector<uint32_t> image;
     CircuitImage at;
 
@@ -87,6 +96,9 @@ struct CircuitPlan {
     bool gate3_in(uint32_t ka, uint32_t kb) const { return sum_before[kb + 1] != sum_before[ka]; }
     // live nodes order[ka .. kb] hold a LUT node: the call carries a LUT descriptor
     bool lut_in(uint32_t ka, uint32_t kb) const { return lut_before[kb + 1] != lut_before[ka]; }
+    // live nodes order[ka .. kb] lead a live sibling: the call extracts further tables (k_final_lut_multi)
+    bool fam_in(uint32_t ka, uint32_t kb) const { return !fam_node.empty() && fam_start[kb + 1] != fam_start[ka]; }
+    size_t siblings() const { return fam_node.size(); }
     uint32_t kind(size_t k) const { return node_kind[k] & 0xFFu; }
     uint32_t table(size_t k) const { return (node_kind[k] >> 8) & 0xFFu; }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
@@ -104,6 +116,8 @@ inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
 // one, the node is the sum node of three unit weights).  `arity` 0: the CSR arrays of sgfhe_circuit_create_w.  Term i
 // of the circuit is refs[i], shifts[i] (NULL: 0), weights[i] (NULL: 1); node g's terms are first(g) .. first(g) +
 // count(g).  `lut`: the arrays of sgfhe_circuit_create_lut, whose kind 2 marks a LUT node of table tables[g].
+// `multi`: those of sgfhe_circuit_create_lut_multi, whose kind 3 marks a sibling -- no terms, table tables[g], a further
+// table on the bootstrap of its LEADER, the nearest earlier kind-2 node.
 struct CircuitNodes {
     int arity;
     const uint32_t *refs;
@@ -111,7 +125,7 @@ struct CircuitNodes {
     const uint32_t *kind = nullptr, *start = nullptr;
     const int32_t *weights = nullptr;
     const uint32_t *tables = nullptr;
-    bool lut = false;
+    bool lut = false, multi = false;
 
     size_t first(size_t g) const { return arity ? (size_t)arity * g : start[g]; }
     size_t count(size_t g) const {
@@ -119,7 +133,8 @@ struct CircuitNodes {
         return arity == 3 && refs[3 * g + 2] != CIRC_NO_INPUT ? 3 : 2;
     }
     bool classic(size_t g) const { return arity ? count(g) == 2 : kind[g] == 0; }
-    bool is_lut(size_t g) const { return !arity && kind[g] == 2; }
+    bool is_sibling(size_t g) const { return !arity && kind[g] == 3; }
+    bool is_lut(size_t g) const { return !arity && (kind[g] == 2 || kind[g] == 3); }   // (wires with scales 0, 1, 2)
     uint32_t kind_of(size_t g) const { return classic(g) ? 0u : (is_lut(g) ? 2u : 1u); }
     int32_t weight(size_t i) const { return weights ? weights[i] : 1; }
 };
@@ -143,9 +158,16 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
     if (!N.arity) {   // the CSR itself, node by node, before a term of the node is read
         if (n_gates && (!N.kind || !N.start || !N.weights || N.start[0] != 0)) return SGFHE_ERR_INVALID_ARG;
         if (n_gates && N.lut && !N.tables) return SGFHE_ERR_INVALID_ARG;
+        size_t family = 0;   // members so far of the family node g - 1 belongs to (0: it is no LUT node)
         for (size_t g = 0; g < n_gates; g++) {
-            if (N.kind[g] > (N.lut ? 2u : 1u) || N.start[g + 1] < N.start[g]) return SGFHE_ERR_INVALID_ARG;
+            if (N.kind[g] > (N.multi ? 3u : (N.lut ? 2u : 1u)) || N.start[g + 1] < N.start[g]) return SGFHE_ERR_INVALID_ARG;
             const size_t nj = N.count(g);
+            if (N.kind[g] == 3) {   // a sibling: no terms, a table, behind a LUT node or a sibling, in a family that has room
+                if (nj != 0 || N.tables[g] >= 256 || family == 0 || family >= SGFHE_LUT_MAX_TABLES) return SGFHE_ERR_INVALID_ARG;
+                family++;
+                continue;
+            }
+            family = N.kind[g] == 2 ? 1 : 0;
             if (N.kind[g] == 2) {   // a LUT node: three unit terms (positions 0, 1, 2), a table of 8 entries
                 if (nj != 3 || N.tables[g] >= 256) return SGFHE_ERR_INVALID_ARG;
             } else if (N.kind[g] == 0 ? nj != 2 : (nj < 1 || nj > SGFHE_CIRCUIT_MAX_TERMS)) {
@@ -198,7 +220,10 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         auto node_of = [&](uint32_t id) -> int64_t {   // producing node of a wire, -1 for inputs and the constant
             return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
         };
-        // ---- prune: a node is live when an output reaches it (walk back from the outputs, last node first)
+        // ---- prune: a node is live when an output reaches it (walk back from the outputs, last node first); a leader
+        // is live when any of its siblings is
+        std::vector<uint32_t> leader(NG);
+        for (uint32_t g = 0; g < NG; g++) leader[g] = N.is_sibling(g) ? leader[g - 1] : g;
         std::vector<uint8_t> live(NG, 0);
         for (size_t o = 0; o < n_outputs; o++) {
             const int64_t g = node_of(wire_id(outputs[o]));
@@ -206,15 +231,24 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         }
         for (uint32_t g = NG; g-- > 0;) {
             if (!live[g]) continue;
+            live[leader[g]] = 1;
             for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
                 const int64_t h = node_of(wire_id(refs[i]));
                 if (h >= 0) live[h] = 1;
             }
         }
-        // ---- level ASAP: 1 + the largest level of its input nodes (inputs and the constant: 0)
+        // ---- level ASAP: 1 + the largest level of its input nodes (inputs and the constant: 0); a sibling has its
+        // leader's level and takes no row
         P.level.assign(NG, 0);
+        auto takes_row = [&](uint32_t g) { return P.level[g] && !N.is_sibling(g); };
+        // the live siblings of node g, in ascending index
+        auto each_sibling = [&](uint32_t g, auto &&fn) {
+            for (uint32_t h = g + 1; h < NG && N.is_sibling(h); h++)
+                if (live[h]) fn(h);
+        };
         for (uint32_t g = 0; g < NG; g++) {
             if (!live[g]) continue;
+            if (N.is_sibling(g)) { P.level[g] = P.level[leader[g]]; continue; }
             uint32_t L = 0;
             for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
                 const int64_t h = node_of(wire_id(refs[i]));
@@ -226,7 +260,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         // ---- order: level by level, ascending node index within a level (counting sort)
         P.level_start.assign((size_t)P.levels + 2, 0);
         for (uint32_t g = 0; g < NG; g++)
-            if (P.level[g]) P.level_start[P.level[g] + 1]++;
+            if (takes_row(g)) P.level_start[P.level[g] + 1]++;
         for (uint32_t L = 1; L <= P.levels; L++) {
             P.widest = std::max(P.widest, P.level_start[L + 1]);
             P.level_start[L + 1] += P.level_start[L];
@@ -235,7 +269,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         {
             std::vector<uint32_t> fill(P.level_start.begin(), P.level_start.end() - 1);
             for (uint32_t g = 0; g < NG; g++)
-                if (P.level[g]) P.order[fill[P.level[g]]++] = g;
+                if (takes_row(g)) P.order[fill[P.level[g]]++] = g;
         }
         // ---- liveness: the last level that reads each wire (outputs: beyond the last level)
         const uint32_t END = P.levels + 1;
@@ -267,11 +301,28 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             if (last_read[i] != UNREAD) { take(i); P.input_slot[i] = slot_of[i]; }
         for (uint32_t L = 1; L <= P.levels; L++) {
             for (uint32_t s : release[L - 1]) free_slots.push(s);
-            for (uint32_t k = P.level_start[L]; k < P.level_start[L + 1]; k++)
+            auto take_read = [&](uint32_t g) {
                 for (uint32_t w = 0; w < 3; w++) {
-                    const uint32_t id = n_inputs + 3 * P.order[k] + w;
+                    const uint32_t id = n_inputs + 3 * g + w;
                     if (last_read[id] != UNREAD) take(id);
                 }
+            };
+            for (uint32_t k = P.level_start[L]; k < P.level_start[L + 1]; k++) {
+                take_read(P.order[k]);
+                each_sibling(P.order[k], take_read);   // written by the leader's call: slots of the same level
+            }
+        }
+        // ---- the families: every live node's live siblings, their tables and slots; a sibling's probe rows
+        std::vector<uint32_t> sib_index(NG, CIRC_NONE);
+        P.fam_start.assign(P.live() + 1, 0);
+        for (size_t k = 0; k < P.live(); k++) {
+            each_sibling(P.order[k], [&](uint32_t h) {
+                sib_index[h] = (uint32_t)P.fam_node.size();
+                P.fam_node.push_back(h);
+                P.fam_entry.push_back(N.tables[h]);
+                for (uint32_t w = 0; w < 3; w++) P.fam_entry.push_back(slot_of[n_inputs + 3 * h + w]);
+            });
+            P.fam_start[k + 1] = (uint32_t)P.fam_node.size();
         }
         // ---- the node table: every live node's terms in the caller's order.  A shifted reference reads other ROWS of
         // the slot it names, nothing else: the wire is of an earlier level (or an input), so all its rows are written
@@ -289,7 +340,9 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         auto row_ref = [&](uint32_t ref) -> uint32_t {
             const uint32_t id = wire_id(ref);
             const int64_t g = node_of(id);
-            return (g < 0 ? id : n_inputs + 3 * rank_of[g] + (id - n_inputs) % 3) | (ref & CIRC_NOT);
+            if (g < 0) return id | (ref & CIRC_NOT);
+            const size_t node_row = N.is_sibling((size_t)g) ? P.live() + sib_index[g] : rank_of[g];
+            return (uint32_t)(n_inputs + 3 * node_row + (id - n_inputs) % 3) | (ref & CIRC_NOT);
         };
         auto term = [&](uint32_t ref, int32_t shift, int32_t weight) {
             P.term_ref.push_back(ref);
@@ -364,6 +417,10 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         P.at.out_shift = place(P.out_shift);
         P.at.input_slot = place(P.input_slot);
         P.at.jobs = place(P.jobs);
+        if (P.siblings()) {
+            P.at.fam_start = place(P.fam_start);
+            P.at.fam_entry = place(P.fam_entry);
+        }
         P.at.words = (uint32_t)P.image.size();
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
         P = CircuitPlan();
@@ -400,6 +457,15 @@ inline int32_t circuit_plan_lut(uint32_t n_inputs, const uint32_t *node_kind, co
     return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
 }
 
+// The arrays of sgfhe_circuit_create_lut_multi: those of sgfhe_circuit_create_lut, and kind 3 for a sibling.
+inline int32_t circuit_plan_lut_multi(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
+                                      const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                      const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
+                                      const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
+    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true, true};
+    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
+}
+
 // The arrays of sgfhe_circuit_create_lanes.
 inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                             const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
@@ -421,7 +487,8 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
 }
 
 // The circuit in clear over `instances`, for the noise probe (sgfhe_circuit_run_probe): the plaintext bit of every
-// probe row -- the n_inputs input wires, then AND, OR, XOR of every live node in `order` -- as a bit table of
+// probe row -- the n_inputs input wires, then AND, OR, XOR of every live node in `order`, then the three wires of every
+// live sibling in the order of CircuitPlan::fam_node -- as a bit table of
 // circuit_probe_rows(P) rows of circuit_bit_words(instances) uint64 words each: bit (t & 63) of word t / 64 of a row
 // is instance t (the bits past `instances` in a row's last word are unspecified).  in_bits [n_inputs][instances],
 // bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances); a lane-shifted input is first
@@ -429,13 +496,13 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
 // `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  A sum node's rows are HI, MID and LOW
 // of s = sum of w x mod 4: MAJ, ONE_OR_TWO (one or two of its inputs true) and XOR3 of a three-input node.
 // SGFHE_ERR_OOM when the table cannot be allocated; nothing throws out of it.
-inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * P.live(); }
+inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * (P.live() + P.siblings()); }
 inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
 // wire id of a probe row (the inverse of CircuitPlan::term_row's numbering)
 inline uint32_t circuit_probe_wire(const CircuitPlan &P, size_t row) {
     if (row < P.n_inputs) return (uint32_t)row;
     const size_t k = (row - P.n_inputs) / 3, w = (row - P.n_inputs) % 3;
-    return (uint32_t)(P.n_inputs + 3 * (size_t)P.order[k] + w);
+    return (uint32_t)(P.n_inputs + 3 * (size_t)(k < P.live() ? P.order[k] : P.fam_node[k - P.live()]) + w);
 }
 inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, size_t instances,
                                   std::vector<uint64_t> &table) noexcept {
@@ -478,18 +545,22 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
         const uint32_t t0 = P.term_start[k], t1 = P.term_start[k + 1];
         if (P.kind(k) == 2) {
             // a LUT node: all three wires carry bit s of the table, s = x0 + 2 x1 + 4 x2 -- the OR over the set table
-            // entries of their minterms
+            // entries of their minterms; its live siblings carry their own tables' bits of the same s
             const uint64_t *sx[3];
             for (uint32_t p = 0; p < 3; p++) sx[p] = source(P.term_row[t0 + p], P.term_shift[t0 + p], shifted[p]);
-            const uint32_t tb = P.table(k);
-            for (size_t w = 0; w < wpr; w++) {
-                uint64_t x[3], f = 0;
-                for (uint32_t p = 0; p < 3; p++) x[p] = word(sx[p], P.term_row[t0 + p], w);
-                for (uint32_t sv = 0; sv < 8; sv++)
-                    if ((tb >> sv) & 1u)
-                        f |= (sv & 1 ? x[0] : ~x[0]) & (sv & 2 ? x[1] : ~x[1]) & (sv & 4 ? x[2] : ~x[2]);
-                o[w] = o[wpr + w] = o[2 * wpr + w] = f;
-            }
+            auto fill = [&](uint32_t tb, uint64_t *dst) {
+                for (size_t w = 0; w < wpr; w++) {
+                    uint64_t x[3], f = 0;
+                    for (uint32_t p = 0; p < 3; p++) x[p] = word(sx[p], P.term_row[t0 + p], w);
+                    for (uint32_t sv = 0; sv < 8; sv++)
+                        if ((tb >> sv) & 1u)
+                            f |= (sv & 1 ? x[0] : ~x[0]) & (sv & 2 ? x[1] : ~x[1]) & (sv & 4 ? x[2] : ~x[2]);
+                    dst[w] = dst[wpr + w] = dst[2 * wpr + w] = f;
+                }
+            };
+            fill(P.table(k), o);
+            for (size_t i = P.siblings() ? P.fam_start[k] : 0, end = P.siblings() ? P.fam_start[k + 1] : 0; i < end; i++)
+                fill(P.fam_entry[4 * i], table.data() + ((size_t)P.n_inputs + 3 * (P.live() + i)) * wpr);
             continue;
         }
         if (P.kind(k) == 1) {
@@ -541,6 +612,7 @@ struct CircuitCall {
                        // un-reduced
     bool sum;          // one of the nodes is a sum node: the call takes an XOR3 kernel for its LOW rows
     bool lut;          // one of the nodes is a LUT node: the call carries a LUT descriptor
+    bool fam;          // one of the nodes leads a live sibling: the call extracts further tables into the wire table
 };
 inline CircuitCall circuit_level_call(const CircuitPlan &P, uint32_t L, uint64_t row0, uint64_t instances) noexcept {
     CircuitCall C;
@@ -552,6 +624,7 @@ inline CircuitCall circuit_level_call(const CircuitPlan &P, uint32_t L, uint64_t
     C.j1 = (size_t)(std::upper_bound(P.job_k.begin(), P.job_k.end(), C.kb) - P.job_k.begin());
     C.sum = P.gate3_in(C.ka, C.kb);
     C.lut = P.lut_in(C.ka, C.kb);
+    C.fam = P.fam_in(C.ka, C.kb);
     return C;
 }
 

@@ -898,9 +898,19 @@ struct HostPipe {
 // The LUT rows of a call (sgfhe_bootstrap_lut_batch): `rows` is a device array of one word per row of the call,
 // LUT_ROW | truth table for a LUT row and 0 for a row of the classic path.  A LUT row starts at amplitude A0 (k_init)
 // and leaves through k_final_lut; `all` says that every row is one, so that k_final has nothing to write.
+// A LUT family call (sgfhe_bootstrap_lut_multi_batch) sets `tables`, the device array [row][n_tables] of every row's
+// tables: every row is a LUT row, `out` is [row][n_tables][3][n + 1], and the rows leave through k_final_lut_multi.
+// A level call whose LUT nodes lead live siblings (sgfhe_circuit_create_lut_multi) sets `wires` and the family CSR
+// (kernels.h LutTables, with row0 the call's first row of its level): the leaders' rows leave as any LUT row, and
+// k_final_lut_multi writes the siblings' wires from the same accumulators straight into the wire table -- per chunk,
+// before the next chunk reuses the digits.
 struct LutDesc {
     const uint32_t *rows;
     bool all;
+    const uint8_t *tables = nullptr;
+    uint32_t n_tables = 1;
+    uint64_t *wires = nullptr;
+    LutTables fam = {};
 };
 
 int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, const uint64_t *a2,
@@ -1104,7 +1114,20 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
                     hipLaunchKernelGGL(k_final, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
                                        out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, J.cb, n,
                                        (uint32_t)c->logm, raw ? 1u : 0u, mode);
-                if (lut)   // the LUT rows of the chunk, over what k_final wrote for them
+                if (lut && lut->tables) {   // a family call: every table of every row of the chunk
+                    LutTables T = {};
+                    T.tables = lut->tables + J.c0 * lut->n_tables;
+                    T.n_tables = lut->n_tables;
+                    hipLaunchKernelGGL(k_final_lut_multi<false>, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
+                                       out + J.c0 * lut->n_tables * 3 * (n + 1) * (raw ? 2 : 1), d_crt, T, J.cb, n,
+                                       (uint32_t)c->logm, raw ? 1u : 0u, mode);
+                } else if (lut && lut->wires) {   // the siblings of the chunk's LUT nodes, into the wire table
+                    LutTables T = lut->fam;
+                    T.row0 += (uint32_t)J.c0;
+                    hipLaunchKernelGGL(k_final_lut_multi<true>, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
+                                       lut->wires, d_crt, T, J.cb, n, (uint32_t)c->logm, 0u, mode);
+                }
+                if (lut && !lut->tables)   // the LUT rows of the chunk, over what k_final wrote for them
                     hipLaunchKernelGGL(k_final_lut, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
                                        out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, lut->rows + J.c0, J.cb, n,
                                        (uint32_t)c->logm, raw ? 1u : 0u, mode);
@@ -2689,6 +2712,69 @@ int32_t sgfhe_bootstrap_lut_batch(sgfhe_ctx *c, const uint64_t *a, const uint64_
     return run_drained(c, [&] { return bootstrap_lut_queued(c, a, b, words, batch, out, flags); });
 }
 
+// everything sgfhe_bootstrap_lut_multi_batch does on the device
+// (the buffers of bootstrap_lut_queued; the tables lie behind the descriptor, eight to a uint64)
+static int32_t bootstrap_lut_multi_queued(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint8_t *tables,
+                                          size_t n_tables, const std::vector<uint32_t> &words, size_t batch, uint64_t *out,
+                                          uint32_t flags) {
+    const size_t n = c->n;
+    hipStream_t st = c->stream;
+    const bool raw = flags & SGFHE_FLAG_RAW_MODQ;
+    const size_t out_words = batch * n_tables * 3 * (n + 1) * (raw ? 2 : 1);
+    const size_t desc = 2 * batch * n + 2 * batch, tab = desc + (batch + 1) / 2;
+    int32_t rc;
+    if ((rc = circ_grow(c, c->pack_lwe, tab + (batch * n_tables + 7) / 8))) return rc;
+    if ((rc = circ_grow(c, c->pack_raw, (out_words + 1) / 2))) return rc;
+    const Staging S = staging(c->pack_lwe.p, batch, n);
+    uint32_t *d_lut = reinterpret_cast<uint32_t *>(c->pack_lwe.p + desc);
+    uint8_t *d_tab = reinterpret_cast<uint8_t *>(c->pack_lwe.p + tab);
+    HIPCHK(c, hipMemcpyAsync(S.a1, a, batch * n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.b1, b, batch * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(S.a2, 0, batch * n * 8, st));
+    HIPCHK(c, hipMemsetAsync(S.b2, 0, batch * 8, st));
+    HIPCHK(c, hipMemcpyAsync(d_lut, words.data(), batch * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_tab, tables, batch * n_tables, hipMemcpyHostToDevice, st));
+    LutDesc lut = {d_lut, true};
+    lut.tables = d_tab;
+    lut.n_tables = (uint32_t)n_tables;
+    uint64_t *d_out = reinterpret_cast<uint64_t *>(c->pack_raw.p);
+    if ((rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, batch, d_out, flags, c->n, nullptr, st, nullptr, nullptr, &lut)))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->pending = false;
+    return SGFHE_OK;
+}
+
+int32_t sgfhe_bootstrap_lut_multi_batch(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint8_t *tables,
+                                        size_t n_tables, size_t batch, uint64_t *out, uint32_t flags) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    if (n_tables < 1 || n_tables > SGFHE_LUT_MAX_TABLES)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: n_tables is 1 to SGFHE_LUT_MAX_TABLES");
+    if (flags & ~SGFHE_FLAG_RAW_MODQ)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: flags is 0 or SGFHE_FLAG_RAW_MODQ");
+    if (batch == 0) return SGFHE_OK;
+    if (!a || !b || !tables || !out)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: NULL row, table or output pointer");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    if (batch > ((size_t)1 << 31) / (c->n + 1) / n_tables)   // (row and table counts are 32-bit on the device)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: too many rows");
+    for (size_t i = 0; i < batch * c->n; i++)
+        if (a[i] >= c->par.r)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: word " + std::to_string(i) + " of a is not below r");
+    for (size_t i = 0; i < batch; i++)
+        if (b[i] >= c->par.r)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: b of row " + std::to_string(i) + " is not below r");
+    std::vector<uint32_t> words;   // the descriptor of k_init: every row is a LUT row
+    try {
+        words.assign(batch, LUT_ROW);
+    } catch (...) {
+        return fail(c, SGFHE_ERR_OOM, "out of host memory");
+    }
+    return run_drained(c, [&] { return bootstrap_lut_multi_queued(c, a, b, tables, n_tables, words, batch, out, flags); });
+}
+
 int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const uint32_t *in,
                         uint32_t *out) {
     if (!c || !in || !out) return SGFHE_ERR_INVALID_ARG;
@@ -3010,6 +3096,14 @@ int32_t sgfhe_circuit_create_lut(uint32_t n_inputs, const uint32_t *node_kind, c
     return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
 }
 
+int32_t sgfhe_circuit_create_lut_multi(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
+                                       const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                       const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
+                                       const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out) {
+    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true, true};
+    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
+}
+
 int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
                              size_t n_outputs, sgfhe_circuit **out) {
     return sgfhe_circuit_create_lanes(n_inputs, gates, nullptr, n_gates, outputs, nullptr, n_outputs, 1u, out);
@@ -3141,6 +3235,7 @@ struct CircuitRun {
     // the plan's tables on the device (views into circ_tab), and the probe's
     CircNodes nodes = {};
     const uint32_t *d_out_slot = nullptr, *d_out_ref = nullptr, *d_in_slot = nullptr, *d_jobs = nullptr;
+    const uint32_t *d_fam_start = nullptr, *d_fam_entry = nullptr;   // (a plan with live siblings)
     const int32_t *d_out_shift = nullptr;
     NoiseLayout NL = {};
     std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
@@ -3221,6 +3316,7 @@ int32_t CircuitRun::upload_tables() {
              reinterpret_cast<const int32_t *>(tab + P.at.term_weight)};
     d_out_slot = tab + P.at.out_slot, d_out_ref = tab + P.at.out_ref, d_in_slot = tab + P.at.input_slot;
     d_jobs = tab + P.at.jobs;
+    if (P.siblings()) d_fam_start = tab + P.at.fam_start, d_fam_entry = tab + P.at.fam_entry;
     d_out_shift = reinterpret_cast<const int32_t *>(tab + P.at.out_shift);
     if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
         HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
@@ -3274,7 +3370,12 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
     const uint32_t un = (uint32_t)n, r0 = (uint32_t)row0;
     const bool raw = direct && C.j1 > C.j0;
     // a call that holds a LUT node: its rows start at amplitude A0 and leave through k_final_lut (LutDesc)
-    const LutDesc lut = {reinterpret_cast<uint32_t *>(c->circ_stage.p + stage_words()), false};
+    LutDesc lut = {reinterpret_cast<uint32_t *>(c->circ_stage.p + stage_words()), false};
+    if (C.fam) {   // ... and the live siblings of its LUT nodes leave through k_final_lut_multi, into the wire table
+        lut.wires = c->circ_wires.p;
+        lut.fam.start = d_fam_start, lut.fam.entry = d_fam_entry;
+        lut.fam.node0 = C.k0, lut.fam.row0 = r0, lut.fam.instances = inst;
+    }
     gather(C.k0, S, row0, C.rows, C.lut ? const_cast<uint32_t *>(lut.rows) : nullptr);
     HIPCHK(c, hipGetLastError());
     int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, C.rows, S.res, raw ? SGFHE_FLAG_RAW_MODQ : 0u, c->n, nullptr, st,
@@ -3307,10 +3408,27 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
                        C.rows, inst, un);
     HIPCHK(c, hipGetLastError());
     // the probe: the call's own result rows, read or not, before the next call overwrites them (same stream)
-    if (probe) return launch_lwe_noise(c, st, S.res, NL,
-                                       noise_call_rows(n, P.n_inputs, C, row0, inst, bit_words, nodes.kind + C.ka),
-                                       C.kb - C.ka + 1, 3);
-    return SGFHE_OK;
+    if (!probe) return SGFHE_OK;
+    rc = launch_lwe_noise(c, st, S.res, NL, noise_call_rows(n, P.n_inputs, C, row0, inst, bit_words, nodes.kind + C.ka),
+                          C.kb - C.ka + 1, 3);
+    // a sibling has no result rows: the wires of it that have a slot are measured there, over the instances of its
+    // leader that this call holds, each against its own codeword
+    for (uint32_t k = C.ka; !rc && C.fam && k <= C.kb; k++) {
+        const uint64_t lo = std::max<uint64_t>(row0, (uint64_t)(k - C.k0) * inst);
+        const uint64_t hi = std::min<uint64_t>(row0 + C.rows, (uint64_t)(k - C.k0 + 1) * inst);
+        const uint32_t i0 = (uint32_t)(lo - (uint64_t)(k - C.k0) * inst), cnt = (uint32_t)(hi - lo);
+        for (uint32_t i = P.fam_start[k]; !rc && i < P.fam_start[k + 1]; i++)
+            for (uint32_t w = 0; !rc && w < 3; w++) {
+                const uint32_t slot = P.fam_entry[4 * i + 1 + w];
+                if (slot == CIRC_NONE) continue;
+                NoiseGeom G = noise_wire_rows(n, (uint32_t)(P.n_inputs + 3 * (P.live() + i) + w), cnt, bit_words);
+                G.instances = inst;
+                G.inst0 = G.row0 = i0;
+                G.scale = w;
+                rc = launch_lwe_noise(c, st, c->circ_wires.p + ((size_t)slot * inst + i0) * row, NL, G);
+            }
+    }
+    return rc;
 }
 
 // One pack group: ciphertexts q0 .. q0 + cnt are rows q0 * n .. of the "level" whose node o is (TRUE, output o) --

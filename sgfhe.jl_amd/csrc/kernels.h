@@ -1683,6 +1683,64 @@ k_final(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out,
 // chunk that are not LUT rows are left alone (k_final has written them).  The table decode is uniform over a row;
 // consecutive threads read consecutive (descending) coefficients.  c(j) - e is taken mod 2 m: c(j) >= m for j <= 4
 // (the negated half), and c(4) - m = Dr/8 < n, so the index does wrap below 0 into the other half, negating again.
+// P(acc, c(j) - e) of one thread, j in 1..8: the coefficient index with its wrap, and the negation that goes with it.
+__device__ __forceinline__ u128 lut_coeff(const uint64_t *__restrict__ dig, size_t bc, uint32_t shift, uint32_t j,
+                                          uint32_t M, bool wide, const CrtConst *CC, uint32_t mode) {
+    const uint32_t c = 3 * (M / 2) - (2 * j - 1) * (M / 16);          // below 3 m / 2
+    uint32_t idx = (c + 2 * M - shift) & (2 * M - 1);
+    const bool neg = idx >= M;
+    if (neg) idx -= M;
+    const u128 w = acc_from_digits(load_digits(dig, bc, idx, M, wide), CC, mode);
+    return neg && w ? CC->Q - w : w;
+}
+
+// bit j of the result marks a transition of the table at j in 1..8 (sigma(8) = -sigma(0))
+__device__ __forceinline__ uint32_t lut_edges(uint32_t table) {
+    const uint32_t ext = (table & 0xFFu) | ((~table & 1u) << 8);   // bit j is sigma(j) for j in 0..8
+    return (ext ^ (ext << 1)) & 0x1FEu;
+}
+
+// The base LWE word of one table: A0 on the b word only, then kappa_i coeff(j_i) over the table's transitions, folded
+// after every add.  coeff(j) is P(acc, c(j) - e): k_final_lut loads it, k_final_lut_multi has it in a register.
+template <class F>
+__device__ __forceinline__ u128 lut_base(uint32_t table, bool bword, const CrtConst *CC, F coeff) {
+    const u128 Q = CC->Q;
+    const uint32_t edge = lut_edges(table);
+    bool minus = (table & 1u) != 0;      // kappa_0 = -sigma(0)
+    u128 v = bword ? CC->DQL : (u128)0;
+#pragma unroll
+    for (uint32_t j = 1; j <= 8; j++) {
+        if (!((edge >> j) & 1u)) continue;
+        u128 w = coeff(j);
+        if (minus) w = w ? Q - w : 0;
+        v += w;
+        if (v >= Q) v -= Q;
+        minus = !minus;
+    }
+    return v;
+}
+
+// The three scaled rows of a base word v: 4 v, 2 v and v mod Q at `o`, `o + stride`, `o + 2 stride` -- 16-byte
+// residues when raw (`o` then counts residues), through ModRed otherwise.
+__device__ __forceinline__ void lut_store_rows(uint64_t *__restrict__ o, size_t stride, u128 v, uint32_t raw,
+                                               const CrtConst *CC) {
+    const u128 Q = CC->Q;
+    u128 v2 = v + v;
+    if (v2 >= Q) v2 -= Q;
+    u128 v4 = v2 + v2;
+    if (v4 >= Q) v4 -= Q;
+    if (raw) {
+        ulonglong2 *o2 = reinterpret_cast<ulonglong2 *>(o);
+        o2[0] = make_ulonglong2((uint64_t)v4, (uint64_t)(v4 >> 64));
+        o2[stride] = make_ulonglong2((uint64_t)v2, (uint64_t)(v2 >> 64));
+        o2[2 * stride] = make_ulonglong2((uint64_t)v, (uint64_t)(v >> 64));
+    } else {
+        o[0] = modred(v4, CC);
+        o[stride] = modred(v2, CC);
+        o[2 * stride] = modred(v, CC);
+    }
+}
+
 __global__ void __launch_bounds__(256)
 k_final_lut(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, const CrtConst *__restrict__ CC,
             const uint32_t *__restrict__ lut, uint32_t nvalid, uint32_t n, uint32_t logm, uint32_t raw, uint32_t mode) {
@@ -1692,42 +1750,86 @@ k_final_lut(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, const 
     const uint32_t b = t / (n + 1), e = t % (n + 1);
     const uint32_t word = lut[b];
     if (!(word & LUT_ROW)) return;
-    const u128 Q = CC->Q;
     const bool wide = (mode & MODE_WIDE) != 0;
     const size_t bc = (size_t)b * 2 + (e < n ? 0 : 1);
     const uint32_t shift = e < n ? e : 0u;
-    // bit j of `ext` is sigma(j) for j in 0..8; bit j of `edge` marks a transition at j
-    const uint32_t ext = (word & 0xFFu) | ((~word & 1u) << 8);
-    const uint32_t edge = (ext ^ (ext << 1)) & 0x1FEu;
-    bool minus = (word & 1u) != 0;      // kappa_0 = -sigma(0)
-    u128 v = e < n ? (u128)0 : CC->DQL;
-    for (uint32_t j = 1; j <= 8; j++) {
-        if (!((edge >> j) & 1u)) continue;
-        const uint32_t c = 3 * (M / 2) - (2 * j - 1) * (M / 16);          // below 3 m / 2
-        uint32_t idx = (c + 2 * M - shift) & (2 * M - 1);
-        bool neg = minus;
-        if (idx >= M) { idx -= M; neg = !neg; }
-        u128 w = acc_from_digits(load_digits(dig, bc, idx, M, wide), CC, mode);
-        if (neg) w = w ? Q - w : 0;
-        v += w;
-        if (v >= Q) v -= Q;
-        minus = !minus;
-    }
+    const u128 v = lut_base(word, e == n, CC,
+                            [&](uint32_t j) { return lut_coeff(dig, bc, shift, j, M, wide, CC, mode); });
     const size_t stride = n + 1;
-    u128 v2 = v + v;
-    if (v2 >= Q) v2 -= Q;
-    u128 v4 = v2 + v2;
-    if (v4 >= Q) v4 -= Q;
-    if (raw) {
-        ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out) + (size_t)b * 3 * stride + e;
-        o[0] = make_ulonglong2((uint64_t)v4, (uint64_t)(v4 >> 64));
-        o[stride] = make_ulonglong2((uint64_t)v2, (uint64_t)(v2 >> 64));
-        o[2 * stride] = make_ulonglong2((uint64_t)v, (uint64_t)(v >> 64));
+    lut_store_rows(out + ((size_t)b * 3 * stride + e) * (raw ? 2 : 1), stride, v, raw, CC);
+}
+
+// (slot references of the circuit tables, described with the gate circuits below)
+constexpr uint32_t CIRC_REF_FALSE = 0x7FFFFFFFu, CIRC_REF_NOT = 0x80000000u, CIRC_SLOT_NONE = 0xFFFFFFFFu;
+
+// ---- k_final_lut_multi --------------------------------------------------------------------------
+// A LUT family: several truth tables on the accumulator of one row.  The k-loop does not know the table; a further
+// table costs one more +-1 combination of the same eight coefficients.
+// One thread per (row of the chunk, word e in [0, n]), as k_final_lut.  The thread reconstructs P(acc, c(j) - e) once
+// for every j that is a transition of some table of its row (lut_coeff: the index wrap and the double negation are
+// k_final_lut's), keeps the eight values in registers -- the loops over j are unrolled, so the array is never indexed
+// at run time -- and then forms lut_base and the three scaled rows table by table: the bytes of k_final_lut for that
+// table.  The table list is uniform over a row, and for every table consecutive threads store consecutive words:
+// coalesced 8-byte stores, or 16-byte ones when raw.  The kernel is bound by those stores, 3 words a table and thread.
+// The primitive (sgfhe_bootstrap_lut_multi_batch, CIRC = false): the row's tables are tables[row][0 .. n_tables), and
+// the rows go to out [row][n_tables][3][n + 1], both from the chunk's first row on.
+// A level call of a circuit (sgfhe_circuit_create_lut_multi, CIRC = true): chunk row b is row R = row0 + b of its
+// level, node node0 + R / instances of the plan at instance R % instances; the live siblings of that node are the
+// entries start[node] .. start[node + 1] of {table, slot of wire +0, +1, +2} (CircuitPlan::fam_entry), and wire w goes
+// to its slot of the wire table `out` ([slot][instances][n + 1]) -- as the ModRed word, in an un-reduced call too;
+// a wire nothing reads has no slot (CIRC_SLOT_NONE) and is not formed.  The node's own table leaves through k_final_lut.
+struct LutTables {
+    const uint8_t *tables;            // the primitive
+    uint32_t n_tables;
+    const uint32_t *start, *entry;    // a level call
+    uint32_t node0, row0, instances;
+};
+__device__ __forceinline__ void lut_coeffs(u128 (&P)[8], uint32_t need, const uint64_t *__restrict__ dig, size_t bc,
+                                           uint32_t shift, uint32_t M, bool wide, const CrtConst *CC, uint32_t mode) {
+#pragma unroll
+    for (uint32_t j = 1; j <= 8; j++)
+        P[j - 1] = (need >> j) & 1u ? lut_coeff(dig, bc, shift, j, M, wide, CC, mode) : (u128)0;
+}
+template <bool CIRC>
+__global__ void __launch_bounds__(256)
+k_final_lut_multi(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, const CrtConst *__restrict__ CC,
+                  LutTables T, uint32_t nvalid, uint32_t n, uint32_t logm, uint32_t raw, uint32_t mode) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nvalid * (n + 1)) return;
+    const uint32_t M = 1u << logm;
+    const uint32_t b = t / (n + 1), e = t % (n + 1);
+    const bool wide = (mode & MODE_WIDE) != 0;
+    const size_t bc = (size_t)b * 2 + (e < n ? 0 : 1);
+    const uint32_t shift = e < n ? e : 0u;
+    const size_t stride = n + 1;
+    uint32_t need = 0;                   // bit j: some table of the row has a transition at j
+    u128 P[8];
+    if constexpr (CIRC) {
+        const uint32_t R = T.row0 + b, node = T.node0 + R / T.instances, inst = R % T.instances;
+        const uint32_t s0 = T.start[node], s1 = T.start[node + 1];
+        if (s0 == s1) return;
+        for (uint32_t i = s0; i < s1; i++) need |= lut_edges(T.entry[4 * i]);
+        lut_coeffs(P, need, dig, bc, shift, M, wide, CC, mode);
+        const u128 Q = CC->Q;
+        for (uint32_t i = s0; i < s1; i++) {
+            u128 v = lut_base(T.entry[4 * i], e == n, CC, [&](uint32_t j) { return P[j - 1]; });
+#pragma unroll
+            for (int w = 2; w >= 0; w--) {   // wire +2 is the base word, +1 twice and +0 four times it
+                const uint32_t slot = T.entry[4 * i + 1 + w];
+                if (slot != CIRC_SLOT_NONE) out[((size_t)slot * T.instances + inst) * stride + e] = modred(v, CC);
+                v += v;
+                if (v >= Q) v -= Q;
+            }
+        }
     } else {
-        uint64_t *o = out + (size_t)b * 3 * stride + e;
-        o[0] = modred(v4, CC);
-        o[stride] = modred(v2, CC);
-        o[2 * stride] = modred(v, CC);
+        const uint8_t *tab = T.tables + (size_t)b * T.n_tables;
+        for (uint32_t i = 0; i < T.n_tables; i++) need |= lut_edges(tab[i]);
+        lut_coeffs(P, need, dig, bc, shift, M, wide, CC, mode);
+        uint64_t *o = out + (((size_t)b * T.n_tables) * 3 * stride + e) * (raw ? 2 : 1);
+        for (uint32_t i = 0; i < T.n_tables; i++, o += 3 * stride * (raw ? 2 : 1)) {
+            const u128 v = lut_base(tab[i], e == n, CC, [&](uint32_t j) { return P[j - 1]; });
+            lut_store_rows(o, stride, v, raw, CC);
+        }
     }
 }
 
@@ -1738,7 +1840,6 @@ k_final_lut(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, const 
 // are not 16-byte aligned).  Row R of a level is node rank R / instances, instance R % instances.
 // A slot reference is a slot number, or CIRC_FALSE (the trivial LWE (0, 0)), plus CIRC_NOT:
 // NOT w = enc_trivial(true) - w (fhe.jl:221-223,669-670), a -> -a mod r, b -> (Dr - b) mod r.
-constexpr uint32_t CIRC_REF_FALSE = 0x7FFFFFFFu, CIRC_REF_NOT = 0x80000000u, CIRC_SLOT_NONE = 0xFFFFFFFFu;
 
 // `one`: the codeword of the wire, b of its trivial TRUE -- Dr = r / 4 everywhere but at positions 0 and 1 of a LUT node,
 // which read wires at Dr/4 and Dr/2.
@@ -2048,6 +2149,7 @@ struct NoiseGeom {
     uint32_t wire0, node0, row0, rows, instances, inst0, tiles, bit_words, n;
     const uint32_t *kind;             // the node kinds of the launch, by node_in_launch (device; NULL: no LUT node) --
                                       // gate g of a LUT node is measured against its own codeword Dr >> g
+    uint32_t scale;                   // added to that scale: the launch over one wire of a LUT sibling, from its slot
 };
 
 __device__ __forceinline__ void noise_load_mask(uint64_t *smask, const uint64_t *__restrict__ keymask, uint32_t n) {
@@ -2081,7 +2183,7 @@ k_lwe_noise(const uint64_t *__restrict__ lwe, const uint64_t *__restrict__ keyma
     const uint32_t wire = G.wire0 + node * gridDim.y + blockIdx.y;
     const uint64_t rmask = (1ull << logr) - 1, Dr = 1ull << (logr - 2);
     // the wire's codeword C = Dr >> scale (uniform over the workgroup): scale 0 but for wires +1, +2 of a LUT node
-    const uint32_t scale = G.kind && (G.kind[node] & 0xFFu) == 2 ? blockIdx.y : 0u;
+    const uint32_t scale = G.scale + (G.kind && (G.kind[node] & 0xFFu) == 2 ? blockIdx.y : 0u);
     const uint64_t C = Dr >> scale;
     const uint64_t *wbits = bits + (size_t)wire * G.bit_words;
     uint64_t cnt = 0, wrong = 0, emax = 0, esum = 0, esq = 0, margin = 0;

@@ -17,6 +17,7 @@ FLAG_RAW_MODQ = 1
 CIRCUIT_PACK_DIRECT = 1      # SGFHE_CIRCUIT_PACK_DIRECT
 CIRCUIT_PACK_LIFT = 2        # SGFHE_CIRCUIT_PACK_LIFT
 FLAG_RAW_RNS2 = 2
+LUT_MAX_TABLES = 256         # SGFHE_LUT_MAX_TABLES
 CTX_RANDOM_FLATTEN = 1          # accepted, without effect since ABI revision 6
 CTX_DETERMINISTIC_ONLY = 2
 
@@ -254,6 +255,28 @@ class Engine:
                        FLAG_RAW_MODQ if raw else 0)
         return out
 
+    def bootstrap_lut_multi_batch(self, a, b, tables, raw=False):
+        """A LUT family (sgfhe_bootstrap_lut_multi_batch): T truth tables on one bootstrap per row.  a [batch][n],
+        b [batch] as in bootstrap_lut_batch; tables [batch][T], T in 1..256.  Returns [batch][T][3][n+1] uint64 (or
+        [batch][T][3][n+1][2] residues mod Q with raw=True): [:, j] has the bytes of bootstrap_lut_batch(a, b,
+        tables[:, j]) at the same call number of the draw stream, for the cost of one k-loop per row."""
+        n = self.params.n
+        a, pa = _c(a)
+        b, pb = _c(b)
+        t, pt = _c(tables, np.uint8)
+        a = a.reshape(-1, n)
+        batch = a.shape[0]
+        if b.size != batch or t.ndim != 2 or t.shape[0] != batch:
+            raise ValueError("bootstrap_lut_multi_batch: a is [batch][n], b is [batch], tables is [batch][T]")
+        T = t.shape[1]
+        if not 1 <= T <= LUT_MAX_TABLES:
+            raise ValueError("bootstrap_lut_multi_batch: 1 to %d tables per row" % LUT_MAX_TABLES)
+        out = np.zeros((batch, T, 3, n + 1, 2) if raw else (batch, T, 3, n + 1), dtype=np.uint64)
+        if batch:
+            self._call("sgfhe_bootstrap_lut_multi_batch", pa, pb, pt, T, batch, out.ctypes.data_as(ctypes.c_void_p),
+                       FLAG_RAW_MODQ if raw else 0)
+        return out
+
     def bootstrap_batch_device(self, a1_ptr, b1_ptr, a2_ptr, b2_ptr, batch, out_ptr, raw=False,
                                stream=None):
         """Asynchronous, all buffers device-resident (raw pointers)."""
@@ -281,7 +304,8 @@ class Engine:
         """circuit_run that also measures every wire against the secret key (sgfhe_circuit_run_probe; a
         DIAGNOSTIC: the key crosses the boundary).  sk: n key bits; in_bits [n_inputs][instances]: the plaintext
         bit of every input LWE.  Returns (out, stats): out as circuit_run (the same bytes), stats a list of
-        NoiseStats by wire id -- inputs, then AND, OR, XOR of every node; all-zero records for pruned nodes."""
+        NoiseStats by wire id -- inputs, then AND, OR, XOR of every node; all-zero records for pruned nodes and for the
+        wires of a LUT sibling (Circuit.lut_multi) that nothing reads: those are never formed."""
         n = self.params.n
         a, ptr = _c(inputs)
         if a.ndim != 3 or a.shape[0] != circuit.n_inputs or a.shape[2] != n + 1:

@@ -12,6 +12,14 @@
       sgfhe_bootstrap_lut_batch beside sgfhe_bootstrap_batch at the same batch on one ctx, alternating (the order swaps
       every round): the k-loop is the same, the difference is k_final_lut against k_final and the staging of one input
       instead of two.
+  python tools/lut_bench.py --tables 1 8 64 256 [--batch 4096] [--reps 3]
+      LUT families: sgfhe_bootstrap_lut_multi_batch with T tables per row beside sgfhe_bootstrap_lut_batch at the same
+      batch on one ctx, alternating as --rate does.  The k-loop is the same; the difference is k_final_lut_multi, which
+      writes T times the rows, and their way to the host.  The batch is cut (to a multiple of 8) where the result of the
+      family call would exceed --max-gib.
+  python tools/lut_bench.py --family-noise [--instances 256]
+      The circuit of --noise with each level as LUT families (Circuit.lut_multi) through the noise probe: max |e| of the
+      family wires that have a slot, two levels deep, in both flatten modes.
 """
 
 import argparse
@@ -170,6 +178,76 @@ def rate(args):
     eng.close()
 
 
+def tables_rate(args):
+    import sgfhe_jl_amd as S
+    params = S.Params(1024)
+    n, r = params.n, params.r
+    rng = np.random.default_rng(21)
+    eng = S.Engine(params)
+    eng.generate_key(rng.integers(0, 2, size=n).astype(np.uint64), 22)
+    print("build %s, Params(1024), deterministic flatten" % eng.build_id())
+    for T in args.tables:
+        fit = int(args.max_gib * 2 ** 30) // (T * 3 * (n + 1) * 8)
+        B = min(args.batch, max(8, fit // 8 * 8))
+        a = rng.integers(0, r, size=(B, n), dtype=np.uint64)
+        b = rng.integers(0, r, size=B, dtype=np.uint64)
+        t = rng.integers(0, 256, size=(B, T)).astype(np.uint8)
+        eng.bootstrap_lut_batch(a[:256], b[:256], t[:256, 0])
+        eng.bootstrap_lut_multi_batch(a[:256], b[:256], t[:256])
+        for rep in range(args.reps):
+            res = {}
+            for what in (("single", "multi") if rep % 2 == 0 else ("multi", "single")):
+                t0 = time.perf_counter()
+                if what == "single":
+                    eng.bootstrap_lut_batch(a, b, t[:, 0])
+                else:
+                    eng.bootstrap_lut_multi_batch(a, b, t)
+                res[what] = time.perf_counter() - t0
+            print("  T = %3d, batch %4d, rep %d: bootstrap_lut_batch %.3f s = %.0f /s | bootstrap_lut_multi_batch %.3f s = "
+                  "%.0f rows/s = %.0f tables/s | time ratio %.3f"
+                  % (T, B, rep, res["single"], B / res["single"], res["multi"], B / res["multi"], B * T / res["multi"],
+                     res["multi"] / res["single"]))
+    eng.close()
+
+
+def family_noise(args):
+    import sgfhe_jl_amd as S
+    from sgfhe_jl_amd import circuit as C
+    params = S.Params(1024)
+    n, Dr = params.n, params.r // 4
+    inst = args.instances
+    rng = np.random.default_rng(11)
+    sk = rng.integers(0, 2, size=n).astype(np.uint64)
+    eng = S.Engine(params)
+    eng.generate_key(sk, 12)
+    bits = rng.integers(0, 2, size=(3, inst))
+    fresh = encrypt(params, sk, bits, Dr // 16, rng).reshape(3, inst, n + 1)
+    c = S.Circuit(3)
+    f = [c.fan(c.refresh(w)) for w in c.inputs]
+    n1 = c.lut_multi(TABLES1, f[0][2], f[1][1], f[2][0])
+    n2 = c.lut_multi(TABLES2, n1[0][2], n1[1][1], n1[2][0]) + c.lut_multi(TABLES2, n1[3][2], n1[4][1], n1[5][0])
+    c.output(*[w[0] for w in n2])
+    print("build %s, Params(1024): Dr = %d, %d instances; %d bootstraps per instance in %d levels (%d with one LUT node "
+          "per table)" % (eng.build_id(), Dr, inst, c.info()["nodes"], c.info()["levels"],
+                          c.info()["nodes"] + len(TABLES1) - 1 + 2 * (len(TABLES2) - 1)))
+    for rnd in (False, True):
+        eng.set_random_flatten(rnd, 13)
+        out, stats = eng.circuit_probe(c, fresh, sk, bits.astype(np.uint8))
+        assert np.all(np.abs(errors(params, sk, out, c.evaluate_plain(bits), 0)) < Dr // 2)
+        rep = C.noise_report(c, stats)
+        assert all(d["wrong"] == 0 for d in rep)
+        by = {}
+        for d in rep:
+            if d["node"] is not None and c.kind(d["node"]) == "sibling":
+                key = (d["level"], d["kind"])
+                by[key] = max(by.get(key, 0), d["max_abs"])
+        print("  %s flatten, sibling wires with a slot: %s; rows past a quarter of their codeword: %d"
+              % ("randomised" if rnd else "deterministic",
+                 ", ".join("level %d %s %d" % (k[0], k[1], v) for k, v in sorted(by.items())),
+                 sum(d["margin"] for d in rep if d["kind"] != "input")))
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--noise", action="store_true")
@@ -177,13 +255,20 @@ def main():
     ap.add_argument("--instances", type=int, default=256)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--tables", type=int, nargs="+")
+    ap.add_argument("--max-gib", type=float, default=2.0)
+    ap.add_argument("--family-noise", action="store_true")
     args = ap.parse_args()
     if args.noise:
         noise(args)
     if args.rate:
         rate(args)
-    if not (args.noise or args.rate):
-        ap.error("--noise or --rate")
+    if args.tables:
+        tables_rate(args)
+    if args.family_noise:
+        family_noise(args)
+    if not (args.noise or args.rate or args.tables or args.family_noise):
+        ap.error("--noise, --rate, --tables or --family-noise")
 
 
 if __name__ == "__main__":

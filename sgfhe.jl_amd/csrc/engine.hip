@@ -24,6 +24,7 @@
 #include "host_plumbing.h"
 #include "coalescer.h"
 #include "circuit.h"
+#include "chunking.h"
 
 using namespace sgfhe;
 
@@ -726,29 +727,14 @@ int32_t launch_crt(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, uint32_t cnt, uint32_
 
 // ---- buffers ------------------------------------------------------------------------------------
 
-uint32_t round_up8(uint32_t x) { return (x + 7u) & ~7u; }
-
 size_t per_bootstrap_bytes(const sgfhe_ctx *c) {
     return (size_t)2 * c->M * sizeof(ulonglong2) + (size_t)2 * cur(c).npr * c->M * 4 + (size_t)c->n * 4;
 }
 
-// Default chunk: the per-iteration working set (digits + residues) of a chunk stays near the size
-// of the 256 MiB Infinity Cache while a launch is long enough to amortise its ramp-up and drain
-// (about 9 us per k_extprod launch).  Measured at Params(1024) (tools/chunk_sweep.py, us of
-// k_extprod per bootstrap and iteration): chunk 256 0.568, 408 0.553, 512 0.547, 608 0.572,
-// 816 0.575.
-uint32_t default_chunk(const sgfhe_ctx *c) {
-    // Two lanes (the default): half the budget per lane, so that the working sets of both chunks
-    // stay near the Infinity Cache together.  Measured at Params(1024) with k_crt_lean
-    // (profiles/r03_exp_lanes_sweep.txt): two lanes of 128 / 192 / 256 / 320 / 384 give
-    // 1892 / 1916 / 1907 / 1825 / 1814 bootstraps/s against 1864 for one lane of 512.
-    size_t budget = (size_t)(c->lanes == 2 ? 160 : 320) << 20;
-    size_t k = budget / per_bootstrap_bytes(c);
-    if (k >= 256) k = (k / 256) * 256;
-    else k = (k / 8) * 8;
-    if (k < 8) k = 8;
-    if (k > 4096) k = 4096;
-    return (uint32_t)k;
+// what the chunk policy (chunking.h) reads of the ctx, for calls at flatten mode `mode`
+ChunkPolicy chunk_policy(const sgfhe_ctx *c, uint32_t mode) {
+    return {c->chunk, default_chunk(c->lanes, per_bootstrap_bytes(c)), c->lanes, c->small_max, c->small_lanes,
+            c->small_lanes_max, c->logm, fused_cap(c, mode)};
 }
 
 void free_lanes(sgfhe_ctx *c) {
@@ -880,6 +866,28 @@ void host_copy(void *dst, const void *src, size_t bytes) {
     for (size_t i = 0; i < nth; i++) th[i].join();
 }
 
+// [a1 | a2 | b1 | b2 | res]: the bootstrap inputs of `rows` rows (a: n words, b: one) carved out of `base`, and what
+// follows them (the result rows, where the buffer holds them)
+struct Staging {
+    uint64_t *a1, *a2, *b1, *b2, *res;
+    Staging from_row(size_t off, size_t n) const { return {a1 + off * n, a2 + off * n, b1 + off, b2 + off, res}; }
+};
+Staging staging(uint64_t *base, size_t rows, size_t n) {
+    uint64_t *a2 = base + rows * n, *b1 = a2 + rows * n;
+    return {base, a2, b1, b1 + rows, b1 + 2 * rows};
+}
+
+// The bootstrap inputs of a call or of a chunk as the kernels read them, on the device: a Staging's rows, or four
+// arrays of the caller's.
+struct BootRows {
+    const uint64_t *a1 = nullptr, *a2 = nullptr, *b1 = nullptr, *b2 = nullptr;
+    BootRows() = default;
+    BootRows(const uint64_t *a1_, const uint64_t *a2_, const uint64_t *b1_, const uint64_t *b2_)
+        : a1(a1_), a2(a2_), b1(b1_), b2(b2_) {}
+    BootRows(const Staging &S) : a1(S.a1), a2(S.a2), b1(S.b1), b2(S.b2) {}
+    BootRows from_row(size_t off, size_t n) const { return {a1 + off * n, a2 + off * n, b1 + off, b2 + off}; }
+};
+
 // Host buffers of sgfhe_bootstrap_batch, moved chunk by chunk beside the lanes' kernels (stream_io):
 // a chunk's inputs go up while the chunks before it compute, its outputs come down while the chunks
 // after it compute, and the CPU copies between the caller's (pageable) arrays and the page-locked
@@ -893,6 +901,138 @@ struct HostPipe {
     uint64_t *p_in, *p_out;               // page-locked mirrors of both, same layouts
     size_t out_row_words;                 // 3 (n + 1), twice that with SGFHE_FLAG_RAW_MODQ
     bool dbg;                             // SGFHE_DEBUG_IO is set (read once per call, bootstrap_host)
+};
+
+// One call's run of that pipeline (bootstrap_device): where the rows of every chunk lie on the device, the events of
+// the copies, the results on their way to the caller's array, and the SGFHE_DEBUG_IO phase clock.  Without a HostPipe
+// (rows and results are the caller's device arrays) every step does nothing.  The only place that knows the
+// [a1 | a2 | b1 | b2] layout of the mirrors.
+// A host-pointer call that is one group of chunks (a handful of gates up to two chunks' worth) has nothing to overlap
+// its copies with: they go on the call's stream itself, in order with the kernels -- one upload before the first
+// kernel, one download behind the last -- without the copy streams' events (`single`).
+// (Round 4 also measured collecting the results only at the end, all results after the last kernel, and all inputs
+// before the first kernel; this pipeline measured best, 1.003 x the device-resident call:
+// profiles/r04_exp_io_variants.txt.)
+struct PipeRun {
+    sgfhe_ctx *const c;
+    const HostPipe *const hp;
+    const size_t batch, n;
+    const bool single, dbg;
+    size_t ev_next = 0;   // events of the host pipeline, from the ctx's pool
+    struct OutJob { hipEvent_t done; size_t c0; uint32_t cb; };
+    std::vector<OutJob> outq;   // result rows on their way to the page-locked mirror
+    size_t out_drained = 0;
+    double tw0 = 0.0, tw_first = 0.0, tw_wait = 0.0;   // SGFHE_DEBUG_IO=1: wall-clock phases of a pipelined call
+
+    PipeRun(sgfhe_ctx *c_, const HostPipe *hp_, size_t batch_, size_t stride)
+        : c(c_), hp(hp_), batch(batch_), n(c_->n), single(hp_ && batch_ <= stride), dbg(hp_ && hp_->dbg) {}
+
+    // rows [c0, c0 + cb) of the caller's a1, a2, b1, b2 into the page-locked mirror, laid out
+    // [a1 | a2 | b1 | b2] from word c0 (2 n + 2); returns where they start
+    uint64_t *stage_in(size_t c0, size_t cb) const {
+        uint64_t *pi = hp->p_in + c0 * (2 * n + 2);
+        const Staging P = staging(pi, cb, n);
+        host_copy(P.a1, hp->a1 + c0 * n, cb * n * 8);
+        host_copy(P.a2, hp->a2 + c0 * n, cb * n * 8);
+        memcpy(P.b1, hp->b1 + c0, cb * 8);
+        memcpy(P.b2, hp->b2 + c0, cb * 8);
+        return pi;
+    }
+    int32_t next_event(hipEvent_t *e) {
+        if (ev_next == c->ev_pool.size()) {
+            hipEvent_t ne = nullptr;
+            HIPCHK(c, hipEventCreateWithFlags(&ne, hipEventDisableTiming));
+            c->ev_pool.push_back(ne);
+        }
+        *e = c->ev_pool[ev_next++];
+        return SGFHE_OK;
+    }
+    // a single-group call: all its rows up, on `st`
+    int32_t upload_call(hipStream_t st) const {
+        if (!single) return SGFHE_OK;
+        stage_in(0, batch);
+        HIPCHK(c, hipMemcpyAsync(hp->d_in, hp->p_in, batch * (2 * n + 2) * 8, hipMemcpyHostToDevice, st));
+        return SGFHE_OK;
+    }
+    // R, the call's device rows, becomes the chunk's: rows J.c0 ... of the call's own arrays or of the whole-call
+    // upload, or this chunk's inputs on their way caller's arrays -> page-locked mirror -> device on stream_io,
+    // which the chunk's stream then waits for
+    int32_t chunk_in(const ChunkJob &J, BootRows &R) {
+        if (!hp) { R = R.from_row(J.c0, n); return SGFHE_OK; }
+        if (single) { R = BootRows(staging(hp->d_in, batch, n)).from_row(J.c0, n); return SGFHE_OK; }
+        if (dbg && J.c0 == 0) tw0 = wall_ms();
+        const size_t cb = J.cb;
+        uint64_t *pi = stage_in(J.c0, cb), *di = hp->d_in + J.c0 * (2 * n + 2);
+        HIPCHK(c, hipMemcpyAsync(di, pi, cb * (2 * n + 2) * 8, hipMemcpyHostToDevice, c->stream_io));
+        hipEvent_t ein;
+        int32_t rc = next_event(&ein);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(ein, c->stream_io));
+        HIPCHK(c, hipStreamWaitEvent(J.st, ein, 0));
+        R = staging(di, cb, n);
+        return SGFHE_OK;
+    }
+    void first_group_queued(size_t g0) {
+        if (dbg && g0 == 0) tw_first = wall_ms();
+    }
+    // this chunk's results: device -> page-locked mirror on stream_io2, behind its last kernel
+    // (a single-group call: one download behind the join, finish())
+    int32_t chunk_out(const ChunkJob &J) {
+        if (!hp || single) return SGFHE_OK;
+        hipEvent_t ek, eo;
+        int32_t rc;
+        if ((rc = next_event(&ek)) || (rc = next_event(&eo))) return rc;
+        HIPCHK(c, hipEventRecord(ek, J.st));
+        HIPCHK(c, hipStreamWaitEvent(c->stream_io2, ek, 0));
+        const size_t w0 = J.c0 * hp->out_row_words;
+        HIPCHK(c, hipMemcpyAsync(hp->p_out + w0, hp->d_out + w0, (size_t)J.cb * hp->out_row_words * 8,
+                                 hipMemcpyDeviceToHost, c->stream_io2));
+        HIPCHK(c, hipEventRecord(eo, c->stream_io2));
+        outq.push_back({eo, J.c0, J.cb});
+        return SGFHE_OK;
+    }
+    // the first `upto` results queued: from the page-locked mirror into the caller's array
+    int32_t drain_out(size_t upto) {
+        for (; out_drained < upto; out_drained++) {
+            const OutJob &o = outq[out_drained];
+            HIPCHK(c, hipEventSynchronize(o.done));
+            host_copy(hp->out + o.c0 * hp->out_row_words, hp->p_out + o.c0 * hp->out_row_words,
+                      (size_t)o.cb * hp->out_row_words * 8);
+        }
+        return SGFHE_OK;
+    }
+    // with a group of `njobs` chunks queued, collect the results of the groups before it
+    int32_t collect_earlier(int njobs) {
+        if (!hp || single) return SGFHE_OK;
+        const double t = dbg ? wall_ms() : 0.0;
+        const int32_t rc = drain_out(outq.size() - (size_t)njobs);
+        if (dbg) tw_wait += wall_ms() - t;
+        return rc;
+    }
+    // behind the call's last work on `st`: the single-group download, or the results still on their way
+    int32_t finish(hipStream_t st) {
+        if (!hp) return SGFHE_OK;
+        if (single) {
+            HIPCHK(c, hipMemcpyAsync(hp->p_out, hp->d_out, batch * hp->out_row_words * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            c->pending = false;
+            host_copy(hp->out, hp->p_out, batch * hp->out_row_words * 8);
+            return SGFHE_OK;
+        }
+        const double t1 = dbg ? wall_ms() : 0.0;
+        double t2 = 0.0;
+        if (dbg && !outq.empty()) {   // the last chunks' kernels are done when their download may start
+            (void)hipEventSynchronize(c->ev_done);
+            t2 = wall_ms();
+        }
+        const int32_t rc = drain_out(outq.size());
+        if (rc) return rc;
+        if (dbg)
+            fprintf(stderr, "[sgfhe io] pipelined call of %zu: first chunks staged and queued after %.2f ms, all queued after "
+                    "%.2f ms (of which %.2f waiting for earlier results), last kernel done at %.2f, results in the "
+                    "caller's array at %.2f\n", batch, tw_first - tw0, t1 - tw0, tw_wait, t2 - tw0, wall_ms() - tw0);
+        return SGFHE_OK;
+    }
 };
 
 // The LUT rows of a call (sgfhe_bootstrap_lut_batch): `rows` is a device array of one word per row of the call,
@@ -913,70 +1053,116 @@ struct LutDesc {
     LutTables fam = {};
 };
 
-int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, const uint64_t *a2,
-                         const uint64_t *b2, size_t batch, uint64_t *out, uint32_t flags,
-                         uint64_t n_iters, ulonglong2 *acc_out, hipStream_t st,
-                         uint64_t *dig_out = nullptr, const HostPipe *hp = nullptr, const LutDesc *lut = nullptr) {
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    uint32_t chunk = c->chunk ? c->chunk : default_chunk(c);
-    const uint32_t mode = flatten_mode(c);
-    CrtConst *const d_crt = cur(c).d_crt;
-    if (!c->chunk && c->lanes == 2 && batch > 2 * (size_t)c->small_max) {
-        // Automatic chunk size with two lanes: cut the batch into an even number of equal chunks no
-        // larger than the default, so that both lanes are busy from the first bootstrap to the last
-        // (a batch of 256 runs as 128 + 128 instead of one chunk on one lane, 384 as 192 + 192
-        // instead of 256 + 128).  Measured at Params(1024) (profiles/r03_exp_mid_batches.txt):
-        // 64 / 128 / 256 / 384 / 640 bootstraps 1158 -> 1401, 1555 -> 1858, 1875 -> 1981, 1847 -> 2071,
-        // 1850 -> 2030 per second.  Halves that would fall to the small-batch form (batch <= 48) are not
-        // split: 48 bootstraps run at 1277 per second as one chunk and at 1024 as 24 + 24.
-        const size_t pairs = (batch + 2 * (size_t)chunk - 1) / (2 * (size_t)chunk);
-        chunk = round_up8((uint32_t)((batch + 2 * pairs - 1) / (2 * pairs)));
-    } else if (!c->chunk && c->lanes == 2 && c->small_lanes && c->logm >= 12 &&
-               batch >= (fused_cap(c, mode) ? fused_cap(c, mode) + 1 : 8u) &&
-               batch <= c->small_lanes_max && (batch + 1) / 2 <= c->small_max) {
-        // A call of 8 to 24 gates in the latency form: two halves on the two lanes.  Each half is a chain of
-        // dependent launches on a mostly idle device, and two chains overlap; the halves need no rounding
-        // to 8 (the latency kernels index their gates directly), so 8 gates run as 4 + 4 and 12 as 6 + 6
-        // in the quarter form.  Same call (profiles/r04_exp_small_lanes.txt): 8 / 10 / 12 / 16 / 20 / 24 gates
-        // 20.8 / 21.6 / 22.8 / 27.4 / 27.8 / 29.7 ms against 23.4 / 25.2 / 27.0 / 27.8 / 30.5 / 31.4 as one chunk;
-        // below 8 gates two chains cost more than they overlap (2 / 4 / 6 gates 18.3 / 18.3 / 19.0 against
-        // 15.8 / 17.8 / 19.8), so those stay on one stream.
-        // With the fused quarter kernel (m = 4096, 8192) one chain takes up to 12 gates at the cost of two
-        // chains of half the size or less (8 / 10 / 12 gates 20.9 / 21.9 / 22.7 ms against 21.0 / 22.0 / 22.9;
-        // Params(512) 7.7 / 8.0 / 8.3 against 9.1 / 9.0 / 9.2), and the halves of 13 to 24 gates take it
-        // (profiles/r04_exp_fused.txt): two chains from 13 gates there.
-        // Rings below m = 4096 stay on one chain: their launches are too short for two chains to overlap, and
-        // the halves then cost their sum (Params(64) / (128) / (256), 8 to 24 gates: 1.4 / 2.75 / 5.4 ms as two
-        // halves against 0.7 / 1.4 / 3.3 as one chunk, profiles/r04_exp_small_rings_lanes.txt).
-        chunk = (uint32_t)((batch + 1) / 2);
+// One call of bootstrap_device.  A call site sets the fields it uses; the others keep what the constructor gives them.
+struct BootCall {
+    BootRows rows;                   // the inputs on the device (none with `pipe`, which brings them)
+    size_t batch = 0;
+    uint64_t *out = nullptr;         // device result rows [batch][3][n + 1], of 16-byte residues with SGFHE_FLAG_RAW_MODQ
+    uint32_t flags = 0;
+    uint64_t n_iters;                // iterations of the k-loop: the ctx's n, fewer for the debug entries
+    hipStream_t st;                  // the stream the call is queued on: the ctx's own, or a caller's
+    ulonglong2 *acc_out = nullptr;   // debug taps: the accumulators and the digits of every row after the k-loop
+    uint64_t *dig_out = nullptr;
+    const HostPipe *pipe = nullptr;  // a host-pointer call: inputs and results pipelined beside the kernels
+    const LutDesc *lut = nullptr;    // a call with LUT rows
+    explicit BootCall(const sgfhe_ctx *c) : n_iters(c->n), st(c->stream) {}
+};
+
+// The call number of the draw stream: this ctx's counter -- unless the call was numbered when it was handed
+// to the coalescer, or is a gathered call, whose rows carry their own numbers: kernels.h RndRow.
+uint32_t next_call_number(sgfhe_ctx *c) {
+    if (!c->rnd || c->gather_rows) return 0u;
+    if (c->call_fixed >= 0) {
+        const uint32_t call = (uint32_t)c->call_fixed;
+        c->call_fixed = -1;
+        return call;
     }
-    const uint32_t n = c->n, M = c->M;
-    const bool raw = flags & SGFHE_FLAG_RAW_MODQ;
-    if (flags & SGFHE_FLAG_RAW_RNS2) {
-        if (!raw) return fail(c, SGFHE_ERR_INVALID_ARG, "SGFHE_FLAG_RAW_RNS2 needs SGFHE_FLAG_RAW_MODQ");
+    return c->rnd_call++;
+}
+
+// Chunk entry: accumulators, first digits and rotation amounts of the chunk from its rows R.
+int32_t chunk_entry(sgfhe_ctx *c, const ChunkJob &J, const BootRows &R, const LutDesc *lut, uint32_t mode) {
+    const uint32_t tot = J.cpad * c->M;
+    const uint32_t *jlut = lut ? lut->rows + J.c0 : nullptr;
+    with_bool(J.ra.rows != nullptr, [&](auto rows) {
+        hipLaunchKernelGGL(k_init<decltype(rows)::value>, dim3((tot + 255) / 256), dim3(256), 0, J.st, R.a1, R.b1, R.a2,
+                           R.b2, J.L->dig, J.L->ua, cur(c).d_crt, J.cb, J.cpad, c->n, (uint32_t)c->logm, mode, J.ra, jlut);
+    });
+    HIPCHK(c, hipGetLastError());
+    return SGFHE_OK;
+}
+
+// Chunk exit: what leaves the chunk's accumulators behind the k-loop -- the debug taps, then the result rows
+// through the kernel their kind takes (LutDesc).
+int32_t chunk_exit(sgfhe_ctx *c, const ChunkJob &J, const BootCall &call, uint32_t mode) {
+    const uint32_t n = c->n, M = c->M, logm = (uint32_t)c->logm;
+    CrtConst *const d_crt = cur(c).d_crt;
+    const dim3 block(256);
+    if (call.acc_out) {
+        const uint32_t t2 = J.cb * 2 * M;
+        hipLaunchKernelGGL(k_dump_acc, dim3((t2 + 255) / 256), block, 0, J.st, J.L->dig, call.acc_out + J.c0 * 2 * M,
+                           d_crt, t2, logm, mode);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (call.dig_out) {
+        const uint32_t t2 = J.cb * 2 * M;
+        hipLaunchKernelGGL(k_dump_digits, dim3((t2 + 255) / 256), block, 0, J.st, J.L->dig, call.dig_out + J.c0 * 4 * M,
+                           t2, logm, mode);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (!call.out) return SGFHE_OK;
+    const LutDesc *lut = call.lut;
+    const bool raw = call.flags & SGFHE_FLAG_RAW_MODQ;
+    const uint32_t t3 = J.cb * (n + 1), rawk = raw ? 1u : 0u;
+    const dim3 grid((t3 + 255) / 256);
+    const size_t row_words = (size_t)3 * (n + 1) * (raw ? 2 : 1);
+    uint64_t *const out = call.out + J.c0 * row_words;   // the chunk's rows, one result each
+    if (!lut || !lut->all)
+        hipLaunchKernelGGL(k_final, grid, block, 0, J.st, J.L->dig, out, d_crt, J.cb, n, logm, rawk, mode);
+    if (lut && lut->tables) {   // a family call: every table of every row of the chunk, n_tables results to a row
+        LutTables T = {};
+        T.tables = lut->tables + J.c0 * lut->n_tables;
+        T.n_tables = lut->n_tables;
+        hipLaunchKernelGGL(k_final_lut_multi<false>, grid, block, 0, J.st, J.L->dig,
+                           call.out + J.c0 * lut->n_tables * row_words, d_crt, T, J.cb, n, logm, rawk, mode);
+    } else if (lut && lut->wires) {   // the siblings of the chunk's LUT nodes, into the wire table
+        LutTables T = lut->fam;
+        T.row0 += (uint32_t)J.c0;
+        hipLaunchKernelGGL(k_final_lut_multi<true>, grid, block, 0, J.st, J.L->dig, lut->wires, d_crt, T, J.cb, n, logm,
+                           0u, mode);
+    }
+    if (lut && !lut->tables)   // the LUT rows of the chunk, over what k_final wrote for them
+        hipLaunchKernelGGL(k_final_lut, grid, block, 0, J.st, J.L->dig, out, d_crt, lut->rows + J.c0, J.cb, n, logm, rawk,
+                           mode);
+    if (raw && (call.flags & SGFHE_FLAG_RAW_RNS2))  // residues leave as (v1, v2) pairs (rns.jl:16-18)
+        hipLaunchKernelGGL(k_canon_to_rns2, dim3((3 * t3 + 255) / 256), block, 0, J.st,
+                           reinterpret_cast<ulonglong2 *>(call.out) + J.c0 * 3 * (n + 1), (size_t)3 * t3, c->rns2);
+    HIPCHK(c, hipGetLastError());
+    return SGFHE_OK;
+}
+
+// Every bootstrap goes through here: `call.batch` gate bootstraps, cut into chunks across the lanes (chunking.h),
+// queued on call.st.  Reads top to bottom as the stream operations of a call.
+int32_t bootstrap_device(sgfhe_ctx *c, const BootCall &call) {
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    const size_t batch = call.batch;
+    const hipStream_t st = call.st;
+    const uint32_t mode = flatten_mode(c);
+    const CallChunks cut = call_chunks(chunk_policy(c, mode), batch);
+    if (call.flags & SGFHE_FLAG_RAW_RNS2) {
+        if (!(call.flags & SGFHE_FLAG_RAW_MODQ))
+            return fail(c, SGFHE_ERR_INVALID_ARG, "SGFHE_FLAG_RAW_RNS2 needs SGFHE_FLAG_RAW_MODQ");
         if (!c->have_rns2)
             return fail(c, SGFHE_ERR_INVALID_ARG, "SGFHE_FLAG_RAW_RNS2: no RNS2 moduli (upload the key with sgfhe_bkey_upload_rns2)");
     }
-    const bool two_lanes = c->lanes == 2 && batch > chunk;
-    // (the call number of the draw stream: this ctx's counter -- unless the call was numbered when it was handed
-    //  to the coalescer, or is a gathered call, whose rows carry their own numbers: kernels.h RndRow)
-    uint32_t call = 0u;
-    if (c->rnd) {
-        if (c->gather_rows) call = 0u;
-        else if (c->call_fixed >= 0) { call = (uint32_t)c->call_fixed; c->call_fixed = -1; }
-        else call = c->rnd_call++;
-    }
-    c->last_call = call;
-    {   // work buffers for the largest chunk of this call, before anything of it is queued
-        const uint32_t first = (uint32_t)(batch < chunk ? batch : chunk);
-        int32_t rc = ensure_work(c, round_up8(first));
-        if (rc) return rc;
-        c->last_chunk = round_up8(first);
-    }
-    {   // after everything earlier calls queued on this ctx, whatever their streams
-        int32_t rc = fence_begin(c, st);
-        if (rc) return rc;
-    }
+    const uint32_t callno = next_call_number(c);
+    c->last_call = callno;
+    int32_t rc;
+    // work buffers for the largest chunk of this call, before anything of it is queued
+    if ((rc = ensure_work(c, chunk_rows(cut, batch)))) return rc;
+    c->last_chunk = chunk_rows(cut, batch);
+    // after everything earlier calls queued on this ctx, whatever their streams
+    if ((rc = fence_begin(c, st))) return rc;
     // From here on work is queued: should a later step fail, whatever has been queued still ends in
     // ev_done, so that the next call (or the destructor) waits for it before touching the buffers.
     struct QueuedWork {
@@ -997,169 +1183,39 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
         HIPCHK(c, hipEventCreate(&ecall1));
         HIPCHK(c, hipEventRecord(ecall0, st));
     }
-    // A host-pointer call that is one group of chunks (a handful of gates up to two chunks' worth) has
-    // nothing to overlap its copies with: they go on `st` itself, in order with the kernels -- one upload
-    // before the first kernel, one download behind the last -- without the copy streams' events.
-    const size_t stride = (size_t)chunk * (two_lanes ? 2 : 1);
-    const bool hp_single = hp && batch <= stride;
-    // rows [c0, c0 + cb) of the caller's a1, a2, b1, b2 into the page-locked mirror, laid out
-    // [a1 | a2 | b1 | b2] from word c0 (2 n + 2); returns where they start
-    auto stage_in = [&](size_t c0, size_t cb) -> uint64_t * {
-        uint64_t *pi = hp->p_in + c0 * (2 * (size_t)n + 2);
-        host_copy(pi, hp->a1 + c0 * n, cb * n * 8);
-        host_copy(pi + cb * n, hp->a2 + c0 * n, cb * n * 8);
-        memcpy(pi + 2 * cb * n, hp->b1 + c0, cb * 8);
-        memcpy(pi + 2 * cb * n + cb, hp->b2 + c0, cb * 8);
-        return pi;
-    };
-    if (hp_single) {
-        stage_in(0, batch);
-        HIPCHK(c, hipMemcpyAsync(hp->d_in, hp->p_in, batch * (2 * (size_t)n + 2) * 8, hipMemcpyHostToDevice, st));
-    }
-    if (two_lanes) {  // fork: the second lane starts after everything already queued on st
+    PipeRun io(c, call.pipe, batch, cut.stride);
+    if ((rc = io.upload_call(st))) return rc;
+    if (cut.two_lanes) {  // fork: the second lane starts after everything already queued on st
         HIPCHK(c, hipEventRecord(c->ev_fork, st));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     }
-    // events of the host pipeline, from the ctx's pool
-    size_t ev_next = 0;
-    auto next_event = [&](hipEvent_t *e) -> hipError_t {
-        if (ev_next == c->ev_pool.size()) {
-            hipEvent_t ne = nullptr;
-            const hipError_t er = hipEventCreateWithFlags(&ne, hipEventDisableTiming);
-            if (er != hipSuccess) return er;
-            c->ev_pool.push_back(ne);
-        }
-        *e = c->ev_pool[ev_next++];
-        return hipSuccess;
-    };
-    struct OutJob { hipEvent_t done; size_t c0; uint32_t cb; };
-    std::vector<OutJob> outq;   // result rows on their way to the page-locked mirror
-    size_t out_drained = 0;
-    auto drain_out = [&](size_t upto) -> hipError_t {   // ... and from there into the caller's array
-        for (; out_drained < upto; out_drained++) {
-            const OutJob &o = outq[out_drained];
-            const hipError_t er = hipEventSynchronize(o.done);
-            if (er != hipSuccess) return er;
-            host_copy(hp->out + o.c0 * hp->out_row_words, hp->p_out + o.c0 * hp->out_row_words,
-                      (size_t)o.cb * hp->out_row_words * 8);
-        }
-        return hipSuccess;
-    };
-    // SGFHE_DEBUG_IO=1: wall-clock phases of a pipelined host-pointer call
-    const bool dbg_io = hp && hp->dbg;
-    // (Round 4 also measured collecting the results only at the end, all results after the last kernel,
-    // and all inputs before the first kernel; this pipeline measured best, 1.003 x the device-resident
-    // call: profiles/r04_exp_io_variants.txt.)
-    const double tw0 = dbg_io ? wall_ms() : 0.0;
-    double tw_first = 0.0, tw_wait = 0.0;
-    for (size_t g0 = 0; g0 < batch; g0 += stride) {
+    for (size_t g0 = 0; g0 < batch; g0 += cut.stride) {   // a group: one chunk per lane in use
         ChunkJob jobs[2];
         int njobs = 0;
-        const size_t out_before = outq.size();
-        for (int li = 0; li < (two_lanes ? 2 : 1); li++) {
-            const size_t c0 = g0 + (size_t)li * chunk;
+        for (int li = 0; li < (cut.two_lanes ? 2 : 1); li++) {
+            const size_t c0 = g0 + (size_t)li * cut.chunk;
             if (c0 >= batch) break;
             ChunkJob &J = jobs[njobs++];
             J.L = &c->lane[li];
             J.st = li ? c->stream2 : st;
-            J.cb = (uint32_t)((batch - c0 < chunk) ? batch - c0 : chunk);
+            J.cb = (uint32_t)((batch - c0 < cut.chunk) ? batch - c0 : cut.chunk);
             J.cpad = round_up8(J.cb);
             J.c0 = c0;
-            J.ra = RndArgs{c->rnd_key, call, (uint32_t)c0, c->gather_rows};
+            J.ra = RndArgs{c->rnd_key, callno, (uint32_t)c0, c->gather_rows};
             J.sampled = li == 0 && J.cpad == c->last_chunk;
-            const uint64_t *ja1 = a1 + c0 * n, *jb1 = b1 + c0, *ja2 = a2 + c0 * n, *jb2 = b2 + c0;
-            if (hp_single) {   // whole-call layout [a1 | a2 | b1 | b2], uploaded above
-                ja1 = hp->d_in + c0 * n; ja2 = hp->d_in + (batch + c0) * n;
-                jb1 = hp->d_in + 2 * batch * n + c0; jb2 = jb1 + batch;
-            } else if (hp) {   // this chunk's inputs: caller's arrays -> page-locked mirror -> device, on stream_io
-                const size_t cb = J.cb;
-                uint64_t *pi = stage_in(c0, cb), *di = hp->d_in + c0 * (2 * (size_t)n + 2);
-                HIPCHK(c, hipMemcpyAsync(di, pi, cb * (2 * (size_t)n + 2) * 8, hipMemcpyHostToDevice, c->stream_io));
-                hipEvent_t ein;
-                HIPCHK(c, next_event(&ein));
-                HIPCHK(c, hipEventRecord(ein, c->stream_io));
-                HIPCHK(c, hipStreamWaitEvent(J.st, ein, 0));
-                ja1 = di; ja2 = di + cb * n; jb1 = di + 2 * cb * n; jb2 = jb1 + cb;
-            }
-            const uint32_t tot = J.cpad * M;
-            const uint32_t *jlut = lut ? lut->rows + c0 : nullptr;
-            if (J.ra.rows)
-                hipLaunchKernelGGL(k_init<true>, dim3((tot + 255) / 256), dim3(256), 0, J.st, ja1, jb1, ja2, jb2,
-                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra, jlut);
-            else
-                hipLaunchKernelGGL(k_init<false>, dim3((tot + 255) / 256), dim3(256), 0, J.st, ja1, jb1, ja2, jb2,
-                                   J.L->dig, J.L->ua, d_crt, J.cb, J.cpad, n, (uint32_t)c->logm, mode, J.ra, jlut);
-            HIPCHK(c, hipGetLastError());
+            BootRows R = call.rows;
+            if ((rc = io.chunk_in(J, R))) return rc;
+            if ((rc = chunk_entry(c, J, R, call.lut, mode))) return rc;
         }
-        if (dbg_io && g0 == 0) tw_first = wall_ms();
-        int32_t rc = run_iterations(c, jobs, njobs, n_iters, mode);
-        if (rc) return rc;
+        io.first_group_queued(g0);
+        if ((rc = run_iterations(c, jobs, njobs, call.n_iters, mode))) return rc;
         for (int j = 0; j < njobs; j++) {
-            const ChunkJob &J = jobs[j];
-            if (acc_out) {
-                const uint32_t t2 = J.cb * 2 * M;
-                hipLaunchKernelGGL(k_dump_acc, dim3((t2 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                   acc_out + J.c0 * 2 * M, d_crt, t2, (uint32_t)c->logm, mode);
-                HIPCHK(c, hipGetLastError());
-            }
-            if (dig_out) {
-                const uint32_t t2 = J.cb * 2 * M;
-                hipLaunchKernelGGL(k_dump_digits, dim3((t2 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                   dig_out + J.c0 * 4 * M, t2, (uint32_t)c->logm, mode);
-                HIPCHK(c, hipGetLastError());
-            }
-            if (out) {
-                const uint32_t t3 = J.cb * (n + 1);
-                if (!lut || !lut->all)
-                    hipLaunchKernelGGL(k_final, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                       out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, J.cb, n,
-                                       (uint32_t)c->logm, raw ? 1u : 0u, mode);
-                if (lut && lut->tables) {   // a family call: every table of every row of the chunk
-                    LutTables T = {};
-                    T.tables = lut->tables + J.c0 * lut->n_tables;
-                    T.n_tables = lut->n_tables;
-                    hipLaunchKernelGGL(k_final_lut_multi<false>, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                       out + J.c0 * lut->n_tables * 3 * (n + 1) * (raw ? 2 : 1), d_crt, T, J.cb, n,
-                                       (uint32_t)c->logm, raw ? 1u : 0u, mode);
-                } else if (lut && lut->wires) {   // the siblings of the chunk's LUT nodes, into the wire table
-                    LutTables T = lut->fam;
-                    T.row0 += (uint32_t)J.c0;
-                    hipLaunchKernelGGL(k_final_lut_multi<true>, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                       lut->wires, d_crt, T, J.cb, n, (uint32_t)c->logm, 0u, mode);
-                }
-                if (lut && !lut->tables)   // the LUT rows of the chunk, over what k_final wrote for them
-                    hipLaunchKernelGGL(k_final_lut, dim3((t3 + 255) / 256), dim3(256), 0, J.st, J.L->dig,
-                                       out + J.c0 * 3 * (n + 1) * (raw ? 2 : 1), d_crt, lut->rows + J.c0, J.cb, n,
-                                       (uint32_t)c->logm, raw ? 1u : 0u, mode);
-                if (raw && (flags & SGFHE_FLAG_RAW_RNS2))  // residues leave as (v1, v2) pairs (rns.jl:16-18)
-                    hipLaunchKernelGGL(k_canon_to_rns2, dim3((3 * t3 + 255) / 256), dim3(256), 0, J.st,
-                                       reinterpret_cast<ulonglong2 *>(out) + J.c0 * 3 * (n + 1),
-                                       (size_t)3 * t3, c->rns2);
-                HIPCHK(c, hipGetLastError());
-            }
-            if (hp_single) {
-                // one download behind the join, below
-            } else if (hp) {   // this chunk's results: device -> page-locked mirror on stream_io2, behind its last kernel
-                hipEvent_t ek, eo;
-                HIPCHK(c, next_event(&ek));
-                HIPCHK(c, next_event(&eo));
-                HIPCHK(c, hipEventRecord(ek, J.st));
-                HIPCHK(c, hipStreamWaitEvent(c->stream_io2, ek, 0));
-                const size_t w0 = J.c0 * hp->out_row_words;
-                HIPCHK(c, hipMemcpyAsync(hp->p_out + w0, hp->d_out + w0, (size_t)J.cb * hp->out_row_words * 8,
-                                         hipMemcpyDeviceToHost, c->stream_io2));
-                HIPCHK(c, hipEventRecord(eo, c->stream_io2));
-                outq.push_back({eo, J.c0, J.cb});
-            }
+            if ((rc = chunk_exit(c, jobs[j], call, mode))) return rc;
+            if ((rc = io.chunk_out(jobs[j]))) return rc;
         }
-        // with this group queued, collect the results of the group before it
-        if (hp) {
-            const double t = dbg_io ? wall_ms() : 0.0;
-            HIPCHK(c, drain_out(out_before));
-            if (dbg_io) tw_wait += wall_ms() - t;
-        }
+        if ((rc = io.collect_earlier(njobs))) return rc;
     }
-    if (two_lanes) {  // join
+    if (cut.two_lanes) {  // join
         HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
     }
@@ -1167,32 +1223,9 @@ int32_t bootstrap_device(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, c
         HIPCHK(c, hipEventRecord(ecall1, st));
         c->ev_call.push_back({ecall0, ecall1, (uint64_t)batch});
     }
-    {
-        int32_t rc = fence_end(c, st);
-        if (rc) return rc;
-        queued.closed = true;
-    }
-    if (hp_single) {
-        HIPCHK(c, hipMemcpyAsync(hp->p_out, hp->d_out, batch * hp->out_row_words * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        c->pending = false;
-        host_copy(hp->out, hp->p_out, batch * hp->out_row_words * 8);
-        return SGFHE_OK;
-    }
-    if (hp) {
-        const double t1 = dbg_io ? wall_ms() : 0.0;
-        double t2 = 0.0;
-        if (dbg_io && !outq.empty()) {   // the last chunks' kernels are done when their download may start
-            (void)hipEventSynchronize(c->ev_done);
-            t2 = wall_ms();
-        }
-        HIPCHK(c, drain_out(outq.size()));
-        if (dbg_io)
-            fprintf(stderr, "[sgfhe io] pipelined call of %zu: first chunks staged and queued after %.2f ms, all queued after "
-                    "%.2f ms (of which %.2f waiting for earlier results), last kernel done at %.2f, results in the "
-                    "caller's array at %.2f\n", batch, tw_first - tw0, t1 - tw0, tw_wait, t2 - tw0, wall_ms() - tw0);
-    }
-    return SGFHE_OK;
+    if ((rc = fence_end(c, st))) return rc;
+    queued.closed = true;
+    return io.finish(st);
 }
 
 // ---- constants -------------------------------------------------------------------------------------
@@ -1842,17 +1875,6 @@ static int32_t key_transform_host(sgfhe_ctx *c, const uint64_t *canon, uint32_t 
     });
 }
 
-// [a1 | a2 | b1 | b2 | res]: the bootstrap inputs of `rows` rows (a: n words, b: one) carved out of `base`, and what
-// follows them (the result rows, where the buffer holds them)
-struct Staging {
-    uint64_t *a1, *a2, *b1, *b2, *res;
-    Staging from_row(size_t off, size_t n) const { return {a1 + off * n, a2 + off * n, b1 + off, b2 + off, res}; }
-};
-static Staging staging(uint64_t *base, size_t rows, size_t n) {
-    uint64_t *a2 = base + rows * n, *b1 = a2 + rows * n;
-    return {base, a2, b1, b1 + rows, b1 + 2 * rows};
-}
-
 int32_t sgfhe_ctx_destroy(sgfhe_ctx *c) {
     if (!c) return SGFHE_OK;
     (void)hipSetDevice(c->device);
@@ -2180,8 +2202,11 @@ int32_t sgfhe_bootstrap_batch_device(sgfhe_ctx *c, const uint64_t *a1, const uin
     // The call's work is queued on the caller's stream (or the ctx's own), behind everything earlier
     // calls queued on this ctx on any stream (fence_begin): calls on one ctx never overlap on the
     // device, so two threads or two streams may share it.
-    return bootstrap_device(c, a1, b1, a2, b2, batch, out, flags, c->n, nullptr,
-                            stream ? (hipStream_t)stream : c->stream);
+    BootCall call(c);
+    call.rows = {a1, a2, b1, b2};
+    call.batch = batch, call.out = out, call.flags = flags;
+    if (stream) call.st = (hipStream_t)stream;
+    return bootstrap_device(c, call);
 }
 
 int32_t sgfhe_sync(sgfhe_ctx *c) {
@@ -2228,10 +2253,12 @@ static int32_t bootstrap_host(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
     pin_grow(c->pin_in, in_words, "pin_in");
     pin_grow(c->pin_out, out_words, "pin_out");
     const double t0 = wall_ms();
+    BootCall call(c);
+    call.batch = batch, call.out = d_out, call.flags = flags, call.n_iters = n_iters;
     if (pipe) {
         const HostPipe hp = {a1, b1, a2, b2, out, d_in, d_out, c->pin_in.p, c->pin_out.p, out_row, dbg};
-        rc = bootstrap_device(c, nullptr, nullptr, nullptr, nullptr, batch, d_out, flags, n_iters, nullptr,
-                              c->stream, nullptr, &hp);
+        call.pipe = &hp;
+        rc = bootstrap_device(c, call);
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess && rc == SGFHE_OK) rc = fail(c, SGFHE_ERR_HIP, hipGetErrorString(e));
         if (rc == SGFHE_OK) c->pending = false;
@@ -2251,8 +2278,9 @@ static int32_t bootstrap_host(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *
         HIPCHK(c, hipMemcpyAsync(d_b1, b1, batch * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(d_b2, b2, batch * 8, hipMemcpyHostToDevice, c->stream));
         const double t1 = wall_ms();
-        if ((rq = bootstrap_device(c, d_a1, d_b1, d_a2, d_b2, batch, d_out, flags, n_iters, d_acc.p, c->stream, d_dig.p)))
-            return rq;
+        call.rows = {d_a1, d_a2, d_b1, d_b2};
+        call.acc_out = d_acc.p, call.dig_out = d_dig.p;
+        if ((rq = bootstrap_device(c, call))) return rq;
         const double t2 = wall_ms();
         if (digs) HIPCHK(c, hipMemcpyAsync(digs, d_dig.p, dig_words * 8, hipMemcpyDeviceToHost, c->stream));
         if (out) HIPCHK(c, hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2571,8 +2599,9 @@ static int32_t pack_bits_queued(sgfhe_ctx *c, const uint64_t *a, const uint64_t 
     HIPCHK(c, hipMemcpyAsync(S.b1, ones.data(), nb * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(S.a2, a, nb * n * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(S.b2, b, nb * 8, hipMemcpyHostToDevice, st));
-    int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ, c->n,
-                                  nullptr, st);
+    BootCall call(c);
+    call.rows = S, call.batch = nb, call.out = (uint64_t *)c->pack_raw.p, call.flags = SGFHE_FLAG_RAW_MODQ;
+    int32_t rc = bootstrap_device(c, call);
     if (rc) return rc;
     if ((rc = pack_tail(c, c->pack_raw.p, 3 * (uint32_t)(n + 1), count, d_w, d_v, c->last_call, st))) return rc;
     HIPCHK(c, hipMemcpyAsync(out_w, d_w, count * M * 8, hipMemcpyDeviceToHost, st));
@@ -2654,76 +2683,20 @@ int32_t sgfhe_lwe_lift_modq(sgfhe_ctx *c, const uint64_t *lwe, size_t count, uin
     return run_drained(c, [&] { return lwe_lift_queued(c, lwe, words, out); });
 }
 
-// everything sgfhe_bootstrap_lut_batch does on the device
-// (the pack path's buffers: its LWE staging takes the rows, zeros for the second input and the descriptor, its
-//  un-reduced rows the result in either form)
+// everything sgfhe_bootstrap_lut_batch and sgfhe_bootstrap_lut_multi_batch do on the device; `tables`: the family
+// call's [row][n_tables], NULL for the single-table call, whose tables are in the descriptor words
+// (the pack path's buffers: its LWE staging takes the rows, zeros for the second input, the descriptor and, behind
+//  it, eight to a uint64, the tables; its un-reduced rows the result in either form)
 static int32_t bootstrap_lut_queued(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const std::vector<uint32_t> &words,
-                                    size_t batch, uint64_t *out, uint32_t flags) {
-    const size_t n = c->n;
-    hipStream_t st = c->stream;
-    const bool raw = flags & SGFHE_FLAG_RAW_MODQ;
-    const size_t out_words = batch * 3 * (n + 1) * (raw ? 2 : 1);
-    int32_t rc;
-    // [a1 | a2 = 0 | b1 | b2 = 0 | descriptor words, two to a uint64]
-    if ((rc = circ_grow(c, c->pack_lwe, 2 * batch * n + 2 * batch + (batch + 1) / 2))) return rc;
-    if ((rc = circ_grow(c, c->pack_raw, batch * 3 * (n + 1)))) return rc;
-    const Staging S = staging(c->pack_lwe.p, batch, n);
-    uint32_t *d_lut = reinterpret_cast<uint32_t *>(c->pack_lwe.p + 2 * batch * n + 2 * batch);
-    HIPCHK(c, hipMemcpyAsync(S.a1, a, batch * n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.b1, b, batch * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(S.a2, 0, batch * n * 8, st));
-    HIPCHK(c, hipMemsetAsync(S.b2, 0, batch * 8, st));
-    HIPCHK(c, hipMemcpyAsync(d_lut, words.data(), batch * 4, hipMemcpyHostToDevice, st));
-    const LutDesc lut = {d_lut, true};
-    uint64_t *d_out = reinterpret_cast<uint64_t *>(c->pack_raw.p);
-    if ((rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, batch, d_out, flags, c->n, nullptr, st, nullptr, nullptr, &lut)))
-        return rc;
-    HIPCHK(c, hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->pending = false;
-    return SGFHE_OK;
-}
-
-int32_t sgfhe_bootstrap_lut_batch(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint8_t *table, size_t batch,
-                                  uint64_t *out, uint32_t flags) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);
-    if (batch == 0) return SGFHE_OK;
-    if (!a || !b || !table || !out)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: NULL row, table or output pointer");
-    if (flags & ~SGFHE_FLAG_RAW_MODQ)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: flags is 0 or SGFHE_FLAG_RAW_MODQ");
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    if (batch > ((size_t)1 << 31) / (c->n + 1))   // (row counts are 32-bit on the device)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: too many rows");
-    for (size_t i = 0; i < batch * c->n; i++)
-        if (a[i] >= c->par.r)
-            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: word " + std::to_string(i) + " of a is not below r");
-    for (size_t i = 0; i < batch; i++)
-        if (b[i] >= c->par.r)
-            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_batch: b of row " + std::to_string(i) + " is not below r");
-    std::vector<uint32_t> words;   // the descriptor: LUT_ROW | table for every row
-    try {
-        words.resize(batch);
-    } catch (...) {
-        return fail(c, SGFHE_ERR_OOM, "out of host memory");
-    }
-    for (size_t t = 0; t < batch; t++) words[t] = LUT_ROW | table[t];
-    return run_drained(c, [&] { return bootstrap_lut_queued(c, a, b, words, batch, out, flags); });
-}
-
-// everything sgfhe_bootstrap_lut_multi_batch does on the device
-// (the buffers of bootstrap_lut_queued; the tables lie behind the descriptor, eight to a uint64)
-static int32_t bootstrap_lut_multi_queued(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint8_t *tables,
-                                          size_t n_tables, const std::vector<uint32_t> &words, size_t batch, uint64_t *out,
-                                          uint32_t flags) {
+                                    const uint8_t *tables, size_t n_tables, size_t batch, uint64_t *out, uint32_t flags) {
     const size_t n = c->n;
     hipStream_t st = c->stream;
     const bool raw = flags & SGFHE_FLAG_RAW_MODQ;
     const size_t out_words = batch * n_tables * 3 * (n + 1) * (raw ? 2 : 1);
+    // [a1 | a2 = 0 | b1 | b2 = 0 | descriptor words, two to a uint64 | tables]
     const size_t desc = 2 * batch * n + 2 * batch, tab = desc + (batch + 1) / 2;
     int32_t rc;
-    if ((rc = circ_grow(c, c->pack_lwe, tab + (batch * n_tables + 7) / 8))) return rc;
+    if ((rc = circ_grow(c, c->pack_lwe, tab + (tables ? (batch * n_tables + 7) / 8 : 0)))) return rc;
     if ((rc = circ_grow(c, c->pack_raw, (out_words + 1) / 2))) return rc;
     const Staging S = staging(c->pack_lwe.p, batch, n);
     uint32_t *d_lut = reinterpret_cast<uint32_t *>(c->pack_lwe.p + desc);
@@ -2733,17 +2706,57 @@ static int32_t bootstrap_lut_multi_queued(sgfhe_ctx *c, const uint64_t *a, const
     HIPCHK(c, hipMemsetAsync(S.a2, 0, batch * n * 8, st));
     HIPCHK(c, hipMemsetAsync(S.b2, 0, batch * 8, st));
     HIPCHK(c, hipMemcpyAsync(d_lut, words.data(), batch * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_tab, tables, batch * n_tables, hipMemcpyHostToDevice, st));
+    if (tables) HIPCHK(c, hipMemcpyAsync(d_tab, tables, batch * n_tables, hipMemcpyHostToDevice, st));
     LutDesc lut = {d_lut, true};
-    lut.tables = d_tab;
-    lut.n_tables = (uint32_t)n_tables;
+    if (tables) lut.tables = d_tab, lut.n_tables = (uint32_t)n_tables;
     uint64_t *d_out = reinterpret_cast<uint64_t *>(c->pack_raw.p);
-    if ((rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, batch, d_out, flags, c->n, nullptr, st, nullptr, nullptr, &lut)))
-        return rc;
+    BootCall call(c);
+    call.rows = S, call.batch = batch, call.out = d_out, call.flags = flags, call.lut = &lut;
+    if ((rc = bootstrap_device(c, call))) return rc;
     HIPCHK(c, hipMemcpyAsync(out, d_out, out_words * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     c->pending = false;
     return SGFHE_OK;
+}
+
+// What both entries check of a call that has rows, build of it on the host, and run: `name` is the entry's, for the
+// error strings.  `family`: `tables` is [row][n_tables] and goes to the device as it is; otherwise it holds one
+// table per row, which goes into the row's descriptor word.
+static int32_t bootstrap_lut(sgfhe_ctx *c, const std::string &name, const uint64_t *a, const uint64_t *b,
+                             const uint8_t *tables, size_t n_tables, bool family, size_t batch, uint64_t *out,
+                             uint32_t flags) {
+    if (!a || !b || !tables || !out)
+        return fail(c, SGFHE_ERR_INVALID_ARG, name + ": NULL row, table or output pointer");
+    if (flags & ~SGFHE_FLAG_RAW_MODQ)
+        return fail(c, SGFHE_ERR_INVALID_ARG, name + ": flags is 0 or SGFHE_FLAG_RAW_MODQ");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    if (batch > ((size_t)1 << 31) / (c->n + 1) / n_tables)   // (row and table counts are 32-bit on the device)
+        return fail(c, SGFHE_ERR_INVALID_ARG, name + ": too many rows");
+    for (size_t i = 0; i < batch * c->n; i++)
+        if (a[i] >= c->par.r)
+            return fail(c, SGFHE_ERR_INVALID_ARG, name + ": word " + std::to_string(i) + " of a is not below r");
+    for (size_t i = 0; i < batch; i++)
+        if (b[i] >= c->par.r)
+            return fail(c, SGFHE_ERR_INVALID_ARG, name + ": b of row " + std::to_string(i) + " is not below r");
+    std::vector<uint32_t> words;   // the descriptor of k_init: every row is a LUT row
+    try {
+        words.assign(batch, LUT_ROW);
+    } catch (...) {
+        return fail(c, SGFHE_ERR_OOM, "out of host memory");
+    }
+    if (!family)   // ... and carries its table: LUT_ROW | table
+        for (size_t t = 0; t < batch; t++) words[t] |= tables[t];
+    return run_drained(c, [&] {
+        return bootstrap_lut_queued(c, a, b, words, family ? tables : nullptr, n_tables, batch, out, flags);
+    });
+}
+
+int32_t sgfhe_bootstrap_lut_batch(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint8_t *table, size_t batch,
+                                  uint64_t *out, uint32_t flags) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    if (batch == 0) return SGFHE_OK;
+    return bootstrap_lut(c, "sgfhe_bootstrap_lut_batch", a, b, table, 1, false, batch, out, flags);
 }
 
 int32_t sgfhe_bootstrap_lut_multi_batch(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, const uint8_t *tables,
@@ -2752,27 +2765,10 @@ int32_t sgfhe_bootstrap_lut_multi_batch(sgfhe_ctx *c, const uint64_t *a, const u
     SGFHE_LOCK(c);
     if (n_tables < 1 || n_tables > SGFHE_LUT_MAX_TABLES)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: n_tables is 1 to SGFHE_LUT_MAX_TABLES");
-    if (flags & ~SGFHE_FLAG_RAW_MODQ)
+    if (flags & ~SGFHE_FLAG_RAW_MODQ)   // (this entry checks its flags on an empty call too)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: flags is 0 or SGFHE_FLAG_RAW_MODQ");
     if (batch == 0) return SGFHE_OK;
-    if (!a || !b || !tables || !out)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: NULL row, table or output pointer");
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    if (batch > ((size_t)1 << 31) / (c->n + 1) / n_tables)   // (row and table counts are 32-bit on the device)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: too many rows");
-    for (size_t i = 0; i < batch * c->n; i++)
-        if (a[i] >= c->par.r)
-            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: word " + std::to_string(i) + " of a is not below r");
-    for (size_t i = 0; i < batch; i++)
-        if (b[i] >= c->par.r)
-            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_bootstrap_lut_multi_batch: b of row " + std::to_string(i) + " is not below r");
-    std::vector<uint32_t> words;   // the descriptor of k_init: every row is a LUT row
-    try {
-        words.assign(batch, LUT_ROW);
-    } catch (...) {
-        return fail(c, SGFHE_ERR_OOM, "out of host memory");
-    }
-    return run_drained(c, [&] { return bootstrap_lut_multi_queued(c, a, b, tables, n_tables, words, batch, out, flags); });
+    return bootstrap_lut(c, "sgfhe_bootstrap_lut_multi_batch", a, b, tables, n_tables, true, batch, out, flags);
 }
 
 int32_t sgfhe_debug_ntt(sgfhe_ctx *c, uint32_t prime_index, int inverse, const uint32_t *in,
@@ -3301,8 +3297,7 @@ int32_t CircuitRun::grow() {
     }
     if (sz.work_rows) {   // the lanes' work buffers for the largest chunk of any call (bootstrap_device's ensure_work is
                           // then a no-op and never waits on the host between levels)
-        const uint32_t chunk0 = c->chunk ? c->chunk : default_chunk(c);
-        if ((rc = ensure_work(c, round_up8((uint32_t)std::min<uint64_t>(sz.work_rows, chunk0))))) return rc;
+        if ((rc = ensure_work(c, max_chunk_rows(chunk_policy(c, flatten_mode(c)), sz.work_rows)))) return rc;
     }
     return SGFHE_OK;
 }
@@ -3378,8 +3373,11 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
     }
     gather(C.k0, S, row0, C.rows, C.lut ? const_cast<uint32_t *>(lut.rows) : nullptr);
     HIPCHK(c, hipGetLastError());
-    int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, C.rows, S.res, raw ? SGFHE_FLAG_RAW_MODQ : 0u, c->n, nullptr, st,
-                                  nullptr, nullptr, C.lut ? &lut : nullptr);
+    BootCall call(c);
+    call.rows = S, call.batch = C.rows, call.out = S.res, call.st = st;
+    if (raw) call.flags = SGFHE_FLAG_RAW_MODQ;
+    if (C.lut) call.lut = &lut;
+    int32_t rc = bootstrap_device(c, call);
     if (rc) return rc;
     if (raw) {
         const ulonglong2 *res = reinterpret_cast<const ulonglong2 *>(S.res);
@@ -3456,8 +3454,9 @@ int32_t CircuitRun::pack_group(size_t q0) {
             gather((uint32_t)P.live(), S.from_row(U.rank * n, n), U.q * n, U.len * n);
             HIPCHK(c, hipGetLastError());
         }
-        const int32_t rc = bootstrap_device(c, S.a1, S.b1, S.a2, S.b2, nb, (uint64_t *)c->pack_raw.p, SGFHE_FLAG_RAW_MODQ,
-                                            c->n, nullptr, st);
+        BootCall call(c);
+        call.rows = S, call.batch = nb, call.out = (uint64_t *)c->pack_raw.p, call.flags = SGFHE_FLAG_RAW_MODQ, call.st = st;
+        const int32_t rc = bootstrap_device(c, call);
         if (rc) return rc;
         for (size_t i = 0; direct && i < runs.size(); i++) {
             const CircuitPackRun &U = runs[i];

@@ -28,53 +28,6 @@
 
 using namespace sgfhe;
 
-namespace {
-
-// ---------------------------------------------------------------- host number theory (word size)
-
-uint32_t mulmod32(uint32_t a, uint32_t b, uint32_t p) { return (uint32_t)((uint64_t)a * b % p); }
-uint32_t powmod32(uint32_t a, uint64_t e, uint32_t p) {
-    uint32_t r = 1 % p;
-    a %= p;
-    while (e) {
-        if (e & 1) r = mulmod32(r, a, p);
-        a = mulmod32(a, a, p);
-        e >>= 1;
-    }
-    return r;
-}
-bool is_prime32(uint32_t x) {
-    if (x < 2) return false;
-    for (uint32_t q : {2u, 3u, 5u, 7u, 11u, 13u}) {
-        if (x % q == 0) return x == q;
-    }
-    uint32_t d = x - 1;
-    int s = 0;
-    while (!(d & 1)) { d >>= 1; s++; }
-    for (uint32_t a : {2u, 3u, 5u, 7u}) {  // deterministic below 3,215,031,751
-        uint32_t y = powmod32(a, d, x);
-        if (y == 1 || y == x - 1) continue;
-        bool comp = true;
-        for (int i = 0; i < s - 1; i++) {
-            y = mulmod32(y, y, x);
-            if (y == x - 1) { comp = false; break; }
-        }
-        if (comp) return false;
-    }
-    return true;
-}
-uint32_t bitrev(uint32_t x, int bits) {
-    uint32_t r = 0;
-    for (int i = 0; i < bits; i++) { r = (r << 1) | (x & 1); x >>= 1; }
-    return r;
-}
-inline u128 ld128(const uint64_t *w) { return ((u128)w[1] << 64) | w[0]; }
-inline int32_t centre32(uint32_t x, uint32_t p) { return x > (p - 1) / 2 ? (int32_t)x - (int32_t)p : (int32_t)x; }
-double u128_log2(u128 x) { return log2((double)(uint64_t)(x >> 64) * 18446744073709551616.0 + (double)(uint64_t)x); }
-double u128_dbl(u128 x) { return (double)(uint64_t)(x >> 64) * 18446744073709551616.0 + (double)(uint64_t)x; }
-
-}  // namespace
-
 // wall clock in milliseconds (the SGFHE_DEBUG_IO phase lines)
 static double wall_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -168,7 +121,7 @@ struct CtxShared {
         CrtConst h_crt;
         CrtLean *d_lean = nullptr;  // constants of k_crt_lean (nl = 0: this parameter set keeps k_crt_acc)
         CrtLean h_lean;
-        bool lean_rnd_ok = false;   // k_crt_lean_rnd's width bounds hold for this parameter set (build_basis)
+        bool lean_rnd_ok = false;   // k_crt_lean_rnd's width bounds hold for this parameter set (derive_basis)
         uint32_t pack_G = 1, pack_G_rnd = 0;  // key slices per exact-accumulation group of the packing path
                                               // (deterministic / randomised flatten; 0 = not available)
         int32_t *d_key = nullptr;
@@ -1230,264 +1183,78 @@ int32_t bootstrap_device(sgfhe_ctx *c, const BootCall &call) {
 
 // ---- constants -------------------------------------------------------------------------------------
 
-// One basis: everything that depends on which primes are in use -- CRT / flatten constants, the
-// per-prime records, the twiddle tables of primes not yet on the device -- into S (its key comes later).
-int32_t build_basis(sgfhe_ctx *c, sgfhe_ctx::Basis &S, uint32_t npr, const uint32_t *cand_primes, double log_have, double log_mbq) {
-    const uint32_t M = c->M;
-    const int logm = c->logm;
-    const u128 Q = c->Q, B = c->B;
+// The arithmetic of every constant is csrc/constants.h (plan_bases, derive_basis, prime_tables); here they are
+// allocated, uploaded and given their device pointers.
+
+// The scheduling knobs of the environment (CtxKnobs), read once at ctx creation.
+void read_env_knobs(sgfhe_ctx *c) {
+    const char *env = getenv("SGFHE_HOST_PIN");
+    c->use_pin = !(env && env[0] == '0');
+    env = getenv("SGFHE_SMALL_PADDED");
+    c->small_padded = env && env[0] == '1';
+    env = getenv("SGFHE_SMALL_LANES");
+    if (env) { c->small_lanes = atoi(env) != 0; if (atoi(env) > 1) c->small_lanes_max = (uint32_t)atoi(env); }
+    env = getenv("SGFHE_CRT1_GATES");
+    c->crt1_max = (uint32_t)(env ? atoi(env) : 8) * 2u * c->M;
+    // m = 16384: the latency form ends at 16 gates (20 / 24 gates take 114 / 144 ms in it, 112 / 112 in the
+    // throughput form; 12 / 14 gates 86 / 93 against 107; profiles/r04_exp_small_rings_lanes.txt)
+    if (c->logm >= 14) { c->small_max = 16; if (c->small_lanes_max > 16) c->small_lanes_max = 16; }
+    env = getenv("SGFHE_SMALL_SPLIT");
+    if (env) c->split_max = (uint32_t)atoi(env);
+    env = getenv("SGFHE_SMALL_FUSED");
+    if (env) c->fused_min = (uint32_t)atoi(env);
+}
+
+// The twiddle tables of primes[tw_done .. npr) onto the device (a second, smaller basis shares the tables of the first).
+int32_t upload_prime_tables(sgfhe_ctx *c, const uint32_t *primes, uint32_t npr) {
+    const size_t M = c->M;
+    PrimeTables T;
+    for (uint32_t i = c->tw_done; i < npr; i++) {
+        const Refusal r = prime_tables(primes[i], c->logm, &T);
+        if (r) return fail(c, r.code, r.msg);
+        HIPCHK(c, hipMemcpy(c->d_tw + 4 * i * M, T.tw.data(), 4 * M * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (!T.twq.empty())
+            HIPCHK(c, hipMemcpy(c->d_twq + 4 * i * M, T.twq.data(), 4 * M * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->d_pow + 2 * i * M, T.pw.data(), 2 * M * sizeof(int32_t), hipMemcpyHostToDevice));
+        memcpy(c->tw_head[i], T.head, sizeof T.head);
+        c->tw_done = i + 1;
+    }
+    return SGFHE_OK;
+}
+
+// One basis of the plan into S (its key comes later): constants and per-prime records, with the records' pointers
+// into the tables on the device.
+int32_t upload_basis(sgfhe_ctx *c, sgfhe_ctx::Basis &S, const BasisPlan &plan, int mode) {
+    const size_t M = c->M;
+    const uint32_t npr = plan.npr[mode];
     S.npr = npr;
-    for (uint32_t i = 0; i < npr; i++) S.primes[i] = cand_primes[i];
-    const int NPR = (int)npr;  // the loops below run over the primes in use
-
-    // Packing (fhe.jl:683-687): G slices of two digit polynomials each are summed exactly before a
-    // CRT: |sum| <= G m B Q / 2 (four times that with the randomised flatten) must stay below
-    // 0.4 M_rns.
-    {
-        auto group = [&](double lg) {
-            uint32_t G = 0;
-            if (lg >= 0) { G = 1; while (G < c->n && (double)(31 - __builtin_clz(2 * G)) <= lg) G *= 2; }
-            return G;
-        };
-        const double lg = log_have + log2(0.8) - log_mbq - 0.001;
-        S.pack_G = group(lg);
-        S.pack_G_rnd = group(lg - 2.0);
+    for (uint32_t i = 0; i < npr; i++) S.primes[i] = plan.primes[i];
+    const int32_t rc = upload_prime_tables(c, S.primes, npr);
+    if (rc) return rc;
+    BasisConst K;
+    derive_basis(c->logm, c->n, c->Q, c->B, ld128(c->par.DQ_tilde), S.primes, npr, plan.log_have[mode], plan.log_mbq, &K);
+    memcpy(&S.h_crt, &K.crt, sizeof(CrtConst));     // (byte for byte, padding included: they go to the device)
+    memcpy(&S.h_lean, &K.lean, sizeof(CrtLean));
+    S.lean_rnd_ok = K.lean_rnd_ok;
+    S.pack_G = K.pack_G;
+    S.pack_G_rnd = K.pack_G_rnd;
+    for (uint32_t i = 0; i < npr; i++) {
+        PrimeK &P = K.pk[i];
+        const int32_t *h = c->tw_head[i];
+        P.twf = c->d_tw + 4 * i * M;
+        P.twi = c->d_tw + (4 * i + 1) * M;
+        P.f1 = h[0]; P.f2 = h[1]; P.f3 = h[2];
+        P.fp2 = h[3]; P.fp3 = h[4];
+        P.v1 = h[5]; P.v2 = h[6]; P.v3 = h[7];
+        P.twq = c->d_twq + 4 * i * M;
+        P.pw = c->d_pow + 2 * i * M;
     }
-
-    // flatten constants (utils.jl:162-169)
-    const u128 s = (B & 1) ? (B - 1) / 2 : B / 2 - 1;
-    const u128 off = (((1 + B) % Q) * (s % Q)) % Q;  // (1+B) < 2^63, s < 2^62
-    auto digits_of = [&](u128 acc) {
-        u128 x = (acc + off) % Q;
-        return make_ulonglong2((uint64_t)(x % B), (uint64_t)(x / B));
-    };
-
-    CrtConst &cc = S.h_crt;
-    memset(&cc, 0, sizeof cc);
-    cc.Q = Q;
-    cc.B = B;
-    cc.offneg = (Q - off) % Q;
-    {   // randomised flatten: v_i in [-xmax, xmax], digits shifted by s + xmax (utils.jl:204-216)
-        const u128 xmax = (B & 1) ? (B - 1) / 2 * 3 : B / 2 * 3;
-        const u128 stot = s + xmax;
-        cc.xmax = (uint64_t)xmax;
-        cc.offneg_rnd = (Q - (((1 + B) % Q) * (stot % Q)) % Q) % Q;
-    }
-    cc.DQ = ld128(c->par.DQ_tilde) % Q;
-    cc.halfQ = Q / 2;
-    cc.roundthr = Q / 2 + (Q & 1);
-    cc.invQ = 1.0 / u128_dbl(Q);
-    cc.invB = 1.0 / u128_dbl(B);
-    cc.logr = logm + 1;
-    cc.dig0 = digits_of(0);
-    cc.digP = digits_of(cc.DQ);
-    cc.digN = digits_of((Q - cc.DQ) % Q);
-    cc.DQL = ld128(c->par.DQ_tilde) >> 2;   // LUT rows: A0 (DQ_tilde < Q is checked at ctx creation)
-    cc.digPL = digits_of(cc.DQL);
-    cc.digNL = digits_of((Q - cc.DQL) % Q);
-    u128 cM = 1 % Q;
-    for (int i = 0; i < NPR; i++) cM = (cM * S.primes[i]) % Q;  // < 2^94 * 2^29
-    for (int i = 0; i < NPR; i++) {
-        u128 ci = 1 % Q;
-        for (int j = 0; j < NPR; j++)
-            if (j != i) ci = (ci * S.primes[j]) % Q;
-        cc.c[i] = ci;
-        cc.invp[i] = 1.0f / (float)S.primes[i];
-    }
-    const uint32_t plast = S.primes[NPR - 1];
-    const u128 cH = (cc.c[NPR - 1] * ((plast - 1) / 2)) % Q;
-    for (int a = 0; a < 6 * NPR + 2; a++) cc.T[a] = (Q - (((u128)a * cM) % Q + cH) % Q) % Q;
-    auto limbs = [](u128 v, uint32_t *w, int n) {
-        for (int i = 0; i < n; i++) w[i] = (uint32_t)(v >> (32 * i));
-    };
-    for (int i = 0; i < NPR; i++) { limbs(cc.c[i], cc.c32[i], 3); cc.cd[i] = u128_dbl(cc.c[i]); }
-    for (int a = 0; a < 6 * NPR + 2; a++) { limbs(cc.T[a], cc.T32[a], 4); cc.Td[a] = u128_dbl(cc.T[a]); }
-    limbs(Q, cc.Q32, 3);
-    cc.Bd = u128_dbl(B);
-
-    {   // k_crt_lean (kernels.h; tests/rns_model.py::CrtLean derives the same values)
-        CrtLean &K = S.h_lean;
-        memset(&K, 0, sizeof K);
-        int nq = 0, nb = 0;
-        while (nq < 128 && (Q >> nq)) nq++;
-        while (nb < 64 && (B >> nb)) nb++;
-        int NL = (nq + 28) / 29;
-        if (NL < 2) NL = 2;
-        const int t = nq - 29, a = 29 * (NL - 1) - t;
-        if (nb >= 13 && NL <= 4 && nq >= 30 && a >= 0 && a <= 28) {
-            auto lim = [&](u128 v, uint32_t *w) {
-                for (int k = 0; k < 4; k++) w[k] = (uint32_t)((v >> (29 * k)) & 0x1FFFFFFFu);
-            };
-            for (int i = 0; i < NPR; i++) {
-                lim(cc.c[i], K.c[i]);
-                K.w[i] = (uint32_t)((1ull << 58) / S.primes[i]);
-            }
-            lim((Q - cM % Q) % Q, K.cMn);
-            K.hoff = (plast - 1) / 2;
-            limbs(Q, K.Qw, 3);
-            K.B0 = (uint32_t)(B & 0x1FFFFFFFu);
-            K.B1 = (uint32_t)(B >> 29);
-            K.Bw0 = (uint32_t)B;
-            K.Bw1 = (uint32_t)(B >> 32);
-            // floor(2^(t + 72) / Q) < 2^44: long division, 2^(t + 72) has up to 138 bits
-            {
-                u128 rem = 0, quo = 0;
-                for (int bit = t + 72; bit >= 0; bit--) {
-                    rem = (rem << 1) | (bit == t + 72 ? 1 : 0);
-                    quo <<= 1;
-                    if (rem >= Q) { rem -= Q; quo |= 1; }
-                }
-                K.mq0 = (uint32_t)quo;
-                K.mq1 = (uint32_t)(quo >> 32);
-            }
-            {   // floor(2^(nb + 51) / B) <= 2^52
-                const u128 quo = ((u128)1 << (nb + 51)) / B;
-                K.mb0 = (uint32_t)quo;
-                K.mb1 = (uint32_t)(quo >> 32);
-            }
-            K.a = (uint32_t)a;
-            K.t2 = (uint32_t)(nq > 63 ? nq - 63 : 0);
-            K.sB = (uint32_t)(nb + 51 - (int)K.t2 - 64);
-            K.nl = (uint32_t)NL;
-            // randomised flatten: 2 xmax and (-2 xmax (1 + B)) mod Q  (2 xmax (1 + B) < 3.1 B^2 < 2^96)
-            const u128 xm2 = (u128)2 * cc.xmax;
-            lim((Q - (xm2 * (1 + B)) % Q) % Q, K.cR);
-            K.xm2lo = (uint32_t)xm2;
-            K.xm2hi = (uint32_t)(xm2 >> 32);
-            // k_crt_lean_rnd adds the draws to the old stored digits: its hi operand reaches
-            // Q / B + 6 B <= 7 B.  With two limbs (Q < 2^58) the term h1 B1 2^61 of hi B has no limb
-            // sum to go to (crt_lean_one drops it), so the kernel is taken only where that term is
-            // zero; and 6 B^2 has to stay far below the 2^34 Q of the residue sum for the quotient
-            // estimate's width (tests/rns_model.py CrtLean.digits asserts both).  Reference
-            // parameter sets have three limbs and B ~ sqrt(Q); others fall back to k_crt_acc.
-            S.lean_rnd_ok = (NL >= 3 || ((7 * B) >> 32) == 0 || K.B1 == 0) && B * B <= (Q << 27);
-            // crt_lean87_one: five primes, Q of 87 bits, B of 44 bits (Params(1024)); its register
-            // widths and quotient estimates hold for every such Q and B
-            // (tests/test_crt_lean87_model.py)
-            if (NPR == 5 && nq == 87 && nb == 44) {
-                const u128 mq = ((u128)1 << 122) / Q, mb = ((u128)1 << 96) / B;
-                K.mqw0 = (uint32_t)mq;
-                K.mqw1 = (uint32_t)(mq >> 32);
-                K.mbw0 = (uint32_t)mb;
-                K.mbw1 = (uint32_t)(mb >> 32);
-                K.p87 = 1;
-            }
-        }
-    }
-
-    // twiddle tables and per-prime constants (all residues centred: |.| <= (p - 1) / 2)
-    // per prime four tables of m entries: forward twiddles, inverse twiddles, and at + 2 m from each the
-    // product twiddles of the radix-4 steps (ntt.h fwd_step4): twp[j] = +-tw[j >> 1] tw[j], minus for odd j
-    std::vector<int32_t> tw((size_t)NPR * 4 * M), twq, pwt;
-    std::vector<PrimeK> pk(NPR);
-    cc.npr = npr;
-    for (int i = 0; i < NPR; i++) {
-        const uint32_t p = S.primes[i];
-        if ((uint32_t)i >= c->tw_done) {   // (a second, smaller basis shares the tables of the first)
-        uint32_t psi = 0;
-        for (uint32_t x = 2; x < 2000 && !psi; x++) {
-            uint32_t g = powmod32(x, (p - 1) / (2 * M), p);
-            if (powmod32(g, M, p) == p - 1) psi = g;
-        }
-        if (!psi) return fail(c, SGFHE_ERR_UNSUPPORTED, "no primitive 2m-th root of unity");
-        const uint32_t ipsi = powmod32(psi, p - 2, p);
-        int32_t *f = tw.data() + (size_t)(4 * i) * M, *v = f + M, *fp = f + 2 * M, *vp = f + 3 * M;
-        const uint32_t R1m = (uint32_t)((1ull << 32) % p);
-        std::vector<uint32_t> pf(M), pv(M);   // plain values in table order
-        uint32_t pw = 1, ipw = 1;
-        for (uint32_t t = 0; t < M; t++) {
-            const uint32_t br = bitrev(t, logm);
-            pf[br] = pw;
-            pv[br] = ipw;
-            f[br] = centre32(mulmod32(pw, R1m, p), p);   // Montgomery form
-            v[br] = centre32(mulmod32(ipw, R1m, p), p);
-            pw = mulmod32(pw, psi, p);
-            ipw = mulmod32(ipw, ipsi, p);
-        }
-        fp[0] = fp[1] = vp[0] = vp[1] = 0;
-        for (uint32_t j = 2; j < M; j++) {
-            const uint32_t a = mulmod32(mulmod32(pf[j >> 1], pf[j], p), R1m, p);
-            const uint32_t b = mulmod32(mulmod32(pv[j >> 1], pv[j], p), R1m, p);
-            fp[j] = centre32((j & 1) ? (p - a) % p : a, p);
-            vp[j] = centre32((j & 1) ? (p - b) % p : b, p);
-        }
-        // quarter form of the latency kernels: after the first two Cooley-Tukey stages quarter q of the
-        // array runs on the sub-tree of the twiddle table rooted at entry 4 + q, so its tables are a
-        // re-indexing of the big ones: entry mm' + i' (mm' a power of two, i' < mm') = big entry
-        // 4 mm' + q mm' + i'; the same for the inverse and for both product tables
-        if (M >= 16) {
-            const uint32_t MS = M / 4;
-            twq.assign((size_t)4 * M, 0);
-            for (uint32_t q = 0; q < 4; q++)
-                for (uint32_t jj = 1; jj < MS; jj++) {
-                    const uint32_t mmq = 1u << (31 - __builtin_clz(jj)), J = 4 * mmq + q * mmq + (jj - mmq);
-                    int32_t *blk = twq.data() + (size_t)q * M;
-                    blk[jj] = f[J];
-                    blk[MS + jj] = v[J];
-                    blk[2 * MS + jj] = jj >= 2 ? fp[J] : 0;
-                    blk[3 * MS + jj] = jj >= 2 ? vp[J] : 0;
-                }
-            HIPCHK(c, hipMemcpy(c->d_twq + (size_t)(4 * i) * M, twq.data(), (size_t)4 * M * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        {   // psi^e R mod p, centred
-            pwt.resize((size_t)2 * M);
-            uint32_t pe = 1;
-            for (uint32_t e = 0; e < 2 * M; e++) { pwt[e] = centre32(mulmod32(pe, R1m, p), p); pe = mulmod32(pe, psi, p); }
-            HIPCHK(c, hipMemcpy(c->d_pow + (size_t)(2 * i) * M, pwt.data(), (size_t)2 * M * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        const int32_t head[8] = {f[1], M > 2 ? f[2] : 0, M > 2 ? f[3] : 0, M > 2 ? fp[2] : 0, M > 2 ? fp[3] : 0,
-                                 v[1], M > 2 ? v[2] : 0, M > 2 ? v[3] : 0};
-        memcpy(c->tw_head[i], head, sizeof head);
-        }
-        PrimeK &P = pk[i];
-        memset(&P, 0, sizeof P);
-        P.p = (int32_t)p;
-        uint32_t inv = p;  // Newton: p^-1 mod 2^32
-        for (int it = 0; it < 5; it++) inv *= 2u - p * inv;
-        P.pinv = inv;
-        const uint32_t R1 = (uint32_t)((1ull << 32) % p);
-        const uint32_t Rinv = powmod32(R1, p - 2, p);
-        const uint32_t R2 = mulmod32(R1, R1, p);
-        P.r1 = centre32(R1, p);
-        P.r2 = centre32(R2, p);
-        P.r3 = centre32(mulmod32(R2, R1, p), p);
-        P.sR = centre32((p - mulmod32((uint32_t)(s % p), Rinv, p)) % p, p);
-        {
-            const u128 xmax = (B & 1) ? (B - 1) / 2 * 3 : B / 2 * 3;
-            P.sRr = centre32((p - mulmod32((uint32_t)((s + xmax) % p), Rinv, p)) % p, p);
-        }
-        P.hoff = (i == NPR - 1) ? (p - 1) / 2 : 0;
-        P.qmodp = centre32((uint32_t)(Q % p), p);
-        uint32_t Mi = 1;  // (M_rns / p_i) mod p_i
-        for (int j = 0; j < NPR; j++)
-            if (j != i) Mi = mulmod32(Mi, S.primes[j] % p, p);
-        const uint32_t ei = powmod32(Mi, p - 2, p);
-        const uint32_t minv = powmod32(M % p, p - 2, p);
-        const uint32_t kappa = mulmod32(mulmod32(R2, minv, p), ei, p);
-        P.kappaR = centre32(mulmod32(kappa, R1, p), p);
-        P.minvR = centre32(mulmod32(minv, R1, p), p);
-        P.invp = 1.0f / (float)p;
-        P.twf = c->d_tw + (size_t)(4 * i) * M;
-        P.twi = c->d_tw + (size_t)(4 * i + 1) * M;
-        P.npr = npr;
-        P.f1 = c->tw_head[i][0]; P.f2 = c->tw_head[i][1]; P.f3 = c->tw_head[i][2];
-        P.fp2 = c->tw_head[i][3]; P.fp3 = c->tw_head[i][4];
-        P.v1 = c->tw_head[i][5]; P.v2 = c->tw_head[i][6]; P.v3 = c->tw_head[i][7];
-        P.twq = c->d_twq + (size_t)(4 * i) * M;
-        P.pw = c->d_pow + (size_t)(2 * i) * M;
-    }
-    if (c->tw_done < npr) {
-        const size_t off = (size_t)c->tw_done * 4 * M;
-        HIPCHK(c, hipMemcpy(c->d_tw + off, tw.data() + off, ((size_t)npr * 4 * M - off) * sizeof(int32_t),
-                            hipMemcpyHostToDevice));
-        c->tw_done = npr;
-    }
-    HIPCHK(c, hipMalloc(&S.d_primes, NPR * sizeof(PrimeK)));
+    HIPCHK(c, hipMalloc(&S.d_primes, npr * sizeof(PrimeK)));
     c->shared->own(S.d_primes);
-    HIPCHK(c, hipMemcpy(S.d_primes, pk.data(), NPR * sizeof(PrimeK), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(S.d_primes, K.pk, npr * sizeof(PrimeK), hipMemcpyHostToDevice));
     HIPCHK(c, hipMalloc(&S.d_crt, sizeof(CrtConst)));
     c->shared->own(S.d_crt);
-    HIPCHK(c, hipMemcpy(S.d_crt, &cc, sizeof(CrtConst), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(S.d_crt, &S.h_crt, sizeof(CrtConst), hipMemcpyHostToDevice));
     HIPCHK(c, hipMalloc(&S.d_lean, sizeof(CrtLean)));
     c->shared->own(S.d_lean);
     HIPCHK(c, hipMemcpy(S.d_lean, &S.h_lean, sizeof(CrtLean), hipMemcpyHostToDevice));
@@ -1495,81 +1262,24 @@ int32_t build_basis(sgfhe_ctx *c, sgfhe_ctx::Basis &S, uint32_t npr, const uint3
 }
 
 int32_t build_constants(sgfhe_ctx *c) {
-    const int logm = c->logm;
-    const u128 Q = c->Q, B = c->B;
-
-    // RNS primes: the largest primes below 2^29 with p = 1 mod 2^15 (2 m | p - 1 for every
-    // supported m), as many as the exactness bound needs.  The exact integer the CRT has to
-    // recover is D = (x^j - 1) sum_row u_row (*) C_row with |u| <= B / 2 (deterministic flatten,
-    // utils.jl:155-189) and the key lifted to |C| <= Q / 2, so |D| <= 2 m B Q; k_crt_acc needs
-    // |D| <= 0.4 M_rns, i.e. 5 m B Q <= M_rns.  The randomised flatten (|u| <= 2 B,
-    // utils.jl:198-241) needs a factor 4 more.  Where that takes one more prime (Params(1024): six
-    // against five) the ctx gets a basis per mode (sgfhe_ctx::Basis), unless it was created with
-    // SGFHE_CTX_DETERMINISTIC_ONLY.
-    uint32_t cand_primes[NPR_MAX];
-    {
-        int found = 0;
-        for (uint64_t kk = ((1ull << 29) - 1) >> 15; kk > 0 && found < NPR_MAX; kk--) {
-            uint32_t cand = (uint32_t)((kk << 15) + 1);
-            if (cand < (1u << 29) && is_prime32(cand)) cand_primes[found++] = cand;
-        }
-        if (found < NPR_MAX) return fail(c, SGFHE_ERR_UNSUPPORTED, "could not find RNS primes");
-    }
-    const double log_mbq = logm + u128_log2(B) + u128_log2(Q);
-    const double log_need = log2(5.0) + log_mbq + 0.001;
-    auto fewest = [&](double target, double *have) {
-        uint32_t npr = 0;
-        double lh = 0;
-        while (npr < NPR_MAX && (npr < 2 || lh < target)) lh += log2((double)cand_primes[npr++]);
-        *have = lh;
-        return lh >= target ? npr : 0u;
-    };
-    double have_det = 0, have_rnd = 0;
-    const uint32_t npr_det = fewest(log_need, &have_det);
-    if (!npr_det)
-        return fail(c, SGFHE_ERR_UNSUPPORTED, "5 m B Q exceeds the product of the RNS primes");
-    // |u| <= 2 B in the randomised mode: the exactness bound needs 4 x more head-room.  Its reductions
-    // (random_digits, acc_from_digits, crt_reduce) divide values up to about 4 B^2 by Q with a
-    // double-precision quotient estimate, exact while the quotient stays below 2^50.
-    // (stored digits reach 4 B: above 2^48 they take the third plane of the digit record,
-    // MODE_WIDE; B < 2^47 is checked at ctx creation)
-    const bool rnd_width_ok = 2.0 * u128_log2(B) + 2.0 - u128_log2(Q) < 50.0;
-    const uint32_t npr_rnd = fewest(log_need + 2.0, &have_rnd);
-    const bool det_only = (c->create_flags & SGFHE_CTX_DETERMINISTIC_ONLY) != 0;
-    c->nb = (!det_only && rnd_width_ok && npr_rnd > npr_det) ? 2 : 1;
-    c->rnd_ok = rnd_width_ok && npr_rnd != 0 && (c->nb == 2 || npr_rnd == npr_det);
-    c->npr_max = c->nb == 2 ? npr_rnd : npr_det;
-    {
-        const char *env = getenv("SGFHE_HOST_PIN");
-        c->use_pin = !(env && env[0] == '0');
-        env = getenv("SGFHE_SMALL_PADDED");
-        c->small_padded = env && env[0] == '1';
-        env = getenv("SGFHE_SMALL_LANES");
-        if (env) { c->small_lanes = atoi(env) != 0; if (atoi(env) > 1) c->small_lanes_max = (uint32_t)atoi(env); }
-        env = getenv("SGFHE_CRT1_GATES");
-        c->crt1_max = (uint32_t)(env ? atoi(env) : 8) * 2u * c->M;
-        // m = 16384: the latency form ends at 16 gates (20 / 24 gates take 114 / 144 ms in it, 112 / 112 in the
-        // throughput form; 12 / 14 gates 86 / 93 against 107; profiles/r04_exp_small_rings_lanes.txt)
-        if (c->logm >= 14) { c->small_max = 16; if (c->small_lanes_max > 16) c->small_lanes_max = 16; }
-    }
+    BasisPlan plan;
+    const Refusal r = plan_bases(c->logm, c->Q, c->B, (c->create_flags & SGFHE_CTX_DETERMINISTIC_ONLY) != 0, &plan);
+    if (r) return fail(c, r.code, r.msg);
+    c->nb = plan.nb;
+    c->rnd_ok = plan.rnd_ok;
+    c->npr_max = plan.npr_max;
+    read_env_knobs(c);
     HIPCHK(c, hipMalloc(&c->d_tw, (size_t)c->npr_max * 4 * c->M * sizeof(int32_t)));
     c->shared->own(c->d_tw);
     HIPCHK(c, hipMalloc(&c->d_twq, (size_t)c->npr_max * 4 * c->M * sizeof(int32_t)));
     c->shared->own(c->d_twq);
     HIPCHK(c, hipMalloc(&c->d_pow, (size_t)c->npr_max * 2 * c->M * sizeof(int32_t)));
     c->shared->own(c->d_pow);
-    {
-        const char *env = getenv("SGFHE_SMALL_SPLIT");
-        if (env) c->split_max = (uint32_t)atoi(env);
-        env = getenv("SGFHE_SMALL_FUSED");
-        if (env) c->fused_min = (uint32_t)atoi(env);
-    }
     HIPCHK(c, hipMalloc(&c->d_bad, sizeof(uint32_t)));
     HIPCHK(c, hipMemset(c->d_bad, 0, sizeof(uint32_t)));
     // the larger basis first: its pass puts every prime's twiddle tables on the device
     for (int b = c->nb - 1; b >= 0; b--) {
-        const bool big = b == c->nb - 1 && c->nb == 2;
-        int32_t rc = build_basis(c, c->basis[b], big ? npr_rnd : npr_det, cand_primes, big ? have_rnd : have_det, log_mbq);
+        const int32_t rc = upload_basis(c, c->basis[b], plan, plan.mode_of(b));
         if (rc) return rc;
     }
     c->active = 0;
@@ -1606,13 +1316,7 @@ int32_t key_derive(sgfhe_ctx *c) {
     sgfhe_ctx::Basis &Sm = c->basis[0];
     const int32_t rc = key_alloc(c, Sm);
     if (rc) return rc;
-    KeyFactors fac = {};
-    for (uint32_t i = 0; i < Sm.npr; i++) {
-        const uint32_t p = Sm.primes[i];
-        uint32_t f = (uint32_t)((1ull << 32) % p);                   // R: Montgomery form
-        for (uint32_t j = Sm.npr; j < Bg.npr; j++) f = mulmod32(f, Bg.primes[j] % p, p);
-        fac.f[i] = centre32(f, p);
-    }
+    const KeyFactors fac = key_factors(Bg.primes, Sm.npr, Bg.npr);   // (the smaller basis is the first primes of the larger)
     const size_t total = Sm.key_bytes / 4;
     hipLaunchKernelGGL(k_key_derive, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
                        Bg.d_key, Sm.d_key, Sm.d_primes, fac, Bg.npr, Sm.npr, (uint32_t)c->logm, total);
@@ -1734,26 +1438,12 @@ int32_t sgfhe_ctx_create_ex(const sgfhe_params *p, int device, uint32_t flags, s
         const char *env = getenv("SGFHE_COALESCE");
         if (env && env[0] == '0') c->shared->co.enabled = false;
     }
-    const uint64_t m = p->m;
-    if (p->ell != 2) return fail(c, SGFHE_ERR_UNSUPPORTED, "ell must be 2 (fhe.jl:576)");
-    if (m < 64 || m > 16384 || (m & (m - 1)))
-        return fail(c, SGFHE_ERR_UNSUPPORTED, "m must be a power of two in [2^6, 2^14]");
-    if (p->r != 2 * m) return fail(c, SGFHE_ERR_INVALID_ARG, "r must equal 2 m (fhe.jl:62)");
-    if (p->n == 0 || p->n > m / 4 || (p->n & (p->n - 1)))
-        return fail(c, SGFHE_ERR_INVALID_ARG,
-                    "n must be a power of two in [1, m / 4] (fhe.jl:45-46; extract, fhe.jl:585-590)");
-    c->M = (uint32_t)m;
+    const Refusal r = check_params(*p, &c->logm);
+    if (r) return fail(c, r.code, r.msg);
+    c->M = (uint32_t)p->m;
     c->n = (uint32_t)p->n;
-    while ((1u << c->logm) < c->M) c->logm++;
     c->Q = ld128(p->Q);
     c->B = ld128(p->B);
-    if (c->Q < 3 || (c->Q >> 94)) return fail(c, SGFHE_ERR_UNSUPPORTED, "Q must be in [3, 2^94)");
-    if (c->B < 2 || (c->B >> 47)) return fail(c, SGFHE_ERR_UNSUPPORTED, "B must be in [2, 2^47)");
-    {
-        // B^2 >= Q (utils.jl:145); B < 2^46 so B*B fits 128 bits
-        if (c->B * c->B < c->Q) return fail(c, SGFHE_ERR_INVALID_ARG, "B^2 must be >= Q");
-    }
-    if (ld128(p->DQ_tilde) >= c->Q) return fail(c, SGFHE_ERR_INVALID_ARG, "DQ_tilde must be < Q");
     int32_t rc = create_streams(c);
     if (rc) return rc;
     return build_constants(c);
@@ -2075,26 +1765,8 @@ int32_t sgfhe_bkey_generate(sgfhe_ctx *c, const uint64_t *sk, size_t n_sk, const
 }
 
 static int32_t rns2_configure(sgfhe_ctx *c, uint64_t m1, uint64_t m2) {
-    if ((u128)m1 * m2 != c->Q) return fail(c, SGFHE_ERR_INVALID_ARG, "m1 * m2 != Q");
-    if (m1 >= (1ull << 47) || m2 >= (1ull << 47) || m1 < 2 || m2 < 2)
-        return fail(c, SGFHE_ERR_UNSUPPORTED, "RNS2 limb moduli must be in [2, 2^47)");
-    // CRT of rns.jl:32-40: c1 = m2^(m1-1) mod Q = m2 (m2^-1 mod m1), c2 = m1 (m1^-1 mod m2)
-    // (Fermat idempotents, m1 and m2 prime)
-    auto powmod64 = [](uint64_t a, uint64_t e, uint64_t md) {
-        u128 r = 1, b = a % md;
-        while (e) { if (e & 1) r = r * b % md; b = b * b % md; e >>= 1; }
-        return (uint64_t)r;
-    };
-    Rns2Const rc;
-    rc.m1 = m1;
-    rc.m2 = m2;
-    rc.i21 = powmod64(m2 % m1, m1 - 2, m1);
-    rc.i12 = powmod64(m1 % m2, m2 - 2, m2);
-    if ((u128)(m2 % m1) * rc.i21 % m1 != 1 || (u128)(m1 % m2) * rc.i12 % m2 != 1)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "RNS2 limb moduli must be distinct primes");
-    rc.inv1 = 1.0 / (double)m1;
-    rc.inv2 = 1.0 / (double)m2;
-    c->rns2 = rc;
+    const Refusal r = rns2_const(c->Q, m1, m2, &c->rns2);
+    if (r) return fail(c, r.code, r.msg);
     c->have_rns2 = true;
     return SGFHE_OK;
 }

@@ -15,70 +15,17 @@
 #pragma once
 
 #include "ntt.h"
+#include "constants.h"
 
 namespace sgfhe {
 
-typedef unsigned __int128 u128;
-
-constexpr int NPR_MAX = 7;  // at most this many RNS primes (p_i < 2^29); a ctx uses the fewest whose
-                            // product covers 5 m B Q (4 at Params(64), 5 at Params(512/1024))
 constexpr int LOGE = 4;  // points per thread (2^LOGE) in every NTT of the engine
 
-struct PrimeK {
-    int32_t p;        // prime, < 2^29
-    uint32_t pinv;    // p^-1 mod 2^32
-    int32_t sR;       // -(s R^-1) mod p, centred (digit offset s of utils.jl:162-166, R = 2^32)
-    int32_t sRr;      // the same for the randomised flatten: offset s + xmax (utils.jl:198-241)
-    uint32_t hoff;    // offset added to the output residue: (p-1)/2 for the last prime, else 0
-    int32_t r1, r2, r3;  // R, R^2, R^3 mod p, centred
-    int32_t qmodp;    // Q mod p, centred
-    int32_t kappaR;   // key scale kappa * R mod p (centred), kappa = R^2 m^-1 (M/p)^-1 mod p
-    int32_t minvR;    // m^-1 * R mod p, centred (debug inverse NTT scaling)
-    float invp;       // 1 / p
-    const int32_t *twf;  // forward twiddles psi^bitrev(i) * R mod p (Montgomery form, centred)
-    const int32_t *twi;  // inverse twiddles psi^-bitrev(i) * R mod p
-    uint32_t npr;     // number of primes of the ctx (the same in every record)
-    // quarter form of the latency kernels (k_fwd_quarter / k_inv_quarter / k_crt_lean1q):
-    int32_t f1, f2, f3, fp2, fp3;   // forward twiddles of the first two stages: twf[1..3], and the products twf[2 m + 2], [2 m + 3]
-    int32_t v1, v2, v3;             // inverse twiddles of the last two stages: twi[1..3]
-    const int32_t *twq;  // twiddle tables of the four quarter transforms: block q = [f_q | v_q | fp_q | vp_q], m / 4 words each
-    const int32_t *pw;   // psi^e * R mod p, centred, e in [0, 2 m): (x^j - 1) in the NTT domain is psi^(j (2 brv(s) + 1)) - 1 at slot s
-};
 __device__ __forceinline__ Mod mod_of(const PrimeK &P) { return Mod{P.p, -P.p, P.pinv}; }
 
 // The npr PrimeK records live in device memory and are indexed by the (wave-uniform) prime
 // index of the workgroup.
 typedef const PrimeK *__restrict__ PrimeSet;
-
-constexpr int CRT_ALPHA_MAX = 6 * NPR_MAX + 2;  // entries of the alpha-indexed CRT correction table
-
-// CRT / flatten constants, resident in device memory.
-struct CrtConst {
-    u128 Q, B;
-    u128 c[NPR_MAX];     // (M / p_i) mod Q
-    u128 T[CRT_ALPHA_MAX];   // (-alpha * M - H') mod Q,  H' = (M / p_last) * (p_last - 1) / 2;
-                             // alpha < 6 npr + 1: the residues are non-negative representatives
-                             // below 5.7 p (6.2 p for the last prime), not canonical ones
-    u128 offneg;         // (Q - off) mod Q, off = (1 + B) s mod Q
-    u128 offneg_rnd;     // the same with s + xmax in place of s (randomised flatten)
-    uint64_t xmax;       // v_i uniform in [-xmax, xmax], xmax = 3 (B / 2) (utils.jl:210-214)
-    u128 DQ;             // DQ_tilde mod Q
-    u128 halfQ;          // Q / 2 (centred lift of key residues)
-    u128 roundthr;       // Q / 2 + (Q odd)        (utils.jl:84)
-    double invQ, invB;
-    // 32-bit limb / double views of the same constants for k_crt_acc's 96-bit arithmetic
-    uint32_t c32[NPR_MAX][3];
-    uint32_t Q32[3];
-    alignas(16) uint32_t T32[CRT_ALPHA_MAX][4];
-    double cd[NPR_MAX], Td[CRT_ALPHA_MAX], Bd;
-    float invp[NPR_MAX];
-    uint32_t npr;        // number of primes in use
-    uint32_t logr;
-    ulonglong2 dig0, digP, digN;  // (lo, hi) digits of x' for acc = 0, DQ_tilde, Q - DQ_tilde
-    // LUT rows (sgfhe_bootstrap_lut_batch) start at a quarter of the amplitude
-    u128 DQL;                     // A0 = DQ_tilde >> 2
-    ulonglong2 digPL, digNL;      // digits of x' for acc = A0, Q - A0
-};
 
 // A call's optional per-row LUT descriptor (bootstrap_device): one word per row of the call, LUT_ROW | truth table for
 // a LUT row, 0 for a row of the classic path.
@@ -895,25 +842,7 @@ k_crt_acc2(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
 // width and both estimates checked against the exact quotients.
 // Four adjacent coefficients per thread: 16-byte residue and digit-word accesses, 8-byte accesses
 // of the 16-bit high words.
-struct CrtLean {
-    uint32_t c[NPR_MAX][4];   // (M / p_i) mod Q in 29-bit limbs
-    uint32_t w[NPR_MAX];      // floor(2^58 / p_i)
-    uint32_t cMn[4];          // (-M) mod Q in 29-bit limbs
-    uint32_t hoff;            // (p_last - 1) / 2, the offset k_extprod adds to the last prime's residue
-    uint32_t Qw[3];           // Q in 32-bit words
-    uint32_t B0, B1;          // B = B0 + B1 2^29
-    uint32_t Bw0, Bw1;        // B in 32-bit words
-    uint32_t mq0, mq1;        // floor(2^(t + 72) / Q)
-    uint32_t mb0, mb1;        // floor(2^(bits(B) + 51) / B)
-    uint32_t a;               // top limb sum << a, the next >> 29 - a, the next >> 58 - a
-    uint32_t t2, sB;          // x >> t2;  final shift of the digit estimate
-    uint32_t nl;              // limbs in use (2, 3 or 4); 0 = parameter set outside this kernel's bounds
-    uint32_t cR[4];           // randomised flatten: (-2 xmax (1 + B)) mod Q in 29-bit limbs
-    uint32_t xm2lo, xm2hi;    //   2 xmax
-    uint32_t p87;             // 1: crt_lean87_one applies (five primes, Q of 87 bits, B of 44 bits)
-    uint32_t mqw0, mqw1;      //   floor(2^122 / Q)
-    uint32_t mbw0, mbw1;      //   floor(2^96 / B)
-};
+// (struct CrtLean, the constants: constants.h)
 
 // (x m) >> 64 for x < 2^63.5 and m = m1 2^32 + m0 with m1 <= 2^20
 __device__ __forceinline__ uint64_t mulhi64_lean(uint64_t x, uint32_t m0, uint32_t m1) {
@@ -2705,9 +2634,7 @@ k_key_transform(const ulonglong2 *__restrict__ canon, int32_t *__restrict__ keyh
 // mod p_i -- one constant per prime, no transform.  fac.f[i] = that constant in Montgomery form, centred.
 // The result is the centred canonical residue, i.e. byte for byte what k_key_transform writes for the
 // smaller basis.  One thread per element of the smaller key: keyhat[k][prime][row * 2 + col][slot].
-struct KeyFactors {
-    int32_t f[NPR_MAX];
-};
+// (struct KeyFactors: constants.h, where key_factors derives it)
 __global__ void __launch_bounds__(256)
 k_key_derive(const int32_t *__restrict__ big, int32_t *__restrict__ small, PrimeSet PS, KeyFactors fac,
              uint32_t npb, uint32_t nps, uint32_t logm, size_t total) {
@@ -2730,11 +2657,7 @@ k_key_derive(const int32_t *__restrict__ big, int32_t *__restrict__ small, Prime
 // c1 = m2 (m2^-1 mod m1) and c2 = m1 (m1^-1 mod m2) that is
 //   x = ((v1 i21) mod m1) m2 + ((v2 i12) mod m2) m1,  minus Q if >= Q.
 // Both kernels work in place on 16-byte elements ({v1, v2} <-> {x lo, x hi}).
-struct Rns2Const {
-    uint64_t m1, m2;   // limb moduli, distinct primes below 2^47
-    uint64_t i21, i12; // m2^-1 mod m1, m1^-1 mod m2
-    double inv1, inv2; // 1 / m1, 1 / m2
-};
+// (struct Rns2Const: constants.h, where rns2_const derives it)
 __global__ void __launch_bounds__(256)
 k_rns2_to_canon(ulonglong2 *__restrict__ buf, size_t count, Rns2Const rc,
                 const CrtConst *__restrict__ CC, uint32_t *__restrict__ bad) {

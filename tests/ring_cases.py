@@ -14,8 +14,8 @@ costs milliseconds:
   m128       n = 16, Q ~ 2^52, B = 2^27 (test_random_mode_equals_oracle_bit_for_bit, "synthetic"): m = 128, the other pass
              structure of the small NTT
 
-`kernels[rnd]` is what Engine.kernel_names() must report in that flatten mode, derived from crt_form / build_basis of
-csrc/engine.hip: the primes are the fewest below 2^29 whose product covers 5 m B Q (20 m B Q randomised), the limbs
+`kernels[rnd]` is what Engine.kernel_names() must report in that flatten mode, derived from crt_form of csrc/engine.hip
+and plan_bases / derive_basis of csrc/constants.h: the primes are the fewest below 2^29 whose product covers 5 m B Q (20 m B Q randomised), the limbs
 ceil(bits of Q / 29) with two at least, and the lean kernels need B >= 2^12 and Q >= 2^29.  `random`: the ctx has the
 randomised mode (2 log2 B + 2 - log2 Q < 50; all five do), `pack[rnd]`: the pack stage in that mode (the primes chosen
 for the k-loop leave the factor 0.8 n its sums need on all five).  `noise`: the bound of the key's error draws -- 2 as in the

@@ -1,5 +1,5 @@
 """
-Host model of the device algorithm (sgfhe.jl_amd/csrc/{rns_arith,ntt,kernels}.h, engine.hip):
+Host model of the device algorithm (sgfhe.jl_amd/csrc/{constants,rns_arith,ntt,kernels}.h, engine.hip):
 same RNS primes, constants, pass structure, LDS swizzle and index formulas, written with numpy so
 that the restructured algorithm and its indexing can be checked against the oracle without a GPU.
 Test infrastructure only (used by tests/test_rns_model.py).
@@ -11,7 +11,12 @@ NPR_MAX = 7
 MASK32 = 0xFFFFFFFF
 
 
-# ---- engine.hip: build_constants -------------------------------------------------------------
+# ---- csrc/constants.h: plan_bases, derive_basis, prime_tables -----------------------------------
+# (tests/test_constants_host.py holds the header to this restatement field by field)
+
+import functools
+import math
+
 
 def is_prime32(x):
     if x < 2:
@@ -36,8 +41,8 @@ def is_prime32(x):
     return True
 
 
-def rns_primes(count=NPR_MAX):
-    """The `count` largest primes below 2^29 that are 1 mod 2^15 (candidates of build_constants)."""
+@functools.lru_cache(maxsize=None)
+def _rns_primes(count):
     out = []
     kk = ((1 << 29) - 1) >> 15
     while len(out) < count:
@@ -45,22 +50,62 @@ def rns_primes(count=NPR_MAX):
         if cand < (1 << 29) and is_prime32(cand):
             out.append(cand)
         kk -= 1
-    return out
+    return tuple(out)
 
 
-def select_npr(logm, B, Q, random_flatten=False):
-    """build_constants: the fewest primes covering 5 m B Q (20 m B Q when the ctx is created for
-    the randomised flatten), at least 2; same floating-point rule as the engine."""
-    import math
+def rns_primes(count=NPR_MAX):
+    """The `count` largest primes below 2^29 that are 1 mod 2^15 (candidates of plan_bases)."""
+    return list(_rns_primes(count))
+
+
+def u128_dbl(x):
+    """constants.h u128_dbl: the double the engine takes for a 128-bit value (high and low word rounded apart)."""
+    return float(x >> 64) * 18446744073709551616.0 + float(x & ((1 << 64) - 1))
+
+
+def fewest_primes(logm, B, Q, random_flatten=False):
+    """plan_bases: (npr, log_have, log_mbq) -- the fewest primes covering 5 m B Q (20 m B Q for the randomised
+    flatten), at least 2, by the engine's floating-point rule, term for term; npr = 0 where all NPR_MAX do not cover it."""
     cand = rns_primes()
-    need = math.log2(5.0) + logm + math.log2(float(B)) + math.log2(float(Q)) + 0.001
-    target = need + (2.0 if random_flatten else 0.0)
+    mbq = logm + math.log2(u128_dbl(B)) + math.log2(u128_dbl(Q))
+    target = math.log2(5.0) + mbq + 0.001
+    if random_flatten:
+        target = target + 2.0
     have, k = 0.0, 0
     while k < NPR_MAX and (k < 2 or have < target):
         have += math.log2(float(cand[k]))
         k += 1
-    assert have >= target, "exactness bound"
+    return (k if have >= target else 0), have, mbq
+
+
+def select_npr(logm, B, Q, random_flatten=False):
+    """plan_bases: the number of primes of the basis sized for a flatten mode."""
+    k = fewest_primes(logm, B, Q, random_flatten)[0]
+    assert k, "exactness bound"
     return k
+
+
+def pack_group(n, logm, B, Q, random_flatten=False, sized_for=None):
+    """derive_basis: key slices per exact-accumulation group of the packing path in a flatten mode, on the basis sized
+    for that mode (or for the mode `sized_for`) -- the largest power of two, n at most, with G m B Q / 2 (four times
+    that randomised) below 0.4 of the primes' product; 0 where not even one slice fits.  The engine's floating-point
+    rule, term for term."""
+    _, have, mbq = fewest_primes(logm, B, Q, random_flatten if sized_for is None else sized_for)
+    lg = have + math.log2(0.8) - mbq - 0.001
+    if random_flatten:
+        lg = lg - 2.0
+    G = 0
+    if lg >= 0:
+        G = 1
+        while G < n and (2 * G).bit_length() - 1 <= lg:
+            G *= 2
+    return G
+
+
+def basis(p, rnd):
+    """(primes, pack group) of the ctx's basis for a flatten mode (p: a parameter set with n, m, Q, B)."""
+    logm = p.m.bit_length() - 1
+    return rns_primes()[:select_npr(logm, p.B, p.Q, rnd)], pack_group(p.n, logm, p.B, p.Q, rnd)
 
 
 def bitrev(x, bits):
@@ -76,11 +121,51 @@ def centre(x, p):
     return x - p if x > (p - 1) // 2 else x
 
 
+@functools.lru_cache(maxsize=None)
+def prime_tables(p, m):
+    """constants.h prime_tables: psi and the four twiddle tables of a prime (shared by every Consts of that m; read-only)."""
+    logm = m.bit_length() - 1
+    psi = None
+    for x in range(2, 2000):
+        g = pow(x, (p - 1) // (2 * m), p)
+        if pow(g, m, p) == p - 1:
+            psi = g
+            break
+    ipsi = pow(psi, p - 2, p)
+    R1 = (1 << 32) % p
+    twf = np.zeros(m, dtype=np.int64)
+    twi = np.zeros(m, dtype=np.int64)
+    pf, pv = [0] * m, [0] * m
+    pw = ipw = 1
+    for t in range(m):
+        br = bitrev(t, logm)
+        twf[br] = centre(pw * R1, p)          # Montgomery form, centred
+        twi[br] = centre(ipw * R1, p)
+        pf[br], pv[br] = pw, ipw
+        pw = pw * psi % p
+        ipw = ipw * ipsi % p
+    # product twiddles of the forward radix-4 steps (table tw + 2 m on the device):
+    # twfp[j] = +-tw[j >> 1] tw[j], minus for odd j
+    twfp = np.zeros(m, dtype=np.int64)
+    twip = np.zeros(m, dtype=np.int64)
+    for j in range(2, m):
+        v = pf[j >> 1] * pf[j] % p * R1 % p
+        twfp[j] = centre((p - v) % p if j & 1 else v, p)
+        v = pv[j >> 1] * pv[j] % p * R1 % p
+        twip[j] = centre((p - v) % p if j & 1 else v, p)
+    for t in (twf, twi, twfp, twip):
+        t.setflags(write=False)
+    return dict(psi=psi, twf=twf, twi=twi, twfp=twfp, twip=twip)
+
+
 class Consts:
-    def __init__(self, n, m, Q, B, DQ_tilde, random_flatten=False):
+    """derive_basis of one basis: the one sized for the flatten mode, or the first `npr` candidates.  tables=False
+    leaves the twiddle tables (and psi) out of pk[i]."""
+
+    def __init__(self, n, m, Q, B, DQ_tilde, random_flatten=False, tables=True, npr=None):
         self.n, self.M, self.Q, self.B = n, m, Q, B
         self.logm = m.bit_length() - 1
-        self.npr = NPR = select_npr(self.logm, B, Q, random_flatten)
+        self.npr = NPR = npr if npr is not None else select_npr(self.logm, B, Q, random_flatten)
         self.primes = rns_primes()[:NPR]
         prod = 1
         for p in self.primes:
@@ -99,34 +184,7 @@ class Consts:
         self.T = [(Q - (a * cM + cH) % Q) % Q for a in range(6 * NPR + 2)]
         self.pk = []
         for i, p in enumerate(self.primes):
-            psi = None
-            for x in range(2, 2000):
-                g = pow(x, (p - 1) // (2 * m), p)
-                if pow(g, m, p) == p - 1:
-                    psi = g
-                    break
-            ipsi = pow(psi, p - 2, p)
             R1 = (1 << 32) % p
-            twf = np.zeros(m, dtype=np.int64)
-            twi = np.zeros(m, dtype=np.int64)
-            pf, pv = [0] * m, [0] * m
-            pw = ipw = 1
-            for t in range(m):
-                br = bitrev(t, self.logm)
-                twf[br] = centre(pw * R1, p)          # Montgomery form, centred
-                twi[br] = centre(ipw * R1, p)
-                pf[br], pv[br] = pw, ipw
-                pw = pw * psi % p
-                ipw = ipw * ipsi % p
-            # product twiddles of the forward radix-4 steps (table tw + 2 m on the device):
-            # twfp[j] = +-tw[j >> 1] tw[j], minus for odd j
-            twfp = np.zeros(m, dtype=np.int64)
-            twip = np.zeros(m, dtype=np.int64)
-            for j in range(2, m):
-                v = pf[j >> 1] * pf[j] % p * R1 % p
-                twfp[j] = centre((p - v) % p if j & 1 else v, p)
-                v = pv[j >> 1] * pv[j] % p * R1 % p
-                twip[j] = centre((p - v) % p if j & 1 else v, p)
             Rinv = pow(R1, p - 2, p)
             Mi = prod // p % p
             ei = pow(Mi, p - 2, p)
@@ -137,7 +195,9 @@ class Consts:
                 sRr=centre(-((self.s + self.xmax) % p) * Rinv, p),
                 hoff=(p - 1) // 2 if i == NPR - 1 else 0, r1=centre(R1, p), r2=centre(R1 * R1, p),
                 r3=centre(R1 * R1 * R1, p), qmodp=centre(Q, p), kappaR=centre(kappa * R1, p),
-                minvR=centre(minv * R1, p), twf=twf, twi=twi, twfp=twfp, twip=twip, psi=psi, kappa=kappa, ei=ei))
+                minvR=centre(minv * R1, p), kappa=kappa, ei=ei))
+            if tables:
+                self.pk[-1].update(prime_tables(p, m))
 
     def digits_of(self, acc):
         x = (acc + self.off) % self.Q
@@ -605,7 +665,7 @@ class RangeModel:
 
 # ---- k_crt_lean (kernels.h): the k-loop's CRT + accumulate + flatten in integer arithmetic -------
 # Model of the device algorithm with every intermediate checked against the width of the register
-# it lives in.  Constants as build_constants derives them.
+# it lives in.  Constants as derive_basis (csrc/constants.h) derives them.
 
 M64 = (1 << 64) - 1
 
@@ -625,7 +685,7 @@ class CrtLean:
         Q, B, npr = C.Q, C.B, C.npr
         self.nq, self.nb = Q.bit_length(), B.bit_length()
         self.NL = NL = max(2, -(-self.nq // 29))
-        self.ok = self.nb >= 13 and NL <= 4 and 29 * (NL - 1) - (self.nq - 29) <= 28
+        self.ok = self.nb >= 13 and NL <= 4 and self.nq >= 30 and 0 <= 29 * (NL - 1) - (self.nq - 29) <= 28   # (derive_basis)
         if not self.ok:
             return
         lim = lambda v: [(v >> (29 * k)) & ((1 << 29) - 1) for k in range(NL)]

@@ -81,8 +81,8 @@ def test_library_records_its_sources(S):
 def test_header_documents_what_the_engine_accepts():
     """The two places round 2's header had drifted from the engine."""
     hdr = open(HDR).read()
-    eng = open(os.path.join(ROOT, "sgfhe.jl_amd", "csrc", "engine.hip")).read()
-    assert "B < 2^47" in hdr and "(c->B >> 47)" in eng
+    chk = open(os.path.join(ROOT, "sgfhe.jl_amd", "csrc", "constants.h")).read()      # check_params
+    assert "B < 2^47" in hdr and "(B >> 47)" in chk
     assert "Always the deterministic flatten" not in hdr
 
 

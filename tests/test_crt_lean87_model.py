@@ -2,7 +2,7 @@
 87 bits and B of 44 bits (Params(1024)).  Every intermediate is checked against the register it lives
 in, both quotient estimates against the exact quotients, and the digits against the generic form
 (rns_model.CrtLean) and the exact (x_old + D) mod Q, on every parameter set the engine hands the
-specialisation (build_constants: npr = 5, bits(Q) = 87, bits(B) = 44) and at the edges of that range."""
+specialisation (derive_basis of csrc/constants.h: npr = 5, bits(Q) = 87, bits(B) = 44) and at the edges of that range."""
 
 import random
 
@@ -14,7 +14,7 @@ M32, M64, M96 = (1 << 32) - 1, (1 << 64) - 1, (1 << 96) - 1
 
 
 def accepts(C):
-    """build_constants: the engine takes crt_lean87_one for this ctx."""
+    """derive_basis: the engine takes crt_lean87_one for this ctx."""
     return C.npr == 5 and C.Q.bit_length() == 87 and C.B.bit_length() == 44
 
 
@@ -114,7 +114,7 @@ def _cases():
     for name in ("params1024", "rns2"):
         p = bench.make_params(S, name)
         yield name, (p.n, p.m, p.Q, p.B, p.DQ_tilde)
-    # the edges of what build_constants hands the specialisation: Q of 87 bits, B of 44 bits
+    # the edges of what derive_basis hands the specialisation: Q of 87 bits, B of 44 bits
     for i, (Q, B) in enumerate((((1 << 86) + 1, 1 << 43), ((1 << 87) - 1, (1 << 44) - 1),
                                 ((1 << 86) + 1, (1 << 44) - 1), ((1 << 87) - 1, 1 << 43),
                                 ((1 << 87) - 12345, (1 << 43) + 987), (0x5a5a5a5a5a5a5a5a5a5a5b, 0xb0b0b0b0b0b))):

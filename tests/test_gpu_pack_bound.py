@@ -27,6 +27,7 @@ import bigint_oracle as BO
 import keygen_cases as KC
 import pack_direct_ref as R
 import ring_cases as RC
+import rns_model as RM
 from conftest import oracle_threads
 
 pytestmark = pytest.mark.gpu
@@ -36,36 +37,11 @@ KEY_PATTERNS = ("all +", "all -", "column 0 +, column 1 -", "alternating", "jitt
 BIGINT_RING = "limb64"          # also against tail_bigint: two groups deterministic, a basis per mode
 
 
-# ---- the sizing rule, restated (build_constants / build_basis of csrc/engine.hip) ---------------------------------------
-
-def _candidates():
-    out, k = [], ((1 << 29) - 1) >> 15
-    while len(out) < 7:
-        c = (k << 15) + 1
-        if c < (1 << 29) and BO.is_prime(c):
-            out.append(c)
-        k -= 1
-    return out
-
-
-def basis(p, rnd):
-    """(primes, pack group) of the ctx's basis for a flatten mode: the fewest of the largest primes below 2^29 with
-    p = 1 mod 2^15 whose product covers 5 m B Q (20 m B Q randomised), two at least; G the largest power of two, n at
-    most, with G m B Q / 2 (four times that randomised) below 0.4 of the product."""
-    cand = _candidates()
-    mbq = math.log2(p.m) + math.log2(p.B) + math.log2(p.Q)
-    need = math.log2(5.0) + mbq + 0.001 + (2.0 if rnd else 0.0)
-    k, have = 0, 0.0
-    while k < len(cand) and (k < 2 or have < need):
-        have += math.log2(cand[k])
-        k += 1
-    lg = have + math.log2(0.8) - mbq - 0.001 - (2.0 if rnd else 0.0)
-    G = 0
-    if lg >= 0:
-        G = 1
-        while G < p.n and (2 * G).bit_length() - 1 <= lg:
-            G *= 2
-    return cand[:k], G
+# The sizing rule (plan_bases / derive_basis of csrc/constants.h), restated once in rns_model: (primes, pack group) of the
+# ctx's basis for a flatten mode -- the fewest of the largest primes below 2^29 with p = 1 mod 2^15 whose product covers
+# 5 m B Q (20 m B Q randomised), two at least; G the largest power of two, n at most, with G m B Q / 2 (four times that
+# randomised) below 0.4 of the product.
+basis = RM.basis
 
 
 # ---- operands ------------------------------------------------------------------------------------------------------------
@@ -213,7 +189,7 @@ def test_tail_on_chosen_operands(S, oc, ring, rnd):
     finally:
         eng.set_random_flatten(False)
     top = max(worst, key=worst.get)
-    sized = G * p.m * p.B * p.Q // 2 * (4 if rnd else 1)      # what build_basis sizes pack_G for
+    sized = G * p.m * p.B * p.Q // 2 * (4 if rnd else 1)      # what derive_basis sizes pack_G for
     print("pack margin %-9s %-13s %d primes, G = %2d of n = %2d (%d groups): max |group sum| = %.3g of 0.4 M, %.3g of the "
           "G m B Q / 2%s the group is sized for  (key %s, LWEs %s)"
           % (rg.name, RC.MODE_IDS[rnd], len(primes), G, n, n // G, worst[top],

@@ -333,7 +333,7 @@ def test_crt_lean_random_model(name, args):
 # ---- the quarter form of the latency kernels (round 4: k_fwd_quarter / k_inv_quarter / k_crt_lean1q) ----
 
 def _quarter_tables(P, logm):
-    """engine.hip build_basis: entry mm' + i' of quarter q's tables = entry 4 mm' + q mm' + i' of the big ones."""
+    """constants.h prime_tables: entry mm' + i' of quarter q's tables = entry 4 mm' + q mm' + i' of the big ones."""
     m, ms = 1 << logm, 1 << (logm - 2)
     out = []
     for q in range(4):

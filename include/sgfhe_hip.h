@@ -586,6 +586,38 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * wire is measured, against its own codeword, WHEN IT HAS A SLOT -- when a node or an output reads it -- from the
  * slot's rows of that call.  A sibling wire that nothing reads is never written anywhere and gets an all-zero record,
  * as the wires of dead siblings do: the one place where "every wire of every live node" does not extend.
+ *
+ * Data planes (sgfhe_circuit_create_data): truth tables that differ from instance to instance.  The arrays are those of
+ * sgfhe_circuit_create_lut_multi with two more kinds: node_kind[g] = 4 is a DATA LUT node -- a kind-2 node in every
+ * respect (three unit terms at positions 0, 1, 2, the scale rule, wires of scales 0, 1, 2, the output rule) whose
+ * node_table[g] is a PLANE index below n_planes, not a table -- and node_kind[g] = 5 a DATA sibling, a kind-3 node whose
+ * node_table[g] is a plane index.  A sibling of kind 3 or 5 belongs to the nearest earlier node of kind 2 or 4, node
+ * g - 1 of a sibling is of kind 2, 3, 4 or 5, and a family may mix constant and data members, SGFHE_LUT_MAX_TABLES at
+ * most.  n_planes is at most SGFHE_CIRCUIT_MAX_PLANES; a plane may be used by several nodes or by none.  A plane index
+ * that is not below n_planes, or n_planes above the cap, is SGFHE_ERR_INVALID_ARG with *out NULL and nothing allocated.
+ * Every other creator keeps rejecting kinds 4 and 5.  Pruning, liveness, levels, slots, rows, calls, call numbers and
+ * sgfhe_circuit_info are those of the same arrays with kind 4 read as 2 and kind 5 as 3; with n_planes = 0 and no node
+ * of kind 4 or 5 the plan is the sgfhe_circuit_create_lut_multi plan.  sgfhe_circuit_planes gives n_planes (0 for a plan
+ * of any other creator).
+ * The run entries sgfhe_circuit_run_data, _run_ct_data and _run_probe_data take `data`, [n_planes][instances] uint8
+ * (instances = blocks * n in the ciphertext form, numbered as sgfhe_circuit_run_ct numbers them): at instance t a data
+ * node or data sibling of plane p has the truth table data[p][t], bit s its value at s = x0 + 2 x1 + 4 x2 -- at the
+ * node's OWN instance, whatever lane shifts its terms carry.  Any byte is a table; `data` is not validated beyond NULL.
+ * The planes go up once per run into a buffer kept on the ctx like the wire table (grown on demand, freed by
+ * sgfhe_release_host_staging and sgfhe_ctx_destroy); no host synchronisation is added.  The contract: the run is, byte
+ * for byte, the run of the constant-table plan with each row evaluated under its own table -- calls, rows, call numbers
+ * and every row's draws unchanged, in both flatten modes, reduced and un-reduced, under every flag set of
+ * sgfhe_circuit_run_ct_ex.  Row R of a level call of a data leader is the row of sgfhe_bootstrap_lut_batch with
+ * table[R] = data[p][R % instances]; a live data sibling's three wires are what the leader's would be under the
+ * sibling's byte at that instance.  An output naming wire +0 of a data node or data sibling is refreshed, or lifted
+ * under SGFHE_CIRCUIT_PACK_LIFT, as for kinds 2 and 3.  The probe variant evaluates the plaintext circuit with `data`
+ * and measures data wires by the rules of LUT and sibling wires (a sibling wire without a slot: an all-zero record).
+ * The table does not enter the k-loop, so the noise rule is that of LUT nodes and no new rule is claimed.
+ * Errors, before anything is queued or written: SGFHE_ERR_INVALID_ARG for data == NULL when the plan has planes and
+ * instances > 0, and for everything the entry without data rejects; SGFHE_ERR_NO_KEY and SGFHE_ERR_OOM as there.  A
+ * plan without planes may go through the _data entries with data NULL: that run is the old entry.  sgfhe_circuit_run,
+ * _run_ct, _run_ct_ex and _run_probe return SGFHE_ERR_INVALID_ARG for a plan with planes, write nothing and consume no
+ * call number.
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -628,6 +660,17 @@ int32_t sgfhe_circuit_create_lut_multi(uint32_t n_inputs,
                                        size_t n_gates, const uint32_t *outputs,
                                        const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
                                        uint32_t group, sgfhe_circuit **out);
+#define SGFHE_CIRCUIT_MAX_PLANES 65536u
+int32_t sgfhe_circuit_create_data(uint32_t n_inputs, uint32_t n_planes,
+                                  const uint32_t *node_kind /* [n_gates]: 0 .. 3 as above, 4 = data LUT node, 5 = data sibling */,
+                                  const uint32_t *node_start /* [n_gates + 1], CSR into the term arrays, [0] = 0 */,
+                                  const uint32_t *term_ref, const int32_t *term_shift /* NULL = all 0 */,
+                                  const int32_t *term_weight,
+                                  const uint32_t *node_table /* [n_gates]: a table for kinds 2 and 3, a plane for 4 and 5 */,
+                                  size_t n_gates, const uint32_t *outputs,
+                                  const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
+                                  uint32_t group, sgfhe_circuit **out);
+int32_t sgfhe_circuit_planes(const sgfhe_circuit *c, uint32_t *n_planes);   /* 0 for every other creator */
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
@@ -876,6 +919,15 @@ int32_t sgfhe_lwe_noise(sgfhe_ctx *ctx, const uint64_t *sk, const uint64_t *lwe,
                         size_t row_stride_words, const uint8_t *expected, uint32_t flags, uint64_t stats[8]);
 int32_t sgfhe_circuit_run_probe(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
                                 uint64_t *out, const uint64_t *sk, const uint8_t *in_bits, uint64_t *stats);
+/* The run entries of a plan with data planes ("Data planes" above): data [n_planes][instances] uint8. */
+int32_t sgfhe_circuit_run_data(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
+                               const uint8_t *data, uint64_t *out);
+int32_t sgfhe_circuit_run_ct_data(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, const uint64_t *in_a,
+                                  const uint64_t *in_b, size_t N, const uint8_t *data, uint64_t *out_w,
+                                  uint64_t *out_v, uint64_t *out_lwe, uint32_t flags);
+int32_t sgfhe_circuit_run_probe_data(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
+                                     const uint8_t *data, uint64_t *out, const uint64_t *sk, const uint8_t *in_bits,
+                                     uint64_t *stats);
 
 /*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled

@@ -42,6 +42,13 @@ same three wires on ONE bootstrap: the k-loop does not depend on the table, so e
 extraction of the same accumulator and no row.  The first table is the family's leader, a LUT node; each other is a
 SIBLING, a node with no inputs of its own whose three wires are numbered like any node's.  `shannon(c, tables, xs)`
 builds any functions of k >= 3 wires this way: all cofactors on (x0, x1, x2) are one family, a mux tree follows.
+
+Data planes (sgfhe_circuit_create_data).  Circuit(n_inputs, planes=P) has P planes of run-time data: a run takes
+`data`, uint8 [P][instances], and `lut_data(p, x0, x1, x2)` is the LUT node whose truth table at instance t is
+data[p][t] -- public data that differs from instance to instance, in one bootstrap, with no extra rows or inputs.
+`Circuit.plane(p)` among the tables of lut_multi makes that member a data table.  `lookup(c, xs)` with
+`lookup_data(tables, k)` is shannon with per-instance tables: T_t[x] for a different public table T_t at every instance.
+The table never enters the k-loop: rows, calls, draws and the noise rule are those of the constant-table circuit.
 """
 
 import ctypes
@@ -55,6 +62,7 @@ FALSE_ID = 0x7FFFFFFF      # SGFHE_CIRCUIT_FALSE
 NONE_ID = 0x7FFFFFFE       # SGFHE_CIRCUIT_NONE: the third reference of a two-input node
 NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
 MAX_TERMS = 64             # SGFHE_CIRCUIT_MAX_TERMS
+MAX_PLANES = 65536         # SGFHE_CIRCUIT_MAX_PLANES
 LUT_MAX_TABLES = 256       # SGFHE_LUT_MAX_TABLES
 CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
 
@@ -95,24 +103,40 @@ class Wire:
                                  ".lane(%+d)" % self.shift if self.shift else "")
 
 
+class Plane:
+    """A data plane among the tables of Circuit.lut_multi: that member's truth table is run-time data (Circuit.plane)."""
+
+    __slots__ = ("index",)
+
+    def __init__(self, index):
+        self.index = int(index)
+
+    def __repr__(self):
+        return "Plane(%d)" % self.index
+
+
 class Circuit:
     """Builder of a gate circuit: `n_inputs` input wires, nodes added with gate(), outputs set with
     output().  `group`: the lane group size (instances form consecutive groups of `group` lanes; a reference may be
     shifted by |d| < group lanes, Wire.lane).  The C plan (sgfhe_circuit_create, sgfhe_circuit_create_lanes when
     the group is above 1, sgfhe_circuit_create3 when a gate3 exists, sgfhe_circuit_create_w when a sum node exists that
     is no three-input node, sgfhe_circuit_create_lut when a LUT node exists, sgfhe_circuit_create_lut_multi when a LUT
-    sibling exists) is made on first use and freed with the object."""
+    sibling exists, sgfhe_circuit_create_data when the circuit has planes) is made on first use and freed with the object.
+    `planes`: the number of data planes a run brings (lut_data, Circuit.plane), uint8 [planes][instances]."""
 
     FALSE = Wire(FALSE_ID)
     TRUE = Wire(FALSE_ID | NOT_BIT)
 
-    def __init__(self, n_inputs, group=1):
+    def __init__(self, n_inputs, group=1, planes=0):
         if not 0 <= int(n_inputs) < FALSE_ID:
             raise ValueError("n_inputs out of range")
         if not 1 <= int(group) <= 0xFFFFFFFF:
             raise ValueError("group out of range")
+        if not 0 <= int(planes) <= MAX_PLANES:
+            raise ValueError("planes out of range (at most %d)" % MAX_PLANES)
         self.n_inputs = int(n_inputs)
         self.group = int(group)
+        self.planes = int(planes)
         self.inputs = [Wire(i) for i in range(self.n_inputs)]
         self.gates = []            # [(x ref, y ref)], or (x ref, y ref, z ref) for a three-input node
         self.outputs = []          # [ref]
@@ -120,6 +144,7 @@ class Circuit:
         self.gate_weights = {}     # node -> (weight, ...) beside its references: the sum nodes (sum_node)
         self.gate_tables = {}      # node -> truth table: the LUT nodes (lut) and their siblings (lut_multi)
         self.gate_leader = {}      # sibling -> its leader, a LUT node: no inputs of its own, () in gates and gate_shifts
+        self.gate_planes = {}      # data LUT node or data sibling -> its plane (its entry of gate_tables is None)
         self.output_shifts = []    # [lane shift], beside outputs
         self._plan = None
         self._L = None
@@ -192,30 +217,70 @@ class Circuit:
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
 
+    @staticmethod
+    def plane(p):
+        """Plane p as a member of lut_multi's tables: the member's truth table at instance t is data[p][t]."""
+        return Plane(p)
+
+    def _plane(self, p):
+        if not 0 <= int(p) < self.planes:
+            raise ValueError("plane %r is not below the circuit's %d planes (Circuit(planes=...))" % (p, self.planes))
+        return int(p)
+
+    def lut_data(self, plane, x0, x1, x2):
+        """One DATA LUT node: lut(table, x0, x1, x2) whose table at instance t is the byte data[plane][t] of the run's
+        data (evaluate_circuit(..., data=...)), read at the node's own instance whatever lane shifts its inputs carry.
+        Scales, wires and cost are those of lut."""
+        plane = self._plane(plane)
+        out = self.lut(0, x0, x1, x2)
+        self.gate_tables[len(self.gates) - 1] = None
+        self.gate_planes[len(self.gates) - 1] = plane
+        return out
+
     def lut_multi(self, tables, x0, x1, x2):
         """A LUT family: 1 to 256 functions of the same three wires on ONE bootstrap.  tables[0] is the table of the
         LUT node lut(tables[0], x0, x1, x2), the family's leader; every further table is a sibling -- a node that takes
-        no row of its level, whose wires are extracted from the leader's accumulator.  Returns one (f, f_half,
-        f_quarter) triple per table, the leader's first."""
-        tables = [int(t) for t in tables]
+        no row of its level, whose wires are extracted from the leader's accumulator.  A member may be Circuit.plane(p)
+        in place of a table: its table is run-time data (lut_data); planes are not de-duplicated.  Returns one (f,
+        f_half, f_quarter) triple per table, the leader's first."""
+        tables = [t if isinstance(t, Plane) else int(t) for t in tables]
         if not 1 <= len(tables) <= LUT_MAX_TABLES:
             raise ValueError("a LUT family has 1 to %d tables" % LUT_MAX_TABLES)
-        if any(not 0 <= t < 256 for t in tables):
+        if any(not isinstance(t, Plane) and not 0 <= t < 256 for t in tables):
             raise ValueError("a LUT node's table has 8 entries: 0 .. 255")
-        out = [self.lut(tables[0], x0, x1, x2)]
+        for t in tables:
+            if isinstance(t, Plane):
+                self._plane(t.index)
+        if isinstance(tables[0], Plane):
+            out = [self.lut_data(tables[0].index, x0, x1, x2)]
+        else:
+            out = [self.lut(tables[0], x0, x1, x2)]
         leader = len(self.gates) - 1
         for t in tables[1:]:
             self.gates.append(())
             self.gate_shifts.append(())
-            self.gate_tables[len(self.gates) - 1] = t
+            if isinstance(t, Plane):
+                self.gate_tables[len(self.gates) - 1] = None
+                self.gate_planes[len(self.gates) - 1] = t.index
+            else:
+                self.gate_tables[len(self.gates) - 1] = t
             self.gate_leader[len(self.gates) - 1] = leader
             base = self.n_inputs + 3 * (len(self.gates) - 1)
             out.append((Wire(base), Wire(base + 1), Wire(base + 2)))
         self._invalidate()
         return out
 
+    def node_tables(self, g, instances, data=None):
+        """The truth table of LUT node or sibling g at every instance, uint8 [instances]: its constant table, or its
+        plane of `data` ([planes][instances])."""
+        if g in self.gate_planes:
+            if data is None:
+                raise ValueError("a circuit with data planes needs data [planes=%d][instances]" % self.planes)
+            return np.asarray(data)[self.gate_planes[g]].astype(np.uint8)
+        return np.full(instances, self.gate_tables[g], dtype=np.uint8)
+
     def siblings(self, g):
-        """The siblings of LUT node g, in ascending index."""
+        """The siblings of LUT node g (constant or data), in ascending index."""
         out, h = [], g + 1
         while self.gate_leader.get(h) == g:
             out.append(h)
@@ -248,11 +313,11 @@ class Circuit:
 
     def kind(self, g):
         """Node g: "classic" (gate), "gate3", "sum" (sum_node), "lut" or "sibling" (a further table of a LUT node,
-        lut_multi)."""
+        lut_multi), "data" (lut_data) or "data_sibling" (a Circuit.plane member of lut_multi)."""
         if g in self.gate_leader:
-            return "sibling"
+            return "data_sibling" if g in self.gate_planes else "sibling"
         if g in self.gate_tables:
-            return "lut"
+            return "data" if g in self.gate_planes else "lut"
         return "sum" if g in self.gate_weights else ("gate3" if len(self.gates[g]) == 3 else "classic")
 
     def weights(self, g):
@@ -305,15 +370,22 @@ class Circuit:
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
             os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
             h = ctypes.c_void_p()
-            if self.has_wsum or self.has_lut:   # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes,
-                                                # 3 for their siblings
-                kind = np.array([{"classic": 0, "lut": 2, "sibling": 3}.get(self.kind(g), 1) for g in range(len(self.gates))],
-                                dtype=np.uint32)
+            if self.has_wsum or self.has_lut or self.planes:
+                # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes, 3 for their siblings, 4 and 5
+                # for those whose table is a data plane
+                kind = np.array([{"classic": 0, "lut": 2, "sibling": 3, "data": 4, "data_sibling": 5}.get(self.kind(g), 1)
+                                 for g in range(len(self.gates))], dtype=np.uint32)
                 start = np.cumsum([0] + [len(x) for x in self.gates]).astype(np.uint32)
                 tr = np.array([ref for x in self.gates for ref in x], dtype=np.uint32)
                 ts = np.array([d for x in self.gate_shifts for d in x], dtype=np.int32)
                 tw = np.array([w for g in range(len(self.gates)) for w in self.weights(g)], dtype=np.int32)
-                if self.has_lut:
+                if self.planes:   # (only a circuit with planes: every other keeps the creator it has)
+                    tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
+                                   for g in range(len(self.gates))], dtype=np.uint32)
+                    rc = L.sgfhe_circuit_create_data(self.n_inputs, self.planes, vp(kind), vp(start), vp(tr), vp(ts), vp(tw),
+                                                     vp(tb), len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
+                                                     ctypes.byref(h))
+                elif self.has_lut:
                     tb = np.array([self.gate_tables.get(g, 0) for g in range(len(self.gates))], dtype=np.uint32)
                     # (the new entry only when a sibling exists: every other circuit takes the entry it always took)
                     create = L.sgfhe_circuit_create_lut_multi if self.has_sibling else L.sgfhe_circuit_create_lut
@@ -406,10 +478,12 @@ class Circuit:
                 levels[level[g] - 1].append(g)
         return levels
 
-    def evaluate_plain(self, bits):
-        """The circuit in clear: bits [n_inputs][instances] (bool) -> [n_outputs][instances] (bool)."""
+    def evaluate_plain(self, bits, data=None):
+        """The circuit in clear: bits [n_inputs][instances] (bool) -> [n_outputs][instances] (bool).  data: the planes
+        of a circuit that has any, uint8 [planes][instances]."""
         bits = np.asarray(bits, dtype=bool).reshape(self.n_inputs, -1)
         inst = bits.shape[1]
+        data = check_data(self, data, inst)
         wires = {}
 
         def val(ref, d):
@@ -424,7 +498,7 @@ class Circuit:
                 if g in self.gate_tables:
                     x = [val(ref, d).astype(np.int64) for ref, d in zip(self.gates[g], self.gate_shifts[g])]
                     for h in [g] + self.siblings(g):   # (a sibling: its own table at the leader's inputs)
-                        f = ((self.gate_tables[h] >> (x[0] + 2 * x[1] + 4 * x[2])) & 1).astype(bool)
+                        f = ((self.node_tables(h, inst, data).astype(np.int64) >> (x[0] + 2 * x[1] + 4 * x[2])) & 1).astype(bool)
                         hb = self.n_inputs + 3 * h
                         wires[hb], wires[hb + 1], wires[hb + 2] = f, f, f
                     continue
@@ -443,6 +517,22 @@ class Circuit:
         if not self.outputs:
             raise ValueError("circuit has no outputs")
         return np.stack([val(ref, d) for ref, d in zip(self.outputs, self.output_shifts)])
+
+
+def check_data(circuit, data, instances):
+    """The planes of a run, checked: uint8 [circuit.planes][instances] (ValueError otherwise, and for a circuit with
+    planes and no data); None for a circuit without planes."""
+    if not circuit.planes:
+        if data is not None:
+            raise ValueError("data given for a circuit without data planes")
+        return None
+    if data is None:
+        raise ValueError("a circuit with data planes needs data [planes=%d][instances]" % circuit.planes)
+    d = np.asarray(data)
+    if d.dtype != np.uint8 or d.shape != (circuit.planes, instances):
+        raise ValueError("data must be uint8 [planes=%d][instances=%d], got %s %r"
+                         % (circuit.planes, instances, d.dtype, d.shape))
+    return d
 
 
 def lane_shift(v, d, group):
@@ -540,6 +630,17 @@ def crc16_ccitt(message_bits, refresh_inputs=True):
     return gf2_matvec(crc16_matrix(message_bits), refresh_inputs=refresh_inputs)
 
 
+def _at_scale(circuit, w, want):
+    """w at scale `want`: as it is, or through one LUT node at its own position (the table of "the input at position p")."""
+    have = circuit.scale(w)
+    if have in (None, want):
+        return w
+    p = 2 - have
+    args = [Circuit.FALSE] * 3
+    args[p] = w
+    return circuit.lut((0xAA, 0xCC, 0xF0)[p], *args)[want]
+
+
 def shannon(circuit, tables, xs, refresh=False, family=True):
     """Any functions of k >= 3 wires by Shannon expansion.  tables: one integer per function, bit s of which is its value
     at s = x_0 + 2 x_1 + ... + 2^(k-1) x_(k-1); xs: the k wires, bootstrapped ones (refresh=True refreshes each first,
@@ -559,17 +660,7 @@ def shannon(circuit, tables, xs, refresh=False, family=True):
         raise ValueError("shannon: a function of %d wires has a table of %d bits" % (k, 1 << k))
     if refresh:
         xs = [circuit.refresh(x) for x in xs]
-    IDENTITY = (0xAA, 0xCC, 0xF0)        # the table of "the input at position p"
-
-    def at_scale(w, want):               # w at scale `want`: as it is, or through one LUT node at its own position
-        have = circuit.scale(w)
-        if have in (None, want):
-            return w
-        p = 2 - have
-        args = [Circuit.FALSE] * 3
-        args[p] = w
-        return circuit.lut(IDENTITY[p], *args)[want]
-
+    at_scale = lambda w, want: _at_scale(circuit, w, want)
     const = {0x00: (Circuit.FALSE,) * 3, 0xFF: (Circuit.TRUE,) * 3}
     cof = [[(t >> (8 * h)) & 0xFF for h in range(1 << (k - 3))] for t in tables]
     distinct = sorted({c for row in cof for c in row if c not in const})
@@ -599,6 +690,56 @@ def shannon(circuit, tables, xs, refresh=False, family=True):
     return [row[0][0] for row in layer]
 
 
+def lookup(circuit, xs, count=1, plane0=0, refresh=False):
+    """`count` functions of k = len(xs) >= 3 wires whose tables are run-time data: shannon with per-instance tables.
+    Function f's cofactor h -- the value of x_3 .. x_(k-1) -- on (x_0, x_1, x_2) is the data table of plane
+    plane0 + f 2^(k-3) + h (lookup_data lays a run's planes out this way).  All these tables are members of LUT families on
+    (x_0, x_1, x_2), one family -- one bootstrap -- per 256 members; shannon's mux tree follows, lut(0xCA, lo[2], hi[1],
+    x_j) for j = 3 .. k - 1, with nothing merged, as the tables are unknown when the circuit is built.  Scales and
+    refresh as in shannon.  Returns one scale-0 wire per function."""
+    xs = list(xs)
+    k = len(xs)
+    if k < 3:
+        raise ValueError("lookup: at least three wires")
+    count, plane0 = int(count), int(plane0)
+    H = 1 << (k - 3)
+    if count < 1 or plane0 < 0 or plane0 + count * H > circuit.planes:
+        raise ValueError("lookup: planes %d .. %d are needed, the circuit has %d" % (plane0, plane0 + count * H - 1,
+                                                                                   circuit.planes))
+    if refresh:
+        xs = [circuit.refresh(x) for x in xs]
+    x0, x1, x2 = _at_scale(circuit, xs[0], 2), _at_scale(circuit, xs[1], 1), _at_scale(circuit, xs[2], 0)
+    members = [Circuit.plane(plane0 + i) for i in range(count * H)]
+    triples = []
+    for i in range(0, len(members), LUT_MAX_TABLES):
+        triples += circuit.lut_multi(members[i:i + LUT_MAX_TABLES], x0, x1, x2)
+    layer = [triples[f * H:(f + 1) * H] for f in range(count)]
+    for j in range(3, k):
+        sel = _at_scale(circuit, xs[j], 0)
+        layer = [[circuit.lut(0xCA, lo[2], hi[1], sel) for lo, hi in zip(row[0::2], row[1::2])] for row in layer]
+    return [row[0][0] for row in layer]
+
+
+def lookup_data(tables, k):
+    """The planes of lookup: tables [count][instances] of integers of 2^k bits (bit s of tables[f][t] is function f's
+    value at s = x_0 + 2 x_1 + ... at instance t) -> uint8 [count 2^(k-3)][instances], plane f 2^(k-3) + h holding
+    bits 8 h .. 8 h + 7 of every table of function f."""
+    k = int(k)
+    if k < 3:
+        raise ValueError("lookup_data: at least three wires")
+    rows = [[int(t) for t in row] for row in tables]
+    if any(len(row) != len(rows[0]) for row in rows):
+        raise ValueError("lookup_data: ragged tables")
+    if any(not 0 <= t < 1 << (1 << k) for row in rows for t in row):
+        raise ValueError("lookup_data: a function of %d wires has a table of %d bits" % (k, 1 << k))
+    H = 1 << (k - 3)
+    out = np.zeros((len(rows) * H, len(rows[0]) if rows else 0), dtype=np.uint8)
+    for f, row in enumerate(rows):
+        for t, tab in enumerate(row):
+            out[f * H:(f + 1) * H, t] = np.frombuffer(tab.to_bytes(H, "little"), dtype=np.uint8)
+    return out
+
+
 def lwe_not(words, r, one=None):
     """NOT of LWEs [..., n + 1] over Z_r: enc_trivial(true) - w (a -> -a, b -> Dr - b, mod r).  one: the codeword of
     the wire in place of Dr (positions 0 and 1 of a LUT node read wires at Dr/4 and Dr/2)."""
@@ -608,7 +749,7 @@ def lwe_not(words, r, one=None):
     return (t + np.uint64(r) - words) & np.uint64(r - 1)
 
 
-def replay_levels(circuit, inputs, r, boot, boot_lut=None):
+def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None):
     """The circuit composed on the host from whole-level bootstrap calls, in the row and call order of
     sgfhe_circuit_run: inputs [n_inputs][instances][n + 1] -> outputs [n_outputs][instances][n + 1].
     `boot(call, a1, b1, a2, b2)` runs one call (rows of at most CALL_ROWS) and returns [rows][3][n + 1];
@@ -621,10 +762,13 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
     sees every row of a call that holds other rows too (its results for the LUT rows are dropped) and is not called
     for a call of LUT rows only.  The wires of a live LUT sibling are boot_lut of its leader's rows and indices with the
     sibling's table -- boot_lut is a function of (call, row, index, table) --, all siblings of a call in one further
-    boot_lut(call, ...) whose rows and indices repeat.  A checking and measuring aid: the engine's circuit path does
-    this on the device (Engine.circuit_run)."""
+    boot_lut(call, ...) whose rows and indices repeat.  data: the planes of a circuit that has any, uint8
+    [planes][instances]; the row of a data node or data sibling at instance t goes to boot_lut with the table
+    data[plane][t].  A checking and measuring aid: the engine's circuit path does this on the device
+    (Engine.circuit_run)."""
     inputs = np.asarray(inputs, dtype=np.uint64)
     inst, row = inputs.shape[1], inputs.shape[2]
+    data = check_data(circuit, data, inst)
     n = row - 1
     wires = {}
 
@@ -641,7 +785,7 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
         mask = np.uint64(r - 1)
 
         def pair(g):   # the bootstrap inputs of node g: (x, y), (x + y mod r, z) of a three-input node, (U, FALSE)
-            if circuit.kind(g) == "lut":   # position p reads a wire at the codeword Dr >> (2 - p)
+            if circuit.kind(g) in ("lut", "data"):   # position p reads a wire at the codeword Dr >> (2 - p)
                 vals = [val(ref, d, (r // 4) >> (2 - p))
                         for p, (ref, d) in enumerate(zip(circuit.gates[g], circuit.gate_shifts[g]))]
                 return (vals[0] + vals[1] + vals[2]) & mask, np.zeros_like(vals[0])
@@ -657,7 +801,8 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
         x = np.concatenate([p[0] for p in pairs])
         y = np.concatenate([p[1] for p in pairs])
         res = np.zeros((len(x), 3, row), dtype=np.uint64)
-        tables = np.repeat(np.array([circuit.gate_tables.get(g, -1) for g in nodes], dtype=np.int64), inst)
+        tables = np.concatenate([circuit.node_tables(g, inst, data).astype(np.int64) if g in circuit.gate_tables
+                                 else np.full(inst, -1, dtype=np.int64) for g in nodes])
         sibs = [(k, h) for k, g in enumerate(nodes) for h in circuit.live_siblings(g)]   # (rank of the leader, sibling)
         for _, h in sibs:
             for w in range(3):
@@ -674,7 +819,7 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
             part = [(k, h, sel) for k, h, sel in part if len(sel)]
             if part:
                 sel = np.concatenate([s_ for _, _, s_ in part])
-                tab = np.concatenate([np.full(len(s_), circuit.gate_tables[h], dtype=np.uint8) for _, h, s_ in part])
+                tab = np.concatenate([circuit.node_tables(h, inst, data)[r0 + s_ - k * inst] for k, h, s_ in part])
                 got = boot_lut(call, x[sl, :n][sel], x[sl, n][sel], tab, sel)
                 at = 0
                 for k, h, s_ in part:
@@ -686,7 +831,7 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None):
             sl = slice(k * inst, (k + 1) * inst)
             for w in range(3):
                 wires[circuit.n_inputs + 3 * g + w] = res[sl, w]
-            if circuit.kind(g) not in ("classic", "lut"):
+            if circuit.kind(g) not in ("classic", "lut", "data"):
                 wires[circuit.n_inputs + 3 * g + 2] = (x[sl] + y[sl] - np.uint64(2) * res[sl, 0]) & mask
     return np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
         else np.zeros((0, inst, row), np.uint64)
@@ -697,13 +842,13 @@ def pack_calls(n):
     return max(1, CALL_ROWS // n)
 
 
-def replay_ct(circuit, a, b, params, boot, pack, boot_lut=None):
+def replay_ct(circuit, a, b, params, boot, pack, boot_lut=None, data=None):
     """sgfhe_circuit_run_ct composed on the host: a, b [n_inputs][blocks][N] (N = n or m) -> ((w, v), lwe) with
     w, v [n_outputs][blocks][m] and lwe [n_outputs][blocks * n][n + 1].  The inputs are split with
     scheme.split_ciphertext_array (instance block * n + i = bit i of the block's ciphertext), the levels run
     through replay_levels and `boot`, and the ciphertexts q = output * blocks + block are packed in ascending
     order, pack_calls(n) at a time, by `pack(call, a, b)` (a [count][n][n], b [count][n] -> (w, v), each
-    [count][m]); `call` goes on counting after the levels' calls.  boot_lut: as in replay_levels.  A checking and
+    [count][m]); `call` goes on counting after the levels' calls.  boot_lut, data: as in replay_levels.  A checking and
     measuring aid."""
     n, m = params.n, params.m
     a = np.asarray(a, dtype=np.uint64)
@@ -720,7 +865,7 @@ def replay_ct(circuit, a, b, params, boot, pack, boot_lut=None):
         calls[0] = call + 1
         return boot_lut(call, *args)
 
-    lwe = replay_levels(circuit, inputs, params.r, counted, counted_lut)
+    lwe = replay_levels(circuit, inputs, params.r, counted, counted_lut, data=data)
     groups = lwe.reshape(circuit.n_outputs * blocks, n, n + 1)
     w = np.zeros((len(groups), m), dtype=np.uint64)
     v = np.zeros((len(groups), m), dtype=np.uint64)
@@ -809,7 +954,7 @@ def lwe_not_modq(x, Q, DQ_tilde):
     return out
 
 
-def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut_raw=None):
+def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut_raw=None, data=None):
     """sgfhe_circuit_run_ct_ex with SGFHE_CIRCUIT_PACK_DIRECT composed on the host: a, b [n_inputs][blocks][N] ->
     ((w, v), lwe) as replay_ct.  `boot_raw(call, a1, b1, a2, b2)` runs one call un-reduced and returns
     [rows][3][n + 1][2] residues mod Q; the levels run through it in the row and call order of replay_levels, their
@@ -822,8 +967,8 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
     over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  lift=True (SGFHE_CIRCUIT_PACK_LIFT): the
     ciphertexts that are not direct take lift_words of their `lwe` rows instead -- no `boot_raw` call in the pack stage,
     one call number per group.  boot_lut_raw(call, a, b, tables, idx): the LUT rows of a call as in replay_levels,
-    un-reduced ([rows][3][n + 1][2]); an output naming wire +0 of a LUT node is refreshed or lifted.  A checking and
-    measuring aid."""
+    un-reduced ([rows][3][n + 1][2]); an output naming wire +0 of a LUT node is refreshed or lifted.  data: as in
+    replay_levels.  A checking and measuring aid."""
     n, m, r, Q = params.n, params.m, params.r, params.Q
     a = np.asarray(a, dtype=np.uint64)
     b = np.asarray(b, dtype=np.uint64)
@@ -839,7 +984,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
     def reduced_lut(call, *args):
         return modred_words(np.asarray(boot_lut_raw(call, *args), dtype=np.uint64), Q, r)
 
-    lwe = replay_levels(circuit, inputs, r, reduced, reduced_lut)
+    lwe = replay_levels(circuit, inputs, r, reduced, reduced_lut, data=data)
     call, k, raw_wire = 0, 0, {}
     for nodes in circuit.schedule():                        # the calls of a level, back into the level's rows
         rows = len(nodes) * inst
@@ -858,7 +1003,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
         if i == FALSE_ID or i < circuit.n_inputs or circuit.output_shifts[o] != 0:
             return False
         g, w = divmod(i - circuit.n_inputs, 3)
-        if circuit.kind(g) in ("lut", "sibling"):               # wire +0 of a LUT node: refreshed or lifted
+        if g in circuit.gate_tables:                            # wire +0 of a LUT node: refreshed or lifted
             return False
         return not (w == 2 and circuit.kind(g) != "classic")   # XOR3 / LOW is linear over Z_r: no gate row over Z_Q
 
@@ -892,7 +1037,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
     return (w.reshape(shape), v.reshape(shape)), lwe
 
 
-def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False, lift=False):
+def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False, lift=False, data=None):
     """The circuit on RLWE ciphertexts, the reference's user flow (encrypt -> split_ciphertext -> gates ->
     pack_encrypted_bits -> decrypt) with the split and the pack on the device (Engine.circuit_run_ct).
     cts: [n_inputs][blocks] of PackedCiphertext or Ciphertext (all of one kind); bit i of a ciphertext is
@@ -902,6 +1047,7 @@ def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False, lift=False):
     bootstrap in the pack stage, but such an output carries its wire's error on -- meant for inputs that are themselves
     packed outputs, not for sums of freshly encrypted bits (the noise rule in include/sgfhe_hip.h).
     A circuit with lane groups needs n to be a multiple of its group: a ciphertext then holds n / group words.
+    data: the planes of a circuit that has any, uint8 [planes][blocks * n] (instance block * n + i is bit i of a block).
     Returns [n_outputs][blocks] of Ciphertext."""
     p = bkey.params
     if len(cts) != circuit.n_inputs:
@@ -922,7 +1068,7 @@ def evaluate_circuit_ct(bkey, rng, circuit, cts, direct=False, lift=False):
         raise ValueError("evaluate_circuit_ct: ciphertext polynomials of length %d expected" % N)
     with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
         _set_flatten_mode(bkey, rng)
-        w, v = bkey.engine.circuit_run_ct(circuit, a, b, direct=direct, lift=lift)
+        w, v = bkey.engine.circuit_run_ct(circuit, a, b, direct=direct, lift=lift, data=data)
     return [[Ciphertext(p, RLWE(w[o, t], v[o, t])) for t in range(blocks)] for o in range(circuit.n_outputs)]
 
 
@@ -938,11 +1084,11 @@ def _input_array(circuit, inputs, n):
     return arr
 
 
-def probe_circuit(bkey, key, rng, circuit, inputs, bits):
+def probe_circuit(bkey, key, rng, circuit, inputs, bits, data=None):
     """evaluate_circuit that also measures the LWE error of every wire on the device (Engine.circuit_probe,
     sgfhe_circuit_run_probe).  A DIAGNOSTIC for parameter studies and tests: `key` is the PrivateKey, and its
     bits cross the library boundary.  inputs as evaluate_circuit; bits [n_inputs][instances]: the plaintext of
-    every input.  Returns (outputs, stats): outputs as evaluate_circuit (the same bytes), stats a list of
+    every input; data as evaluate_circuit.  Returns (outputs, stats): outputs as evaluate_circuit (the same bytes), stats a list of
     engine.NoiseStats by wire id (noise_report formats it)."""
     n = bkey.params.n
     as_bits = not isinstance(inputs, np.ndarray)
@@ -951,7 +1097,7 @@ def probe_circuit(bkey, key, rng, circuit, inputs, bits):
     bits = np.asarray(bits).astype(np.uint8).reshape(circuit.n_inputs, -1)
     with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
         _set_flatten_mode(bkey, rng)
-        out, stats = bkey.engine.circuit_probe(circuit, inputs, key.key, bits)
+        out, stats = bkey.engine.circuit_probe(circuit, inputs, key.key, bits, data=data)
     if as_bits:
         out = [[EncryptedBit(LWE(out[o, t, :n], out[o, t, n])) for t in range(out.shape[1])]
                for o in range(out.shape[0])]
@@ -976,7 +1122,8 @@ def noise_report(circuit, stats):
         g = (wire - circuit.n_inputs) // 3 if wire >= circuit.n_inputs else None
         names = ("AND", "OR", "XOR") if g is None else \
             {"classic": ("AND", "OR", "XOR"), "gate3": ("MAJ", "ONE_OR_TWO", "XOR3"), "sum": ("HI", "MID", "LOW"),
-             "lut": ("F", "F_HALF", "F_QUARTER"), "sibling": ("F", "F_HALF", "F_QUARTER")}[circuit.kind(g)]
+             "lut": ("F", "F_HALF", "F_QUARTER"), "sibling": ("F", "F_HALF", "F_QUARTER"),
+             "data": ("F", "F_HALF", "F_QUARTER"), "data_sibling": ("F", "F_HALF", "F_QUARTER")}[circuit.kind(g)]
         kind = "input" if g is None else names[(wire - circuit.n_inputs) % 3]
         rows.append(dict(wire=wire, kind=kind, node=g, level=0 if g is None else level[g], rows=st.rows,
                          wrong=st.wrong, max_abs=st.max_abs, mean=st.sum / st.rows,
@@ -985,10 +1132,11 @@ def noise_report(circuit, stats):
     return rows
 
 
-def evaluate_circuit(bkey, rng, circuit, inputs):
+def evaluate_circuit(bkey, rng, circuit, inputs, data=None):
     """The circuit over many instances on the HIP engine.  rng = None: deterministic flatten; a numpy
     Generator: randomised flatten (its ChaCha8 key drawn from `rng`, call counter from 0).
     inputs: [n_inputs][instances] of EncryptedBit, or the array form [n_inputs][instances][n + 1] uint64.
+    data: the planes of a circuit that has any (Circuit(planes=P)), uint8 [P][instances].
     Returns [n_outputs][instances] of EncryptedBit (the array form when given the array form)."""
     n = bkey.params.n
     as_bits = not isinstance(inputs, np.ndarray)
@@ -996,7 +1144,7 @@ def evaluate_circuit(bkey, rng, circuit, inputs):
         inputs = _input_array(circuit, inputs, n)
     with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
         _set_flatten_mode(bkey, rng)
-        out = bkey.engine.circuit_run(circuit, inputs)
+        out = bkey.engine.circuit_run(circuit, inputs, data=data)
     if not as_bits:
         return out
     return [[EncryptedBit(LWE(out[o, t, :n], out[o, t, n])) for t in range(out.shape[1])]

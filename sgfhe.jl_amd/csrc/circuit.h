@@ -6,8 +6,8 @@
 // The call arithmetic of a run lives here too (at the end): circuit_level_call, circuit_job_chunk, circuit_pack_runs and
 // circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
-// circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp, circuit_lut_multi_sanitized.cpp and
-// circuit_calls_sanitized.cpp drive it under ASan / UBSan on the CPU.
+// circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp, circuit_lut_multi_sanitized.cpp,
+// circuit_data_sanitized.cpp and circuit_calls_sanitized.cpp drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -30,6 +30,9 @@ constexpr uint32_t CIRC_FALSE = SGFHE_CIRCUIT_FALSE;
 constexpr uint32_t CIRC_NOT = SGFHE_CIRCUIT_NOT;
 constexpr uint32_t CIRC_NONE = 0xFFFFFFFFu;     // out_slot of a gate output nothing reads
 constexpr uint32_t CIRC_NO_INPUT = SGFHE_CIRCUIT_NONE;   // third reference of a two-input node (never a wire id)
+// A table that is run-time data (sgfhe_circuit_create_data): bit 24 of a LUT node's kind word, whose bits 8..23 then hold
+// the plane, and of fam_entry[4 i], whose low bits then hold the plane (kernels.h CIRC_TABLE_DATA)
+constexpr uint32_t CIRC_DATA = 0x01000000u;
 
 // Word offsets of the device tables in CircuitPlan::image (int32_t tables by bit pattern); `words` is its length.
 struct CircuitImage {
@@ -42,6 +45,7 @@ struct CircuitPlan {
     uint32_t n_inputs = 0, n_gates = 0, n_outputs = 0;
     uint32_t levels = 0, widest = 0, slots = 0;
     uint32_t group = 1;                 // lane group size G (sgfhe_circuit_create_lanes); 1: no reference is shifted
+    uint32_t n_planes = 0;              // data planes of a run (sgfhe_circuit_create_data); 0: every table is the plan's
     std::vector<uint32_t> level;        // [n_gates]: level of every node, 0 = pruned
     std::vector<uint32_t> order;        // live nodes, level by level, ascending index within a level
     std::vector<uint32_t> level_start;  // [levels + 2]: level L's nodes are order[level_start[L] .. level_start[L + 1])
@@ -54,7 +58,7 @@ struct CircuitPlan {
     // node of its three unit weights.
     std::vector<uint32_t> node_kind;    // [live + n_outputs]: bits 0..7 the kind -- 0 classic (two unit terms), 1 sum
                                         // node, 2 LUT node (sgfhe_circuit_create_lut) -- and for a LUT node bits 8..15
-                                        // its truth table
+                                        // its truth table, or CIRC_DATA and in bits 8..23 its plane
     std::vector<uint32_t> term_start;   // [live + n_outputs + 1]: node k's terms are term_start[k] .. term_start[k + 1]
     std::vector<uint32_t> term_ref;     // [terms + 2 n_outputs]
     std::vector<int32_t> term_shift;    // [terms + 2 n_outputs]
@@ -81,8 +85,8 @@ struct CircuitPlan {
     // It takes no row and is not in `order`; the live siblings of the live node k are entries fam_start[k] ..
     // fam_start[k + 1] of one CSR (empty in a plan without live siblings, and then not in the image).
     std::vector<uint32_t> fam_start;    // [live + 1]
-    std::vector<uint32_t> fam_entry;    // [live siblings][4]: truth table, then the slots of its three wires (CIRC_NONE
-                                        // if unread)
+    std::vector<uint32_t> fam_entry;    // [live siblings][4]: truth table (or CIRC_DATA | plane), then the slots of its
+                                        // three wires (CIRC_NONE if unread)
     std::vector<uint32_t> fam_node;     // [live siblings], host only: the sibling's node index; its wires are the probe
                                         // rows n_inputs + 3 live() + 3 i + w
     // Every device table above in one array, uploaded once per run: node_kind, term_start, term_ref, term_shift,
@@ -101,6 +105,12 @@ struct CircuitPlan {
     size_t siblings() const { return fam_node.size(); }
     uint32_t kind(size_t k) const { return node_kind[k] & 0xFFu; }
     uint32_t table(size_t k) const { return (node_kind[k] >> 8) & 0xFFu; }
+    // the table of a LUT node's kind word or of a family entry at instance t of a run whose planes are `data`
+    // ([n_planes][instances])
+    static uint32_t table_at(uint32_t word, uint32_t plane_shift, const uint8_t *data, size_t instances, size_t t) {
+        if (!(word & CIRC_DATA)) return (word >> plane_shift) & 0xFFu;
+        return data[(size_t)((word >> plane_shift) & 0xFFFFu) * instances + t];
+    }
     // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
     uint64_t level_rows(uint32_t L, uint64_t instances) const {
         return (uint64_t)(level_start[L + 1] - level_start[L]) * instances;
@@ -117,7 +127,8 @@ inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
 // of the circuit is refs[i], shifts[i] (NULL: 0), weights[i] (NULL: 1); node g's terms are first(g) .. first(g) +
 // count(g).  `lut`: the arrays of sgfhe_circuit_create_lut, whose kind 2 marks a LUT node of table tables[g].
 // `multi`: those of sgfhe_circuit_create_lut_multi, whose kind 3 marks a sibling -- no terms, table tables[g], a further
-// table on the bootstrap of its LEADER, the nearest earlier kind-2 node.
+// table on the bootstrap of its LEADER, the nearest earlier kind-2 node.  `data`: those of sgfhe_circuit_create_data,
+// whose kinds 4 and 5 are a LUT node and a sibling with tables[g] a plane index below `n_planes`.
 struct CircuitNodes {
     int arity;
     const uint32_t *refs;
@@ -125,7 +136,8 @@ struct CircuitNodes {
     const uint32_t *kind = nullptr, *start = nullptr;
     const int32_t *weights = nullptr;
     const uint32_t *tables = nullptr;
-    bool lut = false, multi = false;
+    bool lut = false, multi = false, data = false;
+    uint32_t n_planes = 0;
 
     size_t first(size_t g) const { return arity ? (size_t)arity * g : start[g]; }
     size_t count(size_t g) const {
@@ -133,8 +145,13 @@ struct CircuitNodes {
         return arity == 3 && refs[3 * g + 2] != CIRC_NO_INPUT ? 3 : 2;
     }
     bool classic(size_t g) const { return arity ? count(g) == 2 : kind[g] == 0; }
-    bool is_sibling(size_t g) const { return !arity && kind[g] == 3; }
-    bool is_lut(size_t g) const { return !arity && (kind[g] == 2 || kind[g] == 3); }   // (wires with scales 0, 1, 2)
+    bool is_sibling(size_t g) const { return !arity && (kind[g] == 3 || kind[g] == 5); }
+    bool is_lut(size_t g) const { return !arity && kind[g] >= 2 && kind[g] <= 5; }   // (wires with scales 0, 1, 2)
+    bool is_data(size_t g) const { return !arity && (kind[g] == 4 || kind[g] == 5); }
+    // a LUT node's or sibling's table as the device tables hold it, before any shift
+    uint32_t table_word(size_t g, uint32_t shift) const {
+        return is_data(g) ? CIRC_DATA | tables[g] << shift : tables[g] << shift;
+    }
     uint32_t kind_of(size_t g) const { return classic(g) ? 0u : (is_lut(g) ? 2u : 1u); }
     int32_t weight(size_t i) const { return weights ? weights[i] : 1; }
 };
@@ -158,18 +175,21 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
     if (!N.arity) {   // the CSR itself, node by node, before a term of the node is read
         if (n_gates && (!N.kind || !N.start || !N.weights || N.start[0] != 0)) return SGFHE_ERR_INVALID_ARG;
         if (n_gates && N.lut && !N.tables) return SGFHE_ERR_INVALID_ARG;
+        if (N.n_planes > SGFHE_CIRCUIT_MAX_PLANES) return SGFHE_ERR_INVALID_ARG;
+        auto table_ok = [&](size_t g) { return N.tables[g] < (N.is_data(g) ? N.n_planes : 256u); };
         size_t family = 0;   // members so far of the family node g - 1 belongs to (0: it is no LUT node)
         for (size_t g = 0; g < n_gates; g++) {
-            if (N.kind[g] > (N.multi ? 3u : (N.lut ? 2u : 1u)) || N.start[g + 1] < N.start[g]) return SGFHE_ERR_INVALID_ARG;
+            if (N.kind[g] > (N.data ? 5u : (N.multi ? 3u : (N.lut ? 2u : 1u))) || N.start[g + 1] < N.start[g])
+                return SGFHE_ERR_INVALID_ARG;
             const size_t nj = N.count(g);
-            if (N.kind[g] == 3) {   // a sibling: no terms, a table, behind a LUT node or a sibling, in a family that has room
-                if (nj != 0 || N.tables[g] >= 256 || family == 0 || family >= SGFHE_LUT_MAX_TABLES) return SGFHE_ERR_INVALID_ARG;
+            if (N.is_sibling(g)) {   // a sibling: no terms, a table, behind a LUT node or a sibling, in a family that has room
+                if (nj != 0 || !table_ok(g) || family == 0 || family >= SGFHE_LUT_MAX_TABLES) return SGFHE_ERR_INVALID_ARG;
                 family++;
                 continue;
             }
-            family = N.kind[g] == 2 ? 1 : 0;
-            if (N.kind[g] == 2) {   // a LUT node: three unit terms (positions 0, 1, 2), a table of 8 entries
-                if (nj != 3 || N.tables[g] >= 256) return SGFHE_ERR_INVALID_ARG;
+            family = N.is_lut(g) ? 1 : 0;
+            if (N.is_lut(g)) {   // a LUT node: three unit terms (positions 0, 1, 2), a table of 8 entries (or a plane)
+                if (nj != 3 || !table_ok(g)) return SGFHE_ERR_INVALID_ARG;
             } else if (N.kind[g] == 0 ? nj != 2 : (nj < 1 || nj > SGFHE_CIRCUIT_MAX_TERMS)) {
                 return SGFHE_ERR_INVALID_ARG;
             }
@@ -216,6 +236,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         P.n_gates = (uint32_t)n_gates;
         P.n_outputs = (uint32_t)n_outputs;
         P.group = group;
+        P.n_planes = N.n_planes;
         const uint32_t NG = (uint32_t)n_gates;
         auto node_of = [&](uint32_t id) -> int64_t {   // producing node of a wire, -1 for inputs and the constant
             return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
@@ -319,7 +340,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             each_sibling(P.order[k], [&](uint32_t h) {
                 sib_index[h] = (uint32_t)P.fam_node.size();
                 P.fam_node.push_back(h);
-                P.fam_entry.push_back(N.tables[h]);
+                P.fam_entry.push_back(N.table_word(h, 0));
                 for (uint32_t w = 0; w < 3; w++) P.fam_entry.push_back(slot_of[n_inputs + 3 * h + w]);
             });
             P.fam_start[k + 1] = (uint32_t)P.fam_node.size();
@@ -354,7 +375,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         P.lut_before.assign(P.live() + 1, 0);
         for (size_t k = 0; k < P.live(); k++) {
             const size_t g = P.order[k];
-            P.node_kind.push_back(N.kind_of(g) | (N.is_lut(g) ? N.tables[g] << 8 : 0u));
+            P.node_kind.push_back(N.kind_of(g) | (N.is_lut(g) ? N.table_word(g, 8) : 0u));
             P.term_start.push_back((uint32_t)P.term_ref.size());
             for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
                 term(slot_ref(refs[i]), shift_of(refs[i], gate_shift, i), N.weight(i));
@@ -466,6 +487,24 @@ inline int32_t circuit_plan_lut_multi(uint32_t n_inputs, const uint32_t *node_ki
     return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
 }
 
+// The arrays of sgfhe_circuit_create_data: those of sgfhe_circuit_create_lut_multi, kinds 4 and 5 for a data LUT node and
+// a data sibling, and the number of planes.
+inline CircuitNodes circuit_nodes_data(uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
+                                       const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                       const uint32_t *node_table) {
+    CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true, true};
+    N.data = true;
+    N.n_planes = n_planes;
+    return N;
+}
+inline int32_t circuit_plan_data(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
+                                 const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                 const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
+                                 const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
+    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
+}
+
 // The arrays of sgfhe_circuit_create_lanes.
 inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                             const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
@@ -495,6 +534,9 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
 // laid out as a row of its own, instance by instance (instance t reads bit t + d where its lane allows, 0 elsewhere;
 // `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  A sum node's rows are HI, MID and LOW
 // of s = sum of w x mod 4: MAJ, ONE_OR_TWO (one or two of its inputs true) and XOR3 of a three-input node.
+// `data` [n_planes][instances]: the planes of a run (sgfhe_circuit_run_probe_data); a data LUT node or data sibling of
+// plane p has the table data[p][t] at instance t, its own instance whatever its terms' shifts (SGFHE_ERR_INVALID_ARG for
+// NULL when the plan has planes and instances > 0).
 // SGFHE_ERR_OOM when the table cannot be allocated; nothing throws out of it.
 inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * (P.live() + P.siblings()); }
 inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
@@ -505,8 +547,9 @@ inline uint32_t circuit_probe_wire(const CircuitPlan &P, size_t row) {
     return (uint32_t)(P.n_inputs + 3 * (size_t)(k < P.live() ? P.order[k] : P.fam_node[k - P.live()]) + w);
 }
 inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, size_t instances,
-                                  std::vector<uint64_t> &table) noexcept {
+                                  std::vector<uint64_t> &table, const uint8_t *data = nullptr) noexcept {
     if (!in_bits && P.n_inputs && instances) return SGFHE_ERR_INVALID_ARG;
+    if (!data && P.n_planes && instances) return SGFHE_ERR_INVALID_ARG;
     if (instances % P.group) return SGFHE_ERR_INVALID_ARG;
     const size_t wpr = circuit_bit_words(instances);
     std::vector<uint64_t> shifted[3];
@@ -548,19 +591,28 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
             // entries of their minterms; its live siblings carry their own tables' bits of the same s
             const uint64_t *sx[3];
             for (uint32_t p = 0; p < 3; p++) sx[p] = source(P.term_row[t0 + p], P.term_shift[t0 + p], shifted[p]);
-            auto fill = [&](uint32_t tb, uint64_t *dst) {
+            // (`tw`, `ps`: a kind word with its table from bit 8, or a family entry with it from bit 0; a data table is
+            // one mask per entry: the instances of the word whose byte has bit sv set)
+            auto fill = [&](uint32_t tw, uint32_t ps, uint64_t *dst) {
                 for (size_t w = 0; w < wpr; w++) {
                     uint64_t x[3], f = 0;
                     for (uint32_t p = 0; p < 3; p++) x[p] = word(sx[p], P.term_row[t0 + p], w);
-                    for (uint32_t sv = 0; sv < 8; sv++)
-                        if ((tb >> sv) & 1u)
-                            f |= (sv & 1 ? x[0] : ~x[0]) & (sv & 2 ? x[1] : ~x[1]) & (sv & 4 ? x[2] : ~x[2]);
+                    for (uint32_t sv = 0; sv < 8; sv++) {
+                        uint64_t on = 0;
+                        if (!(tw & CIRC_DATA)) {
+                            on = ((tw >> ps) >> sv) & 1u ? ~0ull : 0ull;
+                        } else {
+                            for (size_t t = 64 * w; t < std::min(instances, 64 * w + 64); t++)
+                                on |= (uint64_t)((CircuitPlan::table_at(tw, ps, data, instances, t) >> sv) & 1u) << (t % 64);
+                        }
+                        if (on) f |= on & (sv & 1 ? x[0] : ~x[0]) & (sv & 2 ? x[1] : ~x[1]) & (sv & 4 ? x[2] : ~x[2]);
+                    }
                     dst[w] = dst[wpr + w] = dst[2 * wpr + w] = f;
                 }
             };
-            fill(P.table(k), o);
+            fill(P.node_kind[k], 8, o);
             for (size_t i = P.siblings() ? P.fam_start[k] : 0, end = P.siblings() ? P.fam_start[k + 1] : 0; i < end; i++)
-                fill(P.fam_entry[4 * i], table.data() + ((size_t)P.n_inputs + 3 * (P.live() + i)) * wpr);
+                fill(P.fam_entry[4 * i], 0, table.data() + ((size_t)P.n_inputs + 3 * (P.live() + i)) * wpr);
             continue;
         }
         if (P.kind(k) == 1) {

@@ -229,6 +229,7 @@ struct sgfhe_ctx : CtxShared, CtxKnobs, CtxKeyState {
     // and the collected outputs
     DevBuf<uint64_t> circ_wires, circ_stage, circ_out;
     DevBuf<uint32_t> circ_tab;
+    DevBuf<uint8_t> circ_data;            // the data planes of a run (sgfhe_circuit_run_data): [n_planes][instances]
     // sgfhe_circuit_run_ct: the uploaded input ciphertexts [a | b], each [n_inputs][blocks][N]
     DevBuf<uint64_t> circ_ct;
     // work buffers of the packing path (pack_tail), shared by sgfhe_pack_encrypted_bits and the pack stage
@@ -1489,6 +1490,7 @@ static void free_circuit_buffers(sgfhe_ctx *c) {
     c->circ_stage.release();
     c->circ_out.release();
     c->circ_tab.release();
+    c->circ_data.release();
     c->circ_ct.release();
     c->circ_raw.release();
     c->noise_tab.release();
@@ -2772,6 +2774,21 @@ int32_t sgfhe_circuit_create_lut_multi(uint32_t n_inputs, const uint32_t *node_k
     return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
 }
 
+int32_t sgfhe_circuit_create_data(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
+                                  const uint32_t *node_start, const uint32_t *term_ref, const int32_t *term_shift,
+                                  const int32_t *term_weight, const uint32_t *node_table, size_t n_gates,
+                                  const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                                  sgfhe_circuit **out) {
+    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
+}
+
+int32_t sgfhe_circuit_planes(const sgfhe_circuit *c, uint32_t *n_planes) {
+    if (!c || !n_planes) return SGFHE_ERR_INVALID_ARG;
+    *n_planes = c->plan.n_planes;
+    return SGFHE_OK;
+}
+
 int32_t sgfhe_circuit_create(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
                              size_t n_outputs, sgfhe_circuit **out) {
     return sgfhe_circuit_create_lanes(n_inputs, gates, nullptr, n_gates, outputs, nullptr, n_outputs, 1u, out);
@@ -2880,7 +2897,8 @@ struct CircuitProbe {
 // ciphertexts a call covers is csrc/circuit.h's (circuit_level_call, circuit_pack_runs, circuit_run_sizes).
 // `in` / `out`: the LWE form ([wire][instances][n + 1]); with `ct` the inputs come from ct->in_a / in_b instead and
 // `out` is optional.  `probe` (LWE form only): the noise records of every input wire and of every live node's three
-// wires, taken from the uploaded inputs and from each level call's own result rows.
+// wires, taken from the uploaded inputs and from each level call's own result rows.  `data`: the planes of a plan that
+// has any ([n_planes][instances], sgfhe_circuit_run_data), uploaded once with the tables.
 struct CircuitRun {
     sgfhe_ctx *c;
     const CircuitPlan &P;
@@ -2889,6 +2907,7 @@ struct CircuitRun {
     uint64_t *out;
     const CircuitCt *ct;
     CircuitProbe *probe;
+    const uint8_t *data;
     const hipStream_t st = c->stream;
     const size_t n = c->n, row = n + 1, M = c->M;   // row: words of an LWE
     const uint32_t inst = (uint32_t)instances;
@@ -2909,8 +2928,8 @@ struct CircuitRun {
     std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
 
     CircuitRun(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in, uint64_t *out,
-               const CircuitCt *ct, CircuitProbe *probe)
-        : c(c), P(P), instances(instances), in(in), out(out), ct(ct), probe(probe) {}
+               const CircuitCt *ct, CircuitProbe *probe, const uint8_t *data)
+        : c(c), P(P), instances(instances), in(in), out(out), ct(ct), probe(probe), data(P.n_planes ? data : nullptr) {}
 
     int32_t grow();
     int32_t upload_tables();
@@ -2926,7 +2945,7 @@ struct CircuitRun {
     void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows, uint32_t *lutw = nullptr) const {
         hipLaunchKernelGGL(k_circ_gather, dim3(((uint32_t)rows * (uint32_t)row + 255) / 256), dim3(256), 0, st,
                            c->circ_wires.p, nodes, node0, S.a1, S.b1, S.a2, S.b2, (uint32_t)row0, (uint32_t)rows, inst,
-                           (uint32_t)n, r, P.group, lutw);
+                           (uint32_t)n, r, P.group, lutw, (const uint8_t *)(data ? c->circ_data.p : nullptr));
     }
     // words of the staging's rows (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even
     // word offset); the LUT descriptor of a call lies behind them, one 32-bit word per row
@@ -2943,6 +2962,7 @@ int32_t CircuitRun::grow() {
     if (direct && (rc = circ_grow(c, c->circ_raw, sz.n_ct * n * row))) return rc;
     if (out && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_tab, P.at.words))) return rc;
+    if (data && (rc = circ_grow(c, c->circ_data, (size_t)P.n_planes * instances))) return rc;
     if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
     if (pack && (rc = pack_grow(c, sz.cpc, sz.n_ct, sz.max_ref))) return rc;
     if (probe) {
@@ -2950,7 +2970,7 @@ int32_t CircuitRun::grow() {
         for (uint32_t i = 0; i < P.n_inputs; i++) unread += P.input_slot[i] == CIRC_NONE;
         if ((rc = noise_grow(c, probe_rows, bit_words, unread * instances * row))) return rc;
         std::vector<uint64_t> table;
-        if ((rc = circuit_plain_bits(P, probe->in_bits, instances, table)))
+        if ((rc = circuit_plain_bits(P, probe->in_bits, instances, table, data)))
             return fail(c, rc, "sgfhe_circuit_run_probe: no memory for the plaintext bit table");
         try {
             probe->up.assign(NOISE_MASK_WORDS, 0);
@@ -2974,9 +2994,11 @@ int32_t CircuitRun::grow() {
     return SGFHE_OK;
 }
 
-// the plan's tables (the image outlives the asynchronous copy: it belongs to the circuit), and the probe's
+// the plan's tables (the image outlives the asynchronous copy: it belongs to the circuit), the run's planes (the
+// caller's array, as the inputs are), and the probe's
 int32_t CircuitRun::upload_tables() {
     HIPCHK(c, hipMemcpyAsync(c->circ_tab.p, P.image.data(), (size_t)P.at.words * 4, hipMemcpyHostToDevice, st));
+    if (data) HIPCHK(c, hipMemcpyAsync(c->circ_data.p, data, (size_t)P.n_planes * instances, hipMemcpyHostToDevice, st));
     const uint32_t *tab = c->circ_tab.p;
     nodes = {tab + P.at.node_kind, tab + P.at.term_start, tab + P.at.term_ref,
              reinterpret_cast<const int32_t *>(tab + P.at.term_shift),
@@ -3042,6 +3064,7 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
         lut.wires = c->circ_wires.p;
         lut.fam.start = d_fam_start, lut.fam.entry = d_fam_entry;
         lut.fam.node0 = C.k0, lut.fam.row0 = r0, lut.fam.instances = inst;
+        lut.fam.data = data ? c->circ_data.p : nullptr;
     }
     gather(C.k0, S, row0, C.rows, C.lut ? const_cast<uint32_t *>(lut.rows) : nullptr);
     HIPCHK(c, hipGetLastError());
@@ -3185,11 +3208,23 @@ int32_t CircuitRun::run() {
     return download();
 }
 
-// sgfhe_circuit_run, with `probe` the run of sgfhe_circuit_run_probe
+// A plan with planes runs through the _data entries only (`with_data`), and with planes (unless it has no instances)
+static int32_t circuit_data_ok(sgfhe_ctx *c, const sgfhe_circuit *circ, bool with_data, const uint8_t *data,
+                               size_t instances) {
+    if (!circ || !circ->plan.n_planes) return SGFHE_OK;   // (a NULL circuit is the entry's own error)
+    if (!with_data)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: a plan with data planes runs through the _data entries");
+    if (!data && instances)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_data: NULL data for a plan with data planes");
+    return SGFHE_OK;
+}
+
+// sgfhe_circuit_run[_data], with `probe` the run of sgfhe_circuit_run_probe[_data]
 static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
-                               uint64_t *out, CircuitProbe *probe) {
+                               uint64_t *out, CircuitProbe *probe, bool with_data = false, const uint8_t *data = nullptr) {
     if (!circ || !out || (!in && circ->plan.n_inputs))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: NULL circuit, input or output pointer");
+    if (const int32_t rd = circuit_data_ok(c, circ, with_data, data, instances)) return rd;
     if (probe && (!probe->sk || !probe->stats || (!probe->in_bits && circ->plan.n_inputs)))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_probe: NULL secret key, input bits or statistics pointer");
     if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
@@ -3203,7 +3238,7 @@ static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t i
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
     if (instances % P.group)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: instances must be a multiple of the circuit's lane group");
-    return run_drained(c, [&] { return CircuitRun(c, P, instances, in, out, nullptr, probe).run(); });
+    return run_drained(c, [&] { return CircuitRun(c, P, instances, in, out, nullptr, probe, data).run(); });
 }
 
 int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
@@ -3212,6 +3247,15 @@ int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
     SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
     CircuitProbe probe = {sk, in_bits, stats, {}, {}};
     return circuit_run_lwe(c, circ, instances, in, out, &probe);
+}
+
+int32_t sgfhe_circuit_run_probe_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                                     const uint8_t *data, uint64_t *out, const uint64_t *sk, const uint8_t *in_bits,
+                                     uint64_t *stats) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    CircuitProbe probe = {sk, in_bits, stats, {}, {}};
+    return circuit_run_lwe(c, circ, instances, in, out, &probe, true, data);
 }
 
 // everything sgfhe_lwe_noise queues (run_drained waits for the stream when a step fails)
@@ -3306,21 +3350,48 @@ int32_t sgfhe_circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instan
     return circuit_run_lwe(c, circ, instances, in, out, nullptr);
 }
 
+int32_t sgfhe_circuit_run_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                               const uint8_t *data, uint64_t *out) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    return circuit_run_lwe(c, circ, instances, in, out, nullptr, true, data);
+}
+
 int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe) {
     return sgfhe_circuit_run_ct_ex(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, 0u);
 }
+
+// sgfhe_circuit_run_ct_ex and sgfhe_circuit_run_ct_data (`with_data`), the ctx locked
+static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
+                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
+                              uint32_t flags, bool with_data, const uint8_t *data);
 
 int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                                 const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
                                 uint32_t flags) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    return circuit_run_ct(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, flags, false, nullptr);
+}
+
+int32_t sgfhe_circuit_run_ct_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
+                                  const uint64_t *in_b, size_t N, const uint8_t *data, uint64_t *out_w, uint64_t *out_v,
+                                  uint64_t *out_lwe, uint32_t flags) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    return circuit_run_ct(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, flags, true, data);
+}
+
+static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
+                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
+                              uint32_t flags, bool with_data, const uint8_t *data) {
     // (bit 1 without bit 0 was an unknown bit before SGFHE_CIRCUIT_PACK_LIFT existed, and stays refused)
     if ((flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || flags == SGFHE_CIRCUIT_PACK_LIFT)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct_ex: unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
     if (!circ || ((!in_a || !in_b) && circ->plan.n_inputs))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: NULL circuit or input pointer");
+    if (const int32_t rd = circuit_data_ok(c, circ, with_data, data, blocks)) return rd;
     if (!out_w != !out_v || (!out_w && !out_lwe))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: out_w and out_v go together, and one output form is needed");
     if (N != c->n && N != c->M)
@@ -3342,7 +3413,7 @@ int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: n must be a multiple of the circuit's lane group");
     const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
                           (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
-    return run_drained(c, [&] { return CircuitRun(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr).run(); });
+    return run_drained(c, [&] { return CircuitRun(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data).run(); });
 }
 
 }  // extern "C"

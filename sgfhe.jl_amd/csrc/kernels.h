@@ -1690,6 +1690,10 @@ k_final_lut(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, const 
 
 // (slot references of the circuit tables, described with the gate circuits below)
 constexpr uint32_t CIRC_REF_FALSE = 0x7FFFFFFFu, CIRC_REF_NOT = 0x80000000u, CIRC_SLOT_NONE = 0xFFFFFFFFu;
+// A table that is run-time data (sgfhe_circuit_create_data, circuit.h CIRC_DATA): bit 24 of a LUT node's kind word, whose
+// bits 8..23 then hold the plane, and of a family entry, whose low 16 bits then hold it.  The table of instance `inst`
+// is the byte data[plane * instances + inst] of the run's planes.
+constexpr uint32_t CIRC_TABLE_DATA = 0x01000000u;
 
 // ---- k_final_lut_multi --------------------------------------------------------------------------
 // A LUT family: several truth tables on the accumulator of one row.  The k-loop does not know the table; a further
@@ -1707,12 +1711,19 @@ constexpr uint32_t CIRC_REF_FALSE = 0x7FFFFFFFu, CIRC_REF_NOT = 0x80000000u, CIR
 // entries start[node] .. start[node + 1] of {table, slot of wire +0, +1, +2} (CircuitPlan::fam_entry), and wire w goes
 // to its slot of the wire table `out` ([slot][instances][n + 1]) -- as the ModRed word, in an un-reduced call too;
 // a wire nothing reads has no slot (CIRC_SLOT_NONE) and is not formed.  The node's own table leaves through k_final_lut.
+// An entry may name a plane instead of a table (CIRC_TABLE_DATA): the thread resolves it with one byte load at its
+// instance, uniform over the row, before the entry's table is used at all (lut_fam_table).
 struct LutTables {
     const uint8_t *tables;            // the primitive
     uint32_t n_tables;
     const uint32_t *start, *entry;    // a level call
     uint32_t node0, row0, instances;
+    const uint8_t *data;              // a level call of a plan with planes: [n_planes][instances]
 };
+__device__ __forceinline__ uint32_t lut_fam_table(const LutTables &T, uint32_t i, uint32_t inst) {
+    const uint32_t w = T.entry[4 * i];
+    return w & CIRC_TABLE_DATA ? T.data[(size_t)(w & 0xFFFFu) * T.instances + inst] : w;
+}
 __device__ __forceinline__ void lut_coeffs(u128 (&P)[8], uint32_t need, const uint64_t *__restrict__ dig, size_t bc,
                                            uint32_t shift, uint32_t M, bool wide, const CrtConst *CC, uint32_t mode) {
 #pragma unroll
@@ -1737,11 +1748,11 @@ k_final_lut_multi(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, 
         const uint32_t R = T.row0 + b, node = T.node0 + R / T.instances, inst = R % T.instances;
         const uint32_t s0 = T.start[node], s1 = T.start[node + 1];
         if (s0 == s1) return;
-        for (uint32_t i = s0; i < s1; i++) need |= lut_edges(T.entry[4 * i]);
+        for (uint32_t i = s0; i < s1; i++) need |= lut_edges(lut_fam_table(T, i, inst));
         lut_coeffs(P, need, dig, bc, shift, M, wide, CC, mode);
         const u128 Q = CC->Q;
         for (uint32_t i = s0; i < s1; i++) {
-            u128 v = lut_base(T.entry[4 * i], e == n, CC, [&](uint32_t j) { return P[j - 1]; });
+            u128 v = lut_base(lut_fam_table(T, i, inst), e == n, CC, [&](uint32_t j) { return P[j - 1]; });
 #pragma unroll
             for (int w = 2; w >= 0; w--) {   // wire +2 is the base word, +1 twice and +0 four times it
                 const uint32_t slot = T.entry[4 * i + 1 + w];
@@ -1813,12 +1824,14 @@ struct CircNodes {
 // A LUT node (kind 2, its table in bits 8..15 of the kind word; sgfhe_circuit_create_lut) writes a1 = U = X0 + X1 + X2
 // and a2 = 0 as a sum node of unit weights does, but position i reads a wire at the codeword Dr >> (2 - i), so NOT at
 // position i is b -> (Dr >> (2 - i)) - b.  `lutw` (NULL for a call without LUT nodes): the call's LUT descriptor, one
-// word per row, LUT_ROW | table for the rows of a LUT node and 0 for the others (bootstrap_device's LutDesc).
+// word per row, LUT_ROW | table for the rows of a LUT node and 0 for the others (bootstrap_device's LutDesc).  The
+// table of a data LUT node (CIRC_TABLE_DATA) is the byte of its plane at the row's own instance, data[plane * instances +
+// inst]: one load, by the thread that writes the word.
 __global__ void __launch_bounds__(256)
 k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node0, uint64_t *__restrict__ a1,
               uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
               uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group,
-              uint32_t *__restrict__ lutw = nullptr) {
+              uint32_t *__restrict__ lutw = nullptr, const uint8_t *__restrict__ data = nullptr) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
@@ -1844,7 +1857,11 @@ k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node
     } else {
         b1[lr] = u;
         b2[lr] = v;
-        if (lutw) lutw[lr] = kd == 2 ? LUT_ROW | ((kw >> 8) & 0xFFu) : 0u;
+        if (lutw) {
+            uint32_t tb = (kw >> 8) & 0xFFu;
+            if (kw & CIRC_TABLE_DATA) tb = data[(size_t)((kw >> 8) & 0xFFFFu) * instances + inst];
+            lutw[lr] = kd == 2 ? LUT_ROW | tb : 0u;
+        }
     }
 }
 

@@ -287,25 +287,43 @@ class Engine:
     def sync(self):
         self._call("sgfhe_sync")
 
-    def circuit_run(self, circuit, inputs):
+    @staticmethod
+    def _planes(circuit, data, instances):
+        """The data planes of a run as the C ABI takes them: (array or None, pointer or None).  A circuit with planes
+        needs data [planes][instances] of uint8; one without takes none (circuit.check_data raises ValueError)."""
+        from .circuit import check_data
+        d = check_data(circuit, data, instances)
+        if d is None:
+            return None, None
+        d = np.ascontiguousarray(d)
+        return d, d.ctypes.data_as(ctypes.c_void_p)
+
+    def circuit_run(self, circuit, inputs, data=None):
         """A gate circuit (circuit.Circuit) over many instances on the device (sgfhe_circuit_run):
         inputs [n_inputs][instances][n+1] uint64 (a then b) -> outputs [n_outputs][instances][n+1].
         A circuit with lane groups (Circuit(group=G)) needs instances to be a multiple of G; in the ciphertext
-        form (circuit_run_ct) n must be one, so that no group straddles two ciphertexts."""
+        form (circuit_run_ct) n must be one, so that no group straddles two ciphertexts.
+        data: the planes of a circuit that has any (Circuit(planes=P)): uint8 [planes][instances], the truth table of
+        every data node at every instance (sgfhe_circuit_run_data)."""
         n = self.params.n
         a, ptr = _c(inputs)
         if a.ndim != 3 or a.shape[0] != circuit.n_inputs or a.shape[2] != n + 1:
             raise ValueError("circuit_run: inputs must be [n_inputs=%d][instances][n+1=%d]" % (circuit.n_inputs, n + 1))
+        d, pd = self._planes(circuit, data, a.shape[1])
         out = np.zeros((circuit.n_outputs, a.shape[1], n + 1), dtype=np.uint64)
-        self._call("sgfhe_circuit_run", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p))
+        if d is not None:
+            self._call("sgfhe_circuit_run_data", circuit.handle(), a.shape[1], ptr, pd, out.ctypes.data_as(ctypes.c_void_p))
+        else:
+            self._call("sgfhe_circuit_run", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p))
         return out
 
-    def circuit_probe(self, circuit, inputs, sk, in_bits):
+    def circuit_probe(self, circuit, inputs, sk, in_bits, data=None):
         """circuit_run that also measures every wire against the secret key (sgfhe_circuit_run_probe; a
         DIAGNOSTIC: the key crosses the boundary).  sk: n key bits; in_bits [n_inputs][instances]: the plaintext
         bit of every input LWE.  Returns (out, stats): out as circuit_run (the same bytes), stats a list of
         NoiseStats by wire id -- inputs, then AND, OR, XOR of every node; all-zero records for pruned nodes and for the
-        wires of a LUT sibling (Circuit.lut_multi) that nothing reads: those are never formed."""
+        wires of a LUT sibling (Circuit.lut_multi) that nothing reads: those are never formed.  data: as circuit_run
+        (sgfhe_circuit_run_probe_data)."""
         n = self.params.n
         a, ptr = _c(inputs)
         if a.ndim != 3 or a.shape[0] != circuit.n_inputs or a.shape[2] != n + 1:
@@ -314,10 +332,15 @@ class Engine:
         bits, pbits = _c(in_bits, np.uint8)
         if sk.size != n or bits.size != circuit.n_inputs * a.shape[1]:
             raise ValueError("circuit_probe: sk holds n key bits, in_bits is [n_inputs][instances]")
+        d, pd = self._planes(circuit, data, a.shape[1])
         out = np.zeros((circuit.n_outputs, a.shape[1], n + 1), dtype=np.uint64)
         stats = np.zeros((circuit.n_inputs + 3 * circuit.n_gates, 8), dtype=np.uint64)
-        self._call("sgfhe_circuit_run_probe", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p),
-                   psk, pbits, stats.ctypes.data_as(ctypes.c_void_p))
+        if d is not None:
+            self._call("sgfhe_circuit_run_probe_data", circuit.handle(), a.shape[1], ptr, pd,
+                       out.ctypes.data_as(ctypes.c_void_p), psk, pbits, stats.ctypes.data_as(ctypes.c_void_p))
+        else:
+            self._call("sgfhe_circuit_run_probe", circuit.handle(), a.shape[1], ptr, out.ctypes.data_as(ctypes.c_void_p),
+                       psk, pbits, stats.ctypes.data_as(ctypes.c_void_p))
         return out, [noise_record(rec) for rec in stats]
 
     def lwe_noise(self, sk, lwe, expected, raw=False, stride=None):
@@ -343,7 +366,7 @@ class Engine:
         self._call("sgfhe_lwe_noise", psk, parr, count, stride, pexp, FLAG_RAW_MODQ if raw else 0, st)
         return noise_record(st, raw)
 
-    def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False, direct=False, lift=False):
+    def circuit_run_ct(self, circuit, a, b, packed=True, lwe=False, direct=False, lift=False, data=None):
         """A gate circuit with RLWE ciphertexts at both ends (sgfhe_circuit_run_ct): split_ciphertext of the
         inputs and pack_encrypted_bits of the outputs run on the device inside the one run.
         a, b: [n_inputs][blocks][N] uint64, rlwe.a / rlwe.b of one ciphertext per (input, block), N = n
@@ -356,7 +379,8 @@ class Engine:
         lift: SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT, with or without direct=True (the C ABI takes the
         lift bit only together with the direct bit) -- direct as above, and every other output (an input, the constant, an XOR3
         wire, a lane-shifted reference) is lifted from Z_r (lwe_lift) instead of refreshed: no bootstrap in the pack
-        stage, but such an output carries its wire's error on (see the noise rule in include/sgfhe_hip.h)."""
+        stage, but such an output carries its wire's error on (see the noise rule in include/sgfhe_hip.h).
+        data: the planes of a circuit that has any, uint8 [planes][blocks * n] (sgfhe_circuit_run_ct_data)."""
         p = self.params
         a, pa = _c(a)
         b, pb = _c(b)
@@ -370,7 +394,12 @@ class Engine:
         v = np.zeros((circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
         out = np.zeros((circuit.n_outputs, blocks * p.n, p.n + 1), dtype=np.uint64) if lwe else None
         ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None else None
-        if direct or lift:
+        d, pd = self._planes(circuit, data, blocks * p.n)
+        if d is not None:
+            flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
+            self._call("sgfhe_circuit_run_ct_data", circuit.handle(), blocks, pa, pb, a.shape[2], pd, ptr(w), ptr(v),
+                       ptr(out), flags)
+        elif direct or lift:
             self._call("sgfhe_circuit_run_ct_ex", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out),
                        CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0))
         else:

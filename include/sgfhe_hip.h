@@ -618,6 +618,63 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * plan without planes may go through the _data entries with data NULL: that run is the old entry.  sgfhe_circuit_run,
  * _run_ct, _run_ct_ex and _run_probe return SGFHE_ERR_INVALID_ARG for a plan with planes, write nothing and consume no
  * call number.
+ *
+ * Registers and stepped runs (sgfhe_circuit_create_seq, sgfhe_circuit_run_steps, sgfhe_circuit_run_steps_ct): a
+ * SEQUENTIAL circuit is a plan whose first n_regs input wires are REGISTERS, and a stepped run evaluates it `steps`
+ * times over the same instances in one queued run; after each step every register takes the value of its next-state
+ * reference.  The other n_inputs - n_regs inputs (the STREAM inputs), the data planes and the outputs are per step.
+ * Nothing is added to the k-loop: a step's level calls are exactly those of sgfhe_circuit_run_data.
+ * The creator takes the arrays of sgfhe_circuit_create_data and
+ *   n_regs      : at most n_inputs; register i is input wire i;
+ *   next_ref    : [n_regs] wire references, validated like outputs: an input, a register (itself included), the
+ *                 constant or any node wire, with or without SGFHE_CIRCUIT_NOT;
+ *   next_shift  : [n_regs] lane shifts, NULL = all 0, every |d| below `group`;
+ *   reg_scale   : [n_regs], each 0, 1 or 2, NULL = all 0.  For the scale rule register i is a wire of scale
+ *                 reg_scale[i] (so a LUT node may read a scale-2 register at position 0 without a fan), and its
+ *                 next_ref names the constant or a wire of that same scale.  NOT on a next-state reference of scale k
+ *                 is a -> -a, b -> (Dr >> k) - b.  Stream inputs are scale 0.
+ * Next-state references count as readers exactly as outputs do -- liveness, levels, slot lifetime (held to the end of
+ * the step) -- so a node reached only through next_ref is live, and levels, order, rows and calls are those of the STEP
+ * PLAN: the sgfhe_circuit_create_data plan of the same node arrays with outputs = outputs ++ next_ref.  n_outputs >= 1
+ * stays.  With n_regs = 0 the plan is the sgfhe_circuit_create_data plan of the same arrays (info, tables, rows, calls).
+ * sgfhe_circuit_registers gives n_regs (0 for a plan of any other creator).  Every other run entry (sgfhe_circuit_run,
+ * _run_data, _run_ct, _run_ct_ex, _run_ct_data, _run_probe, _run_probe_data) returns SGFHE_ERR_INVALID_ARG for a plan
+ * with registers before anything is queued, writes nothing and consumes no call number.
+ * sgfhe_circuit_run_steps, the LWE form (host pointers, synchronous, the ctx locked for the whole run):
+ *   state_in  : [n_regs][instances][n + 1], the registers before step 0; NULL = every register FALSE (the trivial LWE);
+ *   in        : [steps][n_inputs - n_regs][instances][n + 1], the stream inputs of every step;
+ *   data      : [steps][n_planes][instances], the planes of every step (NULL for a plan without planes);
+ *   emit      : [steps] uint8, nonzero = the step's outputs are wanted; NULL = every step;
+ *   out       : [emitted steps][n_outputs][instances][n + 1], the emitted steps in order; rows past them are not written;
+ *   state_out : [n_regs][instances][n + 1], the registers after the last step.  At least one of out, state_out.
+ * The contract: step s is, byte for byte, sgfhe_circuit_run_data of the step plan on (the registers at the start of step
+ * s) ++ in[s] with the planes data[s]; its first n_outputs outputs are the step's outputs and the others the registers
+ * at the start of step s + 1.  The level calls of successive steps take consecutive call numbers of the ctx's draw
+ * stream.  A step's outputs are taken BEFORE the feedback: an output that names a register shows the value the step
+ * started with.  steps = 0 or instances = 0 does nothing and consumes nothing.  A run of a + b steps equals a run of a
+ * steps followed by a run of b steps started from the first run's state_out, on the same stream.
+ * Host and device memory do not grow with `steps`: the wire table is slots * instances * (n + 1) words as for one run,
+ * the registers live between steps in a ctx buffer [n_regs][instances][n + 1] (grown on demand, freed with the other
+ * circuit buffers), in[s] and data[s] go up at the start of step s and an emitted step's outputs come down in stream
+ * order; the host waits once, at the end.  In a step with emit[s] = 0 nothing is collected or downloaded, but ITS NODES
+ * STILL RUN, output-only nodes included: the plan is static, and the call numbers do not depend on `emit`.
+ * sgfhe_circuit_run_steps_ct, the ciphertext form (numbering, N and flags as sgfhe_circuit_run_ct_ex):
+ *   state_a, state_b : [n_regs][blocks][N], the registers start as the split of these; both NULL = FALSE;
+ *   in_a, in_b       : [steps][n_inputs - n_regs][blocks][N], split into the input slots at the start of each step;
+ *   out_w, out_v     : [emitted steps][n_outputs][blocks][m]: an emitted step runs the pack stage of
+ *                      sgfhe_circuit_run_ct_ex on that step's wire table under `flags`;
+ *   out_lwe          : [emitted steps][n_outputs][blocks * n][n + 1], the bytes of the LWE-form stepped run;
+ *   state_lwe        : [n_regs][blocks * n][n + 1], the registers after the last step (LWEs: feed them to
+ *                      sgfhe_circuit_run_steps, or pack them).  One of (out_w, out_v), out_lwe, state_lwe is needed.
+ * Call numbers per step: the step's level calls, then the step's pack calls if it is emitted.  A plan with a register
+ * of scale 1 or 2 is refused (SGFHE_ERR_INVALID_ARG, nothing written): a split ciphertext is scale 0 and an LWE cannot
+ * be halved.  There is no probe variant of a stepped run.
+ * Errors of both, before anything is queued or written: SGFHE_ERR_INVALID_ARG for a NULL plan, NULL stream inputs when
+ * the plan has any, NULL data when it has planes (and steps, instances > 0), no output pointer, instances not a
+ * multiple of the group, and the size limits of the one-shot entries; SGFHE_ERR_NO_KEY, SGFHE_ERR_OOM as there.
+ * Noise rule for registers, MEASURED, NOT PROVED (tests/test_gpu_circuit_steps.py: a serial adder over 64 steps): a
+ * register should be fed by a bootstrapped wire -- a gate row, HI / MID of a sum node, a LUT wire -- whose error does
+ * not depend on the step.  A LOW / XOR3 wire or a stream input fed back carries its error on and adds to it every step.
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -671,6 +728,18 @@ int32_t sgfhe_circuit_create_data(uint32_t n_inputs, uint32_t n_planes,
                                   const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
                                   uint32_t group, sgfhe_circuit **out);
 int32_t sgfhe_circuit_planes(const sgfhe_circuit *c, uint32_t *n_planes);   /* 0 for every other creator */
+int32_t sgfhe_circuit_create_seq(uint32_t n_inputs, uint32_t n_planes,
+                                 const uint32_t *node_kind /* [n_gates]: 0 .. 5 as sgfhe_circuit_create_data */,
+                                 const uint32_t *node_start /* [n_gates + 1], CSR into the term arrays, [0] = 0 */,
+                                 const uint32_t *term_ref, const int32_t *term_shift /* NULL = all 0 */,
+                                 const int32_t *term_weight,
+                                 const uint32_t *node_table /* [n_gates]: a table for kinds 2 and 3, a plane for 4 and 5 */,
+                                 size_t n_gates, const uint32_t *outputs,
+                                 const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
+                                 uint32_t group, uint32_t n_regs, const uint32_t *next_ref /* [n_regs] */,
+                                 const int32_t *next_shift /* [n_regs], NULL = all 0 */,
+                                 const uint32_t *reg_scale /* [n_regs]: 0, 1, 2; NULL = all 0 */, sgfhe_circuit **out);
+int32_t sgfhe_circuit_registers(const sgfhe_circuit *c, uint32_t *n_regs);   /* 0 for every other creator */
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);
@@ -928,6 +997,21 @@ int32_t sgfhe_circuit_run_ct_data(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t
 int32_t sgfhe_circuit_run_probe_data(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
                                      const uint8_t *data, uint64_t *out, const uint64_t *sk, const uint8_t *in_bits,
                                      uint64_t *stats);
+/* The stepped runs of a plan with registers ("Registers and stepped runs" above). */
+int32_t sgfhe_circuit_run_steps(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, size_t steps,
+                                const uint64_t *state_in /* [n_regs][instances][n + 1], NULL = every register FALSE */,
+                                const uint64_t *in /* [steps][n_inputs - n_regs][instances][n + 1] */,
+                                const uint8_t *data /* [steps][n_planes][instances] */,
+                                const uint8_t *emit /* [steps], NULL = every step */,
+                                uint64_t *out /* [emitted steps][n_outputs][instances][n + 1] */,
+                                uint64_t *state_out /* [n_regs][instances][n + 1], optional */);
+int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, size_t steps,
+                                   const uint64_t *state_a, const uint64_t *state_b /* [n_regs][blocks][N] */,
+                                   const uint64_t *in_a, const uint64_t *in_b /* [steps][n_inputs - n_regs][blocks][N] */,
+                                   size_t N, const uint8_t *data, const uint8_t *emit, uint64_t *out_w,
+                                   uint64_t *out_v /* [emitted steps][n_outputs][blocks][m] */,
+                                   uint64_t *out_lwe /* [emitted steps][n_outputs][blocks * n][n + 1] */,
+                                   uint64_t *state_lwe /* [n_regs][blocks * n][n + 1], optional */, uint32_t flags);
 
 /*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled

@@ -49,6 +49,14 @@ data[p][t] -- public data that differs from instance to instance, in one bootstr
 `Circuit.plane(p)` among the tables of lut_multi makes that member a data table.  `lookup(c, xs)` with
 `lookup_data(tables, k)` is shannon with per-instance tables: T_t[x] for a different public table T_t at every instance.
 The table never enters the k-loop: rows, calls, draws and the noise rule are those of the constant-table circuit.
+
+Registers (sgfhe_circuit_create_seq).  Circuit(n_inputs, registers=R) makes the first R inputs REGISTERS and the others
+STREAM inputs; `next_state(*wires)` names the wire every register takes after a step, and a STEPPED run
+(evaluate_circuit_steps, Engine.circuit_run_steps) evaluates the circuit `steps` times in one queued run with the
+registers fed back on the device: stream inputs, planes and outputs are per step, and memory does not grow with the
+steps.  serial_adder() adds numbers of any width with one bootstrap per bit; crc16_stream(8) is the CRC-16 of a message
+of any length, a byte per step.  Feed a register from a bootstrapped wire (a gate row, HI / MID, a LUT wire): an XOR3 /
+LOW wire or a stream input fed back adds its error every step.
 """
 
 import ctypes
@@ -121,23 +129,38 @@ class Circuit:
     shifted by |d| < group lanes, Wire.lane).  The C plan (sgfhe_circuit_create, sgfhe_circuit_create_lanes when
     the group is above 1, sgfhe_circuit_create3 when a gate3 exists, sgfhe_circuit_create_w when a sum node exists that
     is no three-input node, sgfhe_circuit_create_lut when a LUT node exists, sgfhe_circuit_create_lut_multi when a LUT
-    sibling exists, sgfhe_circuit_create_data when the circuit has planes) is made on first use and freed with the object.
-    `planes`: the number of data planes a run brings (lut_data, Circuit.plane), uint8 [planes][instances]."""
+    sibling exists, sgfhe_circuit_create_data when the circuit has planes, sgfhe_circuit_create_seq when it has
+    registers) is made on first use and freed with the object.
+    `planes`: the number of data planes a run brings (lut_data, Circuit.plane), uint8 [planes][instances].
+    `registers`: the first `registers` inputs are registers (`c.registers`), fed back by a stepped run from the wires
+    given to next_state; the others are the stream inputs (`c.stream_inputs`).  `reg_scales`: the scale of every
+    register (0, 1 or 2; default all 0): a register of scale 2 can be read at position 0 of a LUT node."""
 
     FALSE = Wire(FALSE_ID)
     TRUE = Wire(FALSE_ID | NOT_BIT)
 
-    def __init__(self, n_inputs, group=1, planes=0):
+    def __init__(self, n_inputs, group=1, planes=0, registers=0, reg_scales=None):
         if not 0 <= int(n_inputs) < FALSE_ID:
             raise ValueError("n_inputs out of range")
         if not 1 <= int(group) <= 0xFFFFFFFF:
             raise ValueError("group out of range")
         if not 0 <= int(planes) <= MAX_PLANES:
             raise ValueError("planes out of range (at most %d)" % MAX_PLANES)
+        if not 0 <= int(registers) <= int(n_inputs):
+            raise ValueError("registers out of range (at most n_inputs)")
+        reg_scales = [0] * int(registers) if reg_scales is None else [int(k) for k in reg_scales]
+        if len(reg_scales) != int(registers) or any(k not in (0, 1, 2) for k in reg_scales):
+            raise ValueError("reg_scales: one scale 0, 1 or 2 per register")
         self.n_inputs = int(n_inputs)
         self.group = int(group)
         self.planes = int(planes)
+        self.n_regs = int(registers)
+        self.reg_scales = reg_scales
         self.inputs = [Wire(i) for i in range(self.n_inputs)]
+        self.registers = self.inputs[:self.n_regs]
+        self.stream_inputs = self.inputs[self.n_regs:]
+        self.next_refs = [FALSE_ID] * self.n_regs   # [ref]: the next state of every register (next_state); FALSE until set
+        self.next_shifts = [0] * self.n_regs
         self.gates = []            # [(x ref, y ref)], or (x ref, y ref, z ref) for a three-input node
         self.outputs = []          # [ref]
         self.gate_shifts = []      # [(x lane shift, y lane shift)] or (x, y, z lane shift), beside gates
@@ -151,11 +174,11 @@ class Circuit:
 
     def scale(self, w):
         """The scale of a wire: 0 (codeword Dr) but for wires +1 and +2 of a LUT node (1: Dr/2, 2: Dr/4); None for the
-        constant, which fits every scale."""
+        constant, which fits every scale; a register has the scale it was given (Circuit(reg_scales=...))."""
         if w.id == FALSE_ID:
             return None
         if w.id < self.n_inputs:
-            return 0
+            return self.reg_scales[w.id] if w.id < self.n_regs else 0
         g, k = divmod(w.id - self.n_inputs, 3)
         return k if g in self.gate_tables else 0
 
@@ -347,6 +370,29 @@ class Circuit:
         self.output_shifts = [w.shift for w in wires]
         self._invalidate()
 
+    def next_state(self, *wires):
+        """Set the next state of every register: after a step register i takes the value of wires[i] (any wire
+        reference -- a node wire, an input, a register, a constant, negated or lane-shifted -- of the register's
+        scale), read before any register changes."""
+        if len(wires) != self.n_regs:
+            raise ValueError("next_state: one wire per register (%d)" % self.n_regs)
+        self.next_refs = [self._ref(w, k) for w, k in zip(wires, self.reg_scales)]
+        self.next_shifts = [w.shift for w in wires]
+        self._invalidate()
+
+    def step_plan(self):
+        """The feed-forward circuit one step is: the same nodes, no registers, outputs = outputs ++ next states.  A step
+        of a stepped run is, byte for byte, a run of it (registers of scale 0 only: an output has scale 0)."""
+        if any(self.reg_scales):
+            raise ValueError("step_plan: a register of scale 1 or 2 has no step plan (outputs are scale 0)")
+        c = Circuit(self.n_inputs, group=self.group, planes=self.planes)
+        c.gates, c.gate_shifts = list(self.gates), list(self.gate_shifts)
+        c.gate_weights, c.gate_tables = dict(self.gate_weights), dict(self.gate_tables)
+        c.gate_leader, c.gate_planes = dict(self.gate_leader), dict(self.gate_planes)
+        c.outputs = list(self.outputs) + list(self.next_refs)
+        c.output_shifts = list(self.output_shifts) + list(self.next_shifts)
+        return c
+
     @property
     def n_gates(self):
         return len(self.gates)
@@ -370,7 +416,7 @@ class Circuit:
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
             os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
             h = ctypes.c_void_p()
-            if self.has_wsum or self.has_lut or self.planes:
+            if self.has_wsum or self.has_lut or self.planes or self.n_regs:
                 # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes, 3 for their siblings, 4 and 5
                 # for those whose table is a data plane
                 kind = np.array([{"classic": 0, "lut": 2, "sibling": 3, "data": 4, "data_sibling": 5}.get(self.kind(g), 1)
@@ -379,7 +425,16 @@ class Circuit:
                 tr = np.array([ref for x in self.gates for ref in x], dtype=np.uint32)
                 ts = np.array([d for x in self.gate_shifts for d in x], dtype=np.int32)
                 tw = np.array([w for g in range(len(self.gates)) for w in self.weights(g)], dtype=np.int32)
-                if self.planes:   # (only a circuit with planes: every other keeps the creator it has)
+                if self.n_regs:   # (only a circuit with registers: every other keeps the creator it has)
+                    tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
+                                   for g in range(len(self.gates))], dtype=np.uint32)
+                    nr = np.ascontiguousarray(np.array(self.next_refs, dtype=np.uint32))
+                    ns = np.ascontiguousarray(np.array(self.next_shifts, dtype=np.int32))
+                    rs = np.ascontiguousarray(np.array(self.reg_scales, dtype=np.uint32))
+                    rc = L.sgfhe_circuit_create_seq(self.n_inputs, self.planes, vp(kind), vp(start), vp(tr), vp(ts), vp(tw),
+                                                    vp(tb), len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
+                                                    self.n_regs, vp(nr), vp(ns), vp(rs), ctypes.byref(h))
+                elif self.planes:   # (only a circuit with planes: every other keeps the creator it has)
                     tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
                                    for g in range(len(self.gates))], dtype=np.uint32)
                     rc = L.sgfhe_circuit_create_data(self.n_inputs, self.planes, vp(kind), vp(start), vp(tr), vp(ts), vp(tw),
@@ -444,7 +499,7 @@ class Circuit:
             return -1 if i == FALSE_ID or i < self.n_inputs else (i - self.n_inputs) // 3
 
         live = [False] * len(self.gates)
-        for ref in self.outputs:
+        for ref in self.outputs + self.next_refs:   # (a next state is a reader, as an output is)
             if node(ref) >= 0:
                 live[node(ref)] = True
         for g in range(len(self.gates) - 1, -1, -1):
@@ -478,9 +533,10 @@ class Circuit:
                 levels[level[g] - 1].append(g)
         return levels
 
-    def evaluate_plain(self, bits, data=None):
+    def evaluate_plain(self, bits, data=None, _next=False):
         """The circuit in clear: bits [n_inputs][instances] (bool) -> [n_outputs][instances] (bool).  data: the planes
-        of a circuit that has any, uint8 [planes][instances]."""
+        of a circuit that has any, uint8 [planes][instances].  (One step of a circuit with registers, whose values are
+        the first rows of `bits`; evaluate_plain_steps feeds them back.)"""
         bits = np.asarray(bits, dtype=bool).reshape(self.n_inputs, -1)
         inst = bits.shape[1]
         data = check_data(self, data, inst)
@@ -516,7 +572,28 @@ class Circuit:
                 wires[base], wires[base + 1], wires[base + 2] = x & y, x | y, x ^ y
         if not self.outputs:
             raise ValueError("circuit has no outputs")
-        return np.stack([val(ref, d) for ref, d in zip(self.outputs, self.output_shifts)])
+        out = np.stack([val(ref, d) for ref, d in zip(self.outputs, self.output_shifts)])
+        if not _next:
+            return out
+        return out, np.array([val(ref, d) for ref, d in zip(self.next_refs, self.next_shifts)], dtype=bool).reshape(self.n_regs, inst)
+
+    def evaluate_plain_steps(self, state_bits, stream_bits, data=None):
+        """A stepped run in clear: state_bits [registers][instances] (None: all FALSE), stream_bits
+        [steps][stream inputs][instances], data [steps][planes][instances] for a circuit with planes ->
+        (outputs [steps][n_outputs][instances], state [registers][instances] after the last step).  A step's outputs
+        are taken before the registers change."""
+        stream = np.asarray(stream_bits, dtype=bool)
+        if stream.ndim != 3 or stream.shape[1] != self.n_inputs - self.n_regs:
+            raise ValueError("stream_bits must be [steps][stream inputs=%d][instances]" % (self.n_inputs - self.n_regs))
+        steps, inst = stream.shape[0], stream.shape[2]
+        state = np.zeros((self.n_regs, inst), dtype=bool) if state_bits is None else \
+            np.asarray(state_bits, dtype=bool).reshape(self.n_regs, inst).copy()
+        data = check_step_data(self, data, steps, inst)
+        outs = np.zeros((steps, len(self.outputs), inst), dtype=bool)
+        for s in range(steps):
+            outs[s], state = self.evaluate_plain(np.concatenate([state, stream[s]]), None if data is None else data[s],
+                                                 _next=True)
+        return outs, state
 
 
 def check_data(circuit, data, instances):
@@ -532,6 +609,17 @@ def check_data(circuit, data, instances):
     if d.dtype != np.uint8 or d.shape != (circuit.planes, instances):
         raise ValueError("data must be uint8 [planes=%d][instances=%d], got %s %r"
                          % (circuit.planes, instances, d.dtype, d.shape))
+    return d
+
+
+def check_step_data(circuit, data, steps, instances):
+    """The planes of a stepped run, checked: uint8 [steps][circuit.planes][instances]; None for a circuit without."""
+    if not circuit.planes or data is None:
+        return check_data(circuit, data, instances)
+    d = np.asarray(data)
+    if d.dtype != np.uint8 or d.shape != (steps, circuit.planes, instances):
+        raise ValueError("data must be uint8 [steps=%d][planes=%d][instances=%d], got %s %r"
+                         % (steps, circuit.planes, instances, d.dtype, d.shape))
     return d
 
 
@@ -628,6 +716,50 @@ def crc16_ccitt(message_bits, refresh_inputs=True):
     as gf2_matvec(crc16_matrix(message_bits)): 16 sum nodes, plus one refresh per message bit when asked.  Inputs and
     outputs in the bit orders of crc16_matrix."""
     return gf2_matvec(crc16_matrix(message_bits), refresh_inputs=refresh_inputs)
+
+
+def serial_adder():
+    """A bit-serial adder: Circuit(3, registers=1) whose register is the carry and whose stream inputs are one bit of
+    x and one of y per step, LSB first.  One full_adder -- one bootstrap -- per step: the output is the sum bit (XOR3),
+    the next state the carry (MAJ, a gate row, so nothing accumulates over the steps).  Numbers of any width in a wire
+    table of one step; the carry-out is the state after the last step."""
+    c = Circuit(3, registers=1)
+    s, carry = c.full_adder(c.stream_inputs[0], c.stream_inputs[1], c.registers[0])
+    c.output(s)
+    c.next_state(carry)
+    return c
+
+
+def crc16_stream_matrix(chunk_bits):
+    """The 16 x (16 + chunk_bits) 0/1 matrix of one CRC-16/XMODEM step, crc' = binascii.crc_hqx(chunk, crc), which is
+    GF(2)-linear in (crc, chunk): columns 0 .. 15 are the bits of the running CRC (LSB first), the others the chunk's
+    bits in the order the CRC consumes them; rows as crc16_matrix.  From binascii.crc_hqx on unit vectors."""
+    import binascii
+    if chunk_bits < 8 or chunk_bits % 8:
+        raise ValueError("crc16: a chunk is a whole number of bytes")
+    M = np.zeros((16, 16 + chunk_bits), dtype=np.uint8)
+    zero = bytes(chunk_bits // 8)
+    for j in range(16):
+        crc = binascii.crc_hqx(zero, 1 << j)
+        M[:, j] = [(crc >> k) & 1 for k in range(16)]
+    M[:, 16:] = crc16_matrix(chunk_bits)
+    return M
+
+
+def crc16_stream(chunk_bits):
+    """CRC-16 (binascii.crc_hqx) of a message of any whole number of chunks, one chunk of `chunk_bits` bits per step:
+    Circuit(16 + chunk_bits, registers=16) whose registers hold the running CRC (bit k in register k) and whose stream
+    inputs are the chunk's bits in the order the CRC consumes them (bit 7 of byte 0 first).  The state update is
+    gf2_matvec's construction over (state ++ refreshed chunk): the chunk bits, fresh encryptions, are refreshed first;
+    the registers are HI wires already.  Next state = the 16 HI wires = the outputs: after the last chunk the outputs
+    are the CRC of the whole message (registers that start FALSE: initial value 0).  chunk_bits + 16 bootstraps a step."""
+    M = crc16_stream_matrix(chunk_bits).astype(bool)
+    c = Circuit(16 + int(chunk_bits), registers=16)
+    src = list(c.registers) + [c.refresh(w) for w in c.stream_inputs]
+    hi = [c.xor(*[src[j] for j in np.flatnonzero(row)]) for row in M]
+    c.output(*hi)
+    c.next_state(*hi)
+    return c
 
 
 def _at_scale(circuit, w, want):
@@ -749,7 +881,7 @@ def lwe_not(words, r, one=None):
     return (t + np.uint64(r) - words) & np.uint64(r - 1)
 
 
-def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None):
+def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None, call0=0, _next=False):
     """The circuit composed on the host from whole-level bootstrap calls, in the row and call order of
     sgfhe_circuit_run: inputs [n_inputs][instances][n + 1] -> outputs [n_outputs][instances][n + 1].
     `boot(call, a1, b1, a2, b2)` runs one call (rows of at most CALL_ROWS) and returns [rows][3][n + 1];
@@ -764,8 +896,8 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None):
     sibling's table -- boot_lut is a function of (call, row, index, table) --, all siblings of a call in one further
     boot_lut(call, ...) whose rows and indices repeat.  data: the planes of a circuit that has any, uint8
     [planes][instances]; the row of a data node or data sibling at instance t goes to boot_lut with the table
-    data[plane][t].  A checking and measuring aid: the engine's circuit path does this on the device
-    (Engine.circuit_run)."""
+    data[plane][t].  call0: the number of the first call (replay_steps counts on from step to step).  A checking and
+    measuring aid: the engine's circuit path does this on the device (Engine.circuit_run)."""
     inputs = np.asarray(inputs, dtype=np.uint64)
     inst, row = inputs.shape[1], inputs.shape[2]
     data = check_data(circuit, data, inst)
@@ -779,7 +911,7 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None):
         v = lane_shift(v, d, circuit.group)
         return lwe_not(v, r, one) if ref & NOT_BIT else v
 
-    call = 0
+    call = call0
     for nodes in circuit.schedule():
         # row = rank * instances + instance
         mask = np.uint64(r - 1)
@@ -833,8 +965,33 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None):
                 wires[circuit.n_inputs + 3 * g + w] = res[sl, w]
             if circuit.kind(g) not in ("classic", "lut", "data"):
                 wires[circuit.n_inputs + 3 * g + 2] = (x[sl] + y[sl] - np.uint64(2) * res[sl, 0]) & mask
-    return np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
+    out = np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
         else np.zeros((0, inst, row), np.uint64)
+    if not _next:
+        return out
+    # the registers' next states: NOT at the register's own codeword Dr >> scale
+    nxt = [val(ref, d, (r // 4) >> k) for ref, d, k in zip(circuit.next_refs, circuit.next_shifts, circuit.reg_scales)]
+    return out, np.array(nxt, dtype=np.uint64).reshape(circuit.n_regs, inst, row), call
+
+
+def replay_steps(circuit, state, stream, r, boot, boot_lut=None, data=None, emit=None):
+    """A stepped run (sgfhe_circuit_run_steps) composed on the host from replay_levels: state [registers][instances][n + 1]
+    (None: every register FALSE), stream [steps][stream inputs][instances][n + 1], data [steps][planes][instances],
+    emit [steps] (None: every step) -> (outputs [emitted steps][n_outputs][instances][n + 1], the state after the last
+    step).  Step s is replay_levels on (state ++ stream[s]) with data[s]; `call` goes on counting from step to step; the
+    outputs are taken before the feedback.  boot, boot_lut: as in replay_levels.  A checking aid, like replay_levels."""
+    stream = np.asarray(stream, dtype=np.uint64)
+    steps, inst, row = stream.shape[0], stream.shape[2], stream.shape[3]
+    state = np.zeros((circuit.n_regs, inst, row), dtype=np.uint64) if state is None else \
+        np.asarray(state, dtype=np.uint64).reshape(circuit.n_regs, inst, row)
+    data = check_step_data(circuit, data, steps, inst)
+    outs, call = [], 0
+    for s in range(steps):
+        out, state, call = replay_levels(circuit, np.concatenate([state, stream[s]]), r, boot, boot_lut,
+                                         data=None if data is None else data[s], call0=call, _next=True)
+        if emit is None or emit[s]:
+            outs.append(out)
+    return (np.stack(outs) if outs else np.zeros((0, circuit.n_outputs, inst, row), np.uint64)), state
 
 
 def pack_calls(n):
@@ -1149,3 +1306,75 @@ def evaluate_circuit(bkey, rng, circuit, inputs, data=None):
         return out
     return [[EncryptedBit(LWE(out[o, t, :n], out[o, t, n])) for t in range(out.shape[1])]
             for o in range(out.shape[0])]
+
+
+def evaluate_circuit_steps(bkey, rng, circuit, state, stream, data=None, emit=None):
+    """A circuit with registers over many instances and many steps on the HIP engine (Engine.circuit_run_steps): one
+    queued run, the registers fed back on the device.  rng as in evaluate_circuit.
+    state: [registers][instances] of EncryptedBit, the array form [registers][instances][n + 1], or None (every register
+    FALSE); stream: [steps][stream inputs][instances] of EncryptedBit or the array form [steps][stream inputs]
+    [instances][n + 1]; data: uint8 [steps][planes][instances] for a circuit with planes; emit: [steps] of bool, the steps
+    whose outputs are wanted (None: all).
+    Returns (outputs [emitted steps][n_outputs][instances], state [registers][instances] after the last step), of
+    EncryptedBit -- in the array form when `stream` came in the array form."""
+    n = bkey.params.n
+    as_bits = not isinstance(stream, np.ndarray)
+
+    def arr(rows, count):   # [count][instances] of EncryptedBit -> [count][instances][n + 1]
+        out = np.zeros((count, len(rows[0]) if count else 0, n + 1), dtype=np.uint64)
+        for i, row_ in enumerate(rows):
+            if len(row_) != out.shape[1]:
+                raise ValueError("ragged inputs: one EncryptedBit per instance")
+            for t, e in enumerate(row_):
+                out[i, t, :n] = e.lwe.a
+                out[i, t, n] = e.lwe.b
+        return out
+
+    def bits(a):
+        return [[EncryptedBit(LWE(row_[t, :n], row_[t, n])) for t in range(row_.shape[0])] for row_ in a]
+
+    if as_bits:
+        stream = np.stack([arr(step, circuit.n_inputs - circuit.n_regs) for step in stream])
+    if state is not None and not isinstance(state, np.ndarray):
+        state = arr(state, circuit.n_regs)
+    with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
+        _set_flatten_mode(bkey, rng)
+        out, st = bkey.engine.circuit_run_steps(circuit, state, stream, data=data, emit=emit)
+    if not as_bits:
+        return out, st
+    return [bits(step) for step in out], bits(st)
+
+
+def evaluate_circuit_steps_ct(bkey, rng, circuit, state_cts, stream_cts, direct=False, lift=False, data=None, emit=None):
+    """A stepped run on RLWE ciphertexts (Engine.circuit_run_steps_ct): every step's stream ciphertexts are split on
+    the device, every emitted step's outputs packed on the device; the registers stay on the device in between.
+    state_cts: [registers][blocks] of PackedCiphertext or Ciphertext, or None (every register FALSE); stream_cts:
+    [steps][stream inputs][blocks], all of one kind; direct, lift: as evaluate_circuit_ct; data: uint8
+    [steps][planes][blocks * n]; emit: as evaluate_circuit_steps.  Registers of scale 0 only.
+    Returns (outputs [emitted steps][n_outputs][blocks] of Ciphertext, state): the state after the last step as the
+    LWE array [registers][blocks * n][n + 1] (feed it to evaluate_circuit_steps, or pack it)."""
+    p = bkey.params
+    flat = [ct for step in stream_cts for row_ in step for ct in row_] + [ct for row_ in (state_cts or []) for ct in row_]
+    if not flat:
+        raise ValueError("evaluate_circuit_steps_ct: at least one ciphertext is needed (it fixes the blocks)")
+    kind = type(flat[0])
+    if kind not in (PackedCiphertext, Ciphertext) or any(type(ct) is not kind for ct in flat):
+        raise TypeError("evaluate_circuit_steps_ct: PackedCiphertext or Ciphertext, all of one kind")
+    N = p.n if kind is PackedCiphertext else p.m
+
+    def ab(rows, lead):   # nested lists of ciphertexts -> a, b [lead..][blocks][N]
+        cts = np.array([[np.asarray(ct.rlwe.a, dtype=np.uint64), np.asarray(ct.rlwe.b, dtype=np.uint64)] for ct in rows],
+                       dtype=np.uint64).reshape(lead + (-1, 2, N))
+        return np.ascontiguousarray(cts[..., 0, :]), np.ascontiguousarray(cts[..., 1, :])
+
+    n_stream = circuit.n_inputs - circuit.n_regs
+    a, b = ab([ct for step in stream_cts for row_ in step for ct in row_], (len(stream_cts), n_stream))
+    sa = sb = None
+    if state_cts is not None:
+        sa, sb = ab([ct for row_ in state_cts for ct in row_], (circuit.n_regs,))
+    with bkey.engine.lock:                       # mode and run stay together (threads sharing a key)
+        _set_flatten_mode(bkey, rng)
+        (w, v), st = bkey.engine.circuit_run_steps_ct(circuit, sa, sb, a, b, N=N, direct=direct, lift=lift, data=data,
+                                                      emit=emit)
+    return [[[Ciphertext(p, RLWE(w[s, o, t], v[s, o, t])) for t in range(w.shape[2])] for o in range(w.shape[1])]
+            for s in range(w.shape[0])], st

@@ -7,7 +7,7 @@
 // circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
 // circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp, circuit_lut_multi_sanitized.cpp,
-// circuit_data_sanitized.cpp and circuit_calls_sanitized.cpp drive it under ASan / UBSan on the CPU.
+// circuit_data_sanitized.cpp, circuit_calls_sanitized.cpp and circuit_steps_sanitized.cpp drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -39,6 +39,9 @@ struct CircuitImage {
     uint32_t node_kind = 0, term_start = 0, term_ref = 0, term_shift = 0, term_weight = 0;
     uint32_t out_slot = 0, out_ref = 0, out_shift = 0, input_slot = 0, jobs = 0, words = 0;
     uint32_t fam_start = 0, fam_entry = 0;   // behind `jobs`, and only in a plan that has live siblings
+    // behind those, and only in a plan with registers (sgfhe_circuit_create_seq); the registers' slots are the first
+    // n_regs entries of input_slot
+    uint32_t next_ref = 0, next_shift = 0, next_scale = 0, reg_index = 0;
 };
 
 struct CircuitPlan {
@@ -46,6 +49,8 @@ struct CircuitPlan {
     uint32_t levels = 0, widest = 0, slots = 0;
     uint32_t group = 1;                 // lane group size G (sgfhe_circuit_create_lanes); 1: no reference is shifted
     uint32_t n_planes = 0;              // data planes of a run (sgfhe_circuit_create_data); 0: every table is the plan's
+    uint32_t n_regs = 0;                // registers (sgfhe_circuit_create_seq): input wires 0 .. n_regs, fed back by a
+                                        // stepped run; 0: a feed-forward plan
     std::vector<uint32_t> level;        // [n_gates]: level of every node, 0 = pruned
     std::vector<uint32_t> order;        // live nodes, level by level, ascending index within a level
     std::vector<uint32_t> level_start;  // [levels + 2]: level L's nodes are order[level_start[L] .. level_start[L + 1])
@@ -89,12 +94,21 @@ struct CircuitPlan {
                                         // three wires (CIRC_NONE if unread)
     std::vector<uint32_t> fam_node;     // [live siblings], host only: the sibling's node index; its wires are the probe
                                         // rows n_inputs + 3 live() + 3 i + w
+    // Registers (sgfhe_circuit_create_seq): after a step register i takes the value of next_ref[i] (a slot reference)
+    // read at the lane shift next_shift[i]; NOT on it is taken at the codeword Dr >> reg_scale[i].  reg_index is 0, 1, ..
+    // (the "slots" of the state buffer, for the split of state ciphertexts).  All empty in a plan without registers.
+    std::vector<uint32_t> next_ref;     // [n_regs]
+    std::vector<int32_t> next_shift;    // [n_regs]
+    std::vector<uint32_t> reg_scale;    // [n_regs]: 0, 1, 2
+    std::vector<uint32_t> reg_index;    // [n_regs]
     // Every device table above in one array, uploaded once per run: node_kind, term_start, term_ref, term_shift,
-    // term_weight, out_slot, out_ref, out_shift, input_slot, jobs (then fam_start, fam_entry), each at its offset `at`
+    // term_weight, out_slot, out_ref, out_shift, input_slot, jobs (then fam_start, fam_entry; then next_ref, next_shift,
+    // reg_scale, reg_index), each at its offset `at`
     std::vector<uint32_t> image;
     CircuitImage at;
 
     size_t live() const { return order.size(); }
+    uint32_t n_stream() const { return n_inputs - n_regs; }   // the inputs a step brings
     bool lanes() const { return group > 1; }   // (group 1 admits no shift but 0)
     // live nodes order[ka .. kb] hold a sum node: the call takes an XOR3 kernel for its LOW rows
     bool gate3_in(uint32_t ka, uint32_t kb) const { return sum_before[kb + 1] != sum_before[ka]; }
@@ -156,13 +170,27 @@ struct CircuitNodes {
     int32_t weight(size_t i) const { return weights ? weights[i] : 1; }
 };
 
-// Builds `P` from the nodes `N` (gate shifts / out_shift NULL: all 0).  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
+// The registers of sgfhe_circuit_create_seq: input wires 0 .. n_regs; next_ref [n_regs] wire references validated like
+// outputs, next_shift [n_regs] (NULL: all 0), reg_scale [n_regs] (NULL: all 0; each 0, 1 or 2).
+struct CircuitRegs {
+    uint32_t n_regs;
+    const uint32_t *next_ref;
+    const int32_t *next_shift;
+    const uint32_t *reg_scale;
+    uint32_t scale(uint32_t i) const { return reg_scale ? reg_scale[i] : 0u; }
+};
+
+// Builds `P` from the nodes `N` (gate shifts / out_shift NULL: all 0).  `R` (NULL or n_regs 0: none): the registers; their
+// next-state references count as readers exactly as outputs do -- liveness, levels, slot lifetime -- so the plan's
+// order, levels and slots are those of the plan whose outputs are outputs ++ next_ref.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
 // malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it, and a refused circuit costs no
 // allocation.
 inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
-                                  const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
+                                  const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P,
+                                  const CircuitRegs *R = nullptr) noexcept {
     using circuit_detail::wire_id;
     const uint32_t *refs = N.refs;
+    const uint32_t n_regs = R ? R->n_regs : 0u;
     const int32_t *gate_shift = N.shifts;
     // ---- validate: every size below 2^31, wire ids below the constant, inputs name earlier wires only,
     // every shift inside the group (in 64 bits: -INT32_MIN does not exist).  CIRC_NO_INPUT is above every wire id, so
@@ -172,6 +200,12 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
     if (n_inputs >= 0x80000000u || n_gates >= 0x80000000u || n_outputs >= 0x80000000u) return SGFHE_ERR_INVALID_ARG;
     const uint64_t n_wires = (uint64_t)n_inputs + 3 * (uint64_t)n_gates;
     if (n_wires >= CIRC_FALSE) return SGFHE_ERR_INVALID_ARG;
+    if (n_regs > n_inputs || (n_regs && !R->next_ref)) return SGFHE_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_regs; i++) {   // (CIRC_NO_INPUT is above every wire id)
+        const uint32_t id = wire_id(R->next_ref[i]);
+        if ((id != CIRC_FALSE && id >= n_wires) || R->scale(i) > 2u) return SGFHE_ERR_INVALID_ARG;
+        if (R->next_shift && !shift_ok(R->next_shift[i])) return SGFHE_ERR_INVALID_ARG;
+    }
     if (!N.arity) {   // the CSR itself, node by node, before a term of the node is read
         if (n_gates && (!N.kind || !N.start || !N.weights || N.start[0] != 0)) return SGFHE_ERR_INVALID_ARG;
         if (n_gates && N.lut && !N.tables) return SGFHE_ERR_INVALID_ARG;
@@ -209,14 +243,17 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         const uint32_t id = wire_id(outputs[o]);
         if (id != CIRC_FALSE && id >= n_wires) return SGFHE_ERR_INVALID_ARG;
     }
-    if (N.lut) {
+    bool scaled_reg = false;
+    for (uint32_t i = 0; i < n_regs; i++) scaled_reg = scaled_reg || R->scale(i) != 0;
+    if (N.lut || scaled_reg) {
         // ---- the scale rule: a wire carries its bit at the codeword Dr >> scale.  Scale 0: inputs, every wire of a
         // classic or sum node, wire +0 of a LUT node; wires +1 and +2 of a LUT node have scales 1 and 2.  Position i of
         // a LUT node reads the constant or a wire of scale 2 - i; every other reference reads scale 0.
         auto scale_ok = [&](uint32_t ref, uint32_t want) {
             const uint32_t id = wire_id(ref);
             if (id == CIRC_FALSE) return true;
-            const uint32_t have = id < n_inputs || !N.is_lut((id - n_inputs) / 3) ? 0u : (id - n_inputs) % 3;
+            if (id < n_inputs) return (id < n_regs ? R->scale(id) : 0u) == want;   // a register has the scale it was given
+            const uint32_t have = !N.is_lut((id - n_inputs) / 3) ? 0u : (id - n_inputs) % 3;
             return have == want;
         };
         for (size_t g = 0; g < n_gates; g++)
@@ -224,6 +261,8 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
                 if (!scale_ok(refs[i], N.is_lut(g) ? 2u - (uint32_t)p : 0u)) return SGFHE_ERR_INVALID_ARG;
         for (size_t o = 0; o < n_outputs; o++)
             if (!scale_ok(outputs[o], 0u)) return SGFHE_ERR_INVALID_ARG;
+        for (uint32_t i = 0; i < n_regs; i++)   // a register is fed the constant or a wire of its own scale
+            if (!scale_ok(R->next_ref[i], R->scale(i))) return SGFHE_ERR_INVALID_ARG;
     }
     for (size_t g = 0; gate_shift && g < n_gates; g++)   // (the shift beside CIRC_NO_INPUT is ignored)
         for (size_t i = N.first(g), end = i + N.count(g); i < end; i++)
@@ -237,6 +276,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         P.n_outputs = (uint32_t)n_outputs;
         P.group = group;
         P.n_planes = N.n_planes;
+        P.n_regs = n_regs;
         const uint32_t NG = (uint32_t)n_gates;
         auto node_of = [&](uint32_t id) -> int64_t {   // producing node of a wire, -1 for inputs and the constant
             return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
@@ -248,6 +288,10 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         std::vector<uint8_t> live(NG, 0);
         for (size_t o = 0; o < n_outputs; o++) {
             const int64_t g = node_of(wire_id(outputs[o]));
+            if (g >= 0) live[g] = 1;
+        }
+        for (uint32_t i = 0; i < n_regs; i++) {
+            const int64_t g = node_of(wire_id(R->next_ref[i]));
             if (g >= 0) live[g] = 1;
         }
         for (uint32_t g = NG; g-- > 0;) {
@@ -303,6 +347,10 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             }
         for (size_t o = 0; o < n_outputs; o++) {
             const uint32_t id = wire_id(outputs[o]);
+            if (id != CIRC_FALSE) last_read[id] = END;
+        }
+        for (uint32_t i = 0; i < n_regs; i++) {   // the feedback reads at the end of the step
+            const uint32_t id = wire_id(R->next_ref[i]);
             if (id != CIRC_FALSE) last_read[id] = END;
         }
         // ---- slots: a wire written at level L takes the lowest free slot; a slot is free again after the
@@ -407,6 +455,13 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.out_gate[o] = (id - n_inputs) % 3;
         }
         P.term_start.push_back((uint32_t)P.term_ref.size());
+        // ---- the registers' next states as slot references
+        for (uint32_t i = 0; i < n_regs; i++) {
+            P.next_ref.push_back(slot_ref(R->next_ref[i]));
+            P.next_shift.push_back(shift_of(R->next_ref[i], R->next_shift, i));
+            P.reg_scale.push_back(R->scale(i));
+            P.reg_index.push_back(i);
+        }
         // ---- the direct-pack jobs, by producing node
         std::vector<uint32_t> byk;
         for (uint32_t o = 0; o < n_outputs; o++)
@@ -427,7 +482,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             return (uint32_t)at;
         };
         P.image.reserve(P.node_kind.size() + P.term_start.size() + 3 * P.term_ref.size() + P.out_slot.size() +
-                        2 * n_outputs + n_inputs + P.jobs.size());
+                        2 * n_outputs + n_inputs + P.jobs.size() + 4 * (size_t)n_regs);
         P.at.node_kind = place(P.node_kind);
         P.at.term_start = place(P.term_start);
         P.at.term_ref = place(P.term_ref);
@@ -441,6 +496,12 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         if (P.siblings()) {
             P.at.fam_start = place(P.fam_start);
             P.at.fam_entry = place(P.fam_entry);
+        }
+        if (n_regs) {
+            P.at.next_ref = place(P.next_ref);
+            P.at.next_shift = place(P.next_shift);
+            P.at.next_scale = place(P.reg_scale);
+            P.at.reg_index = place(P.reg_index);
         }
         P.at.words = (uint32_t)P.image.size();
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
@@ -503,6 +564,19 @@ inline int32_t circuit_plan_data(uint32_t n_inputs, uint32_t n_planes, const uin
                                  const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
     const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
     return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
+}
+
+// The arrays of sgfhe_circuit_create_seq: those of sgfhe_circuit_create_data, and the registers.  With n_regs = 0 the
+// plan is the sgfhe_circuit_create_data plan, field for field.
+inline int32_t circuit_plan_seq(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
+                                const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
+                                const int32_t *out_shift, size_t n_outputs, uint32_t group, uint32_t n_regs,
+                                const uint32_t *next_ref, const int32_t *next_shift, const uint32_t *reg_scale,
+                                CircuitPlan &P) noexcept {
+    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
+    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P, &R);
 }
 
 // The arrays of sgfhe_circuit_create_lanes.

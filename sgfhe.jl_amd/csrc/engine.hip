@@ -230,6 +230,8 @@ struct sgfhe_ctx : CtxShared, CtxKnobs, CtxKeyState {
     DevBuf<uint64_t> circ_wires, circ_stage, circ_out;
     DevBuf<uint32_t> circ_tab;
     DevBuf<uint8_t> circ_data;            // the data planes of a run (sgfhe_circuit_run_data): [n_planes][instances]
+    // sgfhe_circuit_run_steps: the registers between steps, [n_regs][instances][n + 1]
+    DevBuf<uint64_t> circ_state;
     // sgfhe_circuit_run_ct: the uploaded input ciphertexts [a | b], each [n_inputs][blocks][N]
     DevBuf<uint64_t> circ_ct;
     // work buffers of the packing path (pack_tail), shared by sgfhe_pack_encrypted_bits and the pack stage
@@ -1491,6 +1493,7 @@ static void free_circuit_buffers(sgfhe_ctx *c) {
     c->circ_out.release();
     c->circ_tab.release();
     c->circ_data.release();
+    c->circ_state.release();
     c->circ_ct.release();
     c->circ_raw.release();
     c->noise_tab.release();
@@ -2725,11 +2728,12 @@ int32_t sgfhe_timing_read(sgfhe_ctx *c, double *stats, int reset) {
 // every entry: `N` views its node arrays (csrc/circuit.h).  A refused circuit allocates nothing: the plan is
 // validated into a local first
 static int32_t circuit_create(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
-                              const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out) {
+                              const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out,
+                              const CircuitRegs *regs = nullptr) {
     if (!out) return SGFHE_ERR_INVALID_ARG;
     *out = nullptr;
     CircuitPlan plan;
-    const int32_t rc = circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, plan);
+    const int32_t rc = circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, plan, regs);
     if (rc) return rc;
     sgfhe_circuit *c = new (std::nothrow) sgfhe_circuit();
     if (!c) return SGFHE_ERR_OOM;
@@ -2783,6 +2787,23 @@ int32_t sgfhe_circuit_create_data(uint32_t n_inputs, uint32_t n_planes, const ui
     return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
 }
 
+int32_t sgfhe_circuit_create_seq(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
+                                 const uint32_t *node_start, const uint32_t *term_ref, const int32_t *term_shift,
+                                 const int32_t *term_weight, const uint32_t *node_table, size_t n_gates,
+                                 const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                                 uint32_t n_regs, const uint32_t *next_ref, const int32_t *next_shift,
+                                 const uint32_t *reg_scale, sgfhe_circuit **out) {
+    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
+    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out, &R);
+}
+
+int32_t sgfhe_circuit_registers(const sgfhe_circuit *c, uint32_t *n_regs) {
+    if (!c || !n_regs) return SGFHE_ERR_INVALID_ARG;
+    *n_regs = c->plan.n_regs;
+    return SGFHE_OK;
+}
+
 int32_t sgfhe_circuit_planes(const sgfhe_circuit *c, uint32_t *n_planes) {
     if (!c || !n_planes) return SGFHE_ERR_INVALID_ARG;
     *n_planes = c->plan.n_planes;
@@ -2821,6 +2842,17 @@ struct CircuitCt {
     uint64_t *out_w, *out_v;       // [n_outputs][blocks][m], or both NULL
     bool direct;                   // SGFHE_CIRCUIT_PACK_DIRECT
     bool lift;                     // SGFHE_CIRCUIT_PACK_LIFT (with direct): what is not direct is lifted, not refreshed
+};
+
+// A stepped run (sgfhe_circuit_run_steps[_ct]): the plan evaluated `steps` times over the same instances, the registers
+// fed back on the device after every step.  The run's `in` / ct->in_a, in_b / data / out / ct->out_w, out_v are then
+// per step (per emitted step, for the outputs).
+struct CircuitSteps {
+    size_t steps;
+    const uint8_t *emit;                // [steps], NULL: every step's outputs are collected
+    const uint64_t *state_in;           // LWE form: [n_regs][instances][n + 1], NULL: every register FALSE
+    const uint64_t *state_a, *state_b;  // ciphertext form: [n_regs][blocks][N], both NULL: every register FALSE
+    uint64_t *state_out;                // [n_regs][instances][n + 1] after the last step, optional
 };
 
 // ---- noise probe: LWE error statistics against the secret key, on the device -------------
@@ -2908,6 +2940,7 @@ struct CircuitRun {
     const CircuitCt *ct;
     CircuitProbe *probe;
     const uint8_t *data;
+    const CircuitSteps *seq = nullptr;   // a stepped run (run_steps)
     const hipStream_t st = c->stream;
     const size_t n = c->n, row = n + 1, M = c->M;   // row: words of an LWE
     const uint32_t inst = (uint32_t)instances;
@@ -2917,12 +2950,15 @@ struct CircuitRun {
     // raw table (k_circ_lift), so no group has a refreshed one
     const bool pack = ct && ct->out_w, direct = pack && ct->direct, lift = direct && ct->lift;
     const CircuitRunSizes sz = circuit_run_sizes(P, instances, n, ct ? ct->blocks : 0, pack, direct, lift);
+    // (a stepped run splits the registers' ciphertexts and a step's stream ciphertexts in turn through the one buffer)
     const size_t ct_words = ct ? (size_t)P.n_inputs * ct->blocks * ct->N : 0;
     const size_t probe_rows = probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
     // the plan's tables on the device (views into circ_tab), and the probe's
     CircNodes nodes = {};
     const uint32_t *d_out_slot = nullptr, *d_out_ref = nullptr, *d_in_slot = nullptr, *d_jobs = nullptr;
     const uint32_t *d_fam_start = nullptr, *d_fam_entry = nullptr;   // (a plan with live siblings)
+    const uint32_t *d_next_ref = nullptr, *d_next_scale = nullptr, *d_reg_index = nullptr;   // (a plan with registers)
+    const int32_t *d_next_shift = nullptr;
     const int32_t *d_out_shift = nullptr;
     NoiseLayout NL = {};
     std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
@@ -2937,8 +2973,18 @@ struct CircuitRun {
     int32_t upload_lwe();
     int32_t level_call(uint32_t L, uint64_t row0);
     int32_t pack_group(size_t q0);
+    int32_t fetch(uint64_t *o, uint64_t *w, uint64_t *v);
     int32_t download();
     int32_t run();
+    // a stepped run
+    int32_t upload_state();
+    int32_t upload_step(size_t s);
+    int32_t feedback();
+    int32_t run_steps();
+    int32_t split(const uint64_t *a, const uint64_t *b, uint32_t count, const uint32_t *slot, uint64_t *rows);
+    int32_t copy_inputs(uint32_t first, const uint64_t *src);
+    size_t state_words() const { return (size_t)P.n_regs * instances * row; }
+    static uint32_t copy_grid(size_t total) { return (uint32_t)std::min<size_t>((total + 255) / 256, (size_t)1 << 20); }
     // the gather of one call: rows row0 .. row0 + rows of the level whose first node is `node0` of the plan's node table
     // (a level's first node, or live() for the pack stage's pseudo-level)
     // `lutw`: the call's LUT descriptor, for a level call that holds a LUT node
@@ -2964,6 +3010,7 @@ int32_t CircuitRun::grow() {
     if ((rc = circ_grow(c, c->circ_tab, P.at.words))) return rc;
     if (data && (rc = circ_grow(c, c->circ_data, (size_t)P.n_planes * instances))) return rc;
     if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
+    if (seq && (rc = circ_grow(c, c->circ_state, state_words()))) return rc;
     if (pack && (rc = pack_grow(c, sz.cpc, sz.n_ct, sz.max_ref))) return rc;
     if (probe) {
         size_t unread = 0;   // inputs nothing reads have no slot: the probe uploads them for itself
@@ -2998,7 +3045,8 @@ int32_t CircuitRun::grow() {
 // caller's array, as the inputs are), and the probe's
 int32_t CircuitRun::upload_tables() {
     HIPCHK(c, hipMemcpyAsync(c->circ_tab.p, P.image.data(), (size_t)P.at.words * 4, hipMemcpyHostToDevice, st));
-    if (data) HIPCHK(c, hipMemcpyAsync(c->circ_data.p, data, (size_t)P.n_planes * instances, hipMemcpyHostToDevice, st));
+    if (data && !seq)   // (a stepped run brings planes with every step: upload_step)
+        HIPCHK(c, hipMemcpyAsync(c->circ_data.p, data, (size_t)P.n_planes * instances, hipMemcpyHostToDevice, st));
     const uint32_t *tab = c->circ_tab.p;
     nodes = {tab + P.at.node_kind, tab + P.at.term_start, tab + P.at.term_ref,
              reinterpret_cast<const int32_t *>(tab + P.at.term_shift),
@@ -3006,6 +3054,10 @@ int32_t CircuitRun::upload_tables() {
     d_out_slot = tab + P.at.out_slot, d_out_ref = tab + P.at.out_ref, d_in_slot = tab + P.at.input_slot;
     d_jobs = tab + P.at.jobs;
     if (P.siblings()) d_fam_start = tab + P.at.fam_start, d_fam_entry = tab + P.at.fam_entry;
+    if (P.n_regs) {
+        d_next_ref = tab + P.at.next_ref, d_next_scale = tab + P.at.next_scale, d_reg_index = tab + P.at.reg_index;
+        d_next_shift = reinterpret_cast<const int32_t *>(tab + P.at.next_shift);
+    }
     d_out_shift = reinterpret_cast<const int32_t *>(tab + P.at.out_shift);
     if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
         HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
@@ -3015,29 +3067,40 @@ int32_t CircuitRun::upload_tables() {
 }
 
 // ciphertext form: the ciphertexts as they are, and extract() of every bit into the slot of its input wire
-int32_t CircuitRun::upload_ct() {
-    if (!P.n_inputs) return SGFHE_OK;
-    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p, ct->in_a, ct_words * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p + ct_words, ct->in_b, ct_words * 8, hipMemcpyHostToDevice, st));
+int32_t CircuitRun::upload_ct() { return split(ct->in_a, ct->in_b, P.n_inputs, d_in_slot, c->circ_wires.p); }
+
+// `count` wires of ciphertexts a, b [count][blocks][N] (host) split into the slots slot[0 .. count) (device) of `rows`
+// ([slot][instances][n + 1])
+int32_t CircuitRun::split(const uint64_t *a, const uint64_t *b, uint32_t count, const uint32_t *slot, uint64_t *rows) {
+    if (!count) return SGFHE_OK;
+    const size_t words = (size_t)count * ct->blocks * ct->N;
+    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p, a, words * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p + words, b, words * 8, hipMemcpyHostToDevice, st));
     const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
-    hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(P.n_inputs * ct->blocks * tiles)), dim3(256),
-                       (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct.p, c->circ_ct.p + ct_words, d_in_slot,
-                       c->circ_wires.p, (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
+    hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(count * ct->blocks * tiles)), dim3(256),
+                       (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct.p, c->circ_ct.p + words, slot, rows,
+                       (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
     HIPCHK(c, hipGetLastError());
     return SGFHE_OK;
 }
 
 // LWE form: inputs straight into their slots; runs of consecutive inputs in consecutive slots as one copy
-int32_t CircuitRun::upload_lwe() {
+int32_t CircuitRun::copy_inputs(uint32_t first, const uint64_t *src) {   // input wires first .. n_inputs, src[0] the first
     const size_t in_words = instances * row;
-    for (uint32_t i = 0; i < P.n_inputs;) {
+    for (uint32_t i = first; i < P.n_inputs;) {
         if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
         uint32_t k = i + 1;
         while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
-        HIPCHK(c, hipMemcpyAsync(c->circ_wires.p + (size_t)P.input_slot[i] * in_words, in + (size_t)i * in_words,
+        HIPCHK(c, hipMemcpyAsync(c->circ_wires.p + (size_t)P.input_slot[i] * in_words, src + (size_t)(i - first) * in_words,
                                  (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
         i = k;
     }
+    return SGFHE_OK;
+}
+
+int32_t CircuitRun::upload_lwe() {
+    const size_t in_words = instances * row;
+    if (const int32_t rc = copy_inputs(0, in)) return rc;
     // the probe of the input wires, from the rows as uploaded (before a level reuses a slot)
     for (uint32_t i = 0, u = 0; probe && i < P.n_inputs; i++) {
         const bool own = P.input_slot[i] == CIRC_NONE;
@@ -3169,19 +3232,7 @@ int32_t CircuitRun::pack_group(size_t q0) {
 
 // (w, v) of every ciphertext, the outputs in the LWE form, the probe's records; then the host waits
 int32_t CircuitRun::download() {
-    if (pack) {
-        const size_t wv = sz.n_ct * M;
-        HIPCHK(c, hipMemcpyAsync(ct->out_w, c->pack_wv.p, wv * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(ct->out_v, c->pack_wv.p + wv, wv * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (out) {
-        const size_t total = (size_t)P.n_outputs * instances * row;
-        const size_t blocks = std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
-        hipLaunchKernelGGL(k_circ_collect, dim3((uint32_t)blocks), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
-                           d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
-    }
+    if (const int32_t rc = fetch(out, ct ? ct->out_w : nullptr, ct ? ct->out_v : nullptr)) return rc;
     if (probe && probe_rows)
         HIPCHK(c, hipMemcpyAsync(probe->down.data(), NL.stats, probe_rows * 64, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -3195,8 +3246,101 @@ int32_t CircuitRun::download() {
     return SGFHE_OK;
 }
 
+// the outputs of the wire table as it stands, queued: (w, v) of the packed ciphertexts (a run that packs) and the
+// collected LWEs (`o` NULL: not wanted)
+int32_t CircuitRun::fetch(uint64_t *o, uint64_t *w, uint64_t *v) {
+    if (pack) {
+        const size_t wv = sz.n_ct * M;
+        HIPCHK(c, hipMemcpyAsync(w, c->pack_wv.p, wv * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(v, c->pack_wv.p + wv, wv * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (o) {
+        const size_t total = (size_t)P.n_outputs * instances * row;
+        hipLaunchKernelGGL(k_circ_collect, dim3(copy_grid(total)), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
+                           d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(o, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
+    }
+    return SGFHE_OK;
+}
+
+// ---- a stepped run: the stages around the level calls and pack groups of one step ---------------------------------
+
+// the registers' first values into the state buffer: the caller's LWEs, the split of the caller's ciphertexts, or FALSE
+int32_t CircuitRun::upload_state() {
+    if (!P.n_regs) return SGFHE_OK;
+    if (ct && seq->state_a) return split(seq->state_a, seq->state_b, P.n_regs, d_reg_index, c->circ_state.p);
+    if (!ct && seq->state_in)
+        HIPCHK(c, hipMemcpyAsync(c->circ_state.p, seq->state_in, state_words() * 8, hipMemcpyHostToDevice, st));
+    else
+        HIPCHK(c, hipMemsetAsync(c->circ_state.p, 0, state_words() * 8, st));
+    return SGFHE_OK;
+}
+
+// start of step s: the registers into their slots (one launch), the step's stream inputs into theirs, the step's planes
+int32_t CircuitRun::upload_step(size_t s) {
+    if (P.n_regs) {
+        hipLaunchKernelGGL(k_circ_state_load, dim3(copy_grid(state_words())), dim3(256), 0, st, c->circ_state.p, d_in_slot,
+                           c->circ_wires.p, state_words(), inst, (uint32_t)n);
+        HIPCHK(c, hipGetLastError());
+    }
+    int32_t rc;
+    if (ct) {
+        const size_t per = (size_t)P.n_stream() * ct->blocks * ct->N;
+        rc = split(ct->in_a + s * per, ct->in_b + s * per, P.n_stream(), d_in_slot + P.n_regs, c->circ_wires.p);
+    } else {
+        rc = copy_inputs(P.n_regs, in + s * (size_t)P.n_stream() * instances * row);
+    }
+    if (rc) return rc;
+    if (data) {
+        const size_t per = (size_t)P.n_planes * instances;
+        HIPCHK(c, hipMemcpyAsync(c->circ_data.p, data + s * per, per, hipMemcpyHostToDevice, st));
+    }
+    return SGFHE_OK;
+}
+
+// end of a step: every register's next state, from the wire table into the state buffer (one launch)
+int32_t CircuitRun::feedback() {
+    if (!P.n_regs) return SGFHE_OK;
+    hipLaunchKernelGGL(k_circ_next, dim3(copy_grid(state_words())), dim3(256), 0, st, c->circ_wires.p, d_next_ref,
+                       d_next_shift, d_next_scale, c->circ_state.p, state_words(), inst, (uint32_t)n, r, P.group);
+    HIPCHK(c, hipGetLastError());
+    return SGFHE_OK;
+}
+
+// Every step is the run() of the step plan: its level calls, then -- an emitted step -- its pack groups and its
+// outputs, taken before the feedback.  Everything is queued on the one stream; the host waits once, at the end.
+int32_t CircuitRun::run_steps() {
+    int32_t rc;
+    if ((rc = grow())) return rc;
+    if ((rc = upload_tables())) return rc;
+    if ((rc = upload_state())) return rc;
+    const size_t out_words = (size_t)P.n_outputs * instances * row, wv = sz.n_ct * M;
+    for (size_t s = 0, emitted = 0; s < seq->steps; s++) {
+        if ((rc = upload_step(s))) return rc;
+        for (uint32_t L = 1; L <= P.levels; L++)
+            for (uint64_t row0 = 0; row0 < P.level_rows(L, instances); row0 += SGFHE_CIRCUIT_CALL_ROWS)
+                if ((rc = level_call(L, row0))) return rc;
+        if (!seq->emit || seq->emit[s]) {
+            for (size_t q0 = 0; q0 < sz.n_ct; q0 += sz.cpc)
+                if ((rc = pack_group(q0))) return rc;
+            if ((rc = fetch(out ? out + emitted * out_words : nullptr, pack ? ct->out_w + emitted * wv : nullptr,
+                            pack ? ct->out_v + emitted * wv : nullptr)))
+                return rc;
+            emitted++;
+        }
+        if ((rc = feedback())) return rc;
+    }
+    if (seq->state_out && P.n_regs)
+        HIPCHK(c, hipMemcpyAsync(seq->state_out, c->circ_state.p, state_words() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->pending = false;
+    return SGFHE_OK;
+}
+
 int32_t CircuitRun::run() {
     int32_t rc;
+    if (seq) return run_steps();
     if ((rc = grow())) return rc;
     if ((rc = upload_tables())) return rc;
     if ((rc = ct ? upload_ct() : upload_lwe())) return rc;
@@ -3208,9 +3352,12 @@ int32_t CircuitRun::run() {
     return download();
 }
 
-// A plan with planes runs through the _data entries only (`with_data`), and with planes (unless it has no instances)
+// A plan with planes runs through the _data entries only (`with_data`), and with planes (unless it has no instances); a
+// plan with registers through none of the one-shot entries
 static int32_t circuit_data_ok(sgfhe_ctx *c, const sgfhe_circuit *circ, bool with_data, const uint8_t *data,
                                size_t instances) {
+    if (circ && circ->plan.n_regs)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: a plan with registers runs through the _steps entries");
     if (!circ || !circ->plan.n_planes) return SGFHE_OK;   // (a NULL circuit is the entry's own error)
     if (!with_data)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: a plan with data planes runs through the _data entries");
@@ -3414,6 +3561,75 @@ static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t bl
     const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
                           (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
     return run_drained(c, [&] { return CircuitRun(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data).run(); });
+}
+
+int32_t sgfhe_circuit_run_steps(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
+                                const uint64_t *state_in, const uint64_t *in, const uint8_t *data, const uint8_t *emit,
+                                uint64_t *out, uint64_t *state_out) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    if (!circ || (!in && circ->plan.n_stream()) || (!out && !state_out))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: NULL circuit or input pointer, or no output pointer");
+    const CircuitPlan &P = circ->plan;
+    if (!data && P.n_planes && instances && steps)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: NULL data for a plan with data planes");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    if (instances == 0 || steps == 0) return SGFHE_OK;
+    // the limits of sgfhe_circuit_run
+    if (instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: too many instances for this circuit");
+    if (instances % P.group)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: instances must be a multiple of the circuit's lane group");
+    const CircuitSteps seq = {steps, emit, state_in, nullptr, nullptr, state_out};
+    return run_drained(c, [&] {
+        CircuitRun R(c, P, instances, in, out, nullptr, nullptr, data);
+        R.seq = &seq;
+        return R.run();
+    });
+}
+
+int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
+                                   const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
+                                   const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit,
+                                   uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
+                                   uint32_t flags) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    if ((flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || flags == SGFHE_CIRCUIT_PACK_LIFT)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
+    if (!circ || ((!in_a || !in_b) && circ->plan.n_stream()) || !state_a != !state_b)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: NULL circuit or input pointer (state_a and state_b go together)");
+    const CircuitPlan &P = circ->plan;
+    for (uint32_t i = 0; i < P.n_regs; i++)   // a split ciphertext is scale 0, and an LWE cannot be halved
+        if (P.reg_scale[i])
+            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: a register of scale 1 or 2 has no ciphertext form");
+    if (!data && P.n_planes && blocks && steps)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: NULL data for a plan with data planes");
+    if (!out_w != !out_v || (!out_w && !out_lwe && !state_lwe))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: out_w and out_v go together, and one output form is needed");
+    if (N != c->n && N != c->M)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: N must be n (PackedCiphertext) or m (Ciphertext)");
+    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
+    if (out_w && !(pack_group(c)))
+        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
+    if (blocks == 0 || steps == 0) return SGFHE_OK;
+    // the limits of sgfhe_circuit_run_ct
+    const uint64_t instances = (uint64_t)blocks * c->n;
+    const uint64_t tiles = (c->n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS;
+    if (blocks >= 0x80000000u || instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull ||
+        (out_w && (uint64_t)P.n_outputs * instances > 0xFFFFFFFFull) ||
+        (uint64_t)P.n_inputs * blocks * tiles > 0x7FFFFFFFull)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: too many instances for this circuit");
+    if (c->n % P.group)   // (a group must not straddle two ciphertexts)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: n must be a multiple of the circuit's lane group");
+    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
+                          (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
+    const CircuitSteps seq = {steps, emit, nullptr, state_a, state_b, state_lwe};
+    return run_drained(c, [&] {
+        CircuitRun R(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data);
+        R.seq = &seq;
+        return R.run();
+    });
 }
 
 }  // extern "C"

@@ -2030,6 +2030,42 @@ k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ 
     }
 }
 
+// ---- registers of a stepped run (sgfhe_circuit_run_steps) ------------------------------------------------------------
+// The state buffer [n_regs][instances][n + 1] is the canonical value of the registers between steps; the wire table
+// only holds a copy for the length of a step.  Both kernels are memory-bound copies in the thread-to-word map of
+// k_circ_collect: one word per thread and step of the grid-stride loop, consecutive threads consecutive words of a row
+// (coalesced 8-byte accesses), the register decode uniform over a row.
+
+// Start of a step: register i's rows into its slot of the wire table (reg_slot = the first n_regs entries of the
+// plan's input_slot; a register nothing reads has no slot).  One launch for all registers.
+__global__ void __launch_bounds__(256)
+k_circ_state_load(const uint64_t *__restrict__ state, const uint32_t *__restrict__ reg_slot,
+                  uint64_t *__restrict__ wires, size_t total, uint32_t instances, uint32_t n) {
+    const size_t per_reg = (size_t)instances * (n + 1);
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t i = t / per_reg, w = t % per_reg;
+        const uint32_t slot = reg_slot[i];
+        if (slot != CIRC_SLOT_NONE) wires[(size_t)slot * per_reg + w] = state[t];
+    }
+}
+
+// End of a step: the next-state gather.  Register i takes next_ref[i] read at the lane shift next_shift[i] -- NOT, the
+// constant and the shift as k_circ_collect applies them to an output, with the codeword of NOT and of the TRUE fill
+// Dr >> next_scale[i], the register's scale.  It reads the wire table and writes the state buffer, never the same
+// words: a swap, a rotation, a register holding itself or reading a stream input need no ordering between threads.
+__global__ void __launch_bounds__(256)
+k_circ_next(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ next_ref,
+            const int32_t *__restrict__ next_shift, const uint32_t *__restrict__ next_scale,
+            uint64_t *__restrict__ state, size_t total, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+    const size_t per_reg = (size_t)instances * (n + 1);
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t i = t / per_reg, w = t % per_reg;
+        const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
+        state[t] = circ_word_lane(wires, next_ref[i], next_shift[i], group, instances, inst, e, n, r,
+                                  (r / 4) >> next_scale[i]);
+    }
+}
+
 // split_ciphertext (fhe.jl:287-290, extract :237-244) of the input ciphertexts of sgfhe_circuit_run_ct, straight
 // into the wire table.  ct_a / ct_b [n_inputs][blocks][N] (N = n or m); bit i of (input, block) becomes the row of
 // instance block * n + i in the input's slot: word j < n is a[i - j] for j <= i and -a[N - (j - i)] mod r beyond,

@@ -408,6 +408,86 @@ class Engine:
             return (w, v), out
         return (w, v) if packed else out
 
+    @staticmethod
+    def _step_args(circuit, data, emit, steps, instances):
+        """(planes array, its pointer, emit array, its pointer, emitted steps) of a stepped run."""
+        from .circuit import check_step_data
+        d = check_step_data(circuit, data, steps, instances)
+        pd = None
+        if d is not None:
+            d = np.ascontiguousarray(d)
+            pd = d.ctypes.data_as(ctypes.c_void_p)
+        if emit is None:
+            return d, pd, None, None, steps
+        e = np.ascontiguousarray(np.asarray(emit).astype(bool).astype(np.uint8))
+        if e.shape != (steps,):
+            raise ValueError("emit: one flag per step (%d)" % steps)
+        return d, pd, e, e.ctypes.data_as(ctypes.c_void_p), int(e.sum())
+
+    def circuit_run_steps(self, circuit, state, stream, data=None, emit=None):
+        """A circuit with registers (Circuit(registers=R)) evaluated `steps` times over the same instances in one queued
+        run, the registers fed back on the device (sgfhe_circuit_run_steps).
+        state: [registers][instances][n + 1] uint64, or None: every register FALSE; stream:
+        [steps][stream inputs][instances][n + 1]; data: uint8 [steps][planes][instances] for a circuit with planes;
+        emit: [steps] flags, the steps whose outputs are wanted (None: all).
+        Returns (out [emitted steps][n_outputs][instances][n + 1], state [registers][instances][n + 1] after the last
+        step).  Step s is, byte for byte, circuit_run of circuit.step_plan() on (state ++ stream[s])."""
+        n = self.params.n
+        x, px = _c(stream)
+        if x.ndim != 4 or x.shape[1] != circuit.n_inputs - circuit.n_regs or x.shape[3] != n + 1:
+            raise ValueError("circuit_run_steps: stream must be [steps][stream inputs=%d][instances][n+1=%d]"
+                             % (circuit.n_inputs - circuit.n_regs, n + 1))
+        steps, inst = x.shape[0], x.shape[2]
+        ps = None
+        if state is not None:
+            state, ps = _c(state)
+            if state.shape != (circuit.n_regs, inst, n + 1):
+                raise ValueError("circuit_run_steps: state must be [registers=%d][instances=%d][n+1]" % (circuit.n_regs, inst))
+        d, pd, e, pe, emitted = self._step_args(circuit, data, emit, steps, inst)
+        out = np.zeros((emitted, circuit.n_outputs, inst, n + 1), dtype=np.uint64)
+        st = np.zeros((circuit.n_regs, inst, n + 1), dtype=np.uint64)
+        self._call("sgfhe_circuit_run_steps", circuit.handle(), inst, steps, ps, px, pd, pe,
+                   out.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        return out, st
+
+    def circuit_run_steps_ct(self, circuit, state_a, state_b, a, b, N=None, packed=True, lwe=False, direct=False,
+                             lift=False, data=None, emit=None):
+        """The stepped run with RLWE ciphertexts at both ends (sgfhe_circuit_run_steps_ct).
+        state_a, state_b: [registers][blocks][N] or None (every register FALSE); a, b: [steps][stream inputs][blocks][N],
+        N = n or m (given as N when the circuit has no stream input and no state); packed, lwe, direct, lift: as
+        circuit_run_ct, per emitted step; data: uint8 [steps][planes][blocks * n]; emit: as circuit_run_steps.
+        Registers of scale 0 only.  Returns (outputs, state): outputs (w, v), each [emitted steps][n_outputs][blocks][m],
+        the LWE array [emitted steps][n_outputs][blocks * n][n + 1], or ((w, v), lwe), as circuit_run_ct; state
+        [registers][blocks * n][n + 1], the registers after the last step as LWEs."""
+        p = self.params
+        a, pa = _c(a)
+        b, pb = _c(b)
+        if a.ndim != 4 or a.shape != b.shape or a.shape[1] != circuit.n_inputs - circuit.n_regs or \
+                a.shape[3] not in (p.n, p.m) or (N is not None and a.shape[3] != N):
+            raise ValueError("circuit_run_steps_ct: a and b must be [steps][stream inputs=%d][blocks][N], N = n = %d or m = %d"
+                             % (circuit.n_inputs - circuit.n_regs, p.n, p.m))
+        if not packed and not lwe:
+            raise ValueError("circuit_run_steps_ct: ask for the packed outputs, the LWE outputs or both")
+        steps, blocks, N = a.shape[0], a.shape[2], a.shape[3]
+        psa = psb = None
+        if state_a is not None:
+            state_a, psa = _c(state_a)
+            state_b, psb = _c(state_b)
+            if state_a.shape != (circuit.n_regs, blocks, N) or state_b.shape != state_a.shape:
+                raise ValueError("circuit_run_steps_ct: state_a and state_b must be [registers=%d][blocks=%d][N=%d]"
+                                 % (circuit.n_regs, blocks, N))
+        d, pd, e, pe, emitted = self._step_args(circuit, data, emit, steps, blocks * p.n)
+        w = np.zeros((emitted, circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
+        v = np.zeros((emitted, circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
+        out = np.zeros((emitted, circuit.n_outputs, blocks * p.n, p.n + 1), dtype=np.uint64) if lwe else None
+        st = np.zeros((circuit.n_regs, blocks * p.n, p.n + 1), dtype=np.uint64)
+        ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None else None
+        flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
+        self._call("sgfhe_circuit_run_steps_ct", circuit.handle(), blocks, steps, psa, psb, pa, pb, N, pd, pe, ptr(w),
+                   ptr(v), ptr(out), ptr(st), flags)
+        res = ((w, v), out) if packed and lwe else ((w, v) if packed else out)
+        return res, st
+
     def pack_encrypted_bits(self, a, b):
         """pack_encrypted_bits (fhe.jl:660-696) for `count` groups of n LWEs: a [count][n][n],
         b [count][n] -> (w, v), each [count][m] uint64 over Z_r."""

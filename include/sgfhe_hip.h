@@ -345,6 +345,27 @@ int32_t sgfhe_debug_digits(sgfhe_ctx *ctx, const uint64_t *a1, const uint64_t *b
  * digits [2][2][m] uint64 in the stored form of sgfhe_debug_digits (e_i = u_i + s).  Host pointers. */
 int32_t sgfhe_debug_flatten(sgfhe_ctx *ctx, const uint64_t *values, uint64_t *digits);
 
+/*
+ * Parity / debug hook: one k-loop step (external product, then CRT + flatten) from caller-chosen stored digits,
+ * through the function every bootstrap call runs per iteration, so the kernels are the ones a real call of `gates`
+ * bootstraps takes in the ctx's present flatten mode and knob settings (throughput, small, quarter or fused quarter
+ * form).
+ *   digits     : [gates][2][2][m] uint64, the stored form of sgfhe_debug_digits (in the randomised mode with the draws)
+ *   C          : [4][2][m][2] canonical residues, one key slice, as in sgfhe_debug_cmux
+ *   j          : [gates] rotation amounts in [0, 2 m): u.a[k] of every gate
+ *   k          : iteration index in [0, n); the randomised flatten draws with tag k + 1, gate b as bootstrap b of one
+ *                call of the ctx's draw stream (the call takes one call number, as a bootstrap call does)
+ *   digits_out : [gates][2][2][m] uint64, the stored digits of acc + (x^j - 1) sum_row u_row (*) C[row] after the step
+ *   ext_name, crt_name : the kernels the step launched, as a kernel trace names them ("a+b" for a pair of launches)
+ * Needs no key.  Host pointers; synchronous.  SGFHE_ERR_INVALID_ARG, before anything is queued or a call number taken:
+ * a null pointer, gates = 0 or more than one chunk of the ctx, k >= n, a j >= 2 m, a key residue >= Q, or a digit pair
+ * that no flatten of the present mode stores: e_lo <= B - 1 + 2 xmax rnd and e_hi <= floor((Q - 1) / B) + 2 xmax rnd
+ * (xmax = 3 (B / 2), rnd = 1 in the randomised mode, else 0), and in the deterministic mode e_lo + e_hi B < Q.
+ */
+int32_t sgfhe_debug_kloop_step(sgfhe_ctx *ctx, const uint64_t *digits, const uint64_t *C, const uint32_t *j,
+                               size_t gates, uint32_t k, uint64_t *digits_out, char *ext_name, size_t ext_cap,
+                               char *crt_name, size_t crt_cap);
+
 /* Parity / debug hook: negacyclic NTT of one polynomial modulo RNS prime `prime_index`.
  * in/out: [m] uint32 residues; forward maps natural order to the engine's slot order,
  * inverse maps back (and divides by m).  Host pointers. */

@@ -421,6 +421,39 @@ size_t lds_bytes(int logm, int npoly) { return (size_t)npoly * ((size_t)4 << log
 // points per thread of k_extprod: 16, or 8 where 16 would leave half a wavefront idle (m <= 512)
 template <int LOGM> constexpr int ext_loge() { return LOGM <= EXT_LE3_MAX ? 3 : LOGE; }
 template <int LOGM> constexpr int threads_of() { return NttGeom<LOGM, LOGE>::T; }
+// points per thread of k_fwd_phase / k_inv_column: 8 while m / 8 threads fit a workgroup, else the engine's 16
+constexpr int small_loge(int logm) { return (logm - 3 <= 10 && logm >= 9) ? 3 : LOGE; }
+constexpr int QUARTER_LOGE = 3;   // ... of the quarter kernels
+
+// The kernels of a form as a rocprofv3 kernel trace names them (sgfhe_kernel_names, sgfhe_debug_kloop_step): the
+// only place that turns an ExtForm / CrtForm into text.
+void ext_form_name(const sgfhe_ctx *c, ExtForm f, uint32_t mode, char *out, size_t cap) {
+    const char *wide = (mode & MODE_WIDE) ? "true" : "false";
+    const int lm = c->logm, ls = small_loge(lm);
+    switch (f.kind) {
+    case ExtKind::Throughput: snprintf(out, cap, "k_extprod<%d, %d, %s>", lm, lm <= EXT_LE3_MAX ? 3 : LOGE, wide); break;
+    case ExtKind::Small: snprintf(out, cap, "k_fwd_phase<%d, %d, %s>+k_inv_column<%d, %d>", lm, ls, wide, lm, ls); break;
+    case ExtKind::Quarter:
+        snprintf(out, cap, "k_fwd_quarter<%d, %d>+k_inv_quarter<%d, %d>", lm, QUARTER_LOGE, lm, QUARTER_LOGE);
+        break;
+    case ExtKind::Fused: snprintf(out, cap, "k_ext_quarter<%d, %d>", lm, QUARTER_LOGE); break;
+    }
+}
+void crt_form_name(CrtForm f, char *out, size_t cap) {
+    switch (f.kind) {
+    case CrtKind::Lean:
+        if (f.quarter) snprintf(out, cap, "k_crt_lean1q<%u, %u>", f.np, f.nl);
+        else if (f.one) snprintf(out, cap, "k_crt_lean1<%u, %u>", f.np, f.nl);
+        else snprintf(out, cap, f.p87 ? "k_crt_lean<%u, %u, true>" : "k_crt_lean<%u, %u>", f.np, f.nl);
+        break;
+    case CrtKind::LeanRnd:
+        if (f.quarter || f.one) snprintf(out, cap, "k_crt_lean_rnd1<%u, %u, %s>", f.np, f.nl, f.quarter ? "true" : "false");
+        else snprintf(out, cap, "k_crt_lean_rnd<%u, %u, %s>", f.np, f.nl, f.wide ? "true" : "false");
+        break;
+    case CrtKind::Acc2: snprintf(out, cap, "k_crt_acc2<%u>", f.np); break;
+    case CrtKind::Acc: snprintf(out, cap, "k_crt_acc<%u>", f.np); break;
+    }
+}
 
 // ---- one dispatcher per template axis -------------------------------------------------------------
 // Each hands the run-time value to a generic lambda as a compile-time constant.  What a lambda
@@ -484,8 +517,7 @@ int32_t launch_small(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *keyk
                      uint32_t k, uint32_t mode, hipStream_t st) {
     return with_logm(c, [&](auto lm) -> int32_t {
         constexpr int LOGM = decltype(lm)::value;
-        // 8 points per thread while m / 8 threads fit a workgroup, else the engine's 16
-        constexpr int LE = (LOGM - 3 <= 10 && LOGM >= 9) ? 3 : LOGE;
+        constexpr int LE = small_loge(LOGM);
         constexpr int TH = NttGeom<LOGM, LE>::T;
         const size_t lds = lds_bytes(LOGM, 1);
         if (!(c->attr_done & ATTR_SMALL)) {
@@ -520,7 +552,7 @@ int32_t launch_quarter(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, const int32_t *ke
     return with_logm(c, [&](auto lm) -> int32_t {
         constexpr int LOGM = decltype(lm)::value;
         if constexpr (LOGM >= 12) {
-            constexpr int LE = 3;
+            constexpr int LE = QUARTER_LOGE;
             constexpr int TH = NttGeom<LOGM - 2, LE>::T;
             const sgfhe_ctx::Basis &S = cur(c);
             if constexpr (LOGM <= 13) if (fused) {
@@ -618,9 +650,10 @@ int32_t launch_dbgntt(sgfhe_ctx *c, const uint32_t *in, uint32_t *out, uint32_t 
 
 // The CRT of `total` coefficients in the form crt_form chooses (`quarter`: after a quarter-form external product).
 int32_t launch_crt_raw(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32_t total, uint32_t mode,
-                       hipStream_t st, RndArgs ra, uint32_t iter, bool quarter = false) {
+                       hipStream_t st, RndArgs ra, uint32_t iter, bool quarter = false, CrtForm *used = nullptr) {
     const sgfhe_ctx::Basis &S = cur(c);
     const CrtForm f = crt_form(c, mode, total, ra.rows != nullptr, quarter);
+    if (used) *used = f;
     const uint32_t logm = (uint32_t)c->logm, work = total / f.per_thread();
     const dim3 grid((work + 255) / 256), block(256);
     const int32_t rc = with_npr(c, f.np, [&](auto np) -> int32_t {
@@ -677,8 +710,8 @@ int32_t launch_crt_raw(sgfhe_ctx *c, const uint32_t *yres, uint64_t *dig, uint32
     return SGFHE_OK;
 }
 int32_t launch_crt(sgfhe_ctx *c, const sgfhe_ctx::Lane &L, uint32_t cnt, uint32_t mode, hipStream_t st,
-                   RndArgs ra = RndArgs{}, uint32_t iter = 0, bool quarter = false) {
-    return launch_crt_raw(c, L.yres, L.dig, cnt * 2 * c->M, mode, st, ra, iter, quarter);
+                   RndArgs ra = RndArgs{}, uint32_t iter = 0, bool quarter = false, CrtForm *used = nullptr) {
+    return launch_crt_raw(c, L.yres, L.dig, cnt * 2 * c->M, mode, st, ra, iter, quarter, used);
 }
 
 // ---- buffers ------------------------------------------------------------------------------------
@@ -756,7 +789,28 @@ struct ChunkJob {
     bool sampled;       // HIP-event timing samples are taken on this chunk
 };
 
-// Iteration k of every job: k_extprod (or its small-batch form) then k_crt_acc, each job on its
+// The forms one step took.
+struct StepForms {
+    ExtForm ext;
+    CrtForm crt;
+};
+// Iteration k of one job on its stream: the external product with key slice `keyk` in the form ext_form chooses for
+// the chunk, then the CRT that form hands its residues to.  `mid`: an event to record between the two (a timing
+// sample), `used`: the forms the step took (sgfhe_debug_kloop_step reports them).
+int32_t kloop_step(sgfhe_ctx *c, const ChunkJob &J, const int32_t *keyk, uint32_t k, uint32_t mode,
+                   hipEvent_t mid = nullptr, StepForms *used = nullptr) {
+    const ExtForm form = ext_form(c, mode, J.cb, J.cpad, J.L->zpart != nullptr);
+    // (Round 4 also tried warming the next iteration's key slice from a second stream, one iteration
+    // ahead, with k_fwd_phase's own workgroup -> XCD mapping: 18.06 / 19.01 / 20.85 ms against 17.94 /
+    // 18.80 / 20.24 for 1 / 2 / 4 gates, no gain, profiles/r04_exp_prefetch.txt.)
+    int32_t rc = launch_ext(c, *J.L, keyk, form, k, mode, J.st);
+    if (rc) return rc;
+    if (mid) HIPCHK(c, hipEventRecord(mid, J.st));
+    if (used) used->ext = form;
+    return launch_crt(c, *J.L, form.cnt, mode, J.st, J.ra, k + 1, form.quarter(), used ? &used->crt : nullptr);
+}
+
+// Iteration k of every job: kloop_step, each job on its
 // own stream.  (Measured and rejected in round 2: chaining the two streams so that one chunk's
 // CRT kernel runs beside the other chunk's external product -- also with the CRT as a
 // one-workgroup-per-CU grid-stride "rider" kernel -- costs the external product as much time
@@ -767,7 +821,6 @@ int32_t run_iterations(sgfhe_ctx *c, ChunkJob *jobs, int njobs, uint64_t n_iters
     for (uint64_t k = 0; k < n_iters; k++) {
         for (int j = 0; j < njobs; j++) {
             const ChunkJob &J = jobs[j];
-            const ExtForm form = ext_form(c, mode, J.cb, J.cpad, J.L->zpart != nullptr);
             const bool sample = c->timing && J.sampled && (k % 64 == 1) && c->ev.size() < 2048;
             hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
             if (sample) {
@@ -776,13 +829,7 @@ int32_t run_iterations(sgfhe_ctx *c, ChunkJob *jobs, int njobs, uint64_t n_iters
                 HIPCHK(c, hipEventCreate(&e2));
                 HIPCHK(c, hipEventRecord(e0, J.st));
             }
-            // (Round 4 also tried warming the next iteration's key slice from a second stream, one iteration
-            // ahead, with k_fwd_phase's own workgroup -> XCD mapping: 18.06 / 19.01 / 20.85 ms against 17.94 /
-            // 18.80 / 20.24 for 1 / 2 / 4 gates, no gain, profiles/r04_exp_prefetch.txt.)
-            int32_t rc = launch_ext(c, *J.L, key + k * slice, form, (uint32_t)k, mode, J.st);
-            if (rc) return rc;
-            if (sample) HIPCHK(c, hipEventRecord(e1, J.st));
-            rc = launch_crt(c, *J.L, form.cnt, mode, J.st, J.ra, (uint32_t)k + 1, form.quarter());
+            const int32_t rc = kloop_step(c, J, key + k * slice, (uint32_t)k, mode, e1);
             if (rc) return rc;
             if (sample) {
                 HIPCHK(c, hipEventRecord(e2, J.st));
@@ -2208,6 +2255,78 @@ int32_t sgfhe_debug_cmux(sgfhe_ctx *c, const uint64_t *a, const uint64_t *b, con
     });
 }
 
+// What a flatten of the ctx's present mode can store as the digit pair (e_lo, e_hi) of one coefficient: x mod B and
+// x div B of an x < Q, each plus a draw in [0, 2 xmax] in the randomised mode.
+static bool storable_digits(const sgfhe_ctx *c, uint64_t e_lo, uint64_t e_hi) {
+    const u128 draw = c->rnd ? 2 * (3 * (c->B / 2)) : 0;
+    if (e_lo > c->B - 1 + draw || e_hi > (c->Q - 1) / c->B + draw) return false;
+    return c->rnd || e_lo + e_hi * c->B < c->Q;
+}
+
+int32_t sgfhe_debug_kloop_step(sgfhe_ctx *c, const uint64_t *digits, const uint64_t *C, const uint32_t *j, size_t gates,
+                               uint32_t k, uint64_t *digits_out, char *ext_name, size_t ext_cap, char *crt_name,
+                               size_t crt_cap) {
+    if (!c || !digits || !C || !j || !digits_out || !ext_name || !crt_name || !ext_cap || !crt_cap)
+        return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    const uint32_t mode = flatten_mode(c), M = c->M, n = c->n;
+    if (gates == 0 || gates > base_chunk(chunk_policy(c, mode)))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_kloop_step: between 1 gate and one chunk of the ctx");
+    if (k >= n) return fail(c, SGFHE_ERR_INVALID_ARG, "debug_kloop_step: k must be in [0, n)");
+    for (size_t b = 0; b < gates; b++)
+        if (j[b] >= 2 * M) return fail(c, SGFHE_ERR_INVALID_ARG, "debug_kloop_step: j must be in [0, 2 m)");
+    for (size_t bc = 0; bc < gates * 2; bc++)
+        for (uint32_t i = 0; i < M; i++)
+            if (!storable_digits(c, digits[bc * 2 * M + i], digits[(bc * 2 + 1) * M + i]))
+                return fail(c, SGFHE_ERR_INVALID_ARG, "debug_kloop_step: a digit pair no flatten of this mode stores");
+    for (uint32_t i = 0; i < 8 * M; i++)
+        if (ld128(C + 2 * (size_t)i) >= c->Q)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "debug_kloop_step: a key residue is not in [0, Q)");
+    const uint32_t cb = (uint32_t)gates, cpad = round_up8(cb), t2 = cb * 2 * M;
+    Scratch<int32_t> d_slice;
+    Scratch<uint64_t> d_io;
+    StepForms used;
+    std::vector<uint32_t> ua((size_t)cb * n, 0u);   // ua[b * n + k] = j[b]
+    for (uint32_t b = 0; b < cb; b++) ua[(size_t)b * n + k] = j[b];
+    int32_t rc = run_drained(c, [&]() -> int32_t {
+        int32_t rc = ensure_work(c, cpad);
+        if (rc) return rc;
+        const sgfhe_ctx::Lane &L = c->lane[0];
+        if ((rc = scratch_alloc(c, d_slice, (size_t)cur(c).npr * 8 * M))) return rc;
+        if ((rc = scratch_alloc(c, d_io, (size_t)cb * 4 * M))) return rc;
+        if ((rc = key_transform_host(c, C, 8, d_slice.p))) return rc;
+        // one chunk as chunk_entry leaves it: the gates' digit records (the padding rows zero), u.a[k] of every gate
+        HIPCHK(c, hipMemsetAsync(L.dig, 0, (size_t)cpad * 2 * M * 16, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_io.p, digits, (size_t)cb * 4 * M * 8, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_load_digits, dim3((t2 + 255) / 256), dim3(256), 0, c->stream, d_io.p, L.dig, t2,
+                           (uint32_t)c->logm, mode);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemsetAsync(L.ua, 0, (size_t)cpad * n * 4, c->stream));
+        HIPCHK(c, hipMemcpyAsync(L.ua, ua.data(), ua.size() * 4, hipMemcpyHostToDevice, c->stream));
+        const uint32_t callno = next_call_number(c);   // gate b draws as bootstrap b of this call
+        c->last_call = callno;
+        ChunkJob J;
+        J.L = &L;
+        J.st = c->stream;
+        J.cb = cb;
+        J.cpad = cpad;
+        J.c0 = 0;
+        J.ra = RndArgs{c->rnd_key, callno, 0u, c->gather_rows};
+        J.sampled = false;
+        if ((rc = kloop_step(c, J, d_slice.p, k, mode, nullptr, &used))) return rc;
+        hipLaunchKernelGGL(k_dump_digits, dim3((t2 + 255) / 256), dim3(256), 0, c->stream, L.dig, d_io.p, t2,
+                           (uint32_t)c->logm, mode);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(digits_out, d_io.p, (size_t)cb * 4 * M * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SGFHE_OK;
+    });
+    if (rc) return rc;
+    ext_form_name(c, used.ext, mode, ext_name, ext_cap);
+    crt_form_name(used.crt, crt_name, crt_cap);
+    return SGFHE_OK;
+}
+
 // The pack work buffers of the ctx for calls of at most `count` ciphertexts and `total` ciphertexts of
 // (w | v), in the ctx's present flatten mode; before anything is queued (nothing of the ctx in flight).
 // `boots` of the call's ciphertexts are bootstrapped first (all of them in pack_encrypted_bits; the refreshed ones
@@ -2668,17 +2787,12 @@ int32_t sgfhe_kernel_names(const sgfhe_ctx *c, char *extprod, size_t extprod_cap
     SGFHE_LOCK(c);
     // the throughput form at the ctx's present mode: what ext_form / crt_form give a large chunk
     const uint32_t mode = flatten_mode(c);
-    const char *wide = (mode & MODE_WIDE) ? "true" : "false";
-    snprintf(extprod, extprod_cap, "k_extprod<%d, %d, %s>", c->logm, c->logm <= EXT_LE3_MAX ? 3 : LOGE, wide);
-    const CrtForm f = crt_form(c, mode, ~0u, false);
-    // (k_crt_lean<5, 3, true>, the crt_lean87_one instantiation, reports as k_crt_lean<5, 3>: same
-    // function, same memory side)
-    switch (f.kind) {
-    case CrtKind::Lean: snprintf(crt, crt_cap, "k_crt_lean<%u, %u>", f.np, f.nl); break;
-    case CrtKind::LeanRnd: snprintf(crt, crt_cap, "k_crt_lean_rnd<%u, %u, %s>", f.np, f.nl, wide); break;
-    case CrtKind::Acc2: snprintf(crt, crt_cap, "k_crt_acc2<%u>", f.np); break;
-    case CrtKind::Acc: snprintf(crt, crt_cap, "k_crt_acc<%u>", f.np); break;
-    }
+    ext_form_name(c, ExtForm{ExtKind::Throughput, ~0u}, mode, extprod, extprod_cap);
+    CrtForm f = crt_form(c, mode, ~0u, false);
+    // (k_crt_lean<5, 3, true>, the crt_lean87_one instantiation, reports as k_crt_lean<5, 3> here: same
+    // function, same memory side; sgfhe_debug_kloop_step tells the two apart)
+    f.p87 = false;
+    crt_form_name(f, crt, crt_cap);
     return SGFHE_OK;
 }
 

@@ -2306,6 +2306,18 @@ k_dump_digits(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, uint
     out[((size_t)bc * 2 + 1) * M + i] = d.y;
 }
 
+// [bootstrap][c][digit][m] uint64 -> stored digit planes, the inverse of k_dump_digits (debug hook:
+// sgfhe_debug_kloop_step, which has checked that every value is one a flatten stores)
+__global__ void __launch_bounds__(256)
+k_load_digits(const uint64_t *__restrict__ in, uint64_t *__restrict__ dig, uint32_t total,
+              uint32_t logm, uint32_t mode) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const uint32_t M = 1u << logm, bc = t >> logm, i = t & (M - 1);
+    store_digits(dig, bc, i, M, in[((size_t)bc * 2 + 0) * M + i], in[((size_t)bc * 2 + 1) * M + i],
+                 (mode & MODE_WIDE) != 0);
+}
+
 // canonical residues -> digits of x' = (v + off) mod Q  (flatten, utils.jl:155-189)
 __global__ void __launch_bounds__(256)
 k_flatten_canon(const ulonglong2 *__restrict__ in, uint64_t *__restrict__ dig,

@@ -592,6 +592,22 @@ class Engine:
         self._call("sgfhe_debug_flatten", ptr, dig.ctypes.data_as(ctypes.c_void_p))
         return dig
 
+    def debug_kloop_step(self, digits, C, j, k=0):
+        """One k-loop step from chosen stored digits, in the form a call of that many gates takes
+        (sgfhe_debug_kloop_step): digits [gates][2][2][m] uint64, C [4][2][m][2], j [gates] ->
+        (digits after the step, (external-product kernels, CRT kernel))."""
+        m = self.params.m
+        digits, pd = _c(digits)
+        C, pC = _c(C)
+        j, pj = _c(j, np.uint32)
+        gates = j.size
+        if digits.size != gates * 4 * m or C.size != 16 * m:
+            raise ValueError("debug_kloop_step: digits is [gates][2][2][m], C is [4][2][m][2], j is [gates]")
+        out = np.zeros((gates, 2, 2, m), dtype=np.uint64)
+        a, b = ctypes.create_string_buffer(96), ctypes.create_string_buffer(96)
+        self._call("sgfhe_debug_kloop_step", pd, pC, pj, gates, int(k), out.ctypes.data_as(ctypes.c_void_p), a, 96, b, 96)
+        return out, (a.value.decode(), b.value.decode())
+
     def debug_ntt(self, prime_index, poly, inverse=False):
         x, px = _c(poly, np.uint32)
         out = np.zeros(self.params.m, dtype=np.uint32)

@@ -836,6 +836,17 @@ def rnd128(key, ctr):
     return blk[4 * (x & 3):4 * (x & 3) + 4]
 
 
+def digit_planes(e, wide=False):
+    """store_digits / load_digits of kernels.h for one stored digit: bits 0..31 in the lo plane, 32..47 in the hi plane,
+    48..55 in the top plane of a MODE_WIDE record.  Returns what load_digits reads back; a digit the planes cannot hold
+    would come back short, which is asserted here."""
+    e = int(e)
+    lo, hi, top = e & MASK32, (e >> 32) & 0xFFFF, (e >> 48) & 0xFF
+    back = lo | (hi << 32) | ((top << 48) if wide else 0)
+    assert back == e, "stored digit %d does not fit the %s planes" % (e, "three" if wide else "two")
+    return back
+
+
 class EngineModel:
     def __init__(self, n, m, Q, B, DQ_tilde, random_flatten=False):
         self.C = Consts(n, m, Q, B, DQ_tilde, random_flatten)

@@ -366,6 +366,52 @@ int32_t sgfhe_debug_kloop_step(sgfhe_ctx *ctx, const uint64_t *digits, const uin
                                size_t gates, uint32_t k, uint64_t *digits_out, char *ext_name, size_t ext_cap,
                                char *crt_name, size_t crt_cap);
 
+/*
+ * Parity / debug hook: the entry of one chunk (k_init) from caller-chosen rows, through the function every bootstrap
+ * call runs before its k-loop: the first digits and the rotation amounts the k-loop starts from, in the ctx's present
+ * flatten mode.
+ *   a1, a2 : [rows][n], b1, b2 : [rows] uint64 over Z_r, as in sgfhe_bootstrap_batch (u = lwe1 + lwe2 mod r)
+ *   lut    : NULL, or [rows] uint32 descriptor words as a level call of a circuit carries them: 0 for a row of the
+ *            classic path, 0x100 | truth table for a LUT row, which starts at amplitude DQ_tilde >> 2
+ *   digits : [rows][2][2][m] uint64, the stored form of sgfhe_debug_digits: a = 0 and b = x^(-u.b) t DQ_tilde flattened
+ *            -- what sgfhe_debug_digits returns at n_iters = 0 for the same rows and call number
+ *   ua     : [rows][n] uint32, u.a of every row in [0, r)
+ * The chunk is padded to a multiple of 8 rows as in a call; the padding rows are not returned.  In the randomised
+ * mode row b draws (tag 0) as bootstrap b of one call of the ctx's draw stream, and the entry takes one call number,
+ * as a bootstrap call does.  Needs no key.  Host pointers; synchronous.  SGFHE_ERR_INVALID_ARG, before anything is
+ * queued or a call number taken: a null pointer (lut excepted), rows = 0 or more than one chunk of the ctx, a
+ * descriptor word that is neither 0 nor 0x100 | table, or a word of a LUT row that is not below r (as the LUT
+ * entries refuse it; the rows of the classic path are taken mod r, as sgfhe_bootstrap_batch takes them).
+ */
+int32_t sgfhe_debug_chunk_entry(sgfhe_ctx *ctx, const uint64_t *a1, const uint64_t *b1, const uint64_t *a2,
+                                const uint64_t *b2, size_t rows, const uint32_t *lut, uint64_t *digits, uint32_t *ua);
+
+/*
+ * Parity / debug hook: the exit of one chunk (k_final, k_final_lut, k_final_lut_multi, the RNS2 conversion) from
+ * caller-chosen stored digits, through the function every bootstrap call runs behind its k-loop: the result rows as
+ * a real call of that kind leaves them, in the ctx's present flatten mode.
+ *   digits   : [rows][2][2][m] uint64, the stored form of sgfhe_debug_digits (in the randomised mode with the draws)
+ *   lut      : NULL, or [rows] uint32 descriptor words (0: a row of the classic path, 0x100 | truth table: a LUT row,
+ *              as in sgfhe_debug_chunk_entry).  Classic rows leave as those of sgfhe_bootstrap_batch, LUT rows as those
+ *              of sgfhe_bootstrap_lut_batch, over what the classic extraction wrote for them; with every row a LUT
+ *              row the classic extraction is skipped, as in sgfhe_bootstrap_lut_batch.
+ *   tables   : NULL, or [rows][n_tables] truth tables, n_tables in 1..SGFHE_LUT_MAX_TABLES: a LUT family, every row a
+ *              LUT row, the rows of sgfhe_bootstrap_lut_multi_batch.  Not together with `lut`; n_tables is read only
+ *              with `tables`.
+ *   flags    : 0, SGFHE_FLAG_RAW_MODQ, or (no LUT rows, RNS2 moduli set) SGFHE_FLAG_RAW_MODQ | SGFHE_FLAG_RAW_RNS2
+ *   out      : [rows][3][n + 1] uint64 (with `tables`: [rows][n_tables][3][n + 1]); x2 words with SGFHE_FLAG_RAW_MODQ
+ *   acc      : NULL, or [rows][2][m][2]: the accumulators the digits store, canonical residues, as
+ *              sgfhe_debug_accumulators returns them
+ * Needs no key and draws nothing: the call takes no call number of the draw stream.  Host pointers; synchronous.
+ * SGFHE_ERR_INVALID_ARG, before anything is queued: a null ctx, digits or out; rows = 0 or more than one chunk of the
+ * ctx; a digit pair that no flatten of the present mode stores (the rule of sgfhe_debug_kloop_step); `lut` and `tables`
+ * together; n_tables outside 1..SGFHE_LUT_MAX_TABLES; a descriptor word that is neither 0 nor 0x100 | table; an
+ * unknown flag; SGFHE_FLAG_RAW_RNS2 without SGFHE_FLAG_RAW_MODQ, on a ctx without RNS2 moduli, or with `lut` or `tables`.
+ * The wire-table form of a circuit's LUT families (sgfhe_circuit_create_lut_multi) is not reached from here.
+ */
+int32_t sgfhe_debug_chunk_exit(sgfhe_ctx *ctx, const uint64_t *digits, size_t rows, const uint32_t *lut,
+                               const uint8_t *tables, size_t n_tables, uint32_t flags, uint64_t *out, uint64_t *acc);
+
 /* Parity / debug hook: negacyclic NTT of one polynomial modulo RNS prime `prime_index`.
  * in/out: [m] uint32 residues; forward maps natural order to the engine's slot order,
  * inverse maps back (and divides by m).  Host pointers. */

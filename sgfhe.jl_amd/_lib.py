@@ -123,6 +123,8 @@ def lib():
         "sgfhe_debug_digits": (i32, [vp, vp, vp, vp, vp, sz, u64, vp]),
         "sgfhe_debug_flatten": (i32, [vp, vp, vp]),
         "sgfhe_debug_kloop_step": (i32, [vp, vp, vp, vp, sz, u32, vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz]),
+        "sgfhe_debug_chunk_entry": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "sgfhe_debug_chunk_exit": (i32, [vp, vp, sz, vp, vp, sz, u32, vp, vp]),
         "sgfhe_debug_ntt": (i32, [vp, u32, ctypes.c_int, vp, vp]),
         "sgfhe_debug_primes": (i32, [vp, _u32p, _u32p]),
         "sgfhe_host_deterministic_expand": (i32, [ctypes.POINTER(SgfheParams), vp, vp]),
@@ -185,7 +187,7 @@ EXPORTED_SYMBOLS = (
     "sgfhe_set_chunk", "sgfhe_set_lanes", "sgfhe_set_small_batch_max", "sgfhe_set_random_flatten", "sgfhe_set_random_flatten_key", "sgfhe_bkey_upload", "sgfhe_bkey_upload_rns2", "sgfhe_rns2_convert", "sgfhe_bkey_generate",
     "sgfhe_bkey_device_form_bytes", "sgfhe_bkey_export_device_form",
     "sgfhe_bkey_import_device_form", "sgfhe_bootstrap_batch", "sgfhe_bootstrap_batch_device",
-    "sgfhe_sync", "sgfhe_external_product", "sgfhe_pack_encrypted_bits", "sgfhe_debug_cmux", "sgfhe_debug_accumulators", "sgfhe_debug_digits", "sgfhe_debug_flatten", "sgfhe_debug_kloop_step", "sgfhe_debug_ntt",
+    "sgfhe_sync", "sgfhe_external_product", "sgfhe_pack_encrypted_bits", "sgfhe_debug_cmux", "sgfhe_debug_accumulators", "sgfhe_debug_digits", "sgfhe_debug_flatten", "sgfhe_debug_kloop_step", "sgfhe_debug_chunk_entry", "sgfhe_debug_chunk_exit", "sgfhe_debug_ntt",
     "sgfhe_debug_primes", "sgfhe_host_deterministic_expand", "sgfhe_host_encrypt_private",
     "sgfhe_host_pack_private", "sgfhe_host_normalize_private", "sgfhe_host_split_ciphertext",
     "sgfhe_host_decrypt_lwe", "sgfhe_host_decrypt_rlwe", "sgfhe_host_public_key",

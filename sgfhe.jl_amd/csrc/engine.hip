@@ -2263,6 +2263,28 @@ static bool storable_digits(const sgfhe_ctx *c, uint64_t e_lo, uint64_t e_hi) {
     return c->rnd || e_lo + e_hi * c->B < c->Q;
 }
 
+// The chunk the chosen-operand hooks work on (sgfhe_debug_kloop_step, sgfhe_debug_chunk_entry, sgfhe_debug_chunk_exit):
+// `cb` rows from row 0 of a call numbered `callno`, on lane 0 and the ctx stream, as bootstrap_device makes the first
+// chunk of a call that fits one chunk.
+static ChunkJob debug_chunk_job(sgfhe_ctx *c, uint32_t cb, uint32_t callno) {
+    ChunkJob J;
+    J.L = &c->lane[0];
+    J.st = c->stream;
+    J.cb = cb;
+    J.cpad = round_up8(cb);
+    J.c0 = 0;
+    J.ra = RndArgs{c->rnd_key, callno, 0u, c->gather_rows};
+    J.sampled = false;
+    return J;
+}
+
+// a per-row LUT descriptor of the hooks: every word 0 (a row of the classic path) or LUT_ROW | truth table
+static bool lut_words_ok(const uint32_t *lut, size_t rows) {
+    for (size_t b = 0; b < rows; b++)
+        if (lut[b] != 0 && (lut[b] & ~0xFFu) != LUT_ROW) return false;
+    return true;
+}
+
 int32_t sgfhe_debug_kloop_step(sgfhe_ctx *c, const uint64_t *digits, const uint64_t *C, const uint32_t *j, size_t gates,
                                uint32_t k, uint64_t *digits_out, char *ext_name, size_t ext_cap, char *crt_name,
                                size_t crt_cap) {
@@ -2305,14 +2327,7 @@ int32_t sgfhe_debug_kloop_step(sgfhe_ctx *c, const uint64_t *digits, const uint6
         HIPCHK(c, hipMemcpyAsync(L.ua, ua.data(), ua.size() * 4, hipMemcpyHostToDevice, c->stream));
         const uint32_t callno = next_call_number(c);   // gate b draws as bootstrap b of this call
         c->last_call = callno;
-        ChunkJob J;
-        J.L = &L;
-        J.st = c->stream;
-        J.cb = cb;
-        J.cpad = cpad;
-        J.c0 = 0;
-        J.ra = RndArgs{c->rnd_key, callno, 0u, c->gather_rows};
-        J.sampled = false;
+        const ChunkJob J = debug_chunk_job(c, cb, callno);
         if ((rc = kloop_step(c, J, d_slice.p, k, mode, nullptr, &used))) return rc;
         hipLaunchKernelGGL(k_dump_digits, dim3((t2 + 255) / 256), dim3(256), 0, c->stream, L.dig, d_io.p, t2,
                            (uint32_t)c->logm, mode);
@@ -2325,6 +2340,121 @@ int32_t sgfhe_debug_kloop_step(sgfhe_ctx *c, const uint64_t *digits, const uint6
     ext_form_name(c, used.ext, mode, ext_name, ext_cap);
     crt_form_name(used.crt, crt_name, crt_cap);
     return SGFHE_OK;
+}
+
+int32_t sgfhe_debug_chunk_entry(sgfhe_ctx *c, const uint64_t *a1, const uint64_t *b1, const uint64_t *a2,
+                                const uint64_t *b2, size_t rows, const uint32_t *lut, uint64_t *digits, uint32_t *ua) {
+    if (!c || !a1 || !b1 || !a2 || !b2 || !digits || !ua) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    const uint32_t mode = flatten_mode(c), M = c->M, n = c->n;
+    if (rows == 0 || rows > base_chunk(chunk_policy(c, mode)))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_entry: between 1 row and one chunk of the ctx");
+    if (lut) {
+        if (!lut_words_ok(lut, rows))
+            return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_entry: a descriptor word is 0 or LUT_ROW | table");
+        for (size_t b = 0; b < rows; b++) {   // a LUT row: words below r, as the LUT entries ask
+            if (!(lut[b] & LUT_ROW)) continue;
+            bool ok = b1[b] < c->par.r && b2[b] < c->par.r;
+            for (size_t i = b * n; ok && i < (b + 1) * n; i++) ok = a1[i] < c->par.r && a2[i] < c->par.r;
+            if (!ok) return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_entry: a word of LUT row " + std::to_string(b) + " is not below r");
+        }
+    }
+    const uint32_t cb = (uint32_t)rows, cpad = round_up8(cb), t2 = cb * 2 * M;
+    Scratch<uint64_t> d_in, d_dig;
+    Scratch<uint32_t> d_lut;
+    return run_drained(c, [&]() -> int32_t {
+        int32_t rc = ensure_work(c, cpad);
+        if (rc) return rc;
+        if ((rc = scratch_alloc(c, d_in, (size_t)2 * cb * (n + 1)))) return rc;
+        if ((rc = scratch_alloc(c, d_dig, (size_t)cb * 4 * M))) return rc;
+        if (lut && (rc = scratch_alloc(c, d_lut, cb))) return rc;
+        const Staging S = staging(d_in.p, cb, n);
+        HIPCHK(c, hipMemcpyAsync(S.a1, a1, (size_t)cb * n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.a2, a2, (size_t)cb * n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.b1, b1, (size_t)cb * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(S.b2, b2, (size_t)cb * 8, hipMemcpyHostToDevice, c->stream));
+        if (lut) HIPCHK(c, hipMemcpyAsync(d_lut.p, lut, (size_t)cb * 4, hipMemcpyHostToDevice, c->stream));
+        const uint32_t callno = next_call_number(c);   // row b draws as bootstrap b of this call
+        c->last_call = callno;
+        const ChunkJob J = debug_chunk_job(c, cb, callno);
+        const LutDesc desc = {d_lut.p, false};
+        if ((rc = chunk_entry(c, J, BootRows(S), lut ? &desc : nullptr, mode))) return rc;
+        hipLaunchKernelGGL(k_dump_digits, dim3((t2 + 255) / 256), dim3(256), 0, c->stream, J.L->dig, d_dig.p, t2,
+                           (uint32_t)c->logm, mode);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(digits, d_dig.p, (size_t)cb * 4 * M * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ua, J.L->ua, (size_t)cb * n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SGFHE_OK;
+    });
+}
+
+int32_t sgfhe_debug_chunk_exit(sgfhe_ctx *c, const uint64_t *digits, size_t rows, const uint32_t *lut,
+                               const uint8_t *tables, size_t n_tables, uint32_t flags, uint64_t *out, uint64_t *acc) {
+    if (!c || !digits || !out) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    const uint32_t mode = flatten_mode(c), M = c->M, n = c->n;
+    if (rows == 0 || rows > base_chunk(chunk_policy(c, mode)))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: between 1 row and one chunk of the ctx");
+    if (flags & ~(SGFHE_FLAG_RAW_MODQ | SGFHE_FLAG_RAW_RNS2))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: flags are SGFHE_FLAG_RAW_MODQ and SGFHE_FLAG_RAW_RNS2");
+    if (lut && tables)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: a per-row descriptor or a family, not both");
+    if (tables && (n_tables < 1 || n_tables > SGFHE_LUT_MAX_TABLES))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: n_tables is 1 to SGFHE_LUT_MAX_TABLES");
+    const size_t T = tables ? n_tables : 1;
+    if (rows > ((size_t)1 << 31) / (n + 1) / T)   // (row and table counts are 32-bit on the device)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: too many rows");
+    if (lut && !lut_words_ok(lut, rows))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: a descriptor word is 0 or LUT_ROW | table");
+    if (flags & SGFHE_FLAG_RAW_RNS2) {
+        if (!(flags & SGFHE_FLAG_RAW_MODQ))
+            return fail(c, SGFHE_ERR_INVALID_ARG, "SGFHE_FLAG_RAW_RNS2 needs SGFHE_FLAG_RAW_MODQ");
+        if (!c->have_rns2)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "SGFHE_FLAG_RAW_RNS2: no RNS2 moduli (upload the key with sgfhe_bkey_upload_rns2)");
+        if (lut || tables)
+            return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: no SGFHE_FLAG_RAW_RNS2 with LUT rows");
+    }
+    for (size_t bc = 0; bc < rows * 2; bc++)
+        for (uint32_t i = 0; i < M; i++)
+            if (!storable_digits(c, digits[bc * 2 * M + i], digits[(bc * 2 + 1) * M + i]))
+                return fail(c, SGFHE_ERR_INVALID_ARG, "debug_chunk_exit: a digit pair no flatten of this mode stores");
+    const uint32_t cb = (uint32_t)rows, cpad = round_up8(cb), t2 = cb * 2 * M;
+    const size_t out_words = rows * T * 3 * (n + 1) * ((flags & SGFHE_FLAG_RAW_MODQ) ? 2 : 1);
+    bool all = lut != nullptr;   // every row a LUT row: k_final has nothing to write (sgfhe_bootstrap_lut_batch)
+    for (size_t b = 0; lut && b < rows; b++) all = all && (lut[b] & LUT_ROW);
+    Scratch<uint64_t> d_io, d_out;
+    Scratch<ulonglong2> d_acc;
+    Scratch<uint32_t> d_lut;
+    Scratch<uint8_t> d_tab;
+    return run_drained(c, [&]() -> int32_t {
+        int32_t rc = ensure_work(c, cpad);
+        if (rc) return rc;
+        if ((rc = scratch_alloc(c, d_io, (size_t)cb * 4 * M))) return rc;
+        if ((rc = scratch_alloc(c, d_out, out_words))) return rc;
+        if (acc && (rc = scratch_alloc(c, d_acc, (size_t)cb * 2 * M))) return rc;
+        if (lut && (rc = scratch_alloc(c, d_lut, cb))) return rc;
+        if (tables && (rc = scratch_alloc(c, d_tab, rows * T))) return rc;
+        const ChunkJob J = debug_chunk_job(c, cb, 0u);   // the exit draws nothing
+        // one chunk as the k-loop leaves it: the rows' digit records (the padding rows zero)
+        HIPCHK(c, hipMemsetAsync(J.L->dig, 0, (size_t)cpad * 2 * M * 16, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_io.p, digits, (size_t)cb * 4 * M * 8, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_load_digits, dim3((t2 + 255) / 256), dim3(256), 0, c->stream, d_io.p, J.L->dig, t2,
+                           (uint32_t)c->logm, mode);
+        HIPCHK(c, hipGetLastError());
+        if (lut) HIPCHK(c, hipMemcpyAsync(d_lut.p, lut, (size_t)cb * 4, hipMemcpyHostToDevice, c->stream));
+        if (tables) HIPCHK(c, hipMemcpyAsync(d_tab.p, tables, rows * T, hipMemcpyHostToDevice, c->stream));
+        LutDesc desc = {d_lut.p, tables ? true : all};
+        if (tables) desc.tables = d_tab.p, desc.n_tables = (uint32_t)T;
+        BootCall call(c);
+        call.batch = rows, call.out = d_out.p, call.flags = flags, call.acc_out = d_acc.p;
+        if (lut || tables) call.lut = &desc;
+        if ((rc = chunk_exit(c, J, call, mode))) return rc;
+        HIPCHK(c, hipMemcpyAsync(out, d_out.p, out_words * 8, hipMemcpyDeviceToHost, c->stream));
+        if (acc) HIPCHK(c, hipMemcpyAsync(acc, d_acc.p, (size_t)cb * 2 * M * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SGFHE_OK;
+    });
 }
 
 // The pack work buffers of the ctx for calls of at most `count` ciphertexts and `total` ciphertexts of

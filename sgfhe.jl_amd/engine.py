@@ -608,6 +608,53 @@ class Engine:
         self._call("sgfhe_debug_kloop_step", pd, pC, pj, gates, int(k), out.ctypes.data_as(ctypes.c_void_p), a, 96, b, 96)
         return out, (a.value.decode(), b.value.decode())
 
+    def debug_chunk_entry(self, a1, b1, a2, b2, lut=None):
+        """The entry of one chunk from chosen rows (sgfhe_debug_chunk_entry): a1, a2 [rows][n], b1, b2 [rows] as in
+        bootstrap_batch, lut None or [rows] uint32 descriptor words (0, or 0x100 | table for a LUT row) ->
+        (stored digits [rows][2][2][m] uint64, u.a [rows][n] uint32) as the k-loop of a call finds them."""
+        rows, (p1, q1, p2, q2), _keep = self._lwe_args(a1, b1, a2, b2)
+        pl = None
+        if lut is not None:
+            lut, pl = _c(lut, np.uint32)
+            if lut.size != rows:
+                raise ValueError("debug_chunk_entry: lut is [rows]")
+        dig = np.zeros((rows, 2, 2, self.params.m), dtype=np.uint64)
+        ua = np.zeros((rows, self.params.n), dtype=np.uint32)
+        self._call("sgfhe_debug_chunk_entry", p1, q1, p2, q2, rows, pl, dig.ctypes.data_as(ctypes.c_void_p),
+                   ua.ctypes.data_as(ctypes.c_void_p))
+        return dig, ua
+
+    def debug_chunk_exit(self, digits, lut=None, tables=None, raw=False, rns2=False, want_acc=False):
+        """The exit of one chunk from chosen stored digits (sgfhe_debug_chunk_exit): digits [rows][2][2][m] uint64;
+        lut None or [rows] uint32 descriptor words (0: a classic row, 0x100 | table: a LUT row); tables None or
+        [rows][T] uint8, a LUT family.  Returns the rows of a call of that kind -- [rows][3][n+1] uint64, with tables
+        [rows][T][3][n+1], a last axis of 2 with raw (residues mod Q) or rns2 (RNS2 limb pairs) -- and with want_acc
+        also the accumulators [rows][2][m][2] the digits store."""
+        n, m = self.params.n, self.params.m
+        digits, pd = _c(digits)
+        if digits.size % (4 * m):
+            raise ValueError("debug_chunk_exit: digits is [rows][2][2][m]")
+        rows = digits.size // (4 * m)
+        pl = pt = None
+        T = 0
+        shape = (rows, 3, n + 1)
+        if lut is not None:
+            lut, pl = _c(lut, np.uint32)
+            if lut.size != rows:
+                raise ValueError("debug_chunk_exit: lut is [rows]")
+        if tables is not None:
+            tables, pt = _c(tables, np.uint8)
+            if tables.ndim != 2 or tables.shape[0] != rows:
+                raise ValueError("debug_chunk_exit: tables is [rows][T]")
+            T = tables.shape[1]
+            shape = (rows, T, 3, n + 1)
+        raw = raw or rns2
+        out = np.zeros(shape + (2,) if raw else shape, dtype=np.uint64)
+        acc = np.zeros((rows, 2, m, 2), dtype=np.uint64) if want_acc else None
+        self._call("sgfhe_debug_chunk_exit", pd, rows, pl, pt, T, (FLAG_RAW_MODQ if raw else 0) | (FLAG_RAW_RNS2 if rns2 else 0),
+                   out.ctypes.data_as(ctypes.c_void_p), acc.ctypes.data_as(ctypes.c_void_p) if want_acc else None)
+        return (out, acc) if want_acc else out
+
     def debug_ntt(self, prime_index, poly, inverse=False):
         x, px = _c(poly, np.uint32)
         out = np.zeros(self.params.m, dtype=np.uint32)

@@ -742,6 +742,28 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * Noise rule for registers, MEASURED, NOT PROVED (tests/test_gpu_circuit_steps.py: a serial adder over 64 steps): a
  * register should be fed by a bootstrapped wire -- a gate row, HI / MID of a sum node, a LUT wire -- whose error does
  * not depend on the step.  A LOW / XOR3 wire or a stream input fed back carries its error on and adds to it every step.
+ *
+ * Lane routes (sgfhe_circuit_create_routed): any public lane map inside a group, at no bootstrap.  The creator takes the
+ * arrays of sgfhe_circuit_create_seq and
+ *   n_routes   : route tables, at most SGFHE_CIRCUIT_MAX_ROUTES; a table may be used by several references or by none;
+ *   routes     : [n_routes][group] int32, each entry a source lane in [0, group) or SGFHE_CIRCUIT_ROUTE_FALSE (-1);
+ *   term_route : beside term_shift, NULL = all 0; out_route [n_outputs] and next_route [n_regs] likewise.
+ * A route index 0 means none -- the shift applies as before -- and k >= 1 names table k - 1.  The reference (w, NOT,
+ * route rho) at instance t, lane l = t mod group, is w at instance t - l + rho[l], and the constant FALSE where rho[l]
+ * is SGFHE_CIRCUIT_ROUTE_FALSE; NOT is applied afterwards at the codeword of the position (Dr, Dr/2 or Dr/4 by the scale
+ * rule), so a negated reference fills with TRUE exactly as a shift that leaves the group does.  A reference with a
+ * route has shift 0; a route on a reference to the constant is dropped, as a shift is.  The table of a data LUT node
+ * stays the byte at the node's OWN instance, whatever routes its terms carry.  Numbering, pruning, levels, slots, rows,
+ * calls, call numbers and sgfhe_circuit_info do not see routes (a routed read names a wire of an earlier level,
+ * whichever instance of it is read), and with n_routes = 0 the plan is the sgfhe_circuit_create_seq plan of the same
+ * arrays.  SGFHE_ERR_INVALID_ARG with *out NULL and nothing allocated for: an entry outside [-1, group), a route index
+ * above n_routes, a route beside a non-zero shift, n_routes > 0 with routes NULL, n_routes above the cap, and everything
+ * sgfhe_circuit_create_seq rejects.  sgfhe_circuit_routes gives n_routes (0 for a plan of any other creator).
+ * A routed plan runs through every run entry above that takes its plan otherwise (planes: the _data entries, registers:
+ * the _steps entries).  In the ciphertext form an output with a route is REFRESHED, or LIFTED under
+ * SGFHE_CIRCUIT_PACK_LIFT, as an output with a non-zero shift is -- even where its table is the identity.  The probe
+ * applies the routes in its plaintext bit table; its launches are unchanged.  A route moves whole LWEs and adds no
+ * error: no noise rule is added.
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -807,6 +829,24 @@ int32_t sgfhe_circuit_create_seq(uint32_t n_inputs, uint32_t n_planes,
                                  const int32_t *next_shift /* [n_regs], NULL = all 0 */,
                                  const uint32_t *reg_scale /* [n_regs]: 0, 1, 2; NULL = all 0 */, sgfhe_circuit **out);
 int32_t sgfhe_circuit_registers(const sgfhe_circuit *c, uint32_t *n_regs);   /* 0 for every other creator */
+#define SGFHE_CIRCUIT_MAX_ROUTES 65536u
+#define SGFHE_CIRCUIT_ROUTE_FALSE (-1)   /* entry of a route table: the constant FALSE at that lane */
+int32_t sgfhe_circuit_create_routed(uint32_t n_inputs, uint32_t n_planes,
+                                    const uint32_t *node_kind /* [n_gates]: 0 .. 5 as sgfhe_circuit_create_data */,
+                                    const uint32_t *node_start /* [n_gates + 1], CSR into the term arrays, [0] = 0 */,
+                                    const uint32_t *term_ref, const int32_t *term_shift /* NULL = all 0 */,
+                                    const int32_t *term_weight,
+                                    const uint32_t *node_table /* [n_gates]: a table for kinds 2 and 3, a plane for 4 and 5 */,
+                                    size_t n_gates, const uint32_t *outputs,
+                                    const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
+                                    uint32_t group, uint32_t n_regs, const uint32_t *next_ref /* [n_regs] */,
+                                    const int32_t *next_shift /* [n_regs], NULL = all 0 */,
+                                    const uint32_t *reg_scale /* [n_regs]: 0, 1, 2; NULL = all 0 */,
+                                    uint32_t n_routes, const int32_t *routes /* [n_routes][group] */,
+                                    const uint32_t *term_route /* beside term_shift, NULL = all 0 */,
+                                    const uint32_t *out_route /* [n_outputs], NULL = all 0 */,
+                                    const uint32_t *next_route /* [n_regs], NULL = all 0 */, sgfhe_circuit **out);
+int32_t sgfhe_circuit_routes(const sgfhe_circuit *c, uint32_t *n_routes);   /* 0 for every other creator */
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);

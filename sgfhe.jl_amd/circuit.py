@@ -57,6 +57,13 @@ registers fed back on the device: stream inputs, planes and outputs are per step
 steps.  serial_adder() adds numbers of any width with one bootstrap per bit; crc16_stream(8) is the CRC-16 of a message
 of any length, a byte per step.  Feed a register from a bootstrapped wire (a gate row, HI / MID, a LUT wire): an XOR3 /
 LOW wire or a stream input fed back adds its error every step.
+
+Lane routes (sgfhe_circuit_create_routed).  `w.route(table)` is the reference that reads lane table[t] of `w` at lane t
+of every group -- any public lane map, FALSE where table[t] is ROUTE_FALSE, before `~` -- at no bootstrap, no row and no
+draw: Circuit.rot (rotation inside a word), Circuit.swap (partner t ^ k), Circuit.bcast (one lane to the whole group),
+Circuit.reverse.  Routes compose with each other and with lane shifts and are normalised, so the identity is nothing
+and a pure shift is the shift.  Terms, outputs and next states may be routed; a routed output is refreshed or lifted,
+never direct.  bitonic_sort(width, G) sorts the G numbers of every group with routes alone between its nodes.
 """
 
 import ctypes
@@ -71,26 +78,74 @@ NONE_ID = 0x7FFFFFFE       # SGFHE_CIRCUIT_NONE: the third reference of a two-in
 NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
 MAX_TERMS = 64             # SGFHE_CIRCUIT_MAX_TERMS
 MAX_PLANES = 65536         # SGFHE_CIRCUIT_MAX_PLANES
+MAX_ROUTES = 65536         # SGFHE_CIRCUIT_MAX_ROUTES
+ROUTE_FALSE = -1           # SGFHE_CIRCUIT_ROUTE_FALSE: entry of a route table, the constant FALSE at that lane
 LUT_MAX_TABLES = 256       # SGFHE_LUT_MAX_TABLES
 CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
 
 
+def shift_table(d, group):
+    """The lane shift d as a route table of `group` entries: lane t reads lane t + d, ROUTE_FALSE where that leaves
+    the group."""
+    return tuple(t + d if 0 <= t + d < group else ROUTE_FALSE for t in range(group))
+
+
+def normal_route(table):
+    """A route table in its normal form, (shift, route): the identity is (0, None), a table that is a pure shift with
+    FALSE fill (shift_table) is (d, None) with the smallest such |d|, anything else (0, the table as a tuple)."""
+    table = tuple(int(x) for x in table)
+    G = len(table)
+    if any(not ROUTE_FALSE <= x < G for x in table):
+        raise ValueError("a route entry is a lane 0 .. %d or ROUTE_FALSE (-1): %r" % (G - 1, table))
+    for d in sorted(range(-G + 1, G), key=abs):
+        if table == shift_table(d, G):
+            return d, None
+    return 0, table
+
+
 class Wire:
-    """A wire reference: the wire id, plus bit 31 for its negation (`~w`), and a lane shift (`w.lane(d)`)."""
+    """A wire reference: the wire id, plus bit 31 for its negation (`~w`), and a lane shift (`w.lane(d)`) or a lane
+    route (`w.route(table)`), never both."""
 
-    __slots__ = ("ref", "shift")
+    __slots__ = ("ref", "shift", "table")
 
-    def __init__(self, ref, shift=0):
+    def __init__(self, ref, shift=0, table=None):
         self.ref = int(ref) & 0xFFFFFFFF
         self.shift = int(shift)
+        self.table = None if table is None else tuple(int(x) for x in table)
 
     def __invert__(self):
-        return Wire(self.ref ^ NOT_BIT, self.shift)
+        return Wire(self.ref ^ NOT_BIT, self.shift, self.table)
 
     def lane(self, d):
         """The reference that reads lane t + d of this one at lane t of every group (FALSE, or TRUE for a negated
-        reference, where t + d leaves the group).  Shifts add up."""
+        reference, where t + d leaves the group).  Shifts add up; on a routed reference the shift composes with the
+        route as route(shift_table(d, G)) does."""
+        if self.table is not None:
+            return self.route(shift_table(int(d), len(self.table)))
         return Wire(self.ref, self.shift + int(d))
+
+    def route(self, table):
+        """The reference that reads lane table[t] of this one at lane t of every group of G = len(table) lanes, and
+        FALSE (TRUE for a negated reference) where table[t] is ROUTE_FALSE.  It costs no bootstrap.  It composes with an
+        earlier shift or route -- w.route(A).route(B) reads w at lane A[B[t]], and a fill stays a fill -- and the result
+        is normalised (normal_route): the identity is no route at all, a pure shift with FALSE fill is that shift."""
+        table = tuple(int(x) for x in table)
+        G = len(table)
+        if G < 1 or any(not ROUTE_FALSE <= x < G for x in table):
+            raise ValueError("a route entry is a lane 0 .. %d or ROUTE_FALSE (-1): %r" % (G - 1, table))
+        if self.table is not None and len(self.table) != G:
+            raise ValueError("route: a table of %d lanes on a reference routed over %d" % (G, len(self.table)))
+        if self.table is None and abs(self.shift) >= G:
+            raise ValueError("route: the reference's lane shift %+d is outside a group of %d" % (self.shift, G))
+        inner = self.table if self.table is not None else shift_table(self.shift, G)
+        shift, table = normal_route(ROUTE_FALSE if x < 0 else inner[x] for x in table)
+        return Wire(self.ref, shift, table)
+
+    @property
+    def lanes(self):
+        """How the reference reads its group: the route table (a tuple) of a routed reference, the lane shift otherwise."""
+        return self.shift if self.table is None else self.table
 
     @property
     def id(self):
@@ -101,14 +156,15 @@ class Wire:
         return bool(self.ref & NOT_BIT)
 
     def __eq__(self, other):
-        return isinstance(other, Wire) and other.ref == self.ref and other.shift == self.shift
+        return isinstance(other, Wire) and other.ref == self.ref and other.shift == self.shift and other.table == self.table
 
     def __hash__(self):
-        return hash((self.ref, self.shift))
+        return hash((self.ref, self.shift, self.table))
 
     def __repr__(self):
         return "%sWire(%s)%s" % ("~" if self.negated else "", "FALSE" if self.id == FALSE_ID else self.id,
-                                 ".lane(%+d)" % self.shift if self.shift else "")
+                                 ".route(%r)" % (self.table,) if self.table is not None else
+                                 (".lane(%+d)" % self.shift if self.shift else ""))
 
 
 class Plane:
@@ -130,7 +186,8 @@ class Circuit:
     the group is above 1, sgfhe_circuit_create3 when a gate3 exists, sgfhe_circuit_create_w when a sum node exists that
     is no three-input node, sgfhe_circuit_create_lut when a LUT node exists, sgfhe_circuit_create_lut_multi when a LUT
     sibling exists, sgfhe_circuit_create_data when the circuit has planes, sgfhe_circuit_create_seq when it has
-    registers) is made on first use and freed with the object.
+    registers, sgfhe_circuit_create_routed when a reference carries a lane route that normalisation leaves a route) is
+    made on first use and freed with the object.
     `planes`: the number of data planes a run brings (lut_data, Circuit.plane), uint8 [planes][instances].
     `registers`: the first `registers` inputs are registers (`c.registers`), fed back by a stepped run from the wires
     given to next_state; the others are the stream inputs (`c.stream_inputs`).  `reg_scales`: the scale of every
@@ -163,7 +220,9 @@ class Circuit:
         self.next_shifts = [0] * self.n_regs
         self.gates = []            # [(x ref, y ref)], or (x ref, y ref, z ref) for a three-input node
         self.outputs = []          # [ref]
-        self.gate_shifts = []      # [(x lane shift, y lane shift)] or (x, y, z lane shift), beside gates
+        self.gate_shifts = []      # [(x lane shift, y lane shift)] or (x, y, z lane shift), beside gates; in place of a
+                                   # shift, here and in output_shifts and next_shifts, a routed reference has its
+                                   # route table (a tuple of `group` entries: Wire.lanes)
         self.gate_weights = {}     # node -> (weight, ...) beside its references: the sum nodes (sum_node)
         self.gate_tables = {}      # node -> truth table: the LUT nodes (lut) and their siblings (lut_multi)
         self.gate_leader = {}      # sibling -> its leader, a LUT node: no inputs of its own, () in gates and gate_shifts
@@ -187,6 +246,8 @@ class Circuit:
             raise TypeError("expected a Wire, got %r" % (w,))
         if abs(w.shift) >= self.group:
             raise ValueError("%r: a lane shift must be inside the group of %d" % (w, self.group))
+        if w.table is not None and len(w.table) != self.group:
+            raise ValueError("%r: a route table has one entry per lane of the group of %d" % (w, self.group))
         if self.scale(w) not in (None, scale):
             raise ValueError("%r has scale %d where scale %d is read (Circuit.lut, Circuit.fan)" % (w, self.scale(w), scale))
         return w.ref
@@ -194,7 +255,7 @@ class Circuit:
     def gate(self, x, y):
         """One node: bootstrap(x, y).  Returns its (AND, OR, XOR) wires."""
         self.gates.append((self._ref(x), self._ref(y)))
-        self.gate_shifts.append((x.shift, y.shift))
+        self.gate_shifts.append((x.lanes, y.lanes))
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
@@ -204,7 +265,7 @@ class Circuit:
         or two of the inputs true" (not all equal), and the parity x + y + z - 2 MAJ over Z_r, which is linear and
         carries the errors of x, y and z on."""
         self.gates.append((self._ref(x), self._ref(y), self._ref(z)))
-        self.gate_shifts.append((x.shift, y.shift, z.shift))
+        self.gate_shifts.append((x.lanes, y.lanes, z.lanes))
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
@@ -221,7 +282,7 @@ class Circuit:
         if any(int(w) not in (-2, -1, 1, 2) for w, _ in terms):
             raise ValueError("the weights of a sum node are -2, -1, 1 or 2")
         self.gates.append(tuple(self._ref(x) for _, x in terms))
-        self.gate_shifts.append(tuple(x.shift for _, x in terms))
+        self.gate_shifts.append(tuple(x.lanes for _, x in terms))
         self.gate_weights[len(self.gates) - 1] = tuple(int(w) for w, _ in terms)
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
@@ -234,7 +295,7 @@ class Circuit:
         if not 0 <= int(table) < 256:
             raise ValueError("a LUT node's table has 8 entries: 0 .. 255")
         self.gates.append((self._ref(x0, 2), self._ref(x1, 1), self._ref(x2, 0)))
-        self.gate_shifts.append((x0.shift, x1.shift, x2.shift))
+        self.gate_shifts.append((x0.lanes, x1.lanes, x2.lanes))
         self.gate_tables[len(self.gates) - 1] = int(table)
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
@@ -322,6 +383,36 @@ class Circuit:
     def has_lut(self):
         return bool(self.gate_tables)
 
+    # ---- lane routes: any public lane map inside a group, at no bootstrap (Wire.route) --------------
+    def rot(self, w, d):
+        """`w` rotated inside every group: lane t reads lane (t + d) mod group.  lane(d) with the lanes that leave the
+        group coming back in at the other end."""
+        return w.route([(t + int(d)) % self.group for t in range(self.group)])
+
+    def swap(self, w, k):
+        """Partner exchange: lane t reads lane t ^ k (butterflies, sorting networks, transposes); FALSE where t ^ k is
+        no lane of the group."""
+        return w.route([t ^ int(k) if (t ^ int(k)) < self.group else ROUTE_FALSE for t in range(self.group)])
+
+    def bcast(self, w, lane):
+        """Lane `lane` of `w` at every lane of its group (a flag or a carry-out every lane needs)."""
+        if not 0 <= int(lane) < self.group:
+            raise ValueError("bcast: lane %r is outside the group of %d" % (lane, self.group))
+        return w.route([int(lane)] * self.group)
+
+    def reverse(self, w):
+        """`w` with the lanes of every group in reverse order."""
+        return w.route([self.group - 1 - t for t in range(self.group)])
+
+    @property
+    def route_tables(self):
+        """The distinct route tables of the circuit's references, in order of first use (terms, outputs, next states)."""
+        seen = {}
+        for d in [d for x in self.gate_shifts for d in x] + list(self.output_shifts) + list(self.next_shifts):
+            if isinstance(d, tuple):
+                seen.setdefault(d, len(seen))
+        return list(seen)
+
     def xor(self, *wires):
         """The XOR of any number of wires (up to 64) in ONE bootstrap: HI of the sum node with every weight 2.  The
         wires should be bootstrapped ones (gate rows, refreshed wires): the node doubles their errors.  No wire at
@@ -367,7 +458,7 @@ class Circuit:
     def output(self, *wires):
         """Set the circuit's outputs (wire references: inputs, constants and negated wires allowed)."""
         self.outputs = [self._ref(w) for w in wires]
-        self.output_shifts = [w.shift for w in wires]
+        self.output_shifts = [w.lanes for w in wires]
         self._invalidate()
 
     def next_state(self, *wires):
@@ -377,7 +468,7 @@ class Circuit:
         if len(wires) != self.n_regs:
             raise ValueError("next_state: one wire per register (%d)" % self.n_regs)
         self.next_refs = [self._ref(w, k) for w, k in zip(wires, self.reg_scales)]
-        self.next_shifts = [w.shift for w in wires]
+        self.next_shifts = [w.lanes for w in wires]
         self._invalidate()
 
     def step_plan(self):
@@ -414,18 +505,35 @@ class Circuit:
             L = _lib.lib()
             vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
             o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
-            os_ = np.ascontiguousarray(np.array(self.output_shifts, dtype=np.int32))
+            shift_of = lambda d: 0 if isinstance(d, tuple) else d   # (a routed reference has shift 0)
+            os_ = np.ascontiguousarray(np.array([shift_of(d) for d in self.output_shifts], dtype=np.int32))
             h = ctypes.c_void_p()
-            if self.has_wsum or self.has_lut or self.planes or self.n_regs:
+            routes = self.route_tables
+            if self.has_wsum or self.has_lut or self.planes or self.n_regs or routes:
                 # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes, 3 for their siblings, 4 and 5
                 # for those whose table is a data plane
                 kind = np.array([{"classic": 0, "lut": 2, "sibling": 3, "data": 4, "data_sibling": 5}.get(self.kind(g), 1)
                                  for g in range(len(self.gates))], dtype=np.uint32)
                 start = np.cumsum([0] + [len(x) for x in self.gates]).astype(np.uint32)
                 tr = np.array([ref for x in self.gates for ref in x], dtype=np.uint32)
-                ts = np.array([d for x in self.gate_shifts for d in x], dtype=np.int32)
+                index = {t: k + 1 for k, t in enumerate(routes)}   # route index: 0 none, k = table k - 1
+                ts = np.array([shift_of(d) for x in self.gate_shifts for d in x], dtype=np.int32)
                 tw = np.array([w for g in range(len(self.gates)) for w in self.weights(g)], dtype=np.int32)
-                if self.n_regs:   # (only a circuit with registers: every other keeps the creator it has)
+                if routes:   # (only a circuit a route survives in: every other keeps the creator it has)
+                    tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
+                                   for g in range(len(self.gates))], dtype=np.uint32)
+                    nr = np.ascontiguousarray(np.array(self.next_refs, dtype=np.uint32))
+                    ns = np.ascontiguousarray(np.array([shift_of(d) for d in self.next_shifts], dtype=np.int32))
+                    rs = np.ascontiguousarray(np.array(self.reg_scales, dtype=np.uint32))
+                    rt = np.ascontiguousarray(np.array(routes, dtype=np.int32).reshape(len(routes), self.group))
+                    tt = np.array([index.get(d, 0) for x in self.gate_shifts for d in x], dtype=np.uint32)
+                    ot = np.array([index.get(d, 0) for d in self.output_shifts], dtype=np.uint32)
+                    nt = np.array([index.get(d, 0) for d in self.next_shifts], dtype=np.uint32)
+                    rc = L.sgfhe_circuit_create_routed(self.n_inputs, self.planes, vp(kind), vp(start), vp(tr), vp(ts), vp(tw),
+                                                       vp(tb), len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
+                                                       self.n_regs, vp(nr), vp(ns), vp(rs), len(routes), vp(rt), vp(tt),
+                                                       vp(ot), vp(nt), ctypes.byref(h))
+                elif self.n_regs:   # (only a circuit with registers: every other keeps the creator it has)
                     tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
                                    for g in range(len(self.gates))], dtype=np.uint32)
                     nr = np.ascontiguousarray(np.array(self.next_refs, dtype=np.uint32))
@@ -625,12 +733,22 @@ def check_step_data(circuit, data, steps, instances):
 
 def lane_shift(v, d, group):
     """The lane-shifted read of a wire: v [instances, ...] -> the array whose entry t is v[t + d] where
-    0 <= t % group + d < group, and zero (the constant FALSE, the trivial LWE (0, 0)) elsewhere."""
-    if d == 0:
+    0 <= t % group + d < group, and zero (the constant FALSE, the trivial LWE (0, 0)) elsewhere.  d a route table (a
+    tuple of `group` entries, Wire.route): entry t is v[t - t % group + d[t % group]], and zero where that entry of the
+    table is ROUTE_FALSE."""
+    if not isinstance(d, tuple) and d == 0:
         return v
     if v.shape[0] % group:
         raise ValueError("the instances (%d) must be a multiple of the lane group (%d)" % (v.shape[0], group))
     t = np.arange(v.shape[0])
+    if isinstance(d, tuple):
+        if len(d) != group:
+            raise ValueError("a route table of %d entries in a group of %d" % (len(d), group))
+        src = np.asarray(d, dtype=np.int64)[t % group]
+        ok = src >= 0
+        out = np.zeros_like(v)
+        out[ok] = v[(t - t % group + src)[ok]]
+        return out
     ok = (t % group + d >= 0) & (t % group + d < group)
     out = np.zeros_like(v)
     out[ok] = v[t[ok] + d]
@@ -759,6 +877,58 @@ def crc16_stream(chunk_bits):
     hi = [c.xor(*[src[j] for j in np.flatnonzero(row)]) for row in M]
     c.output(*hi)
     c.next_state(*hi)
+    return c
+
+
+def bitonic_stages(G):
+    """The compare-exchange stages of the bitonic sorting network on G = 2^k lanes, ascending: a list of (k, table) --
+    the partner of lane t is lane t ^ k, and table[t] in {t, t ^ k} is the lane whose [own > partner] decides the swap
+    at lane t: the lane itself where it keeps the smaller element when it is the larger (the low partner of an ascending
+    block, the high partner of a descending one), its partner otherwise.  Both partners read the same decision."""
+    G = int(G)
+    if G < 1 or G & (G - 1):
+        raise ValueError("bitonic sort: the group must be a power of two")
+    stages, block = [], 2
+    while block <= G:
+        k = block // 2
+        while k >= 1:
+            stages.append((k, tuple(t if ((t & k) == 0) == ((t & block) == 0) else t ^ k for t in range(G))))
+            k //= 2
+        block *= 2
+    return stages
+
+
+def bitonic_sort(width, G, refresh_inputs=True):
+    """Sorts the G numbers of `width` bits of every lane group ascending: Circuit(width, group=G), bit-sliced -- input
+    wire i holds bit i (LSB first) of every number, lane = element -- and outputs laid out the same way, lane 0 the
+    smallest.  The bitonic network's log2(G) (log2(G) + 1) / 2 stages (bitonic_stages), each one compare-exchange at a
+    distance k built from lane routes (Circuit.swap, Wire.route), so no input is per lane and nothing but the nodes
+    below costs a bootstrap:
+      * g = [own > partner] is the carry out of own + ~partner: a chain of `width` gate3 nodes, carry' = MAJ(x_i,
+        ~swap(x_i, k), carry) from the LSB up, the first carry FALSE;
+      * the swap decision s = g.route(table) of bitonic_stages -- g at the lane itself or at its partner;
+      * the new bit i is the mux (s ? partner : own) as ONE LUT node, lut(0xCA, x_i at Dr/4, swap(x_i, k) at Dr/2, s).
+    The LUT mux is the cheapest the noise rules allow: it reads bootstrapped wires only (the rule of LUT nodes), and a
+    mux from two-input nodes takes three bootstraps a bit.  It needs every bit at the scales 2 and 1, which a LUT node
+    returns itself; before the first stage one fan per bit brings the inputs there.  refresh_inputs: every input is
+    refreshed first (Circuit.refresh, one bootstrap each), as it must be when the inputs are fresh encryptions -- the fan
+    is a LUT node, and a split encrypt_private bit is already at the limit of its rule; False for inputs that are gate
+    rows or packed outputs.
+    Nodes: width refreshes and width fans, then 2 width per stage -- 2 width + width log2(G) (log2(G) + 1); levels:
+    2 + (width + 1) per stage (one node and one level less per bit without the refreshes)."""
+    width, G = int(width), int(G)
+    if width < 1:
+        raise ValueError("bitonic sort: width must be at least 1")
+    stages = bitonic_stages(G)
+    c = Circuit(width, group=G)
+    x = [c.fan(c.refresh(w) if refresh_inputs else w) for w in c.inputs]   # per bit: (scale 0, scale 1, scale 2)
+    for k, table in stages:
+        carry = Circuit.FALSE
+        for i in range(width):
+            carry = c.gate3(x[i][0], ~c.swap(x[i][0], k), carry)[0]
+        s = carry.route(table)
+        x = [c.lut(0xCA, x[i][2], c.swap(x[i][1], k), s) for i in range(width)]
+    c.output(*[xi[0] for xi in x])
     return c
 
 

@@ -7,7 +7,8 @@
 // circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
 // circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp, circuit_lut_multi_sanitized.cpp,
-// circuit_data_sanitized.cpp, circuit_calls_sanitized.cpp and circuit_steps_sanitized.cpp drive it under ASan / UBSan on the CPU.
+// circuit_data_sanitized.cpp, circuit_calls_sanitized.cpp, circuit_steps_sanitized.cpp and circuit_routes_sanitized.cpp
+// drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -33,6 +34,7 @@ constexpr uint32_t CIRC_NO_INPUT = SGFHE_CIRCUIT_NONE;   // third reference of a
 // A table that is run-time data (sgfhe_circuit_create_data): bit 24 of a LUT node's kind word, whose bits 8..23 then hold
 // the plane, and of fam_entry[4 i], whose low bits then hold the plane (kernels.h CIRC_TABLE_DATA)
 constexpr uint32_t CIRC_DATA = 0x01000000u;
+constexpr int32_t CIRC_ROUTE_FALSE = SGFHE_CIRCUIT_ROUTE_FALSE;   // entry of a route table: the constant FALSE at that lane
 
 // Word offsets of the device tables in CircuitPlan::image (int32_t tables by bit pattern); `words` is its length.
 struct CircuitImage {
@@ -42,6 +44,9 @@ struct CircuitImage {
     // behind those, and only in a plan with registers (sgfhe_circuit_create_seq); the registers' slots are the first
     // n_regs entries of input_slot
     uint32_t next_ref = 0, next_shift = 0, next_scale = 0, reg_index = 0;
+    // behind every other table, and only in a plan with route tables (sgfhe_circuit_create_routed, n_routes > 0);
+    // next_route only when the plan has registers as well
+    uint32_t routes = 0, term_route = 0, out_route = 0, next_route = 0;
 };
 
 struct CircuitPlan {
@@ -51,6 +56,7 @@ struct CircuitPlan {
     uint32_t n_planes = 0;              // data planes of a run (sgfhe_circuit_create_data); 0: every table is the plan's
     uint32_t n_regs = 0;                // registers (sgfhe_circuit_create_seq): input wires 0 .. n_regs, fed back by a
                                         // stepped run; 0: a feed-forward plan
+    uint32_t n_routes = 0;              // route tables (sgfhe_circuit_create_routed); 0: every reference reads by its shift
     std::vector<uint32_t> level;        // [n_gates]: level of every node, 0 = pruned
     std::vector<uint32_t> order;        // live nodes, level by level, ascending index within a level
     std::vector<uint32_t> level_start;  // [levels + 2]: level L's nodes are order[level_start[L] .. level_start[L + 1])
@@ -101,15 +107,25 @@ struct CircuitPlan {
     std::vector<int32_t> next_shift;    // [n_regs]
     std::vector<uint32_t> reg_scale;    // [n_regs]: 0, 1, 2
     std::vector<uint32_t> reg_index;    // [n_regs]
+    // Lane routes (sgfhe_circuit_create_routed): a reference whose route index is k >= 1 reads, at lane l of its group,
+    // lane routes[(k - 1) * group + l] of the same group -- the constant FALSE where that is CIRC_ROUTE_FALSE -- and has
+    // shift 0; index 0: the shift applies.  0 on every reference to the constant.  All empty in a plan without tables.
+    std::vector<int32_t> routes;        // [n_routes][group]
+    std::vector<uint32_t> term_route;   // [terms + 2 n_outputs], beside term_shift
+    std::vector<uint32_t> out_route;    // [n_outputs], beside out_shift
+    std::vector<uint32_t> next_route;   // [n_regs], beside next_shift
     // Every device table above in one array, uploaded once per run: node_kind, term_start, term_ref, term_shift,
     // term_weight, out_slot, out_ref, out_shift, input_slot, jobs (then fam_start, fam_entry; then next_ref, next_shift,
-    // reg_scale, reg_index), each at its offset `at`
+    // reg_scale, reg_index; then routes, term_route, out_route, next_route), each at its offset `at`
     std::vector<uint32_t> image;
     CircuitImage at;
 
     size_t live() const { return order.size(); }
     uint32_t n_stream() const { return n_inputs - n_regs; }   // the inputs a step brings
     bool lanes() const { return group > 1; }   // (group 1 admits no shift but 0)
+    // the route table of a reference whose route index is `k`, NULL for none
+    const int32_t *route(uint32_t k) const { return k ? routes.data() + (size_t)(k - 1) * group : nullptr; }
+    const int32_t *term_route_of(size_t i) const { return n_routes ? route(term_route[i]) : nullptr; }
     // live nodes order[ka .. kb] hold a sum node: the call takes an XOR3 kernel for its LOW rows
     bool gate3_in(uint32_t ka, uint32_t kb) const { return sum_before[kb + 1] != sum_before[ka]; }
     // live nodes order[ka .. kb] hold a LUT node: the call carries a LUT descriptor
@@ -180,14 +196,24 @@ struct CircuitRegs {
     uint32_t scale(uint32_t i) const { return reg_scale ? reg_scale[i] : 0u; }
 };
 
+// The lane routes of sgfhe_circuit_create_routed: routes [n_routes][group], entries in [0, group) or CIRC_ROUTE_FALSE;
+// term_route beside the term arrays, out_route [n_outputs], next_route [n_regs] (each NULL: all 0): 0 = none, k >= 1 =
+// table k - 1, and then the reference's shift must be 0.
+struct CircuitRoutes {
+    uint32_t n_routes;
+    const int32_t *routes;
+    const uint32_t *term_route, *out_route, *next_route;
+};
+
 // Builds `P` from the nodes `N` (gate shifts / out_shift NULL: all 0).  `R` (NULL or n_regs 0: none): the registers; their
 // next-state references count as readers exactly as outputs do -- liveness, levels, slot lifetime -- so the plan's
-// order, levels and slots are those of the plan whose outputs are outputs ++ next_ref.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
+// order, levels and slots are those of the plan whose outputs are outputs ++ next_ref.  `T` (NULL: none): the lane routes;
+// nothing but the route tables of the plan sees them, and with n_routes = 0 the plan is the plan without `T`.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
 // malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it, and a refused circuit costs no
 // allocation.
 inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
                                   const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P,
-                                  const CircuitRegs *R = nullptr) noexcept {
+                                  const CircuitRegs *R = nullptr, const CircuitRoutes *T = nullptr) noexcept {
     using circuit_detail::wire_id;
     const uint32_t *refs = N.refs;
     const uint32_t n_regs = R ? R->n_regs : 0u;
@@ -269,6 +295,23 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             if (!shift_ok(gate_shift[i])) return SGFHE_ERR_INVALID_ARG;
     for (size_t o = 0; out_shift && o < n_outputs; o++)
         if (!shift_ok(out_shift[o])) return SGFHE_ERR_INVALID_ARG;
+    // ---- the routes: every entry a lane of the group or the fill, every index a table, and never beside a shift
+    const uint32_t n_routes = T ? T->n_routes : 0u;
+    if (T) {
+        if (n_routes > SGFHE_CIRCUIT_MAX_ROUTES || (n_routes && !T->routes)) return SGFHE_ERR_INVALID_ARG;
+        for (size_t i = 0; i < (size_t)n_routes * group; i++)
+            if (T->routes[i] < CIRC_ROUTE_FALSE || T->routes[i] >= (int64_t)group) return SGFHE_ERR_INVALID_ARG;
+        auto route_ok = [&](const uint32_t *route, const int32_t *shift, size_t i) {
+            return !route || (route[i] <= n_routes && (route[i] == 0 || !shift || shift[i] == 0));
+        };
+        for (size_t g = 0; g < n_gates; g++)
+            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++)
+                if (!route_ok(T->term_route, gate_shift, i)) return SGFHE_ERR_INVALID_ARG;
+        for (size_t o = 0; o < n_outputs; o++)
+            if (!route_ok(T->out_route, out_shift, o)) return SGFHE_ERR_INVALID_ARG;
+        for (uint32_t i = 0; i < n_regs; i++)
+            if (!route_ok(T->next_route, R->next_shift, i)) return SGFHE_ERR_INVALID_ARG;
+    }
     try {
         P = CircuitPlan();
         P.n_inputs = n_inputs;
@@ -277,6 +320,8 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
         P.group = group;
         P.n_planes = N.n_planes;
         P.n_regs = n_regs;
+        P.n_routes = n_routes;
+        if (n_routes) P.routes.assign(T->routes, T->routes + (size_t)n_routes * group);
         const uint32_t NG = (uint32_t)n_gates;
         auto node_of = [&](uint32_t id) -> int64_t {   // producing node of a wire, -1 for inputs and the constant
             return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
@@ -413,10 +458,15 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             const size_t node_row = N.is_sibling((size_t)g) ? P.live() + sib_index[g] : rank_of[g];
             return (uint32_t)(n_inputs + 3 * node_row + (id - n_inputs) % 3) | (ref & CIRC_NOT);
         };
-        auto term = [&](uint32_t ref, int32_t shift, int32_t weight) {
+        // (a route, like a shift, is dropped on a reference to the constant; no route array is kept without tables)
+        auto route_of = [&](uint32_t ref, const uint32_t *tab, size_t i) -> uint32_t {
+            return n_routes && tab && wire_id(ref) != CIRC_FALSE ? tab[i] : 0u;
+        };
+        auto term = [&](uint32_t ref, int32_t shift, int32_t weight, uint32_t route) {
             P.term_ref.push_back(ref);
             P.term_shift.push_back(shift);
             P.term_weight.push_back(weight);
+            if (n_routes) P.term_route.push_back(route);
         };
         P.out_slot.resize(3 * P.live());
         P.sum_before.assign(P.live() + 1, 0);
@@ -426,7 +476,8 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.node_kind.push_back(N.kind_of(g) | (N.is_lut(g) ? N.table_word(g, 8) : 0u));
             P.term_start.push_back((uint32_t)P.term_ref.size());
             for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
-                term(slot_ref(refs[i]), shift_of(refs[i], gate_shift, i), N.weight(i));
+                term(slot_ref(refs[i]), shift_of(refs[i], gate_shift, i), N.weight(i),
+                     route_of(refs[i], T ? T->term_route : nullptr, i));
                 P.term_row.push_back(row_ref(refs[i]));
             }
             for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
@@ -444,11 +495,14 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.out_shift[o] = shift_of(outputs[o], out_shift, o);
             P.node_kind.push_back(0u);
             P.term_start.push_back((uint32_t)P.term_ref.size());
-            term(CIRC_FALSE | CIRC_NOT, 0, 1);
-            term(P.out_ref[o], P.out_shift[o], 1);
+            const uint32_t route = route_of(outputs[o], T ? T->out_route : nullptr, o);
+            if (n_routes) P.out_route.push_back(route);
+            term(CIRC_FALSE | CIRC_NOT, 0, 1, 0u);
+            term(P.out_ref[o], P.out_shift[o], 1, route);
             const uint32_t id = wire_id(outputs[o]);
             const int64_t g = node_of(id);
-            if (g < 0 || P.out_shift[o] != 0) continue;
+            // (a routed output is no gate row in order, even under the identity table: refreshed or lifted, as a shifted one)
+            if (g < 0 || P.out_shift[o] != 0 || route != 0) continue;
             if ((id - n_inputs) % 3 == 2 && !N.classic((size_t)g)) continue;   // LOW: linear over Z_r, no gate row
             if (N.is_lut((size_t)g)) continue;   // wire +0 of a LUT node: refreshed or lifted, as a LOW wire is
             P.out_node[o] = rank_of[g];
@@ -461,6 +515,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.next_shift.push_back(shift_of(R->next_ref[i], R->next_shift, i));
             P.reg_scale.push_back(R->scale(i));
             P.reg_index.push_back(i);
+            if (n_routes) P.next_route.push_back(route_of(R->next_ref[i], T ? T->next_route : nullptr, i));
         }
         // ---- the direct-pack jobs, by producing node
         std::vector<uint32_t> byk;
@@ -482,7 +537,8 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             return (uint32_t)at;
         };
         P.image.reserve(P.node_kind.size() + P.term_start.size() + 3 * P.term_ref.size() + P.out_slot.size() +
-                        2 * n_outputs + n_inputs + P.jobs.size() + 4 * (size_t)n_regs);
+                        2 * n_outputs + n_inputs + P.jobs.size() + 4 * (size_t)n_regs + P.routes.size() +
+                        P.term_route.size() + P.out_route.size() + P.next_route.size());
         P.at.node_kind = place(P.node_kind);
         P.at.term_start = place(P.term_start);
         P.at.term_ref = place(P.term_ref);
@@ -502,6 +558,12 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.at.next_shift = place(P.next_shift);
             P.at.next_scale = place(P.reg_scale);
             P.at.reg_index = place(P.reg_index);
+        }
+        if (n_routes) {
+            P.at.routes = place(P.routes);
+            P.at.term_route = place(P.term_route);
+            P.at.out_route = place(P.out_route);
+            if (n_regs) P.at.next_route = place(P.next_route);
         }
         P.at.words = (uint32_t)P.image.size();
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
@@ -579,6 +641,21 @@ inline int32_t circuit_plan_seq(uint32_t n_inputs, uint32_t n_planes, const uint
     return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P, &R);
 }
 
+// The arrays of sgfhe_circuit_create_routed: those of sgfhe_circuit_create_seq, and the lane routes.  With n_routes = 0
+// the plan is the sgfhe_circuit_create_seq plan, image word for word.
+inline int32_t circuit_plan_routed(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
+                                   const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                   const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
+                                   const int32_t *out_shift, size_t n_outputs, uint32_t group, uint32_t n_regs,
+                                   const uint32_t *next_ref, const int32_t *next_shift, const uint32_t *reg_scale,
+                                   uint32_t n_routes, const int32_t *routes, const uint32_t *term_route,
+                                   const uint32_t *out_route, const uint32_t *next_route, CircuitPlan &P) noexcept {
+    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
+    const CircuitRoutes T = {n_routes, routes, term_route, out_route, next_route};
+    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P, &R, &T);
+}
+
 // The arrays of sgfhe_circuit_create_lanes.
 inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                             const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
@@ -606,7 +683,8 @@ inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_g
 // is instance t (the bits past `instances` in a row's last word are unspecified).  in_bits [n_inputs][instances],
 // bit 0 of each byte.  Word-parallel: three operations per (live node, 64 instances); a lane-shifted input is first
 // laid out as a row of its own, instance by instance (instance t reads bit t + d where its lane allows, 0 elsewhere;
-// `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise).  A sum node's rows are HI, MID and LOW
+// `instances` must be a multiple of P.group, SGFHE_ERR_INVALID_ARG otherwise), and a routed one likewise (instance t of
+// lane l reads bit t - l + route[l], 0 where the entry is CIRC_ROUTE_FALSE).  A sum node's rows are HI, MID and LOW
 // of s = sum of w x mod 4: MAJ, ONE_OR_TWO (one or two of its inputs true) and XOR3 of a three-input node.
 // `data` [n_planes][instances]: the planes of a run (sgfhe_circuit_run_probe_data); a data LUT node or data sibling of
 // plane p has the table data[p][t] at instance t, its own instance whatever its terms' shifts (SGFHE_ERR_INVALID_ARG for
@@ -629,7 +707,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
     std::vector<uint64_t> shifted[3];
     try {
         table.assign(circuit_probe_rows(P) * wpr, 0);
-        if (P.lanes())
+        if (P.lanes() || P.n_routes)
             for (auto &s : shifted) s.assign(wpr, 0);
     } catch (...) {
         return SGFHE_ERR_OOM;
@@ -638,17 +716,19 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
         for (size_t t = 0; t < instances; t++)
             table[i * wpr + t / 64] |= (uint64_t)(in_bits[i * instances + t] & 1u) << (t % 64);
     const int64_t G = P.group;
-    // the row a reference reads, before NOT: the table's own row, or that row shifted by d inside every group
-    auto source = [&](uint32_t ref, int32_t d, std::vector<uint64_t> &tmp) -> const uint64_t * {
-        const uint32_t row = circuit_detail::wire_id(ref);
+    // the row term i reads, before NOT: the table's own row, or that row shifted by d or routed inside every group
+    auto source = [&](size_t i, std::vector<uint64_t> &tmp) -> const uint64_t * {
+        const uint32_t row = circuit_detail::wire_id(P.term_row[i]);
+        const int32_t d = P.term_shift[i];
+        const int32_t *rho = P.term_route_of(i);
         if (row == CIRC_FALSE) return nullptr;
         const uint64_t *src = table.data() + (size_t)row * wpr;
-        if (d == 0) return src;
+        if (d == 0 && !rho) return src;
         std::fill(tmp.begin(), tmp.end(), 0ull);
         for (size_t t = 0; t < instances; t++) {
-            const int64_t lane = (int64_t)(t % (size_t)G) + d;
+            const int64_t own = (int64_t)(t % (size_t)G), lane = rho ? (int64_t)rho[own] : own + d;
             if (lane < 0 || lane >= G) continue;
-            const size_t u = (size_t)((int64_t)t + d);   // same group: 0 <= u < instances
+            const size_t u = (size_t)((int64_t)t - own + lane);   // same group: 0 <= u < instances
             tmp[t / 64] |= (src[u / 64] >> (u % 64) & 1ull) << (t % 64);
         }
         return tmp.data();
@@ -664,7 +744,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
             // a LUT node: all three wires carry bit s of the table, s = x0 + 2 x1 + 4 x2 -- the OR over the set table
             // entries of their minterms; its live siblings carry their own tables' bits of the same s
             const uint64_t *sx[3];
-            for (uint32_t p = 0; p < 3; p++) sx[p] = source(P.term_row[t0 + p], P.term_shift[t0 + p], shifted[p]);
+            for (uint32_t p = 0; p < 3; p++) sx[p] = source(t0 + p, shifted[p]);
             // (`tw`, `ps`: a kind word with its table from bit 8, or a family entry with it from bit 0; a data table is
             // one mask per entry: the instances of the word whose byte has bit sv set)
             auto fill = [&](uint32_t tw, uint32_t ps, uint64_t *dst) {
@@ -695,7 +775,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
             // (of three unit weights: MAJ, ONE_OR_TWO, XOR3)
             uint64_t *hi = o, *lo = o + 2 * wpr;
             for (uint32_t i = t0; i < t1; i++) {
-                const uint64_t *sx = source(P.term_row[i], P.term_shift[i], shifted[0]);
+                const uint64_t *sx = source(i, shifted[0]);
                 const int32_t wt = P.term_weight[i];
                 for (size_t w = 0; w < wpr; w++) {
                     const uint64_t x = word(sx, P.term_row[i], w);
@@ -711,7 +791,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
             continue;
         }
         const uint32_t rx = P.term_row[t0], ry = P.term_row[t0 + 1];
-        const uint64_t *sx = source(rx, P.term_shift[t0], shifted[0]), *sy = source(ry, P.term_shift[t0 + 1], shifted[1]);
+        const uint64_t *sx = source(t0, shifted[0]), *sy = source(t0 + 1, shifted[1]);
         for (size_t w = 0; w < wpr; w++) {
             const uint64_t x = word(sx, rx, w), y = word(sy, ry, w);
             o[w] = x & y;

@@ -2973,11 +2973,11 @@ int32_t sgfhe_timing_read(sgfhe_ctx *c, double *stats, int reset) {
 // validated into a local first
 static int32_t circuit_create(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
                               const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out,
-                              const CircuitRegs *regs = nullptr) {
+                              const CircuitRegs *regs = nullptr, const CircuitRoutes *routes = nullptr) {
     if (!out) return SGFHE_ERR_INVALID_ARG;
     *out = nullptr;
     CircuitPlan plan;
-    const int32_t rc = circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, plan, regs);
+    const int32_t rc = circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, plan, regs, routes);
     if (rc) return rc;
     sgfhe_circuit *c = new (std::nothrow) sgfhe_circuit();
     if (!c) return SGFHE_ERR_OOM;
@@ -3040,6 +3040,26 @@ int32_t sgfhe_circuit_create_seq(uint32_t n_inputs, uint32_t n_planes, const uin
     const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
     const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
     return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out, &R);
+}
+
+int32_t sgfhe_circuit_create_routed(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
+                                    const uint32_t *node_start, const uint32_t *term_ref, const int32_t *term_shift,
+                                    const int32_t *term_weight, const uint32_t *node_table, size_t n_gates,
+                                    const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                                    uint32_t n_regs, const uint32_t *next_ref, const int32_t *next_shift,
+                                    const uint32_t *reg_scale, uint32_t n_routes, const int32_t *routes,
+                                    const uint32_t *term_route, const uint32_t *out_route, const uint32_t *next_route,
+                                    sgfhe_circuit **out) {
+    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
+    const CircuitRoutes T = {n_routes, routes, term_route, out_route, next_route};
+    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out, &R, &T);
+}
+
+int32_t sgfhe_circuit_routes(const sgfhe_circuit *c, uint32_t *n_routes) {
+    if (!c || !n_routes) return SGFHE_ERR_INVALID_ARG;
+    *n_routes = c->plan.n_routes;
+    return SGFHE_OK;
 }
 
 int32_t sgfhe_circuit_registers(const sgfhe_circuit *c, uint32_t *n_regs) {
@@ -3204,6 +3224,7 @@ struct CircuitRun {
     const uint32_t *d_next_ref = nullptr, *d_next_scale = nullptr, *d_reg_index = nullptr;   // (a plan with registers)
     const int32_t *d_next_shift = nullptr;
     const int32_t *d_out_shift = nullptr;
+    const uint32_t *d_out_route = nullptr, *d_next_route = nullptr;   // (a plan with route tables; the tables: nodes.routes)
     NoiseLayout NL = {};
     std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
 
@@ -3294,7 +3315,7 @@ int32_t CircuitRun::upload_tables() {
     const uint32_t *tab = c->circ_tab.p;
     nodes = {tab + P.at.node_kind, tab + P.at.term_start, tab + P.at.term_ref,
              reinterpret_cast<const int32_t *>(tab + P.at.term_shift),
-             reinterpret_cast<const int32_t *>(tab + P.at.term_weight)};
+             reinterpret_cast<const int32_t *>(tab + P.at.term_weight), nullptr, nullptr};
     d_out_slot = tab + P.at.out_slot, d_out_ref = tab + P.at.out_ref, d_in_slot = tab + P.at.input_slot;
     d_jobs = tab + P.at.jobs;
     if (P.siblings()) d_fam_start = tab + P.at.fam_start, d_fam_entry = tab + P.at.fam_entry;
@@ -3303,6 +3324,11 @@ int32_t CircuitRun::upload_tables() {
         d_next_shift = reinterpret_cast<const int32_t *>(tab + P.at.next_shift);
     }
     d_out_shift = reinterpret_cast<const int32_t *>(tab + P.at.out_shift);
+    if (P.n_routes) {   // (a plan without tables leaves all of these NULL: its kernels read no route)
+        nodes.route = tab + P.at.term_route, nodes.routes = reinterpret_cast<const int32_t *>(tab + P.at.routes);
+        d_out_route = tab + P.at.out_route;
+        if (P.n_regs) d_next_route = tab + P.at.next_route;
+    }
     if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
         HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
         if (probe_rows) HIPCHK(c, hipMemsetAsync(NL.stats, 0, probe_rows * 64, st));
@@ -3447,7 +3473,7 @@ int32_t CircuitRun::pack_group(size_t q0) {
             const uint32_t rows = (uint32_t)(U.len * n);
             hipLaunchKernelGGL(k_circ_lift, dim3((rows * (uint32_t)row + 255) / 256), dim3(256), 0, st, c->circ_wires.p,
                                d_out_ref, d_out_shift, c->circ_raw.p, cur(c).d_crt, (uint32_t)(U.q * n), rows, inst,
-                               (uint32_t)n, r, P.group);
+                               (uint32_t)n, r, P.group, d_out_route, nodes.routes);
             HIPCHK(c, hipGetLastError());
         }
     } else if (nb) {
@@ -3501,7 +3527,7 @@ int32_t CircuitRun::fetch(uint64_t *o, uint64_t *w, uint64_t *v) {
     if (o) {
         const size_t total = (size_t)P.n_outputs * instances * row;
         hipLaunchKernelGGL(k_circ_collect, dim3(copy_grid(total)), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
-                           d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group);
+                           d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group, d_out_route, nodes.routes);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(o, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
     }
@@ -3547,7 +3573,8 @@ int32_t CircuitRun::upload_step(size_t s) {
 int32_t CircuitRun::feedback() {
     if (!P.n_regs) return SGFHE_OK;
     hipLaunchKernelGGL(k_circ_next, dim3(copy_grid(state_words())), dim3(256), 0, st, c->circ_wires.p, d_next_ref,
-                       d_next_shift, d_next_scale, c->circ_state.p, state_words(), inst, (uint32_t)n, r, P.group);
+                       d_next_shift, d_next_scale, c->circ_state.p, state_words(), inst, (uint32_t)n, r, P.group,
+                       d_next_route, nodes.routes);
     HIPCHK(c, hipGetLastError());
     return SGFHE_OK;
 }

@@ -1796,21 +1796,40 @@ __device__ __forceinline__ uint64_t circ_word(const uint64_t *__restrict__ wires
 // FALSE elsewhere (NOT applied afterwards, so a negated reference fills with TRUE).  The lane sum is signed and 64 bits
 // wide -- d < 0 must not wrap -- and the test is uniform over a row, so a wave diverges only where it straddles rows.
 // instances is a multiple of group (checked before a run is queued): row inst + d is inside the slot.
+// A routed reference (sgfhe_circuit_create_routed; `rho` its table of `group` entries, NULL for none, and then d is 0)
+// reads lane rho[inst % group] of its own group in place of lane + d: the constant where the entry is negative (the
+// planner admits -1 and [0, group) only), row inst - inst % group + rho[..] otherwise.  The entry is one 4-byte load
+// at an address that is uniform over a row, as the group test is; the source row stays a coalesced 8-byte access.
+// It is a per-lane load on purpose: rows are n + 1 words, so a wave may straddle two rows and the entry is uniform over
+// a row, not over a wave -- broadcasting the first lane's entry would read the wrong lane past the row's end.  The lanes
+// of a row hit one cache line.
 __device__ __forceinline__ uint64_t circ_word_lane(const uint64_t *__restrict__ wires, uint32_t ref, int32_t d,
-                                                   uint32_t group, uint32_t instances, uint32_t inst, uint32_t e,
-                                                   uint32_t n, uint64_t r, uint64_t one) {
-    const int64_t lane = (int64_t)(inst % group) + d;
+                                                   const int32_t *__restrict__ rho, uint32_t group, uint32_t instances,
+                                                   uint32_t inst, uint32_t e, uint32_t n, uint64_t r, uint64_t one) {
+    const uint32_t own = inst % group;
+    const int64_t lane = rho ? (int64_t)rho[own] : (int64_t)own + d;
     if (lane < 0 || lane >= (int64_t)group) ref = CIRC_REF_FALSE | (ref & CIRC_REF_NOT);
-    const size_t src = (size_t)((int64_t)inst + d);   // (not read for the constant)
+    const size_t src = (size_t)((int64_t)(inst - own) + lane);   // (not read for the constant)
     return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + src, e, n, r, one);
 }
 
 // The node table of a plan on the device (CircuitPlan::node_kind ..): one CSR over the live nodes and the pack stage's
 // pseudo-level, node k's terms term_start[k] .. term_start[k + 1] of ref / shift / weight.
+// `route` / `routes` (both NULL in a plan without route tables): the terms' route indices beside `shift`, and the
+// tables [n_routes][group] -- index k >= 1 is table k - 1, 0 none.
 struct CircNodes {
     const uint32_t *kind, *start, *ref;
     const int32_t *shift, *weight;
+    const uint32_t *route;
+    const int32_t *routes;
 };
+
+// the route table of reference i of a route-index array (NULL array: a plan without tables)
+__device__ __forceinline__ const int32_t *circ_route(const uint32_t *__restrict__ route, const int32_t *__restrict__ routes,
+                                                     size_t i, uint32_t group) {
+    const uint32_t k = route ? route[i] : 0u;
+    return k ? routes + (size_t)(k - 1) * group : nullptr;
+}
 
 // The staged inputs of one call, a1 / a2 [rows][n], b1 / b2 [rows]: rows row0 .. row0 + rows of the level whose first
 // node is `node0` of the table.  A classic node (kind 0) writes (a1, a2) = (X, Y), its two terms.  A sum node writes
@@ -1837,7 +1856,8 @@ k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
     const uint32_t k = node0 + R / instances, inst = R % instances;
     auto read = [&](uint32_t i, uint64_t one) -> uint64_t {
-        return circ_word_lane(wires, nodes.ref[i], nodes.shift[i], group, instances, inst, e, n, r, one);
+        return circ_word_lane(wires, nodes.ref[i], nodes.shift[i], circ_route(nodes.route, nodes.routes, i, group), group,
+                              instances, inst, e, n, r, one);
     };
     const uint32_t t0 = nodes.start[k], t1 = nodes.start[k + 1];
     const uint32_t kw = nodes.kind[k], kd = kw & 0xFFu;
@@ -1999,12 +2019,14 @@ __device__ __forceinline__ ulonglong2 lift_word(uint64_t x, const CrtConst *CC) 
 __global__ void __launch_bounds__(256)
 k_circ_lift(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
             const int32_t *__restrict__ out_shift, ulonglong2 *__restrict__ rawout, const CrtConst *__restrict__ CC,
-            uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+            uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group,
+            const uint32_t *__restrict__ out_route, const int32_t *__restrict__ routes) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
     const uint32_t o = R / instances, inst = R % instances;
-    const uint64_t v = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r, r / 4);
+    const uint64_t v = circ_word_lane(wires, out_ref[o], out_shift[o], circ_route(out_route, routes, o, group), group,
+                                      instances, inst, e, n, r, r / 4);
     rawout[(size_t)R * (n + 1) + e] = lift_word(v, CC);
 }
 
@@ -2016,17 +2038,19 @@ k_lwe_lift(const uint64_t *__restrict__ in, ulonglong2 *__restrict__ out, const 
         out[t] = lift_word(in[t], CC);
 }
 
-// the circuit's outputs [n_outputs][instances][n + 1], NOT, the constant and the lane shift (out_shift [n_outputs]
-// beside out_ref) applied (grid-stride: the array may hold more than 2^32 words)
+// the circuit's outputs [n_outputs][instances][n + 1], NOT, the constant and the lane shift or route (out_shift /
+// out_route [n_outputs] beside out_ref) applied (grid-stride: the array may hold more than 2^32 words)
 __global__ void __launch_bounds__(256)
 k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
                const int32_t *__restrict__ out_shift, uint64_t *__restrict__ out, size_t total, uint32_t instances,
-               uint32_t n, uint64_t r, uint32_t group) {
+               uint32_t n, uint64_t r, uint32_t group, const uint32_t *__restrict__ out_route,
+               const int32_t *__restrict__ routes) {
     const size_t per_out = (size_t)instances * (n + 1);
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t o = t / per_out, w = t % per_out;
         const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
-        out[t] = circ_word_lane(wires, out_ref[o], out_shift[o], group, instances, inst, e, n, r, r / 4);
+        out[t] = circ_word_lane(wires, out_ref[o], out_shift[o], circ_route(out_route, routes, o, group), group, instances,
+                                inst, e, n, r, r / 4);
     }
 }
 
@@ -2056,13 +2080,14 @@ k_circ_state_load(const uint64_t *__restrict__ state, const uint32_t *__restrict
 __global__ void __launch_bounds__(256)
 k_circ_next(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ next_ref,
             const int32_t *__restrict__ next_shift, const uint32_t *__restrict__ next_scale,
-            uint64_t *__restrict__ state, size_t total, uint32_t instances, uint32_t n, uint64_t r, uint32_t group) {
+            uint64_t *__restrict__ state, size_t total, uint32_t instances, uint32_t n, uint64_t r, uint32_t group,
+            const uint32_t *__restrict__ next_route, const int32_t *__restrict__ routes) {
     const size_t per_reg = (size_t)instances * (n + 1);
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t i = t / per_reg, w = t % per_reg;
         const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
-        state[t] = circ_word_lane(wires, next_ref[i], next_shift[i], group, instances, inst, e, n, r,
-                                  (r / 4) >> next_scale[i]);
+        state[t] = circ_word_lane(wires, next_ref[i], next_shift[i], circ_route(next_route, routes, i, group), group,
+                                  instances, inst, e, n, r, (r / 4) >> next_scale[i]);
     }
 }
 

@@ -338,6 +338,36 @@ function circuit_run_ct(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing}, 
     w, v
 end
 
+"""
+    circuit_create_routed(n_inputs, kind, start, ref, weight, table, outputs, group, routes, term_route, out_route)
+
+sgfhe_circuit_create_routed for a feed-forward plan without planes, shifts or registers: the CSR node arrays of
+sgfhe_circuit_create_lut_multi, `routes` a `group x n_routes` Int32 matrix (column k is table k: a source lane, 0-based,
+or -1 for the constant FALSE) and a route index per term and per output (0 = none, k = table k - 1).  Returns the plan
+handle for `circuit_run_ct`; `circuit_routes(plan)` gives its number of tables.
+"""
+function circuit_create_routed(n_inputs::Integer, kind::Vector{UInt32}, start::Vector{UInt32}, ref::Vector{UInt32},
+                               weight::Vector{Int32}, table::Vector{UInt32}, outputs::Vector{UInt32}, group::Integer,
+                               routes::Matrix{Int32}, term_route::Vector{UInt32}, out_route::Vector{UInt32})
+    size(routes, 1) == group || error("routes must have `group` rows")
+    plan = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = ccall((:sgfhe_circuit_create_routed, libsgfhe_hip), Int32,
+               (UInt32, UInt32, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt32}, Csize_t,
+                Ptr{UInt32}, Ptr{Int32}, Csize_t, UInt32, UInt32, Ptr{UInt32}, Ptr{Int32}, Ptr{UInt32}, UInt32,
+                Ptr{Int32}, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}, Ptr{Ptr{Cvoid}}),
+               n_inputs, 0, kind, start, ref, C_NULL, weight, table, length(kind), outputs, C_NULL, length(outputs),
+               group, 0, C_NULL, C_NULL, C_NULL, size(routes, 2), routes, term_route, out_route, C_NULL, plan)
+    rc == 0 || error("sgfhe_circuit_create_routed: error $rc")
+    plan[]
+end
+
+function circuit_routes(plan::Ptr{Cvoid})
+    n = Ref{UInt32}(0)
+    rc = ccall((:sgfhe_circuit_routes, libsgfhe_hip), Int32, (Ptr{Cvoid}, Ptr{UInt32}), plan, n)
+    rc == 0 || error("sgfhe_circuit_routes: error $rc")
+    Int(n[])
+end
+
 # The drop-in: same signature as src/fhe.jl:608-610, batch of one.
 SGFHE.bootstrap(hkey::HipBootstrapKey, rng::Union{AbstractRNG,Nothing},
                 bit1::EncryptedBit, bit2::EncryptedBit) =

@@ -503,79 +503,53 @@ class Circuit:
         if self._plan is None:
             from .engine import SgfheError
             L = _lib.lib()
+            arr = lambda x, t: np.ascontiguousarray(np.array(x, dtype=t))
             vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-            o = np.ascontiguousarray(np.array(self.outputs, dtype=np.uint32))
-            shift_of = lambda d: 0 if isinstance(d, tuple) else d   # (a routed reference has shift 0)
-            os_ = np.ascontiguousarray(np.array([shift_of(d) for d in self.output_shifts], dtype=np.int32))
-            h = ctypes.c_void_p()
             routes = self.route_tables
-            if self.has_wsum or self.has_lut or self.planes or self.n_regs or routes:
-                # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes, 3 for their siblings, 4 and 5
-                # for those whose table is a data plane
-                kind = np.array([{"classic": 0, "lut": 2, "sibling": 3, "data": 4, "data_sibling": 5}.get(self.kind(g), 1)
-                                 for g in range(len(self.gates))], dtype=np.uint32)
-                start = np.cumsum([0] + [len(x) for x in self.gates]).astype(np.uint32)
-                tr = np.array([ref for x in self.gates for ref in x], dtype=np.uint32)
-                index = {t: k + 1 for k, t in enumerate(routes)}   # route index: 0 none, k = table k - 1
-                ts = np.array([shift_of(d) for x in self.gate_shifts for d in x], dtype=np.int32)
-                tw = np.array([w for g in range(len(self.gates)) for w in self.weights(g)], dtype=np.int32)
-                if routes:   # (only a circuit a route survives in: every other keeps the creator it has)
-                    tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
-                                   for g in range(len(self.gates))], dtype=np.uint32)
-                    nr = np.ascontiguousarray(np.array(self.next_refs, dtype=np.uint32))
-                    ns = np.ascontiguousarray(np.array([shift_of(d) for d in self.next_shifts], dtype=np.int32))
-                    rs = np.ascontiguousarray(np.array(self.reg_scales, dtype=np.uint32))
-                    rt = np.ascontiguousarray(np.array(routes, dtype=np.int32).reshape(len(routes), self.group))
-                    tt = np.array([index.get(d, 0) for x in self.gate_shifts for d in x], dtype=np.uint32)
-                    ot = np.array([index.get(d, 0) for d in self.output_shifts], dtype=np.uint32)
-                    nt = np.array([index.get(d, 0) for d in self.next_shifts], dtype=np.uint32)
-                    rc = L.sgfhe_circuit_create_routed(self.n_inputs, self.planes, vp(kind), vp(start), vp(tr), vp(ts), vp(tw),
-                                                       vp(tb), len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
-                                                       self.n_regs, vp(nr), vp(ns), vp(rs), len(routes), vp(rt), vp(tt),
-                                                       vp(ot), vp(nt), ctypes.byref(h))
-                elif self.n_regs:   # (only a circuit with registers: every other keeps the creator it has)
-                    tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
-                                   for g in range(len(self.gates))], dtype=np.uint32)
-                    nr = np.ascontiguousarray(np.array(self.next_refs, dtype=np.uint32))
-                    ns = np.ascontiguousarray(np.array(self.next_shifts, dtype=np.int32))
-                    rs = np.ascontiguousarray(np.array(self.reg_scales, dtype=np.uint32))
-                    rc = L.sgfhe_circuit_create_seq(self.n_inputs, self.planes, vp(kind), vp(start), vp(tr), vp(ts), vp(tw),
-                                                    vp(tb), len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
-                                                    self.n_regs, vp(nr), vp(ns), vp(rs), ctypes.byref(h))
-                elif self.planes:   # (only a circuit with planes: every other keeps the creator it has)
-                    tb = np.array([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0)
-                                   for g in range(len(self.gates))], dtype=np.uint32)
-                    rc = L.sgfhe_circuit_create_data(self.n_inputs, self.planes, vp(kind), vp(start), vp(tr), vp(ts), vp(tw),
-                                                     vp(tb), len(self.gates), vp(o), vp(os_), len(self.outputs), self.group,
-                                                     ctypes.byref(h))
-                elif self.has_lut:
-                    tb = np.array([self.gate_tables.get(g, 0) for g in range(len(self.gates))], dtype=np.uint32)
-                    # (the new entry only when a sibling exists: every other circuit takes the entry it always took)
-                    create = L.sgfhe_circuit_create_lut_multi if self.has_sibling else L.sgfhe_circuit_create_lut
-                    rc = create(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), vp(tb), len(self.gates), vp(o),
-                                vp(os_), len(self.outputs), self.group, ctypes.byref(h))
-                else:
-                    rc = L.sgfhe_circuit_create_w(self.n_inputs, vp(kind), vp(start), vp(tr), vp(ts), vp(tw), len(self.gates),
-                                                  vp(o), vp(os_), len(self.outputs), self.group, ctypes.byref(h))
-            elif self.has_gate3 or self.gate_weights:
-                # two-input nodes padded with SGFHE_CIRCUIT_NONE (and a shift of 0); a sum node of two unit weights is
-                # the three-input node (x, y, FALSE)
-                pad = lambda i: FALSE_ID if i in self.gate_weights else NONE_ID
-                g = np.ascontiguousarray(np.array([tuple(x) + (pad(i),) * (3 - len(x)) for i, x in enumerate(self.gates)],
-                                                  dtype=np.uint32).reshape(-1, 3))
-                gs = np.ascontiguousarray(np.array([tuple(x) + (0,) * (3 - len(x)) for x in self.gate_shifts],
-                                                   dtype=np.int32).reshape(-1, 3))
-                rc = L.sgfhe_circuit_create3(self.n_inputs, vp(g), vp(gs), len(self.gates), vp(o), vp(os_),
-                                             len(self.outputs), self.group, ctypes.byref(h))
-            elif self.group > 1 or any(d for pair in self.gate_shifts for d in pair) or any(self.output_shifts):
-                g = np.ascontiguousarray(np.array(self.gates, dtype=np.uint32).reshape(-1, 2))
-                gs = np.ascontiguousarray(np.array(self.gate_shifts, dtype=np.int32).reshape(-1, 2))
-                rc = L.sgfhe_circuit_create_lanes(self.n_inputs, vp(g), vp(gs), len(self.gates), vp(o), vp(os_),
-                                                  len(self.outputs), self.group, ctypes.byref(h))
+            index = {t: k + 1 for k, t in enumerate(routes)}   # route index: 0 none, k = table k - 1
+            shifts = lambda ds: arr([0 if isinstance(d, tuple) else d for d in ds], np.int32)   # (a routed reference: 0)
+            route_of = lambda ds: arr([index.get(d, 0) for d in ds], np.uint32)
+            # The entry: the first whose feature the circuit has, so every circuit keeps the creator it always took
+            entry = next(name for name, has in (
+                ("_routed", routes), ("_seq", self.n_regs), ("_data", self.planes),
+                ("_lut_multi", self.has_lut and self.has_sibling), ("_lut", self.has_lut), ("_w", self.has_wsum),
+                ("3", self.has_gate3 or self.gate_weights),
+                ("_lanes", self.group > 1 or any(d for x in self.gate_shifts for d in x) or any(self.output_shifts)),
+                ("", True)) if has)
+            n, terms = len(self.gates), [d for x in self.gate_shifts for d in x]
+            o, os_ = arr(self.outputs, np.uint32), shifts(self.output_shifts)
+            outs = (vp(o), vp(os_), len(self.outputs), self.group)
+            if entry in ("", "_lanes", "3"):
+                # [n_gates][arity]; for sgfhe_circuit_create3 two-input nodes are padded with SGFHE_CIRCUIT_NONE (and a
+                # shift of 0), and a sum node of two unit weights is the three-input node (x, y, FALSE)
+                arity = 3 if entry == "3" else 2
+                pad = lambda i, x: (FALSE_ID if i in self.gate_weights else NONE_ID,) * (arity - len(x))
+                g = arr([tuple(x) + pad(i, x) for i, x in enumerate(self.gates)], np.uint32).reshape(-1, arity)
+                gs = arr([tuple(x) + (0,) * (arity - len(x)) for x in self.gate_shifts], np.int32).reshape(-1, arity)
+                args = (self.n_inputs, vp(g), vp(gs), n) + outs   # (sgfhe_circuit_create: no shifts, no group)
+                if not entry:
+                    args = (self.n_inputs, vp(g), n, vp(o), len(self.outputs))
             else:
-                g = np.ascontiguousarray(np.array(self.gates, dtype=np.uint32).reshape(-1, 2))
-                rc = L.sgfhe_circuit_create(self.n_inputs, vp(g), len(self.gates), vp(o), len(self.outputs),
-                                            ctypes.byref(h))
+                # CSR: every node's terms, kind 1 for gate3 and sum nodes, 2 for LUT nodes, 3 for their siblings, 4 and 5
+                # for those whose table is a data plane; the table array from sgfhe_circuit_create_lut on, the planes
+                # from _data on, the registers from _seq on, the routes in _routed
+                kind = arr([{"classic": 0, "lut": 2, "sibling": 3, "data": 4, "data_sibling": 5}.get(self.kind(g), 1)
+                            for g in range(n)], np.uint32)
+                start = np.cumsum([0] + [len(x) for x in self.gates]).astype(np.uint32)
+                tr, ts = arr([ref for x in self.gates for ref in x], np.uint32), shifts(terms)
+                tw = arr([w for g in range(n) for w in self.weights(g)], np.int32)
+                tb = arr([self.gate_planes[g] if g in self.gate_planes else self.gate_tables.get(g, 0) for g in range(n)],
+                         np.uint32)
+                nr, ns, rs = arr(self.next_refs, np.uint32), shifts(self.next_shifts), arr(self.reg_scales, np.uint32)
+                rt = arr(routes, np.int32).reshape(len(routes), self.group)
+                tt, ot, nt = route_of(terms), route_of(self.output_shifts), route_of(self.next_shifts)
+                data = entry in ("_data", "_seq", "_routed")
+                args = ((self.n_inputs,) + ((self.planes,) if data else ()) + (vp(kind), vp(start), vp(tr), vp(ts), vp(tw)) +
+                        ((vp(tb),) if entry != "_w" else ()) + (n,) + outs +
+                        ((self.n_regs, vp(nr), vp(ns), vp(rs)) if entry in ("_seq", "_routed") else ()) +
+                        ((len(routes), vp(rt), vp(tt), vp(ot), vp(nt)) if entry == "_routed" else ()))
+            h = ctypes.c_void_p()
+            rc = getattr(L, "sgfhe_circuit_create" + entry)(*args, ctypes.byref(h))
             if rc != 0:
                 raise SgfheError(rc, "sgfhe_circuit_create: %s" % (
                     "malformed circuit (ids, topological order, at least one output, lane shifts inside the group)"

@@ -1,8 +1,11 @@
-// Host-side planner of sgfhe_circuit_* (include/sgfhe_hip.h): validates a gate
-// graph, prunes the nodes no output depends on, levels the rest ASAP, gives every wire that is read a
-// slot of the device wire table by liveness, fixes the row and call numbering of a run, and writes every node's inputs
-// -- whichever entry the arrays came through -- into one CSR node table, which it lays with the other device tables
-// into the one image a run uploads; circuit_plain_bits evaluates a planned circuit in clear for the noise probe.
+// Host-side planner of sgfhe_circuit_* (include/sgfhe_hip.h).  Every create entry describes its
+// circuit as one CircuitSpec -- the node view, the outputs, the lane group, the registers and the routes, with the
+// kinds the entry admits as one number (CircuitNodes::max_kind) -- and circuit_plan(spec, plan) is the only way in.  It
+// runs in named stages over one working struct (circuit_detail::PlanBuild): validate (pure: a refused circuit costs no
+// allocation), prune and level ASAP, order, liveness and slots of the device wire table, LUT families, the CSR node
+// table, outputs and direct-pack jobs, registers, and the one image a run uploads.  The three lists of references --
+// node terms, outputs, next states -- go through one view (CircuitRefs), so every per-reference rule is written once.
+// circuit_plain_bits evaluates a planned circuit in clear for the noise probe.
 // The call arithmetic of a run lives here too (at the end): circuit_level_call, circuit_job_chunk, circuit_pack_runs and
 // circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
@@ -153,20 +156,20 @@ inline uint32_t wire_id(uint32_t ref) { return ref & ~CIRC_NOT; }
 
 // One view of the nodes' inputs behind every entry.  `arity` 2 or 3: the [n_gates][arity] arrays of
 // sgfhe_circuit_create_lanes / sgfhe_circuit_create3 (a third reference CIRC_NO_INPUT leaves a two-input node; with
-// one, the node is the sum node of three unit weights).  `arity` 0: the CSR arrays of sgfhe_circuit_create_w.  Term i
-// of the circuit is refs[i], shifts[i] (NULL: 0), weights[i] (NULL: 1); node g's terms are first(g) .. first(g) +
-// count(g).  `lut`: the arrays of sgfhe_circuit_create_lut, whose kind 2 marks a LUT node of table tables[g].
-// `multi`: those of sgfhe_circuit_create_lut_multi, whose kind 3 marks a sibling -- no terms, table tables[g], a further
-// table on the bootstrap of its LEADER, the nearest earlier kind-2 node.  `data`: those of sgfhe_circuit_create_data,
-// whose kinds 4 and 5 are a LUT node and a sibling with tables[g] a plane index below `n_planes`.
+// one, the node is the sum node of three unit weights).  `arity` 0: the CSR arrays of sgfhe_circuit_create_w and every
+// later entry.  Term i of the circuit is refs[i], shifts[i] (NULL: 0), weights[i] (NULL: 1); node g's terms are
+// first(g) .. first(g) + count(g).  `max_kind` is the largest kind[g] the entry admits: 1 a sum node; 2 a LUT node of
+// table tables[g] (sgfhe_circuit_create_lut); 3 a sibling -- no terms, table tables[g], a further table on the bootstrap
+// of its LEADER, the nearest earlier LUT node (sgfhe_circuit_create_lut_multi); 5 kinds 4 and 5, a LUT node and a
+// sibling with tables[g] a plane index below `n_planes` (sgfhe_circuit_create_data and later).
 struct CircuitNodes {
-    int arity;
-    const uint32_t *refs;
-    const int32_t *shifts;
+    int arity = 2;
+    const uint32_t *refs = nullptr;
+    const int32_t *shifts = nullptr;
     const uint32_t *kind = nullptr, *start = nullptr;
     const int32_t *weights = nullptr;
     const uint32_t *tables = nullptr;
-    bool lut = false, multi = false, data = false;
+    uint32_t max_kind = 1;
     uint32_t n_planes = 0;
 
     size_t first(size_t g) const { return arity ? (size_t)arity * g : start[g]; }
@@ -185,189 +188,271 @@ struct CircuitNodes {
     uint32_t kind_of(size_t g) const { return classic(g) ? 0u : (is_lut(g) ? 2u : 1u); }
     int32_t weight(size_t i) const { return weights ? weights[i] : 1; }
 };
+// the [n_gates][arity] arrays, arity 2 or 3
+inline CircuitNodes circuit_nodes_arity(int arity, const uint32_t *gates, const int32_t *gate_shift) {
+    CircuitNodes N;
+    N.arity = arity, N.refs = gates, N.shifts = gate_shift;
+    return N;
+}
+// the CSR arrays of an entry that admits kinds 0 .. max_kind (1, 2, 3 or 5; planes only at 5)
+inline CircuitNodes circuit_nodes_csr(uint32_t max_kind, const uint32_t *node_kind, const uint32_t *node_start,
+                                      const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
+                                      const uint32_t *node_table = nullptr, uint32_t n_planes = 0) {
+    CircuitNodes N;
+    N.arity = 0, N.refs = term_ref, N.shifts = term_shift, N.kind = node_kind, N.start = node_start;
+    N.weights = term_weight, N.tables = node_table, N.max_kind = max_kind, N.n_planes = n_planes;
+    return N;
+}
 
-// The registers of sgfhe_circuit_create_seq: input wires 0 .. n_regs; next_ref [n_regs] wire references validated like
-// outputs, next_shift [n_regs] (NULL: all 0), reg_scale [n_regs] (NULL: all 0; each 0, 1 or 2).
+// The registers of sgfhe_circuit_create_seq: input wires 0 .. n_regs (0: none); next_ref [n_regs] wire references
+// validated like outputs, next_shift [n_regs] (NULL: all 0), reg_scale [n_regs] (NULL: all 0; each 0, 1 or 2).
 struct CircuitRegs {
-    uint32_t n_regs;
-    const uint32_t *next_ref;
-    const int32_t *next_shift;
-    const uint32_t *reg_scale;
+    uint32_t n_regs = 0;
+    const uint32_t *next_ref = nullptr;
+    const int32_t *next_shift = nullptr;
+    const uint32_t *reg_scale = nullptr;
     uint32_t scale(uint32_t i) const { return reg_scale ? reg_scale[i] : 0u; }
 };
 
-// The lane routes of sgfhe_circuit_create_routed: routes [n_routes][group], entries in [0, group) or CIRC_ROUTE_FALSE;
-// term_route beside the term arrays, out_route [n_outputs], next_route [n_regs] (each NULL: all 0): 0 = none, k >= 1 =
-// table k - 1, and then the reference's shift must be 0.
+// The lane routes of sgfhe_circuit_create_routed: routes [n_routes][group] (n_routes 0: none), entries in [0, group) or
+// CIRC_ROUTE_FALSE; term_route beside the term arrays, out_route [n_outputs], next_route [n_regs] (each NULL: all 0):
+// 0 = none, k >= 1 = table k - 1, and then the reference's shift must be 0.
 struct CircuitRoutes {
-    uint32_t n_routes;
-    const int32_t *routes;
-    const uint32_t *term_route, *out_route, *next_route;
+    uint32_t n_routes = 0;
+    const int32_t *routes = nullptr;
+    const uint32_t *term_route = nullptr, *out_route = nullptr, *next_route = nullptr;
 };
 
-// Builds `P` from the nodes `N` (gate shifts / out_shift NULL: all 0).  `R` (NULL or n_regs 0: none): the registers; their
-// next-state references count as readers exactly as outputs do -- liveness, levels, slot lifetime -- so the plan's
-// order, levels and slots are those of the plan whose outputs are outputs ++ next_ref.  `T` (NULL: none): the lane routes;
-// nothing but the route tables of the plan sees them, and with n_routes = 0 the plan is the plan without `T`.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a
-// malformed circuit, SGFHE_ERR_OOM when an allocation fails.  Nothing throws out of it, and a refused circuit costs no
-// allocation.
-inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
-                                  const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P,
-                                  const CircuitRegs *R = nullptr, const CircuitRoutes *T = nullptr) noexcept {
-    using circuit_detail::wire_id;
-    const uint32_t *refs = N.refs;
-    const uint32_t n_regs = R ? R->n_regs : 0u;
-    const int32_t *gate_shift = N.shifts;
-    // ---- validate: every size below 2^31, wire ids below the constant, inputs name earlier wires only,
-    // every shift inside the group (in 64 bits: -INT32_MIN does not exist).  CIRC_NO_INPUT is above every wire id, so
-    // anywhere but beside a two-input node of the [n_gates][3] arrays it fails the id checks below.
-    if (n_outputs < 1 || !outputs || (n_gates && !refs) || group < 1) return SGFHE_ERR_INVALID_ARG;
-    auto shift_ok = [&](int32_t d) { return (d < 0 ? -(int64_t)d : (int64_t)d) < (int64_t)group; };
-    if (n_inputs >= 0x80000000u || n_gates >= 0x80000000u || n_outputs >= 0x80000000u) return SGFHE_ERR_INVALID_ARG;
-    const uint64_t n_wires = (uint64_t)n_inputs + 3 * (uint64_t)n_gates;
-    if (n_wires >= CIRC_FALSE) return SGFHE_ERR_INVALID_ARG;
-    if (n_regs > n_inputs || (n_regs && !R->next_ref)) return SGFHE_ERR_INVALID_ARG;
-    for (uint32_t i = 0; i < n_regs; i++) {   // (CIRC_NO_INPUT is above every wire id)
-        const uint32_t id = wire_id(R->next_ref[i]);
-        if ((id != CIRC_FALSE && id >= n_wires) || R->scale(i) > 2u) return SGFHE_ERR_INVALID_ARG;
-        if (R->next_shift && !shift_ok(R->next_shift[i])) return SGFHE_ERR_INVALID_ARG;
+// One list of references -- a node's terms, the outputs, the registers' next states -- as the per-reference rules and
+// the plan's tables read it: reference i is ref[i] at the lane shift shift[i] (NULL: 0) or through route[i] (NULL: 0).
+// It may name the constant or a wire id below `wires`, of the scale want(i): position i of a LUT node's terms (`lut`)
+// reads scale 2 - i, every other reference scale[i] (NULL: 0).
+struct CircuitRefs {
+    const uint32_t *ref;
+    const int32_t *shift;
+    const uint32_t *route;
+    size_t count;
+    uint64_t wires;
+    const uint32_t *scale;
+    bool lut;
+    int32_t shift_of(size_t i) const { return shift ? shift[i] : 0; }
+    uint32_t route_of(size_t i) const { return route ? route[i] : 0u; }
+    uint32_t want(size_t i) const { return lut ? 2u - (uint32_t)i : (scale ? scale[i] : 0u); }
+};
+
+// A circuit as every entry describes it: wires 0 .. n_inputs are inputs, node g's three wires n_inputs + 3 g + 0 / 1 / 2.
+// out_shift NULL: all 0.  The registers' next-state references count as readers exactly as outputs do -- liveness,
+// levels, slot lifetime -- so the plan's order, levels and slots are those of the plan whose outputs are outputs ++
+// next_ref.  Nothing but the route tables of the plan sees the routes, and with n_routes = 0 the plan is the plan
+// without them, image word for word.
+struct CircuitSpec {
+    uint32_t n_inputs = 0;
+    CircuitNodes nodes;
+    size_t n_gates = 0;
+    const uint32_t *outputs = nullptr;
+    const int32_t *out_shift = nullptr;
+    size_t n_outputs = 0;
+    uint32_t group = 1;
+    CircuitRegs regs;
+    CircuitRoutes routes;
+
+    uint64_t n_wires() const { return (uint64_t)n_inputs + 3 * (uint64_t)n_gates; }
+    // the three lists of references; node g's terms may name the wires before its own
+    CircuitRefs terms(size_t g) const {
+        const size_t i = nodes.first(g);
+        return {nodes.refs + i, nodes.shifts ? nodes.shifts + i : nullptr, routes.term_route ? routes.term_route + i : nullptr,
+                nodes.count(g), (uint64_t)n_inputs + 3 * (uint64_t)g, nullptr, nodes.is_lut(g)};
     }
-    if (!N.arity) {   // the CSR itself, node by node, before a term of the node is read
-        if (n_gates && (!N.kind || !N.start || !N.weights || N.start[0] != 0)) return SGFHE_ERR_INVALID_ARG;
-        if (n_gates && N.lut && !N.tables) return SGFHE_ERR_INVALID_ARG;
-        if (N.n_planes > SGFHE_CIRCUIT_MAX_PLANES) return SGFHE_ERR_INVALID_ARG;
-        auto table_ok = [&](size_t g) { return N.tables[g] < (N.is_data(g) ? N.n_planes : 256u); };
-        size_t family = 0;   // members so far of the family node g - 1 belongs to (0: it is no LUT node)
-        for (size_t g = 0; g < n_gates; g++) {
-            if (N.kind[g] > (N.data ? 5u : (N.multi ? 3u : (N.lut ? 2u : 1u))) || N.start[g + 1] < N.start[g])
-                return SGFHE_ERR_INVALID_ARG;
-            const size_t nj = N.count(g);
-            if (N.is_sibling(g)) {   // a sibling: no terms, a table, behind a LUT node or a sibling, in a family that has room
-                if (nj != 0 || !table_ok(g) || family == 0 || family >= SGFHE_LUT_MAX_TABLES) return SGFHE_ERR_INVALID_ARG;
-                family++;
-                continue;
-            }
-            family = N.is_lut(g) ? 1 : 0;
-            if (N.is_lut(g)) {   // a LUT node: three unit terms (positions 0, 1, 2), a table of 8 entries (or a plane)
-                if (nj != 3 || !table_ok(g)) return SGFHE_ERR_INVALID_ARG;
-            } else if (N.kind[g] == 0 ? nj != 2 : (nj < 1 || nj > SGFHE_CIRCUIT_MAX_TERMS)) {
-                return SGFHE_ERR_INVALID_ARG;
-            }
-            for (size_t i = N.first(g); i < N.first(g) + nj; i++) {
-                const int32_t w = N.weights[i];
-                if (N.kind[g] != 1 ? w != 1 : (w == 0 || w < -2 || w > 2)) return SGFHE_ERR_INVALID_ARG;
-            }
+    CircuitRefs outs() const { return {outputs, out_shift, routes.out_route, n_outputs, n_wires(), nullptr, false}; }
+    CircuitRefs nexts() const {   // a register is fed the constant or a wire of its own scale
+        return {regs.next_ref, regs.next_shift, routes.next_route, regs.n_regs, n_wires(), regs.reg_scale, false};
+    }
+    // The scale rule: a wire carries its bit at the codeword Dr >> scale.  Scale 0: stream inputs, every wire of a
+    // classic or sum node, wire +0 of a LUT node; wires +1 and +2 of a LUT node have scales 1 and 2; a register has the
+    // scale it was given.
+    uint32_t scale_of(uint32_t id) const {
+        if (id < n_inputs) return id < regs.n_regs ? regs.scale(id) : 0u;
+        return nodes.is_lut((id - n_inputs) / 3) ? (id - n_inputs) % 3 : 0u;
+    }
+};
+
+namespace circuit_detail {
+
+// The CSR of an arity-0 entry, node by node, before a term of any node is read: kinds the entry admits, ascending
+// starts, the term count and weights of every kind, tables and planes in range, siblings behind a LUT node in a family
+// that has room.
+inline bool csr_ok(const CircuitSpec &S) noexcept {
+    const CircuitNodes &N = S.nodes;
+    if (N.max_kind != 1 && N.max_kind != 2 && N.max_kind != 3 && N.max_kind != 5) return false;
+    if (N.n_planes > SGFHE_CIRCUIT_MAX_PLANES || (N.n_planes && N.max_kind < 5)) return false;
+    if (!S.n_gates) return true;
+    if (!N.kind || !N.start || !N.weights || N.start[0] != 0 || (N.max_kind >= 2 && !N.tables)) return false;
+    auto table_ok = [&](size_t g) { return N.tables[g] < (N.is_data(g) ? N.n_planes : 256u); };
+    size_t family = 0;   // members so far of the family node g - 1 belongs to (0: it is no LUT node)
+    for (size_t g = 0; g < S.n_gates; g++) {
+        if (N.kind[g] > N.max_kind || N.start[g + 1] < N.start[g]) return false;
+        const size_t nj = N.count(g);
+        if (N.is_sibling(g)) {   // a sibling: no terms, a table, behind a LUT node or a sibling, in a family that has room
+            if (nj != 0 || !table_ok(g) || family == 0 || family >= SGFHE_LUT_MAX_TABLES) return false;
+            family++;
+            continue;
+        }
+        family = N.is_lut(g) ? 1 : 0;
+        if (N.is_lut(g)) {   // a LUT node: three unit terms (positions 0, 1, 2), a table of 8 entries (or a plane)
+            if (nj != 3 || !table_ok(g)) return false;
+        } else if (N.kind[g] == 0 ? nj != 2 : (nj < 1 || nj > SGFHE_CIRCUIT_MAX_TERMS)) {
+            return false;
+        }
+        for (size_t i = N.first(g); i < N.first(g) + nj; i++) {
+            const int32_t w = N.weights[i];
+            if (N.kind[g] != 1 ? w != 1 : (w == 0 || w < -2 || w > 2)) return false;
         }
     }
-    for (size_t g = 0; g < n_gates; g++)
-        for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
-            const uint32_t id = wire_id(refs[i]);
-            if (id == CIRC_FALSE || id < n_inputs) continue;
-            if (id >= n_wires || (id - n_inputs) / 3 >= g) return SGFHE_ERR_INVALID_ARG;   // own or later node
-        }
-    for (size_t o = 0; o < n_outputs; o++) {
-        const uint32_t id = wire_id(outputs[o]);
-        if (id != CIRC_FALSE && id >= n_wires) return SGFHE_ERR_INVALID_ARG;
+    return true;
+}
+
+// The per-reference rules, each once, over a list `V` of a circuit whose sizes and CSR hold: the id names the constant
+// or a wire the list may read (a node: earlier wires only; CIRC_NO_INPUT is above every wire id, so anywhere but beside
+// a two-input node of the [n_gates][3] arrays it fails here), of the wanted scale; the shift stays inside the group (in
+// 64 bits: -INT32_MIN does not exist); the route index names a table, and never beside a shift.
+inline bool refs_ok(const CircuitSpec &S, const CircuitRefs &V) noexcept {
+    for (size_t i = 0; i < V.count; i++) {
+        const uint32_t id = wire_id(V.ref[i]), k = V.route_of(i);
+        const int64_t d = V.shift_of(i);
+        if (id != CIRC_FALSE && (id >= V.wires || S.scale_of(id) != V.want(i))) return false;
+        if ((d < 0 ? -d : d) >= (int64_t)S.group) return false;
+        if (k > S.routes.n_routes || (k != 0 && d != 0)) return false;
     }
-    bool scaled_reg = false;
-    for (uint32_t i = 0; i < n_regs; i++) scaled_reg = scaled_reg || R->scale(i) != 0;
-    if (N.lut || scaled_reg) {
-        // ---- the scale rule: a wire carries its bit at the codeword Dr >> scale.  Scale 0: inputs, every wire of a
-        // classic or sum node, wire +0 of a LUT node; wires +1 and +2 of a LUT node have scales 1 and 2.  Position i of
-        // a LUT node reads the constant or a wire of scale 2 - i; every other reference reads scale 0.
-        auto scale_ok = [&](uint32_t ref, uint32_t want) {
-            const uint32_t id = wire_id(ref);
-            if (id == CIRC_FALSE) return true;
-            if (id < n_inputs) return (id < n_regs ? R->scale(id) : 0u) == want;   // a register has the scale it was given
-            const uint32_t have = !N.is_lut((id - n_inputs) / 3) ? 0u : (id - n_inputs) % 3;
-            return have == want;
-        };
-        for (size_t g = 0; g < n_gates; g++)
-            for (size_t i = N.first(g), end = i + N.count(g), p = 0; i < end; i++, p++)
-                if (!scale_ok(refs[i], N.is_lut(g) ? 2u - (uint32_t)p : 0u)) return SGFHE_ERR_INVALID_ARG;
-        for (size_t o = 0; o < n_outputs; o++)
-            if (!scale_ok(outputs[o], 0u)) return SGFHE_ERR_INVALID_ARG;
-        for (uint32_t i = 0; i < n_regs; i++)   // a register is fed the constant or a wire of its own scale
-            if (!scale_ok(R->next_ref[i], R->scale(i))) return SGFHE_ERR_INVALID_ARG;
+    return true;
+}
+
+// Stage 1, validate: whether `S` is a circuit at all.  Pure -- it reads the caller's arrays and allocates nothing, so
+// a refused circuit costs no allocation.  Every size below 2^31, wire ids below the constant, the registers among the
+// inputs, every route entry a lane of the group or the fill, the CSR, then every reference of the three lists.
+inline bool valid(const CircuitSpec &S) noexcept {
+    const CircuitNodes &N = S.nodes;
+    const CircuitRegs &R = S.regs;
+    const CircuitRoutes &T = S.routes;
+    if (S.n_outputs < 1 || !S.outputs || (S.n_gates && !N.refs) || S.group < 1) return false;
+    if (S.n_inputs >= 0x80000000u || S.n_gates >= 0x80000000u || S.n_outputs >= 0x80000000u) return false;
+    if (S.n_wires() >= CIRC_FALSE) return false;
+    if (R.n_regs > S.n_inputs || (R.n_regs && !R.next_ref)) return false;
+    for (uint32_t i = 0; i < R.n_regs; i++)
+        if (R.scale(i) > 2u) return false;
+    if (T.n_routes > SGFHE_CIRCUIT_MAX_ROUTES || (T.n_routes && !T.routes)) return false;
+    for (size_t i = 0; i < (size_t)T.n_routes * S.group; i++)
+        if (T.routes[i] < CIRC_ROUTE_FALSE || T.routes[i] >= (int64_t)S.group) return false;
+    if (!N.arity && !csr_ok(S)) return false;
+    for (size_t g = 0; g < S.n_gates; g++)
+        if (!refs_ok(S, S.terms(g))) return false;
+    return refs_ok(S, S.outs()) && refs_ok(S, S.nexts());
+}
+
+// What the stages behind `valid` share: the circuit, the plan they fill, and the per-node and per-wire working tables.
+// Each stage reads what the stages before it left; any of them may throw std::bad_alloc (std::length_error: `image`).
+struct PlanBuild {
+    const CircuitSpec &S;
+    const CircuitNodes &N;
+    CircuitPlan &P;
+    const uint32_t NG, n_inputs;
+    static constexpr uint32_t UNREAD = 0;   // (no wire is read at level 0)
+    uint32_t END = 0;                       // the "level" of the readers behind the last one: outputs and next states
+    std::vector<uint32_t> leader;           // [n_gates]: a sibling's leader, every other node itself
+    std::vector<uint8_t> live;              // [n_gates]: an output or next state reaches the node
+    std::vector<uint32_t> last_read;        // [wires]: the last level that reads the wire, UNREAD .. END
+    std::vector<uint32_t> slot_of;          // [wires]: CIRC_NONE for a wire nothing reads
+    std::vector<uint32_t> sib_index;        // [n_gates]: a live sibling's index in fam_node
+    std::vector<uint32_t> rank_of;          // [n_gates]: a live node's index in `order`
+
+    PlanBuild(const CircuitSpec &S, CircuitPlan &P)
+        : S(S), N(S.nodes), P(P), NG((uint32_t)S.n_gates), n_inputs(S.n_inputs) {}
+
+    // producing node of a wire, -1 for inputs and the constant
+    int64_t node_of(uint32_t id) const {
+        return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
     }
-    for (size_t g = 0; gate_shift && g < n_gates; g++)   // (the shift beside CIRC_NO_INPUT is ignored)
-        for (size_t i = N.first(g), end = i + N.count(g); i < end; i++)
-            if (!shift_ok(gate_shift[i])) return SGFHE_ERR_INVALID_ARG;
-    for (size_t o = 0; out_shift && o < n_outputs; o++)
-        if (!shift_ok(out_shift[o])) return SGFHE_ERR_INVALID_ARG;
-    // ---- the routes: every entry a lane of the group or the fill, every index a table, and never beside a shift
-    const uint32_t n_routes = T ? T->n_routes : 0u;
-    if (T) {
-        if (n_routes > SGFHE_CIRCUIT_MAX_ROUTES || (n_routes && !T->routes)) return SGFHE_ERR_INVALID_ARG;
-        for (size_t i = 0; i < (size_t)n_routes * group; i++)
-            if (T->routes[i] < CIRC_ROUTE_FALSE || T->routes[i] >= (int64_t)group) return SGFHE_ERR_INVALID_ARG;
-        auto route_ok = [&](const uint32_t *route, const int32_t *shift, size_t i) {
-            return !route || (route[i] <= n_routes && (route[i] == 0 || !shift || shift[i] == 0));
-        };
-        for (size_t g = 0; g < n_gates; g++)
-            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++)
-                if (!route_ok(T->term_route, gate_shift, i)) return SGFHE_ERR_INVALID_ARG;
-        for (size_t o = 0; o < n_outputs; o++)
-            if (!route_ok(T->out_route, out_shift, o)) return SGFHE_ERR_INVALID_ARG;
-        for (uint32_t i = 0; i < n_regs; i++)
-            if (!route_ok(T->next_route, R->next_shift, i)) return SGFHE_ERR_INVALID_ARG;
+    // the live siblings of node g, in ascending index
+    template <class F> void each_sibling(uint32_t g, F &&fn) const {
+        for (uint32_t h = g + 1; h < NG && N.is_sibling(h); h++)
+            if (live[h]) fn(h);
     }
-    try {
-        P = CircuitPlan();
-        P.n_inputs = n_inputs;
-        P.n_gates = (uint32_t)n_gates;
-        P.n_outputs = (uint32_t)n_outputs;
-        P.group = group;
-        P.n_planes = N.n_planes;
-        P.n_regs = n_regs;
-        P.n_routes = n_routes;
-        if (n_routes) P.routes.assign(T->routes, T->routes + (size_t)n_routes * group);
-        const uint32_t NG = (uint32_t)n_gates;
-        auto node_of = [&](uint32_t id) -> int64_t {   // producing node of a wire, -1 for inputs and the constant
-            return (id == CIRC_FALSE || id < n_inputs) ? -1 : (int64_t)((id - n_inputs) / 3);
-        };
-        // ---- prune: a node is live when an output reaches it (walk back from the outputs, last node first); a leader
-        // is live when any of its siblings is
-        std::vector<uint32_t> leader(NG);
+    // the wires of a list, the constant left out
+    template <class F> static void each_wire(const CircuitRefs &V, F &&fn) {
+        for (size_t i = 0; i < V.count; i++)
+            if (wire_id(V.ref[i]) != CIRC_FALSE) fn(wire_id(V.ref[i]));
+    }
+    // Outputs and next states read at END: the wires both lists name (the feedback reads at the end of the step)
+    template <class F> void each_end_wire(F &&fn) const {
+        each_wire(S.outs(), fn);
+        each_wire(S.nexts(), fn);
+    }
+    // Reference i of a list as the plan's tables hold it: the slot for the wire id (NOT kept); shift and route dropped
+    // on a reference to the constant, and no route kept in a plan without tables.  A shifted reference reads other ROWS
+    // of the slot it names, nothing else: the wire is of an earlier level (or an input), so all its rows are written
+    // before the reading level's first call in stream order, and its slot is held until the last level that reads the
+    // wire ends, whichever instance is read.  The slot rule therefore knows no shift.
+    struct Ref {
+        uint32_t ref;
+        int32_t shift;
+        uint32_t route;
+    };
+    Ref slot_ref(const CircuitRefs &V, size_t i) const {
+        const uint32_t id = wire_id(V.ref[i]);
+        if (id == CIRC_FALSE) return {V.ref[i], 0, 0u};
+        return {slot_of[id] | (V.ref[i] & CIRC_NOT), V.shift_of(i), P.n_routes ? V.route_of(i) : 0u};
+    }
+    // the same reference as a probe row (CircuitPlan::term_row)
+    uint32_t row_ref(uint32_t ref) const {
+        const uint32_t id = wire_id(ref);
+        const int64_t g = node_of(id);
+        if (g < 0) return ref;
+        const size_t node_row = N.is_sibling((size_t)g) ? P.live() + sib_index[g] : rank_of[g];
+        return (uint32_t)(n_inputs + 3 * node_row + (id - n_inputs) % 3) | (ref & CIRC_NOT);
+    }
+    void term(const Ref &r, int32_t weight) {
+        P.term_ref.push_back(r.ref);
+        P.term_shift.push_back(r.shift);
+        P.term_weight.push_back(weight);
+        if (P.n_routes) P.term_route.push_back(r.route);
+    }
+
+    // Stage 2, prune and level: the plan's scalars; a node is live when an output or next state reaches it (walk back,
+    // last node first), a leader when any of its siblings is; level ASAP = 1 + the largest level of the node's input
+    // nodes (inputs and the constant: 0), a sibling has its leader's level.
+    void prune_and_level() {
+        P.n_inputs = n_inputs, P.n_gates = NG, P.n_outputs = (uint32_t)S.n_outputs;
+        P.group = S.group, P.n_planes = N.n_planes, P.n_regs = S.regs.n_regs, P.n_routes = S.routes.n_routes;
+        if (P.n_routes) P.routes.assign(S.routes.routes, S.routes.routes + (size_t)P.n_routes * P.group);
+        leader.resize(NG);
         for (uint32_t g = 0; g < NG; g++) leader[g] = N.is_sibling(g) ? leader[g - 1] : g;
-        std::vector<uint8_t> live(NG, 0);
-        for (size_t o = 0; o < n_outputs; o++) {
-            const int64_t g = node_of(wire_id(outputs[o]));
-            if (g >= 0) live[g] = 1;
-        }
-        for (uint32_t i = 0; i < n_regs; i++) {
-            const int64_t g = node_of(wire_id(R->next_ref[i]));
-            if (g >= 0) live[g] = 1;
-        }
+        live.assign(NG, 0);
+        auto reach = [&](uint32_t id) {
+            if (node_of(id) >= 0) live[node_of(id)] = 1;
+        };
+        each_end_wire(reach);
         for (uint32_t g = NG; g-- > 0;) {
             if (!live[g]) continue;
             live[leader[g]] = 1;
-            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
-                const int64_t h = node_of(wire_id(refs[i]));
-                if (h >= 0) live[h] = 1;
-            }
+            each_wire(S.terms(g), reach);
         }
-        // ---- level ASAP: 1 + the largest level of its input nodes (inputs and the constant: 0); a sibling has its
-        // leader's level and takes no row
         P.level.assign(NG, 0);
-        auto takes_row = [&](uint32_t g) { return P.level[g] && !N.is_sibling(g); };
-        // the live siblings of node g, in ascending index
-        auto each_sibling = [&](uint32_t g, auto &&fn) {
-            for (uint32_t h = g + 1; h < NG && N.is_sibling(h); h++)
-                if (live[h]) fn(h);
-        };
         for (uint32_t g = 0; g < NG; g++) {
             if (!live[g]) continue;
             if (N.is_sibling(g)) { P.level[g] = P.level[leader[g]]; continue; }
             uint32_t L = 0;
-            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
-                const int64_t h = node_of(wire_id(refs[i]));
-                if (h >= 0) L = std::max(L, P.level[h]);
-            }
+            each_wire(S.terms(g), [&](uint32_t id) {
+                if (node_of(id) >= 0) L = std::max(L, P.level[node_of(id)]);
+            });
             P.level[g] = L + 1;
             P.levels = std::max(P.levels, L + 1);
         }
-        // ---- order: level by level, ascending node index within a level (counting sort)
+        END = P.levels + 1;
+    }
+
+    // Stage 3, order: the live nodes that take a row (no sibling does), level by level, ascending node index within a
+    // level (counting sort); level_start, widest, and every live node's rank.
+    void order() {
+        auto takes_row = [&](uint32_t g) { return P.level[g] && !N.is_sibling(g); };
         P.level_start.assign((size_t)P.levels + 2, 0);
         for (uint32_t g = 0; g < NG; g++)
             if (takes_row(g)) P.level_start[P.level[g] + 1]++;
@@ -376,58 +461,50 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.level_start[L + 1] += P.level_start[L];
         }
         P.order.resize(P.level_start[P.levels + 1]);
-        {
-            std::vector<uint32_t> fill(P.level_start.begin(), P.level_start.end() - 1);
-            for (uint32_t g = 0; g < NG; g++)
-                if (takes_row(g)) P.order[fill[P.level[g]]++] = g;
-        }
-        // ---- liveness: the last level that reads each wire (outputs: beyond the last level)
-        const uint32_t END = P.levels + 1;
-        constexpr uint32_t UNREAD = 0;   // no wire is read at level 0
-        std::vector<uint32_t> last_read((size_t)n_wires, UNREAD);
+        std::vector<uint32_t> fill(P.level_start.begin(), P.level_start.end() - 1);
+        for (uint32_t g = 0; g < NG; g++)
+            if (takes_row(g)) P.order[fill[P.level[g]]++] = g;
+        rank_of.assign(NG, CIRC_NONE);
+        for (size_t k = 0; k < P.live(); k++) rank_of[P.order[k]] = (uint32_t)k;
+    }
+
+    // Stage 4, liveness and slots: the last level that reads each wire; a wire written at level L takes the lowest free
+    // slot, and a slot is free again after the last level that reads its wire (so no call of level L overwrites what a
+    // later call of L gathers).  A sibling's wires are written by its leader's call: slots of the same level.
+    void slots() {
+        last_read.assign((size_t)S.n_wires(), UNREAD);
         for (uint32_t g : P.order)
-            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
-                const uint32_t id = wire_id(refs[i]);
-                if (id != CIRC_FALSE) last_read[id] = std::max(last_read[id], P.level[g]);
-            }
-        for (size_t o = 0; o < n_outputs; o++) {
-            const uint32_t id = wire_id(outputs[o]);
-            if (id != CIRC_FALSE) last_read[id] = END;
-        }
-        for (uint32_t i = 0; i < n_regs; i++) {   // the feedback reads at the end of the step
-            const uint32_t id = wire_id(R->next_ref[i]);
-            if (id != CIRC_FALSE) last_read[id] = END;
-        }
-        // ---- slots: a wire written at level L takes the lowest free slot; a slot is free again after the
-        // last level that reads its wire (so no call of level L overwrites what a later call of L gathers)
-        std::vector<uint32_t> slot_of((size_t)n_wires, CIRC_NONE);
+            each_wire(S.terms(g), [&](uint32_t id) { last_read[id] = std::max(last_read[id], P.level[g]); });
+        each_end_wire([&](uint32_t id) { last_read[id] = END; });
+        slot_of.assign((size_t)S.n_wires(), CIRC_NONE);
         std::vector<std::vector<uint32_t>> release((size_t)END + 1);   // slots freed after level L
         std::priority_queue<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> free_slots;
         auto take = [&](uint32_t id) {
+            if (last_read[id] == UNREAD) return;
             uint32_t s;
             if (free_slots.empty()) s = P.slots++;
             else { s = free_slots.top(); free_slots.pop(); }
             slot_of[id] = s;
             release[last_read[id]].push_back(s);
         };
-        P.input_slot.assign(n_inputs, CIRC_NONE);
-        for (uint32_t i = 0; i < n_inputs; i++)
-            if (last_read[i] != UNREAD) { take(i); P.input_slot[i] = slot_of[i]; }
+        auto take_node = [&](uint32_t g) {
+            for (uint32_t w = 0; w < 3; w++) take(n_inputs + 3 * g + w);
+        };
+        for (uint32_t i = 0; i < n_inputs; i++) take(i);
+        P.input_slot.assign(slot_of.begin(), slot_of.begin() + n_inputs);
         for (uint32_t L = 1; L <= P.levels; L++) {
             for (uint32_t s : release[L - 1]) free_slots.push(s);
-            auto take_read = [&](uint32_t g) {
-                for (uint32_t w = 0; w < 3; w++) {
-                    const uint32_t id = n_inputs + 3 * g + w;
-                    if (last_read[id] != UNREAD) take(id);
-                }
-            };
             for (uint32_t k = P.level_start[L]; k < P.level_start[L + 1]; k++) {
-                take_read(P.order[k]);
-                each_sibling(P.order[k], take_read);   // written by the leader's call: slots of the same level
+                take_node(P.order[k]);
+                each_sibling(P.order[k], take_node);
             }
         }
-        // ---- the families: every live node's live siblings, their tables and slots; a sibling's probe rows
-        std::vector<uint32_t> sib_index(NG, CIRC_NONE);
+    }
+
+    // Stage 5, families: every live node's live siblings as one CSR over `order` -- their tables and slots, and their
+    // numbering (fam_node, which numbers a sibling's probe rows).
+    void families() {
+        sib_index.assign(NG, CIRC_NONE);
         P.fam_start.assign(P.live() + 1, 0);
         for (size_t k = 0; k < P.live(); k++) {
             each_sibling(P.order[k], [&](uint32_t h) {
@@ -438,88 +515,57 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             });
             P.fam_start[k + 1] = (uint32_t)P.fam_node.size();
         }
-        // ---- the node table: every live node's terms in the caller's order.  A shifted reference reads other ROWS of
-        // the slot it names, nothing else: the wire is of an earlier level (or an input), so all its rows are written
-        // before the reading level's first call in stream order, and its slot is held until the last level that reads
-        // the wire ends, whichever instance is read.  The slot rule above therefore needs no change.
-        auto slot_ref = [&](uint32_t ref) -> uint32_t {
-            const uint32_t id = wire_id(ref);
-            return (id == CIRC_FALSE ? CIRC_FALSE : slot_of[id]) | (ref & CIRC_NOT);
-        };
-        auto shift_of = [&](uint32_t ref, const int32_t *tab, size_t i) -> int32_t {
-            return tab && wire_id(ref) != CIRC_FALSE ? tab[i] : 0;
-        };
-        std::vector<uint32_t> rank_of(NG, CIRC_NONE);   // node -> index in `order`
-        for (size_t k = 0; k < P.live(); k++) rank_of[P.order[k]] = (uint32_t)k;
-        auto row_ref = [&](uint32_t ref) -> uint32_t {
-            const uint32_t id = wire_id(ref);
-            const int64_t g = node_of(id);
-            if (g < 0) return id | (ref & CIRC_NOT);
-            const size_t node_row = N.is_sibling((size_t)g) ? P.live() + sib_index[g] : rank_of[g];
-            return (uint32_t)(n_inputs + 3 * node_row + (id - n_inputs) % 3) | (ref & CIRC_NOT);
-        };
-        // (a route, like a shift, is dropped on a reference to the constant; no route array is kept without tables)
-        auto route_of = [&](uint32_t ref, const uint32_t *tab, size_t i) -> uint32_t {
-            return n_routes && tab && wire_id(ref) != CIRC_FALSE ? tab[i] : 0u;
-        };
-        auto term = [&](uint32_t ref, int32_t shift, int32_t weight, uint32_t route) {
-            P.term_ref.push_back(ref);
-            P.term_shift.push_back(shift);
-            P.term_weight.push_back(weight);
-            if (n_routes) P.term_route.push_back(route);
-        };
+    }
+
+    // Stage 6, node table: every live node's kind word, its terms in the caller's order (as slot references and as
+    // probe rows), the slots of its three wires, and the running counts of sum and LUT nodes.
+    void node_table() {
         P.out_slot.resize(3 * P.live());
         P.sum_before.assign(P.live() + 1, 0);
         P.lut_before.assign(P.live() + 1, 0);
         for (size_t k = 0; k < P.live(); k++) {
             const size_t g = P.order[k];
+            const CircuitRefs V = S.terms(g);
             P.node_kind.push_back(N.kind_of(g) | (N.is_lut(g) ? N.table_word(g, 8) : 0u));
             P.term_start.push_back((uint32_t)P.term_ref.size());
-            for (size_t i = N.first(g), end = i + N.count(g); i < end; i++) {
-                term(slot_ref(refs[i]), shift_of(refs[i], gate_shift, i), N.weight(i),
-                     route_of(refs[i], T ? T->term_route : nullptr, i));
-                P.term_row.push_back(row_ref(refs[i]));
+            for (size_t i = 0; i < V.count; i++) {
+                term(slot_ref(V, i), N.weight(N.first(g) + i));
+                P.term_row.push_back(row_ref(V.ref[i]));
             }
             for (uint32_t w = 0; w < 3; w++) P.out_slot[3 * k + w] = slot_of[n_inputs + 3 * g + w];
             P.sum_before[k + 1] = P.sum_before[k] + (P.kind(k) == 1);
             P.lut_before[k + 1] = P.lut_before[k] + (P.kind(k) == 2);
         }
-        // ---- outputs, and the pack stage's pseudo-level: node live() + o is (TRUE, output o), the pair of
-        // fhe.jl:669-673
-        P.out_ref.resize(n_outputs);
-        P.out_shift.resize(n_outputs);
-        P.out_node.assign(n_outputs, CIRC_NONE);
-        P.out_gate.assign(n_outputs, 0);
-        for (size_t o = 0; o < n_outputs; o++) {
-            P.out_ref[o] = slot_ref(outputs[o]);
-            P.out_shift[o] = shift_of(outputs[o], out_shift, o);
+    }
+
+    // Stage 7, outputs and jobs: the outputs as slot references; the pack stage's pseudo-level behind the node table --
+    // node live() + o is (TRUE, output o), the pair of fhe.jl:669-673; which outputs are gate rows of a level call
+    // (out_node, out_gate), and those as direct-pack jobs by producing node.
+    void outputs_and_jobs() {
+        const CircuitRefs V = S.outs();
+        P.out_node.assign(V.count, CIRC_NONE);
+        P.out_gate.assign(V.count, 0);
+        for (size_t o = 0; o < V.count; o++) {
+            const Ref r = slot_ref(V, o);
+            P.out_ref.push_back(r.ref);
+            P.out_shift.push_back(r.shift);
+            if (P.n_routes) P.out_route.push_back(r.route);
             P.node_kind.push_back(0u);
             P.term_start.push_back((uint32_t)P.term_ref.size());
-            const uint32_t route = route_of(outputs[o], T ? T->out_route : nullptr, o);
-            if (n_routes) P.out_route.push_back(route);
-            term(CIRC_FALSE | CIRC_NOT, 0, 1, 0u);
-            term(P.out_ref[o], P.out_shift[o], 1, route);
-            const uint32_t id = wire_id(outputs[o]);
+            term({CIRC_FALSE | CIRC_NOT, 0, 0u}, 1);
+            term(r, 1);
+            const uint32_t id = wire_id(V.ref[o]);
             const int64_t g = node_of(id);
             // (a routed output is no gate row in order, even under the identity table: refreshed or lifted, as a shifted one)
-            if (g < 0 || P.out_shift[o] != 0 || route != 0) continue;
+            if (g < 0 || r.shift != 0 || r.route != 0) continue;
             if ((id - n_inputs) % 3 == 2 && !N.classic((size_t)g)) continue;   // LOW: linear over Z_r, no gate row
             if (N.is_lut((size_t)g)) continue;   // wire +0 of a LUT node: refreshed or lifted, as a LOW wire is
             P.out_node[o] = rank_of[g];
             P.out_gate[o] = (id - n_inputs) % 3;
         }
         P.term_start.push_back((uint32_t)P.term_ref.size());
-        // ---- the registers' next states as slot references
-        for (uint32_t i = 0; i < n_regs; i++) {
-            P.next_ref.push_back(slot_ref(R->next_ref[i]));
-            P.next_shift.push_back(shift_of(R->next_ref[i], R->next_shift, i));
-            P.reg_scale.push_back(R->scale(i));
-            P.reg_index.push_back(i);
-            if (n_routes) P.next_route.push_back(route_of(R->next_ref[i], T ? T->next_route : nullptr, i));
-        }
-        // ---- the direct-pack jobs, by producing node
         std::vector<uint32_t> byk;
-        for (uint32_t o = 0; o < n_outputs; o++)
+        for (uint32_t o = 0; o < V.count; o++)
             if (P.out_node[o] != CIRC_NONE) byk.push_back(o);
         std::sort(byk.begin(), byk.end(), [&](uint32_t x, uint32_t y) {   // (outputs of one node in ascending index)
             return P.out_node[x] != P.out_node[y] ? P.out_node[x] < P.out_node[y] : x < y;
@@ -529,7 +575,23 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.job_k.push_back(k);
             P.jobs.insert(P.jobs.end(), {o, k - P.level_start[L], P.out_gate[o] | (P.out_ref[o] & CIRC_NOT)});
         }
-        // ---- the image of the device tables
+    }
+
+    // Stage 8, registers: the next states as slot references, each register's scale and its index in the state buffer.
+    void registers() {
+        const CircuitRefs V = S.nexts();
+        for (uint32_t i = 0; i < V.count; i++) {
+            const Ref r = slot_ref(V, i);
+            P.next_ref.push_back(r.ref);
+            P.next_shift.push_back(r.shift);
+            P.reg_scale.push_back(S.regs.scale(i));
+            P.reg_index.push_back(i);
+            if (P.n_routes) P.next_route.push_back(r.route);
+        }
+    }
+
+    // Stage 9, image: every device table in the order CircuitPlan::image states, each at its offset in P.at.
+    void image() {
         auto place = [&](const auto &tab) -> uint32_t {
             const size_t at = P.image.size();
             if (at + tab.size() >= 0x100000000ull) throw std::length_error("circuit image");
@@ -537,7 +599,7 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             return (uint32_t)at;
         };
         P.image.reserve(P.node_kind.size() + P.term_start.size() + 3 * P.term_ref.size() + P.out_slot.size() +
-                        2 * n_outputs + n_inputs + P.jobs.size() + 4 * (size_t)n_regs + P.routes.size() +
+                        2 * (size_t)P.n_outputs + n_inputs + P.jobs.size() + 4 * (size_t)P.n_regs + P.routes.size() +
                         P.term_route.size() + P.out_route.size() + P.next_route.size());
         P.at.node_kind = place(P.node_kind);
         P.at.term_start = place(P.term_start);
@@ -553,127 +615,44 @@ inline int32_t circuit_plan_nodes(uint32_t n_inputs, const CircuitNodes &N, size
             P.at.fam_start = place(P.fam_start);
             P.at.fam_entry = place(P.fam_entry);
         }
-        if (n_regs) {
+        if (P.n_regs) {
             P.at.next_ref = place(P.next_ref);
             P.at.next_shift = place(P.next_shift);
             P.at.next_scale = place(P.reg_scale);
             P.at.reg_index = place(P.reg_index);
         }
-        if (n_routes) {
+        if (P.n_routes) {
             P.at.routes = place(P.routes);
             P.at.term_route = place(P.term_route);
             P.at.out_route = place(P.out_route);
-            if (n_regs) P.at.next_route = place(P.next_route);
+            if (P.n_regs) P.at.next_route = place(P.next_route);
         }
         P.at.words = (uint32_t)P.image.size();
+    }
+};
+
+}  // namespace circuit_detail
+
+// Builds `P` from the circuit `S`, stage by stage.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a malformed circuit (`P`
+// is not touched), SGFHE_ERR_OOM when an allocation fails (`P` is reset).  Nothing throws out of it.
+inline int32_t circuit_plan(const CircuitSpec &S, CircuitPlan &P) noexcept {
+    if (!circuit_detail::valid(S)) return SGFHE_ERR_INVALID_ARG;
+    try {
+        P = CircuitPlan();
+        circuit_detail::PlanBuild B(S, P);
+        B.prune_and_level();
+        B.order();
+        B.slots();
+        B.families();
+        B.node_table();
+        B.outputs_and_jobs();
+        B.registers();
+        B.image();
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
         P = CircuitPlan();
         return SGFHE_ERR_OOM;
     }
     return SGFHE_OK;
-}
-
-// The arrays of sgfhe_circuit_create3 (`arity` 3: gates and gate_shift are [n_gates][3], and a third reference
-// CIRC_NO_INPUT makes the node a two-input node) or of sgfhe_circuit_create_lanes (`arity` 2: [n_gates][2], every node
-// a two-input node).
-inline int32_t circuit_plan_arity(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
-                                  int arity, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
-                                  uint32_t group, CircuitPlan &P) noexcept {
-    const CircuitNodes N = {arity, gates, gate_shift};
-    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
-}
-
-// The arrays of sgfhe_circuit_create_w.
-inline int32_t circuit_plan_w(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
-                              const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
-                              size_t n_gates, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
-                              uint32_t group, CircuitPlan &P) noexcept {
-    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight};
-    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
-}
-
-// The arrays of sgfhe_circuit_create_lut: those of sgfhe_circuit_create_w, kind 2 for a LUT node, and node_table.
-inline int32_t circuit_plan_lut(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
-                                const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
-                                const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
-                                const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
-    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true};
-    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
-}
-
-// The arrays of sgfhe_circuit_create_lut_multi: those of sgfhe_circuit_create_lut, and kind 3 for a sibling.
-inline int32_t circuit_plan_lut_multi(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
-                                      const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
-                                      const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
-                                      const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
-    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true, true};
-    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
-}
-
-// The arrays of sgfhe_circuit_create_data: those of sgfhe_circuit_create_lut_multi, kinds 4 and 5 for a data LUT node and
-// a data sibling, and the number of planes.
-inline CircuitNodes circuit_nodes_data(uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
-                                       const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
-                                       const uint32_t *node_table) {
-    CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true, true};
-    N.data = true;
-    N.n_planes = n_planes;
-    return N;
-}
-inline int32_t circuit_plan_data(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
-                                 const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
-                                 const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
-                                 const int32_t *out_shift, size_t n_outputs, uint32_t group, CircuitPlan &P) noexcept {
-    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
-    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P);
-}
-
-// The arrays of sgfhe_circuit_create_seq: those of sgfhe_circuit_create_data, and the registers.  With n_regs = 0 the
-// plan is the sgfhe_circuit_create_data plan, field for field.
-inline int32_t circuit_plan_seq(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
-                                const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
-                                const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
-                                const int32_t *out_shift, size_t n_outputs, uint32_t group, uint32_t n_regs,
-                                const uint32_t *next_ref, const int32_t *next_shift, const uint32_t *reg_scale,
-                                CircuitPlan &P) noexcept {
-    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
-    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
-    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P, &R);
-}
-
-// The arrays of sgfhe_circuit_create_routed: those of sgfhe_circuit_create_seq, and the lane routes.  With n_routes = 0
-// the plan is the sgfhe_circuit_create_seq plan, image word for word.
-inline int32_t circuit_plan_routed(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind, const uint32_t *node_start,
-                                   const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
-                                   const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
-                                   const int32_t *out_shift, size_t n_outputs, uint32_t group, uint32_t n_regs,
-                                   const uint32_t *next_ref, const int32_t *next_shift, const uint32_t *reg_scale,
-                                   uint32_t n_routes, const int32_t *routes, const uint32_t *term_route,
-                                   const uint32_t *out_route, const uint32_t *next_route, CircuitPlan &P) noexcept {
-    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
-    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
-    const CircuitRoutes T = {n_routes, routes, term_route, out_route, next_route};
-    return circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, P, &R, &T);
-}
-
-// The arrays of sgfhe_circuit_create_lanes.
-inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
-                            const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
-                            CircuitPlan &P) noexcept {
-    return circuit_plan_arity(n_inputs, gates, gate_shift, n_gates, 2, outputs, out_shift, n_outputs, group, P);
-}
-
-// The arrays of sgfhe_circuit_create3.
-inline int32_t circuit_plan3(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
-                             const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
-                             CircuitPlan &P) noexcept {
-    return circuit_plan_arity(n_inputs, gates, gate_shift, n_gates, 3, outputs, out_shift, n_outputs, group, P);
-}
-
-// The arrays of sgfhe_circuit_create: no shifts, group 1.
-inline int32_t circuit_plan(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
-                            size_t n_outputs, CircuitPlan &P) noexcept {
-    return circuit_plan(n_inputs, gates, nullptr, n_gates, outputs, nullptr, n_outputs, 1u, P);
 }
 
 // The circuit in clear over `instances`, for the noise probe (sgfhe_circuit_run_probe): the plaintext bit of every

@@ -2969,15 +2969,13 @@ int32_t sgfhe_timing_read(sgfhe_ctx *c, double *stats, int reset) {
 
 // ---- gate circuits (csrc/circuit.h plans) ---------------------------------------
 
-// every entry: `N` views its node arrays (csrc/circuit.h).  A refused circuit allocates nothing: the plan is
-// validated into a local first
-static int32_t circuit_create(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
-                              const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out,
-                              const CircuitRegs *regs = nullptr, const CircuitRoutes *routes = nullptr) {
+// Every entry fills one CircuitSpec (csrc/circuit.h) from its arrays.  A refused circuit allocates nothing: the planner
+// validates before it builds, and into a local
+static int32_t circuit_create(const CircuitSpec &S, sgfhe_circuit **out) {
     if (!out) return SGFHE_ERR_INVALID_ARG;
     *out = nullptr;
     CircuitPlan plan;
-    const int32_t rc = circuit_plan_nodes(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, plan, regs, routes);
+    const int32_t rc = circuit_plan(S, plan);
     if (rc) return rc;
     sgfhe_circuit *c = new (std::nothrow) sgfhe_circuit();
     if (!c) return SGFHE_ERR_OOM;
@@ -2986,49 +2984,62 @@ static int32_t circuit_create(uint32_t n_inputs, const CircuitNodes &N, size_t n
     return SGFHE_OK;
 }
 
+// what every entry has: the inputs, the nodes, the outputs and the lane group
+static CircuitSpec circuit_spec(uint32_t n_inputs, const CircuitNodes &N, size_t n_gates, const uint32_t *outputs,
+                                const int32_t *out_shift, size_t n_outputs, uint32_t group) {
+    CircuitSpec S;
+    S.n_inputs = n_inputs, S.nodes = N, S.n_gates = n_gates;
+    S.outputs = outputs, S.out_shift = out_shift, S.n_outputs = n_outputs, S.group = group;
+    return S;
+}
+
 int32_t sgfhe_circuit_create_lanes(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                                    const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
                                    sgfhe_circuit **out) {
-    return circuit_create(n_inputs, {2, gates, gate_shift}, n_gates, outputs, out_shift, n_outputs, group, out);
+    const CircuitNodes N = circuit_nodes_arity(2, gates, gate_shift);
+    return circuit_create(circuit_spec(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group), out);
 }
 
 int32_t sgfhe_circuit_create3(uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift, size_t n_gates,
                               const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
                               sgfhe_circuit **out) {
-    return circuit_create(n_inputs, {3, gates, gate_shift}, n_gates, outputs, out_shift, n_outputs, group, out);
+    const CircuitNodes N = circuit_nodes_arity(3, gates, gate_shift);
+    return circuit_create(circuit_spec(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group), out);
 }
 
 int32_t sgfhe_circuit_create_w(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
                                const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
                                size_t n_gates, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
                                uint32_t group, sgfhe_circuit **out) {
-    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight};
-    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
+    const CircuitNodes N = circuit_nodes_csr(1, node_kind, node_start, term_ref, term_shift, term_weight);
+    return circuit_create(circuit_spec(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group), out);
 }
 
 int32_t sgfhe_circuit_create_lut(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
                                  const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
                                  const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
                                  const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out) {
-    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true};
-    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
+    const CircuitNodes N = circuit_nodes_csr(2, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    return circuit_create(circuit_spec(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group), out);
 }
 
 int32_t sgfhe_circuit_create_lut_multi(uint32_t n_inputs, const uint32_t *node_kind, const uint32_t *node_start,
                                        const uint32_t *term_ref, const int32_t *term_shift, const int32_t *term_weight,
                                        const uint32_t *node_table, size_t n_gates, const uint32_t *outputs,
                                        const int32_t *out_shift, size_t n_outputs, uint32_t group, sgfhe_circuit **out) {
-    const CircuitNodes N = {0, term_ref, term_shift, node_kind, node_start, term_weight, node_table, true, true};
-    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
+    const CircuitNodes N = circuit_nodes_csr(3, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
+    return circuit_create(circuit_spec(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group), out);
 }
 
+// (sgfhe_circuit_create_data is the routed entry without registers, and sgfhe_circuit_create_seq without routes)
 int32_t sgfhe_circuit_create_data(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
                                   const uint32_t *node_start, const uint32_t *term_ref, const int32_t *term_shift,
                                   const int32_t *term_weight, const uint32_t *node_table, size_t n_gates,
                                   const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
                                   sgfhe_circuit **out) {
-    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
-    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out);
+    return sgfhe_circuit_create_routed(n_inputs, n_planes, node_kind, node_start, term_ref, term_shift, term_weight,
+                                       node_table, n_gates, outputs, out_shift, n_outputs, group, 0, nullptr, nullptr,
+                                       nullptr, 0, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int32_t sgfhe_circuit_create_seq(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
@@ -3037,9 +3048,9 @@ int32_t sgfhe_circuit_create_seq(uint32_t n_inputs, uint32_t n_planes, const uin
                                  const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
                                  uint32_t n_regs, const uint32_t *next_ref, const int32_t *next_shift,
                                  const uint32_t *reg_scale, sgfhe_circuit **out) {
-    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
-    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
-    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out, &R);
+    return sgfhe_circuit_create_routed(n_inputs, n_planes, node_kind, node_start, term_ref, term_shift, term_weight,
+                                       node_table, n_gates, outputs, out_shift, n_outputs, group, n_regs, next_ref,
+                                       next_shift, reg_scale, 0, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int32_t sgfhe_circuit_create_routed(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
@@ -3050,10 +3061,12 @@ int32_t sgfhe_circuit_create_routed(uint32_t n_inputs, uint32_t n_planes, const 
                                     const uint32_t *reg_scale, uint32_t n_routes, const int32_t *routes,
                                     const uint32_t *term_route, const uint32_t *out_route, const uint32_t *next_route,
                                     sgfhe_circuit **out) {
-    const CircuitNodes N = circuit_nodes_data(n_planes, node_kind, node_start, term_ref, term_shift, term_weight, node_table);
-    const CircuitRegs R = {n_regs, next_ref, next_shift, reg_scale};
-    const CircuitRoutes T = {n_routes, routes, term_route, out_route, next_route};
-    return circuit_create(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group, out, &R, &T);
+    const CircuitNodes N = circuit_nodes_csr(5, node_kind, node_start, term_ref, term_shift, term_weight, node_table, n_planes);
+    CircuitSpec S = circuit_spec(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group);
+    S.regs.n_regs = n_regs, S.regs.next_ref = next_ref, S.regs.next_shift = next_shift, S.regs.reg_scale = reg_scale;
+    S.routes.n_routes = n_routes, S.routes.routes = routes;
+    S.routes.term_route = term_route, S.routes.out_route = out_route, S.routes.next_route = next_route;
+    return circuit_create(S, out);
 }
 
 int32_t sgfhe_circuit_routes(const sgfhe_circuit *c, uint32_t *n_routes) {
@@ -3219,12 +3232,10 @@ struct CircuitRun {
     const size_t probe_rows = probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
     // the plan's tables on the device (views into circ_tab), and the probe's
     CircNodes nodes = {};
-    const uint32_t *d_out_slot = nullptr, *d_out_ref = nullptr, *d_in_slot = nullptr, *d_jobs = nullptr;
+    CircRefs outs = {}, nexts = {};   // the outputs; the registers' next states (a plan with registers)
+    const uint32_t *d_out_slot = nullptr, *d_in_slot = nullptr, *d_jobs = nullptr;
     const uint32_t *d_fam_start = nullptr, *d_fam_entry = nullptr;   // (a plan with live siblings)
-    const uint32_t *d_next_ref = nullptr, *d_next_scale = nullptr, *d_reg_index = nullptr;   // (a plan with registers)
-    const int32_t *d_next_shift = nullptr;
-    const int32_t *d_out_shift = nullptr;
-    const uint32_t *d_out_route = nullptr, *d_next_route = nullptr;   // (a plan with route tables; the tables: nodes.routes)
+    const uint32_t *d_next_scale = nullptr, *d_reg_index = nullptr;   // (a plan with registers)
     NoiseLayout NL = {};
     std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
 
@@ -3238,6 +3249,19 @@ struct CircuitRun {
     int32_t upload_lwe();
     int32_t level_call(uint32_t L, uint64_t row0);
     int32_t pack_group(size_t q0);
+    // every level L = 1 .. levels in calls of SGFHE_CIRCUIT_CALL_ROWS rows from row 0; then every pack group from
+    // ciphertext 0: the walk that numbers a run's calls (csrc/circuit.h)
+    int32_t level_calls() {
+        for (uint32_t L = 1; L <= P.levels; L++)
+            for (uint64_t row0 = 0; row0 < P.level_rows(L, instances); row0 += SGFHE_CIRCUIT_CALL_ROWS)
+                if (const int32_t rc = level_call(L, row0)) return rc;
+        return SGFHE_OK;
+    }
+    int32_t pack_groups() {
+        for (size_t q0 = 0; q0 < sz.n_ct; q0 += sz.cpc)
+            if (const int32_t rc = pack_group(q0)) return rc;
+        return SGFHE_OK;
+    }
     int32_t fetch(uint64_t *o, uint64_t *w, uint64_t *v);
     int32_t download();
     int32_t run();
@@ -3256,7 +3280,13 @@ struct CircuitRun {
     void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows, uint32_t *lutw = nullptr) const {
         hipLaunchKernelGGL(k_circ_gather, dim3(((uint32_t)rows * (uint32_t)row + 255) / 256), dim3(256), 0, st,
                            c->circ_wires.p, nodes, node0, S.a1, S.b1, S.a2, S.b2, (uint32_t)row0, (uint32_t)rows, inst,
-                           (uint32_t)n, r, P.group, lutw, (const uint8_t *)(data ? c->circ_data.p : nullptr));
+                           (uint32_t)n, r, lutw, (const uint8_t *)(data ? c->circ_data.p : nullptr));
+    }
+    // a reference list of the uploaded image, from its offsets (`route` is read only in a plan with route tables)
+    CircRefs refs_at(uint32_t ref, uint32_t shift, uint32_t route) const {
+        const uint32_t *tab = c->circ_tab.p;
+        return {tab + ref, reinterpret_cast<const int32_t *>(tab + shift), P.n_routes ? tab + route : nullptr,
+                P.n_routes ? reinterpret_cast<const int32_t *>(tab + P.at.routes) : nullptr, P.group};
     }
     // words of the staging's rows (a direct run's level calls may leave un-reduced rows: 16-byte residues, at an even
     // word offset); the LUT descriptor of a call lies behind them, one 32-bit word per row
@@ -3313,21 +3343,14 @@ int32_t CircuitRun::upload_tables() {
     if (data && !seq)   // (a stepped run brings planes with every step: upload_step)
         HIPCHK(c, hipMemcpyAsync(c->circ_data.p, data, (size_t)P.n_planes * instances, hipMemcpyHostToDevice, st));
     const uint32_t *tab = c->circ_tab.p;
-    nodes = {tab + P.at.node_kind, tab + P.at.term_start, tab + P.at.term_ref,
-             reinterpret_cast<const int32_t *>(tab + P.at.term_shift),
-             reinterpret_cast<const int32_t *>(tab + P.at.term_weight), nullptr, nullptr};
-    d_out_slot = tab + P.at.out_slot, d_out_ref = tab + P.at.out_ref, d_in_slot = tab + P.at.input_slot;
-    d_jobs = tab + P.at.jobs;
+    nodes = {tab + P.at.node_kind, tab + P.at.term_start, reinterpret_cast<const int32_t *>(tab + P.at.term_weight),
+             refs_at(P.at.term_ref, P.at.term_shift, P.at.term_route)};
+    outs = refs_at(P.at.out_ref, P.at.out_shift, P.at.out_route);
+    d_out_slot = tab + P.at.out_slot, d_in_slot = tab + P.at.input_slot, d_jobs = tab + P.at.jobs;
     if (P.siblings()) d_fam_start = tab + P.at.fam_start, d_fam_entry = tab + P.at.fam_entry;
     if (P.n_regs) {
-        d_next_ref = tab + P.at.next_ref, d_next_scale = tab + P.at.next_scale, d_reg_index = tab + P.at.reg_index;
-        d_next_shift = reinterpret_cast<const int32_t *>(tab + P.at.next_shift);
-    }
-    d_out_shift = reinterpret_cast<const int32_t *>(tab + P.at.out_shift);
-    if (P.n_routes) {   // (a plan without tables leaves all of these NULL: its kernels read no route)
-        nodes.route = tab + P.at.term_route, nodes.routes = reinterpret_cast<const int32_t *>(tab + P.at.routes);
-        d_out_route = tab + P.at.out_route;
-        if (P.n_regs) d_next_route = tab + P.at.next_route;
+        nexts = refs_at(P.at.next_ref, P.at.next_shift, P.at.next_route);
+        d_next_scale = tab + P.at.next_scale, d_reg_index = tab + P.at.reg_index;
     }
     if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
         HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
@@ -3472,8 +3495,7 @@ int32_t CircuitRun::pack_group(size_t q0) {
         for (const CircuitPackRun &U : runs) {
             const uint32_t rows = (uint32_t)(U.len * n);
             hipLaunchKernelGGL(k_circ_lift, dim3((rows * (uint32_t)row + 255) / 256), dim3(256), 0, st, c->circ_wires.p,
-                               d_out_ref, d_out_shift, c->circ_raw.p, cur(c).d_crt, (uint32_t)(U.q * n), rows, inst,
-                               (uint32_t)n, r, P.group, d_out_route, nodes.routes);
+                               outs, c->circ_raw.p, cur(c).d_crt, (uint32_t)(U.q * n), rows, inst, (uint32_t)n, r);
             HIPCHK(c, hipGetLastError());
         }
     } else if (nb) {
@@ -3526,8 +3548,8 @@ int32_t CircuitRun::fetch(uint64_t *o, uint64_t *w, uint64_t *v) {
     }
     if (o) {
         const size_t total = (size_t)P.n_outputs * instances * row;
-        hipLaunchKernelGGL(k_circ_collect, dim3(copy_grid(total)), dim3(256), 0, st, c->circ_wires.p, d_out_ref,
-                           d_out_shift, c->circ_out.p, total, inst, (uint32_t)n, r, P.group, d_out_route, nodes.routes);
+        hipLaunchKernelGGL(k_circ_collect, dim3(copy_grid(total)), dim3(256), 0, st, c->circ_wires.p, outs, c->circ_out.p,
+                           total, inst, (uint32_t)n, r);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(o, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
     }
@@ -3572,9 +3594,8 @@ int32_t CircuitRun::upload_step(size_t s) {
 // end of a step: every register's next state, from the wire table into the state buffer (one launch)
 int32_t CircuitRun::feedback() {
     if (!P.n_regs) return SGFHE_OK;
-    hipLaunchKernelGGL(k_circ_next, dim3(copy_grid(state_words())), dim3(256), 0, st, c->circ_wires.p, d_next_ref,
-                       d_next_shift, d_next_scale, c->circ_state.p, state_words(), inst, (uint32_t)n, r, P.group,
-                       d_next_route, nodes.routes);
+    hipLaunchKernelGGL(k_circ_next, dim3(copy_grid(state_words())), dim3(256), 0, st, c->circ_wires.p, nexts,
+                       d_next_scale, c->circ_state.p, state_words(), inst, (uint32_t)n, r);
     HIPCHK(c, hipGetLastError());
     return SGFHE_OK;
 }
@@ -3589,12 +3610,9 @@ int32_t CircuitRun::run_steps() {
     const size_t out_words = (size_t)P.n_outputs * instances * row, wv = sz.n_ct * M;
     for (size_t s = 0, emitted = 0; s < seq->steps; s++) {
         if ((rc = upload_step(s))) return rc;
-        for (uint32_t L = 1; L <= P.levels; L++)
-            for (uint64_t row0 = 0; row0 < P.level_rows(L, instances); row0 += SGFHE_CIRCUIT_CALL_ROWS)
-                if ((rc = level_call(L, row0))) return rc;
+        if ((rc = level_calls())) return rc;
         if (!seq->emit || seq->emit[s]) {
-            for (size_t q0 = 0; q0 < sz.n_ct; q0 += sz.cpc)
-                if ((rc = pack_group(q0))) return rc;
+            if ((rc = pack_groups())) return rc;
             if ((rc = fetch(out ? out + emitted * out_words : nullptr, pack ? ct->out_w + emitted * wv : nullptr,
                             pack ? ct->out_v + emitted * wv : nullptr)))
                 return rc;
@@ -3615,11 +3633,8 @@ int32_t CircuitRun::run() {
     if ((rc = grow())) return rc;
     if ((rc = upload_tables())) return rc;
     if ((rc = ct ? upload_ct() : upload_lwe())) return rc;
-    for (uint32_t L = 1; L <= P.levels; L++)
-        for (uint64_t row0 = 0; row0 < P.level_rows(L, instances); row0 += SGFHE_CIRCUIT_CALL_ROWS)
-            if ((rc = level_call(L, row0))) return rc;
-    for (size_t q0 = 0; q0 < sz.n_ct; q0 += sz.cpc)
-        if ((rc = pack_group(q0))) return rc;
+    if ((rc = level_calls())) return rc;
+    if ((rc = pack_groups())) return rc;
     return download();
 }
 

@@ -1803,33 +1803,40 @@ __device__ __forceinline__ uint64_t circ_word(const uint64_t *__restrict__ wires
 // It is a per-lane load on purpose: rows are n + 1 words, so a wave may straddle two rows and the entry is uniform over
 // a row, not over a wave -- broadcasting the first lane's entry would read the wrong lane past the row's end.  The lanes
 // of a row hit one cache line.
-__device__ __forceinline__ uint64_t circ_word_lane(const uint64_t *__restrict__ wires, uint32_t ref, int32_t d,
-                                                   const int32_t *__restrict__ rho, uint32_t group, uint32_t instances,
-                                                   uint32_t inst, uint32_t e, uint32_t n, uint64_t r, uint64_t one) {
-    const uint32_t own = inst % group;
+// One list of references of a plan on the device -- the terms of the node table, the outputs, the registers' next
+// states: reference i is the slot reference ref[i] at the lane shift shift[i], or through the table of its route index
+// route[i] -- k >= 1 is table k - 1 of `routes` [n_routes][group], 0 none; `route` and `routes` are both NULL in a plan
+// without route tables.
+struct CircRefs {
+    const uint32_t *ref;
+    const int32_t *shift;
+    const uint32_t *route;
+    const int32_t *routes;
+    uint32_t group;
+};
+
+// word e of reference i of `refs` at instance `inst`; `one` is the codeword NOT is taken at
+__device__ __forceinline__ uint64_t circ_ref_word(const uint64_t *__restrict__ wires, const CircRefs &refs, size_t i,
+                                                  uint32_t instances, uint32_t inst, uint32_t e, uint32_t n, uint64_t r,
+                                                  uint64_t one) {
+    uint32_t ref = refs.ref[i];
+    const int32_t d = refs.shift[i];
+    const uint32_t k = refs.route ? refs.route[i] : 0u;
+    const int32_t *rho = k ? refs.routes + (size_t)(k - 1) * refs.group : nullptr;
+    const uint32_t own = inst % refs.group;
     const int64_t lane = rho ? (int64_t)rho[own] : (int64_t)own + d;
-    if (lane < 0 || lane >= (int64_t)group) ref = CIRC_REF_FALSE | (ref & CIRC_REF_NOT);
+    if (lane < 0 || lane >= (int64_t)refs.group) ref = CIRC_REF_FALSE | (ref & CIRC_REF_NOT);
     const size_t src = (size_t)((int64_t)(inst - own) + lane);   // (not read for the constant)
     return circ_word(wires, ref, (size_t)(ref & ~CIRC_REF_NOT) * instances + src, e, n, r, one);
 }
 
 // The node table of a plan on the device (CircuitPlan::node_kind ..): one CSR over the live nodes and the pack stage's
-// pseudo-level, node k's terms term_start[k] .. term_start[k + 1] of ref / shift / weight.
-// `route` / `routes` (both NULL in a plan without route tables): the terms' route indices beside `shift`, and the
-// tables [n_routes][group] -- index k >= 1 is table k - 1, 0 none.
+// pseudo-level, node k's terms term_start[k] .. term_start[k + 1] of `terms` and `weight`.
 struct CircNodes {
-    const uint32_t *kind, *start, *ref;
-    const int32_t *shift, *weight;
-    const uint32_t *route;
-    const int32_t *routes;
+    const uint32_t *kind, *start;
+    const int32_t *weight;
+    CircRefs terms;
 };
-
-// the route table of reference i of a route-index array (NULL array: a plan without tables)
-__device__ __forceinline__ const int32_t *circ_route(const uint32_t *__restrict__ route, const int32_t *__restrict__ routes,
-                                                     size_t i, uint32_t group) {
-    const uint32_t k = route ? route[i] : 0u;
-    return k ? routes + (size_t)(k - 1) * group : nullptr;
-}
 
 // The staged inputs of one call, a1 / a2 [rows][n], b1 / b2 [rows]: rows row0 .. row0 + rows of the level whose first
 // node is `node0` of the table.  A classic node (kind 0) writes (a1, a2) = (X, Y), its two terms.  A sum node writes
@@ -1849,15 +1856,14 @@ __device__ __forceinline__ const int32_t *circ_route(const uint32_t *__restrict_
 __global__ void __launch_bounds__(256)
 k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node0, uint64_t *__restrict__ a1,
               uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
-              uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group,
-              uint32_t *__restrict__ lutw = nullptr, const uint8_t *__restrict__ data = nullptr) {
+              uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t *__restrict__ lutw = nullptr,
+              const uint8_t *__restrict__ data = nullptr) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
     const uint32_t k = node0 + R / instances, inst = R % instances;
     auto read = [&](uint32_t i, uint64_t one) -> uint64_t {
-        return circ_word_lane(wires, nodes.ref[i], nodes.shift[i], circ_route(nodes.route, nodes.routes, i, group), group,
-                              instances, inst, e, n, r, one);
+        return circ_ref_word(wires, nodes.terms, i, instances, inst, e, n, r, one);
     };
     const uint32_t t0 = nodes.start[k], t1 = nodes.start[k + 1];
     const uint32_t kw = nodes.kind[k], kd = kw & 0xFFu;
@@ -2012,21 +2018,18 @@ __device__ __forceinline__ ulonglong2 lift_word(uint64_t x, const CrtConst *CC) 
 
 // The lifted ciphertexts of a pack group (SGFHE_CIRCUIT_PACK_LIFT): rows row0 .. row0 + rows of the pack stage's
 // pseudo-level, whose node o is (TRUE, output o) -- row R = q n + bit is output R / instances at instance R % instances
-// -- read from the wire table as that level's gather reads its second input (out_ref / out_shift [n_outputs]; NOT,
-// the constant and the lane shift applied over Z_r), lifted word by word into row R of the raw output table
+// -- read from the wire table as that level's gather reads its second input (`outs` [n_outputs]; NOT, the constant
+// and the lane shift or route applied over Z_r), lifted word by word into row R of the raw output table
 // [q][n][n + 1].  Thread-to-word map of the gathers: coalesced 8-byte loads along a source row, 16-byte stores
 // (raw rows are 16-byte aligned), the row decode uniform over a row.
 __global__ void __launch_bounds__(256)
-k_circ_lift(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
-            const int32_t *__restrict__ out_shift, ulonglong2 *__restrict__ rawout, const CrtConst *__restrict__ CC,
-            uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t group,
-            const uint32_t *__restrict__ out_route, const int32_t *__restrict__ routes) {
+k_circ_lift(const uint64_t *__restrict__ wires, CircRefs outs, ulonglong2 *__restrict__ rawout,
+            const CrtConst *__restrict__ CC, uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
     const uint32_t o = R / instances, inst = R % instances;
-    const uint64_t v = circ_word_lane(wires, out_ref[o], out_shift[o], circ_route(out_route, routes, o, group), group,
-                                      instances, inst, e, n, r, r / 4);
+    const uint64_t v = circ_ref_word(wires, outs, o, instances, inst, e, n, r, r / 4);
     rawout[(size_t)R * (n + 1) + e] = lift_word(v, CC);
 }
 
@@ -2038,19 +2041,16 @@ k_lwe_lift(const uint64_t *__restrict__ in, ulonglong2 *__restrict__ out, const 
         out[t] = lift_word(in[t], CC);
 }
 
-// the circuit's outputs [n_outputs][instances][n + 1], NOT, the constant and the lane shift or route (out_shift /
-// out_route [n_outputs] beside out_ref) applied (grid-stride: the array may hold more than 2^32 words)
+// the circuit's outputs [n_outputs][instances][n + 1], NOT, the constant and the lane shift or route of `outs`
+// [n_outputs] applied (grid-stride: the array may hold more than 2^32 words)
 __global__ void __launch_bounds__(256)
-k_circ_collect(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ out_ref,
-               const int32_t *__restrict__ out_shift, uint64_t *__restrict__ out, size_t total, uint32_t instances,
-               uint32_t n, uint64_t r, uint32_t group, const uint32_t *__restrict__ out_route,
-               const int32_t *__restrict__ routes) {
+k_circ_collect(const uint64_t *__restrict__ wires, CircRefs outs, uint64_t *__restrict__ out, size_t total,
+               uint32_t instances, uint32_t n, uint64_t r) {
     const size_t per_out = (size_t)instances * (n + 1);
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t o = t / per_out, w = t % per_out;
         const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
-        out[t] = circ_word_lane(wires, out_ref[o], out_shift[o], circ_route(out_route, routes, o, group), group, instances,
-                                inst, e, n, r, r / 4);
+        out[t] = circ_ref_word(wires, outs, o, instances, inst, e, n, r, r / 4);
     }
 }
 
@@ -2073,21 +2073,18 @@ k_circ_state_load(const uint64_t *__restrict__ state, const uint32_t *__restrict
     }
 }
 
-// End of a step: the next-state gather.  Register i takes next_ref[i] read at the lane shift next_shift[i] -- NOT, the
-// constant and the shift as k_circ_collect applies them to an output, with the codeword of NOT and of the TRUE fill
+// End of a step: the next-state gather.  Register i takes reference i of `nexts` -- NOT, the constant and the shift
+// or route as k_circ_collect applies them to an output, with the codeword of NOT and of the TRUE fill
 // Dr >> next_scale[i], the register's scale.  It reads the wire table and writes the state buffer, never the same
 // words: a swap, a rotation, a register holding itself or reading a stream input need no ordering between threads.
 __global__ void __launch_bounds__(256)
-k_circ_next(const uint64_t *__restrict__ wires, const uint32_t *__restrict__ next_ref,
-            const int32_t *__restrict__ next_shift, const uint32_t *__restrict__ next_scale,
-            uint64_t *__restrict__ state, size_t total, uint32_t instances, uint32_t n, uint64_t r, uint32_t group,
-            const uint32_t *__restrict__ next_route, const int32_t *__restrict__ routes) {
+k_circ_next(const uint64_t *__restrict__ wires, CircRefs nexts, const uint32_t *__restrict__ next_scale,
+            uint64_t *__restrict__ state, size_t total, uint32_t instances, uint32_t n, uint64_t r) {
     const size_t per_reg = (size_t)instances * (n + 1);
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t i = t / per_reg, w = t % per_reg;
         const uint32_t inst = (uint32_t)(w / (n + 1)), e = (uint32_t)(w % (n + 1));
-        state[t] = circ_word_lane(wires, next_ref[i], next_shift[i], circ_route(next_route, routes, i, group), group,
-                                  instances, inst, e, n, r, (r / 4) >> next_scale[i]);
+        state[t] = circ_ref_word(wires, nexts, i, instances, inst, e, n, r, (r / 4) >> next_scale[i]);
     }
 }
 

@@ -41,7 +41,7 @@ int main() {
         for (size_t t = 0; t < instances; t++) bits[i * instances + t] = (uint8_t)(line[t] - '0');
     }
     CircuitPlan P;
-    CHECK(circuit_plan(n_inputs, gates.data(), n_gates, outs.data(), n_outputs, P) == SGFHE_OK);
+    CHECK(circuit_plan(spec_gates(n_inputs, gates.data(), n_gates, outs.data(), n_outputs), P) == SGFHE_OK);
     // the probe rows: inputs, then the three wires of every live node in `order`; term_row names them
     check_plan_tables(P);
     for (size_t k = 0; k < P.live(); k++) check_node_terms(P, k, 0, 2, &gates[2 * P.order[k]], nullptr, nullptr);

@@ -220,8 +220,8 @@ struct Arrays {
     }
     void out(uint32_t ref, int32_t d = 0) { outs.push_back(ref); oshift.push_back(d); }
     int32_t plan(uint32_t G, CircuitPlan &P) const {
-        return circuit_plan_w(n_inputs, kind.data(), start.data(), refs.data(), shift.data(), weight.data(), kind.size(),
-                              outs.data(), oshift.data(), outs.size(), G, P);
+        return circuit_plan(spec_csr(1, n_inputs, 0, kind.data(), start.data(), refs.data(), shift.data(), weight.data(),
+                                     nullptr, kind.size(), outs.data(), oshift.data(), outs.size(), G), P);
     }
 };
 
@@ -295,12 +295,12 @@ int main() {
         const uint32_t gates[8] = {0, 1, 1 | CIRC_NOT, 0, 2, 5, 3, 9}, outs[5] = {11, 0, 2 | CIRC_NOT, CIRC_FALSE, 11};
         CircuitPlan P;
         cs = -100;
-        CHECK(circuit_plan(2, gates, 4, outs, 5, P) == SGFHE_OK);
+        CHECK(circuit_plan(spec_gates(2, gates, 4, outs, 5), P) == SGFHE_OK);
         for (uint64_t instances : {(uint64_t)1, (uint64_t)5, (uint64_t)4200, (uint64_t)8192}) check_plan(P, instances, instances > 5 ? 8 : 1);
         const uint32_t g3[9] = {0, 1, 2, 0, 1 | CIRC_NOT, CIRC_NO_INPUT, 3, 6, 8}, o3[4] = {9, 5, 11 | CIRC_NOT, 2};
         const int32_t s3[9] = {0, 0, 0, 0, 0, 0, -1, 3, 0}, os3[4] = {0, 0, 0, 2};
         cs = -101;
-        CHECK(circuit_plan3(3, g3, s3, 3, o3, os3, 4, 4, P) == SGFHE_OK);
+        CHECK(circuit_plan(spec_arity(3, 3, g3, s3, 3, o3, os3, 4, 4), P) == SGFHE_OK);
         for (uint64_t instances : {(uint64_t)4, (uint64_t)64, (uint64_t)4100}) check_plan(P, instances, 4);
     }
     // ---- random circuits of every node kind, with and without lane groups

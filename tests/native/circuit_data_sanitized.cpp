@@ -65,18 +65,15 @@ struct Arrays {
     std::vector<uint32_t> kind, start, ref, table, outputs;
     std::vector<int32_t> shift, weight, out_shift;
     size_t n_gates() const { return kind.size(); }
-    int32_t plan(CircuitPlan &P) const {
-        return circuit_plan_data(n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                 table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, P);
+    // through the entry that admits kinds 0 .. max_kind; only sgfhe_circuit_create_data (5) takes the planes
+    int32_t plan_kinds(uint32_t max_kind, CircuitPlan &P) const {
+        return circuit_plan(spec_csr(max_kind, n_inputs, max_kind == 5 ? n_planes : 0, kind.data(), start.data(), ref.data(),
+                                     shift.data(), weight.data(), table.data(), n_gates(), outputs.data(), out_shift.data(),
+                                     outputs.size(), group), P);
     }
-    int32_t plan_multi(CircuitPlan &P) const {
-        return circuit_plan_lut_multi(n_inputs, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                      table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, P);
-    }
-    int32_t plan_lut(CircuitPlan &P) const {
-        return circuit_plan_lut(n_inputs, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, P);
-    }
+    int32_t plan(CircuitPlan &P) const { return plan_kinds(5, P); }
+    int32_t plan_multi(CircuitPlan &P) const { return plan_kinds(3, P); }
+    int32_t plan_lut(CircuitPlan &P) const { return plan_kinds(2, P); }
     bool sibling(size_t g) const { return kind[g] == 3 || kind[g] == 5; }
     bool data(size_t g) const { return kind[g] == 4 || kind[g] == 5; }
     size_t leader(size_t g) const {

@@ -108,8 +108,8 @@ static int lane_read(const std::vector<uint8_t> &wire, uint32_t ref, int32_t d, 
 static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32_t n_gates, uint32_t n_outputs) {
     const Arrays A = random_circuit(n_inputs, n_gates, n_outputs, G);
     CircuitPlan P;
-    CHECK(circuit_plan3(n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G,
-                        P) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(3, n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(),
+                                  n_outputs, G), P) == SGFHE_OK);
     CHECK(P.group == G);
     check_plan_tables(P);
     uint32_t three = 0;
@@ -187,9 +187,10 @@ static void check_all_none(uint32_t G) {
         }
     }
     CircuitPlan P, Z;
-    CHECK(circuit_plan3(n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G,
-                        P) == SGFHE_OK);
-    CHECK(circuit_plan(n_inputs, g2.data(), s2.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G, Z) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(3, n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(),
+                                  n_outputs, G), P) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(2, n_inputs, g2.data(), s2.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G),
+                       Z) == SGFHE_OK);
     CHECK(P.sum_before[P.live()] == 0 && same_tables(P, Z));
 }
 
@@ -200,7 +201,7 @@ static void check_rejected() {
     P.n_inputs = 77;   // (stays: a refused call does not touch the plan)
     auto refused = [&](const uint32_t *gates, const int32_t *gs, const uint32_t *o, uint32_t group) {
         const size_t before = g_allocs;
-        const int32_t rc = circuit_plan3(2, gates, gs, 2, o, nullptr, 2, group, P);
+        const int32_t rc = circuit_plan(spec_arity(3, 2, gates, gs, 2, o, nullptr, 2, group), P);
         CHECK(rc == SGFHE_ERR_INVALID_ARG && g_allocs == before && P.n_inputs == 77 && P.order.empty());
     };
     const uint32_t none_x[6] = {N, 1, 0, 2, 0, N}, none_y[6] = {0, N, 1, 2, 0, N};      // NONE as a first / second input
@@ -221,16 +222,17 @@ static void check_rejected() {
     refused(good, nullptr, outs, 0);
     // accepted: the largest shifts on a third input, anything beside NONE, a shift on a constant third input (dropped)
     const int32_t edge[6] = {0, 0, -7, 0, 0, 7};
-    CHECK(circuit_plan3(2, good, edge, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.sum_before[2] == 2 && P.n_inputs == 2);
+    CHECK(circuit_plan(spec_arity(3, 2, good, edge, 2, outs, nullptr, 2, 8), P) == SGFHE_OK && P.sum_before[2] == 2 &&
+          P.n_inputs == 2);
     CHECK(P.term_shift[2] == -7 && P.term_shift[5] == 7 && P.levels == 2);
     const uint32_t mixed[6] = {0, 1, N, 2, 0, CIRC_FALSE | CIRC_NOT};
     const int32_t wild[6] = {0, 0, INT32_MAX, 0, 0, 5};
-    CHECK(circuit_plan3(2, mixed, wild, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.sum_before[2] == 1);
+    CHECK(circuit_plan(spec_arity(3, 2, mixed, wild, 2, outs, nullptr, 2, 8), P) == SGFHE_OK && P.sum_before[2] == 1);
     CHECK(P.node_kind[0] == 0 && P.node_kind[1] == 1 && P.term_start[1] == 2 && P.term_start[2] == 5);
     CHECK(P.term_ref[4] == (CIRC_FALSE | CIRC_NOT) && P.term_shift[4] == 0);
     // a third input alone keeps its node alive and sets the level
     const uint32_t chain[9] = {0, 1, N, 0, 1, N, 0, 0, 5 | CIRC_NOT}, last[1] = {2 + 3 * 2 + 2};
-    CHECK(circuit_plan3(2, chain, nullptr, 3, last, nullptr, 1, 1, P) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(3, 2, chain, nullptr, 3, last, nullptr, 1, 1), P) == SGFHE_OK);
     CHECK(P.live() == 2 && P.levels == 2 && P.level[0] == 0 && P.level[1] == 1 && P.level[2] == 2);
     CHECK(P.out_node[0] == CIRC_NONE);   // XOR3
 }

@@ -102,8 +102,8 @@ static int lane_read(const std::vector<uint8_t> &wire, uint32_t ref, int32_t d, 
 static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32_t n_gates, uint32_t n_outputs) {
     const Arrays A = random_circuit(n_inputs, n_gates, n_outputs, G);
     CircuitPlan P;
-    CHECK(circuit_plan(n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G,
-                       P) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(2, n_inputs, A.gates.data(), A.gshift.data(), n_gates, A.outs.data(), A.oshift.data(),
+                                  n_outputs, G), P) == SGFHE_OK);
     CHECK(P.group == G && P.lanes() == (G > 1));
     check_plan_tables(P);
     for (size_t k = 0; k < P.live(); k++)
@@ -114,14 +114,15 @@ static size_t check_case(uint32_t G, size_t instances, uint32_t n_inputs, uint32
     }
     // the same arrays without shifts: levels, order and slots do not depend on the shifts
     CircuitPlan Z;
-    CHECK(circuit_plan(n_inputs, A.gates.data(), n_gates, A.outs.data(), n_outputs, Z) == SGFHE_OK);
+    CHECK(circuit_plan(spec_gates(n_inputs, A.gates.data(), n_gates, A.outs.data(), n_outputs), Z) == SGFHE_OK);
     CHECK(Z.level == P.level && Z.order == P.order && Z.level_start == P.level_start && Z.slots == P.slots);
     CHECK(Z.node_kind == P.node_kind && Z.term_start == P.term_start && Z.term_ref == P.term_ref && Z.term_row == P.term_row);
     CHECK(Z.term_weight == P.term_weight && Z.out_slot == P.out_slot && Z.out_ref == P.out_ref);
     // and with every shift zero the lanes plan IS the plan of the old entry, table by table
     const std::vector<int32_t> gz(A.gshift.size(), 0), oz(A.oshift.size(), 0);
     CircuitPlan ZL;
-    CHECK(circuit_plan(n_inputs, A.gates.data(), gz.data(), n_gates, A.outs.data(), oz.data(), n_outputs, G, ZL) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(2, n_inputs, A.gates.data(), gz.data(), n_gates, A.outs.data(), oz.data(), n_outputs, G),
+                       ZL) == SGFHE_OK);
     ZL.group = Z.group;   // (the group is the one thing the entries give differently)
     CHECK(same_tables(ZL, Z));
 
@@ -164,7 +165,7 @@ static void check_rejected() {
     P.n_inputs = 77;   // (stays: a refused call does not touch the plan)
     auto refused = [&](const int32_t *gs, const int32_t *os, uint32_t group) {
         const size_t before = g_allocs;
-        const int32_t rc = circuit_plan(2, gates, gs, 2, outs, os, 2, group, P);
+        const int32_t rc = circuit_plan(spec_arity(2, 2, gates, gs, 2, outs, os, 2, group), P);
         CHECK(rc == SGFHE_ERR_INVALID_ARG && g_allocs == before && P.n_inputs == 77 && P.order.empty());
     };
     refused(nullptr, nullptr, 0);                          // group = 0
@@ -182,18 +183,18 @@ static void check_rejected() {
     const uint32_t later[4] = {0, 5, 2, 0};                // what sgfhe_circuit_create refuses is refused here too
     {
         const size_t before = g_allocs;
-        CHECK(circuit_plan(2, later, zero, 2, outs, zero, 2, 8, P) == SGFHE_ERR_INVALID_ARG && g_allocs == before);
-        CHECK(circuit_plan(2, gates, zero, 2, outs, zero, 0, 8, P) == SGFHE_ERR_INVALID_ARG && g_allocs == before);
+        CHECK(circuit_plan(spec_arity(2, 2, later, zero, 2, outs, zero, 2, 8), P) == SGFHE_ERR_INVALID_ARG && g_allocs == before);
+        CHECK(circuit_plan(spec_arity(2, 2, gates, zero, 2, outs, zero, 0, 8), P) == SGFHE_ERR_INVALID_ARG && g_allocs == before);
     }
     // accepted: the largest shifts, NULL arrays, a shift on the constant (dropped)
     const int32_t edge[4] = {7, -7, 0, 0}, oedge[2] = {-7, 7};
-    CHECK(circuit_plan(2, gates, edge, 2, outs, oedge, 2, 8, P) == SGFHE_OK && P.group == 8 && P.n_inputs == 2);
+    CHECK(circuit_plan(spec_arity(2, 2, gates, edge, 2, outs, oedge, 2, 8), P) == SGFHE_OK && P.group == 8 && P.n_inputs == 2);
     CHECK(P.term_shift[0] == 7 && P.term_shift[1] == -7 && P.out_shift[0] == -7 && P.out_shift[1] == 7);
-    CHECK(circuit_plan(2, gates, nullptr, 2, outs, nullptr, 2, 8, P) == SGFHE_OK && P.lanes());
+    CHECK(circuit_plan(spec_arity(2, 2, gates, nullptr, 2, outs, nullptr, 2, 8), P) == SGFHE_OK && P.lanes());
     for (int32_t d : P.term_shift) CHECK(d == 0);
     const uint32_t cgates[2] = {CIRC_FALSE | CIRC_NOT, 0}, couts[1] = {CIRC_FALSE};
     const int32_t cs[2] = {3, 0}, cos_[1] = {-3};
-    CHECK(circuit_plan(1, cgates, cs, 1, couts, cos_, 1, 4, P) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(2, 1, cgates, cs, 1, couts, cos_, 1, 4), P) == SGFHE_OK);
     CHECK(P.out_shift[0] == 0 && P.live() == 0);
 }
 

@@ -70,18 +70,15 @@ struct Arrays {
     std::vector<uint32_t> kind, start, ref, table, outputs;
     std::vector<int32_t> shift, weight, out_shift;
     size_t n_gates() const { return kind.size(); }
-    int32_t plan(CircuitPlan &P) const {
-        return circuit_plan_lut_multi(n_inputs, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                      table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, P);
+    // through the entry that admits kinds 0 .. max_kind (1: sgfhe_circuit_create_w, which takes no node_table)
+    int32_t plan_kinds(uint32_t max_kind, CircuitPlan &P) const {
+        return circuit_plan(spec_csr(max_kind, n_inputs, 0, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
+                                     max_kind >= 2 ? table.data() : nullptr, n_gates(), outputs.data(), out_shift.data(),
+                                     outputs.size(), group), P);
     }
-    int32_t plan_lut(CircuitPlan &P) const {
-        return circuit_plan_lut(n_inputs, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, P);
-    }
-    int32_t plan_w(CircuitPlan &P) const {
-        return circuit_plan_w(n_inputs, kind.data(), start.data(), ref.data(), shift.data(), weight.data(), n_gates(),
-                              outputs.data(), out_shift.data(), outputs.size(), group, P);
-    }
+    int32_t plan(CircuitPlan &P) const { return plan_kinds(3, P); }
+    int32_t plan_lut(CircuitPlan &P) const { return plan_kinds(2, P); }
+    int32_t plan_w(CircuitPlan &P) const { return plan_kinds(1, P); }
     size_t leader(size_t g) const {
         while (kind[g] == 3) g--;
         return g;

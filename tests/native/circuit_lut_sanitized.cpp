@@ -63,14 +63,14 @@ struct Arrays {
     std::vector<uint32_t> kind, start, ref, table, outputs;
     std::vector<int32_t> shift, weight, out_shift;
     size_t n_gates() const { return kind.size(); }
-    int32_t plan(CircuitPlan &P) const {
-        return circuit_plan_lut(n_inputs, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, P);
+    // through the entry that admits kinds 0 .. max_kind (1: sgfhe_circuit_create_w, which takes no node_table)
+    int32_t plan_kinds(uint32_t max_kind, CircuitPlan &P) const {
+        return circuit_plan(spec_csr(max_kind, n_inputs, 0, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
+                                     max_kind >= 2 ? table.data() : nullptr, n_gates(), outputs.data(), out_shift.data(),
+                                     outputs.size(), group), P);
     }
-    int32_t plan_w(CircuitPlan &P) const {
-        return circuit_plan_w(n_inputs, kind.data(), start.data(), ref.data(), shift.data(), weight.data(), n_gates(),
-                              outputs.data(), out_shift.data(), outputs.size(), group, P);
-    }
+    int32_t plan(CircuitPlan &P) const { return plan_kinds(2, P); }
+    int32_t plan_w(CircuitPlan &P) const { return plan_kinds(1, P); }
 };
 
 static int32_t a_shift(uint32_t group) { return group > 1 ? (int32_t)rnd(2 * group - 1) - (int32_t)(group - 1) : 0; }
@@ -281,9 +281,9 @@ int main() {
         CircuitPlan Q;
         Q.n_inputs = 77;
         const size_t before = g_allocs;
-        CHECK(circuit_plan_lut(G.n_inputs, G.kind.data(), G.start.data(), G.ref.data(), G.shift.data(), G.weight.data(),
-                               nullptr, G.n_gates(), G.outputs.data(), G.out_shift.data(), G.outputs.size(), 1, Q) ==
-              SGFHE_ERR_INVALID_ARG && g_allocs == before && Q.n_inputs == 77);
+        CHECK(circuit_plan(spec_csr(2, G.n_inputs, 0, G.kind.data(), G.start.data(), G.ref.data(), G.shift.data(),
+                                    G.weight.data(), nullptr, G.n_gates(), G.outputs.data(), G.out_shift.data(),
+                                    G.outputs.size(), 1), Q) == SGFHE_ERR_INVALID_ARG && g_allocs == before && Q.n_inputs == 77);
     }
     printf("ok %zu\n", compared);
     return 0;

@@ -62,17 +62,17 @@ int main() {
         CircuitPlan P;
         const uint32_t own[2] = {2, 0}, later[4] = {0, 5, 0, 1}, past[2] = {0, 9}, notpast[2] = {0, 9u | CIRC_NOT};
         const uint32_t outs[1] = {2};
-        CHECK(circuit_plan(2, own, 1, outs, 1, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(2, later, 2, outs, 1, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(2, past, 1, outs, 1, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(2, notpast, 1, outs, 1, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(2, nullptr, 1, outs, 1, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(2, past, 0, outs, 0, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(2, past, 0, nullptr, 1, P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, own, 1, outs, 1), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, later, 2, outs, 1), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, past, 1, outs, 1), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, notpast, 1, outs, 1), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, nullptr, 1, outs, 1), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, past, 0, outs, 0), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, past, 0, nullptr, 1), P) == SGFHE_ERR_INVALID_ARG);
         const uint32_t bad_out[1] = {5};
-        CHECK(circuit_plan(2, past, 0, bad_out, 1, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(0x80000000u, past, 0, outs, 1, P) == SGFHE_ERR_INVALID_ARG);
-        CHECK(circuit_plan(0x7FFFFFF0u, past, 10, outs, 1, P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(2, past, 0, bad_out, 1), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(0x80000000u, past, 0, outs, 1), P) == SGFHE_ERR_INVALID_ARG);
+        CHECK(circuit_plan(spec_gates(0x7FFFFFF0u, past, 10, outs, 1), P) == SGFHE_ERR_INVALID_ARG);
     }
     for (cs = 0; cs < 3000; cs++) {
         const uint32_t n_inputs = below(cs % 10 == 0 ? 3 : 24);
@@ -83,7 +83,7 @@ int main() {
             for (int j = 0; j < 2; j++) gates[2 * g + j] = random_ref(n_inputs, g);
         for (auto &o : outs) o = random_ref(n_inputs, n_gates);
         CircuitPlan P;
-        CHECK(circuit_plan(n_inputs, gates.data(), n_gates, outs.data(), n_outputs, P) == SGFHE_OK);
+        CHECK(circuit_plan(spec_gates(n_inputs, gates.data(), n_gates, outs.data(), n_outputs), P) == SGFHE_OK);
         const uint32_t n_wires = n_inputs + 3 * n_gates;
         auto id_of = [](uint32_t ref) { return ref & ~CIRC_NOT; };
         auto node_of = [&](uint32_t id) -> int64_t {

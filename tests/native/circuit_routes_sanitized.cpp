@@ -44,6 +44,7 @@ void operator delete[](void *p, size_t) noexcept { free(p); }
 #endif
 
 #include "circuit.h"
+#include "circuit_tables.h"
 
 using namespace sgfhe;
 
@@ -75,18 +76,23 @@ struct Arrays {
     std::vector<uint32_t> kind, start, ref, table, outputs, next_ref, reg_scale, term_route, out_route, next_route;
     std::vector<int32_t> shift, weight, out_shift, next_shift, routes;
     size_t n_gates() const { return kind.size(); }
-    int32_t plan(CircuitPlan &P) const {
-        return circuit_plan_routed(n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                   table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, n_regs,
-                                   next_ref.data(), next_shift.data(), reg_scale.data(), n_routes, routes.data(),
-                                   term_route.data(), out_route.data(), next_route.data(), P);
+    // what sgfhe_circuit_create_seq fills, then (spec) the routes of sgfhe_circuit_create_routed
+    CircuitSpec spec_seq() const {
+        CircuitSpec S = spec_csr(5, n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
+                                 table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group);
+        S.regs.n_regs = n_regs, S.regs.next_ref = next_ref.data();
+        S.regs.next_shift = next_shift.data(), S.regs.reg_scale = reg_scale.data();
+        return S;
     }
+    CircuitSpec spec() const {
+        CircuitSpec S = spec_seq();
+        S.routes.n_routes = n_routes, S.routes.routes = routes.data(), S.routes.term_route = term_route.data();
+        S.routes.out_route = out_route.data(), S.routes.next_route = next_route.data();
+        return S;
+    }
+    int32_t plan(CircuitPlan &P) const { return circuit_plan(spec(), P); }
     // the same arrays without routes: every route index 0
-    int32_t plan_seq(CircuitPlan &P) const {
-        return circuit_plan_seq(n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, n_regs,
-                                next_ref.data(), next_shift.data(), reg_scale.data(), P);
-    }
+    int32_t plan_seq(CircuitPlan &P) const { return circuit_plan(spec_seq(), P); }
     bool lut(size_t g) const { return kind[g] >= 2; }
     bool sibling(size_t g) const { return kind[g] == 3 || kind[g] == 5; }
     bool data(size_t g) const { return kind[g] >= 4; }
@@ -294,10 +300,9 @@ static void no_routes_is_the_seq_plan(const Arrays &A0) {
     for (auto *v : {&A.term_route, &A.out_route, &A.next_route}) std::fill(v->begin(), v->end(), 0u);
     CircuitPlan P, N, Z;
     CHECK(A.plan(P) == SGFHE_OK && A.plan_seq(Z) == SGFHE_OK);
-    CHECK(circuit_plan_routed(A.n_inputs, A.n_planes, A.kind.data(), A.start.data(), A.ref.data(), A.shift.data(),
-                              A.weight.data(), A.table.data(), A.n_gates(), A.outputs.data(), A.out_shift.data(),
-                              A.outputs.size(), A.group, A.n_regs, A.next_ref.data(), A.next_shift.data(), A.reg_scale.data(),
-                              0, nullptr, nullptr, nullptr, nullptr, N) == SGFHE_OK);
+    CircuitSpec S = A.spec();
+    S.routes = CircuitRoutes();   // n_routes 0 and every array NULL
+    CHECK(circuit_plan(S, N) == SGFHE_OK);
     for (const CircuitPlan *Q : {&P, &N}) {
         CHECK(Q->n_routes == 0 && Q->levels == Z.levels && Q->slots == Z.slots && Q->n_regs == Z.n_regs);
         same(Q->image, Z.image), same(Q->order, Z.order), same(Q->out_node, Z.out_node), same(Q->jobs, Z.jobs);
@@ -411,11 +416,11 @@ int main() {
             const Arrays A = small();
             CircuitPlan P;
             P.slots = 77;
+            CircuitSpec S = A.spec();
+            S.nodes.n_planes = 0, S.regs = CircuitRegs();
+            S.routes.n_routes = 2, S.routes.routes = nullptr, S.routes.next_route = nullptr;
             const size_t before = g_allocs;
-            CHECK(circuit_plan_routed(A.n_inputs, 0, A.kind.data(), A.start.data(), A.ref.data(), A.shift.data(),
-                                      A.weight.data(), A.table.data(), A.n_gates(), A.outputs.data(), A.out_shift.data(),
-                                      A.outputs.size(), A.group, 0, nullptr, nullptr, nullptr, 2, nullptr, A.term_route.data(),
-                                      A.out_route.data(), nullptr, P) == SGFHE_ERR_INVALID_ARG);   // NULL routes
+            CHECK(circuit_plan(S, P) == SGFHE_ERR_INVALID_ARG);   // NULL routes
             CHECK(g_allocs == before && P.slots == 77);
         }
     }

@@ -43,6 +43,7 @@ void operator delete[](void *p, size_t) noexcept { free(p); }
 #endif
 
 #include "circuit.h"
+#include "circuit_tables.h"
 
 using namespace sgfhe;
 
@@ -74,21 +75,25 @@ struct Arrays {
     std::vector<uint32_t> kind, start, ref, table, outputs, next_ref, reg_scale;
     std::vector<int32_t> shift, weight, out_shift, next_shift;
     size_t n_gates() const { return kind.size(); }
-    int32_t plan(CircuitPlan &P) const {
-        return circuit_plan_seq(n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, n_regs,
-                                next_ref.data(), next_shift.data(), reg_scale.data(), P);
+    // what sgfhe_circuit_create_data fills, then (spec) the registers of sgfhe_circuit_create_seq
+    CircuitSpec spec_data() const {
+        return spec_csr(5, n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(), table.data(),
+                        n_gates(), outputs.data(), out_shift.data(), outputs.size(), group);
     }
+    CircuitSpec spec() const {
+        CircuitSpec S = spec_data();
+        S.regs.n_regs = n_regs, S.regs.next_ref = next_ref.data();
+        S.regs.next_shift = next_shift.data(), S.regs.reg_scale = reg_scale.data();
+        return S;
+    }
+    int32_t plan(CircuitPlan &P) const { return circuit_plan(spec(), P); }
     // the same with next_shift and reg_scale NULL
     int32_t plan_null(CircuitPlan &P) const {
-        return circuit_plan_seq(n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, n_regs,
-                                next_ref.data(), nullptr, nullptr, P);
+        CircuitSpec S = spec();
+        S.regs.next_shift = nullptr, S.regs.reg_scale = nullptr;
+        return circuit_plan(S, P);
     }
-    int32_t plan_data(CircuitPlan &P) const {
-        return circuit_plan_data(n_inputs, n_planes, kind.data(), start.data(), ref.data(), shift.data(), weight.data(),
-                                 table.data(), n_gates(), outputs.data(), out_shift.data(), outputs.size(), group, P);
-    }
+    int32_t plan_data(CircuitPlan &P) const { return circuit_plan(spec_data(), P); }
     // no registers, outputs = outputs ++ next_ref
     Arrays step() const {
         Arrays Z = *this;
@@ -366,10 +371,10 @@ int main() {
             const Arrays A = small();
             CircuitPlan P;
             P.slots = 77;
+            CircuitSpec S = A.spec();
+            S.nodes.n_planes = 0, S.regs.next_ref = nullptr, S.regs.next_shift = nullptr, S.regs.reg_scale = nullptr;
             const size_t before = g_allocs;
-            CHECK(circuit_plan_seq(A.n_inputs, 0, A.kind.data(), A.start.data(), A.ref.data(), A.shift.data(), A.weight.data(),
-                                   A.table.data(), A.n_gates(), A.outputs.data(), A.out_shift.data(), A.outputs.size(), A.group,
-                                   A.n_regs, nullptr, nullptr, nullptr, P) == SGFHE_ERR_INVALID_ARG);
+            CHECK(circuit_plan(S, P) == SGFHE_ERR_INVALID_ARG);   // NULL next_ref
             CHECK(g_allocs == before && P.slots == 77);
         }
         B = small(), B.next_shift = {3, -3};

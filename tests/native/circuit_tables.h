@@ -26,6 +26,31 @@
         }                                                                                             \
     } while (0)
 
+// The CircuitSpec an entry of the C ABI fills from its arrays.  spec_gates: sgfhe_circuit_create; spec_arity: the
+// [n_gates][arity] arrays of sgfhe_circuit_create_lanes (2) and sgfhe_circuit_create3 (3); spec_csr: the CSR arrays of
+// the entry that admits kinds 0 .. max_kind -- 1 sgfhe_circuit_create_w (no node_table), 2 _lut, 3 _lut_multi, 5 _data
+// (and its planes).  Registers and routes (_seq, _routed) are set by field: S.regs, S.routes.
+inline sgfhe::CircuitSpec spec_arity(int arity, uint32_t n_inputs, const uint32_t *gates, const int32_t *gate_shift,
+                                     size_t n_gates, const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs,
+                                     uint32_t group) {
+    sgfhe::CircuitSpec S;
+    S.n_inputs = n_inputs, S.nodes = sgfhe::circuit_nodes_arity(arity, gates, gate_shift), S.n_gates = n_gates;
+    S.outputs = outputs, S.out_shift = out_shift, S.n_outputs = n_outputs, S.group = group;
+    return S;
+}
+inline sgfhe::CircuitSpec spec_gates(uint32_t n_inputs, const uint32_t *gates, size_t n_gates, const uint32_t *outputs,
+                                     size_t n_outputs) {
+    return spec_arity(2, n_inputs, gates, nullptr, n_gates, outputs, nullptr, n_outputs, 1u);
+}
+inline sgfhe::CircuitSpec spec_csr(uint32_t max_kind, uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
+                                   const uint32_t *node_start, const uint32_t *term_ref, const int32_t *term_shift,
+                                   const int32_t *term_weight, const uint32_t *node_table, size_t n_gates,
+                                   const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group) {
+    sgfhe::CircuitSpec S = spec_arity(0, n_inputs, nullptr, nullptr, n_gates, outputs, out_shift, n_outputs, group);
+    S.nodes = sgfhe::circuit_nodes_csr(max_kind, node_kind, node_start, term_ref, term_shift, term_weight, node_table, n_planes);
+    return S;
+}
+
 // `count` terms refs[0 ..] / shifts[0 ..] (NULL: all 0) / weights[0 ..] (NULL: all 1) of the caller's node order[k]
 inline void check_node_terms(const sgfhe::CircuitPlan &P, size_t k, uint32_t kind, size_t count, const uint32_t *refs,
                              const int32_t *shifts, const int32_t *weights) {

@@ -109,8 +109,8 @@ static Arrays random_circuit(uint32_t n_inputs, uint32_t n_gates, uint32_t n_out
 }
 
 static int32_t plan_w(const Arrays &A, uint32_t G, CircuitPlan &P) {
-    return circuit_plan_w(A.n_inputs, A.kind.data(), A.start.data(), A.refs.data(), A.shift.data(), A.weight.data(),
-                          A.gates(), A.outs.data(), A.oshift.data(), A.outs.size(), G, P);
+    return circuit_plan(spec_csr(1, A.n_inputs, 0, A.kind.data(), A.start.data(), A.refs.data(), A.shift.data(),
+                                 A.weight.data(), nullptr, A.gates(), A.outs.data(), A.oshift.data(), A.outs.size(), G), P);
 }
 
 // the model of include/sgfhe_hip.h, one instance at a time
@@ -202,7 +202,8 @@ static void check_unit_is_create3(uint32_t G) {
         }
     CircuitPlan P, Z;
     CHECK(plan_w(A, G, P) == SGFHE_OK);
-    CHECK(circuit_plan3(n_inputs, g3.data(), s3.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G, Z) == SGFHE_OK);
+    CHECK(circuit_plan(spec_arity(3, n_inputs, g3.data(), s3.data(), n_gates, A.outs.data(), A.oshift.data(), n_outputs, G),
+                       Z) == SGFHE_OK);
     check_plan_tables(P);
     check_plan_tables(Z);
     CHECK(P.levels == Z.levels && P.widest == Z.widest && P.slots == Z.slots && P.group == Z.group);
@@ -242,7 +243,7 @@ static void check_rejected() {
     auto refused = [&](const uint32_t *k, const uint32_t *s, const uint32_t *r, const int32_t *sh, const int32_t *w,
                        const uint32_t *o, uint32_t group) {
         const size_t before = g_allocs;
-        const int32_t rc = circuit_plan_w(2, k, s, r, sh, w, 2, o, nullptr, 2, group, P);
+        const int32_t rc = circuit_plan(spec_csr(1, 2, 0, k, s, r, sh, w, nullptr, 2, o, nullptr, 2, group), P);
         CHECK(rc == SGFHE_ERR_INVALID_ARG && g_allocs == before && P.n_inputs == 77 && P.order.empty());
     };
     for (int32_t bad : {0, 3, -3, INT32_MIN, INT32_MAX}) {   // weights
@@ -288,13 +289,14 @@ static void check_rejected() {
         sh64[2] = 7, sh64[3] = -7;
         r65[4] = CIRC_FALSE | CIRC_NOT, sh64[4] = 5;
         for (size_t i = 2; i < 66; i++) w65[i] = (i & 1) ? -2 : 2;
-        CHECK(circuit_plan_w(2, kind, s64, r65.data(), sh64.data(), w65.data(), 2, outs, nullptr, 2, 8, P) == SGFHE_OK);
+        CHECK(circuit_plan(spec_csr(1, 2, 0, kind, s64, r65.data(), sh64.data(), w65.data(), nullptr, 2, outs, nullptr, 2, 8),
+                           P) == SGFHE_OK);
         CHECK(P.node_kind[0] == 1 && P.n_inputs == 2 && P.live() == 1 && P.term_row.size() == 64);   // (node 0 is pruned)
         CHECK(P.term_shift[0] == 7 && P.term_shift[1] == -7 && P.term_shift[2] == 0 && P.out_node[0] == 0 && P.out_node[1] == CIRC_NONE);
         for (size_t i = 0; i < 64; i++) CHECK(P.term_weight[i] == w65[2 + i]);
         check_plan_tables(P);
     }
-    CHECK(circuit_plan_w(2, kind, start, refs, nullptr, weight, 2, outs, nullptr, 2, 1, P) == SGFHE_OK);
+    CHECK(circuit_plan(spec_csr(1, 2, 0, kind, start, refs, nullptr, weight, nullptr, 2, outs, nullptr, 2, 1), P) == SGFHE_OK);
     CHECK(P.sum_before[2] == 1 && P.levels == 2 && P.live() == 2 && P.term_start[2] == 5 && P.term_row.size() == 5);
 }
 

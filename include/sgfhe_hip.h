@@ -1121,6 +1121,57 @@ int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_
                                    uint64_t *state_lwe /* [n_regs][blocks * n][n + 1], optional */, uint32_t flags);
 
 /*
+ * Device-resident runs: every run form with its inputs and outputs in device memory, asynchronous, with the contract
+ * of sgfhe_bootstrap_batch_device.  Each entry is the most general host entry of its form -- sgfhe_circuit_run_data,
+ * sgfhe_circuit_run_ct_data, sgfhe_circuit_run_steps, sgfhe_circuit_run_steps_ct -- plus a trailing `stream`.  A
+ * packed output or a state_out of one run is the input of the next without leaving the device, and public LWE glue
+ * between two runs (NOT, select, concatenate) is the caller's own device code on the same stream.
+ *
+ * Pointers.  Every array is device memory on the ctx's device, in the shape and layout of the host entry, `data`
+ * included.  The one exception is `emit`: it steers the host loop, stays a host array and is read before the call
+ * returns.  Pointer kinds are not validated (as in sgfhe_bootstrap_batch_device).  `data` may be NULL for a plan
+ * without planes; a plan with planes goes through these entries only with `data`, a plan with registers through the
+ * _steps entries only.
+ *
+ * Asynchronous, stream-ordered.  The work is queued on `stream` (a hipStream_t, NULL = the ctx's own), behind
+ * everything earlier calls queued on this ctx on any stream, and the call returns when it is queued.  The outputs are
+ * complete when that stream reaches the end of the call's work; sgfhe_sync waits for it on the host.  The inputs,
+ * `data` and the circuit must stay alive until then (the circuit's tables go up by an asynchronous copy).  The ctx is
+ * locked while the call queues.  A run whose ctx buffers are large enough waits for nothing on the host; a run that
+ * must regrow one (the wire table, the call staging, the lanes' work buffers ...) first waits for the work queued on
+ * the ctx, as a larger sgfhe_bootstrap_batch_device does.
+ *
+ * Bytes.  Every output word is the word the host entry writes for the same arguments on the same ctx state, in both
+ * flatten modes and under every flag set, and the call consumes the same call numbers of the draw stream.
+ * instances / blocks / steps = 0 does nothing and consumes nothing.
+ *
+ * No staging.  The LWE outputs are collected straight into `out` / `out_lwe`, the ciphertexts are split where they
+ * are; inputs, state and planes, (w, v) and state_out are device-to-device copies on the run's stream.
+ *
+ * Aliasing.  No output range may overlap an input range, with one exception: state_out == state_in exactly.  The
+ * state is read in full into the ctx's state buffer before anything is written, so a caller may keep one state array
+ * and feed a stream chunk by chunk.
+ *
+ * Errors.  Everything the host entry rejects is rejected with the same code before anything is queued or written and
+ * before a call number is taken.  Should queueing fail part way, the entry waits for the stream and returns the
+ * error; the outputs are then unspecified.  The probe entries have no device form: they need host tables.
+ */
+int32_t sgfhe_circuit_run_device(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, const uint64_t *in,
+                                 const uint8_t *data, uint64_t *out, void *stream);
+int32_t sgfhe_circuit_run_ct_device(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, const uint64_t *in_a,
+                                    const uint64_t *in_b, size_t N, const uint8_t *data, uint64_t *out_w,
+                                    uint64_t *out_v, uint64_t *out_lwe, uint32_t flags, void *stream);
+int32_t sgfhe_circuit_run_steps_device(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t instances, size_t steps,
+                                       const uint64_t *state_in, const uint64_t *in, const uint8_t *data,
+                                       const uint8_t *emit /* host */, uint64_t *out, uint64_t *state_out,
+                                       void *stream);
+int32_t sgfhe_circuit_run_steps_ct_device(sgfhe_ctx *ctx, const sgfhe_circuit *c, size_t blocks, size_t steps,
+                                          const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
+                                          const uint64_t *in_b, size_t N, const uint8_t *data,
+                                          const uint8_t *emit /* host */, uint64_t *out_w, uint64_t *out_v,
+                                          uint64_t *out_lwe, uint64_t *state_lwe, uint32_t flags, void *stream);
+
+/*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled
  * launches of the two per-iteration kernels since the last reset (stats must hold 8 doubles).
  *   stats[0] = average external-product kernel time (ms)   stats[1] = its sampled launches

@@ -173,6 +173,10 @@ def lib():
         "sgfhe_circuit_create_routed": (i32, [u32, u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, u32, vp, vp, vp,
                                               u32, vp, vp, vp, vp, ctypes.POINTER(vp)]),
         "sgfhe_circuit_routes": (i32, [vp, _u32p]),
+        "sgfhe_circuit_run_device": (i32, [vp, vp, sz, vp, vp, vp, vp]),
+        "sgfhe_circuit_run_ct_device": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, vp]),
+        "sgfhe_circuit_run_steps_device": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]),
+        "sgfhe_circuit_run_steps_ct_device": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -203,4 +207,5 @@ EXPORTED_SYMBOLS = (
     "sgfhe_bootstrap_lut_multi_batch", "sgfhe_circuit_create_lut_multi", "sgfhe_circuit_create_data",
     "sgfhe_circuit_planes", "sgfhe_circuit_run_data", "sgfhe_circuit_run_ct_data", "sgfhe_circuit_run_probe_data",
     "sgfhe_circuit_create_seq", "sgfhe_circuit_registers", "sgfhe_circuit_run_steps", "sgfhe_circuit_run_steps_ct",
-    "sgfhe_circuit_create_routed", "sgfhe_circuit_routes")
+    "sgfhe_circuit_create_routed", "sgfhe_circuit_routes", "sgfhe_circuit_run_device", "sgfhe_circuit_run_ct_device",
+    "sgfhe_circuit_run_steps_device", "sgfhe_circuit_run_steps_ct_device")

@@ -1559,9 +1559,13 @@ static void free_io_buffers(sgfhe_ctx *c) {
     c->pin_out.release();
 }
 
-// DevBuf::grow for the circuit and pack paths: out of device memory is their caller's error to handle
+// DevBuf::grow for the circuit and pack paths: out of device memory is their caller's error to handle.  A buffer that
+// grows is freed first, so the host waits for the ctx's queued work before it does, and only then, as ensure_work does
+// (a device-resident run arrives here with earlier runs still in flight; behind run_drained there is nothing to wait for)
 extern "C++" template <typename T>
 static int32_t circ_grow(sgfhe_ctx *c, DevBuf<T> &buf, size_t words) {
+    if (words <= buf.cap) return SGFHE_OK;
+    if (const int32_t rc = drain(c)) return rc;
     if (buf.grow(words) == hipSuccess) return SGFHE_OK;
     return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run: hipMalloc of " + std::to_string(words * sizeof(T)) +
                                       " bytes failed");
@@ -1577,6 +1581,21 @@ static int32_t run_drained(sgfhe_ctx *c, F &&queued) {
     if (rc) return rc;
     if ((rc = queued())) {
         (void)hipStreamSynchronize(c->stream);
+        c->pending = false;
+    }
+    return rc;
+}
+
+// An asynchronous entry, after its checks: `queued` queues on `st` behind the ctx's earlier work and returns with its
+// own work in flight (fence_begin ... fence_end are its own to place: it may regrow ctx buffers first).  Should it fail
+// part way, the host waits for the earlier work and for whatever was queued on `st`, as run_drained does.
+extern "C++" template <class F>
+static int32_t run_queued(sgfhe_ctx *c, hipStream_t st, F &&queued) {
+    (void)hipSetDevice(c->device);
+    const int32_t rc = queued();
+    if (rc) {
+        if (c->pending) (void)hipEventSynchronize(c->ev_done);
+        (void)hipStreamSynchronize(st);
         c->pending = false;
     }
     return rc;
@@ -3218,7 +3237,11 @@ struct CircuitRun {
     CircuitProbe *probe;
     const uint8_t *data;
     const CircuitSteps *seq = nullptr;   // a stepped run (run_steps)
-    const hipStream_t st = c->stream;
+    // The device-resident form (sgfhe_circuit_run*_device): every array of the caller's (but seq->emit) is device
+    // memory, the run is queued on the caller's stream between fence_begin and fence_end, and the host waits for
+    // nothing.  The host form: the ctx's own stream, drained before the run (run_drained) and waited for at its end.
+    const bool device;
+    const hipStream_t st;
     const size_t n = c->n, row = n + 1, M = c->M;   // row: words of an LWE
     const uint32_t inst = (uint32_t)instances;
     const uint64_t r = c->par.r;
@@ -3240,8 +3263,10 @@ struct CircuitRun {
     std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
 
     CircuitRun(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in, uint64_t *out,
-               const CircuitCt *ct, CircuitProbe *probe, const uint8_t *data)
-        : c(c), P(P), instances(instances), in(in), out(out), ct(ct), probe(probe), data(P.n_planes ? data : nullptr) {}
+               const CircuitCt *ct, CircuitProbe *probe, const uint8_t *data, bool device = false,
+               hipStream_t stream = nullptr)
+        : c(c), P(P), instances(instances), in(in), out(out), ct(ct), probe(probe), data(P.n_planes ? data : nullptr),
+          device(device), st(device && stream ? stream : c->stream) {}
 
     int32_t grow();
     int32_t upload_tables();
@@ -3264,6 +3289,23 @@ struct CircuitRun {
     }
     int32_t fetch(uint64_t *o, uint64_t *w, uint64_t *v);
     int32_t download();
+    // The caller's arrays, one helper per direction, so that the stages read the same in both forms: `src` into a ctx
+    // buffer, a ctx buffer into `dst`, queued on `st` (host form: from and to host memory; device form: device to device)
+    int32_t copy_in(void *d_dst, const void *src, size_t bytes) {
+        HIPCHK(c, hipMemcpyAsync(d_dst, src, bytes, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        return SGFHE_OK;
+    }
+    int32_t copy_out(void *dst, const void *d_src, size_t bytes) {
+        HIPCHK(c, hipMemcpyAsync(dst, d_src, bytes, device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        return SGFHE_OK;
+    }
+    // the end of a run that has queued everything: the host form waits for it, the device form leaves it in flight
+    int32_t finish() {
+        if (device) return fence_end(c, st);
+        HIPCHK(c, hipStreamSynchronize(st));
+        c->pending = false;
+        return SGFHE_OK;
+    }
     int32_t run();
     // a stepped run
     int32_t upload_state();
@@ -3294,17 +3336,19 @@ struct CircuitRun {
     bool has_lut() const { return P.lut_before[P.live()] != 0; }
 };
 
-// every buffer before anything is queued (a regrown buffer waits for nothing: drained by the caller), and the probe's
-// host images
+// every buffer before anything is queued (host form: a regrown buffer waits for nothing, drained by the caller; device
+// form: circ_grow and ensure_work wait for the ctx's queued work where a buffer grows, and nowhere else), and the
+// probe's host images.  The device form stages neither the collected outputs nor the ciphertexts: the kernels write
+// and read the caller's arrays in place.
 int32_t CircuitRun::grow() {
     int32_t rc;
     if ((rc = circ_grow(c, c->circ_wires, (size_t)P.slots * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_stage, stage_words() + (has_lut() ? ((size_t)sz.max_rows + 1) / 2 : 0)))) return rc;
     if (direct && (rc = circ_grow(c, c->circ_raw, sz.n_ct * n * row))) return rc;
-    if (out && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
+    if (out && !device && (rc = circ_grow(c, c->circ_out, (size_t)P.n_outputs * instances * row))) return rc;
     if ((rc = circ_grow(c, c->circ_tab, P.at.words))) return rc;
     if (data && (rc = circ_grow(c, c->circ_data, (size_t)P.n_planes * instances))) return rc;
-    if ((rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
+    if (!device && (rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
     if (seq && (rc = circ_grow(c, c->circ_state, state_words()))) return rc;
     if (pack && (rc = pack_grow(c, sz.cpc, sz.n_ct, sz.max_ref))) return rc;
     if (probe) {
@@ -3341,7 +3385,7 @@ int32_t CircuitRun::grow() {
 int32_t CircuitRun::upload_tables() {
     HIPCHK(c, hipMemcpyAsync(c->circ_tab.p, P.image.data(), (size_t)P.at.words * 4, hipMemcpyHostToDevice, st));
     if (data && !seq)   // (a stepped run brings planes with every step: upload_step)
-        HIPCHK(c, hipMemcpyAsync(c->circ_data.p, data, (size_t)P.n_planes * instances, hipMemcpyHostToDevice, st));
+        if (const int32_t rc = copy_in(c->circ_data.p, data, (size_t)P.n_planes * instances)) return rc;
     const uint32_t *tab = c->circ_tab.p;
     nodes = {tab + P.at.node_kind, tab + P.at.term_start, reinterpret_cast<const int32_t *>(tab + P.at.term_weight),
              refs_at(P.at.term_ref, P.at.term_shift, P.at.term_route)};
@@ -3362,16 +3406,20 @@ int32_t CircuitRun::upload_tables() {
 // ciphertext form: the ciphertexts as they are, and extract() of every bit into the slot of its input wire
 int32_t CircuitRun::upload_ct() { return split(ct->in_a, ct->in_b, P.n_inputs, d_in_slot, c->circ_wires.p); }
 
-// `count` wires of ciphertexts a, b [count][blocks][N] (host) split into the slots slot[0 .. count) (device) of `rows`
-// ([slot][instances][n + 1])
+// `count` wires of ciphertexts a, b [count][blocks][N] (the caller's) split into the slots slot[0 .. count) (device) of
+// `rows` ([slot][instances][n + 1]): uploaded into circ_ct first, or -- device form -- read where they are
 int32_t CircuitRun::split(const uint64_t *a, const uint64_t *b, uint32_t count, const uint32_t *slot, uint64_t *rows) {
     if (!count) return SGFHE_OK;
     const size_t words = (size_t)count * ct->blocks * ct->N;
-    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p, a, words * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->circ_ct.p + words, b, words * 8, hipMemcpyHostToDevice, st));
+    if (!device) {
+        int32_t rc;
+        if ((rc = copy_in(c->circ_ct.p, a, words * 8))) return rc;
+        if ((rc = copy_in(c->circ_ct.p + words, b, words * 8))) return rc;
+        a = c->circ_ct.p, b = c->circ_ct.p + words;
+    }
     const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
     hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(count * ct->blocks * tiles)), dim3(256),
-                       (n + CIRC_SPLIT_ROWS - 1) * 8, st, c->circ_ct.p, c->circ_ct.p + words, slot, rows,
+                       (n + CIRC_SPLIT_ROWS - 1) * 8, st, a, b, slot, rows,
                        (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
     HIPCHK(c, hipGetLastError());
     return SGFHE_OK;
@@ -3384,8 +3432,9 @@ int32_t CircuitRun::copy_inputs(uint32_t first, const uint64_t *src) {   // inpu
         if (P.input_slot[i] == CIRC_NONE) { i++; continue; }
         uint32_t k = i + 1;
         while (k < P.n_inputs && P.input_slot[k] == P.input_slot[k - 1] + 1) k++;
-        HIPCHK(c, hipMemcpyAsync(c->circ_wires.p + (size_t)P.input_slot[i] * in_words, src + (size_t)(i - first) * in_words,
-                                 (size_t)(k - i) * in_words * 8, hipMemcpyHostToDevice, st));
+        if (const int32_t rc = copy_in(c->circ_wires.p + (size_t)P.input_slot[i] * in_words,
+                                       src + (size_t)(i - first) * in_words, (size_t)(k - i) * in_words * 8))
+            return rc;
         i = k;
     }
     return SGFHE_OK;
@@ -3522,13 +3571,13 @@ int32_t CircuitRun::pack_group(size_t q0) {
     return pack_tail(c, c->circ_raw.p + q0 * n * row, (uint32_t)row, cnt, d_w, d_v, call, st);
 }
 
-// (w, v) of every ciphertext, the outputs in the LWE form, the probe's records; then the host waits
+// (w, v) of every ciphertext, the outputs in the LWE form, the probe's records; then the host waits (host form)
 int32_t CircuitRun::download() {
-    if (const int32_t rc = fetch(out, ct ? ct->out_w : nullptr, ct ? ct->out_v : nullptr)) return rc;
+    int32_t rc;
+    if ((rc = fetch(out, ct ? ct->out_w : nullptr, ct ? ct->out_v : nullptr))) return rc;
     if (probe && probe_rows)
         HIPCHK(c, hipMemcpyAsync(probe->down.data(), NL.stats, probe_rows * 64, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->pending = false;
+    if ((rc = finish())) return rc;
     if (probe) {   // records by wire id; the wires of pruned nodes stay zero
         std::fill(probe->stats, probe->stats + ((size_t)P.n_inputs + 3 * (size_t)P.n_gates) * 8, 0ull);
         for (size_t w = 0; w < probe_rows; w++)
@@ -3539,19 +3588,20 @@ int32_t CircuitRun::download() {
 }
 
 // the outputs of the wire table as it stands, queued: (w, v) of the packed ciphertexts (a run that packs) and the
-// collected LWEs (`o` NULL: not wanted)
+// collected LWEs (`o` NULL: not wanted), which the device form collects straight into `o`
 int32_t CircuitRun::fetch(uint64_t *o, uint64_t *w, uint64_t *v) {
+    int32_t rc;
     if (pack) {
         const size_t wv = sz.n_ct * M;
-        HIPCHK(c, hipMemcpyAsync(w, c->pack_wv.p, wv * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(v, c->pack_wv.p + wv, wv * 8, hipMemcpyDeviceToHost, st));
+        if ((rc = copy_out(w, c->pack_wv.p, wv * 8))) return rc;
+        if ((rc = copy_out(v, c->pack_wv.p + wv, wv * 8))) return rc;
     }
     if (o) {
         const size_t total = (size_t)P.n_outputs * instances * row;
-        hipLaunchKernelGGL(k_circ_collect, dim3(copy_grid(total)), dim3(256), 0, st, c->circ_wires.p, outs, c->circ_out.p,
-                           total, inst, (uint32_t)n, r);
+        hipLaunchKernelGGL(k_circ_collect, dim3(copy_grid(total)), dim3(256), 0, st, c->circ_wires.p, outs,
+                           device ? o : c->circ_out.p, total, inst, (uint32_t)n, r);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(o, c->circ_out.p, total * 8, hipMemcpyDeviceToHost, st));
+        if (!device && (rc = copy_out(o, c->circ_out.p, total * 8))) return rc;
     }
     return SGFHE_OK;
 }
@@ -3562,10 +3612,9 @@ int32_t CircuitRun::fetch(uint64_t *o, uint64_t *w, uint64_t *v) {
 int32_t CircuitRun::upload_state() {
     if (!P.n_regs) return SGFHE_OK;
     if (ct && seq->state_a) return split(seq->state_a, seq->state_b, P.n_regs, d_reg_index, c->circ_state.p);
-    if (!ct && seq->state_in)
-        HIPCHK(c, hipMemcpyAsync(c->circ_state.p, seq->state_in, state_words() * 8, hipMemcpyHostToDevice, st));
-    else
-        HIPCHK(c, hipMemsetAsync(c->circ_state.p, 0, state_words() * 8, st));
+    if (!ct && seq->state_in)   // (read in full before anything is written: state_out may be this very array)
+        return copy_in(c->circ_state.p, seq->state_in, state_words() * 8);
+    HIPCHK(c, hipMemsetAsync(c->circ_state.p, 0, state_words() * 8, st));
     return SGFHE_OK;
 }
 
@@ -3586,7 +3635,7 @@ int32_t CircuitRun::upload_step(size_t s) {
     if (rc) return rc;
     if (data) {
         const size_t per = (size_t)P.n_planes * instances;
-        HIPCHK(c, hipMemcpyAsync(c->circ_data.p, data + s * per, per, hipMemcpyHostToDevice, st));
+        return copy_in(c->circ_data.p, data + s * per, per);
     }
     return SGFHE_OK;
 }
@@ -3601,10 +3650,12 @@ int32_t CircuitRun::feedback() {
 }
 
 // Every step is the run() of the step plan: its level calls, then -- an emitted step -- its pack groups and its
-// outputs, taken before the feedback.  Everything is queued on the one stream; the host waits once, at the end.
+// outputs, taken before the feedback.  Everything is queued on the one stream; the host waits once, at the end (host
+// form), or not at all.
 int32_t CircuitRun::run_steps() {
     int32_t rc;
     if ((rc = grow())) return rc;
+    if (device && (rc = fence_begin(c, st))) return rc;
     if ((rc = upload_tables())) return rc;
     if ((rc = upload_state())) return rc;
     const size_t out_words = (size_t)P.n_outputs * instances * row, wv = sz.n_ct * M;
@@ -3620,17 +3671,15 @@ int32_t CircuitRun::run_steps() {
         }
         if ((rc = feedback())) return rc;
     }
-    if (seq->state_out && P.n_regs)
-        HIPCHK(c, hipMemcpyAsync(seq->state_out, c->circ_state.p, state_words() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->pending = false;
-    return SGFHE_OK;
+    if (seq->state_out && P.n_regs && (rc = copy_out(seq->state_out, c->circ_state.p, state_words() * 8))) return rc;
+    return finish();
 }
 
 int32_t CircuitRun::run() {
     int32_t rc;
     if (seq) return run_steps();
     if ((rc = grow())) return rc;
+    if (device && (rc = fence_begin(c, st))) return rc;   // (after grow: a buffer that grew has drained the ctx)
     if ((rc = upload_tables())) return rc;
     if ((rc = ct ? upload_ct() : upload_lwe())) return rc;
     if ((rc = level_calls())) return rc;
@@ -3652,9 +3701,17 @@ static int32_t circuit_data_ok(sgfhe_ctx *c, const sgfhe_circuit *circ, bool wit
     return SGFHE_OK;
 }
 
-// sgfhe_circuit_run[_data], with `probe` the run of sgfhe_circuit_run_probe[_data]
+// The run of an entry whose checks have passed: the host form behind a drained ctx, waited for; the device form
+// (`device`, on `st`: sgfhe_circuit_run*_device) queued behind the ctx's work and left in flight
+extern "C++" template <class F>
+static int32_t circuit_run_form(sgfhe_ctx *c, bool device, hipStream_t st, F &&body) {
+    return device ? run_queued(c, st ? st : c->stream, body) : run_drained(c, body);
+}
+
+// sgfhe_circuit_run[_data], with `probe` the run of sgfhe_circuit_run_probe[_data]; sgfhe_circuit_run_device (`device`)
 static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
-                               uint64_t *out, CircuitProbe *probe, bool with_data = false, const uint8_t *data = nullptr) {
+                               uint64_t *out, CircuitProbe *probe, bool with_data = false, const uint8_t *data = nullptr,
+                               bool device = false, hipStream_t st = nullptr) {
     if (!circ || !out || (!in && circ->plan.n_inputs))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: NULL circuit, input or output pointer");
     if (const int32_t rd = circuit_data_ok(c, circ, with_data, data, instances)) return rd;
@@ -3671,7 +3728,8 @@ static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t i
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
     if (instances % P.group)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: instances must be a multiple of the circuit's lane group");
-    return run_drained(c, [&] { return CircuitRun(c, P, instances, in, out, nullptr, probe, data).run(); });
+    return circuit_run_form(c, device, st,
+                            [&] { return CircuitRun(c, P, instances, in, out, nullptr, probe, data, device, st).run(); });
 }
 
 int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
@@ -3798,7 +3856,8 @@ int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blo
 // sgfhe_circuit_run_ct_ex and sgfhe_circuit_run_ct_data (`with_data`), the ctx locked
 static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                               const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
-                              uint32_t flags, bool with_data, const uint8_t *data);
+                              uint32_t flags, bool with_data, const uint8_t *data, bool device = false,
+                              hipStream_t st = nullptr);
 
 int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                                 const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
@@ -3818,7 +3877,7 @@ int32_t sgfhe_circuit_run_ct_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_
 
 static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                               const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
-                              uint32_t flags, bool with_data, const uint8_t *data) {
+                              uint32_t flags, bool with_data, const uint8_t *data, bool device, hipStream_t st) {
     // (bit 1 without bit 0 was an unknown bit before SGFHE_CIRCUIT_PACK_LIFT existed, and stays refused)
     if ((flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || flags == SGFHE_CIRCUIT_PACK_LIFT)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct_ex: unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
@@ -3846,14 +3905,15 @@ static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t bl
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: n must be a multiple of the circuit's lane group");
     const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
                           (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
-    return run_drained(c, [&] { return CircuitRun(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data).run(); });
+    return circuit_run_form(c, device, st, [&] {
+        return CircuitRun(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data, device, st).run();
+    });
 }
 
-int32_t sgfhe_circuit_run_steps(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
-                                const uint64_t *state_in, const uint64_t *in, const uint8_t *data, const uint8_t *emit,
-                                uint64_t *out, uint64_t *state_out) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+// sgfhe_circuit_run_steps and sgfhe_circuit_run_steps_device (`device`), the ctx locked
+static int32_t circuit_run_steps(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
+                                 const uint64_t *state_in, const uint64_t *in, const uint8_t *data, const uint8_t *emit,
+                                 uint64_t *out, uint64_t *state_out, bool device, hipStream_t st) {
     if (!circ || (!in && circ->plan.n_stream()) || (!out && !state_out))
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: NULL circuit or input pointer, or no output pointer");
     const CircuitPlan &P = circ->plan;
@@ -3867,12 +3927,27 @@ int32_t sgfhe_circuit_run_steps(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t 
     if (instances % P.group)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: instances must be a multiple of the circuit's lane group");
     const CircuitSteps seq = {steps, emit, state_in, nullptr, nullptr, state_out};
-    return run_drained(c, [&] {
-        CircuitRun R(c, P, instances, in, out, nullptr, nullptr, data);
+    return circuit_run_form(c, device, st, [&] {
+        CircuitRun R(c, P, instances, in, out, nullptr, nullptr, data, device, st);
         R.seq = &seq;
         return R.run();
     });
 }
+
+int32_t sgfhe_circuit_run_steps(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
+                                const uint64_t *state_in, const uint64_t *in, const uint8_t *data, const uint8_t *emit,
+                                uint64_t *out, uint64_t *state_out) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    return circuit_run_steps(c, circ, instances, steps, state_in, in, data, emit, out, state_out, false, nullptr);
+}
+
+// sgfhe_circuit_run_steps_ct and sgfhe_circuit_run_steps_ct_device (`device`), the ctx locked
+static int32_t circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
+                                    const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
+                                    const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit,
+                                    uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
+                                    uint32_t flags, bool device, hipStream_t st);
 
 int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
                                    const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
@@ -3881,6 +3956,15 @@ int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size
                                    uint32_t flags) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
     SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
+    return circuit_run_steps_ct(c, circ, blocks, steps, state_a, state_b, in_a, in_b, N, data, emit, out_w, out_v, out_lwe,
+                                state_lwe, flags, false, nullptr);
+}
+
+static int32_t circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
+                                    const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
+                                    const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit,
+                                    uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
+                                    uint32_t flags, bool device, hipStream_t st) {
     if ((flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || flags == SGFHE_CIRCUIT_PACK_LIFT)
         return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
     if (!circ || ((!in_a || !in_b) && circ->plan.n_stream()) || !state_a != !state_b)
@@ -3911,11 +3995,50 @@ int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size
     const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
                           (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
     const CircuitSteps seq = {steps, emit, nullptr, state_a, state_b, state_lwe};
-    return run_drained(c, [&] {
-        CircuitRun R(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data);
+    return circuit_run_form(c, device, st, [&] {
+        CircuitRun R(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data, device, st);
         R.seq = &seq;
         return R.run();
     });
+}
+
+// ---- device-resident runs: the most general host entry of each form, every array (but `emit`) in device memory, the
+// work queued on `stream` (NULL: the ctx's own) and left in flight (include/sgfhe_hip.h) ----------------------------
+
+int32_t sgfhe_circuit_run_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                                 const uint8_t *data, uint64_t *out, void *stream) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
+    return circuit_run_lwe(c, circ, instances, in, out, nullptr, true, data, true, (hipStream_t)stream);
+}
+
+int32_t sgfhe_circuit_run_ct_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
+                                    const uint64_t *in_b, size_t N, const uint8_t *data, uint64_t *out_w, uint64_t *out_v,
+                                    uint64_t *out_lwe, uint32_t flags, void *stream) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
+    return circuit_run_ct(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, flags, true, data, true,
+                          (hipStream_t)stream);
+}
+
+int32_t sgfhe_circuit_run_steps_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
+                                       const uint64_t *state_in, const uint64_t *in, const uint8_t *data,
+                                       const uint8_t *emit, uint64_t *out, uint64_t *state_out, void *stream) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
+    return circuit_run_steps(c, circ, instances, steps, state_in, in, data, emit, out, state_out, true,
+                             (hipStream_t)stream);
+}
+
+int32_t sgfhe_circuit_run_steps_ct_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
+                                          const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
+                                          const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit,
+                                          uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
+                                          uint32_t flags, void *stream) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
+    return circuit_run_steps_ct(c, circ, blocks, steps, state_a, state_b, in_a, in_b, N, data, emit, out_w, out_v, out_lwe,
+                                state_lwe, flags, true, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -52,6 +52,39 @@ def _c(arr, dtype=np.uint64):
     return a, a.ctypes.data_as(ctypes.c_void_p)
 
 
+def check_device_tensor(name, t, shape, device, words=True):
+    """An argument of the device-resident circuit runs (Engine.circuit_run_device and its kin), checked before any
+    library call; needs no engine and no GPU.  `t` must be a torch.Tensor of dtype int64 or uint64 (words=True: LWE
+    and ciphertext words) or uint8 (words=False: data planes), C-contiguous, of shape `shape` (an entry None matches
+    any length), on the device `device` (an index: cuda:<device>).  ValueError otherwise.  Returns t."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: a torch.Tensor is needed, got %s" % (name, type(t).__name__))
+    dtypes = (torch.int64, torch.uint64) if words else (torch.uint8,)
+    if t.dtype not in dtypes:
+        raise ValueError("%s: dtype must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if not t.is_contiguous():
+        raise ValueError("%s: the tensor must be contiguous" % name)
+    if t.dim() != len(shape) or any(w is not None and int(w) != int(g) for w, g in zip(shape, t.shape)):
+        raise ValueError("%s: shape must be %r, got %r" % (name, tuple(shape), tuple(t.shape)))
+    if t.device.type == "cpu":
+        raise ValueError("%s: a CPU tensor; the device-resident runs take tensors on cuda:%d" % (name, device))
+    if t.device.type != "cuda" or t.device.index != device:
+        raise ValueError("%s: the tensor is on %s, the engine on cuda:%d" % (name, t.device, device))
+    return t
+
+
+def _stream_handle(hip_stream):
+    """A torch.cuda.Stream, a raw hipStream_t (int) or None (the ctx's own stream) as the C ABI's `void *stream`."""
+    if hip_stream is None:
+        return ctypes.c_void_p(0)
+    return ctypes.c_void_p(int(getattr(hip_stream, "cuda_stream", hip_stream)))
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
 class Engine:
     """One bootstrap engine (ctx) for one parameter set on one HIP device."""
 
@@ -417,12 +450,17 @@ class Engine:
         if d is not None:
             d = np.ascontiguousarray(d)
             pd = d.ctypes.data_as(ctypes.c_void_p)
+        return (d, pd) + Engine._emit_arg(emit, steps)
+
+    @staticmethod
+    def _emit_arg(emit, steps):
+        """(emit array, its pointer, emitted steps) of a stepped run; emit None: every step."""
         if emit is None:
-            return d, pd, None, None, steps
+            return None, None, steps
         e = np.ascontiguousarray(np.asarray(emit).astype(bool).astype(np.uint8))
         if e.shape != (steps,):
             raise ValueError("emit: one flag per step (%d)" % steps)
-        return d, pd, e, e.ctypes.data_as(ctypes.c_void_p), int(e.sum())
+        return e, e.ctypes.data_as(ctypes.c_void_p), int(e.sum())
 
     def circuit_run_steps(self, circuit, state, stream, data=None, emit=None):
         """A circuit with registers (Circuit(registers=R)) evaluated `steps` times over the same instances in one queued
@@ -485,6 +523,163 @@ class Engine:
         flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
         self._call("sgfhe_circuit_run_steps_ct", circuit.handle(), blocks, steps, psa, psb, pa, pb, N, pd, pe, ptr(w),
                    ptr(v), ptr(out), ptr(st), flags)
+        res = ((w, v), out) if packed and lwe else ((w, v) if packed else out)
+        return res, st
+
+    # ---- device-resident circuit runs --------------------------------------------------------------
+    # The run forms above with every array a torch.Tensor on the engine's device (sgfhe_circuit_run*_device): the same
+    # shapes, the same bytes, the same call numbers, nothing copied to or from the host and no host wait.
+    #
+    # Ordering is the caller's duty.  The work is queued on `hip_stream` -- a torch.cuda.Stream, a raw hipStream_t, or
+    # None.  None names the ctx's OWN stream, never torch's default stream.  Torch work on any other stream is not
+    # ordered against the run: synchronise before the call (torch.cuda.synchronize(), or the stream that produced the
+    # inputs) and call eng.sync() after it, before torch reads the results.  The alternative is to run everything,
+    # the torch work included, on one explicit non-default torch.cuda.Stream and to pass it as `hip_stream`: the runs
+    # and the torch kernels between them are then in stream order and nothing waits on the host.  Every tensor handed
+    # in or returned must outlive the queued work (keep a reference until eng.sync() or a synchronise of the stream).
+    # A call waits for nothing, but it launches the whole run from the host, and the hardware queue runs only so far
+    # ahead of the device: the call of a long run is paced by it, as bootstrap_batch_device is.
+
+    def _planes_device(self, circuit, data, shape):
+        """The planes of a device-resident run: a uint8 tensor of `shape`, or None for a circuit without planes."""
+        if not circuit.planes:
+            if data is not None:
+                raise ValueError("data given for a circuit without data planes")
+            return None
+        if data is None:
+            raise ValueError("a circuit with data planes needs data [planes=%d][instances]" % circuit.planes)
+        return check_device_tensor("data", data, shape, self.device, words=False)
+
+    def _empty(self, shape, dtype, hip_stream):
+        """An uninitialised result tensor (no fill kernel: it would run on torch's stream, unordered against the run);
+        allocated under `hip_stream` where that is a torch stream, so that torch's allocator knows its user."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(hip_stream, torch.cuda.Stream):
+            with torch.cuda.stream(hip_stream):
+                return torch.empty(shape, dtype=dtype, device=dev)
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    def _result(self, name, t, shape, like, hip_stream):
+        """A result tensor of the words' dtype: the caller's `t`, checked, or a new one."""
+        if t is None:
+            return self._empty(shape, like.dtype, hip_stream)
+        check_device_tensor(name, t, shape, self.device)
+        if t.dtype != like.dtype:
+            raise ValueError("%s: dtype %s, the inputs have %s" % (name, t.dtype, like.dtype))
+        return t
+
+    def circuit_run_device(self, circuit, inputs, data=None, out=None, hip_stream=None):
+        """circuit_run with the LWEs resident on the device (sgfhe_circuit_run_device), asynchronous: inputs
+        [n_inputs][instances][n+1] int64 or uint64 -> out [n_outputs][instances][n+1] of the same dtype (every word is
+        below 2^63), the bytes of circuit_run; data uint8 [planes][instances].  out: a tensor to write into (it must
+        not overlap the inputs).  Ordering and lifetimes: see the note above -- hip_stream=None is the ctx's own
+        stream, never torch's default stream; synchronise before and eng.sync() after, or run everything on one
+        explicit torch.cuda.Stream passed as hip_stream; the tensors must outlive the queued work."""
+        n = self.params.n
+        x = check_device_tensor("inputs", inputs, (circuit.n_inputs, None, n + 1), self.device)
+        inst = x.shape[1]
+        d = self._planes_device(circuit, data, (circuit.planes, inst))
+        out = self._result("out", out, (circuit.n_outputs, inst, n + 1), x, hip_stream)
+        if inst:
+            self._call("sgfhe_circuit_run_device", circuit.handle(), inst, _ptr(x), _ptr(d), _ptr(out),
+                       _stream_handle(hip_stream))
+        return out
+
+    def circuit_run_ct_device(self, circuit, a, b, packed=True, lwe=False, direct=False, lift=False, data=None,
+                              hip_stream=None):
+        """circuit_run_ct with the ciphertexts resident on the device (sgfhe_circuit_run_ct_device), asynchronous:
+        a, b [n_inputs][blocks][N] int64 or uint64 tensors, N = n or m; packed, lwe, direct, lift and the results as
+        circuit_run_ct, as tensors of the inputs' dtype; data uint8 [planes][blocks * n].  The ciphertexts are split
+        where they are, (w, v) is the input of a next run without leaving the device.  Ordering and lifetimes as
+        circuit_run_device: hip_stream=None is the ctx's own stream, never torch's default stream; synchronise before
+        and eng.sync() after, or one explicit torch.cuda.Stream for everything; the tensors outlive the queued work."""
+        p = self.params
+        a = check_device_tensor("a", a, (circuit.n_inputs, None, None), self.device)
+        if a.shape[2] not in (p.n, p.m):
+            raise ValueError("a: shape must be [n_inputs=%d][blocks][N], N = n = %d or m = %d" % (circuit.n_inputs, p.n, p.m))
+        b = check_device_tensor("b", b, tuple(a.shape), self.device)
+        if b.dtype != a.dtype:
+            raise ValueError("b: dtype %s, a has %s" % (b.dtype, a.dtype))
+        if not packed and not lwe:
+            raise ValueError("circuit_run_ct_device: ask for the packed outputs, the LWE outputs or both")
+        blocks = a.shape[1]
+        d = self._planes_device(circuit, data, (circuit.planes, blocks * p.n))
+        w = self._empty((circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
+        v = self._empty((circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
+        out = self._empty((circuit.n_outputs, blocks * p.n, p.n + 1), a.dtype, hip_stream) if lwe else None
+        flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
+        if blocks:
+            self._call("sgfhe_circuit_run_ct_device", circuit.handle(), blocks, _ptr(a), _ptr(b), a.shape[2], _ptr(d),
+                       _ptr(w), _ptr(v), _ptr(out), flags, _stream_handle(hip_stream))
+        if packed and lwe:
+            return (w, v), out
+        return (w, v) if packed else out
+
+    def circuit_run_steps_device(self, circuit, state, stream, data=None, emit=None, out=None, state_out=None,
+                                 hip_stream=None):
+        """circuit_run_steps with state and stream resident on the device (sgfhe_circuit_run_steps_device),
+        asynchronous: state [registers][instances][n+1] or None (every register FALSE), stream
+        [steps][stream inputs][instances][n+1], int64 or uint64 tensors; data uint8 [steps][planes][instances]; emit a
+        HOST sequence of [steps] flags (it steers the host loop).  Returns (out [emitted steps][n_outputs][instances]
+        [n+1], state after the last step) as tensors; out / state_out: tensors to write into.  state_out may be `state`
+        itself -- the state is read in full before anything is written -- so a caller keeps one state tensor and feeds
+        a stream chunk by chunk; no other result may overlap an input.  Ordering and lifetimes as circuit_run_device:
+        hip_stream=None is the ctx's own stream, never torch's default stream; synchronise before and eng.sync() after,
+        or one explicit torch.cuda.Stream for everything; the tensors outlive the queued work."""
+        n = self.params.n
+        x = check_device_tensor("stream", stream, (None, circuit.n_inputs - circuit.n_regs, None, n + 1), self.device)
+        steps, inst = x.shape[0], x.shape[2]
+        if state is not None:
+            check_device_tensor("state", state, (circuit.n_regs, inst, n + 1), self.device)
+            if state.dtype != x.dtype:
+                raise ValueError("state: dtype %s, stream has %s" % (state.dtype, x.dtype))
+        d = self._planes_device(circuit, data, (steps, circuit.planes, inst))
+        e, pe, emitted = self._emit_arg(emit, steps)
+        out = self._result("out", out, (emitted, circuit.n_outputs, inst, n + 1), x, hip_stream)
+        state_out = self._result("state_out", state_out, (circuit.n_regs, inst, n + 1), x, hip_stream)
+        if steps and inst:
+            self._call("sgfhe_circuit_run_steps_device", circuit.handle(), inst, steps, _ptr(state), _ptr(x), _ptr(d), pe,
+                       _ptr(out), _ptr(state_out), _stream_handle(hip_stream))
+        return out, state_out
+
+    def circuit_run_steps_ct_device(self, circuit, state_a, state_b, a, b, N=None, packed=True, lwe=False, direct=False,
+                                    lift=False, data=None, emit=None, hip_stream=None):
+        """circuit_run_steps_ct with the ciphertexts resident on the device (sgfhe_circuit_run_steps_ct_device),
+        asynchronous: state_a, state_b [registers][blocks][N] or None, a, b [steps][stream inputs][blocks][N], int64 or
+        uint64 tensors; everything else, and the results (as tensors), as circuit_run_steps_ct; emit stays a host
+        sequence.  Ordering and lifetimes as circuit_run_device: hip_stream=None is the ctx's own stream, never torch's
+        default stream; synchronise before and eng.sync() after, or one explicit torch.cuda.Stream for everything; the
+        tensors outlive the queued work."""
+        p = self.params
+        a = check_device_tensor("a", a, (None, circuit.n_inputs - circuit.n_regs, None, None), self.device)
+        if a.shape[3] not in (p.n, p.m) or (N is not None and a.shape[3] != N):
+            raise ValueError("a: shape must be [steps][stream inputs=%d][blocks][N], N = n = %d or m = %d"
+                             % (circuit.n_inputs - circuit.n_regs, p.n, p.m))
+        b = check_device_tensor("b", b, tuple(a.shape), self.device)
+        if b.dtype != a.dtype:
+            raise ValueError("b: dtype %s, a has %s" % (b.dtype, a.dtype))
+        if not packed and not lwe:
+            raise ValueError("circuit_run_steps_ct_device: ask for the packed outputs, the LWE outputs or both")
+        steps, blocks, N = a.shape[0], a.shape[2], a.shape[3]
+        if (state_a is None) != (state_b is None):
+            raise ValueError("state_a and state_b go together")
+        for name, s in (("state_a", state_a), ("state_b", state_b)):
+            if s is not None:
+                check_device_tensor(name, s, (circuit.n_regs, blocks, N), self.device)
+                if s.dtype != a.dtype:
+                    raise ValueError("%s: dtype %s, a has %s" % (name, s.dtype, a.dtype))
+        d = self._planes_device(circuit, data, (steps, circuit.planes, blocks * p.n))
+        e, pe, emitted = self._emit_arg(emit, steps)
+        w = self._empty((emitted, circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
+        v = self._empty((emitted, circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
+        out = self._empty((emitted, circuit.n_outputs, blocks * p.n, p.n + 1), a.dtype, hip_stream) if lwe else None
+        st = self._empty((circuit.n_regs, blocks * p.n, p.n + 1), a.dtype, hip_stream)
+        flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
+        if steps and blocks:
+            self._call("sgfhe_circuit_run_steps_ct_device", circuit.handle(), blocks, steps, _ptr(state_a), _ptr(state_b),
+                       _ptr(a), _ptr(b), N, _ptr(d), pe, _ptr(w), _ptr(v), _ptr(out), _ptr(st), flags,
+                       _stream_handle(hip_stream))
         res = ((w, v), out) if packed and lwe else ((w, v) if packed else out)
         return res, st
 

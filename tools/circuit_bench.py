@@ -37,6 +37,10 @@ Engine.bootstrap_batch on host arrays, at Params(1024), deterministic flatten.
       beside the bootstraps each runs, and the worst packed phase error of each.
   python tools/circuit_bench.py --ct --trace [--configs 16x1] [--dir DIR]
       run (A) alone in a child process under `rocprofv3 --kernel-trace --stats`: the share of k_circ_split.
+  python tools/circuit_bench.py --device [--configs 16x1024] [--reps 3]
+      ripple_adder: (H) the host form, circuit_run on numpy arrays, against (D) the device-resident form,
+      circuit_run_device on torch tensors, timed from the call to the end of sync(), with the time the call itself
+      takes (the queueing); alternating on one ctx (the order swaps every round); the bytes must be equal.
 
 Inputs are uniform words of [0, r): a bootstrap's time does not depend on what it encrypts."""
 
@@ -428,6 +432,50 @@ def wall_lift(args):
     eng.close()
 
 
+def wall_device(args):
+    import torch
+    import sgfhe_jl_amd as S
+    params = S.Params(1024)
+    eng = S.Engine(params)
+    rng = np.random.default_rng(1)
+    eng.generate_key(rng.integers(0, 2, size=params.n).astype(np.uint64), 2)
+    print("build %s, Params(1024), deterministic flatten" % eng.build_id())
+    for bits, inst in configs(args.configs):
+        c = S.ripple_adder(bits)
+        info = c.info()
+        x = rng.integers(0, params.r, size=(2 * bits, inst, params.n + 1), dtype=np.uint64)
+        xt = torch.from_numpy(x.view(np.int64)).cuda()
+        out = torch.empty((c.n_outputs, inst, params.n + 1), dtype=torch.int64, device=xt.device)
+        torch.cuda.synchronize()
+        eng.circuit_run(c, x[:, :64])                # both forms once: buffers, kernels, pinned pages
+        eng.circuit_run_device(c, xt, out=out)
+        eng.sync()
+        print("\nripple_adder(%d) x %d instances: %d levels, %d bootstraps per run; %.1f MB of inputs, %.1f MB of outputs"
+              % (bits, inst, info["levels"], info["nodes"] * inst, x.nbytes / 1e6, out.numel() * 8 / 1e6))
+        th, td = [], []
+        for rep in range(args.reps):
+            order = ("host", "device") if rep % 2 == 0 else ("device", "host")
+            for what in order:
+                t0 = time.perf_counter()
+                if what == "host":
+                    h = eng.circuit_run(c, x)
+                    th.append(time.perf_counter() - t0)
+                else:
+                    eng.circuit_run_device(c, xt, out=out)
+                    tq = time.perf_counter() - t0
+                    eng.sync()
+                    td.append(time.perf_counter() - t0)
+            same = np.array_equal(out.cpu().numpy().view(np.uint64), h)
+            print("  round %d (%s first): (H) host form %.3f s | (D) device form %.3f s, of which the call %.1f ms | "
+                  "D / H %.4f | same bytes: %s" % (rep, order[0], th[-1], td[-1], tq * 1e3, td[-1] / th[-1], same))
+            if not same:
+                sys.exit("the host form and the device-resident form differ")
+        print("  (H) min %.3f max %.3f spread %.1f %% | (D) min %.3f max %.3f spread %.1f %% | D / H of the medians %.4f"
+              % (min(th), max(th), 100 * (max(th) - min(th)) / min(th), min(td), max(td),
+                 100 * (max(td) - min(td)) / min(td), float(np.median(td) / np.median(th))))
+    eng.close()
+
+
 def ct_only(args):
     import sgfhe_jl_amd as S
     import encrypted_adder
@@ -497,20 +545,23 @@ def main():
     ap.add_argument("--gate3", action="store_true", help="the adder of two-input nodes against ripple_adder (full adders)")
     ap.add_argument("--lift", action="store_true",
                     help="with --ct --gate3: ripple_adder refreshed, direct and with SGFHE_CIRCUIT_PACK_LIFT")
+    ap.add_argument("--device", action="store_true", help="ripple_adder: circuit_run against circuit_run_device")
     ap.add_argument("--run-only", action="store_true", help="with --probe: circuit_run alone, the same rounds")
     ap.add_argument("--circuit-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--ct-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dir", default="circuit_trace", help="where rocprofv3 writes its files")
     args = ap.parse_args()
     if args.configs is None:
-        args.configs = "16x1" if args.ct or args.ct_only else "16x1024" if args.trace or args.probe or args.gate3 else \
+        args.configs = "16x1" if args.ct or args.ct_only else "16x1024" if args.trace or args.probe or args.gate3 or args.device else \
             "16x256,16x1024,32x256,32x1024"
-    if (args.ct or args.probe or args.gate3) and not args.trace and args.reps == 1:
+    if (args.ct or args.probe or args.gate3 or args.device) and not args.trace and args.reps == 1:
         args.reps = 3
     if args.circuit_only:
         circuit_only(args)
     elif args.ct_only:
         ct_only(args)
+    elif args.device:
+        wall_device(args)
     elif args.trace:
         trace(args)
     elif args.lift:

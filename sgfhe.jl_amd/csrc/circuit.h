@@ -8,10 +8,11 @@
 // circuit_plain_bits evaluates a planned circuit in clear for the noise probe.
 // The call arithmetic of a run lives here too (at the end): circuit_level_call, circuit_job_chunk, circuit_pack_runs and
 // circuit_run_sizes say which rows, nodes and jobs a call covers and what the buffers hold; the engine only launches.
+// So do the arguments of a run: every run entry fills one CircuitRequest, and circuit_request_check is its only judge.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
 // circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp, circuit_lut_multi_sanitized.cpp,
-// circuit_data_sanitized.cpp, circuit_calls_sanitized.cpp, circuit_steps_sanitized.cpp and circuit_routes_sanitized.cpp
-// drive it under ASan / UBSan on the CPU.
+// circuit_data_sanitized.cpp, circuit_calls_sanitized.cpp, circuit_steps_sanitized.cpp, circuit_routes_sanitized.cpp
+// and circuit_request_sanitized.cpp drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -22,6 +23,7 @@
 #include <new>
 #include <queue>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../../include/sgfhe_hip.h"
@@ -870,6 +872,101 @@ inline CircuitRunSizes circuit_run_sizes(const CircuitPlan &P, uint64_t instance
         S.max_ref = std::max(S.max_ref, circuit_pack_runs(P, blocks, q0, std::min(S.cpc, S.n_ct - q0), !direct, nullptr));
     S.work_rows = std::max<uint64_t>(S.max_rows, (uint64_t)S.max_ref * n);
     return S;
+}
+
+// ---- the arguments of a run ----------------------------------------------------------------------------------------
+// Everything a caller can pass to a run entry (sgfhe_circuit_run*, include/sgfhe_hip.h); an entry leaves what it does
+// not take as it is here.  The form bits say which entry it is: `ct` the ciphertext forms, `stepped` the _steps
+// entries, `probe` the _probe entries, `device` the _device entries -- and with them which text a refusal carries,
+// since every entry of one form speaks under one name.
+struct CircuitRequest {
+    bool ct = false, stepped = false, probe = false, device = false;
+    bool with_data = false;    // the entry takes `data`: the _data, _steps and _device entries
+    void *stream = nullptr;    // device form: the caller's hipStream_t, NULL for the ctx's own
+    size_t count = 0;          // instances, or -- ct -- blocks of n instances
+    size_t steps = 1;          // stepped: the plan is evaluated so often; in, in_a / in_b, data are then per step,
+                               // out, out_w / out_v per emitted step
+    size_t N = 0;              // ct: words of a ciphertext, n (PackedCiphertext) or m (Ciphertext)
+    const uint64_t *in = nullptr;                        // [wire][instances][n + 1]
+    const uint64_t *in_a = nullptr, *in_b = nullptr;     // ct: [wire][blocks][N]
+    const uint64_t *state_in = nullptr;                  // stepped: [n_regs][instances][n + 1], NULL: every register FALSE
+    const uint64_t *state_a = nullptr, *state_b = nullptr;   // stepped ct: [n_regs][blocks][N], both NULL: FALSE
+    const uint8_t *data = nullptr;                       // [n_planes][instances] of a plan that has planes
+    const uint8_t *emit = nullptr;                       // stepped: [steps] in host memory, NULL: every step's outputs
+    uint64_t *out = nullptr;                             // [n_outputs][instances][n + 1]; optional in the ct and stepped forms
+    uint64_t *out_w = nullptr, *out_v = nullptr;         // ct: [n_outputs][blocks][m], or both NULL
+    uint64_t *state_out = nullptr;                       // stepped: [n_regs][instances][n + 1] after the last step, optional
+    uint32_t flags = 0;                                  // ct: SGFHE_CIRCUIT_PACK_DIRECT, SGFHE_CIRCUIT_PACK_LIFT
+    const uint64_t *sk = nullptr;                        // probe: n key bits,
+    const uint8_t *in_bits = nullptr;                    // the plaintext bit of every input LWE [n_inputs][instances],
+    uint64_t *stats = nullptr;                           // the records [n_inputs + 3 n_gates][8], by wire id
+
+    bool direct() const { return (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0; }
+    bool lift() const { return (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0; }   // (with direct)
+};
+
+// What the checks read of a ctx
+struct CircuitEnv {
+    size_t n = 0, M = 0;
+    bool have_key = false;
+    bool pack_exact = false;    // the exactness bound of pack_encrypted_bits holds for the ctx's primes
+    uint32_t split_tiles = 0;   // workgroups of the split kernel per ciphertext
+};
+
+struct CircuitVerdict {
+    enum What { REFUSED, EMPTY, RUN } what;   // EMPTY: SGFHE_OK, and the device is not touched
+    int32_t code;                             // REFUSED: the error code, with `message`
+    std::string message;
+    size_t instances;                         // RUN: count, or -- ct -- count * n
+};
+
+// The only judge of a run's arguments: one ordered pass for every entry (DESIGN.md section 11 lists it), so which of
+// two defects is reported does not depend on the entry.  Reads the plan and the request's own words, never the memory
+// behind its pointers; allocates only for the message of a refusal.
+inline CircuitVerdict circuit_request_check(const CircuitPlan *P, const CircuitRequest &q, const CircuitEnv &env) {
+    const char *form = q.ct ? (q.stepped ? "sgfhe_circuit_run_steps_ct" : "sgfhe_circuit_run_ct")
+                            : (q.stepped ? "sgfhe_circuit_run_steps" : "sgfhe_circuit_run");
+    const auto refused = [](const char *entry, const std::string &what, int32_t code = SGFHE_ERR_INVALID_ARG) {
+        return CircuitVerdict{CircuitVerdict::REFUSED, code, *entry ? std::string(entry) + ": " + what : what, 0};
+    };
+    // (bit 1 without bit 0 was an unknown bit before SGFHE_CIRCUIT_PACK_LIFT existed, and stays refused)
+    if (q.ct && ((q.flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || q.flags == SGFHE_CIRCUIT_PACK_LIFT))
+        return refused(q.stepped ? form : "sgfhe_circuit_run_ct_ex", "unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
+    const uint32_t fed = P ? (q.stepped ? P->n_stream() : P->n_inputs) : 0;   // the input wires the caller brings
+    const bool no_in = fed && (q.ct ? !q.in_a || !q.in_b : !q.in);
+    const bool no_out = !q.ct && !q.out && !q.state_out;                       // (the ct forms: with out_w, below)
+    if (!P || no_in || no_out || !q.state_a != !q.state_b)
+        return refused(form, q.ct ? (q.stepped ? "NULL circuit or input pointer (state_a and state_b go together)"
+                                               : "NULL circuit or input pointer")
+                                  : (q.stepped ? "NULL circuit or input pointer, or no output pointer"
+                                               : "NULL circuit, input or output pointer"));
+    if (!q.stepped && P->n_regs)
+        return refused("sgfhe_circuit_run", "a plan with registers runs through the _steps entries");
+    for (uint32_t i = 0; q.stepped && q.ct && i < P->n_regs; i++)   // a split ciphertext is scale 0, and an LWE cannot be halved
+        if (P->reg_scale[i]) return refused(form, "a register of scale 1 or 2 has no ciphertext form");
+    if (P->n_planes && !q.with_data)
+        return refused("sgfhe_circuit_run", "a plan with data planes runs through the _data entries");
+    if (P->n_planes && !q.data && q.count && q.steps)
+        return refused(q.stepped ? form : "sgfhe_circuit_run_data", "NULL data for a plan with data planes");
+    if (q.probe && (!q.sk || !q.stats || (!q.in_bits && P->n_inputs)))
+        return refused("sgfhe_circuit_run_probe", "NULL secret key, input bits or statistics pointer");
+    if (q.ct && (!q.out_w != !q.out_v || (!q.out_w && !q.out && !q.state_out)))
+        return refused(form, "out_w and out_v go together, and one output form is needed");
+    if (q.ct && q.N != env.n && q.N != env.M) return refused(form, "N must be n (PackedCiphertext) or m (Ciphertext)");
+    if (!env.have_key) return refused("", "no bootstrap key uploaded", SGFHE_ERR_NO_KEY);
+    if (q.ct && q.out_w && !env.pack_exact)
+        return refused("pack_encrypted_bits", "exactness bound of the RNS primes", SGFHE_ERR_UNSUPPORTED);
+    if (q.count == 0 || q.steps == 0) return {CircuitVerdict::EMPTY, SGFHE_OK, {}, 0};
+    // rows of a level, and words of every table, must be addressable by the kernels' indices; in the ct forms the rows
+    // of the pack stage (n_outputs * instances) and the workgroups of the split kernel too
+    const uint64_t instances = q.ct ? (uint64_t)q.count * env.n : q.count;
+    if (q.count >= 0x80000000u || instances >= 0x80000000u || (uint64_t)P->widest * instances > 0xFFFFFFFFull ||
+        (q.ct && ((q.out_w && (uint64_t)P->n_outputs * instances > 0xFFFFFFFFull) ||
+                  (uint64_t)P->n_inputs * q.count * env.split_tiles > 0x7FFFFFFFull)))
+        return refused(form, "too many instances for this circuit");
+    if ((q.ct ? env.n : instances) % P->group)   // (ct: a group must not straddle two ciphertexts)
+        return refused(form, std::string(q.ct ? "n" : "instances") + " must be a multiple of the circuit's lane group");
+    return {CircuitVerdict::RUN, SGFHE_OK, {}, (size_t)instances};
 }
 
 }  // namespace sgfhe

@@ -3131,26 +3131,6 @@ int32_t sgfhe_circuit_destroy(sgfhe_circuit *c) {
     return SGFHE_OK;
 }
 
-// ciphertext form of a run (sgfhe_circuit_run_ct): inputs split on the device, outputs packed on the device
-struct CircuitCt {
-    const uint64_t *in_a, *in_b;   // [n_inputs][blocks][N]
-    size_t blocks, N;
-    uint64_t *out_w, *out_v;       // [n_outputs][blocks][m], or both NULL
-    bool direct;                   // SGFHE_CIRCUIT_PACK_DIRECT
-    bool lift;                     // SGFHE_CIRCUIT_PACK_LIFT (with direct): what is not direct is lifted, not refreshed
-};
-
-// A stepped run (sgfhe_circuit_run_steps[_ct]): the plan evaluated `steps` times over the same instances, the registers
-// fed back on the device after every step.  The run's `in` / ct->in_a, in_b / data / out / ct->out_w, out_v are then
-// per step (per emitted step, for the outputs).
-struct CircuitSteps {
-    size_t steps;
-    const uint8_t *emit;                // [steps], NULL: every step's outputs are collected
-    const uint64_t *state_in;           // LWE form: [n_regs][instances][n + 1], NULL: every register FALSE
-    const uint64_t *state_a, *state_b;  // ciphertext form: [n_regs][blocks][N], both NULL: every register FALSE
-    uint64_t *state_out;                // [n_regs][instances][n + 1] after the last step, optional
-};
-
 // ---- noise probe: LWE error statistics against the secret key, on the device -------------
 
 static constexpr uint32_t NOISE_Q_GRID = 1024;   // workgroups (partial records) of k_lwe_noise_q
@@ -3213,46 +3193,34 @@ static int32_t launch_lwe_noise(sgfhe_ctx *c, hipStream_t st, const uint64_t *ro
     return SGFHE_OK;
 }
 
-// the probe of a run (sgfhe_circuit_run_probe): host images that outlive the run's asynchronous copies
-struct CircuitProbe {
-    const uint64_t *sk;
-    const uint8_t *in_bits;
-    uint64_t *stats;                  // [n_inputs + 3 n_gates][8], by wire id
-    std::vector<uint64_t> up, down;   // [key mask | bit table]; the records by probe row
-};
-
 // One run: what its stages share, and the stages in the order run() queues them on `st`.  Which rows, nodes, jobs and
-// ciphertexts a call covers is csrc/circuit.h's (circuit_level_call, circuit_pack_runs, circuit_run_sizes).
-// `in` / `out`: the LWE form ([wire][instances][n + 1]); with `ct` the inputs come from ct->in_a / in_b instead and
-// `out` is optional.  `probe` (LWE form only): the noise records of every input wire and of every live node's three
-// wires, taken from the uploaded inputs and from each level call's own result rows.  `data`: the planes of a plan that
-// has any ([n_planes][instances], sgfhe_circuit_run_data), uploaded once with the tables.
+// ciphertexts a call covers is csrc/circuit.h's (circuit_level_call, circuit_pack_runs, circuit_run_sizes), and so is
+// what the caller passed: the stages read the request `q` (CircuitRequest), which circuit_request_check has passed for
+// `instances`.  The probe (LWE form only) takes the noise records of every input wire and of every live node's three
+// wires from the uploaded inputs and from each level call's own result rows.
 struct CircuitRun {
     sgfhe_ctx *c;
     const CircuitPlan &P;
+    const CircuitRequest &q;
     const size_t instances;
-    const uint64_t *in;
-    uint64_t *out;
-    const CircuitCt *ct;
-    CircuitProbe *probe;
-    const uint8_t *data;
-    const CircuitSteps *seq = nullptr;   // a stepped run (run_steps)
-    // The device-resident form (sgfhe_circuit_run*_device): every array of the caller's (but seq->emit) is device
+    uint64_t *const out = q.out;
+    const uint8_t *const data = P.n_planes ? q.data : nullptr;   // uploaded with the tables, or -- stepped -- with every step
+    // The device-resident form (sgfhe_circuit_run*_device): every array of the caller's (but q.emit) is device
     // memory, the run is queued on the caller's stream between fence_begin and fence_end, and the host waits for
     // nothing.  The host form: the ctx's own stream, drained before the run (run_drained) and waited for at its end.
-    const bool device;
-    const hipStream_t st;
+    const bool device = q.device;
+    const hipStream_t st = device && q.stream ? (hipStream_t)q.stream : c->stream;
     const size_t n = c->n, row = n + 1, M = c->M;   // row: words of an LWE
     const uint32_t inst = (uint32_t)instances;
     const uint64_t r = c->par.r;
     // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire are the plan's jobs, and their rows go from the level
     // calls into the raw table.  SGFHE_CIRCUIT_PACK_LIFT: every other ciphertext is lifted from the wire table into the
     // raw table (k_circ_lift), so no group has a refreshed one
-    const bool pack = ct && ct->out_w, direct = pack && ct->direct, lift = direct && ct->lift;
-    const CircuitRunSizes sz = circuit_run_sizes(P, instances, n, ct ? ct->blocks : 0, pack, direct, lift);
+    const bool pack = q.ct && q.out_w, direct = pack && q.direct(), lift = direct && q.lift();
+    const CircuitRunSizes sz = circuit_run_sizes(P, instances, n, q.ct ? q.count : 0, pack, direct, lift);
     // (a stepped run splits the registers' ciphertexts and a step's stream ciphertexts in turn through the one buffer)
-    const size_t ct_words = ct ? (size_t)P.n_inputs * ct->blocks * ct->N : 0;
-    const size_t probe_rows = probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
+    const size_t ct_words = q.ct ? (size_t)P.n_inputs * q.count * q.N : 0;
+    const size_t probe_rows = q.probe ? circuit_probe_rows(P) : 0, bit_words = circuit_bit_words(instances);
     // the plan's tables on the device (views into circ_tab), and the probe's
     CircNodes nodes = {};
     CircRefs outs = {}, nexts = {};   // the outputs; the registers' next states (a plan with registers)
@@ -3261,12 +3229,12 @@ struct CircuitRun {
     const uint32_t *d_next_scale = nullptr, *d_reg_index = nullptr;   // (a plan with registers)
     NoiseLayout NL = {};
     std::vector<CircuitPackRun> runs;   // of the pack group at hand (reserved with the buffers)
+    // the probe's host images, which the run's asynchronous copies read and write: [key mask | bit table]; the records
+    // by probe row
+    std::vector<uint64_t> up, down;
 
-    CircuitRun(sgfhe_ctx *c, const CircuitPlan &P, size_t instances, const uint64_t *in, uint64_t *out,
-               const CircuitCt *ct, CircuitProbe *probe, const uint8_t *data, bool device = false,
-               hipStream_t stream = nullptr)
-        : c(c), P(P), instances(instances), in(in), out(out), ct(ct), probe(probe), data(P.n_planes ? data : nullptr),
-          device(device), st(device && stream ? stream : c->stream) {}
+    CircuitRun(sgfhe_ctx *c, const CircuitPlan &P, const CircuitRequest &q, size_t instances)
+        : c(c), P(P), q(q), instances(instances) {}
 
     int32_t grow();
     int32_t upload_tables();
@@ -3318,8 +3286,8 @@ struct CircuitRun {
     static uint32_t copy_grid(size_t total) { return (uint32_t)std::min<size_t>((total + 255) / 256, (size_t)1 << 20); }
     // the gather of one call: rows row0 .. row0 + rows of the level whose first node is `node0` of the plan's node table
     // (a level's first node, or live() for the pack stage's pseudo-level)
-    // `lutw`: the call's LUT descriptor, for a level call that holds a LUT node
-    void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows, uint32_t *lutw = nullptr) const {
+    // `lutw`: the call's LUT descriptor, for a level call that holds a LUT node (NULL otherwise)
+    void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows, uint32_t *lutw) const {
         hipLaunchKernelGGL(k_circ_gather, dim3(((uint32_t)rows * (uint32_t)row + 255) / 256), dim3(256), 0, st,
                            c->circ_wires.p, nodes, node0, S.a1, S.b1, S.a2, S.b2, (uint32_t)row0, (uint32_t)rows, inst,
                            (uint32_t)n, r, lutw, (const uint8_t *)(data ? c->circ_data.p : nullptr));
@@ -3349,23 +3317,23 @@ int32_t CircuitRun::grow() {
     if ((rc = circ_grow(c, c->circ_tab, P.at.words))) return rc;
     if (data && (rc = circ_grow(c, c->circ_data, (size_t)P.n_planes * instances))) return rc;
     if (!device && (rc = circ_grow(c, c->circ_ct, 2 * ct_words))) return rc;
-    if (seq && (rc = circ_grow(c, c->circ_state, state_words()))) return rc;
+    if (q.stepped && (rc = circ_grow(c, c->circ_state, state_words()))) return rc;
     if (pack && (rc = pack_grow(c, sz.cpc, sz.n_ct, sz.max_ref))) return rc;
-    if (probe) {
+    if (q.probe) {
         size_t unread = 0;   // inputs nothing reads have no slot: the probe uploads them for itself
         for (uint32_t i = 0; i < P.n_inputs; i++) unread += P.input_slot[i] == CIRC_NONE;
         if ((rc = noise_grow(c, probe_rows, bit_words, unread * instances * row))) return rc;
         std::vector<uint64_t> table;
-        if ((rc = circuit_plain_bits(P, probe->in_bits, instances, table, data)))
+        if ((rc = circuit_plain_bits(P, q.in_bits, instances, table, data)))
             return fail(c, rc, "sgfhe_circuit_run_probe: no memory for the plaintext bit table");
         try {
-            probe->up.assign(NOISE_MASK_WORDS, 0);
-            probe->up.insert(probe->up.end(), table.begin(), table.end());
-            probe->down.assign(probe_rows * 8, 0);
+            up.assign(NOISE_MASK_WORDS, 0);
+            up.insert(up.end(), table.begin(), table.end());
+            down.assign(probe_rows * 8, 0);
         } catch (...) {
             return fail(c, SGFHE_ERR_OOM, "sgfhe_circuit_run_probe: no memory for the plaintext bit table");
         }
-        noise_key_mask(c, probe->sk, probe->up.data());
+        noise_key_mask(c, q.sk, up.data());
         NL = noise_layout(c, probe_rows);
     }
     try {
@@ -3384,7 +3352,7 @@ int32_t CircuitRun::grow() {
 // caller's array, as the inputs are), and the probe's
 int32_t CircuitRun::upload_tables() {
     HIPCHK(c, hipMemcpyAsync(c->circ_tab.p, P.image.data(), (size_t)P.at.words * 4, hipMemcpyHostToDevice, st));
-    if (data && !seq)   // (a stepped run brings planes with every step: upload_step)
+    if (data && !q.stepped)   // (a stepped run brings planes with every step: upload_step)
         if (const int32_t rc = copy_in(c->circ_data.p, data, (size_t)P.n_planes * instances)) return rc;
     const uint32_t *tab = c->circ_tab.p;
     nodes = {tab + P.at.node_kind, tab + P.at.term_start, reinterpret_cast<const int32_t *>(tab + P.at.term_weight),
@@ -3396,21 +3364,21 @@ int32_t CircuitRun::upload_tables() {
         nexts = refs_at(P.at.next_ref, P.at.next_shift, P.at.next_route);
         d_next_scale = tab + P.at.next_scale, d_reg_index = tab + P.at.reg_index;
     }
-    if (probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
-        HIPCHK(c, hipMemcpyAsync(NL.mask, probe->up.data(), probe->up.size() * 8, hipMemcpyHostToDevice, st));
+    if (q.probe) {   // (mask and bit table are adjacent in noise_tab: one copy)
+        HIPCHK(c, hipMemcpyAsync(NL.mask, up.data(), up.size() * 8, hipMemcpyHostToDevice, st));
         if (probe_rows) HIPCHK(c, hipMemsetAsync(NL.stats, 0, probe_rows * 64, st));
     }
     return SGFHE_OK;
 }
 
 // ciphertext form: the ciphertexts as they are, and extract() of every bit into the slot of its input wire
-int32_t CircuitRun::upload_ct() { return split(ct->in_a, ct->in_b, P.n_inputs, d_in_slot, c->circ_wires.p); }
+int32_t CircuitRun::upload_ct() { return split(q.in_a, q.in_b, P.n_inputs, d_in_slot, c->circ_wires.p); }
 
 // `count` wires of ciphertexts a, b [count][blocks][N] (the caller's) split into the slots slot[0 .. count) (device) of
 // `rows` ([slot][instances][n + 1]): uploaded into circ_ct first, or -- device form -- read where they are
 int32_t CircuitRun::split(const uint64_t *a, const uint64_t *b, uint32_t count, const uint32_t *slot, uint64_t *rows) {
     if (!count) return SGFHE_OK;
-    const size_t words = (size_t)count * ct->blocks * ct->N;
+    const size_t words = (size_t)count * q.count * q.N;
     if (!device) {
         int32_t rc;
         if ((rc = copy_in(c->circ_ct.p, a, words * 8))) return rc;
@@ -3418,9 +3386,9 @@ int32_t CircuitRun::split(const uint64_t *a, const uint64_t *b, uint32_t count, 
         a = c->circ_ct.p, b = c->circ_ct.p + words;
     }
     const uint32_t tiles = (uint32_t)((n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS);
-    hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(count * ct->blocks * tiles)), dim3(256),
+    hipLaunchKernelGGL(k_circ_split, dim3((uint32_t)(count * q.count * tiles)), dim3(256),
                        (n + CIRC_SPLIT_ROWS - 1) * 8, st, a, b, slot, rows,
-                       (uint32_t)ct->blocks, (uint32_t)ct->N, (uint32_t)n, r);
+                       (uint32_t)q.count, (uint32_t)q.N, (uint32_t)n, r);
     HIPCHK(c, hipGetLastError());
     return SGFHE_OK;
 }
@@ -3442,12 +3410,12 @@ int32_t CircuitRun::copy_inputs(uint32_t first, const uint64_t *src) {   // inpu
 
 int32_t CircuitRun::upload_lwe() {
     const size_t in_words = instances * row;
-    if (const int32_t rc = copy_inputs(0, in)) return rc;
+    if (const int32_t rc = copy_inputs(0, q.in)) return rc;
     // the probe of the input wires, from the rows as uploaded (before a level reuses a slot)
-    for (uint32_t i = 0, u = 0; probe && i < P.n_inputs; i++) {
+    for (uint32_t i = 0, u = 0; q.probe && i < P.n_inputs; i++) {
         const bool own = P.input_slot[i] == CIRC_NONE;
         uint64_t *rows_i = own ? c->noise_lwe.p + (size_t)u++ * in_words : c->circ_wires.p + (size_t)P.input_slot[i] * in_words;
-        if (own) HIPCHK(c, hipMemcpyAsync(rows_i, in + (size_t)i * in_words, in_words * 8, hipMemcpyHostToDevice, st));
+        if (own) HIPCHK(c, hipMemcpyAsync(rows_i, q.in + (size_t)i * in_words, in_words * 8, hipMemcpyHostToDevice, st));
         const int32_t rc = launch_lwe_noise(c, st, rows_i, NL, noise_wire_rows(n, i, inst, bit_words));
         if (rc) return rc;
     }
@@ -3506,7 +3474,7 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
                        C.rows, inst, un);
     HIPCHK(c, hipGetLastError());
     // the probe: the call's own result rows, read or not, before the next call overwrites them (same stream)
-    if (!probe) return SGFHE_OK;
+    if (!q.probe) return SGFHE_OK;
     rc = launch_lwe_noise(c, st, S.res, NL, noise_call_rows(n, P.n_inputs, C, row0, inst, bit_words, nodes.kind + C.ka),
                           C.kb - C.ka + 1, 3);
     // a sibling has no result rows: the wires of it that have a slot are measured there, over the instances of its
@@ -3539,7 +3507,7 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
 // bootstrap's own call number, which is one sgfhe_pack_encrypted_bits(count = cnt).
 int32_t CircuitRun::pack_group(size_t q0) {
     const size_t cnt = std::min(sz.cpc, sz.n_ct - q0);
-    const size_t nb = circuit_pack_runs(P, ct->blocks, q0, cnt, !direct, &runs) * n;
+    const size_t nb = circuit_pack_runs(P, q.count, q0, cnt, !direct, &runs) * n;
     if (lift) {
         for (const CircuitPackRun &U : runs) {
             const uint32_t rows = (uint32_t)(U.len * n);
@@ -3550,7 +3518,7 @@ int32_t CircuitRun::pack_group(size_t q0) {
     } else if (nb) {
         const Staging S = staging(c->pack_lwe.p, nb, n);
         for (const CircuitPackRun &U : runs) {
-            gather((uint32_t)P.live(), S.from_row(U.rank * n, n), U.q * n, U.len * n);
+            gather((uint32_t)P.live(), S.from_row(U.rank * n, n), U.q * n, U.len * n, nullptr);
             HIPCHK(c, hipGetLastError());
         }
         BootCall call(c);
@@ -3574,15 +3542,14 @@ int32_t CircuitRun::pack_group(size_t q0) {
 // (w, v) of every ciphertext, the outputs in the LWE form, the probe's records; then the host waits (host form)
 int32_t CircuitRun::download() {
     int32_t rc;
-    if ((rc = fetch(out, ct ? ct->out_w : nullptr, ct ? ct->out_v : nullptr))) return rc;
-    if (probe && probe_rows)
-        HIPCHK(c, hipMemcpyAsync(probe->down.data(), NL.stats, probe_rows * 64, hipMemcpyDeviceToHost, st));
+    if ((rc = fetch(out, q.out_w, q.out_v))) return rc;
+    if (probe_rows)
+        HIPCHK(c, hipMemcpyAsync(down.data(), NL.stats, probe_rows * 64, hipMemcpyDeviceToHost, st));
     if ((rc = finish())) return rc;
-    if (probe) {   // records by wire id; the wires of pruned nodes stay zero
-        std::fill(probe->stats, probe->stats + ((size_t)P.n_inputs + 3 * (size_t)P.n_gates) * 8, 0ull);
+    if (q.probe) {   // records by wire id; the wires of pruned nodes stay zero
+        std::fill(q.stats, q.stats + ((size_t)P.n_inputs + 3 * (size_t)P.n_gates) * 8, 0ull);
         for (size_t w = 0; w < probe_rows; w++)
-            std::copy(probe->down.begin() + w * 8, probe->down.begin() + w * 8 + 8,
-                      probe->stats + (size_t)circuit_probe_wire(P, w) * 8);
+            std::copy(down.begin() + w * 8, down.begin() + w * 8 + 8, q.stats + (size_t)circuit_probe_wire(P, w) * 8);
     }
     return SGFHE_OK;
 }
@@ -3611,9 +3578,9 @@ int32_t CircuitRun::fetch(uint64_t *o, uint64_t *w, uint64_t *v) {
 // the registers' first values into the state buffer: the caller's LWEs, the split of the caller's ciphertexts, or FALSE
 int32_t CircuitRun::upload_state() {
     if (!P.n_regs) return SGFHE_OK;
-    if (ct && seq->state_a) return split(seq->state_a, seq->state_b, P.n_regs, d_reg_index, c->circ_state.p);
-    if (!ct && seq->state_in)   // (read in full before anything is written: state_out may be this very array)
-        return copy_in(c->circ_state.p, seq->state_in, state_words() * 8);
+    if (q.state_a) return split(q.state_a, q.state_b, P.n_regs, d_reg_index, c->circ_state.p);
+    if (q.state_in)   // (read in full before anything is written: state_out may be this very array)
+        return copy_in(c->circ_state.p, q.state_in, state_words() * 8);
     HIPCHK(c, hipMemsetAsync(c->circ_state.p, 0, state_words() * 8, st));
     return SGFHE_OK;
 }
@@ -3626,11 +3593,11 @@ int32_t CircuitRun::upload_step(size_t s) {
         HIPCHK(c, hipGetLastError());
     }
     int32_t rc;
-    if (ct) {
-        const size_t per = (size_t)P.n_stream() * ct->blocks * ct->N;
-        rc = split(ct->in_a + s * per, ct->in_b + s * per, P.n_stream(), d_in_slot + P.n_regs, c->circ_wires.p);
+    if (q.ct) {
+        const size_t per = (size_t)P.n_stream() * q.count * q.N;
+        rc = split(q.in_a + s * per, q.in_b + s * per, P.n_stream(), d_in_slot + P.n_regs, c->circ_wires.p);
     } else {
-        rc = copy_inputs(P.n_regs, in + s * (size_t)P.n_stream() * instances * row);
+        rc = copy_inputs(P.n_regs, q.in + s * (size_t)P.n_stream() * instances * row);
     }
     if (rc) return rc;
     if (data) {
@@ -3659,46 +3626,32 @@ int32_t CircuitRun::run_steps() {
     if ((rc = upload_tables())) return rc;
     if ((rc = upload_state())) return rc;
     const size_t out_words = (size_t)P.n_outputs * instances * row, wv = sz.n_ct * M;
-    for (size_t s = 0, emitted = 0; s < seq->steps; s++) {
+    for (size_t s = 0, emitted = 0; s < q.steps; s++) {
         if ((rc = upload_step(s))) return rc;
         if ((rc = level_calls())) return rc;
-        if (!seq->emit || seq->emit[s]) {
+        if (!q.emit || q.emit[s]) {
             if ((rc = pack_groups())) return rc;
-            if ((rc = fetch(out ? out + emitted * out_words : nullptr, pack ? ct->out_w + emitted * wv : nullptr,
-                            pack ? ct->out_v + emitted * wv : nullptr)))
+            if ((rc = fetch(out ? out + emitted * out_words : nullptr, pack ? q.out_w + emitted * wv : nullptr,
+                            pack ? q.out_v + emitted * wv : nullptr)))
                 return rc;
             emitted++;
         }
         if ((rc = feedback())) return rc;
     }
-    if (seq->state_out && P.n_regs && (rc = copy_out(seq->state_out, c->circ_state.p, state_words() * 8))) return rc;
+    if (q.state_out && P.n_regs && (rc = copy_out(q.state_out, c->circ_state.p, state_words() * 8))) return rc;
     return finish();
 }
 
 int32_t CircuitRun::run() {
     int32_t rc;
-    if (seq) return run_steps();
+    if (q.stepped) return run_steps();
     if ((rc = grow())) return rc;
     if (device && (rc = fence_begin(c, st))) return rc;   // (after grow: a buffer that grew has drained the ctx)
     if ((rc = upload_tables())) return rc;
-    if ((rc = ct ? upload_ct() : upload_lwe())) return rc;
+    if ((rc = q.ct ? upload_ct() : upload_lwe())) return rc;
     if ((rc = level_calls())) return rc;
     if ((rc = pack_groups())) return rc;
     return download();
-}
-
-// A plan with planes runs through the _data entries only (`with_data`), and with planes (unless it has no instances); a
-// plan with registers through none of the one-shot entries
-static int32_t circuit_data_ok(sgfhe_ctx *c, const sgfhe_circuit *circ, bool with_data, const uint8_t *data,
-                               size_t instances) {
-    if (circ && circ->plan.n_regs)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: a plan with registers runs through the _steps entries");
-    if (!circ || !circ->plan.n_planes) return SGFHE_OK;   // (a NULL circuit is the entry's own error)
-    if (!with_data)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: a plan with data planes runs through the _data entries");
-    if (!data && instances)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_data: NULL data for a plan with data planes");
-    return SGFHE_OK;
 }
 
 // The run of an entry whose checks have passed: the host form behind a drained ctx, waited for; the device form
@@ -3708,45 +3661,20 @@ static int32_t circuit_run_form(sgfhe_ctx *c, bool device, hipStream_t st, F &&b
     return device ? run_queued(c, st ? st : c->stream, body) : run_drained(c, body);
 }
 
-// sgfhe_circuit_run[_data], with `probe` the run of sgfhe_circuit_run_probe[_data]; sgfhe_circuit_run_device (`device`)
-static int32_t circuit_run_lwe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
-                               uint64_t *out, CircuitProbe *probe, bool with_data = false, const uint8_t *data = nullptr,
-                               bool device = false, hipStream_t st = nullptr) {
-    if (!circ || !out || (!in && circ->plan.n_inputs))
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: NULL circuit, input or output pointer");
-    if (const int32_t rd = circuit_data_ok(c, circ, with_data, data, instances)) return rd;
-    if (probe && (!probe->sk || !probe->stats || (!probe->in_bits && circ->plan.n_inputs)))
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_probe: NULL secret key, input bits or statistics pointer");
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    const CircuitPlan &P = circ->plan;
-    if (instances == 0) {
-        if (probe) std::fill(probe->stats, probe->stats + ((size_t)P.n_inputs + 3 * (size_t)P.n_gates) * 8, 0ull);
+// Every run entry, the ctx locked: the one check of the request (csrc/circuit.h), then the run in the request's form.
+// An empty probe run still clears the caller's records.
+static int32_t circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, const CircuitRequest &q) {
+    const CircuitPlan *P = circ ? &circ->plan : nullptr;
+    const CircuitEnv env = {c->n, c->M, c->have_key, pack_group(c) != 0,
+                            (uint32_t)((c->n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS)};
+    const CircuitVerdict v = circuit_request_check(P, q, env);
+    if (v.what == CircuitVerdict::REFUSED) return fail(c, v.code, v.message);
+    if (v.what == CircuitVerdict::EMPTY) {
+        if (q.probe) std::fill(q.stats, q.stats + ((size_t)P->n_inputs + 3 * (size_t)P->n_gates) * 8, 0ull);
         return SGFHE_OK;
     }
-    // rows of a level, and words of every table, must be addressable by the kernels' indices
-    if (instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: too many instances for this circuit");
-    if (instances % P.group)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run: instances must be a multiple of the circuit's lane group");
-    return circuit_run_form(c, device, st,
-                            [&] { return CircuitRun(c, P, instances, in, out, nullptr, probe, data, device, st).run(); });
-}
-
-int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
-                                uint64_t *out, const uint64_t *sk, const uint8_t *in_bits, uint64_t *stats) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    CircuitProbe probe = {sk, in_bits, stats, {}, {}};
-    return circuit_run_lwe(c, circ, instances, in, out, &probe);
-}
-
-int32_t sgfhe_circuit_run_probe_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
-                                     const uint8_t *data, uint64_t *out, const uint64_t *sk, const uint8_t *in_bits,
-                                     uint64_t *stats) {
-    if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    CircuitProbe probe = {sk, in_bits, stats, {}, {}};
-    return circuit_run_lwe(c, circ, instances, in, out, &probe, true, data);
+    CircuitRun R(c, *P, q, v.instances);   // (outlives the wait that follows a failed step: the probe's host images)
+    return circuit_run_form(c, q.device, (hipStream_t)q.stream, [&] { return R.run(); });
 }
 
 // everything sgfhe_lwe_noise queues (run_drained waits for the stream when a step fails)
@@ -3834,120 +3762,98 @@ int32_t sgfhe_lwe_noise(sgfhe_ctx *c, const uint64_t *sk, const uint64_t *lwe, s
     return SGFHE_OK;
 }
 
+// ---- the run entries (include/sgfhe_hip.h).  Each fills the request of its form (CircuitRequest, csrc/circuit.h) and
+// runs it with the ctx locked -- for the whole run, or while a device entry queues -- so that its call numbers are
+// contiguous ---------------------------------------------------------------------------------------------------------
+
 int32_t sgfhe_circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
                           uint64_t *out) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    return circuit_run_lwe(c, circ, instances, in, out, nullptr);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.count = instances, q.in = in, q.out = out;
+    return circuit_run(c, circ, q);
 }
 
 int32_t sgfhe_circuit_run_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
                                const uint8_t *data, uint64_t *out) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    return circuit_run_lwe(c, circ, instances, in, out, nullptr, true, data);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.with_data = true;
+    q.count = instances, q.in = in, q.data = data, q.out = out;
+    return circuit_run(c, circ, q);
+}
+
+int32_t sgfhe_circuit_run_probe(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                                uint64_t *out, const uint64_t *sk, const uint8_t *in_bits, uint64_t *stats) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.probe = true;
+    q.count = instances, q.in = in, q.out = out;
+    q.sk = sk, q.in_bits = in_bits, q.stats = stats;
+    return circuit_run(c, circ, q);
+}
+
+int32_t sgfhe_circuit_run_probe_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
+                                     const uint8_t *data, uint64_t *out, const uint64_t *sk, const uint8_t *in_bits,
+                                     uint64_t *stats) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.probe = q.with_data = true;
+    q.count = instances, q.in = in, q.data = data, q.out = out;
+    q.sk = sk, q.in_bits = in_bits, q.stats = stats;
+    return circuit_run(c, circ, q);
 }
 
 int32_t sgfhe_circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe) {
-    return sgfhe_circuit_run_ct_ex(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, 0u);
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.ct = true;
+    q.count = blocks, q.in_a = in_a, q.in_b = in_b, q.N = N;
+    q.out_w = out_w, q.out_v = out_v, q.out = out_lwe;
+    return circuit_run(c, circ, q);
 }
-
-// sgfhe_circuit_run_ct_ex and sgfhe_circuit_run_ct_data (`with_data`), the ctx locked
-static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
-                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
-                              uint32_t flags, bool with_data, const uint8_t *data, bool device = false,
-                              hipStream_t st = nullptr);
 
 int32_t sgfhe_circuit_run_ct_ex(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                                 const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
                                 uint32_t flags) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    return circuit_run_ct(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, flags, false, nullptr);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.ct = true;
+    q.count = blocks, q.in_a = in_a, q.in_b = in_b, q.N = N;
+    q.out_w = out_w, q.out_v = out_v, q.out = out_lwe, q.flags = flags;
+    return circuit_run(c, circ, q);
 }
 
 int32_t sgfhe_circuit_run_ct_data(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                                   const uint64_t *in_b, size_t N, const uint8_t *data, uint64_t *out_w, uint64_t *out_v,
                                   uint64_t *out_lwe, uint32_t flags) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    return circuit_run_ct(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, flags, true, data);
-}
-
-static int32_t circuit_run_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
-                              const uint64_t *in_b, size_t N, uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe,
-                              uint32_t flags, bool with_data, const uint8_t *data, bool device, hipStream_t st) {
-    // (bit 1 without bit 0 was an unknown bit before SGFHE_CIRCUIT_PACK_LIFT existed, and stays refused)
-    if ((flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || flags == SGFHE_CIRCUIT_PACK_LIFT)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct_ex: unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
-    if (!circ || ((!in_a || !in_b) && circ->plan.n_inputs))
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: NULL circuit or input pointer");
-    if (const int32_t rd = circuit_data_ok(c, circ, with_data, data, blocks)) return rd;
-    if (!out_w != !out_v || (!out_w && !out_lwe))
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: out_w and out_v go together, and one output form is needed");
-    if (N != c->n && N != c->M)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: N must be n (PackedCiphertext) or m (Ciphertext)");
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    if (out_w && !(pack_group(c)))
-        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
-    const CircuitPlan &P = circ->plan;
-    if (blocks == 0) return SGFHE_OK;
-    // the limits of sgfhe_circuit_run on blocks * n instances; the rows of the pack stage (n_outputs * instances)
-    // and the workgroups of the split kernel must be addressable too
-    const uint64_t instances = (uint64_t)blocks * c->n;
-    const uint64_t tiles = (c->n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS;
-    if (blocks >= 0x80000000u || instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull ||
-        (out_w && (uint64_t)P.n_outputs * instances > 0xFFFFFFFFull) ||
-        (uint64_t)P.n_inputs * blocks * tiles > 0x7FFFFFFFull)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: too many instances for this circuit");
-    if (c->n % P.group)   // (a group must not straddle two ciphertexts)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_ct: n must be a multiple of the circuit's lane group");
-    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
-                          (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
-    return circuit_run_form(c, device, st, [&] {
-        return CircuitRun(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data, device, st).run();
-    });
-}
-
-// sgfhe_circuit_run_steps and sgfhe_circuit_run_steps_device (`device`), the ctx locked
-static int32_t circuit_run_steps(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
-                                 const uint64_t *state_in, const uint64_t *in, const uint8_t *data, const uint8_t *emit,
-                                 uint64_t *out, uint64_t *state_out, bool device, hipStream_t st) {
-    if (!circ || (!in && circ->plan.n_stream()) || (!out && !state_out))
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: NULL circuit or input pointer, or no output pointer");
-    const CircuitPlan &P = circ->plan;
-    if (!data && P.n_planes && instances && steps)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: NULL data for a plan with data planes");
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    if (instances == 0 || steps == 0) return SGFHE_OK;
-    // the limits of sgfhe_circuit_run
-    if (instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: too many instances for this circuit");
-    if (instances % P.group)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps: instances must be a multiple of the circuit's lane group");
-    const CircuitSteps seq = {steps, emit, state_in, nullptr, nullptr, state_out};
-    return circuit_run_form(c, device, st, [&] {
-        CircuitRun R(c, P, instances, in, out, nullptr, nullptr, data, device, st);
-        R.seq = &seq;
-        return R.run();
-    });
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.ct = q.with_data = true;
+    q.count = blocks, q.in_a = in_a, q.in_b = in_b, q.N = N, q.data = data;
+    q.out_w = out_w, q.out_v = out_v, q.out = out_lwe, q.flags = flags;
+    return circuit_run(c, circ, q);
 }
 
 int32_t sgfhe_circuit_run_steps(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
                                 const uint64_t *state_in, const uint64_t *in, const uint8_t *data, const uint8_t *emit,
                                 uint64_t *out, uint64_t *state_out) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    return circuit_run_steps(c, circ, instances, steps, state_in, in, data, emit, out, state_out, false, nullptr);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.stepped = q.with_data = true;
+    q.count = instances, q.steps = steps, q.state_in = state_in, q.in = in, q.data = data, q.emit = emit;
+    q.out = out, q.state_out = state_out;
+    return circuit_run(c, circ, q);
 }
-
-// sgfhe_circuit_run_steps_ct and sgfhe_circuit_run_steps_ct_device (`device`), the ctx locked
-static int32_t circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
-                                    const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
-                                    const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit,
-                                    uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
-                                    uint32_t flags, bool device, hipStream_t st);
 
 int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
                                    const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
@@ -3955,79 +3861,50 @@ int32_t sgfhe_circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size
                                    uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
                                    uint32_t flags) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // the whole run: its call numbers are contiguous
-    return circuit_run_steps_ct(c, circ, blocks, steps, state_a, state_b, in_a, in_b, N, data, emit, out_w, out_v, out_lwe,
-                                state_lwe, flags, false, nullptr);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.ct = q.stepped = q.with_data = true;
+    q.count = blocks, q.steps = steps, q.state_a = state_a, q.state_b = state_b, q.in_a = in_a, q.in_b = in_b, q.N = N;
+    q.data = data, q.emit = emit;
+    q.out_w = out_w, q.out_v = out_v, q.out = out_lwe, q.state_out = state_lwe, q.flags = flags;
+    return circuit_run(c, circ, q);
 }
 
-static int32_t circuit_run_steps_ct(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
-                                    const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
-                                    const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit,
-                                    uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
-                                    uint32_t flags, bool device, hipStream_t st) {
-    if ((flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || flags == SGFHE_CIRCUIT_PACK_LIFT)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
-    if (!circ || ((!in_a || !in_b) && circ->plan.n_stream()) || !state_a != !state_b)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: NULL circuit or input pointer (state_a and state_b go together)");
-    const CircuitPlan &P = circ->plan;
-    for (uint32_t i = 0; i < P.n_regs; i++)   // a split ciphertext is scale 0, and an LWE cannot be halved
-        if (P.reg_scale[i])
-            return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: a register of scale 1 or 2 has no ciphertext form");
-    if (!data && P.n_planes && blocks && steps)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: NULL data for a plan with data planes");
-    if (!out_w != !out_v || (!out_w && !out_lwe && !state_lwe))
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: out_w and out_v go together, and one output form is needed");
-    if (N != c->n && N != c->M)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: N must be n (PackedCiphertext) or m (Ciphertext)");
-    if (!c->have_key) return fail(c, SGFHE_ERR_NO_KEY, "no bootstrap key uploaded");
-    if (out_w && !(pack_group(c)))
-        return fail(c, SGFHE_ERR_UNSUPPORTED, "pack_encrypted_bits: exactness bound of the RNS primes");
-    if (blocks == 0 || steps == 0) return SGFHE_OK;
-    // the limits of sgfhe_circuit_run_ct
-    const uint64_t instances = (uint64_t)blocks * c->n;
-    const uint64_t tiles = (c->n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS;
-    if (blocks >= 0x80000000u || instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull ||
-        (out_w && (uint64_t)P.n_outputs * instances > 0xFFFFFFFFull) ||
-        (uint64_t)P.n_inputs * blocks * tiles > 0x7FFFFFFFull)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: too many instances for this circuit");
-    if (c->n % P.group)   // (a group must not straddle two ciphertexts)
-        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_circuit_run_steps_ct: n must be a multiple of the circuit's lane group");
-    const CircuitCt ct = {in_a, in_b, blocks, N, out_w, out_v, (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0,
-                          (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0};
-    const CircuitSteps seq = {steps, emit, nullptr, state_a, state_b, state_lwe};
-    return circuit_run_form(c, device, st, [&] {
-        CircuitRun R(c, P, (size_t)instances, nullptr, out_lwe, &ct, nullptr, data, device, st);
-        R.seq = &seq;
-        return R.run();
-    });
-}
-
-// ---- device-resident runs: the most general host entry of each form, every array (but `emit`) in device memory, the
-// work queued on `stream` (NULL: the ctx's own) and left in flight (include/sgfhe_hip.h) ----------------------------
+// device-resident runs: the most general host entry of each form, every array (but `emit`) in device memory, the work
+// queued on `stream` and left in flight
 
 int32_t sgfhe_circuit_run_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, const uint64_t *in,
                                  const uint8_t *data, uint64_t *out, void *stream) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
-    return circuit_run_lwe(c, circ, instances, in, out, nullptr, true, data, true, (hipStream_t)stream);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.device = q.with_data = true, q.stream = stream;
+    q.count = instances, q.in = in, q.data = data, q.out = out;
+    return circuit_run(c, circ, q);
 }
 
 int32_t sgfhe_circuit_run_ct_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, const uint64_t *in_a,
                                     const uint64_t *in_b, size_t N, const uint8_t *data, uint64_t *out_w, uint64_t *out_v,
                                     uint64_t *out_lwe, uint32_t flags, void *stream) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
-    return circuit_run_ct(c, circ, blocks, in_a, in_b, N, out_w, out_v, out_lwe, flags, true, data, true,
-                          (hipStream_t)stream);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.ct = q.device = q.with_data = true, q.stream = stream;
+    q.count = blocks, q.in_a = in_a, q.in_b = in_b, q.N = N, q.data = data;
+    q.out_w = out_w, q.out_v = out_v, q.out = out_lwe, q.flags = flags;
+    return circuit_run(c, circ, q);
 }
 
 int32_t sgfhe_circuit_run_steps_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t instances, size_t steps,
                                        const uint64_t *state_in, const uint64_t *in, const uint8_t *data,
                                        const uint8_t *emit, uint64_t *out, uint64_t *state_out, void *stream) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
-    return circuit_run_steps(c, circ, instances, steps, state_in, in, data, emit, out, state_out, true,
-                             (hipStream_t)stream);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.stepped = q.device = q.with_data = true, q.stream = stream;
+    q.count = instances, q.steps = steps, q.state_in = state_in, q.in = in, q.data = data, q.emit = emit;
+    q.out = out, q.state_out = state_out;
+    return circuit_run(c, circ, q);
 }
 
 int32_t sgfhe_circuit_run_steps_ct_device(sgfhe_ctx *c, const sgfhe_circuit *circ, size_t blocks, size_t steps,
@@ -4036,9 +3913,13 @@ int32_t sgfhe_circuit_run_steps_ct_device(sgfhe_ctx *c, const sgfhe_circuit *cir
                                           uint64_t *out_w, uint64_t *out_v, uint64_t *out_lwe, uint64_t *state_lwe,
                                           uint32_t flags, void *stream) {
     if (!c) return SGFHE_ERR_INVALID_ARG;
-    SGFHE_LOCK(c);   // while the run queues: its call numbers are contiguous
-    return circuit_run_steps_ct(c, circ, blocks, steps, state_a, state_b, in_a, in_b, N, data, emit, out_w, out_v, out_lwe,
-                                state_lwe, flags, true, (hipStream_t)stream);
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    q.ct = q.stepped = q.device = q.with_data = true, q.stream = stream;
+    q.count = blocks, q.steps = steps, q.state_a = state_a, q.state_b = state_b, q.in_a = in_a, q.in_b = in_b, q.N = N;
+    q.data = data, q.emit = emit;
+    q.out_w = out_w, q.out_v = out_v, q.out = out_lwe, q.state_out = state_lwe, q.flags = flags;
+    return circuit_run(c, circ, q);
 }
 
 }  // extern "C"

@@ -85,6 +85,39 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _hptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+
+# What the ciphertext forms of a circuit run share, host and device-resident alike
+
+def _pack_flags(direct, lift):
+    """The flag word of sgfhe_circuit_run_ct_ex and its kin: the C ABI takes the lift bit only with the direct bit."""
+    return (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
+
+
+def _ct_outputs(circuit, p, blocks, packed, lwe, alloc, emitted=None):
+    """(w, v, out) of a ciphertext run over `blocks`: w, v [n_outputs][blocks][m] if packed, out [n_outputs][blocks * n]
+    [n + 1] if lwe, None otherwise; a stepped run has them per emitted step.  alloc(shape) makes each."""
+    lead = () if emitted is None else (emitted,)
+    wv = lead + (circuit.n_outputs, blocks, p.m)
+    return (alloc(wv) if packed else None, alloc(wv) if packed else None,
+            alloc(lead + (circuit.n_outputs, blocks * p.n, p.n + 1)) if lwe else None)
+
+
+def _ct_result(w, v, out):
+    """(w, v), the LWE array, or ((w, v), lwe): whichever of them the caller asked for."""
+    if w is not None and out is not None:
+        return (w, v), out
+    return (w, v) if w is not None else out
+
+
+def _same_dtype(name, t, like_name, like):
+    """An argument of a device-resident run has the dtype of the tensor it goes with."""
+    if t.dtype != like.dtype:
+        raise ValueError("%s: dtype %s, %s has %s" % (name, t.dtype, like_name, like.dtype))
+
+
 class Engine:
     """One bootstrap engine (ctx) for one parameter set on one HIP device."""
 
@@ -423,23 +456,17 @@ class Engine:
         if not packed and not lwe:
             raise ValueError("circuit_run_ct: ask for the packed outputs, the LWE outputs or both")
         blocks = a.shape[1]
-        w = np.zeros((circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
-        v = np.zeros((circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
-        out = np.zeros((circuit.n_outputs, blocks * p.n, p.n + 1), dtype=np.uint64) if lwe else None
-        ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None else None
+        w, v, out = _ct_outputs(circuit, p, blocks, packed, lwe, lambda shape: np.zeros(shape, dtype=np.uint64))
+        outs = (_hptr(w), _hptr(v), _hptr(out))
         d, pd = self._planes(circuit, data, blocks * p.n)
         if d is not None:
-            flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
-            self._call("sgfhe_circuit_run_ct_data", circuit.handle(), blocks, pa, pb, a.shape[2], pd, ptr(w), ptr(v),
-                       ptr(out), flags)
+            self._call("sgfhe_circuit_run_ct_data", circuit.handle(), blocks, pa, pb, a.shape[2], pd, *outs,
+                       _pack_flags(direct, lift))
         elif direct or lift:
-            self._call("sgfhe_circuit_run_ct_ex", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out),
-                       CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0))
+            self._call("sgfhe_circuit_run_ct_ex", circuit.handle(), blocks, pa, pb, a.shape[2], *outs, _pack_flags(direct, lift))
         else:
-            self._call("sgfhe_circuit_run_ct", circuit.handle(), blocks, pa, pb, a.shape[2], ptr(w), ptr(v), ptr(out))
-        if packed and lwe:
-            return (w, v), out
-        return (w, v) if packed else out
+            self._call("sgfhe_circuit_run_ct", circuit.handle(), blocks, pa, pb, a.shape[2], *outs)
+        return _ct_result(w, v, out)
 
     @staticmethod
     def _step_args(circuit, data, emit, steps, instances):
@@ -515,16 +542,11 @@ class Engine:
                 raise ValueError("circuit_run_steps_ct: state_a and state_b must be [registers=%d][blocks=%d][N=%d]"
                                  % (circuit.n_regs, blocks, N))
         d, pd, e, pe, emitted = self._step_args(circuit, data, emit, steps, blocks * p.n)
-        w = np.zeros((emitted, circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
-        v = np.zeros((emitted, circuit.n_outputs, blocks, p.m), dtype=np.uint64) if packed else None
-        out = np.zeros((emitted, circuit.n_outputs, blocks * p.n, p.n + 1), dtype=np.uint64) if lwe else None
+        w, v, out = _ct_outputs(circuit, p, blocks, packed, lwe, lambda shape: np.zeros(shape, dtype=np.uint64), emitted)
         st = np.zeros((circuit.n_regs, blocks * p.n, p.n + 1), dtype=np.uint64)
-        ptr = lambda x: x.ctypes.data_as(ctypes.c_void_p) if x is not None else None
-        flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
-        self._call("sgfhe_circuit_run_steps_ct", circuit.handle(), blocks, steps, psa, psb, pa, pb, N, pd, pe, ptr(w),
-                   ptr(v), ptr(out), ptr(st), flags)
-        res = ((w, v), out) if packed and lwe else ((w, v) if packed else out)
-        return res, st
+        self._call("sgfhe_circuit_run_steps_ct", circuit.handle(), blocks, steps, psa, psb, pa, pb, N, pd, pe, _hptr(w),
+                   _hptr(v), _hptr(out), _hptr(st), _pack_flags(direct, lift))
+        return _ct_result(w, v, out), st
 
     # ---- device-resident circuit runs --------------------------------------------------------------
     # The run forms above with every array a torch.Tensor on the engine's device (sgfhe_circuit_run*_device): the same
@@ -599,22 +621,16 @@ class Engine:
         if a.shape[2] not in (p.n, p.m):
             raise ValueError("a: shape must be [n_inputs=%d][blocks][N], N = n = %d or m = %d" % (circuit.n_inputs, p.n, p.m))
         b = check_device_tensor("b", b, tuple(a.shape), self.device)
-        if b.dtype != a.dtype:
-            raise ValueError("b: dtype %s, a has %s" % (b.dtype, a.dtype))
+        _same_dtype("b", b, "a", a)
         if not packed and not lwe:
             raise ValueError("circuit_run_ct_device: ask for the packed outputs, the LWE outputs or both")
         blocks = a.shape[1]
         d = self._planes_device(circuit, data, (circuit.planes, blocks * p.n))
-        w = self._empty((circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
-        v = self._empty((circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
-        out = self._empty((circuit.n_outputs, blocks * p.n, p.n + 1), a.dtype, hip_stream) if lwe else None
-        flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
+        w, v, out = _ct_outputs(circuit, p, blocks, packed, lwe, lambda shape: self._empty(shape, a.dtype, hip_stream))
         if blocks:
             self._call("sgfhe_circuit_run_ct_device", circuit.handle(), blocks, _ptr(a), _ptr(b), a.shape[2], _ptr(d),
-                       _ptr(w), _ptr(v), _ptr(out), flags, _stream_handle(hip_stream))
-        if packed and lwe:
-            return (w, v), out
-        return (w, v) if packed else out
+                       _ptr(w), _ptr(v), _ptr(out), _pack_flags(direct, lift), _stream_handle(hip_stream))
+        return _ct_result(w, v, out)
 
     def circuit_run_steps_device(self, circuit, state, stream, data=None, emit=None, out=None, state_out=None,
                                  hip_stream=None):
@@ -632,8 +648,7 @@ class Engine:
         steps, inst = x.shape[0], x.shape[2]
         if state is not None:
             check_device_tensor("state", state, (circuit.n_regs, inst, n + 1), self.device)
-            if state.dtype != x.dtype:
-                raise ValueError("state: dtype %s, stream has %s" % (state.dtype, x.dtype))
+            _same_dtype("state", state, "stream", x)
         d = self._planes_device(circuit, data, (steps, circuit.planes, inst))
         e, pe, emitted = self._emit_arg(emit, steps)
         out = self._result("out", out, (emitted, circuit.n_outputs, inst, n + 1), x, hip_stream)
@@ -657,8 +672,7 @@ class Engine:
             raise ValueError("a: shape must be [steps][stream inputs=%d][blocks][N], N = n = %d or m = %d"
                              % (circuit.n_inputs - circuit.n_regs, p.n, p.m))
         b = check_device_tensor("b", b, tuple(a.shape), self.device)
-        if b.dtype != a.dtype:
-            raise ValueError("b: dtype %s, a has %s" % (b.dtype, a.dtype))
+        _same_dtype("b", b, "a", a)
         if not packed and not lwe:
             raise ValueError("circuit_run_steps_ct_device: ask for the packed outputs, the LWE outputs or both")
         steps, blocks, N = a.shape[0], a.shape[2], a.shape[3]
@@ -667,21 +681,17 @@ class Engine:
         for name, s in (("state_a", state_a), ("state_b", state_b)):
             if s is not None:
                 check_device_tensor(name, s, (circuit.n_regs, blocks, N), self.device)
-                if s.dtype != a.dtype:
-                    raise ValueError("%s: dtype %s, a has %s" % (name, s.dtype, a.dtype))
+                _same_dtype(name, s, "a", a)
         d = self._planes_device(circuit, data, (steps, circuit.planes, blocks * p.n))
         e, pe, emitted = self._emit_arg(emit, steps)
-        w = self._empty((emitted, circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
-        v = self._empty((emitted, circuit.n_outputs, blocks, p.m), a.dtype, hip_stream) if packed else None
-        out = self._empty((emitted, circuit.n_outputs, blocks * p.n, p.n + 1), a.dtype, hip_stream) if lwe else None
+        w, v, out = _ct_outputs(circuit, p, blocks, packed, lwe, lambda shape: self._empty(shape, a.dtype, hip_stream),
+                                emitted)
         st = self._empty((circuit.n_regs, blocks * p.n, p.n + 1), a.dtype, hip_stream)
-        flags = (CIRCUIT_PACK_DIRECT | (CIRCUIT_PACK_LIFT if lift else 0)) if direct or lift else 0
         if steps and blocks:
             self._call("sgfhe_circuit_run_steps_ct_device", circuit.handle(), blocks, steps, _ptr(state_a), _ptr(state_b),
-                       _ptr(a), _ptr(b), N, _ptr(d), pe, _ptr(w), _ptr(v), _ptr(out), _ptr(st), flags,
+                       _ptr(a), _ptr(b), N, _ptr(d), pe, _ptr(w), _ptr(v), _ptr(out), _ptr(st), _pack_flags(direct, lift),
                        _stream_handle(hip_stream))
-        res = ((w, v), out) if packed and lwe else ((w, v) if packed else out)
-        return res, st
+        return _ct_result(w, v, out), st
 
     def pack_encrypted_bits(self, a, b):
         """pack_encrypted_bits (fhe.jl:660-696) for `count` groups of n LWEs: a [count][n][n],

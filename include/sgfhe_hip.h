@@ -1172,6 +1172,57 @@ int32_t sgfhe_circuit_run_steps_ct_device(sgfhe_ctx *ctx, const sgfhe_circuit *c
                                           uint64_t *out_lwe, uint64_t *state_lwe, uint32_t flags, void *stream);
 
 /*
+ * Parity / debug hook: a circuit run with every bootstrap call and the pack tail replaced by a script, so that the glue
+ * kernels of a run (k_circ_split, k_circ_gather, k_circ_xor3[_raw], k_circ_scatter[_raw], k_circ_raw_and, k_circ_lift,
+ * k_circ_collect, k_circ_state_load, k_circ_next) work on caller-chosen words.  The run is built and checked as the run
+ * entries build and check theirs, and walks the same calls with the same kernels, grids, buffers and job chunks; only
+ *   - a level call: the gather runs; the staged rows of the call go to `staged`, and the call's LUT descriptor, if it
+ *     carries one, to `lut`; in place of the bootstrap the script's result rows of the call are copied in; the call's
+ *     XOR3 and scatter kernels follow;
+ *   - the refresh call of a pack group: its gathers run, the staged rows are logged, and scripted un-reduced rows stand
+ *     in for the bootstrap; k_circ_raw_and follows in a direct run (a lifted group has no call: k_circ_lift runs);
+ *   - the tail: the rows it would read -- gate 0 of the refresh result, or with SGFHE_CIRCUIT_PACK_DIRECT the group's
+ *     rows of the raw output table -- go to `tail_in`; no (w, v) is formed.
+ *   form     : SGFHE_SCRIPT_CT (the arguments of sgfhe_circuit_run_ct_ex; otherwise those of sgfhe_circuit_run_data) |
+ *              SGFHE_SCRIPT_STEPPED (those of sgfhe_circuit_run_steps[_ct]).  The probe and the device forms
+ *              (SGFHE_SCRIPT_PROBE, SGFHE_SCRIPT_DEVICE) are refused.
+ *   count, steps, N, data, emit, out, state_out, flags : as in the run entry of that form (steps, emit and state_out
+ *              are read in the stepped forms, N and flags in the ciphertext forms); `out` is the LWE output
+ *   in_a, in_b       : the ciphertext forms' inputs; the LWE forms take `in` as in_a and ignore in_b
+ *   state_a, state_b : stepped: the ciphertext forms' first state; the LWE form takes state_in as state_a
+ *   results  : the scripted calls' result rows, concatenated in the run's own call order -- per step the level calls,
+ *              then the refresh calls of an emitted step's pack groups --, each block compact: [rows][3][n + 1] words
+ *              of Z_r, or where the real run leaves the call un-reduced (a level call of a direct run that produces a
+ *              direct output; every refresh call) [rows][3][n + 1][2] residues mod Q, {lo, hi}
+ *   staged   : log, per scripted call [rows][2][n + 1]: input 1 then input 2 of every row, a then b
+ *   lut      : log, per scripted call [rows] uint32: the descriptor words (0x100 | table for a LUT row, 0 for any
+ *              other), 0 throughout for a call that carries no descriptor
+ *   tail_in  : log [emitted steps][n_outputs * blocks][n][n + 1][2], or NULL: the run has no pack stage (then `out` or
+ *              state_out is needed); this is what out_w / out_v are to a run entry
+ * sgfhe_debug_circuit_script_calls gives the number of scripted calls of such a run (`pack`: tail_in is given), and
+ * for the first `cap` of them the rows and whether they are un-reduced, so that a caller can size its arrays.
+ * Needs no key, takes no call number and draws nothing: last_call and the draw stream stay as they were, and the bytes
+ * are the same in either flatten mode.  Host pointers; synchronous.  SGFHE_ERR_INVALID_ARG, before anything is queued
+ * or written: everything the run entries refuse (but a missing key), in their order and words; NULL results, staged or
+ * lut; a scripted word that is not below r; a scripted residue that is not below Q; a plan with a live LUT sibling
+ * (sgfhe_circuit_create_lut_multi) -- the sibling's wires are written into the wire table inside the bootstrap call, by
+ * k_final_lut_multi from the accumulator, which result rows cannot stand in for.  An empty run (count or steps 0)
+ * returns SGFHE_OK and touches nothing.
+ */
+#define SGFHE_SCRIPT_CT 1u
+#define SGFHE_SCRIPT_STEPPED 2u
+#define SGFHE_SCRIPT_PROBE 4u
+#define SGFHE_SCRIPT_DEVICE 8u
+int32_t sgfhe_debug_circuit_script(sgfhe_ctx *ctx, const sgfhe_circuit *circuit, uint32_t form, size_t count, size_t steps,
+                                   const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
+                                   const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit, uint64_t *out,
+                                   uint64_t *state_out, uint32_t flags, const uint64_t *results, uint64_t *staged,
+                                   uint32_t *lut, uint64_t *tail_in);
+int32_t sgfhe_debug_circuit_script_calls(sgfhe_ctx *ctx, const sgfhe_circuit *circuit, uint32_t form, size_t count,
+                                         size_t steps, const uint8_t *emit, int pack, uint32_t flags, size_t *n_calls,
+                                         uint32_t *rows, uint8_t *raw, size_t cap);
+
+/*
  * Measurement hook for bench.py: HIP-event timings taken on the ctx stream around sampled
  * launches of the two per-iteration kernels since the last reset (stats must hold 8 doubles).
  *   stats[0] = average external-product kernel time (ms)   stats[1] = its sampled launches

@@ -177,6 +177,8 @@ def lib():
         "sgfhe_circuit_run_ct_device": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, vp]),
         "sgfhe_circuit_run_steps_device": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]),
         "sgfhe_circuit_run_steps_ct_device": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, u32, vp]),
+        "sgfhe_debug_circuit_script": (i32, [vp, vp, u32, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+        "sgfhe_debug_circuit_script_calls": (i32, [vp, vp, u32, sz, sz, vp, ctypes.c_int, u32, ctypes.POINTER(sz), vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
@@ -208,4 +210,5 @@ EXPORTED_SYMBOLS = (
     "sgfhe_circuit_planes", "sgfhe_circuit_run_data", "sgfhe_circuit_run_ct_data", "sgfhe_circuit_run_probe_data",
     "sgfhe_circuit_create_seq", "sgfhe_circuit_registers", "sgfhe_circuit_run_steps", "sgfhe_circuit_run_steps_ct",
     "sgfhe_circuit_create_routed", "sgfhe_circuit_routes", "sgfhe_circuit_run_device", "sgfhe_circuit_run_ct_device",
-    "sgfhe_circuit_run_steps_device", "sgfhe_circuit_run_steps_ct_device")
+    "sgfhe_circuit_run_steps_device", "sgfhe_circuit_run_steps_ct_device", "sgfhe_debug_circuit_script",
+    "sgfhe_debug_circuit_script_calls")

@@ -11,8 +11,8 @@
 // So do the arguments of a run: every run entry fills one CircuitRequest, and circuit_request_check is its only judge.
 // Plain C++, no HIP: tests/native/circuit_plan_sanitized.cpp, circuit_bits_sanitized.cpp, circuit_lanes_sanitized.cpp,
 // circuit_gate3_sanitized.cpp, circuit_wsum_sanitized.cpp, circuit_lut_sanitized.cpp, circuit_lut_multi_sanitized.cpp,
-// circuit_data_sanitized.cpp, circuit_calls_sanitized.cpp, circuit_steps_sanitized.cpp, circuit_routes_sanitized.cpp
-// and circuit_request_sanitized.cpp drive it under ASan / UBSan on the CPU.
+// circuit_data_sanitized.cpp, circuit_calls_sanitized.cpp, circuit_steps_sanitized.cpp, circuit_routes_sanitized.cpp,
+// circuit_request_sanitized.cpp and circuit_script_sanitized.cpp drive it under ASan / UBSan on the CPU.
 #pragma once
 
 #include <stddef.h>
@@ -900,10 +900,56 @@ struct CircuitRequest {
     const uint64_t *sk = nullptr;                        // probe: n key bits,
     const uint8_t *in_bits = nullptr;                    // the plaintext bit of every input LWE [n_inputs][instances],
     uint64_t *stats = nullptr;                           // the records [n_inputs + 3 n_gates][8], by wire id
+    const struct CircuitScript *script = nullptr;        // sgfhe_debug_circuit_script: the run's calls are scripted (below)
 
+    bool packs() const;                                  // ct: the run has a pack stage (out_w, or the script's tail_in)
     bool direct() const { return (flags & SGFHE_CIRCUIT_PACK_DIRECT) != 0; }
     bool lift() const { return (flags & SGFHE_CIRCUIT_PACK_LIFT) != 0; }   // (with direct)
 };
+
+// A scripted run (sgfhe_debug_circuit_script): the run of a host-form request with every bootstrap call and the pack
+// tail replaced by the caller's arrays.  The scripted calls are those of circuit_script_calls, in that order; each
+// block is compact.
+struct CircuitScript {
+    const uint64_t *results = nullptr;   // per call [rows][3][n + 1] words of Z_r, or -- un-reduced -- [rows][3][n + 1][2]
+    uint64_t *staged = nullptr;          // log, per call [rows][2][n + 1]: input 1 then input 2 of every row, a then b
+    uint32_t *lut = nullptr;             // log, per call [rows]: the call's LUT descriptor, 0 for a call that carries none
+    uint64_t *tail_in = nullptr;         // log [emitted steps][n_ct][n][n + 1][2]: what the tail would read; NULL: no pack stage
+};
+inline bool CircuitRequest::packs() const { return ct && (out_w || (script && script->tail_in)); }
+
+// The scripted calls of a run: every step's level calls (circuit_level_call, every level from row 0), then -- an emitted
+// step of a run that packs -- the refresh call of every pack group that has one (circuit_pack_runs; none with lift).  A
+// call is un-reduced (16-byte residues mod Q) where the real run leaves it so: a level call of a direct run that
+// produces a direct output, and every refresh call.  `emit` is read ([steps], host memory; NULL: every step).  Returns
+// the number of calls; `calls` may be NULL to count only (and is otherwise what may allocate here).
+struct CircuitScriptCall {
+    uint32_t rows;
+    bool raw;   // un-reduced
+    bool lut;   // the call carries a LUT descriptor
+};
+inline size_t circuit_script_calls(const CircuitPlan &P, const CircuitRequest &q, size_t n, uint64_t instances,
+                                   std::vector<CircuitScriptCall> *calls) {
+    if (calls) calls->clear();
+    const bool pack = q.packs(), direct = pack && q.direct(), lift = direct && q.lift();
+    const CircuitRunSizes sz = circuit_run_sizes(P, instances, n, q.ct ? q.count : 0, pack, direct, lift);
+    size_t count = 0;
+    for (size_t s = 0; s < (q.stepped ? q.steps : 1); s++) {
+        for (uint32_t L = 1; L <= P.levels; L++)
+            for (uint64_t row0 = 0; row0 < P.level_rows(L, instances); row0 += SGFHE_CIRCUIT_CALL_ROWS, count++) {
+                const CircuitCall C = circuit_level_call(P, L, row0, instances);
+                if (calls) calls->push_back({C.rows, direct && C.j1 > C.j0, C.lut});
+            }
+        if (q.stepped && q.emit && !q.emit[s]) continue;
+        for (size_t q0 = 0; !lift && q0 < sz.n_ct; q0 += sz.cpc) {
+            const size_t nb = circuit_pack_runs(P, q.count, q0, std::min(sz.cpc, sz.n_ct - q0), !direct, nullptr) * n;
+            if (!nb) continue;
+            if (calls) calls->push_back({(uint32_t)nb, true, false});
+            count++;
+        }
+    }
+    return count;
+}
 
 // What the checks read of a ctx
 struct CircuitEnv {
@@ -929,6 +975,8 @@ inline CircuitVerdict circuit_request_check(const CircuitPlan *P, const CircuitR
     const auto refused = [](const char *entry, const std::string &what, int32_t code = SGFHE_ERR_INVALID_ARG) {
         return CircuitVerdict{CircuitVerdict::REFUSED, code, *entry ? std::string(entry) + ": " + what : what, 0};
     };
+    const char *hook = "sgfhe_debug_circuit_script";
+    if (q.script && (q.probe || q.device)) return refused(hook, "the host forms only: no probe, no device form");
     // (bit 1 without bit 0 was an unknown bit before SGFHE_CIRCUIT_PACK_LIFT existed, and stays refused)
     if (q.ct && ((q.flags & ~(SGFHE_CIRCUIT_PACK_DIRECT | SGFHE_CIRCUIT_PACK_LIFT)) || q.flags == SGFHE_CIRCUIT_PACK_LIFT))
         return refused(q.stepped ? form : "sgfhe_circuit_run_ct_ex", "unknown flag bits (PACK_LIFT goes with PACK_DIRECT)");
@@ -940,6 +988,11 @@ inline CircuitVerdict circuit_request_check(const CircuitPlan *P, const CircuitR
                                                : "NULL circuit or input pointer")
                                   : (q.stepped ? "NULL circuit or input pointer, or no output pointer"
                                                : "NULL circuit, input or output pointer"));
+    if (q.script && (!q.script->results || !q.script->staged || !q.script->lut))
+        return refused(hook, "NULL script: the calls' results, the staged log and the descriptor log are needed");
+    if (q.script && P->siblings())   // k_final_lut_multi writes the wires of a sibling inside the call
+        return refused(hook, "a plan with a live LUT sibling: its wires are written inside the bootstrap call, from the "
+                             "accumulator, which scripted result rows cannot stand in for");
     if (!q.stepped && P->n_regs)
         return refused("sgfhe_circuit_run", "a plan with registers runs through the _steps entries");
     for (uint32_t i = 0; q.stepped && q.ct && i < P->n_regs; i++)   // a split ciphertext is scale 0, and an LWE cannot be halved
@@ -950,18 +1003,18 @@ inline CircuitVerdict circuit_request_check(const CircuitPlan *P, const CircuitR
         return refused(q.stepped ? form : "sgfhe_circuit_run_data", "NULL data for a plan with data planes");
     if (q.probe && (!q.sk || !q.stats || (!q.in_bits && P->n_inputs)))
         return refused("sgfhe_circuit_run_probe", "NULL secret key, input bits or statistics pointer");
-    if (q.ct && (!q.out_w != !q.out_v || (!q.out_w && !q.out && !q.state_out)))
+    if (q.ct && (!q.out_w != !q.out_v || (!q.packs() && !q.out && !q.state_out)))
         return refused(form, "out_w and out_v go together, and one output form is needed");
     if (q.ct && q.N != env.n && q.N != env.M) return refused(form, "N must be n (PackedCiphertext) or m (Ciphertext)");
-    if (!env.have_key) return refused("", "no bootstrap key uploaded", SGFHE_ERR_NO_KEY);
-    if (q.ct && q.out_w && !env.pack_exact)
+    if (!env.have_key && !q.script) return refused("", "no bootstrap key uploaded", SGFHE_ERR_NO_KEY);   // (no call: no key)
+    if (q.packs() && !env.pack_exact)
         return refused("pack_encrypted_bits", "exactness bound of the RNS primes", SGFHE_ERR_UNSUPPORTED);
     if (q.count == 0 || q.steps == 0) return {CircuitVerdict::EMPTY, SGFHE_OK, {}, 0};
     // rows of a level, and words of every table, must be addressable by the kernels' indices; in the ct forms the rows
     // of the pack stage (n_outputs * instances) and the workgroups of the split kernel too
     const uint64_t instances = q.ct ? (uint64_t)q.count * env.n : q.count;
     if (q.count >= 0x80000000u || instances >= 0x80000000u || (uint64_t)P->widest * instances > 0xFFFFFFFFull ||
-        (q.ct && ((q.out_w && (uint64_t)P->n_outputs * instances > 0xFFFFFFFFull) ||
+        (q.ct && ((q.packs() && (uint64_t)P->n_outputs * instances > 0xFFFFFFFFull) ||
                   (uint64_t)P->n_inputs * q.count * env.split_tiles > 0x7FFFFFFFull)))
         return refused(form, "too many instances for this circuit");
     if ((q.ct ? env.n : instances) % P->group)   // (ct: a group must not straddle two ciphertexts)

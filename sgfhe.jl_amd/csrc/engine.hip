@@ -3216,7 +3216,7 @@ struct CircuitRun {
     // SGFHE_CIRCUIT_PACK_DIRECT: the outputs that name a gate wire are the plan's jobs, and their rows go from the level
     // calls into the raw table.  SGFHE_CIRCUIT_PACK_LIFT: every other ciphertext is lifted from the wire table into the
     // raw table (k_circ_lift), so no group has a refreshed one
-    const bool pack = q.ct && q.out_w, direct = pack && q.direct(), lift = direct && q.lift();
+    const bool pack = q.packs(), direct = pack && q.direct(), lift = direct && q.lift();
     const CircuitRunSizes sz = circuit_run_sizes(P, instances, n, q.ct ? q.count : 0, pack, direct, lift);
     // (a stepped run splits the registers' ciphertexts and a step's stream ciphertexts in turn through the one buffer)
     const size_t ct_words = q.ct ? (size_t)P.n_inputs * q.count * q.N : 0;
@@ -3232,6 +3232,9 @@ struct CircuitRun {
     // the probe's host images, which the run's asynchronous copies read and write: [key mask | bit table]; the records
     // by probe row
     std::vector<uint64_t> up, down;
+    // a scripted run (sgfhe_debug_circuit_script): where the next scripted call, and the next group's tail rows, lie in
+    // the script's arrays -- words of `results`, rows of the two logs, ciphertexts of `tail_in`
+    size_t script_words = 0, script_rows = 0, script_cts = 0;
 
     CircuitRun(sgfhe_ctx *c, const CircuitPlan &P, const CircuitRequest &q, size_t instances)
         : c(c), P(P), q(q), instances(instances) {}
@@ -3242,6 +3245,8 @@ struct CircuitRun {
     int32_t upload_lwe();
     int32_t level_call(uint32_t L, uint64_t row0);
     int32_t pack_group(size_t q0);
+    int32_t script_call(const Staging &S, size_t rows, bool raw, const uint32_t *lutw, uint64_t *res);
+    int32_t script_tail(const ulonglong2 *raw, size_t rstride, size_t cnt);
     // every level L = 1 .. levels in calls of SGFHE_CIRCUIT_CALL_ROWS rows from row 0; then every pack group from
     // ciphertext 0: the walk that numbers a run's calls (csrc/circuit.h)
     int32_t level_calls() {
@@ -3422,6 +3427,33 @@ int32_t CircuitRun::upload_lwe() {
     return SGFHE_OK;
 }
 
+// A scripted call (sgfhe_debug_circuit_script) in place of bootstrap_device: the staged rows of the call -- and its LUT
+// descriptor `lutw`, if it carries one -- go to the script's logs, and the script's result rows of the call into `res`,
+// reduced words or -- `raw` -- 16-byte residues, as the real call would leave them there
+int32_t CircuitRun::script_call(const Staging &S, size_t rows, bool raw, const uint32_t *lutw, uint64_t *res) {
+    const CircuitScript &X = *q.script;
+    uint64_t *log = X.staged + script_rows * 2 * row;   // [rows][2][n + 1]: (a1, b1), (a2, b2)
+    const size_t pitch = 2 * row * 8;
+    HIPCHK(c, hipMemcpy2DAsync(log, pitch, S.a1, n * 8, n * 8, rows, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpy2DAsync(log + n, pitch, S.b1, 8, 8, rows, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpy2DAsync(log + row, pitch, S.a2, n * 8, n * 8, rows, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpy2DAsync(log + row + n, pitch, S.b2, 8, 8, rows, hipMemcpyDeviceToHost, st));
+    if (lutw) HIPCHK(c, hipMemcpyAsync(X.lut + script_rows, lutw, rows * 4, hipMemcpyDeviceToHost, st));
+    const size_t words = rows * 3 * row * (raw ? 2 : 1);
+    HIPCHK(c, hipMemcpyAsync(res, X.results + script_words, words * 8, hipMemcpyHostToDevice, st));
+    script_rows += rows, script_words += words;
+    return SGFHE_OK;
+}
+
+// ... and in place of pack_tail: the `cnt` * n rows the tail would read, n + 1 residues each at raw + row * rstride,
+// into the script's tail_in
+int32_t CircuitRun::script_tail(const ulonglong2 *raw, size_t rstride, size_t cnt) {
+    HIPCHK(c, hipMemcpy2DAsync(q.script->tail_in + script_cts * n * row * 2, row * 16, raw, rstride * 16, row * 16, cnt * n,
+                               hipMemcpyDeviceToHost, st));
+    script_cts += cnt;
+    return SGFHE_OK;
+}
+
 // One level call: gather, the k-loop of sgfhe_bootstrap_batch_device (the next call number of the ctx's draw stream),
 // scatter.  In a direct run, a call that produces a wire some direct output names leaves its rows un-reduced: the
 // scatter reduces what the wire table takes (the words k_final writes) and copies the named rows into the raw table.
@@ -3445,7 +3477,7 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
     call.rows = S, call.batch = C.rows, call.out = S.res, call.st = st;
     if (raw) call.flags = SGFHE_FLAG_RAW_MODQ;
     if (C.lut) call.lut = &lut;
-    int32_t rc = bootstrap_device(c, call);
+    int32_t rc = q.script ? script_call(S, C.rows, raw, C.lut ? lut.rows : nullptr, S.res) : bootstrap_device(c, call);
     if (rc) return rc;
     if (raw) {
         const ulonglong2 *res = reinterpret_cast<const ulonglong2 *>(S.res);
@@ -3523,7 +3555,7 @@ int32_t CircuitRun::pack_group(size_t q0) {
         }
         BootCall call(c);
         call.rows = S, call.batch = nb, call.out = (uint64_t *)c->pack_raw.p, call.flags = SGFHE_FLAG_RAW_MODQ, call.st = st;
-        const int32_t rc = bootstrap_device(c, call);
+        const int32_t rc = q.script ? script_call(S, nb, true, nullptr, call.out) : bootstrap_device(c, call);
         if (rc) return rc;
         for (size_t i = 0; direct && i < runs.size(); i++) {
             const CircuitPackRun &U = runs[i];
@@ -3532,6 +3564,8 @@ int32_t CircuitRun::pack_group(size_t q0) {
             HIPCHK(c, hipGetLastError());
         }
     }
+    if (q.script)   // (no tail: no call number is taken)
+        return direct ? script_tail(c->circ_raw.p + q0 * n * row, row, cnt) : script_tail(c->pack_raw.p, 3 * row, cnt);
     uint64_t *d_w = c->pack_wv.p + q0 * M, *d_v = c->pack_wv.p + (sz.n_ct + q0) * M;
     if (!direct) return pack_tail(c, c->pack_raw.p, 3 * (uint32_t)row, cnt, d_w, d_v, c->last_call, st);
     const uint32_t call = c->rnd ? c->rnd_call++ : 0u;
@@ -3558,7 +3592,7 @@ int32_t CircuitRun::download() {
 // collected LWEs (`o` NULL: not wanted), which the device form collects straight into `o`
 int32_t CircuitRun::fetch(uint64_t *o, uint64_t *w, uint64_t *v) {
     int32_t rc;
-    if (pack) {
+    if (pack && !q.script) {   // (a scripted run has no tail: nothing wrote (w, v))
         const size_t wv = sz.n_ct * M;
         if ((rc = copy_out(w, c->pack_wv.p, wv * 8))) return rc;
         if ((rc = copy_out(v, c->pack_wv.p + wv, wv * 8))) return rc;
@@ -3661,6 +3695,31 @@ static int32_t circuit_run_form(sgfhe_ctx *c, bool device, hipStream_t st, F &&b
     return device ? run_queued(c, st ? st : c->stream, body) : run_drained(c, body);
 }
 
+// What sgfhe_debug_circuit_script checks of the script's memory, behind the request's check and before anything is
+// queued: every scripted word below r, every scripted residue below Q.  Then the descriptor log is cleared, so that a
+// call without a descriptor reads 0 there.
+static int32_t script_check(sgfhe_ctx *c, const CircuitPlan &P, const CircuitRequest &q, size_t instances) {
+    std::vector<CircuitScriptCall> calls;
+    try {
+        circuit_script_calls(P, q, c->n, instances, &calls);
+    } catch (...) {
+        return fail(c, SGFHE_ERR_OOM, "sgfhe_debug_circuit_script: no memory for the list of calls");
+    }
+    const uint64_t r = c->par.r, Qlo = c->par.Q[0], Qhi = c->par.Q[1];
+    const uint64_t *w = q.script->results;
+    size_t rows = 0;
+    for (const CircuitScriptCall &C : calls) {
+        const size_t words = (size_t)C.rows * 3 * (c->n + 1);
+        for (size_t i = 0; i < words; i++)
+            if (C.raw ? (w[2 * i + 1] > Qhi || (w[2 * i + 1] == Qhi && w[2 * i] >= Qlo)) : w[i] >= r)
+                return fail(c, SGFHE_ERR_INVALID_ARG, C.raw ? "sgfhe_debug_circuit_script: a scripted residue is not below Q"
+                                                            : "sgfhe_debug_circuit_script: a scripted word is not below r");
+        w += words * (C.raw ? 2 : 1), rows += C.rows;
+    }
+    std::fill(q.script->lut, q.script->lut + rows, 0u);
+    return SGFHE_OK;
+}
+
 // Every run entry, the ctx locked: the one check of the request (csrc/circuit.h), then the run in the request's form.
 // An empty probe run still clears the caller's records.
 static int32_t circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, const CircuitRequest &q) {
@@ -3673,6 +3732,8 @@ static int32_t circuit_run(sgfhe_ctx *c, const sgfhe_circuit *circ, const Circui
         if (q.probe) std::fill(q.stats, q.stats + ((size_t)P->n_inputs + 3 * (size_t)P->n_gates) * 8, 0ull);
         return SGFHE_OK;
     }
+    if (q.script)
+        if (const int32_t rc = script_check(c, *P, q, v.instances)) return rc;
     CircuitRun R(c, *P, q, v.instances);   // (outlives the wait that follows a failed step: the probe's host images)
     return circuit_run_form(c, q.device, (hipStream_t)q.stream, [&] { return R.run(); });
 }
@@ -3920,6 +3981,65 @@ int32_t sgfhe_circuit_run_steps_ct_device(sgfhe_ctx *c, const sgfhe_circuit *cir
     q.data = data, q.emit = emit;
     q.out_w = out_w, q.out_v = out_v, q.out = out_lwe, q.state_out = state_lwe, q.flags = flags;
     return circuit_run(c, circ, q);
+}
+
+// ---- the scripted run (a debug hook): the glue of a run with its calls and its tail replaced by the caller's arrays ----
+
+static bool script_form(uint32_t form, CircuitRequest &q) {
+    q.ct = form & SGFHE_SCRIPT_CT, q.stepped = (form & SGFHE_SCRIPT_STEPPED) != 0;
+    q.probe = (form & SGFHE_SCRIPT_PROBE) != 0, q.device = (form & SGFHE_SCRIPT_DEVICE) != 0;
+    q.with_data = true;
+    return !(form & ~(SGFHE_SCRIPT_CT | SGFHE_SCRIPT_STEPPED | SGFHE_SCRIPT_PROBE | SGFHE_SCRIPT_DEVICE));
+}
+
+int32_t sgfhe_debug_circuit_script(sgfhe_ctx *c, const sgfhe_circuit *circ, uint32_t form, size_t count, size_t steps,
+                                   const uint64_t *state_a, const uint64_t *state_b, const uint64_t *in_a,
+                                   const uint64_t *in_b, size_t N, const uint8_t *data, const uint8_t *emit, uint64_t *out,
+                                   uint64_t *state_out, uint32_t flags, const uint64_t *results, uint64_t *staged,
+                                   uint32_t *lut, uint64_t *tail_in) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    CircuitScript X;
+    X.results = results, X.staged = staged, X.lut = lut, X.tail_in = tail_in;
+    if (!script_form(form, q)) return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_debug_circuit_script: unknown form bits");
+    q.script = &X;
+    q.count = count, q.data = data, q.out = out;
+    if (q.stepped) q.steps = steps, q.emit = emit, q.state_out = state_out;
+    if (q.ct) q.in_a = in_a, q.in_b = in_b, q.N = N, q.flags = flags;
+    else q.in = in_a;
+    if (q.stepped && q.ct) q.state_a = state_a, q.state_b = state_b;
+    else if (q.stepped) q.state_in = state_a;
+    return circuit_run(c, circ, q);
+}
+
+int32_t sgfhe_debug_circuit_script_calls(sgfhe_ctx *c, const sgfhe_circuit *circ, uint32_t form, size_t count, size_t steps,
+                                         const uint8_t *emit, int pack, uint32_t flags, size_t *n_calls, uint32_t *rows,
+                                         uint8_t *raw, size_t cap) {
+    if (!c) return SGFHE_ERR_INVALID_ARG;
+    SGFHE_LOCK(c);
+    CircuitRequest q;
+    CircuitScript X;
+    uint64_t some = 0;
+    if (pack) X.tail_in = &some;   // (read as a flag only)
+    if (!script_form(form, q) || q.probe || q.device || !circ || !n_calls || (cap && (!rows || !raw)))
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_debug_circuit_script_calls: NULL pointer or a form the hook does not run");
+    q.script = &X, q.count = count, q.flags = q.ct ? flags : 0u;
+    if (q.stepped) q.steps = steps, q.emit = emit;
+    const CircuitPlan &P = circ->plan;
+    const uint64_t instances = q.ct ? (uint64_t)count * c->n : count;
+    if (count >= 0x80000000u || instances >= 0x80000000u || (uint64_t)P.widest * instances > 0xFFFFFFFFull ||
+        (uint64_t)P.n_outputs * instances > 0xFFFFFFFFull)
+        return fail(c, SGFHE_ERR_INVALID_ARG, "sgfhe_debug_circuit_script_calls: too many instances for this circuit");
+    std::vector<CircuitScriptCall> calls;
+    try {
+        if (count && q.steps) circuit_script_calls(P, q, c->n, instances, &calls);
+    } catch (...) {
+        return fail(c, SGFHE_ERR_OOM, "sgfhe_debug_circuit_script_calls: no memory for the list of calls");
+    }
+    *n_calls = calls.size();
+    for (size_t i = 0; i < std::min(cap, calls.size()); i++) rows[i] = calls[i].rows, raw[i] = calls[i].raw;
+    return SGFHE_OK;
 }
 
 }  // extern "C"

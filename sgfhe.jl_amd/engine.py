@@ -16,6 +16,7 @@ from . import _lib
 FLAG_RAW_MODQ = 1
 CIRCUIT_PACK_DIRECT = 1      # SGFHE_CIRCUIT_PACK_DIRECT
 CIRCUIT_PACK_LIFT = 2        # SGFHE_CIRCUIT_PACK_LIFT
+SCRIPT_CT, SCRIPT_STEPPED, SCRIPT_PROBE, SCRIPT_DEVICE = 1, 2, 4, 8   # SGFHE_SCRIPT_*: forms of sgfhe_debug_circuit_script
 FLAG_RAW_RNS2 = 2
 LUT_MAX_TABLES = 256         # SGFHE_LUT_MAX_TABLES
 CTX_RANDOM_FLATTEN = 1          # accepted, without effect since ABI revision 6
@@ -859,6 +860,95 @@ class Engine:
         self._call("sgfhe_debug_chunk_exit", pd, rows, pl, pt, T, (FLAG_RAW_MODQ if raw else 0) | (FLAG_RAW_RNS2 if rns2 else 0),
                    out.ctypes.data_as(ctypes.c_void_p), acc.ctypes.data_as(ctypes.c_void_p) if want_acc else None)
         return (out, acc) if want_acc else out
+
+    def debug_circuit_script_calls(self, circuit, count, ct=False, steps=None, emit=None, pack=False, direct=False,
+                                   lift=False):
+        """The scripted calls of a debug_circuit_script run (sgfhe_debug_circuit_script_calls), in the run's call order:
+        a list of (rows, un-reduced).  count: instances, or with ct=True blocks; steps: None for a one-shot run."""
+        form = (SCRIPT_CT if ct else 0) | (SCRIPT_STEPPED if steps is not None else 0)
+        _e, pe, _n = self._emit_arg(emit, steps) if steps is not None else (None, None, 1)
+        args = (circuit.handle(), form, count, steps or 0, pe, int(pack), _pack_flags(direct, lift))
+        k = ctypes.c_size_t(0)
+        self._call("sgfhe_debug_circuit_script_calls", *args, ctypes.byref(k), None, None, 0)
+        rows, raw = np.zeros(k.value, dtype=np.uint32), np.zeros(k.value, dtype=np.uint8)
+        self._call("sgfhe_debug_circuit_script_calls", *args, ctypes.byref(k), _hptr(rows), _hptr(raw), k.value)
+        return [(int(x), bool(y)) for x, y in zip(rows, raw)]
+
+    def debug_circuit_script(self, circuit, results, inputs, state=None, stepped=False, data=None, emit=None, pack=False,
+                             direct=False, lift=False, state_in_place=False):
+        """A circuit run whose bootstrap calls and pack tail are scripted (sgfhe_debug_circuit_script): the glue kernels
+        of a real run on chosen words, without a key.
+        inputs: the LWE form's array ([n_inputs][instances][n + 1]; stepped: [steps][stream inputs][instances][n + 1]) or
+        a pair (a, b) of the ciphertext form's ([n_inputs][blocks][N]; stepped: [steps][stream inputs][blocks][N]).
+        state: stepped: [registers][instances][n + 1], a pair (state_a, state_b), or None.  data, emit: as in the run of
+        that form.  pack (ciphertext form): the run has a pack stage; direct, lift: its flags.  state_in_place (LWE form,
+        stepped): the registers after the last step are written over `state`, which must then be a C-contiguous uint64
+        array: state_out is the very array state_in is.
+        results: one array per scripted call, in the order and of the rows of debug_circuit_script_calls: [rows][3][n + 1]
+        words of Z_r, or [rows][3][n + 1][2] residues of an un-reduced call.
+        Returns a dict: `out` the LWE outputs as the run of that form returns them, `state` (stepped) the registers after
+        the last step, `staged` a list of [rows][2][n + 1] per call (input 1, input 2; a then b), `lut` a list of [rows]
+        descriptor words per call, `tail_in` [emitted steps][n_outputs * blocks][n][n + 1][2] (pack) or None, `calls`."""
+        p = self.params
+        n = p.n
+        ct = isinstance(inputs, tuple)
+        if ct:
+            a, pa = _c(inputs[0])
+            b, pb = _c(inputs[1])
+            if a.shape != b.shape or a.ndim != (4 if stepped else 3):
+                raise ValueError("debug_circuit_script: a and b are [n_inputs][blocks][N], with [steps] in front when stepped")
+            count, N = a.shape[-2], a.shape[-1]
+            inst = count * n
+        else:
+            a, pa = _c(inputs)
+            pb, N = None, 0
+            if a.ndim != (4 if stepped else 3) or a.shape[-1] != n + 1:
+                raise ValueError("debug_circuit_script: inputs are [n_inputs][instances][n + 1], with [steps] in front when stepped")
+            count = inst = a.shape[-2]
+        steps = a.shape[0] if stepped else None
+        if a.shape[-3] != circuit.n_inputs - (circuit.n_regs if stepped else 0):
+            raise ValueError("debug_circuit_script: one input per input wire the caller brings")
+        psa = psb = None
+        if state is not None:
+            if ct:
+                sa, psa = _c(state[0])
+                sb, psb = _c(state[1])
+            else:
+                sa, psa = _c(state)
+        if stepped:
+            d, pd, e, pe, emitted = self._step_args(circuit, data, emit, steps, inst)
+        else:
+            (d, pd), pe, emitted = self._planes(circuit, data, inst), None, 1
+        pack = bool(pack or direct or lift)
+        calls = self.debug_circuit_script_calls(circuit, count, ct, steps, emit, pack, direct, lift) if count else []
+        if len(results) != len(calls):
+            raise ValueError("debug_circuit_script: %d scripted calls, %d result arrays" % (len(calls), len(results)))
+        flat = []
+        for i, ((rows, raw), res) in enumerate(zip(calls, results)):
+            res = np.ascontiguousarray(res, dtype=np.uint64)
+            if res.shape != (rows, 3, n + 1) + ((2,) if raw else ()):
+                raise ValueError("debug_circuit_script: call %d takes %s, got %s"
+                                 % (i, (rows, 3, n + 1) + ((2,) if raw else ()), res.shape))
+            flat.append(res.reshape(-1))
+        script = np.concatenate(flat) if flat else np.zeros(1, dtype=np.uint64)
+        total = sum(rows for rows, _ in calls)
+        staged = np.zeros((max(total, 1), 2, n + 1), dtype=np.uint64)
+        lut = np.zeros(max(total, 1), dtype=np.uint32)
+        n_ct = circuit.n_outputs * count
+        tail = np.zeros((emitted, n_ct, n, n + 1, 2), dtype=np.uint64) if pack else None
+        out = np.zeros(((emitted,) if stepped else ()) + (circuit.n_outputs, inst, n + 1), dtype=np.uint64)
+        st = np.zeros((circuit.n_regs, inst, n + 1), dtype=np.uint64) if stepped else None
+        if state_in_place:
+            if ct or state is None or sa is not state:
+                raise ValueError("debug_circuit_script: state_in_place takes the LWE form's state as a contiguous uint64 array")
+            st = sa
+        form = (SCRIPT_CT if ct else 0) | (SCRIPT_STEPPED if stepped else 0)
+        self._call("sgfhe_debug_circuit_script", circuit.handle(), form, count, steps or 0, psa, psb, pa, pb, N, pd, pe,
+                   _hptr(out), _hptr(st), _pack_flags(direct, lift) if ct else 0, _hptr(script), _hptr(staged), _hptr(lut),
+                   _hptr(tail))
+        cuts = np.cumsum([rows for rows, _ in calls])[:-1] if calls else []
+        return {"out": out, "state": st, "staged": np.split(staged[:total], cuts) if calls else [],
+                "lut": np.split(lut[:total], cuts) if calls else [], "tail_in": tail, "calls": calls}
 
     def debug_ntt(self, prime_index, poly, inverse=False):
         x, px = _c(poly, np.uint32)

@@ -7,6 +7,11 @@
 //     shows.  stdout: "entry case code message" per case, for the test to hold against the recorded fixture.
 //   - every case again with `device` flipped and with a stream: the same verdict.
 //   - a seeded sweep of accepted requests: the verdict's instances are count (LWE forms) or count * n (ct forms).
+//   - the scripted form (CircuitRequest::script, sgfhe_debug_circuit_script): every case again with a script -- the
+//     probe and device forms are refused as such, every other case has the verdict of the same request on a ctx with a
+//     key, since the key is the one thing a scripted run does not need -- and every request of the sweep without a
+//     key, with tail_in in place of out_w / out_v, with a NULL array of the script, and on a plan with a live LUT
+//     sibling; the refusals are printed as "script <case> code message".
 // Ends with "ok <cases> <sweep>".
 #include <stdio.h>
 #include <stdlib.h>
@@ -56,6 +61,8 @@ static Arrays named(const std::string &name) {
     } else if (name == "wide") {
         A.kind = {0, 0, 0}, A.table = {0, 0, 0}, A.start = {0, 2, 4, 6};
         A.ref = {0, 1, 0, 1 | CIRC_NOT, 0 | CIRC_NOT, 1}, A.outputs = {2, 5, 8};
+    } else if (name == "family") {   // a LUT node and a live sibling of it
+        A.kind = {2, 3}, A.table = {0x96, 0xE8}, A.start = {0, 3, 3}, A.ref = {CIRC_FALSE, CIRC_FALSE, 0}, A.outputs = {5};
     } else CHECK(name == "plain");
     A.shift.assign(A.ref.size(), 0), A.weight.assign(A.ref.size(), 1);
     return A;
@@ -118,6 +125,19 @@ int main() {
         CHECK(same(circuit_request_check(circ ? &P : nullptr, d, env), v));
         d = q, d.stream = dummy<void>(true, 15);
         CHECK(same(circuit_request_check(circ ? &P : nullptr, d, env), v));
+        // the scripted form: no probe, no device form; otherwise the verdict of a ctx that has a key
+        CircuitScript X;
+        X.results = dummy<const uint64_t>(true, 16), X.staged = dummy<uint64_t>(true, 17), X.lut = dummy<uint32_t>(true, 18);
+        d = q, d.script = &X;
+        const CircuitVerdict sv = circuit_request_check(circ ? &P : nullptr, d, env);
+        if (q.probe || q.device) {
+            CHECK(sv.what == CircuitVerdict::REFUSED && sv.code == SGFHE_ERR_INVALID_ARG);
+            CHECK(sv.message == "sgfhe_debug_circuit_script: the host forms only: no probe, no device form");
+        } else {
+            CircuitEnv keyed = env;
+            keyed.have_key = true;
+            CHECK(same(sv, circuit_request_check(circ ? &P : nullptr, q, keyed)));
+        }
         cases++;
     }
     // accepted requests: every form on every plan it admits, counts the limits and the lane group allow
@@ -141,7 +161,53 @@ int main() {
                 CHECK(v.what == CircuitVerdict::RUN && v.code == SGFHE_OK && v.message.empty());
                 CHECK(v.instances == (q.ct ? q.count * env.n : q.count));
                 sweep++;
+                // scripted: no key needed; tail_in stands for out_w / out_v; each array of the script is needed
+                CircuitScript X;
+                X.results = dummy<const uint64_t>(true, 16), X.staged = dummy<uint64_t>(true, 17), X.lut = dummy<uint32_t>(true, 18);
+                CircuitRequest s = q;
+                s.script = &X, s.device = false;
+                CircuitEnv bare = env;
+                bare.have_key = false;
+                CHECK(same(circuit_request_check(&P, s, bare), v));
+                if (q.ct) {
+                    s.out_w = s.out_v = nullptr;
+                    CHECK(same(circuit_request_check(&P, s, bare), v) && !s.packs());   // (the LWE outputs alone)
+                    s.out = nullptr;
+                    CHECK(circuit_request_check(&P, s, bare).what == CircuitVerdict::REFUSED);   // no output form
+                    X.tail_in = dummy<uint64_t>(true, 19);
+                    CHECK(same(circuit_request_check(&P, s, bare), v) && s.packs());
+                    bare.pack_exact = false;
+                    CHECK(circuit_request_check(&P, s, bare).code == SGFHE_ERR_UNSUPPORTED);
+                    bare.pack_exact = true;
+                }
+                for (int hole = 0; hole < 3; hole++) {
+                    CircuitScript Y = X;
+                    if (hole == 0) Y.results = nullptr;
+                    if (hole == 1) Y.staged = nullptr;
+                    if (hole == 2) Y.lut = nullptr;
+                    s.script = &Y;
+                    const CircuitVerdict h = circuit_request_check(&P, s, bare);
+                    CHECK(h.what == CircuitVerdict::REFUSED && h.code == SGFHE_ERR_INVALID_ARG);
+                    if (sweep == 1 && hole == 0) printf("script null_script %d %s\n", h.code, h.message.c_str());
+                }
             }
+    {   // a plan with a live LUT sibling: run by the entries, refused by the hook
+        CircuitPlan P;
+        named("family").plan(P);
+        CHECK(P.siblings() == 1);
+        CircuitRequest q;
+        q.with_data = true, q.count = 8;
+        set_pointers(q, 0x101ul);   // in out
+        CHECK(circuit_request_check(&P, q, env).what == CircuitVerdict::RUN);
+        CircuitScript X;
+        X.results = dummy<const uint64_t>(true, 16), X.staged = dummy<uint64_t>(true, 17), X.lut = dummy<uint32_t>(true, 18);
+        q.script = &X;
+        const CircuitVerdict h = circuit_request_check(&P, q, env);
+        CHECK(h.what == CircuitVerdict::REFUSED && h.code == SGFHE_ERR_INVALID_ARG);
+        printf("script live_sibling %d %s\n", h.code, h.message.c_str());
+        q.probe = true;
+        printf("script probe_form %d %s\n", circuit_request_check(&P, q, env).code, circuit_request_check(&P, q, env).message.c_str());
+    }
     printf("ok %zu %zu\n", cases, sweep);
     return 0;
 }

@@ -47,7 +47,8 @@ def _build(tmp_path, gxx, name, flags):
 
 def test_request_check_under_asan_and_ubsan(tmp_path):
     """Every case's code and message equal the fixture's; the pack bound; `device` and the stream change no verdict; a
-    seeded sweep of accepted requests returns count or count * n instances; the plain build prints the same."""
+    seeded sweep of accepted requests returns count or count * n instances; a request with a script is judged as on a ctx
+    with a key, but for the refusals of its own; the plain build prints the same."""
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("no g++")
@@ -77,6 +78,12 @@ def test_request_check_under_asan_and_ubsan(tmp_path):
         assert (got[(e, c.name)][0] == 0) == (c.expect == "empty"), (e, c.name)
     for e, c in bound:
         assert got[(e, c.name)] == list(PACK_BOUND), e
+    # the scripted form (sgfhe_debug_circuit_script): the refusals of its own, in the hook's name and saying why
+    assert got[("script", "null_script")] == [-1, "sgfhe_debug_circuit_script: NULL script: the calls' results, the staged log "
+                                              "and the descriptor log are needed"]
+    assert got[("script", "probe_form")] == [-1, "sgfhe_debug_circuit_script: the host forms only: no probe, no device form"]
+    code, why = got[("script", "live_sibling")]
+    assert code == -1 and why.startswith("sgfhe_debug_circuit_script: a plan with a live LUT sibling") and "inside the bootstrap call" in why
     exe2 = _build(tmp_path, gxx, "circuit_request_plain", ["-O2"])
     r2 = subprocess.run([exe2], input=text, capture_output=True, text=True, timeout=300)
     assert r2.returncode == 0 and r2.stdout == r.stdout

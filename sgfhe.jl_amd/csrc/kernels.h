@@ -405,7 +405,7 @@ k_extprod(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
           uint32_t n, uint32_t mode) {
     using G = NttGeom<LOGM, LE>;
     constexpr int M = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     int32_t *const z1 = reinterpret_cast<int32_t *>(lds) + M + threadIdx.x;  // z1[e * T]: private to the thread, conflict-free
 
     const int tid = threadIdx.x;
@@ -953,9 +953,13 @@ __device__ __forceinline__ uint32_t sub_borrow(uint32_t a, uint32_t b, uint32_t 
 // mulhi64_lean with its three multiply-adds in this order (left to itself the compiler reassociates
 // them into four instructions and a move).  m0 and m1 are wave-uniform (SGPRs).
 __device__ __forceinline__ uint64_t mad_u64_u32_vs(uint32_t a, uint32_t b, uint64_t c) {
+#ifdef SGFHE_HOST_KERNELS
+    return (uint64_t)a * b + c;
+#else
     uint64_t r, cy;
     asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(cy) : "v"(a), "s"(b), "v"(c));
     return r;
+#endif
 }
 __device__ __forceinline__ uint64_t mulhi64_87(uint64_t x, uint32_t m0, uint32_t m1) {
     const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32);
@@ -995,7 +999,7 @@ __device__ __forceinline__ void crt_lean87_one(const uint32_t (&y)[NP], uint64_t
     // (the multipliers 2^29 and 8 are hidden from the optimiser, which would otherwise turn these two
     // multiply-adds into 64-bit shifts, masks and adds)
     uint32_t m29 = 1u << 29, m3 = 8;
-    asm volatile("" : "+s"(m29), "+s"(m3));
+    SGFHE_HIDE("+s"(m29), "+s"(m3));
     const uint64_t U = (uint64_t)(uint32_t)L1 * m29 + L0;
     const uint64_t X = (uint64_t)(uint32_t)(L1 >> 32) * m3 + L2;
     // quotient by Q and q Q modulo 2^96
@@ -1060,7 +1064,7 @@ k_crt_lean(const uint32_t *__restrict__ yres, uint64_t *__restrict__ dig,
     Lean87W W{};
     if constexpr (P87) {
         W = Lean87W{K->Qw[0], K->Qw[1], K->Qw[2], K->Bw0, K->Bw1};
-        asm volatile("" : "+v"(W.Q0), "+v"(W.Q1), "+v"(W.Q2), "+v"(W.B0), "+v"(W.B1));
+        SGFHE_HIDE("+v"(W.Q0), "+v"(W.Q1), "+v"(W.Q2), "+v"(W.B0), "+v"(W.B1));
     }
     uint64_t nlo[4], nhi[4];
 #pragma unroll
@@ -1232,7 +1236,7 @@ k_fwd_phase(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk,
             int32_t *__restrict__ zpart, PrimeSet PS, uint32_t mode) {
     using G = NttGeom<LOGM, LE>;
     constexpr int M = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const uint32_t npr = PS[0].npr;
     const uint32_t ph = blockIdx.x & 3u;
@@ -1265,7 +1269,7 @@ k_inv_column(const int32_t *__restrict__ zpart, uint32_t *__restrict__ yres,
              const uint32_t *__restrict__ ua, PrimeSet PS, uint32_t k, uint32_t n) {
     using G = NttGeom<LOGM, LE>;
     constexpr int M = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const uint32_t npr = PS[0].npr;
     const uint32_t c = blockIdx.x & 1u;
@@ -1331,7 +1335,7 @@ k_fwd_quarter(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk
     constexpr int LS = LOGM - 2;
     using G = NttGeom<LS, LE>;
     constexpr int M = 1 << LOGM, MS = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const uint32_t npr = PS[0].npr;
     const uint32_t q = blockIdx.x & 3u, ph = (blockIdx.x >> 2) & 3u;
@@ -1358,7 +1362,7 @@ k_inv_quarter(const int32_t *__restrict__ zpart, int32_t *__restrict__ ypart,
     constexpr int LS = LOGM - 2;
     using G = NttGeom<LS, LE>;
     constexpr int M = 1 << LOGM, MS = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const uint32_t npr = PS[0].npr;
     const uint32_t q = blockIdx.x & 3u, c = (blockIdx.x >> 2) & 1u;
@@ -1402,7 +1406,7 @@ k_ext_quarter(const uint64_t *__restrict__ dig, const int32_t *__restrict__ keyk
     constexpr int LS = LOGM - 2;
     using G = NttGeom<LS, LE>;
     constexpr int M = 1 << LOGM, MS = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const uint32_t g = (uint32_t)threadIdx.x / (uint32_t)T;          // key rows 2 g, 2 g + 1; product column g
     const int tl = (int)((uint32_t)threadIdx.x & (uint32_t)(T - 1));
     const uint32_t npr = PS[0].npr;
@@ -2103,14 +2107,14 @@ __global__ void __launch_bounds__(256)
 k_circ_split(const uint64_t *__restrict__ ct_a, const uint64_t *__restrict__ ct_b,
              const uint32_t *__restrict__ in_slot, uint64_t *__restrict__ wires, uint32_t blocks, uint32_t N,
              uint32_t n, uint64_t r) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t split_ext[];
+    SGFHE_DYN_LDS(uint64_t, split_ext);
     const uint32_t tiles = (n + CIRC_SPLIT_ROWS - 1) / CIRC_SPLIT_ROWS;
     const uint32_t tile = blockIdx.x % tiles, q = blockIdx.x / tiles;   // q = input * blocks + block
     const uint32_t input = q / blocks, block = q % blocks;
     const uint32_t slot = in_slot[input];
     if (slot == CIRC_SLOT_NONE) return;   // nothing reads this input (uniform over the workgroup)
     const uint32_t i0 = tile * CIRC_SPLIT_ROWS;
-    const uint32_t rows = min(CIRC_SPLIT_ROWS, n - i0);
+    const uint32_t rows = n - i0 < CIRC_SPLIT_ROWS ? n - i0 : CIRC_SPLIT_ROWS;
     const uint64_t *a = ct_a + (size_t)q * N, *b = ct_b + (size_t)q * N;
     // split_ext[k] = ext[i0 - (n - 1) + k], k < n + rows - 1: d runs from i0 - n + 1 to i0 + rows - 1 <= n - 1 < N
     for (uint32_t k = threadIdx.x; k < n + rows - 1; k += 256) {
@@ -2417,7 +2421,7 @@ k_shortprod(const uint64_t *__restrict__ pdig, const int32_t *__restrict__ keyha
             uint32_t G, uint32_t groups, uint32_t mode) {
     using GE = NttGeom<LOGM, LOGE>;
     constexpr int M = GE::M, T = GE::T, E = GE::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     int32_t *const ldsi = reinterpret_cast<int32_t *>(lds);
     const uint32_t npr = PS[0].npr;
     const uint32_t pi = blockIdx.x % npr;
@@ -2594,7 +2598,7 @@ __global__ void __launch_bounds__((NttGeom<LOGM, LOGE>::T))
 k_shat(const uint64_t *__restrict__ sk, int32_t *__restrict__ shat, PrimeSet PS, uint32_t n) {
     using G = NttGeom<LOGM, LOGE>;
     constexpr int M = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const uint32_t pi = blockIdx.x;
     const PrimeK P = PS[pi];
@@ -2623,7 +2627,7 @@ k_polymul_s(const ulonglong2 *__restrict__ acan, const int32_t *__restrict__ sha
             uint32_t *__restrict__ y, PrimeSet PS, const CrtConst *__restrict__ CC) {
     using G = NttGeom<LOGM, LOGE>;
     constexpr int M = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const uint32_t npr = PS[0].npr;
     const uint32_t r = blockIdx.x / npr, pi = blockIdx.x % npr;
@@ -2686,7 +2690,7 @@ k_key_transform(const ulonglong2 *__restrict__ canon, int32_t *__restrict__ keyh
                 const CrtConst *__restrict__ CC, uint32_t poly0, uint32_t *__restrict__ bad) {
     using G = NttGeom<LOGM, LOGE>;
     constexpr int M = G::M, T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const uint32_t npr = PS[0].npr;
     const uint32_t pl = blockIdx.x / npr;  // polynomial within this staging batch
@@ -2775,7 +2779,7 @@ k_debug_ntt(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, PrimeSe
             uint32_t inverse) {
     using G = NttGeom<LOGM, LOGE>;
     constexpr int T = G::T, E = G::E;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    SGFHE_DYN_LDS(uint32_t, lds);
     const int tid = threadIdx.x;
     const PrimeK P = PS[pi];
     const Mod md = mod_of(P);

@@ -72,13 +72,13 @@ struct NttGeom {
 // further: hoisting all ~46 loads of an NTT to its top costs that many registers.
 __device__ __forceinline__ uint32_t opaque_zero() {
     uint32_t z = 0;
-    asm volatile("" : "+v"(z));
+    SGFHE_HIDE("+v"(z));
     return z;
 }
 // The same in a scalar register, for addresses that are uniform over the wavefront.
 __device__ __forceinline__ uint32_t opaque_zero_s() {
     uint32_t z = 0;
-    asm volatile("" : "+s"(z));
+    SGFHE_HIDE("+s"(z));
     return z;
 }
 

@@ -22,6 +22,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The kernels also compile for the host against the HIP stand-in of tests/native/hipcpu, which
+// defines SGFHE_HOST_KERNELS.  Two spellings differ there: the dynamic-LDS array of a kernel is the block the launch
+// allocated, and the empty asm statements that hide a value from the optimiser are dropped.
+#ifdef SGFHE_HOST_KERNELS
+#define SGFHE_DYN_LDS(T, name) T *const name = static_cast<T *>(hipcpu::dynamic_lds())
+#define SGFHE_HIDE(...) ((void)0)
+#else
+#define SGFHE_DYN_LDS(T, name) extern __shared__ __attribute__((aligned(16))) T name[]
+#define SGFHE_HIDE(...) asm volatile("" : __VA_ARGS__)
+#endif
+
 namespace sgfhe {
 
 // Modulus record kept in registers by the NTT code.

@@ -764,6 +764,35 @@ int32_t sgfhe_host_normalize_public(const sgfhe_params *p, const uint8_t *a_bits
  * SGFHE_CIRCUIT_PACK_LIFT, as an output with a non-zero shift is -- even where its table is the identity.  The probe
  * applies the routes in its plaintext bit table; its launches are unchanged.  A route moves whole LWEs and adds no
  * error: no noise rule is added.
+ *
+ * Lane masks (sgfhe_circuit_create_masked): a node bootstraps only the lanes that are read.  The creator takes the
+ * arrays of sgfhe_circuit_create_routed and
+ *   n_masks   : mask tables, at most SGFHE_CIRCUIT_MAX_MASKS; a table may be used by several nodes or by none;
+ *   masks     : [n_masks][group] uint8, each entry 0 or 1, every table with at least one lane set;
+ *   node_mask : [n_gates], NULL = all 0.
+ * A mask index 0 means every lane -- the node as before -- and k >= 1 names table k - 1.  A masked node takes a row
+ * only at the instances t whose lane t mod group is set.  On the lanes that are off EVERY wire of the node is the
+ * constant FALSE -- AND / OR / XOR, HI / MID / LOW, the three scales of a LUT node all read as the trivial LWE (0, 0),
+ * all n + 1 words zero -- wherever it is read: by a term, an output, a next state, the lift, the collected LWEs.  NOT
+ * on such a reference gives TRUE at the codeword of the reading position, exactly as for a shift that leaves its
+ * group.  Numbering, pruning, liveness, levels, slots and sgfhe_circuit_info do not see masks, and with n_masks = 0 the
+ * plan is the sgfhe_circuit_create_routed plan of the same arrays.
+ * Rows of a masked plan (n_masks > 0; a plan without masks keeps row = rank * instances + instance and every byte, call
+ * and call number it has): every level is a list of (node, lane) PAIRS, nodes ascending in the level's order, lanes
+ * ascending, an unmasked node contributing all `group` lanes; with per = instances / group, row R of the level is pair
+ * R / per at group R mod per, that is instance (R mod per) * group + lane.  Levels are cut into calls of
+ * SGFHE_CIRCUIT_CALL_ROWS rows from row 0 as before, and a row draws at its index within its call.
+ * SGFHE_ERR_INVALID_ARG with *out NULL and nothing allocated for: an entry other than 0 or 1, a table with no lane set,
+ * a mask index above n_masks, n_masks > 0 with masks NULL, n_masks above the cap, a mask on a sibling (kinds 3 and 5),
+ * and everything sgfhe_circuit_create_routed rejects; and, with *out NULL and nothing kept, for a masked LUT node that
+ * leads a LIVE sibling (the sibling's wires are written inside the bootstrap call, which knows no off lanes).
+ * sgfhe_circuit_masks gives n_masks and rows_per_group, the level-call rows one group of `group` instances costs: the
+ * sum over the live row-taking nodes of the lanes set (0 and bootstraps * group for a plan of any other creator).
+ * A masked plan runs through every run entry that takes its planes, registers and routes, the device-resident forms
+ * and sgfhe_debug_circuit_script[_calls] included.  The probe entries refuse it with SGFHE_ERR_UNSUPPORTED and a
+ * message, before anything is queued or a call number is taken.  In the ciphertext form an output that names a wire of
+ * a masked node is REFRESHED, or LIFTED under SGFHE_CIRCUIT_PACK_LIFT, never direct; outputs of unmasked nodes of the
+ * same plan stay direct.  An off lane is the exact trivial LWE and carries no error: no noise rule is added.
  */
 typedef struct sgfhe_circuit sgfhe_circuit;
 #define SGFHE_CIRCUIT_FALSE 0x7FFFFFFFu
@@ -847,6 +876,26 @@ int32_t sgfhe_circuit_create_routed(uint32_t n_inputs, uint32_t n_planes,
                                     const uint32_t *out_route /* [n_outputs], NULL = all 0 */,
                                     const uint32_t *next_route /* [n_regs], NULL = all 0 */, sgfhe_circuit **out);
 int32_t sgfhe_circuit_routes(const sgfhe_circuit *c, uint32_t *n_routes);   /* 0 for every other creator */
+#define SGFHE_CIRCUIT_MAX_MASKS 65536u
+int32_t sgfhe_circuit_create_masked(uint32_t n_inputs, uint32_t n_planes,
+                                    const uint32_t *node_kind /* [n_gates]: 0 .. 5 as sgfhe_circuit_create_data */,
+                                    const uint32_t *node_start /* [n_gates + 1], CSR into the term arrays, [0] = 0 */,
+                                    const uint32_t *term_ref, const int32_t *term_shift /* NULL = all 0 */,
+                                    const int32_t *term_weight,
+                                    const uint32_t *node_table /* [n_gates]: a table for kinds 2 and 3, a plane for 4 and 5 */,
+                                    size_t n_gates, const uint32_t *outputs,
+                                    const int32_t *out_shift /* [n_outputs], NULL = all 0 */, size_t n_outputs,
+                                    uint32_t group, uint32_t n_regs, const uint32_t *next_ref /* [n_regs] */,
+                                    const int32_t *next_shift /* [n_regs], NULL = all 0 */,
+                                    const uint32_t *reg_scale /* [n_regs]: 0, 1, 2; NULL = all 0 */,
+                                    uint32_t n_routes, const int32_t *routes /* [n_routes][group] */,
+                                    const uint32_t *term_route /* beside term_shift, NULL = all 0 */,
+                                    const uint32_t *out_route /* [n_outputs], NULL = all 0 */,
+                                    const uint32_t *next_route /* [n_regs], NULL = all 0 */,
+                                    uint32_t n_masks, const uint8_t *masks /* [n_masks][group], 0 or 1 */,
+                                    const uint32_t *node_mask /* [n_gates], NULL = all 0 */, sgfhe_circuit **out);
+/* n_masks: 0 for every other creator; rows_per_group: level-call rows per group of `group` instances */
+int32_t sgfhe_circuit_masks(const sgfhe_circuit *c, uint32_t *n_masks, uint64_t *rows_per_group);
 int32_t sgfhe_circuit_group(const sgfhe_circuit *c, uint32_t *group);   /* 1 for sgfhe_circuit_create plans */
 int32_t sgfhe_circuit_info(const sgfhe_circuit *c, uint64_t info[4]);
 int32_t sgfhe_circuit_destroy(sgfhe_circuit *c);

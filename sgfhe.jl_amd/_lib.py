@@ -173,6 +173,9 @@ def lib():
         "sgfhe_circuit_create_routed": (i32, [u32, u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, u32, vp, vp, vp,
                                               u32, vp, vp, vp, vp, ctypes.POINTER(vp)]),
         "sgfhe_circuit_routes": (i32, [vp, _u32p]),
+        "sgfhe_circuit_create_masked": (i32, [u32, u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz, u32, u32, vp, vp, vp,
+                                              u32, vp, vp, vp, vp, u32, vp, vp, ctypes.POINTER(vp)]),
+        "sgfhe_circuit_masks": (i32, [vp, _u32p, _u64p]),
         "sgfhe_circuit_run_device": (i32, [vp, vp, sz, vp, vp, vp, vp]),
         "sgfhe_circuit_run_ct_device": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, vp]),
         "sgfhe_circuit_run_steps_device": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]),
@@ -211,4 +214,4 @@ EXPORTED_SYMBOLS = (
     "sgfhe_circuit_create_seq", "sgfhe_circuit_registers", "sgfhe_circuit_run_steps", "sgfhe_circuit_run_steps_ct",
     "sgfhe_circuit_create_routed", "sgfhe_circuit_routes", "sgfhe_circuit_run_device", "sgfhe_circuit_run_ct_device",
     "sgfhe_circuit_run_steps_device", "sgfhe_circuit_run_steps_ct_device", "sgfhe_debug_circuit_script",
-    "sgfhe_debug_circuit_script_calls")
+    "sgfhe_debug_circuit_script_calls", "sgfhe_circuit_create_masked", "sgfhe_circuit_masks")

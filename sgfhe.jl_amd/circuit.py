@@ -64,6 +64,14 @@ draw: Circuit.rot (rotation inside a word), Circuit.swap (partner t ^ k), Circui
 Circuit.reverse.  Routes compose with each other and with lane shifts and are normalised, so the identity is nothing
 and a pure shift is the shift.  Terms, outputs and next states may be routed; a routed output is refreshed or lifted,
 never direct.  bitonic_sort(width, G) sorts the G numbers of every group with routes alone between its nodes.
+
+Lane masks (sgfhe_circuit_create_masked).  `lanes=` on gate / gate3 / sum_node / xor / refresh / lut / lut_data / fan /
+full_adder makes the node bootstrap only the lanes named -- an iterable of lane indices or a 0/1 sequence of length G.
+On the other lanes every wire of the node is the constant FALSE (TRUE under `~`), wherever it is read, and the node takes
+no row there: a run's cost is its rows, `Circuit.info()["rows_per_group"]`.  All lanes is no mask at all.  lane_reduce
+folds a wire over the lanes of a word in G - 1 rows a group, packed_equal(width) compares two packed words in
+2 width - 1, and bitonic_sort(width, G, masked=True) evaluates every comparator chain at its decision lanes only.  An
+output naming a masked node's wire is refreshed or lifted, never direct; a LUT node that leads siblings takes no mask.
 """
 
 import ctypes
@@ -79,6 +87,7 @@ NOT_BIT = 0x80000000       # SGFHE_CIRCUIT_NOT
 MAX_TERMS = 64             # SGFHE_CIRCUIT_MAX_TERMS
 MAX_PLANES = 65536         # SGFHE_CIRCUIT_MAX_PLANES
 MAX_ROUTES = 65536         # SGFHE_CIRCUIT_MAX_ROUTES
+MAX_MASKS = 65536          # SGFHE_CIRCUIT_MAX_MASKS
 ROUTE_FALSE = -1           # SGFHE_CIRCUIT_ROUTE_FALSE: entry of a route table, the constant FALSE at that lane
 LUT_MAX_TABLES = 256       # SGFHE_LUT_MAX_TABLES
 CALL_ROWS = 8192           # SGFHE_CIRCUIT_CALL_ROWS
@@ -186,8 +195,9 @@ class Circuit:
     the group is above 1, sgfhe_circuit_create3 when a gate3 exists, sgfhe_circuit_create_w when a sum node exists that
     is no three-input node, sgfhe_circuit_create_lut when a LUT node exists, sgfhe_circuit_create_lut_multi when a LUT
     sibling exists, sgfhe_circuit_create_data when the circuit has planes, sgfhe_circuit_create_seq when it has
-    registers, sgfhe_circuit_create_routed when a reference carries a lane route that normalisation leaves a route) is
-    made on first use and freed with the object.
+    registers, sgfhe_circuit_create_routed when a reference carries a lane route that normalisation leaves a route,
+    sgfhe_circuit_create_masked when a node carries a lane mask that normalisation leaves a mask) is made on first use
+    and freed with the object.
     `planes`: the number of data planes a run brings (lut_data, Circuit.plane), uint8 [planes][instances].
     `registers`: the first `registers` inputs are registers (`c.registers`), fed back by a stepped run from the wires
     given to next_state; the others are the stream inputs (`c.stream_inputs`).  `reg_scales`: the scale of every
@@ -228,6 +238,7 @@ class Circuit:
         self.gate_leader = {}      # sibling -> its leader, a LUT node: no inputs of its own, () in gates and gate_shifts
         self.gate_planes = {}      # data LUT node or data sibling -> its plane (its entry of gate_tables is None)
         self.output_shifts = []    # [lane shift], beside outputs
+        self.gate_masks = {}       # node -> its lane mask, a tuple of `group` entries 0 / 1 (never all 1: that is no mask)
         self._plan = None
         self._L = None
 
@@ -252,31 +263,72 @@ class Circuit:
             raise ValueError("%r has scale %d where scale %d is read (Circuit.lut, Circuit.fan)" % (w, self.scale(w), scale))
         return w.ref
 
-    def gate(self, x, y):
-        """One node: bootstrap(x, y).  Returns its (AND, OR, XOR) wires."""
+    def _lanes(self, lanes):
+        """`lanes=` of a node in its normal form: None for no mask (None, or every lane), else a tuple of `group` entries
+        0 / 1.  lanes: an iterable of lane indices, or a 0/1 sequence of length `group` (a sequence of length `group`
+        whose entries are all 0 or 1 is read as 0/1 flags; in a group of 1 or 2 lanes write the flags)."""
+        if lanes is None:
+            return None
+        lanes = [int(l) for l in lanes]
+        G = self.group
+        if G == 1:
+            raise ValueError("lanes=: a circuit without lane groups (group 1) takes no lane mask")
+        if len(lanes) == G and all(l in (0, 1) for l in lanes):
+            mask = tuple(lanes)
+        else:
+            if any(not 0 <= l < G for l in lanes):
+                raise ValueError("lanes=: a lane is 0 .. %d: %r" % (G - 1, lanes))
+            mask = tuple(1 if t in set(lanes) else 0 for t in range(G))
+        if not any(mask):
+            raise ValueError("lanes=: a node must take a row on at least one lane")
+        return None if all(mask) else mask
+
+    @property
+    def mask_tables(self):
+        """The distinct lane masks of the circuit's nodes, in order of first use."""
+        seen = {}
+        for g in sorted(self.gate_masks):
+            seen.setdefault(self.gate_masks[g], len(seen))
+        return list(seen)
+
+    def lanes_on(self, g):
+        """The lanes node g takes a row on, ascending (all of them without a mask)."""
+        m = self.gate_masks.get(g)
+        return list(range(self.group)) if m is None else [t for t in range(self.group) if m[t]]
+
+    def gate(self, x, y, lanes=None):
+        """One node: bootstrap(x, y).  Returns its (AND, OR, XOR) wires.  lanes: the lanes the node bootstraps (all);
+        its wires are FALSE on the others (the module's text on lane masks)."""
+        mask = self._lanes(lanes)
         self.gates.append((self._ref(x), self._ref(y)))
         self.gate_shifts.append((x.lanes, y.lanes))
+        if mask is not None:
+            self.gate_masks[len(self.gates) - 1] = mask
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
 
-    def gate3(self, x, y, z):
+    def gate3(self, x, y, z, lanes=None):
         """One three-input node: bootstrap(x + y, z).  Returns its (MAJ, ONE_OR_TWO, XOR3) wires: the majority, "one
         or two of the inputs true" (not all equal), and the parity x + y + z - 2 MAJ over Z_r, which is linear and
-        carries the errors of x, y and z on."""
+        carries the errors of x, y and z on.  lanes: as in gate."""
+        mask = self._lanes(lanes)
         self.gates.append((self._ref(x), self._ref(y), self._ref(z)))
         self.gate_shifts.append((x.lanes, y.lanes, z.lanes))
+        if mask is not None:
+            self.gate_masks[len(self.gates) - 1] = mask
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
 
-    def sum_node(self, terms):
+    def sum_node(self, terms, lanes=None):
         """One weighted-sum node: ONE bootstrap on U = the sum of weight * wire over Z_r.  terms: [(weight, wire), ...],
         1 to 64 of them, weight in {-2, -1, 1, 2}; TRUE with weight c adds the constant c Dr.  Returns its (HI, MID, LOW)
         wires: with s = the sum of weight * bit mod 4, HI is s in {2, 3} (the AND row), MID is s in {1, 2} (the OR row)
         and LOW is s mod 2 = U - 2 HI over Z_r, which is linear and carries the error of the sum on.  Weights (1, 1, 1)
-        are gate3."""
+        are gate3.  lanes: as in gate."""
         terms = list(terms)
+        mask = self._lanes(lanes)
         if not 1 <= len(terms) <= MAX_TERMS:
             raise ValueError("a sum node has 1 to %d terms" % MAX_TERMS)
         if any(int(w) not in (-2, -1, 1, 2) for w, _ in terms):
@@ -284,19 +336,25 @@ class Circuit:
         self.gates.append(tuple(self._ref(x) for _, x in terms))
         self.gate_shifts.append(tuple(x.lanes for _, x in terms))
         self.gate_weights[len(self.gates) - 1] = tuple(int(w) for w, _ in terms)
+        if mask is not None:
+            self.gate_masks[len(self.gates) - 1] = mask
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
 
-    def lut(self, table, x0, x1, x2):
+    def lut(self, table, x0, x1, x2, lanes=None):
         """One LUT node: ONE bootstrap for any function of three bits.  Bit s of `table` (0 .. 255) is the value at
         s = x0 + 2 x1 + 4 x2.  x0 must be a wire of scale 2 (codeword Dr/4), x1 of scale 1, x2 of scale 0, or the
-        constants.  Returns (f, f_half, f_quarter): the result at scales 0, 1 and 2."""
+        constants.  Returns (f, f_half, f_quarter): the result at scales 0, 1 and 2.  lanes: as in gate (FALSE at all three
+        scales on the other lanes); not for the leader of lut_multi."""
         if not 0 <= int(table) < 256:
             raise ValueError("a LUT node's table has 8 entries: 0 .. 255")
+        mask = self._lanes(lanes)
         self.gates.append((self._ref(x0, 2), self._ref(x1, 1), self._ref(x2, 0)))
         self.gate_shifts.append((x0.lanes, x1.lanes, x2.lanes))
         self.gate_tables[len(self.gates) - 1] = int(table)
+        if mask is not None:
+            self.gate_masks[len(self.gates) - 1] = mask
         self._invalidate()
         base = self.n_inputs + 3 * (len(self.gates) - 1)
         return Wire(base), Wire(base + 1), Wire(base + 2)
@@ -311,12 +369,12 @@ class Circuit:
             raise ValueError("plane %r is not below the circuit's %d planes (Circuit(planes=...))" % (p, self.planes))
         return int(p)
 
-    def lut_data(self, plane, x0, x1, x2):
+    def lut_data(self, plane, x0, x1, x2, lanes=None):
         """One DATA LUT node: lut(table, x0, x1, x2) whose table at instance t is the byte data[plane][t] of the run's
         data (evaluate_circuit(..., data=...)), read at the node's own instance whatever lane shifts its inputs carry.
-        Scales, wires and cost are those of lut."""
+        Scales, wires, cost and lanes are those of lut."""
         plane = self._plane(plane)
-        out = self.lut(0, x0, x1, x2)
+        out = self.lut(0, x0, x1, x2, lanes=lanes)
         self.gate_tables[len(self.gates) - 1] = None
         self.gate_planes[len(self.gates) - 1] = plane
         return out
@@ -375,9 +433,9 @@ class Circuit:
     def has_sibling(self):
         return bool(self.gate_leader)
 
-    def fan(self, x):
-        """A scale-0 wire at all three scales in one bootstrap: lut(0xF0, FALSE, FALSE, x)."""
-        return self.lut(0xF0, Circuit.FALSE, Circuit.FALSE, x)
+    def fan(self, x, lanes=None):
+        """A scale-0 wire at all three scales in one bootstrap: lut(0xF0, FALSE, FALSE, x).  lanes: as in gate."""
+        return self.lut(0xF0, Circuit.FALSE, Circuit.FALSE, x, lanes=lanes)
 
     @property
     def has_lut(self):
@@ -413,17 +471,17 @@ class Circuit:
                 seen.setdefault(d, len(seen))
         return list(seen)
 
-    def xor(self, *wires):
+    def xor(self, *wires, lanes=None):
         """The XOR of any number of wires (up to 64) in ONE bootstrap: HI of the sum node with every weight 2.  The
         wires should be bootstrapped ones (gate rows, refreshed wires): the node doubles their errors.  No wire at
-        all is the constant FALSE."""
+        all is the constant FALSE.  lanes: as in gate."""
         if not wires:
             return Circuit.FALSE
-        return self.sum_node([(2, w) for w in wires])[0]
+        return self.sum_node([(2, w) for w in wires], lanes=lanes)[0]
 
-    def refresh(self, w):
-        """A bootstrapped copy of `w`: MID of the sum node with the one term (1, w)."""
-        return self.sum_node([(1, w)])[1]
+    def refresh(self, w, lanes=None):
+        """A bootstrapped copy of `w`: MID of the sum node with the one term (1, w).  lanes: as in gate."""
+        return self.sum_node([(1, w)], lanes=lanes)[1]
 
     def kind(self, g):
         """Node g: "classic" (gate), "gate3", "sum" (sum_node), "lut" or "sibling" (a further table of a LUT node,
@@ -446,9 +504,9 @@ class Circuit:
     def has_wsum(self):
         return any(self._wide(g) for g in self.gate_weights)
 
-    def full_adder(self, x, y, c):
-        """x + y + c in one bootstrap: returns (sum, carry) = (XOR3, MAJ) of gate3(x, y, c)."""
-        maj, _, xor3 = self.gate3(x, y, c)
+    def full_adder(self, x, y, c, lanes=None):
+        """x + y + c in one bootstrap: returns (sum, carry) = (XOR3, MAJ) of gate3(x, y, c).  lanes: as in gate."""
+        maj, _, xor3 = self.gate3(x, y, c, lanes=lanes)
         return xor3, maj
 
     @property
@@ -480,6 +538,7 @@ class Circuit:
         c.gates, c.gate_shifts = list(self.gates), list(self.gate_shifts)
         c.gate_weights, c.gate_tables = dict(self.gate_weights), dict(self.gate_tables)
         c.gate_leader, c.gate_planes = dict(self.gate_leader), dict(self.gate_planes)
+        c.gate_masks = dict(self.gate_masks)
         c.outputs = list(self.outputs) + list(self.next_refs)
         c.output_shifts = list(self.output_shifts) + list(self.next_shifts)
         return c
@@ -510,8 +569,10 @@ class Circuit:
             shifts = lambda ds: arr([0 if isinstance(d, tuple) else d for d in ds], np.int32)   # (a routed reference: 0)
             route_of = lambda ds: arr([index.get(d, 0) for d in ds], np.uint32)
             # The entry: the first whose feature the circuit has, so every circuit keeps the creator it always took
+            masks = self.mask_tables
+            mask_index = {m: k + 1 for k, m in enumerate(masks)}   # mask index: 0 every lane, k = table k - 1
             entry = next(name for name, has in (
-                ("_routed", routes), ("_seq", self.n_regs), ("_data", self.planes),
+                ("_masked", masks), ("_routed", routes), ("_seq", self.n_regs), ("_data", self.planes),
                 ("_lut_multi", self.has_lut and self.has_sibling), ("_lut", self.has_lut), ("_w", self.has_wsum),
                 ("3", self.has_gate3 or self.gate_weights),
                 ("_lanes", self.group > 1 or any(d for x in self.gate_shifts for d in x) or any(self.output_shifts)),
@@ -543,28 +604,46 @@ class Circuit:
                 nr, ns, rs = arr(self.next_refs, np.uint32), shifts(self.next_shifts), arr(self.reg_scales, np.uint32)
                 rt = arr(routes, np.int32).reshape(len(routes), self.group)
                 tt, ot, nt = route_of(terms), route_of(self.output_shifts), route_of(self.next_shifts)
-                data = entry in ("_data", "_seq", "_routed")
+                data = entry in ("_data", "_seq", "_routed", "_masked")
+                mt = arr(masks, np.uint8).reshape(len(masks), self.group)
+                nm = arr([mask_index.get(self.gate_masks.get(g), 0) for g in range(n)], np.uint32)
                 args = ((self.n_inputs,) + ((self.planes,) if data else ()) + (vp(kind), vp(start), vp(tr), vp(ts), vp(tw)) +
                         ((vp(tb),) if entry != "_w" else ()) + (n,) + outs +
-                        ((self.n_regs, vp(nr), vp(ns), vp(rs)) if entry in ("_seq", "_routed") else ()) +
-                        ((len(routes), vp(rt), vp(tt), vp(ot), vp(nt)) if entry == "_routed" else ()))
+                        ((self.n_regs, vp(nr), vp(ns), vp(rs)) if entry in ("_seq", "_routed", "_masked") else ()) +
+                        ((len(routes), vp(rt), vp(tt), vp(ot), vp(nt)) if entry in ("_routed", "_masked") else ()) +
+                        ((len(masks), vp(mt), vp(nm)) if entry == "_masked" else ()))
             h = ctypes.c_void_p()
             rc = getattr(L, "sgfhe_circuit_create" + entry)(*args, ctypes.byref(h))
             if rc != 0:
                 raise SgfheError(rc, "sgfhe_circuit_create: %s" % (
-                    "malformed circuit (ids, topological order, at least one output, lane shifts inside the group)"
+                    "malformed circuit (ids, topological order, at least one output, lane shifts inside the group, no "
+                    "lane mask on a LUT node that leads a live sibling)"
                     if rc == -1 else "out of memory"))
             self._L, self._plan = L, h
         return self._plan
 
     def info(self):
         """dict(levels, nodes (bootstraps per instance: the live nodes that take a row, so no LUT sibling), widest (such
-        nodes in the widest level), slots (those of sibling wires included))."""
+        nodes in the widest level), slots (those of sibling wires included)) -- none of which sees lane masks -- and, for
+        a circuit with lane masks, rows_per_group (Circuit.rows_per_group; without masks it is nodes * group, and the
+        dict stays the four entries it always was)."""
         info = (ctypes.c_uint64 * 4)()
         h = self.handle()
         rc = self._L.sgfhe_circuit_info(h, info)
         assert rc == 0
-        return dict(levels=int(info[0]), nodes=int(info[1]), widest=int(info[2]), slots=int(info[3]))
+        out = dict(levels=int(info[0]), nodes=int(info[1]), widest=int(info[2]), slots=int(info[3]))
+        if self.gate_masks:
+            out["rows_per_group"] = self.rows_per_group()
+        return out
+
+    def rows_per_group(self):
+        """The level-call rows one group of `group` instances costs (sgfhe_circuit_masks): the lanes a node takes a row
+        on, summed over the live nodes that take a row -- nodes * group for a circuit without lane masks."""
+        n_masks, rows = ctypes.c_uint32(), ctypes.c_uint64()
+        h = self.handle()
+        rc = self._L.sgfhe_circuit_masks(h, ctypes.byref(n_masks), ctypes.byref(rows))
+        assert rc == 0
+        return int(rows.value)
 
     def __del__(self):
         try:
@@ -630,34 +709,43 @@ class Circuit:
             v = lane_shift(v, d, self.group)
             return ~v if ref & NOT_BIT else v
 
+        if self.gate_masks and inst % self.group:
+            raise ValueError("the instances (%d) must be a multiple of the lane group (%d)" % (inst, self.group))
+        on = {g: np.asarray(m, dtype=bool)[np.arange(inst) % self.group] for g, m in self.gate_masks.items()}
         for levelnodes in self.schedule():
             for g in levelnodes:
                 base = self.n_inputs + 3 * g
-                if g in self.gate_tables:
-                    x = [val(ref, d).astype(np.int64) for ref, d in zip(self.gates[g], self.gate_shifts[g])]
-                    for h in [g] + self.siblings(g):   # (a sibling: its own table at the leader's inputs)
-                        f = ((self.node_tables(h, inst, data).astype(np.int64) >> (x[0] + 2 * x[1] + 4 * x[2])) & 1).astype(bool)
-                        hb = self.n_inputs + 3 * h
-                        wires[hb], wires[hb + 1], wires[hb + 2] = f, f, f
-                    continue
-                if g in self.gate_weights:
-                    s = sum(w * val(ref, d).astype(np.int64)
-                            for w, ref, d in zip(self.gate_weights[g], self.gates[g], self.gate_shifts[g])) % 4
-                    wires[base], wires[base + 1], wires[base + 2] = s >= 2, (s == 1) | (s == 2), s % 2 == 1
-                    continue
-                if len(self.gates[g]) == 3:
-                    x, y, z = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
-                    wires[base], wires[base + 1], wires[base + 2] = (x & y) | (z & (x | y)), (x | y | z) & ~(x & y & z), \
-                        x ^ y ^ z
-                    continue
-                x, y = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
-                wires[base], wires[base + 1], wires[base + 2] = x & y, x | y, x ^ y
+                self._plain_node(g, base, val, wires, inst, data)
+                for w in range(3 if g in on else 0):   # a masked node (it leads no sibling): FALSE on its off lanes
+                    wires[base + w] = wires[base + w] & on[g]
         if not self.outputs:
             raise ValueError("circuit has no outputs")
         out = np.stack([val(ref, d) for ref, d in zip(self.outputs, self.output_shifts)])
         if not _next:
             return out
         return out, np.array([val(ref, d) for ref, d in zip(self.next_refs, self.next_shifts)], dtype=bool).reshape(self.n_regs, inst)
+
+    def _plain_node(self, g, base, val, wires, inst, data):
+        """The three wires of node g (and of its siblings) in clear, into `wires`: evaluate_plain's step for one node."""
+        if g in self.gate_tables:
+            x = [val(ref, d).astype(np.int64) for ref, d in zip(self.gates[g], self.gate_shifts[g])]
+            for h in [g] + self.siblings(g):   # (a sibling: its own table at the leader's inputs)
+                f = ((self.node_tables(h, inst, data).astype(np.int64) >> (x[0] + 2 * x[1] + 4 * x[2])) & 1).astype(bool)
+                hb = self.n_inputs + 3 * h
+                wires[hb], wires[hb + 1], wires[hb + 2] = f, f, f
+            return
+        if g in self.gate_weights:
+            s = sum(w * val(ref, d).astype(np.int64)
+                    for w, ref, d in zip(self.gate_weights[g], self.gates[g], self.gate_shifts[g])) % 4
+            wires[base], wires[base + 1], wires[base + 2] = s >= 2, (s == 1) | (s == 2), s % 2 == 1
+            return
+        if len(self.gates[g]) == 3:
+            x, y, z = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
+            wires[base], wires[base + 1], wires[base + 2] = (x & y) | (z & (x | y)), (x | y | z) & ~(x & y & z), \
+                x ^ y ^ z
+            return
+        x, y = (val(ref, d) for ref, d in zip(self.gates[g], self.gate_shifts[g]))
+        wires[base], wires[base + 1], wires[base + 2] = x & y, x | y, x ^ y
 
     def evaluate_plain_steps(self, state_bits, stream_bits, data=None):
         """A stepped run in clear: state_bits [registers][instances] (None: all FALSE), stream_bits
@@ -872,7 +960,7 @@ def bitonic_stages(G):
     return stages
 
 
-def bitonic_sort(width, G, refresh_inputs=True):
+def bitonic_sort(width, G, refresh_inputs=True, masked=False):
     """Sorts the G numbers of `width` bits of every lane group ascending: Circuit(width, group=G), bit-sliced -- input
     wire i holds bit i (LSB first) of every number, lane = element -- and outputs laid out the same way, lane 0 the
     smallest.  The bitonic network's log2(G) (log2(G) + 1) / 2 stages (bitonic_stages), each one compare-exchange at a
@@ -888,6 +976,9 @@ def bitonic_sort(width, G, refresh_inputs=True):
     refreshed first (Circuit.refresh, one bootstrap each), as it must be when the inputs are fresh encryptions -- the fan
     is a LUT node, and a split encrypt_private bit is already at the limit of its rule; False for inputs that are gate
     rows or packed outputs.
+    masked=True: the comparator chain carries lanes=sorted(set(table)), the decision lanes of the stage -- G / 2 of them,
+    the only lanes of g the swap decision reads, and the chain reads its own carry at those lanes only -- so a stage costs
+    width G / 2 + width G rows a group in place of 2 width G: bitonic_sort(3, 8) 264 rows a group in place of 336.
     Nodes: width refreshes and width fans, then 2 width per stage -- 2 width + width log2(G) (log2(G) + 1); levels:
     2 + (width + 1) per stage (one node and one level less per bit without the refreshes)."""
     width, G = int(width), int(G)
@@ -897,12 +988,41 @@ def bitonic_sort(width, G, refresh_inputs=True):
     c = Circuit(width, group=G)
     x = [c.fan(c.refresh(w) if refresh_inputs else w) for w in c.inputs]   # per bit: (scale 0, scale 1, scale 2)
     for k, table in stages:
-        carry = Circuit.FALSE
+        carry, lanes = Circuit.FALSE, sorted(set(table)) if masked else None
         for i in range(width):
-            carry = c.gate3(x[i][0], ~c.swap(x[i][0], k), carry)[0]
+            carry = c.gate3(x[i][0], ~c.swap(x[i][0], k), carry, lanes=lanes)[0]
         s = carry.route(table)
         x = [c.lut(0xCA, x[i][2], c.swap(x[i][1], k), s) for i in range(width)]
     c.output(*[xi[0] for xi in x])
+    return c
+
+
+def lane_reduce(c, w, which, G=None):
+    """`w` folded over the lanes of every group with `which` (0 AND, 1 OR, 2 XOR: the index of the wire in gate()'s
+    triple), G = c.group a power of two: stage k = 1, 2, 4 ... < G is c.gate(acc, acc.lane(k), lanes=range(0, G, 2 k))
+    [which] -- lane t takes (acc[t], acc[t + k]) at the lanes that are multiples of 2 k, which are on in stage k / 2.  The
+    result sits at lane 0 and is FALSE at every other lane (Circuit.bcast brings it to all).  G - 1 rows a group, in
+    log2(G) levels, where a tree on all lanes costs G log2(G)."""
+    G = c.group if G is None else int(G)
+    if G != c.group or G < 2 or G & (G - 1):
+        raise ValueError("lane_reduce: G must be the circuit's lane group, a power of two above 1")
+    if which not in (0, 1, 2):
+        raise ValueError("lane_reduce: which is 0 (AND), 1 (OR) or 2 (XOR)")
+    acc, k = w, 1
+    while k < G:
+        acc = c.gate(acc, acc.lane(k), lanes=range(0, G, 2 * k))[which]
+        k *= 2
+    return acc
+
+
+def packed_equal(width):
+    """Are two packed words equal: Circuit(2, group=width) whose input wires hold words of `width` bits (a power of two),
+    one bit a lane.  One XNOR node on all lanes, then lane_reduce with AND: the output is [x == y] at lane 0 of every
+    group and FALSE at the other lanes.  2 width - 1 rows a group."""
+    width = int(width)
+    c = Circuit(2, group=width)
+    x, y = c.inputs
+    c.output(lane_reduce(c, ~c.gate(x, y)[2], 0))
     return c
 
 
@@ -1025,6 +1145,22 @@ def lwe_not(words, r, one=None):
     return (t + np.uint64(r) - words) & np.uint64(r - 1)
 
 
+def level_row_map(circuit, nodes, inst):
+    """The rows of a level whose nodes are `nodes` (one list of Circuit.schedule) over `inst` instances, as two arrays
+    (rank of the row's node in `nodes`, instance of the row).  A circuit without lane masks: row = rank * instances +
+    instance.  A circuit with any (the masked plan): the level's (node, lane) pairs -- nodes ascending, the lanes a node
+    takes a row on ascending (Circuit.lanes_on) -- each over the instances / group groups, row = pair * per + group."""
+    if not circuit.gate_masks:
+        return np.repeat(np.arange(len(nodes)), inst), np.tile(np.arange(inst), len(nodes))
+    if inst % circuit.group:
+        raise ValueError("the instances (%d) must be a multiple of the lane group (%d)" % (inst, circuit.group))
+    grp = np.arange(inst // circuit.group) * circuit.group
+    pairs = [(k, l) for k, g in enumerate(nodes) for l in circuit.lanes_on(g)]
+    rank = np.repeat(np.array([k for k, _ in pairs], dtype=np.int64), len(grp))
+    at = np.concatenate([grp + l for _, l in pairs]) if pairs else np.zeros(0, dtype=np.int64)
+    return rank, at
+
+
 def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None, call0=0, _next=False):
     """The circuit composed on the host from whole-level bootstrap calls, in the row and call order of
     sgfhe_circuit_run: inputs [n_inputs][instances][n + 1] -> outputs [n_outputs][instances][n + 1].
@@ -1040,8 +1176,10 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None, call0=0, _
     sibling's table -- boot_lut is a function of (call, row, index, table) --, all siblings of a call in one further
     boot_lut(call, ...) whose rows and indices repeat.  data: the planes of a circuit that has any, uint8
     [planes][instances]; the row of a data node or data sibling at instance t goes to boot_lut with the table
-    data[plane][t].  call0: the number of the first call (replay_steps counts on from step to step).  A checking and
-    measuring aid: the engine's circuit path does this on the device (Engine.circuit_run)."""
+    data[plane][t].  call0: the number of the first call (replay_steps counts on from step to step).  A circuit with lane
+    masks runs its levels in the row order of the masked plan (level_row_map), and the wires of a masked node are the
+    trivial LWE (0, 0) on its off lanes.  A checking and measuring aid: the engine's circuit path does this on the
+    device (Engine.circuit_run)."""
     inputs = np.asarray(inputs, dtype=np.uint64)
     inst, row = inputs.shape[1], inputs.shape[2]
     data = check_data(circuit, data, inst)
@@ -1057,8 +1195,9 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None, call0=0, _
 
     call = call0
     for nodes in circuit.schedule():
-        # row = rank * instances + instance
+        # row = rank * instances + instance, or the pairs of a masked plan: row j is node rk[j] at instance ri[j]
         mask = np.uint64(r - 1)
+        rk, ri = level_row_map(circuit, nodes, inst)
 
         def pair(g):   # the bootstrap inputs of node g: (x, y), (x + y mod r, z) of a three-input node, (U, FALSE)
             if circuit.kind(g) in ("lut", "data"):   # position p reads a wire at the codeword Dr >> (2 - p)
@@ -1074,11 +1213,11 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None, call0=0, _
             return vals[0], vals[1]
 
         pairs = [pair(g) for g in nodes]
-        x = np.concatenate([p[0] for p in pairs])
-        y = np.concatenate([p[1] for p in pairs])
+        x = np.stack([p[0] for p in pairs])[rk, ri]
+        y = np.stack([p[1] for p in pairs])[rk, ri]
         res = np.zeros((len(x), 3, row), dtype=np.uint64)
-        tables = np.concatenate([circuit.node_tables(g, inst, data).astype(np.int64) if g in circuit.gate_tables
-                                 else np.full(inst, -1, dtype=np.int64) for g in nodes])
+        tables = np.stack([circuit.node_tables(g, inst, data).astype(np.int64) if g in circuit.gate_tables
+                           else np.full(inst, -1, dtype=np.int64) for g in nodes])[rk, ri]
         sibs = [(k, h) for k, g in enumerate(nodes) for h in circuit.live_siblings(g)]   # (rank of the leader, sibling)
         for _, h in sibs:
             for w in range(3):
@@ -1090,25 +1229,25 @@ def replay_levels(circuit, inputs, r, boot, boot_lut=None, data=None, call0=0, _
                 res[sl] = boot(call, x[sl, :n], x[sl, n], y[sl, :n], y[sl, n])
             if len(idx):
                 res[r0 + idx] = boot_lut(call, x[sl, :n][idx], x[sl, n][idx], tables[sl][idx].astype(np.uint8), idx)
-            rows_in_call = len(x[sl])
-            part = [(k, h, np.arange(max(r0, k * inst), min(r0 + rows_in_call, (k + 1) * inst)) - r0) for k, h in sibs]
+            part = [(k, h, np.flatnonzero(rk[sl] == k)) for k, h in sibs]   # the leader's rows of this call
             part = [(k, h, sel) for k, h, sel in part if len(sel)]
             if part:
                 sel = np.concatenate([s_ for _, _, s_ in part])
-                tab = np.concatenate([circuit.node_tables(h, inst, data)[r0 + s_ - k * inst] for k, h, s_ in part])
+                tab = np.concatenate([circuit.node_tables(h, inst, data)[ri[r0 + s_]] for k, h, s_ in part])
                 got = boot_lut(call, x[sl, :n][sel], x[sl, n][sel], tab, sel)
                 at = 0
                 for k, h, s_ in part:
                     for w in range(3):
-                        wires[circuit.n_inputs + 3 * h + w][r0 + s_ - k * inst] = got[at:at + len(s_), w]
+                        wires[circuit.n_inputs + 3 * h + w][ri[r0 + s_]] = got[at:at + len(s_), w]
                     at += len(s_)
             call += 1
         for k, g in enumerate(nodes):
-            sl = slice(k * inst, (k + 1) * inst)
+            sl = np.flatnonzero(rk == k)   # (every instance in order, or those of a masked node's lanes)
             for w in range(3):
-                wires[circuit.n_inputs + 3 * g + w] = res[sl, w]
+                wires[circuit.n_inputs + 3 * g + w] = np.zeros((inst, row), dtype=np.uint64)
+                wires[circuit.n_inputs + 3 * g + w][ri[sl]] = res[sl, w]
             if circuit.kind(g) not in ("classic", "lut", "data"):
-                wires[circuit.n_inputs + 3 * g + 2] = (x[sl] + y[sl] - np.uint64(2) * res[sl, 0]) & mask
+                wires[circuit.n_inputs + 3 * g + 2][ri[sl]] = (x[sl] + y[sl] - np.uint64(2) * res[sl, 0]) & mask
     out = np.stack([val(ref, d) for ref, d in zip(circuit.outputs, circuit.output_shifts)]) if circuit.outputs \
         else np.zeros((0, inst, row), np.uint64)
     if not _next:
@@ -1262,7 +1401,7 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
     ModRed (modred_words) being what the next level reads and what `lwe` holds.  The pack stage takes the
     ciphertexts q = output * blocks + block in ascending order, pack_calls(n) at a time: a group's refreshed
     ciphertexts (outputs that name an input wire, the constant, an XOR3 wire or the LOW wire of a sum node, or carry a
-    lane shift) are bootstrapped as one call -- trivial 1 paired
+    lane shift or route, or name a wire of a node with a lane mask) are bootstrapped as one call -- trivial 1 paired
     with every bit, row = rank among them * n + bit, AND rows kept -- and then `tail(call, lwe_q)` (lwe_q
     [count][n][n + 1][2] -> (w, v), each [count][m]) packs the group: the gate's own rows for a direct output, NOT
     over Z_Q applied (lwe_not_modq).  `call` counts every call from 0.  lift=True (SGFHE_CIRCUIT_PACK_LIFT): the
@@ -1288,7 +1427,8 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
     lwe = replay_levels(circuit, inputs, r, reduced, reduced_lut, data=data)
     call, k, raw_wire = 0, 0, {}
     for nodes in circuit.schedule():                        # the calls of a level, back into the level's rows
-        rows = len(nodes) * inst
+        rk, ri = level_row_map(circuit, nodes, inst)
+        rows = len(rk)
         calls = -(-rows // CALL_ROWS)
         level = np.concatenate([raws[k + j] if k + j in raws else
                                 np.zeros((min(CALL_ROWS, rows - j * CALL_ROWS), 3, n + 1, 2), dtype=np.uint64)
@@ -1296,16 +1436,18 @@ def replay_ct_direct(circuit, a, b, params, boot_raw, tail, lift=False, boot_lut
         k += calls
         call = k
         for rank, g in enumerate(nodes):
+            sl = np.flatnonzero(rk == rank)
             for w in range(3):
-                raw_wire[circuit.n_inputs + 3 * g + w] = level[rank * inst:(rank + 1) * inst, w]
+                raw_wire[circuit.n_inputs + 3 * g + w] = np.zeros((inst, n + 1, 2), dtype=np.uint64)
+                raw_wire[circuit.n_inputs + 3 * g + w][ri[sl]] = level[sl, w]
 
     def is_direct(o):
         i = circuit.outputs[o] & ~NOT_BIT & 0xFFFFFFFF
         if i == FALSE_ID or i < circuit.n_inputs or circuit.output_shifts[o] != 0:
             return False
         g, w = divmod(i - circuit.n_inputs, 3)
-        if g in circuit.gate_tables:                            # wire +0 of a LUT node: refreshed or lifted
-            return False
+        if g in circuit.gate_tables or g in circuit.gate_masks:   # wire +0 of a LUT node, a wire of a masked node:
+            return False                                            # refreshed or lifted
         return not (w == 2 and circuit.kind(g) != "classic")   # XOR3 / LOW is linear over Z_r: no gate row over Z_Q
 
     n_ct, cpc = circuit.n_outputs * blocks, pack_calls(n)

@@ -52,6 +52,9 @@ struct CircuitImage {
     // behind every other table, and only in a plan with route tables (sgfhe_circuit_create_routed, n_routes > 0);
     // next_route only when the plan has registers as well
     uint32_t routes = 0, term_route = 0, out_route = 0, next_route = 0;
+    // behind every other table, and only in a plan with mask tables (sgfhe_circuit_create_masked, n_masks > 0): the
+    // levels' (node, lane) pairs that take a row, then those that take none
+    uint32_t pair_node = 0, pair_lane = 0, off_node = 0, off_lane = 0;
 };
 
 struct CircuitPlan {
@@ -119,15 +122,41 @@ struct CircuitPlan {
     std::vector<uint32_t> term_route;   // [terms + 2 n_outputs], beside term_shift
     std::vector<uint32_t> out_route;    // [n_outputs], beside out_shift
     std::vector<uint32_t> next_route;   // [n_regs], beside next_shift
+    // Lane masks (sgfhe_circuit_create_masked): a node whose mask index is k >= 1 takes a row only at the instances whose
+    // lane t % group is set in masks[(k - 1) * group ..]; on the other lanes all three of its wires are the constant FALSE.
+    // Index 0: every lane.  In a plan with masks every level is a list of (node, lane) PAIRS -- nodes ascending in
+    // `order`, lanes ascending, an unmasked node all `group` of them -- and with per = instances / group row R of the
+    // level is pair R / per at group R % per: instance (R % per) * group + lane.  The OFF pairs of a level are the
+    // (masked node, lane not set) in the same order: the rows the level's fill writes as zeros.  All empty in a plan
+    // without mask tables, whose rows stay rank * instances + instance.
+    uint32_t n_masks = 0;
+    std::vector<uint8_t> masks;         // [n_masks][group], 0 or 1
+    std::vector<uint32_t> node_mask;    // [live], host only: the mask index of every live node in `order`
+    std::vector<uint32_t> pair_start;   // [levels + 2]: level L's pairs are pair_node / pair_lane[pair_start[L] ..
+                                        // pair_start[L + 1]) (level 0 holds none)
+    std::vector<uint32_t> pair_node;    // [pairs]: the node's rank in its level, index in `order` - level_start[L]
+    std::vector<uint32_t> pair_lane;    // [pairs]
+    std::vector<uint32_t> off_start;    // [levels + 2], as pair_start
+    std::vector<uint32_t> off_node;     // [off pairs]: rank in the level
+    std::vector<uint32_t> off_lane;     // [off pairs]
+    uint64_t rows_per_group = 0;        // level-call rows one group of `group` instances costs: the pairs of all levels
+                                        // (live() * group in a plan without masks)
     // Every device table above in one array, uploaded once per run: node_kind, term_start, term_ref, term_shift,
     // term_weight, out_slot, out_ref, out_shift, input_slot, jobs (then fam_start, fam_entry; then next_ref, next_shift,
-    // reg_scale, reg_index; then routes, term_route, out_route, next_route), each at its offset `at`
+    // reg_scale, reg_index; then routes, term_route, out_route, next_route; then pair_node, pair_lane, off_node,
+    // off_lane), each at its offset `at`
     std::vector<uint32_t> image;
     CircuitImage at;
 
     size_t live() const { return order.size(); }
     uint32_t n_stream() const { return n_inputs - n_regs; }   // the inputs a step brings
     bool lanes() const { return group > 1; }   // (group 1 admits no shift but 0)
+    bool masked() const { return n_masks != 0; }   // the levels' rows are (node, lane) pairs
+    // whether live node k takes a row at lane l
+    bool lane_on(size_t k, uint32_t l) const {
+        return !masked() || !node_mask[k] || masks[(size_t)(node_mask[k] - 1) * group + l] != 0;
+    }
+    uint32_t level_pairs(uint32_t L) const { return pair_start[L + 1] - pair_start[L]; }
     // the route table of a reference whose route index is `k`, NULL for none
     const int32_t *route(uint32_t k) const { return k ? routes.data() + (size_t)(k - 1) * group : nullptr; }
     const int32_t *term_route_of(size_t i) const { return n_routes ? route(term_route[i]) : nullptr; }
@@ -146,8 +175,10 @@ struct CircuitPlan {
         if (!(word & CIRC_DATA)) return (word >> plane_shift) & 0xFFu;
         return data[(size_t)((word >> plane_shift) & 0xFFFFu) * instances + t];
     }
-    // rows of level L in a run over `instances`; row = rank_in_level * instances + instance
+    // rows of level L in a run over `instances`; row = rank_in_level * instances + instance -- in a plan with masks
+    // (`instances` a multiple of the group) row = pair * (instances / group) + group of the instance
     uint64_t level_rows(uint32_t L, uint64_t instances) const {
+        if (masked()) return (uint64_t)level_pairs(L) * (instances / group);
         return (uint64_t)(level_start[L + 1] - level_start[L]) * instances;
     }
 };
@@ -225,6 +256,15 @@ struct CircuitRoutes {
     const uint32_t *term_route = nullptr, *out_route = nullptr, *next_route = nullptr;
 };
 
+// The lane masks of sgfhe_circuit_create_masked: masks [n_masks][group] (n_masks 0: none), every entry 0 or 1 and every
+// table with a lane set; node_mask [n_gates] (NULL: all 0): 0 = every lane, k >= 1 = table k - 1.  No sibling carries one.
+struct CircuitMasks {
+    uint32_t n_masks = 0;
+    const uint8_t *masks = nullptr;
+    const uint32_t *node_mask = nullptr;
+    uint32_t of(size_t g) const { return node_mask ? node_mask[g] : 0u; }
+};
+
 // One list of references -- a node's terms, the outputs, the registers' next states -- as the per-reference rules and
 // the plan's tables read it: reference i is ref[i] at the lane shift shift[i] (NULL: 0) or through route[i] (NULL: 0).
 // It may name the constant or a wire id below `wires`, of the scale want(i): position i of a LUT node's terms (`lut`)
@@ -257,6 +297,7 @@ struct CircuitSpec {
     uint32_t group = 1;
     CircuitRegs regs;
     CircuitRoutes routes;
+    CircuitMasks masks;   // (numbering, pruning, liveness, levels and slots do not see them)
 
     uint64_t n_wires() const { return (uint64_t)n_inputs + 3 * (uint64_t)n_gates; }
     // the three lists of references; node g's terms may name the wires before its own
@@ -345,6 +386,18 @@ inline bool valid(const CircuitSpec &S) noexcept {
     for (size_t i = 0; i < (size_t)T.n_routes * S.group; i++)
         if (T.routes[i] < CIRC_ROUTE_FALSE || T.routes[i] >= (int64_t)S.group) return false;
     if (!N.arity && !csr_ok(S)) return false;
+    const CircuitMasks &K = S.masks;
+    if (K.n_masks > SGFHE_CIRCUIT_MAX_MASKS || (K.n_masks && !K.masks)) return false;
+    for (uint32_t k = 0; k < K.n_masks; k++) {   // entries 0 or 1, and a lane set in every table
+        bool any = false;
+        for (size_t l = 0; l < S.group; l++) {
+            if (K.masks[(size_t)k * S.group + l] > 1) return false;
+            any = any || K.masks[(size_t)k * S.group + l];
+        }
+        if (!any) return false;
+    }
+    for (size_t g = 0; g < S.n_gates; g++)
+        if (K.of(g) > K.n_masks || (K.of(g) && N.is_sibling(g))) return false;
     for (size_t g = 0; g < S.n_gates; g++)
         if (!refs_ok(S, S.terms(g))) return false;
     return refs_ok(S, S.outs()) && refs_ok(S, S.nexts());
@@ -425,6 +478,8 @@ struct PlanBuild {
         P.n_inputs = n_inputs, P.n_gates = NG, P.n_outputs = (uint32_t)S.n_outputs;
         P.group = S.group, P.n_planes = N.n_planes, P.n_regs = S.regs.n_regs, P.n_routes = S.routes.n_routes;
         if (P.n_routes) P.routes.assign(S.routes.routes, S.routes.routes + (size_t)P.n_routes * P.group);
+        P.n_masks = S.masks.n_masks;
+        if (P.n_masks) P.masks.assign(S.masks.masks, S.masks.masks + (size_t)P.n_masks * P.group);
         leader.resize(NG);
         for (uint32_t g = 0; g < NG; g++) leader[g] = N.is_sibling(g) ? leader[g - 1] : g;
         live.assign(NG, 0);
@@ -562,6 +617,7 @@ struct PlanBuild {
             if (g < 0 || r.shift != 0 || r.route != 0) continue;
             if ((id - n_inputs) % 3 == 2 && !N.classic((size_t)g)) continue;   // LOW: linear over Z_r, no gate row
             if (N.is_lut((size_t)g)) continue;   // wire +0 of a LUT node: refreshed or lifted, as a LOW wire is
+            if (S.masks.of((size_t)g)) continue;   // a masked node has no gate row on its off lanes: refreshed or lifted
             P.out_node[o] = rank_of[g];
             P.out_gate[o] = (id - n_inputs) % 3;
         }
@@ -592,6 +648,37 @@ struct PlanBuild {
         }
     }
 
+    // A masked LUT node must not lead a live sibling: the sibling's wires are written inside the bootstrap call
+    // (k_final_lut_multi), which knows no off lanes.  Read after stage 2, which says which siblings are live.
+    bool masked_family() const {
+        for (uint32_t g = 0; g < NG; g++)
+            if (live[g] && N.is_sibling(g) && S.masks.of(leader[g])) return true;
+        return false;
+    }
+
+    // Stage 8b, masks: the rows a group costs; in a plan with mask tables every live node's mask index, and every
+    // level's pairs -- those that take a row, and the off pairs of its masked nodes.
+    void mask_pairs() {
+        P.rows_per_group = (uint64_t)P.live() * P.group;
+        if (!P.n_masks) return;
+        P.rows_per_group = 0;
+        for (size_t k = 0; k < P.live(); k++) P.node_mask.push_back(S.masks.of(P.order[k]));
+        P.pair_start.assign((size_t)P.levels + 2, 0);
+        P.off_start.assign((size_t)P.levels + 2, 0);
+        for (uint32_t L = 1; L <= P.levels; L++) {
+            for (uint32_t k = P.level_start[L]; k < P.level_start[L + 1]; k++)
+                for (uint32_t l = 0; l < P.group; l++) {
+                    const bool on = P.lane_on(k, l);
+                    (on ? P.pair_node : P.off_node).push_back(k - P.level_start[L]);
+                    (on ? P.pair_lane : P.off_lane).push_back(l);
+                }
+            if (P.pair_node.size() >= 0x100000000ull) throw std::length_error("circuit pairs");
+            P.pair_start[L + 1] = (uint32_t)P.pair_node.size();
+            P.off_start[L + 1] = (uint32_t)P.off_node.size();
+        }
+        P.rows_per_group = P.pair_node.size();
+    }
+
     // Stage 9, image: every device table in the order CircuitPlan::image states, each at its offset in P.at.
     void image() {
         auto place = [&](const auto &tab) -> uint32_t {
@@ -602,7 +689,8 @@ struct PlanBuild {
         };
         P.image.reserve(P.node_kind.size() + P.term_start.size() + 3 * P.term_ref.size() + P.out_slot.size() +
                         2 * (size_t)P.n_outputs + n_inputs + P.jobs.size() + 4 * (size_t)P.n_regs + P.routes.size() +
-                        P.term_route.size() + P.out_route.size() + P.next_route.size());
+                        P.term_route.size() + P.out_route.size() + P.next_route.size() + 2 * P.pair_node.size() +
+                        2 * P.off_node.size());
         P.at.node_kind = place(P.node_kind);
         P.at.term_start = place(P.term_start);
         P.at.term_ref = place(P.term_ref);
@@ -629,6 +717,12 @@ struct PlanBuild {
             P.at.out_route = place(P.out_route);
             if (P.n_regs) P.at.next_route = place(P.next_route);
         }
+        if (P.n_masks) {
+            P.at.pair_node = place(P.pair_node);
+            P.at.pair_lane = place(P.pair_lane);
+            P.at.off_node = place(P.off_node);
+            P.at.off_lane = place(P.off_lane);
+        }
         P.at.words = (uint32_t)P.image.size();
     }
 };
@@ -636,19 +730,25 @@ struct PlanBuild {
 }  // namespace circuit_detail
 
 // Builds `P` from the circuit `S`, stage by stage.  Returns SGFHE_OK, SGFHE_ERR_INVALID_ARG for a malformed circuit (`P`
-// is not touched), SGFHE_ERR_OOM when an allocation fails (`P` is reset).  Nothing throws out of it.
+// is not touched) or for a masked LUT node that leads a live sibling (known after pruning: `P` is reset),
+// SGFHE_ERR_OOM when an allocation fails (`P` is reset).  Nothing throws out of it.
 inline int32_t circuit_plan(const CircuitSpec &S, CircuitPlan &P) noexcept {
     if (!circuit_detail::valid(S)) return SGFHE_ERR_INVALID_ARG;
     try {
         P = CircuitPlan();
         circuit_detail::PlanBuild B(S, P);
         B.prune_and_level();
+        if (B.masked_family()) {
+            P = CircuitPlan();
+            return SGFHE_ERR_INVALID_ARG;
+        }
         B.order();
         B.slots();
         B.families();
         B.node_table();
         B.outputs_and_jobs();
         B.registers();
+        B.mask_pairs();
         B.image();
     } catch (...) {   // std::bad_alloc, std::length_error: nothing else allocates or throws here
         P = CircuitPlan();
@@ -669,7 +769,8 @@ inline int32_t circuit_plan(const CircuitSpec &S, CircuitPlan &P) noexcept {
 // of s = sum of w x mod 4: MAJ, ONE_OR_TWO (one or two of its inputs true) and XOR3 of a three-input node.
 // `data` [n_planes][instances]: the planes of a run (sgfhe_circuit_run_probe_data); a data LUT node or data sibling of
 // plane p has the table data[p][t] at instance t, its own instance whatever its terms' shifts (SGFHE_ERR_INVALID_ARG for
-// NULL when the plan has planes and instances > 0).
+// NULL when the plan has planes and instances > 0).  In a plan with lane masks the three rows of a masked node are 0 on
+// the lanes that are off.
 // SGFHE_ERR_OOM when the table cannot be allocated; nothing throws out of it.
 inline size_t circuit_probe_rows(const CircuitPlan &P) { return (size_t)P.n_inputs + 3 * (P.live() + P.siblings()); }
 inline size_t circuit_bit_words(size_t instances) { return (instances + 63) / 64; }
@@ -718,6 +819,13 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
         const uint64_t v = src ? src[w] : 0ull;
         return ref & CIRC_NOT ? ~v : v;
     };
+    // a masked node's three rows are FALSE on its off lanes (it leads no live sibling), instance by instance
+    auto mask_rows = [&](size_t k, uint64_t *o) {
+        if (!P.masked() || !P.node_mask[k]) return;
+        for (size_t t = 0; t < instances; t++)
+            if (!P.lane_on(k, (uint32_t)(t % (size_t)G)))
+                for (size_t w = 0; w < 3; w++) o[w * wpr + t / 64] &= ~(1ull << (t % 64));
+    };
     for (size_t k = 0; k < P.live(); k++) {   // `order` is a topological order: inputs are rows filled before
         uint64_t *o = table.data() + ((size_t)P.n_inputs + 3 * k) * wpr;
         const uint32_t t0 = P.term_start[k], t1 = P.term_start[k + 1];
@@ -748,6 +856,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
             fill(P.node_kind[k], 8, o);
             for (size_t i = P.siblings() ? P.fam_start[k] : 0, end = P.siblings() ? P.fam_start[k + 1] : 0; i < end; i++)
                 fill(P.fam_entry[4 * i], 0, table.data() + ((size_t)P.n_inputs + 3 * (P.live() + i)) * wpr);
+            mask_rows(k, o);
             continue;
         }
         if (P.kind(k) == 1) {
@@ -769,6 +878,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
                 }
             }
             for (size_t w = 0; w < wpr; w++) o[wpr + w] = lo[w] ^ hi[w];
+            mask_rows(k, o);
             continue;
         }
         const uint32_t rx = P.term_row[t0], ry = P.term_row[t0 + 1];
@@ -779,6 +889,7 @@ inline int32_t circuit_plain_bits(const CircuitPlan &P, const uint8_t *in_bits, 
             o[wpr + w] = x | y;
             o[2 * wpr + w] = x ^ y;
         }
+        mask_rows(k, o);
     }
     return SGFHE_OK;
 }
@@ -805,8 +916,14 @@ inline CircuitCall circuit_level_call(const CircuitPlan &P, uint32_t L, uint64_t
     CircuitCall C;
     C.k0 = P.level_start[L];
     C.rows = (uint32_t)std::min<uint64_t>(SGFHE_CIRCUIT_CALL_ROWS, P.level_rows(L, instances) - row0);
-    C.ka = C.k0 + (uint32_t)(row0 / instances);
-    C.kb = C.k0 + (uint32_t)((row0 + C.rows - 1) / instances);
+    if (P.masked()) {   // the nodes of the first and the last pair
+        const uint64_t per = instances / P.group;
+        C.ka = C.k0 + P.pair_node[P.pair_start[L] + (size_t)(row0 / per)];
+        C.kb = C.k0 + P.pair_node[P.pair_start[L] + (size_t)((row0 + C.rows - 1) / per)];
+    } else {
+        C.ka = C.k0 + (uint32_t)(row0 / instances);
+        C.kb = C.k0 + (uint32_t)((row0 + C.rows - 1) / instances);
+    }
     C.j0 = (size_t)(std::lower_bound(P.job_k.begin(), P.job_k.end(), C.ka) - P.job_k.begin());
     C.j1 = (size_t)(std::upper_bound(P.job_k.begin(), P.job_k.end(), C.kb) - P.job_k.begin());
     C.sum = P.gate3_in(C.ka, C.kb);
@@ -1001,6 +1118,8 @@ inline CircuitVerdict circuit_request_check(const CircuitPlan *P, const CircuitR
         return refused("sgfhe_circuit_run", "a plan with data planes runs through the _data entries");
     if (P->n_planes && !q.data && q.count && q.steps)
         return refused(q.stepped ? form : "sgfhe_circuit_run_data", "NULL data for a plan with data planes");
+    if (q.probe && P->masked())   // (the probe's rows are rank * instances + instance)
+        return refused("sgfhe_circuit_run_probe", "a plan with lane masks has no probe", SGFHE_ERR_UNSUPPORTED);
     if (q.probe && (!q.sk || !q.stats || (!q.in_bits && P->n_inputs)))
         return refused("sgfhe_circuit_run_probe", "NULL secret key, input bits or statistics pointer");
     if (q.ct && (!q.out_w != !q.out_v || (!q.packs() && !q.out && !q.state_out)))

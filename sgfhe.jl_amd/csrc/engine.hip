@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "circuit_masks.h"
 #include "host_plumbing.h"
 #include "coalescer.h"
 #include "circuit.h"
@@ -3072,6 +3073,7 @@ int32_t sgfhe_circuit_create_seq(uint32_t n_inputs, uint32_t n_planes, const uin
                                        next_shift, reg_scale, 0, nullptr, nullptr, nullptr, nullptr, out);
 }
 
+// (... and sgfhe_circuit_create_routed the masked entry without masks)
 int32_t sgfhe_circuit_create_routed(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
                                     const uint32_t *node_start, const uint32_t *term_ref, const int32_t *term_shift,
                                     const int32_t *term_weight, const uint32_t *node_table, size_t n_gates,
@@ -3080,12 +3082,35 @@ int32_t sgfhe_circuit_create_routed(uint32_t n_inputs, uint32_t n_planes, const 
                                     const uint32_t *reg_scale, uint32_t n_routes, const int32_t *routes,
                                     const uint32_t *term_route, const uint32_t *out_route, const uint32_t *next_route,
                                     sgfhe_circuit **out) {
+    return sgfhe_circuit_create_masked(n_inputs, n_planes, node_kind, node_start, term_ref, term_shift, term_weight,
+                                       node_table, n_gates, outputs, out_shift, n_outputs, group, n_regs, next_ref,
+                                       next_shift, reg_scale, n_routes, routes, term_route, out_route, next_route, 0,
+                                       nullptr, nullptr, out);
+}
+
+int32_t sgfhe_circuit_create_masked(uint32_t n_inputs, uint32_t n_planes, const uint32_t *node_kind,
+                                    const uint32_t *node_start, const uint32_t *term_ref, const int32_t *term_shift,
+                                    const int32_t *term_weight, const uint32_t *node_table, size_t n_gates,
+                                    const uint32_t *outputs, const int32_t *out_shift, size_t n_outputs, uint32_t group,
+                                    uint32_t n_regs, const uint32_t *next_ref, const int32_t *next_shift,
+                                    const uint32_t *reg_scale, uint32_t n_routes, const int32_t *routes,
+                                    const uint32_t *term_route, const uint32_t *out_route, const uint32_t *next_route,
+                                    uint32_t n_masks, const uint8_t *masks, const uint32_t *node_mask,
+                                    sgfhe_circuit **out) {
     const CircuitNodes N = circuit_nodes_csr(5, node_kind, node_start, term_ref, term_shift, term_weight, node_table, n_planes);
     CircuitSpec S = circuit_spec(n_inputs, N, n_gates, outputs, out_shift, n_outputs, group);
     S.regs.n_regs = n_regs, S.regs.next_ref = next_ref, S.regs.next_shift = next_shift, S.regs.reg_scale = reg_scale;
     S.routes.n_routes = n_routes, S.routes.routes = routes;
     S.routes.term_route = term_route, S.routes.out_route = out_route, S.routes.next_route = next_route;
+    S.masks.n_masks = n_masks, S.masks.masks = masks, S.masks.node_mask = node_mask;
     return circuit_create(S, out);
+}
+
+int32_t sgfhe_circuit_masks(const sgfhe_circuit *c, uint32_t *n_masks, uint64_t *rows_per_group) {
+    if (!c || !n_masks || !rows_per_group) return SGFHE_ERR_INVALID_ARG;
+    *n_masks = c->plan.n_masks;
+    *rows_per_group = c->plan.rows_per_group;
+    return SGFHE_OK;
 }
 
 int32_t sgfhe_circuit_routes(const sgfhe_circuit *c, uint32_t *n_routes) {
@@ -3250,9 +3275,30 @@ struct CircuitRun {
     // every level L = 1 .. levels in calls of SGFHE_CIRCUIT_CALL_ROWS rows from row 0; then every pack group from
     // ciphertext 0: the walk that numbers a run's calls (csrc/circuit.h)
     int32_t level_calls() {
-        for (uint32_t L = 1; L <= P.levels; L++)
+        for (uint32_t L = 1; L <= P.levels; L++) {
+            if (const int32_t rc = mask_fill(L)) return rc;
             for (uint64_t row0 = 0; row0 < P.level_rows(L, instances); row0 += SGFHE_CIRCUIT_CALL_ROWS)
                 if (const int32_t rc = level_call(L, row0)) return rc;
+        }
+        return SGFHE_OK;
+    }
+    // A plan with lane masks: the pairs of level L on the device (views into circ_tab; none in a plan without masks,
+    // whose kernels then decode a row as they always did), and the level's fill -- the off lanes of its masked nodes as
+    // zeros, once per level and step, before the level's first call (k_circ_mask_fill says why any place in the level
+    // would do)
+    CircPairs level_pairs(uint32_t L) const {
+        if (!P.masked()) return {};
+        const uint32_t *tab = c->circ_tab.p;
+        return {tab + P.at.pair_node + P.pair_start[L], tab + P.at.pair_lane + P.pair_start[L], inst / P.group, P.group};
+    }
+    int32_t mask_fill(uint32_t L) {
+        if (!P.masked() || P.off_start[L + 1] == P.off_start[L]) return SGFHE_OK;
+        const uint32_t *tab = c->circ_tab.p;
+        const uint32_t n_off = P.off_start[L + 1] - P.off_start[L], per = inst / P.group;
+        hipLaunchKernelGGL(k_circ_mask_fill, dim3(copy_grid((size_t)n_off * 3 * per * row)), dim3(256), 0, st,
+                           c->circ_wires.p, d_out_slot + 3 * (size_t)P.level_start[L], tab + P.at.off_node + P.off_start[L],
+                           tab + P.at.off_lane + P.off_start[L], n_off, per, P.group, inst, (uint32_t)n);
+        HIPCHK(c, hipGetLastError());
         return SGFHE_OK;
     }
     int32_t pack_groups() {
@@ -3292,10 +3338,11 @@ struct CircuitRun {
     // the gather of one call: rows row0 .. row0 + rows of the level whose first node is `node0` of the plan's node table
     // (a level's first node, or live() for the pack stage's pseudo-level)
     // `lutw`: the call's LUT descriptor, for a level call that holds a LUT node (NULL otherwise)
-    void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows, uint32_t *lutw) const {
+    // `X`: the level's pairs in a plan with lane masks (level_pairs; the pack stage's pseudo-level has none)
+    void gather(uint32_t node0, const Staging &S, size_t row0, size_t rows, uint32_t *lutw, CircPairs X = {}) const {
         hipLaunchKernelGGL(k_circ_gather, dim3(((uint32_t)rows * (uint32_t)row + 255) / 256), dim3(256), 0, st,
                            c->circ_wires.p, nodes, node0, S.a1, S.b1, S.a2, S.b2, (uint32_t)row0, (uint32_t)rows, inst,
-                           (uint32_t)n, r, lutw, (const uint8_t *)(data ? c->circ_data.p : nullptr));
+                           (uint32_t)n, r, lutw, (const uint8_t *)(data ? c->circ_data.p : nullptr), X);
     }
     // a reference list of the uploaded image, from its offsets (`route` is read only in a plan with route tables)
     CircRefs refs_at(uint32_t ref, uint32_t shift, uint32_t route) const {
@@ -3463,6 +3510,7 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
     const uint32_t *out_slot = d_out_slot + 3 * (size_t)C.k0, *kind = nodes.kind + C.k0;
     const uint32_t un = (uint32_t)n, r0 = (uint32_t)row0;
     const bool raw = direct && C.j1 > C.j0;
+    const CircPairs X = level_pairs(L);
     // a call that holds a LUT node: its rows start at amplitude A0 and leave through k_final_lut (LutDesc)
     LutDesc lut = {reinterpret_cast<uint32_t *>(c->circ_stage.p + stage_words()), false};
     if (C.fam) {   // ... and the live siblings of its LUT nodes leave through k_final_lut_multi, into the wire table
@@ -3470,8 +3518,9 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
         lut.fam.start = d_fam_start, lut.fam.entry = d_fam_entry;
         lut.fam.node0 = C.k0, lut.fam.row0 = r0, lut.fam.instances = inst;
         lut.fam.data = data ? c->circ_data.p : nullptr;
+        lut.fam.pairs = X;
     }
-    gather(C.k0, S, row0, C.rows, C.lut ? const_cast<uint32_t *>(lut.rows) : nullptr);
+    gather(C.k0, S, row0, C.rows, C.lut ? const_cast<uint32_t *>(lut.rows) : nullptr, X);
     HIPCHK(c, hipGetLastError());
     BootCall call(c);
     call.rows = S, call.batch = C.rows, call.out = S.res, call.st = st;
@@ -3484,14 +3533,14 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
         for (size_t j = C.j0; j < C.j1;) {
             const CircuitJobChunk ch = circuit_job_chunk(j, C.j0, C.j1);
             hipLaunchKernelGGL(k_circ_scatter_raw, dim3(C.rows, ch.nj + ch.wires), dim3(256), 0, st, res, out_slot,
-                               c->circ_wires.p, d_jobs + 3 * j, c->circ_raw.p, cur(c).d_crt, r0, inst, un, ch.wires);
+                               c->circ_wires.p, d_jobs + 3 * j, c->circ_raw.p, cur(c).d_crt, r0, inst, un, ch.wires, X);
             HIPCHK(c, hipGetLastError());
             j += ch.nj;
         }
         if (C.sum) {   // a sum node's LOW rows, from the staging the bootstrap consumed (after the scatter: over the XOR
                        // row's words in the wire table)
             hipLaunchKernelGGL(k_circ_xor3_raw, dim3(C.rows), dim3(256), 0, st, res, kind, out_slot, c->circ_wires.p,
-                               S.a1, S.b1, S.a2, S.b2, cur(c).d_crt, r0, inst, un, r);
+                               S.a1, S.b1, S.a2, S.b2, cur(c).d_crt, r0, inst, un, r, X);
             HIPCHK(c, hipGetLastError());
         }
         return SGFHE_OK;
@@ -3499,11 +3548,11 @@ int32_t CircuitRun::level_call(uint32_t L, uint64_t row0) {
     const uint32_t tg = C.rows * (uint32_t)row;
     if (C.sum) {   // (before the scatter and the probe read the result rows)
         hipLaunchKernelGGL(k_circ_xor3, dim3((tg + 255) / 256), dim3(256), 0, st, S.res, kind, S.a1, S.b1, S.a2, S.b2, r0,
-                           C.rows, inst, un, r);
+                           C.rows, inst, un, r, X);
         HIPCHK(c, hipGetLastError());
     }
     hipLaunchKernelGGL(k_circ_scatter, dim3((3 * tg + 255) / 256), dim3(256), 0, st, S.res, out_slot, c->circ_wires.p, r0,
-                       C.rows, inst, un);
+                       C.rows, inst, un, X);
     HIPCHK(c, hipGetLastError());
     // the probe: the call's own result rows, read or not, before the next call overwrites them (same stream)
     if (!q.probe) return SGFHE_OK;

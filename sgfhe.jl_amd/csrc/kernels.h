@@ -1711,18 +1711,41 @@ constexpr uint32_t CIRC_TABLE_DATA = 0x01000000u;
 // The primitive (sgfhe_bootstrap_lut_multi_batch, CIRC = false): the row's tables are tables[row][0 .. n_tables), and
 // the rows go to out [row][n_tables][3][n + 1], both from the chunk's first row on.
 // A level call of a circuit (sgfhe_circuit_create_lut_multi, CIRC = true): chunk row b is row R = row0 + b of its
-// level, node node0 + R / instances of the plan at instance R % instances; the live siblings of that node are the
+// level, node node0 + R / instances of the plan at instance R % instances (circ_row: a plan with lane masks decodes
+// the row through its pairs); the live siblings of that node are the
 // entries start[node] .. start[node + 1] of {table, slot of wire +0, +1, +2} (CircuitPlan::fam_entry), and wire w goes
 // to its slot of the wire table `out` ([slot][instances][n + 1]) -- as the ModRed word, in an un-reduced call too;
 // a wire nothing reads has no slot (CIRC_SLOT_NONE) and is not formed.  The node's own table leaves through k_final_lut.
 // An entry may name a plane instead of a table (CIRC_TABLE_DATA): the thread resolves it with one byte load at its
 // instance, uniform over the row, before the entry's table is used at all (lut_fam_table).
+// The rows of a level call of a plan with lane masks (sgfhe_circuit_create_masked): the level's (node, lane) pairs --
+// `node` the rank in the level -- with per = instances / group; row R of the level is pair R / per at group R % per,
+// instance (R % per) * group + lane.  `node` NULL: a plan without masks, rank R / instances at instance R % instances.
+// The two entries are 4-byte loads at an address that is uniform over a row, and per-lane loads for the reason written
+// at circ_ref_word: a wave may straddle two rows, so they are not wave-uniform broadcasts.
+struct CircPairs {
+    const uint32_t *node = nullptr, *lane = nullptr;
+    uint32_t per = 0, group = 0;
+};
+// row R of a level -> (rank of its node in the level, instance)
+__device__ __forceinline__ void circ_row(const CircPairs &X, uint32_t R, uint32_t instances, uint32_t &rank,
+                                         uint32_t &inst) {
+    if (!X.node) {
+        rank = R / instances, inst = R % instances;
+        return;
+    }
+    const uint32_t p = R / X.per;
+    rank = X.node[p];
+    inst = (R % X.per) * X.group + X.lane[p];
+}
+
 struct LutTables {
     const uint8_t *tables;            // the primitive
     uint32_t n_tables;
     const uint32_t *start, *entry;    // a level call
     uint32_t node0, row0, instances;
     const uint8_t *data;              // a level call of a plan with planes: [n_planes][instances]
+    CircPairs pairs;                  // a level call of a plan with lane masks (an unmasked leader: all its lanes)
 };
 __device__ __forceinline__ uint32_t lut_fam_table(const LutTables &T, uint32_t i, uint32_t inst) {
     const uint32_t w = T.entry[4 * i];
@@ -1749,7 +1772,9 @@ k_final_lut_multi(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, 
     uint32_t need = 0;                   // bit j: some table of the row has a transition at j
     u128 P[8];
     if constexpr (CIRC) {
-        const uint32_t R = T.row0 + b, node = T.node0 + R / T.instances, inst = R % T.instances;
+        uint32_t rank, inst;
+        circ_row(T.pairs, T.row0 + b, T.instances, rank, inst);
+        const uint32_t node = T.node0 + rank;
         const uint32_t s0 = T.start[node], s1 = T.start[node + 1];
         if (s0 == s1) return;
         for (uint32_t i = s0; i < s1; i++) need |= lut_edges(lut_fam_table(T, i, inst));
@@ -1781,7 +1806,8 @@ k_final_lut_multi(const uint64_t *__restrict__ dig, uint64_t *__restrict__ out, 
 // Memory-bound copies of rows of n + 1 uint64 words (a[0..n) then b) between the wire table
 // ([slot][instances][n + 1]) and the staging of one bootstrap call, one thread per word: consecutive
 // threads touch consecutive words of a row, so loads and stores are coalesced 8-byte accesses (rows
-// are not 16-byte aligned).  Row R of a level is node rank R / instances, instance R % instances.
+// are not 16-byte aligned).  Row R of a level is node rank R / instances, instance R % instances -- or, in a plan
+// with lane masks, what circ_row makes of the level's pairs (`X`, the last parameter of every kernel that decodes a row).
 // A slot reference is a slot number, or CIRC_FALSE (the trivial LWE (0, 0)), plus CIRC_NOT:
 // NOT w = enc_trivial(true) - w (fhe.jl:221-223,669-670), a -> -a mod r, b -> (Dr - b) mod r.
 
@@ -1861,11 +1887,13 @@ __global__ void __launch_bounds__(256)
 k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node0, uint64_t *__restrict__ a1,
               uint64_t *__restrict__ b1, uint64_t *__restrict__ a2, uint64_t *__restrict__ b2, uint32_t row0,
               uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, uint32_t *__restrict__ lutw = nullptr,
-              const uint8_t *__restrict__ data = nullptr) {
+              const uint8_t *__restrict__ data = nullptr, CircPairs X = {}) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1), R = row0 + lr;
-    const uint32_t k = node0 + R / instances, inst = R % instances;
+    uint32_t rank, inst;
+    circ_row(X, R, instances, rank, inst);
+    const uint32_t k = node0 + rank;
     auto read = [&](uint32_t i, uint64_t one) -> uint64_t {
         return circ_ref_word(wires, nodes.terms, i, instances, inst, e, n, r, one);
     };
@@ -1903,11 +1931,13 @@ k_circ_gather(const uint64_t *__restrict__ wires, CircNodes nodes, uint32_t node
 __global__ void __launch_bounds__(256)
 k_circ_xor3(uint64_t *__restrict__ res, const uint32_t *__restrict__ node_kind, const uint64_t *__restrict__ a1,
             const uint64_t *__restrict__ b1, const uint64_t *__restrict__ a2, const uint64_t *__restrict__ b2,
-            uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r) {
+            uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, uint64_t r, CircPairs X = {}) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= rows * (n + 1)) return;
     const uint32_t lr = t / (n + 1), e = t % (n + 1);
-    if ((node_kind[(row0 + lr) / instances] & 0xFFu) != 1) return;   // a sum node's rows only
+    uint32_t rank, inst;
+    circ_row(X, row0 + lr, instances, rank, inst);
+    if ((node_kind[rank] & 0xFFu) != 1) return;   // a sum node's rows only
     const uint64_t s = e < n ? a1[(size_t)lr * n + e] + a2[(size_t)lr * n + e] : b1[lr] + b2[lr];
     uint64_t *o = res + (size_t)lr * 3 * (n + 1) + e;
     o[2 * (size_t)(n + 1)] = (s - 2 * o[0]) & (r - 1);
@@ -1921,9 +1951,11 @@ __global__ void __launch_bounds__(256)
 k_circ_xor3_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__ node_kind,
                 const uint32_t *__restrict__ out_slot, uint64_t *__restrict__ wires, const uint64_t *__restrict__ a1,
                 const uint64_t *__restrict__ b1, const uint64_t *__restrict__ a2, const uint64_t *__restrict__ b2,
-                const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint64_t r) {
+                const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint64_t r,
+                CircPairs X = {}) {
     const uint32_t lr = blockIdx.x, R = row0 + lr;
-    const uint32_t rank = R / instances, inst = R % instances;   // (uniform over the workgroup)
+    uint32_t rank, inst;   // (uniform over the workgroup)
+    circ_row(X, R, instances, rank, inst);
     if ((node_kind[rank] & 0xFFu) != 1) return;   // a sum node's rows only
     const uint32_t slot = out_slot[3 * rank + 2];
     if (slot == CIRC_SLOT_NONE) return;
@@ -1940,12 +1972,13 @@ k_circ_xor3_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__
 // bootstrap output [rows][3][n + 1] -> the slots of the gate outputs something reads
 __global__ void __launch_bounds__(256)
 k_circ_scatter(const uint64_t *__restrict__ res, const uint32_t *__restrict__ out_slot, uint64_t *__restrict__ wires,
-               uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n) {
+               uint32_t row0, uint32_t rows, uint32_t instances, uint32_t n, CircPairs X = {}) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     const uint32_t w3 = 3 * (n + 1);
     if (t >= rows * w3) return;
     const uint32_t lr = t / w3, rem = t % w3, g = rem / (n + 1), e = rem % (n + 1), R = row0 + lr;
-    const uint32_t rank = R / instances, inst = R % instances;
+    uint32_t rank, inst;
+    circ_row(X, R, instances, rank, inst);
     const uint32_t slot = out_slot[3 * rank + g];
     if (slot == CIRC_SLOT_NONE) return;
     wires[((size_t)slot * instances + inst) * (n + 1) + e] = res[t];
@@ -1964,9 +1997,11 @@ k_circ_scatter(const uint64_t *__restrict__ res, const uint32_t *__restrict__ ou
 __global__ void __launch_bounds__(256)
 k_circ_scatter_raw(const ulonglong2 *__restrict__ res, const uint32_t *__restrict__ out_slot,
                    uint64_t *__restrict__ wires, const uint32_t *__restrict__ jobs, ulonglong2 *__restrict__ rawout,
-                   const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint32_t with_wires) {
+                   const CrtConst *__restrict__ CC, uint32_t row0, uint32_t instances, uint32_t n, uint32_t with_wires,
+                   CircPairs X = {}) {
     const uint32_t lr = blockIdx.x, R = row0 + lr;
-    const uint32_t rank = R / instances, inst = R % instances;   // (uniform over the workgroup)
+    uint32_t rank, inst;   // (uniform over the workgroup; both halves below read them)
+    circ_row(X, R, instances, rank, inst);
     const size_t stride = n + 1;
     if (with_wires && blockIdx.y == 0) {
         for (uint32_t g = 0; g < 3; g++) {
